@@ -5,12 +5,16 @@ factor, 10 Euler steps, 22.05 kHz, batch 64 synthetic 6-s utterances).
   python bench.py [--gpus N] [--steps K] [--warmup W]                      config 2 (headline; N > 1 = config 3's per-GPU shape)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+  python bench.py --full          config 2 plus every side measurement: serial schedule, roofline, text encoder, PCIe-inclusive rate,
+                                  CPU baseline and parity, fp32-MFMA step, hand-off counters, all-gather alone, compact config-4 / config-5 records
+  python bench.py --dump-outputs DIR   also write the last timed step's waveform and mel as DIR/waveform.npy, DIR/mel.npy (float32)
   python bench.py --config 4      ODE-step sweep {2,4,10,20,50} at batch 64: latency, mel-MSE vs n = 50 and vs the CPU oracle at the same n
   python bench.py --config 5      streaming feel_me.py loop: 128 mixed-length utterances, all 11 emojis + default, p50 / p99 latency
 
 One "step" (config 2) = CFM decode (n Euler steps of the U-Net estimator) + HiFi-GAN on one batch of B utterances per
 GPU (inputs resident in HBM, z given, weights resident), plus — for N > 1 — the single RCCL all-gather that
-collates the waveforms.  Rank 0 prints ONE JSON line.
+collates the waveforms.  Rank 0 prints ONE JSON line.  Without --full a run sets up, warms up, times the K steps and
+prints the headline fields only.
 """
 import argparse
 import json
@@ -418,6 +422,27 @@ def config5_record(model, voc, n_utt=32):
 # ---------------------------------------------------------------------------------------------------------------------
 # config 2 / 3 (default)
 # ---------------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirname, arrays):
+    """Write each {name: tensor} as DIR/<name>.npy in float32.  Arrays that together exceed DUMP_LIMIT_BYTES (N > 1: the collated
+    waveforms of the global batch) keep a fixed, seeded, sorted sample of their rows (dim 0), each in proportion to the limit."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if total > DUMP_LIMIT_BYTES:
+            n = t.shape[0]
+            rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:max(1, n * DUMP_LIMIT_BYTES // total)].sort().values
+            t = t[rows.to(t.device)]
+            log(f"[bench] dump {name}: {len(rows)} of {n} rows kept")
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+    log(f"[bench] outputs of the last timed step written to {dirname}: {', '.join(n + '.npy' for n in arrays)}")
+
+
 def close_models(*objs):
     """Destroy the native handles explicitly, while the HIP runtime (and a profiler wrapped around it) is still alive."""
     for o in objs:
@@ -437,15 +462,24 @@ def main():
     ap.add_argument("--frames", type=int, default=516, help="mel frames per utterance (516 = 5.99 s)")
     ap.add_argument("--ode-steps", type=int, default=10)
     ap.add_argument("--utterances", type=int, default=128, help="config 5: utterances in the streaming loop")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every side measurement and check of the line "
+                    "(serial schedule, roofline, text encoder, PCIe-inclusive rate, CPU baseline and parity, fp32-MFMA step, hand-off counters, "
+                    "all-gather alone, compact config-4 / config-5 / arithmetic records)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (collated waveform, this rank's mel) "
+                    "as DIR/<name>.npy in float32, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check")
     ap.add_argument("--no-pipeline", action="store_true", help="run CFM and HiFi-GAN of each batch back to back on one stream")
     ap.add_argument("--pipelines", type=int, default=2, help="batch pipelines in flight (each its own engine pair and two streams); "
                     "consecutive batches go to them in turn")
     ap.add_argument("--cpu-sample", type=int, default=8)
-    ap.add_argument("--no-extras", action="store_true", help="skip the compact config-4 / config-5 records of the default line")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the compact config-4 / config-5 records")
     ap.add_argument("--plain", action="store_true", help="profiling aid: warm-up + K serial steps and nothing else (no roofline / CPU / PCIe legs), "
                     "so that a rocprofv3 --pmc pass sees exactly (W + K) x launches_per_step conv launches")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.plain or args.config in (4, 5)):
+        ap.error("--dump-outputs applies to the timed steps of configs 2 / 3")
 
     from emojivoice_amd import dist as D
     from emojivoice_amd.pipeline import PipelineGroup
@@ -525,21 +559,23 @@ def main():
         log(f"[bench] warmup step {time.perf_counter() - tw:.3f} s")
     D.barrier()
     torch.cuda.synchronize()
-    sk_engines = [model.engine] + [m.engine for m in extra_models[0::2]]   # the decoders' handles: their balanced launches hand partial tiles over
-    sk0 = [e.sk_stats() for e in sk_engines]
-    tk0 = [e.sk_taken() for e in sk_engines]
+    if args.full:
+        sk_engines = [model.engine] + [m.engine for m in extra_models[0::2]]   # the decoders' handles: their balanced launches hand partial tiles over
+        sk0 = [e.sk_stats() for e in sk_engines]
+        tk0 = [e.sk_taken() for e in sk_engines]
     t0 = time.perf_counter()
     for _ in range(args.steps):
         full, wav, mel = step()
     torch.cuda.synchronize()
     D.barrier()
     dt = time.perf_counter() - t0
-    sk1 = [e.sk_stats() for e in sk_engines]
-    tk1 = [e.sk_taken() for e in sk_engines]
-    handoffs = {"balanced_launches": int(sum(b[0] - a[0] for a, b in zip(sk0, sk1))), "waits_ran_out": int(sum(b[2] - a[2] for a, b in zip(sk0, sk1))),
-                "shares_taken_over": int(sum(b - a for a, b in zip(tk0, tk1))),
-                "note": "over the timed steps, all pipelines: launches of the balanced persistent builds; hand-off waits that ran out (a contributor that had started did not "
-                        "deliver within the spin limit: the owner recomputed its share); shares an owner took over at once because the contributor had not started (not resident)"}
+    if args.full:
+        sk1 = [e.sk_stats() for e in sk_engines]
+        tk1 = [e.sk_taken() for e in sk_engines]
+        handoffs = {"balanced_launches": int(sum(b[0] - a[0] for a, b in zip(sk0, sk1))), "waits_ran_out": int(sum(b[2] - a[2] for a, b in zip(sk0, sk1))),
+                    "shares_taken_over": int(sum(b - a for a, b in zip(tk0, tk1))),
+                    "note": "over the timed steps, all pipelines: launches of the balanced persistent builds; hand-off waits that ran out (a contributor that had started did not "
+                            "deliver within the spin limit: the owner recomputed its share); shares an owner took over at once because the contributor had not started (not resident)"}
     dt_rank = dt
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     per_rank_ms = [round(dt / args.steps * 1e3, 2)]
@@ -551,16 +587,17 @@ def main():
         trs[rank] = dt_rank
         torch.distributed.all_reduce(trs)
         per_rank_ms = [round(float(v) / args.steps * 1e3, 2) for v in trs.tolist()]
-        # the collective alone: 5 gathers of this rank's last waveform block, nothing else in flight
-        torch.cuda.synchronize()
-        D.barrier()
-        tg = time.perf_counter()
-        for _ in range(5):
-            D.all_gather_waveforms(wav, B * world)
-        torch.cuda.synchronize()
-        tga = torch.tensor([(time.perf_counter() - tg) / 5 * 1e3], dtype=torch.float64, device=device)
-        torch.distributed.all_reduce(tga, op=torch.distributed.ReduceOp.MAX)
-        allgather_ms = round(float(tga.item()), 3)
+        if args.full:
+            # the collective alone: 5 gathers of this rank's last waveform block, nothing else in flight
+            torch.cuda.synchronize()
+            D.barrier()
+            tg = time.perf_counter()
+            for _ in range(5):
+                D.all_gather_waveforms(wav, B * world)
+            torch.cuda.synchronize()
+            tga = torch.tensor([(time.perf_counter() - tg) / 5 * 1e3], dtype=torch.float64, device=device)
+            torch.distributed.all_reduce(tga, op=torch.distributed.ReduceOp.MAX)
+            allgather_ms = round(float(tga.item()), 3)
     dt = float(tmax.item())
     log(f"[bench] timed {args.steps} steps in {dt:.3f} s")
     audio_s_total = args.steps * B * world * T * HOP / SR
@@ -576,8 +613,31 @@ def main():
         assert tuple(full.shape) == (B * world, 1, T * HOP), tuple(full.shape)
         assert torch.equal(full[lo:hi], wav), "this rank's rows are not at their global offset in the gathered block"
     gathered_shape = list(full.shape)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"waveform": full, "mel": mel})
 
-    if rank == 0:
+    per_gpu = value / world
+    out = {
+        "metric": "audio_seconds_per_second", "value": round(value, 2), "unit": "audio_s/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
+        "config": {"workload": f"config2: batch {B} x {T}-frame (5.99 s) utterances per GPU, {n_ode} Euler steps + HiFi-GAN V1, 22.05 kHz",
+                   "global_batch": B * world, "frames": T, "ode_steps": n_ode, "parallelism": f"dp{world}",
+                   "collective": "all_gather(waveforms)" if world > 1 else "none",
+                   "arithmetic": "f32 tensors and f32 accumulation throughout; EV_SPLIT=0 -> every product on the f32 MFMA" if ARITH == 0 else
+                                 ("f32 tensors and f32 accumulation throughout; deep layers: operand = two fp16 pieces of the operand times a power-of-two block "
+                                  "scale (22-23 significand bits), product = h0g0 + h0g1 + h1g0; one conv layer vs fp64 (tools/arith_accuracy.py): rms 3.4e-7 of "
+                                  "the output scale against 5.4e-7 for the f32 MFMA; with --full, cpu_baseline.parity_* are measured on this run's timed output") if ARITH == 16 else
+                                 "f32 tensors and f32 accumulation throughout; deep layers: operand = exact sum of 3 bf16 pieces, product = the piece products of "
+                                 "weight <= 2 (6) / <= 1 (3); profiles/r03_bf16_split_probe.txt; with --full, cpu_baseline.parity_* are measured on this run's timed output",
+                   "batch_pipeline": "off" if pipe is None else f"cfm(i+1) || hifigan(i) on two streams, {len(pipes)} pipeline(s) in flight",
+                   "memory": "off" if pipe is None else f"{len(pipes)} engine pairs resident per GPU, each its own weights (about 0.45 GB: fp32 fragments + bf16 and fp16 piece planes in both MFMA layouts) + workspace "
+                             f"({round(model.engine.workspace_bytes(B, T, 0) / 1e9 + voc.engine.workspace_bytes(B, 0, T) / 1e9, 1)} GB at this shape)"},
+        "ranks_seen": ranks_seen, "gathered_shape": gathered_shape, "per_rank_ms_per_step": per_rank_ms,
+        "per_gpu_audio_s_per_s": round(per_gpu, 2), "rtf": round(1.0 / per_gpu, 6), "x_realtime_per_gpu": round(per_gpu, 1),
+    }
+
+    if rank == 0 and args.full:
         # ---- the same workload on the serial schedule (one stream, stages back to back): what the roofline pass below runs on
         torch.cuda.synchronize()
         ts = time.perf_counter()
@@ -616,7 +676,6 @@ def main():
                     break
             except Exception:
                 pass
-        per_gpu = value / world
         # The dominant family = the launches on the bf16 matrix pipe (every fp32 multiply-add as SPLIT_PRODUCTS exact bf16 products,
         # fp32 accumulation): algorithmic FLOP / time against dense-bf16-peak / SPLIT_PRODUCTS, which is the same fraction as
         # executed MFMA FLOP against the bf16 peak.  The launches still on v_mfma_f32_32x32x2_f32 are priced against the fp32 peak.
@@ -736,30 +795,15 @@ def main():
                 c5 = config5_record(model, voc)
             except Exception as ex:  # noqa: BLE001 - the headline line must not die with a side record
                 log(f"[bench] config-4 / config-5 records skipped: {type(ex).__name__}: {ex}")
-        out = {
-            "metric": "audio_seconds_per_second", "value": round(value, 2), "unit": "audio_s/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
-            "config": {"workload": f"config2: batch {B} x {T}-frame (5.99 s) utterances per GPU, {n_ode} Euler steps + HiFi-GAN V1, 22.05 kHz",
-                       "global_batch": B * world, "frames": T, "ode_steps": n_ode, "parallelism": f"dp{world}",
-                       "collective": "all_gather(waveforms)" if world > 1 else "none",
-                       "arithmetic": "f32 tensors and f32 accumulation throughout; EV_SPLIT=0 -> every product on the f32 MFMA" if ARITH == 0 else
-                                     ("f32 tensors and f32 accumulation throughout; deep layers: operand = two fp16 pieces of the operand times a power-of-two block "
-                                      "scale (22-23 significand bits), product = h0g0 + h0g1 + h1g0; one conv layer vs fp64 (tools/arith_accuracy.py): rms 3.4e-7 of "
-                                      "the output scale against 5.4e-7 for the f32 MFMA; parity_* below are measured on this run's timed output") if ARITH == 16 else
-                                     "f32 tensors and f32 accumulation throughout; deep layers: operand = exact sum of 3 bf16 pieces, product = the piece products of "
-                                     "weight <= 2 (6) / <= 1 (3); profiles/r03_bf16_split_probe.txt; parity_* below are measured on this run's timed output",
-                       "batch_pipeline": "off" if pipe is None else f"cfm(i+1) || hifigan(i) on two streams, {len(pipes)} pipeline(s) in flight",
-                       "memory": "off" if pipe is None else f"{len(pipes)} engine pairs resident per GPU, each its own weights (about 0.45 GB: fp32 fragments + bf16 and fp16 piece planes in both MFMA layouts) + workspace "
-                                 f"({round(model.engine.workspace_bytes(B, T, 0) / 1e9 + voc.engine.workspace_bytes(B, 0, T) / 1e9, 1)} GB at this shape)"},
-            "ranks_seen": ranks_seen, "gathered_shape": gathered_shape, "per_rank_ms_per_step": per_rank_ms, "allgather_ms": allgather_ms,
-            "per_gpu_audio_s_per_s": round(per_gpu, 2), "rtf": round(1.0 / per_gpu, 6), "x_realtime_per_gpu": round(per_gpu, 1),
+        out.update({
+            "allgather_ms": allgather_ms,
             "serial_ms_per_step": round(serial_ms, 2), "batch_latency_ms": round(batch_latency_ms, 2), "stage_ms": stage_ms,
             "text_encoder": text_enc,
             "value_fp32_mfma": fp32, "balanced_handoffs": handoffs,
             "roofline": roofline, "path_roofline": path_roof, "cpu_baseline": cpu, "pcie_inclusive": pcie,
             "config4": c4, "config5": c5, "arithmetic_settings": arith,
-        }
+        })
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         D.barrier()

@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("EV_LIB_PATH") or os.path.join(_HERE, "lib", "libemoji
 CSRC = os.path.join(_HERE, "csrc")
 
 EXPORTS = [
-    "ev_abi_version", "ev_create", "ev_destroy", "ev_last_error", "ev_load_estimator", "ev_load_vocoder", "ev_load_text_encoder", "ev_text_encoder",
+    "ev_abi_version", "ev_create", "ev_destroy", "ev_last_error", "ev_load_estimator", "ev_load_vocoder", "ev_load_vocoder_cfg", "ev_load_text_encoder", "ev_text_encoder",
     "ev_text_encoder_status", "ev_stft_magnitude", "ev_denoise", "ev_align", "ev_dbg_conv_bench",
     "ev_workspace_bytes", "ev_cfm_decode", "ev_estimator", "ev_hifigan", "ev_profile_enable", "ev_profile_read", "ev_profile_read_split", "ev_dbg_last_cfg", "ev_set_arithmetic", "ev_get_arithmetic",
     "ev_op_conv1d", "ev_op_groupnorm_mish", "ev_op_layernorm", "ev_op_split_pieces", "ev_op_attention", "ev_op_ln_mlp", "ev_set_mrf_streams_max",
@@ -38,6 +38,41 @@ class ev_tensor_index(C.Structure):
 class ev_model_dims(C.Structure):
     _fields_ = [("n_feats", C.c_int32), ("spk_emb_dim", C.c_int32), ("channels", C.c_int32), ("heads", C.c_int32),
                 ("head_dim", C.c_int32)]
+
+
+class ev_vocoder_config(C.Structure):
+    _fields_ = [("resblock", C.c_int32), ("num_levels", C.c_int32), ("upsample_rates", C.c_int32 * 4), ("upsample_kernel_sizes", C.c_int32 * 4),
+                ("resblock_kernel_sizes", C.c_int32 * 3), ("resblock_dilations", (C.c_int32 * 3) * 3)]
+
+
+def vocoder_config(h) -> ev_vocoder_config:
+    """The C form of a HiFi-GAN config dict (emojivoice_amd.hifigan.check_config has vetted it)."""
+    c = ev_vocoder_config()
+    c.resblock = 1 if str(h["resblock"]) == "1" else 2
+    c.num_levels = len(h["upsample_rates"])
+    for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
+        c.upsample_rates[i], c.upsample_kernel_sizes[i] = int(u), int(k)
+    for j, (k, ds) in enumerate(zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"])):
+        c.resblock_kernel_sizes[j] = int(k)
+        for m, d in enumerate(ds):
+            c.resblock_dilations[j][m] = int(d)
+    return c
+
+
+def vocoder_frame_bytes(h) -> int:
+    """Bytes per mel frame of the widest tensor ev_hifigan plans for config h, padding excluded, and the pad frames a side
+    of the mel level (ev_engine.hip: load_vocoder sets P0, plan_voc the level geometry).  V1: (32768, 4)."""
+    rates, rb1 = list(h["upsample_rates"]), str(h["resblock"]) == "1"
+    widest, prod, p0 = 0, 1, 4
+    for i, u in enumerate(rates):
+        prod *= u
+        widest = max(widest, prod * (h["upsample_initial_channel"] // 2 ** (i + 1)) * 4)
+        halo = 3 if i == len(rates) - 1 else 0
+        for k, ds in zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"]):
+            for d in (ds if rb1 else ds[:2]):
+                halo = max(halo, (k - 1) * d // 2)
+        p0 = max(p0, -(-halo // prod))
+    return widest, p0
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -77,6 +112,7 @@ def load_library() -> C.CDLL:
     lib.ev_last_error.restype = C.c_char_p
     for f in (lib.ev_load_estimator, lib.ev_load_vocoder, lib.ev_load_text_encoder):
         f.argtypes = [vp, vp, C.POINTER(ev_tensor_index), u64]
+    lib.ev_load_vocoder_cfg.argtypes = [vp, vp, C.POINTER(ev_tensor_index), u64, C.POINTER(ev_vocoder_config)]
     lib.ev_set_mrf_streams_max.argtypes = [vp, i32]
     lib.ev_set_mrf_streams_max.restype = i32
     lib.ev_workspace_bytes.argtypes = [vp, i32, i32, i32]
@@ -146,6 +182,7 @@ class Engine:
         else:
             self.mrf_streams_max = 16384
         self.pipeline_owner = None                       # {holders, saved limit} while BatchPipelines hold the vocoder's fan-out off (pipeline.py)
+        self.voc_frame_bytes, self.voc_pad0 = 256 * 128, 4   # widest vocoder tensor per mel frame, pad frames a side (V1 until load_vocoder says otherwise)
 
     def set_mrf_streams_max(self, max_frames: int) -> None:
         """Largest ``hifigan`` call (B*T mel frames) that runs its three ResBlock1 chains on three streams (0 = never)."""
@@ -169,7 +206,7 @@ class Engine:
             raise EvLibraryError(f"{what} failed: {self.lib.ev_last_error(self.h).decode()}")
 
     # ---- weights -----------------------------------------------------------
-    def _load(self, fn, tensors: Dict[str, torch.Tensor], what: str):
+    def _load(self, fn, tensors: Dict[str, torch.Tensor], what: str, *extra):
         names = list(tensors.keys())
         arrs = [np.ascontiguousarray(tensors[k].detach().to("cpu", torch.float32).numpy()).reshape(-1) for k in names]
         blob = np.concatenate(arrs) if arrs else np.zeros(1, np.float32)
@@ -186,15 +223,22 @@ class Engine:
             for d, s in enumerate(shp):
                 idx[i].shape[d] = s
             off += arrs[i].size
-        self._check(fn(self.h, blob.ctypes.data_as(C.c_void_p), idx, len(names)), what)
+        self._check(fn(self.h, blob.ctypes.data_as(C.c_void_p), idx, len(names), *extra), what)
 
     def load_estimator(self, tensors: Dict[str, torch.Tensor]):
         """``tensors``: reference ``decoder.estimator.*`` entries with that prefix stripped, plus the derived
         ``*.ff.net.0.alpha_exp`` / ``*.ff.net.0.beta_inv`` (see matcha_tts.estimator_tensors)."""
         self._load(self.lib.ev_load_estimator, tensors, "ev_load_estimator")
 
-    def load_vocoder(self, tensors: Dict[str, torch.Tensor]):
-        self._load(self.lib.ev_load_vocoder, tensors, "ev_load_vocoder")
+    def load_vocoder(self, tensors: Dict[str, torch.Tensor], h=None):
+        """Generator weights (folded weight norm).  ``h``: a HiFi-GAN config inside the supported envelope (ev_load_vocoder_cfg); None: V1."""
+        if h is None:
+            self._load(self.lib.ev_load_vocoder, tensors, "ev_load_vocoder")
+            self.voc_frame_bytes, self.voc_pad0 = 256 * 128, 4
+            return
+        cfg = vocoder_config(h)
+        self._load(self.lib.ev_load_vocoder_cfg, tensors, "ev_load_vocoder_cfg", C.byref(cfg))
+        self.voc_frame_bytes, self.voc_pad0 = vocoder_frame_bytes(h)
 
     def align(self, w_ceil, mu_x, x_lengths, y_lengths, Tp: int, want_attn: bool = True):
         """generate_path + mu_y = attn^T mu_x (utils/model.py:29-41, matcha_tts.py:131-135).  Returns (mu_y (B,80,Tp), attn (B,1,Tx,Tp))."""
@@ -324,8 +368,8 @@ class Engine:
         assert F == 80
         wav = torch.empty((B, 1, T * 256), dtype=torch.float32, device=mel.device)
         # the kernels address tensors with 32-bit byte offsets (< 4 GiB each): the widest vocoder tensor holds
-        # 256 * (T + 8) frames x 128 B per utterance (levels 2-4), so very large batches are processed in row chunks
-        per_utt = 256 * (T + 8) * 128
+        # (T + 2 P0) x voc_frame_bytes per utterance (V1: 256 * (T + 8) frames x 128 B, levels 2-4), so very large batches are processed in row chunks
+        per_utt = (T + 2 * self.voc_pad0) * self.voc_frame_bytes
         bmax = max(1, int((2**32 - 2**20) // per_utt))
         for b0 in range(0, B, bmax):
             b1 = min(B, b0 + bmax)

@@ -50,21 +50,36 @@ def validate_args(args):
 def load_models(args, device):
     from . import weights as W
     from .denoiser import Denoiser
-    from .hifigan import AttrDict, Generator, v1
+    from .hifigan import AttrDict, Generator
     from .matcha_tts import MatchaTTS
 
+    h = AttrDict(vocoder_config(args.vocoder_config))
     if args.synthetic:
         model = MatchaTTS(W.synthetic_matcha_state(), device=device)
-        voc_sd = W.synthetic_hifigan_state()
+        voc_sd = W.synthetic_hifigan_state(h)
     else:
         model = MatchaTTS.load_from_checkpoint(args.checkpoint_path, map_location=device)
         voc_sd = torch.load(args.vocoder_path, map_location="cpu")["generator"]
-    vocoder = Generator(AttrDict(v1)).to(device)
+    vocoder = Generator(h).to(device)
     vocoder.load_state_dict(voc_sd)
     vocoder.eval()
     vocoder.remove_weight_norm()
     denoiser = Denoiser(vocoder, mode="zeros") if args.denoiser_strength > 0 else None
     return model.eval(), vocoder, denoiser
+
+
+def vocoder_config(name: str) -> dict:
+    """--vocoder_config: v1 / v2 / v3, or the path of an upstream HiFi-GAN config.json."""
+    import json
+
+    from . import hifigan
+
+    if name in ("v1", "v2", "v3"):
+        return dict(getattr(hifigan, name))
+    with open(name, encoding="utf-8") as f:
+        h = json.load(f)
+    hifigan.check_config(h)
+    return h
 
 
 @torch.inference_mode()
@@ -105,6 +120,8 @@ def cli(argv=None):
     p.add_argument("--checkpoint_path", type=str, default=None)
     p.add_argument("--vocoder_path", type=str, default=None, help="HiFi-GAN generator checkpoint (dict with 'generator')")
     p.add_argument("--synthetic", action="store_true", help="random-init weights (no checkpoint is available offline)")
+    p.add_argument("--vocoder_config", type=str, default="v1", help="HiFi-GAN generator config: v1, v2, v3 or the path of an upstream "
+                   "config.json (with --synthetic: random weights of that config)")
     p.add_argument("--ids", type=str, default=None, help="phoneme ids of one utterance, space separated")
     p.add_argument("--phonemes", type=str, default=None, help="one pre-phonemised (IPA) utterance, e.g. the output of english_cleaners2; "
                    "mapped through the 198-symbol table and interspersed with blanks like the reference front end")

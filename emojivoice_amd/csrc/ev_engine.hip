@@ -47,6 +47,7 @@ struct ConvLayer {
     int kstack_mt = 0, kstack_tap = 0;      // sparse_taps of the stacked [k-tap conv | 1x1 conv] kind: 32-channel tiles >= kstack_mt carry only tap kstack_tap
     int ntaps = 0, off[EV_MAX_TAPS] = {0};
     int halo_lo = 0, halo_hi = 0;
+    bool wide = false;        // halo_lo + halo_hi may exceed EV_HALO: for resblock2_h16_kernel only (launch_conv refuses it)
     int Cin = 0, Cout = 0, Mpad = 0, Kpad = 0;
     double macs_per_row = 0;  // algorithmic MACs per output view-row (reference arithmetic, no padding)
 };
@@ -91,9 +92,16 @@ struct EstimatorW {
 
 struct VocoderW {
     bool loaded = false;
+    int rb = 1;                     // ResBlock1 / ResBlock2 (models.py:160)
+    int nl = 4;                     // upsampling levels
+    int rates[4] = {8, 8, 2, 2};
+    int P0 = 4;                     // pad rows a side of the mel level: every level's P_l = P0 x (rates so far) covers its widest conv halo
     ConvLayer pre, post, ups[4];
-    ConvLayer c1[12][3], c2[12][3];
-    int ch[5];  // channels per level: 512, 256, 128, 64, 32
+    ConvLayer c1[12][3], c2[12][3]; // ResBlock1: convs1 / convs2; ResBlock2: c1[b][0..1] = convs.0 / convs.1 (whole, for resblock2_h16_kernel)
+    // ResBlock2 convs whose two sides together exceed EV_HALO (k = 7, d = 12): the taps left of and at the centre (lo) and right of it (hi)
+    // as two layers of their own, for the conv launches (ntaps = 0: the conv is not split)
+    ConvLayer lo[12][2], hi[12][2];
+    int ch[5];  // channels per level (V1: 512, 256, 128, 64, 32)
     float* post_w = nullptr; float post_b = 0.f; int post_k = 0;   // conv_post as [K][C] for conv_post_kernel
 };
 
@@ -232,7 +240,7 @@ int finish_layer(ev_handle* h, ConvLayer& L, const std::vector<float>& Wh, const
     int lo = 0, hi = 0;
     for (int i = 0; i < L.ntaps; ++i) { if (-L.off[i] > lo) lo = -L.off[i]; if (L.off[i] > hi) hi = L.off[i]; }
     L.halo_lo = lo; L.halo_hi = hi;
-    if (lo + hi > EV_HALO) return fail(h, "conv halo %d exceeds EV_HALO", lo + hi);
+    if (lo + hi > EV_HALO && !L.wide) return fail(h, "conv halo %d exceeds EV_HALO", lo + hi);
     {   // re-order [tap][Mpad][Kpad] into MFMA-fragment order [tap][Mpad/32][Kpad/8][lane][4] (see conv_gemm_kernel)
         std::vector<float> Wf(Wh.size());
         const int MT32 = L.Mpad / 32, KG8 = L.Kpad / 8;
@@ -374,18 +382,20 @@ int finish_layer(ev_handle* h, ConvLayer& L, const std::vector<float>& Wh, const
     return 0;
 }
 
-// Conv1d weight (Cout, Cin, K), stride 1, "same" padding (K*d - d)/2, dilation d
-int pack_conv(ev_handle* h, ConvLayer& L, const HostTensor& w, const HostTensor* b, int dilation) {
+// Conv1d weight (Cout, Cin, K), stride 1, "same" padding (K*d - d)/2, dilation d; taps k0 .. k1 - 1 of it (default: all)
+int pack_conv(ev_handle* h, ConvLayer& L, const HostTensor& w, const HostTensor* b, int dilation, int k0 = 0, int k1 = -1) {
     const int Cout = (int)w.shape[0], Cin = (int)w.shape[1], K = w.ndim == 3 ? (int)w.shape[2] : 1;
     if (K > EV_MAX_TAPS) return fail(h, "kernel size %d > %d", K, EV_MAX_TAPS);
-    L.Cin = Cin; L.Cout = Cout; L.ntaps = K; L.Mpad = round_up(Cout, 128); L.Kpad = round_up(Cin, EV_BK);
+    if (k1 < 0) k1 = K;
+    const int nk = k1 - k0;
+    L.Cin = Cin; L.Cout = Cout; L.ntaps = nk; L.Mpad = round_up(Cout, 128); L.Kpad = round_up(Cin, EV_BK);
     const int pad = (K * dilation - dilation) / 2;
-    for (int k = 0; k < K; ++k) L.off[k] = k * dilation - pad;
-    std::vector<float> Wh((size_t)K * L.Mpad * L.Kpad, 0.f);
+    for (int k = 0; k < nk; ++k) L.off[k] = (k0 + k) * dilation - pad;
+    std::vector<float> Wh((size_t)nk * L.Mpad * L.Kpad, 0.f);
     for (int co = 0; co < Cout; ++co)
         for (int ci = 0; ci < Cin; ++ci)
-            for (int k = 0; k < K; ++k) Wh[((size_t)k * L.Mpad + co) * L.Kpad + ci] = w.p[((size_t)co * Cin + ci) * K + k];
-    L.macs_per_row = (double)Cout * Cin * K;
+            for (int k = 0; k < nk; ++k) Wh[((size_t)k * L.Mpad + co) * L.Kpad + ci] = w.p[((size_t)co * Cin + ci) * K + k0 + k];
+    L.macs_per_row = (double)Cout * Cin * nk;
     std::vector<float> bh;
     if (b) bh.assign(b->p, b->p + Cout);
     return finish_layer(h, L, Wh, b ? &bh : nullptr);
@@ -776,6 +786,7 @@ int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float
     ConvParams p;
     memset(&p, 0, sizeof p);
     h->gn_stats_tiles = 0;
+    if (L.halo_lo + L.halo_hi > EV_HALO) return fail(h, "launch_conv: conv halo %d exceeds EV_HALO", L.halo_lo + L.halo_hi);
     p.X = X; p.ldx = ldx; p.Cin = L.Cin; p.isplit_log2 = e.isplit_log2; p.isstride = e.isstride;
     p.W = L.W; p.Wx = L.Wx; p.Wh = L.Wh; p.Wq = L.Wq; p.wh_scale = L.wh_scale; p.Mpad = L.Mpad; p.Kpad = L.Kpad; p.bias = L.bias;
     p.Y = Y; p.ldy = ldy; p.Cout = L.Cout; p.osplit_log2 = e.osplit_log2; p.osstride = e.osstride; p.mmul = e.mmul;
@@ -1215,6 +1226,72 @@ int launch_chain(ev_handle* h, const ConvLayer* L1, const ConvLayer* L2, const f
         h->prof_flops += 2.0 * macs * valid_rows;
         h->prof_launches += 1;
         h->prof_recs.push_back({1, C, C, L1[0].ntaps, g.nrows, 180 + L2[0].ntaps, lean, 2.0 * macs * valid_rows});
+    }
+    return 0;
+}
+
+// A whole ResBlock2 — two dilated convs with their residual adds — in one launch (resblock2_h16_kernel), arithmetic setting 16.  rb2_ok() is the
+// gate; the caller falls back to one conv launch per step.  A tile of NT frames (C = 32: 256, 64: 128, 128: 64) stores NT - 2 halo of them, halo =
+// the two convs' halos summed, so the gate takes a block when its stored share is at least `EV_RB2_MINKEEP` / 8 of the tile (default 4: half).
+// The threshold is a measurement (tools/vocoder_configs_bench.py).
+inline int rb2_halo(const ConvLayer* L) { return L[0].halo_lo + L[1].halo_lo; }
+inline bool rb2_ok(const ev_handle* h, const ConvLayer* L, int C) {
+    static const bool off = getenv("EV_NO_CHAIN") != nullptr;
+    static const int keep8 = getenv("EV_RB2_MINKEEP") ? atoi(getenv("EV_RB2_MINKEEP")) : 4;
+    if (off || !h->use_chain || h->split_terms != 16 || (C != 32 && C != 64 && C != 128)) return false;
+    for (int m = 0; m < 2; ++m) {
+        const ConvLayer& a = L[m];
+        if (!a.Wh || !a.bias || a.sparse_taps || a.Kpad != C || a.Mpad != L[0].Mpad || a.halo_lo != a.halo_hi || a.ntaps != L[0].ntaps || a.ntaps > 64) return false;
+    }
+    const int NT = C == 32 ? 256 : C == 64 ? 128 : 64;
+    return 8 * (NT - 2 * rb2_halo(L)) >= keep8 * NT && NT - 2 * rb2_halo(L) > 0;
+}
+int launch_rb2(ev_handle* h, const ConvLayer* L, const float* X, float* Y, int C, const Geom& g, const Epi& e) {
+    Rb2Params cp;
+    memset(&cp, 0, sizeof cp);
+    ConvParams& p = cp.c2;
+    p.X = X; p.ldx = C; p.Cin = C; p.isplit_log2 = 31;
+    p.Mpad = L[1].Mpad; p.Kpad = L[1].Kpad;
+    p.Y = Y; p.ldy = C; p.Cout = C; p.osplit_log2 = 31; p.mmul = 1;
+    p.nrows = g.nrows; p.S = g.S; p.P = g.P; p.T = g.T;
+    p.pro_lrelu = 1; p.pro_slope = 0.1f;
+    p.scale = 1.f; p.R = nullptr; p.ldr = C; p.accum = e.accum; p.div3 = e.div3; p.act2_lrelu = e.act2_lrelu; p.act2_slope = e.act2_slope;
+    p.rmax = nullptr; p.yold = e.yold; p.ymax_mul = 1; h->amax_emitted = false;
+    if (e.ymax && (!e.accum || e.yold) && h->use_amax) { p.ymax = e.ymax; h->amax_emitted = true; }
+    if ((double)g.nrows * C * 4.0 >= 4294967296.0) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
+    int hb = 0;
+    for (int m = 0; m < 2; ++m) {
+        cp.Wh[m] = L[m].Wh; cp.w_scale[m] = L[m].wh_scale; cp.b[m] = L[m].bias; cp.tl[m] = L[m].taplist[0];
+        hb = std::max(hb, L[m].halo_lo);
+    }
+    cp.ntaps = L[0].ntaps; cp.hb = hb; cp.halo = rb2_halo(L);
+    const int NT = C == 32 ? 256 : C == 64 ? 128 : 64, RSB = 4 * C + 16;
+    cp.out_rows = NT - 2 * cp.halo; p.mtiles = 1; p.ntiles = (g.nrows + cp.out_rows - 1) / cp.out_rows;
+    if (cp.out_rows <= 0) return fail(h, "launch_rb2: halo %d leaves no row of a %d-frame tile", cp.halo, NT);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (h->prof) {
+        if (h->ev_used + 2 > h->ev_pool.size()) {
+            for (int i = 0; i < 64; ++i) { hipEvent_t ev; HIPCHK(h, hipEventCreate(&ev)); h->ev_pool.push_back(ev); }
+        }
+        e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
+        HIPCHK(h, hipEventRecord(e0, h->stream));
+    }
+    const int lean = (e.accum || e.div3 || e.act2_lrelu) ? 3 : 1;
+    const size_t smem = std::max((size_t)(NT + 2 * hb) * RSB + 64, (size_t)4 * 32 * 36 * sizeof(float));
+    const dim3 grid(p.ntiles);
+#define EV_RB2(WM, WN) do { \
+        if (lean == 1) { ensure_dyn_smem<resblock2_h16_kernel<WM, WN, 1>>(smem, h->device); hipLaunchKernelGGL((resblock2_h16_kernel<WM, WN, 1>), grid, dim3(256), smem, h->stream, cp); } \
+        else { ensure_dyn_smem<resblock2_h16_kernel<WM, WN, 3>>(smem, h->device); hipLaunchKernelGGL((resblock2_h16_kernel<WM, WN, 3>), grid, dim3(256), smem, h->stream, cp); } } while (0)
+    if (C == 32) EV_RB2(1, 4); else if (C == 64) EV_RB2(2, 2); else EV_RB2(4, 1);
+#undef EV_RB2
+    HIPCHK(h, hipGetLastError());
+    h->last_cfg = 200 + L[0].ntaps;
+    if (h->prof) {
+        HIPCHK(h, hipEventRecord(e1, h->stream));
+        const double valid_rows = (double)(g.nrows / g.S) * g.T, macs = L[0].macs_per_row + L[1].macs_per_row;
+        h->prof_flops += 2.0 * macs * valid_rows;
+        h->prof_launches += 1;
+        h->prof_recs.push_back({1, C, C, L[0].ntaps, g.nrows, 200 + L[0].ntaps, lean, 2.0 * macs * valid_rows});
     }
     return 0;
 }
@@ -1667,21 +1744,21 @@ void plan_est(Bump& b, int B, int Tp, int in_ch, int nsteps, EstBufs& e) {
 }
 
 struct VocBufs {
-    Geom g[5];
-    float *M0, *C0;
-    float *U[5], *XS[5], *T1[5], *Pa[5], *Pb[5];
-    float *T1x[2][5], *Pax[2][5], *Pbx[2][5];   // scratch of the second and third ResBlock1 chain (three-stream MRF; null otherwise)
+    Geom g[5] = {};
+    float *M0 = nullptr, *C0 = nullptr;          // (levels past the config's last stay null: a stale level index faults at address 0, not at garbage)
+    float *U[5] = {}, *XS[5] = {}, *T1[5] = {}, *Pa[5] = {}, *Pb[5] = {};
+    float *T1x[2][5] = {}, *Pax[2][5] = {}, *Pbx[2][5] = {};   // scratch of the second and third ResBlock1 chain (three-stream MRF; null otherwise)
     struct { float* p; int C, l; unsigned* amax[2]; int amax_n; } zl[64]; int nz = 0;   // every tensor of the plan (for zero_pads_kernel) and its two sets of amax slots
     unsigned* slots = nullptr; size_t slot_words = 0;    // one block behind the tensors: per tensor 2 x ((rows >> 7) + 2) words, zeroed by every ev_hifigan call
     // slots of a tensor of this plan (null: not one of them)
     int index_of(const float* q) const { for (int k = 0; k < nz; ++k) if (zl[k].p == q) return k; return -1; }
 };
 
-void plan_voc(Bump& b, int B, int T, const int* ch, VocBufs& v, bool mrf_streams = false) {
-    const int rates[4] = {8, 8, 2, 2};
-    int Tl = T, Pl = 4;
+// levels 0 .. nl (0 = mel / conv_pre); level l's frames are rates[l - 1] view rows of level l - 1, so its pad rows P_l are P0 times the rates so far
+void plan_voc(Bump& b, int B, int T, const int* ch, const int* rates, int nl, int P0, VocBufs& v, bool mrf_streams = false) {
+    int Tl = T, Pl = P0;
     v.g[0] = {B * (Tl + 2 * Pl), Tl + 2 * Pl, Pl, Tl};
-    for (int l = 1; l <= 4; ++l) {
+    for (int l = 1; l <= nl; ++l) {
         Tl *= rates[l - 1]; Pl *= rates[l - 1];
         v.g[l] = {B * (Tl + 2 * Pl), Tl + 2 * Pl, Pl, Tl};
     }
@@ -1689,7 +1766,7 @@ void plan_voc(Bump& b, int B, int T, const int* ch, VocBufs& v, bool mrf_streams
     auto take = [&](size_t n, int C, int l) { float* q = b.take(n); v.zl[v.nz].p = q; v.zl[v.nz].C = C; v.zl[v.nz].l = l; ++v.nz; return q; };
     v.M0 = take((size_t)v.g[0].nrows * 80, 80, 0);
     v.C0 = take((size_t)v.g[0].nrows * ch[0], ch[0], 0);
-    for (int l = 1; l <= 4; ++l) {
+    for (int l = 1; l <= nl; ++l) {
         const size_t n = (size_t)v.g[l].nrows * ch[l];
         v.U[l] = take(n, ch[l], l); v.XS[l] = take(n, ch[l], l); v.T1[l] = take(n, ch[l], l); v.Pa[l] = take(n, ch[l], l); v.Pb[l] = take(n, ch[l], l);
         for (int c = 0; c < 2; ++c) {
@@ -1713,8 +1790,9 @@ size_t plan_all(ev_handle* h, char* base, int B, int Tp, int Tv, EstBufs* eb, Vo
     if (Tp > 0) plan_est(b, B, Tp, h->est.loaded ? h->est.in_ch : 2 * h->dims.n_feats + h->dims.spk_emb_dim, h->max_steps, e);
     if (voc_off) *voc_off = b.off;
     if (Tv > 0) {
-        int ch[5] = {512, 256, 128, 64, 32};
-        plan_voc(b, B, Tv, h->voc.loaded ? h->voc.ch : ch, v, mrf_streams_for(h, B, Tv));
+        const int ch[5] = {512, 256, 128, 64, 32}, rates[4] = {8, 8, 2, 2};   // (no vocoder loaded: plan V1)
+        const VocoderW& w = h->voc;
+        plan_voc(b, B, Tv, w.loaded ? w.ch : ch, w.loaded ? w.rates : rates, w.loaded ? w.nl : 4, w.loaded ? w.P0 : 4, v, mrf_streams_for(h, B, Tv));
     }
     if (eb) *eb = e;
     if (vb) *vb = v;
@@ -2354,16 +2432,46 @@ int ev_load_estimator(ev_handle* h, const float* blob, const ev_tensor_index* in
     return 0;
 }
 
-int ev_load_vocoder(ev_handle* h, const float* blob, const ev_tensor_index* index, size_t n) {
+// The envelope of configs ev_load_vocoder_cfg takes (include/emojivoice.h; emojivoice_amd/hifigan.py checks the same in Python)
+static int check_vocoder_config(ev_handle* h, const ev_vocoder_config& c) {
+    if (c.resblock != 1 && c.resblock != 2) return fail(h, "vocoder config: resblock must be 1 or 2 (got %d)", c.resblock);
+    if (c.num_levels < 1 || c.num_levels > 4) return fail(h, "vocoder config: 1 to 4 upsampling levels (got %d)", c.num_levels);
+    long prod = 1;
+    for (int i = 0; i < c.num_levels; ++i) {
+        const int u = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
+        if (u < 1) return fail(h, "vocoder config: upsample rate %d of level %d must be positive", u, i);
+        if (k < u || ((k - u) & 1)) return fail(h, "vocoder config: level %d needs k >= u and k - u even (k = %d, u = %d)", i, k, u);
+        prod *= u;
+    }
+    if (prod != 256) return fail(h, "vocoder config: the product of the upsample rates must be 256, the hop size (got %ld)", prod);
+    const int nd = c.resblock == 1 ? 3 : 2;
+    for (int j = 0; j < 3; ++j) {
+        const int k = c.resblock_kernel_sizes[j];
+        if (k < 1 || !(k & 1) || k > EV_MAX_TAPS) return fail(h, "vocoder config: resblock kernel sizes must be odd and at most %d (got %d)", EV_MAX_TAPS, k);
+        for (int m = 0; m < nd; ++m) {
+            const int d = c.resblock_dilations[j][m], halo = (k - 1) * d / 2;
+            if (d < 1) return fail(h, "vocoder config: dilation %d must be positive", d);
+            if (2 * halo > (c.resblock == 1 ? EV_HALO : 2 * EV_HALO))
+                return fail(h, "vocoder config: conv halo (k - 1) d / 2 = %d exceeds %d for ResBlock%d", halo, c.resblock == 1 ? EV_HALO / 2 : EV_HALO, c.resblock);
+        }
+    }
+    return 0;
+}
+
+static int load_vocoder(ev_handle* h, const float* blob, const ev_tensor_index* index, size_t n, const ev_vocoder_config& cfg) {
     if (!h) return 1;
     HIPCHK(h, hipSetDevice(h->device));
+    if (check_vocoder_config(h, cfg)) return 1;
     TensorMap m;
     if (build_map(h, blob, index, n, m)) return 1;
     VocoderW& v = h->voc;
-    v.loaded = false;
-    const int rates[4] = {8, 8, 2, 2}, ksz[4] = {16, 16, 4, 4}, rk[3] = {3, 7, 11}, rd[3] = {1, 3, 5};
+    v = VocoderW();
+    v.rb = cfg.resblock; v.nl = cfg.num_levels;
+    const int nl = v.nl, nd = v.rb == 1 ? 3 : 2;
+    for (int i = 0; i < nl; ++i) v.rates[i] = cfg.upsample_rates[i];
     const HostTensor *pw = T_("conv_pre.weight"), *pb = T_("conv_pre.bias"), *qw = T_("conv_post.weight"), *qb = T_("conv_post.bias");
     if (!pw || !pb || !qw || !qb) return 1;
+    if (pw->ndim != 3 || pw->shape[1] != 80) return fail(h, "conv_pre.weight must be (C, 80, k): num_mels = 80");
     REQ(pack_conv(h, v.pre, *pw, pb, 1));
     REQ(pack_conv(h, v.post, *qw, qb, 1));
     {   // conv_post_kernel's copy: (1, C, K) -> [K][C]
@@ -2374,29 +2482,77 @@ int ev_load_vocoder(ev_handle* h, const float* blob, const ev_tensor_index* inde
         v.post_b = qb->p[0]; v.post_k = K;
     }
     v.ch[0] = (int)pw->shape[0];
-    for (int i = 0; i < 4; ++i) {
+    // pad rows: the mel level keeps 4 (V1's plan) unless a level's widest conv halo needs more than 4 x (rates so far)
+    v.P0 = 4;
+    for (int i = 0, prod = 1; i < nl; ++i) {
+        prod *= v.rates[i];
+        int halo = i == nl - 1 ? 3 : 0;                     // (conv_post, k = 7)
+        for (int j = 0; j < 3; ++j)
+            for (int mm = 0; mm < nd; ++mm) halo = std::max(halo, (cfg.resblock_kernel_sizes[j] - 1) * cfg.resblock_dilations[j][mm] / 2);
+        v.P0 = std::max(v.P0, (halo + prod - 1) / prod);
+    }
+    for (int i = 0; i < nl; ++i) {
         char nm[64];
         snprintf(nm, sizeof nm, "ups.%d.weight", i); const HostTensor* uw = T_(nm);
         snprintf(nm, sizeof nm, "ups.%d.bias", i); const HostTensor* ub = T_(nm);
         if (!uw || !ub) return 1;
-        if ((int)uw->shape[2] != ksz[i]) return fail(h, "ups.%d kernel %d != %d", i, (int)uw->shape[2], ksz[i]);
-        REQ(pack_convT(h, v.ups[i], *uw, ub, rates[i], (ksz[i] - rates[i]) / 2));
+        const int u = v.rates[i], k = cfg.upsample_kernel_sizes[i];
+        if ((int)uw->shape[2] != k) return fail(h, "ups.%d kernel %d != %d", i, (int)uw->shape[2], k);
         v.ch[i + 1] = (int)uw->shape[1];
-        for (int j = 0; j < 3; ++j)
-            for (int mm = 0; mm < 3; ++mm) {
-                snprintf(nm, sizeof nm, "resblocks.%d.convs1.%d.weight", i * 3 + j, mm); const HostTensor* w1 = T_(nm);
-                snprintf(nm, sizeof nm, "resblocks.%d.convs1.%d.bias", i * 3 + j, mm); const HostTensor* b1 = T_(nm);
-                snprintf(nm, sizeof nm, "resblocks.%d.convs2.%d.weight", i * 3 + j, mm); const HostTensor* w2 = T_(nm);
-                snprintf(nm, sizeof nm, "resblocks.%d.convs2.%d.bias", i * 3 + j, mm); const HostTensor* b2 = T_(nm);
-                if (!w1 || !b1 || !w2 || !b2) return 1;
-                if ((int)w1->shape[2] != rk[j]) return fail(h, "resblock kernel mismatch");
-                REQ(pack_conv(h, v.c1[i * 3 + j][mm], *w1, b1, rd[mm]));
-                REQ(pack_conv(h, v.c2[i * 3 + j][mm], *w2, b2, 1));
+        if (uw->shape[0] != v.ch[i] || 2 * v.ch[i + 1] != v.ch[i]) return fail(h, "ups.%d: channels must halve per level (%d -> %d)", i, v.ch[i], v.ch[i + 1]);
+        if (v.ch[i + 1] % 8) return fail(h, "vocoder config: level %d is %d channels wide, not a multiple of 8", i + 1, v.ch[i + 1]);
+        REQ(pack_convT(h, v.ups[i], *uw, ub, u, (k - u) / 2));
+        for (int j = 0; j < 3; ++j) {
+            const int b = i * 3 + j, K = cfg.resblock_kernel_sizes[j];
+            for (int mm = 0; mm < nd; ++mm) {
+                const HostTensor *w1, *b1, *w2 = nullptr, *b2 = nullptr;
+                if (v.rb == 1) {
+                    snprintf(nm, sizeof nm, "resblocks.%d.convs1.%d.weight", b, mm); w1 = T_(nm);
+                    snprintf(nm, sizeof nm, "resblocks.%d.convs1.%d.bias", b, mm); b1 = T_(nm);
+                    snprintf(nm, sizeof nm, "resblocks.%d.convs2.%d.weight", b, mm); w2 = T_(nm);
+                    snprintf(nm, sizeof nm, "resblocks.%d.convs2.%d.bias", b, mm); b2 = T_(nm);
+                    if (!w2 || !b2) return 1;
+                } else {
+                    snprintf(nm, sizeof nm, "resblocks.%d.convs.%d.weight", b, mm); w1 = T_(nm);
+                    snprintf(nm, sizeof nm, "resblocks.%d.convs.%d.bias", b, mm); b1 = T_(nm);
+                }
+                if (!w1 || !b1) return 1;
+                if ((int)w1->shape[2] != K) return fail(h, "resblocks.%d kernel %d != %d", b, (int)w1->shape[2], K);
+                const int d = cfg.resblock_dilations[j][mm];
+                if (v.rb == 1) {
+                    REQ(pack_conv(h, v.c1[b][mm], *w1, b1, d));
+                    REQ(pack_conv(h, v.c2[b][mm], *w2, b2, 1));
+                } else {
+                    v.c1[b][mm].wide = true;                 // (whole: resblock2_h16_kernel carries its own halo)
+                    REQ(pack_conv(h, v.c1[b][mm], *w1, b1, d));
+                    if (v.c1[b][mm].halo_lo + v.c1[b][mm].halo_hi > EV_HALO) {   // the conv launches take it as two tap subsets
+                        REQ(pack_conv(h, v.lo[b][mm], *w1, b1, d, 0, K / 2 + 1));
+                        REQ(pack_conv(h, v.hi[b][mm], *w1, nullptr, d, K / 2 + 1, K));
+                    }
+                }
             }
+        }
     }
     REQ(ensure_sk(h, false));   // the balanced builds' hand-off area: a mid-size ev_hifigan call (e.g. 8 x 516 frames) takes them — never allocate on the request path
+    h->ws_B = -1;               // (another config plans other tensors: re-plan and re-zero on the next call)
     v.loaded = true;
     return 0;
+}
+
+int ev_load_vocoder(ev_handle* h, const float* blob, const ev_tensor_index* index, size_t n) {
+    ev_vocoder_config c;
+    memset(&c, 0, sizeof c);
+    c.resblock = 1; c.num_levels = 4;
+    const int rates[4] = {8, 8, 2, 2}, ksz[4] = {16, 16, 4, 4}, rk[3] = {3, 7, 11};
+    for (int i = 0; i < 4; ++i) { c.upsample_rates[i] = rates[i]; c.upsample_kernel_sizes[i] = ksz[i]; }
+    for (int j = 0; j < 3; ++j) { c.resblock_kernel_sizes[j] = rk[j]; c.resblock_dilations[j][0] = 1; c.resblock_dilations[j][1] = 3; c.resblock_dilations[j][2] = 5; }
+    return load_vocoder(h, blob, index, n, c);
+}
+
+int ev_load_vocoder_cfg(ev_handle* h, const float* blob, const ev_tensor_index* index, size_t n, const ev_vocoder_config* cfg) {
+    if (!h) return 1;
+    if (!cfg) return fail(h, "ev_load_vocoder_cfg: null config");
+    return load_vocoder(h, blob, index, n, *cfg);
 }
 #undef T_
 #undef REQ
@@ -2809,8 +2965,10 @@ int ev_hifigan(ev_handle* h, const float* d_mel, int B, int T, float* d_wav, voi
         }
     } guard{h, s0, h->sk_balance, ms, false};
     if (ms) h->sk_balance = false;
-    for (int i = 0; i < 4; ++i) {
+    const int nl = w.nl;
+    for (int i = 0; i < nl; ++i) {
         const int l = i + 1, C = w.ch[l], s = w.ups[i].Cout / C;
+        const float next_slope = (l == nl) ? 0.01f : 0.1f;      // the leaky_relu in front of the next consumer: ups[l] (0.1) or conv_post (0.01)
         {   // transposed conv: input frames of level l-1 -> view rows of s output frames each
             Epi e;
             with_slots(e, xin, nullptr, v.U[l], s);         // (a row of this launch = s rows of U[l]'s axis)
@@ -2827,14 +2985,51 @@ int ev_hifigan(ev_handle* h, const float* d_mel, int B, int T, float* d_wav, voi
             h->stream = own ? h->mrf_stream[j - 1] : s0;
             float* pp[2] = {own ? v.Pax[j - 1][l] : v.Pa[l], own ? v.Pbx[j - 1][l] : v.Pb[l]};
             float* t1 = own ? v.T1x[j - 1][l] : v.T1[l];
+            if (w.rb == 2) {   // ResBlock2 (models.py:136-141): x = x + c_d1(lrelu(x)); x = x + c_d2(lrelu(x)), the result joins the running mean
+                const int b = i * 3 + j;
+                auto join = [&](Epi& e) {
+                    e.accum = (j > 0);
+                    if (j == 2) { e.div3 = 1; e.act2_lrelu = 1; e.act2_slope = next_slope; }
+                };
+                if (rb2_ok(h, w.c1[b], C)) {   // the whole block in one launch (resblock2_h16_kernel)
+                    if (ms && j > 0) HIPCHK(h, hipStreamWaitEvent(h->stream, h->mrf_ev[j - 1], 0));
+                    Epi e; join(e);
+                    float* y = v.XS[l];
+                    if (l < nl) with_slots(e, x, nullptr, y, 1);
+                    if (launch_rb2(h, w.c1[b], x, y, C, v.g[l], e)) return 1;
+                    wrote(y, e.accum != 0);
+                } else {
+                    for (int mm = 0; mm < 2; ++mm) {   // one conv launch per step: prologue leaky_relu, residual epilogue
+                        float* y = mm == 0 ? pp[0] : v.XS[l];
+                        const float* r = x;
+                        if (w.lo[b][mm].ntaps) {       // halo beyond EV_HALO: the left taps (+ bias + residual) into t1, the right taps added below
+                            Epi ea; ea.pro_slope = 0.1f; ea.R = x; ea.ldr = C;
+                            with_slots(ea, x, x, t1, 1);
+                            if (launch_conv(h, w.lo[b][mm], x, C, t1, C, v.g[l], ea)) return 1;
+                            wrote(t1, false);
+                            r = t1;
+                        }
+                        const ConvLayer& L = w.lo[b][mm].ntaps ? w.hi[b][mm] : w.c1[b][mm];
+                        Epi e; e.pro_slope = 0.1f; e.R = r; e.ldr = C;
+                        if (mm == 1) join(e);
+                        if (ms && mm == 1 && j > 0) HIPCHK(h, hipStreamWaitEvent(h->stream, h->mrf_ev[j - 1], 0));   // the sum so far is in XS
+                        with_slots(e, x, r, y, 1);
+                        if (launch_conv(h, L, x, C, y, C, v.g[l], e)) return 1;
+                        wrote(y, e.accum != 0);
+                        x = y;
+                    }
+                }
+                if (ms) HIPCHK(h, hipEventRecord(h->mrf_ev[j], h->stream));
+                continue;
+            }
             if (h->fuse_pairs && chain_ok(h, w.c1[i * 3 + j], w.c2[i * 3 + j], C)) {
                 // the whole ResBlock in one launch: x never leaves the CU between its three pairs (resblock_chain_h16_kernel)
                 if (ms && j > 0) HIPCHK(h, hipStreamWaitEvent(h->stream, h->mrf_ev[j - 1], 0));
                 Epi e2;
                 float* y = v.XS[l];
                 e2.accum = (j > 0);
-                if (j == 2) { e2.div3 = 1; e2.act2_lrelu = 1; e2.act2_slope = (i == 3) ? 0.01f : 0.1f; }
-                if (l < 4) with_slots(e2, x, nullptr, y, 1);
+                if (j == 2) { e2.div3 = 1; e2.act2_lrelu = 1; e2.act2_slope = next_slope; }
+                if (l < nl) with_slots(e2, x, nullptr, y, 1);
                 if (launch_chain(h, w.c1[i * 3 + j], w.c2[i * 3 + j], x, y, C, v.g[l], e2)) return 1;
                 wrote(y, e2.accum != 0);
                 if (ms) HIPCHK(h, hipEventRecord(h->mrf_ev[j], h->stream));
@@ -2847,14 +3042,14 @@ int ev_hifigan(ev_handle* h, const float* d_mel, int B, int T, float* d_wav, voi
                 if (mm == 2) {   // resblock output joins the running mean over the 3 kernel sizes (models.py:186-192)
                     y = v.XS[l];
                     e2.accum = (j > 0);
-                    if (j == 2) { e2.div3 = 1; e2.act2_lrelu = 1; e2.act2_slope = (i == 3) ? 0.01f : 0.1f; }  // next consumer's leaky_relu
+                    if (j == 2) { e2.div3 = 1; e2.act2_lrelu = 1; e2.act2_slope = next_slope; }  // next consumer's leaky_relu
                 }
                 if (h->fuse_pairs && (C == 32 || C == 64 || (C == 128 && h->fuse128 && w.c1[i * 3 + j][mm].ntaps <= h->fuse128))) {
                     // narrow stages: both convs of the pair in one launch, intermediate kept in LDS
                     // (a fused pair finds its own tile maximum and bounds its residual with it: it needs no slots of x, and only the pair that
                     // closes a chain into the running sum of a level whose sum an fp16 build consumes — the upsampler of levels 1..3 — leaves
                     // bounds at all: an atomic per wave costs the narrow pairs 3-10 %, profiles/r04_amax_ab.txt)
-                    if (mm == 2 && l < 4) with_slots(e2, x, nullptr, y, 1);
+                    if (mm == 2 && l < nl) with_slots(e2, x, nullptr, y, 1);
                     if (launch_pair(h, w.c1[i * 3 + j][mm], w.c2[i * 3 + j][mm], x, y, C, v.g[l], e2)) return 1;
                     wrote(y, e2.accum != 0);
                 } else {
@@ -2876,17 +3071,20 @@ int ev_hifigan(ev_handle* h, const float* d_mel, int B, int T, float* d_wav, voi
         cin = C;
     }
     {   // conv_post + tanh straight into (B, 256 T)
-        const Geom& g4 = v.g[4];
-        if (w.ch[4] == 32 && w.post_k == 7 && w.post_w && g4.P >= 3) {
+        const Geom& g4 = v.g[nl];
+        const int Cl = w.ch[nl];
+        if ((Cl == 32 || Cl == 16 || Cl == 8) && w.post_k == 7 && w.post_w && g4.P >= 3) {
             const int tiles = (g4.T + 255) / 256;
-            hipLaunchKernelGGL((conv_post_kernel<32, 7>), dim3((unsigned)(B * tiles)), dim3(256), 0, h->stream, (const float*)v.XS[4], (const float*)w.post_w,
-                               w.post_b, d_wav, g4.T, g4.S, g4.P);
+            const dim3 grid((unsigned)(B * tiles));
+            if (Cl == 32) hipLaunchKernelGGL((conv_post_kernel<32, 7>), grid, dim3(256), 0, h->stream, (const float*)v.XS[nl], (const float*)w.post_w, w.post_b, d_wav, g4.T, g4.S, g4.P);
+            else if (Cl == 16) hipLaunchKernelGGL((conv_post_kernel<16, 7>), grid, dim3(256), 0, h->stream, (const float*)v.XS[nl], (const float*)w.post_w, w.post_b, d_wav, g4.T, g4.S, g4.P);
+            else hipLaunchKernelGGL((conv_post_kernel<8, 7>), grid, dim3(256), 0, h->stream, (const float*)v.XS[nl], (const float*)w.post_w, w.post_b, d_wav, g4.T, g4.S, g4.P);
             HIPCHK(h, hipGetLastError());
         } else {   // other channel / tap counts: the generic conv + a strip pass
             Epi e; e.act = ACT_TANH;
-            if (launch_conv(h, w.post, v.XS[4], w.ch[4], v.T1[4], 1, g4, e)) return 1;
+            if (launch_conv(h, w.post, v.XS[nl], Cl, v.T1[nl], 1, g4, e)) return 1;
             const size_t total = (size_t)B * g4.T;
-            hipLaunchKernelGGL(strip_pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, (const float*)v.T1[4], d_wav, g4.T, g4.S, g4.P, total);
+            hipLaunchKernelGGL(strip_pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, (const float*)v.T1[nl], d_wav, g4.T, g4.S, g4.P, total);
             HIPCHK(h, hipGetLastError());
         }
     }

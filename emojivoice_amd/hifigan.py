@@ -1,4 +1,4 @@
-"""Drop-in for ``matcha.hifigan.models.Generator`` (+ ``config.v1``, ``env.AttrDict``).
+"""Drop-in for ``matcha.hifigan.models.Generator`` (+ ``config.v1``, ``env.AttrDict``) and the V2 / V3 configs (``v2``, ``v3``).
 
 Call surface kept from the reference (hifigan/models.py:148-206, cli.py:84-90):
 
@@ -20,6 +20,51 @@ from ._lib import Engine, EvLibraryError
 v1 = dict(W.HIFIGAN_V1, num_gpus=0, batch_size=16, learning_rate=0.0004, adam_b1=0.8, adam_b2=0.99, lr_decay=0.999, seed=1234,
           resblock_initial_channel=256, segment_size=8192, num_freq=1025, n_fft=1024, win_size=1024, fmin=0, fmax=8000,
           fmax_loss=None, num_workers=4)
+_train = {k: v for k, v in v1.items() if k not in W.HIFIGAN_V1}
+v2 = dict(W.HIFIGAN_V2, **dict(_train, learning_rate=0.0002))
+v3 = dict(W.HIFIGAN_V3, **dict(_train, learning_rate=0.0002))
+
+EV_MAX_TAPS = 16   # ev_kernels.h
+EV_HALO = 64       # ev_kernels.h: halo rows (both sides) of one conv launch
+
+
+def check_config(h) -> None:
+    """Raise ValueError unless ``h`` lies inside the envelope the HIP vocoder supports (include/emojivoice.h, ev_vocoder_config)."""
+    def bad(msg):
+        raise ValueError(f"unsupported HiFi-GAN config: {msg}")
+
+    rb = str(h["resblock"])
+    if rb not in ("1", "2"):
+        bad(f"resblock must be '1' or '2' (got {h['resblock']!r})")
+    if int(h.get("num_mels", 80)) != 80:
+        bad(f"num_mels must be 80 (got {h['num_mels']})")
+    rates, ks = list(h["upsample_rates"]), list(h["upsample_kernel_sizes"])
+    if not 1 <= len(rates) <= 4 or len(ks) != len(rates):
+        bad(f"1 to 4 upsampling levels with one kernel size each (got rates {rates}, kernel sizes {ks})")
+    prod = 1
+    for i, (u, k) in enumerate(zip(rates, ks)):
+        if u < 1 or k < u or (k - u) % 2:
+            bad(f"level {i} needs k >= u and k - u even (k = {k}, u = {u})")
+        prod *= u
+    if prod != 256:
+        bad(f"the product of upsample_rates must be 256, the hop size (got {prod})")
+    rk, rd = list(h["resblock_kernel_sizes"]), [list(d) for d in h["resblock_dilation_sizes"]]
+    if len(rk) != 3 or len(rd) != 3:
+        bad(f"exactly 3 resblock kernel sizes with one dilation list each (got {len(rk)} and {len(rd)})")
+    nd, max_halo = (3, EV_HALO // 2) if rb == "1" else (2, EV_HALO)
+    for k, ds in zip(rk, rd):
+        if k < 1 or k % 2 == 0 or k > EV_MAX_TAPS:
+            bad(f"resblock kernel sizes must be odd and at most {EV_MAX_TAPS} (got {k})")
+        if len(ds) != nd:
+            bad(f"ResBlock{rb} takes {nd} dilations per kernel size (got {ds})")
+        for d in ds:
+            if d < 1 or (k - 1) * d // 2 > max_halo:
+                bad(f"dilation {d} at kernel size {k}: conv halo (k - 1) d / 2 must be 1..{max_halo} for ResBlock{rb}")
+    c0 = int(h["upsample_initial_channel"])
+    for i in range(len(rates)):
+        if c0 % (2 ** (i + 1)) or (c0 // 2 ** (i + 1)) % 8:
+            bad(f"level {i + 1} width {c0 / 2 ** (i + 1):g} is not a multiple of 8")
+
 
 
 class AttrDict(dict):
@@ -33,8 +78,7 @@ class AttrDict(dict):
 class Generator:
     def __init__(self, h):
         self.h = h
-        if str(h["resblock"]) != "1" or list(h["upsample_rates"]) != [8, 8, 2, 2] or list(h["resblock_kernel_sizes"]) != [3, 7, 11]:
-            raise ValueError("only the HiFi-GAN V1 configuration (hifigan/config.py:1-28) is implemented")
+        check_config(h)
         self.num_kernels = len(h["resblock_kernel_sizes"])
         self.num_upsamples = len(h["upsample_rates"])
         self._raw: Optional[Dict[str, torch.Tensor]] = None
@@ -102,7 +146,7 @@ class Generator:
             if self.engine is not None:
                 self.engine.close()
             self.engine = Engine(self.device.index, spk_emb_dim=64)
-            self.engine.load_vocoder(self._folded)
+            self.engine.load_vocoder(self._folded, self.h)
             self._dirty = False
 
     @torch.inference_mode()
@@ -123,9 +167,10 @@ class Generator:
     __call__ = forward
 
 
-def synthetic(device="cuda:0") -> Generator:
-    g = Generator(AttrDict(v1)).to(device)
-    g.load_state_dict(W.synthetic_hifigan_state())
+def synthetic(device="cuda:0", h=None) -> Generator:
+    h = AttrDict(v1 if h is None else h)
+    g = Generator(h).to(device)
+    g.load_state_dict(W.synthetic_hifigan_state(h))
     return g
 
 

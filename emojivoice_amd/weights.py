@@ -57,6 +57,10 @@ HIFIGAN_V1 = {
     "sampling_rate": 22050,
     "hop_size": 256,
 }
+# The published lighter generators (upstream HiFi-GAN config_v2.json / config_v3.json)
+HIFIGAN_V2 = dict(HIFIGAN_V1, upsample_initial_channel=128)
+HIFIGAN_V3 = dict(HIFIGAN_V1, resblock="2", upsample_rates=[8, 8, 4], upsample_kernel_sizes=[16, 16, 8], upsample_initial_channel=256,
+                  resblock_kernel_sizes=[3, 5, 7], resblock_dilation_sizes=[[1, 2], [2, 6], [3, 12]])
 
 Shape = Tuple[int, ...]
 
@@ -194,9 +198,15 @@ def hifigan_shapes(h: dict = HIFIGAN_V1) -> "OrderedDict[str, Shape]":
         o[f"ups.{i}.weight"] = (c0 // (2**i), c0 // (2 ** (i + 1)), k)  # ConvTranspose1d (Cin, Cout, k)
         o[f"ups.{i}.bias"] = (c0 // (2 ** (i + 1)),)
     nk = len(h["resblock_kernel_sizes"])
+    rb2 = str(h["resblock"]) != "1"
     for i in range(len(h["upsample_rates"])):
         ch = c0 // (2 ** (i + 1))
         for j, k in enumerate(h["resblock_kernel_sizes"]):
+            if rb2:   # ResBlock2 (models.py:106-137): one ModuleList of two dilated convs
+                for m in range(2):
+                    o[f"resblocks.{i * nk + j}.convs.{m}.weight"] = (ch, ch, k)
+                    o[f"resblocks.{i * nk + j}.convs.{m}.bias"] = (ch,)
+                continue
             for m in range(3):
                 for cs in ("convs1", "convs2"):
                     o[f"resblocks.{i * nk + j}.{cs}.{m}.weight"] = (ch, ch, k)
@@ -260,8 +270,9 @@ def synthetic_hifigan_state(h: dict = HIFIGAN_V1, salt: str = "ev0") -> "Ordered
     The reference ``init_weights`` (xutils.py:25-28, std 0.01) yields ~1e-2 RMS
     audio that makes the 1e-3 waveform gate vacuous, so matrices
     are drawn at variance-preserving scale instead: the residual branch of each
-    ResBlock1 pair is damped (0.5/sqrt(fan_in) on its second conv) and
-    ``conv_post`` targets a pre-tanh std of ~0.5.
+    ResBlock1 pair is damped (0.5/sqrt(fan_in) on its second conv), likewise
+    each conv of a ResBlock2 (its residual branches), and ``conv_post``
+    targets a pre-tanh std of ~0.5.
     """
     sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
     strides = h["upsample_rates"]
@@ -272,7 +283,7 @@ def synthetic_hifigan_state(h: dict = HIFIGAN_V1, salt: str = "ev0") -> "Ordered
             i = int(k.split(".")[1])
             fan_in = s[0] * s[2] // strides[i]
             t = _randn(k, s, 1.3 / math.sqrt(fan_in), salt)
-        elif ".convs2." in k:
+        elif ".convs2." in k or ".convs." in k:
             t = _randn(k, s, 0.5 / math.sqrt(s[1] * s[2]), salt)
         elif k == "conv_post.weight":
             t = _randn(k, s, 0.5 / math.sqrt(s[1] * s[2]), salt)

@@ -10,13 +10,16 @@
  *                       (BasicTransformerBlock             models/components/transformer.py:243-316,
  *                        diffusers Attention, SnakeBeta    transformer.py:17-80)
  *   ev_hifigan      <-  Generator.forward                  hifigan/models.py:181-197
- *                       (ResBlock1.forward                 hifigan/models.py:90-97)
+ *                       (ResBlock1.forward                 hifigan/models.py:90-97,
+ *                        ResBlock2.forward                 hifigan/models.py:106-145: x = x + c_d(lrelu(x)) for two dilations,
+ *                        keys resblocks.N.convs.{0,1}.{weight,bias})
  *   ev_text_encoder <-  TextEncoder.forward                models/components/text_encoder.py:378-410
  *                       (ConvReluNorm :36-67, Encoder :276-325, MultiHeadAttention + RoPE :97-246, FFN :255-273,
  *                        DurationPredictor :70-94, channel LayerNorm :15-33) — the caller of the hot path
  *   ev_load_estimator <- MatchaTTS.load_from_checkpoint -> state_dict["decoder.estimator.*"]   cli.py:110-118
  *   ev_load_text_encoder <- same checkpoint, state_dict["encoder.*"] + the derived "rope_theta" table
  *   ev_load_vocoder   <- Generator.load_state_dict(ckpt["generator"]) + remove_weight_norm()   cli.py:84-90
+ *   ev_load_vocoder_cfg <- the same for the Generator(h) of any HiFi-GAN config inside the supported envelope (V1, V2, V3 ...)
  *
  * Conventions
  *   - All tensors are fp32.  Pointers named d_* are DEVICE pointers owned by the
@@ -54,7 +57,8 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg (look the symbol up to detect them);
+                              4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
 
@@ -84,7 +88,21 @@ const char *ev_last_error(ev_handle *h);
 
 /* Weights: host blob + index; copied and re-laid-out into library-owned device memory. */
 int ev_load_estimator(ev_handle *h, const float *blob, const ev_tensor_index *index, size_t n);
-int ev_load_vocoder(ev_handle *h, const float *blob, const ev_tensor_index *index, size_t n);
+int ev_load_vocoder(ev_handle *h, const float *blob, const ev_tensor_index *index, size_t n);   /* the V1 config (hifigan/config.py:1-28) */
+
+/* A HiFi-GAN generator config (the `h` of hifigan/models.py:148-179).  Channel widths come from the tensors (conv_pre's output
+ * halving per level).  Supported envelope — anything else fails with a message naming the constraint:
+ *   1..4 levels, product of the rates 256; k >= u and k - u even per level; exactly 3 resblock kernel sizes, odd, <= 16;
+ *   3 dilations per ResBlock1 (halo (k-1) d / 2 <= 32), 2 per ResBlock2 (halo <= 64); every level's width a multiple of 8. */
+typedef struct ev_vocoder_config {
+    int32_t resblock;                   /* 1: ResBlock1, 2: ResBlock2 */
+    int32_t num_levels;                 /* len(upsample_rates) */
+    int32_t upsample_rates[4];
+    int32_t upsample_kernel_sizes[4];
+    int32_t resblock_kernel_sizes[3];
+    int32_t resblock_dilations[3][3];   /* per kernel size; ResBlock2 reads the first two */
+} ev_vocoder_config;
+int ev_load_vocoder_cfg(ev_handle *h, const float *blob, const ev_tensor_index *index, size_t n, const ev_vocoder_config *cfg);
 /* Text-encoder keys: state_dict["encoder.<key>"] (matcha_tts.py:52-60) plus "rope_theta" =
  * 1 / (10000 ** (arange(0, d, 2) / d)), d = 64  (text_encoder.py:115-117), computed by the loader with the reference's ops. */
 int ev_load_text_encoder(ev_handle *h, const float *blob, const ev_tensor_index *index, size_t n);
@@ -149,7 +167,7 @@ int ev_align(ev_handle *h, const float *d_wceil, const float *d_mu_x, const int3
  * must not have the host wait inside the call, sets 0 (emojivoice_amd/pipeline.py does). */
 int ev_set_mrf_streams_max(ev_handle *h, int max_frames);
 
-/* HiFi-GAN V1 generator: d_mel (B, 80, T) -> d_wav (B, 256*T), tanh output, no clamp/denoiser.
+/* HiFi-GAN generator of the loaded config: d_mel (B, 80, T) -> d_wav (B, 256*T), tanh output, no clamp/denoiser.
  * Calls of B*T <= 16384 mel frames (EV_MRF_STREAMS_MAX) first wait for `stream` to drain on the host, then run the three
  * ResBlock1 chains of each level on `stream` and two streams of the handle, joined back into `stream` by events before the
  * call returns: the result is ordered on `stream` like that of any other call.  Such a call is not graph-capturable. */
@@ -211,7 +229,8 @@ int ev_dbg_set_attn_h16(ev_handle *h, int on);
 /* Diagnostic / A-B switch (ABI 4): on = 1 (default): under arithmetic setting 16, ev_hifigan runs a whole ResBlock1 (hifigan/models.py:90-97: three
  * (dilated conv, conv) pairs with their residual adds) as ONE launch where the level is narrow (32 / 64 channels) and the kernel size small enough
  * for the summed halos (k = 3): the running x stays in registers between the pairs; on = 0: three fused-pair launches as before.  EV_NO_CHAIN=1
- * presets 0.  Results differ by rounding only (other tile boundaries, hence other power-of-two tile scales). */
+ * presets 0.  The same switch turns off the one-launch ResBlock2 (resblock2_h16_kernel; off: one conv launch per step).
+ * Results differ by rounding only (other tile boundaries, hence other power-of-two tile scales). */
 int ev_dbg_set_chain(ev_handle *h, int on);
 
 /* Diagnostic: the control words of the balanced ("stream-K") launches (ev_kernels.h, SkCtl) after a device synchronisation:

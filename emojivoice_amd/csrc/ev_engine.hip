@@ -40,8 +40,6 @@ struct ConvLayer {
     float* bias = nullptr;    // [Cout] (stacked / phase-replicated as needed) or null
     int2* taplist[3] = {nullptr, nullptr, nullptr};   // for BM = 128, 64, 32: [mtiles][EV_MAX_TAPS] {tap, row offset} (one shared row when dense)
     int* nact[3] = {nullptr, nullptr, nullptr};       // per-tile active tap count (null when dense)
-    unsigned char nact64[16] = {0};                   // host copy of the BM = 64 counts of the first 16 M tiles (unit weights of the balanced build)
-    bool pair256_uniform = false;                     // Mpad % 256 == 0 and the two 128-channel tiles of every 256-channel tile carry the same tap list (conv_h16_bal_kernel<256, 128>)
     bool sparse_taps = false;
     bool tile128_exact = true;              // every 128-channel M tile carries exactly the taps of both its 64-channel halves (no union waste)
     int kstack_mt = 0, kstack_tap = 0;      // sparse_taps of the stacked [k-tap conv | 1x1 conv] kind: 32-channel tiles >= kstack_mt carry only tap kstack_tap
@@ -58,7 +56,7 @@ struct Epi {
     int act2_lrelu = 0; float act2_slope = 0.f; int mask2 = 0; const float* rowmask = nullptr; int mmul = 1;
     float* Y2 = nullptr; int ldy2 = 0;
     float pro_slope = -1.f;                 // >= 0: prologue leaky-relu on the input
-    int dbg = 0; int force_cfg = -1; int stagger = -1; unsigned long long* stamps = nullptr;
+    int dbg = 0; int force_cfg = -1; int stagger = -1; unsigned long long* stamps = nullptr;   // ev_dbg_conv_bench only
     float* gn_part = nullptr;               // ask for the per-tile GroupNorm statistics of the output (conv_sk32_kernel, one utterance); whether
                                             // they were produced is left in ev_handle::gn_stats_tiles (0 = no)
     int isplit_log2 = 31, isstride = 0;     // input column split (pair view of a strided slice)
@@ -142,7 +140,6 @@ struct ev_handle {
     // profiling
     bool prof = false;
     bool fuse_pairs = true;     // EV_FUSE_PAIRS=0 disables resblock_pair_kernel (A/B runs)
-    int fuse128 = 3;            // fuse C=128 pairs up to this kernel size (EV_FUSE128=0/3/7/11)
     bool fuse_attn = true;      // EV_FUSE_ATTN=0: attention and its output projection as separate launches (attention_kernel + a 1x1 conv)
     bool attn_h16 = true;       // EV_NO_ATTN_H16=1: the fused attention stays on the fp32 MFMA under arithmetic setting 16 too
     bool use_chain = true;      // ev_dbg_set_chain(h, 0) / EV_NO_CHAIN=1: ResBlock1 chains as three fused pairs instead of one launch
@@ -185,14 +182,23 @@ struct ev_handle {
     bool amax_emitted = false;      // set by every launch_conv / launch_pair: the launch left per-granule bounds of its output in Epi::ymax
     int n_fp32_only_layers = 0;     // layers whose weights are not the exact sum of three bf16 pieces (tiny or non-finite): they keep the fp32 MFMA build
     int last_cfg = -1;              // build the last launch_conv / launch_pair took (ev_dbg_last_cfg: tests assert that a shape ran on the build they mean)
-    bool sk_steal = true;           // EV_NO_SK_STEAL=1: owners wait for absent contributors (up to the spin limit) instead of taking their shares over (A/B)
     bool sk_balance = true;         // EV_NO_SK_BALANCE=1: every launch one tile per workgroup (A/B runs)
-    bool sk_spread = false;         // EV_SK_SPREAD=1: launches of fewer row tiles than CUs (small batches) spread their units over up to 2 x CUs workgroups
     int sk_wgs = 2;                 // EV_SK_WGS=<1..3>: persistent workgroups per CU of a balanced ln_mlp launch (A/B runs)
     int sk_spin = 3000;             // EV_SK_SPIN=<polls> before an owner recomputes a contributor's share itself (~1.5 us per poll: at most ~4.5 ms)
     int mrf_max_frames = 16384;     // EV_MRF_STREAMS_MAX=<B*T mel frames>: calls up to this size use the three streams (0 = never).  Six more scratch
                                     // tensors per level; at batch 64 x 516 frames (21 GB) the two-stage pipeline of bench.py already fills the gaps:
                                     // -1.4 % on the vocoder alone, +0.6 % on the pipelined step
+    // The reference sides of tests/test_gpu_variants.py and the other A/B switches, read once by ev_create
+    int force_cfg = -1;             // EV_FORCE_CFG=<cfg>: every conv launch takes this tile configuration (one launch_conv can select; -1 = none)
+    bool lean = true;               // EV_NO_LEAN=1: the generic epilogues instead of the instruction-lean ones
+    bool small_sk = true;           // EV_NO_SK=1: no split-K small-launch builds (conv_gemm_sk_kernel, conv_sk32_kernel)
+    bool sk32_lean = true;          // EV_NO_SK32_LEAN=1: 32 x 32 small launches on conv_gemm_sk_kernel instead of conv_sk32_kernel
+    bool gn_stats = true;           // EV_NO_GN_STATS=1: conv_sk32_kernel leaves no GroupNorm statistics (groupnorm_mish_kernel does them)
+    bool qkv_h16 = true;            // EV_NO_QKV_H16=1: LayerNorm + QKV of a large batch on the fp32 MFMA build
+    bool attn_sk = true;            // EV_NO_ATTN_SK=1: no split-key attention for small launches
+    int attn_tpw = 2;               // EV_ATTN_TPW=<n>: key tiles per workgroup of the split-key attention
+    bool full_rezero = false;       // EV_FULL_REZERO=1: a workspace whose shape changed is zeroed whole, not only the vocoder's pad rows
+    int rb2_minkeep = 4;            // EV_RB2_MINKEEP=<k>: rb2_ok takes a ResBlock2 whose stored share of a tile is at least k / 8
 };
 
 namespace {
@@ -342,12 +348,6 @@ int finish_layer(ev_handle* h, ConvLayer& L, const std::vector<float>& Wh, const
                 else if (t * BM < L.Cout) L.sparse_taps = true;
             }
     }
-    L.pair256_uniform = L.Mpad % 256 == 0;
-    for (int t = 0; t + 1 < L.Mpad / 128 && L.pair256_uniform; t += 2) {
-        const auto &a = lists[0][t], &b = lists[0][t + 1];
-        L.pair256_uniform = a.size() == b.size() && !a.empty();
-        for (size_t i = 0; i < a.size() && L.pair256_uniform; ++i) L.pair256_uniform = a[i].x == b[i].x && a[i].y == b[i].y;
-    }
     L.tile128_exact = true;
     for (int t = 0; t < L.Mpad / 128 && t * 128 < L.Cout; ++t)
         for (int hh = 0; hh < 2; ++hh)
@@ -376,7 +376,6 @@ int finish_layer(ev_handle* h, ConvLayer& L, const std::vector<float>& Wh, const
             }
             if (dev_upload(h, tab, &L.taplist[k])) return 1;
             if (dev_upload(h, cnt, &L.nact[k])) return 1;
-            if (k == 1) for (int t = 0; t < mt && t < 16; ++t) L.nact64[t] = (unsigned char)std::min(cnt[t], 15);
         }
     }
     return 0;
@@ -493,9 +492,9 @@ int upload_vec(ev_handle* h, const TensorMap& m, const std::string& k, float** o
 // Per-launch host-side state (no file-scope mutable state: different handles may be driven from different host threads)
 struct LaunchOpts {
     int halo = EV_HALO;      // halo rows of the layer being launched (LDS is sized for BN + halo, not BN + EV_HALO)
-    int kb = 1;              // k-chunks per stage (see conv_gemm_kernel: KB)
     int wgs_per_cu = 0;      // tools/conv_bench.py: cap workgroups per CU by over-allocating LDS (0 = off)
     int device = 0;
+    bool lean = true;        // ev_handle::lean (EV_NO_LEAN=1: the generic epilogues)
 };
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is sticky per (function, device): issue it only when a launch needs more
@@ -516,7 +515,7 @@ inline void ensure_dyn_smem(size_t smem, int device) {
     else (void)hipGetLastError();         // (the launch that follows reports the failure through hipGetLastError)
 }
 
-template <int BM, int BN, int WM, int WN, bool PF, bool FULL, int LEAN, int KB = 1>
+template <int BM, int BN, int WM, int WN, bool PF, bool FULL, int LEAN>
 void launch_cfg2(const ConvParams& p, hipStream_t st, const LaunchOpts& lo);
 
 // Dispatch on the epilogue flavour:
@@ -534,26 +533,23 @@ inline bool lean_ok(const ConvParams& p) {
 }
 template <int BM, int BN, int WM, int WN, bool PF = false>
 void launch_cfg(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
-    static const bool no_lean = getenv("EV_NO_LEAN") != nullptr;
-    const bool kb2 = !PF && lo.kb == 2;
-    if (!no_lean && lean_ok(p)) {
-        if (p.act == ACT_SNAKE) { if (kb2) launch_cfg2<BM, BN, WM, WN, false, false, 2, 2>(p, st, lo); else launch_cfg2<BM, BN, WM, WN, PF, false, 2>(p, st, lo); }
-        else if (lean_acc(p)) { if (kb2) launch_cfg2<BM, BN, WM, WN, false, false, 3, 2>(p, st, lo); else launch_cfg2<BM, BN, WM, WN, PF, false, 3>(p, st, lo); }
-        else { if (kb2) launch_cfg2<BM, BN, WM, WN, false, false, 1, 2>(p, st, lo); else launch_cfg2<BM, BN, WM, WN, PF, false, 1>(p, st, lo); }
-    } else if (p.act == ACT_NONE || p.act == ACT_LRELU) {
-        if (kb2) launch_cfg2<BM, BN, WM, WN, false, false, 0, 2>(p, st, lo); else launch_cfg2<BM, BN, WM, WN, PF, false, 0>(p, st, lo);
-    } else launch_cfg2<BM, BN, WM, WN, PF, true, 0>(p, st, lo);
+    if (lo.lean && lean_ok(p)) {
+        if (p.act == ACT_SNAKE) launch_cfg2<BM, BN, WM, WN, PF, false, 2>(p, st, lo);
+        else if (lean_acc(p)) launch_cfg2<BM, BN, WM, WN, PF, false, 3>(p, st, lo);
+        else launch_cfg2<BM, BN, WM, WN, PF, false, 1>(p, st, lo);
+    } else if (p.act == ACT_NONE || p.act == ACT_LRELU) launch_cfg2<BM, BN, WM, WN, PF, false, 0>(p, st, lo);
+    else launch_cfg2<BM, BN, WM, WN, PF, true, 0>(p, st, lo);
 }
 
-template <int BM, int BN, int WM, int WN, bool PF, bool FULL, int LEAN, int KB>
+template <int BM, int BN, int WM, int WN, bool PF, bool FULL, int LEAN>
 void launch_cfg2(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
     // LDS holds the X tile during the K loop and, afterwards, one transposed 32-frame slab per wave for the epilogue
-    const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * (32 * KB + 4);
+    const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * 36;
     constexpr size_t es = (size_t)4 * 32 * (BM / WM + 4);
     size_t smem = (xs > es ? xs : es) * sizeof(float);
     if (lo.wgs_per_cu > 0) { size_t cap = (size_t)(160 * 1024 / lo.wgs_per_cu) & ~(size_t)255; if (cap > smem) smem = cap; }
-    ensure_dyn_smem<conv_gemm_kernel<BM, BN, WM, WN, PF, FULL, LEAN, KB>>(smem, lo.device);
-    hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, PF, FULL, LEAN, KB>), dim3(p.mtiles * p.ntiles), dim3(256), smem, st, p);
+    ensure_dyn_smem<conv_gemm_kernel<BM, BN, WM, WN, PF, FULL, LEAN>>(smem, lo.device);
+    hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, PF, FULL, LEAN>), dim3(p.mtiles * p.ntiles), dim3(256), smem, st, p);
 }
 
 // conv_split_kernel (fp32 contraction as six bf16 products per element pair): the lean epilogues only
@@ -561,12 +557,7 @@ template <int BM, int BN, int WM, int WN, int TERMS = 6>
 void launch_split(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
     const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * EVX_RSB;
     constexpr size_t es = (size_t)4 * 32 * (BM / WM + 4) * sizeof(float);
-    size_t smem = xs > es ? xs : es;
-    {   // A/B: EV_SPLIT_WPC=<n> caps the deep-grid split builds at n workgroups per CU by padding the LDS request, which leaves the rest of
-        // the CU (LDS and registers) to the kernels of another stream
-        static const int wpc = getenv("EV_SPLIT_WPC") ? atoi(getenv("EV_SPLIT_WPC")) : 0;
-        if (wpc > 0) smem = std::max(smem, (size_t)((160 * 1024 / (wpc + 1) + 1024) & ~255));
-    }
+    const size_t smem = xs > es ? xs : es;
     const dim3 grid(p.mtiles * p.ntiles);
     if (p.act == ACT_SNAKE) { ensure_dyn_smem<conv_split_kernel<BM, BN, WM, WN, 2, TERMS>>(smem, lo.device); hipLaunchKernelGGL((conv_split_kernel<BM, BN, WM, WN, 2, TERMS>), grid, dim3(256), smem, st, p); }
     else if (lean_acc(p)) { ensure_dyn_smem<conv_split_kernel<BM, BN, WM, WN, 3, TERMS>>(smem, lo.device); hipLaunchKernelGGL((conv_split_kernel<BM, BN, WM, WN, 3, TERMS>), grid, dim3(256), smem, st, p); }
@@ -579,9 +570,8 @@ void launch_h16(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
     constexpr size_t es = (size_t)4 * 32 * (BM / WM + 4) * sizeof(float);
     const size_t smem = xs > es ? xs : es;
     const dim3 grid(p.mtiles * p.ntiles);
-    // the 16 x 16 x 32 K loop (conv_h16_kernel<..., Q = 1>) wherever the layer carries that fragment order; EV_H16Q=0: the 32 x 32 x 16 form (A/B)
-    static const bool use_q = !(getenv("EV_H16Q") && atoi(getenv("EV_H16Q")) == 0);
-    if (use_q && p.Wq && p.act != ACT_SNAKE) {
+    // the 16 x 16 x 32 K loop (conv_h16_kernel<..., Q = 1>) wherever the layer carries that fragment order
+    if (p.Wq && p.act != ACT_SNAKE) {
         if (lean_acc(p)) { ensure_dyn_smem<conv_h16_kernel<BM, BN, WM, WN, 3, 1>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_kernel<BM, BN, WM, WN, 3, 1>), grid, dim3(256), smem, st, p); }
         else { ensure_dyn_smem<conv_h16_kernel<BM, BN, WM, WN, 1, 1>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_kernel<BM, BN, WM, WN, 1, 1>), grid, dim3(256), smem, st, p); }
         return;
@@ -616,8 +606,7 @@ void launch_sk2(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
 }
 template <int TW>
 void launch_sk(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
-    static const bool no_lean = getenv("EV_NO_LEAN") != nullptr;
-    if (!no_lean && lean_ok(p)) {
+    if (lo.lean && lean_ok(p)) {
         if (p.act == ACT_SNAKE) launch_sk2<false, 2, TW>(p, st, lo);
         else if (lean_acc(p)) launch_sk2<false, 3, TW>(p, st, lo);
         else launch_sk2<false, 1, TW>(p, st, lo);
@@ -627,7 +616,7 @@ void launch_sk(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
 
 constexpr int EV_CAPTURE_SLOTS = 8;       // captured ev_cfm_decode calls a handle can hold (pinned staging that is never recycled)
 constexpr int EV_SK_MAXWG = 1024;          // persistent workgroups of a balanced launch (<= 4 per CU on 256 CUs)
-constexpr int EV_SK_PART_FLOATS = 16384;   // largest partial accumulator tile handed over (64 KB: a 64 x 192 conv tile is 48 KB)
+constexpr int EV_SK_PART_FLOATS = 16384;   // largest partial accumulator tile handed over (64 KB: a 128 x 128 conv tile)
 // Hand-off area of the balanced launches: allocated once per handle (never inside a stream capture: ev_load_estimator calls this)
 int ensure_sk(ev_handle* h, bool hot_path = true) {
     if (h->sk_ctrl) return 0;
@@ -641,20 +630,13 @@ int ensure_sk(ev_handle* h, bool hot_path = true) {
 
 // The balanced persistent build of a conv launch (conv_gemm_bal_kernel): G = wpc x CUs workgroups share the (tile, k-chunk) units.
 template <int BM, int BN, int WM, int WN>
-int launch_bal(ev_handle* h, ConvParams p, const LaunchOpts& lo, int wpc, unsigned long long wtab = 0) {
+int launch_bal(ev_handle* h, ConvParams p, const LaunchOpts& lo, int wpc) {
     if (ensure_sk(h)) return 1;
     const int nchunks = p.Kpad / EV_BK;
     const long U = (long)p.mtiles * p.ntiles * nchunks;
     const int G = wpc * h->ncu;
     p.sk.ctrl = h->sk_ctrl; p.sk.flags = h->sk_ctrl + 16; p.sk.part = h->sk_part; p.sk.part_floats = EV_SK_PART_FLOATS;
     p.sk.q = (int)(U / G); p.sk.r = (int)(U % G); p.sk.spin_limit = h->sk_spin;
-    if (wtab) {            // weighted positions (stacked layers): a unit of M tile mt weighs its tap count
-        int wsum = 0;
-        for (int t = 0; t < p.mtiles; ++t) wsum += (int)((wtab >> (4 * t)) & 15ull);
-        const long P = (long)p.ntiles * nchunks * wsum;
-        p.sk.wsum = wsum; p.sk.wtab = wtab; p.sk.mtiles = p.mtiles; p.sk.nchunks = nchunks;
-        p.sk.q = (int)(P / G); p.sk.r = (int)(P % G);
-    }
     const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * 36;
     constexpr size_t es = (size_t)4 * 32 * (BM / WM + 4);
     size_t smem = (xs > es ? xs : es) * sizeof(float);
@@ -691,42 +673,13 @@ int launch_h16_bal(ev_handle* h, ConvParams p, const LaunchOpts& lo, int wpc) {
     const int G = wpc * h->ncu;
     p.sk.ctrl = h->sk_ctrl; p.sk.flags = h->sk_ctrl + 16; p.sk.part = h->sk_part; p.sk.part_floats = EV_SK_PART_FLOATS;
     p.sk.q = (int)(U / G); p.sk.r = (int)(U % G); p.sk.spin_limit = h->sk_spin;
-    if (h->sk_steal) { p.sk.claims = h->sk_ctrl + 16 + EV_SK_MAXWG; p.sk.seq = ++h->sk_seq; }
-    constexpr int NW = WM * WN;                         // 4 waves: two workgroups per CU; 8 waves (256 x 128 tiles): one
+    p.sk.claims = h->sk_ctrl + 16 + EV_SK_MAXWG; p.sk.seq = ++h->sk_seq;
     const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * EVH_RSB;
-    constexpr size_t es = (size_t)NW * 32 * (BM / WM + 4) * sizeof(float);
+    constexpr size_t es = (size_t)4 * 32 * (BM / WM + 4) * sizeof(float);
     size_t smem = xs > es ? xs : es;
     p.sk.lds_word = (int)smem;
-    smem += 16 + 3 * NW * sizeof(float) + 16;           // the wait word + three sets of the waves' maxima
-    static_assert((size_t)BM * BN <= 2 * EV_SK_PART_FLOATS, "hand-off slot");
-    if ((size_t)BM * BN > EV_SK_PART_FLOATS) {          // 256 x 128 tiles: slots twice as large, half as many workgroups (the area is sized for 1024 x 2 x 64 KB)
-        if ((size_t)G * 2 > EV_SK_MAXWG) return fail(h, "launch_h16_bal: %d workgroups of 256 x 128 tiles exceed the hand-off area", G);
-        p.sk.part_floats = (int)((size_t)BM * BN);
-    }
-    static const char* stamp_file = getenv("EV_BAL_STAMPS");         // diagnostic: phase stamps of a few workgroups, once per layer shape
-    static std::vector<long> stamped;
-    const long sig = ((long)p.nrows << 24) ^ ((long)p.Kpad << 12) ^ p.Mpad ^ ((long)p.ntaps << 40);
-    unsigned long long* d = nullptr;
-    if (stamp_file && *stamp_file && stamped.size() < 8 && std::find(stamped.begin(), stamped.end(), sig) == stamped.end()) {
-        stamped.push_back(sig);
-        HIPCHK(h, hipMalloc((void**)&d, (size_t)G * 16 * sizeof(unsigned long long)));
-        HIPCHK(h, hipMemsetAsync(d, 0, (size_t)G * 16 * sizeof(unsigned long long), h->stream));
-        p.stamps = d;
-    }
-    {   // A/B: start stagger of the second workgroup of every CU, in steps of ~1 us (conv_h16_bal_kernel)
-        static const int stag = getenv("EV_BAL_STAGGER") ? atoi(getenv("EV_BAL_STAGGER")) : 0;
-        p.stagger_slots = (wpc == 2) ? stag : 0;
-    }
-    if constexpr (NW == 8) {                            // passes of 32 rows: 5 cover a 3-tap layer's tile, 6 the widest halo
-        const bool narrow8 = BN + p.halo_lo + p.halo_hi <= 32 * 5;
-        if (lean_acc(p)) {
-            if (narrow8) { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 3, 5>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 3, 5>), dim3(G), dim3(512), smem, h->stream, p); }
-            else { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 3, 6>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 3, 6>), dim3(G), dim3(512), smem, h->stream, p); }
-        } else {
-            if (narrow8) { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 1, 5>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 1, 5>), dim3(G), dim3(512), smem, h->stream, p); }
-            else { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 1, 6>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 1, 6>), dim3(G), dim3(512), smem, h->stream, p); }
-        }
-    } else {
+    smem += 16 + 3 * 4 * sizeof(float) + 16;            // the wait word + three sets of the waves' maxima
+    static_assert((size_t)BM * BN <= EV_SK_PART_FLOATS, "hand-off slot");
     const bool narrow = BN + p.halo_lo + p.halo_hi <= 16 * 9;         // a 3-tap layer: nine staging passes instead of twelve
     if (lean_acc(p)) {
         if (narrow) { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 3, 9>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 3, 9>), dim3(G), dim3(256), smem, h->stream, p); }
@@ -735,52 +688,29 @@ int launch_h16_bal(ev_handle* h, ConvParams p, const LaunchOpts& lo, int wpc) {
         if (narrow) { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 1, 9>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 1, 9>), dim3(G), dim3(256), smem, h->stream, p); }
         else { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 1>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 1>), dim3(G), dim3(256), smem, h->stream, p); }
     }
-    }
-    if (d) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::vector<unsigned long long> st((size_t)G * 16);
-        HIPCHK(h, hipMemcpy(st.data(), d, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        hipFree(d);
-        if (FILE* f = fopen(stamp_file, "a")) {
-            unsigned long long t0 = ~0ull, t1 = 0;
-            for (int w = 0; w < G; ++w) for (int k = 0; k < 16; ++k) if (st[(size_t)w * 16 + k]) { t0 = std::min(t0, st[(size_t)w * 16 + k]); t1 = std::max(t1, st[(size_t)w * 16 + k]); }
-            fprintf(f, "## conv_h16_bal_kernel rows=%d Kpad=%d Mpad=%d taps=%d: %d workgroups, %ld units (q=%d r=%d), first stamp -> last %.2f us; per workgroup: start offset | us between consecutive stamps (per pass: pre-scan | per chunk: staged, MFMAs | partial stored or contributors added, epilogue | end)\n",
-                    p.nrows, p.Kpad, p.Mpad, p.ntaps, G, U, p.sk.q, p.sk.r, (double)(t1 - t0) / 100.0);
-            for (int w : {0, 1, 2, 3, 100, 101, 255, 256, 511}) {
-                if (w >= G || !st[(size_t)w * 16]) continue;
-                fprintf(f, "  wg %3d: +%.2f |", w, (double)(st[(size_t)w * 16] - t0) / 100.0);
-                for (int k = 1; k < 16 && st[(size_t)w * 16 + k]; ++k) fprintf(f, " %.2f", (double)(st[(size_t)w * 16 + k] - st[(size_t)w * 16 + k - 1]) / 100.0);
-                fprintf(f, "\n");
-            }
-            fclose(f);
-        }
-    }
     return 0;
 }
 inline bool split_bal_ok(const ev_handle* h, const ConvLayer& L, const ConvParams& p, long nwg, int wpc) {
-    static const bool off = getenv("EV_NO_CONV_BALANCE") != nullptr;
-    return !off && h->sk_balance && h->ncu > 0 && split_ok(L, p) && p.act != ACT_SNAKE && !p.dbg && !p.stamps && !p.gn_part &&
+    return h->sk_balance && h->ncu > 0 && split_ok(L, p) && p.act != ACT_SNAKE && !p.dbg && !p.stamps && !p.gn_part &&
            nwg * 2 >= h->ncu && wpc * h->ncu <= EV_SK_MAXWG && (long)nwg * (p.Kpad / EVX_KC) >= (long)wpc * h->ncu;
 }
 // A conv launch takes the balanced build when it is dense (every tap in every M tile: equal units), has a lean non-transcendental
 // epilogue, fills at least one tile per CU and at most a few rounds (deep grids balance by themselves), and the tile's accumulators fit
 // a hand-off slot.
 inline bool bal_ok(const ev_handle* h, const ConvLayer& L, const ConvParams& p, long nwg, int wpc) {
-    static const bool off = getenv("EV_NO_CONV_BALANCE") != nullptr;
-    // stacked layers (M tiles of unequal cost) keep one tile per workgroup unless EV_CONV_BALANCE_W=1: measured at batch 64
-    // (tools/shape_profile.py) the weighted balanced grid is 3 % SLOWER on them (256 -> 512: 3.13 -> 3.24 ms, 512 -> 512: 1.88 -> 1.94):
-    // 2080 tiles of mixed weight already even out over the CUs, the hand-offs do not pay
-    static const bool no_w = getenv("EV_CONV_BALANCE_W") == nullptr;
-    if (L.sparse_taps) {   // M tiles of unequal cost: weighted units (64-channel tiling only), every tile with at least one tap
-        if (no_w || p.mtiles > 16 || !L.nact[1]) return false;
-        long wsum = 0;
-        for (int t = 0; t < p.mtiles; ++t) { if (L.nact64[t] < 1) return false; wsum += L.nact64[t]; }
-        if ((nwg / p.mtiles) * (p.Kpad / EV_BK) * wsum < 16L * wpc * h->ncu) return false;   // every workgroup several units (none empty)
-    }
-    return !off && h->sk_balance && h->ncu > 0 && lean_ok(p) && p.act != ACT_SNAKE && !p.dbg && !p.stamps && !p.gn_part &&
+    // stacked layers (M tiles of unequal cost) keep one tile per workgroup: measured at batch 64 (tools/shape_profile.py) a balanced grid
+    // of units weighted by their taps was 3 % SLOWER on them (256 -> 512: 3.13 -> 3.24 ms, 512 -> 512: 1.88 -> 1.94): 2080 tiles of mixed
+    // weight already even out over the CUs, the hand-offs do not pay
+    if (L.sparse_taps) return false;
+    return h->sk_balance && h->ncu > 0 && lean_ok(p) && p.act != ACT_SNAKE && !p.dbg && !p.stamps && !p.gn_part &&
            nwg >= h->ncu && nwg < 4L * wpc * h->ncu && wpc * h->ncu <= EV_SK_MAXWG && (long)nwg * (p.Kpad / EV_BK) >= (long)wpc * h->ncu;
 }
 
+// The tile configurations launch_conv selects (cfg 47 / 56 / 66 are what 41 / 6 / 60 become on their launch), the only ones a forced cfg may name
+inline bool forceable_cfg(int cfg) {
+    for (int c : {0, 1, 2, 5, 6, 8, 9, 19, 40, 41, 43, 46, 49, 60}) if (cfg == c) return true;
+    return false;
+}
 constexpr int EV_GN_MAXTILES = 256;    // 32-row tiles of a launch that may leave GroupNorm statistics (EstBufs::GNP)
 int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float* Y, int ldy, const Geom& g, const Epi& e) {
     ConvParams p;
@@ -851,24 +781,14 @@ int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float
     if (cfg == 1 && L.Cout % 128 == 0 && !L.sparse_taps && (long)(L.Cout / 64) * ((g.nrows + 127) / 128) >= 256L * 4 * 6)
         cfg = (L.Cin > 128 && L.ntaps >= 7) ? 5 : 0;
     // launches far below one workgroup per CU with a K loop worth splitting: the 16-wave split-K build (batch-1 decodes)
-    {
-        static const bool no_sk = getenv("EV_NO_SK") != nullptr;
+    if (h->small_sk) {
         const long wg64 = (long)((L.Cout + 63) / 64) * ((g.nrows + 63) / 64);
-        if (!no_sk && (cfg == 6 || cfg == 8) && wg64 <= 192 && (L.Kpad / EV_BK) * L.ntaps >= 8) cfg = 9;
+        if ((cfg == 6 || cfg == 8) && wg64 <= 192 && (L.Kpad / EV_BK) * L.ntaps >= 8) cfg = 9;
         // (a short K loop gains nothing from the split, but the 32 x 32 build for it is the instruction-lean conv_sk32_kernel)
-        if (!no_sk && (cfg == 6 || cfg == 8) && wg64 <= 96 && L.Kpad == 128 && L.Cin == 128 && !L.sparse_taps) cfg = 9;
-        // ... as 32 x 32 tiles on four times as many CUs (EV_SK32_MAX, A/B: 96 while the build held one workgroup per CU; since
-        // conv_sk32_kernel fits two — 119 VGPRs — launches of up to 512 such tiles are still one round: 192; config-5 mean -1.9 %, p99 -4.5 %)
-        static const int sk32_max = getenv("EV_SK32_MAX") ? atoi(getenv("EV_SK32_MAX")) : 192;
-        if (cfg == 9 && wg64 <= sk32_max && L.Cout >= 32) cfg = 19;
-    }
-    {   // A/B override for the stacked sparse-tap layers only (a 3-tap conv over a 1x1 conv): EV_SPARSE_CFG=<cfg>[,<min rows>]
-        static const char* senv = getenv("EV_SPARSE_CFG");
-        if (senv && *senv && L.sparse_taps && L.Cout > 32) {
-            int c = atoi(senv), minrows = 0;
-            if (const char* comma = strchr(senv, ',')) minrows = atoi(comma + 1);
-            if (g.nrows >= minrows) cfg = c;
-        }
+        if ((cfg == 6 || cfg == 8) && wg64 <= 96 && L.Kpad == 128 && L.Cin == 128 && !L.sparse_taps) cfg = 9;
+        // ... as 32 x 32 tiles on four times as many CUs (up to 96 while the build held one workgroup per CU; since conv_sk32_kernel fits
+        // two — 119 VGPRs — launches of up to 512 such tiles are still one round: 192; config-5 mean -1.9 %, p99 -4.5 %)
+        if (cfg == 9 && wg64 <= 192 && L.Cout >= 32) cfg = 19;
     }
     {   // deep grids of dense-channel layers: the bf16-split build (EV_SPLIT=0: fp32 MFMA everywhere; 3 / 9: products per element pair, A/B)
         const int split_terms = h->split_terms;
@@ -884,18 +804,13 @@ int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float
         // launches of a few rounds (the U-Net convs of a large-batch decode): the balanced persistent grid of the split build
         else if ((split_terms == 6 || split_terms == 16) && (cfg == 1 || cfg == 5 || cfg == 6 || cfg == 0) && L.Cout == L.Mpad && split_bal_ok(h, L, p, nwg128, 2)) cfg = 60;
     }
-    {   // debugging / test override: EV_FORCE_CFG=<0..3> forces one tile configuration for every conv launch
-        static const char* env = getenv("EV_FORCE_CFG");
-        if (env && *env) cfg = atoi(env);
-    }
     LaunchOpts lo;
-    lo.device = h->device;
-    {   // A/B override: EV_KB=<1|2> forces the k-chunks per stage of every conv launch
-        static const char* kenv = getenv("EV_KB");
-        if (kenv && *kenv) lo.kb = atoi(kenv) == 2 ? 2 : 1;
-    }
-    if (e.force_cfg >= 0) { cfg = e.force_cfg % 100; lo.wgs_per_cu = (e.force_cfg / 100) % 10; lo.kb = e.force_cfg >= 1000 ? 2 : 1; }
-    lo.halo = L.halo_lo + L.halo_hi;
+    lo.device = h->device; lo.lean = h->lean; lo.halo = L.halo_lo + L.halo_hi;
+    // debugging / test overrides: EV_FORCE_CFG=<cfg> (every launch of the handle), ev_dbg_conv_bench's cfg = <cfg> + 100 x <workgroups per CU>
+    if (h->force_cfg >= 0) cfg = h->force_cfg;
+    if (e.force_cfg >= 0) { cfg = e.force_cfg < 1000 ? e.force_cfg % 100 : -1; lo.wgs_per_cu = (e.force_cfg / 100) % 10; }
+    if ((h->force_cfg >= 0 || e.force_cfg >= 0) && !forceable_cfg(cfg))
+        return fail(h, "launch_conv: forced tile configuration %d is not one launch_conv selects", e.force_cfg >= 0 ? e.force_cfg : h->force_cfg);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->prof) {
         if (h->ev_used + 2 > h->ev_pool.size()) {
@@ -905,20 +820,18 @@ int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float
         HIPCHK(h, hipEventRecord(e0, h->stream));
     }
     {   // start stagger (see conv_gemm_kernel): only worth it when the grid is several rounds deep
-        const int slots = cfg == 0 ? 3 : ((cfg == 1 || cfg == 5 || cfg == 7) ? 4 : ((cfg == 6 || cfg == 8) ? 5 : 3));
-        const long wgs = (cfg == 5 || cfg == 7) ? (long)((L.Cout + 63) / 64) * ((g.nrows + 191) / 192) : (cfg == 6 || cfg == 8) ? (long)((L.Cout + 63) / 64) * ((g.nrows + 63) / 64) : cfg == 0 ? (long)(L.Mpad / 128) * ((g.nrows + 127) / 128) : (cfg == 1 ? (long)((L.Cout + 63) / 64) * ((g.nrows + 127) / 128) : (long)((L.Cout + 31) / 32) * ((g.nrows + 255) / 256));
+        const int slots = cfg == 0 ? 3 : ((cfg == 1 || cfg == 5) ? 4 : ((cfg == 6 || cfg == 8) ? 5 : 3));
+        const long wgs = cfg == 5 ? (long)((L.Cout + 63) / 64) * ((g.nrows + 191) / 192) : (cfg == 6 || cfg == 8) ? (long)((L.Cout + 63) / 64) * ((g.nrows + 63) / 64) : cfg == 0 ? (long)(L.Mpad / 128) * ((g.nrows + 127) / 128) : (cfg == 1 ? (long)((L.Cout + 63) / 64) * ((g.nrows + 127) / 128) : (long)((L.Cout + 31) / 32) * ((g.nrows + 255) / 256));
         p.stagger_slots = (wgs >= 256L * slots * 3 && cfg < 10) ? slots : 0;
         if (e.stagger >= 0) p.stagger_slots = e.stagger;
-        static const char* senv = getenv("EV_STAGGER");
-        if (senv && *senv) p.stagger_slots = atoi(senv) ? p.stagger_slots : 0;
     }
     if ((cfg == 40 || cfg == 41 || cfg == 43 || cfg == 46 || cfg == 49 || cfg == 60) && !split_ok(L, p)) cfg = 0;
     if (cfg == 46 && !L.Wh) cfg = 40;
     {   // which builds leave bounds of their output: the fp16 builds 46 / 47 (cfg 41 becomes 47 below when the layer has fp16 pieces) and the
         // fp32 conv_gemm_kernel tiles with the lean non-SnakeBeta epilogues; a residual without slots of its own cannot be bounded
-        const bool lean1or3 = lean_ok(p) && p.act != ACT_SNAKE && !getenv("EV_NO_LEAN");
+        const bool lean1or3 = lean_ok(p) && p.act != ACT_SNAKE && h->lean;
         const bool h16 = (cfg == 46) || (cfg == 41 && h->split_terms == 16 && L.Wh);
-        const bool gemm = (cfg == 0 || cfg == 1 || cfg == 5 || cfg == 6) && lean1or3 && lo.kb == 1;
+        const bool gemm = (cfg == 0 || cfg == 1 || cfg == 5 || cfg == 6) && lean1or3;
         const bool no_amax = !h->use_amax;                                          // A/B: every fp16 tile pre-scans
         if (!no_amax && e.ymax && lean1or3 && (h16 || gemm) && (!e.R || e.rmax) && (!e.accum || e.yold)) { p.ymax = e.ymax; h->amax_emitted = true; }
         if (no_amax) p.xmax = nullptr;
@@ -934,22 +847,8 @@ int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float
     } else
     if (cfg == 60) {   // 128 x 128 on the bf16 pipe, balanced persistent grid
         p.mtiles = L.Mpad / 128; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[0]; p.nact_tab = L.nact[0]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        static const int bal_wgs = getenv("EV_SPLIT_BAL_WGS") ? atoi(getenv("EV_SPLIT_BAL_WGS")) : 2;    // A/B: persistent workgroups per CU (1 or 2)
-        // EV_BAL_WIDE=1 (A/B, measured null — not the default): layers of 256-channel multiples as ONE eight-wave workgroup per CU on 256 x 128
-        // tiles, so that the X tile is staged once for both halves of the output channels instead of by two lockstep workgroups.  Same box, batch 64:
-        // 256 -> 256 k3 2.585 -> 2.766 ms (T), 2.254 -> 2.426 ms (T / 2), 512 -> 512 1.447 -> 1.415 ms; decode 25.9 -> 26.5 ms (gpurun_out/s22).
-        // Halving the bytes of the burst a chunk begins with does not shorten the chunk: what the two workgroups of a CU wait for in lockstep
-        // is latency, and eight waves meet at every barrier instead of four.
-        static const bool use_wide = getenv("EV_BAL_WIDE") && atoi(getenv("EV_BAL_WIDE")) != 0;
-        bool wide = use_wide && h->split_terms == 16 && L.Wh && L.Mpad % 256 == 0 && L.Cout == L.Mpad && bal_wgs != 1;
-        wide = wide && L.pair256_uniform;
-        if (wide) {
-            p.mtiles = L.Mpad / 256; p.mt_mul = 2;
-            if (launch_h16_bal<256, 128, 4, 2>(h, p, lo, 1)) return 1;
-            cfg = 68;
-        } else
-        if (h->split_terms == 16 && L.Wh) { if (launch_h16_bal<128, 128, 2, 2>(h, p, lo, bal_wgs == 1 ? 1 : 2)) return 1; cfg = 66; }
-        else if (launch_split_bal<128, 128, 2, 2>(h, p, lo, bal_wgs == 1 ? 1 : 2)) return 1;
+        if (h->split_terms == 16 && L.Wh) { if (launch_h16_bal<128, 128, 2, 2>(h, p, lo, 2)) return 1; cfg = 66; }
+        else if (launch_split_bal<128, 128, 2, 2>(h, p, lo, 2)) return 1;
     } else
     if (cfg == 40 || cfg == 43 || cfg == 49) {   // 128 x 128 on the bf16 pipe
         p.mtiles = L.Mpad / 128; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[0]; p.nact_tab = L.nact[0]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
@@ -964,17 +863,7 @@ int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float
         launch_cfg<64, 128, 2, 2>(p, h->stream, lo);
     } else if (cfg == 5) {
         p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 191) / 192; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        static const int bal5 = getenv("EV_BAL5") ? atoi(getenv("EV_BAL5")) : 0;      // A/B: 0 = as is, 192 = balanced 64 x 192, 64 = balanced 64 x 64
-        if (bal5 != 0) { p.ymax = nullptr; h->amax_emitted = false; }
-        if (bal5 == 192 && lo.kb == 1 && bal_ok(h, L, p, (long)p.mtiles * p.ntiles, 3)) { if (launch_bal<64, 192, 2, 2>(h, p, lo, 3)) return 1; cfg = 55; }
-        else if (bal5 == 64 && lo.kb == 1 && bal_ok(h, L, p, (long)((L.Cout + 63) / 64) * ((g.nrows + 63) / 64), 4)) {
-            p.ntiles = (g.nrows + 63) / 64;
-            if (launch_bal<64, 64, 2, 2>(h, p, lo, 4)) return 1;
-            cfg = 56;
-        } else launch_cfg<64, 192, 2, 2>(p, h->stream, lo);
-    } else if (cfg == 7) {   // 64 x 192 with register-prefetched X staging
-        p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 191) / 192; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_cfg<64, 192, 2, 2, true>(p, h->stream, lo);
+        launch_cfg<64, 192, 2, 2>(p, h->stream, lo);
     } else if (cfg == 8) {   // 64 x 64 with register-prefetched X staging
         p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 63) / 64; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
         launch_cfg<64, 64, 2, 2, true>(p, h->stream, lo);
@@ -983,11 +872,9 @@ int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float
         launch_sk<4>(p, h->stream, lo);
     } else if (cfg == 19) {  // 32 x 32 tiles, 8 waves, split-K eight ways
         p.mtiles = (L.Cout + 31) / 32; p.ntiles = (g.nrows + 31) / 32; p.taplist = L.taplist[2]; p.nact_tab = L.nact[2]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        static const bool no_sk32_lean = getenv("EV_NO_SK32_LEAN") != nullptr;
-        static const bool no_lean = getenv("EV_NO_LEAN") != nullptr;
         const int xr = 32 + p.halo_lo + p.halo_hi;
         // conv_sk32_kernel's preconditions (everything else: the general small-launch build)
-        const bool fast = !no_sk32_lean && !no_lean && lean_ok(p) && (p.ktaps_n > 0 || p.kstack_mt > 0) && p.isplit_log2 >= 31 && !p.pro_lrelu && p.Cin == p.Kpad &&
+        const bool fast = h->sk32_lean && h->lean && lean_ok(p) && (p.ktaps_n > 0 || p.kstack_mt > 0) && p.isplit_log2 >= 31 && !p.pro_lrelu && p.Cin == p.Kpad &&
                           (p.Kpad == 128 || p.Kpad == 256 || p.Kpad == 512 || p.Kpad == 1024) && (ldx % 4) == 0 && xr <= 16 * (512 / (p.Kpad / 4)) && (size_t)g.nrows * ldx * 4 < ((size_t)1 << 31) &&
                           (size_t)xr * (p.Kpad + 4) * 4 <= 150 * 1024;
         if (fast) {
@@ -995,8 +882,7 @@ int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float
             const dim3 grid(p.mtiles, p.ntiles);
             // GroupNorm statistics of the output for the layer that follows: one utterance, the tile stored as accumulated, one
             // 32-channel group per M tile over the (first) 256 output channels
-            static const bool no_gn_stats = getenv("EV_NO_GN_STATS") != nullptr;
-            if (!no_gn_stats && e.gn_part && g.nrows == g.S && p.ntiles <= EV_GN_MAXTILES && p.act == ACT_NONE && !p.R && !lean_acc(p) && !p.mask1 && !p.mask2 &&
+            if (h->gn_stats && e.gn_part && g.nrows == g.S && p.ntiles <= EV_GN_MAXTILES && p.act == ACT_NONE && !p.R && !lean_acc(p) && !p.mask1 && !p.mask2 &&
                 (p.kstack_mt == 8 || (p.kstack_mt == 0 && L.Cout == 256))) {
                 p.gn_part = e.gn_part;
                 h->gn_stats_tiles = p.ntiles;
@@ -1007,33 +893,13 @@ int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float
         } else launch_sk<1>(p, h->stream, lo);
     } else if (cfg == 6) {
         p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 63) / 64; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        if (lo.kb == 1 && bal_ok(h, L, p, (long)p.mtiles * p.ntiles, 4)) {
+        if (bal_ok(h, L, p, (long)p.mtiles * p.ntiles, 4)) {
             p.ymax = nullptr; h->amax_emitted = false;          // (the balanced build leaves no bounds)
-            unsigned long long wtab = 0;
-            if (L.sparse_taps) for (int t = 0; t < p.mtiles; ++t) wtab |= (unsigned long long)L.nact64[t] << (4 * t);
-            if (launch_bal<64, 64, 2, 2>(h, p, lo, 4, wtab)) return 1;
-            cfg = L.sparse_taps ? 57 : 56;
+            if (launch_bal<64, 64, 2, 2>(h, p, lo, 4)) return 1;
+            cfg = 56;
         }
         else launch_cfg<64, 64, 2, 2>(p, h->stream, lo);
-    } else if (cfg == 10 && !L.sparse_taps && L.Mpad % 128 == 0) {   // 128 x 192: less halo per MFMA for the wide-halo layers at Cout = 128
-        p.mtiles = L.Mpad / 128; p.ntiles = (g.nrows + 191) / 192; p.taplist = L.taplist[0]; p.nact_tab = L.nact[0]; p.tl_stride = 0;
-        launch_cfg<128, 192, 2, 2>(p, h->stream, lo);
-    } else if (cfg == 20 && L.Mpad % 128 == 0) {   // 128 x 128 with the next chunk's X tile prefetched through registers
-        p.mtiles = L.Mpad / 128; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[0]; p.nact_tab = L.nact[0]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_cfg<128, 128, 2, 2, true>(p, h->stream, lo);
-    } else if (cfg == 13 && !L.sparse_taps && L.Mpad % 128 == 0) {   // 128 x 128 as 4 x 1 waves: a wave owns 32 channels x 128 frames, so a
-        p.mtiles = L.Mpad / 128; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[0]; p.nact_tab = L.nact[0]; p.tl_stride = 0;   // weight fragment feeds 16 MFMAs (half the L2 stream of 2 x 2)
-        launch_cfg<128, 128, 4, 1>(p, h->stream, lo);
-    } else if (cfg == 14) {   // 64 x 256 as 2 x 2 waves: 32 channels x 128 frames per wave
-        p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 255) / 256; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_cfg<64, 256, 2, 2>(p, h->stream, lo);
-    } else if (cfg == 12 && !L.sparse_taps && L.Mpad % 256 == 0) {   // 256 x 64: every output channel of a 256-wide layer from one X tile
-        p.mtiles = L.Mpad / 256; p.ntiles = (g.nrows + 63) / 64; p.taplist = L.taplist[0]; p.nact_tab = nullptr; p.tl_stride = 0;
-        launch_cfg<256, 64, 4, 1>(p, h->stream, lo);
-    } else if (cfg == 4) {   // 64 x 128 tile with register-prefetched X staging (single-round launches)
-        p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_cfg<64, 128, 2, 2, true>(p, h->stream, lo);
-    } else {
+    } else {   // cfg 2
         p.mtiles = (L.Cout + 31) / 32; p.ntiles = (g.nrows + 255) / 256; p.taplist = L.taplist[2]; p.nact_tab = L.nact[2]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
         launch_cfg<32, 256, 1, 4>(p, h->stream, lo);
     }
@@ -1061,7 +927,7 @@ int launch_pair(ev_handle* h, const ConvLayer& L1, const ConvLayer& L2, const fl
     p.ntaps = L2.ntaps; p.taplist = L2.taplist[0]; p.tl_stride = 0; p.nact_tab = nullptr;
     p.pro_lrelu = 1; p.pro_slope = 0.1f;
     p.scale = 1.f; p.R = X; p.ldr = C; p.accum = e.accum; p.div3 = e.div3; p.act2_lrelu = e.act2_lrelu; p.act2_slope = e.act2_slope;
-    pp.W1 = L1.W; pp.W1x = L1.Wx; p.Wx = L2.Wx; pp.W1h = L1.Wh; pp.w1h_scale = L1.wh_scale; p.Wh = L2.Wh; p.wh_scale = L2.wh_scale; pp.W1q = L1.Wq; p.Wq = L2.Wq; pp.b1 = L1.bias; pp.taplist1 = L1.taplist[0]; pp.ntaps1 = L1.ntaps;
+    pp.W1 = L1.W; pp.W1x = L1.Wx; p.Wx = L2.Wx; pp.W1h = L1.Wh; pp.w1h_scale = L1.wh_scale; p.Wh = L2.Wh; p.wh_scale = L2.wh_scale; pp.b1 = L1.bias; pp.taplist1 = L1.taplist[0]; pp.ntaps1 = L1.ntaps;
     pp.h1 = L1.halo_lo; pp.h2 = L2.halo_lo; pp.mid_slope = 0.1f;
     p.rmax = nullptr; p.yold = e.yold; p.ymax_mul = 1; h->amax_emitted = false;   // (R = X: the fp16 pair kernels bound the residual by their own tile maximum; p.ymax below)
     if ((double)g.nrows * C * 4.0 >= 4294967296.0) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
@@ -1076,8 +942,7 @@ int launch_pair(ev_handle* h, const ConvLayer& L1, const ConvLayer& L2, const fl
         e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
         HIPCHK(h, hipEventRecord(e0, h->stream));
     }
-    static const bool no_lean = getenv("EV_NO_LEAN") != nullptr;
-    const int lean = no_lean ? 0 : ((e.accum || e.div3 || e.act2_lrelu) ? 3 : 1);
+    const int lean = !h->lean ? 0 : ((e.accum || e.div3 || e.act2_lrelu) ? 3 : 1);
     const int split_terms = h->split_terms;
     const bool split = split_terms > 0 && lean != 0 && L1.Wx && L2.Wx && !(e.force_cfg == 0);
     const bool h16 = split && split_terms == 16 && L1.Wh && L2.Wh;
@@ -1088,16 +953,10 @@ int launch_pair(ev_handle* h, const ConvLayer& L1, const ConvLayer& L2, const fl
         pp.out_rows = NT - 2 * pp.h2; p.mtiles = 1; p.ntiles = (g.nrows + pp.out_rows - 1) / pp.out_rows;
         const size_t smem = std::max((size_t)(NT + EV_HALO) * RSB + 64, (size_t)4 * 32 * 36 * sizeof(float));   // (+ 16 floats: the waves' maxima)
         const dim3 grid(p.ntiles);
-        // EV_PAIR_Q=1: both K loops on v_mfma_f32_16x16x32_f16 (resblock_pair_h16q_kernel).  Measured null, not the default: same box, config 2 —
-        // every pair shape within 1 % of the 32 x 32 x 16 form (C = 128 k3 3 % slower: 150 registers admit three workgroups per CU instead of four),
-        // while conv_h16_kernel gains 3-9 % from the same change (profiles/r04_mfma_shape_ab.txt): the pairs' K loops are too short (C <= 128 deep)
-        // for the MFMA phase to be what the power limit throttles.
-        static const bool use_q = getenv("EV_PAIR_Q") && atoi(getenv("EV_PAIR_Q")) != 0;
-        const bool q = use_q && L1.Wq && L2.Wq;
+        // (both K loops on v_mfma_f32_16x16x32_f16 were measured null on the pairs, unlike conv_h16_kernel's 3-9 %, profiles/r04_mfma_shape_ab.txt:
+        // their K loops are too short — C <= 128 deep — for the MFMA phase to be what the power limit throttles)
 #define EV_PAIR_H16(WM, WN) do { \
-            if (q && lean == 1) { ensure_dyn_smem<resblock_pair_h16q_kernel<WM, WN, 1>>(smem, h->device); hipLaunchKernelGGL((resblock_pair_h16q_kernel<WM, WN, 1>), grid, dim3(256), smem, h->stream, pp); } \
-            else if (q) { ensure_dyn_smem<resblock_pair_h16q_kernel<WM, WN, 3>>(smem, h->device); hipLaunchKernelGGL((resblock_pair_h16q_kernel<WM, WN, 3>), grid, dim3(256), smem, h->stream, pp); } \
-            else if (lean == 1) { ensure_dyn_smem<resblock_pair_h16_kernel<WM, WN, 1>>(smem, h->device); hipLaunchKernelGGL((resblock_pair_h16_kernel<WM, WN, 1>), grid, dim3(256), smem, h->stream, pp); } \
+            if (lean == 1) { ensure_dyn_smem<resblock_pair_h16_kernel<WM, WN, 1>>(smem, h->device); hipLaunchKernelGGL((resblock_pair_h16_kernel<WM, WN, 1>), grid, dim3(256), smem, h->stream, pp); } \
             else { ensure_dyn_smem<resblock_pair_h16_kernel<WM, WN, 3>>(smem, h->device); hipLaunchKernelGGL((resblock_pair_h16_kernel<WM, WN, 3>), grid, dim3(256), smem, h->stream, pp); } } while (0)
         if (C == 32) EV_PAIR_H16(1, 4); else if (C == 64) EV_PAIR_H16(2, 2); else EV_PAIR_H16(4, 1);
 #undef EV_PAIR_H16
@@ -1107,11 +966,7 @@ int launch_pair(ev_handle* h, const ConvLayer& L1, const ConvLayer& L2, const fl
         if (C != 32 && C != 64 && C != 128) return fail(h, "launch_pair: C must be 32, 64 or 128");
         pp.out_rows = NT - 2 * pp.h2; p.mtiles = 1; p.ntiles = (g.nrows + pp.out_rows - 1) / pp.out_rows;
         const size_t xs = (size_t)(NT + ((2 * pp.h1 + 7) & ~7)) * RSB, ys = (size_t)(NT + 16) * RSB, es = (size_t)4 * 32 * 36 * sizeof(float);
-        size_t smem = std::max(xs, std::max(ys, es));
-        {
-            static const int wpc = getenv("EV_SPLIT_WPC") ? atoi(getenv("EV_SPLIT_WPC")) : 0;
-            if (wpc > 0) smem = std::max(smem, (size_t)((160 * 1024 / (wpc + 1) + 1024) & ~255));
-        }
+        const size_t smem = std::max(xs, std::max(ys, es));
         const dim3 grid(p.ntiles);
 #define EV_PAIR_SPLIT_T(WM, WN, TT) do { \
             if (lean == 1) { ensure_dyn_smem<resblock_pair_split_kernel<WM, WN, 1, TT>>(smem, h->device); hipLaunchKernelGGL((resblock_pair_split_kernel<WM, WN, 1, TT>), grid, dim3(256), smem, h->stream, pp); } \
@@ -1162,12 +1017,10 @@ int launch_pair(ev_handle* h, const ConvLayer& L1, const ConvLayer& L2, const fl
 
 // A whole ResBlock1 — three (dilated conv, conv) pairs with their residual adds — in one launch (resblock_chain_h16_kernel): the narrow levels under
 // arithmetic setting 16, kernel sizes whose summed halos leave most of a tile to store.  chain_ok() is the gate; the caller falls back to three
-// launch_pair calls.  EV_NO_CHAIN=1 switches it off (A/B).
+// launch_pair calls.  ev_dbg_set_chain(h, 0) / EV_NO_CHAIN=1 switches it off (A/B).
 inline int chain_halo(const ConvLayer* L1, const ConvLayer* L2) { int hs = 0; for (int m = 0; m < 3; ++m) hs += L1[m].halo_lo + L2[m].halo_lo; return hs; }
 inline bool chain_ok(const ev_handle* h, const ConvLayer* L1, const ConvLayer* L2, int C) {
-    static const bool off = getenv("EV_NO_CHAIN") != nullptr;
-    static const int max_halo = getenv("EV_CHAIN_MAXHALO") ? atoi(getenv("EV_CHAIN_MAXHALO")) : 12;
-    if (off || !h->use_chain || h->split_terms != 16 || (C != 32 && C != 64)) return false;
+    if (!h->use_chain || h->split_terms != 16 || (C != 32 && C != 64)) return false;
     int hb = 0;
     for (int m = 0; m < 3; ++m) {
         const ConvLayer &a = L1[m], &b = L2[m];
@@ -1176,7 +1029,7 @@ inline bool chain_ok(const ev_handle* h, const ConvLayer* L1, const ConvLayer* L
         hb = std::max(hb, std::max(a.halo_lo, b.halo_lo));
     }
     const int NT = C == 32 ? 256 : 128, hs = chain_halo(L1, L2);
-    return hs <= max_halo && 2 * hb <= EV_HALO && NT - 2 * hs >= NT / 2;
+    return hs <= 12 && 2 * hb <= EV_HALO && NT - 2 * hs >= NT / 2;
 }
 int launch_chain(ev_handle* h, const ConvLayer* L1, const ConvLayer* L2, const float* X, float* Y, int C, const Geom& g, const Epi& e) {
     ChainParams cp;
@@ -1236,15 +1089,13 @@ int launch_chain(ev_handle* h, const ConvLayer* L1, const ConvLayer* L2, const f
 // The threshold is a measurement (tools/vocoder_configs_bench.py).
 inline int rb2_halo(const ConvLayer* L) { return L[0].halo_lo + L[1].halo_lo; }
 inline bool rb2_ok(const ev_handle* h, const ConvLayer* L, int C) {
-    static const bool off = getenv("EV_NO_CHAIN") != nullptr;
-    static const int keep8 = getenv("EV_RB2_MINKEEP") ? atoi(getenv("EV_RB2_MINKEEP")) : 4;
-    if (off || !h->use_chain || h->split_terms != 16 || (C != 32 && C != 64 && C != 128)) return false;
+    if (!h->use_chain || h->split_terms != 16 || (C != 32 && C != 64 && C != 128)) return false;
     for (int m = 0; m < 2; ++m) {
         const ConvLayer& a = L[m];
         if (!a.Wh || !a.bias || a.sparse_taps || a.Kpad != C || a.Mpad != L[0].Mpad || a.halo_lo != a.halo_hi || a.ntaps != L[0].ntaps || a.ntaps > 64) return false;
     }
     const int NT = C == 32 ? 256 : C == 64 ? 128 : 64;
-    return 8 * (NT - 2 * rb2_halo(L)) >= keep8 * NT && NT - 2 * rb2_halo(L) > 0;
+    return 8 * (NT - 2 * rb2_halo(L)) >= h->rb2_minkeep * NT && NT - 2 * rb2_halo(L) > 0;
 }
 int launch_rb2(ev_handle* h, const ConvLayer* L, const float* X, float* Y, int C, const Geom& g, const Epi& e) {
     Rb2Params cp;
@@ -1307,19 +1158,9 @@ int launch_gn(ev_handle* h, const float* X, int ldx, float* Y, int ldy, const fl
         hipLaunchKernelGGL(groupnorm_apply_kernel, dim3(h->gn_stats_tiles, 8), dim3(256), 0, h->stream, p, part, h->gn_stats_tiles);
     // small batches: 1024 threads per (utterance, group) shorten the per-workgroup latency chain (8 workgroups at B = 1)
     else if (g.nrows / g.S < 32) hipLaunchKernelGGL(groupnorm_mish_kernel<1024>, dim3(g.nrows / g.S, 8), dim3(1024), 0, h->stream, p);
-    else {
-        // 512 threads per (utterance, group) slab: the workgroup's serial chain (load, two reductions, apply) is half as long as
-        // with 256 (tools/decode_time.py, batch 64: 41.07 -> 40.60 ms per decode with 512, 40.94 with 1024); EV_GN_THREADS=<256|512|1024>
-        // for A/B runs
-        static const int gnt = getenv("EV_GN_THREADS") ? atoi(getenv("EV_GN_THREADS")) : 512;
-        // EV_GN_PRE=1: residual / mask rows requested together with the slab (one memory round trip less per workgroup) — measured
-        // SLOWER (40.8 -> 41.3 ms): 141 registers leave one 512-thread workgroup per CU where the plain build keeps two
-        static const bool gnpre = getenv("EV_GN_PRE") ? atoi(getenv("EV_GN_PRE")) != 0 : false;
-        if (gnt == 512 && gnpre) hipLaunchKernelGGL((groupnorm_mish_kernel<512, true>), dim3(g.nrows / g.S, 8), dim3(512), 0, h->stream, p);
-        else if (gnt == 512) hipLaunchKernelGGL(groupnorm_mish_kernel<512>, dim3(g.nrows / g.S, 8), dim3(512), 0, h->stream, p);
-        else if (gnt == 1024) hipLaunchKernelGGL(groupnorm_mish_kernel<1024>, dim3(g.nrows / g.S, 8), dim3(1024), 0, h->stream, p);
-        else hipLaunchKernelGGL(groupnorm_mish_kernel<256>, dim3(g.nrows / g.S, 8), dim3(256), 0, h->stream, p);
-    }
+    // 512 threads per (utterance, group) slab: the workgroup's serial chain (load, two reductions, apply) is half as long as
+    // with 256 (tools/decode_time.py, batch 64: 41.07 -> 40.60 ms per decode with 512, 40.94 with 1024)
+    else hipLaunchKernelGGL(groupnorm_mish_kernel<512>, dim3(g.nrows / g.S, 8), dim3(512), 0, h->stream, p);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -1365,9 +1206,8 @@ int launch_mlp(ev_handle* h, int mode, const float* X, const float* ln_g, const 
     const int nchunk = L1.Mpad / 128;
     {   // the feed-forward of a large batch on the bf16 pipe: 64-row tiles, one persistent workgroup per CU (ln_mlp_split_kernel)
         const int split_terms = h->split_terms;
-        static const bool no_mlp_split = getenv("EV_NO_MLP_SPLIT") != nullptr;
         const int nt64 = (g.nrows + 63) / 64;
-        if (mode == 0 && (split_terms == 6 || split_terms == 16) && !no_mlp_split && L1.Wx && L2->Wx && h->sk_balance && h->ncu > 0 && h->ncu <= EV_SK_MAXWG && nt64 >= h->ncu) {
+        if (mode == 0 && (split_terms == 6 || split_terms == 16) && L1.Wx && L2->Wx && h->sk_balance && h->ncu > 0 && h->ncu <= EV_SK_MAXWG && nt64 >= h->ncu) {
             if (ensure_sk(h)) return 1;
             const long U = (long)nt64 * nchunk;
             const int grid = h->ncu;
@@ -1376,7 +1216,7 @@ int launch_mlp(ev_handle* h, int mode, const float* X, const float* ln_g, const 
             mp.W1h = L1.Wh; mp.W2h = L2->Wh; mp.w1_scale = L1.wh_scale; mp.w2_scale = L2->wh_scale;
             mp.sk.q = (int)(U / grid); mp.sk.r = (int)(U % grid); mp.sk.spin_limit = h->sk_spin;
             mp.sk.ctrl = h->sk_ctrl; mp.sk.flags = h->sk_ctrl + 16; mp.sk.part = h->sk_part; mp.sk.part_floats = EV_SK_PART_FLOATS;
-            if (h16 && h->sk_steal) { mp.sk.claims = h->sk_ctrl + 16 + EV_SK_MAXWG; mp.sk.seq = ++h->sk_seq; }
+            if (h16) { mp.sk.claims = h->sk_ctrl + 16 + EV_SK_MAXWG; mp.sk.seq = ++h->sk_seq; }
             if (L1.Mpad > 1024) return fail(h, "launch_mlp: hidden width %d > 1024 (LDS table of the SnakeBeta vectors)", L1.Mpad);
             const size_t smem = h16 ? (size_t)64 * (4 * 256 + 16) + (size_t)64 * (4 * 128 + 16) + 16 + (size_t)2 * L1.Mpad * sizeof(float) + 64
                                     : (size_t)64 * (6 * 256 + 16) + (size_t)64 * (6 * 128 + 16) + 16 + (size_t)2 * L1.Mpad * sizeof(float);
@@ -1389,32 +1229,7 @@ int launch_mlp(ev_handle* h, int mode, const float* X, const float* ln_g, const 
                 HIPCHK(h, hipEventRecord(e0, h->stream));
             }
             if (h16) ensure_dyn_smem<ln_mlp_h16_kernel<0>>(smem, h->device); else ensure_dyn_smem<ln_mlp_split_kernel<6>>(smem, h->device);
-            static const char* stamp_file = getenv("EV_MLP_STAMPS");     // diagnostic: phase stamps of a few workgroups of the first launches
-            static int stamped = 0;
-            if (stamp_file && *stamp_file && stamped < 2) {
-                unsigned long long* d = nullptr;
-                HIPCHK(h, hipMalloc((void**)&d, (size_t)grid * 32 * sizeof(unsigned long long)));
-                HIPCHK(h, hipMemsetAsync(d, 0, (size_t)grid * 32 * sizeof(unsigned long long), h->stream));
-                mp.ep.stamps = d;
-                if (h16) hipLaunchKernelGGL((ln_mlp_h16_kernel<0>), dim3(grid), dim3(256), smem, h->stream, mp);
-                else hipLaunchKernelGGL((ln_mlp_split_kernel<6>), dim3(grid), dim3(256), smem, h->stream, mp);
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                std::vector<unsigned long long> st((size_t)grid * 32);
-                HIPCHK(h, hipMemcpy(st.data(), d, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                hipFree(d);
-                mp.ep.stamps = nullptr;
-                if (FILE* f = fopen(stamp_file, "a")) {
-                    fprintf(f, "## ln_mlp_split_kernel rows=%d: %d workgroups, q=%d r=%d; per workgroup: us between consecutive stamps (start | staged+LN | per chunk: phase 1 | phase 2 + SnakeBeta | planes written ...)\n", g.nrows, grid, mp.sk.q, mp.sk.r);
-                    for (int w : {0, 1, 100, 255}) {
-                        if (w >= grid) continue;
-                        fprintf(f, "  wg %3d:", w);
-                        for (int k = 1; k < 32 && st[(size_t)w * 32 + k]; ++k) fprintf(f, " %.2f", (double)(st[(size_t)w * 32 + k] - st[(size_t)w * 32 + k - 1]) / 100.0);
-                        fprintf(f, "\n");
-                    }
-                    fclose(f);
-                }
-                ++stamped;
-            } else if (h16) hipLaunchKernelGGL((ln_mlp_h16_kernel<0>), dim3(grid), dim3(256), smem, h->stream, mp);
+            if (h16) hipLaunchKernelGGL((ln_mlp_h16_kernel<0>), dim3(grid), dim3(256), smem, h->stream, mp);
             else hipLaunchKernelGGL((ln_mlp_split_kernel<6>), dim3(grid), dim3(256), smem, h->stream, mp);
             HIPCHK(h, hipGetLastError());
             if (h->prof) {
@@ -1429,9 +1244,8 @@ int launch_mlp(ev_handle* h, int mode, const float* X, const float* ln_g, const 
         }
     }
     {   // LayerNorm + QKV of a large batch on the fp16 pipe: one workgroup per 64-row tile (ln_qkv_h16_kernel)
-        static const bool no_qkv_h16 = getenv("EV_NO_QKV_H16") != nullptr;
         const int nt64 = (g.nrows + 63) / 64;
-        if (mode == 1 && h->split_terms == 16 && !no_qkv_h16 && L1.Wh && L1.Mpad == 384 && !R && !rowmask && h->ncu > 0 && nt64 >= h->ncu) {
+        if (mode == 1 && h->split_terms == 16 && h->qkv_h16 && L1.Wh && L1.Mpad == 384 && !R && !rowmask && h->ncu > 0 && nt64 >= h->ncu) {
             mp.W1h = L1.Wh; mp.w1_scale = L1.wh_scale; mp.ntiles = nt64;
             if (qkv_scale && qkv_packed && qkv_scale[0] > 0.f && qkv_scale[1] > 0.f && qkv_scale[2] > 0.f) {
                 mp.qkv_pack = 1; *qkv_packed = 1;
@@ -1446,35 +1260,8 @@ int launch_mlp(ev_handle* h, int mode, const float* X, const float* ln_g, const 
                 e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
                 HIPCHK(h, hipEventRecord(e0, h->stream));
             }
-            ensure_dyn_smem<ln_qkv_h16_kernel<0>>(smem, h->device); ensure_dyn_smem<ln_qkv_h16_kernel<1>>(smem, h->device);
-            static const int qdbg = getenv("EV_QKV_DBG") ? atoi(getenv("EV_QKV_DBG")) : 0;
-            static const char* stamp_file = getenv("EV_QKV_STAMPS");     // diagnostic: phase stamps of a few workgroups of the first launches
-            static int stamped = 0;
-            if (stamp_file && *stamp_file && stamped < 4) {
-                unsigned long long* d = nullptr;
-                HIPCHK(h, hipMalloc((void**)&d, (size_t)nt64 * 8 * sizeof(unsigned long long)));
-                HIPCHK(h, hipMemsetAsync(d, 0, (size_t)nt64 * 8 * sizeof(unsigned long long), h->stream));
-                mp.ep.stamps = d;
-                { if (qdbg == 1) hipLaunchKernelGGL(ln_qkv_h16_kernel<1>, dim3(nt64), dim3(256), smem, h->stream, mp); else hipLaunchKernelGGL(ln_qkv_h16_kernel<0>, dim3(nt64), dim3(256), smem, h->stream, mp); }
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                std::vector<unsigned long long> st((size_t)nt64 * 8);
-                HIPCHK(h, hipMemcpy(st.data(), d, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                hipFree(d);
-                mp.ep.stamps = nullptr;
-                if (FILE* f = fopen(stamp_file, "a")) {
-                    unsigned long long t0 = ~0ull, t1 = 0;
-                    for (int w = 0; w < nt64; ++w) if (st[(size_t)w * 8]) { t0 = std::min(t0, st[(size_t)w * 8]); t1 = std::max(t1, st[(size_t)w * 8 + 5]); }
-                    fprintf(f, "## ln_qkv_h16_kernel rows=%d: %d workgroups, first start -> last end %.2f us; per workgroup: start offset | staged+LN | split+barrier | K loop | epilogue 1 | epilogue 2 (us)\n", g.nrows, nt64, (double)(t1 - t0) / 100.0);
-                    for (int w : {0, 1, 2, 100, 255, 256, 300, 511, 512, 519}) {
-                        if (w >= nt64 || !st[(size_t)w * 8]) continue;
-                        fprintf(f, "  wg %3d: +%.2f |", w, (double)(st[(size_t)w * 8] - t0) / 100.0);
-                        for (int k = 1; k < 6; ++k) fprintf(f, " %.2f", (double)(st[(size_t)w * 8 + k] - st[(size_t)w * 8 + k - 1]) / 100.0);
-                        fprintf(f, "\n");
-                    }
-                    fclose(f);
-                }
-                ++stamped;
-            } else { if (qdbg == 1) hipLaunchKernelGGL(ln_qkv_h16_kernel<1>, dim3(nt64), dim3(256), smem, h->stream, mp); else hipLaunchKernelGGL(ln_qkv_h16_kernel<0>, dim3(nt64), dim3(256), smem, h->stream, mp); }
+            ensure_dyn_smem<ln_qkv_h16_kernel<0>>(smem, h->device);
+            hipLaunchKernelGGL(ln_qkv_h16_kernel<0>, dim3(nt64), dim3(256), smem, h->stream, mp);
             HIPCHK(h, hipGetLastError());
             h->last_cfg = 122;
             if (h->prof) {
@@ -1498,8 +1285,7 @@ int launch_mlp(ev_handle* h, int mode, const float* X, const float* ln_g, const 
     mp.sk.q = nchunk; mp.sk.r = 0; mp.sk.spin_limit = h->sk_spin;
     const int wpc = h->sk_wgs;
     const bool big = ntiles >= h->ncu && (long)ntiles * nchunk >= (long)wpc * h->ncu;
-    const bool spread = !big && h->sk_spread && ntiles < h->ncu && (long)ntiles * nchunk >= 2;   // small batches: one or a few units per workgroup
-    if (h->sk_balance && h->ncu > 0 && wpc * h->ncu <= EV_SK_MAXWG && (big || spread)) {
+    if (h->sk_balance && h->ncu > 0 && wpc * h->ncu <= EV_SK_MAXWG && big) {
         if (ensure_sk(h)) return 1;
         const long U = (long)ntiles * nchunk;
         grid = (int)std::min<long>((long)wpc * h->ncu, U);
@@ -1544,12 +1330,10 @@ int launch_attn(ev_handle* h, const float* QKV, int ld, float* O, int ldo, const
     AttnParams p;
     p.QKV = QKV; p.ld = ld; p.O = O; p.ldo = ldo; p.rowmask = rowmask; p.S = g.S; p.P = g.P; p.T = g.T; p.H = H; p.scale = 0.125f;
     const int nwg = ((g.T + 127) / 128) * H * (g.nrows / g.S), nkt = (g.T + 31) / 32;
-    static const bool no_sk = getenv("EV_NO_ATTN_SK") != nullptr;
-    if (!no_sk && part && nwg <= 64 && nkt >= 4 && g.nrows <= EV_ATTN_MAXROWS) {   // far fewer workgroups than CUs: the key tiles of a query tile go to KS workgroups
+    if (h->attn_sk && part && nwg <= 64 && nkt >= 4 && g.nrows <= EV_ATTN_MAXROWS) {   // far fewer workgroups than CUs: the key tiles of a query tile go to KS workgroups
         AttnPartParams pp;
         pp.a = p; pp.rows = g.nrows;
-        static const int tpw = getenv("EV_ATTN_TPW") ? std::max(1, atoi(getenv("EV_ATTN_TPW"))) : 2;   // key tiles per workgroup (A/B)
-        pp.KS = std::min(EV_ATTN_MAXPARTS, (nkt + tpw - 1) / tpw);
+        pp.KS = std::min(EV_ATTN_MAXPARTS, (nkt + h->attn_tpw - 1) / h->attn_tpw);   // (attn_tpw key tiles per workgroup)
         pp.PO = part; pp.PML = part + (size_t)EV_ATTN_MAXPARTS * g.nrows * H * 64;
         hipLaunchKernelGGL(attention_part_kernel, dim3((g.T + 127) / 128, H, (g.nrows / g.S) * pp.KS), dim3(256), 0, h->stream, pp);
         const long tot = (long)g.nrows * H * 16;
@@ -1624,9 +1408,8 @@ int launch_attn_out(ev_handle* h, const float* QKV, int ld, const ConvLayer& Lo,
     p.QKV = QKV; p.ld = ld; p.rowmask = rowmask; p.Wout = Lo.W; p.S = g.S; p.P = g.P; p.T = g.T; p.B = B; p.nq = (g.T + 31) / 32; p.scale = 0.125f;
     p.xcd_map = (B % 8 == 0) ? 1 : 0;
     {   // a short last query tile (<= AO_TAILQ queries) goes to one small 4 x 4-block workgroup per utterance, dispatched first
-        static const bool no_tail = getenv("EV_ATTN_NO_TAIL") != nullptr;
         const int last = g.T - 32 * (p.nq - 1);
-        if (!no_tail && p.nq >= 2 && last <= AO_TAILQ) { p.ntail = last; p.nq -= 1; }
+        if (p.nq >= 2 && last <= AO_TAILQ) { p.ntail = last; p.nq -= 1; }
     }
     ConvParams& e = p.ep;
     e.Y = Hid; e.ldy = ldh; e.Cout = Lo.Cout; e.bias = Lo.bias; e.R = Hid; e.ldr = ldh; e.osplit_log2 = 31; e.isplit_log2 = 31; e.mmul = 1; e.scale = 1.f;
@@ -1643,51 +1426,9 @@ int launch_attn_out(ev_handle* h, const float* QKV, int ld, const ConvLayer& Lo,
         HIPCHK(h, hipEventRecord(e0, h->stream));
     }
     if (h16) ensure_dyn_smem<attn_out_h16_kernel>(smem, h->device); else ensure_dyn_smem<attn_out_kernel>(smem, h->device);
-    auto launch = [&]() {
-        if (h16) hipLaunchKernelGGL(attn_out_h16_kernel, dim3((unsigned)(p.nq * B + (p.ntail > 0 ? B : 0))), dim3(256), smem, h->stream, p);
-        else hipLaunchKernelGGL(attn_out_kernel, dim3((unsigned)(p.nq * B + (p.ntail > 0 ? B : 0))), dim3(256), smem, h->stream, p);
-    };
-    static const char* stamp_file = getenv("EV_ATTN_STAMPS");      // diagnostic: per-workgroup phase stamps of the first launches, appended to this file
-    static int stamped = 0;
-    const int nwg = p.nq * B + (p.ntail > 0 ? B : 0);
-    if (stamp_file && *stamp_file && stamped < 8 && B >= 32) {
-        unsigned long long* d = nullptr;
-        HIPCHK(h, hipMalloc((void**)&d, (size_t)nwg * 6 * sizeof(unsigned long long)));
-        HIPCHK(h, hipMemsetAsync(d, 0, (size_t)nwg * 6 * sizeof(unsigned long long), h->stream));
-        p.stamps = d;
-        launch();
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::vector<unsigned long long> st((size_t)nwg * 6);
-        HIPCHK(h, hipMemcpy(st.data(), d, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        hipFree(d);
-        unsigned long long t0 = ~0ull;
-        for (int i = 0; i < nwg; ++i) t0 = std::min(t0, st[(size_t)i * 6]);
-        if (FILE* f = fopen(stamp_file, "a")) {
-            const char* names[6] = {"start", "first key tile", "key loop done", "merged", "projection done", "end"};
-            fprintf(f, "## %s T=%d B=%d: %d workgroups; us since the first workgroup started (100 MHz s_memrealtime)\n", h16 ? "attn_out_h16_kernel" : "attn_out_kernel", g.T, B, nwg);
-            for (int k = 0; k < 6; ++k) {
-                std::vector<double> v(nwg);
-                for (int i = 0; i < nwg; ++i) v[i] = (double)(st[(size_t)i * 6 + k] - t0) / 100.0;
-                std::sort(v.begin(), v.end());
-                fprintf(f, "  %-16s min %7.1f  p10 %7.1f  p50 %7.1f  p90 %7.1f  max %7.1f\n", names[k], v[0], v[nwg / 10], v[nwg / 2], v[(size_t)nwg * 9 / 10], v[nwg - 1]);
-            }
-            for (int k = 0; k < 5; ++k) {              // per-workgroup phase durations
-                std::vector<double> v(nwg);
-                for (int i = 0; i < nwg; ++i) v[i] = (double)(st[(size_t)i * 6 + k + 1] - st[(size_t)i * 6 + k]) / 100.0;
-                std::sort(v.begin(), v.end());
-                fprintf(f, "  phase %-16s -> %-16s p10 %6.1f  p50 %6.1f  p90 %6.1f us\n", names[k], names[k + 1], v[nwg / 10], v[nwg / 2], v[(size_t)nwg * 9 / 10]);
-            }
-            if (p.ntail > 0) {                          // the short-tile workgroups (block ids 0 .. B-1) on their own
-                std::vector<double> v0(B), v1(B);
-                for (int i = 0; i < B; ++i) { v0[i] = (double)(st[(size_t)i * 6] - t0) / 100.0; v1[i] = (double)(st[(size_t)i * 6 + 5] - t0) / 100.0; }
-                std::sort(v0.begin(), v0.end()); std::sort(v1.begin(), v1.end());
-                fprintf(f, "  short last tile (%d queries, 4 x 4 blocks): start p50 %6.1f max %6.1f   end p50 %6.1f max %6.1f us\n", p.ntail, v0[B / 2], v0[B - 1], v1[B / 2], v1[B - 1]);
-            }
-            fclose(f);
-        }
-        ++stamped;
-        p.stamps = nullptr;
-    } else launch();
+    const dim3 grid((unsigned)(p.nq * B + (p.ntail > 0 ? B : 0)));
+    if (h16) hipLaunchKernelGGL(attn_out_h16_kernel, grid, dim3(256), smem, h->stream, p);
+    else hipLaunchKernelGGL(attn_out_kernel, grid, dim3(256), smem, h->stream, p);
     HIPCHK(h, hipGetLastError());
     if (h->prof) {
         HIPCHK(h, hipEventRecord(e1, h->stream));
@@ -1838,8 +1579,7 @@ int ensure_ws(ev_handle* h, int B, int Tp, int Tv, EstBufs* eb, VocBufs* vb) {
     if (rezero) {
         // the estimator's part is zeroed whole (small); of the vocoder's tensors — 0.3-1.1 GB for one streaming utterance — only
         // the pad rows, which is all the convolutions need (zero_pads_kernel)
-        static const bool full_zero = getenv("EV_FULL_REZERO") != nullptr;
-        const size_t zbytes = (full_zero || Tv <= 0) ? need : voc_off;
+        const size_t zbytes = (h->full_rezero || Tv <= 0) ? need : voc_off;
         if (zbytes) {
             hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
             const bool capturing = h->stream && hipStreamIsCapturing(h->stream, &cst) == hipSuccess && cst == hipStreamCaptureStatusActive;
@@ -1849,7 +1589,7 @@ int ensure_ws(ev_handle* h, int B, int Tp, int Tv, EstBufs* eb, VocBufs* vb) {
                 HIPCHK(h, hipGetLastError());
             } else HIPCHK(h, hipMemsetAsync(h->ws, 0, zbytes, h->stream));
         }
-        if (!full_zero && Tv > 0 && vplan.nz > 0) {
+        if (!h->full_rezero && Tv > 0 && vplan.nz > 0) {
             ZeroPadParams zp;
             memset(&zp, 0, sizeof zp);
             zp.B = B; zp.n = vplan.nz;
@@ -1898,7 +1638,7 @@ int run_transformer(ev_handle* h, const TransW& w, const LevelBufs& L, float* Z,
     Epi e;
     // row tiles of 32 frames: the fused LayerNorm + linear kernels need about a round of workgroups to pay off (a batch-1
     // decode has 9-27 such tiles: it keeps the split-K small-launch build of the separate linears)
-    const bool fuse = h->fuse_mlp && (g_rows32(L.g) >= h->fuse_mlp_min_tiles || (h->sk_spread && h->sk_balance));
+    const bool fuse = h->fuse_mlp && g_rows32(L.g) >= h->fuse_mlp_min_tiles;
     const bool aok = attn_out_ok(h, w.out, L.g, heads);
     int packed = 0;                                     // q / k / v left as fp16 piece pairs (ln_qkv_h16_kernel -> attn_out_h16_kernel)
     if (fuse) {
@@ -2247,20 +1987,29 @@ int ev_create(ev_handle** out, int device, const ev_model_dims* dims) {
     ev_handle* h = new ev_handle();
     h->device = device;
     h->dims = *dims;
+    // every switch of the engine is read here, once per handle; EV_PROFILE_DUMP is read by ev_profile_read
     { const char* fp = getenv("EV_FUSE_PAIRS"); if (fp && *fp == '0') h->fuse_pairs = false; }
-    { const char* fp = getenv("EV_FUSE128"); if (fp && *fp) h->fuse128 = atoi(fp); }
     { const char* fp = getenv("EV_FUSE_MLP"); if (fp && *fp == '0') h->fuse_mlp = false; }
     { const char* fp = getenv("EV_FUSE_ATTN"); if (fp && *fp == '0') h->fuse_attn = false; }
     if (getenv("EV_NO_ATTN_H16")) h->attn_h16 = false;
+    if (getenv("EV_NO_CHAIN")) h->use_chain = false;
     { const char* fp = getenv("EV_FUSE_MLP_MIN"); if (fp && *fp) h->fuse_mlp_min_tiles = atoi(fp); }
     { const char* fp = getenv("EV_MRF_STREAMS_MAX"); if (fp && *fp) h->mrf_max_frames = atoi(fp); }
     if (getenv("EV_NO_AMAX")) h->use_amax = false;
     { const char* sp = getenv("EV_SPLIT"); if (sp && *sp) { const int t = atoi(sp); h->split_terms = (t == 0 || t == 3 || t == 6 || t == 9 || t == 16) ? t : 16; } }
     { const char* fp = getenv("EV_NO_SK_BALANCE"); if (fp && *fp && *fp != '0') h->sk_balance = false; }
     { const char* fp = getenv("EV_SK_SPIN"); if (fp && *fp) h->sk_spin = atoi(fp); }
-    if (getenv("EV_NO_SK_STEAL")) h->sk_steal = false;
     { const char* fp = getenv("EV_SK_WGS"); if (fp && *fp) h->sk_wgs = std::min(3, std::max(1, atoi(fp))); }
-    { const char* fp = getenv("EV_SK_SPREAD"); if (fp && *fp) h->sk_spread = *fp != '0'; }
+    { const char* fp = getenv("EV_FORCE_CFG"); if (fp && *fp) h->force_cfg = atoi(fp); }
+    if (getenv("EV_NO_LEAN")) h->lean = false;
+    if (getenv("EV_NO_SK")) h->small_sk = false;
+    if (getenv("EV_NO_SK32_LEAN")) h->sk32_lean = false;
+    if (getenv("EV_NO_GN_STATS")) h->gn_stats = false;
+    if (getenv("EV_NO_QKV_H16")) h->qkv_h16 = false;
+    if (getenv("EV_NO_ATTN_SK")) h->attn_sk = false;
+    { const char* fp = getenv("EV_ATTN_TPW"); if (fp) h->attn_tpw = std::max(1, atoi(fp)); }
+    if (getenv("EV_FULL_REZERO")) h->full_rezero = true;
+    { const char* fp = getenv("EV_RB2_MINKEEP"); if (fp) h->rb2_minkeep = atoi(fp); }
     if (hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) h->ncu = 0;
     // the shipped decoder configuration (configs/model/decoder/default.yaml: 2 heads x 64) is the only one the workspace
     // plan and the transformer launch sequence are laid out for
@@ -2368,9 +2117,8 @@ int ev_load_estimator(ev_handle* h, const float* blob, const ev_tensor_index* in
         REQ(pack_conv(h, w.rn[i].c2, *c2w, c2b, 1));
         if (i == 0) {   // split along Cin at n_feats: [x | mu, spk]
             const int nf = h->dims.n_feats, cin = (int)c1w->shape[1];
-            // x share: n_feats = 80 channels, read as two 64-channel chunks of the [x | mu | spk] row (EV_RN0_PAD=0: as 80 channels on the fp32 MFMA)
-            static const bool no_pad = getenv("EV_RN0_PAD") && atoi(getenv("EV_RN0_PAD")) == 0;
-            const int npad = (!no_pad && nf % 64 != 0 && ((nf + 63) & ~63) <= cin) ? ((nf + 63) & ~63) : 0;
+            // x share: n_feats = 80 channels, read as two 64-channel chunks of the [x | mu | spk] row
+            const int npad = (nf % 64 != 0 && ((nf + 63) & ~63) <= cin) ? ((nf + 63) & ~63) : 0;
             REQ(stack(0, nf, false, w.rn0_c1r_x, npad));
             REQ(stack(nf, cin, true, w.rn0_c1r_ms));
         }
@@ -3044,7 +2792,7 @@ int ev_hifigan(ev_handle* h, const float* d_mel, int B, int T, float* d_wav, voi
                     e2.accum = (j > 0);
                     if (j == 2) { e2.div3 = 1; e2.act2_lrelu = 1; e2.act2_slope = next_slope; }  // next consumer's leaky_relu
                 }
-                if (h->fuse_pairs && (C == 32 || C == 64 || (C == 128 && h->fuse128 && w.c1[i * 3 + j][mm].ntaps <= h->fuse128))) {
+                if (h->fuse_pairs && (C == 32 || C == 64 || (C == 128 && w.c1[i * 3 + j][mm].ntaps <= 3))) {
                     // narrow stages: both convs of the pair in one launch, intermediate kept in LDS
                     // (a fused pair finds its own tile maximum and bounds its residual with it: it needs no slots of x, and only the pair that
                     // closes a chain into the running sum of a level whose sum an fp16 build consumes — the upsampler of levels 1..3 — leaves
@@ -3159,7 +2907,7 @@ int ev_dbg_set_amax(ev_handle* h, int on) {
 }
 
 // Diagnostic / A-B switch (ABI v4): 1 (default) = ev_hifigan runs the ResBlock1 chains that qualify (narrow levels, k = 3) as ONE launch each
-// (resblock_chain_h16_kernel), 0 = as three fused pairs
+// (resblock_chain_h16_kernel), 0 = as three fused pairs.  EV_NO_CHAIN=1 presets 0.
 int ev_dbg_set_chain(ev_handle* h, int on) {
     if (!h) return 1;
     h->use_chain = on != 0;
@@ -3184,7 +2932,7 @@ int ev_profile_read_split(ev_handle* h, double* ms_out, double* flops_out, int64
     if (h->prof_recs.size() * 2 == h->ev_used)
         for (size_t i = 0; i < h->prof_recs.size(); ++i) {
             const auto& r = h->prof_recs[i];
-            const bool split = (r.kind == 0 && (r.cfg == 40 || r.cfg == 41 || r.cfg == 46 || r.cfg == 47 || r.cfg == 66 || r.cfg == 68 || r.cfg == 43 || r.cfg == 49 || r.cfg == 60)) || (r.kind == 1 && r.cfg >= 140) || (r.kind == 2 && (r.cfg == 120 || r.cfg == 121)) || (r.kind == 3 && r.cfg == 122) || (r.kind == 4 && r.cfg == 31);
+            const bool split = (r.kind == 0 && (r.cfg == 40 || r.cfg == 41 || r.cfg == 46 || r.cfg == 47 || r.cfg == 66 || r.cfg == 43 || r.cfg == 49 || r.cfg == 60)) || (r.kind == 1 && r.cfg >= 140) || (r.kind == 2 && (r.cfg == 120 || r.cfg == 121)) || (r.kind == 3 && r.cfg == 122) || (r.kind == 4 && r.cfg == 31);
             if (!split) continue;
             float t = 0;
             HIPCHK(h, hipEventElapsedTime(&t, h->ev_pool[2 * i], h->ev_pool[2 * i + 1]));

@@ -44,10 +44,6 @@ struct SkCtl {
     unsigned* claims;    // one word per workgroup (null: no stealing): 2 seq = "started its share of this launch", 2 seq + 1 = "its owner has taken the share over"
     unsigned seq;        // launch sequence number of the handle (host-side counter: monotonic, so the words never need a reset)
     int lds_word;        // conv_gemm_bal_kernel: byte offset of the sk_wait word in dynamic LDS
-    // conv_gemm_bal_kernel, layers whose M tiles differ in cost (a 3-tap conv stacked over a 1x1 conv: half of the M tiles carry one
-    // tap): the workgroups share WEIGHTED positions — a unit of M tile mt weighs wtab[mt] (its taps, 4 bits each, up to 16 M tiles) —
-    // and a position is rounded down to the unit that contains it.  wsum = sum of the weights over the M tiles (0 = all units equal).
-    int wsum; int mtiles; int nchunks; unsigned long long wtab;
 };
 
 struct ConvParams {
@@ -91,7 +87,6 @@ struct ConvParams {
                                             // a bound read from slots the same launch is updating would depend on timing — and the tile scales, hence the bits, with it)
     const unsigned* xmax; int xmax_n;       // consumer: slots of X and their count (null: pre-scan)
     int stagger_slots;                      // workgroups co-resident per CU (0 = no start stagger), see conv_gemm_kernel
-    int mt_mul;                             // conv_h16_bal_kernel with 256-channel M tiles: tap list / tap count of M tile mt are those of the 128-channel tile mt_mul * mt (0 = 1)
     unsigned long long* stamps;             // dbg bit 16: per-workgroup {start, first stage done, K loop done, end} s_memtime stamps
     int dbg;                                // ablation bits for tools/conv_bench.py: 1 skip X loads, 2 skip A loads, 4 skip epilogue
     SkCtl sk;                               // conv_gemm_kernel<..., SK = true>: the balanced persistent grid (units = (tile, 32-channel k-chunk))
@@ -489,21 +484,7 @@ __device__ __forceinline__ void conv_epilogue_lean_q(const ConvParams& p, f32x4 
 // ---------------------------------------------------------------------------
 typedef __attribute__((address_space(1))) unsigned ev_gu32;
 __device__ __forceinline__ int sk_start(const SkCtl& c, int x) {
-    const int pos = x * c.q + (x < c.r ? x : c.r);
-    if (c.wsum == 0) return pos;
-    // weighted: position -> unit.  Units are ordered (n tile, M tile, chunk); one n tile spans nchunks * wsum positions
-    const int per_nt = c.nchunks * c.wsum;
-    const int nt = pos / per_nt;
-    int rem = pos - nt * per_nt, mt = 0;
-    for (; mt < c.mtiles - 1; ++mt) {
-        const int span = c.nchunks * (int)((c.wtab >> (4 * mt)) & 15ull);
-        if (rem < span) break;
-        rem -= span;
-    }
-    const int w = (int)((c.wtab >> (4 * mt)) & 15ull);
-    int ch = rem / w;
-    if (ch > c.nchunks) ch = c.nchunks;                    // (pos == total: the end sentinel lands on the first unit of the next n tile)
-    return (nt * c.mtiles + mt) * c.nchunks + ch;
+    return x * c.q + (x < c.r ? x : c.r);
 }
 __device__ __forceinline__ unsigned sk_tag(const SkCtl& c) {
     return c.ctrl ? (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load((ev_gu32*)c.ctrl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1u : 0u;
@@ -712,16 +693,14 @@ __device__ __forceinline__ float ev_amax_read(const ConvParams& p, int row_lo, i
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, m)));
 }
 
-// KB = 32-channel k-chunks staged per barrier pair (LDS row = 32*KB + 4 floats).  KB = 2 halves the number of
-// stage / barrier episodes — what the 1x1 and k=3 layers need (a 1x1 conv has only 4 k-groups = 32 MFMAs per wave
-// between two barrier pairs at KB = 1); wide-halo layers (k = 11, d = 5) already run 352 MFMAs per chunk and keep KB = 1
-// for its smaller LDS tile (more workgroups per CU).  The accumulation order (chunk, tap, k-group) is the same for both.
+// One 32-channel k-chunk is staged per barrier pair; the accumulation order is (chunk, tap, k-group).  KB (k-chunks per stage) is 1
+// only: the parameter keeps the kernel names that traces, profiles/ and tests/test_code_object.py carry.
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool PF = false, bool FULL_ACT = true, int LEAN = 0, int KB = 1>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
+    static_assert(KB == 1, "one 32-channel k-chunk per stage");
     constexpr int TM = BM / WAVES_M / 32;
     constexpr int TN = BN / WAVES_N / 32;
-    constexpr int LDK = 32 * KB + 4;                   // LDS row stride (floats): 36 / 68 are both conflict-free for ds_read_b128
-    static_assert(!PF || KB == 1, "the register-prefetch build stages one 32-channel chunk at a time");
+    constexpr int LDK = 36;                            // LDS row stride (floats): conflict-free for ds_read_b128
     static_assert(WAVES_M * WAVES_N == 4, "4 waves per workgroup");
     static_assert(TM >= 1 && TN >= 1, "tile");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -789,7 +768,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
     }
 
     const int xrows = BN + p.halo_lo + p.halo_hi;
-    constexpr int TPR = 8 * KB, RPS = 256 / TPR;   // staging: threads per row, rows per pass
+    constexpr int TPR = 8, RPS = 256 / TPR;        // staging: threads per row, rows per pass
     const int srow = tid / TPR;         // staging row within a pass
     const int sc4 = (tid % TPR) * 4;    // staging column (floats)
     const int nchunks = p.Kpad / EV_BK;
@@ -885,15 +864,13 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
         // Memory phases (X staging, epilogue) issue few instructions but were measured to stretch 2-3x when the other
         // workgroups of the CU are in their MFMA loops (issue arbitration favours the older, MFMA-issuing waves): run
         // them at raised priority so a workgroup gets back to feeding the matrix pipe sooner.
-        const int sub = ch & (KB - 1);
-        if (sub == 0) {
         __builtin_amdgcn_s_setprio(3);
         if (p.dbg & 2) ts0 = __builtin_amdgcn_s_memrealtime();
         if (!(p.dbg & 8)) ev_lds_barrier();  // previous chunk's MFMAs are done with Xs (dbg 8: timing-only ablation without barriers)
         if (p.dbg & 2) { const unsigned long long t1 = __builtin_amdgcn_s_memrealtime(); acc_b1 += t1 - ts0; }
         {
             const int c0 = ch * EV_BK;
-            const bool ctail = (c0 + 32 * KB > p.Cin);       // uniform: only the last chunk of a Cin that is not a multiple of 32
+            const bool ctail = (c0 + 32 > p.Cin);            // uniform: only the last chunk of a Cin that is not a multiple of 32
             if constexpr (PF) {
 #pragma unroll
                 for (int q = 0; q < XPASS; ++q) x_put(q, xv[PF ? q : 0], c0, ctail);
@@ -918,17 +895,15 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
         __builtin_amdgcn_s_setprio(0);
         if (p.dbg & 2) acc_st += __builtin_amdgcn_s_memrealtime() - ts0;
         if constexpr (PF) x_issue(ch + 1 < nchunks ? ch + 1 : ch);   // (after the last chunk: a harmless re-read)
-        }
-        const float* bsub = bbase + sub * 32;
         if ((p.dbg & 18) == 16 && ch == 0 && threadIdx.x == 0) p.stamps[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
         int tap = tv_first.x;
-        const float* brow = bsub + tv_first.y * LDK;
-        if (sub == 0) ldB(B0, brow, 0);                     // (later sub-chunks: prefetched by the last tap of the previous one)
+        const float* brow = bbase + tv_first.y * LDK;
+        ldB(B0, brow, 0);
         for (int ti = 0; ti < nact; ++ti) {
             const bool last_tap = (ti + 1 == nact);
             const int2 ntv = last_tap ? tv_first : ev_tap_at(tlv, ti + 1);
             const int ntap = ntv.x;
-            const float* nbrow = bsub + ntv.y * LDK;
+            const float* nbrow = bbase + ntv.y * LDK;
             const bool have_next = !(last_tap && ch + 1 == nchunks);
             // fragments of the next tap (k-groups +1 KiB each); after the very last tap: a harmless re-read of the first fragments
             const unsigned nap = have_next ? a_off(ntap, last_tap ? ch * 4 + 4 : ch * 4) : a_off(tv_first.x, 0);
@@ -949,9 +924,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
             mma(A2, B0);
             __builtin_amdgcn_sched_barrier(0);
             ldAp(A2, nap + 2048u);
-            // first B fragments of the next tap (after the last tap of a chunk: a harmless read of the tile being retired,
-            // or — KB > 1 — the next sub-chunk, which is already in LDS)
-            ldB(B0, (KB > 1 && last_tap && sub + 1 < KB && ch + 1 < nchunks) ? nbrow + 32 : nbrow, 0);
+            // first B fragments of the next tap (after the last tap of a chunk: a harmless read of the tile being retired)
+            ldB(B0, nbrow, 0);
             __builtin_amdgcn_sched_barrier(0);
             mma(A3, B1);
             __builtin_amdgcn_sched_barrier(0);
@@ -1208,7 +1182,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvParams p) 
 // unit range [start(g), start(g + 1)) in (tile-major, chunk-minor) order.  A tile whose chunks straddle workgroups is finished by
 // the one that holds chunk 0 (it reaches that tile LAST; bias in its accumulators), the others reach their share of it FIRST and
 // hand over an accumulator tile without bias; the owner adds them in ascending workgroup order.  Same K loop as conv_gemm_kernel
-// (KB = 1, no register-prefetched staging), lean epilogues only; the summation order over k-chunks of a split tile differs from
+// (no register-prefetched staging), lean epilogues only; the summation order over k-chunks of a split tile differs from
 // the one-tile-per-workgroup build (partial sums), deterministically for a given device.
 // Measured motive (tools/shape_profile.py, 62 vs 64 utterances): 1040 tiles of 64 x 64 on 256 CUs leave the matrix pipes of three
 // quarters of the chip idle for the last fifth of the launch (4.06 tiles per CU = five rounds on some CUs).
@@ -2029,15 +2003,12 @@ __global__ __launch_bounds__(256, 2) void conv_split_bal_kernel(const ConvParams
 // ---------------------------------------------------------------------------
 // XP = staging passes of 16 rows a chunk is read in: 12 covers the widest halo, 9 the 3-tap layers of the U-Net (host-checked: BN + halo <= 16 XP) —
 // twelve registers fewer held beside the accumulators and the weight ring.
-// EIGHT waves (<256, 128, 4, 2, ...>: one workgroup per CU, all 256 output channels of a 128-frame tile; passes of 32 rows): the two workgroups of
-// a CU in the four-wave build run the same program in lockstep and stage the SAME X rows when the layer has two M tiles — merged, the tile is
-// staged once (half the bytes of the burst every chunk begins with), the MFMA phase is the same two waves per SIMD.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int LEAN, int XP = (BN + EV_HALO) / (4 * WAVES_M * WAVES_N), int XK = (XP > 9 ? 8 : XP)>
-__global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N == 4 ? 2 : 1) void conv_h16_bal_kernel(const ConvParams p) {
+__global__ __launch_bounds__(256, 2) void conv_h16_bal_kernel(const ConvParams p) {
     constexpr int TM = BM / WAVES_M / 32;
     constexpr int TN = BN / WAVES_N / 32;
     constexpr int NW = WAVES_M * WAVES_N, NTHR = 64 * NW;
-    static_assert((NW == 4 || NW == 8) && TM >= 1 && TN >= 1 && LEAN != 0, "balanced build: 4 waves (two workgroups per CU) or 8 (one), lean epilogue");
+    static_assert(NW == 4 && TM >= 1 && TN >= 1 && LEAN != 0, "balanced build: 4 waves (two workgroups per CU), lean epilogue");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* Xb = (char*)smem;
     const int tid = threadIdx.x;
@@ -2064,19 +2035,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N == 4 ? 2 
     bool pend_pub = false;
     const unsigned wlane = (unsigned)lane * 16u;
     const int KG16 = p.Kpad >> 4;
-    constexpr int TPR = EVX_KC / 4, RPS = NTHR / TPR;   // staging: 16 threads per row, 16 (32) rows per pass
+    constexpr int TPR = EVX_KC / 4, RPS = NTHR / TPR;   // staging: 16 threads per row, 16 rows per pass
     const int srow = tid / TPR, sc4 = (tid % TPR) * 4;
     constexpr int XPASS = XP;
     const int xrows = BN + p.halo_lo + p.halo_hi;
-    int nst = 0;                                       // diagnostic (EV_BAL_STAMPS): up to 16 s_memrealtime stamps per workgroup
-    auto stamp = [&]() { if (p.stamps && tid == 0 && nst < 16) p.stamps[16 * g + nst] = __builtin_amdgcn_s_memrealtime(); ++nst; };
-    stamp();
-    // Start stagger (EV_BAL_STAGGER=<us>, A/B): the two workgroups of a CU run the same program on the same amount of work, so they stage (HBM-bound,
-    // all workgroups of the launch at once) and issue MFMAs (both on the same SIMDs) IN PHASE — per-workgroup stamps: 3.5 us staged + 4 us
-    // MFMAs per chunk where one workgroup alone on the matrix pipes needs 2.2.  The second half of the grid (the workgroups that share a CU
-    // with the first half under the dispatcher's round-robin; a placement assumption for speed only) starts late by about half a chunk period.
-    if (p.stagger_slots > 0 && g >= (int)(gridDim.x >> 1))
-        for (int i_ = 0; i_ < p.stagger_slots; ++i_) __builtin_amdgcn_s_sleep(32);      // 32 x 64 cycles ~ 1 us per step
 
     while (u < ue) {
         const int t = u / nchunks, c0 = u - t * nchunks;
@@ -2097,9 +2059,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N == 4 ? 2 
             if (c0 != 0 && sk_claim_taken(p.sk, claim_prev, tid, skw)) continue;     // its owner computes it: skip
         }
         if (pend_pub) { sk_publish(p.sk, g, get_tag(), tid); pend_pub = false; }
-        const int mtl = p.mt_mul > 1 ? mt * p.mt_mul : mt;   // (the tap tables are per 128-channel tile)
-        const int2* tl = p.taplist + (size_t)mtl * p.tl_stride;
-        const int nact = __builtin_amdgcn_readfirstlane(p.nact_tab ? p.nact_tab[mtl] : p.ntaps);
+        const int2* tl = p.taplist + (size_t)mt * p.tl_stride;
+        const int nact = __builtin_amdgcn_readfirstlane(p.nact_tab ? p.nact_tab[mt] : p.ntaps);
         const int mt32 = (m0 + wm * (TM * 32)) >> 5;
         const unsigned wbase = (unsigned)(mt32 * KG16) * 2048u;
         auto a_off = [&](int tap_bytes, int kg16) -> unsigned { return (unsigned)tap_bytes + wbase + (unsigned)kg16 * 2048u; };
@@ -2131,7 +2092,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N == 4 ? 2 
         for (;;) {
             // One activation scale per staged CHUNK, taken from the chunk's own rows while they wait in registers (no pre-scan pass: the
             // launches of the U-Net are one round of workgroups in lockstep, and a pre-scan that re-read every tile — 70-100 MB per
-            // launch, all workgroups at once — took 13-27 us of their 62-90 us: per-workgroup stamps, EV_BAL_STAMPS,
+            // launch, all workgroups at once — took 13-27 us of their 62-90 us: per-workgroup stamps,
             // profiles/r03_conv_h16_bal_stamps.txt).  The accumulators run in units of wh_scale * (scale of the chunk in LDS) and are
             // rescaled by an exact power of two when that changes (ln_mlp_h16_kernel does the same per hidden chunk).
             float xs = 1.0f;                               // scale of the chunk whose planes are in LDS (none yet: unit 1)
@@ -2205,7 +2166,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N == 4 ? 2 
                     if (lane == 0) hr[wave] = mx;
                     ev_lds_barrier();                      // maxima published; the previous chunk's MFMAs (or the previous segment's epilogue) are done with LDS
                     float cmx = fmaxf(fmaxf(hr[0], hr[1]), fmaxf(hr[2], hr[3]));
-                    if constexpr (NW == 8) cmx = fmaxf(cmx, fmaxf(fmaxf(hr[4], hr[5]), fmaxf(hr[6], hr[7])));
                     if (!evh_is_finite(cmx)) {             // an Inf among the chunk's rows (workgroup-uniform, never on clean data): the finite maximum sets the scale
                         mx = mxf;
 #pragma unroll
@@ -2216,7 +2176,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N == 4 ? 2 
                         if (lane == 0) h3[wave] = mx;
                         ev_lds_barrier();
                         cmx = fmaxf(fmaxf(h3[0], h3[1]), fmaxf(h3[2], h3[3]));
-                        if constexpr (NW == 8) cmx = fmaxf(cmx, fmaxf(fmaxf(h3[4], h3[5]), fmaxf(h3[6], h3[7])));
                     }
                     const float xn = evh_scale_for(cmx);
                     if (xn != xs) {                        // (workgroup-uniform)
@@ -2253,7 +2212,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N == 4 ? 2 
                 }
                 ev_lds_barrier();
                 __builtin_amdgcn_s_setprio(0);
-                stamp();                                   // chunk staged
                 const char* brow = bbase + tv_first.y * EVH_RSB;
                 ldB(B0, brow, 0);
                 for (int ti = 0; ti < nact; ++ti) {
@@ -2284,7 +2242,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N == 4 ? 2 
                     ldAp(A3, nap + 6144u);
                     brow = nbrow;
                 }
-                stamp();                                   // chunk's MFMAs issued
             }
             const float acc_out = 1.0f / (p.wh_scale * xs);
 #pragma unroll
@@ -2315,7 +2272,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N == 4 ? 2 
             if (c0 != 0) {                                 // not the owner: hand the partial tile over (flag raised at the next segment)
                 acc_io((unsigned)g * pslot, 0);
                 pend_pub = true;
-                stamp();                                   // partial stored
                 break;
             }
             bool again = false;
@@ -2339,15 +2295,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N == 4 ? 2 
                 }
             }
             if (again) continue;
-            stamp();                                       // contributors' partials added
             __builtin_amdgcn_s_setprio(3);
             conv_epilogue_lean<TM, TN, LEAN>(p, acc, smem + wave * (32 * (TM * 32 + 4)), m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane);
             __builtin_amdgcn_s_setprio(0);
-            stamp();                                       // epilogue done
             break;
         }
     }
-    stamp();
     if (pend_pub) sk_publish(p.sk, g, get_tag(), tid);
     sk_arrive(p.sk, get_tag(), tid);
 }
@@ -2786,7 +2739,6 @@ struct PairParams {
     ConvParams c2;                 // c2 + epilogue view: X = x (input), W/bias/taplist = c2's, R = x, Y = output, flags
     const float* W1; const float* b1; const int2* taplist1; int ntaps1;
     const void* W1h; float w1h_scale;   // resblock_pair_h16_kernel: c1's weights times w1h_scale as two fp16 pieces (c2's: c2.Wh, c2.wh_scale)
-    const void* W1q;               // resblock_pair_h16q_kernel: the same pieces in the 16 x 16 x 32 fragment order (c2's: c2.Wq)
     const void* W1x;               // resblock_pair_split_kernel: c1's weights as three bf16 pieces (c2's: c2.Wx)
     int h1, h2;                    // halos of c1 (dilated) and c2
     float mid_slope;               // leaky-relu slope between the convs
@@ -3790,229 +3742,6 @@ __global__ __launch_bounds__(256, 2) void resblock2_h16_kernel(const Rb2Params c
 }
 
 // ---------------------------------------------------------------------------
-// resblock_pair_h16q_kernel: resblock_pair_h16_kernel with both K loops on v_mfma_f32_16x16x32_f16 (see conv_h16_kernel<..., Q = 1>: the 16 x 16
-// shape holds a higher clock under the chip's power limit).  A "group" of the K loops — two 16-deep slabs of one tap — is exactly one 32-deep
-// step here; a wave's 32 channels x 64 frames are 2 x 4 tiles of 16 x 16.  Weights: W1q / c2.Wq (16 x 16 x 32 fragment order), same pieces,
-// same scales, same accumulation order over (tap, k) as the 32 x 32 form; LDS layout, staging, scale search and epilogue are unchanged.
-// ---------------------------------------------------------------------------
-template <int WAVES_M, int WAVES_N, int LEAN>
-__global__ __launch_bounds__(256, 2) void resblock_pair_h16q_kernel(const PairParams pp) {
-    constexpr int TM = 1, TN = 2, QM = 2, QN = 4;
-    constexpr int C = 32 * WAVES_M;
-    constexpr int NT = WAVES_N * TN * 32;
-    constexpr int RSB = 4 * C + 16;                     // LDS row stride in bytes
-    constexpr int H = C / 32;                           // 32-deep steps per tap
-    constexpr int TPR = C / 4, RPS = 256 / TPR;         // staging: threads per row, rows per pass
-    constexpr int XPASS = (NT + EV_HALO) / RPS;
-    static_assert(WAVES_M * WAVES_N == 4, "4 waves per workgroup");
-    const ConvParams& p = pp.c2;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    char* Xb = (char*)smem;                             // phase 1: [NT + 2 h1][RSB];  phase 2 (aliased): y1 [NT + 2 h2][RSB]
-    float* red = smem + ((NT + EV_HALO) * RSB) / 4;     // 16 floats behind the tiles: the waves' maxima (x: 0..3, y1: 4..7; their finite-only repeats: 8..11, 12..15)
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int f16i = lane & 15, kg = lane >> 4;         // frame inside a 16-wide tile / 8-deep k group (= channel group 4 kg .. of a C/D tile)
-    const int srow = tid / TPR, sc4 = (tid % TPR) * 4;
-
-    const int nt = ev_xcd_remap(blockIdx.x, p.ntiles);
-    const int n0 = nt * pp.out_rows;
-    const int g0 = n0 - pp.h2;
-    {   // tiles whose output window holds no storable row do nothing
-        const int s0 = n0 % p.S, t_first = s0 - p.P;
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - s0 + p.P;
-        if (dist >= pp.out_rows || n0 + dist >= p.nrows) return;
-    }
-    const unsigned wlane = (unsigned)lane * 16u;
-    EvAmax am = ev_amax_begin(p, g0 + wn * (TN * 32), TN * 32);   // (the residual's / running sum's bounds: requested now, used behind the epilogue)
-    const unsigned wbase = (unsigned)(wm * 2 * H) * 2048u;   // this wave's two 16-channel row tiles: m16 = 2 wm + a, H steps of 2 KiB each
-    const __amdgpu_buffer_rsrc_t rX = ev_rsrc(p.X);
-    f32x4 acc[QM][QN];
-    f32x4 A0[2][QM], A1[2][QM], B0[2][QN], B1[2][QN];
-
-    auto ldA = [&](const __amdgpu_buffer_rsrc_t& rW, f32x4 (&dst)[2][QM], unsigned aoff) {
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc)
-#pragma unroll
-            for (int a = 0; a < QM; ++a) dst[pc][a] = ev_bload4(rW, wlane, aoff + (unsigned)(a * H * 2048 + pc * 1024));
-    };
-    auto ldB = [&](f32x4 (&dst)[2][QN], const char* brow, int ks) {
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc)
-#pragma unroll
-            for (int b = 0; b < QN; ++b) dst[pc][b] = *(const f32x4*)(brow + b * 16 * RSB + pc * (2 * C) + ks * 64);
-    };
-    // step g of a phase = the 32-deep step g % H of tap g / H (a tap's plane is as large as its fp32 plane: the tap list's byte offsets apply)
-    auto g_off = [&](int2 tlv, int g, int nsteps) -> unsigned {
-        const int gg = g < nsteps ? g : 0;              // (beyond the phase: a harmless re-read)
-        return (unsigned)__builtin_amdgcn_readlane(tlv.x, gg / H) + wbase + (unsigned)(gg % H) * 2048u;
-    };
-    auto g_row = [&](int2 tlv, int g, int nsteps) -> int {
-        const int gg = g < nsteps ? g : 0;
-        return __builtin_amdgcn_readlane(tlv.y, gg / H);
-    };
-    auto acc_init = [&](const float* binit, float unit) {   // bias in accumulator units; C/D rows 4 kg + 0..3 of tile a
-#pragma unroll
-        for (int a = 0; a < QM; ++a) {
-            const f32x4 bq = *(const f32x4*)(binit + wm * 32 + a * 16 + 4 * kg) * unit;
-#pragma unroll
-            for (int b = 0; b < QN; ++b) acc[a][b] = bq;
-        }
-    };
-    auto mma = [&](const f32x4 (&a)[2][QM], const f32x4 (&b)[2][QN]) {
-        constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int i = 0; i < QM; ++i)
-#pragma unroll
-                for (int jj = 0; jj < QN; ++jj)
-                    acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[PA[t]][i]), __builtin_bit_cast(f16x8, b[PB[t]][jj]), acc[i][jj], 0, 0, 0);
-    };
-    auto ring_fill = [&](const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int nsteps) {
-        ldA(rW, A0, g_off(tlv, 0, nsteps)); ldA(rW, A1, g_off(tlv, 1, nsteps));
-    };
-    auto kloop = [&](const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int nsteps, const char* bbase) {
-        auto step = [&](f32x4 (&Aa)[2][QM], f32x4 (&Bc)[2][QN], f32x4 (&Bn)[2][QN], int g) {
-            const char* nbrow = bbase + g_row(tlv, g + 1, nsteps) * RSB;
-            ldB(Bn, nbrow, (g + 1) % H);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(Aa, Bc);
-            __builtin_amdgcn_sched_barrier(0);
-            ldA(rW, Aa, g_off(tlv, g + 2, nsteps));
-        };
-        ldB(B0, bbase + g_row(tlv, 0, nsteps) * RSB, 0);
-        int g = 0;
-        for (; g + 1 < nsteps; g += 2) { step(A0, B0, B1, g); step(A1, B1, B0, g + 1); }
-        if (g < nsteps) step(A0, B0, B1, g);
-    };
-    auto wg_max = [&](float mx, int slot) -> float {        // workgroup maximum through LDS (one barrier)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        if (lane == 0) red[slot + wave] = mx;
-        ev_lds_barrier();
-        return fmaxf(fmaxf(red[slot], red[slot + 1]), fmaxf(red[slot + 2], red[slot + 3]));
-    };
-
-    // ---------------- phase 1: c1 over lrelu(x); X tile rows [g0 - h1, g0 + NT + h1), all channels, loaded once
-    const __amdgpu_buffer_rsrc_t rW1 = ev_rsrc(pp.W1q), rW2 = ev_rsrc(p.Wq);
-    const int ng1 = pp.ntaps1 * H, ng2 = p.ntaps * H;
-    const int2 tlv1 = (lane < pp.ntaps1) ? pp.taplist1[lane] : make_int2(0, 0);
-    const int2 tlv2 = (lane < p.ntaps) ? p.taplist[lane] : make_int2(0, 0);
-    ring_fill(rW1, tlv1, ng1);
-    float sx;
-    {
-        const int xrows = NT + 2 * pp.h1;
-        f32x4 xg[XPASS];
-        float mx = 0.f;
-#pragma unroll
-        for (int q = 0; q < XPASS; ++q) {
-            const int r = q * RPS + srow;
-            const int gr = g0 - pp.h1 + r;
-            xg[q] = ev_bload4(rX, ((r < xrows && gr >= 0 && gr < p.nrows) ? (unsigned)gr * (unsigned)p.ldx : 0u) * 4u + (unsigned)sc4 * 4u, 0);   // (row 0 is a zero pad row)
-        }
-#pragma unroll
-        for (int q = 0; q < XPASS; ++q) mx = fmaxf(mx, evh_absmax4(xg[q]));
-        float tmx = wg_max(mx, 0);                      // (|lrelu(x)| <= |x|)
-        if (!evh_is_finite(tmx)) {                      // an Inf in the tile (workgroup-uniform): the finite maximum sets the scale
-            mx = 0.f;
-#pragma unroll
-            for (int q = 0; q < XPASS; ++q) mx = fmaxf(mx, evh_absmax4_finite(xg[q]));
-            tmx = wg_max(mx, 8);
-        }
-        sx = evh_scale_for(tmx);
-        am.rlo = am.rhi = tmx;                          // the residual IS this tile's input: its bound for the amax slots is the tile maximum just found (no slots of X needed)
-#pragma unroll
-        for (int q = 0; q < XPASS; ++q) {
-            const int r = q * RPS + srow;
-            f32x4 v = xg[q];
-            v[0] = ev_lrelu(v[0], p.pro_slope); v[1] = ev_lrelu(v[1], p.pro_slope);
-            v[2] = ev_lrelu(v[2], p.pro_slope); v[3] = ev_lrelu(v[3], p.pro_slope);
-            uint2 q0v, q1v;
-            evh_split4(v * sx, q0v, q1v);
-            if (r < xrows) {
-                char* dst = Xb + r * RSB + sc4 * 2;
-                *(uint2*)(dst) = q0v; *(uint2*)(dst + 2 * C) = q1v;
-            }
-        }
-    }
-    const float u1 = pp.w1h_scale * sx;
-    acc_init(pp.b1, u1);
-    ev_lds_barrier();
-    kloop(rW1, tlv1, ng1, Xb + (wn * (TN * 32) + f16i + pp.h1) * RSB + 16 * kg);
-    ring_fill(rW2, tlv2, ng2);                           // c2's first fragments fly under the hand-over below
-
-    // ---------------- y1 = lrelu(c1 + b1), zero outside the utterance; its maximum over the workgroup -> sy; split into LDS rows r + h2
-    float sy;
-    {
-        const float inv1 = 1.0f / u1;
-        float my = 0.f;
-#pragma unroll
-        for (int b = 0; b < QN; ++b) {
-            const int r = wn * (TN * 32) + b * 16 + f16i;
-            const int n = g0 + r;
-            const int t = (n >= 0 && n < p.nrows) ? (n % p.S) - p.P : -1;
-            const float inside = (t >= 0 && t < p.T) ? inv1 : 0.f;
-#pragma unroll
-            for (int a = 0; a < QM; ++a)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float v = ev_lrelu(acc[a][b][e] * inside, pp.mid_slope);    // (back to true units; 0 outside the utterance)
-                    acc[a][b][e] = v;
-                    my = fmaxf(my, fabsf(v));
-                }
-        }
-        float tmy = wg_max(my, 4);                      // (the barrier inside: every wave is done reading the X tile)
-        if (!evh_is_finite(tmy)) {
-            my = 0.f;
-#pragma unroll
-            for (int a = 0; a < QM; ++a)
-#pragma unroll
-                for (int b = 0; b < QN; ++b) my = fmaxf(my, evh_absmax4_finite(acc[a][b]));
-            tmy = wg_max(my, 12);
-        }
-        sy = evh_scale_for(tmy);
-#pragma unroll
-        for (int b = 0; b < QN; ++b) {
-            const int r = wn * (TN * 32) + b * 16 + f16i;
-#pragma unroll
-            for (int a = 0; a < QM; ++a) {
-                uint2 q0v, q1v;
-                evh_split4(acc[a][b] * sy, q0v, q1v);
-                char* dst = Xb + (r + pp.h2) * RSB + (wm * 32 + a * 16 + 4 * kg) * 2;
-                *(uint2*)(dst) = q0v; *(uint2*)(dst + 2 * C) = q1v;
-            }
-        }
-        // the 2 h2 border rows only feed outputs outside the stored window, but must be finite: zero both planes
-        for (int i = tid; i < 2 * pp.h2 * (4 * C / 16); i += 256) {
-            const int br = i / (4 * C / 16), c16 = i % (4 * C / 16);
-            const int row = br < pp.h2 ? br : NT + br;
-            uint4 z = {0u, 0u, 0u, 0u};
-            *(uint4*)(Xb + row * RSB + c16 * 16) = z;
-        }
-    }
-    const float u2 = p.wh_scale * sy;
-    acc_init(p.bias, u2);
-    ev_lds_barrier();
-
-    // ---------------- phase 2: c2 over the LDS-resident y1 (tap offset t reads rows r + h2 + t)
-    kloop(rW2, tlv2, ng2, Xb + (wn * (TN * 32) + f16i + pp.h2) * RSB + 16 * kg);
-    {
-        const float inv2 = 1.0f / u2;
-#pragma unroll
-        for (int a = 0; a < QM; ++a)
-#pragma unroll
-            for (int b = 0; b < QN; ++b) acc[a][b] *= inv2;
-    }
-    ev_amax_from_acc_q<QM, QN>(p, am, acc, g0 + wn * (TN * 32), lane);
-    conv_epilogue_lean_q<TM, TN, LEAN>(p, acc, smem + wave * (32 * (TM * 32 + 4)), wm * 32, g0 + wn * (TN * 32), lane, n0, n0 + pp.out_rows);
-    ev_amax_emit(p, am, g0 + wn * (TN * 32), TN * 32, lane);
-}
-
-// ---------------------------------------------------------------------------
 // Wave / block reductions (64-wide wavefronts)
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float wave_max(float v) {
@@ -4053,8 +3782,9 @@ struct GNParams {
     int S, P, T, CG; int mode; float eps;
 };
 
-template <int NTHR, bool PRE = false>
+template <int NTHR, bool PRE = false>   // (PRE is false only: the parameter keeps the kernel's name, see conv_gemm_kernel's KB)
 __global__ __launch_bounds__(NTHR) void groupnorm_mish_kernel(const GNParams p) {
+    static_assert(!PRE, "the residual and the mask are read in the apply phase");
     __shared__ float red[NTHR / 64];
     const int b = blockIdx.x, g = blockIdx.y;
     const int tid = threadIdx.x;
@@ -4065,19 +3795,12 @@ __global__ __launch_bounds__(NTHR) void groupnorm_mish_kernel(const GNParams p) 
     const int cbase = g * p.CG + c4;
     const float cnt = (float)p.T * (float)p.CG;
     // The (T x 32-channel) slab of one (utterance, group) is read from HBM/L2 ONCE and kept in registers when it fits
-    // (T <= GN_REG_PASSES * rows-per-pass: 768 frames with 256 threads, 1024 with the 1024-thread build used for small batches); longer utterances fall
+    // (T <= GN_REG_PASSES * rows-per-pass: 768 frames with 512 threads, 1024 with the 1024-thread build used for small batches); longer utterances fall
     // back to three passes over the (L2-resident) slab.
-    constexpr int GN_REG_PASSES = NTHR == 256 ? 24 : (NTHR == 512 ? 12 : 8);
+    static_assert(NTHR == 512 || NTHR == 1024, "512 threads, or 1024 for small batches");
+    constexpr int GN_REG_PASSES = NTHR == 512 ? 12 : 8;
     const bool in_regs = p.T <= GN_REG_PASSES * rpp;
     f32x4 keep[GN_REG_PASSES];
-
-    // The residual rows (mode 2) and the frame mask do not depend on the statistics: on the register-resident path they are requested
-    // together with the slab, so that the apply phase after the two reductions is arithmetic and stores only (one memory round trip
-    // less on every workgroup's critical chain).  An A/B build (EV_GN_PRE=1): measured slower at batch 64 — its 141 registers halve the
-    // workgroups per CU — and not the default.
-    // (PRE: only with >= 512 threads — the 256-thread build keeps 24 slab passes and has no registers left for it)
-    f32x4 rkeep[PRE ? GN_REG_PASSES : 1];
-    float mkeep[PRE ? GN_REG_PASSES : 1];
     float s = 0.f;
     if (in_regs) {
 #pragma unroll
@@ -4086,15 +3809,6 @@ __global__ __launch_bounds__(NTHR) void groupnorm_mish_kernel(const GNParams p) 
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (t < p.T) v = *(const f32x4*)(p.X + (rowbase + t) * p.ldx + cbase);
             keep[q] = v;
-            if constexpr (PRE) {
-                f32x4 r = {0.f, 0.f, 0.f, 0.f};
-                float m = 0.f;
-                if (t < p.T) {
-                    m = p.rowmask[rowbase + t];
-                    if (p.mode == 2) r = *(const f32x4*)(p.R + (rowbase + t) * p.ldr + cbase);
-                }
-                rkeep[q] = r; mkeep[q] = m;
-            }
             s += (v[0] + v[1]) + (v[2] + v[3]);
         }
     } else {
@@ -4150,23 +3864,7 @@ __global__ __launch_bounds__(NTHR) void groupnorm_mish_kernel(const GNParams p) 
 #pragma unroll
         for (int q = 0; q < GN_REG_PASSES; ++q) {
             const int t = r0 + q * rpp;
-            if constexpr (PRE) {
-                if (t < p.T) {
-                    const float m = mkeep[q];
-                    f32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float y = (keep[q][e] - mean) * rstd * ga[e] + be[e];
-                        y = ev_mish(y) * m;
-                        if (p.mode == 1) y = (y + te[e]) * m;
-                        o[e] = y;
-                    }
-                    if (p.mode == 2) { o[0] += rkeep[q][0]; o[1] += rkeep[q][1]; o[2] += rkeep[q][2]; o[3] += rkeep[q][3]; }
-                    *(f32x4*)(p.Y + (rowbase + t) * p.ldy + cbase) = o;
-                }
-            } else {
-                if (t < p.T) apply(t, keep[q]);
-            }
+            if (t < p.T) apply(t, keep[q]);
         }
     } else {
         for (int t = r0; t < p.T; t += rpp) apply(t, *(const f32x4*)(p.X + (rowbase + t) * p.ldx + cbase));
@@ -4685,9 +4383,6 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_split_kernel(const MlpParams mp
     const unsigned pslot = (unsigned)mp.sk.part_floats * 8u;
     const unsigned pelem = (unsigned)(wave * 16) * 1024u + wlane;      // element (wave, a, j, q) of a partial tile = 64 lanes x 16 B
     bool pend_pub = false;
-    int nst = 0;                                       // diagnostic (EV_MLP_STAMPS): up to 32 s_memrealtime stamps per workgroup
-    auto stamp = [&]() { if (p.stamps && tid == 0 && nst < 32) p.stamps[32 * g + nst] = __builtin_amdgcn_s_memrealtime(); ++nst; };
-    stamp();
     constexpr int PA[9] = {2, 1, 2, 0, 2, 1, 0, 1, 0}, PB[9] = {2, 2, 1, 2, 0, 1, 1, 0, 0};
 
     while (u < ue) {
@@ -4727,7 +4422,6 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_split_kernel(const MlpParams mp
         }
         if (pend_pub) { sk_publish(mp.sk, g, tag, tid); pend_pub = false; }   // (drain + barrier + flag: the barrier also publishes the staged rows)
         else ev_lds_barrier();
-        stamp();
 
         int cA = c0, cB = c1;
         bool spilled = false;
@@ -4804,7 +4498,7 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_split_kernel(const MlpParams mp
                     // the next slab and the refill of the ring set consumed one step EARLIER (its registers are free) — are interleaved with
                     // the step's MFMAs by an explicit schedule (sched_group_barrier: 2 MFMAs, 1 LDS read, [1 fragment load]).  The set
                     // consumed by a phase's last step is refilled by the first step of whatever phase comes next (sets 6 and 7: a re-load of
-                    // what is already there is harmless).  Per-phase stamps (EV_MLP_STAMPS, profiles/r03_ln_mlp_split_stamps.txt): 3.9 us per
+                    // what is already there is harmless).  Per-phase stamps (profiles/r03_ln_mlp_split_stamps.txt): 3.9 us per
                     // phase 1 = 245 ns per slab, where twelve MFMAs alone take 219 ns at the clock the chip holds under bf16 MFMA load
                     // (tools/mfma_chain_probe.hip: 18.3 ns each, i.e. 32 cycles at ~1.75 GHz) and the probe's loop with the same loads 315 ns.
                     const bool nq1 = p2 || hc + 1 >= cB;                       // what follows this phase 1: a phase 2 (of chunk nx1) or the next chunk's phase 1
@@ -4831,7 +4525,6 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_split_kernel(const MlpParams mp
 #undef EVX_P1
 #pragma unroll
                     for (int j = 0; j < 2; ++j) acc1[j] += acc1b[j];
-                    stamp();
 #pragma unroll
                     for (int q = 0; q < 4; ++q) bq[q] = ev_bload4(rB1, coff + (unsigned)(htn * 32 + 8 * q) * 4u, 0);   // next chunk's bias
                 }
@@ -4887,7 +4580,6 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_split_kernel(const MlpParams mp
 #pragma unroll
                     for (int jq = 0; jq < 8; ++jq) snake(jq);
                 }
-                stamp();
                 if (p1) {
                     ev_lds_barrier();        // every wave is done reading the previous chunk's planes (its phase 2)
 #pragma unroll
@@ -4896,7 +4588,6 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_split_kernel(const MlpParams mp
                         *(uint2*)(dst) = hq[jq][0]; *(uint2*)(dst + 2 * HC) = hq[jq][1]; *(uint2*)(dst + 4 * HC) = hq[jq][2];
                     }
                     ev_lds_barrier();
-                    stamp();
                 }
             }
             auto acc_io = [&](unsigned base, int mode) {    // mode 0: store (write-through), 1: add from memory
@@ -5020,9 +4711,6 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_h16_kernel(const MlpParams mp) 
     const unsigned pslot = (unsigned)mp.sk.part_floats * 8u;
     const unsigned pelem = (unsigned)(wave * 16) * 1024u + wlane;      // element (wave, a, j, q) of a partial tile = 64 lanes x 16 B
     bool pend_pub = false;
-    int nst = 0;                                       // diagnostic (EV_MLP_STAMPS): up to 32 s_memrealtime stamps per workgroup
-    auto stamp = [&]() { if (p.stamps && tid == 0 && nst < 32) p.stamps[32 * g + nst] = __builtin_amdgcn_s_memrealtime(); ++nst; };
-    stamp();
     constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};
 
     while (u < ue) {
@@ -5088,7 +4776,6 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_h16_kernel(const MlpParams mp) 
         }
         if (pend_pub) { sk_publish(mp.sk, g, tag, tid); pend_pub = false; }   // (drain + barrier + flag: the barrier also publishes the staged rows)
         else ev_lds_barrier();
-        stamp();
 
         int cA = c0, cB = c1;
         bool spilled = false;
@@ -5171,7 +4858,7 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_h16_kernel(const MlpParams mp) 
                     // the next slab and the refill of the ring set consumed one step EARLIER (its registers are free) — are interleaved with
                     // the step's MFMAs by an explicit schedule (sched_group_barrier: 2 MFMAs, 1 LDS read, [1 fragment load]).  The set
                     // consumed by a phase's last step is refilled by the first step of whatever phase comes next (sets 6 and 7: a re-load of
-                    // what is already there is harmless).  Per-phase stamps (EV_MLP_STAMPS, profiles/r03_ln_mlp_split_stamps.txt): 3.9 us per
+                    // what is already there is harmless).  Per-phase stamps (profiles/r03_ln_mlp_split_stamps.txt): 3.9 us per
                     // phase 1 = 245 ns per slab, where twelve MFMAs alone take 219 ns at the clock the chip holds under bf16 MFMA load
                     // (tools/mfma_chain_probe.hip: 18.3 ns each, i.e. 32 cycles at ~1.75 GHz) and the probe's loop with the same loads 315 ns.
                     const bool nq1 = p2 || hc + 1 >= cB;                       // what follows this phase 1: a phase 2 (of chunk nx1) or the next chunk's phase 1
@@ -5198,7 +4885,6 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_h16_kernel(const MlpParams mp) 
 #undef EVX_P1
 #pragma unroll
                     for (int j = 0; j < 2; ++j) acc1[j] = (acc1[j] + acc1b[j]) * inv1;      // back to true units
-                    stamp();
 #pragma unroll
                     for (int q = 0; q < 4; ++q) bq[q] = ev_bload4(rB1, coff + (unsigned)(htn * 32 + 8 * q) * 4u, 0);   // next chunk's bias
                 }
@@ -5265,7 +4951,6 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_h16_kernel(const MlpParams mp) 
 #pragma unroll
                     for (int jq = 0; jq < 8; ++jq) snake(jq);
                 }
-                stamp();
                 if (p1) {
 #pragma unroll
                     for (int o = 32; o > 0; o >>= 1) hmax = fmaxf(hmax, __shfl_xor(hmax, o, 64));
@@ -5292,7 +4977,6 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_h16_kernel(const MlpParams mp) 
                         *(uint2*)(dst) = q0v; *(uint2*)(dst + 2 * HC) = q1v;
                     }
                     ev_lds_barrier();
-                    stamp();
                 }
             }
             {   // back to true units: partial tiles are handed over, spilled and stored in them
@@ -5370,7 +5054,7 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_h16_kernel(const MlpParams mp) 
 // L2 three slabs ahead.  The accumulators run in units of w1_scale * sx and return to true units before the lean epilogue (two calls:
 // its lane map needs a channel count that divides 256).
 // ---------------------------------------------------------------------------
-template <int DBG = 0>   // diagnostic build (EV_QKV_DBG=1): no weight-fragment loads inside the K loop
+template <int UNUSED = 0>   // (the parameter keeps the kernel's name, see conv_gemm_kernel's KB)
 __global__ __launch_bounds__(256, 2) void ln_qkv_h16_kernel(const MlpParams mp) {
     constexpr int NT = 64, C = 256, TM = 3;
     constexpr int XRS = 4 * C + 16;
@@ -5384,8 +5068,6 @@ __global__ __launch_bounds__(256, 2) void ln_qkv_h16_kernel(const MlpParams mp) 
     const __amdgpu_buffer_rsrc_t rX = ev_rsrc(mp.X), rW1 = ev_rsrc(mp.W1h), rB1 = ev_rsrc(mp.b1);
     const unsigned wlane = (unsigned)lane * 16u;
     const int n0 = blockIdx.x * NT;
-    auto stamp = [&](int i) { if (p.stamps && tid == 0) p.stamps[8 * blockIdx.x + i] = __builtin_amdgcn_s_memrealtime(); };   // diagnostic (EV_QKV_STAMPS)
-    stamp(0);
     {   // tiles that contain no storable row (pure padding) do nothing
         int t_first = (n0 % p.S) - p.P;
         int dist;
@@ -5427,7 +5109,6 @@ __global__ __launch_bounds__(256, 2) void ln_qkv_h16_kernel(const MlpParams mp) 
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
         if (lane == 0) red[wave] = mx;
-        stamp(1);
         ev_lds_barrier();
         float tmx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         if (!evh_is_finite(tmx)) {                      // (workgroup-uniform slow path, see evh_is_finite)
@@ -5450,7 +5131,6 @@ __global__ __launch_bounds__(256, 2) void ln_qkv_h16_kernel(const MlpParams mp) 
         }
     }
     ev_lds_barrier();
-    stamp(2);
     const float u1 = mp.w1_scale * sx, inv1 = 1.0f / u1;
     f32x16 acc[TM][2];
 #pragma unroll
@@ -5474,7 +5154,7 @@ __global__ __launch_bounds__(256, 2) void ln_qkv_h16_kernel(const MlpParams mp) 
 #pragma unroll
     for (int sl = 0; sl < 16; ++sl) {
         if (sl + 1 < 16) ldB(B[(sl + 1) & 1], sl + 1);
-        if (DBG != 1 && sl + 3 < 16) ldA(A[(sl + 3) & 3], sl + 3);
+        if (sl + 3 < 16) ldA(A[(sl + 3) & 3], sl + 3);
 #pragma unroll
         for (int tt = 0; tt < 3; ++tt)
 #pragma unroll
@@ -5513,7 +5193,6 @@ __global__ __launch_bounds__(256, 2) void ln_qkv_h16_kernel(const MlpParams mp) 
                 }
         }
     }
-    stamp(3);
     // ---- store (the epilogue's first barrier retires the K loop's LDS reads; its slabs lie in the dead X planes)
     {
         f32x16 a2[2][2];
@@ -5523,14 +5202,12 @@ __global__ __launch_bounds__(256, 2) void ln_qkv_h16_kernel(const MlpParams mp) 
             for (int j = 0; j < 2; ++j) a2[i][j] = acc[i][j];
         conv_epilogue_lean<2, 2, 1>(p, a2, smem + wave * (32 * 68), wave * 96, n0, lane);
     }
-    stamp(4);
     {
         f32x16 a1[1][2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) a1[0][j] = acc[2][j];
         conv_epilogue_lean<1, 2, 1>(p, a1, smem + wave * (32 * 68), wave * 96 + 64, n0, lane);
     }
-    stamp(5);
 }
 
 // ---------------------------------------------------------------------------
@@ -5693,7 +5370,6 @@ struct AttnOutParams {
     int ntail;                  // > 0: the last tile holds only ntail (<= 4) queries and is computed by one small workgroup per utterance on
                                 // 4 x 4 MFMA blocks (blocks 0 .. B-1 of the grid, dispatched first): see attn_tail_path
     float scale; int xcd_map;   // xcd_map: B % 8 == 0 -> the tiles of an utterance share an XCD (its K / V stay in that XCD's L2)
-    unsigned long long* stamps; // diagnostic (EV_ATTN_STAMPS): six s_memrealtime stamps per workgroup, or null
     // attn_out_h16_kernel: QKV holds fp16 piece pairs times the powers of two sq / sk / sv (ln_qkv_h16_kernel, qkv_pack)
     float inv_sq, inv_sk, inv_sv;
     float mask_a, mask_b;       // powers of two, both fp16 numbers, mask_a mask_b = 8 sq sk (the frame mask in accumulator units)
@@ -5893,9 +5569,7 @@ __global__ __launch_bounds__(256, 2) void attn_out_kernel(const AttnOutParams p)
         int id = blockIdx.x;
         const int ntw = p.ntail > 0 ? p.B : 0;         // the short last tiles first: small 4 x 4-block workgroups (attn_tail_path)
         if (id < ntw) {
-            if (p.stamps && tid == 0) p.stamps[6 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
             attn_tail_path(p, p.xcd_map ? (id & 7) + 8 * (id >> 3) : id, smem, tid, lane, wave);
-            if (p.stamps && tid == 0) { const unsigned long long t = __builtin_amdgcn_s_memrealtime(); for (int k = 1; k < 6; ++k) p.stamps[6 * blockIdx.x + k] = t; }
             return;
         }
         id -= ntw;                                     // (B % 8 == 0 under xcd_map: the XCD of a block id is unchanged)
@@ -5904,8 +5578,6 @@ __global__ __launch_bounds__(256, 2) void attn_out_kernel(const AttnOutParams p)
     }
     const int q0 = qt * 32;
     const unsigned rowbase = (unsigned)b * p.S + p.P;
-    auto stamp = [&](int k) { if (p.stamps && tid == 0) p.stamps[6 * blockIdx.x + k] = __builtin_amdgcn_s_memrealtime(); };
-    stamp(0);
     float* Ks = smem + wave * (2 * 32 * AO_LDK);       // this wave's private K tile [32 keys][64 + 4]
     float* Vs = Ks + 32 * AO_LDK;                      // ... and V tile
     const __amdgpu_buffer_rsrc_t rQ = ev_rsrc(p.QKV), rM = ev_rsrc(p.rowmask), rW = ev_rsrc(p.Wout);
@@ -5946,7 +5618,6 @@ __global__ __launch_bounds__(256, 2) void attn_out_kernel(const AttnOutParams p)
     float mrun = -1e30f, lrun = 0.f;
     if (kt0 < kt1) kv_issue(kt0);
     for (int kt = kt0; kt < kt1; ++kt) {
-        if (kt == kt0 + 1) stamp(1);                   // (first key tile done)
         // publish the prefetched tile to this wave's LDS (the wave's LDS operations execute in order: no barrier, no other reader)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -5992,7 +5663,6 @@ __global__ __launch_bounds__(256, 2) void attn_out_kernel(const AttnOutParams p)
             o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, s[r], o1, 0, 0, 0);
         }
     }
-    stamp(2);
     // ---- first weight fragments of the projection (this wave: output channels 64 wave .. +63 = row tiles 2 wave, 2 wave + 1; 16
     // k-groups), into the staging registers: they land while the key halves are merged
     const unsigned wlane = (unsigned)lane * 16u;
@@ -6039,7 +5709,6 @@ __global__ __launch_bounds__(256, 2) void attn_out_kernel(const AttnOutParams p)
         }
     }
     ev_lds_barrier();
-    stamp(3);
     // ---- projection: Y^T[256][32] = Wout . O^T, K = 128 = 16 k-groups; bias preloaded into the accumulators (lean epilogue convention)
     f32x16 acc[2][1];
 #pragma unroll
@@ -6063,10 +5732,8 @@ __global__ __launch_bounds__(256, 2) void attn_out_kernel(const AttnOutParams p)
         }
         if (kg < 8) { kr[kg] = ldW(0, kg + 8); vr[kg] = ldW(1, kg + 8); }
     }
-    stamp(4);
     // ---- + residual rows, store (rows of THIS utterance only: a tile's tail rows may belong to the next one)
     conv_epilogue_lean<2, 1, 1>(p.ep, acc, smem + wave * (32 * 68), wave * 64, (int)rowbase + q0, lane, (int)rowbase, (int)rowbase + p.T);
-    stamp(5);
 }
 
 // ---------------------------------------------------------------------------
@@ -6107,9 +5774,7 @@ __global__ __launch_bounds__(256, 2) void attn_out_h16_kernel(const AttnOutParam
         int id = blockIdx.x;
         const int ntw = p.ntail > 0 ? p.B : 0;         // the short last tiles first, on the fp32 4 x 4 blocks (attn_tail_path decodes the pairs)
         if (id < ntw) {
-            if (p.stamps && tid == 0) p.stamps[6 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
             attn_tail_path<true>(p, p.xcd_map ? (id & 7) + 8 * (id >> 3) : id, smem, tid, lane, wave);
-            if (p.stamps && tid == 0) { const unsigned long long t = __builtin_amdgcn_s_memrealtime(); for (int k = 1; k < 6; ++k) p.stamps[6 * blockIdx.x + k] = t; }
             return;
         }
         id -= ntw;
@@ -6118,8 +5783,6 @@ __global__ __launch_bounds__(256, 2) void attn_out_h16_kernel(const AttnOutParam
     }
     const int q0 = qt * 32;
     const unsigned rowbase = (unsigned)b * p.S + p.P;
-    auto stamp = [&](int k) { if (p.stamps && tid == 0) p.stamps[6 * blockIdx.x + k] = __builtin_amdgcn_s_memrealtime(); };
-    stamp(0);
     char* Kt = (char*)smem + wave * AOH_WB;            // [32 keys][AOH_KRS]: the key rows of head h as they lie in the packed tensor
     char* Vt = Kt + 32 * AOH_KRS;                      // [32 keys][AOH_VRS]
     const __amdgpu_buffer_rsrc_t rQ = ev_rsrc(p.QKV), rM = ev_rsrc(p.rowmask), rW = ev_rsrc(p.Wouth);
@@ -6192,7 +5855,6 @@ __global__ __launch_bounds__(256, 2) void attn_out_h16_kernel(const AttnOutParam
                                                                                                        2 * (16 * ((lane >> 4) & 1) + 4 * (lane & 3)));
     const char* krow = Kt + li * AOH_KRS + 16 * lh;
     for (int kt = kt0; kt < kt1; ++kt) {
-        if (kt == kt0 + 1) stamp(1);
         // publish the prefetched tile to this wave's LDS (the wave's LDS operations execute in order: no barrier, no other reader)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -6261,7 +5923,6 @@ __global__ __launch_bounds__(256, 2) void attn_out_h16_kernel(const AttnOutParam
     }
     lrun += __shfl_xor(lrun, 32, 64);
     const float mrun = mref;
-    stamp(2);
     // hi column row + lo column row: od[m][a] = dims 16 m + 4 a + 2 lh + (0, 1) of query li, un-normalised, in units of 2^13 sv
     float od[4][4][2];
 #pragma unroll
@@ -6322,7 +5983,6 @@ __global__ __launch_bounds__(256, 2) void attn_out_h16_kernel(const AttnOutParam
             }
     }
     ev_lds_barrier();
-    stamp(3);
     // ---- projection: Y^T[256][32] = Wout . O^T, K = 128 = 8 steps of 16, three piece products; accumulators in units of wo_scale sv,
     // bias preloaded (lean epilogue convention)
     const float u = p.wo_scale / p.inv_sv, inv_u = 1.0f / u;
@@ -6359,11 +6019,9 @@ __global__ __launch_bounds__(256, 2) void attn_out_h16_kernel(const AttnOutParam
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[a][0][r] *= inv_u;
-    stamp(4);
     };
     // ---- + residual rows, store (rows of THIS utterance only: a tile's tail rows may belong to the next one)
     conv_epilogue_lean<2, 1, 1>(p.ep, acc, smem + wave * (32 * 68), wave * 64, (int)rowbase + q0, lane, (int)rowbase, (int)rowbase + p.T, merge_project);
-    stamp(5);
 }
 
 // attention_part_kernel + attention_merge_kernel: the small-launch build of attention_kernel.  A batch-1 decode has 6-10

@@ -207,13 +207,17 @@ int ev_profile_read_split(ev_handle *h, double *ms, double *flops, int64_t *laun
 int ev_set_arithmetic(ev_handle *h, int setting);
 int ev_get_arithmetic(ev_handle *h);
 
-/* Test hook: the build the last conv / fused-pair launch of this handle took (tile configuration id: 40 / 60 = conv_split_kernel /
- * its balanced grid, 140 + taps = resblock_pair_split_kernel, 100 + taps = resblock_pair_kernel, others: see launch_conv). */
+/* Test hook: the build the last conv / fused-pair launch of this handle took (tile configuration id: 0 / 1 / 2 / 5 / 6 / 8 = conv_gemm_kernel
+ * tiles, 56 = the balanced 64 x 64 grid, 9 / 19 = the split-K small-launch builds, 40 / 60 = conv_split_kernel / its balanced grid, 46 / 47 / 66 =
+ * the fp16 builds, 140 + taps = resblock_pair_split_kernel, 160 + taps = resblock_pair_h16_kernel, 100 + taps = resblock_pair_kernel, others:
+ * see launch_conv). */
 int ev_dbg_last_cfg(ev_handle *h);
 
 /* Kernel microbenchmark hook (tools/conv_bench.py, not part of the product path): times `iters` launches of one
  * resblock-style conv (prologue leaky-relu, bias, residual) at a given geometry with HIP events on the default stream;
- * dbg = ablation bits, cfg = forced tile configuration (< 0: the engine's own choice). */
+ * dbg = ablation bits, cfg = forced tile configuration + 100 x workgroups per CU (< 0: the engine's own choice).  A forced
+ * configuration must be one launch_conv selects (0, 1, 2, 5, 6, 8, 9, 19, 40, 41, 43, 46, 49, 60); any other value, and the
+ * retired two-chunk staging (cfg >= 1000), fails the call.  EV_FORCE_CFG takes the same values. */
 int ev_dbg_conv_bench(ev_handle *h, int Cin, int Cout, int K, int dil, int B, int T, int P, int iters, int dbg, int cfg, float *ms_out);
 
 /* Diagnostic / A-B switch: the fp16 builds need max |x| over the rows a tile stages.  on = 1 (default): they take it from the bounds their

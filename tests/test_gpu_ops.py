@@ -97,6 +97,45 @@ def test_conv1d_split_builds(eng, B, Cin, T, Cout, K, dil, slope, cfg):
         eng.set_arithmetic(orig)
 
 
+def test_forced_tile_configuration_is_a_selectable_build(monkeypatch):
+    """EV_FORCE_CFG (read by ev_create) and ev_dbg_conv_bench's cfg take only the builds launch_conv selects: such a build runs and matches
+    torch; any other value — a retired probe tile, or cfg >= 1000 (the retired two-chunk staging) — fails the call with a message naming it."""
+    import ctypes as C
+
+    from emojivoice_amd._lib import Engine, EvLibraryError
+
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(2, 64, 300, generator=g)
+    w = torch.randn(64, 64, 3, generator=g) / 192 ** 0.5
+    b = torch.randn(64, generator=g)
+    ref = F.conv1d(x, w, b, padding=1)
+    monkeypatch.setenv("EV_FORCE_CFG", "5")
+    e = Engine(0)
+    try:
+        _close(e.op_conv1d(x.cuda(), w, b, padding=1), ref, what="forced cfg 5")
+        assert e.last_cfg() == 5
+    finally:
+        e.close()
+    monkeypatch.setenv("EV_FORCE_CFG", "4")
+    e = Engine(0)
+    try:
+        with pytest.raises(EvLibraryError, match="forced tile configuration 4 "):
+            e.op_conv1d(x.cuda(), w, b, padding=1)
+    finally:
+        e.close()
+    monkeypatch.delenv("EV_FORCE_CFG")
+    e = Engine(0)
+    try:
+        ms = C.c_float()
+        for cfg, ok in ((-1, True), (1, True), (7, False), (1001, False)):
+            rc = e.lib.ev_dbg_conv_bench(e.h, 64, 64, 3, 1, 2, 256, 8, 1, 0, cfg, C.byref(ms))
+            assert (rc == 0) == ok, (cfg, rc)
+            if not ok:
+                assert f"forced tile configuration {cfg} " in e.lib.ev_last_error(e.h).decode()
+    finally:
+        e.close()
+
+
 @pytest.mark.parametrize("B,Cin,T,Cout,K,slope", [(64, 256, 196, 256, 3, -1.0), (64, 256, 194, 256, 3, 0.1), (64, 512, 196, 256, 1, -1.0), (48, 256, 283, 256, 3, -1.0)])
 def test_conv1d_balanced_grid(eng, B, Cin, T, Cout, K, slope, monkeypatch):
     """Dense conv launches of about one round of workgroups take conv_gemm_bal_kernel (a balanced persistent grid over (tile,

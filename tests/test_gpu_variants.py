@@ -1,4 +1,4 @@
-"""The kernel A/B switches (tile configuration, two-chunk staging, generic instead of lean epilogue, unfused resblock pairs,
+"""The kernel A/B switches (tile configuration, generic instead of lean epilogue, unfused resblock pairs,
 fused LayerNorm + QKV / feed-forward kernels forced on at a small batch or switched off, split-key attention switched off,
 the three ResBlock1 chains of an MRF level on one stream instead of three, the workspace zeroed whole instead of its pad rows,
 the balanced persistent grids and the fused attention + projection kernel at batch 64, and EV_SPLIT=0: every conv on the fp32 MFMA
@@ -39,8 +39,8 @@ wav = voc(mel if B < 64 else mel[:4])
 torch.save({"mel": mel.cpu(), "wav": wav.cpu()}, sys.argv[1])
 """ % REPO
 
-VARIANTS = [{"EV_KB": "2"}, {"EV_NO_LEAN": "1"}, {"EV_FUSE_PAIRS": "0"}, {"EV_FORCE_CFG": "0"}, {"EV_FORCE_CFG": "5"}, {"EV_FORCE_CFG": "6"},
-            {"EV_FORCE_CFG": "4"}, {"EV_FUSE_MLP_MIN": "1"}, {"EV_FUSE_MLP": "0"}, {"EV_NO_ATTN_SK": "1"},
+VARIANTS = [{"EV_NO_LEAN": "1"}, {"EV_FUSE_PAIRS": "0"}, {"EV_FORCE_CFG": "0"}, {"EV_FORCE_CFG": "5"}, {"EV_FORCE_CFG": "6"},
+            {"EV_FUSE_MLP_MIN": "1"}, {"EV_FUSE_MLP": "0"}, {"EV_NO_ATTN_SK": "1"},
             {"EV_MRF_STREAMS_MAX": "0"}, {"EV_FULL_REZERO": "1"}, {"EV_SPLIT": "0"}, {"EV_SPLIT": "6"}]
 
 
@@ -81,8 +81,8 @@ def test_batch1_variants_agree(tmp_path):
         assert dmel <= 2e-5 and dwav <= 5e-5, (extra, dmel, dwav)
 
 
-# batch 64: the balanced persistent builds (SkCtl in ev_kernels.h: ln_mlp_kernel, conv_gemm_bal_kernel with equal and with weighted
-# units) and the fused attention + projection kernel.  An owner that never waits (EV_SK_SPIN=0) recomputes every contributor's share
+# batch 64: the balanced persistent builds (SkCtl in ev_kernels.h: ln_mlp_kernel, conv_gemm_bal_kernel) and the fused attention +
+# projection kernel.  An owner that never waits (EV_SK_SPIN=0) recomputes every contributor's share
 # as a separate partial sum: the SAME bits.  The one-tile-per-workgroup builds differ by the order of partial sums only.
 def test_batch64_balanced_builds(tmp_path):
     ref = _run(tmp_path, "b64_default", {}, "b64")
@@ -92,7 +92,7 @@ def test_batch64_balanced_builds(tmp_path):
     nowait = _run(tmp_path, "b64_nowait", {"EV_SK_SPIN": "0"}, "b64")
     assert torch.equal(nowait["mel"], ref["mel"]) and torch.equal(nowait["wav"], ref["wav"])
     # (run-to-run equality of the default build is covered in-process by tests/test_gpu_ops.py; every switch here costs a batch-64 child)
-    for i, extra in enumerate([{"EV_NO_SK_BALANCE": "1"}, {"EV_CONV_BALANCE_W": "1", "EV_BAL5": "64"}, {"EV_FUSE_ATTN": "0", "EV_SK_WGS": "3"}, {"EV_SPLIT": "0"}, {"EV_SPLIT": "6"},
+    for i, extra in enumerate([{"EV_NO_SK_BALANCE": "1"}, {"EV_FUSE_ATTN": "0", "EV_SK_WGS": "3"}, {"EV_SPLIT": "0"}, {"EV_SPLIT": "6"},
                                {"EV_NO_QKV_H16": "1"}]):     # (LayerNorm + QKV back on the fp32 MFMA build)
         got = _run(tmp_path, f"b64_v{i}", extra, "b64")
         dmel = float((got["mel"] - ref["mel"]).abs().max())

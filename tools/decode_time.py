@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Wall time of the batch-64 CFM decode (10 steps, T = 516), median of 5: the A/B meter for switches that shape_profile.py does not time
-(GroupNorm kernels, launch gaps).    EV_GN_THREADS=512 python tools/decode_time.py"""
+(GroupNorm kernels, launch gaps).    python tools/decode_time.py [batch]"""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -645,7 +645,10 @@ __device__ __forceinline__ void ev_amax_emit(const ConvParams& p, const EvAmax& 
         if ((last >> 7) > g0) atomicMax(p.ymax + g0 + 1, bits(mhi + a.rhi + a.yhi));
     } else {                                            // a polyphase transposed conv: row n holds ymax_mul output frames — one bound for all of them
         const unsigned b = bits(fmaxf(mlo, mhi));
-        const int ga = (first * p.ymax_mul) >> 7, gb = ((last + 1) * p.ymax_mul - 1) >> 7;
+        // (last clamped to the launch's rows: a wave tile past the end would otherwise reach granule ((last + 1) * mul - 1) >> 7, beyond
+        // the (nrows * mul >> 7) + 2 slots of the output; clamped, gb <= (nrows * mul - 1) >> 7, the output's last granule)
+        const int lastc = min(last, p.nrows - 1);
+        const int ga = (first * p.ymax_mul) >> 7, gb = ((lastc + 1) * p.ymax_mul - 1) >> 7;
         for (int g = ga; g <= gb; ++g) atomicMax(p.ymax + g, b);
     }
 }

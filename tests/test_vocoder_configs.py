@@ -1,7 +1,7 @@
 """HiFi-GAN V2 / V3 and other configs inside the supported envelope: the CPU side (names, shapes, weights, envelope, ABI, code object).
 
-``restate`` is a plain-torch statement of ``matcha.hifigan.models.Generator.forward`` for ResBlock1 and ResBlock2 (models.py:80-197) at
-any config and precision; it is checked here against the reference's own output (tests/golden/vocoder_configs.npz, written by
+``restate`` (tests/vocoder_ref.py) is a plain-torch statement of ``matcha.hifigan.models.Generator.forward`` for ResBlock1 and ResBlock2
+(models.py:80-197) at any config and precision; it is checked here against the reference's own output (tests/golden/vocoder_configs.npz, written by
 tests/golden/make_vocoder_golden.py) and serves the GPU tests (test_gpu_vocoder_configs.py) as their fp64 yardstick for shapes the
 golden does not hold.  oracle.matcha_oracle.hifigan_forward knows ResBlock1 only.
 """
@@ -14,11 +14,11 @@ import re
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from emojivoice_amd import _lib
 from emojivoice_amd import weights as W
 from emojivoice_amd.hifigan import AttrDict, Generator, check_config, v1, v2, v3
+from vocoder_ref import restate  # noqa: F401  (test_gpu_vocoder_configs imports it from here)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(REPO, "tests", "golden", "vocoder_configs.npz")
@@ -32,32 +32,6 @@ def golden_vocoder():
 
 def golden_config(g, name):
     return AttrDict(json.loads(str(g[f"{name}_config"])))
-
-
-def restate(sd, mel, h, dtype=torch.float64):
-    """Generator.forward (models.py:181-197) with ResBlock1 (:80-97) or ResBlock2 (:136-141), weight norm folded."""
-    sd = {k: v.to(dtype) for k, v in sd.items()}
-    x = F.conv1d(mel.to(dtype), sd["conv_pre.weight"], sd["conv_pre.bias"], padding=3)
-    rk, rd = h["resblock_kernel_sizes"], h["resblock_dilation_sizes"]
-    nk, rb2 = len(rk), str(h["resblock"]) != "1"
-    for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
-        x = F.leaky_relu(x, 0.1)
-        x = F.conv_transpose1d(x, sd[f"ups.{i}.weight"], sd[f"ups.{i}.bias"], stride=u, padding=(k - u) // 2)
-        xs = None
-        for j, (kk, ds) in enumerate(zip(rk, rd)):
-            p, y = f"resblocks.{i * nk + j}", x
-            if rb2:
-                for m, d in enumerate(ds):
-                    y = y + F.conv1d(F.leaky_relu(y, 0.1), sd[f"{p}.convs.{m}.weight"], sd[f"{p}.convs.{m}.bias"], dilation=d, padding=(kk * d - d) // 2)
-            else:
-                for m, d in enumerate(ds):
-                    t = F.conv1d(F.leaky_relu(y, 0.1), sd[f"{p}.convs1.{m}.weight"], sd[f"{p}.convs1.{m}.bias"], dilation=d, padding=(kk * d - d) // 2)
-                    t = F.conv1d(F.leaky_relu(t, 0.1), sd[f"{p}.convs2.{m}.weight"], sd[f"{p}.convs2.{m}.bias"], padding=(kk - 1) // 2)
-                    y = y + t
-            xs = y if xs is None else xs + y
-        x = xs / nk
-    x = F.conv1d(F.leaky_relu(x), sd["conv_post.weight"], sd["conv_post.bias"], padding=3)
-    return torch.tanh(x)
 
 
 # ---- names, shapes, weights ---------------------------------------------------------------------------------------------------------------

@@ -1557,15 +1557,19 @@ int grow_ws(ev_handle* h, size_t need, bool geometric) {
 
 // make sure the arena fits (B, Tp, Tv); zero it when the geometry changes (pad rows must be zero)
 int ensure_ws(ev_handle* h, int B, int Tp, int Tv, EstBufs* eb, VocBufs* vb) {
-    // keep the other path's last shape so alternating cfm/hifigan calls do not thrash
-    if (Tp <= 0) Tp = h->ws_Tp > 0 && h->ws_B == B ? h->ws_Tp : 0;
-    if (Tv <= 0) Tv = h->ws_Tv > 0 && h->ws_B == B ? h->ws_Tv : 0;
+    // keep the other path's last shape so alternating cfm/hifigan calls do not thrash (a handle that holds graphs re-zeroes every call: no carry)
+    if (!h->captured) {
+        if (Tp <= 0) Tp = h->ws_Tp > 0 && h->ws_B == B ? h->ws_Tp : 0;
+        if (Tv <= 0) Tv = h->ws_Tv > 0 && h->ws_B == B ? h->ws_Tv : 0;
+    }
     // the workspace is shared by every call on this handle: a caller that moves to another stream must not overtake the
     // previous call's kernels (one handle = one stream user at a time, include/emojivoice.h)
     if (h->ws_stream_valid && h->ws_stream != h->stream) HIPCHK(h, hipStreamSynchronize(h->ws_stream));
     h->ws_stream = h->stream; h->ws_stream_valid = true;
     const size_t need = plan_all(h, nullptr, B, Tp, Tv, nullptr, nullptr);
-    bool rezero = (B != h->ws_B || Tp != h->ws_Tp || Tv != h->ws_Tv);
+    // ws_B / ws_Tp / ws_Tv record the last HOST call: a graph replay of another shape leaves no trace there, so every call of a handle
+    // that holds graphs (ev_cfm_decode, ev_estimator, ev_hifigan, captured or eager) re-zeroes its own plan
+    bool rezero = h->captured || B != h->ws_B || Tp != h->ws_Tp || Tv != h->ws_Tv;
     if (need > h->ws_bytes) {
         if (h->captured) return fail(h, "this handle holds a captured ev_cfm_decode: its workspace cannot be replaced (needs %zu bytes, has %zu); "
                                         "use ev_reserve before capturing, or another handle", need, h->ws_bytes);
@@ -2460,7 +2464,6 @@ static int cfm_decode_impl(ev_handle* h, const float* d_mu, const int32_t* d_len
                            "the largest shape) first — planning must not allocate under capture", B, Tp);
         h->captured = true; h->cap_B = B; h->cap_Tp = Tp;
     }
-    if (h->captured) h->ws_B = -1;          // (forces the re-zero of this call's plan: a memset + nothing else, capturable)
     EstBufs b;
     if (ensure_ws(h, B, Tp, 0, &b, nullptr)) return 1;
     // time grid exactly as torch.linspace(0, 1, n+1) + the running t / dt of solve_euler (flow_matching.py:52,70-83), in fp32

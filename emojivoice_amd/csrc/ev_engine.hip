@@ -163,7 +163,7 @@ struct ev_handle {
     bool captured = false; int cap_B = 0, cap_Tp = 0;   // a handle with a captured call stays bound to that (B, Tp): see ev_cfm_decode
     int64_t n_allocs = 0;       // device / pinned allocations made by the hot calls after loading (workspace and scratch growth, staging)
     double prof_flops = 0; int64_t prof_launches = 0;
-    struct ProfRec { int kind, Cin, Cout, ntaps, nrows, cfg, lean; double flops; };
+    struct ProfRec { int kind, Cin, Cout, ntaps, nrows, cfg, lean; double flops; bool split = false; };   // (split: a bf16 / fp16 build)
     std::vector<ProfRec> prof_recs;   // one per timed launch (EV_PROFILE_DUMP=<file> writes the per-shape table)
     hipStream_t stream = nullptr;
     // HiFi-GAN at small batch: the three ResBlock1 chains of an MRF level (kernel sizes 3 / 7 / 11, models.py:186-192) run on
@@ -515,14 +515,25 @@ inline void ensure_dyn_smem(size_t smem, int device) {
     else (void)hipGetLastError();         // (the launch that follows reports the failure through hipGetLastError)
 }
 
-template <int BM, int BN, int WM, int WN, bool PF, bool FULL, int LEAN>
-void launch_cfg2(const ConvParams& p, hipStream_t st, const LaunchOpts& lo);
+// Every launch of the section: the kernel's LDS grant, then the launch itself
+template <auto Kernel, class Params>
+inline void launch(int device, dim3 grid, dim3 block, size_t smem, hipStream_t st, const Params& p) {
+    ensure_dyn_smem<Kernel>(smem, device);
+    hipLaunchKernelGGL(Kernel, grid, block, smem, st, p);
+}
 
-// Dispatch on the epilogue flavour:
-//   lean    : y = act(acc + bias) [+ R], act in {none, lrelu, SnakeBeta}, plain row-major Y/R, Cout % 4 == 0
-//             (instruction-lean, bias preloaded into acc)
-//   compact : any flag combination without a transcendental activation (code stays I-cache resident)
-//   full    : tanh / SiLU / Mish / SnakeBeta
+// f(std::integral_constant<int, v>) for the one of Vs that equals v: a template argument chosen at run time, instantiated for the listed
+// values only (each build of the code object, and no other)
+template <int... Vs, class F>
+inline void dispatch(int v, F&& f) { (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
+
+// The epilogue flavour of a launch, the LEAN argument of its build:
+//   1 / 2 / 3 (lean): y = act(acc + bias) [+ R], act in {none, lrelu} / SnakeBeta / with the accumulate steps (accum, div3, act2_lrelu);
+//                     plain row-major Y/R, Cout % 4 == 0 (instruction-lean, bias preloaded into acc)
+//   0 (compact)     : any flag combination without a transcendental activation (code stays I-cache resident)
+//   EPI_FULL        : tanh / SiLU / Mish / SnakeBeta (FULL_ACT, LEAN 0)
+// lean: the launch may take a lean epilogue (the builds that have no other pass true)
+constexpr int EPI_FULL = -1;
 inline bool lean_acc(const ConvParams& p) { return p.accum || p.div3 || p.act2_lrelu; }
 inline bool lean_ok(const ConvParams& p) {
     if (lean_acc(p) && (!p.R || p.act != ACT_NONE)) return false;
@@ -531,25 +542,44 @@ inline bool lean_ok(const ConvParams& p) {
            !p.Y2 && (p.osplit_log2 >= 31 || (p.osplit_log2 >= 2 && (p.osstride & 3) == 0)) && (p.Cout & 3) == 0 && (p.ldy & 3) == 0 && (!p.R || (p.ldr & 3) == 0) &&
            (!p.bias || ((size_t)p.bias & 15) == 0) && !(p.dbg & 4) && p.S >= 4;   // (lean row walk: two wraps per 8-row pass)
 }
-template <int BM, int BN, int WM, int WN, bool PF = false>
-void launch_cfg(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
-    if (lo.lean && lean_ok(p)) {
-        if (p.act == ACT_SNAKE) launch_cfg2<BM, BN, WM, WN, PF, false, 2>(p, st, lo);
-        else if (lean_acc(p)) launch_cfg2<BM, BN, WM, WN, PF, false, 3>(p, st, lo);
-        else launch_cfg2<BM, BN, WM, WN, PF, false, 1>(p, st, lo);
-    } else if (p.act == ACT_NONE || p.act == ACT_LRELU) launch_cfg2<BM, BN, WM, WN, PF, false, 0>(p, st, lo);
-    else launch_cfg2<BM, BN, WM, WN, PF, true, 0>(p, st, lo);
+inline int epi_flavour(const ConvParams& p, bool lean) {
+    if (lean) return p.act == ACT_SNAKE ? 2 : lean_acc(p) ? 3 : 1;
+    return (p.act == ACT_NONE || p.act == ACT_LRELU) ? 0 : EPI_FULL;
 }
 
-template <int BM, int BN, int WM, int WN, bool PF, bool FULL, int LEAN>
-void launch_cfg2(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
+// Profiling (ev_profile_enable): an event pair of h->ev_pool around every timed launch and its ProfRec.  prof_begin records the first
+// event; after the launch, prof_end (called only while profiling) records the second and the record.
+int prof_begin(ev_handle* h) {
+    if (!h->prof) return 0;
+    if (h->ev_used + 2 > h->ev_pool.size()) {
+        for (int i = 0; i < 64; ++i) { hipEvent_t ev; HIPCHK(h, hipEventCreate(&ev)); h->ev_pool.push_back(ev); }
+    }
+    h->ev_used += 2;
+    HIPCHK(h, hipEventRecord(h->ev_pool[h->ev_used - 2], h->stream));
+    return 0;
+}
+int prof_end(ev_handle* h, const ev_handle::ProfRec& r) {
+    HIPCHK(h, hipEventRecord(h->ev_pool[h->ev_used - 1], h->stream));
+    h->prof_flops += r.flops;
+    h->prof_launches += 1;
+    h->prof_recs.push_back(r);
+    return 0;
+}
+inline double valid_rows(const Geom& g) { return (double)(g.nrows / g.S) * g.T; }
+
+// Buffer (SRSRC) addressing uses 32-bit byte offsets: every tensor of a launch must stay below 4 GiB (ld: its row stride in floats)
+inline bool over_4gib(const Geom& g, int ld) { return (double)g.nrows * ld * 4.0 >= 4294967296.0; }
+
+template <int BM, int BN, int WM, int WN, bool PF = false>
+void launch_cfg(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
     // LDS holds the X tile during the K loop and, afterwards, one transposed 32-frame slab per wave for the epilogue
     const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * 36;
     constexpr size_t es = (size_t)4 * 32 * (BM / WM + 4);
     size_t smem = (xs > es ? xs : es) * sizeof(float);
     if (lo.wgs_per_cu > 0) { size_t cap = (size_t)(160 * 1024 / lo.wgs_per_cu) & ~(size_t)255; if (cap > smem) smem = cap; }
-    ensure_dyn_smem<conv_gemm_kernel<BM, BN, WM, WN, PF, FULL, LEAN>>(smem, lo.device);
-    hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, PF, FULL, LEAN>), dim3(p.mtiles * p.ntiles), dim3(256), smem, st, p);
+    dispatch<1, 2, 3, 0, EPI_FULL>(epi_flavour(p, lo.lean && lean_ok(p)), [&](auto E) {
+        launch<conv_gemm_kernel<BM, BN, WM, WN, PF, E == EPI_FULL, (E > 0 ? E : 0)>>(lo.device, dim3(p.mtiles * p.ntiles), dim3(256), smem, st, p);
+    });
 }
 
 // conv_split_kernel (fp32 contraction as six bf16 products per element pair): the lean epilogues only
@@ -558,10 +588,9 @@ void launch_split(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
     const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * EVX_RSB;
     constexpr size_t es = (size_t)4 * 32 * (BM / WM + 4) * sizeof(float);
     const size_t smem = xs > es ? xs : es;
-    const dim3 grid(p.mtiles * p.ntiles);
-    if (p.act == ACT_SNAKE) { ensure_dyn_smem<conv_split_kernel<BM, BN, WM, WN, 2, TERMS>>(smem, lo.device); hipLaunchKernelGGL((conv_split_kernel<BM, BN, WM, WN, 2, TERMS>), grid, dim3(256), smem, st, p); }
-    else if (lean_acc(p)) { ensure_dyn_smem<conv_split_kernel<BM, BN, WM, WN, 3, TERMS>>(smem, lo.device); hipLaunchKernelGGL((conv_split_kernel<BM, BN, WM, WN, 3, TERMS>), grid, dim3(256), smem, st, p); }
-    else { ensure_dyn_smem<conv_split_kernel<BM, BN, WM, WN, 1, TERMS>>(smem, lo.device); hipLaunchKernelGGL((conv_split_kernel<BM, BN, WM, WN, 1, TERMS>), grid, dim3(256), smem, st, p); }
+    dispatch<1, 2, 3>(epi_flavour(p, true), [&](auto E) {
+        launch<conv_split_kernel<BM, BN, WM, WN, E, TERMS>>(lo.device, dim3(p.mtiles * p.ntiles), dim3(256), smem, st, p);
+    });
 }
 // conv_h16_kernel (fp16 two-piece, block-scaled): the lean epilogues only
 template <int BM, int BN, int WM, int WN>
@@ -571,14 +600,9 @@ void launch_h16(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
     const size_t smem = xs > es ? xs : es;
     const dim3 grid(p.mtiles * p.ntiles);
     // the 16 x 16 x 32 K loop (conv_h16_kernel<..., Q = 1>) wherever the layer carries that fragment order
-    if (p.Wq && p.act != ACT_SNAKE) {
-        if (lean_acc(p)) { ensure_dyn_smem<conv_h16_kernel<BM, BN, WM, WN, 3, 1>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_kernel<BM, BN, WM, WN, 3, 1>), grid, dim3(256), smem, st, p); }
-        else { ensure_dyn_smem<conv_h16_kernel<BM, BN, WM, WN, 1, 1>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_kernel<BM, BN, WM, WN, 1, 1>), grid, dim3(256), smem, st, p); }
-        return;
-    }
-    if (p.act == ACT_SNAKE) { ensure_dyn_smem<conv_h16_kernel<BM, BN, WM, WN, 2>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_kernel<BM, BN, WM, WN, 2>), grid, dim3(256), smem, st, p); }
-    else if (lean_acc(p)) { ensure_dyn_smem<conv_h16_kernel<BM, BN, WM, WN, 3>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_kernel<BM, BN, WM, WN, 3>), grid, dim3(256), smem, st, p); }
-    else { ensure_dyn_smem<conv_h16_kernel<BM, BN, WM, WN, 1>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_kernel<BM, BN, WM, WN, 1>), grid, dim3(256), smem, st, p); }
+    if (p.Wq && p.act != ACT_SNAKE)
+        dispatch<1, 3>(epi_flavour(p, true), [&](auto E) { launch<conv_h16_kernel<BM, BN, WM, WN, E, 1>>(lo.device, grid, dim3(256), smem, st, p); });
+    else dispatch<1, 2, 3>(epi_flavour(p, true), [&](auto E) { launch<conv_h16_kernel<BM, BN, WM, WN, E>>(lo.device, grid, dim3(256), smem, st, p); });
 }
 inline bool split_ok(const ConvLayer& L, const ConvParams& p0) {
     ConvParams p = p0;
@@ -588,8 +612,8 @@ inline bool split_ok(const ConvLayer& L, const ConvParams& p0) {
 
 // small-launch builds (conv_gemm_sk_kernel): 64 x 64 tiles, 16 waves, K split four ways inside the workgroup (TW = 4, KS = 4),
 // or 32 x 32 tiles, 8 waves, K split eight ways (TW = 1, KS = 8) for launches of only a few dozen 64 x 64 tiles
-template <bool FULL, int LEAN, int TW>
-void launch_sk2(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
+template <int TW>
+void launch_sk(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
     constexpr int KS = TW == 4 ? 4 : 8, BN = TW == 4 ? 64 : 32;
     // k-chunks per staging round: TW = 4 up to 8; TW = 1 the whole K when the X tile fits LDS (<= 150 KB) and the per-thread
     // staging registers (EV_SK_MAXF4), else the largest multiple of KS that does
@@ -601,17 +625,9 @@ void launch_sk2(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
     size_t smem = std::max(xs, std::max(red, es)) * sizeof(float);
     ConvParams q = p;
     q.sk_kb = kbs;
-    ensure_dyn_smem<conv_gemm_sk_kernel<KS, FULL, LEAN, TW>>(smem, lo.device);
-    hipLaunchKernelGGL((conv_gemm_sk_kernel<KS, FULL, LEAN, TW>), dim3(p.mtiles * p.ntiles), dim3(64 * TW * KS), smem, st, q);
-}
-template <int TW>
-void launch_sk(const ConvParams& p, hipStream_t st, const LaunchOpts& lo) {
-    if (lo.lean && lean_ok(p)) {
-        if (p.act == ACT_SNAKE) launch_sk2<false, 2, TW>(p, st, lo);
-        else if (lean_acc(p)) launch_sk2<false, 3, TW>(p, st, lo);
-        else launch_sk2<false, 1, TW>(p, st, lo);
-    } else if (p.act == ACT_NONE || p.act == ACT_LRELU) launch_sk2<false, 0, TW>(p, st, lo);
-    else launch_sk2<true, 0, TW>(p, st, lo);
+    dispatch<1, 2, 3, 0, EPI_FULL>(epi_flavour(p, lo.lean && lean_ok(p)), [&](auto E) {
+        launch<conv_gemm_sk_kernel<KS, E == EPI_FULL, (E > 0 ? E : 0), TW>>(lo.device, dim3(p.mtiles * p.ntiles), dim3(64 * TW * KS), smem, st, q);
+    });
 }
 
 constexpr int EV_CAPTURE_SLOTS = 8;       // captured ev_cfm_decode calls a handle can hold (pinned staging that is never recycled)
@@ -627,67 +643,39 @@ int ensure_sk(ev_handle* h, bool hot_path = true) {
     HIPCHK(h, hipMalloc((void**)&h->sk_part, (size_t)EV_SK_MAXWG * 2 * EV_SK_PART_FLOATS * sizeof(float)));   // (freed by ev_destroy)
     return 0;
 }
+// A balanced persistent grid (SkCtl): G workgroups share U units over the handle's hand-off area; claims: with work stealing
+int sk_setup(ev_handle* h, SkCtl& sk, long U, int G, bool claims) {
+    if (ensure_sk(h)) return 1;
+    sk.ctrl = h->sk_ctrl; sk.flags = h->sk_ctrl + 16; sk.part = h->sk_part; sk.part_floats = EV_SK_PART_FLOATS;
+    sk.q = (int)(U / G); sk.r = (int)(U % G); sk.spin_limit = h->sk_spin;
+    if (claims) { sk.claims = h->sk_ctrl + 16 + EV_SK_MAXWG; sk.seq = ++h->sk_seq; }
+    return 0;
+}
 
-// The balanced persistent build of a conv launch (conv_gemm_bal_kernel): G = wpc x CUs workgroups share the (tile, k-chunk) units.
-template <int BM, int BN, int WM, int WN>
+// The balanced persistent builds of a conv launch: G = wpc x CUs workgroups share the (tile, k-chunk) units.  PIPE_FP32:
+// conv_gemm_bal_kernel (k-chunks of EV_BK); PIPE_BF16: conv_split_bal_kernel and PIPE_H16: conv_h16_bal_kernel (64-channel chunks; the
+// fp16 build steals work).  Their builds have the plain and the accumulate lean epilogues (LEAN 1 / 3) only.
+enum { PIPE_FP32, PIPE_BF16, PIPE_H16 };
+template <int PIPE, int BM, int BN, int WM, int WN>
 int launch_bal(ev_handle* h, ConvParams p, const LaunchOpts& lo, int wpc) {
-    if (ensure_sk(h)) return 1;
-    const int nchunks = p.Kpad / EV_BK;
-    const long U = (long)p.mtiles * p.ntiles * nchunks;
+    static_assert((size_t)BM * BN <= EV_SK_PART_FLOATS, "hand-off slot");
     const int G = wpc * h->ncu;
-    p.sk.ctrl = h->sk_ctrl; p.sk.flags = h->sk_ctrl + 16; p.sk.part = h->sk_part; p.sk.part_floats = EV_SK_PART_FLOATS;
-    p.sk.q = (int)(U / G); p.sk.r = (int)(U % G); p.sk.spin_limit = h->sk_spin;
-    const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * 36;
-    constexpr size_t es = (size_t)4 * 32 * (BM / WM + 4);
-    size_t smem = (xs > es ? xs : es) * sizeof(float);
-    p.sk.lds_word = (int)smem;
-    smem += 16;
-    if (lean_acc(p)) { ensure_dyn_smem<conv_gemm_bal_kernel<BM, BN, WM, WN, 3>>(smem, lo.device); hipLaunchKernelGGL((conv_gemm_bal_kernel<BM, BN, WM, WN, 3>), dim3(G), dim3(256), smem, h->stream, p); }
-    else { ensure_dyn_smem<conv_gemm_bal_kernel<BM, BN, WM, WN, 1>>(smem, lo.device); hipLaunchKernelGGL((conv_gemm_bal_kernel<BM, BN, WM, WN, 1>), dim3(G), dim3(256), smem, h->stream, p); }
-    return 0;
-}
-// ... and of the bf16-split build (conv_split_bal_kernel): a unit = (tile, 64-channel chunk)
-template <int BM, int BN, int WM, int WN>
-int launch_split_bal(ev_handle* h, ConvParams p, const LaunchOpts& lo, int wpc) {
-    if (ensure_sk(h)) return 1;
-    const int nchunks = p.Kpad / EVX_KC;
-    const long U = (long)p.mtiles * p.ntiles * nchunks;
-    const int G = wpc * h->ncu;
-    p.sk.ctrl = h->sk_ctrl; p.sk.flags = h->sk_ctrl + 16; p.sk.part = h->sk_part; p.sk.part_floats = EV_SK_PART_FLOATS;
-    p.sk.q = (int)(U / G); p.sk.r = (int)(U % G); p.sk.spin_limit = h->sk_spin;
-    const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * EVX_RSB;
+    if (sk_setup(h, p.sk, (long)p.mtiles * p.ntiles * (p.Kpad / (PIPE == PIPE_FP32 ? EV_BK : EVX_KC)), G, PIPE == PIPE_H16)) return 1;
+    const size_t rsb = PIPE == PIPE_FP32 ? 36 * sizeof(float) : PIPE == PIPE_BF16 ? EVX_RSB : EVH_RSB;   // LDS bytes per X-tile row
+    const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * rsb;
     constexpr size_t es = (size_t)4 * 32 * (BM / WM + 4) * sizeof(float);
     size_t smem = xs > es ? xs : es;
     p.sk.lds_word = (int)smem;
-    smem += 16;
-    static_assert((size_t)BM * BN <= EV_SK_PART_FLOATS, "hand-off slot");
-    if (lean_acc(p)) { ensure_dyn_smem<conv_split_bal_kernel<BM, BN, WM, WN, 3>>(smem, lo.device); hipLaunchKernelGGL((conv_split_bal_kernel<BM, BN, WM, WN, 3>), dim3(G), dim3(256), smem, h->stream, p); }
-    else { ensure_dyn_smem<conv_split_bal_kernel<BM, BN, WM, WN, 1>>(smem, lo.device); hipLaunchKernelGGL((conv_split_bal_kernel<BM, BN, WM, WN, 1>), dim3(G), dim3(256), smem, h->stream, p); }
-    return 0;
-}
-template <int BM, int BN, int WM, int WN>
-int launch_h16_bal(ev_handle* h, ConvParams p, const LaunchOpts& lo, int wpc) {
-    if (ensure_sk(h)) return 1;
-    const int nchunks = p.Kpad / EVX_KC;
-    const long U = (long)p.mtiles * p.ntiles * nchunks;
-    const int G = wpc * h->ncu;
-    p.sk.ctrl = h->sk_ctrl; p.sk.flags = h->sk_ctrl + 16; p.sk.part = h->sk_part; p.sk.part_floats = EV_SK_PART_FLOATS;
-    p.sk.q = (int)(U / G); p.sk.r = (int)(U % G); p.sk.spin_limit = h->sk_spin;
-    p.sk.claims = h->sk_ctrl + 16 + EV_SK_MAXWG; p.sk.seq = ++h->sk_seq;
-    const size_t xs = (size_t)(BN + ((lo.halo + 7) & ~7)) * EVH_RSB;
-    constexpr size_t es = (size_t)4 * 32 * (BM / WM + 4) * sizeof(float);
-    size_t smem = xs > es ? xs : es;
-    p.sk.lds_word = (int)smem;
-    smem += 16 + 3 * 4 * sizeof(float) + 16;            // the wait word + three sets of the waves' maxima
-    static_assert((size_t)BM * BN <= EV_SK_PART_FLOATS, "hand-off slot");
-    const bool narrow = BN + p.halo_lo + p.halo_hi <= 16 * 9;         // a 3-tap layer: nine staging passes instead of twelve
-    if (lean_acc(p)) {
-        if (narrow) { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 3, 9>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 3, 9>), dim3(G), dim3(256), smem, h->stream, p); }
-        else { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 3>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 3>), dim3(G), dim3(256), smem, h->stream, p); }
-    } else {
-        if (narrow) { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 1, 9>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 1, 9>), dim3(G), dim3(256), smem, h->stream, p); }
-        else { ensure_dyn_smem<conv_h16_bal_kernel<BM, BN, WM, WN, 1>>(smem, lo.device); hipLaunchKernelGGL((conv_h16_bal_kernel<BM, BN, WM, WN, 1>), dim3(G), dim3(256), smem, h->stream, p); }
-    }
+    smem += PIPE == PIPE_H16 ? 16 + 3 * 4 * sizeof(float) + 16 : 16;     // the wait word (fp16: + three sets of the waves' maxima)
+    const int lean = lean_acc(p) ? 3 : 1;
+    const dim3 grid(G), block(256);
+    if constexpr (PIPE == PIPE_FP32)
+        dispatch<1, 3>(lean, [&](auto E) { launch<conv_gemm_bal_kernel<BM, BN, WM, WN, E>>(lo.device, grid, block, smem, h->stream, p); });
+    else if constexpr (PIPE == PIPE_BF16)
+        dispatch<1, 3>(lean, [&](auto E) { launch<conv_split_bal_kernel<BM, BN, WM, WN, E>>(lo.device, grid, block, smem, h->stream, p); });
+    else if (BN + p.halo_lo + p.halo_hi <= 16 * 9)         // a 3-tap layer: nine staging passes instead of twelve
+        dispatch<1, 3>(lean, [&](auto E) { launch<conv_h16_bal_kernel<BM, BN, WM, WN, E, 9>>(lo.device, grid, block, smem, h->stream, p); });
+    else dispatch<1, 3>(lean, [&](auto E) { launch<conv_h16_bal_kernel<BM, BN, WM, WN, E>>(lo.device, grid, block, smem, h->stream, p); });
     return 0;
 }
 inline bool split_bal_ok(const ev_handle* h, const ConvLayer& L, const ConvParams& p, long nwg, int wpc) {
@@ -706,11 +694,96 @@ inline bool bal_ok(const ev_handle* h, const ConvLayer& L, const ConvParams& p, 
            nwg >= h->ncu && nwg < 4L * wpc * h->ncu && wpc * h->ncu <= EV_SK_MAXWG && (long)nwg * (p.Kpad / EV_BK) >= (long)wpc * h->ncu;
 }
 
-// The tile configurations launch_conv selects (cfg 47 / 56 / 66 are what 41 / 6 / 60 become on their launch), the only ones a forced cfg may name
-inline bool forceable_cfg(int cfg) {
-    for (int c : {0, 1, 2, 5, 6, 8, 9, 19, 40, 41, 43, 46, 49, 60}) if (cfg == c) return true;
-    return false;
+// Build codes of a conv launch (channels x frames per workgroup).  ev_dbg_last_cfg, EV_FORCE_CFG, ev_dbg_conv_bench's cfg and the
+// EV_PROFILE_DUMP table show the numbers.
+enum : int {
+    CFG_128x128 = 0, CFG_64x128 = 1, CFG_32x256 = 2, CFG_64x192 = 5, CFG_64x64 = 6,
+    CFG_64x64_PF = 8,                   // 64 x 64 with register-prefetched X staging
+    CFG_SK64 = 9, CFG_SK32 = 19,        // split-K small-launch builds: 64 x 64 tiles, 16 waves / 32 x 32 tiles, 8 waves
+    CFG_SPLIT = 40, CFG_SPLIT64 = 41, CFG_SPLIT3 = 43, CFG_SPLIT9 = 49,   // bf16 pipe: 128 x 128 (six / three / nine products), 64 x 128
+    CFG_H16 = 46,                       // fp16 pipe, 128 x 128: two block-scaled pieces, three products
+    CFG_SPLIT_BAL = 60,                 // bf16 pipe, 128 x 128, balanced persistent grid
+    CFG_H16_64 = 47, CFG_BAL64 = 56, CFG_H16_BAL = 66,   // what 41 / 6 / 60 become on their launch
+};
+// The tile of every code launch_conv selects (the only codes a forced cfg may name): M x N, start-stagger slots (conv_gemm_kernel's
+// workgroups co-resident per CU; 0: no stagger) and whether the build runs on the split (bf16 / fp16) pipe.  A 128-channel tile counts
+// Mpad / 128 M tiles and takes the layer's tap list [0], a 64 / 32-channel tile ceil(Cout / BM) and list [1] / [2].
+struct ConvTile { int cfg, bm, bn, slots; bool split; };
+constexpr ConvTile EV_TILES[] = {
+    {CFG_128x128, 128, 128, 3, false}, {CFG_64x128, 64, 128, 4, false}, {CFG_32x256, 32, 256, 3, false}, {CFG_64x192, 64, 192, 4, false},
+    {CFG_64x64, 64, 64, 5, false}, {CFG_64x64_PF, 64, 64, 5, false}, {CFG_SK64, 64, 64, 0, false}, {CFG_SK32, 32, 32, 0, false},
+    {CFG_SPLIT, 128, 128, 0, true}, {CFG_SPLIT64, 64, 128, 0, true}, {CFG_SPLIT3, 128, 128, 0, true}, {CFG_H16, 128, 128, 0, true},
+    {CFG_SPLIT9, 128, 128, 0, true}, {CFG_SPLIT_BAL, 128, 128, 0, true},
+};
+inline const ConvTile* conv_tile(int cfg) {
+    for (const ConvTile& t : EV_TILES) if (t.cfg == cfg) return &t;
+    return nullptr;
 }
+inline int tile_list(const ConvTile& t) { return t.bm == 128 ? 0 : t.bm == 64 ? 1 : 2; }
+inline int tile_mtiles(const ConvTile& t, const ConvLayer& L) { return t.bm == 128 ? L.Mpad / 128 : (L.Cout + t.bm - 1) / t.bm; }
+inline long tile_count(const ConvTile& t, const ConvLayer& L, const Geom& g) { return (long)tile_mtiles(t, L) * ((g.nrows + t.bn - 1) / t.bn); }
+
+// The build code of a conv launch (p: its parameters so far).  No side effects.
+int pick_cfg(const ev_handle* h, const ConvLayer& L, const ConvParams& p, const Geom& g) {
+    auto tiles = [&](int cfg) { return tile_count(*conv_tile(cfg), L, g); };
+    // Tile choice.  A launch that fits the chip in about one round of workgroups is decided by its makespan: e.g. 1040 tiles on
+    // 1024 slots run 16 stragglers after everyone else (measured: the matrix pipes idle for half of such a launch), and
+    // 520 tiles on 256 CUs leave 8 CUs with three tiles.  So estimate, per candidate, the busiest CU's share of the
+    // MFMA work and take the minimum; deep grids (HiFi-GAN) keep the 64x128 tile measured best by tools/conv_bench.py.
+    int cfg;
+    if (L.Cout <= 32) cfg = CFG_32x256;
+    else {
+        double best = 1e30;
+        cfg = CFG_64x128;
+        for (int c : {CFG_64x128, CFG_64x192, CFG_64x64}) {
+            const ConvTile& k = *conv_tile(c);
+            const long nwg = tiles(c);
+            const double w = (double)(k.bm / 32) * (k.bn / 32);           // MFMA tiles per workgroup
+            double t;
+            if (nwg <= 256L * k.slots) t = (double)((nwg + 255) / 256) * w;          // one round: the busiest CU
+            else t = (double)nwg * w / 256.0 + (nwg < 256L * k.slots * 3 ? w : 0.0);  // deep grid: balanced + a short tail
+            t *= (c == CFG_64x64 ? 1.08 : 1.0);                               // small tiles re-read more operands
+            if (t < best - 1e-9) { best = t; cfg = c; }
+        }
+    }
+    // stacked layers (a 3-tap conv over a 1x1 conv: half of the M tiles carry one tap) in about one round of workgroups: the
+    // 64 x 64 tile balances the heavy and the light tiles best (measured 3.6 -> 3.1 ms on the T/2-level resnets)
+    if (L.sparse_taps && L.Cout > 32 && tiles(CFG_64x64) <= 256L * 5 * 2) cfg = CFG_64x64;
+    // launches far below one round of workgroups are a latency chain per workgroup: use the build that prefetches the
+    // next chunk's X tile through registers (measured 7-10 % on batch-1 decodes, nothing on full grids)
+    if (cfg == CFG_64x64 && tiles(CFG_64x64) <= 320) cfg = CFG_64x64_PF;
+    // deep grids (>= 6 rounds of 64x128 tiles, dense taps): larger tiles amortise the X staging and the weight-fragment stream over
+    // twice the MFMAs — measured on the HiFi-GAN layers (tools/shape_profile.py with EV_FORCE_CFG): 128x128 is 2-3 % faster
+    // for Cin <= 128 and for 3-tap layers, 64x192 for the 7 / 11-tap layers at Cin = 256
+    if (cfg == CFG_64x128 && L.Cout % 128 == 0 && !L.sparse_taps && tiles(CFG_64x128) >= 256L * 4 * 6)
+        cfg = (L.Cin > 128 && L.ntaps >= 7) ? CFG_64x192 : CFG_128x128;
+    // launches far below one workgroup per CU with a K loop worth splitting: the 16-wave split-K build (batch-1 decodes)
+    if (h->small_sk) {
+        const long wg64 = tiles(CFG_64x64);
+        if ((cfg == CFG_64x64 || cfg == CFG_64x64_PF) && wg64 <= 192 && (L.Kpad / EV_BK) * L.ntaps >= 8) cfg = CFG_SK64;
+        // (a short K loop gains nothing from the split, but the 32 x 32 build for it is the instruction-lean conv_sk32_kernel)
+        if ((cfg == CFG_64x64 || cfg == CFG_64x64_PF) && wg64 <= 96 && L.Kpad == 128 && L.Cin == 128 && !L.sparse_taps) cfg = CFG_SK64;
+        // ... as 32 x 32 tiles on four times as many CUs (up to 96 while the build held one workgroup per CU; since conv_sk32_kernel fits
+        // two — 119 VGPRs — launches of up to 512 such tiles are still one round: 192; config-5 mean -1.9 %, p99 -4.5 %)
+        if (cfg == CFG_SK64 && wg64 <= 192 && L.Cout >= 32) cfg = CFG_SK32;
+    }
+    {   // deep grids of dense-channel layers: the bf16-split build (EV_SPLIT=0: fp32 MFMA everywhere; 3 / 9: products per element pair, A/B)
+        const int split_terms = h->split_terms;
+        const bool fp32_tile = cfg == CFG_128x128 || cfg == CFG_64x128 || cfg == CFG_64x192 || cfg == CFG_64x64;
+        // (polyphase transposed convs whose 64-channel M tiles carry different tap subsets — a 128-channel tile would compute the union — take
+        // the 64 x 128 tile below)
+        const long nwg128 = tiles(CFG_128x128);
+        if (split_terms > 0 && fp32_tile && split_ok(L, p) && L.Cout % 128 == 0 && (!L.sparse_taps || (L.tile128_exact && L.kstack_mt == 0)) && nwg128 >= 2L * 2 * h->ncu && h->ncu > 0)
+            cfg = split_terms == 3 ? CFG_SPLIT3 : split_terms == 9 ? CFG_SPLIT9 : split_terms == 16 ? CFG_H16 : CFG_SPLIT;
+        // polyphase transposed convs (M tiles of 64 channels with different tap subsets) on deep grids: 64 x 128 tiles of the split build
+        else if ((split_terms == 6 || split_terms == 3 || split_terms == 16) && fp32_tile && split_ok(L, p) && L.Cout % 64 == 0 && L.kstack_mt == 0 && h->ncu > 0 &&
+                 (L.sparse_taps || L.Cout % 128 != 0) && tiles(CFG_64x128) >= 2L * 3 * h->ncu) cfg = CFG_SPLIT64;
+        // launches of a few rounds (the U-Net convs of a large-batch decode): the balanced persistent grid of the split build
+        else if ((split_terms == 6 || split_terms == 16) && fp32_tile && L.Cout == L.Mpad && split_bal_ok(h, L, p, nwg128, 2)) cfg = CFG_SPLIT_BAL;
+    }
+    return cfg;
+}
+
 constexpr int EV_GN_MAXTILES = 256;    // 32-row tiles of a launch that may leave GroupNorm statistics (EstBufs::GNP)
 int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float* Y, int ldy, const Geom& g, const Epi& e) {
     ConvParams p;
@@ -740,279 +813,158 @@ int launch_conv(ev_handle* h, const ConvLayer& L, const float* X, int ldx, float
     p.Y2 = e.Y2; p.ldy2 = e.ldy2; p.dbg = e.dbg; p.stamps = e.stamps;
     p.xmax = e.xmax; p.xmax_n = e.xmax_n; p.rmax = e.rmax; p.yold = e.yold; p.ymax_mul = e.ymax_mul; h->amax_emitted = false;   // (p.ymax: set below, once the build is known)
     if ((ldx & 3) || (L.Cin & 3)) return fail(h, "conv input must be float4-aligned (ldx %d Cin %d)", ldx, L.Cin);
-    {   // buffer (SRSRC) addressing uses 32-bit byte offsets: every tensor of a launch must stay below 4 GiB
-        const double lim = 4294967296.0;
-        const double ymax = (double)g.nrows * ldy * 4.0, xmax = (double)g.nrows * ldx * 4.0;
-        if (xmax >= lim || ymax >= lim || (e.R && (double)g.nrows * e.ldr * 4.0 >= lim) || (e.Y2 && (double)g.nrows * e.ldy2 * 4.0 >= lim))
-            return fail(h, "tensor of %.1f GiB exceeds the 4 GiB buffer-addressing limit: split the batch", (xmax > ymax ? xmax : ymax) / 1073741824.0);
-    }
+    if (over_4gib(g, ldx) || over_4gib(g, ldy) || (e.R && over_4gib(g, e.ldr)) || (e.Y2 && over_4gib(g, e.ldy2)))
+        return fail(h, "tensor of %.1f GiB exceeds the 4 GiB buffer-addressing limit: split the batch", (double)g.nrows * std::max(ldx, ldy) * 4.0 / 1073741824.0);
 
-    // Tile choice.  cfg: 0 = 128x128, 1 = 64x128, 2 = 32x256, 5 = 64x192, 6 = 64x64 (channels x frames per workgroup).
-    // A launch that fits the chip in about one round of workgroups is decided by its makespan: e.g. 1040 tiles on
-    // 1024 slots run 16 stragglers after everyone else (measured: the matrix pipes idle for half of such a launch), and
-    // 520 tiles on 256 CUs leave 8 CUs with three tiles.  So estimate, per candidate, the busiest CU's share of the
-    // MFMA work and take the minimum; deep grids (HiFi-GAN) keep the 64x128 tile measured best by tools/conv_bench.py.
-    int cfg;
-    if (L.Cout <= 32) cfg = 2;
-    else {
-        struct Cand { int cfg, bm, bn, slots; };
-        const Cand cands[3] = {{1, 64, 128, 4}, {5, 64, 192, 4}, {6, 64, 64, 5}};
-        double best = 1e30;
-        cfg = 1;
-        for (const Cand& c : cands) {
-            const long nwg = (long)((L.Cout + c.bm - 1) / c.bm) * ((g.nrows + c.bn - 1) / c.bn);
-            const double w = (double)(c.bm / 32) * (c.bn / 32);           // MFMA tiles per workgroup
-            double t;
-            if (nwg <= 256L * c.slots) t = (double)((nwg + 255) / 256) * w;          // one round: the busiest CU
-            else t = (double)nwg * w / 256.0 + (nwg < 256L * c.slots * 3 ? w : 0.0);  // deep grid: balanced + a short tail
-            t *= (c.cfg == 6 ? 1.08 : 1.0);                               // small tiles re-read more operands
-            if (t < best - 1e-9) { best = t; cfg = c.cfg; }
-        }
-    }
-    // stacked layers (a 3-tap conv over a 1x1 conv: half of the M tiles carry one tap) in about one round of workgroups: the
-    // 64 x 64 tile balances the heavy and the light tiles best (measured 3.6 -> 3.1 ms on the T/2-level resnets)
-    if (L.sparse_taps && L.Cout > 32 && (long)((L.Cout + 63) / 64) * ((g.nrows + 63) / 64) <= 256L * 5 * 2) cfg = 6;
-    // launches far below one round of workgroups are a latency chain per workgroup: use the build that prefetches the
-    // next chunk's X tile through registers (measured 7-10 % on batch-1 decodes, nothing on full grids)
-    if (cfg == 6 && (long)((L.Cout + 63) / 64) * ((g.nrows + 63) / 64) <= 320) cfg = 8;
-    // deep grids (>= 6 rounds of 64x128 tiles, dense taps): larger tiles amortise the X staging and the weight-fragment stream over
-    // twice the MFMAs — measured on the HiFi-GAN layers (tools/shape_profile.py with EV_FORCE_CFG): 128x128 is 2-3 % faster
-    // for Cin <= 128 and for 3-tap layers, 64x192 for the 7 / 11-tap layers at Cin = 256
-    if (cfg == 1 && L.Cout % 128 == 0 && !L.sparse_taps && (long)(L.Cout / 64) * ((g.nrows + 127) / 128) >= 256L * 4 * 6)
-        cfg = (L.Cin > 128 && L.ntaps >= 7) ? 5 : 0;
-    // launches far below one workgroup per CU with a K loop worth splitting: the 16-wave split-K build (batch-1 decodes)
-    if (h->small_sk) {
-        const long wg64 = (long)((L.Cout + 63) / 64) * ((g.nrows + 63) / 64);
-        if ((cfg == 6 || cfg == 8) && wg64 <= 192 && (L.Kpad / EV_BK) * L.ntaps >= 8) cfg = 9;
-        // (a short K loop gains nothing from the split, but the 32 x 32 build for it is the instruction-lean conv_sk32_kernel)
-        if ((cfg == 6 || cfg == 8) && wg64 <= 96 && L.Kpad == 128 && L.Cin == 128 && !L.sparse_taps) cfg = 9;
-        // ... as 32 x 32 tiles on four times as many CUs (up to 96 while the build held one workgroup per CU; since conv_sk32_kernel fits
-        // two — 119 VGPRs — launches of up to 512 such tiles are still one round: 192; config-5 mean -1.9 %, p99 -4.5 %)
-        if (cfg == 9 && wg64 <= 192 && L.Cout >= 32) cfg = 19;
-    }
-    {   // deep grids of dense-channel layers: the bf16-split build (EV_SPLIT=0: fp32 MFMA everywhere; 3 / 9: products per element pair, A/B)
-        const int split_terms = h->split_terms;
-        // (polyphase transposed convs whose 64-channel M tiles carry different tap subsets — a 128-channel tile would compute the union — take
-        // the 64 x 128 tile below)
-        const long nwg128 = (long)(L.Mpad / 128) * ((g.nrows + 127) / 128);
-        if (split_terms > 0 && (cfg == 0 || cfg == 1 || cfg == 5 || cfg == 6) && split_ok(L, p) && L.Cout % 128 == 0 && (!L.sparse_taps || (L.tile128_exact && L.kstack_mt == 0)) && nwg128 >= 2L * 2 * h->ncu && h->ncu > 0)
-            cfg = split_terms == 3 ? 43 : split_terms == 9 ? 49 : split_terms == 16 ? 46 : 40;
-        // polyphase transposed convs (M tiles of 64 channels with different tap subsets) on deep grids: 64 x 128 tiles of the split build
-        else if ((split_terms == 6 || split_terms == 3 || split_terms == 16) && (cfg == 0 || cfg == 1 || cfg == 5 || cfg == 6) && split_ok(L, p) && L.Cout % 64 == 0 && L.kstack_mt == 0 && h->ncu > 0 &&
-                 (L.sparse_taps || L.Cout % 128 != 0) &&
-                 (long)((L.Cout + 63) / 64) * ((g.nrows + 127) / 128) >= 2L * 3 * h->ncu) cfg = 41;
-        // launches of a few rounds (the U-Net convs of a large-batch decode): the balanced persistent grid of the split build
-        else if ((split_terms == 6 || split_terms == 16) && (cfg == 1 || cfg == 5 || cfg == 6 || cfg == 0) && L.Cout == L.Mpad && split_bal_ok(h, L, p, nwg128, 2)) cfg = 60;
-    }
+    int cfg = pick_cfg(h, L, p, g);
     LaunchOpts lo;
     lo.device = h->device; lo.lean = h->lean; lo.halo = L.halo_lo + L.halo_hi;
     // debugging / test overrides: EV_FORCE_CFG=<cfg> (every launch of the handle), ev_dbg_conv_bench's cfg = <cfg> + 100 x <workgroups per CU>
     if (h->force_cfg >= 0) cfg = h->force_cfg;
     if (e.force_cfg >= 0) { cfg = e.force_cfg < 1000 ? e.force_cfg % 100 : -1; lo.wgs_per_cu = (e.force_cfg / 100) % 10; }
-    if ((h->force_cfg >= 0 || e.force_cfg >= 0) && !forceable_cfg(cfg))
+    if ((h->force_cfg >= 0 || e.force_cfg >= 0) && !conv_tile(cfg))
         return fail(h, "launch_conv: forced tile configuration %d is not one launch_conv selects", e.force_cfg >= 0 ? e.force_cfg : h->force_cfg);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) {
-        if (h->ev_used + 2 > h->ev_pool.size()) {
-            for (int i = 0; i < 64; ++i) { hipEvent_t ev; HIPCHK(h, hipEventCreate(&ev)); h->ev_pool.push_back(ev); }
-        }
-        e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-    }
-    {   // start stagger (see conv_gemm_kernel): only worth it when the grid is several rounds deep
-        const int slots = cfg == 0 ? 3 : ((cfg == 1 || cfg == 5) ? 4 : ((cfg == 6 || cfg == 8) ? 5 : 3));
-        const long wgs = cfg == 5 ? (long)((L.Cout + 63) / 64) * ((g.nrows + 191) / 192) : (cfg == 6 || cfg == 8) ? (long)((L.Cout + 63) / 64) * ((g.nrows + 63) / 64) : cfg == 0 ? (long)(L.Mpad / 128) * ((g.nrows + 127) / 128) : (cfg == 1 ? (long)((L.Cout + 63) / 64) * ((g.nrows + 127) / 128) : (long)((L.Cout + 31) / 32) * ((g.nrows + 255) / 256));
-        p.stagger_slots = (wgs >= 256L * slots * 3 && cfg < 10) ? slots : 0;
+    if (prof_begin(h)) return 1;
+    {   // start stagger (see conv_gemm_kernel): only worth it when the grid is several rounds deep.  (Code 9's build has no stagger; its
+        // unread field is still set from the 32 x 256 tile count, as it always was.)
+        const ConvTile& s = *conv_tile(cfg == CFG_SK64 ? CFG_32x256 : cfg);
+        p.stagger_slots = tile_count(s, L, g) >= 256L * s.slots * 3 ? s.slots : 0;
         if (e.stagger >= 0) p.stagger_slots = e.stagger;
     }
-    if ((cfg == 40 || cfg == 41 || cfg == 43 || cfg == 46 || cfg == 49 || cfg == 60) && !split_ok(L, p)) cfg = 0;
-    if (cfg == 46 && !L.Wh) cfg = 40;
-    {   // which builds leave bounds of their output: the fp16 builds 46 / 47 (cfg 41 becomes 47 below when the layer has fp16 pieces) and the
-        // fp32 conv_gemm_kernel tiles with the lean non-SnakeBeta epilogues; a residual without slots of its own cannot be bounded
+    if (conv_tile(cfg)->split && !split_ok(L, p)) cfg = CFG_128x128;
+    if (cfg == CFG_H16 && !L.Wh) cfg = CFG_SPLIT;
+    const bool fp16 = h->split_terms == 16 && L.Wh;     // the split builds 41 / 60 on the fp16 pipe (47 / 66)
+    {   // which builds leave bounds of their output: the fp16 builds 46 / 47 and the fp32 conv_gemm_kernel tiles with the lean
+        // non-SnakeBeta epilogues; a residual without slots of its own cannot be bounded
         const bool lean1or3 = lean_ok(p) && p.act != ACT_SNAKE && h->lean;
-        const bool h16 = (cfg == 46) || (cfg == 41 && h->split_terms == 16 && L.Wh);
-        const bool gemm = (cfg == 0 || cfg == 1 || cfg == 5 || cfg == 6) && lean1or3;
+        const bool h16 = cfg == CFG_H16 || (cfg == CFG_SPLIT64 && fp16);
+        const bool gemm = (cfg == CFG_128x128 || cfg == CFG_64x128 || cfg == CFG_64x192 || cfg == CFG_64x64) && lean1or3;
         const bool no_amax = !h->use_amax;                                          // A/B: every fp16 tile pre-scans
         if (!no_amax && e.ymax && lean1or3 && (h16 || gemm) && (!e.R || e.rmax) && (!e.accum || e.yold)) { p.ymax = e.ymax; h->amax_emitted = true; }
         if (no_amax) p.xmax = nullptr;
     }
-    if (cfg == 46) {   // 128 x 128 on the fp16 pipe, two block-scaled pieces, three products
-        p.mtiles = L.Mpad / 128; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[0]; p.nact_tab = L.nact[0]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_h16<128, 128, 2, 2>(p, h->stream, lo);
-    } else
-    if (cfg == 41) {   // 64 x 128 on the bf16 pipe (per-tile tap lists of the 64-channel tiling)
-        p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        if (h->split_terms == 16 && L.Wh) { launch_h16<64, 128, 2, 2>(p, h->stream, lo); cfg = 47; }
-        else if (h->split_terms == 3) launch_split<64, 128, 2, 2, 3>(p, h->stream, lo); else launch_split<64, 128, 2, 2, 6>(p, h->stream, lo);
-    } else
-    if (cfg == 60) {   // 128 x 128 on the bf16 pipe, balanced persistent grid
-        p.mtiles = L.Mpad / 128; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[0]; p.nact_tab = L.nact[0]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        if (h->split_terms == 16 && L.Wh) { if (launch_h16_bal<128, 128, 2, 2>(h, p, lo, 2)) return 1; cfg = 66; }
-        else if (launch_split_bal<128, 128, 2, 2>(h, p, lo, 2)) return 1;
-    } else
-    if (cfg == 40 || cfg == 43 || cfg == 49) {   // 128 x 128 on the bf16 pipe
-        p.mtiles = L.Mpad / 128; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[0]; p.nact_tab = L.nact[0]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        if (cfg == 40) launch_split<128, 128, 2, 2, 6>(p, h->stream, lo);
-        else if (cfg == 43) launch_split<128, 128, 2, 2, 3>(p, h->stream, lo);
-        else launch_split<128, 128, 2, 2, 9>(p, h->stream, lo);
-    } else if (cfg == 0) {
-        p.mtiles = L.Mpad / 128; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[0]; p.nact_tab = L.nact[0]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_cfg<128, 128, 2, 2>(p, h->stream, lo);
-    } else if (cfg == 1) {
-        p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 127) / 128; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_cfg<64, 128, 2, 2>(p, h->stream, lo);
-    } else if (cfg == 5) {
-        p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 191) / 192; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_cfg<64, 192, 2, 2>(p, h->stream, lo);
-    } else if (cfg == 8) {   // 64 x 64 with register-prefetched X staging
-        p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 63) / 64; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_cfg<64, 64, 2, 2, true>(p, h->stream, lo);
-    } else if (cfg == 9) {   // 64 x 64 tiles, 16 waves, split-K inside the workgroup
-        p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 63) / 64; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_sk<4>(p, h->stream, lo);
-    } else if (cfg == 19) {  // 32 x 32 tiles, 8 waves, split-K eight ways
-        p.mtiles = (L.Cout + 31) / 32; p.ntiles = (g.nrows + 31) / 32; p.taplist = L.taplist[2]; p.nact_tab = L.nact[2]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
+    const ConvTile& t = *conv_tile(cfg);
+    p.mtiles = tile_mtiles(t, L); p.ntiles = (g.nrows + t.bn - 1) / t.bn;
+    p.taplist = L.taplist[tile_list(t)]; p.nact_tab = L.nact[tile_list(t)]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
+    switch (cfg) {
+    case CFG_H16: launch_h16<128, 128, 2, 2>(p, h->stream, lo); break;
+    case CFG_SPLIT64:
+        if (fp16) { launch_h16<64, 128, 2, 2>(p, h->stream, lo); cfg = CFG_H16_64; }
+        else if (h->split_terms == 3) launch_split<64, 128, 2, 2, 3>(p, h->stream, lo);
+        else launch_split<64, 128, 2, 2, 6>(p, h->stream, lo);
+        break;
+    case CFG_SPLIT_BAL:
+        if (fp16) { if (launch_bal<PIPE_H16, 128, 128, 2, 2>(h, p, lo, 2)) return 1; cfg = CFG_H16_BAL; }
+        else if (launch_bal<PIPE_BF16, 128, 128, 2, 2>(h, p, lo, 2)) return 1;
+        break;
+    case CFG_SPLIT: launch_split<128, 128, 2, 2, 6>(p, h->stream, lo); break;
+    case CFG_SPLIT3: launch_split<128, 128, 2, 2, 3>(p, h->stream, lo); break;
+    case CFG_SPLIT9: launch_split<128, 128, 2, 2, 9>(p, h->stream, lo); break;
+    case CFG_128x128: launch_cfg<128, 128, 2, 2>(p, h->stream, lo); break;
+    case CFG_64x128: launch_cfg<64, 128, 2, 2>(p, h->stream, lo); break;
+    case CFG_64x192: launch_cfg<64, 192, 2, 2>(p, h->stream, lo); break;
+    case CFG_64x64_PF: launch_cfg<64, 64, 2, 2, true>(p, h->stream, lo); break;
+    case CFG_SK64: launch_sk<4>(p, h->stream, lo); break;
+    case CFG_SK32: {
         const int xr = 32 + p.halo_lo + p.halo_hi;
         // conv_sk32_kernel's preconditions (everything else: the general small-launch build)
         const bool fast = h->sk32_lean && h->lean && lean_ok(p) && (p.ktaps_n > 0 || p.kstack_mt > 0) && p.isplit_log2 >= 31 && !p.pro_lrelu && p.Cin == p.Kpad &&
                           (p.Kpad == 128 || p.Kpad == 256 || p.Kpad == 512 || p.Kpad == 1024) && (ldx % 4) == 0 && xr <= 16 * (512 / (p.Kpad / 4)) && (size_t)g.nrows * ldx * 4 < ((size_t)1 << 31) &&
                           (size_t)xr * (p.Kpad + 4) * 4 <= 150 * 1024;
-        if (fast) {
-            const size_t smem = std::max((size_t)xr * (p.Kpad + 4), (size_t)7 * 16 * 64) * sizeof(float);
-            const dim3 grid(p.mtiles, p.ntiles);
-            // GroupNorm statistics of the output for the layer that follows: one utterance, the tile stored as accumulated, one
-            // 32-channel group per M tile over the (first) 256 output channels
-            if (h->gn_stats && e.gn_part && g.nrows == g.S && p.ntiles <= EV_GN_MAXTILES && p.act == ACT_NONE && !p.R && !lean_acc(p) && !p.mask1 && !p.mask2 &&
-                (p.kstack_mt == 8 || (p.kstack_mt == 0 && L.Cout == 256))) {
-                p.gn_part = e.gn_part;
-                h->gn_stats_tiles = p.ntiles;
-            }
-            if (p.act == ACT_SNAKE) { ensure_dyn_smem<conv_sk32_kernel<2>>(smem, h->device); hipLaunchKernelGGL(conv_sk32_kernel<2>, grid, dim3(512), smem, h->stream, p); }
-            else if (lean_acc(p)) { ensure_dyn_smem<conv_sk32_kernel<3>>(smem, h->device); hipLaunchKernelGGL(conv_sk32_kernel<3>, grid, dim3(512), smem, h->stream, p); }
-            else { ensure_dyn_smem<conv_sk32_kernel<1>>(smem, h->device); hipLaunchKernelGGL(conv_sk32_kernel<1>, grid, dim3(512), smem, h->stream, p); }
-        } else launch_sk<1>(p, h->stream, lo);
-    } else if (cfg == 6) {
-        p.mtiles = (L.Cout + 63) / 64; p.ntiles = (g.nrows + 63) / 64; p.taplist = L.taplist[1]; p.nact_tab = L.nact[1]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
+        if (!fast) { launch_sk<1>(p, h->stream, lo); break; }
+        // GroupNorm statistics of the output for the layer that follows: one utterance, the tile stored as accumulated, one
+        // 32-channel group per M tile over the (first) 256 output channels
+        if (h->gn_stats && e.gn_part && g.nrows == g.S && p.ntiles <= EV_GN_MAXTILES && p.act == ACT_NONE && !p.R && !lean_acc(p) && !p.mask1 && !p.mask2 &&
+            (p.kstack_mt == 8 || (p.kstack_mt == 0 && L.Cout == 256))) {
+            p.gn_part = e.gn_part;
+            h->gn_stats_tiles = p.ntiles;
+        }
+        const size_t smem = std::max((size_t)xr * (p.Kpad + 4), (size_t)7 * 16 * 64) * sizeof(float);
+        dispatch<1, 2, 3>(epi_flavour(p, true), [&](auto E) { launch<conv_sk32_kernel<E>>(h->device, dim3(p.mtiles, p.ntiles), dim3(512), smem, h->stream, p); });
+        break;
+    }
+    case CFG_64x64:
         if (bal_ok(h, L, p, (long)p.mtiles * p.ntiles, 4)) {
             p.ymax = nullptr; h->amax_emitted = false;          // (the balanced build leaves no bounds)
-            if (launch_bal<64, 64, 2, 2>(h, p, lo, 4)) return 1;
-            cfg = 56;
+            if (launch_bal<PIPE_FP32, 64, 64, 2, 2>(h, p, lo, 4)) return 1;
+            cfg = CFG_BAL64;
         }
         else launch_cfg<64, 64, 2, 2>(p, h->stream, lo);
-    } else {   // cfg 2
-        p.mtiles = (L.Cout + 31) / 32; p.ntiles = (g.nrows + 255) / 256; p.taplist = L.taplist[2]; p.nact_tab = L.nact[2]; p.tl_stride = L.sparse_taps ? EV_MAX_TAPS : 0;
-        launch_cfg<32, 256, 1, 4>(p, h->stream, lo);
+        break;
+    default: launch_cfg<32, 256, 1, 4>(p, h->stream, lo);     // CFG_32x256
     }
     HIPCHK(h, hipGetLastError());
     h->last_cfg = cfg;
-    if (h->prof) {
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        const double valid_rows = (double)(g.nrows / g.S) * g.T;
-        h->prof_flops += 2.0 * L.macs_per_row * valid_rows;
-        h->prof_launches += 1;
-        h->prof_recs.push_back({0, L.Cin, L.Cout, L.ntaps, g.nrows, cfg, (int)lean_ok(p), 2.0 * L.macs_per_row * valid_rows});
-    }
-    return 0;
+    return h->prof ? prof_end(h, {0, L.Cin, L.Cout, L.ntaps, g.nrows, cfg, (int)lean_ok(p), 2.0 * L.macs_per_row * valid_rows(g), t.split}) : 0;
 }
 
-// One fused ResBlock1 pair  y = c2(lrelu(c1(lrelu(x)))) + x  (resblock_pair_kernel) for C = 32 / 64.
+// The ConvParams of a fused ResBlock launch (resblock_pair / chain / resblock2 kernels; Lc: the block's last conv): C channels in and out,
+// one workgroup per tile of out_rows stored frames, the leaky-relu prologue and the caller's accumulate steps
+void resblock_params(ev_handle* h, ConvParams& p, const ConvLayer& Lc, const float* X, float* Y, int C, const Geom& g, const Epi& e, int out_rows) {
+    p.X = X; p.ldx = C; p.Cin = C; p.isplit_log2 = 31;
+    p.Mpad = Lc.Mpad; p.Kpad = Lc.Kpad;
+    p.Y = Y; p.ldy = C; p.Cout = C; p.osplit_log2 = 31; p.mmul = 1;
+    p.nrows = g.nrows; p.S = g.S; p.P = g.P; p.T = g.T;
+    p.pro_lrelu = 1; p.pro_slope = 0.1f;
+    p.scale = 1.f; p.ldr = C; p.accum = e.accum; p.div3 = e.div3; p.act2_lrelu = e.act2_lrelu; p.act2_slope = e.act2_slope;
+    p.yold = e.yold; p.ymax_mul = 1; h->amax_emitted = false;
+    p.mtiles = 1; p.ntiles = (g.nrows + out_rows - 1) / out_rows;
+}
+// ... whose fp16 build leaves bounds of its output (the residual's bound: the kernel's own tile maximum)
+inline void resblock_bounds(ev_handle* h, ConvParams& p, const Epi& e) {
+    if (e.ymax && (!e.accum || e.yold) && h->use_amax) { p.ymax = e.ymax; h->amax_emitted = true; }
+}
+
+// One fused ResBlock1 pair  y = c2(lrelu(c1(lrelu(x)))) + x  (resblock_pair_kernel) for C = 32 / 64 / 128: one tile of NT = 8192 / C frames
+// (4 waves as C / 32 x 128 / C) per workgroup.
 int launch_pair(ev_handle* h, const ConvLayer& L1, const ConvLayer& L2, const float* X, float* Y, int C, const Geom& g, const Epi& e) {
+    if (over_4gib(g, C)) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
+    if (L1.sparse_taps || L2.sparse_taps || L1.Kpad != C || L2.Kpad != C || L1.Kpad != L2.Kpad || L1.Mpad != L2.Mpad || L1.halo_lo != L1.halo_hi ||
+        L2.halo_lo != L2.halo_hi || 2 * L2.halo_lo > 16 || !L1.bias || !L2.bias)
+        return fail(h, "launch_pair: unsupported layer pair");
+    if (C != 32 && C != 64 && C != 128) return fail(h, "launch_pair: C must be 32, 64 or 128");
     PairParams pp;
     memset(&pp, 0, sizeof pp);
     ConvParams& p = pp.c2;
-    p.X = X; p.ldx = C; p.Cin = C; p.isplit_log2 = 31;
-    p.W = L2.W; p.Mpad = L2.Mpad; p.Kpad = L2.Kpad; p.bias = L2.bias;
-    p.Y = Y; p.ldy = C; p.Cout = C; p.osplit_log2 = 31; p.mmul = 1;
-    p.nrows = g.nrows; p.S = g.S; p.P = g.P; p.T = g.T;
-    p.ntaps = L2.ntaps; p.taplist = L2.taplist[0]; p.tl_stride = 0; p.nact_tab = nullptr;
-    p.pro_lrelu = 1; p.pro_slope = 0.1f;
-    p.scale = 1.f; p.R = X; p.ldr = C; p.accum = e.accum; p.div3 = e.div3; p.act2_lrelu = e.act2_lrelu; p.act2_slope = e.act2_slope;
+    const int NT = 8192 / C;
+    pp.h1 = L1.halo_lo; pp.h2 = L2.halo_lo; pp.mid_slope = 0.1f; pp.out_rows = NT - 2 * pp.h2;
+    resblock_params(h, p, L2, X, Y, C, g, e, pp.out_rows);
+    p.W = L2.W; p.bias = L2.bias; p.ntaps = L2.ntaps; p.taplist = L2.taplist[0];
+    p.R = X;   // (R = X: the fp16 pair kernels bound the residual by their own tile maximum)
     pp.W1 = L1.W; pp.W1x = L1.Wx; p.Wx = L2.Wx; pp.W1h = L1.Wh; pp.w1h_scale = L1.wh_scale; p.Wh = L2.Wh; p.wh_scale = L2.wh_scale; pp.b1 = L1.bias; pp.taplist1 = L1.taplist[0]; pp.ntaps1 = L1.ntaps;
-    pp.h1 = L1.halo_lo; pp.h2 = L2.halo_lo; pp.mid_slope = 0.1f;
-    p.rmax = nullptr; p.yold = e.yold; p.ymax_mul = 1; h->amax_emitted = false;   // (R = X: the fp16 pair kernels bound the residual by their own tile maximum; p.ymax below)
-    if ((double)g.nrows * C * 4.0 >= 4294967296.0) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
-    if (L1.sparse_taps || L2.sparse_taps || L1.Kpad != C || L2.Kpad != C || L1.Kpad != L2.Kpad || L1.Mpad != L2.Mpad || L1.halo_lo != L1.halo_hi ||
-        L2.halo_lo != L2.halo_hi || 2 * pp.h2 > 16 || !L1.bias || !L2.bias)
-        return fail(h, "launch_pair: unsupported layer pair");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) {
-        if (h->ev_used + 2 > h->ev_pool.size()) {
-            for (int i = 0; i < 64; ++i) { hipEvent_t ev; HIPCHK(h, hipEventCreate(&ev)); h->ev_pool.push_back(ev); }
-        }
-        e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-    }
-    const int lean = !h->lean ? 0 : ((e.accum || e.div3 || e.act2_lrelu) ? 3 : 1);
+    if (prof_begin(h)) return 1;
+    const int lean = epi_flavour(p, h->lean);
     const int split_terms = h->split_terms;
     const bool split = split_terms > 0 && lean != 0 && L1.Wx && L2.Wx && !(e.force_cfg == 0);
     const bool h16 = split && split_terms == 16 && L1.Wh && L2.Wh;
-    if (h16) {   // the fp16 build: two block-scaled fp16 planes per LDS row
-        if (e.ymax && (!e.accum || e.yold) && h->use_amax) { p.ymax = e.ymax; h->amax_emitted = true; }   // (the residual's bound: the pair's own tile maximum)
-        const int NT = C == 32 ? 256 : C == 64 ? 128 : 64, RSB = 4 * C + 16;
-        if (C != 32 && C != 64 && C != 128) return fail(h, "launch_pair: C must be 32, 64 or 128");
-        pp.out_rows = NT - 2 * pp.h2; p.mtiles = 1; p.ntiles = (g.nrows + pp.out_rows - 1) / pp.out_rows;
-        const size_t smem = std::max((size_t)(NT + EV_HALO) * RSB + 64, (size_t)4 * 32 * 36 * sizeof(float));   // (+ 16 floats: the waves' maxima)
-        const dim3 grid(p.ntiles);
-        // (both K loops on v_mfma_f32_16x16x32_f16 were measured null on the pairs, unlike conv_h16_kernel's 3-9 %, profiles/r04_mfma_shape_ab.txt:
-        // their K loops are too short — C <= 128 deep — for the MFMA phase to be what the power limit throttles)
-#define EV_PAIR_H16(WM, WN) do { \
-            if (lean == 1) { ensure_dyn_smem<resblock_pair_h16_kernel<WM, WN, 1>>(smem, h->device); hipLaunchKernelGGL((resblock_pair_h16_kernel<WM, WN, 1>), grid, dim3(256), smem, h->stream, pp); } \
-            else { ensure_dyn_smem<resblock_pair_h16_kernel<WM, WN, 3>>(smem, h->device); hipLaunchKernelGGL((resblock_pair_h16_kernel<WM, WN, 3>), grid, dim3(256), smem, h->stream, pp); } } while (0)
-        if (C == 32) EV_PAIR_H16(1, 4); else if (C == 64) EV_PAIR_H16(2, 2); else EV_PAIR_H16(4, 1);
-#undef EV_PAIR_H16
-    } else
-    if (split) {   // the bf16-split build: LDS rows hold all C channels as three bf16 planes
-        const int NT = C == 32 ? 256 : C == 64 ? 128 : 64, RSB = 6 * C + 16;
-        if (C != 32 && C != 64 && C != 128) return fail(h, "launch_pair: C must be 32, 64 or 128");
-        pp.out_rows = NT - 2 * pp.h2; p.mtiles = 1; p.ntiles = (g.nrows + pp.out_rows - 1) / pp.out_rows;
-        const size_t xs = (size_t)(NT + ((2 * pp.h1 + 7) & ~7)) * RSB, ys = (size_t)(NT + 16) * RSB, es = (size_t)4 * 32 * 36 * sizeof(float);
-        const size_t smem = std::max(xs, std::max(ys, es));
-        const dim3 grid(p.ntiles);
-#define EV_PAIR_SPLIT_T(WM, WN, TT) do { \
-            if (lean == 1) { ensure_dyn_smem<resblock_pair_split_kernel<WM, WN, 1, TT>>(smem, h->device); hipLaunchKernelGGL((resblock_pair_split_kernel<WM, WN, 1, TT>), grid, dim3(256), smem, h->stream, pp); } \
-            else { ensure_dyn_smem<resblock_pair_split_kernel<WM, WN, 3, TT>>(smem, h->device); hipLaunchKernelGGL((resblock_pair_split_kernel<WM, WN, 3, TT>), grid, dim3(256), smem, h->stream, pp); } } while (0)
-#define EV_PAIR_SPLIT(WM, WN) do { if (split_terms == 3) EV_PAIR_SPLIT_T(WM, WN, 3); else EV_PAIR_SPLIT_T(WM, WN, 6); } while (0)   // (9: the six-product build)
-        if (C == 32) EV_PAIR_SPLIT(1, 4); else if (C == 64) EV_PAIR_SPLIT(2, 2); else EV_PAIR_SPLIT(4, 1);
-#undef EV_PAIR_SPLIT
-#undef EV_PAIR_SPLIT_T
-    } else if (C == 32) {
-        constexpr int NT = 256;
-        pp.out_rows = NT - 2 * pp.h2; p.mtiles = 1; p.ntiles = (g.nrows + pp.out_rows - 1) / pp.out_rows;
-        // exact X-tile rows (NT + 2*h1) instead of NT + EV_HALO: 39 KB instead of 46 KB for k = 3 / 7 -> 4 workgroups per CU
-        const size_t xs = (size_t)(NT + ((2 * pp.h1 + 7) & ~7)) * EV_LDK, ys = (size_t)(NT + 16) * EV_LDK, es = (size_t)4 * 32 * 36;
-        const size_t smem = std::max(xs, std::max(ys, es)) * sizeof(float);
-        if (lean == 1) hipLaunchKernelGGL((resblock_pair_kernel<1, 4, 1>), dim3(p.ntiles), dim3(256), smem, h->stream, pp);
-        else if (lean == 3) hipLaunchKernelGGL((resblock_pair_kernel<1, 4, 3>), dim3(p.ntiles), dim3(256), smem, h->stream, pp);
-        else hipLaunchKernelGGL((resblock_pair_kernel<1, 4, 0>), dim3(p.ntiles), dim3(256), smem, h->stream, pp);
-    } else if (C == 64) {
-        constexpr int NT = 128;
-        pp.out_rows = NT - 2 * pp.h2; p.mtiles = 1; p.ntiles = (g.nrows + pp.out_rows - 1) / pp.out_rows;
-        const size_t xs = (size_t)(NT + ((2 * pp.h1 + 7) & ~7)) * EV_LDK, ys = (size_t)2 * (NT + 16) * EV_LDK;
-        const size_t smem = (xs > ys ? xs : ys) * sizeof(float);
-        if (lean == 1) hipLaunchKernelGGL((resblock_pair_kernel<2, 2, 1>), dim3(p.ntiles), dim3(256), smem, h->stream, pp);
-        else if (lean == 3) hipLaunchKernelGGL((resblock_pair_kernel<2, 2, 3>), dim3(p.ntiles), dim3(256), smem, h->stream, pp);
-        else hipLaunchKernelGGL((resblock_pair_kernel<2, 2, 0>), dim3(p.ntiles), dim3(256), smem, h->stream, pp);
-    } else if (C == 128) {
-        constexpr int NT = 64;    // 4 waves = 4 channel tiles; 64 compute rows keep the 128-channel intermediate in 46 KB of LDS
-        pp.out_rows = NT - 2 * pp.h2; p.mtiles = 1; p.ntiles = (g.nrows + pp.out_rows - 1) / pp.out_rows;
-        const size_t xs = (size_t)(NT + ((2 * pp.h1 + 7) & ~7)) * EV_LDK, ys = (size_t)4 * (NT + 16) * EV_LDK;
-        const size_t smem = (xs > ys ? xs : ys) * sizeof(float);
-        if (lean == 1) hipLaunchKernelGGL((resblock_pair_kernel<4, 1, 1>), dim3(p.ntiles), dim3(256), smem, h->stream, pp);
-        else if (lean == 3) hipLaunchKernelGGL((resblock_pair_kernel<4, 1, 3>), dim3(p.ntiles), dim3(256), smem, h->stream, pp);
-        else hipLaunchKernelGGL((resblock_pair_kernel<4, 1, 0>), dim3(p.ntiles), dim3(256), smem, h->stream, pp);
-    } else {
-        return fail(h, "launch_pair: C must be 32, 64 or 128");
-    }
+    const dim3 grid(p.ntiles), block(256);
+    dispatch<32, 64, 128>(C, [&](auto CC) {
+        constexpr int WM = CC / 32, WN = 4 / WM;
+        if (h16) {   // the fp16 build: two block-scaled fp16 planes per LDS row
+            resblock_bounds(h, p, e);
+            const size_t smem = std::max((size_t)(NT + EV_HALO) * (4 * C + 16) + 64, (size_t)4 * 32 * 36 * sizeof(float));   // (+ 16 floats: the waves' maxima)
+            // (both K loops on v_mfma_f32_16x16x32_f16 were measured null on the pairs, unlike conv_h16_kernel's 3-9 %, profiles/r04_mfma_shape_ab.txt:
+            // their K loops are too short — C <= 128 deep — for the MFMA phase to be what the power limit throttles)
+            dispatch<1, 3>(lean, [&](auto E) { launch<resblock_pair_h16_kernel<WM, WN, E>>(h->device, grid, block, smem, h->stream, pp); });
+        } else if (split) {   // the bf16-split build: LDS rows hold all C channels as three bf16 planes
+            const size_t rsb = 6 * C + 16;
+            const size_t xs = (size_t)(NT + ((2 * pp.h1 + 7) & ~7)) * rsb, ys = (size_t)(NT + 16) * rsb, es = (size_t)4 * 32 * 36 * sizeof(float);
+            const size_t smem = std::max(xs, std::max(ys, es));
+            dispatch<1, 3>(lean, [&](auto E) {   // (9: the six-product build)
+                dispatch<3, 6>(split_terms == 3 ? 3 : 6, [&](auto TT) { launch<resblock_pair_split_kernel<WM, WN, E, TT>>(h->device, grid, block, smem, h->stream, pp); });
+            });
+        } else {
+            // exact X-tile rows (NT + 2*h1) instead of NT + EV_HALO: 39 KB instead of 46 KB for k = 3 / 7 -> 4 workgroups per CU; the
+            // intermediate: C / 32 slabs of NT + 16 rows (C = 128: 64 compute rows keep it in 46 KB)
+            const size_t xs = (size_t)(NT + ((2 * pp.h1 + 7) & ~7)) * EV_LDK, ys = (size_t)(C / 32) * (NT + 16) * EV_LDK, es = (size_t)4 * 32 * 36;
+            const size_t smem = std::max(xs, std::max(ys, es)) * sizeof(float);
+            dispatch<0, 1, 3>(lean, [&](auto E) { launch<resblock_pair_kernel<WM, WN, E>>(h->device, grid, block, smem, h->stream, pp); });
+        }
+    });
     HIPCHK(h, hipGetLastError());
-    h->last_cfg = (h16 ? 160 : split ? 140 : 100) + L2.ntaps;
-    if (h->prof) {
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        const double valid_rows = (double)(g.nrows / g.S) * g.T;
-        h->prof_flops += 2.0 * (L1.macs_per_row + L2.macs_per_row) * valid_rows;
-        h->prof_launches += 1;
-        h->prof_recs.push_back({1, C, C, L1.ntaps, g.nrows, (h16 ? 160 : split ? 140 : 100) + L2.ntaps, lean, 2.0 * (L1.macs_per_row + L2.macs_per_row) * valid_rows});
-    }
-    return 0;
+    const int code = (h16 ? 160 : split ? 140 : 100) + L2.ntaps;
+    h->last_cfg = code;
+    return h->prof ? prof_end(h, {1, C, C, L1.ntaps, g.nrows, code, lean, 2.0 * (L1.macs_per_row + L2.macs_per_row) * valid_rows(g), split}) : 0;
 }
 
 // A whole ResBlock1 — three (dilated conv, conv) pairs with their residual adds — in one launch (resblock_chain_h16_kernel): the narrow levels under
@@ -1032,18 +984,10 @@ inline bool chain_ok(const ev_handle* h, const ConvLayer* L1, const ConvLayer* L
     return hs <= 12 && 2 * hb <= EV_HALO && NT - 2 * hs >= NT / 2;
 }
 int launch_chain(ev_handle* h, const ConvLayer* L1, const ConvLayer* L2, const float* X, float* Y, int C, const Geom& g, const Epi& e) {
+    if (over_4gib(g, C)) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
     ChainParams cp;
     memset(&cp, 0, sizeof cp);
     ConvParams& p = cp.c2;
-    p.X = X; p.ldx = C; p.Cin = C; p.isplit_log2 = 31;
-    p.Mpad = L2[2].Mpad; p.Kpad = L2[2].Kpad;
-    p.Y = Y; p.ldy = C; p.Cout = C; p.osplit_log2 = 31; p.mmul = 1;
-    p.nrows = g.nrows; p.S = g.S; p.P = g.P; p.T = g.T;
-    p.pro_lrelu = 1; p.pro_slope = 0.1f;
-    p.scale = 1.f; p.R = nullptr; p.ldr = C; p.accum = e.accum; p.div3 = e.div3; p.act2_lrelu = e.act2_lrelu; p.act2_slope = e.act2_slope;
-    p.rmax = nullptr; p.yold = e.yold; p.ymax_mul = 1; h->amax_emitted = false;
-    if (e.ymax && (!e.accum || e.yold) && h->use_amax) { p.ymax = e.ymax; h->amax_emitted = true; }
-    if ((double)g.nrows * C * 4.0 >= 4294967296.0) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
     int hb = 0;
     double macs = 0;
     for (int m = 0; m < 3; ++m) {
@@ -1053,34 +997,20 @@ int launch_chain(ev_handle* h, const ConvLayer* L1, const ConvLayer* L2, const f
         macs += L1[m].macs_per_row + L2[m].macs_per_row;
     }
     cp.ntaps1 = L1[0].ntaps; cp.ntaps2 = L2[0].ntaps; cp.hb = hb; cp.halo = chain_halo(L1, L2); cp.mid_slope = 0.1f;
-    const int NT = C == 32 ? 256 : 128, RSB = 4 * C + 16;
-    cp.out_rows = NT - 2 * cp.halo; p.mtiles = 1; p.ntiles = (g.nrows + cp.out_rows - 1) / cp.out_rows;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) {
-        if (h->ev_used + 2 > h->ev_pool.size()) {
-            for (int i = 0; i < 64; ++i) { hipEvent_t ev; HIPCHK(h, hipEventCreate(&ev)); h->ev_pool.push_back(ev); }
-        }
-        e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-    }
-    const int lean = (e.accum || e.div3 || e.act2_lrelu) ? 3 : 1;
-    const size_t smem = std::max((size_t)(NT + EV_HALO) * RSB + 64, (size_t)4 * 32 * 36 * sizeof(float));
-    const dim3 grid(p.ntiles);
-#define EV_CHAIN(WM, WN) do { \
-        if (lean == 1) { ensure_dyn_smem<resblock_chain_h16_kernel<WM, WN, 1>>(smem, h->device); hipLaunchKernelGGL((resblock_chain_h16_kernel<WM, WN, 1>), grid, dim3(256), smem, h->stream, cp); } \
-        else { ensure_dyn_smem<resblock_chain_h16_kernel<WM, WN, 3>>(smem, h->device); hipLaunchKernelGGL((resblock_chain_h16_kernel<WM, WN, 3>), grid, dim3(256), smem, h->stream, cp); } } while (0)
-    if (C == 32) EV_CHAIN(1, 4); else EV_CHAIN(2, 2);
-#undef EV_CHAIN
+    const int NT = 8192 / C;
+    cp.out_rows = NT - 2 * cp.halo;
+    resblock_params(h, p, L2[2], X, Y, C, g, e, cp.out_rows);
+    resblock_bounds(h, p, e);
+    if (prof_begin(h)) return 1;
+    const int lean = epi_flavour(p, true);
+    const size_t smem = std::max((size_t)(NT + EV_HALO) * (4 * C + 16) + 64, (size_t)4 * 32 * 36 * sizeof(float));
+    dispatch<32, 64>(C, [&](auto CC) {
+        constexpr int WM = CC / 32, WN = 4 / WM;
+        dispatch<1, 3>(lean, [&](auto E) { launch<resblock_chain_h16_kernel<WM, WN, E>>(h->device, dim3(p.ntiles), dim3(256), smem, h->stream, cp); });
+    });
     HIPCHK(h, hipGetLastError());
     h->last_cfg = 180 + L2[0].ntaps;
-    if (h->prof) {
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        const double valid_rows = (double)(g.nrows / g.S) * g.T;
-        h->prof_flops += 2.0 * macs * valid_rows;
-        h->prof_launches += 1;
-        h->prof_recs.push_back({1, C, C, L1[0].ntaps, g.nrows, 180 + L2[0].ntaps, lean, 2.0 * macs * valid_rows});
-    }
-    return 0;
+    return h->prof ? prof_end(h, {1, C, C, L1[0].ntaps, g.nrows, 180 + L2[0].ntaps, lean, 2.0 * macs * valid_rows(g), true}) : 0;
 }
 
 // A whole ResBlock2 — two dilated convs with their residual adds — in one launch (resblock2_h16_kernel), arithmetic setting 16.  rb2_ok() is the
@@ -1098,53 +1028,31 @@ inline bool rb2_ok(const ev_handle* h, const ConvLayer* L, int C) {
     return 8 * (NT - 2 * rb2_halo(L)) >= h->rb2_minkeep * NT && NT - 2 * rb2_halo(L) > 0;
 }
 int launch_rb2(ev_handle* h, const ConvLayer* L, const float* X, float* Y, int C, const Geom& g, const Epi& e) {
+    if (over_4gib(g, C)) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
     Rb2Params cp;
     memset(&cp, 0, sizeof cp);
     ConvParams& p = cp.c2;
-    p.X = X; p.ldx = C; p.Cin = C; p.isplit_log2 = 31;
-    p.Mpad = L[1].Mpad; p.Kpad = L[1].Kpad;
-    p.Y = Y; p.ldy = C; p.Cout = C; p.osplit_log2 = 31; p.mmul = 1;
-    p.nrows = g.nrows; p.S = g.S; p.P = g.P; p.T = g.T;
-    p.pro_lrelu = 1; p.pro_slope = 0.1f;
-    p.scale = 1.f; p.R = nullptr; p.ldr = C; p.accum = e.accum; p.div3 = e.div3; p.act2_lrelu = e.act2_lrelu; p.act2_slope = e.act2_slope;
-    p.rmax = nullptr; p.yold = e.yold; p.ymax_mul = 1; h->amax_emitted = false;
-    if (e.ymax && (!e.accum || e.yold) && h->use_amax) { p.ymax = e.ymax; h->amax_emitted = true; }
-    if ((double)g.nrows * C * 4.0 >= 4294967296.0) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
     int hb = 0;
     for (int m = 0; m < 2; ++m) {
         cp.Wh[m] = L[m].Wh; cp.w_scale[m] = L[m].wh_scale; cp.b[m] = L[m].bias; cp.tl[m] = L[m].taplist[0];
         hb = std::max(hb, L[m].halo_lo);
     }
     cp.ntaps = L[0].ntaps; cp.hb = hb; cp.halo = rb2_halo(L);
-    const int NT = C == 32 ? 256 : C == 64 ? 128 : 64, RSB = 4 * C + 16;
-    cp.out_rows = NT - 2 * cp.halo; p.mtiles = 1; p.ntiles = (g.nrows + cp.out_rows - 1) / cp.out_rows;
+    const int NT = 8192 / C;
+    cp.out_rows = NT - 2 * cp.halo;
     if (cp.out_rows <= 0) return fail(h, "launch_rb2: halo %d leaves no row of a %d-frame tile", cp.halo, NT);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) {
-        if (h->ev_used + 2 > h->ev_pool.size()) {
-            for (int i = 0; i < 64; ++i) { hipEvent_t ev; HIPCHK(h, hipEventCreate(&ev)); h->ev_pool.push_back(ev); }
-        }
-        e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-    }
-    const int lean = (e.accum || e.div3 || e.act2_lrelu) ? 3 : 1;
-    const size_t smem = std::max((size_t)(NT + 2 * hb) * RSB + 64, (size_t)4 * 32 * 36 * sizeof(float));
-    const dim3 grid(p.ntiles);
-#define EV_RB2(WM, WN) do { \
-        if (lean == 1) { ensure_dyn_smem<resblock2_h16_kernel<WM, WN, 1>>(smem, h->device); hipLaunchKernelGGL((resblock2_h16_kernel<WM, WN, 1>), grid, dim3(256), smem, h->stream, cp); } \
-        else { ensure_dyn_smem<resblock2_h16_kernel<WM, WN, 3>>(smem, h->device); hipLaunchKernelGGL((resblock2_h16_kernel<WM, WN, 3>), grid, dim3(256), smem, h->stream, cp); } } while (0)
-    if (C == 32) EV_RB2(1, 4); else if (C == 64) EV_RB2(2, 2); else EV_RB2(4, 1);
-#undef EV_RB2
+    resblock_params(h, p, L[1], X, Y, C, g, e, cp.out_rows);
+    resblock_bounds(h, p, e);
+    if (prof_begin(h)) return 1;
+    const int lean = epi_flavour(p, true);
+    const size_t smem = std::max((size_t)(NT + 2 * hb) * (4 * C + 16) + 64, (size_t)4 * 32 * 36 * sizeof(float));
+    dispatch<32, 64, 128>(C, [&](auto CC) {
+        constexpr int WM = CC / 32, WN = 4 / WM;
+        dispatch<1, 3>(lean, [&](auto E) { launch<resblock2_h16_kernel<WM, WN, E>>(h->device, dim3(p.ntiles), dim3(256), smem, h->stream, cp); });
+    });
     HIPCHK(h, hipGetLastError());
     h->last_cfg = 200 + L[0].ntaps;
-    if (h->prof) {
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        const double valid_rows = (double)(g.nrows / g.S) * g.T, macs = L[0].macs_per_row + L[1].macs_per_row;
-        h->prof_flops += 2.0 * macs * valid_rows;
-        h->prof_launches += 1;
-        h->prof_recs.push_back({1, C, C, L[0].ntaps, g.nrows, 200 + L[0].ntaps, lean, 2.0 * macs * valid_rows});
-    }
-    return 0;
+    return h->prof ? prof_end(h, {1, C, C, L[0].ntaps, g.nrows, 200 + L[0].ntaps, lean, 2.0 * (L[0].macs_per_row + L[1].macs_per_row) * valid_rows(g), true}) : 0;
 }
 
 int launch_gn(ev_handle* h, const float* X, int ldx, float* Y, int ldy, const float* gamma, const float* beta, const float* rowmask,
@@ -1201,46 +1109,27 @@ int launch_mlp(ev_handle* h, int mode, const float* X, const float* ln_g, const 
         return fail(h, "launch_mlp: first linear must be 256 -> multiple of 128 (got %d -> %d)", L1.Cin, L1.Cout);
     if (mode == 0 && (!L2 || L2->Cout != 256 || L2->Mpad != 256 || L2->Cin != L1.Cout || L2->Kpad != L1.Mpad || L2->ntaps != 1 || !L2->bias || !alpha || !binv))
         return fail(h, "launch_mlp: second linear must be %d -> 256 with bias", L1.Cout);
-    if ((double)g.nrows * std::max(ldy, 256) * 4.0 >= 4294967296.0) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
+    if (over_4gib(g, std::max(ldy, 256))) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
     if (g.S < 4 && g.nrows > 1) return fail(h, "launch_mlp: utterance stride %d < 4 rows is not supported by the lean row walk", g.S);
     const int nchunk = L1.Mpad / 128;
+    const double flops = 2.0 * (L1.macs_per_row + (L2 ? L2->macs_per_row : 0.0)) * valid_rows(g);
     {   // the feed-forward of a large batch on the bf16 pipe: 64-row tiles, one persistent workgroup per CU (ln_mlp_split_kernel)
         const int split_terms = h->split_terms;
         const int nt64 = (g.nrows + 63) / 64;
         if (mode == 0 && (split_terms == 6 || split_terms == 16) && L1.Wx && L2->Wx && h->sk_balance && h->ncu > 0 && h->ncu <= EV_SK_MAXWG && nt64 >= h->ncu) {
-            if (ensure_sk(h)) return 1;
-            const long U = (long)nt64 * nchunk;
             const int grid = h->ncu;
             const bool h16 = split_terms == 16 && L1.Wh && L2->Wh;
             mp.W1x = L1.Wx; mp.W2x = L2->Wx; mp.ntiles = nt64;
             mp.W1h = L1.Wh; mp.W2h = L2->Wh; mp.w1_scale = L1.wh_scale; mp.w2_scale = L2->wh_scale;
-            mp.sk.q = (int)(U / grid); mp.sk.r = (int)(U % grid); mp.sk.spin_limit = h->sk_spin;
-            mp.sk.ctrl = h->sk_ctrl; mp.sk.flags = h->sk_ctrl + 16; mp.sk.part = h->sk_part; mp.sk.part_floats = EV_SK_PART_FLOATS;
-            if (h16) { mp.sk.claims = h->sk_ctrl + 16 + EV_SK_MAXWG; mp.sk.seq = ++h->sk_seq; }
+            if (sk_setup(h, mp.sk, (long)nt64 * nchunk, grid, h16)) return 1;
             if (L1.Mpad > 1024) return fail(h, "launch_mlp: hidden width %d > 1024 (LDS table of the SnakeBeta vectors)", L1.Mpad);
             const size_t smem = h16 ? (size_t)64 * (4 * 256 + 16) + (size_t)64 * (4 * 128 + 16) + 16 + (size_t)2 * L1.Mpad * sizeof(float) + 64
                                     : (size_t)64 * (6 * 256 + 16) + (size_t)64 * (6 * 128 + 16) + 16 + (size_t)2 * L1.Mpad * sizeof(float);
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (h->prof) {
-                if (h->ev_used + 2 > h->ev_pool.size()) {
-                    for (int i = 0; i < 64; ++i) { hipEvent_t ev; HIPCHK(h, hipEventCreate(&ev)); h->ev_pool.push_back(ev); }
-                }
-                e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
-                HIPCHK(h, hipEventRecord(e0, h->stream));
-            }
-            if (h16) ensure_dyn_smem<ln_mlp_h16_kernel<0>>(smem, h->device); else ensure_dyn_smem<ln_mlp_split_kernel<6>>(smem, h->device);
-            if (h16) hipLaunchKernelGGL((ln_mlp_h16_kernel<0>), dim3(grid), dim3(256), smem, h->stream, mp);
-            else hipLaunchKernelGGL((ln_mlp_split_kernel<6>), dim3(grid), dim3(256), smem, h->stream, mp);
+            if (prof_begin(h)) return 1;
+            if (h16) launch<ln_mlp_h16_kernel<0>>(h->device, dim3(grid), dim3(256), smem, h->stream, mp);
+            else launch<ln_mlp_split_kernel<6>>(h->device, dim3(grid), dim3(256), smem, h->stream, mp);
             HIPCHK(h, hipGetLastError());
-            if (h->prof) {
-                HIPCHK(h, hipEventRecord(e1, h->stream));
-                const double valid_rows = (double)(g.nrows / g.S) * g.T;
-                const double fl = 2.0 * (L1.macs_per_row + L2->macs_per_row) * valid_rows;
-                h->prof_flops += fl;
-                h->prof_launches += 1;
-                h->prof_recs.push_back({2, 256, Lout.Cout, 1, g.nrows, h16 ? 121 : 120, 1, fl});
-            }
-            return 0;
+            return h->prof ? prof_end(h, {2, 256, Lout.Cout, 1, g.nrows, h16 ? 121 : 120, 1, flops, true}) : 0;
         }
     }
     {   // LayerNorm + QKV of a large batch on the fp16 pipe: one workgroup per 64-row tile (ln_qkv_h16_kernel)
@@ -1252,27 +1141,11 @@ int launch_mlp(ev_handle* h, int mode, const float* X, const float* ln_g, const 
                 for (int i = 0; i < 3; ++i) mp.qkv_scale[i] = qkv_scale[i];
             }
             const size_t smem = (size_t)64 * (4 * 256 + 16) + 32;   // (+ 8 floats: the waves' maxima and their finite-only repeat)
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (h->prof) {
-                if (h->ev_used + 2 > h->ev_pool.size()) {
-                    for (int i = 0; i < 64; ++i) { hipEvent_t ev; HIPCHK(h, hipEventCreate(&ev)); h->ev_pool.push_back(ev); }
-                }
-                e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
-                HIPCHK(h, hipEventRecord(e0, h->stream));
-            }
-            ensure_dyn_smem<ln_qkv_h16_kernel<0>>(smem, h->device);
-            hipLaunchKernelGGL(ln_qkv_h16_kernel<0>, dim3(nt64), dim3(256), smem, h->stream, mp);
+            if (prof_begin(h)) return 1;
+            launch<ln_qkv_h16_kernel<0>>(h->device, dim3(nt64), dim3(256), smem, h->stream, mp);
             HIPCHK(h, hipGetLastError());
             h->last_cfg = 122;
-            if (h->prof) {
-                HIPCHK(h, hipEventRecord(e1, h->stream));
-                const double valid_rows = (double)(g.nrows / g.S) * g.T;
-                const double fl = 2.0 * L1.macs_per_row * valid_rows;
-                h->prof_flops += fl;
-                h->prof_launches += 1;
-                h->prof_recs.push_back({3, 256, Lout.Cout, 1, g.nrows, 122, 1, fl});
-            }
-            return 0;
+            return h->prof ? prof_end(h, {3, 256, Lout.Cout, 1, g.nrows, 122, 1, flops, true}) : 0;
         }
     }
     const int ntiles = (g.nrows + 31) / 32;
@@ -1286,41 +1159,24 @@ int launch_mlp(ev_handle* h, int mode, const float* X, const float* ln_g, const 
     const int wpc = h->sk_wgs;
     const bool big = ntiles >= h->ncu && (long)ntiles * nchunk >= (long)wpc * h->ncu;
     if (h->sk_balance && h->ncu > 0 && wpc * h->ncu <= EV_SK_MAXWG && big) {
-        if (ensure_sk(h)) return 1;
         const long U = (long)ntiles * nchunk;
         grid = (int)std::min<long>((long)wpc * h->ncu, U);
-        mp.sk.q = (int)(U / grid); mp.sk.r = (int)(U % grid);
-        mp.sk.ctrl = h->sk_ctrl; mp.sk.flags = h->sk_ctrl + 16; mp.sk.part = h->sk_part; mp.sk.part_floats = EV_SK_PART_FLOATS;
+        if (sk_setup(h, mp.sk, U, grid, false)) return 1;
         // three per CU: the LDS request is padded so that exactly three fit.  Two per CU (the default): the 256-register build admits
         // exactly two workgroups per CU by itself, and the un-padded request leaves LDS for the workgroups of another stream (the
         // vocoder of the previous batch in the pipelined schedule) instead of locking them out of the CU.
         if (wpc != 2) smem = std::max(smem, (size_t)((160 * 1024 / wpc) & ~255));
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) {
-        if (h->ev_used + 2 > h->ev_pool.size()) {
-            for (int i = 0; i < 64; ++i) { hipEvent_t ev; HIPCHK(h, hipEventCreate(&ev)); h->ev_pool.push_back(ev); }
-        }
-        e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-    }
+    if (prof_begin(h)) return 1;
     // the balanced grid at two workgroups per CU has its own build (256 registers, no spills); so has every launch of at most two
     // tiles per CU (small batches: one tile per workgroup, at most two of them on a CU)
     const bool two = (mp.sk.ctrl != nullptr && wpc == 2) || (mp.sk.ctrl == nullptr && h->ncu > 0 && ntiles <= 2 * h->ncu);
-    if (mode == 0 && two) { ensure_dyn_smem<ln_mlp_kernel<0, 2>>(smem, h->device); hipLaunchKernelGGL((ln_mlp_kernel<0, 2>), dim3(grid), dim3(256), smem, h->stream, mp); }
-    else if (mode == 0) { ensure_dyn_smem<ln_mlp_kernel<0, 3>>(smem, h->device); hipLaunchKernelGGL((ln_mlp_kernel<0, 3>), dim3(grid), dim3(256), smem, h->stream, mp); }
-    else if (two) { ensure_dyn_smem<ln_mlp_kernel<1, 2>>(smem, h->device); hipLaunchKernelGGL((ln_mlp_kernel<1, 2>), dim3(grid), dim3(256), smem, h->stream, mp); }
-    else { ensure_dyn_smem<ln_mlp_kernel<1, 3>>(smem, h->device); hipLaunchKernelGGL((ln_mlp_kernel<1, 3>), dim3(grid), dim3(256), smem, h->stream, mp); }
+    dispatch<0, 1>(mode != 0, [&](auto M) {
+        if (two) launch<ln_mlp_kernel<M, 2>>(h->device, dim3(grid), dim3(256), smem, h->stream, mp);
+        else launch<ln_mlp_kernel<M, 3>>(h->device, dim3(grid), dim3(256), smem, h->stream, mp);
+    });
     HIPCHK(h, hipGetLastError());
-    if (h->prof) {
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        const double valid_rows = (double)(g.nrows / g.S) * g.T;
-        const double fl = 2.0 * (L1.macs_per_row + (L2 ? L2->macs_per_row : 0.0)) * valid_rows;
-        h->prof_flops += fl;
-        h->prof_launches += 1;
-        h->prof_recs.push_back({2 + mode, 256, Lout.Cout, 1, g.nrows, 20 + mode, 1, fl});
-    }
-    return 0;
+    return h->prof ? prof_end(h, {2 + mode, 256, Lout.Cout, 1, g.nrows, 20 + mode, 1, flops}) : 0;
 }
 
 // `part`: scratch for the split-key small-launch build, 4 * rows * (H*64 + 2*H) floats (null: always the one-launch kernel)
@@ -1415,29 +1271,15 @@ int launch_attn_out(ev_handle* h, const float* QKV, int ld, const ConvLayer& Lo,
     e.Y = Hid; e.ldy = ldh; e.Cout = Lo.Cout; e.bias = Lo.bias; e.R = Hid; e.ldr = ldh; e.osplit_log2 = 31; e.isplit_log2 = 31; e.mmul = 1; e.scale = 1.f;
     e.nrows = g.nrows; e.S = g.S; e.P = g.P; e.T = g.T;
     if ((ldh & 3) || (ld & 3) || ((size_t)Lo.bias & 15)) return fail(h, "launch_attn_out: unaligned operand");
-    if ((double)g.nrows * std::max(ld, ldh) * 4.0 >= 4294967296.0) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
+    if (over_4gib(g, std::max(ld, ldh))) return fail(h, "tensor exceeds the 4 GiB buffer-addressing limit: split the batch");
     const size_t smem = h16 ? (size_t)4 * AOH_WB : (size_t)4 * 2 * 32 * AO_LDK * sizeof(float);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) {
-        if (h->ev_used + 2 > h->ev_pool.size()) {
-            for (int i = 0; i < 64; ++i) { hipEvent_t ev; HIPCHK(h, hipEventCreate(&ev)); h->ev_pool.push_back(ev); }
-        }
-        e0 = h->ev_pool[h->ev_used++]; e1 = h->ev_pool[h->ev_used++];
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-    }
-    if (h16) ensure_dyn_smem<attn_out_h16_kernel>(smem, h->device); else ensure_dyn_smem<attn_out_kernel>(smem, h->device);
+    if (prof_begin(h)) return 1;
     const dim3 grid((unsigned)(p.nq * B + (p.ntail > 0 ? B : 0)));
-    if (h16) hipLaunchKernelGGL(attn_out_h16_kernel, grid, dim3(256), smem, h->stream, p);
-    else hipLaunchKernelGGL(attn_out_kernel, grid, dim3(256), smem, h->stream, p);
+    if (h16) launch<attn_out_h16_kernel>(h->device, grid, dim3(256), smem, h->stream, p);
+    else launch<attn_out_kernel>(h->device, grid, dim3(256), smem, h->stream, p);
     HIPCHK(h, hipGetLastError());
-    if (h->prof) {
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        const double fl = (double)B * ((double)H * 4.0 * g.T * (double)g.T * 64.0 + 2.0 * Lo.macs_per_row * g.T);
-        h->prof_flops += fl;
-        h->prof_launches += 1;
-        h->prof_recs.push_back({4, 128, 256, 1, g.nrows, h16 ? 31 : 30, 1, fl});      // (31: attn_out_h16_kernel, counted with the fp16 builds)
-    }
-    return 0;
+    const double fl = (double)B * ((double)H * 4.0 * g.T * (double)g.T * 64.0 + 2.0 * Lo.macs_per_row * g.T);
+    return h->prof ? prof_end(h, {4, 128, 256, 1, g.nrows, h16 ? 31 : 30, 1, fl, h16}) : 0;   // (31: attn_out_h16_kernel, counted with the fp16 builds)
 }
 
 // ---------------------------------------------------------------------------
@@ -2935,8 +2777,7 @@ int ev_profile_read_split(ev_handle* h, double* ms_out, double* flops_out, int64
     if (h->prof_recs.size() * 2 == h->ev_used)
         for (size_t i = 0; i < h->prof_recs.size(); ++i) {
             const auto& r = h->prof_recs[i];
-            const bool split = (r.kind == 0 && (r.cfg == 40 || r.cfg == 41 || r.cfg == 46 || r.cfg == 47 || r.cfg == 66 || r.cfg == 43 || r.cfg == 49 || r.cfg == 60)) || (r.kind == 1 && r.cfg >= 140) || (r.kind == 2 && (r.cfg == 120 || r.cfg == 121)) || (r.kind == 3 && r.cfg == 122) || (r.kind == 4 && r.cfg == 31);
-            if (!split) continue;
+            if (!r.split) continue;
             float t = 0;
             HIPCHK(h, hipEventElapsedTime(&t, h->ev_pool[2 * i], h->ev_pool[2 * i + 1]));
             ms += t; fl += r.flops; n += 1;

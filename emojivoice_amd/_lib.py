@@ -24,6 +24,7 @@ EXPORTS = [
     "ev_workspace_bytes", "ev_cfm_decode", "ev_estimator", "ev_hifigan", "ev_profile_enable", "ev_profile_read", "ev_profile_read_split", "ev_dbg_last_cfg", "ev_set_arithmetic", "ev_get_arithmetic",
     "ev_op_conv1d", "ev_op_groupnorm_mish", "ev_op_layernorm", "ev_op_split_pieces", "ev_op_attention", "ev_op_ln_mlp", "ev_set_mrf_streams_max",
     "ev_cfm_decode2", "ev_reserve", "ev_alloc_count", "ev_dbg_sk_stats", "ev_op_attn_out", "ev_dbg_set_amax", "ev_dbg_set_attn_h16", "ev_dbg_set_chain", "ev_dbg_sk_taken",
+    "ev_load_mel_basis", "ev_mel_spectrogram",
 ]
 
 
@@ -131,6 +132,8 @@ def load_library() -> C.CDLL:
     lib.ev_stft_magnitude.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.ev_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_denoise.argtypes = [vp, vp, i32, i32, vp, f32, vp, vp]
+    lib.ev_load_mel_basis.argtypes = [vp, vp, i32, i32]
+    lib.ev_mel_spectrogram.argtypes = [vp, vp, i32, i32, f32, f32, vp, vp]
     lib.ev_profile_enable.argtypes = [vp, i32]
     lib.ev_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), i32]
     lib.ev_profile_read_split.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -271,6 +274,25 @@ class Engine:
         out = torch.empty_like(audio)
         self._check(self.lib.ev_denoise(self.h, audio.data_ptr(), B, L, bias.data_ptr(), float(strength), out.data_ptr(), _stream_ptr()), "ev_denoise")
         return out
+
+    def load_mel_basis(self, basis) -> None:
+        """The mel filter bank (n_mels, 513) of ``mel_spectrogram`` (ev_load_mel_basis); a host array or tensor."""
+        b = np.ascontiguousarray(torch.as_tensor(basis).detach().to("cpu", torch.float32).numpy())
+        if b.ndim != 2:
+            raise ValueError(f"mel basis must be (n_mels, n_freq), got shape {b.shape}")
+        self._check(self.lib.ev_load_mel_basis(self.h, b.ctypes.data_as(C.c_void_p), b.shape[0], b.shape[1]), "ev_load_mel_basis")
+        self.n_mels = int(b.shape[0])
+
+    def mel_spectrogram(self, audio, out_scale: float = 1.0, out_shift: float = 0.0):
+        """log-mel (B, n_mels, L/256) of (B, L) audio: the reference's ``mel_spectrogram`` at n_fft 1024 / hop 256 / center=False
+        (utils/audio.py:45-82), times ``out_scale`` plus ``out_shift`` (ev_mel_spectrogram)."""
+        audio = self._f32(audio)
+        B, L = audio.shape
+        n_mels = getattr(self, "n_mels", 0)
+        mel = torch.empty((B, n_mels, L // 256), dtype=torch.float32, device=audio.device)
+        self._check(self.lib.ev_mel_spectrogram(self.h, audio.data_ptr(), B, L, float(out_scale), float(out_shift), mel.data_ptr(), _stream_ptr()),
+                    "ev_mel_spectrogram")
+        return mel
 
     def load_text_encoder(self, tensors: Dict[str, torch.Tensor]):
         self._load(self.lib.ev_load_text_encoder, tensors, "ev_load_text_encoder")

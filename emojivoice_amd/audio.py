@@ -1,0 +1,140 @@
+"""The analysis side: counterpart of ``matcha.utils.audio`` (the same function again in ``hifigan/meldataset.py:52``).
+
+    mel = mel_spectrogram(y, 1024, 80, 22050, 256, 1024, 0, 8000, center=False)     # (B, L) on the GPU -> (B, 80, L / 256)
+
+``mel_spectrogram`` runs entirely in the HIP library (``ev_mel_spectrogram``: reflect padding, the DFT-basis convolution of the
+denoiser, then one kernel for magnitude / mel projection / log compression); there is no torch fallback.  The reference takes its
+filter bank from ``librosa.filters.mel``; ``mel_filterbank`` restates that function's defaults (Slaney scale, Slaney normalisation)
+from the published definition.
+"""
+from __future__ import annotations
+
+import math
+import wave
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from ._lib import Engine, EvLibraryError  # noqa: F401  (EvLibraryError: what every call here raises without the library / a GPU)
+
+_F_SP = 200.0 / 3.0                 # Hz per mel below 1 kHz
+_MIN_LOG_HZ = 1000.0
+_MIN_LOG_MEL = _MIN_LOG_HZ / _F_SP  # = 15
+_LOGSTEP = math.log(6.4) / 27.0     # mel step of the logarithmic part
+
+
+def hz_to_mel(f):
+    """Slaney's mel scale (Auditory Toolbox): linear below 1 kHz, logarithmic above."""
+    f = np.asarray(f, dtype=np.float64)
+    return np.where(f >= _MIN_LOG_HZ, _MIN_LOG_MEL + np.log(np.maximum(f, 1e-300) / _MIN_LOG_HZ) / _LOGSTEP, f / _F_SP)
+
+
+def mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m >= _MIN_LOG_MEL, _MIN_LOG_HZ * np.exp(_LOGSTEP * (m - _MIN_LOG_MEL)), _F_SP * m)
+
+
+def mel_filterbank(sr: int, n_fft: int, n_mels: int, fmin: float = 0.0, fmax: Optional[float] = None) -> np.ndarray:
+    """The (n_mels, n_fft // 2 + 1) triangular filter bank ``librosa.filters.mel(sr=, n_fft=, n_mels=, fmin=, fmax=)`` returns
+    with its defaults (``htk=False, norm="slaney"``): band edges equally spaced on Slaney's mel scale between fmin and fmax
+    (None: sr / 2), each triangle scaled by 2 / (f_hi - f_lo).  Computed in float64, rounded once to float32."""
+    if fmax is None:
+        fmax = sr / 2.0
+    n_freq = n_fft // 2 + 1
+    fft_f = np.arange(n_freq, dtype=np.float64) * (float(sr) / n_fft)
+    edges = mel_to_hz(np.linspace(float(hz_to_mel(fmin)), float(hz_to_mel(fmax)), n_mels + 2))
+    fdiff = np.diff(edges)
+    ramps = edges[:, None] - fft_f[None, :]
+    lower = -ramps[:-2] / fdiff[:-1, None]
+    upper = ramps[2:] / fdiff[1:, None]
+    w = np.maximum(0.0, np.minimum(lower, upper))
+    w *= (2.0 / (edges[2:] - edges[:-2]))[:, None]
+    return w.astype(np.float32)
+
+
+# (device index, sr, n_mels, fmin, fmax) -> Engine with that bank loaded; the reference caches per (fmax, device)
+_engines: Dict[Tuple, Engine] = {}
+
+
+def _engine_for(device: torch.device, sr, n_mels, fmin, fmax) -> Engine:
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, int(sr), int(n_mels), float(fmin), None if fmax is None else float(fmax))
+    eng = _engines.get(key)
+    if eng is None:
+        eng = Engine(idx)
+        eng.load_mel_basis(mel_filterbank(sr, 1024, n_mels, fmin, fmax))
+        _engines[key] = eng
+    return eng
+
+
+def _check_args(n_fft, num_mels, hop_size, win_size, center) -> None:
+    if n_fft != 1024 or win_size != 1024:
+        raise ValueError(f"mel_spectrogram: the HIP engine implements n_fft = win_size = 1024 only (got n_fft={n_fft}, win_size={win_size})")
+    if hop_size != 256:
+        raise ValueError(f"mel_spectrogram: the HIP engine implements hop_size = 256 only (got {hop_size})")
+    if center:
+        raise ValueError("mel_spectrogram: the HIP engine implements center=False only (the reference's only call)")
+    if not 1 <= int(num_mels) <= 128:
+        raise ValueError(f"mel_spectrogram: num_mels must be 1..128 (got {num_mels})")
+
+
+@torch.inference_mode()
+def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False, out_scale: float = 1.0,
+                    out_shift: float = 0.0):
+    """``matcha.utils.audio.mel_spectrogram`` (utils/audio.py:45-82): ``y`` (B, L) on the GPU -> log-mel (B, num_mels, L / 256).
+
+    What the engine does not implement raises ``ValueError``: n_fft = win_size = 1024, hop_size 256, center=False, L a multiple of
+    256 (and > 384, which the reflect padding needs as in torch).  The filter bank and the native handle are cached per
+    (device, sampling_rate, num_mels, fmin, fmax).  The reference's two ``print``s for samples outside [-1, 1] are not reproduced:
+    they would force a host synchronisation on every call.  ``out_scale`` / ``out_shift`` (not in the reference) fuse
+    ``normalize(mel, mel_mean, mel_std)`` of utils/model.py: 1 / mel_std and -mel_mean / mel_std."""
+    _check_args(n_fft, num_mels, hop_size, win_size, center)
+    if y.dim() != 2:
+        raise ValueError(f"mel_spectrogram: y must be (B, L), got shape {tuple(y.shape)}")
+    L = int(y.shape[1])
+    if L % 256 or L <= 384:
+        raise ValueError(f"mel_spectrogram: L must be a multiple of 256 and > 384 (got {L}); trim or pad the signal")
+    if not y.is_cuda:
+        raise EvLibraryError("mel_spectrogram runs on a ROCm GPU only (no CPU fallback): move y to the GPU")
+    return _engine_for(y.device, sampling_rate, num_mels, fmin, fmax).mel_spectrogram(y, out_scale, out_shift)
+
+
+@torch.inference_mode()
+def mel_reconstruction_error(vocoder, mel, lengths=None):
+    """Per-utterance mean |mel - mel_spectrogram(vocoder(mel))| over the valid frames and all mel bins, (B,) on the device: HiFi-GAN's
+    validation measure (the ``mel_loss`` spectrogram of hifigan/meldataset.py:202 against the generator's output, without the x45
+    training weight), with the analysis parameters of the vocoder's config (fmax = ``h.fmax``: the bank the input mel was made
+    with).  ``lengths`` (B,): valid frames per utterance (None: all).  Nothing leaves the device."""
+    h = vocoder.h
+    mel = mel.to(vocoder.device, torch.float32)
+    wav = vocoder(mel).squeeze(1)
+    got = mel_spectrogram(wav, h.get("n_fft", 1024), h.get("num_mels", 80), h.get("sampling_rate", 22050), h.get("hop_size", 256),
+                          h.get("win_size", 1024), h.get("fmin", 0), h.get("fmax", 8000))
+    diff = (mel - got).abs()
+    B, M, T = diff.shape
+    if lengths is None:
+        return diff.mean(dim=(1, 2))
+    lengths = lengths.to(diff.device)
+    mask = (torch.arange(T, device=diff.device)[None, :] < lengths[:, None]).to(diff.dtype)
+    return (diff * mask[:, None, :]).sum(dim=(1, 2)) / (lengths.to(diff.dtype) * M)
+
+
+def read_wav_pcm(path, sr: int = 22050) -> np.ndarray:
+    """A mono 16- or 24-bit PCM wav at ``sr`` as float32 in [-1, 1): the inverse of ``cli.write_wav_pcm24`` for 24-bit files
+    (q / (2**23 - 1)), q / 32768 for 16-bit ones (MAX_WAV_VALUE of utils/audio.py)."""
+    with wave.open(str(path), "rb") as f:
+        if f.getnchannels() != 1:
+            raise ValueError(f"{path}: {f.getnchannels()} channels (mono only)")
+        if f.getframerate() != sr:
+            raise ValueError(f"{path}: {f.getframerate()} Hz (this front end does not resample: {sr} Hz only)")
+        width, raw = f.getsampwidth(), f.readframes(f.getnframes())
+    if width == 2:
+        return (np.frombuffer(raw, dtype="<i2").astype(np.float64) / 32768.0).astype(np.float32)
+    if width == 3:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3)
+        q = np.zeros((b.shape[0], 4), dtype=np.uint8)
+        q[:, 1:] = b                                              # into the top three bytes: the shift back sign-extends
+        q = q.reshape(-1).view("<i4") >> 8
+        return (q.astype(np.float64) / (2**23 - 1)).astype(np.float32)
+    raise ValueError(f"{path}: {8 * width}-bit samples (16- or 24-bit PCM only)")

@@ -7,6 +7,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
 
     python -m emojivoice_amd.cli --checkpoint_path model.ckpt --vocoder_path g_02500000 --ids "0 23 0 51 0" --spk 12
     python -m emojivoice_amd.cli --synthetic --emoji-text "Hello world 🙂" --ids "0 23 0 51 0"
+    python -m emojivoice_amd.cli --mel_from_wav voice.wav [--vocoder_path g_02500000 | --synthetic]     # analysis: voice.wav.mel.npy (+ copy synthesis)
 """
 from __future__ import annotations
 
@@ -36,6 +37,8 @@ def write_wav_pcm24(path, wav: np.ndarray, sr: int = 22050):
 
 
 def validate_args(args):
+    if args.mel_from_wav:
+        return args
     assert args.ids or args.file or args.phonemes, "One of --ids, --phonemes or --file must be provided"
     assert args.temperature >= 0, "Sampling temperature cannot be negative"
     assert args.steps > 0, "Number of ODE steps must be greater than 0"
@@ -115,6 +118,39 @@ def parse_lines(args):
 
 
 @torch.inference_mode()
+def mel_from_wav(args, device):
+    """--mel_from_wav: PATH (22.05 kHz mono PCM, 16 / 24 bit) -> PATH.mel.npy (80, frames) with the analysis parameters of the
+    vocoder config (hifigan/meldataset.py:52 as text_mel_datamodule.py:202 calls it), the signal trimmed to a multiple of 256
+    samples; with vocoder weights also PATH.copysyn.wav, the vocoder's rendering of that mel (copy synthesis)."""
+    from . import weights as W
+    from .audio import mel_spectrogram, read_wav_pcm
+    from .hifigan import AttrDict, Generator
+
+    h = AttrDict(vocoder_config(args.vocoder_config))
+    y = read_wav_pcm(args.mel_from_wav, int(h.get("sampling_rate", 22050)))
+    n = len(y) // 256 * 256
+    if n <= 384:
+        sys.exit(f"[-] {args.mel_from_wav}: {len(y)} samples, at least 512 are needed")
+    y = torch.from_numpy(y[:n].copy()).to(device).unsqueeze(0)
+    mel = mel_spectrogram(y, h.get("n_fft", 1024), h.get("num_mels", 80), h.get("sampling_rate", 22050), h.get("hop_size", 256),
+                          h.get("win_size", 1024), h.get("fmin", 0), h.get("fmax", 8000))
+    out = f"{args.mel_from_wav}.mel.npy"
+    np.save(out, mel[0].cpu().numpy())
+    print(f"[+] Mel saved: {Path(out).resolve()}  ({mel.shape[-1]} frames, {n / 22050:.2f} s)")
+    if not (args.vocoder_path or args.synthetic):
+        return
+    sd = W.synthetic_hifigan_state(h) if args.synthetic else torch.load(args.vocoder_path, map_location="cpu")["generator"]
+    vocoder = Generator(h).to(device)
+    vocoder.load_state_dict(sd)
+    vocoder.eval()
+    vocoder.remove_weight_norm()
+    wav = vocoder(mel).clamp(-1, 1).reshape(-1).cpu().numpy()
+    out = f"{args.mel_from_wav}.copysyn.wav"
+    write_wav_pcm24(out, wav)
+    print(f"[+] Copy synthesis saved: {Path(out).resolve()}")
+
+
+@torch.inference_mode()
 def cli(argv=None):
     p = argparse.ArgumentParser(description="Matcha-TTS / EmojiVoice synthesis on MI355X")
     p.add_argument("--checkpoint_path", type=str, default=None)
@@ -137,7 +173,13 @@ def cli(argv=None):
     p.add_argument("--output_folder", type=str, default=os.getcwd())
     p.add_argument("--batched", action="store_true")
     p.add_argument("--batch_size", type=int, default=32)
+    p.add_argument("--mel_from_wav", type=str, default=None, help="analysis instead of synthesis: a 22.05 kHz mono PCM wav (16 / 24 bit) -> PATH.mel.npy; "
+                   "with --vocoder_path or --synthetic also PATH.copysyn.wav (copy synthesis)")
     args = validate_args(p.parse_args(argv))
+    if args.mel_from_wav:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return mel_from_wav(args, torch.device("cuda", 0))
     if not args.synthetic:
         assert args.checkpoint_path and args.vocoder_path, "--checkpoint_path and --vocoder_path are required (or --synthetic)"
     if not torch.cuda.is_available():

@@ -117,6 +117,9 @@ struct TextEncW {
 // Denoiser STFT pair (hifigan/denoiser.py): windowed DFT bases as two 4-tap convolutions over rows of 256 samples
 struct DenoiserW { bool ready = false; ConvLayer fwd, inv; float* win2 = nullptr; };
 
+// Mel filter bank of ev_mel_spectrogram: per filter {first bin, count, offset into wts} and the weights of those spans only
+struct MelBasisW { bool loaded = false; int n_mels = 0, nb = 0; int* span = nullptr; float* wts = nullptr; };
+
 }  // namespace
 
 struct ev_handle {
@@ -128,6 +131,7 @@ struct ev_handle {
     VocoderW voc;
     TextEncW enc;
     DenoiserW dn;
+    MelBasisW melb;
     // small per-stage scratch arenas (denoiser, text encoder): grown on demand, ordered against their last user's stream
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
     Scratch dn_ws, enc_ws;
@@ -1815,6 +1819,36 @@ int run_denoiser(ev_handle* h, const float* d_audio, int B, int L, const float* 
     return 0;
 }
 
+// mel_spectrogram: reflect pad 384 -> the denoiser's forward DFT (frame f = rows f .. f+3 of the T + 3 signal rows) -> mel_project_kernel.
+// Scratch: the first two tensors of run_denoiser's plan on one row fewer per utterance, so ev_reserve's denoiser share covers it.
+int run_mel(ev_handle* h, const float* d_audio, int B, int L, float out_scale, float out_shift, float* d_mel) {
+    if (denoiser_init(h)) return 1;
+    const DenoiserW& w = h->dn;
+    const MelBasisW& mb = h->melb;
+    const int T = L / 256, R = T + 3, P = 4, S = R + 2 * P;
+    const Geom g{B * S, S, P, R};
+    const size_t n = (size_t)g.nrows;
+    const size_t need = (n * (256 + 1032) + 1024) * sizeof(float);
+    if (scratch_acquire(h, h->dn_ws, need)) return 1;
+    Bump bp; bp.base = h->dn_ws.p; bp.off = 0;
+    float* SIG = bp.take(n * 256); float* SPEC = bp.take(n * 1032);
+    hipStream_t st = h->stream;
+    HIPCHK(h, hipMemsetAsync(SIG, 0, n * 256 * sizeof(float), st));       // the pad rows (read by the partial frames T .. T+2, which nothing consumes)
+    {
+        const size_t tot = (size_t)B * (L + 768);
+        hipLaunchKernelGGL(mel_pad_reflect_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d_audio, SIG, B, L, 384, S, P);
+    }
+    { Epi e; if (launch_conv(h, w.fwd, SIG, 256, SPEC, 1032, g, e)) return 1; }
+    {
+        const size_t smem = (size_t)32 * (mb.nb | 1) * sizeof(float);
+        ensure_dyn_smem<mel_project_kernel>(smem, h->device);
+        hipLaunchKernelGGL(mel_project_kernel, dim3((T + 31) / 32, B), dim3(256), smem, st, (const float*)SPEC, (const int*)mb.span, (const float*)mb.wts, d_mel,
+                           mb.n_mels, mb.nb, T, S, P, out_scale, out_shift);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -2399,7 +2433,7 @@ int ev_reserve(ev_handle* h, int B, int Tx_max, int Tp_max, int T_voc_max, void*
         const size_t need = (n * (1 + 3 * w.nch + 3 * w.C + 2 * w.dp1.Cout + 3 * w.C + w.C + w.ffc + 80 + 4) + 1024) * sizeof(float);
         if (scratch_acquire(h, h->enc_ws, need)) return 1;
     }
-    if (T_voc_max > 0) {   // denoiser scratch for L = 256 * T_voc_max (run_denoiser)
+    if (T_voc_max > 0) {   // denoiser scratch for L = 256 * T_voc_max (run_denoiser; run_mel takes a subset of the same plan)
         const size_t n = (size_t)B * (T_voc_max + 4 + 8);
         const size_t need = (n * (256 + 1032 + 256) + 1024) * sizeof(float);
         if (scratch_acquire(h, h->dn_ws, need)) return 1;
@@ -2488,6 +2522,48 @@ int ev_denoise(ev_handle* h, const float* d_audio, int B, int L, const float* d_
     if ((double)B * (L / 256 + 12) * 1032 * 4.0 >= 4294967296.0) return fail(h, "audio batch exceeds the 4 GiB buffer-addressing limit: split the batch");
     h->stream = (hipStream_t)stream;
     return run_denoiser(h, d_audio, B, L, d_bias_spec, strength, d_out, nullptr);
+}
+
+int ev_load_mel_basis(ev_handle* h, const float* basis, int n_mels, int n_freq) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!basis || n_freq != 513 || n_mels < 1 || n_mels > 128) return fail(h, "ev_load_mel_basis: bad arguments n_mels=%d n_freq=%d (n_freq must be 513 = n_fft 1024 / 2 + 1, 1 <= n_mels <= 128)", n_mels, n_freq);
+    std::vector<int> span((size_t)3 * n_mels);
+    std::vector<float> wts;
+    int nb = 1;
+    for (int m = 0; m < n_mels; ++m) {      // one span per filter: first to last non-zero bin (zeros inside a gapped row are kept, see emojivoice.h)
+        const float* row = basis + (size_t)m * n_freq;
+        int lo = n_freq, hi = -1;
+        for (int k = 0; k < n_freq; ++k) if (!(row[k] == 0.f)) { if (lo == n_freq) lo = k; hi = k; }
+        const int cnt = hi < 0 ? 0 : hi - lo + 1;
+        span[3 * m] = hi < 0 ? 0 : lo; span[3 * m + 1] = cnt; span[3 * m + 2] = (int)wts.size();
+        for (int k = 0; k < cnt; ++k) wts.push_back(row[lo + k]);
+        if (cnt) nb = std::max(nb, hi + 1);
+    }
+    if (wts.empty()) wts.push_back(0.f);
+    if (ensure_sk(h, false)) return 1;      // the forward DFT of a large batch takes a balanced build: its hand-off area is never allocated on the request path
+    MelBasisW& mb = h->melb;
+    if (mb.loaded) {                        // replace: nothing in flight may still read the old bank
+        HIPCHK(h, hipDeviceSynchronize());
+        for (void* p : {(void*)mb.span, (void*)mb.wts}) {
+            auto it = std::find(h->owned.begin(), h->owned.end(), p);
+            if (it != h->owned.end()) { h->owned.erase(it); hipFree(p); }
+        }
+        mb = MelBasisW();
+    }
+    if (dev_upload(h, span, &mb.span) || dev_upload(h, wts, &mb.wts)) return 1;
+    mb.n_mels = n_mels; mb.nb = nb; mb.loaded = true;
+    return 0;
+}
+
+int ev_mel_spectrogram(ev_handle* h, const float* d_audio, int B, int L, float out_scale, float out_shift, float* d_mel, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->melb.loaded) return fail(h, "mel basis not loaded (ev_load_mel_basis)");
+    if (B <= 0 || L <= 384 || (L & 255) || !d_audio || !d_mel) return fail(h, "bad arguments B=%d L=%d (L must be a multiple of 256, > 384: reflect padding of 384 needs more than 384 samples, as in torch's pad)", B, L);
+    if ((double)B * (L / 256 + 12) * 1032 * 4.0 >= 4294967296.0) return fail(h, "audio batch exceeds the 4 GiB buffer-addressing limit: split the batch");
+    h->stream = (hipStream_t)stream;
+    return run_mel(h, d_audio, B, L, out_scale, out_shift, d_mel);
 }
 
 int ev_hifigan(ev_handle* h, const float* d_mel, int B, int T, float* d_wav, void* stream) {

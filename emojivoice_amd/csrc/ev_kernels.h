@@ -6543,6 +6543,59 @@ __global__ void dn_crop_norm_kernel(const float* rows, const float* win2, float*
     out[idx] = env > 1e-11f ? v / env : v;
 }
 
+// ---------------------------------------------------------------------------
+// Analysis side: mel_spectrogram of utils/audio.py:45-82 (n_fft = win 1024, hop 256, center=False).  The STFT is the denoiser's
+// forward basis convolution over the signal reflect-padded by 384 samples a side; mel_project_kernel does everything after it.
+// ---------------------------------------------------------------------------
+// (B, L) audio -> rows of 256 samples of the signal reflect-padded by `pad` a side (pad < L; L + 2 * pad a multiple of 256)
+__global__ void mel_pad_reflect_kernel(const float* audio, float* rows, int B, int L, int pad, int S, int P) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int Lp = L + 2 * pad;
+    if (idx >= (size_t)B * Lp) return;
+    const int b = (int)(idx / Lp), m = (int)(idx % Lp);
+    int i = m - pad;
+    if (i < 0) i = -i;
+    else if (i >= L) i = 2 * (L - 1) - i;
+    rows[((size_t)b * S + P) * 256 + m] = audio[(size_t)b * L + i];
+}
+
+// [re(516) | im(516)] rows -> (B, n_mels, T): log(max(sum_k w[m][k] * sqrt(re_k^2 + im_k^2 + 1e-9), 1e-5)) * scale + shift.
+// One workgroup per 32 frames of one utterance.  The magnitudes of the tile go through LDS once ([frame][bin], row stride LD odd:
+// the 32 frames of a half-wave hit 32 banks for any bin), only the bins below `nb` that some filter reads (372 of 513 at fmax 8 kHz:
+// a quarter of the spectrum is never fetched).  Then lane = frame, and the eight half-waves walk the filters: filter m is the span
+// span[m] = {first bin, count, offset into wts} of the packed weights (ev_load_mel_basis), summed in bin order in fp32.  The stores
+// are 32 consecutive frames of one mel row.  HBM-bound on the read of the spectrum (2 * nb * 4 B per frame in, n_mels * 4 B out).
+// dynamic LDS: 32 * LD floats, LD = nb | 1.
+__global__ __launch_bounds__(256) void mel_project_kernel(const float* __restrict__ spec, const int* __restrict__ span, const float* __restrict__ wts,
+                                                          float* __restrict__ mel, int n_mels, int nb, int T, int S, int P, float scale, float shift) {
+    extern __shared__ __attribute__((aligned(16))) float mel_sm[];
+    const int LD = nb | 1;
+    const int tid = threadIdx.x;
+    const int b = blockIdx.y, t0 = blockIdx.x * 32;
+    const float* rows = spec + ((size_t)b * S + P + t0) * 1032;
+    for (int i = tid; i < 32 * nb; i += 256) {
+        const int f = i / nb, k = i - f * nb;
+        float mag = 0.f;
+        if (t0 + f < T) {
+            const float re = rows[(size_t)f * 1032 + k], im = rows[(size_t)f * 1032 + 516 + k];
+            mag = sqrtf((re * re + im * im) + 1e-9f);
+        }
+        mel_sm[f * LD + k] = mag;
+    }
+    __syncthreads();
+    const int f = tid & 31;
+    if (t0 + f >= T) return;
+    const float* mrow = mel_sm + f * LD;
+    for (int m = tid >> 5; m < n_mels; m += 8) {
+        const int first = span[3 * m], cnt = span[3 * m + 1];
+        const float* w = wts + span[3 * m + 2];
+        float acc = 0.f;
+        for (int j = 0; j < cnt; ++j) acc = fmaf(w[j], mrow[first + j], acc);
+        acc = acc < 1e-5f ? 1e-5f : acc;                       // torch.clamp(min=1e-5): a NaN stays a NaN
+        mel[((size_t)b * n_mels + m) * T + t0 + f] = (float)log((double)acc) * scale + shift;   // correctly rounded (logf is ~2 ulp; n_mels logs per frame cost nothing)
+    }
+}
+
 // conv_post (hifigan/models.py:195-196: Conv1d(C, 1, K, padding = K/2) + tanh) straight into the (B, T) waveform.  One
 // output channel makes this a sliding dot product, not a GEMM: a 32-row MFMA tile would waste 31/32 of the matrix
 // pipe and the launch was latency-bound at ~0.65 TB/s.  Here a workgroup stages 256 + K - 1 frames x C channels in LDS

@@ -20,6 +20,9 @@
  *   ev_load_text_encoder <- same checkpoint, state_dict["encoder.*"] + the derived "rope_theta" table
  *   ev_load_vocoder   <- Generator.load_state_dict(ckpt["generator"]) + remove_weight_norm()   cli.py:84-90
  *   ev_load_vocoder_cfg <- the same for the Generator(h) of any HiFi-GAN config inside the supported envelope (V1, V2, V3 ...)
+ *   ev_mel_spectrogram <- mel_spectrogram(y, 1024, num_mels, sr, 256, 1024, fmin, fmax, center=False)   utils/audio.py:45-82
+ *                       (the same function again in hifigan/meldataset.py:52), optionally with normalize() of utils/model.py fused
+ *   ev_load_mel_basis  <- the librosa mel filter bank that function caches per (fmax, device)
  *
  * Conventions
  *   - All tensors are fp32.  Pointers named d_* are DEVICE pointers owned by the
@@ -57,7 +60,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -127,8 +130,8 @@ int ev_cfm_decode2(ev_handle *h, const float *d_mu, const int32_t *d_lengths, co
                    int B, int Tp, int n_steps, float *d_dec, float mel_std, float mel_mean, float *d_mel, void *stream);
 
 /* Pre-size everything the hot calls allocate on demand, for batches of B utterances of up to Tx_max tokens (ev_text_encoder),
- * Tp_max mel frames (ev_cfm_decode / ev_estimator; multiple of 4) and T_voc_max mel frames (ev_hifigan, ev_denoise at
- * L = 256 * T_voc_max): the workspace arena, the text-encoder and denoiser scratch, the pinned time-embedding ring, the
+ * Tp_max mel frames (ev_cfm_decode / ev_estimator; multiple of 4) and T_voc_max mel frames (ev_hifigan, ev_denoise and
+ * ev_mel_spectrogram at L = 256 * T_voc_max): the workspace arena, the text-encoder and denoiser scratch, the pinned time-embedding ring, the
  * denoiser's DFT bases and the side streams of the small-call vocoder.  0 skips a stage.  After it, calls with the same B and
  * lengths up to the reserved ones never allocate (ev_alloc_count does not move) and never wait for the device to re-plan.
  * The reference has no counterpart: torch's caching allocator amortises the same cost (feel_me.py:181-203). */
@@ -182,6 +185,24 @@ int ev_hifigan(ev_handle *h, const float *d_mel, int B, int T, float *d_wav, voi
  * the reference relies on, inputs of 512 samples or fewer are an error. */
 int ev_stft_magnitude(ev_handle *h, const float *d_audio, int B, int L, float *d_mag, void *stream);
 int ev_denoise(ev_handle *h, const float *d_audio, int B, int L, const float *d_bias_spec, float strength, float *d_out, void *stream);
+
+/* The analysis side: the reference's mel_spectrogram (utils/audio.py:45-82) at n_fft = win_size = 1024, hop_size 256, center=False.
+ * The signal is reflect-padded by (1024 - 256) / 2 = 384 samples a side, the STFT is the denoiser's forward DFT-basis convolution
+ * (periodic Hann window, exact fp32 MFMA in every arithmetic setting), and one kernel (mel_project_kernel) turns the
+ * [re | im] rows into the finished mel: sqrt(re^2 + im^2 + 1e-9), the filter bank, log(clamp(., 1e-5)), scale and shift.
+ *   ev_load_mel_basis: the filter bank, HOST (n_mels, n_freq) row-major; n_freq must be 513, 1 <= n_mels <= 128.  The handle keeps,
+ *     per filter, [first bin, count] and the weights of that span only (a Slaney triangle covers at most ~60 of the 513 bins at
+ *     80 mels).  A row whose non-zero weights are NOT one contiguous run is kept as the single span from its first to its last
+ *     non-zero bin, the zeros in between included (in the worst case the whole row: the dense product), so any basis gives the
+ *     result of the dense matrix product.  Loading again replaces the bank (it waits for the device first).
+ *   ev_mel_spectrogram: d_audio (B, L) -> d_mel (B, n_mels, L / 256):
+ *       log(clamp(basis @ sqrt(re^2 + im^2 + 1e-9), 1e-5)) * out_scale + out_shift
+ *     out_scale = 1 / mel_std, out_shift = -mel_mean / mel_std fuse normalize() (utils/model.py); 1, 0 is the reference function.
+ *     L must be a positive multiple of 256 and > 384 (torch's reflect padding of 384 needs more samples than that); L / 256 frames
+ *     come out, the reference's frame count for such L.  Scratch is the denoiser's: ev_reserve(.., T_voc_max) covers a call at
+ *     L = 256 * T_voc_max.  Needs no estimator or vocoder weights; without a loaded basis the call fails with a message. */
+int ev_load_mel_basis(ev_handle *h, const float *basis, int n_mels, int n_freq);
+int ev_mel_spectrogram(ev_handle *h, const float *d_audio, int B, int L, float out_scale, float out_shift, float *d_mel, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

@@ -25,6 +25,7 @@ EXPORTS = [
     "ev_op_conv1d", "ev_op_groupnorm_mish", "ev_op_layernorm", "ev_op_split_pieces", "ev_op_attention", "ev_op_ln_mlp", "ev_set_mrf_streams_max",
     "ev_cfm_decode2", "ev_reserve", "ev_alloc_count", "ev_dbg_sk_stats", "ev_op_attn_out", "ev_dbg_set_amax", "ev_dbg_set_attn_h16", "ev_dbg_set_chain", "ev_dbg_sk_taken",
     "ev_load_mel_basis", "ev_mel_spectrogram",
+    "ev_maximum_path", "ev_log_prior", "ev_mas_align",
 ]
 
 
@@ -134,6 +135,9 @@ def load_library() -> C.CDLL:
     lib.ev_denoise.argtypes = [vp, vp, i32, i32, vp, f32, vp, vp]
     lib.ev_load_mel_basis.argtypes = [vp, vp, i32, i32]
     lib.ev_mel_spectrogram.argtypes = [vp, vp, i32, i32, f32, f32, vp, vp]
+    lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.ev_profile_enable.argtypes = [vp, i32]
     lib.ev_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), i32]
     lib.ev_profile_read_split.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -293,6 +297,48 @@ class Engine:
         self._check(self.lib.ev_mel_spectrogram(self.h, audio.data_ptr(), B, L, float(out_scale), float(out_shift), mel.data_ptr(), _stream_ptr()),
                     "ev_mel_spectrogram")
         return mel
+
+    def maximum_path(self, value, x_lengths, y_lengths, want_path: bool = True, want_dur: bool = True):
+        """monotonic_align.maximum_path on (B, Tx, Ty) fp32 scores with per-row lengths (ev_maximum_path): (path (B, Tx, Ty) 0/1 or None,
+        durations (B, Tx) int32 or None), bit-equal to the reference's loop.  ``value`` is not modified."""
+        value = self._f32(value)
+        B, Tx, Ty = value.shape
+        xl = x_lengths.to(value.device, torch.int32).contiguous()
+        yl = y_lengths.to(value.device, torch.int32).contiguous()
+        path = torch.empty((B, Tx, Ty), dtype=torch.float32, device=value.device) if want_path else None
+        dur = torch.empty((B, Tx), dtype=torch.int32, device=value.device) if want_dur else None
+        self._check(self.lib.ev_maximum_path(self.h, value.data_ptr(), xl.data_ptr(), yl.data_ptr(), B, Tx, Ty,
+                                             path.data_ptr() if want_path else None, dur.data_ptr() if want_dur else None, _stream_ptr()), "ev_maximum_path")
+        return path, dur
+
+    def log_prior(self, mu_x, y):
+        """log N(y_j; mu_i, I) for every (token, frame) pair (matcha_tts.py:186-193, ev_log_prior): (B, Tx, Ty), unmasked."""
+        mu_x, y = self._f32(mu_x), self._f32(y)
+        B, F, Tx = mu_x.shape
+        Ty = y.shape[2]
+        assert y.shape[:2] == (B, F)
+        logp = torch.empty((B, Tx, Ty), dtype=torch.float32, device=mu_x.device)
+        self._check(self.lib.ev_log_prior(self.h, mu_x.data_ptr(), y.data_ptr(), B, Tx, Ty, logp.data_ptr(), _stream_ptr()), "ev_log_prior")
+        return logp
+
+    def mas_align(self, mu_x, y, x_lengths, y_lengths, want_attn: bool = True, want_dur: bool = True, want_mu_y: bool = True, want_logp: bool = False):
+        """Scores + search + expansion in one call (ev_mas_align): {"attn" (B, Tx, Ty), "dur" (B, Tx) int32, "mu_y" (B, 80, Ty),
+        "logp" (B, Tx, Ty)}, None for what was not asked for."""
+        mu_x, y = self._f32(mu_x), self._f32(y)
+        B, F, Tx = mu_x.shape
+        Ty = y.shape[2]
+        assert y.shape[:2] == (B, F)
+        dev = mu_x.device
+        xl = x_lengths.to(dev, torch.int32).contiguous()
+        yl = y_lengths.to(dev, torch.int32).contiguous()
+        attn = torch.empty((B, Tx, Ty), dtype=torch.float32, device=dev) if want_attn else None
+        dur = torch.empty((B, Tx), dtype=torch.int32, device=dev) if want_dur else None
+        mu_y = torch.empty((B, F, Ty), dtype=torch.float32, device=dev) if want_mu_y else None
+        logp = torch.empty((B, Tx, Ty), dtype=torch.float32, device=dev) if want_logp else None
+        dp = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        self._check(self.lib.ev_mas_align(self.h, mu_x.data_ptr(), y.data_ptr(), xl.data_ptr(), yl.data_ptr(), B, Tx, Ty,
+                                          dp(attn), dp(dur), dp(mu_y), dp(logp), _stream_ptr()), "ev_mas_align")
+        return {"attn": attn, "dur": dur, "mu_y": mu_y, "logp": logp}
 
     def load_text_encoder(self, tensors: Dict[str, torch.Tensor]):
         self._load(self.lib.ev_load_text_encoder, tensors, "ev_load_text_encoder")

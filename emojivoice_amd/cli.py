@@ -8,6 +8,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --checkpoint_path model.ckpt --vocoder_path g_02500000 --ids "0 23 0 51 0" --spk 12
     python -m emojivoice_amd.cli --synthetic --emoji-text "Hello world 🙂" --ids "0 23 0 51 0"
     python -m emojivoice_amd.cli --mel_from_wav voice.wav [--vocoder_path g_02500000 | --synthetic]     # analysis: voice.wav.mel.npy (+ copy synthesis)
+    python -m emojivoice_amd.cli --checkpoint_path model.ckpt --align_wav voice.wav --phonemes "həlˈoʊ" --spk 12   # voice.wav.durations.npy
 """
 from __future__ import annotations
 
@@ -38,6 +39,11 @@ def write_wav_pcm24(path, wav: np.ndarray, sr: int = 22050):
 
 def validate_args(args):
     if args.mel_from_wav:
+        return args
+    if args.align_mel or args.align_wav:
+        assert not (args.align_mel and args.align_wav), "--align_mel and --align_wav exclude each other"
+        assert args.ids or args.phonemes, "--align_mel / --align_wav need the text of that one utterance: --ids or --phonemes"
+        assert args.synthetic or args.checkpoint_path, "--checkpoint_path is required (or --synthetic)"
         return args
     assert args.ids or args.file or args.phonemes, "One of --ids, --phonemes or --file must be provided"
     assert args.temperature >= 0, "Sampling temperature cannot be negative"
@@ -151,6 +157,35 @@ def mel_from_wav(args, device):
 
 
 @torch.inference_mode()
+def align_durations(args, device):
+    """--align_mel MEL.npy (a normalised (80, frames) mel) / --align_wav VOICE.wav (analysed as --mel_from_wav does, normalize() fused)
+    with the text of that utterance -> <input>.durations.npy: the Tx integer durations of MatchaTTS.align, what
+    utils/get_durations_from_trained_model.py saves per file."""
+    from . import weights as W
+    from .audio import mel_spectrogram, read_wav_pcm
+    from .matcha_tts import MatchaTTS
+
+    model = MatchaTTS(W.synthetic_matcha_state(), device=device) if args.synthetic else MatchaTTS.load_from_checkpoint(args.checkpoint_path, map_location=device)
+    src = args.align_mel or args.align_wav
+    if args.align_mel:
+        mel = torch.from_numpy(np.load(src).astype(np.float32)).to(device).reshape(1, model.n_feats, -1)
+    else:
+        y = read_wav_pcm(src, 22050)
+        n = len(y) // 256 * 256
+        if n <= 384:
+            sys.exit(f"[-] {src}: {len(y)} samples, at least 512 are needed")
+        mel = mel_spectrogram(torch.from_numpy(y[:n].copy()).to(device).unsqueeze(0), 1024, model.n_feats, 22050, 256, 1024, 0, 8000,
+                              out_scale=1.0 / model.mel_std, out_shift=-model.mel_mean / model.mel_std)
+    ids, spk = parse_lines(args)[0]
+    x = torch.tensor([ids], dtype=torch.long, device=device)
+    spks = torch.tensor([spk if spk is not None else (args.spk or 0)], dtype=torch.long, device=device)
+    out = model.align(x, torch.tensor([len(ids)], device=device), mel, torch.tensor([mel.shape[-1]], device=device), spks)
+    dur = out["durations"][0].cpu().numpy()
+    np.save(f"{src}.durations.npy", dur)
+    print(f"[+] Durations saved: {Path(f'{src}.durations.npy').resolve()}  ({len(dur)} tokens over {mel.shape[-1]} frames)")
+
+
+@torch.inference_mode()
 def cli(argv=None):
     p = argparse.ArgumentParser(description="Matcha-TTS / EmojiVoice synthesis on MI355X")
     p.add_argument("--checkpoint_path", type=str, default=None)
@@ -175,7 +210,14 @@ def cli(argv=None):
     p.add_argument("--batch_size", type=int, default=32)
     p.add_argument("--mel_from_wav", type=str, default=None, help="analysis instead of synthesis: a 22.05 kHz mono PCM wav (16 / 24 bit) -> PATH.mel.npy; "
                    "with --vocoder_path or --synthetic also PATH.copysyn.wav (copy synthesis)")
+    p.add_argument("--align_mel", type=str, default=None, help="alignment instead of synthesis: a normalised mel (80, frames) .npy of the utterance "
+                   "given by --ids / --phonemes -> PATH.durations.npy (monotonic alignment search, Tx integers)")
+    p.add_argument("--align_wav", type=str, default=None, help="the same from a 22.05 kHz mono PCM wav, analysed as --mel_from_wav does and normalised")
     args = validate_args(p.parse_args(argv))
+    if args.align_mel or args.align_wav:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return align_durations(args, torch.device("cuda", 0))
     if args.mel_from_wav:
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")

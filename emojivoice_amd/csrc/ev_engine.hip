@@ -134,7 +134,7 @@ struct ev_handle {
     MelBasisW melb;
     // small per-stage scratch arenas (denoiser, text encoder): grown on demand, ordered against their last user's stream
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
-    Scratch dn_ws, enc_ws;
+    Scratch dn_ws, enc_ws, mas_ws;   // (mas_ws: the alignment search's frame -> token index and, for large Tx * Ty, its decision bits)
     float* zeros = nullptr;     // 4096 zero floats (stand-in bias for the fused kernels' unconditional loads)
     int max_steps = 64;         // Euler steps the time-grid buffers of the workspace are planned for (grows on demand)
     int* bad_ids_host = nullptr; int* bad_ids_dev = nullptr;   // mapped host word: count of out-of-range token ids seen by ev_text_encoder
@@ -1849,6 +1849,53 @@ int run_mel(ev_handle* h, const float* d_audio, int B, int L, float out_scale, f
     return 0;
 }
 
+// Monotonic alignment search (ev_maximum_path, ev_mas_align): mas_search_kernel, one workgroup per utterance, then mas_fill_kernel for the
+// outputs that are (B, ., Ty) wide.  LDS plan in floats: [y tile C x W (fused)] [two columns 2 x TxP] [score tile W x TxP] [decision bits
+// Ty x ceil(Tx / 64) 64-bit words, where they still fit into the CU's 160 KiB: else in the handle's scratch].  W = 16 frames per tile up to
+// Tx ~ 2200 tokens, 4 above (the tile and the two columns must fit: Tx <= 4096).
+int run_mas(ev_handle* h, bool fused, const float* d_value, const float* d_mu_x, const float* d_y, const int32_t* d_xlen, const int32_t* d_ylen,
+            int B, int Tx, int Ty, float* d_attn, int32_t* d_dur, float* d_mu_y, float* d_logp) {
+    constexpr size_t LDS_MAX = 160 * 1024;
+    const int C = h->dims.n_feats;
+    if (B <= 0 || B > 65535 || Tx <= 0 || Ty <= 0 || Tx > 4096 || !d_xlen || !d_ylen || (fused ? (!d_mu_x || !d_y || C <= 0) : !d_value))
+        return fail(h, "bad arguments B=%d Tx=%d Ty=%d (1 <= B <= 65535, 1 <= Tx <= 4096, 1 <= Ty)", B, Tx, Ty);
+    MasParams p{};
+    p.value = d_value; p.mu_x = d_mu_x; p.y = d_y; p.xlen = d_xlen; p.ylen = d_ylen; p.logp = fused ? d_logp : nullptr; p.dur = d_dur;
+    p.C = C; p.Tx = Tx; p.Ty = Ty; p.TxP = round_up(Tx, 2) + 1; p.nxw = (Tx + 63) / 64;
+    p.cst = (float)(-0.5 * log(2.0 * 3.14159265358979323846) * C);
+    int W = 16;
+    auto plan = [&](int w) {
+        p.off_col = fused ? round_up(C * w, 4) : 0;
+        p.off_tile = p.off_col + round_up(2 * p.TxP, 4);
+        p.off_bits = p.off_tile + round_up(w * p.TxP, 4);
+        return (size_t)p.off_bits * sizeof(float);
+    };
+    if (plan(16) > LDS_MAX) W = 4;
+    size_t smem = plan(W);
+    if (smem > LDS_MAX) return fail(h, "alignment search: Tx=%d does not fit the LDS plan", Tx);
+    const size_t bit_bytes = (size_t)Ty * p.nxw * sizeof(unsigned long long);
+    const bool bits_in_lds = smem + bit_bytes <= LDS_MAX;
+    if (bits_in_lds) smem += bit_bytes;
+    const size_t idx_bytes = ((size_t)B * Ty * sizeof(int32_t) + 255) / 256 * 256;
+    if (scratch_acquire(h, h->mas_ws, idx_bytes + (bits_in_lds ? 0 : (size_t)B * bit_bytes))) return 1;
+    p.idx = (int32_t*)h->mas_ws.p;
+    p.gbits = bits_in_lds ? nullptr : (unsigned long long*)(h->mas_ws.p + idx_bytes);
+    const int NT = std::min(1024, std::max(256, round_up(Tx, 64)));
+    hipStream_t st = h->stream;
+    auto go = [&](auto kernel_tag) {
+        constexpr int w = decltype(kernel_tag)::value;
+        if (fused) launch<mas_search_kernel<w, true>>(h->device, dim3(B), dim3(NT), smem, st, p);
+        else launch<mas_search_kernel<w, false>>(h->device, dim3(B), dim3(NT), smem, st, p);
+    };
+    dispatch<16, 4>(W, go);
+    HIPCHK(h, hipGetLastError());
+    if (d_attn || d_mu_y) {
+        hipLaunchKernelGGL(mas_fill_kernel, dim3((Ty + 255) / 256, B, d_attn ? (Tx + 63) / 64 : 1), dim3(256), 0, st, (const int32_t*)p.idx, d_mu_x, d_attn, d_mu_y, C, Tx, Ty);
+        HIPCHK(h, hipGetLastError());
+    }
+    return 0;
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1914,6 +1961,7 @@ void ev_destroy(ev_handle* h) {
     if (h->sk_part) hipFree(h->sk_part);
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
     if (h->enc_ws.p) hipFree(h->enc_ws.p);
+    if (h->mas_ws.p) hipFree(h->mas_ws.p);
     if (h->dn_ws.p) hipFree(h->dn_ws.p);
     if (h->bad_ids_host) hipHostFree(h->bad_ids_host);
     for (int i = 0; i < 2; ++i) { if (h->temb_ev[i]) hipEventDestroy(h->temb_ev[i]); if (h->temb_host[i]) hipHostFree(h->temb_host[i]); }
@@ -2505,6 +2553,34 @@ int ev_align(ev_handle* h, const float* d_wceil, const float* d_mu_x, const int3
                        h->dims.n_feats, Tx, Tp);
     HIPCHK(h, hipGetLastError());
     return 0;
+}
+
+int ev_maximum_path(ev_handle* h, const float* d_value, const int32_t* d_xlen, const int32_t* d_ylen, int B, int Tx, int Ty,
+                    float* d_path, int32_t* d_dur, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    h->stream = (hipStream_t)stream;
+    return run_mas(h, false, d_value, nullptr, nullptr, d_xlen, d_ylen, B, Tx, Ty, d_path, d_dur, nullptr, nullptr);
+}
+
+int ev_log_prior(ev_handle* h, const float* d_mu_x, const float* d_y, int B, int Tx, int Ty, float* d_logp, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int C = h->dims.n_feats;
+    if (B <= 0 || B > 65535 || Tx <= 0 || Ty <= 0 || C <= 0 || C > 256 || !d_mu_x || !d_y || !d_logp) return fail(h, "bad arguments B=%d Tx=%d Ty=%d", B, Tx, Ty);
+    if ((Tx + 31) / 32 > 65535) return fail(h, "ev_log_prior: Tx=%d exceeds the grid", Tx);
+    const float cst = (float)(-0.5 * log(2.0 * 3.14159265358979323846) * C);
+    hipLaunchKernelGGL(mas_logp_kernel, dim3((Ty + 63) / 64, (Tx + 31) / 32, B), dim3(256), (size_t)C * 32 * sizeof(float), (hipStream_t)stream, d_mu_x, d_y, d_logp, C, Tx, Ty, cst);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int ev_mas_align(ev_handle* h, const float* d_mu_x, const float* d_y, const int32_t* d_xlen, const int32_t* d_ylen, int B, int Tx, int Ty,
+                 float* d_attn, int32_t* d_dur, float* d_mu_y, float* d_logp, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    h->stream = (hipStream_t)stream;
+    return run_mas(h, true, nullptr, d_mu_x, d_y, d_xlen, d_ylen, B, Tx, Ty, d_attn, d_dur, d_mu_y, d_logp);
 }
 
 int ev_stft_magnitude(ev_handle* h, const float* d_audio, int B, int L, float* d_mag, void* stream) {

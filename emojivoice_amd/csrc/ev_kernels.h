@@ -6637,3 +6637,167 @@ __global__ void strip_pad_kernel(const float* src, float* dst, int T, int S, int
     size_t b = idx / T, t = idx % T;
     dst[idx] = src[b * S + P + t];
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Monotonic alignment search (monotonic_align/core.pyx maximum_path_each) and the scores it runs on (matcha_tts.py:186-199).
+//
+// mas_cell_logp: log N(y_j; mu_i, I) of one (token, frame) cell in the direct form -0.5 sum_c (y - mu)^2 - 0.5 C log(2 pi): one fmaf
+// chain over the channels in index order, in ev_log_prior and in the fused search alike (the same bits from both).  Plain fp32 VALU in
+// every arithmetic setting: the scores feed a hard decision.
+//
+// mas_search_kernel: one workgroup per utterance walks the frames.  W frames at a time the scores of every token row are formed
+// (FUSED: from mu_x and an LDS copy of y[:, j0 .. j0 + W); otherwise copied from the caller's matrix) into an LDS tile [W][TxP];
+// then W dependent DP steps, one barrier each: lane x reads the previous column at x and x - 1 from LDS, writes the new column
+// (two column buffers) and contributes ONE decision bit — the backtrack's predicate `x == y or value[x, y-1] < value[x-1, y-1]`,
+// which is `v_cur < v_prev` of the forward step — to a wave ballot; lane 0 of the wave stores the 64-bit word.  Rows are owned
+// x = wave * 64 + lane (+ blockDim per pass), so a ballot is one word of a column.  The bits live in LDS where Ty * ceil(Tx / 64)
+// words fit beside the tile, else in a scratch of the handle.  Only cells inside the band max(0, tx + y - ty) <= x < min(tx, y + 1)
+// are ever read, so only those are computed.  Thread 0 then walks the bits backwards: token per frame (idx, -1 beyond ty) and the
+// durations as run lengths.  The (B, Tx, Ty) value matrix never exists in memory.  max and one add per cell in fp32: bit-equal to the
+// host loop for finite scores, ties (strict <) included.
+// A row with tx < 1, tx > ty, tx > Tx or ty > Ty is searched as an empty one: idx = -1 everywhere, zero durations.
+// mas_fill_kernel: attn[b, i, j] = (i == idx[b, j]) and mu_y[b, :, j] = mu_x[b, :, idx[b, j]] (0 where idx < 0), coalesced over j.
+// ---------------------------------------------------------------------------------------------------------------------------
+#define EV_MAS_NEG (-1e9f)
+
+struct MasParams {
+    const float* value;                 // (B, Tx, Ty) scores (not FUSED)
+    const float* mu_x; const float* y;  // (B, C, Tx), (B, C, Ty) (FUSED)
+    const int32_t* xlen; const int32_t* ylen;
+    float* logp;                        // FUSED: (B, Tx, Ty) or NULL — the scores the DP consumed, every cell
+    int32_t* idx;                       // (B, Ty) token of each frame, -1 beyond ylen
+    int32_t* dur;                       // (B, Tx) or NULL
+    unsigned long long* gbits;          // decision bits per utterance [Ty][nxw], or NULL: they fit in LDS
+    int C, Tx, Ty, TxP, nxw;
+    int off_col, off_tile, off_bits;    // LDS plan in floats (the y tile is at 0)
+    float cst;                          // -0.5 C log(2 pi)
+};
+
+__device__ __forceinline__ float mas_cell_finish(float ss, float cst) { return fmaf(-0.5f, ss, cst); }
+
+template <int W, bool FUSED>
+__global__ __launch_bounds__(1024) void mas_search_kernel(const MasParams p) {
+    extern __shared__ __attribute__((aligned(16))) float mas_lds[];
+    float* ytile = mas_lds;                           // [C][W] (FUSED)
+    float* col = mas_lds + p.off_col;                 // [2][TxP]
+    float* tile = mas_lds + p.off_tile;               // [W][TxP]
+    const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wv = tid >> 6;
+    const int C = p.C, Tx = p.Tx, Ty = p.Ty, TxP = p.TxP, nxw = p.nxw;
+    unsigned long long* bits = p.gbits ? p.gbits + (size_t)b * Ty * nxw : (unsigned long long*)(mas_lds + p.off_bits);
+    int tx = p.xlen[b], ty = p.ylen[b];
+    if (tx < 1 || tx > ty || tx > Tx || ty > Ty) { tx = 0; ty = 0; }
+    int32_t* idx = p.idx + (size_t)b * Ty;
+    int32_t* dur = p.dur ? p.dur + (size_t)b * Tx : nullptr;
+    for (int j = ty + tid; j < Ty; j += NT) idx[j] = -1;
+    if (dur) for (int i = tx + tid; i < Tx; i += NT) dur[i] = 0;
+    const int ncols = (FUSED && p.logp) ? Ty : ty;
+    float* cur = col;
+    float* prev = col + TxP;
+    for (int y0 = 0; y0 < ncols; y0 += W) {
+        if constexpr (FUSED) {
+            for (int i = tid; i < C * W; i += NT) {
+                const int c = i / W, j = y0 + i % W;
+                ytile[i] = j < Ty ? p.y[((size_t)b * C + c) * Ty + j] : 0.f;
+            }
+            __syncthreads();
+            for (int x = tid; x < Tx; x += NT) {
+                float acc[W];
+#pragma unroll
+                for (int jj = 0; jj < W; ++jj) acc[jj] = 0.f;
+                const float* mu = p.mu_x + (size_t)b * C * Tx + x;
+                for (int c = 0; c < C; ++c) {
+                    const float m = mu[(size_t)c * Tx];
+#pragma unroll
+                    for (int jj = 0; jj < W; ++jj) { const float d = ytile[c * W + jj] - m; acc[jj] = fmaf(d, d, acc[jj]); }
+                }
+#pragma unroll
+                for (int jj = 0; jj < W; ++jj) tile[jj * TxP + x] = mas_cell_finish(acc[jj], p.cst);
+            }
+            __syncthreads();
+            if (p.logp)
+                for (int i = tid; i < Tx * W; i += NT) {
+                    const int x = i / W, jj = i % W, j = y0 + jj;
+                    if (j < Ty) p.logp[((size_t)b * Tx + x) * Ty + j] = tile[jj * TxP + x];
+                }
+        } else {
+            for (int i = tid; i < tx * W; i += NT) {
+                const int x = i / W, jj = i % W, j = y0 + jj;
+                tile[jj * TxP + x] = j < ty ? p.value[((size_t)b * Tx + x) * Ty + j] : 0.f;
+            }
+            __syncthreads();
+        }
+        const int jend = min(W, ty - y0);
+        for (int jj = 0; jj < jend; ++jj) {
+            const int yy = y0 + jj;
+            const int lo = max(0, tx + yy - ty), hi = min(tx, yy + 1);
+            for (int x0 = wv * 64; x0 < hi; x0 += NT) {           // wave-uniform
+                if (x0 + 64 <= lo) continue;
+                const int x = x0 + lane;
+                bool bit = false;
+                if (x >= lo && x < hi) {
+                    const float vc = (x == yy) ? EV_MAS_NEG : prev[x];
+                    const float vp = (x == 0) ? (yy == 0 ? 0.f : EV_MAS_NEG) : prev[x - 1];
+                    cur[x] = fmaxf(vc, vp) + tile[jj * TxP + x];
+                    bit = x != 0 && (x == yy || vc < vp);
+                }
+                const unsigned long long m = __ballot(bit);
+                if (lane == 0) bits[(size_t)yy * nxw + (x0 >> 6)] = m;
+            }
+            __syncthreads();
+            float* t = cur; cur = prev; prev = t;
+        }
+    }
+    __syncthreads();
+    if (tid == 0 && ty > 0) {
+        int index = tx - 1, end = ty - 1;
+        for (int yy = ty - 1; yy >= 0; --yy) {
+            idx[yy] = index;
+            if (index != 0 && ((bits[(size_t)yy * nxw + (index >> 6)] >> (index & 63)) & 1ull)) {
+                if (dur) dur[index] = end - yy + 1;
+                end = yy - 1;
+                --index;
+            }
+        }
+        if (dur) dur[index] = end + 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void mas_fill_kernel(const int32_t* __restrict__ idx, const float* __restrict__ mu_x, float* __restrict__ attn,
+                                                       float* __restrict__ mu_y, int C, int Tx, int Ty) {
+    const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, i0 = blockIdx.z * 64;
+    if (j >= Ty) return;
+    const int src = idx[(size_t)b * Ty + j];
+    if (attn) {
+        const int i1 = min(Tx, i0 + 64);
+        for (int i = i0; i < i1; ++i) attn[((size_t)b * Tx + i) * Ty + j] = (i == src) ? 1.f : 0.f;
+    }
+    if (mu_y && blockIdx.z == 0)
+        for (int c = 0; c < C; ++c) mu_y[((size_t)b * C + c) * Ty + j] = src >= 0 ? mu_x[((size_t)b * C + c) * Tx + src] : 0.f;
+}
+
+// ev_log_prior: every cell of (B, Tx, Ty), a 32-token x 64-frame tile per workgroup: mu_x[:, 32 tokens] in LDS (broadcast reads), one frame
+// per lane, eight token rows per thread.
+__global__ __launch_bounds__(256) void mas_logp_kernel(const float* __restrict__ mu_x, const float* __restrict__ y, float* __restrict__ logp,
+                                                       int C, int Tx, int Ty, float cst) {
+    extern __shared__ __attribute__((aligned(16))) float mas_mu[];     // [C][32]
+    const int tid = threadIdx.x, b = blockIdx.z, x0 = blockIdx.y * 32, j = blockIdx.x * 64 + (tid & 63), xg = (tid >> 6) * 8;
+    for (int i = tid; i < C * 32; i += 256) {
+        const int c = i >> 5, x = x0 + (i & 31);
+        mas_mu[i] = x < Tx ? mu_x[((size_t)b * C + c) * Tx + x] : 0.f;
+    }
+    __syncthreads();
+    if (j >= Ty) return;
+    float acc[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[r] = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float yv = y[((size_t)b * C + c) * Ty + j];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) { const float d = yv - mas_mu[c * 32 + xg + r]; acc[r] = fmaf(d, d, acc[r]); }
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int x = x0 + xg + r;
+        if (x < Tx) logp[((size_t)b * Tx + x) * Ty + j] = mas_cell_finish(acc[r], cst);
+    }
+}

@@ -11,11 +11,17 @@ encoder + duration predictor (``ev_text_encoder``), the monotonic alignment
 run in the HIP library through the C ABI; only the duration rounding and the
 integer ``y_lengths`` stay torch ops (data-dependent sizes, matcha_tts.py:121-128).
 ``encoder_stage = "host"`` selects the plain-torch text encoder + alignment instead
-(north_star's "run once on host").  Training (``forward``) is out of scope and raises.
+(north_star's "run once on host").
+
+``forward`` (matcha_tts.py:154-246) is the no-grad pass over (text, mel) pairs that the reference's validation step and
+``utils/get_durations_from_trained_model.py`` make: log-likelihood scores, monotonic alignment search and ``mu_y`` in one
+library call (``ev_mas_align``), the three losses from there.  ``align`` is the durations script without the losses.
+Training with gradients is out of scope.
 """
 from __future__ import annotations
 
 import datetime as dt
+import math
 import pickle
 from collections import OrderedDict
 from typing import Dict, Optional
@@ -25,7 +31,7 @@ import torch.nn.functional as F
 
 from . import weights as W
 from ._lib import Engine, EvLibraryError
-from .text_encoder import TextEncoder, fix_len_compatibility, generate_path, sequence_mask
+from .text_encoder import TextEncoder, duration_loss, fix_len_compatibility, generate_path, sequence_mask
 
 EST_PREFIX = "decoder.estimator."
 
@@ -71,6 +77,7 @@ class MatchaTTS:
         self.n_feats = int(sd["encoder.proj_m.weight"].shape[0])
         self.mel_mean = float(sd.get("mel_mean", torch.tensor(0.0)))
         self.mel_std = float(sd.get("mel_std", torch.tensor(1.0)))
+        self.sigma_min = 1e-4           # cfm_params.sigma_min (configs/model/cfm/default.yaml): not part of a state dict
         self._cpu_sd = sd
         self._enc_cfg = (n_heads_encoder, n_layers_encoder)
         self.encoder_stage = "device"   # "device": ev_text_encoder (HIP, through the C ABI); "host": the plain-torch TextEncoder
@@ -120,8 +127,73 @@ class MatchaTTS:
         sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
         return cls(sd, device=map_location if map_location is not None else "cuda:0")
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("training forward (matcha_tts.py:154-246) is out of scope of the inference hot path")
+    # ---- the no-grad pass over (text, mel) pairs -----------------------------------
+    def _encode_pairs(self, x, x_lengths, y, y_lengths, spks):
+        """Speaker embedding and text encoder for (text, mel) pairs, after the length check both public methods share: the
+        reference's search reads outside its rows for x_lengths > y_lengths or an empty row (one device read here)."""
+        dev = self.device
+        x, x_lengths, y_lengths = x.to(dev), x_lengths.to(dev).long(), y_lengths.to(dev).long()
+        y = y.to(dev, torch.float32).contiguous()
+        if y.dim() != 3 or y.shape[0] != x.shape[0] or y.shape[1] != self.n_feats:
+            raise ValueError(f"y must be (B, {self.n_feats}, Ty), got {tuple(y.shape)} for {x.shape[0]} texts")
+        xl, yl = torch.stack([x_lengths, y_lengths]).cpu()
+        if bool((xl < 1).any()) or bool((yl < 1).any()) or bool((xl > yl).any()) or int(xl.max()) > x.shape[1] or int(yl.max()) > y.shape[2]:
+            raise ValueError(f"every row needs 1 <= x_lengths <= y_lengths within the padded shapes (monotonic alignment search is undefined "
+                             f"otherwise): x_lengths {xl.tolist()}, y_lengths {yl.tolist()}, x {tuple(x.shape)}, y {tuple(y.shape)}")
+        spk = F.embedding(spks.to(dev).long(), self._sd["spk_emb.weight"]) if self.n_spks > 1 else None
+        mu_x, logw, x_mask = self.encode(x, x_lengths, spk)
+        if self.encoder_stage != "host":
+            self.engine.text_encoder_status()
+        return x_lengths, y, y_lengths, spk, mu_x, logw, x_mask
+
+    @torch.inference_mode()
+    def align(self, x, x_lengths, y, y_lengths, spks=None):
+        """What utils/get_durations_from_trained_model.py takes from ``forward``: the monotonic alignment of each text to its
+        (normalised) mel.  Returns {"attn" (B, Tx, Ty), "durations" (B, Tx) int64 = attn.sum(-1), "logw_" (B, 1, Tx), "mu_y" (B, 80, Ty)}."""
+        x_lengths, y, y_lengths, _, mu_x, _, x_mask = self._encode_pairs(x, x_lengths, y, y_lengths, spks)
+        r = self.engine.mas_align(mu_x, y, x_lengths, y_lengths)
+        logw_ = torch.log(1e-8 + r["dur"].to(mu_x.dtype)).unsqueeze(1) * x_mask
+        return {"attn": r["attn"], "durations": r["dur"].long(), "logw_": logw_, "mu_y": r["mu_y"]}
+
+    @torch.inference_mode()
+    def forward(self, x, x_lengths, y, y_lengths, spks=None, out_size=None, cond=None, durations=None, *, t=None, z=None):
+        """Reference matcha_tts.py:154-246 without gradients: (dur_loss, prior_loss, diff_loss, attn (B, Tx, Ty)).
+        ``durations`` (B, 1, Tx) or (B, Tx), as under the reference's ``use_precomputed_durations``, replace the search by
+        generate_path.  Extension: keyword-only ``t`` (B,) and ``z`` (B, 80, Ty) replace the draws of compute_loss
+        (flow_matching.py:105-110) for reproducible runs.  The estimator runs one row at a time (``ev_estimator`` takes one scalar
+        t per call): an evaluation pass, not the request path."""
+        if out_size is not None:
+            raise NotImplementedError("out_size (the random segment cut of matcha_tts.py:206-231, a training memory hack) is not supported: pass out_size=None")
+        x_lengths, y, y_lengths, spk, mu_x, logw, x_mask = self._encode_pairs(x, x_lengths, y, y_lengths, spks)
+        B, _, Ty = y.shape
+        y_mask = sequence_mask(y_lengths, Ty).unsqueeze(1).to(x_mask.dtype)
+        if durations is not None:
+            mu_y, attn = self.engine.align(durations.to(self.device).float(), mu_x, x_lengths, y_lengths, Ty)
+            attn = attn.squeeze(1)
+            tok = attn.sum(-1)
+        else:
+            r = self.engine.mas_align(mu_x, y, x_lengths, y_lengths)
+            mu_y, attn, tok = r["mu_y"], r["attn"], r["dur"].to(mu_x.dtype)
+        # the three reductions accumulate in float64 and round once to the reference's float32 (a few thousand elements each)
+        logw_ = torch.log(1e-8 + tok).unsqueeze(1) * x_mask
+        dur_loss = duration_loss(logw.double(), logw_.double(), x_lengths).float()
+        n_valid = torch.sum(y_lengths).double() * self.n_feats
+        prior_loss = (torch.sum(0.5 * ((y - mu_y).double() ** 2 + math.log(2 * math.pi)) * y_mask) / n_valid).float()
+        # compute_loss (flow_matching.py:87-118)
+        t = torch.rand([B], device=self.device, dtype=y.dtype) if t is None else t.to(self.device, y.dtype).reshape(B)
+        z = torch.randn_like(y) if z is None else z.to(self.device, y.dtype)
+        tb = t.view(B, 1, 1)
+        y_t = (1 - (1 - self.sigma_min) * tb) * z + tb * y
+        u = y - (1 - self.sigma_min) * z
+        pad = fix_len_compatibility(Ty) - Ty          # the U-Net needs a multiple of 4: masked frames, cut off again below
+        y_t_p, mu_y_p = F.pad(y_t, (0, pad)).contiguous(), F.pad(mu_y, (0, pad)).contiguous()
+        v = torch.empty_like(y_t_p)
+        for b, tv in enumerate(t.cpu().tolist()):
+            v[b:b + 1] = self.engine.estimator(y_t_p[b:b + 1], mu_y_p[b:b + 1], y_lengths[b:b + 1], None if spk is None else spk[b:b + 1], tv)
+        diff_loss = (torch.sum((v[:, :, :Ty] - u).double() ** 2) / n_valid).float()
+        return dur_loss, prior_loss, diff_loss, attn
+
+    __call__ = forward
 
     # ---- the hot call ------------------------------------------------------------
     def _durations(self, x, x_lengths, spks, length_scale):

@@ -8,7 +8,7 @@ Follows reference ``matcha/models/components/text_encoder.py`` (TextEncoder.forw
 :378-410 with ConvReluNorm :36-67, Encoder :276-325, MultiHeadAttention + RoPE
 :97-246, FFN :255-273, DurationPredictor :70-94, channel LayerNorm :15-33) and
 ``matcha/utils/model.py`` (sequence_mask :7-11, fix_len_compatibility :14-20,
-generate_path :29-41).
+generate_path :29-41, duration_loss :44-46).
 """
 from __future__ import annotations
 
@@ -39,6 +39,11 @@ def generate_path(duration: Tensor, mask: Tensor) -> Tensor:
     path = sequence_mask(cum, t_y).to(mask.dtype).view(b, t_x, t_y)
     path = path - F.pad(path, (0, 0, 1, 0, 0, 0))[:, :-1]
     return path * mask
+
+
+def duration_loss(logw: Tensor, logw_: Tensor, lengths: Tensor) -> Tensor:
+    """utils/model.py:44-46: squared error of the log-durations, per token of the batch."""
+    return torch.sum((logw - logw_) ** 2) / torch.sum(lengths)
 
 
 def _cln(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-4) -> Tensor:

@@ -23,6 +23,9 @@
  *   ev_mel_spectrogram <- mel_spectrogram(y, 1024, num_mels, sr, 256, 1024, fmin, fmax, center=False)   utils/audio.py:45-82
  *                       (the same function again in hifigan/meldataset.py:52), optionally with normalize() of utils/model.py fused
  *   ev_load_mel_basis  <- the librosa mel filter bank that function caches per (fmax, device)
+ *   ev_log_prior       <- the log-likelihood matrix of MatchaTTS.forward                         models/matcha_tts.py:186-193
+ *   ev_maximum_path    <- monotonic_align.maximum_path (maximum_path_c / maximum_path_each)      utils/monotonic_align/{__init__.py,core.pyx}
+ *   ev_mas_align       <- both, plus attn.sum(-1) and mu_y = attn^T mu_x                          models/matcha_tts.py:186-199, :226-228
  *
  * Conventions
  *   - All tensors are fp32.  Pointers named d_* are DEVICE pointers owned by the
@@ -60,7 +63,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -203,6 +206,38 @@ int ev_denoise(ev_handle *h, const float *d_audio, int B, int L, const float *d_
  *     L = 256 * T_voc_max.  Needs no estimator or vocoder weights; without a loaded basis the call fails with a message. */
 int ev_load_mel_basis(ev_handle *h, const float *basis, int n_mels, int n_freq);
 int ev_mel_spectrogram(ev_handle *h, const float *d_audio, int B, int L, float out_scale, float out_shift, float *d_mel, void *stream);
+
+/* Monotonic alignment search on the device: the no-grad side of MatchaTTS.forward (matcha_tts.py:186-199) and the reference's only native
+ * code, utils/monotonic_align/core.pyx.  Everything is enqueued on `stream`; nothing waits on the host or copies to or from it.
+ *   ev_maximum_path: the search alone, on scores the caller supplies (any Glow-TTS-style aligner).
+ *       d_value (B, Tx, Ty) f32, read only      d_xlen, d_ylen (B) int32: t_x, t_y of each row (what the reference takes from its mask)
+ *       d_path (B, Tx, Ty) f32 0/1 or NULL      d_dur (B, Tx) int32 = sum_j path[b, i, j], or NULL
+ *     Semantics are maximum_path_each's: value[x, y] += max(x == y ? -1e9 : value[x, y-1], x == 0 ? (y == 0 ? 0 : -1e9) : value[x-1, y-1])
+ *     inside the band max(0, t_x + y - t_y) <= x < min(t_x, y + 1), then the backtrack from t_x - 1 that steps down where
+ *     `index == y or value[index, y-1] < value[index-1, y-1]` (strict: a tie stays on the token).  One fp32 max and one fp32 add per cell:
+ *     path and durations are BIT-EQUAL to that loop for every finite input, ties included.  Rows of d_path beyond xlen and columns
+ *     beyond ylen are written as zeros, as the reference's path is.
+ *   ev_log_prior: d_mu_x (B, C, Tx), d_y (B, C, Ty) -> d_logp (B, Tx, Ty), every cell, unmasked; C = n_feats of the handle:
+ *       logp[b, i, j] = -0.5 sum_c (y[c, j] - mu_x[c, i])^2 - 0.5 C log(2 pi)
+ *     the quantity the reference expands into two matmuls and a row sum; here the direct form, one fp32 fmaf chain over the channels
+ *     in every arithmetic setting (no fp16 / bf16 pieces: the scores feed a hard decision).
+ *   ev_mas_align: the fused call.  One workgroup per utterance forms the scores of 16 frames at a time in LDS, takes the DP steps on
+ *     a running column and keeps ONE decision bit per cell (the backtrack's predicate); the fp32 (B, Tx, Ty) matrix is never written
+ *     unless d_logp is given, and then d_logp holds the very values the search consumed (the bits ev_log_prior gives).
+ *       d_attn (B, Tx, Ty) 0/1 or NULL      d_dur (B, Tx) int32 or NULL      d_mu_y (B, C, Ty) = attn^T mu_x (a gather) or NULL
+ *       d_logp (B, Tx, Ty) or NULL
+ *     attn / dur are bit-equal to ev_maximum_path on that d_logp.
+ * Limits: 1 <= B <= 65535, 1 <= Tx <= 4096 (two columns and a tile of at least four frames in the CU's 160 KiB of LDS), 1 <= Ty.
+ * A row with xlen < 1, xlen > ylen (where the reference reads outside the row), xlen > Tx or ylen > Ty is no error and no out-of-bounds
+ * access: its path, durations and mu_y are written as zeros.
+ * Scratch: B x Ty int32 (frame -> token) plus, only when Ty x ceil(Tx / 64) x 8 bytes of decision bits do not fit into LDS beside the tile,
+ * that many bytes per row — an arena of the handle that grows on demand like the denoiser's and counts in ev_alloc_count (a second call
+ * at the same shape allocates nothing); ev_reserve does not cover it. */
+int ev_maximum_path(ev_handle *h, const float *d_value, const int32_t *d_xlen, const int32_t *d_ylen, int B, int Tx, int Ty,
+                    float *d_path, int32_t *d_dur, void *stream);
+int ev_log_prior(ev_handle *h, const float *d_mu_x, const float *d_y, int B, int Tx, int Ty, float *d_logp, void *stream);
+int ev_mas_align(ev_handle *h, const float *d_mu_x, const float *d_y, const int32_t *d_xlen, const int32_t *d_ylen, int B, int Tx, int Ty,
+                 float *d_attn, int32_t *d_dur, float *d_mu_y, float *d_logp, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

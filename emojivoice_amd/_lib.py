@@ -26,6 +26,7 @@ EXPORTS = [
     "ev_cfm_decode2", "ev_reserve", "ev_alloc_count", "ev_dbg_sk_stats", "ev_op_attn_out", "ev_dbg_set_amax", "ev_dbg_set_attn_h16", "ev_dbg_set_chain", "ev_dbg_sk_taken",
     "ev_load_mel_basis", "ev_mel_spectrogram",
     "ev_maximum_path", "ev_log_prior", "ev_mas_align",
+    "ev_estimator_rows", "ev_cfm_loss",
 ]
 
 
@@ -126,6 +127,8 @@ def load_library() -> C.CDLL:
     lib.ev_alloc_count.restype = C.c_int64
     lib.ev_dbg_sk_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.ev_estimator.argtypes = [vp, vp, vp, vp, vp, f32, i32, i32, vp, vp]
+    lib.ev_estimator_rows.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    lib.ev_cfm_loss.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.ev_hifigan.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.ev_text_encoder.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
     lib.ev_text_encoder_status.argtypes = [vp, vp]
@@ -429,6 +432,49 @@ class Engine:
         self._check(self.lib.ev_estimator(self.h, x.data_ptr(), mu.data_ptr(), lengths.data_ptr(), spk_p, float(t), B, Tp,
                                           out.data_ptr(), _stream_ptr()), "ev_estimator")
         return out
+
+    @staticmethod
+    def _host_times(t, B: int) -> np.ndarray:
+        """(B,) float32 on the host: what the two per-row calls take their times as."""
+        tv = np.ascontiguousarray(torch.as_tensor(t).detach().to("cpu", torch.float32).numpy().reshape(-1))
+        if tv.shape[0] != B:
+            raise ValueError(f"t must hold one time per utterance: {B} expected, got {tv.shape[0]}")
+        return tv
+
+    def estimator_rows(self, x, mu, lengths, spk, t):
+        """``estimator`` with one time per utterance (ev_estimator_rows): ``t`` (B,), a tensor or a sequence.  Eager-only."""
+        x, mu = self._f32(x), self._f32(mu)
+        B, F, Tp = mu.shape
+        assert F == 80 and x.shape == mu.shape
+        lengths = lengths.to(mu.device, torch.int32).contiguous()
+        tv = self._host_times(t, B)
+        spk_p = None
+        if spk is not None:
+            spk = self._f32(spk)
+            spk_p = spk.data_ptr()
+        out = torch.empty_like(mu)
+        self._check(self.lib.ev_estimator_rows(self.h, x.data_ptr(), mu.data_ptr(), lengths.data_ptr(), spk_p, tv.ctypes.data_as(C.c_void_p), B, Tp,
+                                               out.data_ptr(), _stream_ptr()), "ev_estimator_rows")
+        return out
+
+    def cfm_loss(self, x1, mu_y, y_lengths, spk, z, t, sigma_min: float, want_v: bool = False):
+        """compute_loss for given draws in one call (ev_cfm_loss): x1, mu_y, z (B, 80, Ty) with any Ty, t (B,).  Returns (sums, v): sums
+        (B, 2) float64 = per row {sum (v - u)^2, sum 0.5 ((x1 - mu_y)^2 + log 2 pi)} over its y_lengths[b] x 80 valid cells, v the
+        velocity (B, 80, Ty) or None.  Eager-only."""
+        x1, mu_y, z = self._f32(x1), self._f32(mu_y), self._f32(z)
+        B, F, Ty = x1.shape
+        assert F == 80 and mu_y.shape == x1.shape and z.shape == x1.shape
+        yl = y_lengths.to(x1.device, torch.int32).contiguous()
+        tv = self._host_times(t, B)
+        spk_p = None
+        if spk is not None:
+            spk = self._f32(spk)
+            spk_p = spk.data_ptr()
+        sums = torch.empty((B, 2), dtype=torch.float64, device=x1.device)
+        v = torch.empty_like(x1) if want_v else None
+        self._check(self.lib.ev_cfm_loss(self.h, x1.data_ptr(), mu_y.data_ptr(), yl.data_ptr(), spk_p, z.data_ptr(), tv.ctypes.data_as(C.c_void_p), B, Ty,
+                                         float(sigma_min), sums.data_ptr(), v.data_ptr() if want_v else None, _stream_ptr()), "ev_cfm_loss")
+        return sums, v
 
     def hifigan(self, mel):
         mel = self._f32(mel)

@@ -9,11 +9,13 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --synthetic --emoji-text "Hello world 🙂" --ids "0 23 0 51 0"
     python -m emojivoice_amd.cli --mel_from_wav voice.wav [--vocoder_path g_02500000 | --synthetic]     # analysis: voice.wav.mel.npy (+ copy synthesis)
     python -m emojivoice_amd.cli --checkpoint_path model.ckpt --align_wav voice.wav --phonemes "həlˈoʊ" --spk 12   # voice.wav.durations.npy
+    python -m emojivoice_amd.cli --checkpoint_path model.ckpt --align_wav voice.wav --phonemes "həlˈoʊ" --spk 12 --losses   # + voice.wav.losses.json
 """
 from __future__ import annotations
 
 import argparse
 import datetime as dt
+import json
 import os
 import struct
 import sys
@@ -160,7 +162,8 @@ def mel_from_wav(args, device):
 def align_durations(args, device):
     """--align_mel MEL.npy (a normalised (80, frames) mel) / --align_wav VOICE.wav (analysed as --mel_from_wav does, normalize() fused)
     with the text of that utterance -> <input>.durations.npy: the Tx integer durations of MatchaTTS.align, what
-    utils/get_durations_from_trained_model.py saves per file."""
+    utils/get_durations_from_trained_model.py saves per file.  With --losses also <input>.losses.json: the utterance's dur_loss,
+    prior_loss and diff_loss of MatchaTTS.score, the time and the noise of the flow-matching loss drawn on the CPU from --seed."""
     from . import weights as W
     from .audio import mel_spectrogram, read_wav_pcm
     from .matcha_tts import MatchaTTS
@@ -179,10 +182,27 @@ def align_durations(args, device):
     ids, spk = parse_lines(args)[0]
     x = torch.tensor([ids], dtype=torch.long, device=device)
     spks = torch.tensor([spk if spk is not None else (args.spk or 0)], dtype=torch.long, device=device)
-    out = model.align(x, torch.tensor([len(ids)], device=device), mel, torch.tensor([mel.shape[-1]], device=device), spks)
+    x_len, y_len = torch.tensor([len(ids)], device=device), torch.tensor([mel.shape[-1]], device=device)
+    if args.losses:
+        t, z = loss_draws(args.seed, model.n_feats, mel.shape[-1])
+        out = model.score(x, x_len, mel, y_len, spks, t=t, z=z)
+    else:
+        out = model.align(x, x_len, mel, y_len, spks)
     dur = out["durations"][0].cpu().numpy()
     np.save(f"{src}.durations.npy", dur)
     print(f"[+] Durations saved: {Path(f'{src}.durations.npy').resolve()}  ({len(dur)} tokens over {mel.shape[-1]} frames)")
+    if args.losses:
+        rec = {k: float(out[k][0]) for k in ("dur_loss", "prior_loss", "diff_loss")}
+        rec.update(seed=int(args.seed), t=float(t[0]), tokens=len(ids), frames=int(mel.shape[-1]))
+        with open(f"{src}.losses.json", "w") as f:
+            json.dump(rec, f, indent=1)
+        print(f"[+] Losses saved: {Path(f'{src}.losses.json').resolve()}  (dur {rec['dur_loss']:.4f}  prior {rec['prior_loss']:.4f}  diff {rec['diff_loss']:.4f})")
+
+
+def loss_draws(seed: int, n_feats: int, frames: int):
+    """(t (1,), z (1, n_feats, frames)) of --losses: one CPU generator seeded with --seed, t first."""
+    g = torch.Generator().manual_seed(int(seed))
+    return torch.rand(1, generator=g), torch.randn(1, n_feats, frames, generator=g)
 
 
 @torch.inference_mode()
@@ -213,6 +233,9 @@ def cli(argv=None):
     p.add_argument("--align_mel", type=str, default=None, help="alignment instead of synthesis: a normalised mel (80, frames) .npy of the utterance "
                    "given by --ids / --phonemes -> PATH.durations.npy (monotonic alignment search, Tx integers)")
     p.add_argument("--align_wav", type=str, default=None, help="the same from a 22.05 kHz mono PCM wav, analysed as --mel_from_wav does and normalised")
+    p.add_argument("--losses", action="store_true", help="with --align_mel / --align_wav: also PATH.losses.json, the utterance's dur_loss, prior_loss and "
+                   "diff_loss (MatchaTTS.score); the loss's time and noise are drawn from --seed")
+    p.add_argument("--seed", type=int, default=0, help="seed of the draws of --losses")
     args = validate_args(p.parse_args(argv))
     if args.align_mel or args.align_wav:
         if not torch.cuda.is_available():

@@ -1060,10 +1060,10 @@ int launch_rb2(ev_handle* h, const ConvLayer* L, const float* X, float* Y, int C
 }
 
 int launch_gn(ev_handle* h, const float* X, int ldx, float* Y, int ldy, const float* gamma, const float* beta, const float* rowmask,
-              const float* temb, const float* R, int ldr, const Geom& g, int C, int mode, const float* part = nullptr) {
+              const float* temb, const float* R, int ldr, const Geom& g, int C, int mode, const float* part = nullptr, int temb_stride = 0) {
     GNParams p;
     p.X = X; p.ldx = ldx; p.Y = Y; p.ldy = ldy; p.gamma = gamma; p.beta = beta; p.rowmask = rowmask; p.temb = temb; p.R = R; p.ldr = ldr;
-    p.S = g.S; p.P = g.P; p.T = g.T; p.CG = C / 8; p.mode = mode; p.eps = 1e-5f;
+    p.S = g.S; p.P = g.P; p.T = g.T; p.CG = C / 8; p.mode = mode; p.eps = 1e-5f; p.temb_stride = temb_stride;
     if (p.CG != 32) return fail(h, "groupnorm kernel expects 32 channels per group, got %d", p.CG);
     // one utterance whose producer (the conv launched just before) left per-tile statistics: a workgroup per (32 frames, group)
     if (part && h->gn_stats_tiles > 0 && g.nrows == g.S && h->gn_stats_tiles == (g.nrows + 31) / 32)
@@ -1304,6 +1304,7 @@ struct EstBufs {
     float *rm0, *rm1, *X0, *state, *A0, *B0, *R0, *H0, *LN0, *QKV0, *ATT0, *FF0, *CAT1, *U1, *F0, *G0, *V0;
     float *A1, *B1, *R1, *H1, *LN1, *QKV1, *ATT1, *FF1, *CAT0, *D1, *D2, *M1, *UU;
     float *tv, *temb_in, *temb_a, *temb_b, *tproj;
+    float *LOSSP; int32_t* elen;   // ev_cfm_loss: per (row, 32-frame tile) {sum d^2, sum prior} in float64, and the lengths its estimator pass runs with
     float *GNP;          // per-tile GroupNorm statistics of a conv_sk32_kernel launch: EV_GN_MAXTILES x 8 groups x {count, mean, M2, -}
     float *ATTP;         // split-key attention partials: EV_ATTN_MAXPARTS x min(rows, EV_ATTN_MAXROWS) x (128 + 4) floats (the levels run one after the other)
     float *C1RMS;        // time-invariant (mu, spk) share of rn[0]'s [block1 conv | res_conv], 512 wide
@@ -1328,6 +1329,7 @@ void plan_est(Bump& b, int B, int Tp, int in_ch, int nsteps, EstBufs& e) {
     e.ATTP = b.take(std::min<size_t>(n0, EV_ATTN_MAXROWS) * EV_ATTN_MAXPARTS * (128 + 4));
     e.GNP = b.take((size_t)EV_GN_MAXTILES * 8 * 4);
     e.tv = b.take(ns); e.temb_in = b.take(ns * in_ch); e.temb_a = b.take(ns * 1024); e.temb_b = b.take(ns * 1024); e.tproj = b.take(ns * 1536);
+    e.LOSSP = b.take((size_t)B * (Tp / 32 + 1) * 4); e.elen = (int32_t*)b.take(B);
 }
 
 struct VocBufs {
@@ -1464,20 +1466,20 @@ int ensure_ws(ev_handle* h, int B, int Tp, int Tv, EstBufs* eb, VocBufs* vb) {
 struct LevelBufs { float *A, *Bf, *R, *H, *LN, *QKV, *ATT, *FF; const float* rm; Geom g; float* AR; float* ATTP; float* GNP; };
 inline int g_rows32(const Geom& g) { return (g.nrows + 31) / 32; }
 
-int run_resnet(ev_handle* h, const ResnetW& w, const float* X, int ldx, const LevelBufs& L, const float* temb) {
+int run_resnet(ev_handle* h, const ResnetW& w, const float* X, int ldx, const LevelBufs& L, const float* temb, int tstride) {
     Epi e; e.gn_part = L.GNP;
     if (launch_conv(h, w.c1r, X, ldx, L.AR, 512, L.g, e)) return 1;                       // [block1 conv | res_conv]
-    if (launch_gn(h, L.AR, 512, L.Bf, 256, w.g1, w.b1, L.rm, temb, nullptr, 0, L.g, 256, 1, L.GNP)) return 1;
+    if (launch_gn(h, L.AR, 512, L.Bf, 256, w.g1, w.b1, L.rm, temb, nullptr, 0, L.g, 256, 1, L.GNP, tstride)) return 1;
     if (launch_conv(h, w.c2, L.Bf, 256, L.A, 256, L.g, e)) return 1;
     return launch_gn(h, L.A, 256, L.H, 256, w.g2, w.b2, L.rm, nullptr, L.AR + 256, 512, L.g, 256, 2, L.GNP);
 }
 
 // rn[0] with the time-invariant input share hoisted out of the Euler loop (see EstimatorW): X = X0 (x in columns [0, n_feats))
-int run_resnet0(ev_handle* h, const EstimatorW& W, const float* X, int ldx, const LevelBufs& L, const float* temb, const float* C1RMS) {
+int run_resnet0(ev_handle* h, const EstimatorW& W, const float* X, int ldx, const LevelBufs& L, const float* temb, int tstride, const float* C1RMS) {
     const ResnetW& w = W.rn[0];
     Epi e;
     { Epi e1; e1.R = C1RMS; e1.ldr = 512; if (launch_conv(h, W.rn0_c1r_x, X, ldx, L.AR, 512, L.g, e1)) return 1; }
-    if (launch_gn(h, L.AR, 512, L.Bf, 256, w.g1, w.b1, L.rm, temb, nullptr, 0, L.g, 256, 1)) return 1;   // (c1r adds the hoisted share: no statistics)
+    if (launch_gn(h, L.AR, 512, L.Bf, 256, w.g1, w.b1, L.rm, temb, nullptr, 0, L.g, 256, 1, nullptr, tstride)) return 1;   // (c1r adds the hoisted share: no statistics)
     e.gn_part = L.GNP;
     if (launch_conv(h, w.c2, L.Bf, 256, L.A, 256, L.g, e)) return 1;
     return launch_gn(h, L.A, 256, L.H, 256, w.g2, w.b2, L.rm, nullptr, L.AR + 256, 512, L.g, 256, 2, L.GNP);
@@ -1513,38 +1515,39 @@ int run_transformer(ev_handle* h, const TransW& w, const LevelBufs& L, float* Z,
     return launch_conv(h, w.ff2, L.FF, 1024, Z, ldz, L.g, e2);
 }
 
-// One estimator evaluation.  euler: state += dt * v, X0[:, :80] = state * m ; else V0 = v.
-int run_estimator(ev_handle* h, EstBufs& b, int step, float dt, bool euler, const float* tproj = nullptr) {
+// One estimator evaluation.  euler: state += dt * v, X0[:, :80] = state * m ; else V0 = v.  tstride 0: every utterance reads row
+// `step` of the time projections; 1536 (with step 0): utterance b reads row b (one time per utterance).
+int run_estimator(ev_handle* h, EstBufs& b, int step, float dt, bool euler, const float* tproj = nullptr, int tstride = 0) {
     const EstimatorW& w = h->est;
     const int heads = h->dims.heads;
     LevelBufs L0{b.A0, b.B0, b.R0, b.H0, b.LN0, b.QKV0, b.ATT0, b.FF0, b.rm0, b.g0, b.AR0, b.ATTP, b.GNP};
     LevelBufs L1{b.A1, b.B1, b.R1, b.H1, b.LN1, b.QKV1, b.ATT1, b.FF1, b.rm1, b.g1, b.AR1, b.ATTP, b.GNP};
     const float* tp = (tproj ? tproj : b.tproj) + (size_t)step * 1536;
     // down 0 @T
-    if (run_resnet0(h, w, b.X0, w.in_ch, L0, tp + 0 * 256, b.C1RMS)) return 1;
+    if (run_resnet0(h, w, b.X0, w.in_ch, L0, tp + 0 * 256, tstride, b.C1RMS)) return 1;
     if (run_transformer(h, w.tr[0], L0, b.CAT1 + 256, 512, heads)) return 1;      // hidden 0
     {   // Downsample1D k3 s2 p1 over the pair view of CAT1[:, 256:512]
         Epi e; e.isplit_log2 = 8; e.isstride = 512; e.mask1 = 1; e.rowmask = b.rm1;
         if (launch_conv(h, w.down0, b.CAT1 + 256, 1024, b.D1, 256, b.g1, e)) return 1;
     }
     // down 1 @T/2
-    if (run_resnet(h, w.rn[1], b.D1, 256, L1, tp + 1 * 256)) return 1;
+    if (run_resnet(h, w.rn[1], b.D1, 256, L1, tp + 1 * 256, tstride)) return 1;
     if (run_transformer(h, w.tr[1], L1, b.CAT0 + 256, 512, heads)) return 1;      // hidden 1
     { Epi e; e.mask1 = 1; e.rowmask = b.rm1; if (launch_conv(h, w.down1, b.CAT0 + 256, 512, b.D2, 256, b.g1, e)) return 1; }
     // mid
-    if (run_resnet(h, w.rn[2], b.D2, 256, L1, tp + 2 * 256)) return 1;
+    if (run_resnet(h, w.rn[2], b.D2, 256, L1, tp + 2 * 256, tstride)) return 1;
     if (run_transformer(h, w.tr[2], L1, b.M1, 256, heads)) return 1;
-    if (run_resnet(h, w.rn[3], b.M1, 256, L1, tp + 3 * 256)) return 1;
+    if (run_resnet(h, w.rn[3], b.M1, 256, L1, tp + 3 * 256, tstride)) return 1;
     if (run_transformer(h, w.tr[3], L1, b.CAT0, 512, heads)) return 1;
     // up 0 @T/2: cat([x, hidden1])
-    if (run_resnet(h, w.rn[4], b.CAT0, 512, L1, tp + 4 * 256)) return 1;
+    if (run_resnet(h, w.rn[4], b.CAT0, 512, L1, tp + 4 * 256, tstride)) return 1;
     if (run_transformer(h, w.tr[4], L1, b.UU, 256, heads)) return 1;
     {   // ConvTranspose1d k4 s2 p1: view-row q -> frames 2q, 2q+1 of CAT1[:, 0:256]
         Epi e; e.osplit_log2 = 8; e.osstride = 512; e.mask1 = 1; e.rowmask = b.rm0; e.mmul = 2;
         if (launch_conv(h, w.up0, b.UU, 256, b.CAT1, 1024, b.g1, e)) return 1;
     }
     // up 1 @T: cat([x, hidden0])
-    if (run_resnet(h, w.rn[5], b.CAT1, 512, L0, tp + 5 * 256)) return 1;
+    if (run_resnet(h, w.rn[5], b.CAT1, 512, L0, tp + 5 * 256, tstride)) return 1;
     if (run_transformer(h, w.tr[5], L0, b.U1, 256, heads)) return 1;
     { Epi e; e.mask1 = 1; e.rowmask = b.rm0; if (launch_conv(h, w.up1, b.U1, 256, b.F0, 256, b.g0, e)) return 1; }
     // final block + projection
@@ -1621,16 +1624,16 @@ int run_time_mlp(ev_handle* h, EstBufs& b, const std::vector<float>& ts) {
     return launch_conv(h, w.tmlp, b.temb_b, 1024, b.tproj, 1536, gt, e3);
 }
 
-int prep_inputs(ev_handle* h, EstBufs& b, const float* d_x, const float* d_mu, const int32_t* d_len, const float* d_spk, int B, int Tp) {
-    const EstimatorW& w = h->est;
+void prep_masks(ev_handle* h, EstBufs& b, const int32_t* d_len) {
     hipStream_t st = h->stream;
     hipLaunchKernelGGL(rowmask_kernel, dim3((b.g0.nrows + 255) / 256), dim3(256), 0, st, b.rm0, d_len, b.g0.nrows, b.g0.S, b.g0.P, b.g0.T, 1);
     hipLaunchKernelGGL(rowmask_kernel, dim3((b.g1.nrows + 255) / 256), dim3(256), 0, st, b.rm1, d_len, b.g1.nrows, b.g1.S, b.g1.P, b.g1.T, 2);
-    dim3 grid((Tp + 31) / 32, (80 + 31) / 32, B);
-    // ODE state (unmasked) and the masked estimator input [x*m | mu*m | spk*m]
-    hipLaunchKernelGGL(cm_to_fm_kernel, grid, dim3(256), 0, st, d_x, b.state, 80, 0, 80, Tp, b.g0.S, b.g0.P, (const float*)nullptr, 1.0f);
-    hipLaunchKernelGGL(cm_to_fm_kernel, grid, dim3(256), 0, st, d_x, b.X0, w.in_ch, 0, 80, Tp, b.g0.S, b.g0.P, (const float*)b.rm0, 1.0f);
-    hipLaunchKernelGGL(cm_to_fm_kernel, grid, dim3(256), 0, st, d_mu, b.X0, w.in_ch, 80, 80, Tp, b.g0.S, b.g0.P, (const float*)b.rm0, 1.0f);
+}
+
+// the speaker columns of X0 and the time-invariant share of rn[0]; X0's [x | mu] columns and the row masks are in place
+int prep_rest(ev_handle* h, EstBufs& b, const float* d_spk) {
+    const EstimatorW& w = h->est;
+    hipStream_t st = h->stream;
     if (w.in_ch > 160) {
         const int C = w.in_ch - 160;
         const long tot = (long)b.g0.nrows * C;
@@ -1642,6 +1645,18 @@ int prep_inputs(ev_handle* h, EstBufs& b, const float* d_x, const float* d_mu, c
         if (launch_conv(h, w.rn0_c1r_ms, b.X0 + h->dims.n_feats, w.in_ch, b.C1RMS, 512, b.g0, e)) return 1;
     }
     return 0;
+}
+
+int prep_inputs(ev_handle* h, EstBufs& b, const float* d_x, const float* d_mu, const int32_t* d_len, const float* d_spk, int B, int Tp) {
+    const EstimatorW& w = h->est;
+    hipStream_t st = h->stream;
+    prep_masks(h, b, d_len);
+    dim3 grid((Tp + 31) / 32, (80 + 31) / 32, B);
+    // ODE state (unmasked) and the masked estimator input [x*m | mu*m | spk*m]
+    hipLaunchKernelGGL(cm_to_fm_kernel, grid, dim3(256), 0, st, d_x, b.state, 80, 0, 80, Tp, b.g0.S, b.g0.P, (const float*)nullptr, 1.0f);
+    hipLaunchKernelGGL(cm_to_fm_kernel, grid, dim3(256), 0, st, d_x, b.X0, w.in_ch, 0, 80, Tp, b.g0.S, b.g0.P, (const float*)b.rm0, 1.0f);
+    hipLaunchKernelGGL(cm_to_fm_kernel, grid, dim3(256), 0, st, d_mu, b.X0, w.in_ch, 80, 80, Tp, b.g0.S, b.g0.P, (const float*)b.rm0, 1.0f);
+    return prep_rest(h, b, d_spk);
 }
 
 int launch_cln(ev_handle* h, const float* X, int ldx, const float* R, int ldr, const float* g, const float* b, const float* rowmask, float* Y, int ldy,
@@ -2540,6 +2555,87 @@ int ev_estimator(ev_handle* h, const float* d_x, const float* d_mu, const int32_
     if (run_estimator(h, b, 0, 0.f, false)) return 1;
     dim3 grid((Tp + 31) / 32, (80 + 31) / 32, B);
     hipLaunchKernelGGL(fm_to_cm_kernel, grid, dim3(256), 0, h->stream, (const float*)b.V0, 80, 0, d_v, 80, Tp, b.g0.S, b.g0.P, 1.0f, 0.0f);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// What the two per-row calls share: the argument and capture checks, a time plan of at least B slots (the buffers of run_time_mlp are
+// sized by the planned step count) with both slots of the pinned ring to match, and the workspace.  One growth — ring, arena or both —
+// moves ev_alloc_count once.
+static int rows_begin(ev_handle* h, const char* who, int B, int Tp, void* stream, EstBufs* b) {
+    if (check_cfm_args(h, B, Tp)) return 1;
+    h->stream = (hipStream_t)stream;
+    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+    if (h->stream && hipStreamIsCapturing(h->stream, &cst) == hipSuccess && cst == hipStreamCaptureStatusActive)
+        return fail(h, "%s is eager-only: under stream capture its host-to-device copy of the B times would replay from recycled staging "
+                       "(see run_time_mlp); call it outside the capture", who);
+    const int64_t before = h->n_allocs;
+    if (B > h->max_steps) {
+        if (h->captured) return fail(h, "%s: %d rows exceed the %d time slots the workspace is planned for and the handle holds a captured call: "
+                                        "its workspace cannot be re-planned", who, B, h->max_steps);
+        while (B > h->max_steps) h->max_steps *= 2;
+        h->ws_B = -1;
+    }
+    bool ring_grew = false;
+    const size_t bytes = (size_t)std::max(64, h->max_steps) * h->est.in_ch * sizeof(float);
+    for (int slot = 0; slot < 2; ++slot) {
+        if (h->temb_cap[slot] >= (size_t)B * h->est.in_ch * sizeof(float)) continue;
+        if (h->temb_host[slot]) { HIPCHK(h, hipEventSynchronize(h->temb_ev[slot])); HIPCHK(h, hipHostFree(h->temb_host[slot])); h->temb_host[slot] = nullptr; h->temb_cap[slot] = 0; }
+        HIPCHK(h, hipHostMalloc((void**)&h->temb_host[slot], bytes, hipHostMallocDefault));
+        h->temb_cap[slot] = bytes;
+        if (!h->temb_ev[slot]) HIPCHK(h, hipEventCreateWithFlags(&h->temb_ev[slot], hipEventDisableTiming));
+        HIPCHK(h, hipEventRecord(h->temb_ev[slot], h->stream));
+        ring_grew = true;
+    }
+    if (ensure_ws(h, B, Tp, 0, b, nullptr)) return 1;
+    if (ring_grew && h->n_allocs == before) ++h->n_allocs;
+    return 0;
+}
+
+int ev_estimator_rows(ev_handle* h, const float* d_x, const float* d_mu, const int32_t* d_lengths, const float* d_spk, const float* t,
+                      int B, int Tp, float* d_v, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    EstBufs b;
+    if (rows_begin(h, "ev_estimator_rows", B, Tp, stream, &b)) return 1;
+    if (!d_x || !d_mu || !t || !d_v || (h->dims.spk_emb_dim > 0 && !d_spk)) return fail(h, "null tensor argument");
+    if (prep_inputs(h, b, d_x, d_mu, d_lengths, d_spk, B, Tp)) return 1;
+    if (run_time_mlp(h, b, std::vector<float>(t, t + B))) return 1;       // tproj: (B, 1536)
+    if (run_estimator(h, b, 0, 0.f, false, nullptr, 1536)) return 1;
+    dim3 grid((Tp + 31) / 32, (80 + 31) / 32, B);
+    hipLaunchKernelGGL(fm_to_cm_kernel, grid, dim3(256), 0, h->stream, (const float*)b.V0, 80, 0, d_v, 80, Tp, b.g0.S, b.g0.P, 1.0f, 0.0f);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int ev_cfm_loss(ev_handle* h, const float* d_x1, const float* d_mu_y, const int32_t* d_ylen, const float* d_spk, const float* d_z, const float* t,
+                int B, int Ty, float sigma_min, double* d_row_sums, float* d_v, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (Ty < 1 || Ty > (1 << 30)) return fail(h, "ev_cfm_loss: bad shape B=%d Ty=%d", B, Ty);
+    const int Tp = (Ty + 3) / 4 * 4;              // fix_len_compatibility: the pad frames are masked ones
+    EstBufs b;
+    if (rows_begin(h, "ev_cfm_loss", B, Tp, stream, &b)) return 1;
+    if (!d_x1 || !d_mu_y || !d_ylen || !d_z || !t || !d_row_sums || (h->dims.spk_emb_dim > 0 && !d_spk)) return fail(h, "null tensor argument");
+    const EstimatorW& w = h->est;
+    hipStream_t st = h->stream;
+    const float c1 = (float)(1.0 - (double)sigma_min);
+    // the times go to the device once (the mix kernel reads them; the time MLP takes its sinusoids from the host as every call does).
+    // t is ordinary host memory: the runtime stages it before the call returns
+    HIPCHK(h, hipMemcpyAsync(b.tv, t, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(cfm_lengths_kernel, dim3((B + 255) / 256), dim3(256), 0, st, d_ylen, b.elen, B, Ty);
+    prep_masks(h, b, b.elen);
+    dim3 grid((Tp + 31) / 32, (80 + 31) / 32, B);
+    hipLaunchKernelGGL(cfm_mix_kernel, grid, dim3(256), 0, st, d_x1, d_z, (const float*)b.tv, d_ylen, b.X0, w.in_ch, 0, 80, Ty, Tp, b.g0.S, b.g0.P, c1);
+    hipLaunchKernelGGL(cfm_mix_kernel, grid, dim3(256), 0, st, d_mu_y, (const float*)nullptr, (const float*)nullptr, d_ylen, b.X0, w.in_ch, 80, 80, Ty, Tp, b.g0.S, b.g0.P, c1);
+    HIPCHK(h, hipGetLastError());
+    if (prep_rest(h, b, d_spk)) return 1;
+    if (run_time_mlp(h, b, std::vector<float>(t, t + B))) return 1;
+    if (run_estimator(h, b, 0, 0.f, false, nullptr, 1536)) return 1;
+    const int ntiles = (Ty + 31) / 32;
+    hipLaunchKernelGGL(cfm_loss_kernel, dim3(ntiles, B), dim3(256), 0, st, (const float*)b.V0, d_x1, d_z, d_mu_y, d_ylen, Ty, b.g0.S, b.g0.P, c1,
+                       (double*)b.LOSSP, ntiles, d_v);
+    hipLaunchKernelGGL(cfm_loss_merge_kernel, dim3((B + 63) / 64), dim3(64), 0, st, (const double*)b.LOSSP, ntiles, B, d_row_sums);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

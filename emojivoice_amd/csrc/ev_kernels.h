@@ -3774,7 +3774,8 @@ __device__ __forceinline__ float block_sum(float v, float* red /*[NTHR/64]*/) {
 // GroupNorm(groups of CG channels over all T frames of one utterance, padded
 // frames included — decoder.py:41-43) + Mish + mask, then one of
 //   mode 0:  y = mish(gn(x)) * m
-//   mode 1:  y = (mish(gn(x)) * m + temb[c]) * m        (ResnetBlock1D block1 + time MLP, decoder.py:56-57)
+//   mode 1:  y = (mish(gn(x)) * m + temb[c]) * m        (ResnetBlock1D block1 + time MLP, decoder.py:56-57); utterance b reads
+//            temb + b * temb_stride (0: every utterance shares one time, the Euler loop; 1536: one time per utterance, ev_estimator_rows)
 //   mode 2:  y = mish(gn(x)) * m + R[n][c]              (block2 + res_conv, decoder.py:58-60)
 // One workgroup per (utterance, group); wavefront shuffles for the reductions.
 // ---------------------------------------------------------------------------
@@ -3783,6 +3784,7 @@ struct GNParams {
     const float* gamma; const float* beta;
     const float* rowmask; const float* temb; const float* R; int ldr;
     int S, P, T, CG; int mode; float eps;
+    int temb_stride;
 };
 
 template <int NTHR, bool PRE = false>   // (PRE is false only: the parameter keeps the kernel's name, see conv_gemm_kernel's KB)
@@ -3844,7 +3846,7 @@ __global__ __launch_bounds__(NTHR) void groupnorm_mish_kernel(const GNParams p) 
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         ga[e] = p.gamma[cbase + e]; be[e] = p.beta[cbase + e];
-        te[e] = (p.mode == 1) ? p.temb[cbase + e] : 0.f;
+        te[e] = (p.mode == 1) ? p.temb[(size_t)b * p.temb_stride + cbase + e] : 0.f;
     }
     auto apply = [&](int t, f32x4 v) {
         const size_t n = rowbase + t;
@@ -6238,6 +6240,103 @@ __global__ void fm_to_cm_kernel(const float* src, int ld, int c0, float* __restr
         int c = cb + i, t = t0 + tx;
         if (c < C && t < T) dst[((size_t)b * C + c) * T + t] = tile[tx][i] * scale + shift;
     }
+}
+
+// ---------------------------------------------------------------------------
+// The flow-matching loss of a batch (flow_matching.py:87-118), ev_cfm_loss.  Neither y_t nor u exists in memory: the mix kernel
+// writes y_t where the estimator reads its input, the loss kernel forms u next to the velocity it is compared with.
+// ---------------------------------------------------------------------------
+// valid frames of a row for the loss: a length outside [1, Ty] marks a row that is skipped (zeros, the ev_mas_align convention)
+__device__ __forceinline__ int cfm_valid_len(int len, int Ty) { return (len >= 1 && len <= Ty) ? len : 0; }
+
+// lengths the estimator runs with: a skipped row becomes one frame of zeros (an utterance of its own: no other row sees it)
+__global__ void cfm_lengths_kernel(const int32_t* ylen, int32_t* elen, int B, int Ty) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) { const int v = cfm_valid_len(ylen[b], Ty); elen[b] = v ? v : 1; }
+}
+
+// (B, C, Ty) channel-major -> frame-major rows (b*S + P + t), columns [c0, c0+C), for ALL t < Tp: frames at or past the row's length
+// and the pad frames Ty .. Tp are written as zeros.  With z: y_t = (1 - (1 - sigma_min) t) z + t x1 in the reference's float32
+// operation order (flow_matching.py:112; c1 = float(1 - sigma_min); every product and sum rounded on its own, as torch's separate ops
+// round them).  Without z: the masked copy of x1 (mu_y).
+__global__ void cfm_mix_kernel(const float* __restrict__ x1, const float* __restrict__ z, const float* __restrict__ tv, const int32_t* __restrict__ ylen,
+                               float* dst, int ld, int c0, int C, int Ty, int Tp, int S, int P, float c1) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z;
+    const int t0 = blockIdx.x * 32, cb = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+    const int valid = cfm_valid_len(ylen[b], Ty);
+    const float tb = z ? tv[b] : 0.f;
+    const float a = __fsub_rn(1.0f, __fmul_rn(c1, tb));
+    for (int i = ty; i < 32; i += 8) {
+        const int c = cb + i, t = t0 + tx;
+        float v = 0.f;
+        if (c < C && t < valid) {
+            const size_t k = ((size_t)b * C + c) * Ty + t;
+            v = x1[k];
+            if (z) v = __fadd_rn(__fmul_rn(a, z[k]), __fmul_rn(tb, v));
+        }
+        tile[i][tx] = v;
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) {
+        const int t = t0 + i, c = cb + tx;
+        if (t < Tp && c < C) dst[((size_t)b * S + P + t) * ld + c0 + c] = tile[tx][i];
+    }
+}
+
+// One pass over the velocity V (frame-major, 80 wide) and x1, z, mu_y (B, 80, Ty): per valid (frame, channel) u = x1 - c1 z and
+// d = v - u in float32, then d^2 and 0.5 ((x1 - mu_y)^2 + log 2 pi) summed in float64.  One workgroup per (row, 32 frames): its two
+// sums go to part[(b * ntiles + tile) * 2 ..] through a fixed shuffle tree and a fixed order over the waves — no atomics, so the
+// bits do not depend on scheduling.  d_v (optional) receives the velocity as (B, 80, Ty), zeros past the row's length.
+__global__ __launch_bounds__(256) void cfm_loss_kernel(const float* __restrict__ V, const float* __restrict__ x1, const float* __restrict__ z,
+                                                        const float* __restrict__ mu, const int32_t* __restrict__ ylen, int Ty, int S, int P, float c1,
+                                                        double* part, int ntiles, float* d_v) {
+    __shared__ float vt[32][81];
+    __shared__ double red[4][2];
+    const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const int t0 = tile * 32;
+    const int valid = cfm_valid_len(ylen[b], Ty);
+    for (int k = tid; k < 32 * 80; k += 256) {
+        const int r = k / 80, c = k - r * 80;
+        vt[r][c] = (t0 + r < valid) ? V[((size_t)b * S + P + t0 + r) * 80 + c] : 0.f;
+    }
+    __syncthreads();
+    const int tx = tid & 31, cy = tid >> 5;
+    const int t = t0 + tx;
+    double sd = 0.0, sp = 0.0;
+    if (t < Ty) {
+        for (int c = cy; c < 80; c += 8) {
+            const size_t k = ((size_t)b * 80 + c) * Ty + t;
+            const float v = vt[tx][c];
+            if (d_v) d_v[k] = v;
+            if (t < valid) {
+                const float x = x1[k];
+                const float u = __fsub_rn(x, __fmul_rn(c1, z[k]));
+                const float d = __fsub_rn(v, u), e = __fsub_rn(x, mu[k]);
+                sd += (double)d * (double)d;
+                sp += 0.5 * ((double)e * (double)e + 1.8378770664093453);   // log(2 pi)
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { sd += __shfl_down(sd, o); sp += __shfl_down(sp, o); }
+    if ((tid & 63) == 0) { red[tid >> 6][0] = sd; red[tid >> 6][1] = sp; }
+    __syncthreads();
+    if (tid == 0) {
+        double* o = part + ((size_t)b * ntiles + tile) * 2;
+        o[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+        o[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+    }
+}
+
+// row sums = the row's tiles in ascending order (one thread per row: a few dozen additions)
+__global__ void cfm_loss_merge_kernel(const double* part, int ntiles, int B, double* out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double sd = 0.0, sp = 0.0;
+    for (int j = 0; j < ntiles; ++j) { sd += part[((size_t)b * ntiles + j) * 2]; sp += part[((size_t)b * ntiles + j) * 2 + 1]; }
+    out[2 * b] = sd; out[2 * b + 1] = sp;
 }
 
 // broadcast a per-utterance vector (B, C) over all valid frames: dst[n][c0 + c] = v[b][c] * rowmask[n]

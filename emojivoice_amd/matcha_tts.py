@@ -68,6 +68,38 @@ def text_encoder_tensors(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]
     return out
 
 
+def row_losses(sums, logw, logw_, x_lengths, y_lengths, n_feats: int = 80) -> Dict[str, torch.Tensor]:
+    """Per-utterance losses from the (B, 2) float64 row sums of ``ev_cfm_loss`` {sum (v - u)^2, sum prior}: each row's sum over its
+    y_lengths[b] * n_feats cells divided by that count; dur_loss of a row = sum (logw - logw_)^2 / x_lengths[b].  Float64 (B,) each; the
+    callers round once to the reference's float32."""
+    B = sums.shape[0]
+    cells = y_lengths.reshape(B).double() * n_feats
+    dur = torch.sum((logw.double() - logw_.double()).reshape(B, -1) ** 2, dim=1) / x_lengths.reshape(B).double()
+    return {"dur_loss": dur, "prior_loss": sums[:, 1].double() / cells, "diff_loss": sums[:, 0].double() / cells}
+
+
+def batch_losses(sums, padded_sum, logw, logw_, x_lengths, y_lengths, n_feats: int = 80):
+    """(dur_loss, prior_loss, diff_loss) of the batch as the reference defines them (matcha_tts.py:203-204, :241-242,
+    flow_matching.py:115-117), float64 scalars: sum_b sums / (sum_b y_lengths * n_feats).  ``padded_sum``: the
+    diff_loss share of the padded frames (``padded_frames_sum``), which the reference's mse_loss counts and the row sums do not."""
+    n_valid = torch.sum(y_lengths).double() * n_feats
+    dur_loss = duration_loss(logw.double(), logw_.double(), x_lengths)
+    return dur_loss, torch.sum(sums[:, 1].double()) / n_valid, (torch.sum(sums[:, 0].double()) + padded_sum) / n_valid
+
+
+def padded_frames_sum(y, z, y_lengths, sigma_min: float) -> torch.Tensor:
+    """sum u^2 over the frames at or past each row's length, float64 scalar, u = y - (1 - sigma_min) z in float32: the reference's
+    F.mse_loss(estimator(...), u, reduction="sum") runs over the padded frames of the shorter rows too, where the estimator is exactly 0
+    and u is not (flow_matching.py:115-117).  It needs no estimator; a batch of full-length rows has none."""
+    Ty = y.shape[2]
+    tail = Ty - int(y_lengths.min())
+    if tail <= 0:
+        return torch.zeros((), dtype=torch.float64, device=y.device)
+    y, z = y[:, :, Ty - tail:], z[:, :, Ty - tail:]                          # only the columns some row pads
+    pad = ~sequence_mask(y_lengths, Ty)[:, Ty - tail:].unsqueeze(1)
+    return torch.sum(((y - (1 - sigma_min) * z) * pad).double() ** 2)
+
+
 class MatchaTTS:
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda:0", n_heads_encoder: int = 2, n_layers_encoder: int = 6):
         sd = {k: v.detach().float() for k, v in state_dict.items()}
@@ -155,33 +187,46 @@ class MatchaTTS:
         logw_ = torch.log(1e-8 + r["dur"].to(mu_x.dtype)).unsqueeze(1) * x_mask
         return {"attn": r["attn"], "durations": r["dur"].long(), "logw_": logw_, "mu_y": r["mu_y"]}
 
-    @torch.inference_mode()
-    def forward(self, x, x_lengths, y, y_lengths, spks=None, out_size=None, cond=None, durations=None, *, t=None, z=None):
-        """Reference matcha_tts.py:154-246 without gradients: (dur_loss, prior_loss, diff_loss, attn (B, Tx, Ty)).
-        ``durations`` (B, 1, Tx) or (B, Tx), as under the reference's ``use_precomputed_durations``, replace the search by
-        generate_path.  Extension: keyword-only ``t`` (B,) and ``z`` (B, 80, Ty) replace the draws of compute_loss
-        (flow_matching.py:105-110) for reproducible runs.  The estimator runs one row at a time (``ev_estimator`` takes one scalar
-        t per call): an evaluation pass, not the request path."""
-        if out_size is not None:
-            raise NotImplementedError("out_size (the random segment cut of matcha_tts.py:206-231, a training memory hack) is not supported: pass out_size=None")
-        x_lengths, y, y_lengths, spk, mu_x, logw, x_mask = self._encode_pairs(x, x_lengths, y, y_lengths, spks)
-        B, _, Ty = y.shape
-        y_mask = sequence_mask(y_lengths, Ty).unsqueeze(1).to(x_mask.dtype)
+    def _align_pairs(self, durations, mu_x, logw, x_mask, y, x_lengths, y_lengths):
+        """(mu_y, attn (B, Tx, Ty), logw_) of forward: from given durations through generate_path, else the search."""
         if durations is not None:
-            mu_y, attn = self.engine.align(durations.to(self.device).float(), mu_x, x_lengths, y_lengths, Ty)
+            mu_y, attn = self.engine.align(durations.to(self.device).float(), mu_x, x_lengths, y_lengths, y.shape[2])
             attn = attn.squeeze(1)
             tok = attn.sum(-1)
         else:
             r = self.engine.mas_align(mu_x, y, x_lengths, y_lengths)
             mu_y, attn, tok = r["mu_y"], r["attn"], r["dur"].to(mu_x.dtype)
+        return mu_y, attn, torch.log(1e-8 + tok).unsqueeze(1) * x_mask
+
+    def _draws(self, y, t, z):
+        """t (B,) and z (B, 80, Ty) of compute_loss (flow_matching.py:105-110): drawn here unless given."""
+        B = y.shape[0]
+        t = torch.rand([B], device=self.device, dtype=y.dtype) if t is None else t.to(self.device, y.dtype).reshape(B)
+        z = torch.randn_like(y) if z is None else z.to(self.device, y.dtype)
+        return t, z
+
+    @torch.inference_mode()
+    def forward(self, x, x_lengths, y, y_lengths, spks=None, out_size=None, cond=None, durations=None, *, t=None, z=None, batched=False):
+        """Reference matcha_tts.py:154-246 without gradients: (dur_loss, prior_loss, diff_loss, attn (B, Tx, Ty)).
+        ``durations`` (B, 1, Tx) or (B, Tx), as under the reference's ``use_precomputed_durations``, replace the search by
+        generate_path.  Extension: keyword-only ``t`` (B,) and ``z`` (B, 80, Ty) replace the draws of compute_loss
+        (flow_matching.py:105-110) for reproducible runs.  ``batched=False``: the estimator runs one row at a time (``ev_estimator``
+        takes one scalar t per call) between torch ops.  ``batched=True``: ``diff_loss`` and ``prior_loss`` come from ONE
+        ``ev_cfm_loss`` call over the batch (one time per utterance inside the U-Net, y_t and u never stored); same 4-tuple."""
+        if out_size is not None:
+            raise NotImplementedError("out_size (the random segment cut of matcha_tts.py:206-231, a training memory hack) is not supported: pass out_size=None")
+        x_lengths, y, y_lengths, spk, mu_x, logw, x_mask = self._encode_pairs(x, x_lengths, y, y_lengths, spks)
+        if batched:
+            return self._forward_batched(x_lengths, y, y_lengths, spk, mu_x, logw, x_mask, durations, t, z)
+        B, _, Ty = y.shape
+        y_mask = sequence_mask(y_lengths, Ty).unsqueeze(1).to(x_mask.dtype)
+        mu_y, attn, logw_ = self._align_pairs(durations, mu_x, logw, x_mask, y, x_lengths, y_lengths)
         # the three reductions accumulate in float64 and round once to the reference's float32 (a few thousand elements each)
-        logw_ = torch.log(1e-8 + tok).unsqueeze(1) * x_mask
         dur_loss = duration_loss(logw.double(), logw_.double(), x_lengths).float()
         n_valid = torch.sum(y_lengths).double() * self.n_feats
         prior_loss = (torch.sum(0.5 * ((y - mu_y).double() ** 2 + math.log(2 * math.pi)) * y_mask) / n_valid).float()
         # compute_loss (flow_matching.py:87-118)
-        t = torch.rand([B], device=self.device, dtype=y.dtype) if t is None else t.to(self.device, y.dtype).reshape(B)
-        z = torch.randn_like(y) if z is None else z.to(self.device, y.dtype)
+        t, z = self._draws(y, t, z)
         tb = t.view(B, 1, 1)
         y_t = (1 - (1 - self.sigma_min) * tb) * z + tb * y
         u = y - (1 - self.sigma_min) * z
@@ -192,6 +237,28 @@ class MatchaTTS:
             v[b:b + 1] = self.engine.estimator(y_t_p[b:b + 1], mu_y_p[b:b + 1], y_lengths[b:b + 1], None if spk is None else spk[b:b + 1], tv)
         diff_loss = (torch.sum((v[:, :, :Ty] - u).double() ** 2) / n_valid).float()
         return dur_loss, prior_loss, diff_loss, attn
+
+    def _forward_batched(self, x_lengths, y, y_lengths, spk, mu_x, logw, x_mask, durations, t, z):
+        """forward(batched=True) after the encoder: the alignment, then one ev_cfm_loss call for both mel-side sums."""
+        mu_y, attn, logw_ = self._align_pairs(durations, mu_x, logw, x_mask, y, x_lengths, y_lengths)
+        t, z = self._draws(y, t, z)
+        sums, _ = self.engine.cfm_loss(y, mu_y, y_lengths, spk, z, t, self.sigma_min)
+        dur_loss, prior_loss, diff_loss = batch_losses(sums, padded_frames_sum(y, z, y_lengths, self.sigma_min), logw, logw_, x_lengths, y_lengths, self.n_feats)
+        return dur_loss.float(), prior_loss.float(), diff_loss.float(), attn
+
+    @torch.inference_mode()
+    def score(self, x, x_lengths, y, y_lengths, spks=None, durations=None, *, t=None, z=None):
+        """The three losses PER UTTERANCE (the number that finds a badly aligned recording), always through ``ev_cfm_loss``:
+        {"dur_loss", "prior_loss", "diff_loss"} each (B,) float32, "attn" (B, Tx, Ty), "durations" (B, Tx) int64.  A row's ``diff_loss``
+        and ``prior_loss`` are its sums over its own y_lengths[b] x 80 cells divided by that count (no padded frame of a longer batch
+        enters), its ``dur_loss`` is sum (logw - logw_)^2 / x_lengths[b].  ``t`` and ``z`` as for ``forward``."""
+        x_lengths, y, y_lengths, spk, mu_x, logw, x_mask = self._encode_pairs(x, x_lengths, y, y_lengths, spks)
+        mu_y, attn, logw_ = self._align_pairs(durations, mu_x, logw, x_mask, y, x_lengths, y_lengths)
+        t, z = self._draws(y, t, z)
+        sums, _ = self.engine.cfm_loss(y, mu_y, y_lengths, spk, z, t, self.sigma_min)
+        out = {k: v.float() for k, v in row_losses(sums, logw, logw_, x_lengths, y_lengths, self.n_feats).items()}
+        out["attn"], out["durations"] = attn, attn.sum(-1).long()
+        return out
 
     __call__ = forward
 

@@ -26,6 +26,8 @@
  *   ev_log_prior       <- the log-likelihood matrix of MatchaTTS.forward                         models/matcha_tts.py:186-193
  *   ev_maximum_path    <- monotonic_align.maximum_path (maximum_path_c / maximum_path_each)      utils/monotonic_align/{__init__.py,core.pyx}
  *   ev_mas_align       <- both, plus attn.sum(-1) and mu_y = attn^T mu_x                          models/matcha_tts.py:186-199, :226-228
+ *   ev_estimator_rows  <- Decoder.forward with t of shape (B,)                                    models/components/decoder.py:363-443
+ *   ev_cfm_loss        <- BASECFM.compute_loss (one time per utterance) + the prior loss's sum        models/components/flow_matching.py:87-118, models/matcha_tts.py:241-242
  *
  * Conventions
  *   - All tensors are fp32.  Pointers named d_* are DEVICE pointers owned by the
@@ -63,7 +65,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -238,6 +240,31 @@ int ev_maximum_path(ev_handle *h, const float *d_value, const int32_t *d_xlen, c
 int ev_log_prior(ev_handle *h, const float *d_mu_x, const float *d_y, int B, int Tx, int Ty, float *d_logp, void *stream);
 int ev_mas_align(ev_handle *h, const float *d_mu_x, const float *d_y, const int32_t *d_xlen, const int32_t *d_ylen, int B, int Tx, int Ty,
                  float *d_attn, int32_t *d_dur, float *d_mu_y, float *d_logp, void *stream);
+
+/* The estimator with one time per utterance, and the flow-matching loss of a batch on top of it: the no-grad validation pass
+ * (MatchaTTS.forward over (text, mel) pairs) at batch speed.  Both are EAGER-ONLY: they copy the B times' sinusoids from the host, and
+ * under stream capture they fail with a message (the staging hazard of "Graph capture" above).  `t` is a HOST pointer to B floats.
+ *   ev_estimator_rows: ev_estimator, utterance b evaluated at t[b] — what Decoder.forward computes for t of shape (B,).  With every
+ *     t[b] equal it agrees with ev_estimator to rounding (the time MLP may run on another build at B rows than at one).
+ *   ev_cfm_loss: compute_loss for given draws, without gradients.
+ *       d_x1 (B, 80, Ty) the target mel      d_mu_y (B, 80, Ty)      d_ylen (B) int32      d_spk (B, 64) or NULL as for ev_cfm_decode
+ *       d_z (B, 80, Ty) unit normal noise    t (B) HOST              Ty >= 1, any value: the call pads to Tp = ceil(Ty / 4) * 4 itself,
+ *                                                                    with masked frames
+ *       d_row_sums (B, 2) float64:  [b][0] = sum (v - u)^2,  [b][1] = sum 0.5 ((x1 - mu_y)^2 + log 2 pi)  over the row's ylen[b] x 80 valid cells
+ *       d_v (B, 80, Ty) or NULL: the estimator's velocity (zeros past a row's length)
+ *     y_t = (1 - (1 - sigma_min) t) z + t x1 and u = x1 - (1 - sigma_min) z are formed in float32 in the reference's operation order,
+ *     and never stored: y_t goes straight into the estimator's input, u is formed where v is read.  The squares accumulate in float64,
+ *     per (row, 32 frames), merged per row in ascending order without atomics: two calls give the same bits.  The batch losses are
+ *     sum_b sums / (sum_b ylen * 80); the caller divides.  (The reference's mse_loss also counts the PADDED frames of shorter rows, where
+ *     v = 0 and u is whatever x1 and z hold there; that term needs no estimator and is the caller's, emojivoice_amd/matcha_tts.py.)
+ *     A row with ylen < 1 or ylen > Ty is no error: its sums and its d_v are zeros.
+ * Both plan one time slot per utterance: B beyond the planned Euler steps (64, or the largest n_steps so far) re-plans the workspace
+ * like a longer decode does, which a handle that holds a captured call refuses.  One such growth moves ev_alloc_count once; a second
+ * call at the same shape allocates nothing. */
+int ev_estimator_rows(ev_handle *h, const float *d_x, const float *d_mu, const int32_t *d_lengths, const float *d_spk,
+                      const float *t /* HOST (B) */, int B, int Tp, float *d_v, void *stream);
+int ev_cfm_loss(ev_handle *h, const float *d_x1, const float *d_mu_y, const int32_t *d_ylen, const float *d_spk, const float *d_z,
+                const float *t /* HOST (B) */, int B, int Ty, float sigma_min, double *d_row_sums, float *d_v, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

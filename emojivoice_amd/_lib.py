@@ -27,6 +27,7 @@ EXPORTS = [
     "ev_load_mel_basis", "ev_mel_spectrogram",
     "ev_maximum_path", "ev_log_prior", "ev_mas_align",
     "ev_estimator_rows", "ev_cfm_loss",
+    "ev_load_resampler", "ev_resample", "ev_mel_stats",
 ]
 
 
@@ -138,6 +139,9 @@ def load_library() -> C.CDLL:
     lib.ev_denoise.argtypes = [vp, vp, i32, i32, vp, f32, vp, vp]
     lib.ev_load_mel_basis.argtypes = [vp, vp, i32, i32]
     lib.ev_mel_spectrogram.argtypes = [vp, vp, i32, i32, f32, f32, vp, vp]
+    lib.ev_load_resampler.argtypes = [vp, vp, i32, i32, i32]
+    lib.ev_resample.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp]
+    lib.ev_mel_stats.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -300,6 +304,40 @@ class Engine:
         self._check(self.lib.ev_mel_spectrogram(self.h, audio.data_ptr(), B, L, float(out_scale), float(out_shift), mel.data_ptr(), _stream_ptr()),
                     "ev_mel_spectrogram")
         return mel
+
+    def load_resampler(self, taps, up: int, down: int) -> None:
+        """The FIR of ``resample`` (ev_load_resampler): ``taps`` (n_taps,) on the host, carrying the gain ``up``; n_taps odd,
+        gcd(up, down) = 1, 1 <= up, down <= 640.  ``audio.resample_filter`` makes scipy's default."""
+        t = np.ascontiguousarray(torch.as_tensor(taps).detach().to("cpu", torch.float32).numpy()).reshape(-1)
+        self._check(self.lib.ev_load_resampler(self.h, t.ctypes.data_as(C.c_void_p), int(t.shape[0]), int(up), int(down)), "ev_load_resampler")
+        self.rs_ratio = (int(up), int(down))
+
+    def resample(self, x, lengths=None):
+        """(B, L) -> (B, ceil(L * up / down)) by the loaded polyphase filter (ev_resample): scipy.signal.resample_poly with zero padding.
+        ``lengths`` (B,): samples per row (None: L); a row's outputs past ceil(len * up / down) are zeros."""
+        x = self._f32(x)
+        if x.dim() != 2:
+            raise ValueError(f"resample: x must be (B, L), got shape {tuple(x.shape)}")
+        B, L = x.shape
+        up, down = getattr(self, "rs_ratio", (1, 1))
+        L_out = -(-L * up // down)
+        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"resample: {B} lengths expected, got {ln.numel()}")
+        y = torch.empty((B, L_out), dtype=torch.float32, device=x.device)
+        self._check(self.lib.ev_resample(self.h, x.data_ptr(), None if ln is None else ln.data_ptr(), B, L, y.data_ptr(), L_out, _stream_ptr()), "ev_resample")
+        return y
+
+    def mel_stats(self, mel, lengths):
+        """(B, 2) float64 on the device: per row sum x and sum x^2 over its lengths[b] x C valid cells of ``mel`` (B, C, T) (ev_mel_stats)."""
+        mel = self._f32(mel)
+        B, Cc, T = mel.shape
+        ln = torch.as_tensor(lengths).to(mel.device, torch.int32).contiguous()
+        if ln.numel() != B:
+            raise ValueError(f"mel_stats: {B} lengths expected, got {ln.numel()}")
+        sums = torch.empty((B, 2), dtype=torch.float64, device=mel.device)
+        self._check(self.lib.ev_mel_stats(self.h, mel.data_ptr(), ln.data_ptr(), B, Cc, T, sums.data_ptr(), _stream_ptr()), "ev_mel_stats")
+        return sums
 
     def maximum_path(self, value, x_lengths, y_lengths, want_path: bool = True, want_dur: bool = True):
         """monotonic_align.maximum_path on (B, Tx, Ty) fp32 scores with per-row lengths (ev_maximum_path): (path (B, Tx, Ty) 0/1 or None,

@@ -6,12 +6,20 @@
 denoiser, then one kernel for magnitude / mel projection / log compression); there is no torch fallback.  The reference takes its
 filter bank from ``librosa.filters.mel``; ``mel_filterbank`` restates that function's defaults (Slaney scale, Slaney normalisation)
 from the published definition.
+
+In front of it, for recordings that are not at 22.05 kHz (the reference's own recorder writes 44.1 kHz, its data module asserts 22050):
+
+    y = load_audio("voice.wav", 22050)                        # any rate, 16 / 24 bit, any channel count -> (1, L) on the GPU
+    y = resample(y, 44100, 22050)                             # (B, L) on the GPU -> (B, ceil(L / 2)): ev_resample, scipy's resample_poly
+
+and behind it ``data_statistics``: the mel_mean / mel_std a fine-tuning config needs (utils/generate_data_statistics.py), reduced on the
+device by ``ev_mel_stats``.
 """
 from __future__ import annotations
 
 import math
 import wave
-from typing import Dict, Optional, Tuple
+from typing import Callable, Dict, Iterable, Optional, Tuple
 
 import numpy as np
 import torch
@@ -138,3 +146,126 @@ def read_wav_pcm(path, sr: int = 22050) -> np.ndarray:
         q = q.reshape(-1).view("<i4") >> 8
         return (q.astype(np.float64) / (2**23 - 1)).astype(np.float32)
     raise ValueError(f"{path}: {8 * width}-bit samples (16- or 24-bit PCM only)")
+
+
+def read_wav(path) -> Tuple[np.ndarray, int]:
+    """(float32 samples in [-1, 1), rate) of a 16- or 24-bit PCM wav at ANY rate; several channels are averaged in float64.  The
+    sample scaling is ``read_wav_pcm``'s (q / 32768, q / (2**23 - 1))."""
+    with wave.open(str(path), "rb") as f:
+        ch, rate, width, raw = f.getnchannels(), f.getframerate(), f.getsampwidth(), f.readframes(f.getnframes())
+    if width == 2:
+        q = np.frombuffer(raw, dtype="<i2").astype(np.float64) / 32768.0
+    elif width == 3:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3)
+        w = np.zeros((b.shape[0], 4), dtype=np.uint8)
+        w[:, 1:] = b                                              # into the top three bytes: the shift back sign-extends
+        q = (w.reshape(-1).view("<i4") >> 8).astype(np.float64) / (2**23 - 1)
+    else:
+        raise ValueError(f"{path}: {8 * width}-bit samples (16- or 24-bit PCM only)")
+    if ch > 1:
+        q = q.reshape(-1, ch).mean(axis=1)
+    return q.astype(np.float32), int(rate)
+
+
+def resample_ratio(orig_sr: int, new_sr: int) -> Tuple[int, int]:
+    """(up, down) of a conversion orig_sr -> new_sr: the rates over their gcd (44100 -> 22050: (1, 2); 48000 -> 22050: (147, 320))."""
+    orig_sr, new_sr = int(orig_sr), int(new_sr)
+    if orig_sr < 1 or new_sr < 1:
+        raise ValueError(f"resample: sample rates must be positive (got {orig_sr} -> {new_sr})")
+    g = math.gcd(orig_sr, new_sr)
+    return new_sr // g, orig_sr // g
+
+
+def resample_filter(up: int, down: int, zeros: int = 10, beta: float = 5.0) -> np.ndarray:
+    """The low-pass of ``scipy.signal.resample_poly(x, up, down)`` restated: with m = max(up, down), 2 * zeros * m + 1 taps
+    sinc(n / m) / m * kaiser(beta) for n = -zeros * m .. zeros * m, normalised to unit sum, times ``up``
+    (= ``firwin(2 * zeros * m + 1, 1 / m, window=("kaiser", beta)) * up``; zeros = 10 and beta = 5.0 are scipy's defaults).  Computed in
+    float64, rounded once to float32."""
+    return _resample_filter64(up, down, zeros, beta).astype(np.float32)
+
+
+def _resample_filter64(up: int, down: int, zeros: int = 10, beta: float = 5.0) -> np.ndarray:
+    m = max(int(up), int(down))
+    half = int(zeros) * m
+    n = np.arange(-half, half + 1, dtype=np.float64)
+    h = np.sinc(n / m) / m * np.kaiser(2 * half + 1, float(beta))
+    return h / h.sum() * up
+
+
+# (device index, up, down, zeros, beta) -> Engine with that filter loaded; (device index, "stats") -> the Engine of data_statistics
+_rs_engines: Dict[Tuple, Engine] = {}
+
+
+def _resampler_for(device: torch.device, up: int, down: int, zeros: int, beta: float) -> Engine:
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, int(up), int(down), int(zeros), float(beta))
+    eng = _rs_engines.get(key)
+    if eng is None:
+        eng = Engine(idx)
+        eng.load_resampler(resample_filter(up, down, zeros, beta), up, down)
+        _rs_engines[key] = eng
+    return eng
+
+
+@torch.inference_mode()
+def resample(y, orig_sr: int, new_sr: int, lengths=None, zeros: int = 10, beta: float = 5.0):
+    """``y`` (B, L) on the GPU at ``orig_sr`` -> (B, ceil(L * up / down)) at ``new_sr``, up / down the rates over their gcd: what
+    ``scipy.signal.resample_poly(y, up, down, axis=-1)`` computes (zero padding, its default Kaiser filter for zeros = 10, beta = 5.0),
+    in the HIP library (``ev_resample``; no torch fallback).  ``lengths`` (B,): samples per row of a padded batch; the outputs past
+    ceil(len * up / down) are zeros.  ``orig_sr == new_sr`` returns ``y`` itself.  The filter and the native handle are cached per
+    (device, up, down, zeros, beta); a ratio outside 1 <= up, down <= 640 raises ``EvLibraryError``."""
+    if int(orig_sr) == int(new_sr):
+        return y
+    up, down = resample_ratio(orig_sr, new_sr)
+    if y.dim() != 2:
+        raise ValueError(f"resample: y must be (B, L), got shape {tuple(y.shape)}")
+    if not y.is_cuda:
+        raise EvLibraryError("resample runs on a ROCm GPU only (no CPU fallback): move y to the GPU")
+    return _resampler_for(y.device, up, down, zeros, beta).resample(y, lengths)
+
+
+def load_audio(path, sr: int = 22050, device="cuda"):
+    """A wav at any rate (``read_wav``) as a (1, L) float32 tensor on ``device`` at ``sr``, resampled on the device when the file's
+    rate differs."""
+    y, rate = read_wav(path)
+    return resample(torch.from_numpy(y).to(device).unsqueeze(0), rate, sr)
+
+
+def statistics_from_sums(sum_x: float, sum_x2: float, total_len: int, n_feats: int) -> Dict[str, float]:
+    """compute_data_statistics' last two lines (utils/generate_data_statistics.py:44-45) in Python float64."""
+    n = float(total_len) * float(n_feats)
+    mean = float(sum_x) / n
+    return {"mel_mean": mean, "mel_std": math.sqrt(float(sum_x2) / n - mean * mean)}
+
+
+def _device_row_sums(mel, lengths) -> np.ndarray:
+    if not mel.is_cuda:
+        raise EvLibraryError("data_statistics runs on a ROCm GPU only (no CPU fallback): move the mels to the GPU")
+    idx = mel.device.index if mel.device.index is not None else torch.cuda.current_device()
+    eng = _rs_engines.get((idx, "stats"))
+    if eng is None:
+        eng = _rs_engines[(idx, "stats")] = Engine(idx)
+    return eng.mel_stats(mel, lengths).cpu().numpy()
+
+
+def data_statistics(batches: Iterable, n_feats: int = 80, row_sums: Optional[Callable] = None) -> Dict[str, float]:
+    """``compute_data_statistics`` (utils/generate_data_statistics.py:25-47) over ``batches``, an iterable of (mel (B, n_feats, T) on
+    the GPU, lengths (B,)): {"mel_mean": sum x / (sum len * n_feats), "mel_std": sqrt(sum x^2 / (sum len * n_feats) - mean^2)}.  Each
+    batch is reduced on the device to per-row float64 sums over the valid cells (``ev_mel_stats``; the reference sums the zero padding
+    too, which adds nothing); rows and batches are combined here in Python float64 (``math.fsum``).  ``row_sums``: the per-batch
+    reduction, (mel, lengths) -> (B, 2) float64 array — the device call unless given."""
+    reduce = row_sums or _device_row_sums
+    sx, sx2, total = [], [], 0
+    for mel, lengths in batches:
+        if mel.shape[1] != n_feats:
+            raise ValueError(f"data_statistics: mel has {mel.shape[1]} channels, n_feats is {n_feats}")
+        ln = [int(v) for v in np.asarray(torch.as_tensor(lengths).cpu()).reshape(-1)]
+        if any(v < 1 or v > mel.shape[2] for v in ln):
+            raise ValueError(f"data_statistics: lengths must be 1..{mel.shape[2]} (got {ln})")
+        s = np.asarray(reduce(mel, lengths), dtype=np.float64)
+        sx.extend(s[:, 0].tolist())
+        sx2.extend(s[:, 1].tolist())
+        total += sum(ln)
+    if total == 0:
+        raise ValueError("data_statistics: no frames")
+    return statistics_from_sums(math.fsum(sx), math.fsum(sx2), total, n_feats)

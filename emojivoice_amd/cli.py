@@ -10,6 +10,11 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --mel_from_wav voice.wav [--vocoder_path g_02500000 | --synthetic]     # analysis: voice.wav.mel.npy (+ copy synthesis)
     python -m emojivoice_amd.cli --checkpoint_path model.ckpt --align_wav voice.wav --phonemes "həlˈoʊ" --spk 12   # voice.wav.durations.npy
     python -m emojivoice_amd.cli --checkpoint_path model.ckpt --align_wav voice.wav --phonemes "həlˈoʊ" --spk 12 --losses   # + voice.wav.losses.json
+    python -m emojivoice_amd.cli --data_statistics train.txt --batch_size 32                            # train.txt.stats.json: mel_mean / mel_std
+    python -m emojivoice_amd.cli --synthetic --ids "0 23 0 51 0" --sample_rate 44100                    # wavs at 44.1 kHz
+
+The wavs of --mel_from_wav, --align_wav and --data_statistics may have any sample rate (the reference's recorder writes 44.1 kHz,
+record_audio.py:31): they are resampled to the analysis rate on the device (emojivoice_amd.audio.resample).
 """
 from __future__ import annotations
 
@@ -40,7 +45,12 @@ def write_wav_pcm24(path, wav: np.ndarray, sr: int = 22050):
 
 
 def validate_args(args):
+    if args.sample_rate is not None:
+        assert args.sample_rate > 0, "--sample_rate must be positive"
     if args.mel_from_wav:
+        return args
+    if args.data_statistics:
+        assert args.batch_size > 0, "Batch size must be greater than 0"
         return args
     if args.align_mel or args.align_wav:
         assert not (args.align_mel and args.align_wav), "--align_mel and --align_wav exclude each other"
@@ -125,21 +135,32 @@ def parse_lines(args):
     return out
 
 
+def wav_at_rate(path, sr: int, device):
+    """The wav at ``path`` (any rate, 16 / 24 bit PCM, channels averaged) as a (1, n) tensor on the device at ``sr``, trimmed to a
+    multiple of 256 samples; None when fewer than 512 are left.  Prints the file's rate."""
+    from .audio import read_wav, resample
+
+    y, rate = read_wav(path)
+    print(f"[i] {path}: {rate} Hz, {len(y)} samples" + ("" if rate == sr else f" -> resampled to {sr} Hz on the device"))
+    y = resample(torch.from_numpy(y).to(device).unsqueeze(0), rate, sr)
+    n = y.shape[1] // 256 * 256
+    return y[:, :n].contiguous() if n > 384 else None
+
+
 @torch.inference_mode()
 def mel_from_wav(args, device):
-    """--mel_from_wav: PATH (22.05 kHz mono PCM, 16 / 24 bit) -> PATH.mel.npy (80, frames) with the analysis parameters of the
+    """--mel_from_wav: PATH (PCM at any rate, 16 / 24 bit; resampled on the device to the config's rate) -> PATH.mel.npy (80, frames) with the analysis parameters of the
     vocoder config (hifigan/meldataset.py:52 as text_mel_datamodule.py:202 calls it), the signal trimmed to a multiple of 256
     samples; with vocoder weights also PATH.copysyn.wav, the vocoder's rendering of that mel (copy synthesis)."""
     from . import weights as W
-    from .audio import mel_spectrogram, read_wav_pcm
+    from .audio import mel_spectrogram
     from .hifigan import AttrDict, Generator
 
     h = AttrDict(vocoder_config(args.vocoder_config))
-    y = read_wav_pcm(args.mel_from_wav, int(h.get("sampling_rate", 22050)))
-    n = len(y) // 256 * 256
-    if n <= 384:
-        sys.exit(f"[-] {args.mel_from_wav}: {len(y)} samples, at least 512 are needed")
-    y = torch.from_numpy(y[:n].copy()).to(device).unsqueeze(0)
+    y = wav_at_rate(args.mel_from_wav, int(h.get("sampling_rate", 22050)), device)
+    if y is None:
+        sys.exit(f"[-] {args.mel_from_wav}: at least 512 samples at {int(h.get('sampling_rate', 22050))} Hz are needed")
+    n = y.shape[1]
     mel = mel_spectrogram(y, h.get("n_fft", 1024), h.get("num_mels", 80), h.get("sampling_rate", 22050), h.get("hop_size", 256),
                           h.get("win_size", 1024), h.get("fmin", 0), h.get("fmax", 8000))
     out = f"{args.mel_from_wav}.mel.npy"
@@ -165,7 +186,7 @@ def align_durations(args, device):
     utils/get_durations_from_trained_model.py saves per file.  With --losses also <input>.losses.json: the utterance's dur_loss,
     prior_loss and diff_loss of MatchaTTS.score, the time and the noise of the flow-matching loss drawn on the CPU from --seed."""
     from . import weights as W
-    from .audio import mel_spectrogram, read_wav_pcm
+    from .audio import mel_spectrogram
     from .matcha_tts import MatchaTTS
 
     model = MatchaTTS(W.synthetic_matcha_state(), device=device) if args.synthetic else MatchaTTS.load_from_checkpoint(args.checkpoint_path, map_location=device)
@@ -173,11 +194,10 @@ def align_durations(args, device):
     if args.align_mel:
         mel = torch.from_numpy(np.load(src).astype(np.float32)).to(device).reshape(1, model.n_feats, -1)
     else:
-        y = read_wav_pcm(src, 22050)
-        n = len(y) // 256 * 256
-        if n <= 384:
-            sys.exit(f"[-] {src}: {len(y)} samples, at least 512 are needed")
-        mel = mel_spectrogram(torch.from_numpy(y[:n].copy()).to(device).unsqueeze(0), 1024, model.n_feats, 22050, 256, 1024, 0, 8000,
+        y = wav_at_rate(src, 22050, device)
+        if y is None:
+            sys.exit(f"[-] {src}: at least 512 samples at 22050 Hz are needed")
+        mel = mel_spectrogram(y, 1024, model.n_feats, 22050, 256, 1024, 0, 8000,
                               out_scale=1.0 / model.mel_std, out_shift=-model.mel_mean / model.mel_std)
     ids, spk = parse_lines(args)[0]
     x = torch.tensor([ids], dtype=torch.long, device=device)
@@ -197,6 +217,43 @@ def align_durations(args, device):
         with open(f"{src}.losses.json", "w") as f:
             json.dump(rec, f, indent=1)
         print(f"[+] Losses saved: {Path(f'{src}.losses.json').resolve()}  (dur {rec['dur_loss']:.4f}  prior {rec['prior_loss']:.4f}  diff {rec['diff_loss']:.4f})")
+
+
+@torch.inference_mode()
+def data_statistics(args, device):
+    """--data_statistics FILELIST: the first '|'-separated field of each line is a wav path, as in the reference's filelists
+    (data/text_mel_datamodule.py:96-99; relative paths are taken from the filelist's folder when they do not exist as given).  The
+    mels are those of --mel_from_wav, reduced --batch_size files at a time (padded to the longest); FILELIST.stats.json receives
+    {"mel_mean", "mel_std"}, the content utils/generate_data_statistics.py writes."""
+    from . import audio
+    from .hifigan import AttrDict
+
+    h = AttrDict(vocoder_config(args.vocoder_config))
+    sr, n_mels = int(h.get("sampling_rate", 22050)), int(h.get("num_mels", 80))
+    flist = Path(args.data_statistics)
+    paths = [ln.split("|")[0].strip() for ln in flist.read_text(encoding="utf-8").splitlines() if ln.strip()]
+    paths = [p if os.path.exists(p) else str(flist.parent / p) for p in paths]
+    if not paths:
+        sys.exit(f"[-] {flist}: no files listed")
+
+    def batches():
+        for b0 in range(0, len(paths), args.batch_size):
+            wavs = [wav_at_rate(p, sr, device) for p in paths[b0:b0 + args.batch_size]]
+            wavs = [w for w in wavs if w is not None]             # (files under 512 samples give no frame)
+            if not wavs:
+                continue
+            mels = [audio.mel_spectrogram(w, h.get("n_fft", 1024), n_mels, sr, h.get("hop_size", 256), h.get("win_size", 1024), h.get("fmin", 0),
+                                          h.get("fmax", 8000)) for w in wavs]     # per file: each signal's own reflect padding
+            mel = torch.zeros(len(mels), n_mels, max(m.shape[2] for m in mels), device=device)
+            for r, m in enumerate(mels):
+                mel[r, :, : m.shape[2]] = m[0]
+            yield mel, torch.tensor([m.shape[2] for m in mels])
+
+    stats = audio.data_statistics(batches(), n_mels)
+    out = f"{flist}.stats.json"
+    with open(out, "w") as f:
+        json.dump(stats, f)
+    print(f"[+] Data statistics saved: {Path(out).resolve()}  ({len(paths)} files: mel_mean {stats['mel_mean']:.6f}  mel_std {stats['mel_std']:.6f})")
 
 
 def loss_draws(seed: int, n_feats: int, frames: int):
@@ -228,14 +285,18 @@ def cli(argv=None):
     p.add_argument("--output_folder", type=str, default=os.getcwd())
     p.add_argument("--batched", action="store_true")
     p.add_argument("--batch_size", type=int, default=32)
-    p.add_argument("--mel_from_wav", type=str, default=None, help="analysis instead of synthesis: a 22.05 kHz mono PCM wav (16 / 24 bit) -> PATH.mel.npy; "
+    p.add_argument("--mel_from_wav", type=str, default=None, help="analysis instead of synthesis: a PCM wav (16 / 24 bit, any rate: resampled on the device) -> PATH.mel.npy; "
                    "with --vocoder_path or --synthetic also PATH.copysyn.wav (copy synthesis)")
     p.add_argument("--align_mel", type=str, default=None, help="alignment instead of synthesis: a normalised mel (80, frames) .npy of the utterance "
                    "given by --ids / --phonemes -> PATH.durations.npy (monotonic alignment search, Tx integers)")
-    p.add_argument("--align_wav", type=str, default=None, help="the same from a 22.05 kHz mono PCM wav, analysed as --mel_from_wav does and normalised")
+    p.add_argument("--align_wav", type=str, default=None, help="the same from a PCM wav at any rate, analysed as --mel_from_wav does and normalised")
     p.add_argument("--losses", action="store_true", help="with --align_mel / --align_wav: also PATH.losses.json, the utterance's dur_loss, prior_loss and "
                    "diff_loss (MatchaTTS.score); the loss's time and noise are drawn from --seed")
     p.add_argument("--seed", type=int, default=0, help="seed of the draws of --losses")
+    p.add_argument("--data_statistics", type=str, default=None, help="dataset statistics instead of synthesis: a filelist whose first '|'-separated field "
+                   "per line is a wav path -> FILELIST.stats.json with mel_mean / mel_std (--batch_size files per batch)")
+    p.add_argument("--sample_rate", type=int, default=None, help="write the synthesised wavs at this rate (resampled on the device from 22050 Hz); "
+                   "omitted: 22050 Hz, untouched")
     args = validate_args(p.parse_args(argv))
     if args.align_mel or args.align_wav:
         if not torch.cuda.is_available():
@@ -245,6 +306,10 @@ def cli(argv=None):
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
         return mel_from_wav(args, torch.device("cuda", 0))
+    if args.data_statistics:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return data_statistics(args, torch.device("cuda", 0))
     if not args.synthetic:
         assert args.checkpoint_path and args.vocoder_path, "--checkpoint_path and --vocoder_path are required (or --synthetic)"
     if not torch.cuda.is_available():
@@ -285,7 +350,13 @@ def cli(argv=None):
             n = int(out["mel_lengths"][r])
             name = f"utterance_{b0 + r + 1:03d}_speaker_{int(spks[r]):03d}"
             np.save(folder / name, out["mel"][r, :, :n].cpu().numpy())
-            write_wav_pcm24(folder / f"{name}.wav", wav[r, : n * 256].numpy())
+            if args.sample_rate is None or args.sample_rate == 22050:
+                write_wav_pcm24(folder / f"{name}.wav", wav[r, : n * 256].numpy())
+            else:
+                from .audio import resample
+
+                out_wav = resample(wav[r, : n * 256].to(device).unsqueeze(0), 22050, args.sample_rate)[0].cpu().numpy()
+                write_wav_pcm24(folder / f"{name}.wav", out_wav, sr=args.sample_rate)
             print(f"[+] Waveform saved: {(folder / (name + '.wav')).resolve()}  ({n * 256 / 22050:.2f} s)")
     print(f"[avg] Matcha-TTS + VOCODER RTF: {np.mean(rtfs):.4f} ± {np.std(rtfs):.4f}")
 

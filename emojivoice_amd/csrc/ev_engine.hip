@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -119,6 +120,8 @@ struct DenoiserW { bool ready = false; ConvLayer fwd, inv; float* win2 = nullptr
 
 // Mel filter bank of ev_mel_spectrogram: per filter {first bin, count, offset into wts} and the weights of those spans only
 struct MelBasisW { bool loaded = false; int n_mels = 0, nb = 0; int* span = nullptr; float* wts = nullptr; };
+// Filter of ev_resample: the taps re-laid phase-major [up][Wp], W = ceil(n_taps / up) taps per phase, row stride Wp = W | 1, zero-padded
+struct ResamplerW { bool loaded = false; int up = 0, down = 0, n_taps = 0, W = 0, Wp = 0, tab_floats = 0; float* table = nullptr; };
 
 }  // namespace
 
@@ -132,9 +135,11 @@ struct ev_handle {
     TextEncW enc;
     DenoiserW dn;
     MelBasisW melb;
+    ResamplerW rs;
     // small per-stage scratch arenas (denoiser, text encoder): grown on demand, ordered against their last user's stream
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
     Scratch dn_ws, enc_ws, mas_ws;   // (mas_ws: the alignment search's frame -> token index and, for large Tx * Ty, its decision bits)
+    Scratch stat_ws;                 // ev_mel_stats: the per-(row, 32 frames) partial sums
     float* zeros = nullptr;     // 4096 zero floats (stand-in bias for the fused kernels' unconditional loads)
     int max_steps = 64;         // Euler steps the time-grid buffers of the workspace are planned for (grows on demand)
     int* bad_ids_host = nullptr; int* bad_ids_dev = nullptr;   // mapped host word: count of out-of-range token ids seen by ev_text_encoder
@@ -1977,6 +1982,7 @@ void ev_destroy(ev_handle* h) {
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
     if (h->enc_ws.p) hipFree(h->enc_ws.p);
     if (h->mas_ws.p) hipFree(h->mas_ws.p);
+    if (h->stat_ws.p) hipFree(h->stat_ws.p);
     if (h->dn_ws.p) hipFree(h->dn_ws.p);
     if (h->bad_ids_host) hipHostFree(h->bad_ids_host);
     for (int i = 0; i < 2; ++i) { if (h->temb_ev[i]) hipEventDestroy(h->temb_ev[i]); if (h->temb_host[i]) hipHostFree(h->temb_host[i]); }
@@ -2736,6 +2742,81 @@ int ev_mel_spectrogram(ev_handle* h, const float* d_audio, int B, int L, float o
     if ((double)B * (L / 256 + 12) * 1032 * 4.0 >= 4294967296.0) return fail(h, "audio batch exceeds the 4 GiB buffer-addressing limit: split the batch");
     h->stream = (hipStream_t)stream;
     return run_mel(h, d_audio, B, L, out_scale, out_shift, d_mel);
+}
+
+// The resampler.  LDS budget of a launch: 64 KiB (16384 floats) for the phase table and the input span together, so that at least two
+// workgroups share a CU and no launch needs a raised LDS grant.  Plan: 1024 outputs per workgroup while their input span fits the budget,
+// else 256, else the span is not staged at all (the kernel reads x from global memory: filters of tens of thousands of taps per phase);
+// the table is staged when it fits beside the span, else read from global memory (L2-resident: at most 66 K floats).
+int ev_load_resampler(ev_handle* h, const float* taps, int n_taps, int up, int down) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!taps) return fail(h, "ev_load_resampler: null taps");
+    if (up < 1 || up > 640 || down < 1 || down > 640) return fail(h, "ev_load_resampler: up=%d down=%d outside 1 <= up, down <= 640", up, down);
+    if (std::gcd(up, down) != 1) return fail(h, "ev_load_resampler: gcd(up, down) must be 1 (up=%d down=%d: reduce the ratio)", up, down);
+    if (n_taps < 1 || n_taps > 65537 || !(n_taps & 1)) return fail(h, "ev_load_resampler: n_taps=%d must be odd and <= 65537", n_taps);
+    ResamplerW r;
+    r.up = up; r.down = down; r.n_taps = n_taps;
+    r.W = (n_taps + up - 1) / up; r.Wp = r.W | 1; r.tab_floats = round_up(up * r.Wp, 4);
+    std::vector<float> tab((size_t)r.tab_floats, 0.f);
+    for (int k = 0; k < n_taps; ++k) tab[(size_t)(k % up) * r.Wp + k / up] = taps[k];
+    ResamplerW& cur = h->rs;
+    if (cur.loaded) {                       // replace: nothing in flight may still read the old table
+        HIPCHK(h, hipDeviceSynchronize());
+        auto it = std::find(h->owned.begin(), h->owned.end(), (void*)cur.table);
+        if (it != h->owned.end()) { h->owned.erase(it); hipFree(cur.table); }
+        cur = ResamplerW();
+    }
+    if (dev_upload(h, tab, &r.table)) return 1;
+    r.loaded = true;
+    cur = r;
+    return 0;
+}
+
+int ev_resample(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L_in, float* d_y, int L_out, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    const ResamplerW& r = h->rs;
+    if (!r.loaded) return fail(h, "resampler not loaded (ev_load_resampler)");
+    if (B < 1 || B > 65535) return fail(h, "ev_resample: B=%d outside 1 <= B <= 65535", B);
+    if (L_in < 1 || !d_x || !d_y) return fail(h, "ev_resample: bad arguments L_in=%d (L_in >= 1, non-null tensors)", L_in);
+    const long long want = ((long long)L_in * r.up + r.down - 1) / r.down;
+    if (want > 2147483647LL || (long long)L_out != want)
+        return fail(h, "ev_resample: L_out=%d must be ceil(L_in * up / down) = %lld (L_in=%d up=%d down=%d) and fit 31 bits", L_out, want, L_in, r.up, r.down);
+    h->stream = (hipStream_t)stream;
+    constexpr int BUDGET = 16384;           // floats of LDS per workgroup
+    auto span_of = [&](int tile) { return (long long)r.W + ((long long)(r.up - 1) + (long long)(tile - 1) * r.down) / r.up; };
+    int tile = 1024;
+    bool sx = true;
+    if (span_of(1024) > BUDGET) { tile = 256; sx = span_of(256) <= BUDGET; }
+    const int span = sx ? (int)span_of(tile) : 0;
+    const bool st = span + r.tab_floats <= BUDGET;
+    ResampleParams p{};
+    p.x = d_x; p.len = d_len; p.y = d_y; p.table = r.table;
+    p.L_in = L_in; p.L_out = L_out; p.up = r.up; p.down = r.down; p.c = (r.n_taps - 1) / 2; p.W = r.W; p.Wp = r.Wp; p.span = span; p.tab_floats = r.tab_floats;
+    const size_t smem = ((size_t)span + (st ? r.tab_floats : 0)) * sizeof(float);
+    const dim3 grid((unsigned)((L_out + tile - 1) / tile), (unsigned)B);
+    hipStream_t s = h->stream;
+    if (tile == 1024) { if (st) launch<resample_kernel<1024, true, true>>(h->device, grid, dim3(256), smem, s, p); else launch<resample_kernel<1024, true, false>>(h->device, grid, dim3(256), smem, s, p); }
+    else if (sx)      { if (st) launch<resample_kernel<256, true, true>>(h->device, grid, dim3(256), smem, s, p);  else launch<resample_kernel<256, true, false>>(h->device, grid, dim3(256), smem, s, p); }
+    else              { if (st) launch<resample_kernel<256, false, true>>(h->device, grid, dim3(256), smem, s, p); else launch<resample_kernel<256, false, false>>(h->device, grid, dim3(256), smem, s, p); }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int ev_mel_stats(ev_handle* h, const float* d_mel, const int32_t* d_len, int B, int C, int T, double* d_row_sums, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (B < 1 || B > 65535 || C < 1 || T < 1 || !d_mel || !d_len || !d_row_sums)
+        return fail(h, "ev_mel_stats: bad arguments B=%d C=%d T=%d (1 <= B <= 65535, C >= 1, T >= 1, non-null tensors)", B, C, T);
+    h->stream = (hipStream_t)stream;
+    const int ntiles = (T + 31) / 32;
+    if (scratch_acquire(h, h->stat_ws, (size_t)B * ntiles * 2 * sizeof(double))) return 1;
+    double* part = (double*)h->stat_ws.p;
+    hipLaunchKernelGGL(mel_stats_kernel, dim3(ntiles, B), dim3(256), 0, h->stream, d_mel, d_len, C, T, part, ntiles);
+    hipLaunchKernelGGL(cfm_loss_merge_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, (const double*)part, ntiles, B, d_row_sums);
+    HIPCHK(h, hipGetLastError());
+    return 0;
 }
 
 int ev_hifigan(ev_handle* h, const float* d_mel, int B, int T, float* d_wav, void* stream) {

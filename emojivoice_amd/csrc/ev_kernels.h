@@ -6339,6 +6339,116 @@ __global__ void cfm_loss_merge_kernel(const double* part, int ntiles, int B, dou
     out[2 * b] = sd; out[2 * b + 1] = sp;
 }
 
+// Dataset statistics of ev_mel_stats: sum x and sum x^2 in float64 over the row's len[b] x C valid cells of a (B, C, T) mel.  One workgroup
+// per (row, 32 frames), lane = frame (32 consecutive floats of one channel row per half-wave), the eight half-waves walk the channels; the
+// same fixed shuffle tree and wave order as cfm_loss_kernel, the same per-row merge (cfm_loss_merge_kernel): no atomics.
+__global__ __launch_bounds__(256) void mel_stats_kernel(const float* __restrict__ mel, const int32_t* __restrict__ len, int C, int T,
+                                                         double* part, int ntiles) {
+    __shared__ double red[4][2];
+    const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const int t = tile * 32 + (tid & 31);
+    const int valid = cfm_valid_len(len[b], T);
+    double s1 = 0.0, s2 = 0.0;
+    if (t < valid) {
+        for (int c = tid >> 5; c < C; c += 8) {
+            const double v = (double)mel[((size_t)b * C + c) * T + t];
+            s1 += v;
+            s2 += v * v;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_down(s1, o); s2 += __shfl_down(s2, o); }
+    if ((tid & 63) == 0) { red[tid >> 6][0] = s1; red[tid >> 6][1] = s2; }
+    __syncthreads();
+    if (tid == 0) {
+        double* o = part + ((size_t)b * ntiles + tile) * 2;
+        o[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+        o[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Rational polyphase FIR resampler (ev_resample):  y[n] = sum_i x[i] taps[n down - i up + c],  c = (n_taps - 1) / 2,  x zero outside [0, len).
+// With q = n down + c, phase ph = q mod up and i0 = q / up the sum is  sum_{j = 0}^{W - 1} table[ph][j] x[i0 - j],  W = ceil(n_taps / up),
+// table[ph][j] = taps[ph + j up] (zero beyond n_taps; row stride Wp = W | 1, so the rows of different phases start on different LDS banks).
+// ARITHMETIC: one fp32 fmaf chain per output, acc = fmaf(table[ph][j], x[i0 - j], acc) for j = 0, 1, ... W - 1 from acc = +0, all W terms
+// always (a sample outside the row enters as +0 and leaves acc as it is).  The chain depends on (n, taps, the row's samples) only: not on the
+// tile, the batch or the padding behind the row.
+// One workgroup owns TILE consecutive outputs of one row (thread t: outputs t, t + 256, ...: coalesced stores).  64-bit arithmetic fixes the
+// tile's origin (q0 = n0 down + c, base_i = q0 / up, r0 = q0 mod up: n down and i up pass 2^31 for minutes of audio); inside the tile
+// everything is a 32-bit offset from it (r0 + t down <= 639 + 1023 * 640).  SX: the input span the tile reads, x[base_i - (W - 1) ..
+// base_i + (r0 + (TILE - 1) down) / up], is staged into LDS by coalesced loads (zeros outside the row); ST: so is the whole phase table
+// (16-byte copies).  Without SX / ST the kernel reads x / the table from global memory (the fallbacks of filters too long for the budget).
+// dynamic LDS: [ST: tab_floats] [SX: span] floats.
+struct ResampleParams {
+    const float* x; const int32_t* len; float* y; const float* table;
+    int L_in, L_out, up, down, c, W, Wp, span, tab_floats;
+};
+
+template <int TILE, bool SX, bool ST>
+__global__ __launch_bounds__(256) void resample_kernel(const ResampleParams p) {
+    extern __shared__ __attribute__((aligned(16))) float rs_sm[];
+    constexpr int PER = TILE / 256;
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const long long n0 = (long long)blockIdx.x * TILE;
+    int len = p.len ? p.len[b] : p.L_in;
+    if (len < 1 || len > p.L_in) len = 0;                                   // a bad row is a row of zeros (the ev_mas_align convention)
+    const long long lout = ((long long)len * p.up + p.down - 1) / p.down;   // outputs the row has: beyond them zeros
+    float* yrow = p.y + (size_t)b * p.L_out;
+    if (n0 >= lout) {                                                       // (uniform over the workgroup)
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const long long n = n0 + tid + 256 * k;
+            if (n < p.L_out) yrow[n] = 0.f;
+        }
+        return;
+    }
+    const long long q0 = n0 * p.down + p.c;
+    const long long base_i = q0 / p.up;
+    const int r0 = (int)(q0 - base_i * p.up);
+    const long long span_base = base_i - (p.W - 1);
+    const float* xrow = p.x + (size_t)b * p.L_in;
+    float* xs = rs_sm + (ST ? p.tab_floats : 0);
+    if (ST) {
+        for (int i = tid; i < p.tab_floats / 4; i += 256) ((f32x4*)rs_sm)[i] = ((const f32x4*)p.table)[i];
+    }
+    if (SX) {
+        for (int s = tid; s < p.span; s += 256) {
+            const long long gi = span_base + s;
+            xs[s] = (gi >= 0 && gi < len) ? xrow[gi] : 0.f;
+        }
+    }
+    if (SX || ST) __syncthreads();
+    const float* trow[PER];
+    int so[PER];
+    float acc[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int v = r0 + (tid + 256 * k) * p.down;
+        const int di = v / p.up, ph = v - di * p.up;
+        trow[k] = (ST ? (const float*)rs_sm : p.table) + ph * p.Wp;
+        so[k] = di + p.W - 1;                                               // x[i0] sits at xs[so]; tap j reads xs[so - j]
+        acc[k] = 0.f;
+    }
+    for (int j = 0; j < p.W; ++j) {
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            float xv;
+            if (SX) xv = xs[so[k] - j];
+            else {
+                const long long gi = span_base + so[k] - j;
+                xv = (gi >= 0 && gi < len) ? xrow[gi] : 0.f;
+            }
+            acc[k] = fmaf(trow[k][j], xv, acc[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const long long n = n0 + tid + 256 * k;
+        if (n < p.L_out) yrow[n] = n < lout ? acc[k] : 0.f;
+    }
+}
+
 // broadcast a per-utterance vector (B, C) over all valid frames: dst[n][c0 + c] = v[b][c] * rowmask[n]
 __global__ void bcast_rows_kernel(const float* v, float* dst, int ld, int c0, int C, int nrows, int S, int P, int T,
                                   const float* rowmask) {

@@ -28,6 +28,10 @@
  *   ev_mas_align       <- both, plus attn.sum(-1) and mu_y = attn^T mu_x                          models/matcha_tts.py:186-199, :226-228
  *   ev_estimator_rows  <- Decoder.forward with t of shape (B,)                                    models/components/decoder.py:363-443
  *   ev_cfm_loss        <- BASECFM.compute_loss (one time per utterance) + the prior loss's sum        models/components/flow_matching.py:87-118, models/matcha_tts.py:241-242
+ *   ev_mel_stats       <- compute_data_statistics (sum x, sum x^2 per utterance)                  utils/generate_data_statistics.py:25-47
+ *   ev_resample        <- no counterpart: the reference asks for 22050 Hz files (README.md:156: fine-tuning audio "must be 22050",
+ *                       data/text_mel_datamodule.py:201 asserts it) while its own recorder writes 44.1 kHz ones (record_audio.py:31)
+ *   ev_load_resampler  <- no counterpart (the filter of ev_resample)
  *
  * Conventions
  *   - All tensors are fp32.  Pointers named d_* are DEVICE pointers owned by the
@@ -65,7 +69,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -265,6 +269,37 @@ int ev_estimator_rows(ev_handle *h, const float *d_x, const float *d_mu, const i
                       const float *t /* HOST (B) */, int B, int Tp, float *d_v, void *stream);
 int ev_cfm_loss(ev_handle *h, const float *d_x1, const float *d_mu_y, const int32_t *d_ylen, const float *d_spk, const float *d_z,
                 const float *t /* HOST (B) */, int B, int Ty, float sigma_min, double *d_row_sums, float *d_v, void *stream);
+
+/* Sample-rate conversion on the device: a rational polyphase FIR, so that recordings at 44.1 / 48 / 16 kHz reach the 22.05 kHz analysis
+ * side (and synthesis can be written at a playback device's rate).  With c = (n_taps - 1) / 2,
+ *       y[b, n] = sum_i x[b, i] * taps[n * down - i * up + c]      for 0 <= n < L_out = ceil(L_in * up / down),
+ * x zero outside [0, len[b]) (d_len == NULL: every row is L_in long); `taps` carries the gain `up`.  This is
+ * scipy.signal.resample_poly(x, up, down, window=taps / up, padtype="constant"); emojivoice_amd.audio.resample_filter restates scipy's
+ * default Kaiser design.  Outputs at or beyond ceil(len[b] * up / down) are written as zeros; a row with len < 1 or len > L_in is no
+ * error: it is written as zeros (the ev_mas_align convention).
+ *   ev_load_resampler: taps HOST (n_taps).  1 <= up, down <= 640 (8 / 11.025 / 16 / 32 / 44.1 / 48 / 96 kHz against 22.05 kHz),
+ *     gcd(up, down) == 1, n_taps odd and <= 65537; each violation fails with a message naming it.  up = down = 1 with one tap is a scaled
+ *     copy.  The handle keeps the taps phase-major, [up][ceil(n_taps / up)] zero-padded: output n reads ONE contiguous row, that of phase
+ *     (n * down + c) mod up.  Loading again replaces the filter (it waits for the device first).
+ *   ev_resample: d_x (B, L_in), d_len (B) int32 or NULL -> d_y (B, L_out); 1 <= B <= 65535, L_out must equal the formula above.  Without
+ *     a loaded resampler the call fails with a message.
+ *     Arithmetic: one fp32 fmaf chain per output in every arithmetic setting (no fp16 / bf16 pieces), over the taps of the output's phase
+ *     in ascending tap index (i descending), ALL ceil(n_taps / up) of them, samples outside the row entering as +0.  The order does not
+ *     depend on tiling or on the batch: a row resampled alone, inside a batch, or as the prefix (d_len) of a longer padded row gives the
+ *     same bits.  Index arithmetic is 64-bit per tile (n * down and i * up pass 2^31 after minutes of audio).
+ *     The call enqueues one kernel on `stream`; its only scratch is the handle's tap table (nothing to reserve, ev_alloc_count never moves).
+ * Dataset statistics (utils/generate_data_statistics.py:25-47, what a fine-tuning config needs as mel_mean / mel_std):
+ *   ev_mel_stats: d_mel (B, C, T), d_len (B) int32 -> d_row_sums (B, 2) float64: [b][0] = sum x, [b][1] = sum x^2 over the row's
+ *     len[b] x C valid cells.  float64 accumulation per (row, 32 frames), merged per row in ascending order without atomics: two calls
+ *     give the same bits.  A row with len < 1 or len > T is written as zeros.  mean = sum_b [0] / (sum_b len * C),
+ *     std = sqrt(sum_b [1] / (sum_b len * C) - mean^2); the caller combines (emojivoice_amd.audio.data_statistics).
+ *     Scratch: B x ceil(T / 32) x 16 bytes in an arena of the handle that grows on demand and counts in ev_alloc_count; ev_reserve does
+ *     not cover it. */
+int ev_load_resampler(ev_handle *h, const float *taps /* HOST (n_taps) */, int n_taps, int up, int down);
+int ev_resample(ev_handle *h, const float *d_x /* (B, L_in) */, const int32_t *d_len /* (B) or NULL */, int B, int L_in,
+                float *d_y /* (B, L_out) */, int L_out, void *stream);
+int ev_mel_stats(ev_handle *h, const float *d_mel /* (B, C, T) */, const int32_t *d_len /* (B) */, int B, int C, int T,
+                 double *d_row_sums /* (B, 2): sum x, sum x^2 over the row's len[b] x C valid cells */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

@@ -28,6 +28,7 @@ EXPORTS = [
     "ev_maximum_path", "ev_log_prior", "ev_mas_align",
     "ev_estimator_rows", "ev_cfm_loss",
     "ev_load_resampler", "ev_resample", "ev_mel_stats",
+    "ev_trim_bounds", "ev_trim_apply",
 ]
 
 
@@ -142,6 +143,8 @@ def load_library() -> C.CDLL:
     lib.ev_load_resampler.argtypes = [vp, vp, i32, i32, i32]
     lib.ev_resample.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp]
     lib.ev_mel_stats.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.ev_trim_bounds.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]
+    lib.ev_trim_apply.argtypes = [vp, vp, vp, vp, f32, i32, i32, vp, i32, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -338,6 +341,45 @@ class Engine:
         sums = torch.empty((B, 2), dtype=torch.float64, device=mel.device)
         self._check(self.lib.ev_mel_stats(self.h, mel.data_ptr(), ln.data_ptr(), B, Cc, T, sums.data_ptr(), _stream_ptr()), "ev_mel_stats")
         return sums
+
+    def trim_bounds(self, x, lengths=None, top_db: float = 60.0, frame_length: int = 2048, hop_length: int = 512, want_peak: bool = True):
+        """librosa.effects.trim's bounds for every row of ``x`` (B, L) (ev_trim_bounds): (bounds (B, 2) int32 {start, end}, peak (B,) fp32
+        = max |x| over the whole row, or None), both on the device.  ``lengths`` (B,): samples per row (None: L).  hop_length a multiple
+        of 64 up to 4096, frame_length a multiple of it, frame_length / hop_length <= 64."""
+        x = self._f32(x)
+        if x.dim() != 2:
+            raise ValueError(f"trim_bounds: x must be (B, L), got shape {tuple(x.shape)}")
+        B, L = x.shape
+        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"trim_bounds: {B} lengths expected, got {ln.numel()}")
+        bounds = torch.empty((B, 2), dtype=torch.int32, device=x.device)
+        peak = torch.empty((B,), dtype=torch.float32, device=x.device) if want_peak else None
+        self._check(self.lib.ev_trim_bounds(self.h, x.data_ptr(), None if ln is None else ln.data_ptr(), B, L, int(frame_length), int(hop_length),
+                                            float(top_db), bounds.data_ptr(), None if peak is None else peak.data_ptr(), _stream_ptr()), "ev_trim_bounds")
+        return bounds, peak
+
+    def trim_apply(self, x, bounds, peak=None, target_peak: float = 0.0, out_len: Optional[int] = None):
+        """y[b, j] = x[b, start[b] + j] * gain[b] (ev_trim_apply): (y (B, L_out), out_len (B,) int32) on the device, zeros right of each
+        row's out_len.  ``bounds`` (B, 2) int32 and ``peak`` (B,) fp32 are device tensors (those of ``trim_bounds``); gain is
+        target_peak / peak when a peak is given, target_peak > 0 and the peak > 0, else 1.  ``out_len``: L_out (None: L); longer rows are
+        truncated to it."""
+        x = self._f32(x)
+        if x.dim() != 2:
+            raise ValueError(f"trim_apply: x must be (B, L), got shape {tuple(x.shape)}")
+        B, L = x.shape
+        bounds = torch.as_tensor(bounds).to(x.device, torch.int32).contiguous()
+        if tuple(bounds.shape) != (B, 2):
+            raise ValueError(f"trim_apply: bounds must be ({B}, 2), got shape {tuple(bounds.shape)}")
+        pk = None if peak is None else self._f32(torch.as_tensor(peak).to(x.device))
+        if pk is not None and pk.numel() != B:
+            raise ValueError(f"trim_apply: {B} peaks expected, got {pk.numel()}")
+        L_out = L if out_len is None else int(out_len)
+        y = torch.empty((B, max(L_out, 1)), dtype=torch.float32, device=x.device)
+        n = torch.empty((B,), dtype=torch.int32, device=x.device)
+        self._check(self.lib.ev_trim_apply(self.h, x.data_ptr(), bounds.data_ptr(), None if pk is None else pk.data_ptr(), float(target_peak), B, L,
+                                           y.data_ptr(), L_out, n.data_ptr(), _stream_ptr()), "ev_trim_apply")
+        return y, n
 
     def maximum_path(self, value, x_lengths, y_lengths, want_path: bool = True, want_dur: bool = True):
         """monotonic_align.maximum_path on (B, Tx, Ty) fp32 scores with per-row lengths (ev_maximum_path): (path (B, Tx, Ty) 0/1 or None,

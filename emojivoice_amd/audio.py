@@ -14,6 +14,12 @@ In front of it, for recordings that are not at 22.05 kHz (the reference's own re
 
 and behind it ``data_statistics``: the mel_mean / mel_std a fine-tuning config needs (utils/generate_data_statistics.py), reduced on the
 device by ``ev_mel_stats``.
+
+Between a raw take and all of that (the recorder's files begin and end on a key press, at the microphone's level):
+
+    y, (start, end) = trim_silence(y)                         # librosa.effects.trim's call shape, on the device (ev_trim_bounds / ev_trim_apply)
+    y = peak_normalize(y, 0.95)                               # normalize(audio) * 0.95 of hifigan/meldataset.py:152
+    y, info = prepare_recording("take.wav", 22050)            # load_audio -> trim -> level: one read of the bounds comes back to the host
 """
 from __future__ import annotations
 
@@ -269,3 +275,69 @@ def data_statistics(batches: Iterable, n_feats: int = 80, row_sums: Optional[Cal
     if total == 0:
         raise ValueError("data_statistics: no frames")
     return statistics_from_sums(math.fsum(sx), math.fsum(sx2), total, n_feats)
+
+
+def _trim_engine(device: torch.device) -> Engine:
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    eng = _rs_engines.get((idx, "trim"))
+    if eng is None:
+        eng = _rs_engines[(idx, "trim")] = Engine(idx)
+    return eng
+
+
+def _trim_input(y, what: str):
+    if not torch.is_tensor(y) or y.dim() not in (1, 2):
+        raise ValueError(f"{what}: y must be a 1-D tensor or a (B, L) batch")
+    if not y.is_cuda:
+        raise EvLibraryError(f"{what} runs on a ROCm GPU only (no CPU fallback): move y to the GPU")
+    if y.shape[-1] < 1:
+        raise ValueError(f"{what}: y is empty")
+
+
+@torch.inference_mode()
+def trim_silence(y, top_db: float = 60, frame_length: int = 2048, hop_length: int = 512, lengths=None):
+    """``librosa.effects.trim(y, top_db=, frame_length=, hop_length=)`` on the device (``ev_trim_bounds`` + ``ev_trim_apply``; no torch
+    fallback): a frame of ``frame_length`` samples centred on every ``hop_length``-th sample is non-silent when its mean square lies
+    within ``top_db`` dB of the loudest frame's.  ``y`` 1-D on the GPU -> ``(y[start:end], (start, end))``, librosa's return shape.
+    ``y`` (B, L) with ``lengths`` (B,) or None -> ``(batch (B, max out_len) zero-padded, out_len (B,) int32, bounds (B, 2) int32)``, all on
+    the device.  One read of the bounds goes back to the host, to size the result."""
+    _trim_input(y, "trim_silence")
+    eng = _trim_engine(y.device)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    bounds, _ = eng.trim_bounds(x, lengths if y.dim() == 2 else None, top_db, frame_length, hop_length, want_peak=False)
+    host = bounds.cpu()
+    n = int((host[:, 1] - host[:, 0]).max())
+    out, out_len = eng.trim_apply(x, bounds, None, 0.0, out_len=max(n, 1))
+    if y.dim() == 1:
+        return out[0, :n], (int(host[0, 0]), int(host[0, 1]))
+    return out[:, :n], out_len, bounds
+
+
+@torch.inference_mode()
+def peak_normalize(y, peak: float = 0.95, lengths=None):
+    """``y * (peak / max |y|)`` per row on the device: ``normalize(audio) * 0.95`` of the vocoder's dataset code
+    (hifigan/meldataset.py:152; librosa.util.normalize with its default norm=inf).  ``y`` 1-D, or (B, L) with ``lengths`` (B,) or None:
+    the samples past a row's length do not enter its peak and come back as zeros.  An all-zero row stays as it is."""
+    _trim_input(y, "peak_normalize")
+    eng = _trim_engine(y.device)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    B, L = x.shape
+    ln = torch.full((B,), L, dtype=torch.int32, device=x.device) if lengths is None or y.dim() == 1 else torch.as_tensor(lengths).to(x.device, torch.int32)
+    _, pk = eng.trim_bounds(x, ln)                                   # (the bounds are not used: the peak is the whole row's)
+    whole = torch.stack([torch.zeros_like(ln), ln], dim=1)
+    out, _ = eng.trim_apply(x, whole, pk, peak)
+    return out[0] if y.dim() == 1 else out
+
+
+@torch.inference_mode()
+def prepare_recording(path, sr: int = 22050, top_db: float = 60, peak: float = 0.95, device="cuda"):
+    """A raw take -> a fine-tuning sample: ``load_audio`` (any rate or channel count, resampled on the device to ``sr``), the bounds of
+    ``trim_silence`` and the whole take's peak (``ev_trim_bounds``), then the trimmed samples times ``peak / max |y|``
+    (``ev_trim_apply``).  Returns (1-D waveform on the device, {"start", "end", "seconds_in", "seconds_out"}); the bounds are samples at
+    ``sr``.  One read of the bounds goes back to the host, to size the result.  ``peak <= 0`` leaves the level alone."""
+    y = load_audio(path, sr, device)
+    eng = _trim_engine(y.device)
+    bounds, pk = eng.trim_bounds(y, None, top_db)
+    start, end = (int(v) for v in bounds[0].cpu())
+    out, _ = eng.trim_apply(y, bounds, pk, peak, out_len=max(end - start, 1))
+    return out[0, : end - start], {"start": start, "end": end, "seconds_in": y.shape[1] / float(sr), "seconds_out": (end - start) / float(sr)}

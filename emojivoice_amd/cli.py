@@ -12,6 +12,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --checkpoint_path model.ckpt --align_wav voice.wav --phonemes "həlˈoʊ" --spk 12 --losses   # + voice.wav.losses.json
     python -m emojivoice_amd.cli --data_statistics train.txt --batch_size 32                            # train.txt.stats.json: mel_mean / mel_std
     python -m emojivoice_amd.cli --synthetic --ids "0 23 0 51 0" --sample_rate 44100                    # wavs at 44.1 kHz
+    python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean                              # trimmed, levelled 22.05 kHz wavs + clean/filelist.txt + raw.txt.durations.json
 
 The wavs of --mel_from_wav, --align_wav and --data_statistics may have any sample rate (the reference's recorder writes 44.1 kHz,
 record_audio.py:31): they are resampled to the analysis rate on the device (emojivoice_amd.audio.resample).
@@ -21,6 +22,7 @@ from __future__ import annotations
 import argparse
 import datetime as dt
 import json
+import math
 import os
 import struct
 import sys
@@ -44,9 +46,23 @@ def write_wav_pcm24(path, wav: np.ndarray, sr: int = 22050):
         f.write(b"data" + struct.pack("<I", len(b)) + b)
 
 
+def write_wav_pcm16(path, wav: np.ndarray, sr: int = 22050):
+    """A 16-bit mono PCM wav (the format of the reference's recorder, record_audio.py) with the stdlib only: round(x * 32767) after
+    clipping to [-1, 1], the 24-bit writer's rule."""
+    x = np.clip(np.asarray(wav, dtype=np.float64), -1.0, 1.0)
+    b = np.round(x * 32767.0).astype("<i2").tobytes()
+    with open(path, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", 36 + len(b)) + b"WAVEfmt " + struct.pack("<IHHIIHH", 16, 1, 1, sr, sr * 2, 2, 16))
+        f.write(b"data" + struct.pack("<I", len(b)) + b)
+
+
 def validate_args(args):
     if args.sample_rate is not None:
         assert args.sample_rate > 0, "--sample_rate must be positive"
+    if args.prepare_dataset:
+        assert args.out_dir, "--prepare_dataset needs --out_dir"
+        assert 0 <= args.peak <= 1, "--peak must lie in [0, 1] (0: no levelling)"
+        return args
     if args.mel_from_wav:
         return args
     if args.data_statistics:
@@ -256,6 +272,82 @@ def data_statistics(args, device):
     print(f"[+] Data statistics saved: {Path(out).resolve()}  ({len(paths)} files: mel_mean {stats['mel_mean']:.6f}  mel_std {stats['mel_std']:.6f})")
 
 
+TWO_MINUTES = 2.0    # minutes of audio per emoji the reference's README names as the least that fine-tunes a voice
+
+
+def parse_filelist(path):
+    """The lines of a reference filelist (data/text_mel_datamodule.py:96-99) as (wav path, speaker id as written or None, the
+    fields after the path): 'path|spk|text' or 'path|text'.  Relative paths that do not exist as given are taken from the filelist's
+    folder; empty lines are skipped."""
+    flist = Path(path)
+    out = []
+    for ln in flist.read_text(encoding="utf-8").splitlines():
+        if not ln.strip():
+            continue
+        fields = ln.split("|")
+        wav = fields[0].strip()
+        if not os.path.exists(wav) and (flist.parent / wav).exists():
+            wav = str(flist.parent / wav)
+        spk = fields[1].strip() if len(fields) >= 3 else None
+        out.append((wav, spk, fields[1:]))
+    return out
+
+
+def duration_report(files, sr: int, top_db: float, peak: float):
+    """The content of FILELIST.durations.json: per file the seconds before and after trimming, per speaker id the minutes after
+    trimming (what get_duration.ipynb adds up), and the speakers below two minutes.  ``files``: dicts with path, out, speaker,
+    seconds_in, seconds_out.  A filelist without a speaker column counts as speaker "0"."""
+    speakers = {}
+    for f in files:
+        s = speakers.setdefault(f["speaker"], {"files": 0, "seconds": []})
+        s["files"] += 1
+        s["seconds"].append(f["seconds_out"])
+    per_spk = {k: {"files": v["files"], "minutes": math.fsum(v["seconds"]) / 60.0} for k, v in speakers.items()}
+    for v in per_spk.values():
+        v["below_two_minutes"] = v["minutes"] < TWO_MINUTES
+    return {"sample_rate": sr, "top_db": top_db, "peak": peak, "files": files, "speakers": per_spk,
+            "below_two_minutes": sorted(k for k, v in per_spk.items() if v["below_two_minutes"]),
+            "total_minutes_in": math.fsum(f["seconds_in"] for f in files) / 60.0,
+            "total_minutes_out": math.fsum(f["seconds_out"] for f in files) / 60.0}
+
+
+def prepare_dataset(args, device):
+    """--prepare_dataset FILELIST --out_dir DIR: every listed recording (any rate, channel count, 16 / 24 bit) through
+    audio.prepare_recording (resampled to --sample_rate, silence trimmed at --top_db, levelled to --peak, all on the device), written
+    as a 16-bit mono wav of the same base name under DIR; DIR/filelist.txt repeats the lines with the new paths and
+    FILELIST.durations.json holds ``duration_report``."""
+    from . import audio
+
+    sr = int(args.sample_rate or 22050)
+    entries = parse_filelist(args.prepare_dataset)
+    if not entries:
+        sys.exit(f"[-] {args.prepare_dataset}: no files listed")
+    names = [Path(wav).stem + ".wav" for wav, _, _ in entries]
+    if len(set(names)) != len(names):
+        sys.exit(f"[-] {args.prepare_dataset}: two recordings share a base name; they would overwrite each other under {args.out_dir}")
+    out_dir = Path(args.out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    files, lines = [], []
+    for (wav, spk, rest), name in zip(entries, names):
+        y, info = audio.prepare_recording(wav, sr, args.top_db, args.peak, device)
+        dst = (out_dir / name).resolve()
+        write_wav_pcm16(dst, y.cpu().numpy(), sr)
+        files.append({"path": wav, "out": str(dst), "speaker": spk if spk is not None else "0",
+                      "seconds_in": info["seconds_in"], "seconds_out": info["seconds_out"]})
+        lines.append("|".join([str(dst)] + rest))
+        print(f"[+] {wav}: {info['seconds_in']:.2f} s -> {info['seconds_out']:.2f} s  ({dst})")
+    (out_dir / "filelist.txt").write_text("\n".join(lines) + "\n", encoding="utf-8")
+    rep = duration_report(files, sr, args.top_db, args.peak)
+    out = f"{args.prepare_dataset}.durations.json"
+    with open(out, "w") as f:
+        json.dump(rep, f, indent=1)
+    for k in sorted(rep["speakers"]):
+        v = rep["speakers"][k]
+        print(f"[i] speaker {k}: {v['files']} files, {v['minutes']:.2f} min" + ("  (below two minutes)" if v["below_two_minutes"] else ""))
+    print(f"[+] File list saved: {(out_dir / 'filelist.txt').resolve()}\n[+] Durations saved: {Path(out).resolve()}")
+    return rep
+
+
 def loss_draws(seed: int, n_feats: int, frames: int):
     """(t (1,), z (1, n_feats, frames)) of --losses: one CPU generator seeded with --seed, t first."""
     g = torch.Generator().manual_seed(int(seed))
@@ -296,8 +388,17 @@ def cli(argv=None):
     p.add_argument("--data_statistics", type=str, default=None, help="dataset statistics instead of synthesis: a filelist whose first '|'-separated field "
                    "per line is a wav path -> FILELIST.stats.json with mel_mean / mel_std (--batch_size files per batch)")
     p.add_argument("--sample_rate", type=int, default=None, help="write the synthesised wavs at this rate (resampled on the device from 22050 Hz); "
-                   "omitted: 22050 Hz, untouched")
+                   "omitted: 22050 Hz, untouched.  With --prepare_dataset: the rate of the prepared recordings (default 22050)")
+    p.add_argument("--prepare_dataset", type=str, default=None, help="dataset preparation instead of synthesis: a filelist 'path|spk|text' or 'path|text' of raw "
+                   "recordings -> trimmed, levelled 16-bit mono wavs under --out_dir, DIR/filelist.txt and FILELIST.durations.json")
+    p.add_argument("--out_dir", type=str, default=None, help="folder of --prepare_dataset's wavs and filelist.txt")
+    p.add_argument("--top_db", type=float, default=60.0, help="--prepare_dataset: frames this many dB below the loudest one are silence (librosa.effects.trim)")
+    p.add_argument("--peak", type=float, default=0.95, help="--prepare_dataset: peak level of the prepared recordings (hifigan/meldataset.py:152); 0: level untouched")
     args = validate_args(p.parse_args(argv))
+    if args.prepare_dataset:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return prepare_dataset(args, torch.device("cuda", 0))
     if args.align_mel or args.align_wav:
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")

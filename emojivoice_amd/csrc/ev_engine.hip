@@ -140,6 +140,7 @@ struct ev_handle {
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
     Scratch dn_ws, enc_ws, mas_ws;   // (mas_ws: the alignment search's frame -> token index and, for large Tx * Ty, its decision bits)
     Scratch stat_ws;                 // ev_mel_stats: the per-(row, 32 frames) partial sums
+    Scratch trim_ws;                 // ev_trim_bounds: the per-(row, hop block) sum of squares (float64) and max |x| (fp32)
     float* zeros = nullptr;     // 4096 zero floats (stand-in bias for the fused kernels' unconditional loads)
     int max_steps = 64;         // Euler steps the time-grid buffers of the workspace are planned for (grows on demand)
     int* bad_ids_host = nullptr; int* bad_ids_dev = nullptr;   // mapped host word: count of out-of-range token ids seen by ev_text_encoder
@@ -1983,6 +1984,7 @@ void ev_destroy(ev_handle* h) {
     if (h->enc_ws.p) hipFree(h->enc_ws.p);
     if (h->mas_ws.p) hipFree(h->mas_ws.p);
     if (h->stat_ws.p) hipFree(h->stat_ws.p);
+    if (h->trim_ws.p) hipFree(h->trim_ws.p);
     if (h->dn_ws.p) hipFree(h->dn_ws.p);
     if (h->bad_ids_host) hipHostFree(h->bad_ids_host);
     for (int i = 0; i < 2; ++i) { if (h->temb_ev[i]) hipEventDestroy(h->temb_ev[i]); if (h->temb_host[i]) hipHostFree(h->temb_host[i]); }
@@ -2815,6 +2817,50 @@ int ev_mel_stats(ev_handle* h, const float* d_mel, const int32_t* d_len, int B, 
     double* part = (double*)h->stat_ws.p;
     hipLaunchKernelGGL(mel_stats_kernel, dim3(ntiles, B), dim3(256), 0, h->stream, d_mel, d_len, C, T, part, ntiles);
     hipLaunchKernelGGL(cfm_loss_merge_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, (const double*)part, ntiles, B, d_row_sums);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Silence trimming.  The hop blocks of a row start at -off, off = (F/2) mod H, so that every frame [f H - F/2, f H + F/2) is F / H whole
+// blocks (kernels: ev_kernels.h); nblk = ceil((L + off) / H) blocks per row, 12 bytes each: all float64 sums first, then all fp32 maxima.
+int ev_trim_bounds(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, int frame_length, int hop_length, float top_db,
+                   int32_t* d_bounds, float* d_peak, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (B < 1 || B > 65535) return fail(h, "ev_trim_bounds: B=%d outside 1 <= B <= 65535", B);
+    if (L < 1 || !d_x || !d_bounds) return fail(h, "ev_trim_bounds: bad arguments L=%d (L >= 1, non-null d_x and d_bounds)", L);
+    const int F = frame_length, H = hop_length;
+    if (H < 64 || H > 4096 || H % 64) return fail(h, "ev_trim_bounds: hop_length=%d must be a multiple of 64 and at most 4096", H);
+    if (F < H || F % H) return fail(h, "ev_trim_bounds: frame_length=%d must be a multiple of hop_length=%d (frame_length %% hop_length != 0)", F, H);
+    if (F / H > 64) return fail(h, "ev_trim_bounds: frame_length / hop_length = %d exceeds 64 (frame_length=%d hop_length=%d)", F / H, F, H);
+    h->stream = (hipStream_t)stream;
+    const int R = F / H, off = (F / 2) % H;
+    const int nblk = (int)(((long long)L + off + H - 1) / H);
+    if (scratch_acquire(h, h->trim_ws, (size_t)B * nblk * 12)) return 1;
+    double* bsum = (double*)h->trim_ws.p;
+    float* bmax = (float*)(bsum + (size_t)B * nblk);
+    TrimBlocksParams pb{};
+    pb.x = d_x; pb.len = d_len; pb.bsum = bsum; pb.bmax = bmax; pb.L = L; pb.H = H; pb.off = off; pb.nblk = nblk;
+    launch<trim_blocks_kernel>(h->device, dim3((unsigned)((nblk + TRIM_TILE - 1) / TRIM_TILE), (unsigned)B), dim3(256), 0, h->stream, pb);
+    TrimBoundsParams pf{};
+    pf.bsum = bsum; pf.bmax = bmax; pf.len = d_len; pf.bounds = d_bounds; pf.peak = d_peak;
+    pf.L = L; pf.H = H; pf.R = R; pf.off = off; pf.nblk = nblk; pf.F = (double)F; pf.thr = pow(10.0, -(double)top_db / 10.0);
+    launch<trim_bounds_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pf);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int ev_trim_apply(ev_handle* h, const float* d_x, const int32_t* d_bounds, const float* d_peak, float target_peak, int B, int L,
+                  float* d_y, int L_out, int32_t* d_out_len, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (B < 1 || B > 65535) return fail(h, "ev_trim_apply: B=%d outside 1 <= B <= 65535", B);
+    if (L < 1 || L_out < 1 || !d_x || !d_bounds || !d_y || !d_out_len)
+        return fail(h, "ev_trim_apply: bad arguments L=%d L_out=%d (L >= 1, L_out >= 1, non-null d_x, d_bounds, d_y and d_out_len)", L, L_out);
+    h->stream = (hipStream_t)stream;
+    TrimApplyParams p{};
+    p.x = d_x; p.bounds = d_bounds; p.peak = d_peak; p.y = d_y; p.out_len = d_out_len; p.target = target_peak; p.L = L; p.L_out = L_out;
+    launch<gather_scale_kernel>(h->device, dim3((unsigned)(((long long)L_out + 1023) / 1024), (unsigned)B), dim3(256), 0, h->stream, p);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

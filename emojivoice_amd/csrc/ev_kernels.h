@@ -6449,6 +6449,172 @@ __global__ __launch_bounds__(256) void resample_kernel(const ResampleParams p) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Silence trimming and levelling (ev_trim_bounds, ev_trim_apply): librosa.effects.trim's frames and the vocoder dataset's peak gain.
+// Frame f of a row covers samples [f H - F/2, f H + F/2), zeros outside [0, len); it is non-silent iff
+// max(ms[f], 1e-10) > max(max_f ms, 1e-10) * 10^(-top_db / 10), ms[f] = (sum x^2) / F.  F = R H, so a frame is R consecutive HOP BLOCKS of
+// a grid whose origin is -off, off = (F/2) mod H (0 for even R, H/2 for odd R): block j covers samples [j H - off, (j + 1) H - off) and
+// frame f is blocks f - R/2 ... f - R/2 + R - 1.
+// ARITHMETIC of a block: each fp32 sample widened to float64 and squared (exact), summed per lane in ascending sample index -- sample c of
+// the block belongs to lane (c / 4) mod 64 -- then one fixed shuffle tree over the wave.  One wave owns a whole block, so its sum depends
+// on the block's samples only: not on the tile, the batch, the padding behind the row or the row's alignment (an unaligned row takes
+// 4-byte loads in the same lane assignment).  No atomics.
+struct TrimBlocksParams {
+    const float* x; const int32_t* len; double* bsum; float* bmax;     // bsum, bmax: (B, nblk)
+    int L, H, off, nblk;
+};
+
+constexpr int TRIM_TILE = 8;                                            // hop blocks per workgroup: two per wave
+
+__global__ __launch_bounds__(256) void trim_blocks_kernel(const TrimBlocksParams p) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;                                  // a bad row is a row of zeros (the ev_mas_align convention)
+    const float* xrow = p.x + (size_t)b * p.L;
+    const bool vec = (((size_t)xrow) & 15) == 0;                        // (H and off are multiples of 32 samples: every block keeps the row's alignment)
+    for (int k = wave; k < TRIM_TILE; k += 4) {                         // (uniform over the wave)
+        const long long j = (long long)blockIdx.x * TRIM_TILE + k;
+        if (j >= p.nblk) break;
+        const long long s0 = j * p.H - p.off;                           // the block's first sample: -off for j = 0
+        double acc = 0.0;
+        float pk = 0.f;
+        for (int c = 4 * lane; c < p.H; c += 256) {
+            const long long i = s0 + c;                                 // (a multiple of 4: i < 0 means the whole quad is left of the row)
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            if (i >= 0 && i + 4 <= len) {
+                if (vec) {
+                    const f32x4 q = *(const f32x4*)(xrow + i);
+                    v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = xrow[i + e];
+                }
+            } else if (i >= 0) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if (i + e < len) v[e] = xrow[i + e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double d = (double)v[e];
+                acc += d * d;
+                pk = fmaxf(pk, fabsf(v[e]));
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { acc += __shfl_down(acc, o); pk = fmaxf(pk, __shfl_down(pk, o)); }
+        if (lane == 0) { p.bsum[(size_t)b * p.nblk + j] = acc; p.bmax[(size_t)b * p.nblk + j] = pk; }
+    }
+}
+
+// One workgroup per row over the block sums: frame sums (R blocks in ascending order, blocks outside the row +0), ref = max_f ms, the
+// predicate, the first and last non-silent frame, start = f_first H, end = min(len, (f_last + 1) H) and the row's peak (max of the block
+// maxima).  Every reduction is a max or a min: the thread count does not enter the result.  A bad row, or one without a non-silent frame
+// (top_db <= 0), gets bounds (0, 0).
+struct TrimBoundsParams {
+    const double* bsum; const float* bmax; const int32_t* len; int32_t* bounds; float* peak;
+    int L, H, R, off, nblk;
+    double F, thr;                                                      // thr = 10^(-top_db / 10)
+};
+
+__device__ __forceinline__ double trim_frame_ms(const double* bs, int f, int R, int nb, double F) {
+    const int j0 = f - R / 2;
+    double s = 0.0;
+    for (int r = 0; r < R; ++r) {
+        const int j = j0 + r;
+        s += (j >= 0 && j < nb) ? bs[j] : 0.0;
+    }
+    return s / F;
+}
+
+__global__ __launch_bounds__(256) void trim_bounds_kernel(const TrimBoundsParams p) {
+    __shared__ double red_d[4];
+    __shared__ float red_f[4];
+    __shared__ int red_i[4][2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;
+    const int nf = len ? 1 + len / p.H : 0;
+    const int nb = len ? (int)(((long long)len + p.off + p.H - 1) / p.H) : 0;   // blocks that hold a sample of the row (<= nblk)
+    const double* bs = p.bsum + (size_t)b * p.nblk;
+    const float* bm = p.bmax + (size_t)b * p.nblk;
+    double ref = 0.0;
+    float pk = 0.f;
+    for (int f = tid; f < nf; f += 256) ref = fmax(ref, trim_frame_ms(bs, f, p.R, nb, p.F));
+    for (int j = tid; j < nb; j += 256) pk = fmaxf(pk, bm[j]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { ref = fmax(ref, __shfl_down(ref, o)); pk = fmaxf(pk, __shfl_down(pk, o)); }
+    if ((tid & 63) == 0) { red_d[tid >> 6] = ref; red_f[tid >> 6] = pk; }
+    __syncthreads();
+    ref = fmax(fmax(red_d[0], red_d[1]), fmax(red_d[2], red_d[3]));
+    pk = fmaxf(fmaxf(red_f[0], red_f[1]), fmaxf(red_f[2], red_f[3]));
+    const double cut = fmax(ref, 1e-10) * p.thr;
+    int first = 0x7fffffff, last = -1;
+    for (int f = tid; f < nf; f += 256) {
+        if (fmax(trim_frame_ms(bs, f, p.R, nb, p.F), 1e-10) > cut) { first = min(first, f); last = max(last, f); }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { first = min(first, __shfl_down(first, o)); last = max(last, __shfl_down(last, o)); }
+    if ((tid & 63) == 0) { red_i[tid >> 6][0] = first; red_i[tid >> 6][1] = last; }
+    __syncthreads();
+    if (tid == 0) {
+        first = min(min(red_i[0][0], red_i[1][0]), min(red_i[2][0], red_i[3][0]));
+        last = max(max(red_i[0][1], red_i[1][1]), max(red_i[2][1], red_i[3][1]));
+        int start = 0, end = 0;
+        if (last >= 0) {
+            start = (int)((long long)first * p.H);
+            end = (int)min((long long)len, ((long long)last + 1) * p.H);
+        }
+        p.bounds[2 * b] = start;
+        p.bounds[2 * b + 1] = end;
+        if (p.peak) p.peak[b] = pk;
+    }
+}
+
+// y[b, j] = x[b, start[b] + j] * gain[b] for j < min(end[b] - start[b], L_out), +0 up to L_out; out_len[b] = that count.  Bounds and peak
+// come from device memory; gain = target / peak[b] (one correctly rounded fp32 division) when a peak is given, target > 0 and peak > 0,
+// else 1 (x * 1 is x: a bit-exact copy).  Bounds outside 0 <= start <= end <= L make a row of zeros.  One workgroup per (row, 1024
+// outputs); 16-byte stores where the output row is aligned (the source starts at an arbitrary sample: 4-byte loads).
+struct TrimApplyParams {
+    const float* x; const int32_t* bounds; const float* peak; float* y; int32_t* out_len;
+    float target;
+    int L, L_out;
+};
+
+__global__ __launch_bounds__(256) void gather_scale_kernel(const TrimApplyParams p) {
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int start = p.bounds[2 * b];
+    const int end = p.bounds[2 * b + 1];
+    int n = 0;
+    if (start >= 0 && end >= start && end <= p.L) n = min(end - start, p.L_out);
+    else start = 0;
+    float g = 1.f;
+    if (p.peak && p.target > 0.f) {
+        const float pk = p.peak[b];
+        if (pk > 0.f) g = __fdiv_rn(p.target, pk);
+    }
+    if (blockIdx.x == 0 && tid == 0) p.out_len[b] = n;
+    const float* xs = p.x + (size_t)b * p.L + start;
+    float* yrow = p.y + (size_t)b * p.L_out;
+    const long long j0 = (long long)blockIdx.x * 1024;
+    if ((((size_t)yrow) & 15) == 0) {
+        const long long j = j0 + 4 * tid;
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (j + e < n) ? xs[j + e] * g : 0.f;
+        if (j + 4 <= p.L_out) { const f32x4 q = {v[0], v[1], v[2], v[3]}; *(f32x4*)(yrow + j) = q; }
+        else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (j + e < p.L_out) yrow[j + e] = v[e];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long long j = j0 + tid + 256 * k;
+            if (j < p.L_out) yrow[j] = (j < n) ? xs[j] * g : 0.f;
+        }
+    }
+}
+
 // broadcast a per-utterance vector (B, C) over all valid frames: dst[n][c0 + c] = v[b][c] * rowmask[n]
 __global__ void bcast_rows_kernel(const float* v, float* dst, int ld, int c0, int C, int nrows, int S, int P, int T,
                                   const float* rowmask) {

@@ -32,6 +32,8 @@
  *   ev_resample        <- no counterpart: the reference asks for 22050 Hz files (README.md:156: fine-tuning audio "must be 22050",
  *                       data/text_mel_datamodule.py:201 asserts it) while its own recorder writes 44.1 kHz ones (record_audio.py:31)
  *   ev_load_resampler  <- no counterpart (the filter of ev_resample)
+ *   ev_trim_bounds     <- no counterpart: the recorder's takes begin and end on a key press (record_audio.py); librosa.effects.trim is the model
+ *   ev_trim_apply      <- the gain is normalize(audio) * 0.95 of the vocoder's dataset code                hifigan/meldataset.py:152
  *
  * Conventions
  *   - All tensors are fp32.  Pointers named d_* are DEVICE pointers owned by the
@@ -69,7 +71,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -300,6 +302,40 @@ int ev_resample(ev_handle *h, const float *d_x /* (B, L_in) */, const int32_t *d
                 float *d_y /* (B, L_out) */, int L_out, void *stream);
 int ev_mel_stats(ev_handle *h, const float *d_mel /* (B, C, T) */, const int32_t *d_len /* (B) */, int B, int C, int T,
                  double *d_row_sums /* (B, 2): sum x, sum x^2 over the row's len[b] x C valid cells */, void *stream);
+
+/* Dataset preparation: trim the silence around a recording and level it, on the device.  The semantics are those of
+ * librosa.effects.trim(y, top_db, ref=np.max, frame_length, hop_length) and of normalize(audio) * 0.95 (hifigan/meldataset.py:152).
+ * For a row of len samples, F = frame_length, H = hop_length:
+ *   frames     n_frames = 1 + len / H; frame f covers samples [f H - F/2, f H + F/2), zeros outside [0, len) (center=True, constant padding)
+ *   ms[f]      (1 / F) sum x^2 over the frame
+ *   non-silent max(ms[f], 1e-10) > max(max_f ms, 1e-10) * 10^(-top_db / 10): amplitude_to_db(rms, ref=np.max, amin=1e-5, top_db=None) > -top_db
+ *              in the power domain
+ *   bounds     start = f_first H, end = min(len, (f_last + 1) H), f_first / f_last the first / last non-silent frame.  The loudest frame
+ *              passes for any top_db > 0, so an all-zero row keeps [0, len); top_db <= 0 leaves no frame and gives (0, 0), as librosa does
+ *   peak       max |x| over the WHOLE row (levelling precedes trimming in meldataset.py)
+ *   ev_trim_bounds: d_x (B, L), d_len (B) int32 or NULL (every row L long) -> d_bounds (B, 2) int32 {start, end}, d_peak (B) or NULL.
+ *     1 <= B <= 65535; hop_length a multiple of 64 and at most 4096; frame_length a multiple of hop_length; frame_length / hop_length <= 64;
+ *     each violation fails with a message naming it.
+ *     Arithmetic: the row is cut into hop blocks of H samples starting at -((F/2) mod H), so that a frame is F / H whole blocks.  A block is
+ *     read once; each fp32 sample is widened to float64 and squared (exact) and the block summed in a fixed order (per-lane partials in
+ *     ascending sample index, one fixed tree over the wave); a frame is the sum of its blocks in ascending order, blocks outside the row
+ *     +0.  No atomics: two calls give the same bits, and a row alone, inside a batch, or as the d_len prefix of a longer padded row gives
+ *     the same block sums, bounds and peak.  ev_set_arithmetic does not reach it.
+ *     Scratch: B x ceil((L + (F/2) mod H) / H) x 12 bytes (B x ceil(L / H) x 12 when F / H is even) in an arena of the handle that grows on
+ *     demand and counts in ev_alloc_count; a second call at the same shape allocates nothing; ev_reserve does not cover it.
+ *   ev_trim_apply: y[b, j] = x[b, start[b] + j] * gain[b] for j < out_len[b] = min(end[b] - start[b], L_out), +0 from there up to L_out
+ *     (L_out >= 1 is the caller's choice: a longer row is truncated).  gain[b] = target_peak / d_peak[b], one fp32 division, when d_peak is
+ *     given, target_peak > 0 and d_peak[b] > 0; otherwise 1 (a bit-exact copy).  One fp32 multiply per sample.  d_bounds and d_peak are read
+ *     on the device: the output of ev_trim_bounds feeds it without a trip to the host.
+ *   Bad rows are no error and no out-of-bounds access (the ev_mas_align convention): len < 1 or len > L gives bounds (0, 0) and peak 0;
+ *   bounds outside 0 <= start <= end <= L give a row of zeros and out_len 0.
+ *   Both calls enqueue kernels on `stream` only (capturable once the scratch has its size) and need no weights. */
+int ev_trim_bounds(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L,
+                   int frame_length, int hop_length, float top_db,
+                   int32_t *d_bounds /* (B, 2): start, end */, float *d_peak /* (B) or NULL */, void *stream);
+int ev_trim_apply(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_bounds /* (B, 2) */,
+                  const float *d_peak /* (B) or NULL */, float target_peak /* <= 0: no levelling */, int B, int L,
+                  float *d_y /* (B, L_out) */, int L_out, int32_t *d_out_len /* (B) */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

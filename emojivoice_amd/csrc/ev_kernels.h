@@ -190,6 +190,19 @@ __device__ __forceinline__ int ev_xcd_remap(int id, int nwg) {
     return base + within;
 }
 
+// Tiles that contain no storable row (pure padding) do nothing: true when none of the `rows` rows from n0 on is a frame of an
+// utterance.  Rows are S per utterance with the T frames behind P rows of padding; the first storable row at or after n0 is n0
+// itself when it falls in [P, P + T), else the first frame of this utterance (n0 in the front padding) or of the next one.
+// Plain ints, so every parameter struct uses it; the caller returns / continues.
+__device__ __forceinline__ bool ev_tile_is_padding(int S, int P, int T, int nrows, int n0, int rows) {
+    const int s0 = n0 % S, t_first = s0 - P;            // (may be negative)
+    int dist;
+    if (t_first >= 0 && t_first < T) dist = 0;
+    else if (t_first < 0) dist = -t_first;
+    else dist = S - s0 + P;
+    return dist >= rows || n0 + dist >= nrows;
+}
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() is a fence: hipcc emits s_waitcnt vmcnt(0) in front
 // of it, i.e. it also waits for every global STORE this wave still has in flight — in the conv epilogue that made each
 // slab's barrier wait for the previous slab's stores to be acknowledged by memory (30-60 us per workgroup, measured
@@ -722,16 +735,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
     const int m0 = mt * BM;
     const int n0 = nt * BN;
 
-    // tiles that contain no storable row (pure padding) do nothing
-    {
-        int t_first = (n0 % p.S) - p.P;  // may be negative
-        // first valid row at or after n0: if t_first in [0,T) -> valid; else next utterance start
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - (n0 % p.S) + p.P;
-        if (dist >= BN || n0 + dist >= p.nrows) return;
-    }
+    if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, BN)) return;
 
     // active (non-zero) taps of this M tile: a host-built compact list read with scalar loads
     const int2* tl = p.taplist + (size_t)mt * p.tl_stride;
@@ -1043,14 +1047,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvParams p) 
     const int nt = work / p.mtiles;
     const int m0 = mt * BM;
     const int n0 = nt * BN;
-    {   // tiles that contain no storable row (pure padding) do nothing
-        const int t_first = (n0 % p.S) - p.P;
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - (n0 % p.S) + p.P;
-        if (dist >= BN || n0 + dist >= p.nrows) return;
-    }
+    if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, BN)) return;
     const int2* tl = p.taplist + (size_t)mt * p.tl_stride;
     const int nact = __builtin_amdgcn_readfirstlane(p.nact_tab ? p.nact_tab[mt] : p.ntaps);
 
@@ -1229,14 +1226,7 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_bal_kernel(const ConvParams 
         u += c1 - c0;
         const int mt = t % p.mtiles, nt = t / p.mtiles;
         const int m0 = mt * BM, n0 = nt * BN;
-        {   // tiles that contain no storable row (pure padding) do nothing — owner and contributors agree, the test only reads t
-            int t_first = (n0 % p.S) - p.P;
-            int dist;
-            if (t_first >= 0 && t_first < p.T) dist = 0;
-            else if (t_first < 0) dist = -t_first;
-            else dist = p.S - (n0 % p.S) + p.P;
-            if (dist >= BN || n0 + dist >= p.nrows) continue;
-        }
+        if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, BN)) continue;   // owner and contributors agree: the test only reads t
         if (pend_pub) { sk_publish(p.sk, g, tag, tid); pend_pub = false; }   // the previous segment's partial tile: drain, then raise its flag
         const int2* tl = p.taplist + (size_t)mt * p.tl_stride;
         const int nact = __builtin_amdgcn_readfirstlane(p.nact_tab ? p.nact_tab[mt] : p.ntaps);
@@ -1470,6 +1460,15 @@ __device__ __forceinline__ float evh_absmax4_finite(const f32x4 v) {
     for (int e = 0; e < 4; ++e) { const float a = fabsf(v[e]); m = fmaxf(m, evh_is_finite(a) ? a : 0.f); }
     return m;
 }
+// Workgroup maximum (4 waves) through LDS: the 64-lane butterfly, one slot per wave at red[slot + wave], one barrier.  A later search must
+// use other slots unless a barrier lies between (a slow wave may still be reading these).
+__device__ __forceinline__ float evh_wg_max(float* red, int slot, int wave, int lane, float mx) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if (lane == 0) red[slot + wave] = mx;
+    ev_lds_barrier();
+    return fmaxf(fmaxf(red[slot], red[slot + 1]), fmaxf(red[slot + 2], red[slot + 3]));
+}
 template <int TM, int TN>
 __device__ __forceinline__ void evh_mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[2][TM], const f32x4 (&b)[2][TN]) {
     constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};
@@ -1508,14 +1507,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_kernel(const ConvParams p) {
     const int nt = work / p.mtiles;
     const int m0 = mt * BM;
     const int n0 = nt * BN;
-    {   // tiles that contain no storable row (pure padding) do nothing
-        const int t_first = (n0 % p.S) - p.P;
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - (n0 % p.S) + p.P;
-        if (dist >= BN || n0 + dist >= p.nrows) return;
-    }
+    if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, BN)) return;
     EvAmax am = ev_amax_begin(p, n0 + wn * (TN * 32), TN * 32);   // (the residual's / running sum's bounds: requested now, used behind the epilogue)
     const int2* tl = p.taplist + (size_t)mt * p.tl_stride;
     const int nact = __builtin_amdgcn_readfirstlane(p.nact_tab ? p.nact_tab[mt] : p.ntaps);
@@ -1599,12 +1591,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_kernel(const ConvParams p) {
                     for (int q = 0; q < XG; ++q) mx = fmaxf(mx, FIN ? evh_absmax4_finite(xg[q]) : evh_absmax4(xg[q]));
                 }
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-            if (lane == 0) red[wave] = mx;
-            ev_lds_barrier();
-            mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-            return mx;
+            return evh_wg_max(red, 0, wave, lane, mx);
         };
         // the producer's bound for the granules this tile stages (ev_amax_emit), when the input has one: no pre-scan.  A non-finite mark
         // sends the tile to the finite-only search — the pre-scan, kept as that slow path and for inputs without slots.
@@ -1822,14 +1809,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_bal_kernel(const ConvParams
         u += c1 - c0;
         const int mt = t % p.mtiles, nt = t / p.mtiles;
         const int m0 = mt * BM, n0 = nt * BN;
-        {   // tiles that contain no storable row (pure padding) do nothing — owner and contributors agree, the test only reads t
-            int t_first = (n0 % p.S) - p.P;
-            int dist;
-            if (t_first >= 0 && t_first < p.T) dist = 0;
-            else if (t_first < 0) dist = -t_first;
-            else dist = p.S - (n0 % p.S) + p.P;
-            if (dist >= BN || n0 + dist >= p.nrows) continue;
-        }
+        if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, BN)) continue;   // owner and contributors agree: the test only reads t
         if (pend_pub) { sk_publish(p.sk, g, tag, tid); pend_pub = false; }
         const int2* tl = p.taplist + (size_t)mt * p.tl_stride;
         const int nact = __builtin_amdgcn_readfirstlane(p.nact_tab ? p.nact_tab[mt] : p.ntaps);
@@ -2049,14 +2029,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_bal_kernel(const ConvParams p
         u += c1 - c0;
         const int mt = t % p.mtiles, nt = t / p.mtiles;
         const int m0 = mt * BM, n0 = nt * BN;
-        {   // tiles that contain no storable row (pure padding) do nothing — owner and contributors agree, the test only reads t
-            int t_first = (n0 % p.S) - p.P;
-            int dist;
-            if (t_first >= 0 && t_first < p.T) dist = 0;
-            else if (t_first < 0) dist = -t_first;
-            else dist = p.S - (n0 % p.S) + p.P;
-            if (dist >= BN || n0 + dist >= p.nrows) continue;
-        }
+        if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, BN)) continue;   // owner and contributors agree: the test only reads t
         if (first_seg) {                                   // (only a workgroup's first segment can be a contributor's share)
             first_seg = false;
             if (c0 != 0 && sk_claim_taken(p.sk, claim_prev, tid, skw)) continue;     // its owner computes it: skip
@@ -2361,14 +2334,7 @@ __global__ __launch_bounds__(64 * TW * KS) void conv_gemm_sk_kernel(const ConvPa
     const int work = blockIdx.x;
     const int mt = work % p.mtiles, nt = work / p.mtiles;
     const int m0 = mt * BM, n0 = nt * BN;
-    {   // tiles that contain no storable row (pure padding) do nothing
-        int t_first = (n0 % p.S) - p.P;
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - (n0 % p.S) + p.P;
-        if (dist >= BN || n0 + dist >= p.nrows) return;
-    }
+    if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, BN)) return;
     if ((p.dbg & 16) && tid == 0) p.stamps[4 * blockIdx.x + 0] = __builtin_amdgcn_s_memrealtime();
 #ifdef EV_NOPSLED
     asm volatile(".rept 1024\n s_nop 0\n .endr" ::: "memory");   // probe: 4 KB of straight-line code on the path
@@ -2771,14 +2737,7 @@ __global__ __launch_bounds__(256, WAVES_M == 2 ? 4 : 3) void resblock_pair_kerne
     const int nt = ev_xcd_remap(blockIdx.x, p.ntiles);
     const int n0 = nt * pp.out_rows;                    // first output row of this tile
     const int g0 = n0 - pp.h2;                          // global row of compute row 0
-    {   // tiles whose output window holds no storable row do nothing
-        const int s0 = n0 % p.S, t_first = s0 - p.P;
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - s0 + p.P;
-        if (dist >= pp.out_rows || n0 + dist >= p.nrows) return;
-    }
+    if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, pp.out_rows)) return;
 
     const int KG8 = p.Kpad >> 3;
     const unsigned wlane = (unsigned)lane * 16u;
@@ -2923,116 +2882,265 @@ __global__ __launch_bounds__(256, WAVES_M == 2 ? 4 : 3) void resblock_pair_kerne
 }
 
 // ---------------------------------------------------------------------------
-// resblock_pair_split_kernel: resblock_pair_kernel on the bf16 matrix pipe (see conv_split_kernel: six exact bf16 products per
-// element pair, fp32 accumulation).  Same tile geometry (compute rows NT, waves = channel tiles x row tiles, wave tile 32 channels
-// x 64 rows).  LDS rows hold ALL C channels as three bf16 planes (row stride 6 C + 16 bytes: 208 / 400 / 784, odd multiples of 16),
-// so x is staged — and split — once, and the intermediate y1 = lrelu(c1 + b1) is split as it leaves the accumulators (register
-// 4 g + e of a lane = four consecutive channels of one row: one 8-byte store per piece).  K loop: the (tap, 16-deep slab) sequence
-// in groups of two slabs, weight fragments two groups ahead in four named sets, activation fragments double-buffered by slab.
+// The core of the fused ResBlock kernels on the split matrix pipes (resblock_pair_split_kernel, resblock_pair_h16_kernel,
+// resblock_chain_h16_kernel, resblock2_h16_kernel): one K loop, one hand-over, one running-x prologue / epilogue.
+//
+// Geometry, the same in all four: 4 waves = WAVES_M channel tiles x WAVES_N row tiles, wave tile 32 channels x 64 rows (TM = 1, TN = 2),
+// C = 32 WAVES_M channels, NT = 64 WAVES_N compute rows per workgroup.  An LDS row holds ALL C channels as PIECES 16-bit planes + 16 bytes
+// (bf16: 6 C + 16 = 208 / 400 / 784;  fp16: 4 C + 16 = 144 / 272 / 528: odd multiples of 16), so a tile is staged — and split — once.
+//
+// A pipe = how an fp32 operand is cut into 16-bit pieces and multiplied:
+//   EvPipeH16         two block-scaled fp16 pieces, three products per fp32 product (conv_h16_kernel); a tap's two planes are as large as
+//                     its fp32 plane, so the tap list's byte offsets apply as they are
+//   EvPipeBf16<TERMS> three bf16 pieces, TERMS exact products (conv_split_kernel); tap-list entries carry the fp32 plane offset and a
+//                     split plane is 1.5 x that
 // ---------------------------------------------------------------------------
-template <int WAVES_M, int WAVES_N, int LEAN, int TERMS = 6>
-__global__ __launch_bounds__(256, 2) void resblock_pair_split_kernel(const PairParams pp) {
-    constexpr int TM = 1, TN = 2;
-    constexpr int C = 32 * WAVES_M;
-    constexpr int NT = WAVES_N * TN * 32;
-    constexpr int RSB = 6 * C + 16;                     // LDS row stride in bytes
-    constexpr int NS = C / 16, H = NS / 2;              // slabs per tap; two-slab groups per tap
-    constexpr int TPR = C / 4, RPS = 256 / TPR;         // staging: threads per row, rows per pass
-    constexpr int XPASS = (NT + EV_HALO) / RPS;
-    constexpr int XG = XPASS > 8 ? XPASS / 2 : XPASS;
-    static_assert(WAVES_M * WAVES_N == 4 && XPASS % XG == 0, "4 waves per workgroup");
-    const ConvParams& p = pp.c2;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    char* Xb = (char*)smem;                             // phase 1: [NT + 2 h1][RSB];  phase 2 (aliased): y1 [NT + 2 h2][RSB]
+struct EvPipeH16 {
+    static constexpr int PIECES = 2;
+    static constexpr unsigned KG_BYTES = 2048u;         // bytes of one 16-deep weight k-group (PIECES fragments of 64 lanes x 16 bytes)
+    static __device__ __forceinline__ unsigned tap_off(unsigned tb) { return tb; }
+    template <int TM, int TN>
+    static __device__ __forceinline__ void mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[2][TM], const f32x4 (&b)[2][TN]) { evh_mma<TM, TN>(acc, a, b); }
+};
+template <int TERMS>
+struct EvPipeBf16 {
+    static constexpr int PIECES = 3;
+    static constexpr unsigned KG_BYTES = 3072u;
+    static __device__ __forceinline__ unsigned tap_off(unsigned tb) { return tb + (tb >> 1); }
+    template <int TM, int TN>
+    static __device__ __forceinline__ void mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[3][TM], const f32x4 (&b)[3][TN]) { evx_mma<TM, TN, TERMS>(acc, a, b); }
+};
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int li = lane & 31, lh = lane >> 5;
-    const int srow = tid / TPR, sc4 = (tid % TPR) * 4;
+// Every member is forced inline and every register array is indexed by compile-time constants, so the fragments and accumulators stay in
+// registers.  Construct it behind the tile-skip test.
+template <int WAVES_M, int WAVES_N, class PIPE>
+struct EvResblockCore {
+    static constexpr int TM = 1, TN = 2;
+    static constexpr int C = 32 * WAVES_M;
+    static constexpr int NT = WAVES_N * TN * 32;        // compute rows per workgroup
+    static constexpr int PIECES = PIPE::PIECES;
+    static constexpr unsigned KGB = PIPE::KG_BYTES;
+    static constexpr int RSB = PIECES * 2 * C + 16;     // LDS row stride in bytes
+    static constexpr int NS = C / 16, H = NS / 2;       // slabs per tap; two-slab groups per tap
+    static_assert(WAVES_M * WAVES_N == 4, "4 waves per workgroup");
 
-    const int nt = ev_xcd_remap(blockIdx.x, p.ntiles);
-    const int n0 = nt * pp.out_rows;
-    const int g0 = n0 - pp.h2;
-    {   // tiles whose output window holds no storable row do nothing
-        const int s0 = n0 % p.S, t_first = s0 - p.P;
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - s0 + p.P;
-        if (dist >= pp.out_rows || n0 + dist >= p.nrows) return;
-    }
-    const int KG16 = p.Kpad >> 4;
-    const unsigned wlane = (unsigned)lane * 16u;
-    const unsigned wbase = (unsigned)(wm * KG16) * 3072u;
-    const __amdgpu_buffer_rsrc_t rX = ev_rsrc(p.X);
+    char* Xb;                                           // the LDS tile, [rows][RSB]
+    float* red;                                         // 16 floats behind the tile: the waves' maxima (fp16 pipe; see hand_over)
+    int tid, lane, wave, wm, wn, li, lh;
+    unsigned wlane, wbase;
     f32x16 acc[TM][TN];
-    f32x4 A0[3][TM], A1[3][TM], A2[3][TM], A3[3][TM], B0[3][TN], B1[3][TN];
+    f32x4 A0[PIECES][TM], A1[PIECES][TM], A2[PIECES][TM], A3[PIECES][TM], B0[PIECES][TN], B1[PIECES][TN];
 
-    auto ldAp = [&](const __amdgpu_buffer_rsrc_t& rW, f32x4 (&dst)[3][TM], unsigned aoff) {
+    __device__ __forceinline__ EvResblockCore(char* tile, float* maxima, int Kpad) : Xb(tile), red(maxima) {
+        tid = threadIdx.x; lane = tid & 63; wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        wm = wave / WAVES_N; wn = wave % WAVES_N;
+        li = lane & 31; lh = lane >> 5;
+        wlane = (unsigned)lane * 16u;
+        wbase = (unsigned)(wm * (Kpad >> 4)) * KGB;
+    }
+    // this wave's first compute row; this lane's LDS row 0 for the K loop when `halo` rows lie in front of compute row 0
+    __device__ __forceinline__ int row0() const { return wn * (TN * 32); }
+    __device__ __forceinline__ const char* bbase(int halo) const { return Xb + (row0() + li + halo) * RSB + 16 * lh; }
+    // whether compute row (row0 + 32 j + li) of the tile whose compute row 0 is global row g0 is a frame of an utterance
+    __device__ __forceinline__ bool row_inside(const ConvParams& p, int g0, int j) const {
+        const int n = g0 + row0() + j * 32 + li;
+        const int t = (n >= 0 && n < p.nrows) ? (n % p.S) - p.P : -1;
+        return t >= 0 && t < p.T;
+    }
+
+    __device__ __forceinline__ void ldAp(const __amdgpu_buffer_rsrc_t& rW, f32x4 (&dst)[PIECES][TM], unsigned aoff) {
 #pragma unroll
-        for (int pc = 0; pc < 3; ++pc) dst[pc][0] = ev_bload4(rW, wlane, aoff + (unsigned)(pc * 1024));
-    };
-    auto ldB = [&](f32x4 (&dst)[3][TN], const char* brow, int slab) {
+        for (int pc = 0; pc < PIECES; ++pc) dst[pc][0] = ev_bload4(rW, wlane, aoff + (unsigned)(pc * 1024));
+    }
+    __device__ __forceinline__ void ldB(f32x4 (&dst)[PIECES][TN], const char* brow, int slab) {
 #pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
+        for (int pc = 0; pc < PIECES; ++pc)
 #pragma unroll
             for (int j = 0; j < TN; ++j) dst[pc][j] = *(const f32x4*)(brow + j * 32 * RSB + pc * (2 * C) + slab * 32);
-    };
-    // group g of a phase = slabs 2 (g % H), 2 (g % H) + 1 of tap g / H; byte offset of its first weight fragment (tap-list entries
-    // carry the fp32 plane offset: a split plane is 1.5 x that)
-    auto g_off = [&](int2 tlv, int g, int ngroups) -> unsigned {
+    }
+    // group g of a phase = slabs 2 (g % H), 2 (g % H) + 1 of tap g / H; byte offset of its first weight fragment, and its tap's row offset
+    __device__ __forceinline__ unsigned g_off(int2 tlv, int g, int ngroups) const {
         const int gg = g < ngroups ? g : 0;             // (beyond the phase: a harmless re-read)
-        const unsigned tb = (unsigned)__builtin_amdgcn_readlane(tlv.x, gg / H);
-        return tb + (tb >> 1) + wbase + (unsigned)(2 * (gg % H)) * 3072u;
-    };
-    auto g_row = [&](int2 tlv, int g, int ngroups) -> int {
+        return PIPE::tap_off((unsigned)__builtin_amdgcn_readlane(tlv.x, gg / H)) + wbase + (unsigned)(2 * (gg % H)) * KGB;
+    }
+    __device__ __forceinline__ int g_row(int2 tlv, int g, int ngroups) const {
         const int gg = g < ngroups ? g : 0;
         return __builtin_amdgcn_readlane(tlv.y, gg / H);
-    };
-    auto acc_init = [&](const float* binit) {
+    }
+    // the accumulators start from the layer's bias in accumulator units (`unit`: 1 on the bf16 pipe): C/D register 4 g + e is channel 8 g + 4 lh + e
+    __device__ __forceinline__ void acc_init(const float* binit, float unit) {
         f32x4 bq[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = *(const f32x4*)(binit + wm * 32 + 8 * g + 4 * lh);
+        for (int g = 0; g < 4; ++g) bq[g] = *(const f32x4*)(binit + wm * 32 + 8 * g + 4 * lh) * unit;
 #pragma unroll
         for (int b = 0; b < TN; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[0][b][r] = bq[r >> 2][r & 3];
-    };
-    auto ring_fill = [&](const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups) {
+    }
+    // the weight fragments of groups 0 and 1, requested early: they fly under the staging / hand-over in front of the K loop
+    __device__ __forceinline__ void ring_fill(const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups) {
         const unsigned o0 = g_off(tlv, 0, ngroups), o1 = g_off(tlv, 1, ngroups);
-        ldAp(rW, A0, o0); ldAp(rW, A1, o0 + 3072u); ldAp(rW, A2, o1); ldAp(rW, A3, o1 + 3072u);
-    };
-    // the K loop of one conv: `bbase` = this lane's LDS row 0 (halo already added), fragments of groups 0 and 1 already requested
-    auto kloop = [&](const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups, const char* bbase) {
-        auto group = [&](f32x4 (&Aa)[3][TM], f32x4 (&Ab)[3][TM], int g) {
-            const char* brow = bbase + g_row(tlv, g, ngroups) * RSB;
-            const char* nbrow = bbase + g_row(tlv, g + 1, ngroups) * RSB;
-            const int s0 = 2 * (g % H), ns0 = 2 * ((g + 1) % H);
-            const unsigned nap = g_off(tlv, g + 2, ngroups);
-            ldB(B1, brow, s0 + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            evx_mma<TM, TN, TERMS>(acc, Aa, B0);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(rW, Aa, nap);
-            ldB(B0, nbrow, ns0);
-            __builtin_amdgcn_sched_barrier(0);
-            evx_mma<TM, TN, TERMS>(acc, Ab, B1);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(rW, Ab, nap + 3072u);
-        };
-        ldB(B0, bbase + g_row(tlv, 0, ngroups) * RSB, 0);
+        ldAp(rW, A0, o0); ldAp(rW, A1, o0 + KGB); ldAp(rW, A2, o1); ldAp(rW, A3, o1 + KGB);
+    }
+    // the K loop of one conv: the (tap, 16-deep slab) sequence in groups of two slabs, weight fragments two groups ahead in four named
+    // sets, activation fragments double-buffered by slab.  `brow0` = this lane's LDS row 0 (bbase), fragments of groups 0 and 1 already requested.
+    __device__ __forceinline__ void group(const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups, const char* brow0,
+                                          f32x4 (&Aa)[PIECES][TM], f32x4 (&Ab)[PIECES][TM], int g) {
+        const char* brow = brow0 + g_row(tlv, g, ngroups) * RSB;
+        const char* nbrow = brow0 + g_row(tlv, g + 1, ngroups) * RSB;
+        const int s0 = 2 * (g % H), ns0 = 2 * ((g + 1) % H);
+        const unsigned nap = g_off(tlv, g + 2, ngroups);
+        ldB(B1, brow, s0 + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        PIPE::template mma<TM, TN>(acc, Aa, B0);
+        __builtin_amdgcn_sched_barrier(0);
+        ldAp(rW, Aa, nap);
+        ldB(B0, nbrow, ns0);
+        __builtin_amdgcn_sched_barrier(0);
+        PIPE::template mma<TM, TN>(acc, Ab, B1);
+        __builtin_amdgcn_sched_barrier(0);
+        ldAp(rW, Ab, nap + KGB);
+    }
+    __device__ __forceinline__ void kloop(const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups, const char* brow0) {
+        ldB(B0, brow0 + g_row(tlv, 0, ngroups) * RSB, 0);
         int g = 0;
-        for (; g + 1 < ngroups; g += 2) { group(A0, A1, g); group(A2, A3, g + 1); }
-        if (g < ngroups) group(A0, A1, g);
-    };
+        for (; g + 1 < ngroups; g += 2) { group(rW, tlv, ngroups, brow0, A0, A1, g); group(rW, tlv, ngroups, brow0, A2, A3, g + 1); }
+        if (g < ngroups) group(rW, tlv, ngroups, brow0, A0, A1, g);
+    }
+    // the hb rows in front of and behind the NT compute rows, ROW16 16-byte units of each: zero (nothing else writes them)
+    template <int ROW16>
+    __device__ __forceinline__ void zero_border_rows(int hb) {
+        for (int i = tid; i < 2 * hb * ROW16; i += 256) {
+            const int br = i / ROW16, c16 = i % ROW16;
+            const int row = br < hb ? br : NT + br;     // rows [0, hb) and [NT + hb, NT + 2 hb)
+            uint4 z = {0u, 0u, 0u, 0u};
+            *(uint4*)(Xb + row * RSB + c16 * 16) = z;
+        }
+    }
+
+    // ---- fp16 pipe only ----
+    // This lane's values (true units, any prologue applied) -> maximum over the workgroup -> scale (a power of two) -> two fp16 planes at
+    // rows r + row_halo; returns the scale.  Register 4 g + e of a lane = four consecutive channels of one row: one 8-byte store per piece.
+    // The barrier inside evh_wg_max is also what lets the planes be overwritten: every wave has left the K loop that read them.
+    // `slot` = 0 or 4 (alternating, so a wave still reading one set cannot see the next search); the finite-only repeat uses 8 + slot.
+    __device__ __forceinline__ float hand_over(f32x16 (&v)[TN], int slot, int row_halo) {
+        float mx = 0.f;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) mx = fmaxf(mx, fmaxf(fabsf(v[j][r]), fabsf(v[j][r + 1])));
+        float tmx = evh_wg_max(red, slot, wave, lane, mx);
+        if (!evh_is_finite(tmx)) {                      // an Inf in the tile (workgroup-uniform slow path): the finite maximum sets the scale
+            mx = 0.f;
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { const float a = fabsf(v[j][r]); mx = fmaxf(mx, evh_is_finite(a) ? a : 0.f); }
+            tmx = evh_wg_max(red, 8 + slot, wave, lane, mx);
+        }
+        const float sc = evh_scale_for(tmx);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int r = row0() + j * 32 + li;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 w = {v[j][4 * g] * sc, v[j][4 * g + 1] * sc, v[j][4 * g + 2] * sc, v[j][4 * g + 3] * sc};
+                uint2 q0v, q1v;
+                evh_split4(w, q0v, q1v);
+                char* dst = Xb + (r + row_halo) * RSB + (wm * 32 + 8 * g + 4 * lh) * 2;
+                *(uint2*)(dst) = q0v; *(uint2*)(dst + 2 * C) = q1v;
+            }
+        }
+        return sc;
+    }
+    // One conv over the values that stand in the accumulators: hand them over, start from the bias, run the K loop.  Returns the
+    // accumulator unit u = weight scale x activation scale (acc / u = the conv's result plus its bias).
+    __device__ __forceinline__ float conv_from_acc(int slot, int row_halo, const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups,
+                                                   const float* bias, float w_scale) {
+        const float u = w_scale * hand_over(acc[0], slot, row_halo);
+        acc_init(bias, u);
+        ev_lds_barrier();
+        kloop(rW, tlv, ngroups, bbase(row_halo));
+        return u;
+    }
+
+    // ---- the running x of the whole-block kernels: this wave's 32 channels x 64 frames live in registers in the accumulator layout
+    // (lane = frame, registers = channels 8 q + 4 lh + e) from the one read of the tile (compute row 0 = global row g0) to the one write.
+    __device__ __forceinline__ void running_x_load(const ConvParams& p, int g0, int hb, f32x16 (&xr)[TN], float (&inside)[TN]) {
+        const __amdgpu_buffer_rsrc_t rX = ev_rsrc(p.X);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int n = g0 + row0() + j * 32 + li;
+            const bool in = n >= 0 && n < p.nrows;
+            inside[j] = row_inside(p, g0, j) ? 1.f : 0.f;
+            const unsigned ro = (in ? (unsigned)n * (unsigned)p.ldx : 0u) * 4u + (unsigned)(wm * 32 + 4 * lh) * 4u;     // (row 0 is a zero pad row)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 v = ev_bload4(rX, ro + (unsigned)(8 * q) * 4u, 0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xr[j][4 * q + e] = v[e];
+            }
+        }
+        zero_border_rows<RSB / 16>(hb);                 // zero for the whole block
+    }
+    __device__ __forceinline__ void acc_from_lrelu_x(const f32x16 (&xr)[TN], float slope) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[0][j][r] = ev_lrelu(xr[j][r], slope);
+    }
+    // x += acc / u (zero outside the utterance: the next conv must see the padding the stored tensor would have)
+    __device__ __forceinline__ void running_x_add(f32x16 (&xr)[TN], const float (&inside)[TN], float u) {
+        const float inv = 1.0f / u;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) xr[j][r] = fmaf(acc[0][j][r], inv, xr[j][r]) * inside[j];
+    }
+    // rows [n0, n0 + out_rows) of the running x leave through the lean epilogue, with their bounds for the amax slots
+    template <int LEAN>
+    __device__ __forceinline__ void running_x_store(const ConvParams& p, EvAmax& am, const f32x16 (&xr)[TN], float* smem, int g0, int n0, int out_rows) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[0][j] = xr[j];
+        ev_amax_from_acc<TM, TN>(p, am, acc, g0 + row0(), lane);
+        conv_epilogue_lean<TM, TN, LEAN>(p, acc, smem + wave * (32 * (TM * 32 + 4)), wm * 32, g0 + row0(), lane, n0, n0 + out_rows);
+        ev_amax_emit(p, am, g0 + row0(), TN * 32, lane);
+    }
+};
+
+// ---------------------------------------------------------------------------
+// resblock_pair_split_kernel: resblock_pair_kernel on the bf16 matrix pipe (see conv_split_kernel: six exact bf16 products per
+// element pair, fp32 accumulation).  Same tile geometry as resblock_pair_kernel; x is staged — and split — once, and the intermediate
+// y1 = lrelu(c1 + b1) is split as it leaves the accumulators.  K loop and LDS layout: EvResblockCore.
+// ---------------------------------------------------------------------------
+template <int WAVES_M, int WAVES_N, int LEAN, int TERMS = 6>
+__global__ __launch_bounds__(256, 2) void resblock_pair_split_kernel(const PairParams pp) {
+    using Core = EvResblockCore<WAVES_M, WAVES_N, EvPipeBf16<TERMS>>;
+    constexpr int TM = Core::TM, TN = Core::TN, C = Core::C, NT = Core::NT, RSB = Core::RSB, H = Core::H;
+    constexpr int TPR = C / 4, RPS = 256 / TPR;         // staging: threads per row, rows per pass
+    constexpr int XPASS = (NT + EV_HALO) / RPS;
+    constexpr int XG = XPASS > 8 ? XPASS / 2 : XPASS;
+    static_assert(XPASS % XG == 0, "staging passes in equal groups");
+    const ConvParams& p = pp.c2;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+
+    const int nt = ev_xcd_remap(blockIdx.x, p.ntiles);
+    const int n0 = nt * pp.out_rows;
+    const int g0 = n0 - pp.h2;
+    if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, pp.out_rows)) return;
+    Core k((char*)smem, nullptr, p.Kpad);               // phase 1: [NT + 2 h1][RSB];  phase 2 (aliased): y1 [NT + 2 h2][RSB]
+    char* Xb = k.Xb;
+    const int tid = k.tid, lane = k.lane, wave = k.wave, wm = k.wm, li = k.li, lh = k.lh;
+    const int srow = tid / TPR, sc4 = (tid % TPR) * 4;
+    const __amdgpu_buffer_rsrc_t rX = ev_rsrc(p.X);
 
     // ---------------- phase 1: c1 over lrelu(x); X tile rows [g0 - h1, g0 + NT + h1), all channels, split into three planes
     const __amdgpu_buffer_rsrc_t rW1 = ev_rsrc(pp.W1x), rW2 = ev_rsrc(p.Wx);
     const int ng1 = pp.ntaps1 * H, ng2 = p.ntaps * H;
     const int2 tlv1 = (lane < pp.ntaps1) ? pp.taplist1[lane] : make_int2(0, 0);
     const int2 tlv2 = (lane < p.ntaps) ? p.taplist[lane] : make_int2(0, 0);
-    ring_fill(rW1, tlv1, ng1);
-    acc_init(pp.b1);
+    k.ring_fill(rW1, tlv1, ng1);
+    k.acc_init(pp.b1, 1.f);
     {
         const int xrows = NT + 2 * pp.h1;
 #pragma unroll
@@ -3061,23 +3169,21 @@ __global__ __launch_bounds__(256, 2) void resblock_pair_split_kernel(const PairP
         }
     }
     ev_lds_barrier();
-    kloop(rW1, tlv1, ng1, Xb + (wn * (TN * 32) + li + pp.h1) * RSB + 16 * lh);
-    ring_fill(rW2, tlv2, ng2);                           // c2's first fragments fly under the hand-over below
+    k.kloop(rW1, tlv1, ng1, k.bbase(pp.h1));
+    k.ring_fill(rW2, tlv2, ng2);                         // c2's first fragments fly under the hand-over below
 
     // ---------------- y1 = lrelu(c1 + b1), zero outside the utterance, split, into LDS rows r + h2
     ev_lds_barrier();                                    // every wave is done reading the X tile
     {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const int r = wn * (TN * 32) + j * 32 + li;
-            const int n = g0 + r;
-            const int t = (n >= 0 && n < p.nrows) ? (n % p.S) - p.P : -1;
-            const float inside = (t >= 0 && t < p.T) ? 1.f : 0.f;
+            const int r = k.row0() + j * 32 + li;
+            const float inside = k.row_inside(p, g0, j) ? 1.f : 0.f;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 f32x4 v;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = ev_lrelu(acc[0][j][4 * g + e], pp.mid_slope) * inside;
+                for (int e = 0; e < 4; ++e) v[e] = ev_lrelu(k.acc[0][j][4 * g + e], pp.mid_slope) * inside;
                 uint2 q0v, q1v, q2v;
                 evx_split4(v, q0v, q1v, q2v);
                 char* dst = Xb + (r + pp.h2) * RSB + (wm * 32 + 8 * g + 4 * lh) * 2;
@@ -3085,137 +3191,51 @@ __global__ __launch_bounds__(256, 2) void resblock_pair_split_kernel(const PairP
             }
         }
         // the 2 h2 border rows only feed outputs outside the stored window, but must be finite: zero all three planes
-        for (int i = tid; i < 2 * pp.h2 * (6 * C / 16); i += 256) {
-            const int br = i / (6 * C / 16), c16 = i % (6 * C / 16);
-            const int row = br < pp.h2 ? br : NT + br;
-            uint4 z = {0u, 0u, 0u, 0u};
-            *(uint4*)(Xb + row * RSB + c16 * 16) = z;
-        }
+        k.template zero_border_rows<6 * C / 16>(pp.h2);
     }
-    acc_init(LEAN ? p.bias : pp.b1);
+    k.acc_init(LEAN ? p.bias : pp.b1, 1.f);
     ev_lds_barrier();
 
     // ---------------- phase 2: c2 over the LDS-resident y1 (tap offset t reads rows r + h2 + t)
-    kloop(rW2, tlv2, ng2, Xb + (wn * (TN * 32) + li + pp.h2) * RSB + 16 * lh);
+    k.kloop(rW2, tlv2, ng2, k.bbase(pp.h2));
 
-    conv_epilogue_lean<TM, TN, LEAN>(p, acc, smem + wave * (32 * (TM * 32 + 4)), wm * 32, g0 + wn * (TN * 32), lane, n0, n0 + pp.out_rows);
+    conv_epilogue_lean<TM, TN, LEAN>(p, k.acc, smem + wave * (32 * (TM * 32 + 4)), wm * 32, g0 + k.row0(), lane, n0, n0 + pp.out_rows);
 }
 
 // ---------------------------------------------------------------------------
 // resblock_pair_h16_kernel: the fused ResBlock pair with fp16 pieces (conv_h16_kernel: two block-scaled fp16 pieces per operand, three
 // products per fp32 product).  Scales, all exact powers of two: the layers' weight scales from the loader; sx from the maximum of the X
 // tile, which is loaded into registers ONCE (maximum, then leaky-relu, scaling, split, LDS); sy from the maximum of the intermediate
-// lrelu(c1 + b1) over the workgroup's tile, exchanged through LDS at the barrier the hand-over has anyway.  LDS row = two fp16 planes of
-// all C channels + 16 bytes (144 / 272 / 528 = 9, 17, 33 x 16).
+// lrelu(c1 + b1) over the workgroup's tile, exchanged through LDS at the barrier the hand-over has anyway (EvResblockCore::hand_over).
 // ---------------------------------------------------------------------------
 template <int WAVES_M, int WAVES_N, int LEAN>
 __global__ __launch_bounds__(256, 2) void resblock_pair_h16_kernel(const PairParams pp) {
-    constexpr int TM = 1, TN = 2;
-    constexpr int C = 32 * WAVES_M;
-    constexpr int NT = WAVES_N * TN * 32;
-    constexpr int RSB = 4 * C + 16;                     // LDS row stride in bytes
-    constexpr int NS = C / 16, H = NS / 2;              // slabs per tap; two-slab groups per tap
+    using Core = EvResblockCore<WAVES_M, WAVES_N, EvPipeH16>;
+    constexpr int TM = Core::TM, TN = Core::TN, C = Core::C, NT = Core::NT, RSB = Core::RSB, H = Core::H;
     constexpr int TPR = C / 4, RPS = 256 / TPR;         // staging: threads per row, rows per pass
     constexpr int XPASS = (NT + EV_HALO) / RPS;
-    static_assert(WAVES_M * WAVES_N == 4, "4 waves per workgroup");
     const ConvParams& p = pp.c2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    char* Xb = (char*)smem;                             // phase 1: [NT + 2 h1][RSB];  phase 2 (aliased): y1 [NT + 2 h2][RSB]
-    float* red = smem + ((NT + EV_HALO) * RSB) / 4;     // 16 floats behind the tiles: the waves' maxima (x: 0..3, y1: 4..7; their finite-only repeats: 8..11, 12..15)
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int li = lane & 31, lh = lane >> 5;
-    const int srow = tid / TPR, sc4 = (tid % TPR) * 4;
 
     const int nt = ev_xcd_remap(blockIdx.x, p.ntiles);
     const int n0 = nt * pp.out_rows;
     const int g0 = n0 - pp.h2;
-    {   // tiles whose output window holds no storable row do nothing
-        const int s0 = n0 % p.S, t_first = s0 - p.P;
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - s0 + p.P;
-        if (dist >= pp.out_rows || n0 + dist >= p.nrows) return;
-    }
-    const int KG16 = p.Kpad >> 4;
-    const unsigned wlane = (unsigned)lane * 16u;
-    EvAmax am = ev_amax_begin(p, g0 + wn * (TN * 32), TN * 32);   // (the residual's / running sum's bounds: requested now, used behind the epilogue)
-    const unsigned wbase = (unsigned)(wm * KG16) * 2048u;
+    if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, pp.out_rows)) return;
+    // tile: phase 1 [NT + 2 h1][RSB], phase 2 (aliased) y1 [NT + 2 h2][RSB]; maxima: x 0..3, y1 4..7, their finite-only repeats 8..11, 12..15
+    Core k((char*)smem, smem + ((NT + EV_HALO) * RSB) / 4, p.Kpad);
+    char* Xb = k.Xb;
+    const int tid = k.tid, lane = k.lane, wave = k.wave, wm = k.wm;
+    const int srow = tid / TPR, sc4 = (tid % TPR) * 4;
+    const int nw0 = g0 + k.row0();                      // global row of this wave's compute row 0
+    EvAmax am = ev_amax_begin(p, nw0, TN * 32);         // (the residual's / running sum's bounds: requested now, used behind the epilogue)
     const __amdgpu_buffer_rsrc_t rX = ev_rsrc(p.X);
-    f32x16 acc[TM][TN];
-    f32x4 A0[2][TM], A1[2][TM], A2[2][TM], A3[2][TM], B0[2][TN], B1[2][TN];
-
-    auto ldAp = [&](const __amdgpu_buffer_rsrc_t& rW, f32x4 (&dst)[2][TM], unsigned aoff) {
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc) dst[pc][0] = ev_bload4(rW, wlane, aoff + (unsigned)(pc * 1024));
-    };
-    auto ldB = [&](f32x4 (&dst)[2][TN], const char* brow, int slab) {
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) dst[pc][j] = *(const f32x4*)(brow + j * 32 * RSB + pc * (2 * C) + slab * 32);
-    };
-    // group g of a phase = slabs 2 (g % H), 2 (g % H) + 1 of tap g / H (a tap's fp16 plane is as large as its fp32 plane: the tap list's
-    // byte offsets apply as they are)
-    auto g_off = [&](int2 tlv, int g, int ngroups) -> unsigned {
-        const int gg = g < ngroups ? g : 0;             // (beyond the phase: a harmless re-read)
-        return (unsigned)__builtin_amdgcn_readlane(tlv.x, gg / H) + wbase + (unsigned)(2 * (gg % H)) * 2048u;
-    };
-    auto g_row = [&](int2 tlv, int g, int ngroups) -> int {
-        const int gg = g < ngroups ? g : 0;
-        return __builtin_amdgcn_readlane(tlv.y, gg / H);
-    };
-    auto acc_init = [&](const float* binit, float unit) {   // bias in accumulator units
-        f32x4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = *(const f32x4*)(binit + wm * 32 + 8 * g + 4 * lh) * unit;
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][b][r] = bq[r >> 2][r & 3];
-    };
-    auto ring_fill = [&](const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups) {
-        const unsigned o0 = g_off(tlv, 0, ngroups), o1 = g_off(tlv, 1, ngroups);
-        ldAp(rW, A0, o0); ldAp(rW, A1, o0 + 2048u); ldAp(rW, A2, o1); ldAp(rW, A3, o1 + 2048u);
-    };
-    auto kloop = [&](const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups, const char* bbase) {
-        auto group = [&](f32x4 (&Aa)[2][TM], f32x4 (&Ab)[2][TM], int g) {
-            const char* brow = bbase + g_row(tlv, g, ngroups) * RSB;
-            const char* nbrow = bbase + g_row(tlv, g + 1, ngroups) * RSB;
-            const int s0 = 2 * (g % H), ns0 = 2 * ((g + 1) % H);
-            const unsigned nap = g_off(tlv, g + 2, ngroups);
-            ldB(B1, brow, s0 + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            evh_mma<TM, TN>(acc, Aa, B0);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(rW, Aa, nap);
-            ldB(B0, nbrow, ns0);
-            __builtin_amdgcn_sched_barrier(0);
-            evh_mma<TM, TN>(acc, Ab, B1);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(rW, Ab, nap + 2048u);
-        };
-        ldB(B0, bbase + g_row(tlv, 0, ngroups) * RSB, 0);
-        int g = 0;
-        for (; g + 1 < ngroups; g += 2) { group(A0, A1, g); group(A2, A3, g + 1); }
-        if (g < ngroups) group(A0, A1, g);
-    };
-    auto wg_max = [&](float mx, int slot) -> float {        // workgroup maximum through LDS (one barrier)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        if (lane == 0) red[slot + wave] = mx;
-        ev_lds_barrier();
-        return fmaxf(fmaxf(red[slot], red[slot + 1]), fmaxf(red[slot + 2], red[slot + 3]));
-    };
 
     // ---------------- phase 1: c1 over lrelu(x); X tile rows [g0 - h1, g0 + NT + h1), all channels, loaded once
     const __amdgpu_buffer_rsrc_t rW1 = ev_rsrc(pp.W1h), rW2 = ev_rsrc(p.Wh);
     const int ng1 = pp.ntaps1 * H, ng2 = p.ntaps * H;
     const int2 tlv1 = (lane < pp.ntaps1) ? pp.taplist1[lane] : make_int2(0, 0);
     const int2 tlv2 = (lane < p.ntaps) ? p.taplist[lane] : make_int2(0, 0);
-    ring_fill(rW1, tlv1, ng1);
+    k.ring_fill(rW1, tlv1, ng1);
     float sx;
     {
         const int xrows = NT + 2 * pp.h1;
@@ -3229,12 +3249,12 @@ __global__ __launch_bounds__(256, 2) void resblock_pair_h16_kernel(const PairPar
         }
 #pragma unroll
         for (int q = 0; q < XPASS; ++q) mx = fmaxf(mx, evh_absmax4(xg[q]));
-        float tmx = wg_max(mx, 0);                      // (|lrelu(x)| <= |x|)
+        float tmx = evh_wg_max(k.red, 0, wave, lane, mx);   // (|lrelu(x)| <= |x|)
         if (!evh_is_finite(tmx)) {                      // an Inf in the tile (workgroup-uniform): the finite maximum sets the scale
             mx = 0.f;
 #pragma unroll
             for (int q = 0; q < XPASS; ++q) mx = fmaxf(mx, evh_absmax4_finite(xg[q]));
-            tmx = wg_max(mx, 8);
+            tmx = evh_wg_max(k.red, 8, wave, lane, mx);
         }
         sx = evh_scale_for(tmx);
         am.rlo = am.rhi = tmx;                          // the residual IS this tile's input: its bound for the amax slots is the tile maximum just found (no slots of X needed)
@@ -3253,75 +3273,41 @@ __global__ __launch_bounds__(256, 2) void resblock_pair_h16_kernel(const PairPar
         }
     }
     const float u1 = pp.w1h_scale * sx;
-    acc_init(pp.b1, u1);
+    k.acc_init(pp.b1, u1);
     ev_lds_barrier();
-    kloop(rW1, tlv1, ng1, Xb + (wn * (TN * 32) + li + pp.h1) * RSB + 16 * lh);
-    ring_fill(rW2, tlv2, ng2);                           // c2's first fragments fly under the hand-over below
+    k.kloop(rW1, tlv1, ng1, k.bbase(pp.h1));
+    k.ring_fill(rW2, tlv2, ng2);                         // c2's first fragments fly under the hand-over below
 
     // ---------------- y1 = lrelu(c1 + b1), zero outside the utterance; its maximum over the workgroup -> sy; split into LDS rows r + h2
     float sy;
     {
         const float inv1 = 1.0f / u1;
-        float my = 0.f;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const int r = wn * (TN * 32) + j * 32 + li;
-            const int n = g0 + r;
-            const int t = (n >= 0 && n < p.nrows) ? (n % p.S) - p.P : -1;
-            const float inside = (t >= 0 && t < p.T) ? inv1 : 0.f;
+            const float inside = k.row_inside(p, g0, j) ? inv1 : 0.f;
 #pragma unroll
-            for (int r16 = 0; r16 < 16; ++r16) {
-                const float v = ev_lrelu(acc[0][j][r16] * inside, pp.mid_slope);    // (back to true units; 0 outside the utterance)
-                acc[0][j][r16] = v;
-                my = fmaxf(my, fabsf(v));
-            }
+            for (int r16 = 0; r16 < 16; ++r16) k.acc[0][j][r16] = ev_lrelu(k.acc[0][j][r16] * inside, pp.mid_slope);    // (back to true units; 0 outside the utterance)
         }
-        float tmy = wg_max(my, 4);                      // (the barrier inside: every wave is done reading the X tile)
-        if (!evh_is_finite(tmy)) {
-            my = 0.f;
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r16 = 0; r16 < 16; ++r16) { const float a = fabsf(acc[0][j][r16]); my = fmaxf(my, evh_is_finite(a) ? a : 0.f); }
-            tmy = wg_max(my, 12);
-        }
-        sy = evh_scale_for(tmy);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int r = wn * (TN * 32) + j * 32 + li;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 v = {acc[0][j][4 * g] * sy, acc[0][j][4 * g + 1] * sy, acc[0][j][4 * g + 2] * sy, acc[0][j][4 * g + 3] * sy};
-                uint2 q0v, q1v;
-                evh_split4(v, q0v, q1v);
-                char* dst = Xb + (r + pp.h2) * RSB + (wm * 32 + 8 * g + 4 * lh) * 2;
-                *(uint2*)(dst) = q0v; *(uint2*)(dst + 2 * C) = q1v;
-            }
-        }
+        sy = k.hand_over(k.acc[0], 4, pp.h2);           // (the barrier inside: every wave is done reading the X tile)
         // the 2 h2 border rows only feed outputs outside the stored window, but must be finite: zero both planes
-        for (int i = tid; i < 2 * pp.h2 * (4 * C / 16); i += 256) {
-            const int br = i / (4 * C / 16), c16 = i % (4 * C / 16);
-            const int row = br < pp.h2 ? br : NT + br;
-            uint4 z = {0u, 0u, 0u, 0u};
-            *(uint4*)(Xb + row * RSB + c16 * 16) = z;
-        }
+        k.template zero_border_rows<4 * C / 16>(pp.h2);
     }
     const float u2 = p.wh_scale * sy;
-    acc_init(LEAN ? p.bias : pp.b1, u2);
+    k.acc_init(LEAN ? p.bias : pp.b1, u2);
     ev_lds_barrier();
 
     // ---------------- phase 2: c2 over the LDS-resident y1 (tap offset t reads rows r + h2 + t)
-    kloop(rW2, tlv2, ng2, Xb + (wn * (TN * 32) + li + pp.h2) * RSB + 16 * lh);
+    k.kloop(rW2, tlv2, ng2, k.bbase(pp.h2));
     {
         const float inv2 = 1.0f / u2;
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int r16 = 0; r16 < 16; ++r16) acc[0][j][r16] *= inv2;
+            for (int r16 = 0; r16 < 16; ++r16) k.acc[0][j][r16] *= inv2;
     }
-    ev_amax_from_acc<TM, TN>(p, am, acc, g0 + wn * (TN * 32), lane);
-    conv_epilogue_lean<TM, TN, LEAN>(p, acc, smem + wave * (32 * (TM * 32 + 4)), wm * 32, g0 + wn * (TN * 32), lane, n0, n0 + pp.out_rows);
-    ev_amax_emit(p, am, g0 + wn * (TN * 32), TN * 32, lane);
+    ev_amax_from_acc<TM, TN>(p, am, k.acc, nw0, lane);
+    conv_epilogue_lean<TM, TN, LEAN>(p, k.acc, smem + wave * (32 * (TM * 32 + 4)), wm * 32, nw0, lane, n0, n0 + pp.out_rows);
+    ev_amax_emit(p, am, nw0, TN * 32, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -3347,173 +3333,33 @@ struct ChainParams {
 };
 template <int WAVES_M, int WAVES_N, int LEAN>
 __global__ __launch_bounds__(256, 2) void resblock_chain_h16_kernel(const ChainParams cp) {
-    constexpr int TM = 1, TN = 2;
-    constexpr int C = 32 * WAVES_M;
-    constexpr int NT = WAVES_N * TN * 32;
-    constexpr int RSB = 4 * C + 16;                     // LDS row stride in bytes: two fp16 planes of all C channels + 16
-    constexpr int NS = C / 16, H = NS / 2;
-    static_assert(WAVES_M * WAVES_N == 4 && (C == 32 || C == 64), "4 waves per workgroup; C = 32 / 64");
+    using Core = EvResblockCore<WAVES_M, WAVES_N, EvPipeH16>;
+    constexpr int TN = Core::TN, C = Core::C, NT = Core::NT, RSB = Core::RSB, H = Core::H;
+    static_assert(C == 32 || C == 64, "C = 32 / 64");
     const ConvParams& p = cp.c2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    char* Xb = (char*)smem;                             // [hb | NT | hb][RSB]
-    float* red = smem + ((NT + EV_HALO) * RSB) / 4;     // 16 floats behind the tile: the waves' maxima (two alternating sets + their finite-only repeats)
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int li = lane & 31, lh = lane >> 5;
     const int nt = ev_xcd_remap(blockIdx.x, p.ntiles);
     const int n0 = nt * cp.out_rows;
     const int g0 = n0 - cp.halo;
-    {   // tiles whose output window holds no storable row do nothing
-        const int s0 = n0 % p.S, t_first = s0 - p.P;
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - s0 + p.P;
-        if (dist >= cp.out_rows || n0 + dist >= p.nrows) return;
-    }
-    const int HB = cp.hb;
-    const int KG16 = p.Kpad >> 4;
-    const unsigned wlane = (unsigned)lane * 16u;
-    const unsigned wbase = (unsigned)(wm * KG16) * 2048u;
-    EvAmax am = ev_amax_begin(p, g0 + wn * (TN * 32), TN * 32);
-    const __amdgpu_buffer_rsrc_t rX = ev_rsrc(p.X);
-    // ---- the running x of this wave's 32 channels x 64 frames, accumulator layout (lane = frame, registers = channels 8 q + 4 lh + e)
+    if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, cp.out_rows)) return;
+    // tile [hb | NT | hb][RSB]; 16 floats behind it: the waves' maxima (two alternating sets + their finite-only repeats)
+    Core k((char*)smem, smem + ((NT + EV_HALO) * RSB) / 4, p.Kpad);
+    const int lane = k.lane;
+    EvAmax am = ev_amax_begin(p, g0 + k.row0(), TN * 32);
     f32x16 xr[TN];
     float inside[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = g0 + wn * (TN * 32) + j * 32 + li;
-        const bool in = n >= 0 && n < p.nrows;
-        const int t = in ? (n % p.S) - p.P : -1;
-        inside[j] = (t >= 0 && t < p.T) ? 1.f : 0.f;
-        const unsigned ro = (in ? (unsigned)n * (unsigned)p.ldx : 0u) * 4u + (unsigned)(wm * 32 + 4 * lh) * 4u;     // (row 0 is a zero pad row)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = ev_bload4(rX, ro + (unsigned)(8 * q) * 4u, 0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xr[j][4 * q + e] = v[e];
-        }
-    }
-    // the rows in front of and behind the tile: zero for the whole chain (nothing writes them)
-    for (int i = tid; i < 2 * HB * (RSB / 16); i += 256) {
-        const int br = i / (RSB / 16), c16 = i % (RSB / 16);
-        const int row = br < HB ? br : NT + br;
-        uint4 z = {0u, 0u, 0u, 0u};
-        *(uint4*)(Xb + row * RSB + c16 * 16) = z;
-    }
-    f32x16 acc[TM][TN];
-    f32x4 A0[2][TM], A1[2][TM], A2[2][TM], A3[2][TM], B0[2][TN], B1[2][TN];
-    auto ldAp = [&](const __amdgpu_buffer_rsrc_t& rW, f32x4 (&dst)[2][TM], unsigned aoff) {
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc) dst[pc][0] = ev_bload4(rW, wlane, aoff + (unsigned)(pc * 1024));
-    };
-    auto ldB = [&](f32x4 (&dst)[2][TN], const char* brow, int slab) {
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) dst[pc][j] = *(const f32x4*)(brow + j * 32 * RSB + pc * (2 * C) + slab * 32);
-    };
-    auto g_off = [&](int2 tlv, int g, int ngroups) -> unsigned {
-        const int gg = g < ngroups ? g : 0;             // (beyond the phase: a harmless re-read)
-        return (unsigned)__builtin_amdgcn_readlane(tlv.x, gg / H) + wbase + (unsigned)(2 * (gg % H)) * 2048u;
-    };
-    auto g_row = [&](int2 tlv, int g, int ngroups) -> int {
-        const int gg = g < ngroups ? g : 0;
-        return __builtin_amdgcn_readlane(tlv.y, gg / H);
-    };
-    auto acc_init = [&](const float* binit, float unit) {   // bias in accumulator units
-        f32x4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = *(const f32x4*)(binit + wm * 32 + 8 * g + 4 * lh) * unit;
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][b][r] = bq[r >> 2][r & 3];
-    };
-    auto ring_fill = [&](const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups) {
-        const unsigned o0 = g_off(tlv, 0, ngroups), o1 = g_off(tlv, 1, ngroups);
-        ldAp(rW, A0, o0); ldAp(rW, A1, o0 + 2048u); ldAp(rW, A2, o1); ldAp(rW, A3, o1 + 2048u);
-    };
-    auto kloop = [&](const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups, const char* bbase) {
-        auto group = [&](f32x4 (&Aa)[2][TM], f32x4 (&Ab)[2][TM], int g) {
-            const char* brow = bbase + g_row(tlv, g, ngroups) * RSB;
-            const char* nbrow = bbase + g_row(tlv, g + 1, ngroups) * RSB;
-            const int s0 = 2 * (g % H), ns0 = 2 * ((g + 1) % H);
-            const unsigned nap = g_off(tlv, g + 2, ngroups);
-            ldB(B1, brow, s0 + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            evh_mma<TM, TN>(acc, Aa, B0);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(rW, Aa, nap);
-            ldB(B0, nbrow, ns0);
-            __builtin_amdgcn_sched_barrier(0);
-            evh_mma<TM, TN>(acc, Ab, B1);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(rW, Ab, nap + 2048u);
-        };
-        ldB(B0, bbase + g_row(tlv, 0, ngroups) * RSB, 0);
-        int g = 0;
-        for (; g + 1 < ngroups; g += 2) { group(A0, A1, g); group(A2, A3, g + 1); }
-        if (g < ngroups) group(A0, A1, g);
-    };
-    auto wg_max = [&](float mx, int slot) -> float {        // workgroup maximum through LDS (one barrier)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        if (lane == 0) red[slot + wave] = mx;
-        ev_lds_barrier();
-        return fmaxf(fmaxf(red[slot], red[slot + 1]), fmaxf(red[slot + 2], red[slot + 3]));
-    };
-    // this lane's values (true units, any prologue applied) -> maximum over the workgroup -> scale -> two fp16 planes at rows r + HB.
-    // The barrier inside wg_max is also what lets the planes be overwritten: every wave has left the K loop that read them.
-    auto hand_over = [&](f32x16 (&v)[TN], int slot) -> float {
-        float mx = 0.f;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) mx = fmaxf(mx, fmaxf(fabsf(v[j][r]), fabsf(v[j][r + 1])));
-        float tmx = wg_max(mx, slot);
-        if (!evh_is_finite(tmx)) {                      // an Inf in the tile (workgroup-uniform slow path): the finite maximum sets the scale
-            mx = 0.f;
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { const float a = fabsf(v[j][r]); mx = fmaxf(mx, evh_is_finite(a) ? a : 0.f); }
-            tmx = wg_max(mx, 8 + slot);
-        }
-        const float sc = evh_scale_for(tmx);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int r = wn * (TN * 32) + j * 32 + li;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 w = {v[j][4 * g] * sc, v[j][4 * g + 1] * sc, v[j][4 * g + 2] * sc, v[j][4 * g + 3] * sc};
-                uint2 q0v, q1v;
-                evh_split4(w, q0v, q1v);
-                char* dst = Xb + (r + HB) * RSB + (wm * 32 + 8 * g + 4 * lh) * 2;
-                *(uint2*)(dst) = q0v; *(uint2*)(dst + 2 * C) = q1v;
-            }
-        }
-        return sc;
-    };
-    const char* bbase = Xb + (wn * (TN * 32) + li + HB) * RSB + 16 * lh;
+    k.running_x_load(p, g0, cp.hb, xr, inside);
     const int ng1 = cp.ntaps1 * H, ng2 = cp.ntaps2 * H;
 #pragma unroll 1
     for (int m = 0; m < 3; ++m) {
         const __amdgpu_buffer_rsrc_t rW1 = ev_rsrc(cp.W1h[m]), rW2 = ev_rsrc(cp.W2h[m]);
         const int2 tlv1 = (lane < cp.ntaps1) ? cp.tl1[m][lane] : make_int2(0, 0);
         const int2 tlv2 = (lane < cp.ntaps2) ? cp.tl2[m][lane] : make_int2(0, 0);
-        ring_fill(rW1, tlv1, ng1);                          // c1's first fragments fly under the hand-over
+        k.ring_fill(rW1, tlv1, ng1);                        // c1's first fragments fly under the hand-over
         // ---- lrelu(x) -> planes; c1
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][j][r] = ev_lrelu(xr[j][r], p.pro_slope);
-        const float sx = hand_over(acc[0], 0);
-        const float u1 = cp.w1_scale[m] * sx;
-        acc_init(cp.b1[m], u1);
-        ev_lds_barrier();
-        kloop(rW1, tlv1, ng1, bbase);
-        ring_fill(rW2, tlv2, ng2);
+        k.acc_from_lrelu_x(xr, p.pro_slope);
+        const float u1 = k.conv_from_acc(0, cp.hb, rW1, tlv1, ng1, cp.b1[m], cp.w1_scale[m]);
+        k.ring_fill(rW2, tlv2, ng2);
         // ---- y1 = lrelu(c1 + b1), zero outside the utterance -> planes; c2
         {
             const float inv1 = 1.0f / u1;
@@ -3521,28 +3367,14 @@ __global__ __launch_bounds__(256, 2) void resblock_chain_h16_kernel(const ChainP
             for (int j = 0; j < TN; ++j) {
                 const float f = inv1 * inside[j];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[0][j][r] = ev_lrelu(acc[0][j][r] * f, cp.mid_slope);
+                for (int r = 0; r < 16; ++r) k.acc[0][j][r] = ev_lrelu(k.acc[0][j][r] * f, cp.mid_slope);
             }
         }
-        const float sy = hand_over(acc[0], 4);
-        const float u2 = cp.w2_scale[m] * sy;
-        acc_init(cp.b2[m], u2);
-        ev_lds_barrier();
-        kloop(rW2, tlv2, ng2, bbase);
-        // ---- x += c2 + b2 (zero outside the utterance: the next conv must see the padding the stored tensor would have)
-        {
-            const float inv2 = 1.0f / u2;
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) xr[j][r] = fmaf(acc[0][j][r], inv2, xr[j][r]) * inside[j];
-        }
+        const float u2 = k.conv_from_acc(4, cp.hb, rW2, tlv2, ng2, cp.b2[m], cp.w2_scale[m]);
+        // ---- x += c2 + b2
+        k.running_x_add(xr, inside, u2);
     }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[0][j] = xr[j];
-    ev_amax_from_acc<TM, TN>(p, am, acc, g0 + wn * (TN * 32), lane);
-    conv_epilogue_lean<TM, TN, LEAN>(p, acc, smem + wave * (32 * (TM * 32 + 4)), wm * 32, g0 + wn * (TN * 32), lane, n0, n0 + cp.out_rows);
-    ev_amax_emit(p, am, g0 + wn * (TN * 32), TN * 32, lane);
+    k.template running_x_store<LEAN>(p, am, xr, smem, g0, n0, cp.out_rows);
 }
 
 // ---------------------------------------------------------------------------
@@ -3563,185 +3395,34 @@ struct Rb2Params {
 };
 template <int WAVES_M, int WAVES_N, int LEAN>
 __global__ __launch_bounds__(256, 2) void resblock2_h16_kernel(const Rb2Params cp) {
-    constexpr int TM = 1, TN = 2;
-    constexpr int C = 32 * WAVES_M;
-    constexpr int NT = WAVES_N * TN * 32;
-    constexpr int RSB = 4 * C + 16;                     // LDS row stride in bytes: two fp16 planes of all C channels + 16
-    constexpr int NS = C / 16, H = NS / 2;
-    static_assert(WAVES_M * WAVES_N == 4 && (C == 32 || C == 64 || C == 128), "4 waves per workgroup; C = 32 / 64 / 128");
+    using Core = EvResblockCore<WAVES_M, WAVES_N, EvPipeH16>;
+    constexpr int TN = Core::TN, C = Core::C, NT = Core::NT, RSB = Core::RSB, H = Core::H;
+    static_assert(C == 32 || C == 64 || C == 128, "C = 32 / 64 / 128");
     const ConvParams& p = cp.c2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    char* Xb = (char*)smem;                             // [hb | NT | hb][RSB]
-    float* red = smem + ((NT + 2 * cp.hb) * RSB) / 4;   // 16 floats behind the tile: the waves' maxima (two alternating sets + their finite-only repeats)
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int li = lane & 31, lh = lane >> 5;
     const int nt = ev_xcd_remap(blockIdx.x, p.ntiles);
     const int n0 = nt * cp.out_rows;
     const int g0 = n0 - cp.halo;
-    {   // tiles whose output window holds no storable row do nothing
-        const int s0 = n0 % p.S, t_first = s0 - p.P;
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - s0 + p.P;
-        if (dist >= cp.out_rows || n0 + dist >= p.nrows) return;
-    }
-    const int HB = cp.hb;
-    const int KG16 = p.Kpad >> 4;
-    const unsigned wlane = (unsigned)lane * 16u;
-    const unsigned wbase = (unsigned)(wm * KG16) * 2048u;
-    EvAmax am = ev_amax_begin(p, g0 + wn * (TN * 32), TN * 32);
-    const __amdgpu_buffer_rsrc_t rX = ev_rsrc(p.X);
-    // ---- the running x of this wave's 32 channels x 64 frames, accumulator layout (lane = frame, registers = channels 8 q + 4 lh + e)
+    if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, cp.out_rows)) return;
+    // tile [hb | NT | hb][RSB]; 16 floats behind it: the waves' maxima (two alternating sets + their finite-only repeats)
+    Core k((char*)smem, smem + ((NT + 2 * cp.hb) * RSB) / 4, p.Kpad);
+    const int lane = k.lane;
+    EvAmax am = ev_amax_begin(p, g0 + k.row0(), TN * 32);
     f32x16 xr[TN];
     float inside[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = g0 + wn * (TN * 32) + j * 32 + li;
-        const bool in = n >= 0 && n < p.nrows;
-        const int t = in ? (n % p.S) - p.P : -1;
-        inside[j] = (t >= 0 && t < p.T) ? 1.f : 0.f;
-        const unsigned ro = (in ? (unsigned)n * (unsigned)p.ldx : 0u) * 4u + (unsigned)(wm * 32 + 4 * lh) * 4u;     // (row 0 is a zero pad row)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = ev_bload4(rX, ro + (unsigned)(8 * q) * 4u, 0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xr[j][4 * q + e] = v[e];
-        }
-    }
-    // the rows in front of and behind the tile: zero for the whole block (nothing writes them)
-    for (int i = tid; i < 2 * HB * (RSB / 16); i += 256) {
-        const int br = i / (RSB / 16), c16 = i % (RSB / 16);
-        const int row = br < HB ? br : NT + br;
-        uint4 z = {0u, 0u, 0u, 0u};
-        *(uint4*)(Xb + row * RSB + c16 * 16) = z;
-    }
-    f32x16 acc[TM][TN];
-    f32x4 A0[2][TM], A1[2][TM], A2[2][TM], A3[2][TM], B0[2][TN], B1[2][TN];
-    auto ldAp = [&](const __amdgpu_buffer_rsrc_t& rW, f32x4 (&dst)[2][TM], unsigned aoff) {
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc) dst[pc][0] = ev_bload4(rW, wlane, aoff + (unsigned)(pc * 1024));
-    };
-    auto ldB = [&](f32x4 (&dst)[2][TN], const char* brow, int slab) {
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) dst[pc][j] = *(const f32x4*)(brow + j * 32 * RSB + pc * (2 * C) + slab * 32);
-    };
-    auto g_off = [&](int2 tlv, int g, int ngroups) -> unsigned {
-        const int gg = g < ngroups ? g : 0;             // (beyond the last tap: a harmless re-read)
-        return (unsigned)__builtin_amdgcn_readlane(tlv.x, gg / H) + wbase + (unsigned)(2 * (gg % H)) * 2048u;
-    };
-    auto g_row = [&](int2 tlv, int g, int ngroups) -> int {
-        const int gg = g < ngroups ? g : 0;
-        return __builtin_amdgcn_readlane(tlv.y, gg / H);
-    };
-    auto acc_init = [&](const float* binit, float unit) {   // bias in accumulator units
-        f32x4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = *(const f32x4*)(binit + wm * 32 + 8 * g + 4 * lh) * unit;
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][b][r] = bq[r >> 2][r & 3];
-    };
-    auto ring_fill = [&](const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups) {
-        const unsigned o0 = g_off(tlv, 0, ngroups), o1 = g_off(tlv, 1, ngroups);
-        ldAp(rW, A0, o0); ldAp(rW, A1, o0 + 2048u); ldAp(rW, A2, o1); ldAp(rW, A3, o1 + 2048u);
-    };
-    auto kloop = [&](const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int ngroups, const char* bbase) {
-        auto group = [&](f32x4 (&Aa)[2][TM], f32x4 (&Ab)[2][TM], int g) {
-            const char* brow = bbase + g_row(tlv, g, ngroups) * RSB;
-            const char* nbrow = bbase + g_row(tlv, g + 1, ngroups) * RSB;
-            const int s0 = 2 * (g % H), ns0 = 2 * ((g + 1) % H);
-            const unsigned nap = g_off(tlv, g + 2, ngroups);
-            ldB(B1, brow, s0 + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            evh_mma<TM, TN>(acc, Aa, B0);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(rW, Aa, nap);
-            ldB(B0, nbrow, ns0);
-            __builtin_amdgcn_sched_barrier(0);
-            evh_mma<TM, TN>(acc, Ab, B1);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(rW, Ab, nap + 2048u);
-        };
-        ldB(B0, bbase + g_row(tlv, 0, ngroups) * RSB, 0);
-        int g = 0;
-        for (; g + 1 < ngroups; g += 2) { group(A0, A1, g); group(A2, A3, g + 1); }
-        if (g < ngroups) group(A0, A1, g);
-    };
-    auto wg_max = [&](float mx, int slot) -> float {        // workgroup maximum through LDS (one barrier)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        if (lane == 0) red[slot + wave] = mx;
-        ev_lds_barrier();
-        return fmaxf(fmaxf(red[slot], red[slot + 1]), fmaxf(red[slot + 2], red[slot + 3]));
-    };
-    // this lane's values -> maximum over the workgroup -> scale -> two fp16 planes at rows r + HB.  The barrier inside wg_max is also what
-    // lets the planes be overwritten: every wave has left the K loop that read them.
-    auto hand_over = [&](f32x16 (&v)[TN], int slot) -> float {
-        float mx = 0.f;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) mx = fmaxf(mx, fmaxf(fabsf(v[j][r]), fabsf(v[j][r + 1])));
-        float tmx = wg_max(mx, slot);
-        if (!evh_is_finite(tmx)) {                      // an Inf in the tile (workgroup-uniform slow path): the finite maximum sets the scale
-            mx = 0.f;
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { const float a = fabsf(v[j][r]); mx = fmaxf(mx, evh_is_finite(a) ? a : 0.f); }
-            tmx = wg_max(mx, 8 + slot);
-        }
-        const float sc = evh_scale_for(tmx);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int r = wn * (TN * 32) + j * 32 + li;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 w = {v[j][4 * g] * sc, v[j][4 * g + 1] * sc, v[j][4 * g + 2] * sc, v[j][4 * g + 3] * sc};
-                uint2 q0v, q1v;
-                evh_split4(w, q0v, q1v);
-                char* dst = Xb + (r + HB) * RSB + (wm * 32 + 8 * g + 4 * lh) * 2;
-                *(uint2*)(dst) = q0v; *(uint2*)(dst + 2 * C) = q1v;
-            }
-        }
-        return sc;
-    };
-    const char* bbase = Xb + (wn * (TN * 32) + li + HB) * RSB + 16 * lh;
+    k.running_x_load(p, g0, cp.hb, xr, inside);
     const int ng = cp.ntaps * H;
 #pragma unroll 1
     for (int m = 0; m < 2; ++m) {
         const __amdgpu_buffer_rsrc_t rW = ev_rsrc(cp.Wh[m]);
         const int2 tlv = (lane < cp.ntaps) ? cp.tl[m][lane] : make_int2(0, 0);
-        ring_fill(rW, tlv, ng);                             // the conv's first fragments fly under the hand-over
-        // ---- lrelu(x) -> planes; conv
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][j][r] = ev_lrelu(xr[j][r], p.pro_slope);
-        const float sx = hand_over(acc[0], 4 * m);
-        const float u = cp.w_scale[m] * sx;
-        acc_init(cp.b[m], u);
-        ev_lds_barrier();
-        kloop(rW, tlv, ng, bbase);
-        // ---- x += conv + b (zero outside the utterance: the next conv must see the padding the stored tensor would have)
-        {
-            const float inv = 1.0f / u;
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) xr[j][r] = fmaf(acc[0][j][r], inv, xr[j][r]) * inside[j];
-        }
+        k.ring_fill(rW, tlv, ng);                           // the conv's first fragments fly under the hand-over
+        // ---- lrelu(x) -> planes; conv; x += conv + b
+        k.acc_from_lrelu_x(xr, p.pro_slope);
+        const float u = k.conv_from_acc(4 * m, cp.hb, rW, tlv, ng, cp.b[m], cp.w_scale[m]);
+        k.running_x_add(xr, inside, u);
     }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[0][j] = xr[j];
-    ev_amax_from_acc<TM, TN>(p, am, acc, g0 + wn * (TN * 32), lane);
-    conv_epilogue_lean<TM, TN, LEAN>(p, acc, smem + wave * (32 * (TM * 32 + 4)), wm * 32, g0 + wn * (TN * 32), lane, n0, n0 + cp.out_rows);
-    ev_amax_emit(p, am, g0 + wn * (TN * 32), TN * 32, lane);
+    k.template running_x_store<LEAN>(p, am, xr, smem, g0, n0, cp.out_rows);
 }
 
 // ---------------------------------------------------------------------------
@@ -4038,14 +3719,7 @@ __global__ __launch_bounds__(256, WPC) void ln_mlp_kernel(const MlpParams mp) {
         const int c1 = (ue - u < nchunk - c0) ? c0 + (ue - u) : nchunk;
         u += c1 - c0;
         const int n0 = t * NT;
-        {   // tiles that contain no storable row (pure padding) do nothing — owner and contributors agree, the test only reads t
-            int t_first = (n0 % p.S) - p.P;
-            int dist;
-            if (t_first >= 0 && t_first < p.T) dist = 0;
-            else if (t_first < 0) dist = -t_first;
-            else dist = p.S - (n0 % p.S) + p.P;
-            if (dist >= NT || n0 + dist >= p.nrows) continue;
-        }
+        if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, NT)) continue;   // owner and contributors agree: the test only reads t
         F0 = ldP(c0 * 4 + wave, 0); F1 = ldP(c0 * 4 + wave, 1); F2 = ldP(c0 * 4 + wave, 2); F3 = ldP(c0 * 4 + wave, 3);
         F4 = ldP(c0 * 4 + wave, 4); F5 = ldP(c0 * 4 + wave, 5); F6 = ldP(c0 * 4 + wave, 6); F7 = ldP(c0 * 4 + wave, 7);
         ev_lds_barrier();                              // the previous segment's epilogue is done with its LDS slabs
@@ -4395,14 +4069,7 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_split_kernel(const MlpParams mp
         const int c1 = (ue - u < nchunk - c0) ? c0 + (ue - u) : nchunk;
         u += c1 - c0;
         const int n0 = t * NT;
-        {   // tiles that contain no storable row (pure padding) do nothing — owner and contributors agree, the test only reads t
-            int t_first = (n0 % p.S) - p.P;
-            int dist;
-            if (t_first >= 0 && t_first < p.T) dist = 0;
-            else if (t_first < 0) dist = -t_first;
-            else dist = p.S - (n0 % p.S) + p.P;
-            if (dist >= NT || n0 + dist >= p.nrows) continue;
-        }
+        if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, NT)) continue;   // owner and contributors agree: the test only reads t
         {
             const int ht0 = c0 * 4 + wave;
             ldP(R0, ht0, 0); ldP(R1, ht0, 1); ldP(R2, ht0, 2); ldP(R3, ht0, 3); ldP(R4, ht0, 4); ldP(R5, ht0, 5); ldP(R6, ht0, 6); ldP(R7, ht0, 7);
@@ -4723,14 +4390,7 @@ __global__ __launch_bounds__(256, 1) void ln_mlp_h16_kernel(const MlpParams mp) 
         const int c1 = (ue - u < nchunk - c0) ? c0 + (ue - u) : nchunk;
         u += c1 - c0;
         const int n0 = t * NT;
-        {   // tiles that contain no storable row (pure padding) do nothing — owner and contributors agree, the test only reads t
-            int t_first = (n0 % p.S) - p.P;
-            int dist;
-            if (t_first >= 0 && t_first < p.T) dist = 0;
-            else if (t_first < 0) dist = -t_first;
-            else dist = p.S - (n0 % p.S) + p.P;
-            if (dist >= NT || n0 + dist >= p.nrows) continue;
-        }
+        if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, NT)) continue;   // owner and contributors agree: the test only reads t
         if (first_seg) {                               // (only a workgroup's first segment can be a contributor's share)
             first_seg = false;
             if (c0 != 0 && sk_claim_taken(mp.sk, claim_prev, tid, skw)) continue;    // its owner computes it: skip
@@ -5073,14 +4733,7 @@ __global__ __launch_bounds__(256, 2) void ln_qkv_h16_kernel(const MlpParams mp) 
     const __amdgpu_buffer_rsrc_t rX = ev_rsrc(mp.X), rW1 = ev_rsrc(mp.W1h), rB1 = ev_rsrc(mp.b1);
     const unsigned wlane = (unsigned)lane * 16u;
     const int n0 = blockIdx.x * NT;
-    {   // tiles that contain no storable row (pure padding) do nothing
-        int t_first = (n0 % p.S) - p.P;
-        int dist;
-        if (t_first >= 0 && t_first < p.T) dist = 0;
-        else if (t_first < 0) dist = -t_first;
-        else dist = p.S - (n0 % p.S) + p.P;
-        if (dist >= NT || n0 + dist >= p.nrows) return;
-    }
+    if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, NT)) return;
     // weight fragments: set s of the ring = slab (k 16 s .. 16 s + 15) of this wave's three row tiles, two pieces each
     f32x4 A[4][TM][2];
     auto ldA = [&](f32x4 (&dst)[TM][2], int sl) {

@@ -30,15 +30,12 @@ import torch
 import bench
 from emojivoice_amd import weights as W
 from emojivoice_amd.hifigan import AttrDict, Generator, v1
-from vocoder_ref import HOP, linear_regime_state, restate_windows
+from vocoder_ref import MARGIN, WEIGHTS, gpu_refs, linear_regime_state   # (the gates, GATE and REF_FLOOR, live there too)
+from vocoder_ref import check as _check, fanout_planned as _fanout_planned, row_windows as _row_windows, run as _run, sweep as _sweep
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-SETTINGS = (16, 6, 0)
-WEIGHTS = ("std", "lin")
-GATE = {"std": (5e-6, 5e-5), "lin": (5e-6, 3e-5)}        # (RMS, L-inf): absolute for std, relative to the row's fp64 RMS for lin
-REF_FLOOR = {"std": 0.2, "lin": 0.01}                  # the row's fp64 RMS must exceed this: the comparison is not vacuous
 _CLOCK = {"gpu_ref": 0.0, "cpu_ref": 0.0}
 
 
@@ -68,82 +65,7 @@ def vocs(sds):
 
 def _refs(sds, mel, wins, check_cpu=1):
     """{weights: [fp64 samples of each window]}; the first ``check_cpu`` windows are also run on the CPU and must agree to 1e-10."""
-    names = list(WEIGHTS)
-    t0 = time.perf_counter()
-    got = restate_windows([sds[n] for n in names], mel, v1, wins, device=DEV)
-    torch.cuda.synchronize()
-    _CLOCK["gpu_ref"] += time.perf_counter() - t0
-    if check_cpu:
-        t0 = time.perf_counter()
-        cpu = restate_windows([sds[n] for n in names], mel.cpu(), v1, wins[:check_cpu])
-        _CLOCK["cpu_ref"] += time.perf_counter() - t0
-        for i in range(len(names)):
-            for n in range(check_cpu):
-                assert float((cpu[i][n] - got[i][n]).abs().max()) <= 1e-10, (names[i], wins[n])
-    return {n: got[i] for i, n in enumerate(names)}
-
-
-def _run(voc, mel, setting=16, chain=True, amax=True):
-    """The vocoder's output under one arithmetic setting, and how many balanced persistent launches the call made."""
-    eng = voc.engine
-    eng.set_arithmetic(setting)
-    eng.set_chain(chain)
-    eng.set_amax(amax)
-    try:
-        e0 = eng.sk_stats()[0]
-        wav = voc(mel)
-        torch.cuda.synchronize()
-        e1 = eng.sk_stats()[0]
-    finally:
-        eng.set_arithmetic(16)
-        eng.set_chain(True)
-        eng.set_amax(True)
-    return wav, (e1 - e0) & 0xFFFFFFFF
-
-
-def _fanout_planned(eng, B, T):
-    """True when a (B, T) call plans the three-stream MRF fan-out: its workspace exceeds the single-stream plan's."""
-    saved = eng.mrf_streams_max
-    ws = eng.workspace_bytes(B, 0, T)
-    eng.set_mrf_streams_max(0)
-    try:
-        single = eng.workspace_bytes(B, 0, T)
-    finally:
-        eng.set_mrf_streams_max(saved)
-    assert ws >= single
-    return ws > single
-
-
-def _check(tag, weights, wav, wins, refs, bad):
-    """Per row over its windows: (RMS, L-inf) of the error against the fp64 reference, gated; one table line per call."""
-    per_row = {}
-    for (r, t0, t1), ref in zip(wins, refs):
-        per_row.setdefault(r, []).append((wav[r, 0, HOP * t0:HOP * t1], ref))
-    worst = [0.0, 0.0, 0.0, 0.0, float("inf")]            # rms, linf, rms / ref, linf / ref, smallest ref RMS
-    g_rms, g_linf = GATE[weights]
-    for r, pairs in per_row.items():
-        got = torch.cat([p[0] for p in pairs]).double().cpu()
-        ref = torch.cat([p[1] for p in pairs])
-        e = got - ref
-        rms, linf, rr = float(e.pow(2).mean().sqrt()), float(e.abs().max()), float(ref.pow(2).mean().sqrt())
-        worst = [max(worst[0], rms), max(worst[1], linf), max(worst[2], rms / rr), max(worst[3], linf / rr), min(worst[4], rr)]
-        scale = 1.0 if weights == "std" else rr
-        if not (rms <= g_rms * scale and linf <= g_linf * scale and rr > REF_FLOOR[weights] and bool(torch.isfinite(got).all())):
-            bad.append((tag, weights, r, rms, linf, rr))
-    print(f"V1ERR {tag:<34s} {weights}  rms {worst[0]:.2e}  linf {worst[1]:.2e}  rel rms {worst[2]:.2e}  rel linf {worst[3]:.2e}  "
-          f"min ref rms {worst[4]:.3f}")
-
-
-def _sweep(tag, vocs, mel, wins, refs, bad, settings=SETTINGS):
-    """Every setting x checkpoint; returns {setting: balanced launches of the std call}."""
-    epochs = {}
-    for s in settings:
-        for w in WEIGHTS:
-            wav, ep = _run(vocs[w], mel, s)
-            _check(f"{tag} s{s}", w, wav, wins, refs[w], bad)
-            if w == "std":
-                epochs[s] = ep
-    return epochs
+    return gpu_refs(sds, mel, v1, wins, _CLOCK, check_cpu=check_cpu, margin=MARGIN, device=DEV)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -165,16 +87,6 @@ def bench_mel():
     mean = float(model.mel_mean)
     del model
     return mel, mean
-
-
-def _row_windows(lengths, w=8):
-    """Head, tail and one interior window per row; the interior offset steps 8 frames a row, so over 64 rows the interior windows
-    cover the whole time axis and, with the rows' 524-frame stride on the flattened axis, every phase of the 128-row tiles."""
-    wins = []
-    for r, L in enumerate(lengths):
-        t0 = w + (w * r) % max(1, L - 2 * w)
-        wins += [(r, 0, min(w, L)), (r, max(0, L - w), L), (r, min(t0, L - w), min(t0, L - w) + w)]
-    return wins
 
 
 def test_bench_batch_every_row(vocs, sds, bench_mel):

@@ -25,6 +25,13 @@ GOLDEN = os.path.join(REPO, "tests", "golden", "vocoder_configs.npz")
 NAMES = ("v2", "v3", "offstd")
 
 
+# configs whose last level is neither 8, 16 nor 32 channels: conv_post runs as a generic conv launch + a pass that strips the pad rows
+WIDE_LAST = {
+    "v3_512": dict(v3, upsample_initial_channel=512),                                  # levels 256 / 128 / 64, ResBlock2 at 256 on the conv launches
+    "rb1_2lvl": dict(v1, upsample_rates=[16, 16], upsample_kernel_sizes=[32, 32], upsample_initial_channel=256),   # two levels: 128 / 64
+}
+
+
 def golden_vocoder():
     with np.load(GOLDEN) as z:
         return {k: z[k] for k in z.files}

@@ -43,7 +43,7 @@ def test_windows_equal_the_full_row():
     for _ in range(4):
         t0 = int(torch.randint(MARGIN, T - MARGIN - 8, (1,), generator=g))
         wins.append((int(torch.randint(0, B, (1,), generator=g)), t0, t0 + int(torch.randint(1, 9, (1,), generator=g))))
-    got = restate_windows(sds, mel, V1, wins)
+    got = restate_windows(sds, mel, V1, wins, margin=MARGIN)
     for i in range(len(sds)):
         for n, (r, t0, t1) in enumerate(wins):
             ref = full[i][r, HOP * t0:HOP * t1]

@@ -29,6 +29,7 @@ EXPORTS = [
     "ev_estimator_rows", "ev_cfm_loss",
     "ev_load_resampler", "ev_resample", "ev_mel_stats",
     "ev_trim_bounds", "ev_trim_apply",
+    "ev_pitch_yin",
 ]
 
 
@@ -145,6 +146,7 @@ def load_library() -> C.CDLL:
     lib.ev_mel_stats.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_trim_bounds.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]
     lib.ev_trim_apply.argtypes = [vp, vp, vp, vp, f32, i32, i32, vp, i32, vp, vp]
+    lib.ev_pitch_yin.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -380,6 +382,27 @@ class Engine:
         self._check(self.lib.ev_trim_apply(self.h, x.data_ptr(), bounds.data_ptr(), None if pk is None else pk.data_ptr(), float(target_peak), B, L,
                                            y.data_ptr(), L_out, n.data_ptr(), _stream_ptr()), "ev_trim_apply")
         return y, n
+
+    def pitch_yin(self, x, lengths=None, frame_length: int = 1024, hop_length: int = 256, tau_min: int = 36, tau_max: int = 340,
+                  threshold: float = 0.1, want_lag: bool = True, want_period: bool = True, want_cmnd: bool = True):
+        """YIN per frame of every row of ``x`` (B, L) (ev_pitch_yin): (lag (B, F) int32, period (B, F) fp32 in samples, cmnd (B, F) fp32) on
+        the device, F = ceil(L / hop_length); an output that is not wanted is None.  Unvoiced frames have lag 0 and period 0, and cmnd =
+        min d' over [tau_min, tau_max].  ``lengths`` (B,): samples per row (None: L); frames past ceil(len / hop_length) are zeros."""
+        x = self._f32(x)
+        if x.dim() != 2:
+            raise ValueError(f"pitch_yin: x must be (B, L), got shape {tuple(x.shape)}")
+        B, L = x.shape
+        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"pitch_yin: {B} lengths expected, got {ln.numel()}")
+        F = -(-L // max(int(hop_length), 1))
+        lag = torch.empty((B, F), dtype=torch.int32, device=x.device) if want_lag else None
+        period = torch.empty((B, F), dtype=torch.float32, device=x.device) if want_period else None
+        cmnd = torch.empty((B, F), dtype=torch.float32, device=x.device) if want_cmnd else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._check(self.lib.ev_pitch_yin(self.h, x.data_ptr(), ptr(ln), B, L, int(frame_length), int(hop_length), int(tau_min), int(tau_max),
+                                          float(threshold), ptr(lag), ptr(period), ptr(cmnd), _stream_ptr()), "ev_pitch_yin")
+        return lag, period, cmnd
 
     def maximum_path(self, value, x_lengths, y_lengths, want_path: bool = True, want_dur: bool = True):
         """monotonic_align.maximum_path on (B, Tx, Ty) fp32 scores with per-row lengths (ev_maximum_path): (path (B, Tx, Ty) 0/1 or None,

@@ -20,6 +20,11 @@ Between a raw take and all of that (the recorder's files begin and end on a key 
     y, (start, end) = trim_silence(y)                         # librosa.effects.trim's call shape, on the device (ev_trim_bounds / ev_trim_apply)
     y = peak_normalize(y, 0.95)                               # normalize(audio) * 0.95 of hifigan/meldataset.py:152
     y, info = prepare_recording("take.wav", 22050)            # load_audio -> trim -> level: one read of the bounds comes back to the host
+
+And beside the mel, frame for frame, the pitch (``ev_pitch_yin``: YIN; librosa.yin is the model):
+
+    p = pitch_yin(y)                                          # {"f0" (B, F) Hz, "voiced" (B, F) bool, "aperiodicity" (B, F)}, F = ceil(L / 256)
+    s = prosody_statistics(p["f0"], p["voiced"])              # voiced fraction, f0 median / 5th / 95th percentile, range in semitones per row
 """
 from __future__ import annotations
 
@@ -341,3 +346,57 @@ def prepare_recording(path, sr: int = 22050, top_db: float = 60, peak: float = 0
     start, end = (int(v) for v in bounds[0].cpu())
     out, _ = eng.trim_apply(y, bounds, pk, peak, out_len=max(end - start, 1))
     return out[0, : end - start], {"start": start, "end": end, "seconds_in": y.shape[1] / float(sr), "seconds_out": (end - start) / float(sr)}
+
+
+def pitch_lag_range(sr: int, fmin: float, fmax: float) -> Tuple[int, int]:
+    """The lags YIN searches for f0 in [fmin, fmax] at rate ``sr``: (floor(sr / fmax), ceil(sr / fmin)); the library takes 1 <= tau_min <=
+    tau_max <= 2048."""
+    if not (0 < fmin <= fmax):
+        raise ValueError(f"pitch_yin: 0 < fmin <= fmax expected (got fmin={fmin} fmax={fmax})")
+    return int(math.floor(sr / fmax)), int(math.ceil(sr / fmin))
+
+
+@torch.inference_mode()
+def pitch_yin(y, sr: int = 22050, fmin: float = 65.0, fmax: float = 600.0, frame_length: int = 1024, hop_length: int = 256,
+              threshold: float = 0.1, lengths=None):
+    """The fundamental frequency per frame by YIN on the device (``ev_pitch_yin``; no torch fallback; ``librosa.yin`` is the model): frame f
+    is centred where mel frame f of ``mel_spectrogram`` at the same hop is, so the contour lines up with the mel.  ``y`` 1-D, or (B, L)
+    with ``lengths`` (B,) samples or None, on the GPU -> {"f0" (B, F) float32 Hz, 0 where unvoiced; "voiced" (B, F) bool; "aperiodicity"
+    (B, F) float32: d' at the chosen lag, or its minimum over the search range for an unvoiced frame}, F = ceil(L / hop_length); a 1-D
+    input gives B = 1.  Frames past a row's ceil(len / hop_length) are unvoiced with aperiodicity 0."""
+    _trim_input(y, "pitch_yin")
+    tau_min, tau_max = pitch_lag_range(sr, fmin, fmax)
+    eng = _trim_engine(y.device)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    lag, period, cmnd = eng.pitch_yin(x, lengths if y.dim() == 2 else None, frame_length, hop_length, tau_min, tau_max, threshold)
+    voiced = lag > 0
+    f0 = torch.where(voiced, float(sr) / torch.where(voiced, period, torch.ones_like(period)), torch.zeros_like(period))
+    return {"f0": f0, "voiced": voiced, "aperiodicity": cmnd}
+
+
+def semitones(f_hi, f_lo):
+    return 12.0 * torch.log2(f_hi / f_lo)
+
+
+@torch.inference_mode()
+def prosody_statistics(f0, voiced, lengths=None):
+    """Per utterance, from the contour of ``pitch_yin``: {"voiced_fraction", "f0_median", "f0_p05", "f0_p95" (Hz), "f0_range_semitones" (the
+    5-to-95 range)}, each (B,) float32 where ``f0`` lives (torch ops only).  ``f0`` and ``voiced`` are (B, F) or 1-D; ``lengths`` (B,): the
+    FRAMES that belong to each row (None: F), the denominator of the voiced fraction.  Percentiles interpolate linearly (numpy's default).
+    An utterance without a voiced frame gets NaN for the pitch fields and 0 for the fraction."""
+    f0 = torch.as_tensor(f0, dtype=torch.float32)
+    voiced = torch.as_tensor(voiced, dtype=torch.bool, device=f0.device)
+    if f0.dim() == 1:
+        f0, voiced = f0.unsqueeze(0), voiced.unsqueeze(0)
+    B, F = f0.shape
+    n = torch.full((B,), F, dtype=torch.int64, device=f0.device) if lengths is None else torch.as_tensor(lengths).to(f0.device, torch.int64)
+    if n.numel() != B:
+        raise ValueError(f"prosody_statistics: {B} lengths expected, got {n.numel()}")
+    voiced = voiced & (torch.arange(F, device=f0.device)[None, :] < n[:, None])
+    count = voiced.sum(dim=1)
+    q = torch.tensor([0.05, 0.5, 0.95], dtype=torch.float32, device=f0.device)
+    pct = torch.full((B, 3), float("nan"), dtype=torch.float32, device=f0.device)
+    for b in torch.nonzero(count > 0).flatten().tolist():
+        pct[b] = torch.quantile(f0[b][voiced[b]], q)
+    return {"voiced_fraction": count.float() / n.clamp_min(1).float(), "f0_median": pct[:, 1], "f0_p05": pct[:, 0], "f0_p95": pct[:, 2],
+            "f0_range_semitones": semitones(pct[:, 2], pct[:, 0])}

@@ -13,6 +13,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --data_statistics train.txt --batch_size 32                            # train.txt.stats.json: mel_mean / mel_std
     python -m emojivoice_amd.cli --synthetic --ids "0 23 0 51 0" --sample_rate 44100                    # wavs at 44.1 kHz
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean                              # trimmed, levelled 22.05 kHz wavs + clean/filelist.txt + raw.txt.durations.json
+    python -m emojivoice_amd.cli --prosody_report clean/filelist.txt                                    # clean/filelist.txt.prosody.json: f0 per file and per speaker
 
 The wavs of --mel_from_wav, --align_wav and --data_statistics may have any sample rate (the reference's recorder writes 44.1 kHz,
 record_audio.py:31): they are resampled to the analysis rate on the device (emojivoice_amd.audio.resample).
@@ -62,6 +63,9 @@ def validate_args(args):
     if args.prepare_dataset:
         assert args.out_dir, "--prepare_dataset needs --out_dir"
         assert 0 <= args.peak <= 1, "--peak must lie in [0, 1] (0: no levelling)"
+        return args
+    if getattr(args, "prosody_report", None):
+        assert args.batch_size > 0, "Batch size must be greater than 0"
         return args
     if args.mel_from_wav:
         return args
@@ -348,6 +352,66 @@ def prepare_dataset(args, device):
     return rep
 
 
+PROSODY_SR, PROSODY_HOP = 22050, 256    # the analysis rate and the mel's hop: frame f of the contour is mel frame f
+
+
+def pitch_summary(f0_voiced):
+    """{"f0_median", "f0_p05", "f0_p95" (Hz), "f0_range_semitones"} of a 1-D tensor of voiced f0 values (linear-interpolated percentiles);
+    None for every field when it is empty."""
+    if f0_voiced.numel() == 0:
+        return {"f0_median": None, "f0_p05": None, "f0_p95": None, "f0_range_semitones": None}
+    p05, med, p95 = (float(v) for v in torch.quantile(f0_voiced.float(), torch.tensor([0.05, 0.5, 0.95], device=f0_voiced.device)))
+    return {"f0_median": med, "f0_p05": p05, "f0_p95": p95, "f0_range_semitones": 12.0 * math.log2(p95 / p05)}
+
+
+@torch.inference_mode()
+def prosody_report(args, device):
+    """--prosody_report FILELIST: the filelist --prepare_dataset writes ('path|spk|text'; 'path|text' counts as speaker "0").  Every file
+    is loaded with audio.load_audio(path, 22050) and tracked by audio.pitch_yin, --batch_size files at a time (padded to the longest,
+    each row with its own length).  FILELIST.prosody.json receives, per file, the numbers of audio.prosody_statistics (voiced fraction,
+    f0 median / 5th / 95th percentile in Hz, the 5-to-95 range in semitones; null where a file has no voiced frame) and, per speaker,
+    the same over that speaker's POOLED voiced frames, with the file count."""
+    from . import audio
+
+    entries = parse_filelist(args.prosody_report)
+    if not entries:
+        sys.exit(f"[-] {args.prosody_report}: no files listed")
+    files, pooled, frames_of = [], {}, {}
+    for b0 in range(0, len(entries), args.batch_size):
+        chunk = entries[b0:b0 + args.batch_size]
+        ys = [audio.load_audio(wav, PROSODY_SR, device) for wav, _, _ in chunk]
+        lens = [int(y.shape[-1]) for y in ys]
+        batch = torch.zeros(len(ys), max(max(lens), 1), device=ys[0].device)
+        for r, y in enumerate(ys):
+            batch[r, : lens[r]] = y.reshape(-1)
+        out = audio.pitch_yin(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
+        n_frames = [-(-n // PROSODY_HOP) for n in lens]
+        st = {k: v.cpu() for k, v in audio.prosody_statistics(out["f0"], out["voiced"], n_frames).items()}
+        for r, (wav, spk, _) in enumerate(chunk):
+            spk = spk if spk is not None else "0"
+            rec = {"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r]}
+            for k, v in st.items():
+                rec[k] = None if math.isnan(float(v[r])) else float(v[r])
+            files.append(rec)
+            pooled.setdefault(spk, []).append(out["f0"][r, : n_frames[r]][out["voiced"][r, : n_frames[r]]])
+            frames_of[spk] = frames_of.get(spk, 0) + n_frames[r]
+    speakers = {}
+    for spk, parts in pooled.items():
+        v = torch.cat(parts)
+        speakers[spk] = {"files": len(parts), "voiced_fraction": v.numel() / max(frames_of[spk], 1), **pitch_summary(v)}
+    rep = {"sample_rate": PROSODY_SR, "hop_length": PROSODY_HOP, "files": files, "speakers": speakers}
+    out_path = f"{args.prosody_report}.prosody.json"
+    with open(out_path, "w") as f:
+        json.dump(rep, f, indent=1)
+    for k in sorted(speakers):
+        v = speakers[k]
+        pitch = "no voiced frame" if v["f0_median"] is None else (f"f0 median {v['f0_median']:.1f} Hz, {v['f0_p05']:.1f} .. {v['f0_p95']:.1f} Hz "
+                                                                  f"({v['f0_range_semitones']:.1f} semitones)")
+        print(f"[i] speaker {k}: {v['files']} files, voiced {100 * v['voiced_fraction']:.0f} %, {pitch}")
+    print(f"[+] Prosody report saved: {Path(out_path).resolve()}")
+    return rep
+
+
 def loss_draws(seed: int, n_feats: int, frames: int):
     """(t (1,), z (1, n_feats, frames)) of --losses: one CPU generator seeded with --seed, t first."""
     g = torch.Generator().manual_seed(int(seed))
@@ -394,7 +458,14 @@ def cli(argv=None):
     p.add_argument("--out_dir", type=str, default=None, help="folder of --prepare_dataset's wavs and filelist.txt")
     p.add_argument("--top_db", type=float, default=60.0, help="--prepare_dataset: frames this many dB below the loudest one are silence (librosa.effects.trim)")
     p.add_argument("--peak", type=float, default=0.95, help="--prepare_dataset: peak level of the prepared recordings (hifigan/meldataset.py:152); 0: level untouched")
+    p.add_argument("--prosody_report", type=str, default=None, help="pitch analysis instead of synthesis: a filelist 'path|spk|text' (the one --prepare_dataset "
+                   "writes) -> FILELIST.prosody.json: voiced fraction, f0 median / 5th / 95th percentile and range in semitones per file and per speaker "
+                   "(YIN on the device, --batch_size files per batch; needs no checkpoint)")
     args = validate_args(p.parse_args(argv))
+    if args.prosody_report:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return prosody_report(args, torch.device("cuda", 0))
     if args.prepare_dataset:
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")

@@ -2865,6 +2865,31 @@ int ev_trim_apply(ev_handle* h, const float* d_x, const int32_t* d_bounds, const
     return 0;
 }
 
+// Pitch tracking: one workgroup per (frame, row); LDS = 4 (tau_max + 1) float64 partials + the W + tau_max + 1 staged samples (ev_kernels.h).
+int ev_pitch_yin(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, int frame_length, int hop_length, int tau_min,
+                 int tau_max, float threshold, int32_t* d_lag, float* d_period, float* d_cmnd, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (B < 1 || B > 65535) return fail(h, "ev_pitch_yin: B=%d outside 1 <= B <= 65535", B);
+    if (L < 1 || !d_x) return fail(h, "ev_pitch_yin: bad arguments L=%d (L >= 1, non-null d_x)", L);
+    const int W = frame_length, H = hop_length;
+    if (H < 64 || H > 4096 || H % 64) return fail(h, "ev_pitch_yin: hop_length=%d must be a multiple of 64 and at most 4096", H);
+    if (W < 64 || W > 4096 || W % 64) return fail(h, "ev_pitch_yin: frame_length=%d must be a multiple of 64 with 64 <= frame_length <= 4096", W);
+    if (tau_min < 1 || tau_min > tau_max || tau_max > 2048)
+        return fail(h, "ev_pitch_yin: tau_min=%d tau_max=%d outside 1 <= tau_min <= tau_max <= 2048", tau_min, tau_max);
+    if (!(threshold > 0.f && threshold <= 1.f)) return fail(h, "ev_pitch_yin: threshold=%g outside 0 < threshold <= 1", (double)threshold);
+    if (!d_lag && !d_period && !d_cmnd) return fail(h, "ev_pitch_yin: no output (at least one of d_lag, d_period, d_cmnd must be non-null)");
+    h->stream = (hipStream_t)stream;
+    PitchYinParams p{};
+    p.x = d_x; p.len = d_len; p.lag = d_lag; p.period = d_period; p.cmnd = d_cmnd;
+    p.L = L; p.F = (int)(((long long)L + H - 1) / H); p.W = W; p.H = H; p.tau_min = tau_min; p.tau_max = tau_max; p.thr = (double)threshold;
+    const size_t n = (size_t)tau_max + 1;
+    const size_t smem = 4 * n * sizeof(double) + ((size_t)W + n) * sizeof(float);
+    launch<pitch_yin_kernel>(h->device, dim3((unsigned)p.F, (unsigned)B), dim3(256), smem, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 int ev_hifigan(ev_handle* h, const float* d_mel, int B, int T, float* d_wav, void* stream) {
     if (!h) return 1;
     HIPCHK(h, hipSetDevice(h->device));

@@ -6268,6 +6268,133 @@ __global__ __launch_bounds__(256) void gather_scale_kernel(const TrimApplyParams
     }
 }
 
+// ---------------------------------------------------------------------------
+// Pitch tracking (ev_pitch_yin): de Cheveigne and Kawahara's YIN without its last ("best local estimate") step.  Frame f of a row
+// analyses the span x[s_f + i], 0 <= i < W + tau_max + 1, s_f = f H + H/2 - (W + tau_max) / 2, zeros outside [0, len):
+//   d(tau)  = sum_{j < W} (x[j] - x[j + tau])^2                       1 <= tau <= n = tau_max + 1
+//   d'(tau) = d(tau) * tau / S(tau), S(tau) = sum_{k <= tau} d(k)     (1 where S(tau) is not > 0)
+//   tau0    = the smallest tau in [tau_min, tau_max] with d'(tau) < threshold, then walked down to the local minimum on its right;
+//   period  = tau0 + the parabola's vertex through d'(tau0 - 1), d'(tau0), d'(tau0 + 1)
+// One workgroup of four waves per (frame, row).  The span is staged in LDS once, as fp32.  TILE: lane l of every wave owns the lags
+// 1 + l + 64 c of lag chunk c, four chunks at a time (one broadcast read of x[j] serves four lags; x[j + tau] over consecutive lags is
+// conflict-free); wave q covers the quarter q W/4 <= j < (q + 1) W/4 of the window for EVERY lag, so the four SIMDs carry equal work
+// whatever tau_max is.
+// ARITHMETIC of d(tau): both samples widened to float64, the difference (exact) squared and added by one fma per term, in ascending j
+// inside a quarter; d = (P0 + P1) + (P2 + P3) over the quarters' partials.  S is one ascending chain of float64 adds (one lane), d' =
+// (d * tau) / S in float64, and the decision runs in wave 0.  Nothing depends on the batch, the grid, the padding behind a row or
+// ev_set_arithmetic; no atomics.
+// LDS: 4 n float64 (the partials; later d, S and d' in place) and W + n fp32: at most 64 KiB + 24 KiB at tau_max = 2048,
+// 16.0 KiB at the defaults (W 1024, tau_max 340).
+struct PitchYinParams {
+    const float* x; const int32_t* len; int32_t* lag; float* period; float* cmnd;
+    int L, F, W, H, tau_min, tau_max;
+    double thr;
+};
+
+// The partial sums of wave `lane`'s lags in chunks c0 .. c0 + NK - 1 over j0 <= j < j1
+template <int NK>
+__device__ __forceinline__ void pitch_yin_pass(const float* xs, double* part, int c0, int n, int j0, int j1, int lane) {
+    int t[NK];
+    double a[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) { t[k] = min(1 + lane + 64 * (c0 + k), n); a[k] = 0.0; }   // (a lane past the last lag repeats it and stores nothing)
+    for (int j = j0; j < j1; ++j) {
+        const double xj = (double)xs[j];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const double d = xj - (double)xs[j + t[k]];
+            a[k] = fma(d, d, a[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int tau = 1 + lane + 64 * (c0 + k);
+        if (tau <= n) part[tau - 1] = a[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void pitch_yin_kernel(const PitchYinParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t o = (size_t)b * p.F + f;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;                                  // a bad row is a row of zeros (the ev_mas_align convention)
+    const int nf = (int)(((long long)len + p.H - 1) / p.H);
+    if (f >= nf) {                                                      // (uniform over the workgroup)
+        if (tid == 0) {
+            if (p.lag) p.lag[o] = 0;
+            if (p.period) p.period[o] = 0.f;
+            if (p.cmnd) p.cmnd[o] = 0.f;
+        }
+        return;
+    }
+    const int n = p.tau_max + 1, span = p.W + n;
+    double* part = (double*)smem;                                       // [4][n]: a quarter's partials; then row 0 = d, row 1 = S, row 2 = d'
+    float* xs = (float*)(part + 4 * (size_t)n);                         // [span]
+    const float* xrow = p.x + (size_t)b * p.L;
+    const long long s0 = (long long)f * p.H + p.H / 2 - (p.W + p.tau_max) / 2;
+    for (int i = tid; i < span; i += 256) {
+        const long long g = s0 + i;
+        xs[i] = (g >= 0 && g < len) ? xrow[g] : 0.f;
+    }
+    __syncthreads();
+    const int nch = (n + 63) >> 6, jq = p.W >> 2;
+    double* mine = part + (size_t)wave * n;
+    for (int c0 = 0; c0 < nch; c0 += 4) {                               // (uniform over the wave)
+        const int nk = min(4, nch - c0), j0 = wave * jq, j1 = j0 + jq;
+        if (nk == 4) pitch_yin_pass<4>(xs, mine, c0, n, j0, j1, lane);
+        else if (nk == 3) pitch_yin_pass<3>(xs, mine, c0, n, j0, j1, lane);
+        else if (nk == 2) pitch_yin_pass<2>(xs, mine, c0, n, j0, j1, lane);
+        else pitch_yin_pass<1>(xs, mine, c0, n, j0, j1, lane);
+    }
+    __syncthreads();
+    double* dd = part;
+    double* S = part + n;
+    double* cm = part + 2 * (size_t)n;
+    for (int i = tid; i < n; i += 256) dd[i] = (part[i] + part[n + i]) + (part[2 * (size_t)n + i] + part[3 * (size_t)n + i]);
+    __syncthreads();
+    if (tid == 0) {                                                     // S(tau): ONE ascending chain
+        double s = 0.0;
+        for (int i = 0; i < n; ++i) { s += dd[i]; S[i] = s; }
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {                                // (index i holds lag tau = i + 1)
+        const double s = S[i];
+        cm[i] = s > 0.0 ? dd[i] * (double)(i + 1) / s : 1.0;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    int first = 0x7fffffff;
+    double mn = 1.0 / 0.0;
+    for (int tau = p.tau_min + lane; tau <= p.tau_max; tau += 64) {
+        const double v = cm[tau - 1];
+        if (v < p.thr) first = min(first, tau);
+        mn = fmin(mn, v);
+    }
+#pragma unroll
+    for (int sft = 32; sft > 0; sft >>= 1) { first = min(first, __shfl_down(first, sft)); mn = fmin(mn, __shfl_down(mn, sft)); }
+    if (lane != 0) return;
+    int tau0 = 0;
+    float per = 0.f;
+    double ap = mn;                                                     // unvoiced: the smallest d' of the search range
+    if (first != 0x7fffffff) {
+        tau0 = first;
+        while (tau0 + 1 <= p.tau_max && cm[tau0] < cm[tau0 - 1]) ++tau0;
+        const double a = cm[tau0 - 2], bq = cm[tau0 - 1], c = cm[tau0];  // tau0 >= 2: d'(1) is 1 and threshold <= 1; tau0 + 1 <= n
+        const double den = a - 2.0 * bq + c;
+        double shift = 0.0;
+        if (den > 0.0) {
+            shift = 0.5 * (a - c) / den;
+            if (!(fabs(shift) <= 1.0)) shift = 0.0;
+        }
+        per = (float)((double)tau0 + shift);
+        ap = bq;
+    }
+    if (p.lag) p.lag[o] = tau0;
+    if (p.period) p.period[o] = per;
+    if (p.cmnd) p.cmnd[o] = (float)ap;
+}
+
 // broadcast a per-utterance vector (B, C) over all valid frames: dst[n][c0 + c] = v[b][c] * rowmask[n]
 __global__ void bcast_rows_kernel(const float* v, float* dst, int ld, int c0, int C, int nrows, int S, int P, int T,
                                   const float* rowmask) {

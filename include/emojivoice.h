@@ -34,6 +34,7 @@
  *   ev_load_resampler  <- no counterpart (the filter of ev_resample)
  *   ev_trim_bounds     <- no counterpart: the recorder's takes begin and end on a key press (record_audio.py); librosa.effects.trim is the model
  *   ev_trim_apply      <- the gain is normalize(audio) * 0.95 of the vocoder's dataset code                hifigan/meldataset.py:152
+ *   ev_pitch_yin       <- no counterpart: the reference never measures pitch; librosa.yin is the model
  *
  * Conventions
  *   - All tensors are fp32.  Pointers named d_* are DEVICE pointers owned by the
@@ -71,7 +72,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -336,6 +337,36 @@ int ev_trim_bounds(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d
 int ev_trim_apply(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_bounds /* (B, 2) */,
                   const float *d_peak /* (B) or NULL */, float target_peak /* <= 0: no levelling */, int B, int L,
                   float *d_y /* (B, L_out) */, int L_out, int32_t *d_out_len /* (B) */, void *stream);
+
+/* Pitch tracking on the device: de Cheveigne and Kawahara's YIN (JASA 111, 2002) without its final "best local estimate" step; librosa.yin is
+ * the model.  W = frame_length, H = hop_length, F = ceil(L / H) frames per row of the outputs; a row of len samples has ceil(len / H) frames.
+ *   framing    frame f analyses x[s_f + j], 0 <= j < W + tau_max + 1, s_f = f H + H/2 - (W + tau_max) / 2 (integer divisions): the span is
+ *              centred on the centre of frame f of ev_mel_spectrogram at the same hop.  Samples outside [0, len) enter as +0.
+ *   d(tau)     sum_{j < W} (x[j] - x[j + tau])^2 for 1 <= tau <= tau_max + 1
+ *   d'(tau)    d(tau) * tau / S(tau) where S(tau) = sum_{k <= tau} d(k) > 0, else 1 (the cumulative mean normalised difference)
+ *   decision   tau0 = the smallest tau in [tau_min, tau_max] with d'(tau) < threshold; then, while tau0 + 1 <= tau_max and
+ *              d'(tau0 + 1) < d'(tau0), tau0 advances.  No such tau: the frame is unvoiced (a silent frame has every d = 0 and is unvoiced)
+ *   refinement a, b, c = d'(tau0 - 1), d'(tau0), d'(tau0 + 1) (tau0 >= 2 because d'(1) = 1; d is computed one lag beyond tau_max);
+ *              shift = 0.5 (a - c) / (a - 2 b + c) when the denominator is > 0 and |shift| <= 1, else 0; period = tau0 + shift
+ *   d_lag (B, F) int32 or NULL     tau0, 0 when unvoiced
+ *   d_period (B, F) or NULL        the period in samples (f0 = sample rate / period), rounded once to float32; 0 when unvoiced
+ *   d_cmnd (B, F) or NULL          d'(tau0) of a voiced frame; of an unvoiced one min d' over [tau_min, tau_max], the aperiodicity a caller
+ *                                  thresholds for itself
+ *   Frames at or beyond a row's ceil(len / H) are written as zeros in all three outputs.  A row with len < 1 or len > L is no error and no
+ *   out-of-bounds access: it is written as zeros (the ev_mas_align convention).  d_len == NULL: every row is L long.
+ * Limits, each violation failing with a message that names it: 1 <= B <= 65535; hop_length a multiple of 64 and at most 4096; frame_length a
+ *   multiple of 64 with 64 <= frame_length <= 4096; 1 <= tau_min <= tau_max <= 2048; 0 < threshold <= 1; at least one output non-NULL.
+ * Arithmetic: all of it float64, in one fixed order.  Both fp32 samples are widened, so the difference is exact; it is squared and added by one
+ *   fma per term, in ascending j within each quarter [q W/4, (q + 1) W/4) of the window (one lane per lag and quarter), and
+ *   d = (P0 + P1) + (P2 + P3) over the four quarters' partials.  S is one chain of adds in ascending tau, d' = (d * tau) / S.  No atomics.
+ *   Nothing depends on the batch, the grid or ev_set_arithmetic: a row alone, inside a batch, or as the d_len prefix of a longer padded row,
+ *   and a second call, give the same bits.
+ * One kernel launch (pitch_yin_kernel, one workgroup per frame and row) on `stream`; capturable; no weights and no scratch: ev_alloc_count
+ *   never moves.  Cost: W (tau_max + 1) float64 fmas per frame. */
+int ev_pitch_yin(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L,
+                 int frame_length /* W */, int hop_length /* H */, int tau_min, int tau_max, float threshold,
+                 int32_t *d_lag /* (B, F) or NULL */, float *d_period /* (B, F) or NULL */, float *d_cmnd /* (B, F) or NULL */,
+                 void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

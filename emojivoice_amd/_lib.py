@@ -29,7 +29,7 @@ EXPORTS = [
     "ev_estimator_rows", "ev_cfm_loss",
     "ev_load_resampler", "ev_resample", "ev_mel_stats",
     "ev_trim_bounds", "ev_trim_apply",
-    "ev_pitch_yin",
+    "ev_pitch_yin", "ev_dtw",
 ]
 
 
@@ -147,6 +147,7 @@ def load_library() -> C.CDLL:
     lib.ev_trim_bounds.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]
     lib.ev_trim_apply.argtypes = [vp, vp, vp, vp, f32, i32, i32, vp, i32, vp, vp]
     lib.ev_pitch_yin.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]
+    lib.ev_dtw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -403,6 +404,36 @@ class Engine:
         self._check(self.lib.ev_pitch_yin(self.h, x.data_ptr(), ptr(ln), B, L, int(frame_length), int(hop_length), int(tau_min), int(tau_max),
                                           float(threshold), ptr(lag), ptr(period), ptr(cmnd), _stream_ptr()), "ev_pitch_yin")
         return lag, period, cmnd
+
+    DTW_METRICS = {"euclidean": 0, "sqeuclidean": 1}
+
+    def dtw(self, x, y, x_lengths=None, y_lengths=None, metric="euclidean", want_path: bool = True):
+        """Dynamic time warping of ``x`` (B, C, Tx) against ``y`` (B, C, Ty) (ev_dtw): (cost (B,) float64, steps (B,) int32, path
+        (B, Tx + Ty - 1, 2) int32 or None) on the device.  Row b's path holds (i, j) for k < steps[b], ascending from (0, 0), and (-1, -1)
+        behind.  ``x_lengths`` / ``y_lengths`` (B,): frames per row (None: the padded size).  ``metric``: "euclidean" (0) or "sqeuclidean"
+        (1), or the integer itself."""
+        x, y = self._f32(x), self._f32(y)
+        if x.dim() != 3 or y.dim() != 3 or x.shape[:2] != y.shape[:2]:
+            raise ValueError(f"dtw: x (B, C, Tx) and y (B, C, Ty) expected, got {tuple(x.shape)} and {tuple(y.shape)}")
+        if isinstance(metric, str):
+            if metric not in self.DTW_METRICS:
+                raise ValueError(f"dtw: metric {metric!r} is none of {sorted(self.DTW_METRICS)}")
+            metric = self.DTW_METRICS[metric]
+        B, C, Tx = x.shape
+        Ty = y.shape[2]
+        lens = []
+        for name, v in (("x_lengths", x_lengths), ("y_lengths", y_lengths)):
+            v = None if v is None else torch.as_tensor(v).to(x.device, torch.int32).contiguous()
+            if v is not None and v.numel() != B:
+                raise ValueError(f"dtw: {B} {name} expected, got {v.numel()}")
+            lens.append(v)
+        cost = torch.empty((B,), dtype=torch.float64, device=x.device)
+        steps = torch.empty((B,), dtype=torch.int32, device=x.device)
+        path = torch.empty((B, max(Tx + Ty - 1, 0), 2), dtype=torch.int32, device=x.device) if want_path else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._check(self.lib.ev_dtw(self.h, x.data_ptr(), y.data_ptr(), ptr(lens[0]), ptr(lens[1]), B, C, Tx, Ty, int(metric), cost.data_ptr(),
+                                    steps.data_ptr(), ptr(path), _stream_ptr()), "ev_dtw")
+        return cost, steps, path
 
     def maximum_path(self, value, x_lengths, y_lengths, want_path: bool = True, want_dur: bool = True):
         """monotonic_align.maximum_path on (B, Tx, Ty) fp32 scores with per-row lengths (ev_maximum_path): (path (B, Tx, Ty) 0/1 or None,

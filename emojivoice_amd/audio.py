@@ -25,6 +25,12 @@ And beside the mel, frame for frame, the pitch (``ev_pitch_yin``: YIN; librosa.y
 
     p = pitch_yin(y)                                          # {"f0" (B, F) Hz, "voiced" (B, F) bool, "aperiodicity" (B, F)}, F = ceil(L / 256)
     s = prosody_statistics(p["f0"], p["voiced"])              # voiced fraction, f0 median / 5th / 95th percentile, range in semitones per row
+
+And between a recording and its synthesised rendering, which differ in length and timing (``ev_dtw``: dynamic time warping):
+
+    a = dtw(mel_cepstrum(mel_a), mel_cepstrum(mel_b))         # {"cost" (B,) float64, "steps" (B,), "path" (B, Ta + Tb - 1, 2)}
+    mcd = mel_cepstral_distortion(mel_a, mel_b)               # dB per utterance over the aligned frame pairs
+    e = f0_errors(f0_a, voiced_a, f0_b, voiced_b, a["path"], a["steps"])   # f0 RMSE in cents, voicing-decision error along the path
 """
 from __future__ import annotations
 
@@ -400,3 +406,95 @@ def prosody_statistics(f0, voiced, lengths=None):
         pct[b] = torch.quantile(f0[b][voiced[b]], q)
     return {"voiced_fraction": count.float() / n.clamp_min(1).float(), "f0_median": pct[:, 1], "f0_p05": pct[:, 0], "f0_p95": pct[:, 2],
             "f0_range_semitones": semitones(pct[:, 2], pct[:, 0])}
+
+
+MCD_DB = 10.0 * math.sqrt(2.0) / math.log(10.0)    # dB per unit of Euclidean distance between natural-log cepstra (6.1418...)
+
+
+def dct_matrix(n_mels: int, n_coeffs: int) -> np.ndarray:
+    """Rows 1 .. n_coeffs of the orthonormal DCT-II over ``n_mels`` points, float64 (n_coeffs, n_mels): row k is
+    sqrt(2 / n) cos(pi k (2 m + 1) / (2 n)).  Row 0, the energy, is not among them."""
+    if not 1 <= n_coeffs < n_mels:
+        raise ValueError(f"mel_cepstrum: 1 <= n_coeffs < n_mels expected (got n_coeffs={n_coeffs} n_mels={n_mels})")
+    k = np.arange(1, n_coeffs + 1, dtype=np.float64)[:, None]
+    m = np.arange(n_mels, dtype=np.float64)[None, :]
+    return math.sqrt(2.0 / n_mels) * np.cos(math.pi * k * (2.0 * m + 1.0) / (2.0 * n_mels))
+
+
+@torch.inference_mode()
+def mel_cepstrum(mel, n_coeffs: int = 13):
+    """Mel-cepstral coefficients 1 .. ``n_coeffs`` of a log-mel (B, n_mels, T): the orthonormal DCT-II over the mel axis without its 0th
+    coefficient (the energy).  The float64 matrix is applied in float64 and the result rounded once to float32: (B, n_coeffs, T) where
+    ``mel`` lives (torch ops only)."""
+    if mel.dim() != 3:
+        raise ValueError(f"mel_cepstrum: mel must be (B, n_mels, T), got shape {tuple(mel.shape)}")
+    D = torch.from_numpy(dct_matrix(int(mel.shape[1]), n_coeffs)).to(mel.device)
+    return torch.matmul(D, mel.to(torch.float64)).to(torch.float32)
+
+
+@torch.inference_mode()
+def dtw(x, y, x_lengths=None, y_lengths=None, metric="euclidean"):
+    """Dynamic time warping on the device (``ev_dtw``; no torch fallback) of ``x`` (B, C, Tx) against ``y`` (B, C, Ty), or (C, T) each for
+    one pair: {"cost" (B,) float64: the summed local cost along the best monotone path from (0, 0) to (tx-1, ty-1) with steps diagonal /
+    up / left; "steps" (B,) int32: its length K; "path" (B, Tx + Ty - 1, 2) int32: (i, j) per step, (-1, -1) from K on}.  ``metric``:
+    "euclidean" or "sqeuclidean" between frames."""
+    if not torch.is_tensor(x) or not torch.is_tensor(y) or x.dim() != y.dim() or x.dim() not in (2, 3):
+        raise ValueError("dtw: x and y must both be (C, T) tensors or (B, C, T) batches")
+    if not x.is_cuda or not y.is_cuda:
+        raise EvLibraryError("dtw runs on a ROCm GPU only (no CPU fallback): move x and y to the GPU")
+    if x.dim() == 2:
+        x, y = x.unsqueeze(0), y.unsqueeze(0)
+    cost, steps, path = _trim_engine(x.device).dtw(x, y, x_lengths, y_lengths, metric)
+    return {"cost": cost, "steps": steps, "path": path}
+
+
+def mcd_from_cost(cost, steps):
+    """MCD in dB from the DTW cost over Euclidean cepstral distances and the path length: (10 sqrt 2 / ln 10) cost / steps, float64;
+    NaN where steps is 0."""
+    cost = torch.as_tensor(cost, dtype=torch.float64)
+    steps = torch.as_tensor(steps).to(cost.device, torch.float64)
+    return torch.where(steps > 0, MCD_DB * cost / steps.clamp_min(1.0), torch.full_like(cost, float("nan")))
+
+
+@torch.inference_mode()
+def mel_cepstral_distortion(mel_a, mel_b, len_a=None, len_b=None, n_coeffs: int = 13):
+    """Per-utterance mel-cepstral distortion in dB between two log-mels (B, n_mels, Ta) and (B, n_mels, Tb) of different lengths, (B,)
+    float64 on the device: MCD = (10 sqrt 2 / ln 10) * cost / steps, the mean over the frame pairs that dynamic time warping aligns
+    (``ev_dtw`` over the Euclidean distance of ``mel_cepstrum``'s coefficients 1 .. ``n_coeffs``) — the convention of mel-spectrogram
+    MCD-DTW.  ``len_a`` / ``len_b`` (B,): frames per row (None: all).
+
+    The cepstrum is computed from the log-mel's DCT, not from a WORLD spectral envelope: the figure is comparable across this project's
+    runs, not with published WORLD-based MCD figures."""
+    out = dtw(mel_cepstrum(mel_a, n_coeffs), mel_cepstrum(mel_b, n_coeffs), len_a, len_b, "euclidean")
+    return mcd_from_cost(out["cost"], out["steps"])
+
+
+@torch.inference_mode()
+def f0_errors(f0_a, voiced_a, f0_b, voiced_b, path, steps):
+    """Pitch agreement over a DTW path, per utterance: ``f0_a`` / ``voiced_a`` (B, Fa), ``f0_b`` / ``voiced_b`` (B, Fb), ``path``
+    (B, P, 2) and ``steps`` (B,) as ``dtw`` returns them (row b uses its first steps[b] pairs (i, j): frame i of a against frame j of b).
+    -> {"rmse_cents": list of B floats, the RMS of 1200 log2(f0_a[i] / f0_b[j]) over the pairs where both are voiced, None without such
+    a pair; "voicing_error" (B,) float64: the share of pairs whose voicing flags differ (NaN for no pair); "voiced_pairs" (B,) int64;
+    "sq_cents" (B,) float64: the sum of the squared cents, for pooling}.  Gathers and reductions in torch where ``f0_a`` lives, float64."""
+    f0_a, f0_b = torch.as_tensor(f0_a).to(torch.float64), torch.as_tensor(f0_b).to(torch.float64)
+    dev = f0_a.device
+    f0_b = f0_b.to(dev)
+    voiced_a, voiced_b = torch.as_tensor(voiced_a).to(dev, torch.bool), torch.as_tensor(voiced_b).to(dev, torch.bool)
+    path, steps = torch.as_tensor(path).to(dev, torch.int64), torch.as_tensor(steps).to(dev, torch.int64)
+    if f0_a.dim() == 1:
+        f0_a, f0_b, voiced_a, voiced_b, path, steps = (f0_a[None], f0_b[None], voiced_a[None], voiced_b[None], path[None], steps.reshape(1))
+    P = path.shape[1]
+    valid = torch.arange(P, device=dev)[None, :] < steps[:, None]
+    i, j = path[..., 0].clamp_min(0), path[..., 1].clamp_min(0)
+    fa, fb = torch.gather(f0_a, 1, i), torch.gather(f0_b, 1, j)
+    va, vb = torch.gather(voiced_a, 1, i) & valid, torch.gather(voiced_b, 1, j) & valid
+    both = va & vb
+    one = torch.ones_like(fa)
+    cents = 1200.0 * torch.log2(torch.where(both, fa, one) / torch.where(both, fb, one))
+    sq = (cents * cents).sum(dim=1)
+    n_both = both.sum(dim=1)
+    n = valid.sum(dim=1)
+    verr = torch.where(n > 0, (va ^ vb).sum(dim=1).to(torch.float64) / n.clamp_min(1).to(torch.float64),
+                       torch.full((n.numel(),), float("nan"), dtype=torch.float64, device=dev))
+    rmse = [math.sqrt(s / c) if c > 0 else None for s, c in zip(sq.tolist(), n_both.tolist())]
+    return {"rmse_cents": rmse, "voicing_error": verr, "voiced_pairs": n_both, "sq_cents": sq}

@@ -14,6 +14,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --synthetic --ids "0 23 0 51 0" --sample_rate 44100                    # wavs at 44.1 kHz
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean                              # trimmed, levelled 22.05 kHz wavs + clean/filelist.txt + raw.txt.durations.json
     python -m emojivoice_amd.cli --prosody_report clean/filelist.txt                                    # clean/filelist.txt.prosody.json: f0 per file and per speaker
+    python -m emojivoice_amd.cli --evaluate_pairs pairs.txt                                             # pairs.txt.eval.json: MCD, f0 RMSE, voicing error per 'recorded.wav|synthesised.wav[|spk]'
 
 The wavs of --mel_from_wav, --align_wav and --data_statistics may have any sample rate (the reference's recorder writes 44.1 kHz,
 record_audio.py:31): they are resampled to the analysis rate on the device (emojivoice_amd.audio.resample).
@@ -64,7 +65,7 @@ def validate_args(args):
         assert args.out_dir, "--prepare_dataset needs --out_dir"
         assert 0 <= args.peak <= 1, "--peak must lie in [0, 1] (0: no levelling)"
         return args
-    if getattr(args, "prosody_report", None):
+    if getattr(args, "prosody_report", None) or getattr(args, "evaluate_pairs", None):
         assert args.batch_size > 0, "Batch size must be greater than 0"
         return args
     if args.mel_from_wav:
@@ -412,6 +413,106 @@ def prosody_report(args, device):
     return rep
 
 
+EVAL_MEL = (1024, 80, 22050, 256, 1024, 0, 8000)    # n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax of the vocoder config
+EVAL_MAX_FRAMES = 4096                              # ev_dtw's limit per side (47.5 s)
+
+
+def parse_pairs(path):
+    """The lines of a pairs file as (recorded wav, synthesised wav, speaker): 'recorded.wav|synthesised.wav' or
+    'recorded.wav|synthesised.wav|spk'; no speaker column counts as "0".  Relative paths resolve as in parse_filelist."""
+    flist = Path(path)
+
+    def resolve(wav):
+        wav = wav.strip()
+        return str(flist.parent / wav) if not os.path.exists(wav) and (flist.parent / wav).exists() else wav
+
+    out = []
+    for ln in flist.read_text(encoding="utf-8").splitlines():
+        if not ln.strip():
+            continue
+        fields = ln.split("|")
+        if len(fields) < 2:
+            sys.exit(f"[-] {path}: 'recorded.wav|synthesised.wav[|spk]' expected, got {ln!r}")
+        out.append((resolve(fields[0]), resolve(fields[1]), fields[2].strip() if len(fields) >= 3 and fields[2].strip() else "0"))
+    return out
+
+
+def evaluation_means(pairs):
+    """The means over per-pair records: MCD and voicing error averaged over the pairs, the f0 RMSE pooled over all both-voiced frame
+    pairs (None without one)."""
+    n = len(pairs)
+    voiced = sum(p["voiced_pairs"] for p in pairs)
+    sq = math.fsum(p["f0_rmse_cents"] ** 2 * p["voiced_pairs"] for p in pairs if p["f0_rmse_cents"] is not None)
+    return {"pairs": n, "mcd_db": math.fsum(p["mcd_db"] for p in pairs) / n, "f0_rmse_cents": math.sqrt(sq / voiced) if voiced else None,
+            "voicing_error": math.fsum(p["voicing_error"] for p in pairs) / n, "voiced_pairs": voiced}
+
+
+@torch.inference_mode()
+def evaluate_pairs(args, device):
+    """--evaluate_pairs PAIRS: how close is what the model says to what the actor recorded.  Each line names a recording and the
+    synthesised wav of the same sentence (and optionally the speaker).  Both go through wav_at_rate(..., 22050), the vocoder config's mel,
+    audio.mel_cepstrum, and audio.pitch_yin (whose first L / 256 frames are the mel's); ev_dtw aligns the two cepstral sequences,
+    --batch_size pairs at a time (padded to the longest, each row with its lengths).  PAIRS.eval.json receives per pair mcd_db,
+    f0_rmse_cents (null without a frame pair voiced on both sides), voicing_error, voiced_pairs, frames_recorded, frames_synthesised and
+    path_steps; per speaker and overall their means, f0 pooled over the both-voiced frame pairs; and under "skipped" the pairs with a file
+    too short for a mel (or longer than 4096 frames).  Needs no checkpoint."""
+    from . import audio
+
+    entries = parse_pairs(args.evaluate_pairs)
+    if not entries:
+        sys.exit(f"[-] {args.evaluate_pairs}: no pairs listed")
+    sr, hop = EVAL_MEL[2], EVAL_MEL[3]
+    records, skipped = [], []
+
+    def side(wavs):
+        """mel cepstra (B, 13, T) padded with zeros, frames per row, and the pitch of every row"""
+        frames = [w.shape[1] // hop for w in wavs]
+        cep = torch.zeros(len(wavs), 13, max(frames), device=device)
+        sig = torch.zeros(len(wavs), max(frames) * hop, device=device)
+        for r, w in enumerate(wavs):
+            cep[r, :, : frames[r]] = audio.mel_cepstrum(audio.mel_spectrogram(w, *EVAL_MEL), 13)[0]   # per file: each signal's own reflect padding
+            sig[r, : w.shape[1]] = w[0]
+        return cep, frames, audio.pitch_yin(sig, sr, hop_length=hop, lengths=[w.shape[1] for w in wavs])
+
+    for b0 in range(0, len(entries), args.batch_size):
+        chunk = []
+        for rec, syn, spk in entries[b0:b0 + args.batch_size]:
+            a, b = wav_at_rate(rec, sr, device), wav_at_rate(syn, sr, device)
+            short = [p for p, w in ((rec, a), (syn, b)) if w is None]
+            long_ = [p for p, w in ((rec, a), (syn, b)) if w is not None and w.shape[1] // hop > EVAL_MAX_FRAMES]
+            if short or long_:
+                skipped.append({"recorded": rec, "synthesised": syn, "speaker": spk,
+                                "reason": (f"too short for a mel: {', '.join(short)}" if short else f"longer than {EVAL_MAX_FRAMES} frames: {', '.join(long_)}")})
+                continue
+            chunk.append((rec, syn, spk, a, b))
+        if not chunk:
+            continue
+        cep_a, fr_a, pitch_a = side([c[3] for c in chunk])
+        cep_b, fr_b, pitch_b = side([c[4] for c in chunk])
+        al = audio.dtw(cep_a, cep_b, fr_a, fr_b, "euclidean")
+        mcd = audio.mcd_from_cost(al["cost"], al["steps"]).cpu()
+        f0 = audio.f0_errors(pitch_a["f0"], pitch_a["voiced"], pitch_b["f0"], pitch_b["voiced"], al["path"], al["steps"])
+        steps, verr, nv = al["steps"].cpu(), f0["voicing_error"].cpu(), f0["voiced_pairs"].cpu()
+        for r, (rec, syn, spk, _, _) in enumerate(chunk):
+            records.append({"recorded": rec, "synthesised": syn, "speaker": spk, "mcd_db": float(mcd[r]), "f0_rmse_cents": f0["rmse_cents"][r],
+                            "voicing_error": float(verr[r]), "voiced_pairs": int(nv[r]), "frames_recorded": fr_a[r], "frames_synthesised": fr_b[r],
+                            "path_steps": int(steps[r])})
+    by_spk = {}
+    for r in records:
+        by_spk.setdefault(r["speaker"], []).append(r)
+    rep = {"sample_rate": sr, "hop_length": hop, "n_coeffs": 13, "pairs": records, "speakers": {k: evaluation_means(v) for k, v in by_spk.items()},
+           "overall": evaluation_means(records) if records else None, "skipped": skipped}
+    out_path = f"{args.evaluate_pairs}.eval.json"
+    with open(out_path, "w") as f:
+        json.dump(rep, f, indent=1)
+    for k in sorted(rep["speakers"]):
+        v = rep["speakers"][k]
+        f0s = "no frame pair voiced on both sides" if v["f0_rmse_cents"] is None else f"f0 RMSE {v['f0_rmse_cents']:.1f} cents"
+        print(f"[i] speaker {k}: {v['pairs']} pairs, MCD {v['mcd_db']:.2f} dB, {f0s}, voicing error {100 * v['voicing_error']:.1f} %")
+    print(f"[+] Evaluation report saved: {Path(out_path).resolve()}  ({len(records)} pairs, {len(skipped)} skipped)")
+    return rep
+
+
 def loss_draws(seed: int, n_feats: int, frames: int):
     """(t (1,), z (1, n_feats, frames)) of --losses: one CPU generator seeded with --seed, t first."""
     g = torch.Generator().manual_seed(int(seed))
@@ -461,7 +562,14 @@ def cli(argv=None):
     p.add_argument("--prosody_report", type=str, default=None, help="pitch analysis instead of synthesis: a filelist 'path|spk|text' (the one --prepare_dataset "
                    "writes) -> FILELIST.prosody.json: voiced fraction, f0 median / 5th / 95th percentile and range in semitones per file and per speaker "
                    "(YIN on the device, --batch_size files per batch; needs no checkpoint)")
+    p.add_argument("--evaluate_pairs", type=str, default=None, help="objective evaluation instead of synthesis: a file of 'recorded.wav|synthesised.wav[|spk]' lines -> "
+                   "PAIRS.eval.json: mel-cepstral distortion (dB), f0 RMSE (cents) and voicing-decision error over the DTW path per pair, per speaker "
+                   "and overall (DTW on the device, --batch_size pairs per batch; needs no checkpoint)")
     args = validate_args(p.parse_args(argv))
+    if args.evaluate_pairs:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return evaluate_pairs(args, torch.device("cuda", 0))
     if args.prosody_report:
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")

@@ -139,6 +139,7 @@ struct ev_handle {
     // small per-stage scratch arenas (denoiser, text encoder): grown on demand, ordered against their last user's stream
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
     Scratch dn_ws, enc_ws, mas_ws;   // (mas_ws: the alignment search's frame -> token index and, for large Tx * Ty, its decision bits)
+    Scratch dtw_ws;                  // (ev_dtw's decision bits where they do not fit in LDS)
     Scratch stat_ws;                 // ev_mel_stats: the per-(row, 32 frames) partial sums
     Scratch trim_ws;                 // ev_trim_bounds: the per-(row, hop block) sum of squares (float64) and max |x| (fp32)
     float* zeros = nullptr;     // 4096 zero floats (stand-in bias for the fused kernels' unconditional loads)
@@ -1983,6 +1984,7 @@ void ev_destroy(ev_handle* h) {
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
     if (h->enc_ws.p) hipFree(h->enc_ws.p);
     if (h->mas_ws.p) hipFree(h->mas_ws.p);
+    if (h->dtw_ws.p) hipFree(h->dtw_ws.p);
     if (h->stat_ws.p) hipFree(h->stat_ws.p);
     if (h->trim_ws.p) hipFree(h->trim_ws.p);
     if (h->dn_ws.p) hipFree(h->dn_ws.p);
@@ -2886,6 +2888,47 @@ int ev_pitch_yin(ev_handle* h, const float* d_x, const int32_t* d_len, int B, in
     const size_t n = (size_t)tau_max + 1;
     const size_t smem = 4 * n * sizeof(double) + ((size_t)W + n) * sizeof(float);
     launch<pitch_yin_kernel>(h->device, dim3((unsigned)p.F, (unsigned)B), dim3(256), smem, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Dynamic time warping: one workgroup per row (dtw_kernel, ev_kernels.h).  LDS plan in bytes: [D ring 3 x Tx float64][S ring 3 x Tx uint16],
+// reused after the forward pass as the path stage of Tx + Ty - 1 words; then the decision words ceil(Ty / 32) x Tx x 8 bytes where they still
+// fit into the CU's 160 KiB, else in the handle's arena.  Without a path there are no decision words at all.
+int ev_dtw(ev_handle* h, const float* d_x, const float* d_y, const int32_t* d_xlen, const int32_t* d_ylen, int B, int C, int Tx, int Ty, int metric,
+           double* d_cost, int32_t* d_steps, int32_t* d_path, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    constexpr size_t LDS_MAX = 160 * 1024 - 64;                          // (the kernel's one static word is taken off the CU's 160 KiB)
+    if (B < 1 || B > 65535) return fail(h, "ev_dtw: B=%d outside 1 <= B <= 65535", B);
+    if (C < 1 || C > 128) return fail(h, "ev_dtw: C=%d outside 1 <= C <= 128", C);
+    if (Tx < 1 || Tx > 4096) return fail(h, "ev_dtw: Tx=%d outside 1 <= Tx <= 4096", Tx);
+    if (Ty < 1 || Ty > 4096) return fail(h, "ev_dtw: Ty=%d outside 1 <= Ty <= 4096", Ty);
+    if (metric != 0 && metric != 1) return fail(h, "ev_dtw: metric=%d is neither 0 (Euclidean) nor 1 (squared Euclidean)", metric);
+    if (!d_x || !d_y) return fail(h, "ev_dtw: d_x and d_y must be non-null");
+    if (!d_cost || !d_steps) return fail(h, "ev_dtw: d_cost and d_steps must be non-null");
+    h->stream = (hipStream_t)stream;
+    DtwParams p{};
+    p.x = d_x; p.y = d_y; p.xlen = d_xlen; p.ylen = d_ylen; p.cost = d_cost; p.steps = d_steps; p.path = d_path;
+    p.C = C; p.Tx = Tx; p.Ty = Ty; p.nyw = (Ty + 31) / 32; p.metric = metric;
+    p.off_s = 3 * Tx * (int)sizeof(double);
+    const size_t ring = (size_t)p.off_s + 3 * (size_t)Tx * sizeof(unsigned short);
+    size_t smem = (ring + 15) / 16 * 16;
+    if (d_path) {
+        smem = (std::max(ring, (size_t)(Tx + Ty - 1) * sizeof(unsigned int)) + 15) / 16 * 16;
+        p.off_bits = (int)smem;
+        const size_t bit_bytes = (size_t)p.nyw * Tx * sizeof(unsigned long long);
+        if (smem + bit_bytes <= LDS_MAX) smem += bit_bytes;
+        else {
+            if (scratch_acquire(h, h->dtw_ws, (size_t)B * bit_bytes)) return 1;
+            p.gbits = (unsigned long long*)h->dtw_ws.p;
+        }
+    }
+    const int NT = std::min(1024, round_up(Tx, 64));
+    const int R = (Tx + NT - 1) / NT;                                    // 1 .. 4 rows of the matrix per thread
+    if (R == 1) launch<dtw_kernel<1, 8>>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
+    else if (R == 2) launch<dtw_kernel<2, 8>>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
+    else launch<dtw_kernel<4, 4>>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -6395,6 +6395,141 @@ __global__ __launch_bounds__(256) void pitch_yin_kernel(const PitchYinParams p) 
     if (p.cmnd) p.cmnd[o] = (float)ap;
 }
 
+// ---------------------------------------------------------------------------
+// Dynamic time warping (ev_dtw): the sibling of mas_search_kernel.  For a row with tx x ty cells
+//   c[i, j] = sum_c (x[c, i] - y[c, j])^2 (float64, one fma per channel in ascending c; one __dsqrt_rn for metric 0)
+//   D[i, j] = c[i, j] + min(D[i-1, j-1], D[i-1, j], D[i, j-1]) over the predecessors that exist, a later one replacing an earlier one
+//             only when strictly smaller; S[i, j] = S[chosen] + 1, S[0, 0] = 1
+// One workgroup per row walks the tx + ty - 1 anti-diagonals k = i + j, one barrier each.  Thread t owns the matrix rows i = t + r NT,
+// r < R.  A ring of three diagonals of D (float64) and of S (16 bits: S <= 8191) lives in LDS, indexed by i: diagonal k is written to
+// buffer k % 3 while k - 1 (up, at i - 1) and k - 2 (diagonal, at i - 1) are read, which is why one barrier per diagonal is enough;
+// the left neighbour D[i, j - 1] is the thread's own previous cell and stays in a register.  The cell does exactly the sequential
+// loop's arithmetic: the wavefront is the only parallelism.
+// Local costs: W diagonals ahead of the DP each thread forms the W cells of its rows into REGISTERS (acc[R][W]): x[c, i] is read once
+// per channel and block, y[c, k - i] W times, both coalesced over i; columns are clamped into [0, ty), so nothing behind a row's length
+// is read and cells outside the matrix cost nothing that is used.  The cost matrix never exists in memory.
+// Decision: 2 bits per cell (0 diagonal, 1 up, 2 left), 32 cells of a matrix row per 64-bit word, gathered in a register and stored
+// once per 32 columns at word (j / 32) * Tx + i: in LDS where they fit beside the ring, else in the handle's arena (p.gbits); none
+// when no path is asked for.  Thread 0 replays the bits from (tx-1, ty-1) into an LDS stage that reuses the ring (K = S[tx-1, ty-1]
+// is known, so entry k goes to slot k), then the workgroup writes the path in ascending order and the -1 tail.
+// No atomics; nothing depends on B, Tx, Ty, the block size or ev_set_arithmetic.
+struct DtwParams {
+    const float* x; const float* y; const int32_t* xlen; const int32_t* ylen;
+    double* cost; int32_t* steps; int32_t* path;
+    unsigned long long* gbits;          // decision words per row [nyw][Tx], or NULL: in LDS (or no path)
+    int C, Tx, Ty, nyw, metric;
+    int off_s, off_bits;                // LDS plan in bytes (the D ring, and later the path stage, are at 0)
+};
+
+template <int R, int W>
+__global__ __launch_bounds__(1024) void dtw_kernel(const DtwParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dtw_lds[];
+    __shared__ int dtw_K;
+    const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+    const int C = p.C, Tx = p.Tx, Ty = p.Ty, NP = Tx + Ty - 1;
+    int tx = p.xlen ? p.xlen[b] : Tx, ty = p.ylen ? p.ylen[b] : Ty;
+    int32_t* path = p.path ? p.path + (size_t)b * NP * 2 : nullptr;
+    if (tx < 1 || ty < 1 || tx > Tx || ty > Ty) {                       // a bad row (uniform over the workgroup): cost 0, steps 0, path -1
+        if (tid == 0) { p.cost[b] = 0.0; p.steps[b] = 0; }
+        if (path) for (int e = tid; e < 2 * NP; e += NT) path[e] = -1;
+        return;
+    }
+    double* ring = (double*)dtw_lds;                                    // [3][Tx]
+    unsigned short* sring = (unsigned short*)(dtw_lds + p.off_s);       // [3][Tx]
+    unsigned long long* bits = !path ? nullptr : (p.gbits ? p.gbits + (size_t)b * p.nyw * Tx : (unsigned long long*)(dtw_lds + p.off_bits));
+    const float* xb = p.x + (size_t)b * C * Tx;
+    const float* yb = p.y + (size_t)b * C * Ty;
+    double leftD[R];
+    int leftS[R];
+    unsigned long long word[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) { leftD[r] = 0.0; leftS[r] = 0; word[r] = 0ull; }
+    double* d0 = ring;                                                  // diagonal k
+    double* d1 = ring + Tx;                                             // k - 1
+    double* d2 = ring + 2 * Tx;                                         // k - 2
+    unsigned short* s0 = sring;
+    unsigned short* s1 = sring + Tx;
+    unsigned short* s2 = sring + 2 * Tx;
+    const int nk = tx + ty - 1;
+    for (int k0 = 0; k0 < nk; k0 += W) {
+        double acc[R][W];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) acc[r][w] = 0.0;
+            const int i = tid + r * NT, j0 = k0 - i;
+            if (i >= tx || j0 + W <= 0 || j0 >= ty) continue;            // no cell of this row on these diagonals
+            int jc[W];
+#pragma unroll
+            for (int w = 0; w < W; ++w) jc[w] = min(max(j0 + w, 0), ty - 1);
+            for (int c = 0; c < C; ++c) {
+                const double xv = (double)xb[(size_t)c * Tx + i];
+                const float* yr = yb + (size_t)c * Ty;
+#pragma unroll
+                for (int w = 0; w < W; ++w) { const double d = xv - (double)yr[jc[w]]; acc[r][w] = fma(d, d, acc[r][w]); }
+            }
+            if (p.metric == 0) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) acc[r][w] = __dsqrt_rn(acc[r][w]);
+            }
+        }
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const int k = k0 + w;
+            if (k < nk) {                                                // (uniform)
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int i = tid + r * NT, j = k - i;
+                    if (i < tx && j >= 0 && j < ty) {
+                        double best = 0.0;
+                        int sb = 0, ch = 0;
+                        bool have = false;
+                        if (i > 0) {
+                            if (j > 0) { best = d2[i - 1]; sb = s2[i - 1]; have = true; }
+                            const double up = d1[i - 1];
+                            if (!have || up < best) { best = up; sb = s1[i - 1]; ch = 1; have = true; }
+                        }
+                        if (j > 0 && (!have || leftD[r] < best)) { best = leftD[r]; sb = leftS[r]; ch = 2; }
+                        const double D = acc[r][w] + best;               // (cell (0, 0): best = 0 is added, D = c exactly)
+                        const int S = sb + 1;
+                        d0[i] = D; s0[i] = (unsigned short)S;
+                        leftD[r] = D; leftS[r] = S;
+                        if (bits) {
+                            word[r] |= (unsigned long long)ch << (2 * (j & 31));
+                            if ((j & 31) == 31 || j == ty - 1) { bits[(size_t)(j >> 5) * Tx + i] = word[r]; word[r] = 0ull; }
+                        }
+                        if (i == tx - 1 && j == ty - 1) { p.cost[b] = D; p.steps[b] = S; dtw_K = S; }
+                    }
+                }
+                __syncthreads();
+                double* t = d2; d2 = d1; d1 = d0; d0 = t;
+                unsigned short* u = s2; s2 = s1; s1 = s0; s0 = u;
+            }
+        }
+    }
+    if (!path) return;
+    const int K = dtw_K;                                                // (written before the last barrier)
+    unsigned int* stage = (unsigned int*)dtw_lds;                       // [K]: i | j << 16, over the ring that is no longer read
+    if (tid == 0) {
+        int i = tx - 1, j = ty - 1;
+        for (int k = K - 1; k >= 0; --k) {
+            stage[k] = (unsigned int)i | ((unsigned int)j << 16);
+            int ch = (int)((bits[(size_t)(j >> 5) * Tx + i] >> (2 * (j & 31))) & 3ull);
+            if (i == 0) ch = 2; else if (j == 0) ch = 1;                 // (what the forward step recorded there; keeps the walk inside the matrix)
+            if (ch != 2) --i;
+            if (ch != 1) --j;
+            if (i < 0 || j < 0) break;                                   // (0, 0) was entry 0
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < 2 * NP; e += NT) {
+        const int k = e >> 1;
+        int v = -1;
+        if (k < K) { const unsigned int s = stage[k]; v = (e & 1) ? (int)(s >> 16) : (int)(s & 0xffffu); }
+        path[e] = v;
+    }
+}
+
 // broadcast a per-utterance vector (B, C) over all valid frames: dst[n][c0 + c] = v[b][c] * rowmask[n]
 __global__ void bcast_rows_kernel(const float* v, float* dst, int ld, int c0, int C, int nrows, int S, int P, int T,
                                   const float* rowmask) {

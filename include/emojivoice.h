@@ -35,6 +35,7 @@
  *   ev_trim_bounds     <- no counterpart: the recorder's takes begin and end on a key press (record_audio.py); librosa.effects.trim is the model
  *   ev_trim_apply      <- the gain is normalize(audio) * 0.95 of the vocoder's dataset code                hifigan/meldataset.py:152
  *   ev_pitch_yin       <- no counterpart: the reference never measures pitch; librosa.yin is the model
+ *   ev_dtw             <- no counterpart: the reference never compares what it says with what was recorded; MCD-DTW evaluation is the model
  *
  * Conventions
  *   - All tensors are fp32.  Pointers named d_* are DEVICE pointers owned by the
@@ -72,7 +73,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -367,6 +368,35 @@ int ev_pitch_yin(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_l
                  int frame_length /* W */, int hop_length /* H */, int tau_min, int tau_max, float threshold,
                  int32_t *d_lag /* (B, F) or NULL */, float *d_period /* (B, F) or NULL */, float *d_cmnd /* (B, F) or NULL */,
                  void *stream);
+
+/* Dynamic time warping on the device between two feature sequences per row: x (B, C, Tx) against y (B, C, Ty), tx = d_xlen[b] and
+ * ty = d_ylen[b] frames of them (a NULL length pointer: the padded size).  The step pattern is the plain one (diagonal, up, left; weight 1).
+ *   local cost  c[i, j] = sum_c (x[c, i] - y[c, j])^2: both fp32 values widened to float64, one float64 fma per channel in ascending c;
+ *               metric 0 (Euclidean): one correctly rounded square root follows; metric 1: the squared distance itself.  The order depends
+ *               on nothing else: not on tiling, the batch or ev_set_arithmetic.
+ *   recurrence  float64, one min chain and one add per cell: D[0, 0] = c[0, 0]; otherwise D[i, j] = c[i, j] + m, m the smallest of the
+ *               predecessors that exist, taken in the order diagonal (i-1, j-1), up (i-1, j), left (i, j-1); a later candidate replaces
+ *               an earlier one only when STRICTLY smaller, so ties go diagonal, then up, then left.  S[i, j] = S[chosen] + 1, S[0, 0] = 1.
+ *   d_cost (B) float64    D[tx-1, ty-1]
+ *   d_steps (B) int32     S[tx-1, ty-1] = K, the length of the path: max(tx, ty) <= K <= tx + ty - 1
+ *   d_path (B, Tx + Ty - 1, 2) int32 or NULL   (i_k, j_k) for k < K, ascending from (0, 0) to (tx-1, ty-1); every entry at or beyond K is
+ *                         (-1, -1).  The backtrack replays the forward step's own choice (2 bits per cell); it never compares again.
+ *   A row with tx < 1, ty < 1, tx > Tx or ty > Ty is no error and no out-of-bounds access: cost 0, steps 0, a path of -1 (the ev_mas_align
+ *   convention).  Nothing behind a row's tx / ty frames is read.  Only finite inputs are specified.
+ * Limits, each violation failing with a message that names it: 1 <= B <= 65535; 1 <= C <= 128; 1 <= Tx <= 4096; 1 <= Ty <= 4096;
+ *   metric 0 or 1; d_cost and d_steps non-NULL.
+ * One kernel launch (dtw_kernel) on `stream`, one workgroup per row walking the tx + ty - 1 anti-diagonals: latency-bound like the alignment
+ *   search.  The cell on the wavefront does the sequential loop's arithmetic, no atomics: a row alone, inside a batch, or as the length
+ *   prefix of longer padded rows, and a second call, give the same bits.  The (B, Tx, Ty) cost matrix never exists in memory.
+ * Scratch: none with d_path == NULL (ev_alloc_count never moves).  With a path, decision bits that do not fit in LDS (Tx * Ty / 4 bytes
+ *   beside 30 Tx bytes of ring in 160 KiB) live in an arena of the handle that grows on demand like the alignment search's and counts in
+ *   ev_alloc_count: a second call at the same shape allocates nothing; ev_reserve does not cover it.  No host wait and no copy: capturable
+ *   once the arena has its size. */
+int ev_dtw(ev_handle *h, const float *d_x /* (B, C, Tx) */, const float *d_y /* (B, C, Ty) */,
+           const int32_t *d_xlen /* (B) or NULL */, const int32_t *d_ylen /* (B) or NULL */,
+           int B, int C, int Tx, int Ty, int metric /* 0 Euclidean, 1 squared Euclidean */,
+           double *d_cost /* (B) */, int32_t *d_steps /* (B) */,
+           int32_t *d_path /* (B, Tx + Ty - 1, 2) or NULL */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

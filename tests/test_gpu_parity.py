@@ -345,21 +345,25 @@ def test_device_text_encoder_vs_golden_and_host(golden, model, matcha_sd):
 
 
 def test_denoiser_vs_oracle_batched(vocoder):
-    """ev_denoise / ev_stft_magnitude (DFT-basis convolutions) vs torch.stft / torch.istft in the oracle on a ragged-content
-    batch, including the shortest supported length (4 hops) and the magnitude spectrum itself."""
+    """ev_denoise / ev_stft_magnitude (DFT-basis convolutions) vs torch.stft / torch.istft on a ragged-content batch, including the
+    shortest supported length (4 hops) and the magnitude spectrum itself: every row against the fp64 yardstick at the per-row gates
+    of tests/denoiser_ref.py (set from the float32 restatement, tests/test_denoiser_reference.py; tests/test_gpu_denoiser.py has the
+    conv builds beyond this one)."""
+    import denoiser_ref as D
+
     vocoder._sync_engine()
     eng = vocoder.engine
     g = torch.Generator().manual_seed(77)
     for B, L in ((3, 256 * 21), (1, 1024)):
         audio = (torch.randn(B, L, generator=g) * 0.3).clamp(-1, 1)
         bias = torch.rand(513, generator=g) * 2.0
-        ref_spec = torch.stft(audio, n_fft=1024, hop_length=256, win_length=1024, window=torch.hann_window(1024), return_complex=True)
+        ref_mag, ref = D.yardstick(audio, bias, 0.01)
+        assert tuple(ref.shape) == tuple(O.denoiser(audio, bias[None, :, None], strength=0.01).shape)
         mag = eng.stft_magnitude(audio.cuda())
-        assert tuple(mag.shape) == tuple(ref_spec.shape)
-        assert _linf(mag, ref_spec.abs()) <= 2e-4 * float(ref_spec.abs().max())
-        ref = O.denoiser(audio, bias[None, :, None], strength=0.01)
+        assert tuple(mag.shape) == tuple(ref_mag.shape)
         got = eng.denoise(audio.cuda(), bias.cuda(), 0.01)
-        assert _linf(got, ref) <= 2e-5
+        rms, mx, mg = D.row_errors((mag, got), (ref_mag, ref), audio)
+        assert bool((rms <= D.GATE_RMS).all()) and bool((mx <= D.GATE_MAX).all()) and bool((mg <= D.GATE_MAG).all()), (B, L, rms, mx, mg)
 
 
 def test_text_encoder_short_utterances(model, matcha_sd):

@@ -30,6 +30,7 @@ EXPORTS = [
     "ev_load_resampler", "ev_resample", "ev_mel_stats",
     "ev_trim_bounds", "ev_trim_apply",
     "ev_pitch_yin", "ev_dtw",
+    "ev_loudness",
 ]
 
 
@@ -148,6 +149,7 @@ def load_library() -> C.CDLL:
     lib.ev_trim_apply.argtypes = [vp, vp, vp, vp, f32, i32, i32, vp, i32, vp, vp]
     lib.ev_pitch_yin.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]
     lib.ev_dtw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.ev_loudness.argtypes = [vp, vp, vp, i32, i32, i32, vp, C.c_double, vp, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -434,6 +436,33 @@ class Engine:
         self._check(self.lib.ev_dtw(self.h, x.data_ptr(), y.data_ptr(), ptr(lens[0]), ptr(lens[1]), B, C, Tx, Ty, int(metric), cost.data_ptr(),
                                     steps.data_ptr(), ptr(path), _stream_ptr()), "ev_dtw")
         return cost, steps, path
+
+    def loudness(self, x, lengths, sub_len: int, coef, abs_gate: float, want_sub: bool = True, want_block: bool = True):
+        """BS.1770 gated loudness of every row of ``x`` (B, L) (ev_loudness): (sub (B, L // S) float64 or None, block (B, max(L // S - 3, 0))
+        float64 or None, gated (B, 2) float64 {mean square over the blocks passing both gates, over those passing the absolute gate}, counts
+        (B, 3) int32 {blocks, passing the absolute gate, passing both}) on the device.  ``coef``: the 10 float64 of ``audio.k_weighting``,
+        read on the host during the call; ``sub_len`` = S, the samples per 100 ms; ``abs_gate`` a mean square.  ``lengths`` (B,): samples per
+        row (None: L)."""
+        x = self._f32(x)
+        if x.dim() != 2:
+            raise ValueError(f"loudness: x must be (B, L), got shape {tuple(x.shape)}")
+        B, L = x.shape
+        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"loudness: {B} lengths expected, got {ln.numel()}")
+        coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float64).reshape(-1))
+        if coef.size != 10:
+            raise ValueError(f"loudness: 10 coefficients expected, got {coef.size}")
+        S = int(sub_len)
+        NS = L // S if S > 0 else 0
+        sub = torch.empty((B, NS), dtype=torch.float64, device=x.device) if want_sub else None
+        block = torch.empty((B, max(NS - 3, 0)), dtype=torch.float64, device=x.device) if want_block else None
+        gated = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+        counts = torch.empty((B, 3), dtype=torch.int32, device=x.device)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._check(self.lib.ev_loudness(self.h, x.data_ptr(), ptr(ln), B, L, S, coef.ctypes.data, float(abs_gate), ptr(sub), ptr(block),
+                                         gated.data_ptr(), counts.data_ptr(), _stream_ptr()), "ev_loudness")
+        return sub, block, gated, counts
 
     def maximum_path(self, value, x_lengths, y_lengths, want_path: bool = True, want_dur: bool = True):
         """monotonic_align.maximum_path on (B, Tx, Ty) fp32 scores with per-row lengths (ev_maximum_path): (path (B, Tx, Ty) 0/1 or None,

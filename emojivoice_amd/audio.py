@@ -31,6 +31,11 @@ And between a recording and its synthesised rendering, which differ in length an
     a = dtw(mel_cepstrum(mel_a), mel_cepstrum(mel_b))         # {"cost" (B,) float64, "steps" (B,), "path" (B, Ta + Tb - 1, 2)}
     mcd = mel_cepstral_distortion(mel_a, mel_b)               # dB per utterance over the aligned frame pairs
     e = f0_errors(f0_a, voiced_a, f0_b, voiced_b, a["path"], a["steps"])   # f0 RMSE in cents, voicing-decision error along the path
+
+And level as a listener hears it (``ev_loudness``: ITU-R BS.1770-4 / EBU R 128 integrated loudness; peak says little about it):
+
+    r = loudness(y)                                           # {"integrated" (B,) LUFS, "momentary" (B, NB) LUFS, "blocks", "gated_blocks", "sub_energy"}
+    y, gain_db, capped = loudness_normalize(y, -23.0)         # every row to -23 LUFS, the gain capped where the peak would pass 0.95
 """
 from __future__ import annotations
 
@@ -498,3 +503,93 @@ def f0_errors(f0_a, voiced_a, f0_b, voiced_b, path, steps):
                        torch.full((n.numel(),), float("nan"), dtype=torch.float64, device=dev))
     rmse = [math.sqrt(s / c) if c > 0 else None for s, c in zip(sq.tolist(), n_both.tolist())]
     return {"rmse_cents": rmse, "voicing_error": verr, "voiced_pairs": n_both, "sq_cents": sq}
+
+
+# ---- loudness: ITU-R BS.1770-4 / EBU R 128 -------------------------------------------------------------------------------------------------
+LOUDNESS_OFFSET = -0.691                                       # LUFS = -0.691 + 10 log10(mean square of the K-weighted signal)
+ABSOLUTE_GATE = 10.0 ** ((-70.0 - LOUDNESS_OFFSET) / 10.0)     # the -70 LUFS gate as a mean square
+
+
+def k_weighting(sr: int) -> np.ndarray:
+    """The K-weighting of BS.1770-4 at rate ``sr``: 10 float64 {b0, b1, b2, a1, a2} of the high shelf, then of the high pass (a0 = 1), the
+    layout ``ev_loudness`` takes.  The standard tabulates the two biquads at 48 kHz only; they are the bilinear transforms of an analogue
+    shelf (f0 1681.97 Hz, +4.00 dB, Q 0.7072) and an analogue high pass (f0 38.135 Hz, Q 0.5003), and this is that design at any rate:
+    ``k_weighting(48000)`` equals the table to better than 1e-13.  ``sr`` must be a multiple of 10 (a 100 ms sub-block is a whole number of
+    samples) and at least 8000 (the shelf's f0 must stay well below Nyquist)."""
+    if int(sr) != sr or int(sr) % 10 or int(sr) < 8000:
+        raise ValueError(f"k_weighting: sr must be a multiple of 10 and at least 8000 (got {sr})")
+    sr = int(sr)
+    f0, gain_db, q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    k = math.tan(math.pi * f0 / sr)
+    vh = 10.0 ** (gain_db / 20.0)
+    vb = vh ** 0.4996667741545416
+    a0 = 1.0 + k / q + k * k
+    shelf = [(vh + vb * k / q + k * k) / a0, 2.0 * (k * k - vh) / a0, (vh - vb * k / q + k * k) / a0, 2.0 * (k * k - 1.0) / a0, (1.0 - k / q + k * k) / a0]
+    f0, q = 38.13547087602444, 0.5003270373238773
+    k = math.tan(math.pi * f0 / sr)
+    a0 = 1.0 + k / q + k * k
+    return np.array(shelf + [1.0, -2.0, 1.0, 2.0 * (k * k - 1.0) / a0, (1.0 - k / q + k * k) / a0], dtype=np.float64)
+
+
+def lufs(mean_square):
+    """-0.691 + 10 log10(mean square) of a float64 tensor; -inf where it is not positive."""
+    ms = torch.as_tensor(mean_square, dtype=torch.float64)
+    return torch.where(ms > 0, LOUDNESS_OFFSET + 10.0 * torch.log10(ms.clamp_min(1e-300)), torch.full_like(ms, float("-inf")))
+
+
+@torch.inference_mode()
+def loudness(y, sr: int = 22050, lengths=None):
+    """Integrated loudness by ITU-R BS.1770-4 on the device (``ev_loudness``; no torch fallback) of mono ``y``, 1-D or (B, L) with
+    ``lengths`` (B,) samples or None, on the GPU: the signal through ``k_weighting(sr)``, mean squares over 400 ms blocks every 100 ms, the
+    absolute gate at -70 LUFS and the relative gate 10 LU below the loudness of what passed it.  -> {"integrated" (B,) float64 LUFS, -inf
+    where no block passes (silence, or a row under 400 ms); "momentary" (B, NB) float64: the LUFS of every block, -inf past a row's own blocks
+    and for digital silence; "blocks" (B,) int32: the row's 400 ms blocks; "gated_blocks" (B,) int32: those that passed both gates;
+    "sub_energy" (B, L // S) float64: the sum of squares of the K-weighted signal per 100 ms, S = sr / 10}; a 1-D input gives B = 1.  The
+    incomplete last 100 ms of a row is discarded, as the standard says."""
+    coef = k_weighting(sr)
+    _trim_input(y, "loudness")
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    sub, block, gated, counts = _trim_engine(y.device).loudness(x, lengths if y.dim() == 2 else None, int(sr) // 10, coef, ABSOLUTE_GATE)
+    return {"integrated": lufs(gated[:, 0]), "momentary": lufs(block), "blocks": counts[:, 0], "gated_blocks": counts[:, 2], "sub_energy": sub}
+
+
+@torch.inference_mode()
+def peak_level(y, lengths=None):
+    """max |y| per row, (B,) float32 on the device (``ev_trim_bounds``' d_peak): ``y`` 1-D or (B, L) with ``lengths`` (B,) or None."""
+    _trim_input(y, "peak_level")
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    _, pk = _trim_engine(y.device).trim_bounds(x, lengths if y.dim() == 2 else None)
+    return pk
+
+
+def loudness_gain(integrated, peak, target_lufs: float = -23.0, peak_ceiling: float = 0.95):
+    """The gain that takes a row of loudness ``integrated`` (LUFS) and peak ``peak`` to ``target_lufs``: 10^((target - L) / 20), capped at
+    peak_ceiling / peak so that the levelled peak stays at or under the ceiling (``peak_ceiling`` None or <= 0: no cap).  A row without a
+    loudness (L = -inf) keeps gain 1.  -> (gain (B,) float64, gain_db (B,) float64, capped (B,) bool); torch ops where ``integrated`` lives."""
+    loud = torch.as_tensor(integrated, dtype=torch.float64)
+    pk = torch.as_tensor(peak).to(loud.device, torch.float64)
+    measured = torch.isfinite(loud)
+    gain = torch.where(measured, 10.0 ** ((float(target_lufs) - torch.where(measured, loud, torch.zeros_like(loud))) / 20.0), torch.ones_like(loud))
+    capped = torch.zeros_like(measured)
+    if peak_ceiling is not None and peak_ceiling > 0:
+        limit = float(peak_ceiling) / pk.clamp_min(1e-300)
+        capped = measured & (pk > 0) & (gain > limit)
+        gain = torch.where(capped, limit, gain)
+    return gain, 20.0 * torch.log10(gain), capped
+
+
+@torch.inference_mode()
+def loudness_normalize(y, target_lufs: float = -23.0, sr: int = 22050, lengths=None, peak_ceiling: float = 0.95):
+    """Every row of ``y`` (1-D, or (B, L) with ``lengths`` (B,) or None, on the GPU) levelled to ``target_lufs`` integrated loudness
+    (``loudness``), the gain capped where the row's peak (``ev_trim_bounds``' d_peak) would pass ``peak_ceiling`` (``loudness_gain``).  A row
+    without a loudness (silence, under 400 ms) is left untouched.  -> (levelled rows, float32, zeros past a row's length; gain_db (B,)
+    float64; capped (B,) bool).  The measurement runs in the HIP library; applying the gain is one torch multiply."""
+    r = loudness(y, sr, lengths)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    ln = lengths if y.dim() == 2 else None
+    gain, gain_db, capped = loudness_gain(r["integrated"], peak_level(x, ln), target_lufs, peak_ceiling)
+    out = x.to(torch.float32) * gain.to(torch.float32)[:, None]
+    if ln is not None:
+        n = torch.as_tensor(ln).to(x.device, torch.int64)
+        out = out * (torch.arange(x.shape[1], device=x.device)[None, :] < n[:, None])
+    return (out[0] if y.dim() == 1 else out), gain_db, capped

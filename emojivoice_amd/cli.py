@@ -15,6 +15,8 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean                              # trimmed, levelled 22.05 kHz wavs + clean/filelist.txt + raw.txt.durations.json
     python -m emojivoice_amd.cli --prosody_report clean/filelist.txt                                    # clean/filelist.txt.prosody.json: f0 per file and per speaker
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt                                             # pairs.txt.eval.json: MCD, f0 RMSE, voicing error per 'recorded.wav|synthesised.wav[|spk]'
+    python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
+    python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
 
 The wavs of --mel_from_wav, --align_wav and --data_statistics may have any sample rate (the reference's recorder writes 44.1 kHz,
 record_audio.py:31): they are resampled to the analysis rate on the device (emojivoice_amd.audio.resample).
@@ -64,8 +66,13 @@ def validate_args(args):
     if args.prepare_dataset:
         assert args.out_dir, "--prepare_dataset needs --out_dir"
         assert 0 <= args.peak <= 1, "--peak must lie in [0, 1] (0: no levelling)"
+        if getattr(args, "target_lufs", None) is not None:
+            assert math.isfinite(args.target_lufs), "--target_lufs must be a finite LUFS value"
+            assert args.peak > 0, "--target_lufs caps the gain at --peak: --peak must lie in (0, 1]"
+            sr = int(args.sample_rate or 22050)
+            assert sr % 10 == 0 and sr >= 8000, "--target_lufs needs a --sample_rate that is a multiple of 10 and at least 8000"
         return args
-    if getattr(args, "prosody_report", None) or getattr(args, "evaluate_pairs", None):
+    if getattr(args, "prosody_report", None) or getattr(args, "evaluate_pairs", None) or getattr(args, "loudness_report", None):
         assert args.batch_size > 0, "Batch size must be greater than 0"
         return args
     if args.mel_from_wav:
@@ -320,8 +327,13 @@ def prepare_dataset(args, device):
     """--prepare_dataset FILELIST --out_dir DIR: every listed recording (any rate, channel count, 16 / 24 bit) through
     audio.prepare_recording (resampled to --sample_rate, silence trimmed at --top_db, levelled to --peak, all on the device), written
     as a 16-bit mono wav of the same base name under DIR; DIR/filelist.txt repeats the lines with the new paths and
-    FILELIST.durations.json holds ``duration_report``."""
+    FILELIST.durations.json holds ``duration_report``.  With --target_lufs X the level comes from loudness instead of from the peak: the take is
+    trimmed with its level untouched, then audio.loudness_normalize takes it to X LUFS (BS.1770), the gain capped where the peak would pass
+    --peak; every file's entry then also holds "integrated_lufs" (before levelling; null without a loudness), "gain_db" and "capped", and the
+    report "target_lufs"."""
     from . import audio
+
+    target = getattr(args, "target_lufs", None)
 
     sr = int(args.sample_rate or 22050)
     entries = parse_filelist(args.prepare_dataset)
@@ -334,15 +346,25 @@ def prepare_dataset(args, device):
     out_dir.mkdir(parents=True, exist_ok=True)
     files, lines = [], []
     for (wav, spk, rest), name in zip(entries, names):
-        y, info = audio.prepare_recording(wav, sr, args.top_db, args.peak, device)
+        level = {}
+        if target is None:
+            y, info = audio.prepare_recording(wav, sr, args.top_db, args.peak, device)
+        else:
+            y, info = audio.prepare_recording(wav, sr, args.top_db, 0.0, device)
+            before = audio.loudness(y, sr)["integrated"]
+            y, gain_db, capped = audio.loudness_normalize(y, target, sr, peak_ceiling=args.peak)
+            level = {"integrated_lufs": float(before[0]) if math.isfinite(float(before[0])) else None, "gain_db": float(gain_db[0]), "capped": bool(capped[0])}
         dst = (out_dir / name).resolve()
         write_wav_pcm16(dst, y.cpu().numpy(), sr)
         files.append({"path": wav, "out": str(dst), "speaker": spk if spk is not None else "0",
-                      "seconds_in": info["seconds_in"], "seconds_out": info["seconds_out"]})
+                      "seconds_in": info["seconds_in"], "seconds_out": info["seconds_out"], **level})
         lines.append("|".join([str(dst)] + rest))
-        print(f"[+] {wav}: {info['seconds_in']:.2f} s -> {info['seconds_out']:.2f} s  ({dst})")
+        print(f"[+] {wav}: {info['seconds_in']:.2f} s -> {info['seconds_out']:.2f} s  ({dst})"
+              + (f"  gain {level['gain_db']:+.2f} dB" + ("  (capped at the peak)" if level["capped"] else "") if level else ""))
     (out_dir / "filelist.txt").write_text("\n".join(lines) + "\n", encoding="utf-8")
     rep = duration_report(files, sr, args.top_db, args.peak)
+    if target is not None:
+        rep["target_lufs"] = float(target)
     out = f"{args.prepare_dataset}.durations.json"
     with open(out, "w") as f:
         json.dump(rep, f, indent=1)
@@ -410,6 +432,69 @@ def prosody_report(args, device):
                                                                   f"({v['f0_range_semitones']:.1f} semitones)")
         print(f"[i] speaker {k}: {v['files']} files, voiced {100 * v['voiced_fraction']:.0f} %, {pitch}")
     print(f"[+] Prosody report saved: {Path(out_path).resolve()}")
+    return rep
+
+
+LOUDNESS_SR = 22050          # the analysis rate, as for the prosody report
+LOUDNESS_OUTLIER_LU = 3.0    # a file this far from its speaker's mean is listed
+
+
+def loudness_summary(values):
+    """{"measured", "mean", "std", "min", "max"} of a speaker's integrated LUFS values (the files that have one): plain mean and population
+    standard deviation of the LUFS figures; None for every statistic when there is none."""
+    n = len(values)
+    if n == 0:
+        return {"measured": 0, "mean": None, "std": None, "min": None, "max": None}
+    mean = math.fsum(values) / n
+    return {"measured": n, "mean": mean, "std": math.sqrt(math.fsum((v - mean) ** 2 for v in values) / n), "min": min(values), "max": max(values)}
+
+
+@torch.inference_mode()
+def loudness_report(args, device):
+    """--loudness_report FILELIST: the filelist format of --prosody_report.  Every file is loaded with audio.load_audio(path, 22050) and measured by
+    audio.loudness (ITU-R BS.1770-4 on the device) and audio.peak_level, --batch_size files at a time (padded to the longest, each row with its
+    own length).  FILELIST.loudness.json receives per file "integrated_lufs", "max_momentary_lufs" (the loudest 400 ms block), "peak_dbfs" and
+    "seconds" (null where a figure does not exist: silence, a file under 400 ms) and per speaker the file count, mean / std / min / max of the
+    integrated LUFS over the files that have one, and under "outliers" the files more than 3 LU from that mean."""
+    from . import audio
+
+    entries = parse_filelist(args.loudness_report)
+    if not entries:
+        sys.exit(f"[-] {args.loudness_report}: no files listed")
+    finite = lambda v: float(v) if math.isfinite(float(v)) else None
+    files = []
+    for b0 in range(0, len(entries), args.batch_size):
+        chunk = entries[b0:b0 + args.batch_size]
+        ys = [audio.load_audio(wav, LOUDNESS_SR, device) for wav, _, _ in chunk]
+        lens = [int(y.shape[-1]) for y in ys]
+        batch = torch.zeros(len(ys), max(max(lens), 1), device=ys[0].device)
+        for r, y in enumerate(ys):
+            batch[r, : lens[r]] = y.reshape(-1)
+        out = audio.loudness(batch, LOUDNESS_SR, lengths=lens)
+        integrated, blocks = out["integrated"].cpu(), out["blocks"].cpu()
+        momentary = out["momentary"].cpu()
+        peak = audio.peak_level(batch, lens).cpu()
+        for r, (wav, spk, _) in enumerate(chunk):
+            nb = int(blocks[r])
+            files.append({"path": wav, "speaker": spk if spk is not None else "0", "seconds": lens[r] / float(LOUDNESS_SR),
+                          "integrated_lufs": finite(integrated[r]), "max_momentary_lufs": finite(momentary[r, :nb].max()) if nb > 0 else None,
+                          "peak_dbfs": 20.0 * math.log10(float(peak[r])) if float(peak[r]) > 0 else None})
+    speakers = {}
+    for spk in dict.fromkeys(f["speaker"] for f in files):
+        mine = [f for f in files if f["speaker"] == spk]
+        st = loudness_summary([f["integrated_lufs"] for f in mine if f["integrated_lufs"] is not None])
+        outliers = [f["path"] for f in mine if f["integrated_lufs"] is not None and abs(f["integrated_lufs"] - st["mean"]) > LOUDNESS_OUTLIER_LU]
+        speakers[spk] = {"files": len(mine), **st, "outliers": outliers}
+    rep = {"sample_rate": LOUDNESS_SR, "outlier_lu": LOUDNESS_OUTLIER_LU, "files": files, "speakers": speakers}
+    out_path = f"{args.loudness_report}.loudness.json"
+    with open(out_path, "w") as f:
+        json.dump(rep, f, indent=1)
+    for k in sorted(speakers):
+        v = speakers[k]
+        level = "no file with a loudness" if v["mean"] is None else (f"{v['mean']:.1f} LUFS mean, std {v['std']:.1f} LU, {v['min']:.1f} .. {v['max']:.1f}"
+                                                                    + (f", {len(v['outliers'])} more than {LOUDNESS_OUTLIER_LU:g} LU off" if v["outliers"] else ""))
+        print(f"[i] speaker {k}: {v['files']} files, {level}")
+    print(f"[+] Loudness report saved: {Path(out_path).resolve()}")
     return rep
 
 
@@ -565,7 +650,16 @@ def cli(argv=None):
     p.add_argument("--evaluate_pairs", type=str, default=None, help="objective evaluation instead of synthesis: a file of 'recorded.wav|synthesised.wav[|spk]' lines -> "
                    "PAIRS.eval.json: mel-cepstral distortion (dB), f0 RMSE (cents) and voicing-decision error over the DTW path per pair, per speaker "
                    "and overall (DTW on the device, --batch_size pairs per batch; needs no checkpoint)")
+    p.add_argument("--loudness_report", type=str, default=None, help="loudness analysis instead of synthesis: a filelist 'path|spk|text' -> FILELIST.loudness.json: "
+                   "ITU-R BS.1770-4 integrated LUFS, loudest 400 ms block, peak in dBFS and seconds per file; mean / std / min / max per speaker and the files "
+                   "more than 3 LU from their speaker's mean (on the device, --batch_size files per batch; needs no checkpoint)")
+    p.add_argument("--target_lufs", type=float, default=None, help="--prepare_dataset: level every recording to this integrated loudness (BS.1770, e.g. -23) "
+                   "instead of to --peak; the gain is capped where the peak would pass --peak, and the gain and the cap go into FILELIST.durations.json")
     args = validate_args(p.parse_args(argv))
+    if args.loudness_report:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return loudness_report(args, torch.device("cuda", 0))
     if args.evaluate_pairs:
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")

@@ -142,6 +142,7 @@ struct ev_handle {
     Scratch dtw_ws;                  // (ev_dtw's decision bits where they do not fit in LDS)
     Scratch stat_ws;                 // ev_mel_stats: the per-(row, 32 frames) partial sums
     Scratch trim_ws;                 // ev_trim_bounds: the per-(row, hop block) sum of squares (float64) and max |x| (fp32)
+    Scratch loud_ws;                 // ev_loudness: per (row, chunk) the four filter-state doubles and the sub-block pieces; the sub-block energies without d_sub
     float* zeros = nullptr;     // 4096 zero floats (stand-in bias for the fused kernels' unconditional loads)
     int max_steps = 64;         // Euler steps the time-grid buffers of the workspace are planned for (grows on demand)
     int* bad_ids_host = nullptr; int* bad_ids_dev = nullptr;   // mapped host word: count of out-of-range token ids seen by ev_text_encoder
@@ -1987,6 +1988,7 @@ void ev_destroy(ev_handle* h) {
     if (h->dtw_ws.p) hipFree(h->dtw_ws.p);
     if (h->stat_ws.p) hipFree(h->stat_ws.p);
     if (h->trim_ws.p) hipFree(h->trim_ws.p);
+    if (h->loud_ws.p) hipFree(h->loud_ws.p);
     if (h->dn_ws.p) hipFree(h->dn_ws.p);
     if (h->bad_ids_host) hipHostFree(h->bad_ids_host);
     for (int i = 0; i < 2; ++i) { if (h->temb_ev[i]) hipEventDestroy(h->temb_ev[i]); if (h->temb_host[i]) hipHostFree(h->temb_host[i]); }
@@ -2929,6 +2931,72 @@ int ev_dtw(ev_handle* h, const float* d_x, const float* d_y, const int32_t* d_xl
     if (R == 1) launch<dtw_kernel<1, 8>>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
     else if (R == 2) launch<dtw_kernel<2, 8>>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
     else launch<dtw_kernel<4, 4>>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Loudness (kernels and the scheme: ev_kernels.h).  Arena, in doubles: [state B x NC x 4][pieces B x NC x npp][sub-block energies B x NS, only
+// without d_sub]; NC = ceil(NS S / LOUD_CHUNK) chunks that can hold a counted sample, npp = the most sub-blocks a chunk can touch.
+int ev_loudness(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, int sub_len, const double* coef, double abs_gate,
+                double* d_sub, double* d_block, double* d_gated, int32_t* d_counts, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int S = sub_len;
+    if (B < 1 || B > 65535) return fail(h, "ev_loudness: B=%d outside 1 <= B <= 65535", B);
+    if (S < 16 || S > 65536) return fail(h, "ev_loudness: sub_len=%d outside 16 <= sub_len <= 65536", S);
+    if (L < 1) return fail(h, "ev_loudness: L=%d must be at least 1", L);
+    if (!d_x) return fail(h, "ev_loudness: d_x must be non-null");
+    if (!coef) return fail(h, "ev_loudness: coef must be non-null (HOST, 10 doubles)");
+    if (!d_gated || !d_counts) return fail(h, "ev_loudness: d_gated and d_counts must be non-null");
+    for (int st = 0; st < 2; ++st) {
+        const double a1 = coef[5 * st + 3], a2 = coef[5 * st + 4];
+        bool finite = true;
+        for (int i = 0; i < 5; ++i) finite = finite && std::isfinite(coef[5 * st + i]);
+        if (!(finite && std::fabs(a2) < 1.0 && std::fabs(a1) < 1.0 + a2))
+            return fail(h, "ev_loudness: coef stage %d is unstable or not finite (a1=%g a2=%g; |a2| < 1 and |a1| < 1 + a2 expected)", st + 1, a1, a2);
+    }
+    h->stream = (hipStream_t)stream;
+    LoudCoef k{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8], coef[9]};
+    const int NS = L / S, NB = std::max(NS - 3, 0);
+    const int NC = (int)(((long long)NS * S + LOUD_CHUNK - 1) / LOUD_CHUNK);
+    const int npp = (LOUD_CHUNK + S - 2) / S + 1;
+    const size_t n_state = (size_t)B * NC * 4, n_part = (size_t)B * NC * npp, n_sub = d_sub ? 0 : (size_t)B * NS;
+    double* sub = d_sub;
+    if (NS > 0) {
+        if (scratch_acquire(h, h->loud_ws, (n_state + n_part + n_sub) * sizeof(double))) return 1;
+        double* state = (double*)h->loud_ws.p;
+        double* part = state + n_state;
+        if (!sub) sub = part + n_part;
+        LoudChunkParams pc{};
+        pc.x = d_x; pc.len = d_len; pc.state = state; pc.part = part; pc.L = L; pc.S = S; pc.NC = NC; pc.npp = npp; pc.k = k;
+        LoudCarryParams pk{};
+        pk.state = state; pk.len = d_len; pk.L = L; pk.S = S; pk.NC = NC;
+        for (int c = 0; c < 4; ++c) {                                    // column c of M: the state LOUD_CHUNK zero samples after unit state c
+            double s[4] = {0.0, 0.0, 0.0, 0.0};
+            s[c] = 1.0;
+            for (int n = 0; n < LOUD_CHUNK; ++n) {
+                const double x = 0.0;
+                const double y1 = std::fma(k.b0, x, s[0]);
+                s[0] = std::fma(-k.a1, y1, std::fma(k.b1, x, s[1]));
+                s[1] = std::fma(-k.a2, y1, k.b2 * x);
+                const double y2 = std::fma(k.c0, y1, s[2]);
+                s[2] = std::fma(-k.d1, y2, std::fma(k.c1, y1, s[3]));
+                s[3] = std::fma(-k.d2, y2, k.c2 * y1);
+            }
+            for (int r = 0; r < 4; ++r) pk.M[4 * r + c] = s[r];
+        }
+        const dim3 grid((unsigned)((NC + 63) / 64), (unsigned)B);
+        launch<loud_chunk_kernel<false>>(h->device, grid, dim3(64), 0, h->stream, pc);
+        launch<loud_carry_kernel>(h->device, dim3((unsigned)B), dim3(64), 0, h->stream, pk);
+        launch<loud_chunk_kernel<true>>(h->device, grid, dim3(64), 0, h->stream, pc);
+        LoudMergeParams pm{};
+        pm.part = part; pm.len = d_len; pm.sub = sub; pm.L = L; pm.S = S; pm.NC = NC; pm.npp = npp; pm.NS = NS;
+        launch<loud_merge_kernel>(h->device, dim3((unsigned)((NS + 255) / 256), (unsigned)B), dim3(256), 0, h->stream, pm);
+    }
+    LoudGateParams pg{};
+    pg.sub = sub; pg.len = d_len; pg.block = d_block; pg.gated = d_gated; pg.counts = d_counts;
+    pg.L = L; pg.S = S; pg.NS = NS; pg.NB = NB; pg.abs_gate = abs_gate;
+    launch<loud_gate_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pg);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -7091,3 +7091,251 @@ __global__ __launch_bounds__(256) void mas_logp_kernel(const float* __restrict__
         if (x < Tx) logp[((size_t)b * Tx + x) * Ty + j] = mas_cell_finish(acc[r], cst);
     }
 }
+
+// ---------------------------------------------------------------------------
+// Loudness (ev_loudness): ITU-R BS.1770-4 K-weighting, 100 ms sub-block energies, 400 ms blocks, two gates.  All float64.
+// The K-weighting is two biquads in series, each in transposed direct form II (what scipy.signal.lfilter runs):
+//     y = b0 x + s1;   s1 = (b1 x + s2) - a1 y;   s2 = b2 x - a2 y
+// so a row's filter state is FOUR doubles (s1, s2 of the shelf, then of the high pass) and the filter is linear in (state, input): the state
+// after a chunk of LOUD_CHUNK samples is (the state the chunk reaches from zero) + M . (the state before it), M the 4 x 4 zero-input
+// transition over one chunk (the host runs this very recurrence on the four unit states and passes M by value).  A row is therefore NOT one
+// chain of len steps but three launches whose longest chain is one chunk plus the carry:
+//   1. loud_chunk_kernel<false>: one lane per (row, chunk) runs its chunk from zero state and keeps the four doubles;
+//   2. loud_carry_kernel:        one wave per row forms s[c + 1] = M s[c] + z[c] in ascending c, in place: slot c then holds the state at the
+//                                START of chunk c;
+//   3. loud_chunk_kernel<true>:  one lane per (row, chunk) reruns the chunk from that state and sums y^2 per PIECE, a piece being the part of
+//                                one sub-block that lies inside the chunk (one fma per sample, ascending);
+// then loud_merge_kernel adds the pieces of sub-block i over the chunks it touches in ascending chunk order (e_i), and loud_gate_kernel forms
+// the blocks, both gates and the two means per row.  No atomics anywhere; the chunk grid hangs on the row's first sample, so nothing depends
+// on the batch, on L or on what lies behind the row.
+// Only samples below lim = (len / S) S are ever read (the incomplete tail is discarded by the standard, and nothing at or behind len may be
+// read).  Staging: a workgroup is ONE wave holding 64 consecutive chunks of a row; a lane reading its own chunk straight from memory would be
+// a 4 KiB-strided access, so the wave loads a tile of 64 chunks x LOUD_T samples with 16-byte loads (8 lanes per chunk: 128 contiguous bytes)
+// into LDS rows of LOUD_T + 4 floats (9 sixteen-byte slots: 16 consecutive lanes reading their rows' same quad hit 16 different slots) and
+// each lane then reads its row with 16-byte LDS loads.  The next tile's global loads are issued before the current tile is filtered and
+// written to the other LDS buffer after it: one barrier per tile.
+constexpr int LOUD_CHUNK = 1024;                                        // samples per chunk
+constexpr int LOUD_T = 32;                                              // samples per chunk and staged tile
+constexpr int LOUD_ROW = LOUD_T + 4;                                    // floats per LDS row
+
+struct LoudCoef { double b0, b1, b2, a1, a2, c0, c1, c2, d1, d2; };     // stage 1 (b, a), stage 2 (c, d)
+
+struct LoudChunkParams {
+    const float* x; const int32_t* len; double* state; double* part;   // state (B, NC, 4); part (B, NC, npp)
+    int L, S, NC, npp;
+    LoudCoef k;
+};
+
+__device__ __forceinline__ long long loud_lim(const int32_t* len, int b, int L, int S) {
+    int n = len ? len[b] : L;
+    if (n < 1 || n > L) n = 0;                                          // a bad row is an empty row (the ev_mas_align convention)
+    return (long long)(n / S) * S;
+}
+
+template <bool ENERGY>
+__global__ __launch_bounds__(64) void loud_chunk_kernel(const LoudChunkParams p) {
+    __shared__ __attribute__((aligned(16))) float xs[2][64 * LOUD_ROW];
+    const int b = blockIdx.y, lane = threadIdx.x;
+    const long long lim = loud_lim(p.len, b, p.L, p.S);
+    const long long c0 = (long long)blockIdx.x * 64;                    // the wave's first chunk
+    if (c0 * LOUD_CHUNK >= lim) return;                                 // (uniform) nothing of this row in these chunks
+    const float* xrow = p.x + (size_t)b * p.L;
+    const bool vec = (((size_t)xrow) & 15) == 0;                        // (chunks and tiles start at multiples of 4 samples of the row)
+    const long long c = c0 + lane, n0 = c * LOUD_CHUNK;
+    const int cnt = (int)max(0LL, min((long long)LOUD_CHUNK, lim - n0));    // samples of this lane's chunk below lim
+    const int ntile = (int)((min((long long)LOUD_CHUNK, lim - c0 * LOUD_CHUNK) + LOUD_T - 1) / LOUD_T);   // (uniform: lane 0 has the most)
+    const LoudCoef k = p.k;
+    double s1 = 0.0, s2 = 0.0, u1 = 0.0, u2 = 0.0;
+    double acc = 0.0;
+    int rem = 0;
+    double* part = nullptr;
+    if (ENERGY) {
+        if (cnt > 0) {
+            const double* st = p.state + ((size_t)b * p.NC + c) * 4;
+            s1 = st[0]; s2 = st[1]; u1 = st[2]; u2 = st[3];
+        }
+        const long long i0 = n0 / p.S;
+        rem = (int)((i0 + 1) * p.S - n0);                               // samples left in the sub-block the chunk starts in
+        part = p.part + ((size_t)b * p.NC + (cnt > 0 ? c : 0)) * p.npp;
+    }
+    // the tile loader: instruction r of 8 covers chunks 8 r .. 8 r + 7, lane -> (chunk 8 r + lane / 8, quad lane % 8)
+    const int lq = lane & 7, lc = lane >> 3;
+    f32x4 stage[8];
+    auto load_tile = [&](int t) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const long long n = (c0 + 8 * r + lc) * LOUD_CHUNK + t * LOUD_T + 4 * lq;
+            f32x4 q = {0.f, 0.f, 0.f, 0.f};
+            if (n + 4 <= lim) {
+                if (vec) q = *(const f32x4*)(xrow + n);
+                else { q[0] = xrow[n]; q[1] = xrow[n + 1]; q[2] = xrow[n + 2]; q[3] = xrow[n + 3]; }
+            } else if (n < lim) {
+                if (n + 0 < lim) q[0] = xrow[n];
+                if (n + 1 < lim) q[1] = xrow[n + 1];
+                if (n + 2 < lim) q[2] = xrow[n + 2];
+                if (n + 3 < lim) q[3] = xrow[n + 3];
+            }
+            stage[r] = q;
+        }
+    };
+    auto store_tile = [&](int buf) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) *(f32x4*)(&xs[buf][(8 * r + lc) * LOUD_ROW + 4 * lq]) = stage[r];
+    };
+    load_tile(0);
+    store_tile(0);
+    __syncthreads();
+    for (int t = 0; t < ntile; ++t) {
+        if (t + 1 < ntile) load_tile(t + 1);
+        const float* row = &xs[t & 1][lane * LOUD_ROW];
+        const int v = cnt - t * LOUD_T;                                 // samples of this tile that belong to the lane's chunk (may be <= 0)
+#pragma unroll
+        for (int j = 0; j < LOUD_T / 4; ++j) {
+            const f32x4 q = *(const f32x4*)(row + 4 * j);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double x = (double)q[e];
+                const double y1 = fma(k.b0, x, s1);
+                s1 = fma(-k.a1, y1, fma(k.b1, x, s2));
+                s2 = fma(-k.a2, y1, k.b2 * x);
+                const double y2 = fma(k.c0, y1, u1);
+                u1 = fma(-k.d1, y2, fma(k.c1, y1, u2));
+                u2 = fma(-k.d2, y2, k.c2 * y1);
+                if (ENERGY) {
+                    if (4 * j + e < v) {
+                        acc = fma(y2, y2, acc);
+                        if (--rem == 0) { *part++ = acc; acc = 0.0; rem = p.S; }
+                    }
+                }
+            }
+        }
+        if (t + 1 < ntile) store_tile((t + 1) & 1);
+        __syncthreads();
+    }
+    if (ENERGY) {
+        if (cnt > 0 && rem != p.S) *part = acc;                         // the piece the chunk's end cuts (lim is a multiple of S: the row's last
+    } else {                                                            // chunk ends on a sub-block's end and leaves none)
+        if (cnt == LOUD_CHUNK) {
+            double* st = p.state + ((size_t)b * p.NC + c) * 4;
+            st[0] = s1; st[1] = s2; st[2] = u1; st[3] = u2;
+        }
+    }
+}
+
+// The carry.  One wave per row; every lane walks the same chain (uniform work, no divergence): 64 chunk results at a time come into LDS with
+// one coalesced load, the chain takes them in ascending order, lane k keeps the state at the start of chunk base + k, and one coalesced store
+// puts those back in place.  s'[r] = (M[r][0] s0 + M[r][1] s1) + (z[r] + M[r][2] s2 + M[r][3] s3), fmas in that association.
+struct LoudCarryParams {
+    double* state; const int32_t* len;
+    int L, S, NC;
+    double M[16];
+};
+
+__global__ __launch_bounds__(64) void loud_carry_kernel(const LoudCarryParams p) {
+    __shared__ double zs[64][4];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const long long lim = loud_lim(p.len, b, p.L, p.S);
+    const long long nact = (lim + LOUD_CHUNK - 1) / LOUD_CHUNK;         // chunks that hold a sample below lim; all but the last are whole
+    double* st = p.state + (size_t)b * p.NC * 4;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (long long base = 0; base < nact; base += 64) {
+        const long long c = base + lane;
+        const bool whole = c < nact - 1;                                // (the last active chunk's result is not needed, and may not exist)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) zs[lane][r] = whole ? st[c * 4 + r] : 0.0;
+        __syncthreads();
+        double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
+        const int n = (int)min(64LL, nact - base);
+        for (int kk = 0; kk < n; ++kk) {
+            if (lane == kk) { m0 = s0; m1 = s1; m2 = s2; m3 = s3; }
+            const double z0 = zs[kk][0], z1 = zs[kk][1], z2 = zs[kk][2], z3 = zs[kk][3];
+            const double t0 = fma(p.M[1], s1, p.M[0] * s0) + fma(p.M[3], s3, fma(p.M[2], s2, z0));
+            const double t1 = fma(p.M[5], s1, p.M[4] * s0) + fma(p.M[7], s3, fma(p.M[6], s2, z1));
+            const double t2 = fma(p.M[9], s1, p.M[8] * s0) + fma(p.M[11], s3, fma(p.M[10], s2, z2));
+            const double t3 = fma(p.M[13], s1, p.M[12] * s0) + fma(p.M[15], s3, fma(p.M[14], s2, z3));
+            s0 = t0; s1 = t1; s2 = t2; s3 = t3;
+        }
+        __syncthreads();
+        if (c < nact) { st[c * 4] = m0; st[c * 4 + 1] = m1; st[c * 4 + 2] = m2; st[c * 4 + 3] = m3; }
+    }
+}
+
+// e[b, i] = the pieces of sub-block i, added in ascending chunk order starting from the first piece itself; 0 for i >= ns.
+struct LoudMergeParams {
+    const double* part; const int32_t* len; double* sub;               // sub (B, NS)
+    int L, S, NC, npp, NS;
+};
+
+__global__ __launch_bounds__(256) void loud_merge_kernel(const LoudMergeParams p) {
+    const int b = blockIdx.y;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.NS) return;
+    const long long ns = loud_lim(p.len, b, p.L, p.S) / p.S;
+    double e = 0.0;
+    if (i < ns) {
+        const long long c_lo = i * p.S / LOUD_CHUNK, c_hi = ((i + 1) * p.S - 1) / LOUD_CHUNK;
+        const double* part = p.part + (size_t)b * p.NC * p.npp;
+        for (long long c = c_lo; c <= c_hi; ++c) {
+            const double v = part[c * p.npp + (i - c * LOUD_CHUNK / p.S)];
+            e = c == c_lo ? v : e + v;
+        }
+    }
+    p.sub[(size_t)b * p.NS + i] = e;
+}
+
+// One workgroup per row over its sub-block energies: z[j] = ((e[j] + e[j+1]) + (e[j+2] + e[j+3])) / (4 S) for j < nb = max(ns - 3, 0); the
+// absolute gate z > abs_gate; m_abs = the mean of the blocks that pass it; the relative gate z > 0.1 m_abs on top; the mean of the blocks
+// that pass both.  SUMMATION ORDER of either mean: thread t of 256 adds its blocks j = t, t + 256, ... in ascending j; the 64 partials of a
+// wave are added by the fixed shuffle tree (offsets 32, 16, ... 1); the four waves' sums as (w0 + w1) + (w2 + w3).  It depends on j alone.
+struct LoudGateParams {
+    const double* sub; const int32_t* len; double* block; double* gated; int32_t* counts;
+    int L, S, NS, NB;
+    double abs_gate;
+};
+
+__device__ __forceinline__ double loud_block(const double* e, long long j, double four_s) {
+    return ((e[j] + e[j + 1]) + (e[j + 2] + e[j + 3])) / four_s;
+}
+
+__device__ __forceinline__ void loud_reduce(double& s, int& n, double* red_d, int* red_i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o); n += __shfl_down(n, o); }
+    __syncthreads();                                                    // (the previous use of red_* is over)
+    if ((threadIdx.x & 63) == 0) { red_d[threadIdx.x >> 6] = s; red_i[threadIdx.x >> 6] = n; }
+    __syncthreads();
+    s = (red_d[0] + red_d[1]) + (red_d[2] + red_d[3]);
+    n = (red_i[0] + red_i[1]) + (red_i[2] + red_i[3]);
+}
+
+__global__ __launch_bounds__(256) void loud_gate_kernel(const LoudGateParams p) {
+    __shared__ double red_d[4];
+    __shared__ int red_i[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const long long ns = loud_lim(p.len, b, p.L, p.S) / p.S;
+    const long long nb = ns > 3 ? ns - 3 : 0;
+    const double* e = p.sub + (size_t)b * p.NS;
+    const double four_s = 4.0 * (double)p.S;
+    if (p.block)
+        for (long long j = tid; j < p.NB; j += 256) p.block[(size_t)b * p.NB + j] = j < nb ? loud_block(e, j, four_s) : 0.0;
+    double s = 0.0;
+    int n = 0;
+    for (long long j = tid; j < nb; j += 256) {
+        const double z = loud_block(e, j, four_s);
+        if (z > p.abs_gate) { s += z; ++n; }
+    }
+    loud_reduce(s, n, red_d, red_i);
+    const int n_abs = n;
+    const double m_abs = n_abs > 0 ? s / (double)n_abs : 0.0;
+    const double rel = 0.1 * m_abs;
+    s = 0.0; n = 0;
+    for (long long j = tid; j < nb; j += 256) {
+        const double z = loud_block(e, j, four_s);
+        if (z > p.abs_gate && z > rel) { s += z; ++n; }
+    }
+    loud_reduce(s, n, red_d, red_i);
+    if (tid == 0) {
+        p.gated[2 * b] = n > 0 ? s / (double)n : 0.0;
+        p.gated[2 * b + 1] = m_abs;
+        p.counts[3 * b] = (int32_t)nb; p.counts[3 * b + 1] = n_abs; p.counts[3 * b + 2] = n;
+    }
+}

@@ -36,6 +36,7 @@
  *   ev_trim_apply      <- the gain is normalize(audio) * 0.95 of the vocoder's dataset code                hifigan/meldataset.py:152
  *   ev_pitch_yin       <- no counterpart: the reference never measures pitch; librosa.yin is the model
  *   ev_dtw             <- no counterpart: the reference never compares what it says with what was recorded; MCD-DTW evaluation is the model
+ *   ev_loudness        <- no counterpart; ITU-R BS.1770-4 is the model
  *
  * Conventions
  *   - All tensors are fp32.  Pointers named d_* are DEVICE pointers owned by the
@@ -73,7 +74,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -397,6 +398,48 @@ int ev_dtw(ev_handle *h, const float *d_x /* (B, C, Tx) */, const float *d_y /* 
            int B, int C, int Tx, int Ty, int metric /* 0 Euclidean, 1 squared Euclidean */,
            double *d_cost /* (B) */, int32_t *d_steps /* (B) */,
            int32_t *d_path /* (B, Tx + Ty - 1, 2) or NULL */, void *stream);
+
+/* Loudness on the device: ITU-R BS.1770-4 / EBU R 128 integrated loudness of mono rows (K-weighting, 400 ms blocks with 75 % overlap, an
+ * absolute and a relative gate).  S = sub_len is the samples per 100 ms; NS = L / S (integer division) sub-blocks and NB = max(NS - 3, 0)
+ * blocks per row of the outputs.  A row of len samples has ns = len / S complete sub-blocks and nb = max(ns - 3, 0) gating blocks; the
+ * incomplete tail is discarded, as the standard says.  d_len == NULL: every row is L long.
+ *   coef      HOST, 10 doubles, read during the call and passed to the kernels by value (no load step, no host-to-device copy: the call stays
+ *             capturable once the arena has its size): {b0, b1, b2, a1, a2} of stage 1 (the high shelf), then of stage 2 (the high pass), a0 = 1.
+ *             emojivoice_amd.audio.k_weighting(sr) designs them for any rate.  A stage is stable iff |a2| < 1 and |a1| < 1 + a2; an unstable
+ *             (or non-finite) stage fails the call with a message naming it.  The kernel does not tie coef to S.
+ *   filter    per stage y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2], every row from zero state, stage 2 on stage 1's output.
+ *             Samples are widened to float64 and everything is float64; ev_set_arithmetic does not reach it.
+ *   d_sub     (B, NS) float64 or NULL: e_i = sum of y^2 over samples [i S, (i + 1) S); 0 for i >= ns
+ *   d_block   (B, NB) float64 or NULL: z_j = ((e_j + e_{j+1}) + (e_{j+2} + e_{j+3})) / (4 S), in exactly that association (one correctly rounded
+ *             division by the double 4 S): bit-derivable from d_sub; 0 for j >= nb
+ *   gates     in the power domain, strict: absolute z_j > abs_gate (the caller passes 10^((-70 + 0.691) / 10)); relative, additionally,
+ *             z_j > 0.1 * m_abs, m_abs the mean of z over the blocks that pass the absolute gate (one multiply gives the -10 LU)
+ *   d_gated   (B, 2) float64: {mean of z over the blocks passing both gates, m_abs}; 0 where the set is empty
+ *   d_counts  (B, 3) int32: {nb, blocks passing the absolute gate, blocks passing both}
+ *   The caller takes -0.691 + 10 log10(.) itself: there is no logarithm on the device.
+ * A row with len < 1 or len > L is no error and no out-of-bounds access: all its outputs are zeros (the ev_mas_align convention).  Nothing at or
+ * behind ns S is read, so nothing at or behind len is.
+ * Limits, each violation failing with a message that names it: 1 <= B <= 65535; 16 <= sub_len <= 65536; L >= 1; d_gated and d_counts non-NULL.
+ * Parallel in time: the 4th-order recurrence is not walked as one chain per row.  A row is cut into chunks of 1024 samples from its first sample.
+ *   The filter's state is four doubles (transposed direct form II, two per stage) and the filter is linear, so the state after a chunk is
+ *   (the state the chunk reaches from zero) + M (the state before it); M, the 4 x 4 zero-input transition over one chunk, is computed on the
+ *   host in double by running the recurrence on the four unit states, and passed by value.  Launches: (1) one lane per (row, chunk) runs its
+ *   chunk from zero state and keeps four doubles; (2) one wave per row carries s[c + 1] = M s[c] + z[c] in ascending c; (3) one lane per (row,
+ *   chunk) reruns the chunk from its true state and sums y^2 (one fma per sample, ascending) per piece of a sub-block inside the chunk; (4) the
+ *   pieces of a sub-block are added in ascending chunk order; (5) one workgroup per row forms blocks, gates and means.  The longest dependent
+ *   chain per row is one chunk plus the carry (len / 1024 steps of one 4 x 4 product).  Samples reach the lanes through LDS tiles (a lane
+ *   reading its own chunk would stride 4 KiB).
+ *   Order of the two means: thread t of 256 adds its blocks j = t, t + 256, ... in ascending j, the 64 partials of a wave go through one fixed
+ *   shuffle tree (offsets 32 .. 1), the four waves' sums are added as (w0 + w1) + (w2 + w3).
+ *   No atomics, and the chunk grid hangs on the row's first sample: a row alone, inside a batch, or as the d_len prefix of a longer padded row
+ *   with anything behind it, and a second call, give the same bits in every output.
+ * Scratch: per (row, chunk) 4 + ((1024 + S - 2) / S + 1) doubles, plus B x NS doubles when d_sub is NULL, in an arena of the handle that grows on
+ *   demand like the trim and DTW arenas and counts in ev_alloc_count: a second call at the same shape allocates nothing; ev_reserve does not
+ *   cover it.  Five kernel launches on `stream` (one when L < S), no host wait, no copy. */
+int ev_loudness(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L,
+                int sub_len /* S: samples per 100 ms */, const double *coef /* HOST (10) */, double abs_gate /* mean square */,
+                double *d_sub /* (B, NS) or NULL */, double *d_block /* (B, NB) or NULL */,
+                double *d_gated /* (B, 2) */, int32_t *d_counts /* (B, 3) */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

@@ -22,7 +22,7 @@ EXPORTS = [
     "ev_abi_version", "ev_create", "ev_destroy", "ev_last_error", "ev_load_estimator", "ev_load_vocoder", "ev_load_vocoder_cfg", "ev_load_text_encoder", "ev_text_encoder",
     "ev_text_encoder_status", "ev_stft_magnitude", "ev_denoise", "ev_align", "ev_dbg_conv_bench",
     "ev_workspace_bytes", "ev_cfm_decode", "ev_estimator", "ev_hifigan", "ev_profile_enable", "ev_profile_read", "ev_profile_read_split", "ev_dbg_last_cfg", "ev_set_arithmetic", "ev_get_arithmetic",
-    "ev_op_conv1d", "ev_op_groupnorm_mish", "ev_op_layernorm", "ev_op_split_pieces", "ev_op_attention", "ev_op_ln_mlp", "ev_set_mrf_streams_max",
+    "ev_op_conv1d", "ev_op_groupnorm_mish", "ev_op_groupnorm_mish2", "ev_op_conv_groupnorm", "ev_op_layernorm", "ev_op_split_pieces", "ev_op_attention", "ev_op_ln_mlp", "ev_set_mrf_streams_max",
     "ev_cfm_decode2", "ev_reserve", "ev_alloc_count", "ev_dbg_sk_stats", "ev_op_attn_out", "ev_dbg_set_amax", "ev_dbg_set_attn_h16", "ev_dbg_set_chain", "ev_dbg_sk_taken",
     "ev_load_mel_basis", "ev_mel_spectrogram",
     "ev_maximum_path", "ev_log_prior", "ev_mas_align",
@@ -166,6 +166,8 @@ def load_library() -> C.CDLL:
     lib.ev_dbg_sk_taken.restype = C.c_int64
     lib.ev_op_conv1d.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]
     lib.ev_op_groupnorm_mish.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    lib.ev_op_groupnorm_mish2.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]
+    lib.ev_op_conv_groupnorm.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, C.POINTER(C.c_int), vp]
     lib.ev_op_layernorm.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
     lib.ev_op_split_pieces.argtypes = [vp, vp, i32, vp, vp]
     lib.ev_op_attention.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
@@ -731,6 +733,56 @@ class Engine:
         self._check(self.lib.ev_op_groupnorm_mish(self.h, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), lengths.data_ptr(), B, Cc, T,
                                                   groups, y.data_ptr(), _stream_ptr()), "ev_op_groupnorm_mish")
         return y
+
+    def op_groupnorm_mish2(self, x, gamma, beta, lengths, mode=0, temb=None, R=None, groups=8):
+        """groupnorm_mish_kernel through launch_gn in the estimator's layout (X | R in one 512-wide buffer).  mode 1: temb (256,) or
+        (1, 256) shared, (B, 256) one row per utterance; mode 2: R (B, 256, T)."""
+        x, gamma, beta = self._f32(x), self._f32(gamma), self._f32(beta)
+        B, Cc, T = x.shape
+        lengths = lengths.to(x.device, torch.int32).contiguous()
+        tp, stride, rp = None, 0, None
+        if mode == 1:
+            temb = self._f32(temb).reshape(-1, Cc)
+            if temb.shape[0] not in (1, B):
+                raise ValueError("temb: (1, C) or (B, C)")
+            stride = Cc if (temb.shape[0] == B and B > 1) else 0
+            tp = temb.data_ptr()
+        if mode == 2:
+            R = self._f32(R)
+            if R.shape != x.shape:
+                raise ValueError("R: the shape of x")
+            rp = R.data_ptr()
+        y = torch.empty_like(x)
+        self._check(self.lib.ev_op_groupnorm_mish2(self.h, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), lengths.data_ptr(), B, Cc, T,
+                                                   groups, int(mode), tp, stride, rp, y.data_ptr(), _stream_ptr()), "ev_op_groupnorm_mish2")
+        return y
+
+    def op_conv_groupnorm(self, x, w, bias, gamma, beta, length=None, mode=0, temb=None, R=None):
+        """One utterance x (1, Cin, T) through conv (w (256, Cin, K), 'same' padding) and GroupNorm + Mish as the estimator chains them.
+        Returns (conv output (1, 256, T), part (256, 8, 4): per (32-row tile, group) {count, mean, M2, -}, GroupNorm output (1, 256, T),
+        tiles): tiles = row tiles whose statistics the conv left for the norm, 0 when it left none."""
+        x, gamma, beta = self._f32(x), self._f32(gamma), self._f32(beta)
+        _, Cin, T = x.shape
+        wh = np.ascontiguousarray(w.detach().cpu().float().numpy())
+        K = wh.shape[2]
+        bh = None if bias is None else np.ascontiguousarray(bias.detach().cpu().float().numpy())
+        lengths = torch.tensor([T if length is None else int(length)], dtype=torch.int32, device=x.device)
+        tp = rp = None
+        if mode == 1:
+            temb = self._f32(temb).reshape(-1)
+            tp = temb.data_ptr()
+        if mode == 2:
+            R = self._f32(R)
+            rp = R.data_ptr()
+        conv = torch.empty((1, 256, T), dtype=torch.float32, device=x.device)
+        y = torch.empty_like(conv)
+        part = torch.empty((256, 8, 4), dtype=torch.float32, device=x.device)
+        tiles = C.c_int(0)
+        self._check(self.lib.ev_op_conv_groupnorm(self.h, x.data_ptr(), wh.ctypes.data_as(C.c_void_p),
+                                                  None if bh is None else bh.ctypes.data_as(C.c_void_p), Cin, T, K, gamma.data_ptr(),
+                                                  beta.data_ptr(), lengths.data_ptr(), int(mode), tp, rp, conv.data_ptr(), part.data_ptr(),
+                                                  y.data_ptr(), C.byref(tiles), _stream_ptr()), "ev_op_conv_groupnorm")
+        return conv, part, y, int(tiles.value)
 
     def op_layernorm(self, x, gamma, beta):
         x, gamma, beta = self._f32(x), self._f32(gamma), self._f32(beta)

@@ -3464,6 +3464,100 @@ int ev_op_groupnorm_mish(ev_handle* h, const float* d_x, const float* d_gamma, c
     return rc;
 }
 
+// ev_op_groupnorm_mish with the epilogue modes of GNParams, in the layout run_resnet gives them: X in columns [0, 256) and R in columns
+// [256, 512) of one 512-wide frame-major buffer (ldx = ldr = 512), the estimator's pad rows (P = 2), through launch_gn
+int ev_op_groupnorm_mish2(ev_handle* h, const float* d_x, const float* d_gamma, const float* d_beta, const int32_t* d_lengths,
+                          int B, int C, int T, int groups, int mode, const float* d_temb, int temb_stride, const float* d_R,
+                          float* d_y, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    h->stream = (hipStream_t)stream;
+    if (groups != 8 || C != 256) return fail(h, "groupnorm op: C=256, groups=8 only");
+    if (B <= 0 || T <= 0 || !d_x || !d_gamma || !d_beta || !d_lengths || !d_y || mode < 0 || mode > 2 ||
+        (mode == 1 && (!d_temb || (temb_stride != 0 && temb_stride != C))) || (mode == 2 && !d_R))
+        return fail(h, "ev_op_groupnorm_mish2: bad arguments");
+    Geom g{B * (T + 4), T + 4, 2, T};
+    float *AR = nullptr, *Y = nullptr, *rm = nullptr;
+    const size_t n = (size_t)g.nrows * C;
+    int rc = 0;
+    do {
+        if (hipMalloc((void**)&AR, 2 * n * 4) != hipSuccess || hipMalloc((void**)&Y, n * 4) != hipSuccess ||
+            hipMalloc((void**)&rm, (size_t)g.nrows * 4) != hipSuccess) { rc = fail(h, "hipMalloc failed"); break; }
+        hipMemsetAsync(AR, 0, 2 * n * 4, h->stream); hipMemsetAsync(Y, 0, n * 4, h->stream);
+        hipLaunchKernelGGL(rowmask_kernel, dim3((g.nrows + 255) / 256), dim3(256), 0, h->stream, rm, d_lengths, g.nrows, g.S, g.P, g.T, 1);
+        dim3 g1((T + 31) / 32, (C + 31) / 32, B);
+        hipLaunchKernelGGL(cm_to_fm_kernel, g1, dim3(256), 0, h->stream, d_x, AR, 2 * C, 0, C, T, g.S, g.P, (const float*)nullptr, 1.0f);
+        if (mode == 2) hipLaunchKernelGGL(cm_to_fm_kernel, g1, dim3(256), 0, h->stream, d_R, AR, 2 * C, C, C, T, g.S, g.P, (const float*)nullptr, 1.0f);
+        rc = launch_gn(h, AR, 2 * C, Y, C, d_gamma, d_beta, rm, mode == 1 ? d_temb : nullptr, mode == 2 ? AR + C : nullptr, mode == 2 ? 2 * C : 0,
+                       g, C, mode, nullptr, temb_stride);
+        if (rc) break;
+        hipLaunchKernelGGL(fm_to_cm_kernel, g1, dim3(256), 0, h->stream, (const float*)Y, C, 0, d_y, C, T, g.S, g.P, 1.0f, 0.0f);
+        if (hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, "sync failed: %s", hipGetErrorString(hipGetLastError()));
+    } while (0);
+    if (AR) hipFree(AR);
+    if (Y) hipFree(Y);
+    if (rm) hipFree(rm);
+    return rc;
+}
+
+// One utterance through [conv Cin -> 256, k taps] -> GroupNorm + Mish as run_resnet chains them: launch_conv is asked for the per-tile
+// GroupNorm statistics (Epi::gn_part), launch_gn is handed them.  *tiles_out = ev_handle::gn_stats_tiles as the conv left it (0: the launch
+// took a build that leaves none, and launch_gn ran groupnorm_mish_kernel).  d_part: EV_GN_MAXTILES x 8 groups x {count, mean, M2, -}.
+int ev_op_conv_groupnorm(ev_handle* h, const float* d_x, const float* w, const float* bias, int Cin, int T, int K, const float* d_gamma,
+                         const float* d_beta, const int32_t* d_lengths, int mode, const float* d_temb, const float* d_R, float* d_conv,
+                         float* d_part, float* d_y, int* tiles_out, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    h->stream = (hipStream_t)stream;
+    constexpr int C = 256;
+    if (Cin <= 0 || T <= 0 || K <= 0 || !(K & 1) || !d_x || !w || !d_gamma || !d_beta || !d_lengths || !d_conv || !d_part || !d_y || !tiles_out ||
+        mode < 0 || mode > 2 || (mode == 1 && !d_temb) || (mode == 2 && !d_R))
+        return fail(h, "ev_op_conv_groupnorm: bad arguments");
+    *tiles_out = 0;
+    size_t owned0 = h->owned.size();
+    ConvLayer L;
+    HostTensor wt, bt;
+    wt.p = w; wt.ndim = 3; wt.shape[0] = C; wt.shape[1] = Cin; wt.shape[2] = K;
+    bt.p = bias; bt.ndim = 1; bt.shape[0] = C;
+    if (pack_conv(h, L, wt, bias ? &bt : nullptr, 1)) return 1;
+    Geom g{T + 4, T + 4, 2, T};                       // plan_est's level-0 geometry of one utterance
+    const size_t npart = (size_t)EV_GN_MAXTILES * 8 * 4;
+    float *X = nullptr, *A = nullptr, *AR = nullptr, *Y = nullptr, *rm = nullptr, *part = nullptr;
+    int rc = 0;
+    do {
+        if (L.halo_lo > g.P || L.halo_hi > g.P) { rc = fail(h, "ev_op_conv_groupnorm: %d taps reach past the %d pad rows", K, g.P); break; }
+        const size_t nx = (size_t)g.nrows * Cin, ny = (size_t)g.nrows * C;
+        if (hipMalloc((void**)&X, nx * 4) != hipSuccess || hipMalloc((void**)&A, ny * 4) != hipSuccess || hipMalloc((void**)&AR, 2 * ny * 4) != hipSuccess ||
+            hipMalloc((void**)&Y, ny * 4) != hipSuccess || hipMalloc((void**)&rm, (size_t)g.nrows * 4) != hipSuccess ||
+            hipMalloc((void**)&part, npart * 4) != hipSuccess) { rc = fail(h, "hipMalloc failed"); break; }
+        hipMemsetAsync(X, 0, nx * 4, h->stream); hipMemsetAsync(A, 0, ny * 4, h->stream); hipMemsetAsync(AR, 0, 2 * ny * 4, h->stream);
+        hipMemsetAsync(Y, 0, ny * 4, h->stream); hipMemsetAsync(part, 0, npart * 4, h->stream);
+        hipLaunchKernelGGL(rowmask_kernel, dim3((g.nrows + 255) / 256), dim3(256), 0, h->stream, rm, d_lengths, g.nrows, g.S, g.P, g.T, 1);
+        dim3 g1((T + 31) / 32, (Cin + 31) / 32, 1), g2((T + 31) / 32, C / 32, 1);
+        hipLaunchKernelGGL(cm_to_fm_kernel, g1, dim3(256), 0, h->stream, d_x, X, Cin, 0, Cin, T, g.S, g.P, (const float*)nullptr, 1.0f);
+        if (mode == 2) hipLaunchKernelGGL(cm_to_fm_kernel, g2, dim3(256), 0, h->stream, d_R, AR, 2 * C, C, C, T, g.S, g.P, (const float*)nullptr, 1.0f);
+        Epi e; e.gn_part = part;
+        rc = launch_conv(h, L, X, Cin, A, C, g, e);
+        if (rc) break;
+        *tiles_out = h->gn_stats_tiles;
+        rc = launch_gn(h, A, C, Y, C, d_gamma, d_beta, rm, mode == 1 ? d_temb : nullptr, mode == 2 ? AR + C : nullptr, mode == 2 ? 2 * C : 0,
+                       g, C, mode, part);
+        if (rc) break;
+        hipLaunchKernelGGL(fm_to_cm_kernel, g2, dim3(256), 0, h->stream, (const float*)A, C, 0, d_conv, C, T, g.S, g.P, 1.0f, 0.0f);
+        hipLaunchKernelGGL(fm_to_cm_kernel, g2, dim3(256), 0, h->stream, (const float*)Y, C, 0, d_y, C, T, g.S, g.P, 1.0f, 0.0f);
+        if (hipMemcpyAsync(d_part, part, npart * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) { rc = fail(h, "copy failed"); break; }
+        if (hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, "sync failed: %s", hipGetErrorString(hipGetLastError()));
+    } while (0);
+    if (X) hipFree(X);
+    if (A) hipFree(A);
+    if (AR) hipFree(AR);
+    if (Y) hipFree(Y);
+    if (rm) hipFree(rm);
+    if (part) hipFree(part);
+    while (h->owned.size() > owned0) { hipFree(h->owned.back()); h->owned.pop_back(); }
+    return rc;
+}
+
 int ev_op_split_pieces(ev_handle* h, const float* d_x, int n, float* d_pieces, void* stream) {
     if (!h || !d_x || !d_pieces || n <= 0) return fail(h, "ev_op_split_pieces: bad arguments");
     HIPCHK(h, hipSetDevice(h->device));

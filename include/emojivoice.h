@@ -74,7 +74,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_op_groupnorm_mish2, ev_op_conv_groupnorm (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -510,6 +510,22 @@ int ev_op_conv1d(ev_handle *h, const float *d_x /*(B,Cin,T)*/, const float *w /*
                  int transposed, int stride, int padding, float pre_lrelu_slope /*<0: none*/, float *d_y, void *stream);
 int ev_op_groupnorm_mish(ev_handle *h, const float *d_x /*(B,C,T)*/, const float *d_gamma, const float *d_beta,
                          const int32_t *d_lengths, int B, int C, int T, int groups, float *d_y, void *stream);
+/* ev_op_groupnorm_mish with the three epilogues of the U-Net's ResnetBlock1D (GNParams in ev_kernels.h): mode 0: mish(gn(x)) * m; mode 1:
+ * (mish(gn(x)) * m + temb[c]) * m with d_temb (1, 256) and temb_stride 0 (every utterance shares one row) or (B, 256) and temb_stride 256;
+ * mode 2: mish(gn(x)) * m + R with d_R (B, 256, T).  X and R are staged as the estimator holds them: one 512-wide frame-major buffer, X in
+ * columns [0, 256), R in [256, 512).  d_temb / d_R may be NULL in the modes that do not read them. */
+int ev_op_groupnorm_mish2(ev_handle *h, const float *d_x /*(B,C,T)*/, const float *d_gamma, const float *d_beta,
+                          const int32_t *d_lengths, int B, int C, int T, int groups, int mode, const float *d_temb,
+                          int temb_stride, const float *d_R, float *d_y, void *stream);
+/* One utterance through conv (Cin -> 256, K taps, 'same' padding; w, bias HOST) and GroupNorm + Mish (mode as above, d_temb (256),
+ * d_R (1, 256, T)) the way the estimator chains them: the conv is asked for per-tile GroupNorm statistics and the norm is handed them.
+ * d_conv (1, 256, T): the conv output; d_part (256 x 8 x 4): per (32-row tile of the padded utterance: 2 pad rows in front, group)
+ * {count, mean, M2, -}; d_y (1, 256, T); *tiles_out: row tiles whose statistics the conv left (0: it took a build that leaves none and
+ * the norm computed its own). */
+int ev_op_conv_groupnorm(ev_handle *h, const float *d_x /*(1,Cin,T)*/, const float *w /*HOST (256,Cin,K)*/,
+                         const float *bias /*HOST (256) or NULL*/, int Cin, int T, int K, const float *d_gamma,
+                         const float *d_beta, const int32_t *d_lengths /*(1)*/, int mode, const float *d_temb, const float *d_R,
+                         float *d_conv, float *d_part, float *d_y, int *tiles_out, void *stream);
 /* The three bf16 pieces (as fp32 values, (3, n)) the split builds cut every fp32 operand into: p0 + p1 + p2 == x exactly. */
 int ev_op_split_pieces(ev_handle *h, const float *d_x, int n, float *d_pieces, void *stream);
 int ev_op_layernorm(ev_handle *h, const float *d_x /*(rows,C)*/, const float *d_gamma, const float *d_beta, int rows,

@@ -31,6 +31,7 @@ EXPORTS = [
     "ev_trim_bounds", "ev_trim_apply",
     "ev_pitch_yin", "ev_dtw",
     "ev_loudness",
+    "ev_pyin_observe", "ev_pyin_decode",
 ]
 
 
@@ -150,6 +151,9 @@ def load_library() -> C.CDLL:
     lib.ev_pitch_yin.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]
     lib.ev_dtw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.ev_loudness.argtypes = [vp, vp, vp, i32, i32, i32, vp, C.c_double, vp, vp, vp, vp, vp]
+    f64 = C.c_double
+    lib.ev_pyin_observe.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, i32, i32, vp, i32, f64, f64, vp, vp, vp]
+    lib.ev_pyin_decode.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, f64, f64, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -465,6 +469,69 @@ class Engine:
         self._check(self.lib.ev_loudness(self.h, x.data_ptr(), ptr(ln), B, L, S, coef.ctypes.data, float(abs_gate), ptr(sub), ptr(block),
                                          gated.data_ptr(), counts.data_ptr(), _stream_ptr()), "ev_loudness")
         return sub, block, gated, counts
+
+    def pyin_observe(self, x, lengths, frame_length: int, hop_length: int, tau_min: int, tau_max: int, sr: float, fmin: float,
+                     bins_per_octave: int, n_bins: int, w, boltzmann: float = 2.0, no_trough_prob: float = 0.01, out=None):
+        """pYIN's observation per frame of every row of ``x`` (B, L) (ev_pyin_observe): (obs (B, F, n_bins) float64: the probability of each
+        pitch bin, pv (B, F) float64: the probability that the frame is voiced) on the device, F = ceil(L / hop_length).  ``w``: the
+        threshold prior of ``audio.pyin_threshold_prior``, float64, read on the host during the call.  ``out``: (obs, pv) tensors to write
+        into instead of new ones."""
+        x = self._f32(x)
+        if x.dim() != 2:
+            raise ValueError(f"pyin_observe: x must be (B, L), got shape {tuple(x.shape)}")
+        B, L = x.shape
+        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"pyin_observe: {B} lengths expected, got {ln.numel()}")
+        w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(-1))
+        F = -(-L // max(int(hop_length), 1))
+        nb = max(int(n_bins), 0)
+        if out is None:
+            obs = torch.empty((B, F, nb), dtype=torch.float64, device=x.device)
+            pv = torch.empty((B, F), dtype=torch.float64, device=x.device)
+        else:
+            obs, pv = out
+            if obs.dtype != torch.float64 or pv.dtype != torch.float64 or tuple(obs.shape) != (B, F, nb) or tuple(pv.shape) != (B, F) \
+                    or not obs.is_contiguous() or not pv.is_contiguous():
+                raise ValueError(f"pyin_observe: out must be contiguous float64 ({B}, {F}, {nb}) and ({B}, {F})")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._check(self.lib.ev_pyin_observe(self.h, x.data_ptr(), ptr(ln), B, L, int(frame_length), int(hop_length), int(tau_min), int(tau_max),
+                                             float(sr), float(fmin), int(bins_per_octave), int(n_bins), w.ctypes.data, int(w.size),
+                                             float(boltzmann), float(no_trough_prob), obs.data_ptr(), pv.data_ptr(), _stream_ptr()),
+                    "ev_pyin_observe")
+        return obs, pv
+
+    def pyin_decode(self, obs, pv, lengths, L: int, hop_length: int, R: int, log_tri, log_Z, log_stay: float, log_switch: float, back=None):
+        """The Viterbi pass over (voiced / unvoiced) x pitch bins (ev_pyin_decode) of ``obs`` (B, F, n_bins) and ``pv`` (B, F), float64, F =
+        ceil(L / hop_length): (state (B, F) int32: v n_bins + i per frame, v = 0 voiced, -1 past a row's ceil(len / hop_length) frames;
+        loglik (B,) float64) on the device.  ``lengths`` (B,): SAMPLES per row (None: L).  The tables of ``audio.pyin_transition`` are read on
+        the host during the call.  ``back``: (B, F, 2 n_bins) uint8 scratch to use instead of a new tensor."""
+        if obs.dtype != torch.float64 or pv.dtype != torch.float64 or obs.dim() != 3 or pv.dim() != 2 or obs.shape[:2] != pv.shape:
+            raise ValueError(f"pyin_decode: float64 obs (B, F, n_bins) and pv (B, F) expected, got {tuple(obs.shape)} and {tuple(pv.shape)}")
+        if not obs.is_cuda:
+            raise EvLibraryError("no CPU fallback: pyin_decode needs its inputs on the GPU")
+        obs, pv = obs.contiguous(), pv.contiguous()
+        B, F, nb = obs.shape
+        if F != -(-int(L) // max(int(hop_length), 1)):
+            raise ValueError(f"pyin_decode: obs has {F} frames, L={L} at hop_length={hop_length} has {-(-int(L) // max(int(hop_length), 1))}")
+        ln = None if lengths is None else torch.as_tensor(lengths).to(obs.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"pyin_decode: {B} lengths expected, got {ln.numel()}")
+        log_tri = np.ascontiguousarray(np.asarray(log_tri, dtype=np.float64).reshape(-1))
+        log_Z = np.ascontiguousarray(np.asarray(log_Z, dtype=np.float64).reshape(-1))
+        if log_tri.size != int(R) + 1 or log_Z.size != nb:
+            raise ValueError(f"pyin_decode: log_tri must hold R + 1 = {int(R) + 1} values and log_Z n_bins = {nb} (got {log_tri.size} and {log_Z.size})")
+        if back is None:
+            back = torch.empty((B, F, 2 * nb), dtype=torch.uint8, device=obs.device)
+        elif back.dtype != torch.uint8 or back.numel() < B * F * 2 * nb or not back.is_contiguous():
+            raise ValueError(f"pyin_decode: back must be contiguous uint8 with at least {B * F * 2 * nb} elements")
+        state = torch.empty((B, F), dtype=torch.int32, device=obs.device)
+        loglik = torch.empty((B,), dtype=torch.float64, device=obs.device)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._check(self.lib.ev_pyin_decode(self.h, obs.data_ptr(), pv.data_ptr(), ptr(ln), B, int(L), int(hop_length), nb, int(R),
+                                            log_tri.ctypes.data, log_Z.ctypes.data, float(log_stay), float(log_switch), back.data_ptr(),
+                                            state.data_ptr(), loglik.data_ptr(), _stream_ptr()), "ev_pyin_decode")
+        return state, loglik
 
     def maximum_path(self, value, x_lengths, y_lengths, want_path: bool = True, want_dur: bool = True):
         """monotonic_align.maximum_path on (B, Tx, Ty) fp32 scores with per-row lengths (ev_maximum_path): (path (B, Tx, Ty) 0/1 or None,

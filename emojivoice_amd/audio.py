@@ -24,6 +24,7 @@ Between a raw take and all of that (the recorder's files begin and end on a key 
 And beside the mel, frame for frame, the pitch (``ev_pitch_yin``: YIN; librosa.yin is the model):
 
     p = pitch_yin(y)                                          # {"f0" (B, F) Hz, "voiced" (B, F) bool, "aperiodicity" (B, F)}, F = ceil(L / 256)
+    p = pitch_pyin(y)                                         # {"f0", "voiced", "voiced_prob"}: probabilistic YIN + Viterbi (ev_pyin_observe / ev_pyin_decode; librosa.pyin)
     s = prosody_statistics(p["f0"], p["voiced"])              # voiced fraction, f0 median / 5th / 95th percentile, range in semitones per row
 
 And between a recording and its synthesised rendering, which differ in length and timing (``ev_dtw``: dynamic time warping):
@@ -383,6 +384,105 @@ def pitch_yin(y, sr: int = 22050, fmin: float = 65.0, fmax: float = 600.0, frame
     voiced = lag > 0
     f0 = torch.where(voiced, float(sr) / torch.where(voiced, period, torch.ones_like(period)), torch.zeros_like(period))
     return {"f0": f0, "voiced": voiced, "aperiodicity": cmnd}
+
+
+def _beta_cdf_integer(x: float, a: int, b: int) -> float:
+    """I_x(a, b) for integers a, b >= 1: the upper tail sum_{j >= a} C(n, j) x^j (1 - x)^(n - j) of a binomial over n = a + b - 1 trials."""
+    n = a + b - 1
+    return float(sum(math.comb(n, j) * x ** j * (1.0 - x) ** (n - j) for j in range(a, n + 1)))
+
+
+def pyin_threshold_prior(n_thresholds: int = 100, beta_parameters=(2, 18)) -> np.ndarray:
+    """pYIN's prior over the YIN threshold, float64 (n_thresholds,): entry t - 1 is the Beta(a, b) mass of ((t - 1) / n, t / n], n =
+    ``n_thresholds`` (the ``w`` of ``ev_pyin_observe``).  Integer a, b use the closed form (a binomial tail); others need scipy's
+    regularised incomplete beta function."""
+    n = int(n_thresholds)
+    if not 1 <= n <= 128:
+        raise ValueError(f"pitch_pyin: 1 <= n_thresholds <= 128 expected (got {n_thresholds})")
+    a, b = beta_parameters
+    if not (a > 0 and b > 0):
+        raise ValueError(f"pitch_pyin: beta_parameters must be positive (got {beta_parameters})")
+    theta = [t / n for t in range(n + 1)]
+    if float(a).is_integer() and float(b).is_integer():
+        cdf = np.array([_beta_cdf_integer(t, int(a), int(b)) for t in theta], dtype=np.float64)
+    else:
+        try:
+            from scipy.special import betainc
+        except ImportError as e:
+            raise ValueError(f"pitch_pyin: beta_parameters={beta_parameters} are not integers, which needs scipy") from e
+        cdf = np.asarray(betainc(float(a), float(b), np.array(theta)), dtype=np.float64)
+    return np.diff(cdf)
+
+
+def pyin_bins(fmin: float, fmax: float, resolution: float = 0.1) -> Tuple[int, int]:
+    """(bins_per_octave, n_bins) of pYIN's pitch grid: 12 ceil(1 / resolution) bins per octave from ``fmin``; bin i is fmin 2^(i / bpo)."""
+    if not (0 < fmin < fmax) or not (0 < resolution <= 1):
+        raise ValueError(f"pitch_pyin: 0 < fmin < fmax and 0 < resolution <= 1 expected (got fmin={fmin} fmax={fmax} resolution={resolution})")
+    bpo = 12 * int(math.ceil(1.0 / resolution))
+    return bpo, int(math.floor(bpo * math.log2(fmax / fmin))) + 1
+
+
+def pyin_transition_radius(sr: int, hop_length: int, bins_per_octave: int, max_transition_rate: float = 35.92) -> int:
+    """R, the most bins the pitch may move between two frames: (bpo / 12) round(max_transition_rate 12 H / sr) / 2, rounded down."""
+    return int((bins_per_octave // 12) * round(max_transition_rate * 12 * hop_length / sr) / 2)
+
+
+def pyin_transition(n_bins: int, R: int, switch_prob: float = 0.01):
+    """The host tables of ``ev_pyin_decode``, float64: (log_tri (R + 1,): log(R + 1 - d); log_Z (n_bins,): log of the triangle's mass that
+    stays inside [0, n_bins) when it is centred on bin j; log_stay = log(1 - switch_prob); log_switch = log(switch_prob))."""
+    if not 0 < switch_prob < 1:
+        raise ValueError(f"pitch_pyin: 0 < switch_prob < 1 expected (got {switch_prob})")
+    n_bins, R = int(n_bins), int(R)
+    num = (R + 1 - np.arange(R + 1)).astype(np.float64)
+    j = np.arange(n_bins)[:, None]
+    i = np.arange(n_bins)[None, :]
+    Z = np.clip(R + 1 - np.abs(i - j), 0, None).astype(np.float64).sum(axis=1)          # (integers: exact in any order)
+    return np.log(num), np.log(Z), math.log(1.0 - switch_prob), math.log(switch_prob)
+
+
+PYIN_SLICE_BYTES = 1 << 30           # pitch_pyin processes this much of obs + back at a time
+
+
+@torch.inference_mode()
+def pitch_pyin(y, sr: int = 22050, fmin: float = 65.0, fmax: float = 600.0, frame_length: int = 1024, hop_length: int = 256, lengths=None,
+               n_thresholds: int = 100, beta_parameters=(2, 18), boltzmann_parameter: float = 2.0, resolution: float = 0.1,
+               max_transition_rate: float = 35.92, switch_prob: float = 0.01, no_trough_prob: float = 0.01):
+    """The fundamental frequency per frame by probabilistic YIN on the device (``ev_pyin_observe`` + ``ev_pyin_decode``; no torch fallback;
+    ``librosa.pyin`` is the model): every trough of YIN's d' is a candidate with a probability under a Beta prior on the threshold, and a
+    Viterbi pass over (voiced / unvoiced) x pitch bins picks the contour, so one frame's octave error or drop-out does not stand against
+    its neighbours.  The frames are ``pitch_yin``'s and the mel's.  ``y`` 1-D, or (B, L) with ``lengths`` (B,) samples or None, on the GPU
+    -> {"f0" (B, F) float32 Hz: fmin 2^(i / bins_per_octave) of the chosen bin, 0 where unvoiced; "voiced" (B, F) bool; "voiced_prob"
+    (B, F) float32: the observation's probability that the frame is voiced}, F = ceil(L / hop_length).  Frames past a row's
+    ceil(len / hop_length) are unvoiced with probability 0.  Rows are processed in slices whose obs and back-pointers stay under 1 GiB."""
+    _trim_input(y, "pitch_pyin")
+    tau_min, tau_max = pitch_lag_range(sr, fmin, fmax)
+    bpo, n_bins = pyin_bins(fmin, fmax, resolution)
+    R = pyin_transition_radius(sr, hop_length, bpo, max_transition_rate)
+    w = pyin_threshold_prior(n_thresholds, beta_parameters)
+    log_tri, log_Z, log_stay, log_switch = pyin_transition(n_bins, R, switch_prob)
+    eng = _trim_engine(y.device)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    B, L = x.shape
+    ln = None if lengths is None or y.dim() == 1 else torch.as_tensor(lengths).to(x.device, torch.int32)
+    if ln is not None and ln.numel() != B:
+        raise ValueError(f"pitch_pyin: {B} lengths expected, got {ln.numel()}")
+    F = -(-L // max(int(hop_length), 1))
+    rows = max(1, min(B, PYIN_SLICE_BYTES // max(F * n_bins * 10, 1)))      # 8 bytes of obs and 2 of back per frame and bin
+    state = torch.empty((B, F), dtype=torch.int32, device=x.device)
+    pv = torch.empty((B, F), dtype=torch.float64, device=x.device)
+    obs = torch.empty((rows, F, n_bins), dtype=torch.float64, device=x.device)
+    back = torch.empty((rows, F, 2 * n_bins), dtype=torch.uint8, device=x.device)
+    for r0 in range(0, B, rows):
+        nr = min(rows, B - r0)
+        lr = None if ln is None else ln[r0: r0 + nr]
+        eng.pyin_observe(x[r0: r0 + nr], lr, frame_length, hop_length, tau_min, tau_max, sr, fmin, bpo, n_bins, w, boltzmann_parameter,
+                         no_trough_prob, out=(obs[:nr], pv[r0: r0 + nr]))
+        st, _ = eng.pyin_decode(obs[:nr], pv[r0: r0 + nr], lr, L, hop_length, R, log_tri, log_Z, log_stay, log_switch, back=back[:nr])
+        state[r0: r0 + nr] = st
+    voiced = (state >= 0) & (state < n_bins)
+    f0 = torch.where(voiced, float(fmin) * torch.exp2(state.clamp_min(0).to(torch.float64) / float(bpo)), torch.zeros((), dtype=torch.float64,
+                                                                                                                     device=x.device))
+    return {"f0": f0.to(torch.float32), "voiced": voiced, "voiced_prob": pv.to(torch.float32)}
 
 
 def semitones(f_hi, f_lo):

@@ -387,10 +387,23 @@ def pitch_summary(f0_voiced):
     return {"f0_median": med, "f0_p05": p05, "f0_p95": p95, "f0_range_semitones": 12.0 * math.log2(p95 / p05)}
 
 
+def pitch_method(args) -> str:
+    return getattr(args, "pitch_method", None) or "yin"
+
+
+def pitch_tracker(args):
+    """--pitch_method: audio.pitch_yin (the default; every frame decided on its own) or audio.pitch_pyin (probabilistic YIN: a Viterbi
+    pass over the frames' candidates).  Both return "f0" and "voiced" of the same shapes and dtypes; looked up at call time."""
+    from . import audio
+
+    return audio.pitch_pyin if pitch_method(args) == "pyin" else audio.pitch_yin
+
+
 @torch.inference_mode()
 def prosody_report(args, device):
     """--prosody_report FILELIST: the filelist --prepare_dataset writes ('path|spk|text'; 'path|text' counts as speaker "0").  Every file
-    is loaded with audio.load_audio(path, 22050) and tracked by audio.pitch_yin, --batch_size files at a time (padded to the longest,
+    is loaded with audio.load_audio(path, 22050) and tracked by audio.pitch_yin (--pitch_method pyin: audio.pitch_pyin, and the report
+    gains "pitch_method": "pyin"), --batch_size files at a time (padded to the longest,
     each row with its own length).  FILELIST.prosody.json receives, per file, the numbers of audio.prosody_statistics (voiced fraction,
     f0 median / 5th / 95th percentile in Hz, the 5-to-95 range in semitones; null where a file has no voiced frame) and, per speaker,
     the same over that speaker's POOLED voiced frames, with the file count."""
@@ -407,7 +420,7 @@ def prosody_report(args, device):
         batch = torch.zeros(len(ys), max(max(lens), 1), device=ys[0].device)
         for r, y in enumerate(ys):
             batch[r, : lens[r]] = y.reshape(-1)
-        out = audio.pitch_yin(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
+        out = pitch_tracker(args)(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
         n_frames = [-(-n // PROSODY_HOP) for n in lens]
         st = {k: v.cpu() for k, v in audio.prosody_statistics(out["f0"], out["voiced"], n_frames).items()}
         for r, (wav, spk, _) in enumerate(chunk):
@@ -423,6 +436,8 @@ def prosody_report(args, device):
         v = torch.cat(parts)
         speakers[spk] = {"files": len(parts), "voiced_fraction": v.numel() / max(frames_of[spk], 1), **pitch_summary(v)}
     rep = {"sample_rate": PROSODY_SR, "hop_length": PROSODY_HOP, "files": files, "speakers": speakers}
+    if pitch_method(args) != "yin":
+        rep["pitch_method"] = pitch_method(args)
     out_path = f"{args.prosody_report}.prosody.json"
     with open(out_path, "w") as f:
         json.dump(rep, f, indent=1)
@@ -536,7 +551,8 @@ def evaluation_means(pairs):
 def evaluate_pairs(args, device):
     """--evaluate_pairs PAIRS: how close is what the model says to what the actor recorded.  Each line names a recording and the
     synthesised wav of the same sentence (and optionally the speaker).  Both go through wav_at_rate(..., 22050), the vocoder config's mel,
-    audio.mel_cepstrum, and audio.pitch_yin (whose first L / 256 frames are the mel's); ev_dtw aligns the two cepstral sequences,
+    audio.mel_cepstrum, and audio.pitch_yin (whose first L / 256 frames are the mel's; --pitch_method pyin: audio.pitch_pyin, and the
+    report gains "pitch_method": "pyin"); ev_dtw aligns the two cepstral sequences,
     --batch_size pairs at a time (padded to the longest, each row with its lengths).  PAIRS.eval.json receives per pair mcd_db,
     f0_rmse_cents (null without a frame pair voiced on both sides), voicing_error, voiced_pairs, frames_recorded, frames_synthesised and
     path_steps; per speaker and overall their means, f0 pooled over the both-voiced frame pairs; and under "skipped" the pairs with a file
@@ -557,7 +573,7 @@ def evaluate_pairs(args, device):
         for r, w in enumerate(wavs):
             cep[r, :, : frames[r]] = audio.mel_cepstrum(audio.mel_spectrogram(w, *EVAL_MEL), 13)[0]   # per file: each signal's own reflect padding
             sig[r, : w.shape[1]] = w[0]
-        return cep, frames, audio.pitch_yin(sig, sr, hop_length=hop, lengths=[w.shape[1] for w in wavs])
+        return cep, frames, pitch_tracker(args)(sig, sr, hop_length=hop, lengths=[w.shape[1] for w in wavs])
 
     for b0 in range(0, len(entries), args.batch_size):
         chunk = []
@@ -587,6 +603,8 @@ def evaluate_pairs(args, device):
         by_spk.setdefault(r["speaker"], []).append(r)
     rep = {"sample_rate": sr, "hop_length": hop, "n_coeffs": 13, "pairs": records, "speakers": {k: evaluation_means(v) for k, v in by_spk.items()},
            "overall": evaluation_means(records) if records else None, "skipped": skipped}
+    if pitch_method(args) != "yin":
+        rep["pitch_method"] = pitch_method(args)
     out_path = f"{args.evaluate_pairs}.eval.json"
     with open(out_path, "w") as f:
         json.dump(rep, f, indent=1)
@@ -650,6 +668,9 @@ def cli(argv=None):
     p.add_argument("--evaluate_pairs", type=str, default=None, help="objective evaluation instead of synthesis: a file of 'recorded.wav|synthesised.wav[|spk]' lines -> "
                    "PAIRS.eval.json: mel-cepstral distortion (dB), f0 RMSE (cents) and voicing-decision error over the DTW path per pair, per speaker "
                    "and overall (DTW on the device, --batch_size pairs per batch; needs no checkpoint)")
+    p.add_argument("--pitch_method", type=str, default="yin", choices=["yin", "pyin"], help="--prosody_report / --evaluate_pairs: the pitch tracker. yin decides "
+                   "every frame on its own; pyin (probabilistic YIN) keeps every candidate of a frame and picks the contour by a Viterbi pass, which "
+                   "removes most octave jumps and dropped frames; its report carries \"pitch_method\": \"pyin\"")
     p.add_argument("--loudness_report", type=str, default=None, help="loudness analysis instead of synthesis: a filelist 'path|spk|text' -> FILELIST.loudness.json: "
                    "ITU-R BS.1770-4 integrated LUFS, loudest 400 ms block, peak in dBFS and seconds per file; mean / std / min / max per speaker and the files "
                    "more than 3 LU from their speaker's mean (on the device, --batch_size files per batch; needs no checkpoint)")

@@ -2894,6 +2894,93 @@ int ev_pitch_yin(ev_handle* h, const float* d_x, const int32_t* d_len, int B, in
     return 0;
 }
 
+// Probabilistic YIN, the observation: pitch_yin_kernel's grid and LDS plus the trough tables behind them (pyin_observe_kernel, ev_kernels.h).
+// The threshold prior travels in the kernel's arguments (n_thr <= 128), with its ascending prefix sums.
+int ev_pyin_observe(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, int frame_length, int hop_length, int tau_min,
+                    int tau_max, double sr, double fmin, int bins_per_octave, int n_bins, const double* w, int n_thr, double boltzmann,
+                    double no_trough_prob, double* d_obs, double* d_pv, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (B < 1 || B > 65535) return fail(h, "ev_pyin_observe: B=%d outside 1 <= B <= 65535", B);
+    if (L < 1 || !d_x) return fail(h, "ev_pyin_observe: bad arguments L=%d (L >= 1, non-null d_x)", L);
+    const int W = frame_length, H = hop_length;
+    if (H < 64 || H > 4096 || H % 64) return fail(h, "ev_pyin_observe: hop_length=%d must be a multiple of 64 and at most 4096", H);
+    if (W < 64 || W > 4096 || W % 64)
+        return fail(h, "ev_pyin_observe: frame_length=%d must be a multiple of 64 with 64 <= frame_length <= 4096", W);
+    if (tau_min < 1 || tau_min > tau_max || tau_max > 2048)
+        return fail(h, "ev_pyin_observe: tau_min=%d tau_max=%d outside 1 <= tau_min <= tau_max <= 2048", tau_min, tau_max);
+    if (n_thr < 1 || n_thr > 128) return fail(h, "ev_pyin_observe: n_thr=%d outside 1 <= n_thr <= 128", n_thr);
+    if (n_bins < 2 || n_bins > 1024) return fail(h, "ev_pyin_observe: n_bins=%d outside 2 <= n_bins <= 1024", n_bins);
+    if (bins_per_octave < 1) return fail(h, "ev_pyin_observe: bins_per_octave=%d must be at least 1", bins_per_octave);
+    if (!(sr > 0.0) || !(fmin > 0.0) || !std::isfinite(sr) || !std::isfinite(fmin))
+        return fail(h, "ev_pyin_observe: sr=%g and fmin=%g must be positive and finite", sr, fmin);
+    if (!(boltzmann > 0.0) || !std::isfinite(boltzmann)) return fail(h, "ev_pyin_observe: boltzmann=%g must be positive and finite", boltzmann);
+    if (!(no_trough_prob >= 0.0 && no_trough_prob <= 1.0))
+        return fail(h, "ev_pyin_observe: no_trough_prob=%g outside 0 <= no_trough_prob <= 1", no_trough_prob);
+    if (!w) return fail(h, "ev_pyin_observe: w must be non-null (HOST, n_thr doubles)");
+    for (int t = 0; t < n_thr; ++t)
+        if (!(w[t] >= 0.0) || !std::isfinite(w[t])) return fail(h, "ev_pyin_observe: w[%d]=%g is not a finite weight >= 0", t, w[t]);
+    if (!d_obs || !d_pv) return fail(h, "ev_pyin_observe: no output (d_obs and d_pv must be non-null)");
+    h->stream = (hipStream_t)stream;
+    PyinObserveParams p{};
+    p.x = d_x; p.len = d_len; p.obs = d_obs; p.pv = d_pv;
+    p.L = L; p.F = (int)(((long long)L + H - 1) / H); p.W = W; p.H = H; p.tau_min = tau_min; p.tau_max = tau_max;
+    p.n_bins = n_bins; p.n_thr = n_thr; p.kmax = (tau_max - tau_min) / 2 + 1;
+    p.sr = sr; p.fmin = fmin; p.bpo = (double)bins_per_octave; p.lambda = boltzmann; p.c0 = 1.0 - std::exp(-boltzmann); p.ntp = no_trough_prob;
+    double run = 0.0;
+    for (int t = 0; t < n_thr; ++t) { p.w[t] = w[t]; run += w[t]; p.cw[t + 1] = run; }
+    const size_t n = (size_t)tau_max + 1, kmax = (size_t)p.kmax;
+    const size_t yin = (4 * n * sizeof(double) + ((size_t)W + n) * sizeof(float) + 7) / 8 * 8;
+    p.off_extra = (int)yin;
+    const size_t smem = yin + (2 * kmax + 1 + (size_t)n_thr + 1 + (size_t)n_bins + 4) * sizeof(double)
+                      + (3 * kmax + 8 + (kmax + 63) / 64 * ((size_t)n_thr + 1)) * sizeof(int);
+    launch<pyin_observe_kernel>(h->device, dim3((unsigned)p.F, (unsigned)B), dim3(256), smem, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Probabilistic YIN, the decoding: one workgroup per row, one thread per state (two beyond 1024 states); LDS = 2 x 2 n_bins float64 of delta,
+// the two transition tables and the end state's reduction (pyin_decode_kernel, ev_kernels.h).  The host tables travel in the kernel's arguments.
+int ev_pyin_decode(ev_handle* h, const double* d_obs, const double* d_pv, const int32_t* d_len, int B, int L, int hop_length, int n_bins, int R,
+                   const double* log_tri, const double* log_Z, double log_stay, double log_switch, uint8_t* d_back, int32_t* d_state,
+                   double* d_loglik, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (B < 1 || B > 65535) return fail(h, "ev_pyin_decode: B=%d outside 1 <= B <= 65535", B);
+    if (L < 1) return fail(h, "ev_pyin_decode: L=%d must be at least 1", L);
+    const int H = hop_length;
+    if (H < 64 || H > 4096 || H % 64) return fail(h, "ev_pyin_decode: hop_length=%d must be a multiple of 64 and at most 4096", H);
+    if (n_bins < 2 || n_bins > 1024) return fail(h, "ev_pyin_decode: n_bins=%d outside 2 <= n_bins <= 1024", n_bins);
+    if (R < 0 || R > 63) return fail(h, "ev_pyin_decode: R=%d outside 0 <= R <= 63", R);
+    if (!(log_stay < 0.0) || !(log_switch < 0.0) || !std::isfinite(log_stay) || !std::isfinite(log_switch))
+        return fail(h, "ev_pyin_decode: switch_prob outside 0 < switch_prob < 1 (log_stay=%g and log_switch=%g must be finite and negative)",
+                    log_stay, log_switch);
+    if (!d_obs || !d_pv) return fail(h, "ev_pyin_decode: d_obs and d_pv must be non-null");
+    if (!log_tri || !log_Z) return fail(h, "ev_pyin_decode: log_tri (HOST, R + 1 doubles) and log_Z (HOST, n_bins doubles) must be non-null");
+    if (!d_back) return fail(h, "ev_pyin_decode: d_back must be non-null (B x F x 2 n_bins bytes of the caller's)");
+    if (!d_state || !d_loglik) return fail(h, "ev_pyin_decode: no output (d_state and d_loglik must be non-null)");
+    for (int d = 0; d <= R; ++d) if (!std::isfinite(log_tri[d])) return fail(h, "ev_pyin_decode: log_tri[%d]=%g is not finite", d, log_tri[d]);
+    for (int j = 0; j < n_bins; ++j) if (!std::isfinite(log_Z[j])) return fail(h, "ev_pyin_decode: log_Z[%d]=%g is not finite", j, log_Z[j]);
+    h->stream = (hipStream_t)stream;
+    PyinDecodeParams p{};
+    p.obs = d_obs; p.pv = d_pv; p.len = d_len; p.back = d_back; p.state = d_state; p.loglik = d_loglik;
+    p.L = L; p.F = (int)(((long long)L + H - 1) / H); p.H = H; p.n_bins = n_bins; p.R = R;
+    p.init = -std::log(2.0 * (double)n_bins); p.tiny = std::numeric_limits<double>::min();
+    for (int d = 0; d <= R; ++d) { p.t_stay[d] = log_tri[d] + log_stay; p.t_switch[d] = log_tri[d] + log_switch; }
+    if (n_bins <= 128) for (int j = 0; j < n_bins; ++j) p.zc[j] = log_Z[j];
+    else {
+        for (int j = 63; j <= n_bins - 64; ++j)
+            if (log_Z[j] != log_Z[63])
+                return fail(h, "ev_pyin_decode: log_Z[%d] differs from log_Z[63]: log_Z must be constant over R <= j <= n_bins - 1 - R", j);
+        for (int j = 0; j < 64; ++j) { p.zc[j] = log_Z[j]; p.zc[64 + j] = log_Z[n_bins - 64 + j]; }
+    }
+    const int S = 2 * n_bins, NT = std::min(1024, round_up(S, 64));
+    const size_t smem = (2 * (size_t)S + 16 + 128) * sizeof(double) + 16 * sizeof(int);
+    launch<pyin_decode_kernel>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 // Dynamic time warping: one workgroup per row (dtw_kernel, ev_kernels.h).  LDS plan in bytes: [D ring 3 x Tx float64][S ring 3 x Tx uint16],
 // reused after the forward pass as the path stage of Tx + Ty - 1 words; then the decision words ceil(Ty / 32) x Tx x 8 bytes where they still
 // fit into the CU's 160 KiB, else in the handle's arena.  Without a path there are no decision words at all.

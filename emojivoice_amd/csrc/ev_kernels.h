@@ -6313,32 +6313,21 @@ __device__ __forceinline__ void pitch_yin_pass(const float* xs, double* part, in
     }
 }
 
-__global__ __launch_bounds__(256) void pitch_yin_kernel(const PitchYinParams p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t o = (size_t)b * p.F + f;
-    int len = p.len ? p.len[b] : p.L;
-    if (len < 1 || len > p.L) len = 0;                                  // a bad row is a row of zeros (the ev_mas_align convention)
-    const int nf = (int)(((long long)len + p.H - 1) / p.H);
-    if (f >= nf) {                                                      // (uniform over the workgroup)
-        if (tid == 0) {
-            if (p.lag) p.lag[o] = 0;
-            if (p.period) p.period[o] = 0.f;
-            if (p.cmnd) p.cmnd[o] = 0.f;
-        }
-        return;
-    }
-    const int n = p.tau_max + 1, span = p.W + n;
+// Frame f of a row of len valid samples: stages its span and leaves d'(tau), 1 <= tau <= n = tau_max + 1, at index tau - 1 of the returned
+// LDS array (n float64; the n before it hold S, the n before those d).  Every thread of the 256 calls it; it ends on a barrier.  smem:
+// 4 n float64 + W + n fp32.  Shared by pitch_yin_kernel and pyin_observe_kernel: one framing, one d, one S chain, one d'.
+__device__ __forceinline__ const double* pitch_cmnd_frame(float* smem, const float* xrow, int len, int f, int W, int H, int tau_max, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int n = tau_max + 1, span = W + n;
     double* part = (double*)smem;                                       // [4][n]: a quarter's partials; then row 0 = d, row 1 = S, row 2 = d'
     float* xs = (float*)(part + 4 * (size_t)n);                         // [span]
-    const float* xrow = p.x + (size_t)b * p.L;
-    const long long s0 = (long long)f * p.H + p.H / 2 - (p.W + p.tau_max) / 2;
+    const long long s0 = (long long)f * H + H / 2 - (W + tau_max) / 2;
     for (int i = tid; i < span; i += 256) {
         const long long g = s0 + i;
         xs[i] = (g >= 0 && g < len) ? xrow[g] : 0.f;
     }
     __syncthreads();
-    const int nch = (n + 63) >> 6, jq = p.W >> 2;
+    const int nch = (n + 63) >> 6, jq = W >> 2;
     double* mine = part + (size_t)wave * n;
     for (int c0 = 0; c0 < nch; c0 += 4) {                               // (uniform over the wave)
         const int nk = min(4, nch - c0), j0 = wave * jq, j1 = j0 + jq;
@@ -6363,6 +6352,25 @@ __global__ __launch_bounds__(256) void pitch_yin_kernel(const PitchYinParams p) 
         cm[i] = s > 0.0 ? dd[i] * (double)(i + 1) / s : 1.0;
     }
     __syncthreads();
+    return cm;
+}
+
+__global__ __launch_bounds__(256) void pitch_yin_kernel(const PitchYinParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t o = (size_t)b * p.F + f;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;                                  // a bad row is a row of zeros (the ev_mas_align convention)
+    const int nf = (int)(((long long)len + p.H - 1) / p.H);
+    if (f >= nf) {                                                      // (uniform over the workgroup)
+        if (tid == 0) {
+            if (p.lag) p.lag[o] = 0;
+            if (p.period) p.period[o] = 0.f;
+            if (p.cmnd) p.cmnd[o] = 0.f;
+        }
+        return;
+    }
+    const double* cm = pitch_cmnd_frame(smem, p.x + (size_t)b * p.L, len, f, p.W, p.H, p.tau_max, tid);
     if (wave != 0) return;
     int first = 0x7fffffff;
     double mn = 1.0 / 0.0;
@@ -6393,6 +6401,288 @@ __global__ __launch_bounds__(256) void pitch_yin_kernel(const PitchYinParams p) 
     if (p.lag) p.lag[o] = tau0;
     if (p.period) p.period[o] = per;
     if (p.cmnd) p.cmnd[o] = (float)ap;
+}
+
+// ---------------------------------------------------------------------------
+// Probabilistic YIN, the observation (ev_pyin_observe): Mauch and Dixon's pYIN over the d' of pitch_cmnd_frame, d'(0) := 1.  Per frame:
+//   troughs   tau in [tau_min, tau_max] with d'(tau) < d'(tau - 1) and d'(tau) <= d'(tau + 1), ascending (no two are adjacent: K <= kmax =
+//             (tau_max - tau_min) / 2 + 1); trough k has ONE activation index a_k = the least t with d'(tau_k) < t / n_thr (n_thr + 1: none)
+//   P_k       sum over t >= a_k, ascending, of G_t E[pos(k, t)]: E[p] = exp(-lambda p), pos(k, t) = #{m < k : a_m <= t}, N(t) = #{m : a_m <= t},
+//             G_t = w_t (1 - e^-lambda) / (1 - E[N(t)]); the trough g of least d' (lowest lag on ties) gains no_trough_prob * cw[a_g - 1],
+//             cw the host's ascending prefix sums of w
+//   bin_k     clip(rint(bpo log2(sr / (period_k fmin))), 0, n_bins - 1), period_k = tau_k + pitch_yin_kernel's parabolic shift
+//   obs[bin_k] += P_k (P_k > 0) in ascending k; pv = min(sum_i obs[i], 1) in ascending i
+// One workgroup of four waves per (frame, row), as pitch_yin_kernel.  Trough k = tid + 256 r is thread tid's: wave q holds the 64-trough
+// blocks q, q + 4, ...  pos comes from ballots: a first sweep over t counts each block's active troughs (cnt[block][t], one lane stores),
+// n_thr threads turn the counts into exclusive prefixes over the blocks, N(t) and G_t, and a second sweep adds G_t E[prefix + the active
+// lanes below mine].  period_k does not decrease with k (the lags differ by >= 2, the shifts by <= 2), so equal bins are RUNS of k: the first
+// trough of a run sums it in ascending k and stores the bin: no atomics, no read-modify-write between threads.  One lane sums pv.
+// LDS beyond pitch_cmnd_frame's: (2 kmax + n_thr + n_bins + 6) float64 + (3 kmax + ceil(kmax / 64) (n_thr + 1) + 8) int32: 9.2 KiB at the
+// defaults (kmax 153, n_thr 100, 385 bins), 46 KiB at the limits.  Nothing depends on the batch, the grid or the padding behind a row.
+struct PyinObserveParams {
+    const float* x; const int32_t* len; double* obs; double* pv;
+    int L, F, W, H, tau_min, tau_max, n_bins, n_thr, kmax, off_extra;
+    double sr, fmin, bpo, lambda, c0, ntp;
+    double w[128];                      // w_t at t - 1
+    double cw[129];                     // cw[t] = w_1 + ... + w_t, one ascending chain; cw[0] = 0
+};
+
+__global__ __launch_bounds__(256) void pyin_observe_kernel(const PyinObserveParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t o = (size_t)b * p.F + f;
+    double* orow = p.obs + o * (size_t)p.n_bins;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;                                  // a bad row is a row of zeros
+    const int nf = (int)(((long long)len + p.H - 1) / p.H);
+    if (f >= nf) {                                                      // (uniform over the workgroup)
+        for (int i = tid; i < p.n_bins; i += 256) orow[i] = 0.0;
+        if (tid == 0) p.pv[o] = 0.0;
+        return;
+    }
+    const double* cm = pitch_cmnd_frame(smem, p.x + (size_t)b * p.L, len, f, p.W, p.H, p.tau_max, tid);
+    const int kmax = p.kmax, n_thr = p.n_thr, n_bins = p.n_bins, ldc = n_thr + 1;
+    double* E = (double*)((unsigned char*)smem + p.off_extra);          // [kmax + 1]
+    double* P = E + kmax + 1;                                           // [kmax]
+    double* G = P + kmax;                                               // [n_thr + 1]
+    double* ob = G + ldc;                                               // [n_bins]
+    double* rv = ob + n_bins;                                           // [4]
+    int* tl = (int*)(rv + 4);                                           // [kmax] trough lags
+    int* act = tl + kmax;                                               // [kmax] activation indices
+    int* bn = act + kmax;                                               // [kmax] bins
+    int* wt = bn + kmax;                                                // [4] troughs found per wave
+    int* ri = wt + 4;                                                   // [4]
+    int* cnt = ri + 4;                                                  // [ceil(kmax / 64)][n_thr + 1]
+    // 1. the troughs, in ascending lag: thread tid looks at a contiguous piece of the range, a scan of the counts places them
+    const int m = p.tau_max - p.tau_min + 1, seg = (m + 255) >> 8;
+    const int ta = p.tau_min + tid * seg, tb = min(ta + seg, p.tau_max + 1);
+    int found = 0;
+    for (int tau = ta; tau < tb; ++tau) {
+        const double v = cm[tau - 1], l = tau > 1 ? cm[tau - 2] : 1.0;
+        found += (v < l && v <= cm[tau]) ? 1 : 0;
+    }
+    int inc = found;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) { const int u = __shfl_up(inc, s); if (lane >= s) inc += u; }
+    if (lane == 63) wt[wave] = inc;
+    for (int i = tid; i < n_bins; i += 256) ob[i] = 0.0;
+    __syncthreads();
+    int k0 = inc - found;
+    for (int q = 0; q < wave; ++q) k0 += wt[q];
+    const int K = min(wt[0] + wt[1] + wt[2] + wt[3], kmax);
+    for (int tau = ta; tau < tb; ++tau) {
+        const double v = cm[tau - 1], l = tau > 1 ? cm[tau - 2] : 1.0;
+        if (v < l && v <= cm[tau]) { if (k0 < kmax) tl[k0] = tau; ++k0; }
+    }
+    for (int i = tid; i <= K; i += 256) E[i] = exp(-p.lambda * (double)i);
+    if (K == 0) {                                                       // (uniform) a silent frame, or one without a trough
+        for (int i = tid; i < n_bins; i += 256) orow[i] = 0.0;
+        if (tid == 0) p.pv[o] = 0.0;
+        return;
+    }
+    __syncthreads();
+    // 2. per trough: activation index, period, bin; the trough of least d'
+    const double nd = (double)n_thr;
+    double bv = 1.0 / 0.0;
+    int bk = 0x7fffffff;
+    for (int k = tid; k < K; k += 256) {
+        const int tau = tl[k];
+        const double a = tau > 1 ? cm[tau - 2] : 1.0, bq = cm[tau - 1], c = cm[tau];
+        int at = n_thr + 1;
+        if (bq < 1.0) {
+            at = min(max((int)(bq * nd) + 1, 1), n_thr);
+            while (at > 1 && bq < (double)(at - 1) / nd) --at;
+            while (at <= n_thr && !(bq < (double)at / nd)) ++at;
+        }
+        act[k] = at;
+        const double den = a - 2.0 * bq + c;
+        double shift = 0.0;
+        if (den > 0.0) {
+            shift = 0.5 * (a - c) / den;
+            if (!(fabs(shift) <= 1.0)) shift = 0.0;
+        }
+        const double q = rint(p.bpo * log2(p.sr / (((double)tau + shift) * p.fmin)));
+        bn[k] = (int)fmin(fmax(q, 0.0), (double)(n_bins - 1));
+        if (bq < bv) { bv = bq; bk = k; }                               // (ascending k: the lowest lag of the least)
+    }
+#pragma unroll
+    for (int sft = 32; sft > 0; sft >>= 1) {
+        const double ov = __shfl_down(bv, sft);
+        const int ok = __shfl_down(bk, sft);
+        if (ov < bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
+    }
+    if (lane == 0) { rv[wave] = bv; ri[wave] = bk; }
+    // 3. first sweep: the active troughs of each block at each threshold
+    const int nblk = (K + 63) >> 6;
+    for (int kb = wave; kb < nblk; kb += 4) {                           // (uniform over the wave; trough 64 kb + lane is this thread's own)
+        const int k = 64 * kb + lane, at = k < K ? act[k] : n_thr + 1;
+        for (int t = 1; t <= n_thr; ++t) {
+            const unsigned long long bal = __ballot(at <= t);
+            if (lane == 0) cnt[kb * ldc + t] = __popcll(bal);
+        }
+    }
+    __syncthreads();
+    int g = ri[0];
+    {
+        double gv = rv[0];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) if (rv[q] < gv || (rv[q] == gv && ri[q] < g)) { gv = rv[q]; g = ri[q]; }
+    }
+    for (int t = 1 + tid; t <= n_thr; t += 256) {
+        int run = 0;
+        for (int kb = 0; kb < nblk; ++kb) { const int c = cnt[kb * ldc + t]; cnt[kb * ldc + t] = run; run += c; }
+        G[t] = run > 0 ? p.w[t - 1] * p.c0 / (1.0 - E[run]) : 0.0;
+    }
+    __syncthreads();
+    // 4. second sweep: P_k
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int kb = wave; kb < nblk; kb += 4) {
+        const int k = 64 * kb + lane, at = k < K ? act[k] : n_thr + 1;
+        double acc = 0.0;
+        for (int t = 1; t <= n_thr; ++t) {
+            const unsigned long long bal = __ballot(at <= t);
+            if (at <= t) acc += G[t] * E[cnt[kb * ldc + t] + __popcll(bal & below)];
+        }
+        if (k == g) acc += p.ntp * p.cw[at - 1];
+        if (k < K) P[k] = acc;
+    }
+    __syncthreads();
+    // 5. runs of equal bins into obs, then pv
+    for (int k = tid; k < K; k += 256) {
+        const int bin = bn[k];
+        if (k > 0 && bn[k - 1] == bin) continue;
+        double s = 0.0;
+        for (int q = k; q < K && bn[q] == bin; ++q) if (P[q] > 0.0) s += P[q];
+        ob[bin] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int i = 0; i < n_bins; ++i) s += ob[i];
+        p.pv[o] = fmin(s, 1.0);
+    }
+    for (int i = tid; i < n_bins; i += 256) orow[i] = ob[i];
+}
+
+// ---------------------------------------------------------------------------
+// Probabilistic YIN, the decoding (ev_pyin_decode): Viterbi over the 2 n_bins states s = v n_bins + i (v = 0 voiced, 1 unvoiced) of one
+// row, one workgroup per row, sequential in time like dtw_kernel.  Thread t owns the states t and t + blockDim.x.  Per frame and state:
+//   l      = log(e + tiny), e = obs[i] (voiced) or (1 - pv) / n_bins (unvoiced)
+//   delta  = max over v' in {0, 1}, j in [i - R, i + R] within [0, n_bins), in ascending s' = v' n_bins + j, a later one replacing an
+//            earlier one only when STRICTLY greater, of dz[s'] + T[|i - j|], plus l; dz[s'] = delta_prev[s'] - log Z_j is what LDS holds,
+//            T = t_stay (v' = v) or t_switch, log_tri[d] + log_stay / log_switch, formed on the host
+// so the recursion is one float64 add and one compare per candidate: 2 (2 R + 1) of them per state; both T tables sit in LDS (128 float64).  dz is double-buffered: frame t reads
+// buffer (t - 1) & 1 and writes t & 1: ONE barrier per frame.  The back-pointer byte v' (2 R + 1) + (j - i + R) goes to the caller's d_back;
+// after the last frame the lowest state of greatest delta is found by a reduction and lane 0 walks the bytes back (F dependent loads).
+// log Z_j reaches the kernel in 128 doubles: all of it for n_bins <= 128; else its first 64, its last 64 and between them the constant
+// they both end on (R <= 63: Z_j is constant for R <= j <= n_bins - 1 - R; the host checks that the caller's table is).
+struct PyinDecodeParams {
+    const double* obs; const double* pv; const int32_t* len; unsigned char* back; int32_t* state; double* loglik;
+    int L, F, H, n_bins, R;
+    double init, tiny;                  // -log(2 n_bins); the smallest normal double
+    double t_stay[64], t_switch[64];
+    double zc[128];
+};
+
+__global__ __launch_bounds__(1024) void pyin_decode_kernel(const PyinDecodeParams p) {
+    extern __shared__ __attribute__((aligned(16))) double pyin_lds[];
+    const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const int nb = p.n_bins, S = 2 * nb, R = p.R, F = p.F;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;
+    const int nf = (int)(((long long)len + p.H - 1) / p.H);
+    int32_t* st = p.state + (size_t)b * F;
+    if (nf == 0) {                                                      // a bad row (uniform): no path, log-likelihood 0
+        for (int t = tid; t < F; t += NT) st[t] = -1;
+        if (tid == 0) p.loglik[b] = 0.0;
+        return;
+    }
+    double* dz = pyin_lds;                                              // [2][S]
+    double* rv = pyin_lds + 2 * (size_t)S;                              // [16]
+    double* tT = rv + 16;                                               // [2][64]: t_stay, t_switch (a broadcast LDS read per candidate)
+    int* ri = (int*)(tT + 128);                                         // [16]
+    for (int d = tid; d <= R; d += NT) { tT[d] = p.t_stay[d]; tT[64 + d] = p.t_switch[d]; }   // (read from frame 1 on: behind frame 0's barrier)
+    const double* ob = p.obs + (size_t)b * F * nb;
+    const double* pvr = p.pv + (size_t)b * F;
+    unsigned char* back = p.back + (size_t)b * F * S;
+    int si[2], sv[2];
+    bool have[2];
+    double lz[2], delta[2], e[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int s = tid + u * NT;
+        have[u] = s < S;
+        sv[u] = (have[u] && s >= nb) ? 1 : 0;
+        si[u] = have[u] ? s - sv[u] * nb : 0;
+        const int j = si[u];
+        lz[u] = nb <= 128 ? p.zc[j] : (j < 64 ? p.zc[j] : (j >= nb - 64 ? p.zc[j - (nb - 128)] : p.zc[64]));
+        delta[u] = 0.0;
+        e[u] = !have[u] ? 0.0 : (sv[u] ? (1.0 - pvr[0]) / (double)nb : ob[si[u]]);
+    }
+    for (int t = 0; t < nf; ++t) {
+        double en[2] = {0.0, 0.0};
+        if (t + 1 < nf) {                                               // the next frame's emissions travel while this one is decided
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                if (have[u]) en[u] = sv[u] ? (1.0 - pvr[t + 1]) / (double)nb : ob[(size_t)(t + 1) * nb + si[u]];
+        }
+        const double* prev = dz + (size_t)((t - 1) & 1) * S;
+        double* cur = dz + (size_t)(t & 1) * S;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (!have[u]) continue;
+            const double l = log(e[u] + p.tiny);
+            if (t == 0) delta[u] = p.init + l;
+            else {
+                const int i = si[u];
+                double best = -1.0 / 0.0;
+                int arg = 0;
+                for (int vp = 0; vp < 2; ++vp) {
+                    const double* pr = prev + vp * nb;
+                    const double* T = tT + (vp == sv[u] ? 0 : 64);
+                    const int base = vp * (2 * R + 1) + R;
+#pragma unroll 4
+                    for (int d = -R; d <= R; ++d) {                     // ascending j = i + d; a j outside the bins is a candidate of -inf
+                        const int j = i + d, ad = d < 0 ? -d : d;
+                        const double c = (j >= 0 && j < nb) ? pr[min(max(j, 0), nb - 1)] + T[ad] : -1.0 / 0.0;
+                        if (c > best) { best = c; arg = base + d; }
+                    }
+                }
+                delta[u] = best + l;
+                back[(size_t)t * S + tid + u * NT] = (unsigned char)arg;
+            }
+            cur[tid + u * NT] = delta[u] - lz[u];
+        }
+        e[0] = en[0]; e[1] = en[1];
+        __syncthreads();
+    }
+    // the end state: the lowest s of greatest delta
+    double bv = -1.0 / 0.0;
+    int bs = 0x7fffffff;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) if (have[u] && delta[u] > bv) { bv = delta[u]; bs = tid + u * NT; }
+#pragma unroll
+    for (int sft = 32; sft > 0; sft >>= 1) {
+        const double ov = __shfl_down(bv, sft);
+        const int os = __shfl_down(bs, sft);
+        if (ov > bv || (ov == bv && os < bs)) { bv = ov; bs = os; }
+    }
+    if (lane == 0) { rv[wave] = bv; ri[wave] = bs; }
+    __syncthreads();
+    for (int t = nf + tid; t < F; t += NT) st[t] = -1;
+    if (tid != 0) return;
+    const int nw = (NT + 63) >> 6;
+    bv = rv[0]; bs = ri[0];
+    for (int q = 1; q < nw; ++q) if (rv[q] > bv || (rv[q] == bv && ri[q] < bs)) { bv = rv[q]; bs = ri[q]; }
+    p.loglik[b] = bv;
+    int s = bs;
+    for (int t = nf - 1; t >= 0; --t) {
+        st[t] = s;
+        if (t == 0) break;
+        const int code = back[(size_t)t * S + s], vp = min(code / (2 * R + 1), 1), d = code - vp * (2 * R + 1) - R;
+        const int v = s >= nb ? 1 : 0;
+        s = vp * nb + min(max(s - v * nb + d, 0), nb - 1);             // (the clamp keeps a damaged byte inside the row's states)
+    }
 }
 
 // ---------------------------------------------------------------------------

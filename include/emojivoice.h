@@ -37,6 +37,8 @@
  *   ev_pitch_yin       <- no counterpart: the reference never measures pitch; librosa.yin is the model
  *   ev_dtw             <- no counterpart: the reference never compares what it says with what was recorded; MCD-DTW evaluation is the model
  *   ev_loudness        <- no counterpart; ITU-R BS.1770-4 is the model
+ *   ev_pyin_observe    <- no counterpart; librosa.pyin is the model
+ *   ev_pyin_decode     <- no counterpart; librosa.pyin is the model
  *
  * Conventions
  *   - All tensors are fp32.  Pointers named d_* are DEVICE pointers owned by the
@@ -74,7 +76,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_op_groupnorm_mish2, ev_op_conv_groupnorm (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -369,6 +371,60 @@ int ev_pitch_yin(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_l
                  int frame_length /* W */, int hop_length /* H */, int tau_min, int tau_max, float threshold,
                  int32_t *d_lag /* (B, F) or NULL */, float *d_period /* (B, F) or NULL */, float *d_cmnd /* (B, F) or NULL */,
                  void *stream);
+
+/* Probabilistic YIN on the device: Mauch and Dixon's pYIN (ICASSP 2014); librosa.pyin is the model.  Two calls: ev_pyin_observe turns every
+ * frame into a distribution over pitch bins and a voicing probability, ev_pyin_decode picks the contour by a Viterbi pass over
+ * (voiced / unvoiced) x pitch bins.  W, H, F, the framing, d(tau) and d'(tau) for 1 <= tau <= tau_max + 1 are EXACTLY ev_pitch_yin's (the same
+ * device code: same spans, same zeros outside [0, len), same fma order, same S chain); additionally d'(0) := 1.
+ * Observation, per frame:
+ *   troughs     the lags tau in [tau_min, tau_max] with d'(tau) < d'(tau - 1) and d'(tau) <= d'(tau + 1), in ascending lag tau_0 < tau_1 < ...
+ *               d' exists one lag beyond each end of the range, so the ends need no rule of their own (librosa pads the ends of its range
+ *               instead).  A silent frame (d' = 1 at every lag) has none.
+ *   thresholds  theta_t = t / n_thr (float64 division), t = 1 .. n_thr; w (HOST, n_thr float64, read during the call): w[t - 1] = the prior
+ *               mass of (theta_{t-1}, theta_t] (audio.pyin_threshold_prior: Beta(2, 18) over 100 thresholds)
+ *   activity    active(k, t) = d'(tau_k) < theta_t (monotone in t); pos(k, t) = #{m < k : active(m, t)}; N(t) = #{m : active(m, t)}
+ *   P_k         sum over t, ascending, of active(k, t) G_t exp(-boltzmann pos(k, t)), G_t = w_t (1 - exp(-boltzmann)) / (1 - exp(-boltzmann N(t)))
+ *   global min  g = the trough of smallest d', lowest lag on ties: P_g += no_trough_prob * (the sum of w_t over the t with active(g, t) false,
+ *               a prefix of t, in ascending t)
+ *   period_k    tau_k + shift_k, the parabolic shift of ev_pitch_yin (denominator > 0 and |shift| <= 1, else 0), kept in float64
+ *   bin_k       clip(rint(bins_per_octave * log2(sr / (period_k * fmin))), 0, n_bins - 1), halves to even: bin i is fmin 2^(i / bins_per_octave)
+ *   d_obs (B, F, n_bins) float64   obs[bin_k] += P_k over the troughs with P_k > 0, in ascending k; every other bin 0
+ *   d_pv (B, F) float64            min(sum_i obs[i], 1), summed in ascending i: the probability that the frame is voiced
+ *   Frames at or beyond a row's ceil(len / H), and rows with len < 1 or len > L, are zeros in both.  d_len == NULL: every row is L long.
+ * Limits, each violation failing with a message that names it: those of ev_pitch_yin for B, frame_length, hop_length, tau_min and tau_max;
+ *   1 <= n_thr <= 128; 2 <= n_bins <= 1024; bins_per_octave >= 1; sr, fmin > 0; boltzmann > 0; 0 <= no_trough_prob <= 1; finite w >= 0;
+ *   d_obs and d_pv non-NULL.
+ * One kernel launch (pyin_observe_kernel, one workgroup per frame and row) on `stream`; all float64; no atomics; capturable; every buffer is
+ *   the caller's: ev_alloc_count never moves.  A row alone, inside a batch, or as the d_len prefix of a longer padded row, and a second call,
+ *   give the same bits.  Cost: ev_pitch_yin's W (tau_max + 1) fmas per frame plus 2 n_thr ballots per 64 troughs. */
+int ev_pyin_observe(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L,
+                    int frame_length /* W */, int hop_length /* H */, int tau_min, int tau_max, double sr, double fmin,
+                    int bins_per_octave, int n_bins, const double *w /* HOST (n_thr) */, int n_thr, double boltzmann,
+                    double no_trough_prob, double *d_obs /* (B, F, n_bins) */, double *d_pv /* (B, F) */, void *stream);
+
+/* Decoding, per row, over that row's own nf = ceil(len / H) frames of d_obs / d_pv (any float64 arrays of those shapes; F = ceil(L / H)).
+ *   states      s = v n_bins + i, v = 0 voiced, v = 1 unvoiced
+ *   emission    e(0, i) = obs[i], e(1, i) = (1 - pv) / n_bins; l = log(e + tiny), tiny the smallest normal double
+ *   transition  (v', j) -> (v, i) exists for |i - j| <= R and has log a = T[|i - j|] - log_Z[j], T[d] = log_tri[d] + (v' == v ? log_stay :
+ *               log_switch), formed first.  HOST float64 tables, read during the call (audio.pyin_transition): log_tri[d] = log(R + 1 - d)
+ *               for d <= R; log_Z[j] = log of the sum of R + 1 - |i - j| over the i inside [0, n_bins); log_stay = log(1 - switch_prob),
+ *               log_switch = log(switch_prob)
+ *   recursion   delta_0(s) = -log(2 n_bins) + l_0(s); delta_t(s) = max_{s'} [(delta_{t-1}(s') - log_Z[j]) + T[|i - j|]] + l_t(s): float64 adds
+ *               and compares only, plus one log per emission.  Predecessors are visited in ascending s' and a later one replaces an earlier one
+ *               only when STRICTLY greater; the end state is the lowest s of greatest delta
+ *   d_back (B, F, 2 n_bins) uint8   scratch of the caller's: the back-pointer byte v' (2 R + 1) + (j - i + R) of frames 1 .. nf - 1
+ *   d_state (B, F) int32            the best path's state per frame; -1 at and beyond nf (a row with len < 1 or len > L: all -1)
+ *   d_loglik (B) float64            delta of the end state (0 for such a row)
+ * Limits, each violation failing with a message that names it: 1 <= B <= 65535; hop_length a multiple of 64 and at most 4096;
+ *   2 <= n_bins <= 1024; 0 <= R <= 63; log_stay and log_switch finite and negative (0 < switch_prob < 1); finite tables; log_Z constant over
+ *   R <= j <= n_bins - 1 - R (as its definition makes it); every pointer but d_len non-NULL.
+ * One kernel launch (pyin_decode_kernel) on `stream`, one workgroup per row, delta double-buffered in LDS, one barrier per frame; one lane walks
+ *   the back-pointers.  Latency-bound like ev_dtw: 2 (2 R + 1) add-compares per state and frame.  No atomics, no scratch of the handle
+ *   (ev_alloc_count never moves), capturable; a row alone, inside a batch, or as a prefix, and a second call, give the same bits. */
+int ev_pyin_decode(ev_handle *h, const double *d_obs /* (B, F, n_bins) */, const double *d_pv /* (B, F) */,
+                   const int32_t *d_len /* (B) or NULL */, int B, int L, int hop_length /* H */, int n_bins, int R,
+                   const double *log_tri /* HOST (R + 1) */, const double *log_Z /* HOST (n_bins) */, double log_stay, double log_switch,
+                   uint8_t *d_back /* (B, F, 2 n_bins) */, int32_t *d_state /* (B, F) */, double *d_loglik /* (B) */, void *stream);
 
 /* Dynamic time warping on the device between two feature sequences per row: x (B, C, Tx) against y (B, C, Ty), tx = d_xlen[b] and
  * ty = d_ylen[b] frames of them (a NULL length pointer: the padded size).  The step pattern is the plain one (diagonal, up, left; weight 1).

@@ -32,6 +32,7 @@ EXPORTS = [
     "ev_pitch_yin", "ev_dtw",
     "ev_loudness",
     "ev_pyin_observe", "ev_pyin_decode",
+    "ev_op_attention2", "ev_op_attn_out2",
 ]
 
 
@@ -176,6 +177,8 @@ def load_library() -> C.CDLL:
     lib.ev_op_split_pieces.argtypes = [vp, vp, i32, vp, vp]
     lib.ev_op_attention.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_op_attn_out.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.ev_op_attention2.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, C.POINTER(C.c_int), vp]
+    lib.ev_op_attn_out2.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, f32, f32, f32, vp, C.POINTER(C.c_int), vp]
     lib.ev_op_ln_mlp.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     for n in EXPORTS:
         getattr(lib, n)  # raises AttributeError if a declared symbol is not exported
@@ -896,3 +899,37 @@ class Engine:
         self._check(self.lib.ev_op_attn_out(self.h, qkv.data_ptr(), lengths.data_ptr(), B, T, wh.ctypes.data_as(C.c_void_p), bh.ctypes.data_as(C.c_void_p),
                                             hid.data_ptr(), _stream_ptr()), "ev_op_attn_out")
         return hid
+
+    def op_attention2(self, qkv, lengths, S, P, T, heads=2, scratch=True, out=None):
+        """launch_attn in a padded geometry: qkv (B*S, 3*heads*64), frame t of utterance b in row b*S + P + t.  scratch: hand it the split-key
+        scratch (the engine's rule then picks the build).  out (B*S, heads*64) is written in place where given (its pad rows stay).
+        Returns (out, {"split": bool, "KS": int})."""
+        qkv = self._f32(qkv)
+        B = qkv.shape[0] // S
+        if qkv.shape != (B * S, 3 * heads * 64):
+            raise ValueError("qkv: (B*S, 3*heads*64)")
+        lengths = lengths.to(qkv.device, torch.int32).contiguous()
+        if out is None:
+            out = torch.zeros((B * S, heads * 64), dtype=torch.float32, device=qkv.device)
+        if out.shape != (B * S, heads * 64) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out: contiguous fp32 (B*S, heads*64)")
+        ran = (C.c_int * 2)()
+        self._check(self.lib.ev_op_attention2(self.h, qkv.data_ptr(), lengths.data_ptr(), B, S, P, T, heads, 0 if scratch else 1, out.data_ptr(),
+                                              ran, _stream_ptr()), "ev_op_attention2")
+        return out, {"split": bool(ran[0]), "KS": int(ran[1])}
+
+    def op_attn_out2(self, qkv, lengths, w_out, b_out, hid, S, P, T, scales=None):
+        """launch_attn_out in a padded geometry, IN PLACE on hid (B*S, 256); qkv (B*S, 384).  scales: (sq, sk, sv) powers of two for the fp16
+        form, None = from the data's maxima.  Returns (hid, {"h16": bool, "ntail": int, "nq": int})."""
+        qkv = self._f32(qkv)
+        B = qkv.shape[0] // S
+        if qkv.shape != (B * S, 384) or hid.shape != (B * S, 256) or hid.dtype != torch.float32 or not hid.is_contiguous():
+            raise ValueError("qkv: (B*S, 384); hid: contiguous fp32 (B*S, 256)")
+        lengths = lengths.to(qkv.device, torch.int32).contiguous()
+        wh = np.ascontiguousarray(w_out.detach().cpu().float().numpy())
+        bh = np.ascontiguousarray(b_out.detach().cpu().float().numpy())
+        sq, sk, sv = (0.0, 0.0, 0.0) if scales is None else (float(x) for x in scales)
+        ran = (C.c_int * 3)()
+        self._check(self.lib.ev_op_attn_out2(self.h, qkv.data_ptr(), lengths.data_ptr(), B, S, P, T, wh.ctypes.data_as(C.c_void_p),
+                                             bh.ctypes.data_as(C.c_void_p), sq, sk, sv, hid.data_ptr(), ran, _stream_ptr()), "ev_op_attn_out2")
+        return hid, {"h16": bool(ran[0]), "ntail": int(ran[1]), "nq": int(ran[2])}

@@ -1194,7 +1194,9 @@ int launch_mlp(ev_handle* h, int mode, const float* X, const float* ln_g, const 
 // `part`: scratch for the split-key small-launch build, 4 * rows * (H*64 + 2*H) floats (null: always the one-launch kernel)
 constexpr int EV_ATTN_MAXPARTS = 16;   // split-key attention (small launches): parts a query tile's key tiles may be spread over,
 constexpr int EV_ATTN_MAXROWS = 8192;  // and the most rows such a launch has (<= 64 workgroups of 128 queries, plus padding)
-int launch_attn(ev_handle* h, const float* QKV, int ld, float* O, int ldo, const float* rowmask, const Geom& g, int H, float* part = nullptr) {
+// `ran` (optional, 2 ints): {0 = attention_kernel, 1 = attention_part_kernel + attention_merge_kernel; KS of the latter, else 0}
+int launch_attn(ev_handle* h, const float* QKV, int ld, float* O, int ldo, const float* rowmask, const Geom& g, int H, float* part = nullptr,
+                int* ran = nullptr) {
     AttnParams p;
     p.QKV = QKV; p.ld = ld; p.O = O; p.ldo = ldo; p.rowmask = rowmask; p.S = g.S; p.P = g.P; p.T = g.T; p.H = H; p.scale = 0.125f;
     const int nwg = ((g.T + 127) / 128) * H * (g.nrows / g.S), nkt = (g.T + 31) / 32;
@@ -1206,8 +1208,10 @@ int launch_attn(ev_handle* h, const float* QKV, int ld, float* O, int ldo, const
         hipLaunchKernelGGL(attention_part_kernel, dim3((g.T + 127) / 128, H, (g.nrows / g.S) * pp.KS), dim3(256), 0, h->stream, pp);
         const long tot = (long)g.nrows * H * 16;
         hipLaunchKernelGGL(attention_merge_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, pp);
+        if (ran) { ran[0] = 1; ran[1] = pp.KS; }
     } else {
         hipLaunchKernelGGL(attention_kernel, dim3((g.T + 127) / 128, H, g.nrows / g.S), dim3(256), 0, h->stream, p);
+        if (ran) { ran[0] = 0; ran[1] = 0; }
     }
     HIPCHK(h, hipGetLastError());
     return 0;
@@ -1263,8 +1267,9 @@ inline bool attn_out_ok(const ev_handle* h, const ConvLayer& Lo, const Geom& g, 
            g.S >= 4 && h->ncu > 0 && wgs >= h->ncu / 2;
 }
 // qkv_scale non-null: QKV holds fp16 piece pairs times these powers of two -> attn_out_h16_kernel
+// `ran` (optional, 3 ints): {0 = attn_out_kernel, 1 = attn_out_h16_kernel; ntail (> 0: attn_tail_path took the last tile); nq}
 int launch_attn_out(ev_handle* h, const float* QKV, int ld, const ConvLayer& Lo, float* Hid, int ldh, const float* rowmask, const Geom& g, int H,
-                    const float* qkv_scale = nullptr) {
+                    const float* qkv_scale = nullptr, int* ran = nullptr) {
     AttnOutParams p;
     memset(&p, 0, sizeof p);
     const bool h16 = qkv_scale != nullptr;
@@ -1290,6 +1295,7 @@ int launch_attn_out(ev_handle* h, const float* QKV, int ld, const ConvLayer& Lo,
     if (h16) launch<attn_out_h16_kernel>(h->device, grid, dim3(256), smem, h->stream, p);
     else launch<attn_out_kernel>(h->device, grid, dim3(256), smem, h->stream, p);
     HIPCHK(h, hipGetLastError());
+    if (ran) { ran[0] = h16 ? 1 : 0; ran[1] = p.ntail; ran[2] = p.nq; }
     const double fl = (double)B * ((double)H * 4.0 * g.T * (double)g.T * 64.0 + 2.0 * Lo.macs_per_row * g.T);
     return h->prof ? prof_end(h, {4, 128, 256, 1, g.nrows, h16 ? 31 : 30, 1, fl, h16}) : 0;   // (31: attn_out_h16_kernel, counted with the fp16 builds)
 }
@@ -3692,65 +3698,120 @@ int ev_op_ln_mlp(ev_handle* h, const float* d_x, const float* d_ln_g, const floa
     return rc;
 }
 
-int ev_op_attention(ev_handle* h, const float* d_qkv, const int32_t* d_lengths, int B, int T, int heads, float* d_out, void* stream) {
+// attention_kernel, or attention_part_kernel + attention_merge_kernel, in a padded geometry: utterance b's frame t is row b * S + P + t of
+// d_qkv (B*S, 3*heads*64) and d_out (B*S, heads*64), S >= P + T.  Without no_scratch the call hands launch_attn the split-key scratch sized as
+// plan_est sizes EstBufs::ATTP, and launch_attn's own rule picks the build; ran (2 ints) = {0 one launch | 1 split-key, KS}.
+static int op_attention_impl(const char* who, ev_handle* h, const float* d_qkv, const int32_t* d_lengths, int B, int S, int P, int T, int heads,
+                             int no_scratch, float* d_out, int* ran, void* stream) {
     if (!h) return 1;
     HIPCHK(h, hipSetDevice(h->device));
     h->stream = (hipStream_t)stream;
-    Geom g{B * T, T, 0, T};
-    float* rm = nullptr;
-    HIPCHK(h, hipMalloc((void**)&rm, (size_t)g.nrows * 4));
-    hipLaunchKernelGGL(rowmask_kernel, dim3((g.nrows + 255) / 256), dim3(256), 0, h->stream, rm, d_lengths, g.nrows, g.S, g.P, g.T, 1);
-    int rc = launch_attn(h, d_qkv, 3 * heads * 64, d_out, heads * 64, rm, g, heads);
-    hipStreamSynchronize(h->stream);
-    hipFree(rm);
+    if (B <= 0 || T <= 0 || P < 0 || S < P + T || heads <= 0 || (long)B * S > 0x7fffffffL / (3 * heads * 64) || !d_qkv || !d_lengths || !d_out)
+        return fail(h, "%s: bad arguments", who);
+    Geom g{B * S, S, P, T};
+    float *rm = nullptr, *part = nullptr;
+    int rc = 0, rn[2] = {0, 0};
+    do {
+        if (hipMalloc((void**)&rm, (size_t)g.nrows * 4) != hipSuccess) { rc = fail(h, "%s: out of memory", who); break; }
+        if (!no_scratch) {
+            // (launch_attn indexes the scratch by the launch's rows: a launch beyond EV_ATTN_MAXROWS never splits and never touches it)
+            const size_t rows = std::min<size_t>((size_t)g.nrows, EV_ATTN_MAXROWS);
+            if (hipMalloc((void**)&part, rows * EV_ATTN_MAXPARTS * (heads * 64 + 2 * heads) * 4) != hipSuccess) { rc = fail(h, "%s: out of memory", who); break; }
+        }
+        hipLaunchKernelGGL(rowmask_kernel, dim3((g.nrows + 255) / 256), dim3(256), 0, h->stream, rm, d_lengths, g.nrows, g.S, g.P, g.T, 1);
+        rc = launch_attn(h, d_qkv, 3 * heads * 64, d_out, heads * 64, rm, g, heads, part, rn);
+        if (rc) break;
+        if (hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, "sync failed: %s", hipGetErrorString(hipGetLastError()));
+    } while (0);
+    if (rc) hipStreamSynchronize(h->stream);              // (nothing of this call may still read what is freed below)
+    if (rm) hipFree(rm);
+    if (part) hipFree(part);
+    if (ran) { ran[0] = rn[0]; ran[1] = rn[1]; }
     return rc;
 }
 
-// attn_out_kernel: d_hid (B*T, 256) <- d_hid + Wout . attention(d_qkv) + bout; w_out (256, 128), b_out (256) are HOST pointers
-int ev_op_attn_out(ev_handle* h, const float* d_qkv, const int32_t* d_lengths, int B, int T, const float* w_out, const float* b_out, float* d_hid, void* stream) {
+int ev_op_attention2(ev_handle* h, const float* d_qkv, const int32_t* d_lengths, int B, int S, int P, int T, int heads, int no_scratch,
+                     float* d_out, int* ran, void* stream) {
+    if (h && heads != 2) return fail(h, "ev_op_attention2: heads = 2 only (the U-Net launches no other; ev_op_attention takes any)");
+    return op_attention_impl("ev_op_attention2", h, d_qkv, d_lengths, B, S, P, T, heads, no_scratch, d_out, ran, stream);
+}
+
+int ev_op_attention(ev_handle* h, const float* d_qkv, const int32_t* d_lengths, int B, int T, int heads, float* d_out, void* stream) {
+    return op_attention_impl("ev_op_attention", h, d_qkv, d_lengths, B, T, 0, T, heads, 1, d_out, nullptr, stream);
+}
+
+// attn_out_kernel / attn_out_h16_kernel in a padded geometry: d_hid (B*S, 256) <- d_hid + Wout . attention(d_qkv) + bout on the rows b * S + P + t,
+// t < T; w_out (256, 128), b_out (256) are HOST pointers.  Under arithmetic setting 16 (with the fp16 attention on) a copy of d_qkv is packed as
+// ln_qkv_h16_kernel leaves it, with the powers of two sq, sk, sv — all three 0: derived from the data's own maxima, where the loader uses its
+// weight bound (qkv_pack_scales).  ran (3 ints) = {0 fp32 | 1 fp16 pipe, ntail, nq}.
+static int op_attn_out_impl(const char* who, ev_handle* h, const float* d_qkv, const int32_t* d_lengths, int B, int S, int P, int T, const float* w_out,
+                            const float* b_out, float sq, float sk, float sv, float* d_hid, int* ran, void* stream) {
     if (!h) return 1;
     HIPCHK(h, hipSetDevice(h->device));
     h->stream = (hipStream_t)stream;
-    if (B <= 0 || T <= 0 || !d_qkv || !w_out || !b_out || !d_hid) return fail(h, "ev_op_attn_out: bad arguments");
+    const bool given = sq != 0.f || sk != 0.f || sv != 0.f;
+    if (B <= 0 || T <= 0 || P < 0 || S < P + T || (long)B * S > 0x7fffffffL / 384 || !d_qkv || !d_lengths || !w_out || !b_out || !d_hid)
+        return fail(h, "%s: bad arguments", who);
+    float sc[3] = {sq, sk, sv};
+    if (given) {
+        float ma, mb; int e;
+        if (sq == 0.f || sk == 0.f || sv == 0.f) return fail(h, "%s: sq, sk, sv must be all zero (derive them from the data) or all set", who);
+        if (!(sv > 0.f) || std::frexp(sv, &e) != 0.5f || !attn_mask_split(sc, &ma, &mb)) return fail(h, "%s: sq, sk, sv must be powers of two the fp16 form can hold", who);
+    }
     size_t owned0 = h->owned.size();
     ConvLayer Lo;
     HostTensor tw, tb;
     tw.p = w_out; tw.ndim = 2; tw.shape[0] = 256; tw.shape[1] = 128;
     tb.p = b_out; tb.ndim = 1; tb.shape[0] = 256;
     int rc = pack_linear_stack(h, Lo, {&tw}, {&tb});
-    Geom g{B * T, T, 0, T};
+    Geom g{B * S, S, P, T};
     float* rm = nullptr;
-    if (!rc && hipMalloc((void**)&rm, (size_t)g.nrows * 4) != hipSuccess) rc = fail(h, "ev_op_attn_out: out of memory");
+    if (!rc && hipMalloc((void**)&rm, (size_t)g.nrows * 4) != hipSuccess) rc = fail(h, "%s: out of memory", who);
     float* packed = nullptr;
-    float sc[3] = {0.f, 0.f, 0.f};
+    int rn[3] = {0, 0, 0};
     if (!rc && h->split_terms == 16 && h->attn_h16 && Lo.Wh) {
         // arithmetic setting 16: the op runs what the model runs — q / k / v as fp16 piece pairs (the model's ln_qkv_h16_kernel writes them so;
-        // here a copy is packed, with scales from the data's own maxima where the loader uses its weight bound) and attn_out_h16_kernel
-        std::vector<float> hq((size_t)g.nrows * 384);
-        if (hipMemcpy(hq.data(), d_qkv, hq.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(h, "ev_op_attn_out: copy failed");
-        float mx[3] = {0.f, 0.f, 0.f};
-        for (size_t i = 0; i < hq.size(); ++i) { const float a = std::fabs(hq[i]); if (std::isfinite(a)) { float& m = mx[(i % 384) / 128]; m = std::max(m, a); } }
-        for (int i = 0; i < 3; ++i) sc[i] = mx[i] > 0.f ? (float)std::ldexp(1.0, std::min(40, std::max(-40, (int)std::floor(std::log2(32768.0 / mx[i]))))) : 1.f;
-        float ma, mb;
-        const bool fits = attn_mask_split(sc, &ma, &mb);                   // (else: the fp32 form, as the model would)
-        if (!rc && fits && hipMalloc((void**)&packed, hq.size() * 4) != hipSuccess) rc = fail(h, "ev_op_attn_out: out of memory");
+        // here a copy is packed) and attn_out_h16_kernel
+        const size_t nw = (size_t)g.nrows * 384;
+        bool fits = true;
+        if (!given) {
+            std::vector<float> hq(nw);
+            if (hipMemcpy(hq.data(), d_qkv, nw * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(h, "%s: copy failed", who);
+            float mx[3] = {0.f, 0.f, 0.f};
+            for (size_t i = 0; i < nw; ++i) { const float a = std::fabs(hq[i]); if (std::isfinite(a)) { float& m = mx[(i % 384) / 128]; m = std::max(m, a); } }
+            for (int i = 0; i < 3; ++i) sc[i] = mx[i] > 0.f ? (float)std::ldexp(1.0, std::min(40, std::max(-40, (int)std::floor(std::log2(32768.0 / mx[i]))))) : 1.f;
+            float ma, mb;
+            fits = attn_mask_split(sc, &ma, &mb);                          // (else: the fp32 form, as the model would)
+        }
+        if (!rc && fits && hipMalloc((void**)&packed, nw * 4) != hipSuccess) rc = fail(h, "%s: out of memory", who);
         if (!rc && fits) {
-            const size_t npairs = hq.size() / 2;
+            const size_t npairs = nw / 2;
             hipLaunchKernelGGL(qkv_pack_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, h->stream, d_qkv, packed, npairs, sc[0], sc[1], sc[2]);
         }
     }
     if (!rc) {
         hipLaunchKernelGGL(rowmask_kernel, dim3((g.nrows + 255) / 256), dim3(256), 0, h->stream, rm, d_lengths, g.nrows, g.S, g.P, g.T, 1);
-        rc = launch_attn_out(h, packed ? packed : d_qkv, 384, Lo, d_hid, 256, rm, g, 2, packed ? sc : nullptr);
+        rc = launch_attn_out(h, packed ? packed : d_qkv, 384, Lo, d_hid, 256, rm, g, 2, packed ? sc : nullptr, rn);
     }
-    if (hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, "sync failed");
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(h, "sync failed: %s", hipGetErrorString(hipGetLastError()));
     if (rm) hipFree(rm);
     if (packed) hipFree(packed);
     while (h->owned.size() > owned0) {
         if (h->owned.back() == (void*)h->zeros) break;
         hipFree(h->owned.back()); h->owned.pop_back();
     }
+    if (ran) { ran[0] = rn[0]; ran[1] = rn[1]; ran[2] = rn[2]; }
     return rc;
+}
+
+int ev_op_attn_out2(ev_handle* h, const float* d_qkv, const int32_t* d_lengths, int B, int S, int P, int T, const float* w_out, const float* b_out,
+                    float sq, float sk, float sv, float* d_hid, int* ran, void* stream) {
+    return op_attn_out_impl("ev_op_attn_out2", h, d_qkv, d_lengths, B, S, P, T, w_out, b_out, sq, sk, sv, d_hid, ran, stream);
+}
+
+// attn_out_kernel: d_hid (B*T, 256) <- d_hid + Wout . attention(d_qkv) + bout; w_out (256, 128), b_out (256) are HOST pointers
+int ev_op_attn_out(ev_handle* h, const float* d_qkv, const int32_t* d_lengths, int B, int T, const float* w_out, const float* b_out, float* d_hid, void* stream) {
+    return op_attn_out_impl("ev_op_attn_out", h, d_qkv, d_lengths, B, T, 0, T, w_out, b_out, 0.f, 0.f, 0.f, d_hid, nullptr, stream);
 }
 
 }  // extern "C"

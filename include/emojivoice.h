@@ -76,7 +76,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2 (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -599,6 +599,23 @@ int ev_op_attention(ev_handle *h, const float *d_qkv /*(B,T,3*heads*64)*/, const
  * d_qkv (B, T, 384) = [q | k | v] x (2 heads x 64); w_out (256, 128) and b_out (256) are HOST pointers. */
 int ev_op_attn_out(ev_handle *h, const float *d_qkv, const int32_t *d_lengths, int B, int T, const float *w_out, const float *b_out,
                    float *d_hid, void *stream);
+
+/* The two attention ops as the estimator launches them (launch_attn / launch_attn_out in ev_engine.hip).
+ * Geometry: utterance b's frame t is row b * S + P + t of every buffer, S >= P + T (the estimator's level 0: S = T + 4, P = 2); rows outside
+ * [P, P + T) are neither read as queries or keys nor written.  d_lengths (B) int32: the additive float mask is 1.0 on keys t < length, 0.0 on
+ * the padded frames, which stay live keys (transformer.py:262-271).
+ * ev_op_attention2: heads = 2 only; d_qkv (B*S, 3*heads*64), d_out (B*S, heads*64).  no_scratch = 0: launch_attn is handed split-key scratch sized as the
+ *   estimator's and picks the build by its own rule (split-key iff few workgroups and >= 4 key tiles); 1: no scratch, always attention_kernel.
+ *   ran (2 ints, may be NULL): {0 = attention_kernel | 1 = attention_part_kernel + attention_merge_kernel, KS = parts per query tile (else 0)}.
+ * ev_op_attn_out2: d_qkv (B*S, 384), d_hid (B*S, 256) in place; w_out (256, 128), b_out (256) HOST.  sq, sk, sv: the powers of two of the fp16
+ *   form (what qkv_pack_scales derives from a weight bound); all three 0 = derive them from the data's maxima, as ev_op_attn_out does (some but not all 0 is refused).  They
+ *   matter only where the fp16 pipe runs (arithmetic setting 16 with ev_dbg_set_attn_h16 on).
+ *   ran (3 ints, may be NULL): {0 = attn_out_kernel | 1 = attn_out_h16_kernel, ntail = queries of a short last tile that attn_tail_path took
+ *   (0: none), nq = 32-query tiles per utterance on the main path}. */
+int ev_op_attention2(ev_handle *h, const float *d_qkv, const int32_t *d_lengths, int B, int S, int P, int T, int heads, int no_scratch,
+                     float *d_out, int *ran, void *stream);
+int ev_op_attn_out2(ev_handle *h, const float *d_qkv, const int32_t *d_lengths, int B, int S, int P, int T, const float *w_out,
+                    const float *b_out, float sq, float sk, float sv, float *d_hid, int *ran, void *stream);
 
 #ifdef __cplusplus
 }

@@ -709,6 +709,375 @@ __device__ __forceinline__ float ev_amax_read(const ConvParams& p, int row_lo, i
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, m)));
 }
 
+// ---------------------------------------------------------------------------
+// What the six implicit-GEMM conv kernels share (conv_gemm_kernel, conv_split_kernel, conv_h16_kernel and their balanced persistent forms
+// conv_gemm_bal_kernel, conv_split_bal_kernel, conv_h16_bal_kernel):
+//   the pipes        EvPipeBf16<TERMS> / EvPipeH16: how an fp32 operand is cut into 16-bit pieces, multiplied, and written to an LDS stage
+//   staging helpers  ev_chunk_off, ev_row_off(s), ev_pro_lrelu4
+//   EvConvCore       wave geometry, accumulators, weight-fragment ring and tap step of the one-tile-per-workgroup split kernels
+//                    (conv_split_kernel, conv_h16_kernel)
+//   hand-over        ev_acc_store / ev_acc_add: an accumulator tile to / from the hand-over area of the balanced grid (SkCtl), in
+//                    conv_gemm_bal_kernel and conv_split_bal_kernel
+// Which kernel takes which piece was decided by the code object: a piece that moved a kernel's spill counts, scratch, LDS or occupancy
+// stayed that kernel's own code (NOTES.md, "One core for the split conv kernels"); the fp32 kernels and the balanced kernels, whose
+// register files are full, keep their own rings and tap loops.  What follows first is the arithmetic of the two split pipes.
+//
+// bf16 (EvPipeBf16<TERMS>).  The fp32 MFMA of gfx950 runs at the vector rate (157 TFLOP/s); v_mfma_f32_32x32x16_bf16 runs sixteen
+// times faster and accumulates in fp32.  Every fp32 value is the EXACT sum of three bf16 values (8 + 8 + 8 significand bits: x0 = the
+// upper half of the word, x1 = the upper half of x - x0, x2 = x - x0 - x1), and a bf16 x bf16 product is exact in the fp32 accumulator, so
+//     a . b  =  sum over pieces  a_p . b_q
+// with the six products of weight p + q <= 2 (a0b0, a0b1, a1b0, a0b2, a1b1, a2b0) leaves out only terms below 2^-24 |a b| — the
+// size of ONE fp32 rounding.  Measured (tools/bf16_split_probe.hip, dot products of length 1408 against fp64): fp32 MFMA max
+// 3.1e-6 / rms 6.9e-7 of the result's scale, six products 3.4e-6 / 5.9e-7, nine products the same, three products 8.9e-5: six it
+// is.  Cost: 6 MFMAs of 32 cycles per 16-deep slab against 8 of 64 — 2.67x the rate of the fp32 pipe (probe: 365 TFLOP/s of
+// fp32-equivalent work in a loop fed from LDS and L2, against 153).
+//   weights:     split once by the loader, fragment order [tap][32-row tile][16-deep slab][piece][lane][8 bf16]
+//                (lane = (row & 31) + 32 * half, element e <-> k = 16 slab + 8 half + e): one 16-byte load per lane and piece
+//   activations: split while they are staged: LDS row = three bf16 planes of the 64-channel chunk (+ 16 bytes: an odd multiple of
+//                16 keeps the 16-byte fragment reads conflict-free); a chunk is four slabs, like the four k-groups of an fp32 chunk
+//   epilogue:    the D layout of the 32 x 32 tile is that of the fp32 instruction: conv_epilogue_lean as is
+//
+// fp16 (EvPipeH16).  An fp16 value carries 11 significand bits, so TWO pieces (x = h0 + h1, h0 = the nearest fp16, h1 = the nearest fp16
+// of the rest) represent an fp32 operand to 2^-22..2^-23, and the three products h0 g0 + h0 g1 + h1 g0 (what is left out is below
+// 2^-22 |a b|) give dot products whose error against fp64 is that of the fp32 FMA chain — measured (in-run probe, length 1408): max
+// 2.4e-6 / rms 4.3e-7 against 3.1e-6 / 6.9e-7 — for HALF the MFMAs of the bf16 form.  What fp16 lacks is RANGE (6e-8 .. 65504), so both
+// operands are block-scaled by exact powers of two:
+//   weights:     one scale per layer, chosen by the loader so that the largest weight lands in [8192, 16384)
+//   activations: one scale per staged tile (conv_h16_kernel) or chunk (conv_h16_bal_kernel), from max |x| after the prologue: the
+//                largest staged value lands in [8192, 16384); values many octaves below the maximum lose relative precision, which is
+//                irrelevant in a sum dominated by the large ones; an all-zero tile takes scale 1
+// The accumulators run in scaled units (bias preloaded times both scales) and are brought back by one exact multiplication per
+// register before the epilogue.  LDS row = two fp16 planes of the 64-channel chunk + 16 bytes (272 = 17 x 16).
+// ---------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+#define EVX_KC 64                           // input channels per LDS stage of the split pipes
+#define EVX_RSB (3 * EVX_KC * 2 + 16)       // LDS row stride in bytes, bf16 (400 = 25 x 16)
+#define EVH_RSB (2 * EVX_KC * 2 + 16)       // ... fp16 (272)
+// three bf16 pieces of four fp32 values, packed as the four channels' bf16 in channel order (8 bytes per piece)
+__device__ __forceinline__ void evx_split4(const f32x4 v, uint2& q0, uint2& q1, uint2& q2) {
+    unsigned u[4], w[4];
+    float r[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { u[e] = __float_as_uint(v[e]); r[e] = v[e] - __uint_as_float(u[e] & 0xffff0000u); w[e] = __float_as_uint(r[e]); }
+    q0.x = __builtin_amdgcn_perm(u[1], u[0], 0x07060302u); q0.y = __builtin_amdgcn_perm(u[3], u[2], 0x07060302u);
+    q1.x = __builtin_amdgcn_perm(w[1], w[0], 0x07060302u); q1.y = __builtin_amdgcn_perm(w[3], w[2], 0x07060302u);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) u[e] = __float_as_uint(r[e] - __uint_as_float(w[e] & 0xffff0000u));
+    q2.x = __builtin_amdgcn_perm(u[1], u[0], 0x07060302u); q2.y = __builtin_amdgcn_perm(u[3], u[2], 0x07060302u);
+}
+// test hook (ev_op_split_pieces): the three pieces of every element, as fp32 values, so that a test can check p0 + p1 + p2 == x bit for bit
+// and that each piece is a bf16 value
+__global__ void evx_split_check_kernel(const float* x, float* pieces /*[3][n]*/, int n) {
+    const int i = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= n) return;
+    f32x4 v = {x[i], i + 1 < n ? x[i + 1] : 0.f, i + 2 < n ? x[i + 2] : 0.f, i + 3 < n ? x[i + 3] : 0.f};
+    uint2 q0, q1, q2;
+    evx_split4(v, q0, q1, q2);
+    const unsigned w[3][2] = {{q0.x, q0.y}, {q1.x, q1.y}, {q2.x, q2.y}};
+    for (int pc = 0; pc < 3; ++pc)
+        for (int e = 0; e < 4; ++e)
+            if (i + e < n) pieces[(size_t)pc * n + i + e] = __uint_as_float(((w[pc][e >> 1] >> (16 * (e & 1))) & 0xffffu) << 16);
+}
+template <int TM, int TN, int TERMS>
+__device__ __forceinline__ void evx_mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[3][TM], const f32x4 (&b)[3][TN]) {
+    // smallest products first; the accumulators of the TM x TN tiles alternate, so consecutive MFMAs are independent
+    constexpr int PA[9] = {2, 1, 2, 0, 2, 1, 0, 1, 0}, PB[9] = {2, 2, 1, 2, 0, 1, 1, 0, 0};
+#pragma unroll
+    for (int t = 9 - TERMS; t < 9; ++t)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[PA[t]][i]), __builtin_bit_cast(bf16x8, b[PB[t]][j]), acc[i][j], 0, 0, 0);
+}
+// two fp16 pieces of four fp32 values (already scaled), packed in channel order (8 bytes per piece)
+__device__ __forceinline__ void evh_split4(const f32x4 v, uint2& q0, uint2& q1) {
+    _Float16 h[4], l[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { h[e] = (_Float16)v[e]; l[e] = (_Float16)(v[e] - (float)h[e]); }
+    const f16x2 a = {h[0], h[1]}, b = {h[2], h[3]}, c = {l[0], l[1]}, d = {l[2], l[3]};
+    q0.x = __builtin_bit_cast(unsigned, a); q0.y = __builtin_bit_cast(unsigned, b);
+    q1.x = __builtin_bit_cast(unsigned, c); q1.y = __builtin_bit_cast(unsigned, d);
+}
+// power of two s with max * s in [8192, 16384), clamped to [2^-40, 2^40]  (max = 0 or not finite: 1).
+// The clamp bounds everything derived from a scale: the product with a weight scale (also within 2^+-40) stays within 2^+-80, and the factor
+// xn / xs by which conv_h16_bal_kernel / ln_mlp_h16_kernel move their running sums (bounded by 2^40 in their own unit) from one chunk's scale
+// to the next is at most 2^80: no step can overflow fp32.  A tile whose maximum is below 2^-27 is ~0 beside the bias; one whose finite maximum
+// exceeds 2^55 (3.6e16) leaves fp16's range and comes out as Inf where the fp32 builds would still be finite — documented in DESIGN 3.
+__device__ __forceinline__ float evh_scale_for(float mx) {
+    const int ex = (int)((__float_as_uint(mx) >> 23) & 255u);          // biased exponent of max
+    if (ex == 0 || ex == 255) return 1.f;
+    int e2 = 267 - ex;                                                  // biased exponent of 2^(13 - floor(log2 max))
+    e2 = e2 > 167 ? 167 : (e2 < 87 ? 87 : e2);
+    return __uint_as_float((unsigned)e2 << 23);
+}
+// A tile maximum that is not finite (an Inf among the staged values; NaNs never reach a maximum: v_max ignores them) must not set the
+// tile's scale: with scale 1 every finite value above 65504 of the SAME tile would overflow too and the small ones would lose their second
+// piece — rows of another utterance that merely share the tile with the bad one.  The kernels therefore repeat their search over the FINITE
+// values only (workgroup-uniform slow path, never taken on clean data); the non-finite elements themselves become fp16 Inf / NaN and spoil
+// exactly the outputs whose taps touch them, as in the fp32 builds.
+__device__ __forceinline__ bool evh_is_finite(float m) { return (__float_as_uint(m) & 0x7f800000u) != 0x7f800000u; }
+__device__ __forceinline__ float evh_absmax4(const f32x4 v) { return fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))); }
+__device__ __forceinline__ float evh_absmax4_finite(const f32x4 v) {
+    float m = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { const float a = fabsf(v[e]); m = fmaxf(m, evh_is_finite(a) ? a : 0.f); }
+    return m;
+}
+// Workgroup maximum (4 waves) through LDS: the 64-lane butterfly, one slot per wave at red[slot + wave], one barrier.  A later search must
+// use other slots unless a barrier lies between (a slow wave may still be reading these).
+__device__ __forceinline__ float evh_wg_max(float* red, int slot, int wave, int lane, float mx) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if (lane == 0) red[slot + wave] = mx;
+    ev_lds_barrier();
+    return fmaxf(fmaxf(red[slot], red[slot + 1]), fmaxf(red[slot + 2], red[slot + 3]));
+}
+template <int TM, int TN>
+__device__ __forceinline__ void evh_mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[2][TM], const f32x4 (&b)[2][TN]) {
+    constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[PA[t]][i]), __builtin_bit_cast(f16x8, b[PB[t]][j]), acc[i][j], 0, 0, 0);
+}
+
+// A pipe = how an fp32 operand is cut into 16-bit pieces and multiplied.  The weights come in MFMA-fragment order, PIECES fragments
+// of 64 lanes x 16 bytes per k-group ([tap][32-row tile][k-group][piece][lane]); an LDS stage holds KC input channels of every tile row as
+// PIECES planes in a row of RSB bytes, and a (chunk, tap) is FOUR 16-deep k-groups: 32 bytes of a plane each, this lane's half at 16 lh.
+//   EvPipeBf16<TERMS> three bf16 pieces, TERMS exact products; tap-list entries carry the fp32 plane offset and a split plane is 1.5 x that
+//   EvPipeH16         two block-scaled fp16 pieces, three products; a tap's two planes are as large as its fp32 plane
+// put(): split and write one staged float4 (channels sc4 .. sc4 + 3 of tile row r; `on`: the row is one of the tile's).
+template <int TERMS>
+struct EvPipeBf16 {
+    static_assert(TERMS == 3 || TERMS == 6 || TERMS == 9, "products per element pair");
+    static constexpr int PIECES = 3, KC = EVX_KC, RSB = EVX_RSB;
+    static constexpr unsigned KG_BYTES = 3072u;
+    static __device__ __forceinline__ unsigned tap_off(unsigned tb) { return tb + (tb >> 1); }
+    template <int TM, int TN>
+    static __device__ __forceinline__ void mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[3][TM], const f32x4 (&b)[3][TN]) { evx_mma<TM, TN, TERMS>(acc, a, b); }
+    // (raw: tools/conv_bench.py ablation — no split arithmetic, timing only)
+    static __device__ __forceinline__ void put(char* Xb, int r, int sc4, bool on, const f32x4 v, bool raw = false) {
+        uint2 q0v, q1v, q2v;
+        if (raw) { q0v.x = __float_as_uint(v[0]); q0v.y = __float_as_uint(v[1]); q1v = q0v; q2v = q0v; }
+        else evx_split4(v, q0v, q1v, q2v);
+        if (on) {
+            char* dst = Xb + r * RSB + sc4 * 2;
+            *(uint2*)(dst) = q0v; *(uint2*)(dst + KC * 2) = q1v; *(uint2*)(dst + KC * 4) = q2v;
+        }
+    }
+};
+struct EvPipeH16 {
+    static constexpr int PIECES = 2, KC = EVX_KC, RSB = EVH_RSB;
+    static constexpr unsigned KG_BYTES = 2048u;
+    static __device__ __forceinline__ unsigned tap_off(unsigned tb) { return tb; }
+    template <int TM, int TN>
+    static __device__ __forceinline__ void mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[2][TM], const f32x4 (&b)[2][TN]) { evh_mma<TM, TN>(acc, a, b); }
+    static __device__ __forceinline__ void put(char* Xb, int r, int sc4, bool on, const f32x4 v /* times the activation scale */) {
+        uint2 q0v, q1v;
+        evh_split4(v, q0v, q1v);
+        if (on) {
+            char* dst = Xb + r * RSB + sc4 * 2;
+            *(uint2*)(dst) = q0v; *(uint2*)(dst + KC * 2) = q1v;
+        }
+    }
+};
+
+// ---- X staging.  A thread stages four channels (sc4 ..) of one row per pass; rows outside the tensor read the all-zero pad row 0 and
+// passes beyond the tile's rows (in_tile false) re-read that row, so every load is UNCONDITIONAL (see EvConvCore::ldAp).
+// byte offset of global row gr for this thread
+__device__ __forceinline__ unsigned ev_row_off(const ConvParams& p, int gr, bool in_tile, int sc4) {
+    return ((in_tile && gr >= 0 && gr < p.nrows) ? (unsigned)gr * (unsigned)p.ldx : 0u) * 4u + (unsigned)sc4 * 4u;
+}
+// ... of all passes of a tile whose first staged row (for this thread) is gr0, fixed for the tile.  (The balanced split kernels recompute
+// their offsets per chunk, in their own words: kept across their MFMA phases the offsets went to scratch.)
+template <int RPS, int XPASS>
+__device__ __forceinline__ void ev_row_offs(const ConvParams& p, int gr0, int xrows, int sc4, unsigned (&xoff)[XPASS]) {
+#pragma unroll
+    for (int q = 0; q < XPASS; ++q) xoff[q] = ev_row_off(p, gr0 + q * RPS, q * RPS < xrows, sc4);
+}
+// byte offset of the KC-channel chunk `ch` inside an input row: channel c lives at (c >> isplit_log2) * isstride + (c & (2^isplit_log2 - 1))
+// (the pair view of a strided slice: the stride-2 down conv reads rows of 2 C channels whose halves lie isstride apart; no split: 2^31)
+template <int KC>
+__device__ __forceinline__ unsigned ev_chunk_off(const ConvParams& p, int ch) {
+    const int c0 = ch * KC;
+    return ((unsigned)(c0 >> p.isplit_log2) * (unsigned)p.isstride + (unsigned)(c0 & ((1 << p.isplit_log2) - 1))) * 4u;
+}
+// the prologue leaky-relu of a staged float4
+__device__ __forceinline__ f32x4 ev_pro_lrelu4(const ConvParams& p, f32x4 v) {
+    if (p.pro_lrelu) {
+        v[0] = ev_lrelu(v[0], p.pro_slope); v[1] = ev_lrelu(v[1], p.pro_slope);
+        v[2] = ev_lrelu(v[2], p.pro_slope); v[3] = ev_lrelu(v[3], p.pro_slope);
+    }
+    return v;
+}
+
+// ---- hand-over of the balanced grid (SkCtl): a wave's accumulator tile in a workgroup's slot of the hand-over area, TM TN 4 float4 per lane;
+// pelem = this lane's place in the slot, base = the slot (wave-uniform: scalar offset)
+template <int TM, int TN>
+__device__ __forceinline__ void ev_acc_store(const __amdgpu_buffer_rsrc_t& rPart, unsigned pelem, unsigned base, const f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 v = {acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]};
+                ev_bstore4_sc1(rPart, pelem, base + (unsigned)((a * TN + b) * 4 + q) * 1024u, v);     // (write-through)
+            }
+}
+template <int TM, int TN>
+__device__ __forceinline__ void ev_acc_add(const __amdgpu_buffer_rsrc_t& rPart, unsigned pelem, unsigned base, f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 v = ev_bload4_sc1(rPart, pelem, base + (unsigned)((a * TN + b) * 4 + q) * 1024u);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[a][b][4 * q + e] += v[e];
+            }
+}
+
+// ---------------------------------------------------------------------------
+// EvConvCore: one workgroup tile of BM output channels x BN rows on 4 waves (WAVES_M x WAVES_N, wave tile TM x TN tiles of 32 x 32) of
+// conv_split_kernel and conv_h16_kernel, in the style of EvResblockCore.
+// Every member is forced inline and every register array is indexed by compile-time constants, so the fragments and accumulators stay in
+// registers.  Construct it behind the tile-skip test.
+//
+// The A operand (weights) never touches LDS: one buffer load per lane and piece reads a contiguous 1 KiB (L2-resident) fragment.  Weight
+// fragments run one whole tap (four k-groups) ahead of the MFMAs in four statically named sets, activation fragments one k-group ahead in
+// two: a load is first touched a k-group (or a tap) after it was issued — no register copies, so the compiler's s_waitcnt lands at the
+// first use and L2 / LDS latency hides under the MFMAs.  (Measured with tools/conv_bench.py: a one-k-group-deep weight pipeline left
+// 6-12 % on the table on every deep layer; halving the L2 stream with a 4 x 1 wave layout recovered 1 % of it: fragment LATENCY under
+// load, not bandwidth.)  So the waves of a workgroup only meet at the two barriers around each X-tile stage.
+// The accumulation order is (chunk, tap, k-group).
+// ---------------------------------------------------------------------------
+template <int BM, int BN, int WAVES_M, int WAVES_N, class PIPE>
+struct EvConvCore {
+    static constexpr int TM = BM / WAVES_M / 32, TN = BN / WAVES_N / 32;
+    static constexpr int PIECES = PIPE::PIECES, RSB = PIPE::RSB;
+    static constexpr unsigned KGB = PIPE::KG_BYTES;
+    static constexpr int TPR = PIPE::KC / 4, RPS = 256 / TPR;           // staging: threads per row, rows per pass
+    static_assert(WAVES_M * WAVES_N == 4 && TM >= 1 && TN >= 1, "4 waves per workgroup");
+
+    int tid, lane, wave, wm, wn, li, lh;
+    int srow, sc4;                                      // staging row within a pass / first of this thread's four channels
+    unsigned wlane;                                     // per-lane byte offset inside a 1 KiB fragment
+    unsigned rstep, wbase;                              // bytes between the k-group rows of consecutive 32-row tiles; of this wave's first tile
+    f32x16 acc[TM][TN];
+    f32x4 A0[PIECES][TM], A1[PIECES][TM], A2[PIECES][TM], A3[PIECES][TM], B0[PIECES][TN], B1[PIECES][TN];
+
+    __device__ __forceinline__ EvConvCore(const ConvParams& p, int m0) {
+        tid = threadIdx.x; lane = tid & 63;
+        wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: keeps fragment offsets in SGPRs
+        wm = wave / WAVES_N; wn = wave % WAVES_N;
+        li = lane & 31; lh = lane >> 5;
+        srow = tid / TPR; sc4 = (tid % TPR) * 4;
+        wlane = (unsigned)lane * 16u;
+        rstep = (unsigned)(p.Kpad >> (TPR == 8 ? 3 : 4)) * KGB;     // (four k-groups per KC channels)
+        wbase = (unsigned)((m0 + wm * (TM * 32)) >> 5) * rstep;
+    }
+    // this wave's first channel / row of the tile at (m0, n0); its scratch for the epilogue's transpose
+    __device__ __forceinline__ int ch0(int m0) const { return m0 + wm * (TM * 32); }
+    __device__ __forceinline__ int row0(int n0) const { return n0 + wn * (TN * 32); }
+    __device__ __forceinline__ float* epi(float* smem) const { return smem + wave * (32 * (TM * 32 + 4)); }
+    // this lane's LDS row 0 for the tap loop when `halo` rows lie in front of the tile's row 0
+    __device__ __forceinline__ const char* bbase(const char* Xb, int halo) const { return Xb + (wn * (TN * 32) + li + halo) * RSB + 16 * lh; }
+
+    // byte offset (wave-uniform) of this wave's fragment at k-group kg of the tap whose list entry is tap_bytes
+    __device__ __forceinline__ unsigned a_off(int tap_bytes, int kg) const { return PIPE::tap_off((unsigned)tap_bytes) + wbase + (unsigned)kg * KGB; }
+    // (no conditional loads anywhere in the K loop: a load under a branch — even a wave-uniform one — makes hipcc's waitcnt
+    // insertion give up counting and wait vmcnt(0) at the next use, which drains the whole fragment pipeline)
+    __device__ __forceinline__ void ldAp(const __amdgpu_buffer_rsrc_t& rW, f32x4 (&dst)[PIECES][TM], unsigned aoff) {
+#pragma unroll
+        for (int pc = 0; pc < PIECES; ++pc)
+#pragma unroll
+            for (int i = 0; i < TM; ++i) dst[pc][i] = ev_bload4(rW, wlane, aoff + (unsigned)i * rstep + (unsigned)(pc * 1024));
+    }
+    __device__ __forceinline__ void ldB(f32x4 (&dst)[PIECES][TN], const char* brow, int kg) {
+#pragma unroll
+        for (int pc = 0; pc < PIECES; ++pc)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) dst[pc][j] = *(const f32x4*)(brow + j * 32 * RSB + pc * (2 * PIPE::KC) + kg * 32);
+    }
+    // The accumulators start from the bias in accumulator units (`unit`: 1 unless the pipe is block-scaled) when the epilogue expects it
+    // there (with_bias: a lean epilogue), else from zero.
+    // C/D row of register 4 g + e is 8 g + 4 lh + e.
+    __device__ __forceinline__ void acc_init(const ConvParams& p, int m0, float unit, bool with_bias) {
+#pragma unroll
+        for (int a = 0; a < TM; ++a) {
+            f32x4 bq[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 z = {0.f, 0.f, 0.f, 0.f};
+                bq[g] = z;
+                const int c0 = ch0(m0) + a * 32 + 8 * g + 4 * lh;
+                if (p.bias && with_bias && c0 < p.Cout) bq[g] = *(const f32x4*)(p.bias + c0) * unit;
+            }
+#pragma unroll
+            for (int b = 0; b < TN; ++b)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[a][b][r] = bq[r >> 2][r & 3];
+        }
+    }
+    // the four k-groups of the first tap (list entry tap0) of chunk 0, requested early: they fly under the first staging
+    __device__ __forceinline__ void ring_fill(const __amdgpu_buffer_rsrc_t& rW, int tap0) {
+        const unsigned a0 = a_off(tap0, 0);
+        ldAp(rW, A0, a0); ldAp(rW, A1, a0 + KGB); ldAp(rW, A2, a0 + 2u * KGB); ldAp(rW, A3, a0 + 3u * KGB);
+    }
+    // The taps of a chunk staged in LDS (`bb` = bbase(), tv_first = ev_tap_at(tlv, 0)):
+    //     const char* brow = c.tap_first(tv_first, bb);
+    //     for (int ti = 0; ti < nact; ++ti) brow = c.tap(rW, tlv, tv_first, nact, ti, ch, nchunks, bb, brow);
+    // The `for` stands in the kernel: inside a member function hipcc optimises the loop on its own before it is inlined, and the kernels came
+    // out with other registers and spills (NOTES.md).  tap_first requests the first activation fragments of the chunk's first tap.
+    __device__ __forceinline__ const char* tap_first(int2 tv_first, const char* bb) {
+        const char* brow = bb + tv_first.y * RSB;
+        ldB(B0, brow, 0);
+        return brow;
+    }
+    // Tap ti of chunk ch of the tile's nchunks; brow = this tap's LDS row, returns the next tap's.  Ring set g
+    // holds k-group g of the current tap and is refilled with k-group g of the NEXT tap (the next chunk's first, after the last) right after
+    // its MFMAs.  sched_barrier pins "loads, then the MFMAs of a k-group": hipcc otherwise sinks the prefetches into the MFMA block and
+    // waits for them a few MFMAs later.
+    __device__ __forceinline__ const char* tap(const __amdgpu_buffer_rsrc_t& rW, int2 tlv, int2 tv_first, int nact, int ti, int ch, int nchunks, const char* bb, const char* brow) {
+        const bool last_tap = (ti + 1 == nact);
+        const int2 ntv = last_tap ? tv_first : ev_tap_at(tlv, ti + 1);
+        const char* nbrow = bb + ntv.y * RSB;
+        const bool have_next = !(last_tap && ch + 1 == nchunks);
+        // after the tile's very last tap: a harmless re-read of its first fragments (unconditional loads)
+        const unsigned nap = have_next ? a_off(ntv.x, last_tap ? ch * 4 + 4 : ch * 4) : a_off(tv_first.x, 0);
+        ldB(B1, brow, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        PIPE::template mma<TM, TN>(acc, A0, B0);
+        __builtin_amdgcn_sched_barrier(0);
+        ldAp(rW, A0, nap);
+        ldB(B0, brow, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        PIPE::template mma<TM, TN>(acc, A1, B1);
+        __builtin_amdgcn_sched_barrier(0);
+        ldAp(rW, A1, nap + KGB);
+        ldB(B1, brow, 3);
+        __builtin_amdgcn_sched_barrier(0);
+        PIPE::template mma<TM, TN>(acc, A2, B0);
+        __builtin_amdgcn_sched_barrier(0);
+        ldAp(rW, A2, nap + 2u * KGB);
+        // first B fragments of the next tap (after the last tap of a chunk: a harmless read of the tile being retired)
+        ldB(B0, nbrow, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        PIPE::template mma<TM, TN>(acc, A3, B1);
+        __builtin_amdgcn_sched_barrier(0);
+        ldAp(rW, A3, nap + 3u * KGB);
+        return nbrow;
+    }
+};
+
 // One 32-channel k-chunk is staged per barrier pair; the accumulation order is (chunk, tap, k-group).  KB (k-chunks per stage) is 1
 // only: the parameter keeps the kernel names that traces, profiles/ and tests/test_code_object.py carry.
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool PF = false, bool FULL_ACT = true, int LEAN = 0, int KB = 1>
@@ -844,15 +1213,11 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
 #pragma unroll
     for (int q = 0; q < XPASS; ++q) {
         const int gr = n0 - p.halo_lo + q * RPS + srow;
-        xoff[q] = ((q < npass && gr >= 0 && gr < p.nrows) ? (unsigned)gr * (unsigned)p.ldx : 0u) * 4u + (unsigned)sc4 * 4u;
+        xoff[q] = ev_row_off(p, gr, q < npass, sc4);
     }
-    auto x_soff = [&](int ch) -> unsigned {
-        const int c0 = ch * EV_BK;
-        return ((unsigned)(c0 >> p.isplit_log2) * p.isstride + (unsigned)(c0 & ((1 << p.isplit_log2) - 1))) * 4u;
-    };
     f32x4 xv[PF ? XPASS : 1];
     auto x_issue = [&](int ch) {                        // PF only: all passes of one chunk into registers
-        const unsigned soff = x_soff(ch);
+        const unsigned soff = ev_chunk_off<EV_BK>(p, ch);
 #pragma unroll
         for (int q = 0; q < XPASS; ++q) xv[PF ? q : 0] = ev_bload4(rX, xoff[q], soff);
     };
@@ -882,7 +1247,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
 #pragma unroll
                 for (int q = 0; q < XPASS; ++q) x_put(q, xv[PF ? q : 0], c0, ctail);
             } else {
-                const unsigned soff = x_soff(ch);
+                const unsigned soff = ev_chunk_off<EV_BK>(p, ch);
 #pragma unroll
                 for (int q0 = 0; q0 < XPASS; q0 += XG) {
                     if (q0 * RPS >= xrows) continue;
@@ -960,86 +1325,16 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
 }
 
 // ---------------------------------------------------------------------------
-// conv_split_kernel: the same implicit GEMM on the bf16 matrix pipe, fp32 in and out.
-//
-// The fp32 MFMA of gfx950 runs at the vector rate (157 TFLOP/s); v_mfma_f32_32x32x16_bf16 runs sixteen times faster and
-// accumulates in fp32.  Every fp32 value is the EXACT sum of three bf16 values (8 + 8 + 8 significand bits: x0 = the upper half
-// of the word, x1 = the upper half of x - x0, x2 = x - x0 - x1), and a bf16 x bf16 product is exact in the fp32 accumulator, so
-//     a . b  =  sum over pieces  a_p . b_q
-// with the six products of weight p + q <= 2 (a0b0, a0b1, a1b0, a0b2, a1b1, a2b0) leaves out only terms below 2^-24 |a b| — the
-// size of ONE fp32 rounding.  Measured (tools/bf16_split_probe.hip, dot products of length 1408 against fp64): fp32 MFMA max
-// 3.1e-6 / rms 6.9e-7 of the result's scale, six products 3.4e-6 / 5.9e-7, nine products the same, three products 8.9e-5: six it
-// is.  Cost: 6 MFMAs of 32 cycles per 16-deep slab against 8 of 64 — 2.67x the rate of the fp32 pipe (probe: 365 TFLOP/s of
-// fp32-equivalent work in a loop fed from LDS and L2, against 153).
-//   weights:     split once by the loader, fragment order [tap][32-row tile][16-deep slab][piece][lane][8 bf16]
-//                (lane = (row & 31) + 32 * half, element e <-> k = 16 slab + 8 half + e): one 16-byte load per lane and piece
-//   activations: split while they are staged: LDS row = three bf16 planes of the 64-channel chunk (+ 16 bytes: an odd multiple of
-//                16 keeps the 16-byte fragment reads conflict-free); a chunk is four slabs, so the fragment ring of the K loop
-//                (four statically named sets, one tap ahead) carries over unchanged from conv_gemm_kernel
-//   epilogue:    the D layout of the 32 x 32 tile is that of the fp32 instruction: conv_epilogue_lean as is
+// conv_split_kernel: conv_gemm_kernel's tile on the bf16 pipe (EvPipeBf16<TERMS>), fp32 in and out, lean epilogues.  Beside the
+// core: staging in batches of six passes, and the conv_bench.py ablations (dbg 4, 8, 32, 64).
 // ---------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#define EVX_KC 64                           // input channels per LDS stage
-#define EVX_RSB (3 * EVX_KC * 2 + 16)       // LDS row stride in bytes (400 = 25 x 16)
-// byte offset of the 64-channel chunk `ch` inside an input row: channel c lives at (c >> isplit_log2) * isstride + (c & (2^isplit_log2 - 1))
-// (the pair view of a strided slice: the stride-2 down conv reads rows of 2 C channels whose halves lie isstride apart; no split: 2^31)
-__device__ __forceinline__ unsigned evx_chunk_off(const ConvParams& p, int ch) {
-    const int c0 = ch * EVX_KC;
-    return ((unsigned)(c0 >> p.isplit_log2) * (unsigned)p.isstride + (unsigned)(c0 & ((1 << p.isplit_log2) - 1))) * 4u;
-}
-// three bf16 pieces of four fp32 values, packed as the four channels' bf16 in channel order (8 bytes per piece)
-__device__ __forceinline__ void evx_split4(const f32x4 v, uint2& q0, uint2& q1, uint2& q2) {
-    unsigned u[4], w[4];
-    float r[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { u[e] = __float_as_uint(v[e]); r[e] = v[e] - __uint_as_float(u[e] & 0xffff0000u); w[e] = __float_as_uint(r[e]); }
-    q0.x = __builtin_amdgcn_perm(u[1], u[0], 0x07060302u); q0.y = __builtin_amdgcn_perm(u[3], u[2], 0x07060302u);
-    q1.x = __builtin_amdgcn_perm(w[1], w[0], 0x07060302u); q1.y = __builtin_amdgcn_perm(w[3], w[2], 0x07060302u);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) u[e] = __float_as_uint(r[e] - __uint_as_float(w[e] & 0xffff0000u));
-    q2.x = __builtin_amdgcn_perm(u[1], u[0], 0x07060302u); q2.y = __builtin_amdgcn_perm(u[3], u[2], 0x07060302u);
-}
-// test hook (ev_op_split_pieces): the three pieces of every element, as fp32 values, so that a test can check p0 + p1 + p2 == x bit for bit
-// and that each piece is a bf16 value
-__global__ void evx_split_check_kernel(const float* x, float* pieces /*[3][n]*/, int n) {
-    const int i = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= n) return;
-    f32x4 v = {x[i], i + 1 < n ? x[i + 1] : 0.f, i + 2 < n ? x[i + 2] : 0.f, i + 3 < n ? x[i + 3] : 0.f};
-    uint2 q0, q1, q2;
-    evx_split4(v, q0, q1, q2);
-    const unsigned w[3][2] = {{q0.x, q0.y}, {q1.x, q1.y}, {q2.x, q2.y}};
-    for (int pc = 0; pc < 3; ++pc)
-        for (int e = 0; e < 4; ++e)
-            if (i + e < n) pieces[(size_t)pc * n + i + e] = __uint_as_float(((w[pc][e >> 1] >> (16 * (e & 1))) & 0xffffu) << 16);
-}
-
-template <int TM, int TN, int TERMS>
-__device__ __forceinline__ void evx_mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[3][TM], const f32x4 (&b)[3][TN]) {
-    // smallest products first; the accumulators of the TM x TN tiles alternate, so consecutive MFMAs are independent
-    constexpr int PA[9] = {2, 1, 2, 0, 2, 1, 0, 1, 0}, PB[9] = {2, 2, 1, 2, 0, 1, 1, 0, 0};
-#pragma unroll
-    for (int t = 9 - TERMS; t < 9; ++t)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[PA[t]][i]), __builtin_bit_cast(bf16x8, b[PB[t]][j]), acc[i][j], 0, 0, 0);
-}
-
 template <int BM, int BN, int WAVES_M, int WAVES_N, int LEAN, int TERMS = 6>
 __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvParams p) {
-    constexpr int TM = BM / WAVES_M / 32;
-    constexpr int TN = BN / WAVES_N / 32;
-    static_assert(WAVES_M * WAVES_N == 4 && TM >= 1 && TN >= 1, "4 waves per workgroup");
-    static_assert(TERMS == 3 || TERMS == 6 || TERMS == 9, "products per element pair");
+    using PIPE = EvPipeBf16<TERMS>;
+    using Core = EvConvCore<BM, BN, WAVES_M, WAVES_N, PIPE>;
+    constexpr int TM = Core::TM, TN = Core::TN, RPS = Core::RPS;   // staging: 16 threads per row, 16 rows per pass
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* Xb = (char*)smem;                            // [(BN + halo)][EVX_RSB bytes]
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int li = lane & 31, lh = lane >> 5;
 
     const int nwg = p.mtiles * p.ntiles;
     const int work = ev_xcd_remap(blockIdx.x, nwg);
@@ -1051,69 +1346,25 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvParams p) 
     const int2* tl = p.taplist + (size_t)mt * p.tl_stride;
     const int nact = __builtin_amdgcn_readfirstlane(p.nact_tab ? p.nact_tab[mt] : p.ntaps);
 
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a) {
-        f32x4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            bq[g] = z;
-            const int c0 = m0 + wm * (TM * 32) + a * 32 + 8 * g + 4 * lh;
-            if (p.bias && c0 < p.Cout) bq[g] = *(const f32x4*)(p.bias + c0);
-        }
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = bq[r >> 2][r & 3];
-    }
-
+    Core c(p, m0);
+    c.acc_init(p, m0, 1.0f, true);
     const int xrows = BN + p.halo_lo + p.halo_hi;
-    constexpr int TPR = EVX_KC / 4, RPS = 256 / TPR;   // staging: 16 threads per row, 16 rows per pass
-    const int srow = tid / TPR;
-    const int sc4 = (tid % TPR) * 4;
     const int nchunks = p.Kpad / EVX_KC;
     constexpr int XPASS = (BN + EV_HALO) / RPS;
     constexpr int XG = 6;
     static_assert(XPASS % XG == 0, "staging batches");
-    const int mt32 = (m0 + wm * (TM * 32)) >> 5;
-    const int KG16 = p.Kpad >> 4;
     const __amdgpu_buffer_rsrc_t rW = ev_rsrc(p.Wx), rX = ev_rsrc(p.X);
-    const unsigned wlane = (unsigned)lane * 16u;
-    const unsigned wbase = (unsigned)(mt32 * KG16) * 3072u;
-    // the tap list carries byte offsets of the fp32 planes ((Mpad/32) (Kpad/8) KiB per tap); a split plane is 1.5 x that
-    auto a_off = [&](int tap_bytes, int kg16) -> unsigned { return (unsigned)tap_bytes + ((unsigned)tap_bytes >> 1) + wbase + (unsigned)kg16 * 3072u; };
-    f32x4 A0[3][TM], A1[3][TM], A2[3][TM], A3[3][TM], B0[3][TN], B1[3][TN];
-    auto ldAp = [&](f32x4 (&dst)[3][TM], unsigned aoff) {
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
-#pragma unroll
-            for (int i = 0; i < TM; ++i) dst[pc][i] = ev_bload4(rW, wlane, aoff + (unsigned)(i * KG16 * 3072 + pc * 1024));
-    };
-    auto ldB = [&](f32x4 (&dst)[3][TN], const char* brow, int slab) {
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) dst[pc][j] = *(const f32x4*)(brow + j * 32 * EVX_RSB + pc * (EVX_KC * 2) + slab * 32);
-    };
-    const char* bbase = Xb + (wn * (TN * 32) + li + p.halo_lo) * EVX_RSB + 16 * lh;
-    const int2 tlv = (lane < nact) ? tl[lane] : make_int2(0, 0);
+    const char* bbase = c.bbase(Xb, p.halo_lo);
+    const int2 tlv = (c.lane < nact) ? tl[c.lane] : make_int2(0, 0);
     const int2 tv_first = ev_tap_at(tlv, 0);
-    if (nact > 0) {
-        const unsigned a0 = a_off(tv_first.x, 0);
-        ldAp(A0, a0); ldAp(A1, a0 + 3072u); ldAp(A2, a0 + 6144u); ldAp(A3, a0 + 9216u);
-    }
+    if (nact > 0) c.ring_fill(rW, tv_first.x);
     unsigned xoff[XPASS];
-#pragma unroll
-    for (int q = 0; q < XPASS; ++q) {
-        const int gr = n0 - p.halo_lo + q * RPS + srow;
-        xoff[q] = ((q * RPS < xrows && gr >= 0 && gr < p.nrows) ? (unsigned)gr * (unsigned)p.ldx : 0u) * 4u + (unsigned)sc4 * 4u;
-    }
+    ev_row_offs<RPS>(p, n0 - p.halo_lo + c.srow, xrows, c.sc4, xoff);
     for (int ch = 0; ch < nchunks; ++ch) {
         __builtin_amdgcn_s_setprio(3);
         if (!(p.dbg & 8)) ev_lds_barrier();             // the previous chunk's MFMAs are done with the tile
         if (!(p.dbg & 64) || ch == 0) {                 // (dbg 64: stage the first chunk only — timing ablation)
-            const unsigned soff = evx_chunk_off(p, ch);
+            const unsigned soff = ev_chunk_off<EVX_KC>(p, ch);
 #pragma unroll
             for (int q0 = 0; q0 < XPASS; q0 += XG) {
                 if (q0 * RPS >= xrows) continue;
@@ -1122,58 +1373,19 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvParams p) 
                 for (int q = 0; q < XG; ++q) xg[q] = ev_bload4(rX, xoff[q0 + q], soff);      // (passes beyond the tile re-read row 0)
 #pragma unroll
                 for (int q = 0; q < XG; ++q) {
-                    const int r = (q0 + q) * RPS + srow;
-                    f32x4 v = xg[q];
-                    if (p.pro_lrelu) {
-                        v[0] = ev_lrelu(v[0], p.pro_slope); v[1] = ev_lrelu(v[1], p.pro_slope);
-                        v[2] = ev_lrelu(v[2], p.pro_slope); v[3] = ev_lrelu(v[3], p.pro_slope);
-                    }
-                    uint2 q0v, q1v, q2v;
-                    if (p.dbg & 32) { q0v.x = __float_as_uint(v[0]); q0v.y = __float_as_uint(v[1]); q1v = q0v; q2v = q0v; }   // tools/conv_bench.py ablation: no split arithmetic (timing only)
-                    else evx_split4(v, q0v, q1v, q2v);
-                    if (r < xrows) {
-                        char* dst = Xb + r * EVX_RSB + sc4 * 2;
-                        *(uint2*)(dst) = q0v; *(uint2*)(dst + EVX_KC * 2) = q1v; *(uint2*)(dst + EVX_KC * 4) = q2v;
-                    }
+                    const int r = (q0 + q) * RPS + c.srow;
+                    PIPE::put(Xb, r, c.sc4, r < xrows, ev_pro_lrelu4(p, xg[q]), (p.dbg & 32) != 0);
                 }
             }
         }
         if (!(p.dbg & 8)) ev_lds_barrier();
         __builtin_amdgcn_s_setprio(0);
-        const char* brow = bbase + tv_first.y * EVX_RSB;
-        ldB(B0, brow, 0);
-        for (int ti = 0; ti < nact; ++ti) {
-            const bool last_tap = (ti + 1 == nact);
-            const int2 ntv = last_tap ? tv_first : ev_tap_at(tlv, ti + 1);
-            const char* nbrow = bbase + ntv.y * EVX_RSB;
-            const bool have_next = !(last_tap && ch + 1 == nchunks);
-            const unsigned nap = have_next ? a_off(ntv.x, last_tap ? ch * 4 + 4 : ch * 4) : a_off(tv_first.x, 0);   // unconditional loads
-            ldB(B1, brow, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            evx_mma<TM, TN, TERMS>(acc, A0, B0);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(A0, nap);
-            ldB(B0, brow, 2);
-            __builtin_amdgcn_sched_barrier(0);
-            evx_mma<TM, TN, TERMS>(acc, A1, B1);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(A1, nap + 3072u);
-            ldB(B1, brow, 3);
-            __builtin_amdgcn_sched_barrier(0);
-            evx_mma<TM, TN, TERMS>(acc, A2, B0);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(A2, nap + 6144u);
-            ldB(B0, nbrow, 0);                          // (after a chunk's last tap: a harmless read of the tile being retired)
-            __builtin_amdgcn_sched_barrier(0);
-            evx_mma<TM, TN, TERMS>(acc, A3, B1);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(A3, nap + 9216u);
-            brow = nbrow;
-        }
+        const char* brow = c.tap_first(tv_first, bbase);
+        for (int ti = 0; ti < nact; ++ti) brow = c.tap(rW, tlv, tv_first, nact, ti, ch, nchunks, bbase, brow);
     }
     __builtin_amdgcn_s_setprio(3);
-    if (p.dbg & 4) { if (acc[0][0][0] == 12345.678f) p.Y[0] = 1.f; return; }   // tools/conv_bench.py ablation: no epilogue
-    conv_epilogue_lean<TM, TN, LEAN>(p, acc, smem + wave * (32 * (TM * 32 + 4)), m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane);
+    if (p.dbg & 4) { if (c.acc[0][0][0] == 12345.678f) p.Y[0] = 1.f; return; }   // tools/conv_bench.py ablation: no epilogue
+    conv_epilogue_lean<TM, TN, LEAN>(p, c.acc, c.epi(smem), c.ch0(m0), c.row0(n0), c.lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -1249,12 +1461,8 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_bal_kernel(const ConvParams 
 #pragma unroll
         for (int q = 0; q < XPASS; ++q) {
             const int gr = n0 - p.halo_lo + q * RPS + srow;
-            xoff[q] = ((q < npass && gr >= 0 && gr < p.nrows) ? (unsigned)gr * (unsigned)p.ldx : 0u) * 4u + (unsigned)sc4 * 4u;
+            xoff[q] = ev_row_off(p, gr, q < npass, sc4);
         }
-        auto x_soff = [&](int ch) -> unsigned {
-            const int cc = ch * EV_BK;
-            return ((unsigned)(cc >> p.isplit_log2) * p.isstride + (unsigned)(cc & ((1 << p.isplit_log2) - 1))) * 4u;
-        };
         auto x_put = [&](int q, f32x4 v, int cc, bool ctail) {
             const int r = q * RPS + srow;
             if (ctail && cc + sc4 >= p.Cin) { v[0] = 0.f; v[1] = 0.f; v[2] = 0.f; v[3] = 0.f; }
@@ -1307,7 +1515,7 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_bal_kernel(const ConvParams 
                 {
                     const int cc = ch * EV_BK;
                     const bool ctail = (cc + 32 > p.Cin);
-                    const unsigned soff = x_soff(ch);
+                    const unsigned soff = ev_chunk_off<EV_BK>(p, ch);
 #pragma unroll
                     for (int q0 = 0; q0 < XPASS; q0 += XG) {
                         if (q0 * RPS >= xrows) continue;
@@ -1355,27 +1563,9 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_bal_kernel(const ConvParams 
                     brow = nbrow;
                 }
             }
-            auto acc_io = [&](unsigned base, int mode) {    // mode 0: store (write-through), 1: add from memory
-#pragma unroll
-                for (int a = 0; a < TM; ++a)
-#pragma unroll
-                    for (int b = 0; b < TN; ++b)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const unsigned soff = base + (unsigned)((a * TN + b) * 4 + q) * 1024u;     // (wave-uniform: scalar offset)
-                            if (mode == 0) {
-                                const f32x4 v = {acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]};
-                                ev_bstore4_sc1(rPart, pelem, soff, v);
-                            } else {
-                                const f32x4 v = ev_bload4_sc1(rPart, pelem, soff);
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) acc[a][b][4 * q + e] += v[e];
-                            }
-                        }
-            };
-            if (spilled) { acc_io((unsigned)g * pslot + pslot / 2, 1); spilled = false; }   // running sum (spilled) + this contributor's share
+            if (spilled) { ev_acc_add<TM, TN>(rPart, pelem, (unsigned)g * pslot + pslot / 2, acc); spilled = false; }   // running sum (spilled) + this contributor's share
             if (c0 != 0) {                                 // not the owner: hand the partial tile over (flag raised at the next segment)
-                acc_io((unsigned)g * pslot, 0);
+                ev_acc_store<TM, TN>(rPart, pelem, (unsigned)g * pslot, acc);
                 pend_pub = true;
                 break;
             }
@@ -1385,13 +1575,13 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_bal_kernel(const ConvParams 
                 while (n < 64 && gi + n < (int)gridDim.x && sk_start(p.sk, gi + n) < tile_end) ++n;
                 if (n == 0) break;
                 const int ready = sk_wait_many(p.sk, gi, n, tag, tid, skw);
-                for (int k = 0; k < ready; ++k) acc_io((unsigned)(gi + k) * pslot, 1);
+                for (int k = 0; k < ready; ++k) ev_acc_add<TM, TN>(rPart, pelem, (unsigned)(gi + k) * pslot, acc);
                 gi += ready;
                 if (ready < n) {                           // gi is not there in time: spill the running sum, compute its share here
                     const int sgi = sk_start(p.sk, gi);
                     int egi = sk_start(p.sk, gi + 1);
                     egi = egi < tile_end ? egi : tile_end;
-                    acc_io((unsigned)g * pslot + pslot / 2, 0);
+                    ev_acc_store<TM, TN>(rPart, pelem, (unsigned)g * pslot + pslot / 2, acc);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     cA = sgi - t * nchunks; cB = egi - t * nchunks;
                     spilled = true; again = true;
@@ -1411,95 +1601,24 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_bal_kernel(const ConvParams 
 }
 
 // ---------------------------------------------------------------------------
-// conv_h16_kernel: conv_split_kernel with fp16 pieces.  An fp16 value carries 11 significand bits, so TWO pieces (x = h0 + h1, h0 = the
-// nearest fp16, h1 = the nearest fp16 of the rest) represent an fp32 operand to 2^-22..2^-23, and the three products h0 g0 + h0 g1 + h1 g0
-// (what is left out is below 2^-22 |a b|) give dot products whose error against fp64 is that of the fp32 FMA chain — measured (in-run probe,
-// length 1408): max 2.4e-6 / rms 4.3e-7 against 3.1e-6 / 6.9e-7 — for HALF the MFMAs of the bf16 form.  What fp16 lacks is RANGE (6e-8 ..
-// 65504), so both operands are block-scaled by exact powers of two:
-//   weights:     one scale per layer, chosen by the loader so that the largest weight lands in [8192, 16384)
-//   activations: one scale per workgroup tile, from a pre-scan of the rows it is about to stage (max |x| after the prologue): the largest
-//                staged value lands in [8192, 16384); values many octaves below the tile's maximum lose relative precision, which is
-//                irrelevant in a sum dominated by the large ones; an all-zero tile takes scale 1
-// The accumulators run in scaled units (bias preloaded times both scales) and are brought back by one exact multiplication per
-// register before the epilogue.  LDS row = two fp16 planes of the 64-channel chunk + 16 bytes (272 = 17 x 16).
-// ---------------------------------------------------------------------------
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-#define EVH_RSB (2 * EVX_KC * 2 + 16)
-// two fp16 pieces of four fp32 values (already scaled), packed in channel order (8 bytes per piece)
-__device__ __forceinline__ void evh_split4(const f32x4 v, uint2& q0, uint2& q1) {
-    _Float16 h[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { h[e] = (_Float16)v[e]; l[e] = (_Float16)(v[e] - (float)h[e]); }
-    const f16x2 a = {h[0], h[1]}, b = {h[2], h[3]}, c = {l[0], l[1]}, d = {l[2], l[3]};
-    q0.x = __builtin_bit_cast(unsigned, a); q0.y = __builtin_bit_cast(unsigned, b);
-    q1.x = __builtin_bit_cast(unsigned, c); q1.y = __builtin_bit_cast(unsigned, d);
-}
-// power of two s with max * s in [8192, 16384), clamped to [2^-40, 2^40]  (max = 0 or not finite: 1).
-// The clamp bounds everything derived from a scale: the product with a weight scale (also within 2^+-40) stays within 2^+-80, and the factor
-// xn / xs by which conv_h16_bal_kernel / ln_mlp_h16_kernel move their running sums (bounded by 2^40 in their own unit) from one chunk's scale
-// to the next is at most 2^80: no step can overflow fp32.  A tile whose maximum is below 2^-27 is ~0 beside the bias; one whose finite maximum
-// exceeds 2^55 (3.6e16) leaves fp16's range and comes out as Inf where the fp32 builds would still be finite — documented in DESIGN 3.
-__device__ __forceinline__ float evh_scale_for(float mx) {
-    const int ex = (int)((__float_as_uint(mx) >> 23) & 255u);          // biased exponent of max
-    if (ex == 0 || ex == 255) return 1.f;
-    int e2 = 267 - ex;                                                  // biased exponent of 2^(13 - floor(log2 max))
-    e2 = e2 > 167 ? 167 : (e2 < 87 ? 87 : e2);
-    return __uint_as_float((unsigned)e2 << 23);
-}
-// A tile maximum that is not finite (an Inf among the staged values; NaNs never reach a maximum: v_max ignores them) must not set the
-// tile's scale: with scale 1 every finite value above 65504 of the SAME tile would overflow too and the small ones would lose their second
-// piece — rows of another utterance that merely share the tile with the bad one.  The kernels therefore repeat their search over the FINITE
-// values only (workgroup-uniform slow path, never taken on clean data); the non-finite elements themselves become fp16 Inf / NaN and spoil
-// exactly the outputs whose taps touch them, as in the fp32 builds.
-__device__ __forceinline__ bool evh_is_finite(float m) { return (__float_as_uint(m) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ float evh_absmax4(const f32x4 v) { return fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))); }
-__device__ __forceinline__ float evh_absmax4_finite(const f32x4 v) {
-    float m = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { const float a = fabsf(v[e]); m = fmaxf(m, evh_is_finite(a) ? a : 0.f); }
-    return m;
-}
-// Workgroup maximum (4 waves) through LDS: the 64-lane butterfly, one slot per wave at red[slot + wave], one barrier.  A later search must
-// use other slots unless a barrier lies between (a slow wave may still be reading these).
-__device__ __forceinline__ float evh_wg_max(float* red, int slot, int wave, int lane, float mx) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if (lane == 0) red[slot + wave] = mx;
-    ev_lds_barrier();
-    return fmaxf(fmaxf(red[slot], red[slot + 1]), fmaxf(red[slot + 2], red[slot + 3]));
-}
-template <int TM, int TN>
-__device__ __forceinline__ void evh_mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[2][TM], const f32x4 (&b)[2][TN]) {
-    constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[PA[t]][i]), __builtin_bit_cast(f16x8, b[PB[t]][j]), acc[i][j], 0, 0, 0);
-}
-
+// conv_h16_kernel: conv_split_kernel's tile on the fp16 pipe (EvPipeH16).  Beside the core: ONE activation scale per workgroup tile,
+// from the producer's bound of the rows it stages (ev_amax_read) or, without one, from a pre-scan of them; the amax bounds of its own
+// output; and the Q = 1 form of the K loop.
+//
 // Q = 1: the K loop on v_mfma_f32_16x16x32_f16 (16 x 16 output tiles, 32-deep steps) instead of v_mfma_f32_32x32x16_f16.  Same FLOP per
 // cycle, same operand bytes per FLOP at the same 64 x 64 wave tile — but under this chip's power limit the 16 x 16 shape holds a higher clock:
 // tools/mfma_shape_probe.hip (LDS + L2 fed loop of this kernel's shape, random data, two waves per SIMD): 1254 vs 1444 TFLOP/s executed,
 // 1.52 vs 1.72 GHz (profiles/r04_mfma_shape_probe.txt; MI355X_MICROARCH.md, DVFS give-back item 7).  Weights: p.Wq, the same two fp16 pieces in
 // the 16 x 16 x 32 fragment order [tap][Mpad/16][Kpad/32][piece][64 lanes][8]: lane = (row & 15) + 16 kgroup, element e = k 32 kg32 + 8 kgroup + e.
+// It keeps a ring of its own (two sets, one 32-deep step ahead) and takes only the geometry and the staging from the core.
+// ---------------------------------------------------------------------------
 template <int BM, int BN, int WAVES_M, int WAVES_N, int LEAN, int Q = 0>
 __global__ __launch_bounds__(256, 2) void conv_h16_kernel(const ConvParams p) {
-    constexpr int TM = BM / WAVES_M / 32;
-    constexpr int TN = BN / WAVES_N / 32;
-    static_assert(WAVES_M * WAVES_N == 4 && TM >= 1 && TN >= 1, "4 waves per workgroup");
+    using Core = EvConvCore<BM, BN, WAVES_M, WAVES_N, EvPipeH16>;
+    constexpr int TM = Core::TM, TN = Core::TN, RPS = Core::RPS;   // staging: 16 threads per row, 16 rows per pass
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* Xb = (char*)smem;                            // [(BN + halo)][EVH_RSB bytes]
     float* red = smem + ((BN + EV_HALO) * EVH_RSB) / 4;  // 4 floats behind the tile: the waves' maxima
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int li = lane & 31, lh = lane >> 5;
 
     const int nwg = p.mtiles * p.ntiles;
     const int work = ev_xcd_remap(blockIdx.x, nwg);
@@ -1508,39 +1627,20 @@ __global__ __launch_bounds__(256, 2) void conv_h16_kernel(const ConvParams p) {
     const int m0 = mt * BM;
     const int n0 = nt * BN;
     if (ev_tile_is_padding(p.S, p.P, p.T, p.nrows, n0, BN)) return;
-    EvAmax am = ev_amax_begin(p, n0 + wn * (TN * 32), TN * 32);   // (the residual's / running sum's bounds: requested now, used behind the epilogue)
+    Core c(p, m0);
+    const int lane = c.lane, wave = c.wave, srow = c.srow, sc4 = c.sc4;
+    EvAmax am = ev_amax_begin(p, c.row0(n0), TN * 32);   // (the residual's / running sum's bounds: requested now, used behind the epilogue)
     const int2* tl = p.taplist + (size_t)mt * p.tl_stride;
     const int nact = __builtin_amdgcn_readfirstlane(p.nact_tab ? p.nact_tab[mt] : p.ntaps);
 
     const int xrows = BN + p.halo_lo + p.halo_hi;
-    constexpr int TPR = EVX_KC / 4, RPS = 256 / TPR;   // staging: 16 threads per row, 16 rows per pass
-    const int srow = tid / TPR;
-    const int sc4 = (tid % TPR) * 4;
     const int nchunks = p.Kpad / EVX_KC;
     constexpr int XPASS = (BN + EV_HALO) / RPS;
     constexpr int XG = XPASS % 6 == 0 ? 6 : 4;
     static_assert(XPASS % XG == 0, "staging batches");
-    const int mt32 = (m0 + wm * (TM * 32)) >> 5;
-    const int KG16 = p.Kpad >> 4;
     const __amdgpu_buffer_rsrc_t rW = ev_rsrc(p.Wh), rX = ev_rsrc(p.X);
-    const unsigned wlane = (unsigned)lane * 16u;
-    const unsigned wbase = (unsigned)(mt32 * KG16) * 2048u;
-    // (a tap's fp16 plane — (Mpad/32) (Kpad/16) x 2 KiB — is as large as its fp32 plane: the tap list's byte offsets apply as they are)
-    auto a_off = [&](int tap_bytes, int kg16) -> unsigned { return (unsigned)tap_bytes + wbase + (unsigned)kg16 * 2048u; };
-    f32x4 A0[2][TM], A1[2][TM], A2[2][TM], A3[2][TM], B0[2][TN], B1[2][TN];
-    auto ldAp = [&](f32x4 (&dst)[2][TM], unsigned aoff) {
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc)
-#pragma unroll
-            for (int i = 0; i < TM; ++i) dst[pc][i] = ev_bload4(rW, wlane, aoff + (unsigned)(i * KG16 * 2048 + pc * 1024));
-    };
-    auto ldB = [&](f32x4 (&dst)[2][TN], const char* brow, int slab) {
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) dst[pc][j] = *(const f32x4*)(brow + j * 32 * EVH_RSB + pc * (EVX_KC * 2) + slab * 32);
-    };
-    const char* bbase = Xb + (wn * (TN * 32) + li + p.halo_lo) * EVH_RSB + 16 * lh;
+    const unsigned wlane = c.wlane;
+    const char* bbase = c.bbase(Xb, p.halo_lo);
     const int2 tlv = (lane < nact) ? tl[lane] : make_int2(0, 0);
     const int2 tv_first = ev_tap_at(tlv, 0);
     // the 16 x 16 x 32 form's fragments (Q = 1; unused and eliminated otherwise)
@@ -1548,7 +1648,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_kernel(const ConvParams p) {
     const int f16i = lane & 15, kg = lane >> 4;        // frame (column) inside a tile / 8-deep k group of the 32-deep step
     const __amdgpu_buffer_rsrc_t rQ = ev_rsrc(p.Wq);
     const int KG32 = p.Kpad >> 5;
-    const unsigned qbase = (unsigned)(((m0 + wm * (TM * 32)) >> 4) * KG32) * 2048u;
+    const unsigned qbase = (unsigned)((c.ch0(m0) >> 4) * KG32) * 2048u;
     // fragment (tile a, piece pc) of the 32-deep step kg32 of a tap: tap bytes + ((m16 KG32 + kg32) 2 + pc) KiB
     auto q_off = [&](int tap_bytes, int kg32) -> unsigned { return (unsigned)tap_bytes + qbase + (unsigned)kg32 * 2048u; };
     f32x4 QA0[2][QM], QA1[2][QM], QB0[2][QN], QB1[2][QN];
@@ -1559,20 +1659,14 @@ __global__ __launch_bounds__(256, 2) void conv_h16_kernel(const ConvParams p) {
             for (int a = 0; a < QM; ++a) dst[pc][a] = ev_bload4(rQ, wlane, aoff + (unsigned)(a * KG32 * 2048 + pc * 1024));
     };
     if (nact > 0) {                                     // the first tap's fragments fly under the pre-scan
-        if constexpr (Q == 0) {
-            const unsigned a0 = a_off(tv_first.x, 0);
-            ldAp(A0, a0); ldAp(A1, a0 + 2048u); ldAp(A2, a0 + 4096u); ldAp(A3, a0 + 6144u);
-        } else {
+        if constexpr (Q == 0) c.ring_fill(rW, tv_first.x);
+        else {
             const unsigned a0 = q_off(tv_first.x, 0);
             ldQA(QA0, a0); ldQA(QA1, a0 + 2048u);
         }
     }
     unsigned xoff[XPASS];
-#pragma unroll
-    for (int q = 0; q < XPASS; ++q) {
-        const int gr = n0 - p.halo_lo + q * RPS + srow;
-        xoff[q] = ((q * RPS < xrows && gr >= 0 && gr < p.nrows) ? (unsigned)gr * (unsigned)p.ldx : 0u) * 4u + (unsigned)sc4 * 4u;
-    }
+    ev_row_offs<RPS>(p, n0 - p.halo_lo + srow, xrows, sc4, xoff);
     // ---- pre-scan: max |x| (after the prologue: |lrelu(x)| <= |x|, so the raw maximum bounds it) over everything this tile stages
     float xs;
     {
@@ -1580,7 +1674,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_kernel(const ConvParams p) {
             constexpr bool FIN = decltype(finite_only)::value;
             float mx = 0.f;
             for (int ch = 0; ch < ((p.dbg & 2048) ? 0 : nchunks); ++ch) {      // (dbg 2048: tools/conv_bench.py ablation — no pre-scan, a fixed scale of 1024)
-                const unsigned soff = evx_chunk_off(p, ch);
+                const unsigned soff = ev_chunk_off<EVX_KC>(p, ch);
 #pragma unroll
                 for (int q0 = 0; q0 < XPASS; q0 += XG) {
                     if (q0 * RPS >= xrows) continue;
@@ -1607,104 +1701,48 @@ __global__ __launch_bounds__(256, 2) void conv_h16_kernel(const ConvParams p) {
     const float acc_out = 1.0f / acc_in;               // (both powers of two: exact)
 
     auto stage = [&](int ch) {                          // chunk ch of the X tile: prologue, scale, split, LDS
-        {
-            const unsigned soff = evx_chunk_off(p, ch);
+        const unsigned soff = ev_chunk_off<EVX_KC>(p, ch);
 #pragma unroll
-            for (int q0 = 0; q0 < XPASS; q0 += XG) {
-                if (q0 * RPS >= xrows) continue;
-                f32x4 xg[XG];
+        for (int q0 = 0; q0 < XPASS; q0 += XG) {
+            if (q0 * RPS >= xrows) continue;
+            f32x4 xg[XG];
 #pragma unroll
-                for (int q = 0; q < XG; ++q) xg[q] = ev_bload4(rX, xoff[q0 + q], soff);      // (passes beyond the tile re-read row 0)
+            for (int q = 0; q < XG; ++q) xg[q] = ev_bload4(rX, xoff[q0 + q], soff);      // (passes beyond the tile re-read row 0)
 #pragma unroll
-                for (int q = 0; q < XG; ++q) {
-                    const int r = (q0 + q) * RPS + srow;
-                    f32x4 v = xg[q];
-                    if (p.pro_lrelu) {
-                        v[0] = ev_lrelu(v[0], p.pro_slope); v[1] = ev_lrelu(v[1], p.pro_slope);
-                        v[2] = ev_lrelu(v[2], p.pro_slope); v[3] = ev_lrelu(v[3], p.pro_slope);
-                    }
-                    uint2 q0v, q1v;
-                    evh_split4(v * xs, q0v, q1v);
-                    if (r < xrows) {
-                        char* dst = Xb + r * EVH_RSB + sc4 * 2;
-                        *(uint2*)(dst) = q0v; *(uint2*)(dst + EVX_KC * 2) = q1v;
-                    }
-                }
+            for (int q = 0; q < XG; ++q) {
+                const int r = (q0 + q) * RPS + srow;
+                EvPipeH16::put(Xb, r, sc4, r < xrows, ev_pro_lrelu4(p, xg[q]) * xs);
             }
         }
     };
     if constexpr (Q == 0) {
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a) {
-        f32x4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            bq[g] = z;
-            const int c0 = m0 + wm * (TM * 32) + a * 32 + 8 * g + 4 * lh;
-            if (p.bias && c0 < p.Cout) bq[g] = *(const f32x4*)(p.bias + c0) * acc_in;
+        c.acc_init(p, m0, acc_in, true);
+        for (int ch = 0; ch < nchunks; ++ch) {
+            __builtin_amdgcn_s_setprio(3);
+            ev_lds_barrier();                               // the previous chunk's MFMAs are done with the tile
+            stage(ch);
+            ev_lds_barrier();
+            __builtin_amdgcn_s_setprio(0);
+            const char* brow = c.tap_first(tv_first, bbase);
+            for (int ti = 0; ti < nact; ++ti) brow = c.tap(rW, tlv, tv_first, nact, ti, ch, nchunks, bbase, brow);
         }
 #pragma unroll
-        for (int b = 0; b < TN; ++b)
+        for (int a = 0; a < TM; ++a)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = bq[r >> 2][r & 3];
-    }
-
-    for (int ch = 0; ch < nchunks; ++ch) {
+            for (int b = 0; b < TN; ++b)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) c.acc[a][b][r] *= acc_out;
         __builtin_amdgcn_s_setprio(3);
-        ev_lds_barrier();                               // the previous chunk's MFMAs are done with the tile
-        stage(ch);
-        ev_lds_barrier();
-        __builtin_amdgcn_s_setprio(0);
-        const char* brow = bbase + tv_first.y * EVH_RSB;
-        ldB(B0, brow, 0);
-        for (int ti = 0; ti < nact; ++ti) {
-            const bool last_tap = (ti + 1 == nact);
-            const int2 ntv = last_tap ? tv_first : ev_tap_at(tlv, ti + 1);
-            const char* nbrow = bbase + ntv.y * EVH_RSB;
-            const bool have_next = !(last_tap && ch + 1 == nchunks);
-            const unsigned nap = have_next ? a_off(ntv.x, last_tap ? ch * 4 + 4 : ch * 4) : a_off(tv_first.x, 0);   // unconditional loads
-            ldB(B1, brow, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            evh_mma<TM, TN>(acc, A0, B0);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(A0, nap);
-            ldB(B0, brow, 2);
-            __builtin_amdgcn_sched_barrier(0);
-            evh_mma<TM, TN>(acc, A1, B1);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(A1, nap + 2048u);
-            ldB(B1, brow, 3);
-            __builtin_amdgcn_sched_barrier(0);
-            evh_mma<TM, TN>(acc, A2, B0);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(A2, nap + 4096u);
-            ldB(B0, nbrow, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            evh_mma<TM, TN>(acc, A3, B1);
-            __builtin_amdgcn_sched_barrier(0);
-            ldAp(A3, nap + 6144u);
-            brow = nbrow;
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] *= acc_out;
-    __builtin_amdgcn_s_setprio(3);
-    ev_amax_from_acc<TM, TN>(p, am, acc, n0 + wn * (TN * 32), lane);
-    conv_epilogue_lean<TM, TN, LEAN>(p, acc, smem + wave * (32 * (TM * 32 + 4)), m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane);
-    ev_amax_emit(p, am, n0 + wn * (TN * 32), TN * 32, lane);
+        ev_amax_from_acc<TM, TN>(p, am, c.acc, c.row0(n0), lane);
+        conv_epilogue_lean<TM, TN, LEAN>(p, c.acc, c.epi(smem), c.ch0(m0), c.row0(n0), lane);
+        ev_amax_emit(p, am, c.row0(n0), TN * 32, lane);
     } else {
         // ---------------- the 16 x 16 x 32 form ----------------
         f32x4 acc[QM][QN];
 #pragma unroll
         for (int a = 0; a < QM; ++a) {
             f32x4 bq = {0.f, 0.f, 0.f, 0.f};
-            const int c0 = m0 + wm * (TM * 32) + a * 16 + 4 * kg;   // C/D layout: rows 4 (lane >> 4) + 0..3 of tile a
+            const int c0 = c.ch0(m0) + a * 16 + 4 * kg;   // C/D layout: rows 4 (lane >> 4) + 0..3 of tile a
             if (p.bias && c0 < p.Cout) bq = *(const f32x4*)(p.bias + c0) * acc_in;
 #pragma unroll
             for (int b = 0; b < QN; ++b) acc[a][b] = bq;
@@ -1726,7 +1764,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_kernel(const ConvParams p) {
                     for (int jj = 0; jj < QN; ++jj)
                         acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[PA[t]][i]), __builtin_bit_cast(f16x8, b[PB[t]][jj]), acc[i][jj], 0, 0, 0);
         };
-        const char* qbb = Xb + (wn * (TN * 32) + f16i + p.halo_lo) * EVH_RSB + 16 * kg;
+        const char* qbb = Xb + (c.wn * (TN * 32) + f16i + p.halo_lo) * EVH_RSB + 16 * kg;
         for (int ch = 0; ch < nchunks; ++ch) {
             __builtin_amdgcn_s_setprio(3);
             ev_lds_barrier();                           // the previous chunk's MFMAs are done with the tile
@@ -1759,9 +1797,9 @@ __global__ __launch_bounds__(256, 2) void conv_h16_kernel(const ConvParams p) {
 #pragma unroll
             for (int b = 0; b < QN; ++b) acc[a][b] *= acc_out;
         __builtin_amdgcn_s_setprio(3);
-        ev_amax_from_acc_q<QM, QN>(p, am, acc, n0 + wn * (TN * 32), lane);
-        conv_epilogue_lean_q<TM, TN, LEAN>(p, acc, smem + wave * (32 * (TM * 32 + 4)), m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane);
-        ev_amax_emit(p, am, n0 + wn * (TN * 32), TN * 32, lane);
+        ev_amax_from_acc_q<QM, QN>(p, am, acc, c.row0(n0), lane);
+        conv_epilogue_lean_q<TM, TN, LEAN>(p, acc, c.epi(smem), c.ch0(m0), c.row0(n0), lane);
+        ev_amax_emit(p, am, c.row0(n0), TN * 32, lane);
     }
 }
 
@@ -1866,7 +1904,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_bal_kernel(const ConvParams
                 __builtin_amdgcn_s_setprio(3);
                 ev_lds_barrier();                          // the previous chunk's MFMAs (or the previous segment's epilogue) are done with LDS
                 {
-                    const unsigned soff = evx_chunk_off(p, ch);
+                    const unsigned soff = ev_chunk_off<EVX_KC>(p, ch);
                     asm volatile("" : "+v"(gr0));          // (row offsets recomputed per chunk, not kept — and spilled — as loop invariants: conv_h16_bal_kernel)
 #pragma unroll
                     for (int q0 = 0; q0 < XPASS; q0 += XG) {
@@ -1877,17 +1915,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_bal_kernel(const ConvParams
 #pragma unroll
                         for (int q = 0; q < XG; ++q) {
                             const int r = (q0 + q) * RPS + srow;
-                            f32x4 v = xg[q];
-                            if (p.pro_lrelu) {
-                                v[0] = ev_lrelu(v[0], p.pro_slope); v[1] = ev_lrelu(v[1], p.pro_slope);
-                                v[2] = ev_lrelu(v[2], p.pro_slope); v[3] = ev_lrelu(v[3], p.pro_slope);
-                            }
-                            uint2 q0v, q1v, q2v;
-                            evx_split4(v, q0v, q1v, q2v);
-                            if (r < xrows) {
-                                char* dst = Xb + r * EVX_RSB + sc4 * 2;
-                                *(uint2*)(dst) = q0v; *(uint2*)(dst + EVX_KC * 2) = q1v; *(uint2*)(dst + EVX_KC * 4) = q2v;
-                            }
+                            EvPipeBf16<TERMS>::put(Xb, r, sc4, r < xrows, ev_pro_lrelu4(p, xg[q]));
                         }
                     }
                 }
@@ -1924,27 +1952,9 @@ __global__ __launch_bounds__(256, 2) void conv_split_bal_kernel(const ConvParams
                     brow = nbrow;
                 }
             }
-            auto acc_io = [&](unsigned base, int mode) {    // mode 0: store (write-through), 1: add from memory
-#pragma unroll
-                for (int a = 0; a < TM; ++a)
-#pragma unroll
-                    for (int b = 0; b < TN; ++b)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const unsigned soff = base + (unsigned)((a * TN + b) * 4 + q) * 1024u;     // (wave-uniform: scalar offset)
-                            if (mode == 0) {
-                                const f32x4 v = {acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]};
-                                ev_bstore4_sc1(rPart, pelem, soff, v);
-                            } else {
-                                const f32x4 v = ev_bload4_sc1(rPart, pelem, soff);
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) acc[a][b][4 * q + e] += v[e];
-                            }
-                        }
-            };
-            if (spilled) { acc_io((unsigned)g * pslot + pslot / 2, 1); spilled = false; }
+            if (spilled) { ev_acc_add<TM, TN>(rPart, pelem, (unsigned)g * pslot + pslot / 2, acc); spilled = false; }
             if (c0 != 0) {                                 // not the owner: hand the partial tile over (flag raised at the next segment)
-                acc_io((unsigned)g * pslot, 0);
+                ev_acc_store<TM, TN>(rPart, pelem, (unsigned)g * pslot, acc);
                 pend_pub = true;
                 break;
             }
@@ -1954,13 +1964,13 @@ __global__ __launch_bounds__(256, 2) void conv_split_bal_kernel(const ConvParams
                 while (n < 64 && gi + n < (int)gridDim.x && sk_start(p.sk, gi + n) < tile_end) ++n;
                 if (n == 0) break;
                 const int ready = sk_wait_many(p.sk, gi, n, tag, tid, skw);
-                for (int k = 0; k < ready; ++k) acc_io((unsigned)(gi + k) * pslot, 1);
+                for (int k = 0; k < ready; ++k) ev_acc_add<TM, TN>(rPart, pelem, (unsigned)(gi + k) * pslot, acc);
                 gi += ready;
                 if (ready < n) {                           // gi is not there in time: spill the running sum, compute its share here
                     const int sgi = sk_start(p.sk, gi);
                     int egi = sk_start(p.sk, gi + 1);
                     egi = egi < tile_end ? egi : tile_end;
-                    acc_io((unsigned)g * pslot + pslot / 2, 0);
+                    ev_acc_store<TM, TN>(rPart, pelem, (unsigned)g * pslot + pslot / 2, acc);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     cA = sgi - t * nchunks; cB = egi - t * nchunks;
                     spilled = true; again = true;
@@ -2097,7 +2107,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_bal_kernel(const ConvParams p
                 {
                     // the chunk's rows into registers (requested before the barrier: the round trip overlaps the other waves' last MFMAs),
                     // prologue applied, and this thread's maximum over the rows the tile really holds
-                    const unsigned soff = evx_chunk_off(p, ch);
+                    const unsigned soff = ev_chunk_off<EVX_KC>(p, ch);
                     // XK of the XPASS staging passes stay in registers from the maximum search to the split; the passes beyond (wide-halo
                     // layers only: XPASS = 12) are read TWICE — once for the maximum, once more (L2-hot, 16 KB per workgroup) for the split —
                     // which keeps the build at 36 staging registers instead of 48 and out of scratch.
@@ -2105,13 +2115,6 @@ __global__ __launch_bounds__(256, 2) void conv_h16_bal_kernel(const ConvParams p
                     // (the row offsets are recomputed per chunk — four vector instructions per pass: as loop invariants hipcc kept all of them,
                     // range tests included, in registers across the MFMA phase and spilled them to scratch; the empty asm hides the invariance)
                     asm volatile("" : "+v"(gr0));
-                    auto pro = [&](f32x4 v) -> f32x4 {
-                        if (p.pro_lrelu) {
-                            v[0] = ev_lrelu(v[0], p.pro_slope); v[1] = ev_lrelu(v[1], p.pro_slope);
-                            v[2] = ev_lrelu(v[2], p.pro_slope); v[3] = ev_lrelu(v[3], p.pro_slope);
-                        }
-                        return v;
-                    };
                     float mx = 0.f, mxf = 0.f;             // maximum / maximum over the finite values of the re-read passes
                     if constexpr (XPASS > XK) {
                         f32x4 xt[XPASS - XK];
@@ -2121,7 +2124,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_bal_kernel(const ConvParams p
                         for (int q = 0; q < XK; ++q) xg[q] = ev_bload4(rX, xoff(q), soff);
 #pragma unroll
                         for (int q = XK; q < XPASS; ++q) {
-                            const f32x4 v = pro(xt[q - XK]);
+                            const f32x4 v = ev_pro_lrelu4(p, xt[q - XK]);
                             const bool in = q * RPS + srow < xrows;
                             mx = in ? fmaxf(mx, evh_absmax4(v)) : mx;
                             mxf = in ? fmaxf(mxf, evh_absmax4_finite(v)) : mxf;
@@ -2132,7 +2135,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_bal_kernel(const ConvParams p
                     }
 #pragma unroll
                     for (int q = 0; q < XK; ++q) {
-                        const f32x4 v = pro(xg[q]);
+                        const f32x4 v = ev_pro_lrelu4(p, xg[q]);
                         xg[q] = v;
                         mx = (q * RPS + srow < xrows) ? fmaxf(mx, evh_absmax4(v)) : mx;
                     }
@@ -2164,15 +2167,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_bal_kernel(const ConvParams p
                                 for (int r = 0; r < 16; ++r) acc[a][b][r] *= f;
                         xs = xn;
                     }
-                    auto put = [&](int q, const f32x4 v) {
-                        const int r = q * RPS + srow;
-                        uint2 q0v, q1v;
-                        evh_split4(v * xs, q0v, q1v);
-                        if (r < xrows) {
-                            char* dst = Xb + r * EVH_RSB + sc4 * 2;
-                            *(uint2*)(dst) = q0v; *(uint2*)(dst + EVX_KC * 2) = q1v;
-                        }
-                    };
+                    auto put = [&](int q, const f32x4 v) { EvPipeH16::put(Xb, q * RPS + srow, sc4, q * RPS + srow < xrows, v * xs); };
                     if constexpr (XPASS > XK) {            // second read of the passes that were not kept
                         f32x4 xt[XPASS - XK];
 #pragma unroll
@@ -2180,7 +2175,7 @@ __global__ __launch_bounds__(256, 2) void conv_h16_bal_kernel(const ConvParams p
 #pragma unroll
                         for (int q = 0; q < XK; ++q) put(q, xg[q]);
 #pragma unroll
-                        for (int q = XK; q < XPASS; ++q) put(q, pro(xt[q - XK]));
+                        for (int q = XK; q < XPASS; ++q) put(q, ev_pro_lrelu4(p, xt[q - XK]));
                     } else {
 #pragma unroll
                         for (int q = 0; q < XK; ++q) put(q, xg[q]);
@@ -2888,29 +2883,8 @@ __global__ __launch_bounds__(256, WAVES_M == 2 ? 4 : 3) void resblock_pair_kerne
 // Geometry, the same in all four: 4 waves = WAVES_M channel tiles x WAVES_N row tiles, wave tile 32 channels x 64 rows (TM = 1, TN = 2),
 // C = 32 WAVES_M channels, NT = 64 WAVES_N compute rows per workgroup.  An LDS row holds ALL C channels as PIECES 16-bit planes + 16 bytes
 // (bf16: 6 C + 16 = 208 / 400 / 784;  fp16: 4 C + 16 = 144 / 272 / 528: odd multiples of 16), so a tile is staged — and split — once.
-//
-// A pipe = how an fp32 operand is cut into 16-bit pieces and multiplied:
-//   EvPipeH16         two block-scaled fp16 pieces, three products per fp32 product (conv_h16_kernel); a tap's two planes are as large as
-//                     its fp32 plane, so the tap list's byte offsets apply as they are
-//   EvPipeBf16<TERMS> three bf16 pieces, TERMS exact products (conv_split_kernel); tap-list entries carry the fp32 plane offset and a
-//                     split plane is 1.5 x that
+// The pipes (EvPipeH16, EvPipeBf16<TERMS>) are those of the conv kernels (EvConvCore); only PIECES, KG_BYTES, tap_off and mma are used here.
 // ---------------------------------------------------------------------------
-struct EvPipeH16 {
-    static constexpr int PIECES = 2;
-    static constexpr unsigned KG_BYTES = 2048u;         // bytes of one 16-deep weight k-group (PIECES fragments of 64 lanes x 16 bytes)
-    static __device__ __forceinline__ unsigned tap_off(unsigned tb) { return tb; }
-    template <int TM, int TN>
-    static __device__ __forceinline__ void mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[2][TM], const f32x4 (&b)[2][TN]) { evh_mma<TM, TN>(acc, a, b); }
-};
-template <int TERMS>
-struct EvPipeBf16 {
-    static constexpr int PIECES = 3;
-    static constexpr unsigned KG_BYTES = 3072u;
-    static __device__ __forceinline__ unsigned tap_off(unsigned tb) { return tb + (tb >> 1); }
-    template <int TM, int TN>
-    static __device__ __forceinline__ void mma(f32x16 (&acc)[TM][TN], const f32x4 (&a)[3][TM], const f32x4 (&b)[3][TN]) { evx_mma<TM, TN, TERMS>(acc, a, b); }
-};
-
 // Every member is forced inline and every register array is indexed by compile-time constants, so the fragments and accumulators stay in
 // registers.  Construct it behind the tile-skip test.
 template <int WAVES_M, int WAVES_N, class PIPE>

@@ -33,6 +33,7 @@ EXPORTS = [
     "ev_loudness",
     "ev_pyin_observe", "ev_pyin_decode",
     "ev_op_attention2", "ev_op_attn_out2",
+    "ev_load_stoi", "ev_stoi",
 ]
 
 
@@ -155,6 +156,8 @@ def load_library() -> C.CDLL:
     f64 = C.c_double
     lib.ev_pyin_observe.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, i32, i32, vp, i32, f64, f64, vp, vp, vp]
     lib.ev_pyin_decode.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, f64, f64, vp, vp, vp, vp]
+    lib.ev_load_stoi.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32]
+    lib.ev_stoi.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -472,6 +475,46 @@ class Engine:
         self._check(self.lib.ev_loudness(self.h, x.data_ptr(), ptr(ln), B, L, S, coef.ctypes.data, float(abs_gate), ptr(sub), ptr(block),
                                          gated.data_ptr(), counts.data_ptr(), _stream_ptr()), "ev_loudness")
         return sub, block, gated, counts
+
+    def load_stoi(self, window, twiddle, bands, hop: int, n_fft: int, seg_frames: int) -> None:
+        """The tables of ``stoi`` (ev_load_stoi), all on the host: ``window`` (W,) float64 with W = 2 hop, ``twiddle`` (n_fft, 2) float64
+        {cos, sin}(2 pi n / n_fft), ``bands`` (n_bands, 2) int32 {first bin, end bin}; ``seg_frames`` = N, the frames per segment."""
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float64).reshape(-1))
+        tw = np.ascontiguousarray(np.asarray(twiddle, dtype=np.float64).reshape(-1, 2))
+        bd = np.ascontiguousarray(np.asarray(bands, dtype=np.int32).reshape(-1, 2))
+        if tw.shape[0] != int(n_fft):
+            raise ValueError(f"load_stoi: {n_fft} twiddles expected, got {tw.shape[0]}")
+        self._check(self.lib.ev_load_stoi(self.h, w.ctypes.data, tw.ctypes.data, bd.ctypes.data, int(w.shape[0]), int(hop), int(n_fft), int(bd.shape[0]),
+                                          int(seg_frames)), "ev_load_stoi")
+        self.stoi_geometry = (int(w.shape[0]), int(hop), int(n_fft), int(bd.shape[0]), int(seg_frames))
+
+    def stoi(self, x, y, lengths, silence_ratio: float, clip: float, want_keep: bool = True, want_tob: bool = False, want_seg: bool = True):
+        """STOI / ESTOI of every processed row of ``y`` against the clean row of ``x``, both (B, L) at the measure's rate (ev_stoi, after
+        load_stoi): (keep (B, NF) uint8 or None, tob (B, 2, n_bands, NM) float64 or None, seg (B, NSEG, 2) float64 or None, score (B, 2)
+        float64 {STOI, ESTOI}, 0 for a row without a segment, counts (B, 3) int32 {frames, kept frames, segments}) on the device.
+        ``lengths`` (B,): samples per row (None: L)."""
+        x, y = self._f32(x), self._f32(y)
+        if x.dim() != 2 or y.shape != x.shape:
+            raise ValueError(f"stoi: x and y must be (B, L) alike, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+        if not hasattr(self, "stoi_geometry"):
+            raise EvLibraryError("stoi: tables not loaded (load_stoi)")
+        B, L = x.shape
+        W, H, _, nb, N = self.stoi_geometry
+        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"stoi: {B} lengths expected, got {ln.numel()}")
+        NF = -(-(L - W) // H) if L > W else 0
+        NM = max(NF - 1, 0)
+        NSEG = max(NM - N + 1, 0)
+        keep = torch.empty((B, NF), dtype=torch.uint8, device=x.device) if want_keep else None
+        tob = torch.empty((B, 2, nb, NM), dtype=torch.float64, device=x.device) if want_tob else None
+        seg = torch.empty((B, NSEG, 2), dtype=torch.float64, device=x.device) if want_seg else None
+        score = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+        counts = torch.empty((B, 3), dtype=torch.int32, device=x.device)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._check(self.lib.ev_stoi(self.h, x.data_ptr(), y.data_ptr(), ptr(ln), B, L, float(silence_ratio), float(clip), ptr(keep), ptr(tob), ptr(seg),
+                                     score.data_ptr(), counts.data_ptr(), _stream_ptr()), "ev_stoi")
+        return keep, tob, seg, score, counts
 
     def pyin_observe(self, x, lengths, frame_length: int, hop_length: int, tau_min: int, tau_max: int, sr: float, fmin: float,
                      bins_per_octave: int, n_bins: int, w, boltzmann: float = 2.0, no_trough_prob: float = 0.01, out=None):

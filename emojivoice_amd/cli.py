@@ -17,6 +17,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt                                             # pairs.txt.eval.json: MCD, f0 RMSE, voicing error per 'recorded.wav|synthesised.wav[|spk]'
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
+    python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000          # clean/filelist.txt.vocoder.json: STOI / ESTOI, mel L1 and loudness shift of copy synthesis
 
 The wavs of --mel_from_wav, --align_wav and --data_statistics may have any sample rate (the reference's recorder writes 44.1 kHz,
 record_audio.py:31): they are resampled to the analysis rate on the device (emojivoice_amd.audio.resample).
@@ -74,6 +75,10 @@ def validate_args(args):
         return args
     if getattr(args, "prosody_report", None) or getattr(args, "evaluate_pairs", None) or getattr(args, "loudness_report", None):
         assert args.batch_size > 0, "Batch size must be greater than 0"
+        return args
+    if getattr(args, "vocoder_report", None):
+        assert args.batch_size > 0, "Batch size must be greater than 0"
+        assert args.synthetic or args.vocoder_path, "--vocoder_report needs --vocoder_path (or --synthetic)"
         return args
     if args.mel_from_wav:
         return args
@@ -513,6 +518,88 @@ def loudness_report(args, device):
     return rep
 
 
+VOCODER_REPORT_KEYS = ("stoi", "estoi", "mel_l1", "lufs_shift")
+
+
+def vocoder_summary(files):
+    """{"files", "unscored": the paths without a STOI score, and per key of VOCODER_REPORT_KEYS {"mean", "min"} over the files that have the
+    figure (null where none has)} of a list of --vocoder_report file entries."""
+    out = {"files": len(files), "unscored": [f["path"] for f in files if f["stoi"] is None]}
+    for k in VOCODER_REPORT_KEYS:
+        v = [f[k] for f in files if f[k] is not None]
+        out[k] = {"mean": math.fsum(v) / len(v) if v else None, "min": min(v) if v else None}
+    return out
+
+
+@torch.inference_mode()
+def vocoder_report(args, device):
+    """--vocoder_report FILELIST (the filelist format of --prosody_report) with --vocoder_path / --synthetic and --vocoder_config: what copy
+    synthesis through this vocoder costs.  Every file is loaded at the config's rate and analysed as --mel_from_wav does (the recording cut to
+    256 x frames samples), --batch_size files at a time (padded with silence to the longest, each row with its own length), then vocoded; the
+    synthesis is sample-aligned with the recording.  FILELIST.vocoder.json receives per file "stoi" and "estoi" (audio.stoi: the synthesis
+    against the recording; null for a file too short to score), "mel_l1" (audio.mel_reconstruction_error), "lufs_shift" (the integrated
+    loudness, audio.loudness, of the synthesis minus that of the recording; null where either has none) and "seconds"; per speaker and
+    under "overall" the mean and the minimum of each and the files without a score."""
+    from . import audio
+    from . import weights as W
+    from .hifigan import AttrDict, Generator
+
+    entries = parse_filelist(args.vocoder_report)
+    if not entries:
+        sys.exit(f"[-] {args.vocoder_report}: no files listed")
+    h = AttrDict(vocoder_config(args.vocoder_config))
+    sr = int(h.get("sampling_rate", 22050))
+    sd = W.synthetic_hifigan_state(h) if args.synthetic else torch.load(args.vocoder_path, map_location="cpu")["generator"]
+    vocoder = Generator(h).to(device)
+    vocoder.load_state_dict(sd)
+    vocoder.eval()
+    vocoder.remove_weight_norm()
+    loud_ok = sr % 10 == 0 and sr >= 8000                                # the rates audio.k_weighting designs a filter for
+    value = lambda v: float(v) if math.isfinite(float(v)) else None
+    files = []
+    for b0 in range(0, len(entries), args.batch_size):
+        chunk = entries[b0:b0 + args.batch_size]
+        ys = [wav_at_rate(wav, sr, device) for wav, _, _ in chunk]
+        rows = [r for r, y in enumerate(ys) if y is not None]
+        fig = {}
+        if rows:
+            lens = [int(ys[r].shape[-1]) for r in rows]
+            rec = torch.zeros(len(rows), max(lens), device=device)
+            for i, r in enumerate(rows):
+                rec[i, : lens[i]] = ys[r].reshape(-1)
+            mel = audio.mel_spectrogram(rec, h.get("n_fft", 1024), h.get("num_mels", 80), sr, h.get("hop_size", 256), h.get("win_size", 1024),
+                                        h.get("fmin", 0), h.get("fmax", 8000))
+            frames = torch.tensor([n // 256 for n in lens], device=device)
+            syn = vocoder(mel).squeeze(1).clamp(-1, 1).contiguous()
+            if syn.shape != rec.shape:
+                sys.exit(f"[-] the vocoder renders {syn.shape[1]} samples for {rec.shape[1]}: --vocoder_report needs a config that upsamples by 256")
+            sc = audio.stoi(rec, syn, sr, lengths=lens)
+            l1 = audio.mel_reconstruction_error(vocoder, mel, frames).cpu()
+            shift = (audio.loudness(syn, sr, lengths=lens)["integrated"] - audio.loudness(rec, sr, lengths=lens)["integrated"]).cpu() if loud_ok else None
+            st, es = sc["stoi"].cpu(), sc["estoi"].cpu()
+            for i, r in enumerate(rows):
+                fig[r] = {"seconds": lens[i] / float(sr), "stoi": value(st[i]), "estoi": value(es[i]), "mel_l1": value(l1[i]),
+                          "lufs_shift": value(shift[i]) if shift is not None else None}
+        for r, (wav, spk, _) in enumerate(chunk):
+            files.append({"path": wav, "speaker": spk if spk is not None else "0",
+                          **fig.get(r, {"seconds": None, "stoi": None, "estoi": None, "mel_l1": None, "lufs_shift": None})})
+    speakers = {spk: vocoder_summary([f for f in files if f["speaker"] == spk]) for spk in dict.fromkeys(f["speaker"] for f in files)}
+    rep = {"sample_rate": sr, "vocoder_config": args.vocoder_config, "stoi_sample_rate": audio.STOI_SR, "files": files, "speakers": speakers,
+           "overall": vocoder_summary(files)}
+    out_path = f"{args.vocoder_report}.vocoder.json"
+    with open(out_path, "w") as f:
+        json.dump(rep, f, indent=1)
+    for k in sorted(speakers):
+        v = speakers[k]
+        score = "no file long enough to score" if v["stoi"]["mean"] is None else (
+            f"STOI {v['stoi']['mean']:.3f} mean, {v['stoi']['min']:.3f} min, ESTOI {v['estoi']['mean']:.3f} mean, mel L1 {v['mel_l1']['mean']:.3f}"
+            + ("" if v["lufs_shift"]["mean"] is None else f", loudness {v['lufs_shift']['mean']:+.2f} LU")
+            + (f", {len(v['unscored'])} without a score" if v["unscored"] else ""))
+        print(f"[i] speaker {k}: {v['files']} files, {score}")
+    print(f"[+] Vocoder report saved: {Path(out_path).resolve()}")
+    return rep
+
+
 EVAL_MEL = (1024, 80, 22050, 256, 1024, 0, 8000)    # n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax of the vocoder config
 EVAL_MAX_FRAMES = 4096                              # ev_dtw's limit per side (47.5 s)
 
@@ -676,7 +763,14 @@ def cli(argv=None):
                    "more than 3 LU from their speaker's mean (on the device, --batch_size files per batch; needs no checkpoint)")
     p.add_argument("--target_lufs", type=float, default=None, help="--prepare_dataset: level every recording to this integrated loudness (BS.1770, e.g. -23) "
                    "instead of to --peak; the gain is capped where the peak would pass --peak, and the gain and the cap go into FILELIST.durations.json")
+    p.add_argument("--vocoder_report", type=str, default=None, help="vocoder evaluation instead of synthesis: a filelist 'path|spk|text' -> FILELIST.vocoder.json: "
+                   "STOI / ESTOI of copy synthesis against the recording, mel L1, loudness shift and seconds per file; mean and minimum per speaker and "
+                   "overall (with --vocoder_path or --synthetic, --vocoder_config; on the device, --batch_size files per batch)")
     args = validate_args(p.parse_args(argv))
+    if args.vocoder_report:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return vocoder_report(args, torch.device("cuda", 0))
     if args.loudness_report:
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")

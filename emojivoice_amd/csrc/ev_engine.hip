@@ -122,6 +122,8 @@ struct DenoiserW { bool ready = false; ConvLayer fwd, inv; float* win2 = nullptr
 struct MelBasisW { bool loaded = false; int n_mels = 0, nb = 0; int* span = nullptr; float* wts = nullptr; };
 // Filter of ev_resample: the taps re-laid phase-major [up][Wp], W = ceil(n_taps / up) taps per phase, row stride Wp = W | 1, zero-padded
 struct ResamplerW { bool loaded = false; int up = 0, down = 0, n_taps = 0, W = 0, Wp = 0, tab_floats = 0; float* table = nullptr; };
+// Tables of ev_stoi: the analysis window (W), the twiddles (nfft, 2) and the bands (n_bands, 2), float64 / int32 on the device
+struct StoiW { bool loaded = false; int W = 0, H = 0, nfft = 0, n_bands = 0, N = 0, bin_lo = 0, bin_hi = 0; double* win = nullptr; double* tw = nullptr; int32_t* bands = nullptr; };
 
 }  // namespace
 
@@ -136,6 +138,7 @@ struct ev_handle {
     DenoiserW dn;
     MelBasisW melb;
     ResamplerW rs;
+    StoiW stoi;
     // small per-stage scratch arenas (denoiser, text encoder): grown on demand, ordered against their last user's stream
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
     Scratch dn_ws, enc_ws, mas_ws;   // (mas_ws: the alignment search's frame -> token index and, for large Tx * Ty, its decision bits)
@@ -143,6 +146,7 @@ struct ev_handle {
     Scratch stat_ws;                 // ev_mel_stats: the per-(row, 32 frames) partial sums
     Scratch trim_ws;                 // ev_trim_bounds: the per-(row, hop block) sum of squares (float64) and max |x| (fp32)
     Scratch loud_ws;                 // ev_loudness: per (row, chunk) the four filter-state doubles and the sub-block pieces; the sub-block energies without d_sub
+    Scratch stoi_ws;                 // ev_stoi: the frame energies, the kept frames' indices, and the band spectra / segment scores not asked for
     float* zeros = nullptr;     // 4096 zero floats (stand-in bias for the fused kernels' unconditional loads)
     int max_steps = 64;         // Euler steps the time-grid buffers of the workspace are planned for (grows on demand)
     int* bad_ids_host = nullptr; int* bad_ids_dev = nullptr;   // mapped host word: count of out-of-range token ids seen by ev_text_encoder
@@ -1995,6 +1999,7 @@ void ev_destroy(ev_handle* h) {
     if (h->stat_ws.p) hipFree(h->stat_ws.p);
     if (h->trim_ws.p) hipFree(h->trim_ws.p);
     if (h->loud_ws.p) hipFree(h->loud_ws.p);
+    if (h->stoi_ws.p) hipFree(h->stoi_ws.p);
     if (h->dn_ws.p) hipFree(h->dn_ws.p);
     if (h->bad_ids_host) hipHostFree(h->bad_ids_host);
     for (int i = 0; i < 2; ++i) { if (h->temb_ev[i]) hipEventDestroy(h->temb_ev[i]); if (h->temb_host[i]) hipHostFree(h->temb_host[i]); }
@@ -3090,6 +3095,88 @@ int ev_loudness(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int
     pg.sub = sub; pg.len = d_len; pg.block = d_block; pg.gated = d_gated; pg.counts = d_counts;
     pg.L = L; pg.S = S; pg.NS = NS; pg.NB = NB; pg.abs_gate = abs_gate;
     launch<loud_gate_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pg);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// STOI / ESTOI (kernels, the definition and every order: ev_kernels.h).  Arena: [E B x NF doubles][band spectra B x 2 x n_bands x NM doubles,
+// only without d_tob][segment scores B x NSEG x 2 doubles, only without d_seg][idx B x NF int32].
+int ev_load_stoi(ev_handle* h, const double* window, const double* twiddle, const int32_t* bands, int W, int H, int nfft, int n_bands, int N) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!window || !twiddle || !bands) return fail(h, "ev_load_stoi: window, twiddle and bands must be non-null (HOST)");
+    if (H < 32 || H > 256 || H % 32) return fail(h, "ev_load_stoi: H=%d must be a multiple of 32 with 32 <= H <= 256", H);
+    if (W != 2 * H) return fail(h, "ev_load_stoi: W=%d must be 2 H = %d (the overlap-add has exactly two terms)", W, 2 * H);
+    if (nfft < W || nfft > 1024) return fail(h, "ev_load_stoi: nfft=%d outside W <= nfft <= 1024 (W=%d)", nfft, W);
+    if (n_bands < 1 || n_bands > 32) return fail(h, "ev_load_stoi: n_bands=%d outside 1 <= n_bands <= 32", n_bands);
+    if (N < 2 || N > 64) return fail(h, "ev_load_stoi: N=%d outside 2 <= N <= 64", N);
+    StoiW t;
+    t.W = W; t.H = H; t.nfft = nfft; t.n_bands = n_bands; t.N = N;
+    t.bin_lo = nfft; t.bin_hi = 0;
+    for (int r = 0; r < n_bands; ++r) {
+        const int first = bands[2 * r], end = bands[2 * r + 1];
+        if (first < 0 || first >= end || end > nfft / 2 + 1)
+            return fail(h, "ev_load_stoi: bands[%d] = [%d, %d) outside 0 <= first < end <= nfft / 2 + 1 = %d", r, first, end, nfft / 2 + 1);
+        t.bin_lo = std::min(t.bin_lo, first); t.bin_hi = std::max(t.bin_hi, end);
+    }
+    for (int j = 0; j < W; ++j) if (!std::isfinite(window[j])) return fail(h, "ev_load_stoi: window[%d] is not finite", j);
+    for (int j = 0; j < 2 * nfft; ++j) if (!std::isfinite(twiddle[j])) return fail(h, "ev_load_stoi: twiddle[%d] is not finite", j);
+    StoiW& cur = h->stoi;
+    if (cur.loaded) {                       // replace: nothing in flight may still read the old tables
+        HIPCHK(h, hipDeviceSynchronize());
+        for (void* q : {(void*)cur.win, (void*)cur.tw, (void*)cur.bands}) {
+            auto it = std::find(h->owned.begin(), h->owned.end(), q);
+            if (it != h->owned.end()) { h->owned.erase(it); hipFree(q); }
+        }
+        cur = StoiW();
+    }
+    if (dev_upload(h, std::vector<double>(window, window + W), &t.win)) return 1;
+    if (dev_upload(h, std::vector<double>(twiddle, twiddle + 2 * (size_t)nfft), &t.tw)) return 1;
+    if (dev_upload(h, std::vector<int32_t>(bands, bands + 2 * (size_t)n_bands), &t.bands)) return 1;
+    t.loaded = true;
+    cur = t;
+    return 0;
+}
+
+int ev_stoi(ev_handle* h, const float* d_x, const float* d_y, const int32_t* d_len, int B, int L, double silence_ratio, double clip,
+            uint8_t* d_keep, double* d_tob, double* d_seg, double* d_score, int32_t* d_counts, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    const StoiW& w = h->stoi;
+    if (!w.loaded) return fail(h, "ev_stoi: tables not loaded (ev_load_stoi)");
+    if (B < 1 || B > 65535) return fail(h, "ev_stoi: B=%d outside 1 <= B <= 65535", B);
+    if (L < 1) return fail(h, "ev_stoi: L=%d must be at least 1", L);
+    if (!d_x || !d_y) return fail(h, "ev_stoi: d_x and d_y must be non-null");
+    if (!(silence_ratio > 0.0 && silence_ratio < 1.0)) return fail(h, "ev_stoi: silence_ratio=%g outside 0 < silence_ratio < 1", silence_ratio);
+    if (!(clip > 1.0) || !std::isfinite(clip)) return fail(h, "ev_stoi: clip=%g must be finite and greater than 1", clip);
+    if (!d_score || !d_counts) return fail(h, "ev_stoi: d_score and d_counts must be non-null");
+    h->stream = (hipStream_t)stream;
+    const int NF = L > w.W ? (L - w.W + w.H - 1) / w.H : 0, NM = std::max(NF - 1, 0), NSEG = std::max(NM - w.N + 1, 0);
+    const size_t n_e = (size_t)B * NF, n_tob = d_tob ? 0 : (size_t)B * 2 * w.n_bands * NM, n_seg = d_seg ? 0 : (size_t)B * NSEG * 2;
+    if (scratch_acquire(h, h->stoi_ws, (n_e + n_tob + n_seg) * sizeof(double) + n_e * sizeof(int32_t))) return 1;
+    double* E = (double*)h->stoi_ws.p;
+    double* tob = d_tob ? d_tob : E + n_e;
+    double* seg = d_seg ? d_seg : E + n_e + n_tob;
+    int32_t* idx = (int32_t*)(E + n_e + n_tob + n_seg);
+    StoiTables t{w.win, w.tw, w.bands, w.W, w.H, w.nfft, w.n_bands, w.N, w.bin_lo, w.bin_hi};
+    if (NF > 0) {
+        StoiEnergyParams pe{d_x, d_len, E, t, L, NF};
+        launch<stoi_energy_kernel>(h->device, dim3((unsigned)((NF + 63) / 64), (unsigned)B), dim3(64), 0, h->stream, pe);
+    }
+    StoiSelectParams ps{E, d_len, idx, d_keep, d_counts, t, L, NF, silence_ratio};
+    launch<stoi_select_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, ps);
+    if (NM > 0) {
+        StoiBandParams pb{d_x, d_y, idx, d_counts, tob, t, L, NF, NM};
+        const size_t smem = ((size_t)2 * w.nfft + 2 * w.W + 2 * (w.bin_hi - w.bin_lo)) * sizeof(double);
+        launch<stoi_band_kernel>(h->device, dim3((unsigned)NM, (unsigned)B), dim3(256), smem, h->stream, pb);
+    }
+    if (NSEG > 0) {
+        StoiSegParams pg{tob, d_counts, seg, t, NM, NSEG, clip};
+        const size_t smem = ((size_t)2 * w.n_bands * (w.N | 1) + 64) * sizeof(double);
+        launch<stoi_segment_kernel>(h->device, dim3((unsigned)NSEG, (unsigned)B), dim3(64), smem, h->stream, pg);
+    }
+    StoiMeanParams pm{seg, d_counts, d_score, NSEG};
+    launch<stoi_mean_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pm);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

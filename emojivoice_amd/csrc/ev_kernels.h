@@ -7603,3 +7603,282 @@ __global__ __launch_bounds__(256) void loud_gate_kernel(const LoudGateParams p) 
         p.counts[3 * b] = (int32_t)nb; p.counts[3 * b + 1] = n_abs; p.counts[3 * b + 2] = n;
     }
 }
+
+// ---------------------------------------------------------------------------
+// STOI / ESTOI (ev_stoi): short-time objective intelligibility of a processed row y against a clean row x (Taal et al. 2011; Jensen and
+// Taal 2016).  All float64; every kernel below compiles with floating-point contraction OFF (STOI_EXACT), so an fma is an fma only where fma()
+// is written and a product that feeds a sum is rounded first wherever `*` and `+` are written.  No atomics.  Five launches:
+//   1. stoi_energy_kernel:   one lane per (row, frame f): E[f] = fma chain over j of t_j^2, t_j = w[j] x[f H + j], ascending j, from 0;
+//   2. stoi_select_kernel:   one workgroup per row: the maximum of E (exact in any order), the mask E[f] > silence_ratio * max, and an
+//                            ordered compaction of the kept frames into idx (256 frames per round: one ballot and one popcount prefix per
+//                            wave, the four waves' totals through LDS, the running base carried from round to round); writes d_keep and
+//                            d_counts = {nf, nk, nseg};
+//   3. stoi_band_kernel:     one workgroup per (row, frame m) for BOTH signals (they share every twiddle read): z through LDS, one lane per
+//                            bin, four fma chains per lane (re and im of x and of y), then one lane per band;
+//   4. stoi_segment_kernel:  one wave per (row, segment): the N frames of every band through LDS; one lane per band for STOI, then one lane
+//                            per band and one lane per frame for the two normalisations of ESTOI;
+//   5. stoi_mean_kernel:     one workgroup per row: the two means in the fixed tree of loud_reduce.
+// Everything a row's outputs depend on hangs on the row's own samples below len: nothing depends on the batch, on L or on what lies behind.
+#define STOI_EXACT _Pragma("clang fp contract(off)")
+constexpr double STOI_EPS = 2.220446049250313e-16;                     // 2^-52
+
+struct StoiTables { const double* win; const double* tw; const int32_t* bands; int W, H, nfft, n_bands, N, bin_lo, bin_hi; };
+
+__device__ __forceinline__ int stoi_frames(const int32_t* len, int b, int L, int W, int H) {
+    int n = len ? len[b] : L;
+    if (n < 1 || n > L) n = 0;                                          // a bad row is an empty row (the ev_mas_align convention)
+    return n > W ? (n - W + H - 1) / H : 0;                             // range(0, n - W, H): a row of exactly W + k H samples has k frames
+}
+
+struct StoiEnergyParams { const float* x; const int32_t* len; double* E; StoiTables t; int L, NF; };
+
+__global__ __launch_bounds__(64) void stoi_energy_kernel(const StoiEnergyParams p) {
+    STOI_EXACT
+    const int b = blockIdx.y, f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= p.NF) return;
+    const int nf = stoi_frames(p.len, b, p.L, p.t.W, p.t.H);
+    double e = 0.0;
+    if (f < nf) {
+        const float* x = p.x + (size_t)b * p.L + (size_t)f * p.t.H;    // (f H + W - 1 < len: the frame lies inside the row)
+#pragma unroll 8
+        for (int j = 0; j < p.t.W; ++j) {                               // (W is a multiple of 64: the loads of eight steps go out together)
+            const double t = p.t.win[j] * (double)x[j];
+            e = fma(t, t, e);
+        }
+    }
+    p.E[(size_t)b * p.NF + f] = e;
+}
+
+struct StoiSelectParams { const double* E; const int32_t* len; int32_t* idx; uint8_t* keep; int32_t* counts; StoiTables t; int L, NF; double ratio; };
+
+__global__ __launch_bounds__(256) void stoi_select_kernel(const StoiSelectParams p) {
+    STOI_EXACT
+    __shared__ double red_d[4];
+    __shared__ int red_i[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nf = stoi_frames(p.len, b, p.L, p.t.W, p.t.H);
+    const double* E = p.E + (size_t)b * p.NF;
+    double mx = 0.0;                                                    // (energies are >= 0)
+    for (int f = tid; f < nf; f += 256) mx = fmax(mx, E[f]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+    if (lane == 0) red_d[wv] = mx;
+    __syncthreads();
+    mx = fmax(fmax(red_d[0], red_d[1]), fmax(red_d[2], red_d[3]));
+    const double thr = p.ratio * mx;
+    int base = 0;                                                       // kept frames before this round (uniform)
+    for (int f0 = 0; f0 < nf; f0 += 256) {
+        const int f = f0 + tid;
+        const bool k = f < nf && E[f] > thr;
+        const unsigned long long m = __ballot(k);
+        const int before = __popcll(m & ((1ull << lane) - 1ull));
+        __syncthreads();                                                // (the previous round's red_i is read)
+        if (lane == 0) red_i[wv] = __popcll(m);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wv; ++w) off += red_i[w];
+        if (k) p.idx[(size_t)b * p.NF + off + before] = f;
+        base += (red_i[0] + red_i[1]) + (red_i[2] + red_i[3]);
+        if (p.keep && f < p.NF) p.keep[(size_t)b * p.NF + f] = k ? 1 : 0;
+    }
+    if (p.keep) {                                                       // zeros from the last round's end up to NF (nf <= NF)
+        const int done = (nf + 255) / 256 * 256;
+        for (int f = done + tid; f < p.NF; f += 256) p.keep[(size_t)b * p.NF + f] = 0;
+    }
+    if (tid == 0) {
+        const int nm = base > 0 ? base - 1 : 0;
+        p.counts[3 * b] = nf; p.counts[3 * b + 1] = base; p.counts[3 * b + 2] = nm >= p.t.N ? nm - p.t.N + 1 : 0;
+    }
+}
+
+// Band spectra of frame m of the silence-removed signals, which never exist in memory: sample n = m H + j of s gathers from the kept frames
+// k = n / H - 1 and n / H (W = 2 H: exactly two overlap), i.e. from kept frames m - 1 and m for j < H and m and m + 1 for j >= H
+// (m + 1 <= nk - 1 always, m - 1 >= 0 from the second frame on).  s = t_lo + t_hi with t_k = w[n - k H] * x[idx[k] H + n - k H], each product
+// rounded, added in ascending k (the first frame's lower half has the one term); z[j] = w[j] * s.  Bin k of lane (k - bin_lo):
+// re = fma(z[j], cos[(j k) mod nfft], re), sm = fma(z[j], sin[(j k) mod nfft], sm) over ascending j from 0, im = -sm, p = fma(im, im, re * re).
+// Band: the p of its bins added in ascending k from 0, then sqrt (correctly rounded).  LDS (doubles): [twiddle 2 nfft][z 2 W][p 2 nbin].
+struct StoiBandParams { const float* x; const float* y; const int32_t* idx; const int32_t* counts; double* tob; StoiTables t; int L, NF, NM; };
+
+__global__ __launch_bounds__(256) void stoi_band_kernel(const StoiBandParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double stoi_smem[];
+    const int b = blockIdx.y, m = blockIdx.x, tid = threadIdx.x;
+    const int W = p.t.W, H = p.t.H, nfft = p.t.nfft, nb = p.t.n_bands;
+    const int nk = p.counts[3 * b + 1], nm = nk > 0 ? nk - 1 : 0;
+    double* tobx = p.tob + ((size_t)b * 2 * nb) * p.NM + m;             // band r of x at tobx[r NM], of y at tobx[(nb + r) NM]
+    if (m >= nm) {                                                      // (uniform) zeros past the row's own frames
+        for (int r = tid; r < 2 * nb; r += 256) tobx[(size_t)r * p.NM] = 0.0;
+        return;
+    }
+    double* tw = stoi_smem;                                             // (nfft, 2)
+    double* zx = tw + 2 * nfft;                                         // (W)
+    double* zy = zx + W;
+    double* px = zy + W;                                                // (bin_hi - bin_lo)
+    const int nbin = p.t.bin_hi - p.t.bin_lo;
+    double* py = px + nbin;
+    for (int i = tid; i < 2 * nfft; i += 256) tw[i] = p.t.tw[i];
+    const int32_t* idx = p.idx + (size_t)b * p.NF;
+    const float* xr = p.x + (size_t)b * p.L;
+    const float* yr = p.y + (size_t)b * p.L;
+    for (int j = tid; j < W; j += 256) {
+        const int k_hi = j < H ? m : m + 1, k_lo = k_hi - 1;            // the two kept frames that overlap at sample m H + j
+        const int o_hi = j < H ? j : j - H, o_lo = o_hi + H;            // the sample's offset inside each
+        const size_t a_hi = (size_t)idx[k_hi] * H + o_hi;
+        const double w_hi = p.t.win[o_hi];
+        double sx = w_hi * (double)xr[a_hi], sy = w_hi * (double)yr[a_hi];
+        if (k_lo >= 0) {
+            const size_t a_lo = (size_t)idx[k_lo] * H + o_lo;
+            const double w_lo = p.t.win[o_lo];
+            sx = w_lo * (double)xr[a_lo] + sx;
+            sy = w_lo * (double)yr[a_lo] + sy;
+        }
+        const double wj = p.t.win[j];
+        zx[j] = wj * sx;
+        zy[j] = wj * sy;
+    }
+    __syncthreads();
+    for (int q = tid; q < nbin; q += 256) {
+        const int k = p.t.bin_lo + q;                                   // k <= nfft / 2 < nfft
+        double rx = 0.0, ix = 0.0, ry = 0.0, iy = 0.0;
+        int ph = 0;                                                     // (j k) mod nfft
+        for (int j = 0; j < W; ++j) {
+            const double c = tw[2 * ph], s = tw[2 * ph + 1];
+            const double a = zx[j], d = zy[j];
+            rx = fma(a, c, rx); ix = fma(a, s, ix);
+            ry = fma(d, c, ry); iy = fma(d, s, iy);
+            ph += k;
+            if (ph >= nfft) ph -= nfft;
+        }
+        ix = -ix; iy = -iy;
+        px[q] = fma(ix, ix, rx * rx);
+        py[q] = fma(iy, iy, ry * ry);
+    }
+    __syncthreads();
+    for (int r = tid; r < 2 * nb; r += 256) {
+        const int band = r < nb ? r : r - nb;
+        const double* pp = r < nb ? px : py;
+        const int k0 = p.t.bands[2 * band] - p.t.bin_lo, k1 = p.t.bands[2 * band + 1] - p.t.bin_lo;
+        double acc = 0.0;
+        for (int k = k0; k < k1; ++k) acc = acc + pp[k];
+        tobx[(size_t)r * p.NM] = sqrt(acc);
+    }
+}
+
+// One wave per (row, segment q): frames [q, q + N) of every band of both signals in LDS rows of NP = N | 1 doubles (an odd stride: the lanes
+// that each walk one band's row hit different banks).  EVERY sum below runs in ascending index from 0, `a * a` terms as fma(a, a, sum).
+// STOI, lane = band r: nx = sqrt(sum X^2), ny = sqrt(sum Y^2), a = nx / (ny + EPS); Y'[i] = min(a * Y[i], clip * X[i]); mx = (sum X) / N,
+//   my = (sum Y') / N; dx = sqrt(sum (X - mx)^2) + EPS, dy = sqrt(sum (Y' - my)^2) + EPS; rho = sum of ((X - mx) / dx) * ((Y' - my) / dy).
+//   d_seg[q][0] = (sum of rho over the bands, ascending) / n_bands.
+// ESTOI, X and Y alike, in place: lane = band: mean over the N frames (sum / N) removed, then divided by (sqrt(sum of squares) + EPS);
+//   lane = frame: mean over the bands (sum / n_bands) removed, then divided by (sqrt(sum of squares) + EPS); c_i = fma chain over the bands of
+//   X[r][i] * Y[r][i]; d_seg[q][1] = (sum of c_i over the frames, ascending) / N.
+struct StoiSegParams { const double* tob; const int32_t* counts; double* seg; StoiTables t; int NM, NSEG; double clip; };
+
+__global__ __launch_bounds__(64) void stoi_segment_kernel(const StoiSegParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double stoi_smem[];
+    const int b = blockIdx.y, q = blockIdx.x, lane = threadIdx.x;
+    const int N = p.t.N, nb = p.t.n_bands, NP = N | 1;
+    const int nseg = p.counts[3 * b + 2];
+    double* out = p.seg + ((size_t)b * p.NSEG + q) * 2;
+    if (q >= nseg) {                                                    // (uniform)
+        if (lane < 2) out[lane] = 0.0;
+        return;
+    }
+    double* X = stoi_smem;                                              // (nb, NP)
+    double* Y = X + nb * NP;
+    double* red = Y + nb * NP;                                          // (64)
+    const double* src = p.tob + ((size_t)b * 2 * nb) * p.NM + q;
+    for (int r = 0; r < nb; ++r)
+        if (lane < N) { X[r * NP + lane] = src[(size_t)r * p.NM + lane]; Y[r * NP + lane] = src[(size_t)(nb + r) * p.NM + lane]; }
+    __syncthreads();
+    const double dN = (double)N, dB = (double)nb;
+    double rho = 0.0;
+    if (lane < nb) {
+        const double* x = X + lane * NP;
+        const double* y = Y + lane * NP;
+        double sxx = 0.0, syy = 0.0;
+        for (int i = 0; i < N; ++i) { sxx = fma(x[i], x[i], sxx); syy = fma(y[i], y[i], syy); }
+        const double a = sqrt(sxx) / (sqrt(syy) + STOI_EPS);
+        double sx = 0.0, sy = 0.0;
+        for (int i = 0; i < N; ++i) { sx = sx + x[i]; sy = sy + fmin(a * y[i], p.clip * x[i]); }
+        const double mx = sx / dN, my = sy / dN;
+        sxx = 0.0; syy = 0.0;
+        for (int i = 0; i < N; ++i) {
+            const double u = x[i] - mx, v = fmin(a * y[i], p.clip * x[i]) - my;
+            sxx = fma(u, u, sxx); syy = fma(v, v, syy);
+        }
+        const double dx = sqrt(sxx) + STOI_EPS, dy = sqrt(syy) + STOI_EPS;
+        for (int i = 0; i < N; ++i) {
+            const double u = (x[i] - mx) / dx, v = (fmin(a * y[i], p.clip * x[i]) - my) / dy;
+            rho = rho + u * v;
+        }
+    }
+    red[lane] = rho;
+    __syncthreads();
+    if (lane == 0) {
+        double s = 0.0;
+        for (int r = 0; r < nb; ++r) s = s + red[r];
+        out[0] = s / dB;
+    }
+    __syncthreads();                                                    // (STOI has read X and Y; ESTOI rewrites them)
+    if (lane < nb) {
+#pragma unroll
+        for (int sig = 0; sig < 2; ++sig) {
+            double* v = (sig ? Y : X) + lane * NP;
+            double s = 0.0;
+            for (int i = 0; i < N; ++i) s = s + v[i];
+            const double mu = s / dN;
+            double ss = 0.0;
+            for (int i = 0; i < N; ++i) { const double u = v[i] - mu; ss = fma(u, u, ss); }
+            const double d = sqrt(ss) + STOI_EPS;
+            for (int i = 0; i < N; ++i) v[i] = (v[i] - mu) / d;
+        }
+    }
+    __syncthreads();
+    double c = 0.0;
+    if (lane < N) {
+#pragma unroll
+        for (int sig = 0; sig < 2; ++sig) {
+            double* v = (sig ? Y : X) + lane;
+            double s = 0.0;
+            for (int r = 0; r < nb; ++r) s = s + v[r * NP];
+            const double mu = s / dB;
+            double ss = 0.0;
+            for (int r = 0; r < nb; ++r) { const double u = v[r * NP] - mu; ss = fma(u, u, ss); }
+            const double d = sqrt(ss) + STOI_EPS;
+            for (int r = 0; r < nb; ++r) v[r * NP] = (v[r * NP] - mu) / d;
+        }
+        for (int r = 0; r < nb; ++r) c = fma(X[r * NP + lane], Y[r * NP + lane], c);
+    }
+    red[lane] = c;
+    __syncthreads();
+    if (lane == 0) {
+        double s = 0.0;
+        for (int i = 0; i < N; ++i) s = s + red[i];
+        out[1] = s / dN;
+    }
+}
+
+// d_score[b] = {mean of d_seg[., 0], mean of d_seg[., 1]} over the row's nseg segments, 0 without a segment: thread t of 256 adds its segments
+// t, t + 256, ... in ascending order, the 64 partials of a wave go through the shuffle tree (offsets 32 .. 1), the four waves' sums are added
+// as (w0 + w1) + (w2 + w3) — the tree of ev_loudness — and one division by nseg follows.
+struct StoiMeanParams { const double* seg; const int32_t* counts; double* score; int NSEG; };
+
+__global__ __launch_bounds__(256) void stoi_mean_kernel(const StoiMeanParams p) {
+    STOI_EXACT
+    __shared__ double red[2][4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int nseg = p.counts[3 * b + 2];
+    const double* seg = p.seg + (size_t)b * p.NSEG * 2;
+    double s0 = 0.0, s1 = 0.0;
+    for (int q = tid; q < nseg; q += 256) { s0 = s0 + seg[2 * q]; s1 = s1 + seg[2 * q + 1]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s0 = s0 + __shfl_down(s0, o); s1 = s1 + __shfl_down(s1, o); }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = s0; red[1][tid >> 6] = s1; }
+    __syncthreads();
+    if (tid < 2) {
+        const double s = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+        p.score[2 * b + tid] = nseg > 0 ? s / (double)nseg : 0.0;
+    }
+}

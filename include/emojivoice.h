@@ -37,6 +37,8 @@
  *   ev_pitch_yin       <- no counterpart: the reference never measures pitch; librosa.yin is the model
  *   ev_dtw             <- no counterpart: the reference never compares what it says with what was recorded; MCD-DTW evaluation is the model
  *   ev_loudness        <- no counterpart; ITU-R BS.1770-4 is the model
+ *   ev_load_stoi       <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
+ *   ev_stoi            <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_pyin_observe    <- no counterpart; librosa.pyin is the model
  *   ev_pyin_decode     <- no counterpart; librosa.pyin is the model
  *
@@ -76,7 +78,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2 (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -496,6 +498,67 @@ int ev_loudness(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_le
                 int sub_len /* S: samples per 100 ms */, const double *coef /* HOST (10) */, double abs_gate /* mean square */,
                 double *d_sub /* (B, NS) or NULL */, double *d_block /* (B, NB) or NULL */,
                 double *d_gated /* (B, 2) */, int32_t *d_counts /* (B, 3) */, void *stream);
+
+/* STOI and ESTOI on the device: short-time objective intelligibility of a processed row y against the clean, sample-aligned row x (Taal,
+ * Hendriks, Heusdens and Jensen, IEEE TASL 19(7), 2011) and its extended form (Jensen and Taal, IEEE/ACM TASLP 24(11), 2016), for rows already
+ * at the measure's rate (10 kHz in the papers).  ev_load_stoi stores the tables; ev_stoi measures.  Everything is float64 (the samples are
+ * widened), in ONE fixed order, stated below; the kernels are compiled with floating-point contraction off, so "fma" below is an fma and every
+ * other product or sum is rounded on its own.  No atomics; ev_set_arithmetic does not reach it.
+ * ev_load_stoi: HOST tables, copied to the device.  window (W) doubles w; twiddle (nfft, 2) doubles {cos, sin}(2 pi n / nfft); bands (n_bands, 2)
+ *   int32 {first bin, end bin (exclusive)}; H the hop, N the frames per segment.  Limits, each violation failing with a message that names it:
+ *   H a multiple of 32 with 32 <= H <= 256; W = 2 H (the overlap-add below has exactly two terms); W <= nfft <= 1024; 1 <= n_bands <= 32;
+ *   0 <= first < end <= nfft / 2 + 1 for every band; 2 <= N <= 64; finite window and twiddle; non-NULL tables.  Loading again replaces the
+ *   tables; it waits for the device first.  ev_stoi without loaded tables fails with a message.
+ * Sizes, with frames(n) = n > W ? ceil((n - W) / H) : 0 (the model frames with range(0, len - W, H): a row of exactly W + k H samples has k
+ *   frames, not k + 1): NF = frames(L), NM = max(NF - 1, 0), NSEG = max(NM - N + 1, 0); a row of len samples has nf = frames(len).
+ *   d_len == NULL: every row is L long.  EPS = 2^-52.
+ * Definition, per row:
+ *   energies  E[f] = the fma chain e = fma(t_j, t_j, e) over ascending j from 0 with t_j = w[j] * x[f H + j], for f < nf: the clean signal only
+ *   mask      frame f is kept iff E[f] > silence_ratio * max_f E[f]: one multiply, strict, in the power domain (the caller passes 10^(-40/10)).
+ *             This is the model's 20 log10(norm + EPS) test without the logarithms; the two differ only for an all-zero clean row, of which the
+ *             device keeps NO frame (the model would keep all of them).  idx[k] = the k-th kept frame, ascending; nk their number.
+ *             d_keep (B, NF) uint8 or NULL: 1 for a kept frame, 0 otherwise and for f >= nf
+ *   signals   s[n] = sum over k in {n / H - 1, n / H} with 0 <= k < nk of w[n - k H] * x[idx[k] H + n - k H], every product rounded, added in
+ *             ascending k, for 0 <= n < (nk - 1) H + W; the same idx for y.  s is never stored: frame m of s gathers from kept frames
+ *             m - 1, m and m + 1 of the input
+ *   spectra   nm = max(nk - 1, 0) frames; z_m[j] = w[j] * s[m H + j]; for every bin k from the lowest first to the highest end of the bands:
+ *             re_k = fma(z_m[j], cos[(j k) mod nfft], re_k) and sm_k = fma(z_m[j], sin[(j k) mod nfft], sm_k) over ascending j from 0,
+ *             im_k = -sm_k, p_k = fma(im_k, im_k, re_k * re_k); tob[band, m] = sqrt(p_k added over the band in ascending k from 0), the square
+ *             root correctly rounded.  d_tob (B, 2, n_bands, NM) or NULL: [b][0] of x, [b][1] of y; zeros at m >= nm
+ *   segments  nseg = max(nm - N + 1, 0); segment q covers frames [q, q + N); X, Y the N values of one band.  Every sum runs in ascending index
+ *             from 0, sums of squares as fma(a, a, sum).
+ *             STOI, per band: a = sqrt(sum X^2) / (sqrt(sum Y^2) + EPS); Y' = min(a * Y, clip * X) element-wise (the caller passes
+ *             clip = 1 + 10^(15/20)); mx = (sum X) / N, my = (sum Y') / N; dx = sqrt(sum (X - mx)^2) + EPS, dy alike of Y' - my;
+ *             rho = sum of ((X - mx) / dx) * ((Y' - my) / dy).  d_seg[q][0] = (sum of rho over the bands in ascending order) / n_bands.
+ *             ESTOI, X and Y alike: every band's mean over the N frames ((sum) / N) removed, then divided by (sqrt(sum of squares) + EPS); then
+ *             every frame's mean over the bands ((sum) / n_bands) removed, then divided by (sqrt(sum of squares) + EPS); c_i = fma(X[r][i],
+ *             Y[r][i], c_i) over the bands r; d_seg[q][1] = (sum of c_i over the frames i) / N.
+ *             d_seg (B, NSEG, 2) or NULL; zeros at q >= nseg
+ *   scores    d_score (B, 2) = {STOI, ESTOI}: the mean of each column of d_seg over the nseg segments, 0 when nseg = 0.  Thread t of 256 adds its
+ *             segments t, t + 256, ... in ascending order, the 64 partials of a wave go through one shuffle tree (offsets 32 .. 1), the four
+ *             waves' sums are added as (w0 + w1) + (w2 + w3) (the tree of ev_loudness); one division by nseg follows.
+ *   d_counts  (B, 3) int32: {nf, nk, nseg}
+ * A row with len < 1 or len > L is no error and no out-of-bounds access: all its outputs are zeros (the ev_mas_align convention); so are those
+ * of an all-zero clean row, except nf.  Nothing at or behind len is read, and nothing depends on the batch or on L: a row alone, inside a batch,
+ * or as the d_len prefix of a longer padded row with anything behind it, and a second call, give the same bits in every output.
+ * Limits of ev_stoi, each violation failing with a message that names it and writing nothing: 1 <= B <= 65535; L >= 1; 0 < silence_ratio < 1;
+ * clip > 1; d_x, d_y, d_score and d_counts non-NULL.
+ * Kernels (five launches on `stream`, fewer where NF, NM or NSEG is 0; no host wait, no copy): (1) one lane per (row, frame): E; (2) one workgroup per
+ *   row: the maximum of E — taken here, not in (1), since a maximum is exact in any order and this needs no atomics — the mask, and idx by
+ *   a ballot and popcount prefix per wave, 256 frames per round with the base carried across rounds; d_keep and d_counts; (3) one workgroup per
+ *   (row, frame m) for BOTH signals, which share every twiddle read: z through LDS, one lane per bin, then one lane per band; (4) one wave per
+ *   (row, segment) with the segment in LDS: one lane per band for STOI, one lane per band and then one lane per frame for ESTOI; (5) one
+ *   workgroup per row: the two means.  The DFT is a vector float64 fma chain, not the matrix core.
+ * Scratch: B x NF doubles of E and B x NF int32 of idx, plus B x 2 x n_bands x NM doubles when d_tob is NULL and B x NSEG x 2 when d_seg is
+ *   NULL, in an arena of the handle that grows on demand like the loudness arena and counts in ev_alloc_count: a second call at the same
+ *   shape allocates nothing; ev_reserve does not cover it.  The call is capturable once the arena has its size. */
+int ev_load_stoi(ev_handle *h, const double *window /* HOST (W) */, const double *twiddle /* HOST (nfft, 2): cos, sin of 2 pi n / nfft */,
+                 const int32_t *bands /* HOST (n_bands, 2): first bin, end bin (exclusive) */,
+                 int W, int H, int nfft, int n_bands, int N /* frames per segment */);
+int ev_stoi(ev_handle *h, const float *d_x /* (B, L) clean */, const float *d_y /* (B, L) processed */, const int32_t *d_len /* (B) or NULL */,
+            int B, int L, double silence_ratio /* 10^(-40/10) */, double clip /* 1 + 10^(15/20) */,
+            uint8_t *d_keep /* (B, NF) or NULL */, double *d_tob /* (B, 2, n_bands, NM) or NULL */, double *d_seg /* (B, NSEG, 2) or NULL */,
+            double *d_score /* (B, 2): STOI, ESTOI */, int32_t *d_counts /* (B, 3): nf, nk, nseg */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

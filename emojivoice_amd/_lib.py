@@ -34,6 +34,7 @@ EXPORTS = [
     "ev_pyin_observe", "ev_pyin_decode",
     "ev_op_attention2", "ev_op_attn_out2",
     "ev_load_stoi", "ev_stoi",
+    "ev_load_stft_dist", "ev_stft_dist",
 ]
 
 
@@ -158,6 +159,8 @@ def load_library() -> C.CDLL:
     lib.ev_pyin_decode.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, f64, f64, vp, vp, vp, vp]
     lib.ev_load_stoi.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32]
     lib.ev_stoi.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
+    lib.ev_load_stft_dist.argtypes = [vp, vp, vp, i32, i32, i32]
+    lib.ev_stft_dist.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -515,6 +518,40 @@ class Engine:
         self._check(self.lib.ev_stoi(self.h, x.data_ptr(), y.data_ptr(), ptr(ln), B, L, float(silence_ratio), float(clip), ptr(keep), ptr(tob), ptr(seg),
                                      score.data_ptr(), counts.data_ptr(), _stream_ptr()), "ev_stoi")
         return keep, tob, seg, score, counts
+
+    def load_stft_dist(self, window, twiddle, H: int, nfft: int) -> None:
+        """One resolution of ``stft_dist`` (ev_load_stft_dist), the tables on the host: ``window`` (W,) float64, ``twiddle`` (nfft, 2) float64
+        {cos, sin}(2 pi n / nfft); ``H`` the hop.  The handle builds the dense windowed DFT basis (W, nfft / 2 + 1) on the device."""
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float64).reshape(-1))
+        tw = np.ascontiguousarray(np.asarray(twiddle, dtype=np.float64).reshape(-1, 2))
+        if tw.shape[0] != int(nfft):
+            raise ValueError(f"load_stft_dist: {nfft} twiddles expected, got {tw.shape[0]}")
+        self._check(self.lib.ev_load_stft_dist(self.h, w.ctypes.data, tw.ctypes.data, int(w.shape[0]), int(H), int(nfft)), "ev_load_stft_dist")
+        self.stft_dist_geometry = (int(w.shape[0]), int(H), int(nfft))
+
+    def stft_dist(self, x, y, lengths, power_floor: float, want_frames: bool = False):
+        """The STFT-distance sums of every processed row of ``y`` against the reference row of ``x``, both (B, L), at the loaded resolution
+        (ev_stft_dist, after load_stft_dist): (frame (B, NF, 4) float64 or None: per frame {sum (my - mx)^2, sum mx^2, sum |ly - lx|,
+        sum (ly - lx)^2} over the bins, sums (B, 4) float64: {sum_f [0], sum_f [1], sum_f [2], sum_f sqrt([3] / NB)}, counts (B,) int32: the
+        row's frames) on the device.  ``lengths`` (B,): samples per row (None: L)."""
+        x, y = self._f32(x), self._f32(y)
+        if x.dim() != 2 or y.shape != x.shape:
+            raise ValueError(f"stft_dist: x and y must be (B, L) alike, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+        if not hasattr(self, "stft_dist_geometry"):
+            raise EvLibraryError("stft_dist: tables not loaded (load_stft_dist)")
+        B, L = x.shape
+        _, H, nfft = self.stft_dist_geometry
+        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"stft_dist: {B} lengths expected, got {ln.numel()}")
+        NF = 1 + L // H if L > nfft // 2 else 0
+        frame = torch.empty((B, NF, 4), dtype=torch.float64, device=x.device) if want_frames else None
+        sums = torch.empty((B, 4), dtype=torch.float64, device=x.device)
+        counts = torch.empty((B,), dtype=torch.int32, device=x.device)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._check(self.lib.ev_stft_dist(self.h, x.data_ptr(), y.data_ptr(), ptr(ln), B, L, float(power_floor), ptr(frame), sums.data_ptr(),
+                                          counts.data_ptr(), _stream_ptr()), "ev_stft_dist")
+        return frame, sums, counts
 
     def pyin_observe(self, x, lengths, frame_length: int, hop_length: int, tau_min: int, tau_max: int, sr: float, fmin: float,
                      bins_per_octave: int, n_bins: int, w, boltzmann: float = 2.0, no_trough_prob: float = 0.01, out=None):

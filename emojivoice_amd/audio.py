@@ -42,6 +42,11 @@ And a processed waveform against the sample-aligned recording it was made from (
 Taal 2016 — what copy synthesis through a vocoder costs in intelligibility):
 
     r = stoi(recording, synthesis)                            # {"stoi" (B,), "estoi" (B,), "segments" (B, NSEG, 2), "counts" (B, 3), "keep" (B, NF)}
+
+And their spectral-magnitude distance (``ev_stft_dist``: the multi-resolution STFT distance of Yamamoto et al. 2020 and the log-spectral
+distance, a float64 DFT on the matrix cores):
+
+    r = stft_distance(recording, synthesis)                   # {"mstft" (B,), "sc" (B,), "log_mag" (B,), "lsd_db" (B,), "per_resolution", "frames" (B, 3)}
 """
 from __future__ import annotations
 
@@ -785,3 +790,81 @@ def stoi(reference, degraded, sr: int = 22050, lengths=None, rows: Optional[Call
     scored = (torch.as_tensor(counts)[:, 2] > 0).to(score.device)
     nan = torch.full_like(score[:, 0], float("nan"))
     return {"stoi": torch.where(scored, score[:, 0], nan), "estoi": torch.where(scored, score[:, 1], nan), "segments": seg, "counts": counts, "keep": keep}
+
+
+# ---- spectral-magnitude distance: multi-resolution STFT (Yamamoto, Song, Kim 2020) and log-spectral distance ---------------------------------------
+MSTFT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))   # (n_fft, hop, win): the published defaults
+MSTFT_POWER_FLOOR = 1e-7                                                    # the clamp of |X|^2 before the root and the logarithm
+
+
+def stft_dist_window(W: int) -> np.ndarray:
+    """The periodic Hann window of W points, float64 (``torch.hann_window(W)``): 0.5 - 0.5 cos(2 pi n / W)."""
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(int(W), dtype=np.float64) / int(W))
+
+
+def _stft_dist_engine(device: torch.device, resolution) -> Engine:
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    nfft, hop, win = (int(v) for v in resolution)
+    key = (idx, "stft_dist", nfft, hop, win)
+    eng = _rs_engines.get(key)
+    if eng is None:
+        eng = Engine(idx)
+        eng.load_stft_dist(stft_dist_window(win), stoi_twiddle(nfft), hop, nfft)
+        _rs_engines[key] = eng
+    return eng
+
+
+def _device_stft_dist_rows(x, y, lengths, resolution):
+    _, sums, counts = _stft_dist_engine(x.device, resolution).stft_dist(x, y, lengths, MSTFT_POWER_FLOOR)
+    return sums, counts
+
+
+@torch.inference_mode()
+def stft_distance(reference, degraded, lengths=None, resolutions=MSTFT_RESOLUTIONS, rows: Optional[Callable] = None):
+    """The multi-resolution STFT distance (spectral convergence + log-magnitude L1; Yamamoto et al. 2020, the "M-STFT" of BigVGAN) and the
+    log-spectral distance of ``degraded`` against the SAMPLE-ALIGNED ``reference``, on the device (``ev_stft_dist``; no torch fallback): both
+    1-D or (B, L) on the GPU at their own rate (nothing is resampled), ``lengths`` (B,) samples per row or None.  ``resolutions``: (n_fft,
+    hop, win) triples; every one is ``torch.stft`` with a periodic Hann window, center=True and reflect padding, the power clamped at 1e-7,
+    in float64.  Per resolution and row: sc = ||my - mx||_F / ||mx||_F, log_mag = mean |log my - log mx|, lsd_db = the mean over the frames
+    of the RMS over the bins of the log-power difference in dB.  -> {"sc", "log_mag", "lsd_db": (B,) float64, the mean over the resolutions;
+    "mstft" (B,) float64: the mean over the resolutions of sc + log_mag; "per_resolution": a list of {"n_fft", "hop", "win", "sc", "log_mag",
+    "lsd_db"}; "frames" (B, R) int32}; a 1-D input gives B = 1.  A row without a frame at some resolution (not more than n_fft / 2 samples)
+    gets NaN at that resolution and in every mean.  ``rows``: the per-resolution measurement, (x, y, lengths, resolution) -> (sums (B, 4),
+    counts (B,)) in ev_stft_dist's terms — the device call unless given."""
+    if not torch.is_tensor(reference) or not torch.is_tensor(degraded) or reference.dim() not in (1, 2) or reference.shape != degraded.shape:
+        raise ValueError("stft_distance: reference and degraded must be tensors of one shape, 1-D or (B, L)")
+    if reference.shape[-1] < 1:
+        raise ValueError("stft_distance: the signals are empty")
+    res = [tuple(int(v) for v in r) for r in resolutions]
+    if not res or any(len(r) != 3 for r in res):
+        raise ValueError("stft_distance: resolutions must be a non-empty list of (n_fft, hop, win)")
+    if rows is None and not (reference.is_cuda and degraded.is_cuda):
+        raise EvLibraryError("stft_distance runs on a ROCm GPU only (no CPU fallback): move the signals to the GPU")
+    x = reference.unsqueeze(0) if reference.dim() == 1 else reference
+    y = degraded.unsqueeze(0) if degraded.dim() == 1 else degraded
+    ln = None
+    if lengths is not None and reference.dim() == 2:
+        ln = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
+        if ln.numel() != x.shape[0]:
+            raise ValueError(f"stft_distance: {x.shape[0]} lengths expected, got {ln.numel()}")
+    per, frames = [], []
+    for nfft, hop, win in res:
+        sums, counts = (rows or _device_stft_dist_rows)(x, y, ln, (nfft, hop, win))
+        s = torch.as_tensor(sums, dtype=torch.float64)
+        nf = torch.as_tensor(counts).to(s.device)
+        has = nf > 0
+        n = nf.clamp(min=1).to(torch.float64)
+        nan = torch.full_like(s[:, 0], float("nan"))
+        per.append({"n_fft": nfft, "hop": hop, "win": win,
+                    "sc": torch.where(has, torch.sqrt(s[:, 0] / s[:, 1].clamp(min=1e-300)), nan),
+                    "log_mag": torch.where(has, 0.5 * s[:, 2] / (n * (nfft // 2 + 1)), nan),
+                    "lsd_db": torch.where(has, (10.0 / math.log(10.0)) * s[:, 3] / n, nan)})
+        frames.append(nf.to(torch.int32))
+    def mean(vals):                                                      # added in the order of ``resolutions``, element by element: a row's
+        acc = vals[0]                                                    # figures do not depend on the batch it is measured in
+        for v in vals[1:]:
+            acc = acc + v
+        return acc / float(len(vals))
+
+    return {"sc": mean([p["sc"] for p in per]), "log_mag": mean([p["log_mag"] for p in per]), "lsd_db": mean([p["lsd_db"] for p in per]),
+            "mstft": mean([p["sc"] + p["log_mag"] for p in per]), "per_resolution": per, "frames": torch.stack(frames, dim=1)}

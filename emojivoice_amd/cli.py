@@ -18,6 +18,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
     python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000          # clean/filelist.txt.vocoder.json: STOI / ESTOI, mel L1 and loudness shift of copy synthesis
+    python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000 --spectral_distance   # + multi-resolution STFT distance and log-spectral distance
 
 The wavs of --mel_from_wav, --align_wav and --data_statistics may have any sample rate (the reference's recorder writes 44.1 kHz,
 record_audio.py:31): they are resampled to the analysis rate on the device (emojivoice_amd.audio.resample).
@@ -62,6 +63,8 @@ def write_wav_pcm16(path, wav: np.ndarray, sr: int = 22050):
 
 
 def validate_args(args):
+    if getattr(args, "spectral_distance", False):
+        assert getattr(args, "vocoder_report", None), "--spectral_distance is an option of --vocoder_report"
     if args.sample_rate is not None:
         assert args.sample_rate > 0, "--sample_rate must be positive"
     if args.prepare_dataset:
@@ -521,13 +524,18 @@ def loudness_report(args, device):
 VOCODER_REPORT_KEYS = ("stoi", "estoi", "mel_l1", "lufs_shift")
 
 
-def vocoder_summary(files):
-    """{"files", "unscored": the paths without a STOI score, and per key of VOCODER_REPORT_KEYS {"mean", "min"} over the files that have the
-    figure (null where none has)} of a list of --vocoder_report file entries."""
+VOCODER_DISTANCE_KEYS = ("mstft", "sc", "log_mag", "lsd_db")     # --spectral_distance: lower is better
+
+
+def vocoder_summary(files, keys=VOCODER_REPORT_KEYS):
+    """{"files", "unscored": the paths without a STOI score, and per key of ``keys`` {"mean", "min"} over the files that have the figure
+    (null where none has) — {"mean", "max"} for the keys of VOCODER_DISTANCE_KEYS, where lower is better} of a list of --vocoder_report
+    file entries."""
     out = {"files": len(files), "unscored": [f["path"] for f in files if f["stoi"] is None]}
-    for k in VOCODER_REPORT_KEYS:
+    for k in keys:
         v = [f[k] for f in files if f[k] is not None]
-        out[k] = {"mean": math.fsum(v) / len(v) if v else None, "min": min(v) if v else None}
+        worst, pick = ("max", max) if k in VOCODER_DISTANCE_KEYS else ("min", min)
+        out[k] = {"mean": math.fsum(v) / len(v) if v else None, worst: pick(v) if v else None}
     return out
 
 
@@ -539,7 +547,10 @@ def vocoder_report(args, device):
     synthesis is sample-aligned with the recording.  FILELIST.vocoder.json receives per file "stoi" and "estoi" (audio.stoi: the synthesis
     against the recording; null for a file too short to score), "mel_l1" (audio.mel_reconstruction_error), "lufs_shift" (the integrated
     loudness, audio.loudness, of the synthesis minus that of the recording; null where either has none) and "seconds"; per speaker and
-    under "overall" the mean and the minimum of each and the files without a score."""
+    under "overall" the mean and the minimum of each and the files without a score.  With --spectral_distance every file also gets "mstft",
+    "sc", "log_mag" and "lsd_db" (audio.stft_distance at the config's rate: the multi-resolution STFT distance, its two terms and the
+    log-spectral distance in dB; null for a file too short for the widest window), the summaries their mean and maximum, and the report
+    "stft_resolutions"."""
     from . import audio
     from . import weights as W
     from .hifigan import AttrDict, Generator
@@ -556,6 +567,8 @@ def vocoder_report(args, device):
     vocoder.remove_weight_norm()
     loud_ok = sr % 10 == 0 and sr >= 8000                                # the rates audio.k_weighting designs a filter for
     value = lambda v: float(v) if math.isfinite(float(v)) else None
+    dist_keys = VOCODER_DISTANCE_KEYS if getattr(args, "spectral_distance", False) else ()
+    keys = VOCODER_REPORT_KEYS + dist_keys
     files = []
     for b0 in range(0, len(entries), args.batch_size):
         chunk = entries[b0:b0 + args.batch_size]
@@ -580,12 +593,20 @@ def vocoder_report(args, device):
             for i, r in enumerate(rows):
                 fig[r] = {"seconds": lens[i] / float(sr), "stoi": value(st[i]), "estoi": value(es[i]), "mel_l1": value(l1[i]),
                           "lufs_shift": value(shift[i]) if shift is not None else None}
+            if dist_keys:
+                dist = audio.stft_distance(rec, syn, lengths=lens)
+                for k in dist_keys:
+                    col = dist[k].cpu()
+                    for i, r in enumerate(rows):
+                        fig[r][k] = value(col[i])
         for r, (wav, spk, _) in enumerate(chunk):
             files.append({"path": wav, "speaker": spk if spk is not None else "0",
-                          **fig.get(r, {"seconds": None, "stoi": None, "estoi": None, "mel_l1": None, "lufs_shift": None})})
-    speakers = {spk: vocoder_summary([f for f in files if f["speaker"] == spk]) for spk in dict.fromkeys(f["speaker"] for f in files)}
+                          **fig.get(r, {"seconds": None, **{k: None for k in keys}})})
+    speakers = {spk: vocoder_summary([f for f in files if f["speaker"] == spk], keys) for spk in dict.fromkeys(f["speaker"] for f in files)}
     rep = {"sample_rate": sr, "vocoder_config": args.vocoder_config, "stoi_sample_rate": audio.STOI_SR, "files": files, "speakers": speakers,
-           "overall": vocoder_summary(files)}
+           "overall": vocoder_summary(files, keys)}
+    if dist_keys:
+        rep["stft_resolutions"] = [list(r) for r in audio.MSTFT_RESOLUTIONS]
     out_path = f"{args.vocoder_report}.vocoder.json"
     with open(out_path, "w") as f:
         json.dump(rep, f, indent=1)
@@ -594,6 +615,7 @@ def vocoder_report(args, device):
         score = "no file long enough to score" if v["stoi"]["mean"] is None else (
             f"STOI {v['stoi']['mean']:.3f} mean, {v['stoi']['min']:.3f} min, ESTOI {v['estoi']['mean']:.3f} mean, mel L1 {v['mel_l1']['mean']:.3f}"
             + ("" if v["lufs_shift"]["mean"] is None else f", loudness {v['lufs_shift']['mean']:+.2f} LU")
+            + ("" if not dist_keys or v["mstft"]["mean"] is None else f", M-STFT {v['mstft']['mean']:.3f} mean, LSD {v['lsd_db']['mean']:.2f} dB")
             + (f", {len(v['unscored'])} without a score" if v["unscored"] else ""))
         print(f"[i] speaker {k}: {v['files']} files, {score}")
     print(f"[+] Vocoder report saved: {Path(out_path).resolve()}")
@@ -766,6 +788,9 @@ def cli(argv=None):
     p.add_argument("--vocoder_report", type=str, default=None, help="vocoder evaluation instead of synthesis: a filelist 'path|spk|text' -> FILELIST.vocoder.json: "
                    "STOI / ESTOI of copy synthesis against the recording, mel L1, loudness shift and seconds per file; mean and minimum per speaker and "
                    "overall (with --vocoder_path or --synthetic, --vocoder_config; on the device, --batch_size files per batch)")
+    p.add_argument("--spectral_distance", action="store_true", help="--vocoder_report: add the multi-resolution STFT distance (\"mstft\": spectral convergence "
+                   "\"sc\" + log-magnitude L1 \"log_mag\" at 1024/120/600, 2048/240/1200 and 512/50/240) and the log-spectral distance \"lsd_db\" per file, "
+                   "with mean and maximum per speaker and overall")
     args = validate_args(p.parse_args(argv))
     if args.vocoder_report:
         if not torch.cuda.is_available():

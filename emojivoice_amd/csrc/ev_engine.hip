@@ -124,6 +124,8 @@ struct MelBasisW { bool loaded = false; int n_mels = 0, nb = 0; int* span = null
 struct ResamplerW { bool loaded = false; int up = 0, down = 0, n_taps = 0, W = 0, Wp = 0, tab_floats = 0; float* table = nullptr; };
 // Tables of ev_stoi: the analysis window (W), the twiddles (nfft, 2) and the bands (n_bands, 2), float64 / int32 on the device
 struct StoiW { bool loaded = false; int W = 0, H = 0, nfft = 0, n_bands = 0, N = 0, bin_lo = 0, bin_hi = 0; double* win = nullptr; double* tw = nullptr; int32_t* bands = nullptr; };
+// Basis of ev_stft_dist: (W, NB) pairs {w[j] cos, w[j] sin}(2 pi (j + off) k / nfft), float64 on the device; skew: the LDS pad per hop (ev_kernels.h)
+struct StftDistW { bool loaded = false; int W = 0, H = 0, nfft = 0, NB = 0, skew = 0; double2* basis = nullptr; };
 
 }  // namespace
 
@@ -139,6 +141,7 @@ struct ev_handle {
     MelBasisW melb;
     ResamplerW rs;
     StoiW stoi;
+    StftDistW stftd;
     // small per-stage scratch arenas (denoiser, text encoder): grown on demand, ordered against their last user's stream
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
     Scratch dn_ws, enc_ws, mas_ws;   // (mas_ws: the alignment search's frame -> token index and, for large Tx * Ty, its decision bits)
@@ -147,6 +150,7 @@ struct ev_handle {
     Scratch trim_ws;                 // ev_trim_bounds: the per-(row, hop block) sum of squares (float64) and max |x| (fp32)
     Scratch loud_ws;                 // ev_loudness: per (row, chunk) the four filter-state doubles and the sub-block pieces; the sub-block energies without d_sub
     Scratch stoi_ws;                 // ev_stoi: the frame energies, the kept frames' indices, and the band spectra / segment scores not asked for
+    Scratch stftd_ws;                // ev_stft_dist: the per-frame sums (B x NF x 4 doubles) without d_frame
     float* zeros = nullptr;     // 4096 zero floats (stand-in bias for the fused kernels' unconditional loads)
     int max_steps = 64;         // Euler steps the time-grid buffers of the workspace are planned for (grows on demand)
     int* bad_ids_host = nullptr; int* bad_ids_dev = nullptr;   // mapped host word: count of out-of-range token ids seen by ev_text_encoder
@@ -2000,6 +2004,7 @@ void ev_destroy(ev_handle* h) {
     if (h->trim_ws.p) hipFree(h->trim_ws.p);
     if (h->loud_ws.p) hipFree(h->loud_ws.p);
     if (h->stoi_ws.p) hipFree(h->stoi_ws.p);
+    if (h->stftd_ws.p) hipFree(h->stftd_ws.p);
     if (h->dn_ws.p) hipFree(h->dn_ws.p);
     if (h->bad_ids_host) hipHostFree(h->bad_ids_host);
     for (int i = 0; i < 2; ++i) { if (h->temb_ev[i]) hipEventDestroy(h->temb_ev[i]); if (h->temb_host[i]) hipHostFree(h->temb_host[i]); }
@@ -3177,6 +3182,81 @@ int ev_stoi(ev_handle* h, const float* d_x, const float* d_y, const int32_t* d_l
     }
     StoiMeanParams pm{seg, d_counts, d_score, NSEG};
     launch<stoi_mean_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pm);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Multi-resolution STFT distance at one resolution (kernels, the definition and every order: ev_kernels.h).  Arena: B x NF x 4 doubles, only
+// without d_frame.
+int ev_load_stft_dist(ev_handle* h, const double* window, const double* twiddle, int W, int H, int nfft) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!window || !twiddle) return fail(h, "ev_load_stft_dist: window and twiddle must be non-null (HOST)");
+    if (nfft < 16 || nfft > 2048 || nfft % 2) return fail(h, "ev_load_stft_dist: nfft=%d must be even with 16 <= nfft <= 2048", nfft);
+    if ((nfft - W) % 2) return fail(h, "ev_load_stft_dist: nfft - W = %d must be even (the window is padded centrally)", nfft - W);
+    if (W < 4 || W > nfft || W % 4) return fail(h, "ev_load_stft_dist: W=%d must be a multiple of 4 with 4 <= W <= nfft = %d", W, nfft);
+    if (H < 1 || H > 512) return fail(h, "ev_load_stft_dist: H=%d outside 1 <= H <= 512", H);
+    for (int j = 0; j < W; ++j) if (!std::isfinite(window[j])) return fail(h, "ev_load_stft_dist: window[%d] is not finite", j);
+    for (int j = 0; j < 2 * nfft; ++j) if (!std::isfinite(twiddle[j])) return fail(h, "ev_load_stft_dist: twiddle[%d] is not finite", j);
+    StftDistW t;
+    t.W = W; t.H = H; t.nfft = nfft; t.NB = nfft / 2 + 1; t.skew = ((2 - H) % 4 + 4) % 4;
+    StftDistW& cur = h->stftd;
+    if (cur.loaded) {                       // replace: nothing in flight may still read the old basis
+        HIPCHK(h, hipDeviceSynchronize());
+        auto it = std::find(h->owned.begin(), h->owned.end(), (void*)cur.basis);
+        if (it != h->owned.end()) { h->owned.erase(it); hipFree(cur.basis); }
+        cur = StftDistW();
+    }
+    double* d_win = nullptr; double* d_tw = nullptr;
+    HIPCHK(h, hipMalloc((void**)&d_win, (size_t)W * sizeof(double)));
+    if (hipMalloc((void**)&d_tw, (size_t)2 * nfft * sizeof(double)) != hipSuccess) { hipFree(d_win); return fail(h, "ev_load_stft_dist: hipMalloc of the twiddles failed"); }
+    const size_t n_basis = (size_t)W * t.NB;
+    hipError_t e = hipMalloc((void**)&t.basis, n_basis * sizeof(double2));
+    if (e == hipSuccess) e = hipMemcpy(d_win, window, (size_t)W * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_tw, twiddle, (size_t)2 * nfft * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        StftBasisParams pb{d_win, d_tw, t.basis, W, nfft, t.NB};
+        launch<stft_dist_basis_kernel>(h->device, dim3((unsigned)((n_basis + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pb);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    hipFree(d_win); hipFree(d_tw);
+    if (e != hipSuccess) { if (t.basis) hipFree(t.basis); return fail(h, "ev_load_stft_dist: building the basis failed: %s", hipGetErrorString(e)); }
+    h->owned.push_back(t.basis);
+    ++h->n_allocs;                          // (the basis is the handle's largest table: 33.6 MB at W = nfft = 2048)
+    t.loaded = true;
+    cur = t;
+    return 0;
+}
+
+int ev_stft_dist(ev_handle* h, const float* d_x, const float* d_y, const int32_t* d_len, int B, int L, double power_floor,
+                 double* d_frame, double* d_sums, int32_t* d_counts, void* stream) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    const StftDistW& w = h->stftd;
+    if (!w.loaded) return fail(h, "ev_stft_dist: tables not loaded (ev_load_stft_dist)");
+    if (B < 1 || B > 65535) return fail(h, "ev_stft_dist: B=%d outside 1 <= B <= 65535", B);
+    if (L < 1) return fail(h, "ev_stft_dist: L=%d must be at least 1", L);
+    if (!d_x || !d_y) return fail(h, "ev_stft_dist: d_x and d_y must be non-null");
+    if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_stft_dist: power_floor=%g must be finite and greater than 0", power_floor);
+    if (!d_sums || !d_counts) return fail(h, "ev_stft_dist: d_sums and d_counts must be non-null");
+    h->stream = (hipStream_t)stream;
+    if (L / w.H > 0x7fffffef) return fail(h, "ev_stft_dist: L=%d at H=%d has more frames than an int32 tile index holds", L, w.H);
+    const int NF = L > w.nfft / 2 ? 1 + L / w.H : 0;
+    double* frame = d_frame;
+    if (!frame && NF > 0) {
+        if (scratch_acquire(h, h->stftd_ws, (size_t)B * NF * 4 * sizeof(double))) return 1;
+        frame = (double*)h->stftd_ws.p;
+    }
+    StftDistTables t{w.basis, w.W, w.H, w.nfft, w.NB, w.skew};
+    if (NF > 0) {
+        StftFramesParams pf{d_x, d_y, d_len, frame, t, L, NF, power_floor};
+        const int span = 15 * w.H + w.W;
+        const size_t smem = (size_t)2 * (span + w.skew * ((span - 1) / w.H)) * sizeof(float);
+        launch<stft_dist_frames_kernel>(h->device, dim3((unsigned)((NF + 15) / 16), (unsigned)B), dim3(256), smem, h->stream, pf);
+    }
+    StftRowsParams pr{frame, d_len, d_sums, d_counts, t, L, NF};
+    launch<stft_dist_rows_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pr);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

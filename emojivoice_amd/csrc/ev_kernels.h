@@ -7882,3 +7882,176 @@ __global__ __launch_bounds__(256) void stoi_mean_kernel(const StoiMeanParams p) 
         p.score[2 * b + tid] = nseg > 0 ? s / (double)nseg : 0.0;
     }
 }
+
+// ---------------------------------------------------------------------------
+// Multi-resolution STFT distance (ev_stft_dist): spectral convergence, log-magnitude L1 (Yamamoto et al. 2020) and log-spectral distance of a
+// processed row y against a reference row x at ONE resolution (W, H, nfft); the caller runs it once per resolution.  All float64, contraction
+// OFF (STOI_EXACT), no atomics.  The DFT is a float64 GEMM on v_mfma_f64_16x16x4_f64: frames x samples times the dense windowed basis
+//   basis[j][k] = {w[j] cos(2 pi (j + off) k / nfft), w[j] sin(2 pi (j + off) k / nfft)},  off = (nfft - W) / 2,  0 <= j < W,  0 <= k < NB,
+// which stft_dist_basis_kernel builds once per load (one rounding per entry, the phase index in exact integers), {cos, sin} interleaved so
+// that one 16-byte load feeds both planes.  Launches of a call:
+//   1. stft_dist_frames_kernel: one workgroup of 4 waves per (row, 16 frames from the row's frame 0) -> d_frame (B, NF, 4);
+//   2. stft_dist_rows_kernel:   one workgroup per row: the four sums in the fixed tree of loud_reduce / stoi_mean_kernel, and the count.
+// Everything a row's outputs depend on hangs on the row's own samples below len.
+struct StftDistTables { const double2* basis; int W, H, nfft, NB, skew; };
+typedef double stftd_acc __attribute__((ext_vector_type(4)));
+
+// (n, nf) of row b: a row with len < 1, len > L or len <= nfft / 2 is an empty row (the reflect padding of nfft / 2 needs more samples)
+__device__ __forceinline__ int stftd_frames(const int32_t* len, int b, int L, const StftDistTables& t, int* n_out) {
+    int n = len ? len[b] : L;
+    if (n < 1 || n > L || n <= t.nfft / 2) n = 0;
+    *n_out = n;
+    return n > 0 ? 1 + n / t.H : 0;
+}
+
+struct StftBasisParams { const double* win; const double* tw; double2* basis; int W, nfft, NB; };
+
+__global__ __launch_bounds__(256) void stft_dist_basis_kernel(const StftBasisParams p) {
+    STOI_EXACT
+    const int i = blockIdx.x * 256 + threadIdx.x;                       // (W NB <= 2048 x 1025)
+    if (i >= p.W * p.NB) return;
+    const int j = i / p.NB, k = i - j * p.NB;
+    const int ph = ((j + (p.nfft - p.W) / 2) * k) % p.nfft;             // (< 2048 x 1024: exact)
+    const double w = p.win[j];
+    p.basis[i] = make_double2(w * p.tw[2 * ph], w * p.tw[2 * ph + 1]);
+}
+
+// One workgroup per (row b, tile of 16 frames f0 .. f0 + 15).  The tile's raw span, samples f0 H - W / 2 + t for 0 <= t < 15 H + W of both
+// signals, is staged once into LDS as fp32 with the reflection applied (refl(i) = -i below 0, 2 (len - 1) - i from len on; what a frame
+// >= nf would read outside the row is staged as 0 and that frame is masked).  Lane l of an A fragment reads t = (l & 15) H + k0 + (l >> 4):
+// with ds_read_b32 banked over 32 words and served in two groups of 32 lanes, a frame stride H = 0 mod 4 (240: 16 banks) lands the 16
+// frames of a group on few banks.  SKEW: sample t lives at word t + skew * (t / H) with skew = (2 - H) mod 4, so the frame stride H + skew
+// is 2 mod 4: 2 r (odd) mod 32 is 16 distinct even banks for r = 0 .. 15, and the two k of a lane group fill the odd ones — conflict-free
+// (except where k0 + (l >> 4) crosses a multiple of H inside a group).  At most 3 (16 + W / H) pad words per signal: 78 160 bytes for
+// both signals at H = 511, W = 2048, the largest footprint.
+// Wave w owns the bin tiles w, w + 4, ...; per bin tile W / 4 steps of four MFMAs (x c, x s, y c, y s): the A fragment of each signal
+// (frame l & 15, sample k0 + (l >> 4), widened on the way out of LDS) serves both planes, the B fragment (basis row k0 + (l >> 4), bin
+// l & 15, read from global memory: L2-resident) serves both signals.  Accumulators in the f64 layout: register i of lane l is frame
+// (l >> 4) + 4 i, bin l & 15.  Epilogue per (frame, bin): p = max(fma(sm, sm, re * re), floor), m = sqrt(p), l = log(p) for both signals; the
+// four terms are accumulated per frame over the wave's bin tiles in ascending order (squares as fma(d, d, sum)), reduced over the 16 bin
+// lanes by one xor tree (offsets 8, 4, 2, 1) and over the waves as ((w0 + w1) + w2) + w3.  Bins >= NB (the address is clamped, the term
+// dropped) and frames >= nf (zeros) are masked.
+struct StftFramesParams { const float* x; const float* y; const int32_t* len; double* frame; StftDistTables t; int L, NF; double floor; };
+
+__global__ __launch_bounds__(256) void stft_dist_frames_kernel(const StftFramesParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) float stftd_smem[];
+    __shared__ double red[4][16][4];
+    const int b = blockIdx.y, f0 = blockIdx.x * 16, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int W = p.t.W, H = p.t.H, NB = p.t.NB, skew = p.t.skew;
+    int n;
+    const int nf = stftd_frames(p.len, b, p.L, p.t, &n);
+    double* out = p.frame + ((size_t)b * p.NF + f0) * 4;
+    if (f0 >= nf) {                                                     // (uniform) zeros past the row's own frames
+        if (tid < 64 && f0 + (tid >> 2) < p.NF) out[tid] = 0.0;
+        return;
+    }
+    const int span = 15 * H + W;
+    float* sx = stftd_smem;
+    float* sy = sx + span + skew * ((span - 1) / H);                    // (the last word of x is (span - 1) + skew ((span - 1) / H))
+    {
+        const float* xr = p.x + (size_t)b * p.L;
+        const float* yr = p.y + (size_t)b * p.L;
+        const long long i0 = (long long)f0 * H - W / 2;
+        for (int t = tid; t < span; t += 256) {
+            long long i = i0 + t;
+            if (i < 0) i = -i;
+            else if (i >= n) i = 2LL * (n - 1) - i;
+            const bool ok = i >= 0 && i < n;                            // (always, for a frame < nf)
+            const int a = t + skew * (t / H);
+            sx[a] = ok ? xr[i] : 0.f;
+            sy[a] = ok ? yr[i] : 0.f;
+        }
+    }
+    __syncthreads();
+    const int r = lane & 15, q = lane >> 4;
+    const int rbase = r * (H + skew);                                   // word of sample r H + j: r (H + skew) + j + skew (j / H)
+    const int ntile = (NB + 15) >> 4;
+    const int step_mod = 4 % H, step_pad = skew * (4 / H), nsteps = W >> 2;
+    double t0[4] = {0.0, 0.0, 0.0, 0.0}, t1[4] = {0.0, 0.0, 0.0, 0.0}, t2[4] = {0.0, 0.0, 0.0, 0.0}, t3[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int bt = wv; bt < ntile; bt += 4) {
+        const int col = bt * 16 + r;
+        const double2* bp = p.t.basis + (size_t)q * NB + (col < NB ? col : NB - 1);
+        stftd_acc xc = {0.0, 0.0, 0.0, 0.0}, xs = xc, yc = xc, ys = xc;
+        int j = q, jm = q % H, pad = skew * (q / H);
+        // four steps per round; the basis of the NEXT round is requested before this round's products (the index clamped at the last
+        // step: a repeated load, never one past the basis), so its L2 latency hides behind sixteen matrix instructions
+        double2 cur[4], nxt[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) cur[u] = bp[(size_t)(u < nsteps ? u : nsteps - 1) * 4 * NB];
+        for (int s0 = 0; s0 < nsteps; s0 += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) nxt[u] = bp[(size_t)(s0 + 4 + u < nsteps ? s0 + 4 + u : nsteps - 1) * 4 * NB];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (s0 + u < nsteps) {                                  // (uniform)
+                    const int a = rbase + j + pad;
+                    const double ax = (double)sx[a], ay = (double)sy[a];
+                    xc = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].x, xc, 0, 0, 0);
+                    xs = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].y, xs, 0, 0, 0);
+                    yc = __builtin_amdgcn_mfma_f64_16x16x4f64(ay, cur[u].x, yc, 0, 0, 0);
+                    ys = __builtin_amdgcn_mfma_f64_16x16x4f64(ay, cur[u].y, ys, 0, 0, 0);
+                    j += 4; jm += step_mod; pad += step_pad;            // (j + 4) / H = j / H + 4 / H + (j % H + 4 % H >= H)
+                    if (jm >= H) { jm -= H; pad += skew; }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+        }
+        if (col < NB) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const double px = fmax(fma(xs[i], xs[i], xc[i] * xc[i]), p.floor), py = fmax(fma(ys[i], ys[i], yc[i] * yc[i]), p.floor);
+                const double mx = sqrt(px), my = sqrt(py);
+                const double dm = my - mx, dl = log(py) - log(px);
+                t0[i] = fma(dm, dm, t0[i]);
+                t1[i] = fma(mx, mx, t1[i]);
+                t2[i] = t2[i] + fabs(dl);
+                t3[i] = fma(dl, dl, t3[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {
+            t0[i] = t0[i] + __shfl_xor(t0[i], o, 64); t1[i] = t1[i] + __shfl_xor(t1[i], o, 64);
+            t2[i] = t2[i] + __shfl_xor(t2[i], o, 64); t3[i] = t3[i] + __shfl_xor(t3[i], o, 64);
+        }
+        if (r == 0) { double* d = red[wv][q + 4 * i]; d[0] = t0[i]; d[1] = t1[i]; d[2] = t2[i]; d[3] = t3[i]; }
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const int fr = tid >> 2, c = tid & 3;
+        const double v = ((red[0][fr][c] + red[1][fr][c]) + red[2][fr][c]) + red[3][fr][c];
+        if (f0 + fr < p.NF) out[tid] = f0 + fr < nf ? v : 0.0;
+    }
+}
+
+// d_sums[b] = {sum_f d_frame[f][0], sum_f [1], sum_f [2], sum_f sqrt([3] / NB)} over the row's nf frames, d_counts[b] = nf: thread t of 256
+// adds its frames t, t + 256, ... in ascending order, the 64 partials of a wave go through the shuffle tree (offsets 32 .. 1), the four
+// waves' sums are added as (w0 + w1) + (w2 + w3) — the tree of ev_loudness / ev_stoi.
+struct StftRowsParams { const double* frame; const int32_t* len; double* sums; int32_t* counts; StftDistTables t; int L, NF; };
+
+__global__ __launch_bounds__(256) void stft_dist_rows_kernel(const StftRowsParams p) {
+    STOI_EXACT
+    __shared__ double red[4][4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int n;
+    const int nf = stftd_frames(p.len, b, p.L, p.t, &n);
+    const double* fr = p.frame + (size_t)b * p.NF * 4;
+    const double dNB = (double)p.t.NB;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int f = tid; f < nf; f += 256) {
+        s0 = s0 + fr[4 * (size_t)f]; s1 = s1 + fr[4 * (size_t)f + 1]; s2 = s2 + fr[4 * (size_t)f + 2];
+        s3 = s3 + sqrt(fr[4 * (size_t)f + 3] / dNB);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s0 = s0 + __shfl_down(s0, o); s1 = s1 + __shfl_down(s1, o); s2 = s2 + __shfl_down(s2, o); s3 = s3 + __shfl_down(s3, o);
+    }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = s0; red[1][tid >> 6] = s1; red[2][tid >> 6] = s2; red[3][tid >> 6] = s3; }
+    __syncthreads();
+    if (tid < 4) p.sums[4 * (size_t)b + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+    if (tid == 0) p.counts[b] = nf;
+}

@@ -39,6 +39,8 @@
  *   ev_loudness        <- no counterpart; ITU-R BS.1770-4 is the model
  *   ev_load_stoi       <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_stoi            <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
+ *   ev_load_stft_dist  <- no counterpart; Yamamoto et al. 2020 (multi-resolution STFT loss) is the model
+ *   ev_stft_dist       <- no counterpart; Yamamoto et al. 2020 (multi-resolution STFT loss) is the model
  *   ev_pyin_observe    <- no counterpart; librosa.pyin is the model
  *   ev_pyin_decode     <- no counterpart; librosa.pyin is the model
  *
@@ -78,7 +80,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -559,6 +561,52 @@ int ev_stoi(ev_handle *h, const float *d_x /* (B, L) clean */, const float *d_y 
             int B, int L, double silence_ratio /* 10^(-40/10) */, double clip /* 1 + 10^(15/20) */,
             uint8_t *d_keep /* (B, NF) or NULL */, double *d_tob /* (B, 2, n_bands, NM) or NULL */, double *d_seg /* (B, NSEG, 2) or NULL */,
             double *d_score /* (B, 2): STOI, ESTOI */, int32_t *d_counts /* (B, 3): nf, nk, nseg */, void *stream);
+
+/* STFT distance at one resolution on the device: the terms of the multi-resolution STFT distance (spectral convergence and log-magnitude L1;
+ * Yamamoto, Song and Kim, "Parallel WaveGAN", ICASSP 2020) and of the log-spectral distance in dB, of a processed row y against the
+ * sample-aligned reference row x.  ev_load_stft_dist stores one resolution (window, hop, n_fft); ev_stft_dist measures; a caller that wants
+ * the multi-resolution figure holds one handle per resolution and averages.  Everything is float64 (the fp32 samples are widened), the kernels
+ * are compiled with floating-point contraction off; no atomics; ev_set_arithmetic does not reach it.
+ * ev_load_stft_dist: HOST tables.  window (W) doubles w; twiddle (nfft, 2) doubles {cos, sin}(2 pi n / nfft); H the hop.  Limits, each
+ *   violation failing with a message that names it: nfft even with 16 <= nfft <= 2048; W a multiple of 4 with 4 <= W <= nfft; nfft - W even;
+ *   1 <= H <= 512 (any integer); finite, non-NULL tables.  With off = (nfft - W) / 2 and NB = nfft / 2 + 1 the handle builds the dense basis
+ *     c[j][k] = w[j] * cos_tab[((j + off) k) mod nfft],  s[j][k] = w[j] * sin_tab[((j + off) k) mod nfft],  0 <= j < W, 0 <= k < NB,
+ *   on the device at load time: each entry rounded once, the index in exact integer arithmetic (torch.stft with `window` zero-padded
+ *   centrally to n_fft).  It takes 16 W NB bytes (33.6 MB at W = nfft = 2048) and counts once in ev_alloc_count.  Loading again replaces the
+ *   basis; it waits for the device first.  ev_stft_dist without a loaded basis fails with a message.
+ * Sizes, with frames(n) = n > nfft / 2 ? 1 + n / H : 0 (torch's reflect padding of nfft / 2 needs more samples than that): NF = frames(L); a
+ *   row of len samples has nf = frames(len).  d_len == NULL: every row is L long.
+ * Definition, per row:
+ *   framing   frame f reads t_j = x[refl(f H - W / 2 + j)] for 0 <= j < W; refl(i) = -i for i < 0, 2 (len - 1) - i for i >= len, i otherwise
+ *             (center=True, pad_mode="reflect"; one reflection suffices because len > nfft / 2 >= W / 2); y alike
+ *   spectra   re_k = sum_j t_j c[j][k], sm_k = sum_j t_j s[j][k] for 0 <= k < NB; p_k = max(fma(sm_k, sm_k, re_k * re_k), power_floor);
+ *             m_k = sqrt(p_k), correctly rounded; l_k = log(p_k), the device library's float64 natural logarithm.  The sums over j run on
+ *             v_mfma_f64_16x16x4_f64 in steps of four j from 0; the order inside the instruction is the hardware's: fixed, not spelled out
+ *   d_frame   (B, NF, 4) or NULL: [b][f] = {sum_k (my_k - mx_k)^2, sum_k mx_k^2, sum_k |ly_k - lx_k|, sum_k (ly_k - lx_k)^2} over the NB bins,
+ *             squares added as fma(d, d, sum); bins k = 16 (w + 4 i) + c are added per (w, c) in ascending i, then over c by an xor tree
+ *             (offsets 8, 4, 2, 1), then over w as ((w0 + w1) + w2) + w3.  Zeros at f >= nf
+ *   d_sums    (B, 4) = {sum_f [0], sum_f [1], sum_f [2], sum_f sqrt([3] / NB)} over the nf frames: thread t of 256 adds frames t, t + 256, ...
+ *             in ascending order, the 64 partials of a wave go through one shuffle tree (offsets 32 .. 1), the four waves' sums are added
+ *             as (w0 + w1) + (w2 + w3) (the tree of ev_loudness and ev_stoi)
+ *   d_counts  (B) int32: nf
+ *   The caller takes sc = sqrt(s0 / s1), log_mag = 0.5 s2 / (nf NB) (the L1 of log magnitudes: half the log power) and
+ *   lsd_db = (10 / ln 10) s3 / nf.
+ * A row with len < 1, len > L or len <= nfft / 2 is no error and no out-of-bounds access: all its outputs are zeros (the ev_mas_align
+ * convention).  Nothing at or behind len is read, and nothing depends on the batch or on L: a row alone, inside a batch, or as the d_len
+ * prefix of a longer padded row with anything behind it, and a second call, give the same bits in every output.
+ * Limits of ev_stft_dist, each violation failing with a message that names it and writing nothing: 1 <= B <= 65535; L >= 1 (and L / H below
+ * 2^31 - 16); power_floor > 0 and finite; d_x, d_y, d_sums and d_counts non-NULL.
+ * Kernels (two launches on `stream`, one where NF = 0; no host wait, no copy): (1) one workgroup of four waves per (row, 16 frames): the
+ *   tile's span of 15 H + W samples of both signals staged once in LDS as fp32, reflection applied, then per wave and 16-bin tile W / 4 steps
+ *   of four matrix instructions (x c, x s, y c, y s: 16 frames x 4 samples times 4 samples x 16 bins); (2) one workgroup per row: d_sums.
+ * Scratch: B x NF x 4 doubles when d_frame is NULL, in an arena of the handle that grows on demand like the loudness arena and counts in
+ *   ev_alloc_count: a second call at the same shape allocates nothing; ev_reserve does not cover it.  The call is capturable once the arena
+ *   has its size. */
+int ev_load_stft_dist(ev_handle *h, const double *window /* HOST (W) */, const double *twiddle /* HOST (nfft, 2): cos, sin of 2 pi n / nfft */,
+                      int W, int H, int nfft);
+int ev_stft_dist(ev_handle *h, const float *d_x /* (B, L) reference */, const float *d_y /* (B, L) processed */, const int32_t *d_len /* (B) or NULL */,
+                 int B, int L, double power_floor /* 1e-7 */,
+                 double *d_frame /* (B, NF, 4) or NULL */, double *d_sums /* (B, 4) */, int32_t *d_counts /* (B) */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

@@ -17,6 +17,9 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EV_LIB_PATH") or os.path.join(_HERE, "lib", "libemojivoice_hip.so")   # EV_LIB_PATH: A/B builds of the same ABI
 CSRC = os.path.join(_HERE, "csrc")
+# Everything the library is built from: the one translation unit first, then what it includes.  build_library rebuilds when any is newer.
+SOURCES = [os.path.join(CSRC, n) for n in ("ev_engine.hip", "ev_kernels.h", "ev_analysis_kernels.h", "ev_analysis.h")] \
+    + [os.path.join(os.path.dirname(_HERE), "include", "emojivoice.h")]
 
 EXPORTS = [
     "ev_abi_version", "ev_create", "ev_destroy", "ev_last_error", "ev_load_estimator", "ev_load_vocoder", "ev_load_vocoder_cfg", "ev_load_text_encoder", "ev_text_encoder",
@@ -88,9 +91,8 @@ def vocoder_frame_bytes(h) -> int:
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP sources for gfx950 into emojivoice_amd/lib/ (hipcc cross-compiles without a GPU)."""
-    src = os.path.join(CSRC, "ev_engine.hip")
-    deps = [src, os.path.join(CSRC, "ev_kernels.h"), os.path.join(os.path.dirname(_HERE), "include", "emojivoice.h")]
-    if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
+    src = SOURCES[0]
+    if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in SOURCES):
         return LIB_PATH
     os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -194,6 +196,11 @@ def load_library() -> C.CDLL:
 
 def _stream_ptr() -> int:
     return int(torch.cuda.current_stream().cuda_stream)
+
+
+def _ptr(t):
+    """The device address of an optional tensor (None: a null pointer)."""
+    return None if t is None else t.data_ptr()
 
 
 class Engine:
@@ -338,17 +345,11 @@ class Engine:
     def resample(self, x, lengths=None):
         """(B, L) -> (B, ceil(L * up / down)) by the loaded polyphase filter (ev_resample): scipy.signal.resample_poly with zero padding.
         ``lengths`` (B,): samples per row (None: L); a row's outputs past ceil(len * up / down) are zeros."""
-        x = self._f32(x)
-        if x.dim() != 2:
-            raise ValueError(f"resample: x must be (B, L), got shape {tuple(x.shape)}")
-        B, L = x.shape
+        x, B, L, ln = self._rows(x, lengths, "resample")
         up, down = getattr(self, "rs_ratio", (1, 1))
         L_out = -(-L * up // down)
-        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
-        if ln is not None and ln.numel() != B:
-            raise ValueError(f"resample: {B} lengths expected, got {ln.numel()}")
         y = torch.empty((B, L_out), dtype=torch.float32, device=x.device)
-        self._check(self.lib.ev_resample(self.h, x.data_ptr(), None if ln is None else ln.data_ptr(), B, L, y.data_ptr(), L_out, _stream_ptr()), "ev_resample")
+        self._check(self.lib.ev_resample(self.h, x.data_ptr(), _ptr(ln), B, L, y.data_ptr(), L_out, _stream_ptr()), "ev_resample")
         return y
 
     def mel_stats(self, mel, lengths):
@@ -366,17 +367,11 @@ class Engine:
         """librosa.effects.trim's bounds for every row of ``x`` (B, L) (ev_trim_bounds): (bounds (B, 2) int32 {start, end}, peak (B,) fp32
         = max |x| over the whole row, or None), both on the device.  ``lengths`` (B,): samples per row (None: L).  hop_length a multiple
         of 64 up to 4096, frame_length a multiple of it, frame_length / hop_length <= 64."""
-        x = self._f32(x)
-        if x.dim() != 2:
-            raise ValueError(f"trim_bounds: x must be (B, L), got shape {tuple(x.shape)}")
-        B, L = x.shape
-        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
-        if ln is not None and ln.numel() != B:
-            raise ValueError(f"trim_bounds: {B} lengths expected, got {ln.numel()}")
+        x, B, L, ln = self._rows(x, lengths, "trim_bounds")
         bounds = torch.empty((B, 2), dtype=torch.int32, device=x.device)
         peak = torch.empty((B,), dtype=torch.float32, device=x.device) if want_peak else None
-        self._check(self.lib.ev_trim_bounds(self.h, x.data_ptr(), None if ln is None else ln.data_ptr(), B, L, int(frame_length), int(hop_length),
-                                            float(top_db), bounds.data_ptr(), None if peak is None else peak.data_ptr(), _stream_ptr()), "ev_trim_bounds")
+        self._check(self.lib.ev_trim_bounds(self.h, x.data_ptr(), _ptr(ln), B, L, int(frame_length), int(hop_length), float(top_db),
+                                            bounds.data_ptr(), _ptr(peak), _stream_ptr()), "ev_trim_bounds")
         return bounds, peak
 
     def trim_apply(self, x, bounds, peak=None, target_peak: float = 0.0, out_len: Optional[int] = None):
@@ -384,10 +379,7 @@ class Engine:
         row's out_len.  ``bounds`` (B, 2) int32 and ``peak`` (B,) fp32 are device tensors (those of ``trim_bounds``); gain is
         target_peak / peak when a peak is given, target_peak > 0 and the peak > 0, else 1.  ``out_len``: L_out (None: L); longer rows are
         truncated to it."""
-        x = self._f32(x)
-        if x.dim() != 2:
-            raise ValueError(f"trim_apply: x must be (B, L), got shape {tuple(x.shape)}")
-        B, L = x.shape
+        x, B, L, _ = self._rows(x, None, "trim_apply")
         bounds = torch.as_tensor(bounds).to(x.device, torch.int32).contiguous()
         if tuple(bounds.shape) != (B, 2):
             raise ValueError(f"trim_apply: bounds must be ({B}, 2), got shape {tuple(bounds.shape)}")
@@ -397,7 +389,7 @@ class Engine:
         L_out = L if out_len is None else int(out_len)
         y = torch.empty((B, max(L_out, 1)), dtype=torch.float32, device=x.device)
         n = torch.empty((B,), dtype=torch.int32, device=x.device)
-        self._check(self.lib.ev_trim_apply(self.h, x.data_ptr(), bounds.data_ptr(), None if pk is None else pk.data_ptr(), float(target_peak), B, L,
+        self._check(self.lib.ev_trim_apply(self.h, x.data_ptr(), bounds.data_ptr(), _ptr(pk), float(target_peak), B, L,
                                            y.data_ptr(), L_out, n.data_ptr(), _stream_ptr()), "ev_trim_apply")
         return y, n
 
@@ -406,20 +398,13 @@ class Engine:
         """YIN per frame of every row of ``x`` (B, L) (ev_pitch_yin): (lag (B, F) int32, period (B, F) fp32 in samples, cmnd (B, F) fp32) on
         the device, F = ceil(L / hop_length); an output that is not wanted is None.  Unvoiced frames have lag 0 and period 0, and cmnd =
         min d' over [tau_min, tau_max].  ``lengths`` (B,): samples per row (None: L); frames past ceil(len / hop_length) are zeros."""
-        x = self._f32(x)
-        if x.dim() != 2:
-            raise ValueError(f"pitch_yin: x must be (B, L), got shape {tuple(x.shape)}")
-        B, L = x.shape
-        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
-        if ln is not None and ln.numel() != B:
-            raise ValueError(f"pitch_yin: {B} lengths expected, got {ln.numel()}")
+        x, B, L, ln = self._rows(x, lengths, "pitch_yin")
         F = -(-L // max(int(hop_length), 1))
         lag = torch.empty((B, F), dtype=torch.int32, device=x.device) if want_lag else None
         period = torch.empty((B, F), dtype=torch.float32, device=x.device) if want_period else None
         cmnd = torch.empty((B, F), dtype=torch.float32, device=x.device) if want_cmnd else None
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._check(self.lib.ev_pitch_yin(self.h, x.data_ptr(), ptr(ln), B, L, int(frame_length), int(hop_length), int(tau_min), int(tau_max),
-                                          float(threshold), ptr(lag), ptr(period), ptr(cmnd), _stream_ptr()), "ev_pitch_yin")
+        self._check(self.lib.ev_pitch_yin(self.h, x.data_ptr(), _ptr(ln), B, L, int(frame_length), int(hop_length), int(tau_min), int(tau_max),
+                                          float(threshold), _ptr(lag), _ptr(period), _ptr(cmnd), _stream_ptr()), "ev_pitch_yin")
         return lag, period, cmnd
 
     DTW_METRICS = {"euclidean": 0, "sqeuclidean": 1}
@@ -447,9 +432,8 @@ class Engine:
         cost = torch.empty((B,), dtype=torch.float64, device=x.device)
         steps = torch.empty((B,), dtype=torch.int32, device=x.device)
         path = torch.empty((B, max(Tx + Ty - 1, 0), 2), dtype=torch.int32, device=x.device) if want_path else None
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._check(self.lib.ev_dtw(self.h, x.data_ptr(), y.data_ptr(), ptr(lens[0]), ptr(lens[1]), B, C, Tx, Ty, int(metric), cost.data_ptr(),
-                                    steps.data_ptr(), ptr(path), _stream_ptr()), "ev_dtw")
+        self._check(self.lib.ev_dtw(self.h, x.data_ptr(), y.data_ptr(), _ptr(lens[0]), _ptr(lens[1]), B, C, Tx, Ty, int(metric), cost.data_ptr(),
+                                    steps.data_ptr(), _ptr(path), _stream_ptr()), "ev_dtw")
         return cost, steps, path
 
     def loudness(self, x, lengths, sub_len: int, coef, abs_gate: float, want_sub: bool = True, want_block: bool = True):
@@ -458,13 +442,7 @@ class Engine:
         (B, 3) int32 {blocks, passing the absolute gate, passing both}) on the device.  ``coef``: the 10 float64 of ``audio.k_weighting``,
         read on the host during the call; ``sub_len`` = S, the samples per 100 ms; ``abs_gate`` a mean square.  ``lengths`` (B,): samples per
         row (None: L)."""
-        x = self._f32(x)
-        if x.dim() != 2:
-            raise ValueError(f"loudness: x must be (B, L), got shape {tuple(x.shape)}")
-        B, L = x.shape
-        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
-        if ln is not None and ln.numel() != B:
-            raise ValueError(f"loudness: {B} lengths expected, got {ln.numel()}")
+        x, B, L, ln = self._rows(x, lengths, "loudness")
         coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float64).reshape(-1))
         if coef.size != 10:
             raise ValueError(f"loudness: 10 coefficients expected, got {coef.size}")
@@ -474,8 +452,7 @@ class Engine:
         block = torch.empty((B, max(NS - 3, 0)), dtype=torch.float64, device=x.device) if want_block else None
         gated = torch.empty((B, 2), dtype=torch.float64, device=x.device)
         counts = torch.empty((B, 3), dtype=torch.int32, device=x.device)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._check(self.lib.ev_loudness(self.h, x.data_ptr(), ptr(ln), B, L, S, coef.ctypes.data, float(abs_gate), ptr(sub), ptr(block),
+        self._check(self.lib.ev_loudness(self.h, x.data_ptr(), _ptr(ln), B, L, S, coef.ctypes.data, float(abs_gate), _ptr(sub), _ptr(block),
                                          gated.data_ptr(), counts.data_ptr(), _stream_ptr()), "ev_loudness")
         return sub, block, gated, counts
 
@@ -501,11 +478,8 @@ class Engine:
             raise ValueError(f"stoi: x and y must be (B, L) alike, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
         if not hasattr(self, "stoi_geometry"):
             raise EvLibraryError("stoi: tables not loaded (load_stoi)")
-        B, L = x.shape
+        x, B, L, ln = self._rows(x, lengths, "stoi")
         W, H, _, nb, N = self.stoi_geometry
-        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
-        if ln is not None and ln.numel() != B:
-            raise ValueError(f"stoi: {B} lengths expected, got {ln.numel()}")
         NF = -(-(L - W) // H) if L > W else 0
         NM = max(NF - 1, 0)
         NSEG = max(NM - N + 1, 0)
@@ -514,8 +488,7 @@ class Engine:
         seg = torch.empty((B, NSEG, 2), dtype=torch.float64, device=x.device) if want_seg else None
         score = torch.empty((B, 2), dtype=torch.float64, device=x.device)
         counts = torch.empty((B, 3), dtype=torch.int32, device=x.device)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._check(self.lib.ev_stoi(self.h, x.data_ptr(), y.data_ptr(), ptr(ln), B, L, float(silence_ratio), float(clip), ptr(keep), ptr(tob), ptr(seg),
+        self._check(self.lib.ev_stoi(self.h, x.data_ptr(), y.data_ptr(), _ptr(ln), B, L, float(silence_ratio), float(clip), _ptr(keep), _ptr(tob), _ptr(seg),
                                      score.data_ptr(), counts.data_ptr(), _stream_ptr()), "ev_stoi")
         return keep, tob, seg, score, counts
 
@@ -539,17 +512,13 @@ class Engine:
             raise ValueError(f"stft_dist: x and y must be (B, L) alike, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
         if not hasattr(self, "stft_dist_geometry"):
             raise EvLibraryError("stft_dist: tables not loaded (load_stft_dist)")
-        B, L = x.shape
+        x, B, L, ln = self._rows(x, lengths, "stft_dist")
         _, H, nfft = self.stft_dist_geometry
-        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
-        if ln is not None and ln.numel() != B:
-            raise ValueError(f"stft_dist: {B} lengths expected, got {ln.numel()}")
         NF = 1 + L // H if L > nfft // 2 else 0
         frame = torch.empty((B, NF, 4), dtype=torch.float64, device=x.device) if want_frames else None
         sums = torch.empty((B, 4), dtype=torch.float64, device=x.device)
         counts = torch.empty((B,), dtype=torch.int32, device=x.device)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._check(self.lib.ev_stft_dist(self.h, x.data_ptr(), y.data_ptr(), ptr(ln), B, L, float(power_floor), ptr(frame), sums.data_ptr(),
+        self._check(self.lib.ev_stft_dist(self.h, x.data_ptr(), y.data_ptr(), _ptr(ln), B, L, float(power_floor), _ptr(frame), sums.data_ptr(),
                                           counts.data_ptr(), _stream_ptr()), "ev_stft_dist")
         return frame, sums, counts
 
@@ -559,13 +528,7 @@ class Engine:
         pitch bin, pv (B, F) float64: the probability that the frame is voiced) on the device, F = ceil(L / hop_length).  ``w``: the
         threshold prior of ``audio.pyin_threshold_prior``, float64, read on the host during the call.  ``out``: (obs, pv) tensors to write
         into instead of new ones."""
-        x = self._f32(x)
-        if x.dim() != 2:
-            raise ValueError(f"pyin_observe: x must be (B, L), got shape {tuple(x.shape)}")
-        B, L = x.shape
-        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
-        if ln is not None and ln.numel() != B:
-            raise ValueError(f"pyin_observe: {B} lengths expected, got {ln.numel()}")
+        x, B, L, ln = self._rows(x, lengths, "pyin_observe")
         w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(-1))
         F = -(-L // max(int(hop_length), 1))
         nb = max(int(n_bins), 0)
@@ -577,8 +540,7 @@ class Engine:
             if obs.dtype != torch.float64 or pv.dtype != torch.float64 or tuple(obs.shape) != (B, F, nb) or tuple(pv.shape) != (B, F) \
                     or not obs.is_contiguous() or not pv.is_contiguous():
                 raise ValueError(f"pyin_observe: out must be contiguous float64 ({B}, {F}, {nb}) and ({B}, {F})")
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._check(self.lib.ev_pyin_observe(self.h, x.data_ptr(), ptr(ln), B, L, int(frame_length), int(hop_length), int(tau_min), int(tau_max),
+        self._check(self.lib.ev_pyin_observe(self.h, x.data_ptr(), _ptr(ln), B, L, int(frame_length), int(hop_length), int(tau_min), int(tau_max),
                                              float(sr), float(fmin), int(bins_per_octave), int(n_bins), w.ctypes.data, int(w.size),
                                              float(boltzmann), float(no_trough_prob), obs.data_ptr(), pv.data_ptr(), _stream_ptr()),
                     "ev_pyin_observe")
@@ -610,8 +572,7 @@ class Engine:
             raise ValueError(f"pyin_decode: back must be contiguous uint8 with at least {B * F * 2 * nb} elements")
         state = torch.empty((B, F), dtype=torch.int32, device=obs.device)
         loglik = torch.empty((B,), dtype=torch.float64, device=obs.device)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._check(self.lib.ev_pyin_decode(self.h, obs.data_ptr(), pv.data_ptr(), ptr(ln), B, int(L), int(hop_length), nb, int(R),
+        self._check(self.lib.ev_pyin_decode(self.h, obs.data_ptr(), pv.data_ptr(), _ptr(ln), B, int(L), int(hop_length), nb, int(R),
                                             log_tri.ctypes.data, log_Z.ctypes.data, float(log_stay), float(log_switch), back.data_ptr(),
                                             state.data_ptr(), loglik.data_ptr(), _stream_ptr()), "ev_pyin_decode")
         return state, loglik
@@ -653,9 +614,8 @@ class Engine:
         dur = torch.empty((B, Tx), dtype=torch.int32, device=dev) if want_dur else None
         mu_y = torch.empty((B, F, Ty), dtype=torch.float32, device=dev) if want_mu_y else None
         logp = torch.empty((B, Tx, Ty), dtype=torch.float32, device=dev) if want_logp else None
-        dp = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         self._check(self.lib.ev_mas_align(self.h, mu_x.data_ptr(), y.data_ptr(), xl.data_ptr(), yl.data_ptr(), B, Tx, Ty,
-                                          dp(attn), dp(dur), dp(mu_y), dp(logp), _stream_ptr()), "ev_mas_align")
+                                          _ptr(attn), _ptr(dur), _ptr(mu_y), _ptr(logp), _stream_ptr()), "ev_mas_align")
         return {"attn": attn, "dur": dur, "mu_y": mu_y, "logp": logp}
 
     def load_text_encoder(self, tensors: Dict[str, torch.Tensor]):
@@ -688,6 +648,17 @@ class Engine:
     def _f32(t: torch.Tensor) -> torch.Tensor:
         assert t.is_cuda, "tensor must live on the GPU"
         return t.contiguous().float()
+
+    def _rows(self, x, lengths, who: str):
+        """The opening of the per-row analysis calls: (x as contiguous fp32 (B, L), B, L, ``lengths`` as int32 (B,) beside x or None)."""
+        x = self._f32(x)
+        if x.dim() != 2:
+            raise ValueError(f"{who}: x must be (B, L), got shape {tuple(x.shape)}")
+        B, L = x.shape
+        ln = None if lengths is None else torch.as_tensor(lengths).to(x.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"{who}: {B} lengths expected, got {ln.numel()}")
+        return x, B, L, ln
 
     def cfm_decode(self, mu, lengths, spk, z, n_steps: int, out_scale: float = 1.0, out_shift: float = 0.0):
         mu, z = self._f32(mu), self._f32(z)
@@ -955,9 +926,8 @@ class Engine:
         b_inv = self._f32((1.0 / (torch.exp(beta.float()) + 0.000000001)).to(x.device)) if beta is not None else None
         rm = self._f32(rowmask) if rowmask is not None else None
         y = torch.empty((rows, 256 if mode == 0 else M1), dtype=torch.float32, device=x.device)
-        dp = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-        self._check(self.lib.ev_op_ln_mlp(self.h, x.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(), ptr(w1h), ptr(b1h), dp(a_exp), dp(b_inv),
-                                          ptr(w2h), ptr(b2h), dp(rm), rows, M1, mode, y.data_ptr(), _stream_ptr()), "ev_op_ln_mlp")
+        self._check(self.lib.ev_op_ln_mlp(self.h, x.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(), ptr(w1h), ptr(b1h), _ptr(a_exp), _ptr(b_inv),
+                                          ptr(w2h), ptr(b2h), _ptr(rm), rows, M1, mode, y.data_ptr(), _stream_ptr()), "ev_op_ln_mlp")
         return y
 
     def op_attention(self, qkv, lengths, heads=2):

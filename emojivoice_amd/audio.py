@@ -229,15 +229,21 @@ def _resample_filter64(up: int, down: int, zeros: int = 10, beta: float = 5.0) -
 _rs_engines: Dict[Tuple, Engine] = {}
 
 
-def _resampler_for(device: torch.device, up: int, down: int, zeros: int, beta: float) -> Engine:
+def _cached_engine(device: torch.device, key: Tuple, load: Optional[Callable] = None) -> Engine:
+    """The Engine of ``_rs_engines`` under (device index, *key), made on first use; ``load(engine)`` puts its tables in before it is kept."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, int(up), int(down), int(zeros), float(beta))
-    eng = _rs_engines.get(key)
+    eng = _rs_engines.get((idx,) + key)
     if eng is None:
         eng = Engine(idx)
-        eng.load_resampler(resample_filter(up, down, zeros, beta), up, down)
-        _rs_engines[key] = eng
+        if load is not None:
+            load(eng)
+        _rs_engines[(idx,) + key] = eng
     return eng
+
+
+def _resampler_for(device: torch.device, up: int, down: int, zeros: int, beta: float) -> Engine:
+    return _cached_engine(device, (int(up), int(down), int(zeros), float(beta)),
+                          lambda eng: eng.load_resampler(resample_filter(up, down, zeros, beta), up, down))
 
 
 @torch.inference_mode()
@@ -274,11 +280,7 @@ def statistics_from_sums(sum_x: float, sum_x2: float, total_len: int, n_feats: i
 def _device_row_sums(mel, lengths) -> np.ndarray:
     if not mel.is_cuda:
         raise EvLibraryError("data_statistics runs on a ROCm GPU only (no CPU fallback): move the mels to the GPU")
-    idx = mel.device.index if mel.device.index is not None else torch.cuda.current_device()
-    eng = _rs_engines.get((idx, "stats"))
-    if eng is None:
-        eng = _rs_engines[(idx, "stats")] = Engine(idx)
-    return eng.mel_stats(mel, lengths).cpu().numpy()
+    return _cached_engine(mel.device, ("stats",)).mel_stats(mel, lengths).cpu().numpy()
 
 
 def data_statistics(batches: Iterable, n_feats: int = 80, row_sums: Optional[Callable] = None) -> Dict[str, float]:
@@ -305,11 +307,7 @@ def data_statistics(batches: Iterable, n_feats: int = 80, row_sums: Optional[Cal
 
 
 def _trim_engine(device: torch.device) -> Engine:
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    eng = _rs_engines.get((idx, "trim"))
-    if eng is None:
-        eng = _rs_engines[(idx, "trim")] = Engine(idx)
-    return eng
+    return _cached_engine(device, ("trim",))
 
 
 def _trim_input(y, what: str):
@@ -739,13 +737,27 @@ def third_octave_bands(fs: int = STOI_SR, nfft: int = STOI_NFFT, n_bands: int = 
 
 
 def _stoi_engine(device: torch.device) -> Engine:
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    eng = _rs_engines.get((idx, "stoi"))
-    if eng is None:
-        eng = Engine(idx)
-        eng.load_stoi(stoi_window(STOI_WINDOW), stoi_twiddle(STOI_NFFT), third_octave_bands(), STOI_HOP, STOI_NFFT, STOI_SEGMENT)
-        _rs_engines[(idx, "stoi")] = eng
-    return eng
+    return _cached_engine(device, ("stoi",), lambda eng: eng.load_stoi(stoi_window(STOI_WINDOW), stoi_twiddle(STOI_NFFT), third_octave_bands(),
+                                                                      STOI_HOP, STOI_NFFT, STOI_SEGMENT))
+
+
+def _aligned_pair(what: str, reference, degraded, lengths, on_device: bool):
+    """The shared opening of ``stoi`` and ``stft_distance``: the checks of a sample-aligned pair, then both as (B, L) batches and the rows'
+    lengths as int64 (B,) on the host, or None."""
+    if not torch.is_tensor(reference) or not torch.is_tensor(degraded) or reference.dim() not in (1, 2) or reference.shape != degraded.shape:
+        raise ValueError(f"{what}: reference and degraded must be tensors of one shape, 1-D or (B, L)")
+    if reference.shape[-1] < 1:
+        raise ValueError(f"{what}: the signals are empty")
+    if on_device and not (reference.is_cuda and degraded.is_cuda):
+        raise EvLibraryError(f"{what} runs on a ROCm GPU only (no CPU fallback): move the signals to the GPU")
+    x = reference.unsqueeze(0) if reference.dim() == 1 else reference
+    y = degraded.unsqueeze(0) if degraded.dim() == 1 else degraded
+    ln = None
+    if lengths is not None and reference.dim() == 2:
+        ln = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
+        if ln.numel() != x.shape[0]:
+            raise ValueError(f"{what}: {x.shape[0]} lengths expected, got {ln.numel()}")
+    return x, y, ln
 
 
 def _device_stoi_rows(x, y, lengths):
@@ -765,21 +777,9 @@ def stoi(reference, degraded, sr: int = 22050, lengths=None, rows: Optional[Call
     A row without a segment (under about 0.4 s of signal after the silent frames are gone) gets NaN for both scores: the published
     implementation returns 1e-5 with a warning, but a number that looks like a score is not handed out for a signal too short to score.
     ``rows``: the per-batch measurement, (x, y, lengths) at 10 kHz -> (keep, segments, score (B, 2), counts) — the device call unless given."""
-    if not torch.is_tensor(reference) or not torch.is_tensor(degraded) or reference.dim() not in (1, 2) or reference.shape != degraded.shape:
-        raise ValueError("stoi: reference and degraded must be tensors of one shape, 1-D or (B, L)")
-    if reference.shape[-1] < 1:
-        raise ValueError("stoi: the signals are empty")
     if int(sr) != sr or int(sr) < 1:
         raise ValueError(f"stoi: sr must be a positive integer (got {sr})")
-    if rows is None and not (reference.is_cuda and degraded.is_cuda):
-        raise EvLibraryError("stoi runs on a ROCm GPU only (no CPU fallback): move the signals to the GPU")
-    x = reference.unsqueeze(0) if reference.dim() == 1 else reference
-    y = degraded.unsqueeze(0) if degraded.dim() == 1 else degraded
-    ln = None
-    if lengths is not None and reference.dim() == 2:
-        ln = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
-        if ln.numel() != x.shape[0]:
-            raise ValueError(f"stoi: {x.shape[0]} lengths expected, got {ln.numel()}")
+    x, y, ln = _aligned_pair("stoi", reference, degraded, lengths, rows is None)
     if int(sr) != STOI_SR:
         up, down = resample_ratio(int(sr), STOI_SR)
         x, y = resample(x, int(sr), STOI_SR, lengths=ln), resample(y, int(sr), STOI_SR, lengths=ln)
@@ -803,15 +803,8 @@ def stft_dist_window(W: int) -> np.ndarray:
 
 
 def _stft_dist_engine(device: torch.device, resolution) -> Engine:
-    idx = device.index if device.index is not None else torch.cuda.current_device()
     nfft, hop, win = (int(v) for v in resolution)
-    key = (idx, "stft_dist", nfft, hop, win)
-    eng = _rs_engines.get(key)
-    if eng is None:
-        eng = Engine(idx)
-        eng.load_stft_dist(stft_dist_window(win), stoi_twiddle(nfft), hop, nfft)
-        _rs_engines[key] = eng
-    return eng
+    return _cached_engine(device, ("stft_dist", nfft, hop, win), lambda eng: eng.load_stft_dist(stft_dist_window(win), stoi_twiddle(nfft), hop, nfft))
 
 
 def _device_stft_dist_rows(x, y, lengths, resolution):
@@ -831,22 +824,10 @@ def stft_distance(reference, degraded, lengths=None, resolutions=MSTFT_RESOLUTIO
     "lsd_db"}; "frames" (B, R) int32}; a 1-D input gives B = 1.  A row without a frame at some resolution (not more than n_fft / 2 samples)
     gets NaN at that resolution and in every mean.  ``rows``: the per-resolution measurement, (x, y, lengths, resolution) -> (sums (B, 4),
     counts (B,)) in ev_stft_dist's terms — the device call unless given."""
-    if not torch.is_tensor(reference) or not torch.is_tensor(degraded) or reference.dim() not in (1, 2) or reference.shape != degraded.shape:
-        raise ValueError("stft_distance: reference and degraded must be tensors of one shape, 1-D or (B, L)")
-    if reference.shape[-1] < 1:
-        raise ValueError("stft_distance: the signals are empty")
     res = [tuple(int(v) for v in r) for r in resolutions]
     if not res or any(len(r) != 3 for r in res):
         raise ValueError("stft_distance: resolutions must be a non-empty list of (n_fft, hop, win)")
-    if rows is None and not (reference.is_cuda and degraded.is_cuda):
-        raise EvLibraryError("stft_distance runs on a ROCm GPU only (no CPU fallback): move the signals to the GPU")
-    x = reference.unsqueeze(0) if reference.dim() == 1 else reference
-    y = degraded.unsqueeze(0) if degraded.dim() == 1 else degraded
-    ln = None
-    if lengths is not None and reference.dim() == 2:
-        ln = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
-        if ln.numel() != x.shape[0]:
-            raise ValueError(f"stft_distance: {x.shape[0]} lengths expected, got {ln.numel()}")
+    x, y, ln = _aligned_pair("stft_distance", reference, degraded, lengths, rows is None)
     per, frames = [], []
     for nfft, hop, win in res:
         sums, counts = (rows or _device_stft_dist_rows)(x, y, ln, (nfft, hop, win))

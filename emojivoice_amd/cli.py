@@ -383,6 +383,23 @@ def prepare_dataset(args, device):
     return rep
 
 
+def filelist_batches(path, batch_size: int, sr: int, device):
+    """(chunk, batch, lens) per ``batch_size`` entries of ``parse_filelist(path)`` (none: exit): the chunk's files through
+    audio.load_audio(path, sr) as one (rows, longest) tensor on the device, zero-padded, and every row's own length in samples."""
+    from . import audio
+
+    entries = parse_filelist(path)
+    if not entries:
+        sys.exit(f"[-] {path}: no files listed")
+    for chunk in (entries[b0:b0 + batch_size] for b0 in range(0, len(entries), batch_size)):
+        ys = [audio.load_audio(wav, sr, device) for wav, _, _ in chunk]
+        lens = [int(y.shape[-1]) for y in ys]
+        batch = torch.zeros(len(ys), max(max(lens), 1), device=ys[0].device)
+        for r, y in enumerate(ys):
+            batch[r, : lens[r]] = y.reshape(-1)
+        yield chunk, batch, lens
+
+
 PROSODY_SR, PROSODY_HOP = 22050, 256    # the analysis rate and the mel's hop: frame f of the contour is mel frame f
 
 
@@ -417,17 +434,8 @@ def prosody_report(args, device):
     the same over that speaker's POOLED voiced frames, with the file count."""
     from . import audio
 
-    entries = parse_filelist(args.prosody_report)
-    if not entries:
-        sys.exit(f"[-] {args.prosody_report}: no files listed")
     files, pooled, frames_of = [], {}, {}
-    for b0 in range(0, len(entries), args.batch_size):
-        chunk = entries[b0:b0 + args.batch_size]
-        ys = [audio.load_audio(wav, PROSODY_SR, device) for wav, _, _ in chunk]
-        lens = [int(y.shape[-1]) for y in ys]
-        batch = torch.zeros(len(ys), max(max(lens), 1), device=ys[0].device)
-        for r, y in enumerate(ys):
-            batch[r, : lens[r]] = y.reshape(-1)
+    for chunk, batch, lens in filelist_batches(args.prosody_report, args.batch_size, PROSODY_SR, device):
         out = pitch_tracker(args)(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
         n_frames = [-(-n // PROSODY_HOP) for n in lens]
         st = {k: v.cpu() for k, v in audio.prosody_statistics(out["f0"], out["voiced"], n_frames).items()}
@@ -481,18 +489,9 @@ def loudness_report(args, device):
     integrated LUFS over the files that have one, and under "outliers" the files more than 3 LU from that mean."""
     from . import audio
 
-    entries = parse_filelist(args.loudness_report)
-    if not entries:
-        sys.exit(f"[-] {args.loudness_report}: no files listed")
     finite = lambda v: float(v) if math.isfinite(float(v)) else None
     files = []
-    for b0 in range(0, len(entries), args.batch_size):
-        chunk = entries[b0:b0 + args.batch_size]
-        ys = [audio.load_audio(wav, LOUDNESS_SR, device) for wav, _, _ in chunk]
-        lens = [int(y.shape[-1]) for y in ys]
-        batch = torch.zeros(len(ys), max(max(lens), 1), device=ys[0].device)
-        for r, y in enumerate(ys):
-            batch[r, : lens[r]] = y.reshape(-1)
+    for chunk, batch, lens in filelist_batches(args.loudness_report, args.batch_size, LOUDNESS_SR, device):
         out = audio.loudness(batch, LOUDNESS_SR, lengths=lens)
         integrated, blocks = out["integrated"].cpu(), out["blocks"].cpu()
         momentary = out["momentary"].cpu()

@@ -1,0 +1,1532 @@
+// Analysis kernels: dataset statistics, resampling, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness, STOI / ESTOI and the
+// STFT distance.  None of them shares code with the synthesis engine: ev_kernels.h includes this file at its end, after every helper the
+// kernels below use (the f32x4 vector type and cfm_valid_len, nothing else).  Their host entry points are in ev_analysis.h.
+#pragma once
+
+// Dataset statistics of ev_mel_stats: sum x and sum x^2 in float64 over the row's len[b] x C valid cells of a (B, C, T) mel.  One workgroup
+// per (row, 32 frames), lane = frame (32 consecutive floats of one channel row per half-wave), the eight half-waves walk the channels; the
+// same fixed shuffle tree and wave order as cfm_loss_kernel, the same per-row merge (cfm_loss_merge_kernel): no atomics.
+__global__ __launch_bounds__(256) void mel_stats_kernel(const float* __restrict__ mel, const int32_t* __restrict__ len, int C, int T,
+                                                         double* part, int ntiles) {
+    __shared__ double red[4][2];
+    const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const int t = tile * 32 + (tid & 31);
+    const int valid = cfm_valid_len(len[b], T);
+    double s1 = 0.0, s2 = 0.0;
+    if (t < valid) {
+        for (int c = tid >> 5; c < C; c += 8) {
+            const double v = (double)mel[((size_t)b * C + c) * T + t];
+            s1 += v;
+            s2 += v * v;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_down(s1, o); s2 += __shfl_down(s2, o); }
+    if ((tid & 63) == 0) { red[tid >> 6][0] = s1; red[tid >> 6][1] = s2; }
+    __syncthreads();
+    if (tid == 0) {
+        double* o = part + ((size_t)b * ntiles + tile) * 2;
+        o[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+        o[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Rational polyphase FIR resampler (ev_resample):  y[n] = sum_i x[i] taps[n down - i up + c],  c = (n_taps - 1) / 2,  x zero outside [0, len).
+// With q = n down + c, phase ph = q mod up and i0 = q / up the sum is  sum_{j = 0}^{W - 1} table[ph][j] x[i0 - j],  W = ceil(n_taps / up),
+// table[ph][j] = taps[ph + j up] (zero beyond n_taps; row stride Wp = W | 1, so the rows of different phases start on different LDS banks).
+// ARITHMETIC: one fp32 fmaf chain per output, acc = fmaf(table[ph][j], x[i0 - j], acc) for j = 0, 1, ... W - 1 from acc = +0, all W terms
+// always (a sample outside the row enters as +0 and leaves acc as it is).  The chain depends on (n, taps, the row's samples) only: not on the
+// tile, the batch or the padding behind the row.
+// One workgroup owns TILE consecutive outputs of one row (thread t: outputs t, t + 256, ...: coalesced stores).  64-bit arithmetic fixes the
+// tile's origin (q0 = n0 down + c, base_i = q0 / up, r0 = q0 mod up: n down and i up pass 2^31 for minutes of audio); inside the tile
+// everything is a 32-bit offset from it (r0 + t down <= 639 + 1023 * 640).  SX: the input span the tile reads, x[base_i - (W - 1) ..
+// base_i + (r0 + (TILE - 1) down) / up], is staged into LDS by coalesced loads (zeros outside the row); ST: so is the whole phase table
+// (16-byte copies).  Without SX / ST the kernel reads x / the table from global memory (the fallbacks of filters too long for the budget).
+// dynamic LDS: [ST: tab_floats] [SX: span] floats.
+struct ResampleParams {
+    const float* x; const int32_t* len; float* y; const float* table;
+    int L_in, L_out, up, down, c, W, Wp, span, tab_floats;
+};
+
+template <int TILE, bool SX, bool ST>
+__global__ __launch_bounds__(256) void resample_kernel(const ResampleParams p) {
+    extern __shared__ __attribute__((aligned(16))) float rs_sm[];
+    constexpr int PER = TILE / 256;
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const long long n0 = (long long)blockIdx.x * TILE;
+    int len = p.len ? p.len[b] : p.L_in;
+    if (len < 1 || len > p.L_in) len = 0;                                   // a bad row is a row of zeros (the ev_mas_align convention)
+    const long long lout = ((long long)len * p.up + p.down - 1) / p.down;   // outputs the row has: beyond them zeros
+    float* yrow = p.y + (size_t)b * p.L_out;
+    if (n0 >= lout) {                                                       // (uniform over the workgroup)
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const long long n = n0 + tid + 256 * k;
+            if (n < p.L_out) yrow[n] = 0.f;
+        }
+        return;
+    }
+    const long long q0 = n0 * p.down + p.c;
+    const long long base_i = q0 / p.up;
+    const int r0 = (int)(q0 - base_i * p.up);
+    const long long span_base = base_i - (p.W - 1);
+    const float* xrow = p.x + (size_t)b * p.L_in;
+    float* xs = rs_sm + (ST ? p.tab_floats : 0);
+    if (ST) {
+        for (int i = tid; i < p.tab_floats / 4; i += 256) ((f32x4*)rs_sm)[i] = ((const f32x4*)p.table)[i];
+    }
+    if (SX) {
+        for (int s = tid; s < p.span; s += 256) {
+            const long long gi = span_base + s;
+            xs[s] = (gi >= 0 && gi < len) ? xrow[gi] : 0.f;
+        }
+    }
+    if (SX || ST) __syncthreads();
+    const float* trow[PER];
+    int so[PER];
+    float acc[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int v = r0 + (tid + 256 * k) * p.down;
+        const int di = v / p.up, ph = v - di * p.up;
+        trow[k] = (ST ? (const float*)rs_sm : p.table) + ph * p.Wp;
+        so[k] = di + p.W - 1;                                               // x[i0] sits at xs[so]; tap j reads xs[so - j]
+        acc[k] = 0.f;
+    }
+    for (int j = 0; j < p.W; ++j) {
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            float xv;
+            if (SX) xv = xs[so[k] - j];
+            else {
+                const long long gi = span_base + so[k] - j;
+                xv = (gi >= 0 && gi < len) ? xrow[gi] : 0.f;
+            }
+            acc[k] = fmaf(trow[k][j], xv, acc[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const long long n = n0 + tid + 256 * k;
+        if (n < p.L_out) yrow[n] = n < lout ? acc[k] : 0.f;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Silence trimming and levelling (ev_trim_bounds, ev_trim_apply): librosa.effects.trim's frames and the vocoder dataset's peak gain.
+// Frame f of a row covers samples [f H - F/2, f H + F/2), zeros outside [0, len); it is non-silent iff
+// max(ms[f], 1e-10) > max(max_f ms, 1e-10) * 10^(-top_db / 10), ms[f] = (sum x^2) / F.  F = R H, so a frame is R consecutive HOP BLOCKS of
+// a grid whose origin is -off, off = (F/2) mod H (0 for even R, H/2 for odd R): block j covers samples [j H - off, (j + 1) H - off) and
+// frame f is blocks f - R/2 ... f - R/2 + R - 1.
+// ARITHMETIC of a block: each fp32 sample widened to float64 and squared (exact), summed per lane in ascending sample index -- sample c of
+// the block belongs to lane (c / 4) mod 64 -- then one fixed shuffle tree over the wave.  One wave owns a whole block, so its sum depends
+// on the block's samples only: not on the tile, the batch, the padding behind the row or the row's alignment (an unaligned row takes
+// 4-byte loads in the same lane assignment).  No atomics.
+struct TrimBlocksParams {
+    const float* x; const int32_t* len; double* bsum; float* bmax;     // bsum, bmax: (B, nblk)
+    int L, H, off, nblk;
+};
+
+constexpr int TRIM_TILE = 8;                                            // hop blocks per workgroup: two per wave
+
+__global__ __launch_bounds__(256) void trim_blocks_kernel(const TrimBlocksParams p) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;                                  // a bad row is a row of zeros (the ev_mas_align convention)
+    const float* xrow = p.x + (size_t)b * p.L;
+    const bool vec = (((size_t)xrow) & 15) == 0;                        // (H and off are multiples of 32 samples: every block keeps the row's alignment)
+    for (int k = wave; k < TRIM_TILE; k += 4) {                         // (uniform over the wave)
+        const long long j = (long long)blockIdx.x * TRIM_TILE + k;
+        if (j >= p.nblk) break;
+        const long long s0 = j * p.H - p.off;                           // the block's first sample: -off for j = 0
+        double acc = 0.0;
+        float pk = 0.f;
+        for (int c = 4 * lane; c < p.H; c += 256) {
+            const long long i = s0 + c;                                 // (a multiple of 4: i < 0 means the whole quad is left of the row)
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            if (i >= 0 && i + 4 <= len) {
+                if (vec) {
+                    const f32x4 q = *(const f32x4*)(xrow + i);
+                    v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = xrow[i + e];
+                }
+            } else if (i >= 0) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if (i + e < len) v[e] = xrow[i + e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double d = (double)v[e];
+                acc += d * d;
+                pk = fmaxf(pk, fabsf(v[e]));
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { acc += __shfl_down(acc, o); pk = fmaxf(pk, __shfl_down(pk, o)); }
+        if (lane == 0) { p.bsum[(size_t)b * p.nblk + j] = acc; p.bmax[(size_t)b * p.nblk + j] = pk; }
+    }
+}
+
+// One workgroup per row over the block sums: frame sums (R blocks in ascending order, blocks outside the row +0), ref = max_f ms, the
+// predicate, the first and last non-silent frame, start = f_first H, end = min(len, (f_last + 1) H) and the row's peak (max of the block
+// maxima).  Every reduction is a max or a min: the thread count does not enter the result.  A bad row, or one without a non-silent frame
+// (top_db <= 0), gets bounds (0, 0).
+struct TrimBoundsParams {
+    const double* bsum; const float* bmax; const int32_t* len; int32_t* bounds; float* peak;
+    int L, H, R, off, nblk;
+    double F, thr;                                                      // thr = 10^(-top_db / 10)
+};
+
+__device__ __forceinline__ double trim_frame_ms(const double* bs, int f, int R, int nb, double F) {
+    const int j0 = f - R / 2;
+    double s = 0.0;
+    for (int r = 0; r < R; ++r) {
+        const int j = j0 + r;
+        s += (j >= 0 && j < nb) ? bs[j] : 0.0;
+    }
+    return s / F;
+}
+
+__global__ __launch_bounds__(256) void trim_bounds_kernel(const TrimBoundsParams p) {
+    __shared__ double red_d[4];
+    __shared__ float red_f[4];
+    __shared__ int red_i[4][2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;
+    const int nf = len ? 1 + len / p.H : 0;
+    const int nb = len ? (int)(((long long)len + p.off + p.H - 1) / p.H) : 0;   // blocks that hold a sample of the row (<= nblk)
+    const double* bs = p.bsum + (size_t)b * p.nblk;
+    const float* bm = p.bmax + (size_t)b * p.nblk;
+    double ref = 0.0;
+    float pk = 0.f;
+    for (int f = tid; f < nf; f += 256) ref = fmax(ref, trim_frame_ms(bs, f, p.R, nb, p.F));
+    for (int j = tid; j < nb; j += 256) pk = fmaxf(pk, bm[j]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { ref = fmax(ref, __shfl_down(ref, o)); pk = fmaxf(pk, __shfl_down(pk, o)); }
+    if ((tid & 63) == 0) { red_d[tid >> 6] = ref; red_f[tid >> 6] = pk; }
+    __syncthreads();
+    ref = fmax(fmax(red_d[0], red_d[1]), fmax(red_d[2], red_d[3]));
+    pk = fmaxf(fmaxf(red_f[0], red_f[1]), fmaxf(red_f[2], red_f[3]));
+    const double cut = fmax(ref, 1e-10) * p.thr;
+    int first = 0x7fffffff, last = -1;
+    for (int f = tid; f < nf; f += 256) {
+        if (fmax(trim_frame_ms(bs, f, p.R, nb, p.F), 1e-10) > cut) { first = min(first, f); last = max(last, f); }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { first = min(first, __shfl_down(first, o)); last = max(last, __shfl_down(last, o)); }
+    if ((tid & 63) == 0) { red_i[tid >> 6][0] = first; red_i[tid >> 6][1] = last; }
+    __syncthreads();
+    if (tid == 0) {
+        first = min(min(red_i[0][0], red_i[1][0]), min(red_i[2][0], red_i[3][0]));
+        last = max(max(red_i[0][1], red_i[1][1]), max(red_i[2][1], red_i[3][1]));
+        int start = 0, end = 0;
+        if (last >= 0) {
+            start = (int)((long long)first * p.H);
+            end = (int)min((long long)len, ((long long)last + 1) * p.H);
+        }
+        p.bounds[2 * b] = start;
+        p.bounds[2 * b + 1] = end;
+        if (p.peak) p.peak[b] = pk;
+    }
+}
+
+// y[b, j] = x[b, start[b] + j] * gain[b] for j < min(end[b] - start[b], L_out), +0 up to L_out; out_len[b] = that count.  Bounds and peak
+// come from device memory; gain = target / peak[b] (one correctly rounded fp32 division) when a peak is given, target > 0 and peak > 0,
+// else 1 (x * 1 is x: a bit-exact copy).  Bounds outside 0 <= start <= end <= L make a row of zeros.  One workgroup per (row, 1024
+// outputs); 16-byte stores where the output row is aligned (the source starts at an arbitrary sample: 4-byte loads).
+struct TrimApplyParams {
+    const float* x; const int32_t* bounds; const float* peak; float* y; int32_t* out_len;
+    float target;
+    int L, L_out;
+};
+
+__global__ __launch_bounds__(256) void gather_scale_kernel(const TrimApplyParams p) {
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int start = p.bounds[2 * b];
+    const int end = p.bounds[2 * b + 1];
+    int n = 0;
+    if (start >= 0 && end >= start && end <= p.L) n = min(end - start, p.L_out);
+    else start = 0;
+    float g = 1.f;
+    if (p.peak && p.target > 0.f) {
+        const float pk = p.peak[b];
+        if (pk > 0.f) g = __fdiv_rn(p.target, pk);
+    }
+    if (blockIdx.x == 0 && tid == 0) p.out_len[b] = n;
+    const float* xs = p.x + (size_t)b * p.L + start;
+    float* yrow = p.y + (size_t)b * p.L_out;
+    const long long j0 = (long long)blockIdx.x * 1024;
+    if ((((size_t)yrow) & 15) == 0) {
+        const long long j = j0 + 4 * tid;
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (j + e < n) ? xs[j + e] * g : 0.f;
+        if (j + 4 <= p.L_out) { const f32x4 q = {v[0], v[1], v[2], v[3]}; *(f32x4*)(yrow + j) = q; }
+        else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (j + e < p.L_out) yrow[j + e] = v[e];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long long j = j0 + tid + 256 * k;
+            if (j < p.L_out) yrow[j] = (j < n) ? xs[j] * g : 0.f;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Pitch tracking (ev_pitch_yin): de Cheveigne and Kawahara's YIN without its last ("best local estimate") step.  Frame f of a row
+// analyses the span x[s_f + i], 0 <= i < W + tau_max + 1, s_f = f H + H/2 - (W + tau_max) / 2, zeros outside [0, len):
+//   d(tau)  = sum_{j < W} (x[j] - x[j + tau])^2                       1 <= tau <= n = tau_max + 1
+//   d'(tau) = d(tau) * tau / S(tau), S(tau) = sum_{k <= tau} d(k)     (1 where S(tau) is not > 0)
+//   tau0    = the smallest tau in [tau_min, tau_max] with d'(tau) < threshold, then walked down to the local minimum on its right;
+//   period  = tau0 + the parabola's vertex through d'(tau0 - 1), d'(tau0), d'(tau0 + 1)
+// One workgroup of four waves per (frame, row).  The span is staged in LDS once, as fp32.  TILE: lane l of every wave owns the lags
+// 1 + l + 64 c of lag chunk c, four chunks at a time (one broadcast read of x[j] serves four lags; x[j + tau] over consecutive lags is
+// conflict-free); wave q covers the quarter q W/4 <= j < (q + 1) W/4 of the window for EVERY lag, so the four SIMDs carry equal work
+// whatever tau_max is.
+// ARITHMETIC of d(tau): both samples widened to float64, the difference (exact) squared and added by one fma per term, in ascending j
+// inside a quarter; d = (P0 + P1) + (P2 + P3) over the quarters' partials.  S is one ascending chain of float64 adds (one lane), d' =
+// (d * tau) / S in float64, and the decision runs in wave 0.  Nothing depends on the batch, the grid, the padding behind a row or
+// ev_set_arithmetic; no atomics.
+// LDS: 4 n float64 (the partials; later d, S and d' in place) and W + n fp32: at most 64 KiB + 24 KiB at tau_max = 2048,
+// 16.0 KiB at the defaults (W 1024, tau_max 340).
+struct PitchYinParams {
+    const float* x; const int32_t* len; int32_t* lag; float* period; float* cmnd;
+    int L, F, W, H, tau_min, tau_max;
+    double thr;
+};
+
+// The partial sums of wave `lane`'s lags in chunks c0 .. c0 + NK - 1 over j0 <= j < j1
+template <int NK>
+__device__ __forceinline__ void pitch_yin_pass(const float* xs, double* part, int c0, int n, int j0, int j1, int lane) {
+    int t[NK];
+    double a[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) { t[k] = min(1 + lane + 64 * (c0 + k), n); a[k] = 0.0; }   // (a lane past the last lag repeats it and stores nothing)
+    for (int j = j0; j < j1; ++j) {
+        const double xj = (double)xs[j];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const double d = xj - (double)xs[j + t[k]];
+            a[k] = fma(d, d, a[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int tau = 1 + lane + 64 * (c0 + k);
+        if (tau <= n) part[tau - 1] = a[k];
+    }
+}
+
+// Frame f of a row of len valid samples: stages its span and leaves d'(tau), 1 <= tau <= n = tau_max + 1, at index tau - 1 of the returned
+// LDS array (n float64; the n before it hold S, the n before those d).  Every thread of the 256 calls it; it ends on a barrier.  smem:
+// 4 n float64 + W + n fp32.  Shared by pitch_yin_kernel and pyin_observe_kernel: one framing, one d, one S chain, one d'.
+__device__ __forceinline__ const double* pitch_cmnd_frame(float* smem, const float* xrow, int len, int f, int W, int H, int tau_max, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int n = tau_max + 1, span = W + n;
+    double* part = (double*)smem;                                       // [4][n]: a quarter's partials; then row 0 = d, row 1 = S, row 2 = d'
+    float* xs = (float*)(part + 4 * (size_t)n);                         // [span]
+    const long long s0 = (long long)f * H + H / 2 - (W + tau_max) / 2;
+    for (int i = tid; i < span; i += 256) {
+        const long long g = s0 + i;
+        xs[i] = (g >= 0 && g < len) ? xrow[g] : 0.f;
+    }
+    __syncthreads();
+    const int nch = (n + 63) >> 6, jq = W >> 2;
+    double* mine = part + (size_t)wave * n;
+    for (int c0 = 0; c0 < nch; c0 += 4) {                               // (uniform over the wave)
+        const int nk = min(4, nch - c0), j0 = wave * jq, j1 = j0 + jq;
+        if (nk == 4) pitch_yin_pass<4>(xs, mine, c0, n, j0, j1, lane);
+        else if (nk == 3) pitch_yin_pass<3>(xs, mine, c0, n, j0, j1, lane);
+        else if (nk == 2) pitch_yin_pass<2>(xs, mine, c0, n, j0, j1, lane);
+        else pitch_yin_pass<1>(xs, mine, c0, n, j0, j1, lane);
+    }
+    __syncthreads();
+    double* dd = part;
+    double* S = part + n;
+    double* cm = part + 2 * (size_t)n;
+    for (int i = tid; i < n; i += 256) dd[i] = (part[i] + part[n + i]) + (part[2 * (size_t)n + i] + part[3 * (size_t)n + i]);
+    __syncthreads();
+    if (tid == 0) {                                                     // S(tau): ONE ascending chain
+        double s = 0.0;
+        for (int i = 0; i < n; ++i) { s += dd[i]; S[i] = s; }
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {                                // (index i holds lag tau = i + 1)
+        const double s = S[i];
+        cm[i] = s > 0.0 ? dd[i] * (double)(i + 1) / s : 1.0;
+    }
+    __syncthreads();
+    return cm;
+}
+
+__global__ __launch_bounds__(256) void pitch_yin_kernel(const PitchYinParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t o = (size_t)b * p.F + f;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;                                  // a bad row is a row of zeros (the ev_mas_align convention)
+    const int nf = (int)(((long long)len + p.H - 1) / p.H);
+    if (f >= nf) {                                                      // (uniform over the workgroup)
+        if (tid == 0) {
+            if (p.lag) p.lag[o] = 0;
+            if (p.period) p.period[o] = 0.f;
+            if (p.cmnd) p.cmnd[o] = 0.f;
+        }
+        return;
+    }
+    const double* cm = pitch_cmnd_frame(smem, p.x + (size_t)b * p.L, len, f, p.W, p.H, p.tau_max, tid);
+    if (wave != 0) return;
+    int first = 0x7fffffff;
+    double mn = 1.0 / 0.0;
+    for (int tau = p.tau_min + lane; tau <= p.tau_max; tau += 64) {
+        const double v = cm[tau - 1];
+        if (v < p.thr) first = min(first, tau);
+        mn = fmin(mn, v);
+    }
+#pragma unroll
+    for (int sft = 32; sft > 0; sft >>= 1) { first = min(first, __shfl_down(first, sft)); mn = fmin(mn, __shfl_down(mn, sft)); }
+    if (lane != 0) return;
+    int tau0 = 0;
+    float per = 0.f;
+    double ap = mn;                                                     // unvoiced: the smallest d' of the search range
+    if (first != 0x7fffffff) {
+        tau0 = first;
+        while (tau0 + 1 <= p.tau_max && cm[tau0] < cm[tau0 - 1]) ++tau0;
+        const double a = cm[tau0 - 2], bq = cm[tau0 - 1], c = cm[tau0];  // tau0 >= 2: d'(1) is 1 and threshold <= 1; tau0 + 1 <= n
+        const double den = a - 2.0 * bq + c;
+        double shift = 0.0;
+        if (den > 0.0) {
+            shift = 0.5 * (a - c) / den;
+            if (!(fabs(shift) <= 1.0)) shift = 0.0;
+        }
+        per = (float)((double)tau0 + shift);
+        ap = bq;
+    }
+    if (p.lag) p.lag[o] = tau0;
+    if (p.period) p.period[o] = per;
+    if (p.cmnd) p.cmnd[o] = (float)ap;
+}
+
+// ---------------------------------------------------------------------------
+// Probabilistic YIN, the observation (ev_pyin_observe): Mauch and Dixon's pYIN over the d' of pitch_cmnd_frame, d'(0) := 1.  Per frame:
+//   troughs   tau in [tau_min, tau_max] with d'(tau) < d'(tau - 1) and d'(tau) <= d'(tau + 1), ascending (no two are adjacent: K <= kmax =
+//             (tau_max - tau_min) / 2 + 1); trough k has ONE activation index a_k = the least t with d'(tau_k) < t / n_thr (n_thr + 1: none)
+//   P_k       sum over t >= a_k, ascending, of G_t E[pos(k, t)]: E[p] = exp(-lambda p), pos(k, t) = #{m < k : a_m <= t}, N(t) = #{m : a_m <= t},
+//             G_t = w_t (1 - e^-lambda) / (1 - E[N(t)]); the trough g of least d' (lowest lag on ties) gains no_trough_prob * cw[a_g - 1],
+//             cw the host's ascending prefix sums of w
+//   bin_k     clip(rint(bpo log2(sr / (period_k fmin))), 0, n_bins - 1), period_k = tau_k + pitch_yin_kernel's parabolic shift
+//   obs[bin_k] += P_k (P_k > 0) in ascending k; pv = min(sum_i obs[i], 1) in ascending i
+// One workgroup of four waves per (frame, row), as pitch_yin_kernel.  Trough k = tid + 256 r is thread tid's: wave q holds the 64-trough
+// blocks q, q + 4, ...  pos comes from ballots: a first sweep over t counts each block's active troughs (cnt[block][t], one lane stores),
+// n_thr threads turn the counts into exclusive prefixes over the blocks, N(t) and G_t, and a second sweep adds G_t E[prefix + the active
+// lanes below mine].  period_k does not decrease with k (the lags differ by >= 2, the shifts by <= 2), so equal bins are RUNS of k: the first
+// trough of a run sums it in ascending k and stores the bin: no atomics, no read-modify-write between threads.  One lane sums pv.
+// LDS beyond pitch_cmnd_frame's: (2 kmax + n_thr + n_bins + 6) float64 + (3 kmax + ceil(kmax / 64) (n_thr + 1) + 8) int32: 9.2 KiB at the
+// defaults (kmax 153, n_thr 100, 385 bins), 46 KiB at the limits.  Nothing depends on the batch, the grid or the padding behind a row.
+struct PyinObserveParams {
+    const float* x; const int32_t* len; double* obs; double* pv;
+    int L, F, W, H, tau_min, tau_max, n_bins, n_thr, kmax, off_extra;
+    double sr, fmin, bpo, lambda, c0, ntp;
+    double w[128];                      // w_t at t - 1
+    double cw[129];                     // cw[t] = w_1 + ... + w_t, one ascending chain; cw[0] = 0
+};
+
+__global__ __launch_bounds__(256) void pyin_observe_kernel(const PyinObserveParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t o = (size_t)b * p.F + f;
+    double* orow = p.obs + o * (size_t)p.n_bins;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;                                  // a bad row is a row of zeros
+    const int nf = (int)(((long long)len + p.H - 1) / p.H);
+    if (f >= nf) {                                                      // (uniform over the workgroup)
+        for (int i = tid; i < p.n_bins; i += 256) orow[i] = 0.0;
+        if (tid == 0) p.pv[o] = 0.0;
+        return;
+    }
+    const double* cm = pitch_cmnd_frame(smem, p.x + (size_t)b * p.L, len, f, p.W, p.H, p.tau_max, tid);
+    const int kmax = p.kmax, n_thr = p.n_thr, n_bins = p.n_bins, ldc = n_thr + 1;
+    double* E = (double*)((unsigned char*)smem + p.off_extra);          // [kmax + 1]
+    double* P = E + kmax + 1;                                           // [kmax]
+    double* G = P + kmax;                                               // [n_thr + 1]
+    double* ob = G + ldc;                                               // [n_bins]
+    double* rv = ob + n_bins;                                           // [4]
+    int* tl = (int*)(rv + 4);                                           // [kmax] trough lags
+    int* act = tl + kmax;                                               // [kmax] activation indices
+    int* bn = act + kmax;                                               // [kmax] bins
+    int* wt = bn + kmax;                                                // [4] troughs found per wave
+    int* ri = wt + 4;                                                   // [4]
+    int* cnt = ri + 4;                                                  // [ceil(kmax / 64)][n_thr + 1]
+    // 1. the troughs, in ascending lag: thread tid looks at a contiguous piece of the range, a scan of the counts places them
+    const int m = p.tau_max - p.tau_min + 1, seg = (m + 255) >> 8;
+    const int ta = p.tau_min + tid * seg, tb = min(ta + seg, p.tau_max + 1);
+    int found = 0;
+    for (int tau = ta; tau < tb; ++tau) {
+        const double v = cm[tau - 1], l = tau > 1 ? cm[tau - 2] : 1.0;
+        found += (v < l && v <= cm[tau]) ? 1 : 0;
+    }
+    int inc = found;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) { const int u = __shfl_up(inc, s); if (lane >= s) inc += u; }
+    if (lane == 63) wt[wave] = inc;
+    for (int i = tid; i < n_bins; i += 256) ob[i] = 0.0;
+    __syncthreads();
+    int k0 = inc - found;
+    for (int q = 0; q < wave; ++q) k0 += wt[q];
+    const int K = min(wt[0] + wt[1] + wt[2] + wt[3], kmax);
+    for (int tau = ta; tau < tb; ++tau) {
+        const double v = cm[tau - 1], l = tau > 1 ? cm[tau - 2] : 1.0;
+        if (v < l && v <= cm[tau]) { if (k0 < kmax) tl[k0] = tau; ++k0; }
+    }
+    for (int i = tid; i <= K; i += 256) E[i] = exp(-p.lambda * (double)i);
+    if (K == 0) {                                                       // (uniform) a silent frame, or one without a trough
+        for (int i = tid; i < n_bins; i += 256) orow[i] = 0.0;
+        if (tid == 0) p.pv[o] = 0.0;
+        return;
+    }
+    __syncthreads();
+    // 2. per trough: activation index, period, bin; the trough of least d'
+    const double nd = (double)n_thr;
+    double bv = 1.0 / 0.0;
+    int bk = 0x7fffffff;
+    for (int k = tid; k < K; k += 256) {
+        const int tau = tl[k];
+        const double a = tau > 1 ? cm[tau - 2] : 1.0, bq = cm[tau - 1], c = cm[tau];
+        int at = n_thr + 1;
+        if (bq < 1.0) {
+            at = min(max((int)(bq * nd) + 1, 1), n_thr);
+            while (at > 1 && bq < (double)(at - 1) / nd) --at;
+            while (at <= n_thr && !(bq < (double)at / nd)) ++at;
+        }
+        act[k] = at;
+        const double den = a - 2.0 * bq + c;
+        double shift = 0.0;
+        if (den > 0.0) {
+            shift = 0.5 * (a - c) / den;
+            if (!(fabs(shift) <= 1.0)) shift = 0.0;
+        }
+        const double q = rint(p.bpo * log2(p.sr / (((double)tau + shift) * p.fmin)));
+        bn[k] = (int)fmin(fmax(q, 0.0), (double)(n_bins - 1));
+        if (bq < bv) { bv = bq; bk = k; }                               // (ascending k: the lowest lag of the least)
+    }
+#pragma unroll
+    for (int sft = 32; sft > 0; sft >>= 1) {
+        const double ov = __shfl_down(bv, sft);
+        const int ok = __shfl_down(bk, sft);
+        if (ov < bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
+    }
+    if (lane == 0) { rv[wave] = bv; ri[wave] = bk; }
+    // 3. first sweep: the active troughs of each block at each threshold
+    const int nblk = (K + 63) >> 6;
+    for (int kb = wave; kb < nblk; kb += 4) {                           // (uniform over the wave; trough 64 kb + lane is this thread's own)
+        const int k = 64 * kb + lane, at = k < K ? act[k] : n_thr + 1;
+        for (int t = 1; t <= n_thr; ++t) {
+            const unsigned long long bal = __ballot(at <= t);
+            if (lane == 0) cnt[kb * ldc + t] = __popcll(bal);
+        }
+    }
+    __syncthreads();
+    int g = ri[0];
+    {
+        double gv = rv[0];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) if (rv[q] < gv || (rv[q] == gv && ri[q] < g)) { gv = rv[q]; g = ri[q]; }
+    }
+    for (int t = 1 + tid; t <= n_thr; t += 256) {
+        int run = 0;
+        for (int kb = 0; kb < nblk; ++kb) { const int c = cnt[kb * ldc + t]; cnt[kb * ldc + t] = run; run += c; }
+        G[t] = run > 0 ? p.w[t - 1] * p.c0 / (1.0 - E[run]) : 0.0;
+    }
+    __syncthreads();
+    // 4. second sweep: P_k
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int kb = wave; kb < nblk; kb += 4) {
+        const int k = 64 * kb + lane, at = k < K ? act[k] : n_thr + 1;
+        double acc = 0.0;
+        for (int t = 1; t <= n_thr; ++t) {
+            const unsigned long long bal = __ballot(at <= t);
+            if (at <= t) acc += G[t] * E[cnt[kb * ldc + t] + __popcll(bal & below)];
+        }
+        if (k == g) acc += p.ntp * p.cw[at - 1];
+        if (k < K) P[k] = acc;
+    }
+    __syncthreads();
+    // 5. runs of equal bins into obs, then pv
+    for (int k = tid; k < K; k += 256) {
+        const int bin = bn[k];
+        if (k > 0 && bn[k - 1] == bin) continue;
+        double s = 0.0;
+        for (int q = k; q < K && bn[q] == bin; ++q) if (P[q] > 0.0) s += P[q];
+        ob[bin] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int i = 0; i < n_bins; ++i) s += ob[i];
+        p.pv[o] = fmin(s, 1.0);
+    }
+    for (int i = tid; i < n_bins; i += 256) orow[i] = ob[i];
+}
+
+// ---------------------------------------------------------------------------
+// Probabilistic YIN, the decoding (ev_pyin_decode): Viterbi over the 2 n_bins states s = v n_bins + i (v = 0 voiced, 1 unvoiced) of one
+// row, one workgroup per row, sequential in time like dtw_kernel.  Thread t owns the states t and t + blockDim.x.  Per frame and state:
+//   l      = log(e + tiny), e = obs[i] (voiced) or (1 - pv) / n_bins (unvoiced)
+//   delta  = max over v' in {0, 1}, j in [i - R, i + R] within [0, n_bins), in ascending s' = v' n_bins + j, a later one replacing an
+//            earlier one only when STRICTLY greater, of dz[s'] + T[|i - j|], plus l; dz[s'] = delta_prev[s'] - log Z_j is what LDS holds,
+//            T = t_stay (v' = v) or t_switch, log_tri[d] + log_stay / log_switch, formed on the host
+// so the recursion is one float64 add and one compare per candidate: 2 (2 R + 1) of them per state; both T tables sit in LDS (128 float64).  dz is double-buffered: frame t reads
+// buffer (t - 1) & 1 and writes t & 1: ONE barrier per frame.  The back-pointer byte v' (2 R + 1) + (j - i + R) goes to the caller's d_back;
+// after the last frame the lowest state of greatest delta is found by a reduction and lane 0 walks the bytes back (F dependent loads).
+// log Z_j reaches the kernel in 128 doubles: all of it for n_bins <= 128; else its first 64, its last 64 and between them the constant
+// they both end on (R <= 63: Z_j is constant for R <= j <= n_bins - 1 - R; the host checks that the caller's table is).
+struct PyinDecodeParams {
+    const double* obs; const double* pv; const int32_t* len; unsigned char* back; int32_t* state; double* loglik;
+    int L, F, H, n_bins, R;
+    double init, tiny;                  // -log(2 n_bins); the smallest normal double
+    double t_stay[64], t_switch[64];
+    double zc[128];
+};
+
+__global__ __launch_bounds__(1024) void pyin_decode_kernel(const PyinDecodeParams p) {
+    extern __shared__ __attribute__((aligned(16))) double pyin_lds[];
+    const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const int nb = p.n_bins, S = 2 * nb, R = p.R, F = p.F;
+    int len = p.len ? p.len[b] : p.L;
+    if (len < 1 || len > p.L) len = 0;
+    const int nf = (int)(((long long)len + p.H - 1) / p.H);
+    int32_t* st = p.state + (size_t)b * F;
+    if (nf == 0) {                                                      // a bad row (uniform): no path, log-likelihood 0
+        for (int t = tid; t < F; t += NT) st[t] = -1;
+        if (tid == 0) p.loglik[b] = 0.0;
+        return;
+    }
+    double* dz = pyin_lds;                                              // [2][S]
+    double* rv = pyin_lds + 2 * (size_t)S;                              // [16]
+    double* tT = rv + 16;                                               // [2][64]: t_stay, t_switch (a broadcast LDS read per candidate)
+    int* ri = (int*)(tT + 128);                                         // [16]
+    for (int d = tid; d <= R; d += NT) { tT[d] = p.t_stay[d]; tT[64 + d] = p.t_switch[d]; }   // (read from frame 1 on: behind frame 0's barrier)
+    const double* ob = p.obs + (size_t)b * F * nb;
+    const double* pvr = p.pv + (size_t)b * F;
+    unsigned char* back = p.back + (size_t)b * F * S;
+    int si[2], sv[2];
+    bool have[2];
+    double lz[2], delta[2], e[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int s = tid + u * NT;
+        have[u] = s < S;
+        sv[u] = (have[u] && s >= nb) ? 1 : 0;
+        si[u] = have[u] ? s - sv[u] * nb : 0;
+        const int j = si[u];
+        lz[u] = nb <= 128 ? p.zc[j] : (j < 64 ? p.zc[j] : (j >= nb - 64 ? p.zc[j - (nb - 128)] : p.zc[64]));
+        delta[u] = 0.0;
+        e[u] = !have[u] ? 0.0 : (sv[u] ? (1.0 - pvr[0]) / (double)nb : ob[si[u]]);
+    }
+    for (int t = 0; t < nf; ++t) {
+        double en[2] = {0.0, 0.0};
+        if (t + 1 < nf) {                                               // the next frame's emissions travel while this one is decided
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                if (have[u]) en[u] = sv[u] ? (1.0 - pvr[t + 1]) / (double)nb : ob[(size_t)(t + 1) * nb + si[u]];
+        }
+        const double* prev = dz + (size_t)((t - 1) & 1) * S;
+        double* cur = dz + (size_t)(t & 1) * S;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (!have[u]) continue;
+            const double l = log(e[u] + p.tiny);
+            if (t == 0) delta[u] = p.init + l;
+            else {
+                const int i = si[u];
+                double best = -1.0 / 0.0;
+                int arg = 0;
+                for (int vp = 0; vp < 2; ++vp) {
+                    const double* pr = prev + vp * nb;
+                    const double* T = tT + (vp == sv[u] ? 0 : 64);
+                    const int base = vp * (2 * R + 1) + R;
+#pragma unroll 4
+                    for (int d = -R; d <= R; ++d) {                     // ascending j = i + d; a j outside the bins is a candidate of -inf
+                        const int j = i + d, ad = d < 0 ? -d : d;
+                        const double c = (j >= 0 && j < nb) ? pr[min(max(j, 0), nb - 1)] + T[ad] : -1.0 / 0.0;
+                        if (c > best) { best = c; arg = base + d; }
+                    }
+                }
+                delta[u] = best + l;
+                back[(size_t)t * S + tid + u * NT] = (unsigned char)arg;
+            }
+            cur[tid + u * NT] = delta[u] - lz[u];
+        }
+        e[0] = en[0]; e[1] = en[1];
+        __syncthreads();
+    }
+    // the end state: the lowest s of greatest delta
+    double bv = -1.0 / 0.0;
+    int bs = 0x7fffffff;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) if (have[u] && delta[u] > bv) { bv = delta[u]; bs = tid + u * NT; }
+#pragma unroll
+    for (int sft = 32; sft > 0; sft >>= 1) {
+        const double ov = __shfl_down(bv, sft);
+        const int os = __shfl_down(bs, sft);
+        if (ov > bv || (ov == bv && os < bs)) { bv = ov; bs = os; }
+    }
+    if (lane == 0) { rv[wave] = bv; ri[wave] = bs; }
+    __syncthreads();
+    for (int t = nf + tid; t < F; t += NT) st[t] = -1;
+    if (tid != 0) return;
+    const int nw = (NT + 63) >> 6;
+    bv = rv[0]; bs = ri[0];
+    for (int q = 1; q < nw; ++q) if (rv[q] > bv || (rv[q] == bv && ri[q] < bs)) { bv = rv[q]; bs = ri[q]; }
+    p.loglik[b] = bv;
+    int s = bs;
+    for (int t = nf - 1; t >= 0; --t) {
+        st[t] = s;
+        if (t == 0) break;
+        const int code = back[(size_t)t * S + s], vp = min(code / (2 * R + 1), 1), d = code - vp * (2 * R + 1) - R;
+        const int v = s >= nb ? 1 : 0;
+        s = vp * nb + min(max(s - v * nb + d, 0), nb - 1);             // (the clamp keeps a damaged byte inside the row's states)
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Dynamic time warping (ev_dtw): the sibling of mas_search_kernel.  For a row with tx x ty cells
+//   c[i, j] = sum_c (x[c, i] - y[c, j])^2 (float64, one fma per channel in ascending c; one __dsqrt_rn for metric 0)
+//   D[i, j] = c[i, j] + min(D[i-1, j-1], D[i-1, j], D[i, j-1]) over the predecessors that exist, a later one replacing an earlier one
+//             only when strictly smaller; S[i, j] = S[chosen] + 1, S[0, 0] = 1
+// One workgroup per row walks the tx + ty - 1 anti-diagonals k = i + j, one barrier each.  Thread t owns the matrix rows i = t + r NT,
+// r < R.  A ring of three diagonals of D (float64) and of S (16 bits: S <= 8191) lives in LDS, indexed by i: diagonal k is written to
+// buffer k % 3 while k - 1 (up, at i - 1) and k - 2 (diagonal, at i - 1) are read, which is why one barrier per diagonal is enough;
+// the left neighbour D[i, j - 1] is the thread's own previous cell and stays in a register.  The cell does exactly the sequential
+// loop's arithmetic: the wavefront is the only parallelism.
+// Local costs: W diagonals ahead of the DP each thread forms the W cells of its rows into REGISTERS (acc[R][W]): x[c, i] is read once
+// per channel and block, y[c, k - i] W times, both coalesced over i; columns are clamped into [0, ty), so nothing behind a row's length
+// is read and cells outside the matrix cost nothing that is used.  The cost matrix never exists in memory.
+// Decision: 2 bits per cell (0 diagonal, 1 up, 2 left), 32 cells of a matrix row per 64-bit word, gathered in a register and stored
+// once per 32 columns at word (j / 32) * Tx + i: in LDS where they fit beside the ring, else in the handle's arena (p.gbits); none
+// when no path is asked for.  Thread 0 replays the bits from (tx-1, ty-1) into an LDS stage that reuses the ring (K = S[tx-1, ty-1]
+// is known, so entry k goes to slot k), then the workgroup writes the path in ascending order and the -1 tail.
+// No atomics; nothing depends on B, Tx, Ty, the block size or ev_set_arithmetic.
+struct DtwParams {
+    const float* x; const float* y; const int32_t* xlen; const int32_t* ylen;
+    double* cost; int32_t* steps; int32_t* path;
+    unsigned long long* gbits;          // decision words per row [nyw][Tx], or NULL: in LDS (or no path)
+    int C, Tx, Ty, nyw, metric;
+    int off_s, off_bits;                // LDS plan in bytes (the D ring, and later the path stage, are at 0)
+};
+
+template <int R, int W>
+__global__ __launch_bounds__(1024) void dtw_kernel(const DtwParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dtw_lds[];
+    __shared__ int dtw_K;
+    const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+    const int C = p.C, Tx = p.Tx, Ty = p.Ty, NP = Tx + Ty - 1;
+    int tx = p.xlen ? p.xlen[b] : Tx, ty = p.ylen ? p.ylen[b] : Ty;
+    int32_t* path = p.path ? p.path + (size_t)b * NP * 2 : nullptr;
+    if (tx < 1 || ty < 1 || tx > Tx || ty > Ty) {                       // a bad row (uniform over the workgroup): cost 0, steps 0, path -1
+        if (tid == 0) { p.cost[b] = 0.0; p.steps[b] = 0; }
+        if (path) for (int e = tid; e < 2 * NP; e += NT) path[e] = -1;
+        return;
+    }
+    double* ring = (double*)dtw_lds;                                    // [3][Tx]
+    unsigned short* sring = (unsigned short*)(dtw_lds + p.off_s);       // [3][Tx]
+    unsigned long long* bits = !path ? nullptr : (p.gbits ? p.gbits + (size_t)b * p.nyw * Tx : (unsigned long long*)(dtw_lds + p.off_bits));
+    const float* xb = p.x + (size_t)b * C * Tx;
+    const float* yb = p.y + (size_t)b * C * Ty;
+    double leftD[R];
+    int leftS[R];
+    unsigned long long word[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) { leftD[r] = 0.0; leftS[r] = 0; word[r] = 0ull; }
+    double* d0 = ring;                                                  // diagonal k
+    double* d1 = ring + Tx;                                             // k - 1
+    double* d2 = ring + 2 * Tx;                                         // k - 2
+    unsigned short* s0 = sring;
+    unsigned short* s1 = sring + Tx;
+    unsigned short* s2 = sring + 2 * Tx;
+    const int nk = tx + ty - 1;
+    for (int k0 = 0; k0 < nk; k0 += W) {
+        double acc[R][W];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) acc[r][w] = 0.0;
+            const int i = tid + r * NT, j0 = k0 - i;
+            if (i >= tx || j0 + W <= 0 || j0 >= ty) continue;            // no cell of this row on these diagonals
+            int jc[W];
+#pragma unroll
+            for (int w = 0; w < W; ++w) jc[w] = min(max(j0 + w, 0), ty - 1);
+            for (int c = 0; c < C; ++c) {
+                const double xv = (double)xb[(size_t)c * Tx + i];
+                const float* yr = yb + (size_t)c * Ty;
+#pragma unroll
+                for (int w = 0; w < W; ++w) { const double d = xv - (double)yr[jc[w]]; acc[r][w] = fma(d, d, acc[r][w]); }
+            }
+            if (p.metric == 0) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) acc[r][w] = __dsqrt_rn(acc[r][w]);
+            }
+        }
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const int k = k0 + w;
+            if (k < nk) {                                                // (uniform)
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int i = tid + r * NT, j = k - i;
+                    if (i < tx && j >= 0 && j < ty) {
+                        double best = 0.0;
+                        int sb = 0, ch = 0;
+                        bool have = false;
+                        if (i > 0) {
+                            if (j > 0) { best = d2[i - 1]; sb = s2[i - 1]; have = true; }
+                            const double up = d1[i - 1];
+                            if (!have || up < best) { best = up; sb = s1[i - 1]; ch = 1; have = true; }
+                        }
+                        if (j > 0 && (!have || leftD[r] < best)) { best = leftD[r]; sb = leftS[r]; ch = 2; }
+                        const double D = acc[r][w] + best;               // (cell (0, 0): best = 0 is added, D = c exactly)
+                        const int S = sb + 1;
+                        d0[i] = D; s0[i] = (unsigned short)S;
+                        leftD[r] = D; leftS[r] = S;
+                        if (bits) {
+                            word[r] |= (unsigned long long)ch << (2 * (j & 31));
+                            if ((j & 31) == 31 || j == ty - 1) { bits[(size_t)(j >> 5) * Tx + i] = word[r]; word[r] = 0ull; }
+                        }
+                        if (i == tx - 1 && j == ty - 1) { p.cost[b] = D; p.steps[b] = S; dtw_K = S; }
+                    }
+                }
+                __syncthreads();
+                double* t = d2; d2 = d1; d1 = d0; d0 = t;
+                unsigned short* u = s2; s2 = s1; s1 = s0; s0 = u;
+            }
+        }
+    }
+    if (!path) return;
+    const int K = dtw_K;                                                // (written before the last barrier)
+    unsigned int* stage = (unsigned int*)dtw_lds;                       // [K]: i | j << 16, over the ring that is no longer read
+    if (tid == 0) {
+        int i = tx - 1, j = ty - 1;
+        for (int k = K - 1; k >= 0; --k) {
+            stage[k] = (unsigned int)i | ((unsigned int)j << 16);
+            int ch = (int)((bits[(size_t)(j >> 5) * Tx + i] >> (2 * (j & 31))) & 3ull);
+            if (i == 0) ch = 2; else if (j == 0) ch = 1;                 // (what the forward step recorded there; keeps the walk inside the matrix)
+            if (ch != 2) --i;
+            if (ch != 1) --j;
+            if (i < 0 || j < 0) break;                                   // (0, 0) was entry 0
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < 2 * NP; e += NT) {
+        const int k = e >> 1;
+        int v = -1;
+        if (k < K) { const unsigned int s = stage[k]; v = (e & 1) ? (int)(s >> 16) : (int)(s & 0xffffu); }
+        path[e] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Loudness (ev_loudness): ITU-R BS.1770-4 K-weighting, 100 ms sub-block energies, 400 ms blocks, two gates.  All float64.
+// The K-weighting is two biquads in series, each in transposed direct form II (what scipy.signal.lfilter runs):
+//     y = b0 x + s1;   s1 = (b1 x + s2) - a1 y;   s2 = b2 x - a2 y
+// so a row's filter state is FOUR doubles (s1, s2 of the shelf, then of the high pass) and the filter is linear in (state, input): the state
+// after a chunk of LOUD_CHUNK samples is (the state the chunk reaches from zero) + M . (the state before it), M the 4 x 4 zero-input
+// transition over one chunk (the host runs this very recurrence on the four unit states and passes M by value).  A row is therefore NOT one
+// chain of len steps but three launches whose longest chain is one chunk plus the carry:
+//   1. loud_chunk_kernel<false>: one lane per (row, chunk) runs its chunk from zero state and keeps the four doubles;
+//   2. loud_carry_kernel:        one wave per row forms s[c + 1] = M s[c] + z[c] in ascending c, in place: slot c then holds the state at the
+//                                START of chunk c;
+//   3. loud_chunk_kernel<true>:  one lane per (row, chunk) reruns the chunk from that state and sums y^2 per PIECE, a piece being the part of
+//                                one sub-block that lies inside the chunk (one fma per sample, ascending);
+// then loud_merge_kernel adds the pieces of sub-block i over the chunks it touches in ascending chunk order (e_i), and loud_gate_kernel forms
+// the blocks, both gates and the two means per row.  No atomics anywhere; the chunk grid hangs on the row's first sample, so nothing depends
+// on the batch, on L or on what lies behind the row.
+// Only samples below lim = (len / S) S are ever read (the incomplete tail is discarded by the standard, and nothing at or behind len may be
+// read).  Staging: a workgroup is ONE wave holding 64 consecutive chunks of a row; a lane reading its own chunk straight from memory would be
+// a 4 KiB-strided access, so the wave loads a tile of 64 chunks x LOUD_T samples with 16-byte loads (8 lanes per chunk: 128 contiguous bytes)
+// into LDS rows of LOUD_T + 4 floats (9 sixteen-byte slots: 16 consecutive lanes reading their rows' same quad hit 16 different slots) and
+// each lane then reads its row with 16-byte LDS loads.  The next tile's global loads are issued before the current tile is filtered and
+// written to the other LDS buffer after it: one barrier per tile.
+constexpr int LOUD_CHUNK = 1024;                                        // samples per chunk
+constexpr int LOUD_T = 32;                                              // samples per chunk and staged tile
+constexpr int LOUD_ROW = LOUD_T + 4;                                    // floats per LDS row
+
+struct LoudCoef { double b0, b1, b2, a1, a2, c0, c1, c2, d1, d2; };     // stage 1 (b, a), stage 2 (c, d)
+
+struct LoudChunkParams {
+    const float* x; const int32_t* len; double* state; double* part;   // state (B, NC, 4); part (B, NC, npp)
+    int L, S, NC, npp;
+    LoudCoef k;
+};
+
+__device__ __forceinline__ long long loud_lim(const int32_t* len, int b, int L, int S) {
+    int n = len ? len[b] : L;
+    if (n < 1 || n > L) n = 0;                                          // a bad row is an empty row (the ev_mas_align convention)
+    return (long long)(n / S) * S;
+}
+
+template <bool ENERGY>
+__global__ __launch_bounds__(64) void loud_chunk_kernel(const LoudChunkParams p) {
+    __shared__ __attribute__((aligned(16))) float xs[2][64 * LOUD_ROW];
+    const int b = blockIdx.y, lane = threadIdx.x;
+    const long long lim = loud_lim(p.len, b, p.L, p.S);
+    const long long c0 = (long long)blockIdx.x * 64;                    // the wave's first chunk
+    if (c0 * LOUD_CHUNK >= lim) return;                                 // (uniform) nothing of this row in these chunks
+    const float* xrow = p.x + (size_t)b * p.L;
+    const bool vec = (((size_t)xrow) & 15) == 0;                        // (chunks and tiles start at multiples of 4 samples of the row)
+    const long long c = c0 + lane, n0 = c * LOUD_CHUNK;
+    const int cnt = (int)max(0LL, min((long long)LOUD_CHUNK, lim - n0));    // samples of this lane's chunk below lim
+    const int ntile = (int)((min((long long)LOUD_CHUNK, lim - c0 * LOUD_CHUNK) + LOUD_T - 1) / LOUD_T);   // (uniform: lane 0 has the most)
+    const LoudCoef k = p.k;
+    double s1 = 0.0, s2 = 0.0, u1 = 0.0, u2 = 0.0;
+    double acc = 0.0;
+    int rem = 0;
+    double* part = nullptr;
+    if (ENERGY) {
+        if (cnt > 0) {
+            const double* st = p.state + ((size_t)b * p.NC + c) * 4;
+            s1 = st[0]; s2 = st[1]; u1 = st[2]; u2 = st[3];
+        }
+        const long long i0 = n0 / p.S;
+        rem = (int)((i0 + 1) * p.S - n0);                               // samples left in the sub-block the chunk starts in
+        part = p.part + ((size_t)b * p.NC + (cnt > 0 ? c : 0)) * p.npp;
+    }
+    // the tile loader: instruction r of 8 covers chunks 8 r .. 8 r + 7, lane -> (chunk 8 r + lane / 8, quad lane % 8)
+    const int lq = lane & 7, lc = lane >> 3;
+    f32x4 stage[8];
+    auto load_tile = [&](int t) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const long long n = (c0 + 8 * r + lc) * LOUD_CHUNK + t * LOUD_T + 4 * lq;
+            f32x4 q = {0.f, 0.f, 0.f, 0.f};
+            if (n + 4 <= lim) {
+                if (vec) q = *(const f32x4*)(xrow + n);
+                else { q[0] = xrow[n]; q[1] = xrow[n + 1]; q[2] = xrow[n + 2]; q[3] = xrow[n + 3]; }
+            } else if (n < lim) {
+                if (n + 0 < lim) q[0] = xrow[n];
+                if (n + 1 < lim) q[1] = xrow[n + 1];
+                if (n + 2 < lim) q[2] = xrow[n + 2];
+                if (n + 3 < lim) q[3] = xrow[n + 3];
+            }
+            stage[r] = q;
+        }
+    };
+    auto store_tile = [&](int buf) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) *(f32x4*)(&xs[buf][(8 * r + lc) * LOUD_ROW + 4 * lq]) = stage[r];
+    };
+    load_tile(0);
+    store_tile(0);
+    __syncthreads();
+    for (int t = 0; t < ntile; ++t) {
+        if (t + 1 < ntile) load_tile(t + 1);
+        const float* row = &xs[t & 1][lane * LOUD_ROW];
+        const int v = cnt - t * LOUD_T;                                 // samples of this tile that belong to the lane's chunk (may be <= 0)
+#pragma unroll
+        for (int j = 0; j < LOUD_T / 4; ++j) {
+            const f32x4 q = *(const f32x4*)(row + 4 * j);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double x = (double)q[e];
+                const double y1 = fma(k.b0, x, s1);
+                s1 = fma(-k.a1, y1, fma(k.b1, x, s2));
+                s2 = fma(-k.a2, y1, k.b2 * x);
+                const double y2 = fma(k.c0, y1, u1);
+                u1 = fma(-k.d1, y2, fma(k.c1, y1, u2));
+                u2 = fma(-k.d2, y2, k.c2 * y1);
+                if (ENERGY) {
+                    if (4 * j + e < v) {
+                        acc = fma(y2, y2, acc);
+                        if (--rem == 0) { *part++ = acc; acc = 0.0; rem = p.S; }
+                    }
+                }
+            }
+        }
+        if (t + 1 < ntile) store_tile((t + 1) & 1);
+        __syncthreads();
+    }
+    if (ENERGY) {
+        if (cnt > 0 && rem != p.S) *part = acc;                         // the piece the chunk's end cuts (lim is a multiple of S: the row's last
+    } else {                                                            // chunk ends on a sub-block's end and leaves none)
+        if (cnt == LOUD_CHUNK) {
+            double* st = p.state + ((size_t)b * p.NC + c) * 4;
+            st[0] = s1; st[1] = s2; st[2] = u1; st[3] = u2;
+        }
+    }
+}
+
+// The carry.  One wave per row; every lane walks the same chain (uniform work, no divergence): 64 chunk results at a time come into LDS with
+// one coalesced load, the chain takes them in ascending order, lane k keeps the state at the start of chunk base + k, and one coalesced store
+// puts those back in place.  s'[r] = (M[r][0] s0 + M[r][1] s1) + (z[r] + M[r][2] s2 + M[r][3] s3), fmas in that association.
+struct LoudCarryParams {
+    double* state; const int32_t* len;
+    int L, S, NC;
+    double M[16];
+};
+
+__global__ __launch_bounds__(64) void loud_carry_kernel(const LoudCarryParams p) {
+    __shared__ double zs[64][4];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const long long lim = loud_lim(p.len, b, p.L, p.S);
+    const long long nact = (lim + LOUD_CHUNK - 1) / LOUD_CHUNK;         // chunks that hold a sample below lim; all but the last are whole
+    double* st = p.state + (size_t)b * p.NC * 4;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (long long base = 0; base < nact; base += 64) {
+        const long long c = base + lane;
+        const bool whole = c < nact - 1;                                // (the last active chunk's result is not needed, and may not exist)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) zs[lane][r] = whole ? st[c * 4 + r] : 0.0;
+        __syncthreads();
+        double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
+        const int n = (int)min(64LL, nact - base);
+        for (int kk = 0; kk < n; ++kk) {
+            if (lane == kk) { m0 = s0; m1 = s1; m2 = s2; m3 = s3; }
+            const double z0 = zs[kk][0], z1 = zs[kk][1], z2 = zs[kk][2], z3 = zs[kk][3];
+            const double t0 = fma(p.M[1], s1, p.M[0] * s0) + fma(p.M[3], s3, fma(p.M[2], s2, z0));
+            const double t1 = fma(p.M[5], s1, p.M[4] * s0) + fma(p.M[7], s3, fma(p.M[6], s2, z1));
+            const double t2 = fma(p.M[9], s1, p.M[8] * s0) + fma(p.M[11], s3, fma(p.M[10], s2, z2));
+            const double t3 = fma(p.M[13], s1, p.M[12] * s0) + fma(p.M[15], s3, fma(p.M[14], s2, z3));
+            s0 = t0; s1 = t1; s2 = t2; s3 = t3;
+        }
+        __syncthreads();
+        if (c < nact) { st[c * 4] = m0; st[c * 4 + 1] = m1; st[c * 4 + 2] = m2; st[c * 4 + 3] = m3; }
+    }
+}
+
+// e[b, i] = the pieces of sub-block i, added in ascending chunk order starting from the first piece itself; 0 for i >= ns.
+struct LoudMergeParams {
+    const double* part; const int32_t* len; double* sub;               // sub (B, NS)
+    int L, S, NC, npp, NS;
+};
+
+__global__ __launch_bounds__(256) void loud_merge_kernel(const LoudMergeParams p) {
+    const int b = blockIdx.y;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.NS) return;
+    const long long ns = loud_lim(p.len, b, p.L, p.S) / p.S;
+    double e = 0.0;
+    if (i < ns) {
+        const long long c_lo = i * p.S / LOUD_CHUNK, c_hi = ((i + 1) * p.S - 1) / LOUD_CHUNK;
+        const double* part = p.part + (size_t)b * p.NC * p.npp;
+        for (long long c = c_lo; c <= c_hi; ++c) {
+            const double v = part[c * p.npp + (i - c * LOUD_CHUNK / p.S)];
+            e = c == c_lo ? v : e + v;
+        }
+    }
+    p.sub[(size_t)b * p.NS + i] = e;
+}
+
+// One workgroup per row over its sub-block energies: z[j] = ((e[j] + e[j+1]) + (e[j+2] + e[j+3])) / (4 S) for j < nb = max(ns - 3, 0); the
+// absolute gate z > abs_gate; m_abs = the mean of the blocks that pass it; the relative gate z > 0.1 m_abs on top; the mean of the blocks
+// that pass both.  SUMMATION ORDER of either mean: thread t of 256 adds its blocks j = t, t + 256, ... in ascending j; the 64 partials of a
+// wave are added by the fixed shuffle tree (offsets 32, 16, ... 1); the four waves' sums as (w0 + w1) + (w2 + w3).  It depends on j alone.
+struct LoudGateParams {
+    const double* sub; const int32_t* len; double* block; double* gated; int32_t* counts;
+    int L, S, NS, NB;
+    double abs_gate;
+};
+
+__device__ __forceinline__ double loud_block(const double* e, long long j, double four_s) {
+    return ((e[j] + e[j + 1]) + (e[j + 2] + e[j + 3])) / four_s;
+}
+
+__device__ __forceinline__ void loud_reduce(double& s, int& n, double* red_d, int* red_i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o); n += __shfl_down(n, o); }
+    __syncthreads();                                                    // (the previous use of red_* is over)
+    if ((threadIdx.x & 63) == 0) { red_d[threadIdx.x >> 6] = s; red_i[threadIdx.x >> 6] = n; }
+    __syncthreads();
+    s = (red_d[0] + red_d[1]) + (red_d[2] + red_d[3]);
+    n = (red_i[0] + red_i[1]) + (red_i[2] + red_i[3]);
+}
+
+__global__ __launch_bounds__(256) void loud_gate_kernel(const LoudGateParams p) {
+    __shared__ double red_d[4];
+    __shared__ int red_i[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const long long ns = loud_lim(p.len, b, p.L, p.S) / p.S;
+    const long long nb = ns > 3 ? ns - 3 : 0;
+    const double* e = p.sub + (size_t)b * p.NS;
+    const double four_s = 4.0 * (double)p.S;
+    if (p.block)
+        for (long long j = tid; j < p.NB; j += 256) p.block[(size_t)b * p.NB + j] = j < nb ? loud_block(e, j, four_s) : 0.0;
+    double s = 0.0;
+    int n = 0;
+    for (long long j = tid; j < nb; j += 256) {
+        const double z = loud_block(e, j, four_s);
+        if (z > p.abs_gate) { s += z; ++n; }
+    }
+    loud_reduce(s, n, red_d, red_i);
+    const int n_abs = n;
+    const double m_abs = n_abs > 0 ? s / (double)n_abs : 0.0;
+    const double rel = 0.1 * m_abs;
+    s = 0.0; n = 0;
+    for (long long j = tid; j < nb; j += 256) {
+        const double z = loud_block(e, j, four_s);
+        if (z > p.abs_gate && z > rel) { s += z; ++n; }
+    }
+    loud_reduce(s, n, red_d, red_i);
+    if (tid == 0) {
+        p.gated[2 * b] = n > 0 ? s / (double)n : 0.0;
+        p.gated[2 * b + 1] = m_abs;
+        p.counts[3 * b] = (int32_t)nb; p.counts[3 * b + 1] = n_abs; p.counts[3 * b + 2] = n;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// STOI / ESTOI (ev_stoi): short-time objective intelligibility of a processed row y against a clean row x (Taal et al. 2011; Jensen and
+// Taal 2016).  All float64; every kernel below compiles with floating-point contraction OFF (STOI_EXACT), so an fma is an fma only where fma()
+// is written and a product that feeds a sum is rounded first wherever `*` and `+` are written.  No atomics.  Five launches:
+//   1. stoi_energy_kernel:   one lane per (row, frame f): E[f] = fma chain over j of t_j^2, t_j = w[j] x[f H + j], ascending j, from 0;
+//   2. stoi_select_kernel:   one workgroup per row: the maximum of E (exact in any order), the mask E[f] > silence_ratio * max, and an
+//                            ordered compaction of the kept frames into idx (256 frames per round: one ballot and one popcount prefix per
+//                            wave, the four waves' totals through LDS, the running base carried from round to round); writes d_keep and
+//                            d_counts = {nf, nk, nseg};
+//   3. stoi_band_kernel:     one workgroup per (row, frame m) for BOTH signals (they share every twiddle read): z through LDS, one lane per
+//                            bin, four fma chains per lane (re and im of x and of y), then one lane per band;
+//   4. stoi_segment_kernel:  one wave per (row, segment): the N frames of every band through LDS; one lane per band for STOI, then one lane
+//                            per band and one lane per frame for the two normalisations of ESTOI;
+//   5. stoi_mean_kernel:     one workgroup per row: the two means in the fixed tree of loud_reduce.
+// Everything a row's outputs depend on hangs on the row's own samples below len: nothing depends on the batch, on L or on what lies behind.
+#define STOI_EXACT _Pragma("clang fp contract(off)")
+constexpr double STOI_EPS = 2.220446049250313e-16;                     // 2^-52
+
+struct StoiTables { const double* win; const double* tw; const int32_t* bands; int W, H, nfft, n_bands, N, bin_lo, bin_hi; };
+
+__device__ __forceinline__ int stoi_frames(const int32_t* len, int b, int L, int W, int H) {
+    int n = len ? len[b] : L;
+    if (n < 1 || n > L) n = 0;                                          // a bad row is an empty row (the ev_mas_align convention)
+    return n > W ? (n - W + H - 1) / H : 0;                             // range(0, n - W, H): a row of exactly W + k H samples has k frames
+}
+
+struct StoiEnergyParams { const float* x; const int32_t* len; double* E; StoiTables t; int L, NF; };
+
+__global__ __launch_bounds__(64) void stoi_energy_kernel(const StoiEnergyParams p) {
+    STOI_EXACT
+    const int b = blockIdx.y, f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= p.NF) return;
+    const int nf = stoi_frames(p.len, b, p.L, p.t.W, p.t.H);
+    double e = 0.0;
+    if (f < nf) {
+        const float* x = p.x + (size_t)b * p.L + (size_t)f * p.t.H;    // (f H + W - 1 < len: the frame lies inside the row)
+#pragma unroll 8
+        for (int j = 0; j < p.t.W; ++j) {                               // (W is a multiple of 64: the loads of eight steps go out together)
+            const double t = p.t.win[j] * (double)x[j];
+            e = fma(t, t, e);
+        }
+    }
+    p.E[(size_t)b * p.NF + f] = e;
+}
+
+struct StoiSelectParams { const double* E; const int32_t* len; int32_t* idx; uint8_t* keep; int32_t* counts; StoiTables t; int L, NF; double ratio; };
+
+__global__ __launch_bounds__(256) void stoi_select_kernel(const StoiSelectParams p) {
+    STOI_EXACT
+    __shared__ double red_d[4];
+    __shared__ int red_i[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nf = stoi_frames(p.len, b, p.L, p.t.W, p.t.H);
+    const double* E = p.E + (size_t)b * p.NF;
+    double mx = 0.0;                                                    // (energies are >= 0)
+    for (int f = tid; f < nf; f += 256) mx = fmax(mx, E[f]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+    if (lane == 0) red_d[wv] = mx;
+    __syncthreads();
+    mx = fmax(fmax(red_d[0], red_d[1]), fmax(red_d[2], red_d[3]));
+    const double thr = p.ratio * mx;
+    int base = 0;                                                       // kept frames before this round (uniform)
+    for (int f0 = 0; f0 < nf; f0 += 256) {
+        const int f = f0 + tid;
+        const bool k = f < nf && E[f] > thr;
+        const unsigned long long m = __ballot(k);
+        const int before = __popcll(m & ((1ull << lane) - 1ull));
+        __syncthreads();                                                // (the previous round's red_i is read)
+        if (lane == 0) red_i[wv] = __popcll(m);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wv; ++w) off += red_i[w];
+        if (k) p.idx[(size_t)b * p.NF + off + before] = f;
+        base += (red_i[0] + red_i[1]) + (red_i[2] + red_i[3]);
+        if (p.keep && f < p.NF) p.keep[(size_t)b * p.NF + f] = k ? 1 : 0;
+    }
+    if (p.keep) {                                                       // zeros from the last round's end up to NF (nf <= NF)
+        const int done = (nf + 255) / 256 * 256;
+        for (int f = done + tid; f < p.NF; f += 256) p.keep[(size_t)b * p.NF + f] = 0;
+    }
+    if (tid == 0) {
+        const int nm = base > 0 ? base - 1 : 0;
+        p.counts[3 * b] = nf; p.counts[3 * b + 1] = base; p.counts[3 * b + 2] = nm >= p.t.N ? nm - p.t.N + 1 : 0;
+    }
+}
+
+// Band spectra of frame m of the silence-removed signals, which never exist in memory: sample n = m H + j of s gathers from the kept frames
+// k = n / H - 1 and n / H (W = 2 H: exactly two overlap), i.e. from kept frames m - 1 and m for j < H and m and m + 1 for j >= H
+// (m + 1 <= nk - 1 always, m - 1 >= 0 from the second frame on).  s = t_lo + t_hi with t_k = w[n - k H] * x[idx[k] H + n - k H], each product
+// rounded, added in ascending k (the first frame's lower half has the one term); z[j] = w[j] * s.  Bin k of lane (k - bin_lo):
+// re = fma(z[j], cos[(j k) mod nfft], re), sm = fma(z[j], sin[(j k) mod nfft], sm) over ascending j from 0, im = -sm, p = fma(im, im, re * re).
+// Band: the p of its bins added in ascending k from 0, then sqrt (correctly rounded).  LDS (doubles): [twiddle 2 nfft][z 2 W][p 2 nbin].
+struct StoiBandParams { const float* x; const float* y; const int32_t* idx; const int32_t* counts; double* tob; StoiTables t; int L, NF, NM; };
+
+__global__ __launch_bounds__(256) void stoi_band_kernel(const StoiBandParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double stoi_smem[];
+    const int b = blockIdx.y, m = blockIdx.x, tid = threadIdx.x;
+    const int W = p.t.W, H = p.t.H, nfft = p.t.nfft, nb = p.t.n_bands;
+    const int nk = p.counts[3 * b + 1], nm = nk > 0 ? nk - 1 : 0;
+    double* tobx = p.tob + ((size_t)b * 2 * nb) * p.NM + m;             // band r of x at tobx[r NM], of y at tobx[(nb + r) NM]
+    if (m >= nm) {                                                      // (uniform) zeros past the row's own frames
+        for (int r = tid; r < 2 * nb; r += 256) tobx[(size_t)r * p.NM] = 0.0;
+        return;
+    }
+    double* tw = stoi_smem;                                             // (nfft, 2)
+    double* zx = tw + 2 * nfft;                                         // (W)
+    double* zy = zx + W;
+    double* px = zy + W;                                                // (bin_hi - bin_lo)
+    const int nbin = p.t.bin_hi - p.t.bin_lo;
+    double* py = px + nbin;
+    for (int i = tid; i < 2 * nfft; i += 256) tw[i] = p.t.tw[i];
+    const int32_t* idx = p.idx + (size_t)b * p.NF;
+    const float* xr = p.x + (size_t)b * p.L;
+    const float* yr = p.y + (size_t)b * p.L;
+    for (int j = tid; j < W; j += 256) {
+        const int k_hi = j < H ? m : m + 1, k_lo = k_hi - 1;            // the two kept frames that overlap at sample m H + j
+        const int o_hi = j < H ? j : j - H, o_lo = o_hi + H;            // the sample's offset inside each
+        const size_t a_hi = (size_t)idx[k_hi] * H + o_hi;
+        const double w_hi = p.t.win[o_hi];
+        double sx = w_hi * (double)xr[a_hi], sy = w_hi * (double)yr[a_hi];
+        if (k_lo >= 0) {
+            const size_t a_lo = (size_t)idx[k_lo] * H + o_lo;
+            const double w_lo = p.t.win[o_lo];
+            sx = w_lo * (double)xr[a_lo] + sx;
+            sy = w_lo * (double)yr[a_lo] + sy;
+        }
+        const double wj = p.t.win[j];
+        zx[j] = wj * sx;
+        zy[j] = wj * sy;
+    }
+    __syncthreads();
+    for (int q = tid; q < nbin; q += 256) {
+        const int k = p.t.bin_lo + q;                                   // k <= nfft / 2 < nfft
+        double rx = 0.0, ix = 0.0, ry = 0.0, iy = 0.0;
+        int ph = 0;                                                     // (j k) mod nfft
+        for (int j = 0; j < W; ++j) {
+            const double c = tw[2 * ph], s = tw[2 * ph + 1];
+            const double a = zx[j], d = zy[j];
+            rx = fma(a, c, rx); ix = fma(a, s, ix);
+            ry = fma(d, c, ry); iy = fma(d, s, iy);
+            ph += k;
+            if (ph >= nfft) ph -= nfft;
+        }
+        ix = -ix; iy = -iy;
+        px[q] = fma(ix, ix, rx * rx);
+        py[q] = fma(iy, iy, ry * ry);
+    }
+    __syncthreads();
+    for (int r = tid; r < 2 * nb; r += 256) {
+        const int band = r < nb ? r : r - nb;
+        const double* pp = r < nb ? px : py;
+        const int k0 = p.t.bands[2 * band] - p.t.bin_lo, k1 = p.t.bands[2 * band + 1] - p.t.bin_lo;
+        double acc = 0.0;
+        for (int k = k0; k < k1; ++k) acc = acc + pp[k];
+        tobx[(size_t)r * p.NM] = sqrt(acc);
+    }
+}
+
+// One wave per (row, segment q): frames [q, q + N) of every band of both signals in LDS rows of NP = N | 1 doubles (an odd stride: the lanes
+// that each walk one band's row hit different banks).  EVERY sum below runs in ascending index from 0, `a * a` terms as fma(a, a, sum).
+// STOI, lane = band r: nx = sqrt(sum X^2), ny = sqrt(sum Y^2), a = nx / (ny + EPS); Y'[i] = min(a * Y[i], clip * X[i]); mx = (sum X) / N,
+//   my = (sum Y') / N; dx = sqrt(sum (X - mx)^2) + EPS, dy = sqrt(sum (Y' - my)^2) + EPS; rho = sum of ((X - mx) / dx) * ((Y' - my) / dy).
+//   d_seg[q][0] = (sum of rho over the bands, ascending) / n_bands.
+// ESTOI, X and Y alike, in place: lane = band: mean over the N frames (sum / N) removed, then divided by (sqrt(sum of squares) + EPS);
+//   lane = frame: mean over the bands (sum / n_bands) removed, then divided by (sqrt(sum of squares) + EPS); c_i = fma chain over the bands of
+//   X[r][i] * Y[r][i]; d_seg[q][1] = (sum of c_i over the frames, ascending) / N.
+struct StoiSegParams { const double* tob; const int32_t* counts; double* seg; StoiTables t; int NM, NSEG; double clip; };
+
+__global__ __launch_bounds__(64) void stoi_segment_kernel(const StoiSegParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double stoi_smem[];
+    const int b = blockIdx.y, q = blockIdx.x, lane = threadIdx.x;
+    const int N = p.t.N, nb = p.t.n_bands, NP = N | 1;
+    const int nseg = p.counts[3 * b + 2];
+    double* out = p.seg + ((size_t)b * p.NSEG + q) * 2;
+    if (q >= nseg) {                                                    // (uniform)
+        if (lane < 2) out[lane] = 0.0;
+        return;
+    }
+    double* X = stoi_smem;                                              // (nb, NP)
+    double* Y = X + nb * NP;
+    double* red = Y + nb * NP;                                          // (64)
+    const double* src = p.tob + ((size_t)b * 2 * nb) * p.NM + q;
+    for (int r = 0; r < nb; ++r)
+        if (lane < N) { X[r * NP + lane] = src[(size_t)r * p.NM + lane]; Y[r * NP + lane] = src[(size_t)(nb + r) * p.NM + lane]; }
+    __syncthreads();
+    const double dN = (double)N, dB = (double)nb;
+    double rho = 0.0;
+    if (lane < nb) {
+        const double* x = X + lane * NP;
+        const double* y = Y + lane * NP;
+        double sxx = 0.0, syy = 0.0;
+        for (int i = 0; i < N; ++i) { sxx = fma(x[i], x[i], sxx); syy = fma(y[i], y[i], syy); }
+        const double a = sqrt(sxx) / (sqrt(syy) + STOI_EPS);
+        double sx = 0.0, sy = 0.0;
+        for (int i = 0; i < N; ++i) { sx = sx + x[i]; sy = sy + fmin(a * y[i], p.clip * x[i]); }
+        const double mx = sx / dN, my = sy / dN;
+        sxx = 0.0; syy = 0.0;
+        for (int i = 0; i < N; ++i) {
+            const double u = x[i] - mx, v = fmin(a * y[i], p.clip * x[i]) - my;
+            sxx = fma(u, u, sxx); syy = fma(v, v, syy);
+        }
+        const double dx = sqrt(sxx) + STOI_EPS, dy = sqrt(syy) + STOI_EPS;
+        for (int i = 0; i < N; ++i) {
+            const double u = (x[i] - mx) / dx, v = (fmin(a * y[i], p.clip * x[i]) - my) / dy;
+            rho = rho + u * v;
+        }
+    }
+    red[lane] = rho;
+    __syncthreads();
+    if (lane == 0) {
+        double s = 0.0;
+        for (int r = 0; r < nb; ++r) s = s + red[r];
+        out[0] = s / dB;
+    }
+    __syncthreads();                                                    // (STOI has read X and Y; ESTOI rewrites them)
+    if (lane < nb) {
+#pragma unroll
+        for (int sig = 0; sig < 2; ++sig) {
+            double* v = (sig ? Y : X) + lane * NP;
+            double s = 0.0;
+            for (int i = 0; i < N; ++i) s = s + v[i];
+            const double mu = s / dN;
+            double ss = 0.0;
+            for (int i = 0; i < N; ++i) { const double u = v[i] - mu; ss = fma(u, u, ss); }
+            const double d = sqrt(ss) + STOI_EPS;
+            for (int i = 0; i < N; ++i) v[i] = (v[i] - mu) / d;
+        }
+    }
+    __syncthreads();
+    double c = 0.0;
+    if (lane < N) {
+#pragma unroll
+        for (int sig = 0; sig < 2; ++sig) {
+            double* v = (sig ? Y : X) + lane;
+            double s = 0.0;
+            for (int r = 0; r < nb; ++r) s = s + v[r * NP];
+            const double mu = s / dB;
+            double ss = 0.0;
+            for (int r = 0; r < nb; ++r) { const double u = v[r * NP] - mu; ss = fma(u, u, ss); }
+            const double d = sqrt(ss) + STOI_EPS;
+            for (int r = 0; r < nb; ++r) v[r * NP] = (v[r * NP] - mu) / d;
+        }
+        for (int r = 0; r < nb; ++r) c = fma(X[r * NP + lane], Y[r * NP + lane], c);
+    }
+    red[lane] = c;
+    __syncthreads();
+    if (lane == 0) {
+        double s = 0.0;
+        for (int i = 0; i < N; ++i) s = s + red[i];
+        out[1] = s / dN;
+    }
+}
+
+// d_score[b] = {mean of d_seg[., 0], mean of d_seg[., 1]} over the row's nseg segments, 0 without a segment: thread t of 256 adds its segments
+// t, t + 256, ... in ascending order, the 64 partials of a wave go through the shuffle tree (offsets 32 .. 1), the four waves' sums are added
+// as (w0 + w1) + (w2 + w3) — the tree of ev_loudness — and one division by nseg follows.
+struct StoiMeanParams { const double* seg; const int32_t* counts; double* score; int NSEG; };
+
+__global__ __launch_bounds__(256) void stoi_mean_kernel(const StoiMeanParams p) {
+    STOI_EXACT
+    __shared__ double red[2][4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int nseg = p.counts[3 * b + 2];
+    const double* seg = p.seg + (size_t)b * p.NSEG * 2;
+    double s0 = 0.0, s1 = 0.0;
+    for (int q = tid; q < nseg; q += 256) { s0 = s0 + seg[2 * q]; s1 = s1 + seg[2 * q + 1]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s0 = s0 + __shfl_down(s0, o); s1 = s1 + __shfl_down(s1, o); }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = s0; red[1][tid >> 6] = s1; }
+    __syncthreads();
+    if (tid < 2) {
+        const double s = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+        p.score[2 * b + tid] = nseg > 0 ? s / (double)nseg : 0.0;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Multi-resolution STFT distance (ev_stft_dist): spectral convergence, log-magnitude L1 (Yamamoto et al. 2020) and log-spectral distance of a
+// processed row y against a reference row x at ONE resolution (W, H, nfft); the caller runs it once per resolution.  All float64, contraction
+// OFF (STOI_EXACT), no atomics.  The DFT is a float64 GEMM on v_mfma_f64_16x16x4_f64: frames x samples times the dense windowed basis
+//   basis[j][k] = {w[j] cos(2 pi (j + off) k / nfft), w[j] sin(2 pi (j + off) k / nfft)},  off = (nfft - W) / 2,  0 <= j < W,  0 <= k < NB,
+// which stft_dist_basis_kernel builds once per load (one rounding per entry, the phase index in exact integers), {cos, sin} interleaved so
+// that one 16-byte load feeds both planes.  Launches of a call:
+//   1. stft_dist_frames_kernel: one workgroup of 4 waves per (row, 16 frames from the row's frame 0) -> d_frame (B, NF, 4);
+//   2. stft_dist_rows_kernel:   one workgroup per row: the four sums in the fixed tree of loud_reduce / stoi_mean_kernel, and the count.
+// Everything a row's outputs depend on hangs on the row's own samples below len.
+struct StftDistTables { const double2* basis; int W, H, nfft, NB, skew; };
+typedef double stftd_acc __attribute__((ext_vector_type(4)));
+
+// (n, nf) of row b: a row with len < 1, len > L or len <= nfft / 2 is an empty row (the reflect padding of nfft / 2 needs more samples)
+__device__ __forceinline__ int stftd_frames(const int32_t* len, int b, int L, const StftDistTables& t, int* n_out) {
+    int n = len ? len[b] : L;
+    if (n < 1 || n > L || n <= t.nfft / 2) n = 0;
+    *n_out = n;
+    return n > 0 ? 1 + n / t.H : 0;
+}
+
+struct StftBasisParams { const double* win; const double* tw; double2* basis; int W, nfft, NB; };
+
+__global__ __launch_bounds__(256) void stft_dist_basis_kernel(const StftBasisParams p) {
+    STOI_EXACT
+    const int i = blockIdx.x * 256 + threadIdx.x;                       // (W NB <= 2048 x 1025)
+    if (i >= p.W * p.NB) return;
+    const int j = i / p.NB, k = i - j * p.NB;
+    const int ph = ((j + (p.nfft - p.W) / 2) * k) % p.nfft;             // (< 2048 x 1024: exact)
+    const double w = p.win[j];
+    p.basis[i] = make_double2(w * p.tw[2 * ph], w * p.tw[2 * ph + 1]);
+}
+
+// One workgroup per (row b, tile of 16 frames f0 .. f0 + 15).  The tile's raw span, samples f0 H - W / 2 + t for 0 <= t < 15 H + W of both
+// signals, is staged once into LDS as fp32 with the reflection applied (refl(i) = -i below 0, 2 (len - 1) - i from len on; what a frame
+// >= nf would read outside the row is staged as 0 and that frame is masked).  Lane l of an A fragment reads t = (l & 15) H + k0 + (l >> 4):
+// with ds_read_b32 banked over 32 words and served in two groups of 32 lanes, a frame stride H = 0 mod 4 (240: 16 banks) lands the 16
+// frames of a group on few banks.  SKEW: sample t lives at word t + skew * (t / H) with skew = (2 - H) mod 4, so the frame stride H + skew
+// is 2 mod 4: 2 r (odd) mod 32 is 16 distinct even banks for r = 0 .. 15, and the two k of a lane group fill the odd ones — conflict-free
+// (except where k0 + (l >> 4) crosses a multiple of H inside a group).  At most 3 (16 + W / H) pad words per signal: 78 160 bytes for
+// both signals at H = 511, W = 2048, the largest footprint.
+// Wave w owns the bin tiles w, w + 4, ...; per bin tile W / 4 steps of four MFMAs (x c, x s, y c, y s): the A fragment of each signal
+// (frame l & 15, sample k0 + (l >> 4), widened on the way out of LDS) serves both planes, the B fragment (basis row k0 + (l >> 4), bin
+// l & 15, read from global memory: L2-resident) serves both signals.  Accumulators in the f64 layout: register i of lane l is frame
+// (l >> 4) + 4 i, bin l & 15.  Epilogue per (frame, bin): p = max(fma(sm, sm, re * re), floor), m = sqrt(p), l = log(p) for both signals; the
+// four terms are accumulated per frame over the wave's bin tiles in ascending order (squares as fma(d, d, sum)), reduced over the 16 bin
+// lanes by one xor tree (offsets 8, 4, 2, 1) and over the waves as ((w0 + w1) + w2) + w3.  Bins >= NB (the address is clamped, the term
+// dropped) and frames >= nf (zeros) are masked.
+struct StftFramesParams { const float* x; const float* y; const int32_t* len; double* frame; StftDistTables t; int L, NF; double floor; };
+
+__global__ __launch_bounds__(256) void stft_dist_frames_kernel(const StftFramesParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) float stftd_smem[];
+    __shared__ double red[4][16][4];
+    const int b = blockIdx.y, f0 = blockIdx.x * 16, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int W = p.t.W, H = p.t.H, NB = p.t.NB, skew = p.t.skew;
+    int n;
+    const int nf = stftd_frames(p.len, b, p.L, p.t, &n);
+    double* out = p.frame + ((size_t)b * p.NF + f0) * 4;
+    if (f0 >= nf) {                                                     // (uniform) zeros past the row's own frames
+        if (tid < 64 && f0 + (tid >> 2) < p.NF) out[tid] = 0.0;
+        return;
+    }
+    const int span = 15 * H + W;
+    float* sx = stftd_smem;
+    float* sy = sx + span + skew * ((span - 1) / H);                    // (the last word of x is (span - 1) + skew ((span - 1) / H))
+    {
+        const float* xr = p.x + (size_t)b * p.L;
+        const float* yr = p.y + (size_t)b * p.L;
+        const long long i0 = (long long)f0 * H - W / 2;
+        for (int t = tid; t < span; t += 256) {
+            long long i = i0 + t;
+            if (i < 0) i = -i;
+            else if (i >= n) i = 2LL * (n - 1) - i;
+            const bool ok = i >= 0 && i < n;                            // (always, for a frame < nf)
+            const int a = t + skew * (t / H);
+            sx[a] = ok ? xr[i] : 0.f;
+            sy[a] = ok ? yr[i] : 0.f;
+        }
+    }
+    __syncthreads();
+    const int r = lane & 15, q = lane >> 4;
+    const int rbase = r * (H + skew);                                   // word of sample r H + j: r (H + skew) + j + skew (j / H)
+    const int ntile = (NB + 15) >> 4;
+    const int step_mod = 4 % H, step_pad = skew * (4 / H), nsteps = W >> 2;
+    double t0[4] = {0.0, 0.0, 0.0, 0.0}, t1[4] = {0.0, 0.0, 0.0, 0.0}, t2[4] = {0.0, 0.0, 0.0, 0.0}, t3[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int bt = wv; bt < ntile; bt += 4) {
+        const int col = bt * 16 + r;
+        const double2* bp = p.t.basis + (size_t)q * NB + (col < NB ? col : NB - 1);
+        stftd_acc xc = {0.0, 0.0, 0.0, 0.0}, xs = xc, yc = xc, ys = xc;
+        int j = q, jm = q % H, pad = skew * (q / H);
+        // four steps per round; the basis of the NEXT round is requested before this round's products (the index clamped at the last
+        // step: a repeated load, never one past the basis), so its L2 latency hides behind sixteen matrix instructions
+        double2 cur[4], nxt[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) cur[u] = bp[(size_t)(u < nsteps ? u : nsteps - 1) * 4 * NB];
+        for (int s0 = 0; s0 < nsteps; s0 += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) nxt[u] = bp[(size_t)(s0 + 4 + u < nsteps ? s0 + 4 + u : nsteps - 1) * 4 * NB];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (s0 + u < nsteps) {                                  // (uniform)
+                    const int a = rbase + j + pad;
+                    const double ax = (double)sx[a], ay = (double)sy[a];
+                    xc = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].x, xc, 0, 0, 0);
+                    xs = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].y, xs, 0, 0, 0);
+                    yc = __builtin_amdgcn_mfma_f64_16x16x4f64(ay, cur[u].x, yc, 0, 0, 0);
+                    ys = __builtin_amdgcn_mfma_f64_16x16x4f64(ay, cur[u].y, ys, 0, 0, 0);
+                    j += 4; jm += step_mod; pad += step_pad;            // (j + 4) / H = j / H + 4 / H + (j % H + 4 % H >= H)
+                    if (jm >= H) { jm -= H; pad += skew; }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+        }
+        if (col < NB) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const double px = fmax(fma(xs[i], xs[i], xc[i] * xc[i]), p.floor), py = fmax(fma(ys[i], ys[i], yc[i] * yc[i]), p.floor);
+                const double mx = sqrt(px), my = sqrt(py);
+                const double dm = my - mx, dl = log(py) - log(px);
+                t0[i] = fma(dm, dm, t0[i]);
+                t1[i] = fma(mx, mx, t1[i]);
+                t2[i] = t2[i] + fabs(dl);
+                t3[i] = fma(dl, dl, t3[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {
+            t0[i] = t0[i] + __shfl_xor(t0[i], o, 64); t1[i] = t1[i] + __shfl_xor(t1[i], o, 64);
+            t2[i] = t2[i] + __shfl_xor(t2[i], o, 64); t3[i] = t3[i] + __shfl_xor(t3[i], o, 64);
+        }
+        if (r == 0) { double* d = red[wv][q + 4 * i]; d[0] = t0[i]; d[1] = t1[i]; d[2] = t2[i]; d[3] = t3[i]; }
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const int fr = tid >> 2, c = tid & 3;
+        const double v = ((red[0][fr][c] + red[1][fr][c]) + red[2][fr][c]) + red[3][fr][c];
+        if (f0 + fr < p.NF) out[tid] = f0 + fr < nf ? v : 0.0;
+    }
+}
+
+// d_sums[b] = {sum_f d_frame[f][0], sum_f [1], sum_f [2], sum_f sqrt([3] / NB)} over the row's nf frames, d_counts[b] = nf: thread t of 256
+// adds its frames t, t + 256, ... in ascending order, the 64 partials of a wave go through the shuffle tree (offsets 32 .. 1), the four
+// waves' sums are added as (w0 + w1) + (w2 + w3) — the tree of ev_loudness / ev_stoi.
+struct StftRowsParams { const double* frame; const int32_t* len; double* sums; int32_t* counts; StftDistTables t; int L, NF; };
+
+__global__ __launch_bounds__(256) void stft_dist_rows_kernel(const StftRowsParams p) {
+    STOI_EXACT
+    __shared__ double red[4][4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int n;
+    const int nf = stftd_frames(p.len, b, p.L, p.t, &n);
+    const double* fr = p.frame + (size_t)b * p.NF * 4;
+    const double dNB = (double)p.t.NB;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int f = tid; f < nf; f += 256) {
+        s0 = s0 + fr[4 * (size_t)f]; s1 = s1 + fr[4 * (size_t)f + 1]; s2 = s2 + fr[4 * (size_t)f + 2];
+        s3 = s3 + sqrt(fr[4 * (size_t)f + 3] / dNB);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s0 = s0 + __shfl_down(s0, o); s1 = s1 + __shfl_down(s1, o); s2 = s2 + __shfl_down(s2, o); s3 = s3 + __shfl_down(s3, o);
+    }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = s0; red[1][tid >> 6] = s1; red[2][tid >> 6] = s2; red[3][tid >> 6] = s3; }
+    __syncthreads();
+    if (tid < 4) p.sums[4 * (size_t)b + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+    if (tid == 0) p.counts[b] = nf;
+}

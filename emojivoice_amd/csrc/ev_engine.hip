@@ -231,6 +231,13 @@ int fail(ev_handle* h, const char* fmt, ...) {
 }
 #define HIPCHK(h, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(h, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
+// The opening of an entry point: a handle, and its device current on the calling thread
+int enter(ev_handle* h) {
+    if (!h) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    return 0;
+}
+
 template <typename T>
 int dev_upload(ev_handle* h, const std::vector<T>& v, T** out) {
     void* d = nullptr;
@@ -238,6 +245,17 @@ int dev_upload(ev_handle* h, const std::vector<T>& v, T** out) {
     HIPCHK(h, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     h->owned.push_back(d);
     *out = (T*)d;
+    return 0;
+}
+
+// Before a loaded table is replaced: nothing in flight may still read the old one, so the device is drained, then its allocations leave
+// h->owned and are freed
+int drop_owned(ev_handle* h, std::initializer_list<void*> ptrs) {
+    HIPCHK(h, hipDeviceSynchronize());
+    for (void* p : ptrs) {
+        auto it = std::find(h->owned.begin(), h->owned.end(), p);
+        if (it != h->owned.end()) { h->owned.erase(it); hipFree(p); }
+    }
     return 0;
 }
 
@@ -2029,8 +2047,7 @@ static int build_map(ev_handle* h, const float* blob, const ev_tensor_index* ind
 }
 
 int ev_load_estimator(ev_handle* h, const float* blob, const ev_tensor_index* index, size_t n) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     TensorMap m;
     if (build_map(h, blob, index, n, m)) return 1;
     if (ensure_sk(h, false)) return 1;
@@ -2178,8 +2195,7 @@ static int check_vocoder_config(ev_handle* h, const ev_vocoder_config& c) {
 }
 
 static int load_vocoder(ev_handle* h, const float* blob, const ev_tensor_index* index, size_t n, const ev_vocoder_config& cfg) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (check_vocoder_config(h, cfg)) return 1;
     TensorMap m;
     if (build_map(h, blob, index, n, m)) return 1;
@@ -2279,8 +2295,7 @@ int ev_load_vocoder_cfg(ev_handle* h, const float* blob, const ev_tensor_index* 
 #define T_(k) find(h, m, k)
 #define REQ(x) do { if (x) return 1; } while (0)
 int ev_load_text_encoder(ev_handle* h, const float* blob, const ev_tensor_index* index, size_t n) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     TensorMap m;
     if (build_map(h, blob, index, n, m)) return 1;
     TextEncW& w = h->enc;
@@ -2359,8 +2374,7 @@ int ev_load_text_encoder(ev_handle* h, const float* blob, const ev_tensor_index*
 #undef REQ
 
 int ev_text_encoder(ev_handle* h, const int64_t* d_ids, const int32_t* d_lengths, const float* d_spk, int B, int Tx, float* d_mu, float* d_logw, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (!h->enc.loaded) return fail(h, "text encoder weights not loaded");
     if (B <= 0 || Tx <= 0 || !d_ids || !d_lengths || !d_mu || !d_logw) return fail(h, "bad arguments B=%d Tx=%d", B, Tx);
     if (h->enc.C > h->enc.nch && !d_spk) return fail(h, "speaker embedding required by a multi-speaker text encoder");
@@ -2375,8 +2389,7 @@ int ev_text_encoder(ev_handle* h, const int64_t* d_ids, const int32_t* d_lengths
 }
 
 int ev_text_encoder_status(ev_handle* h, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
     if (h->bad_ids_host && *(volatile int*)h->bad_ids_host) {
         *(volatile int*)h->bad_ids_host = 0;
@@ -2406,8 +2419,7 @@ static int check_cfm_args(ev_handle* h, int B, int Tp) {
 
 static int cfm_decode_impl(ev_handle* h, const float* d_mu, const int32_t* d_lengths, const float* d_spk, const float* d_z,
                            int B, int Tp, int n_steps, float* d_dec, float out_scale, float out_shift, float* d_out, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (check_cfm_args(h, B, Tp)) return 1;
     if (n_steps <= 0 || n_steps > 65536) return fail(h, "n_steps %d must be positive (cli.py:143) and at most 65536", n_steps);
     if (!d_mu || !d_z || (!d_out && !d_dec) || (h->dims.spk_emb_dim > 0 && !d_spk)) return fail(h, "null tensor argument");
@@ -2501,8 +2513,7 @@ int ev_cfm_decode2(ev_handle* h, const float* d_mu, const int32_t* d_lengths, co
 }
 
 int ev_reserve(ev_handle* h, int B, int Tx_max, int Tp_max, int T_voc_max, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (B <= 0 || Tx_max < 0 || Tp_max < 0 || T_voc_max < 0 || (Tp_max & 3)) return fail(h, "ev_reserve: bad shape B=%d Tx=%d Tp=%d (multiple of 4) T_voc=%d", B, Tx_max, Tp_max, T_voc_max);
     h->stream = (hipStream_t)stream;
     if (ensure_sk(h, false)) return 1;                // (normally there since the loaders; a handle reserved before any load gets it here)
@@ -2572,8 +2583,7 @@ int64_t ev_dbg_sk_taken(ev_handle* h) {
 
 int ev_estimator(ev_handle* h, const float* d_x, const float* d_mu, const int32_t* d_lengths, const float* d_spk, float t,
                  int B, int Tp, float* d_v, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (check_cfm_args(h, B, Tp)) return 1;
     h->stream = (hipStream_t)stream;
     EstBufs b;
@@ -2622,8 +2632,7 @@ static int rows_begin(ev_handle* h, const char* who, int B, int Tp, void* stream
 
 int ev_estimator_rows(ev_handle* h, const float* d_x, const float* d_mu, const int32_t* d_lengths, const float* d_spk, const float* t,
                       int B, int Tp, float* d_v, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     EstBufs b;
     if (rows_begin(h, "ev_estimator_rows", B, Tp, stream, &b)) return 1;
     if (!d_x || !d_mu || !t || !d_v || (h->dims.spk_emb_dim > 0 && !d_spk)) return fail(h, "null tensor argument");
@@ -2638,8 +2647,7 @@ int ev_estimator_rows(ev_handle* h, const float* d_x, const float* d_mu, const i
 
 int ev_cfm_loss(ev_handle* h, const float* d_x1, const float* d_mu_y, const int32_t* d_ylen, const float* d_spk, const float* d_z, const float* t,
                 int B, int Ty, float sigma_min, double* d_row_sums, float* d_v, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (Ty < 1 || Ty > (1 << 30)) return fail(h, "ev_cfm_loss: bad shape B=%d Ty=%d", B, Ty);
     const int Tp = (Ty + 3) / 4 * 4;              // fix_len_compatibility: the pad frames are masked ones
     EstBufs b;
@@ -2670,8 +2678,7 @@ int ev_cfm_loss(ev_handle* h, const float* d_x1, const float* d_mu_y, const int3
 
 int ev_align(ev_handle* h, const float* d_wceil, const float* d_mu_x, const int32_t* d_xlen, const int64_t* d_ylen, int B, int Tx, int Tp,
              float* d_mu_y, float* d_attn, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (B <= 0 || Tx <= 0 || Tp <= 0 || Tx > 8192 || !d_wceil || !d_mu_x || !d_xlen || !d_ylen || !d_mu_y) return fail(h, "bad arguments B=%d Tx=%d Tp=%d", B, Tx, Tp);
     hipLaunchKernelGGL(enc_align_kernel, dim3(B), dim3(256), (size_t)Tx * sizeof(float), (hipStream_t)stream, d_wceil, d_mu_x, d_xlen, d_ylen, d_mu_y, d_attn,
                        h->dims.n_feats, Tx, Tp);
@@ -2681,15 +2688,13 @@ int ev_align(ev_handle* h, const float* d_wceil, const float* d_mu_x, const int3
 
 int ev_maximum_path(ev_handle* h, const float* d_value, const int32_t* d_xlen, const int32_t* d_ylen, int B, int Tx, int Ty,
                     float* d_path, int32_t* d_dur, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = (hipStream_t)stream;
     return run_mas(h, false, d_value, nullptr, nullptr, d_xlen, d_ylen, B, Tx, Ty, d_path, d_dur, nullptr, nullptr);
 }
 
 int ev_log_prior(ev_handle* h, const float* d_mu_x, const float* d_y, int B, int Tx, int Ty, float* d_logp, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     const int C = h->dims.n_feats;
     if (B <= 0 || B > 65535 || Tx <= 0 || Ty <= 0 || C <= 0 || C > 256 || !d_mu_x || !d_y || !d_logp) return fail(h, "bad arguments B=%d Tx=%d Ty=%d", B, Tx, Ty);
     if ((Tx + 31) / 32 > 65535) return fail(h, "ev_log_prior: Tx=%d exceeds the grid", Tx);
@@ -2701,23 +2706,20 @@ int ev_log_prior(ev_handle* h, const float* d_mu_x, const float* d_y, int B, int
 
 int ev_mas_align(ev_handle* h, const float* d_mu_x, const float* d_y, const int32_t* d_xlen, const int32_t* d_ylen, int B, int Tx, int Ty,
                  float* d_attn, int32_t* d_dur, float* d_mu_y, float* d_logp, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = (hipStream_t)stream;
     return run_mas(h, true, nullptr, d_mu_x, d_y, d_xlen, d_ylen, B, Tx, Ty, d_attn, d_dur, d_mu_y, d_logp);
 }
 
 int ev_stft_magnitude(ev_handle* h, const float* d_audio, int B, int L, float* d_mag, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (B <= 0 || L < 768 || (L & 255) || !d_audio || !d_mag) return fail(h, "bad arguments B=%d L=%d (L must be a multiple of 256, >= 768: reflect padding of 512 needs more than 512 samples, as in torch.stft)", B, L);
     h->stream = (hipStream_t)stream;
     return run_denoiser(h, d_audio, B, L, nullptr, 0.f, nullptr, d_mag);
 }
 
 int ev_denoise(ev_handle* h, const float* d_audio, int B, int L, const float* d_bias_spec, float strength, float* d_out, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (B <= 0 || L < 768 || (L & 255) || !d_audio || !d_bias_spec || !d_out) return fail(h, "bad arguments B=%d L=%d (L must be a multiple of 256, >= 768: reflect padding of 512 needs more than 512 samples, as in torch.stft)", B, L);
     if ((double)B * (L / 256 + 12) * 1032 * 4.0 >= 4294967296.0) return fail(h, "audio batch exceeds the 4 GiB buffer-addressing limit: split the batch");
     h->stream = (hipStream_t)stream;
@@ -2725,8 +2727,7 @@ int ev_denoise(ev_handle* h, const float* d_audio, int B, int L, const float* d_
 }
 
 int ev_load_mel_basis(ev_handle* h, const float* basis, int n_mels, int n_freq) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (!basis || n_freq != 513 || n_mels < 1 || n_mels > 128) return fail(h, "ev_load_mel_basis: bad arguments n_mels=%d n_freq=%d (n_freq must be 513 = n_fft 1024 / 2 + 1, 1 <= n_mels <= 128)", n_mels, n_freq);
     std::vector<int> span((size_t)3 * n_mels);
     std::vector<float> wts;
@@ -2743,22 +2744,14 @@ int ev_load_mel_basis(ev_handle* h, const float* basis, int n_mels, int n_freq) 
     if (wts.empty()) wts.push_back(0.f);
     if (ensure_sk(h, false)) return 1;      // the forward DFT of a large batch takes a balanced build: its hand-off area is never allocated on the request path
     MelBasisW& mb = h->melb;
-    if (mb.loaded) {                        // replace: nothing in flight may still read the old bank
-        HIPCHK(h, hipDeviceSynchronize());
-        for (void* p : {(void*)mb.span, (void*)mb.wts}) {
-            auto it = std::find(h->owned.begin(), h->owned.end(), p);
-            if (it != h->owned.end()) { h->owned.erase(it); hipFree(p); }
-        }
-        mb = MelBasisW();
-    }
+    if (mb.loaded) { if (drop_owned(h, {mb.span, mb.wts})) return 1; mb = MelBasisW(); }
     if (dev_upload(h, span, &mb.span) || dev_upload(h, wts, &mb.wts)) return 1;
     mb.n_mels = n_mels; mb.nb = nb; mb.loaded = true;
     return 0;
 }
 
 int ev_mel_spectrogram(ev_handle* h, const float* d_audio, int B, int L, float out_scale, float out_shift, float* d_mel, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (!h->melb.loaded) return fail(h, "mel basis not loaded (ev_load_mel_basis)");
     if (B <= 0 || L <= 384 || (L & 255) || !d_audio || !d_mel) return fail(h, "bad arguments B=%d L=%d (L must be a multiple of 256, > 384: reflect padding of 384 needs more than 384 samples, as in torch's pad)", B, L);
     if ((double)B * (L / 256 + 12) * 1032 * 4.0 >= 4294967296.0) return fail(h, "audio batch exceeds the 4 GiB buffer-addressing limit: split the batch");
@@ -2766,504 +2759,13 @@ int ev_mel_spectrogram(ev_handle* h, const float* d_audio, int B, int L, float o
     return run_mel(h, d_audio, B, L, out_scale, out_shift, d_mel);
 }
 
-// The resampler.  LDS budget of a launch: 64 KiB (16384 floats) for the phase table and the input span together, so that at least two
-// workgroups share a CU and no launch needs a raised LDS grant.  Plan: 1024 outputs per workgroup while their input span fits the budget,
-// else 256, else the span is not staged at all (the kernel reads x from global memory: filters of tens of thousands of taps per phase);
-// the table is staged when it fits beside the span, else read from global memory (L2-resident: at most 66 K floats).
-int ev_load_resampler(ev_handle* h, const float* taps, int n_taps, int up, int down) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!taps) return fail(h, "ev_load_resampler: null taps");
-    if (up < 1 || up > 640 || down < 1 || down > 640) return fail(h, "ev_load_resampler: up=%d down=%d outside 1 <= up, down <= 640", up, down);
-    if (std::gcd(up, down) != 1) return fail(h, "ev_load_resampler: gcd(up, down) must be 1 (up=%d down=%d: reduce the ratio)", up, down);
-    if (n_taps < 1 || n_taps > 65537 || !(n_taps & 1)) return fail(h, "ev_load_resampler: n_taps=%d must be odd and <= 65537", n_taps);
-    ResamplerW r;
-    r.up = up; r.down = down; r.n_taps = n_taps;
-    r.W = (n_taps + up - 1) / up; r.Wp = r.W | 1; r.tab_floats = round_up(up * r.Wp, 4);
-    std::vector<float> tab((size_t)r.tab_floats, 0.f);
-    for (int k = 0; k < n_taps; ++k) tab[(size_t)(k % up) * r.Wp + k / up] = taps[k];
-    ResamplerW& cur = h->rs;
-    if (cur.loaded) {                       // replace: nothing in flight may still read the old table
-        HIPCHK(h, hipDeviceSynchronize());
-        auto it = std::find(h->owned.begin(), h->owned.end(), (void*)cur.table);
-        if (it != h->owned.end()) { h->owned.erase(it); hipFree(cur.table); }
-        cur = ResamplerW();
-    }
-    if (dev_upload(h, tab, &r.table)) return 1;
-    r.loaded = true;
-    cur = r;
-    return 0;
-}
-
-int ev_resample(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L_in, float* d_y, int L_out, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    const ResamplerW& r = h->rs;
-    if (!r.loaded) return fail(h, "resampler not loaded (ev_load_resampler)");
-    if (B < 1 || B > 65535) return fail(h, "ev_resample: B=%d outside 1 <= B <= 65535", B);
-    if (L_in < 1 || !d_x || !d_y) return fail(h, "ev_resample: bad arguments L_in=%d (L_in >= 1, non-null tensors)", L_in);
-    const long long want = ((long long)L_in * r.up + r.down - 1) / r.down;
-    if (want > 2147483647LL || (long long)L_out != want)
-        return fail(h, "ev_resample: L_out=%d must be ceil(L_in * up / down) = %lld (L_in=%d up=%d down=%d) and fit 31 bits", L_out, want, L_in, r.up, r.down);
-    h->stream = (hipStream_t)stream;
-    constexpr int BUDGET = 16384;           // floats of LDS per workgroup
-    auto span_of = [&](int tile) { return (long long)r.W + ((long long)(r.up - 1) + (long long)(tile - 1) * r.down) / r.up; };
-    int tile = 1024;
-    bool sx = true;
-    if (span_of(1024) > BUDGET) { tile = 256; sx = span_of(256) <= BUDGET; }
-    const int span = sx ? (int)span_of(tile) : 0;
-    const bool st = span + r.tab_floats <= BUDGET;
-    ResampleParams p{};
-    p.x = d_x; p.len = d_len; p.y = d_y; p.table = r.table;
-    p.L_in = L_in; p.L_out = L_out; p.up = r.up; p.down = r.down; p.c = (r.n_taps - 1) / 2; p.W = r.W; p.Wp = r.Wp; p.span = span; p.tab_floats = r.tab_floats;
-    const size_t smem = ((size_t)span + (st ? r.tab_floats : 0)) * sizeof(float);
-    const dim3 grid((unsigned)((L_out + tile - 1) / tile), (unsigned)B);
-    hipStream_t s = h->stream;
-    if (tile == 1024) { if (st) launch<resample_kernel<1024, true, true>>(h->device, grid, dim3(256), smem, s, p); else launch<resample_kernel<1024, true, false>>(h->device, grid, dim3(256), smem, s, p); }
-    else if (sx)      { if (st) launch<resample_kernel<256, true, true>>(h->device, grid, dim3(256), smem, s, p);  else launch<resample_kernel<256, true, false>>(h->device, grid, dim3(256), smem, s, p); }
-    else              { if (st) launch<resample_kernel<256, false, true>>(h->device, grid, dim3(256), smem, s, p); else launch<resample_kernel<256, false, false>>(h->device, grid, dim3(256), smem, s, p); }
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
-int ev_mel_stats(ev_handle* h, const float* d_mel, const int32_t* d_len, int B, int C, int T, double* d_row_sums, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (B < 1 || B > 65535 || C < 1 || T < 1 || !d_mel || !d_len || !d_row_sums)
-        return fail(h, "ev_mel_stats: bad arguments B=%d C=%d T=%d (1 <= B <= 65535, C >= 1, T >= 1, non-null tensors)", B, C, T);
-    h->stream = (hipStream_t)stream;
-    const int ntiles = (T + 31) / 32;
-    if (scratch_acquire(h, h->stat_ws, (size_t)B * ntiles * 2 * sizeof(double))) return 1;
-    double* part = (double*)h->stat_ws.p;
-    hipLaunchKernelGGL(mel_stats_kernel, dim3(ntiles, B), dim3(256), 0, h->stream, d_mel, d_len, C, T, part, ntiles);
-    hipLaunchKernelGGL(cfm_loss_merge_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, (const double*)part, ntiles, B, d_row_sums);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
-// Silence trimming.  The hop blocks of a row start at -off, off = (F/2) mod H, so that every frame [f H - F/2, f H + F/2) is F / H whole
-// blocks (kernels: ev_kernels.h); nblk = ceil((L + off) / H) blocks per row, 12 bytes each: all float64 sums first, then all fp32 maxima.
-int ev_trim_bounds(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, int frame_length, int hop_length, float top_db,
-                   int32_t* d_bounds, float* d_peak, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (B < 1 || B > 65535) return fail(h, "ev_trim_bounds: B=%d outside 1 <= B <= 65535", B);
-    if (L < 1 || !d_x || !d_bounds) return fail(h, "ev_trim_bounds: bad arguments L=%d (L >= 1, non-null d_x and d_bounds)", L);
-    const int F = frame_length, H = hop_length;
-    if (H < 64 || H > 4096 || H % 64) return fail(h, "ev_trim_bounds: hop_length=%d must be a multiple of 64 and at most 4096", H);
-    if (F < H || F % H) return fail(h, "ev_trim_bounds: frame_length=%d must be a multiple of hop_length=%d (frame_length %% hop_length != 0)", F, H);
-    if (F / H > 64) return fail(h, "ev_trim_bounds: frame_length / hop_length = %d exceeds 64 (frame_length=%d hop_length=%d)", F / H, F, H);
-    h->stream = (hipStream_t)stream;
-    const int R = F / H, off = (F / 2) % H;
-    const int nblk = (int)(((long long)L + off + H - 1) / H);
-    if (scratch_acquire(h, h->trim_ws, (size_t)B * nblk * 12)) return 1;
-    double* bsum = (double*)h->trim_ws.p;
-    float* bmax = (float*)(bsum + (size_t)B * nblk);
-    TrimBlocksParams pb{};
-    pb.x = d_x; pb.len = d_len; pb.bsum = bsum; pb.bmax = bmax; pb.L = L; pb.H = H; pb.off = off; pb.nblk = nblk;
-    launch<trim_blocks_kernel>(h->device, dim3((unsigned)((nblk + TRIM_TILE - 1) / TRIM_TILE), (unsigned)B), dim3(256), 0, h->stream, pb);
-    TrimBoundsParams pf{};
-    pf.bsum = bsum; pf.bmax = bmax; pf.len = d_len; pf.bounds = d_bounds; pf.peak = d_peak;
-    pf.L = L; pf.H = H; pf.R = R; pf.off = off; pf.nblk = nblk; pf.F = (double)F; pf.thr = pow(10.0, -(double)top_db / 10.0);
-    launch<trim_bounds_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pf);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
-int ev_trim_apply(ev_handle* h, const float* d_x, const int32_t* d_bounds, const float* d_peak, float target_peak, int B, int L,
-                  float* d_y, int L_out, int32_t* d_out_len, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (B < 1 || B > 65535) return fail(h, "ev_trim_apply: B=%d outside 1 <= B <= 65535", B);
-    if (L < 1 || L_out < 1 || !d_x || !d_bounds || !d_y || !d_out_len)
-        return fail(h, "ev_trim_apply: bad arguments L=%d L_out=%d (L >= 1, L_out >= 1, non-null d_x, d_bounds, d_y and d_out_len)", L, L_out);
-    h->stream = (hipStream_t)stream;
-    TrimApplyParams p{};
-    p.x = d_x; p.bounds = d_bounds; p.peak = d_peak; p.y = d_y; p.out_len = d_out_len; p.target = target_peak; p.L = L; p.L_out = L_out;
-    launch<gather_scale_kernel>(h->device, dim3((unsigned)(((long long)L_out + 1023) / 1024), (unsigned)B), dim3(256), 0, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
-// Pitch tracking: one workgroup per (frame, row); LDS = 4 (tau_max + 1) float64 partials + the W + tau_max + 1 staged samples (ev_kernels.h).
-int ev_pitch_yin(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, int frame_length, int hop_length, int tau_min,
-                 int tau_max, float threshold, int32_t* d_lag, float* d_period, float* d_cmnd, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (B < 1 || B > 65535) return fail(h, "ev_pitch_yin: B=%d outside 1 <= B <= 65535", B);
-    if (L < 1 || !d_x) return fail(h, "ev_pitch_yin: bad arguments L=%d (L >= 1, non-null d_x)", L);
-    const int W = frame_length, H = hop_length;
-    if (H < 64 || H > 4096 || H % 64) return fail(h, "ev_pitch_yin: hop_length=%d must be a multiple of 64 and at most 4096", H);
-    if (W < 64 || W > 4096 || W % 64) return fail(h, "ev_pitch_yin: frame_length=%d must be a multiple of 64 with 64 <= frame_length <= 4096", W);
-    if (tau_min < 1 || tau_min > tau_max || tau_max > 2048)
-        return fail(h, "ev_pitch_yin: tau_min=%d tau_max=%d outside 1 <= tau_min <= tau_max <= 2048", tau_min, tau_max);
-    if (!(threshold > 0.f && threshold <= 1.f)) return fail(h, "ev_pitch_yin: threshold=%g outside 0 < threshold <= 1", (double)threshold);
-    if (!d_lag && !d_period && !d_cmnd) return fail(h, "ev_pitch_yin: no output (at least one of d_lag, d_period, d_cmnd must be non-null)");
-    h->stream = (hipStream_t)stream;
-    PitchYinParams p{};
-    p.x = d_x; p.len = d_len; p.lag = d_lag; p.period = d_period; p.cmnd = d_cmnd;
-    p.L = L; p.F = (int)(((long long)L + H - 1) / H); p.W = W; p.H = H; p.tau_min = tau_min; p.tau_max = tau_max; p.thr = (double)threshold;
-    const size_t n = (size_t)tau_max + 1;
-    const size_t smem = 4 * n * sizeof(double) + ((size_t)W + n) * sizeof(float);
-    launch<pitch_yin_kernel>(h->device, dim3((unsigned)p.F, (unsigned)B), dim3(256), smem, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
-// Probabilistic YIN, the observation: pitch_yin_kernel's grid and LDS plus the trough tables behind them (pyin_observe_kernel, ev_kernels.h).
-// The threshold prior travels in the kernel's arguments (n_thr <= 128), with its ascending prefix sums.
-int ev_pyin_observe(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, int frame_length, int hop_length, int tau_min,
-                    int tau_max, double sr, double fmin, int bins_per_octave, int n_bins, const double* w, int n_thr, double boltzmann,
-                    double no_trough_prob, double* d_obs, double* d_pv, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (B < 1 || B > 65535) return fail(h, "ev_pyin_observe: B=%d outside 1 <= B <= 65535", B);
-    if (L < 1 || !d_x) return fail(h, "ev_pyin_observe: bad arguments L=%d (L >= 1, non-null d_x)", L);
-    const int W = frame_length, H = hop_length;
-    if (H < 64 || H > 4096 || H % 64) return fail(h, "ev_pyin_observe: hop_length=%d must be a multiple of 64 and at most 4096", H);
-    if (W < 64 || W > 4096 || W % 64)
-        return fail(h, "ev_pyin_observe: frame_length=%d must be a multiple of 64 with 64 <= frame_length <= 4096", W);
-    if (tau_min < 1 || tau_min > tau_max || tau_max > 2048)
-        return fail(h, "ev_pyin_observe: tau_min=%d tau_max=%d outside 1 <= tau_min <= tau_max <= 2048", tau_min, tau_max);
-    if (n_thr < 1 || n_thr > 128) return fail(h, "ev_pyin_observe: n_thr=%d outside 1 <= n_thr <= 128", n_thr);
-    if (n_bins < 2 || n_bins > 1024) return fail(h, "ev_pyin_observe: n_bins=%d outside 2 <= n_bins <= 1024", n_bins);
-    if (bins_per_octave < 1) return fail(h, "ev_pyin_observe: bins_per_octave=%d must be at least 1", bins_per_octave);
-    if (!(sr > 0.0) || !(fmin > 0.0) || !std::isfinite(sr) || !std::isfinite(fmin))
-        return fail(h, "ev_pyin_observe: sr=%g and fmin=%g must be positive and finite", sr, fmin);
-    if (!(boltzmann > 0.0) || !std::isfinite(boltzmann)) return fail(h, "ev_pyin_observe: boltzmann=%g must be positive and finite", boltzmann);
-    if (!(no_trough_prob >= 0.0 && no_trough_prob <= 1.0))
-        return fail(h, "ev_pyin_observe: no_trough_prob=%g outside 0 <= no_trough_prob <= 1", no_trough_prob);
-    if (!w) return fail(h, "ev_pyin_observe: w must be non-null (HOST, n_thr doubles)");
-    for (int t = 0; t < n_thr; ++t)
-        if (!(w[t] >= 0.0) || !std::isfinite(w[t])) return fail(h, "ev_pyin_observe: w[%d]=%g is not a finite weight >= 0", t, w[t]);
-    if (!d_obs || !d_pv) return fail(h, "ev_pyin_observe: no output (d_obs and d_pv must be non-null)");
-    h->stream = (hipStream_t)stream;
-    PyinObserveParams p{};
-    p.x = d_x; p.len = d_len; p.obs = d_obs; p.pv = d_pv;
-    p.L = L; p.F = (int)(((long long)L + H - 1) / H); p.W = W; p.H = H; p.tau_min = tau_min; p.tau_max = tau_max;
-    p.n_bins = n_bins; p.n_thr = n_thr; p.kmax = (tau_max - tau_min) / 2 + 1;
-    p.sr = sr; p.fmin = fmin; p.bpo = (double)bins_per_octave; p.lambda = boltzmann; p.c0 = 1.0 - std::exp(-boltzmann); p.ntp = no_trough_prob;
-    double run = 0.0;
-    for (int t = 0; t < n_thr; ++t) { p.w[t] = w[t]; run += w[t]; p.cw[t + 1] = run; }
-    const size_t n = (size_t)tau_max + 1, kmax = (size_t)p.kmax;
-    const size_t yin = (4 * n * sizeof(double) + ((size_t)W + n) * sizeof(float) + 7) / 8 * 8;
-    p.off_extra = (int)yin;
-    const size_t smem = yin + (2 * kmax + 1 + (size_t)n_thr + 1 + (size_t)n_bins + 4) * sizeof(double)
-                      + (3 * kmax + 8 + (kmax + 63) / 64 * ((size_t)n_thr + 1)) * sizeof(int);
-    launch<pyin_observe_kernel>(h->device, dim3((unsigned)p.F, (unsigned)B), dim3(256), smem, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
-// Probabilistic YIN, the decoding: one workgroup per row, one thread per state (two beyond 1024 states); LDS = 2 x 2 n_bins float64 of delta,
-// the two transition tables and the end state's reduction (pyin_decode_kernel, ev_kernels.h).  The host tables travel in the kernel's arguments.
-int ev_pyin_decode(ev_handle* h, const double* d_obs, const double* d_pv, const int32_t* d_len, int B, int L, int hop_length, int n_bins, int R,
-                   const double* log_tri, const double* log_Z, double log_stay, double log_switch, uint8_t* d_back, int32_t* d_state,
-                   double* d_loglik, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (B < 1 || B > 65535) return fail(h, "ev_pyin_decode: B=%d outside 1 <= B <= 65535", B);
-    if (L < 1) return fail(h, "ev_pyin_decode: L=%d must be at least 1", L);
-    const int H = hop_length;
-    if (H < 64 || H > 4096 || H % 64) return fail(h, "ev_pyin_decode: hop_length=%d must be a multiple of 64 and at most 4096", H);
-    if (n_bins < 2 || n_bins > 1024) return fail(h, "ev_pyin_decode: n_bins=%d outside 2 <= n_bins <= 1024", n_bins);
-    if (R < 0 || R > 63) return fail(h, "ev_pyin_decode: R=%d outside 0 <= R <= 63", R);
-    if (!(log_stay < 0.0) || !(log_switch < 0.0) || !std::isfinite(log_stay) || !std::isfinite(log_switch))
-        return fail(h, "ev_pyin_decode: switch_prob outside 0 < switch_prob < 1 (log_stay=%g and log_switch=%g must be finite and negative)",
-                    log_stay, log_switch);
-    if (!d_obs || !d_pv) return fail(h, "ev_pyin_decode: d_obs and d_pv must be non-null");
-    if (!log_tri || !log_Z) return fail(h, "ev_pyin_decode: log_tri (HOST, R + 1 doubles) and log_Z (HOST, n_bins doubles) must be non-null");
-    if (!d_back) return fail(h, "ev_pyin_decode: d_back must be non-null (B x F x 2 n_bins bytes of the caller's)");
-    if (!d_state || !d_loglik) return fail(h, "ev_pyin_decode: no output (d_state and d_loglik must be non-null)");
-    for (int d = 0; d <= R; ++d) if (!std::isfinite(log_tri[d])) return fail(h, "ev_pyin_decode: log_tri[%d]=%g is not finite", d, log_tri[d]);
-    for (int j = 0; j < n_bins; ++j) if (!std::isfinite(log_Z[j])) return fail(h, "ev_pyin_decode: log_Z[%d]=%g is not finite", j, log_Z[j]);
-    h->stream = (hipStream_t)stream;
-    PyinDecodeParams p{};
-    p.obs = d_obs; p.pv = d_pv; p.len = d_len; p.back = d_back; p.state = d_state; p.loglik = d_loglik;
-    p.L = L; p.F = (int)(((long long)L + H - 1) / H); p.H = H; p.n_bins = n_bins; p.R = R;
-    p.init = -std::log(2.0 * (double)n_bins); p.tiny = std::numeric_limits<double>::min();
-    for (int d = 0; d <= R; ++d) { p.t_stay[d] = log_tri[d] + log_stay; p.t_switch[d] = log_tri[d] + log_switch; }
-    if (n_bins <= 128) for (int j = 0; j < n_bins; ++j) p.zc[j] = log_Z[j];
-    else {
-        for (int j = 63; j <= n_bins - 64; ++j)
-            if (log_Z[j] != log_Z[63])
-                return fail(h, "ev_pyin_decode: log_Z[%d] differs from log_Z[63]: log_Z must be constant over R <= j <= n_bins - 1 - R", j);
-        for (int j = 0; j < 64; ++j) { p.zc[j] = log_Z[j]; p.zc[64 + j] = log_Z[n_bins - 64 + j]; }
-    }
-    const int S = 2 * n_bins, NT = std::min(1024, round_up(S, 64));
-    const size_t smem = (2 * (size_t)S + 16 + 128) * sizeof(double) + 16 * sizeof(int);
-    launch<pyin_decode_kernel>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
-// Dynamic time warping: one workgroup per row (dtw_kernel, ev_kernels.h).  LDS plan in bytes: [D ring 3 x Tx float64][S ring 3 x Tx uint16],
-// reused after the forward pass as the path stage of Tx + Ty - 1 words; then the decision words ceil(Ty / 32) x Tx x 8 bytes where they still
-// fit into the CU's 160 KiB, else in the handle's arena.  Without a path there are no decision words at all.
-int ev_dtw(ev_handle* h, const float* d_x, const float* d_y, const int32_t* d_xlen, const int32_t* d_ylen, int B, int C, int Tx, int Ty, int metric,
-           double* d_cost, int32_t* d_steps, int32_t* d_path, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    constexpr size_t LDS_MAX = 160 * 1024 - 64;                          // (the kernel's one static word is taken off the CU's 160 KiB)
-    if (B < 1 || B > 65535) return fail(h, "ev_dtw: B=%d outside 1 <= B <= 65535", B);
-    if (C < 1 || C > 128) return fail(h, "ev_dtw: C=%d outside 1 <= C <= 128", C);
-    if (Tx < 1 || Tx > 4096) return fail(h, "ev_dtw: Tx=%d outside 1 <= Tx <= 4096", Tx);
-    if (Ty < 1 || Ty > 4096) return fail(h, "ev_dtw: Ty=%d outside 1 <= Ty <= 4096", Ty);
-    if (metric != 0 && metric != 1) return fail(h, "ev_dtw: metric=%d is neither 0 (Euclidean) nor 1 (squared Euclidean)", metric);
-    if (!d_x || !d_y) return fail(h, "ev_dtw: d_x and d_y must be non-null");
-    if (!d_cost || !d_steps) return fail(h, "ev_dtw: d_cost and d_steps must be non-null");
-    h->stream = (hipStream_t)stream;
-    DtwParams p{};
-    p.x = d_x; p.y = d_y; p.xlen = d_xlen; p.ylen = d_ylen; p.cost = d_cost; p.steps = d_steps; p.path = d_path;
-    p.C = C; p.Tx = Tx; p.Ty = Ty; p.nyw = (Ty + 31) / 32; p.metric = metric;
-    p.off_s = 3 * Tx * (int)sizeof(double);
-    const size_t ring = (size_t)p.off_s + 3 * (size_t)Tx * sizeof(unsigned short);
-    size_t smem = (ring + 15) / 16 * 16;
-    if (d_path) {
-        smem = (std::max(ring, (size_t)(Tx + Ty - 1) * sizeof(unsigned int)) + 15) / 16 * 16;
-        p.off_bits = (int)smem;
-        const size_t bit_bytes = (size_t)p.nyw * Tx * sizeof(unsigned long long);
-        if (smem + bit_bytes <= LDS_MAX) smem += bit_bytes;
-        else {
-            if (scratch_acquire(h, h->dtw_ws, (size_t)B * bit_bytes)) return 1;
-            p.gbits = (unsigned long long*)h->dtw_ws.p;
-        }
-    }
-    const int NT = std::min(1024, round_up(Tx, 64));
-    const int R = (Tx + NT - 1) / NT;                                    // 1 .. 4 rows of the matrix per thread
-    if (R == 1) launch<dtw_kernel<1, 8>>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
-    else if (R == 2) launch<dtw_kernel<2, 8>>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
-    else launch<dtw_kernel<4, 4>>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
-// Loudness (kernels and the scheme: ev_kernels.h).  Arena, in doubles: [state B x NC x 4][pieces B x NC x npp][sub-block energies B x NS, only
-// without d_sub]; NC = ceil(NS S / LOUD_CHUNK) chunks that can hold a counted sample, npp = the most sub-blocks a chunk can touch.
-int ev_loudness(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, int sub_len, const double* coef, double abs_gate,
-                double* d_sub, double* d_block, double* d_gated, int32_t* d_counts, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int S = sub_len;
-    if (B < 1 || B > 65535) return fail(h, "ev_loudness: B=%d outside 1 <= B <= 65535", B);
-    if (S < 16 || S > 65536) return fail(h, "ev_loudness: sub_len=%d outside 16 <= sub_len <= 65536", S);
-    if (L < 1) return fail(h, "ev_loudness: L=%d must be at least 1", L);
-    if (!d_x) return fail(h, "ev_loudness: d_x must be non-null");
-    if (!coef) return fail(h, "ev_loudness: coef must be non-null (HOST, 10 doubles)");
-    if (!d_gated || !d_counts) return fail(h, "ev_loudness: d_gated and d_counts must be non-null");
-    for (int st = 0; st < 2; ++st) {
-        const double a1 = coef[5 * st + 3], a2 = coef[5 * st + 4];
-        bool finite = true;
-        for (int i = 0; i < 5; ++i) finite = finite && std::isfinite(coef[5 * st + i]);
-        if (!(finite && std::fabs(a2) < 1.0 && std::fabs(a1) < 1.0 + a2))
-            return fail(h, "ev_loudness: coef stage %d is unstable or not finite (a1=%g a2=%g; |a2| < 1 and |a1| < 1 + a2 expected)", st + 1, a1, a2);
-    }
-    h->stream = (hipStream_t)stream;
-    LoudCoef k{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8], coef[9]};
-    const int NS = L / S, NB = std::max(NS - 3, 0);
-    const int NC = (int)(((long long)NS * S + LOUD_CHUNK - 1) / LOUD_CHUNK);
-    const int npp = (LOUD_CHUNK + S - 2) / S + 1;
-    const size_t n_state = (size_t)B * NC * 4, n_part = (size_t)B * NC * npp, n_sub = d_sub ? 0 : (size_t)B * NS;
-    double* sub = d_sub;
-    if (NS > 0) {
-        if (scratch_acquire(h, h->loud_ws, (n_state + n_part + n_sub) * sizeof(double))) return 1;
-        double* state = (double*)h->loud_ws.p;
-        double* part = state + n_state;
-        if (!sub) sub = part + n_part;
-        LoudChunkParams pc{};
-        pc.x = d_x; pc.len = d_len; pc.state = state; pc.part = part; pc.L = L; pc.S = S; pc.NC = NC; pc.npp = npp; pc.k = k;
-        LoudCarryParams pk{};
-        pk.state = state; pk.len = d_len; pk.L = L; pk.S = S; pk.NC = NC;
-        for (int c = 0; c < 4; ++c) {                                    // column c of M: the state LOUD_CHUNK zero samples after unit state c
-            double s[4] = {0.0, 0.0, 0.0, 0.0};
-            s[c] = 1.0;
-            for (int n = 0; n < LOUD_CHUNK; ++n) {
-                const double x = 0.0;
-                const double y1 = std::fma(k.b0, x, s[0]);
-                s[0] = std::fma(-k.a1, y1, std::fma(k.b1, x, s[1]));
-                s[1] = std::fma(-k.a2, y1, k.b2 * x);
-                const double y2 = std::fma(k.c0, y1, s[2]);
-                s[2] = std::fma(-k.d1, y2, std::fma(k.c1, y1, s[3]));
-                s[3] = std::fma(-k.d2, y2, k.c2 * y1);
-            }
-            for (int r = 0; r < 4; ++r) pk.M[4 * r + c] = s[r];
-        }
-        const dim3 grid((unsigned)((NC + 63) / 64), (unsigned)B);
-        launch<loud_chunk_kernel<false>>(h->device, grid, dim3(64), 0, h->stream, pc);
-        launch<loud_carry_kernel>(h->device, dim3((unsigned)B), dim3(64), 0, h->stream, pk);
-        launch<loud_chunk_kernel<true>>(h->device, grid, dim3(64), 0, h->stream, pc);
-        LoudMergeParams pm{};
-        pm.part = part; pm.len = d_len; pm.sub = sub; pm.L = L; pm.S = S; pm.NC = NC; pm.npp = npp; pm.NS = NS;
-        launch<loud_merge_kernel>(h->device, dim3((unsigned)((NS + 255) / 256), (unsigned)B), dim3(256), 0, h->stream, pm);
-    }
-    LoudGateParams pg{};
-    pg.sub = sub; pg.len = d_len; pg.block = d_block; pg.gated = d_gated; pg.counts = d_counts;
-    pg.L = L; pg.S = S; pg.NS = NS; pg.NB = NB; pg.abs_gate = abs_gate;
-    launch<loud_gate_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pg);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
-// STOI / ESTOI (kernels, the definition and every order: ev_kernels.h).  Arena: [E B x NF doubles][band spectra B x 2 x n_bands x NM doubles,
-// only without d_tob][segment scores B x NSEG x 2 doubles, only without d_seg][idx B x NF int32].
-int ev_load_stoi(ev_handle* h, const double* window, const double* twiddle, const int32_t* bands, int W, int H, int nfft, int n_bands, int N) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!window || !twiddle || !bands) return fail(h, "ev_load_stoi: window, twiddle and bands must be non-null (HOST)");
-    if (H < 32 || H > 256 || H % 32) return fail(h, "ev_load_stoi: H=%d must be a multiple of 32 with 32 <= H <= 256", H);
-    if (W != 2 * H) return fail(h, "ev_load_stoi: W=%d must be 2 H = %d (the overlap-add has exactly two terms)", W, 2 * H);
-    if (nfft < W || nfft > 1024) return fail(h, "ev_load_stoi: nfft=%d outside W <= nfft <= 1024 (W=%d)", nfft, W);
-    if (n_bands < 1 || n_bands > 32) return fail(h, "ev_load_stoi: n_bands=%d outside 1 <= n_bands <= 32", n_bands);
-    if (N < 2 || N > 64) return fail(h, "ev_load_stoi: N=%d outside 2 <= N <= 64", N);
-    StoiW t;
-    t.W = W; t.H = H; t.nfft = nfft; t.n_bands = n_bands; t.N = N;
-    t.bin_lo = nfft; t.bin_hi = 0;
-    for (int r = 0; r < n_bands; ++r) {
-        const int first = bands[2 * r], end = bands[2 * r + 1];
-        if (first < 0 || first >= end || end > nfft / 2 + 1)
-            return fail(h, "ev_load_stoi: bands[%d] = [%d, %d) outside 0 <= first < end <= nfft / 2 + 1 = %d", r, first, end, nfft / 2 + 1);
-        t.bin_lo = std::min(t.bin_lo, first); t.bin_hi = std::max(t.bin_hi, end);
-    }
-    for (int j = 0; j < W; ++j) if (!std::isfinite(window[j])) return fail(h, "ev_load_stoi: window[%d] is not finite", j);
-    for (int j = 0; j < 2 * nfft; ++j) if (!std::isfinite(twiddle[j])) return fail(h, "ev_load_stoi: twiddle[%d] is not finite", j);
-    StoiW& cur = h->stoi;
-    if (cur.loaded) {                       // replace: nothing in flight may still read the old tables
-        HIPCHK(h, hipDeviceSynchronize());
-        for (void* q : {(void*)cur.win, (void*)cur.tw, (void*)cur.bands}) {
-            auto it = std::find(h->owned.begin(), h->owned.end(), q);
-            if (it != h->owned.end()) { h->owned.erase(it); hipFree(q); }
-        }
-        cur = StoiW();
-    }
-    if (dev_upload(h, std::vector<double>(window, window + W), &t.win)) return 1;
-    if (dev_upload(h, std::vector<double>(twiddle, twiddle + 2 * (size_t)nfft), &t.tw)) return 1;
-    if (dev_upload(h, std::vector<int32_t>(bands, bands + 2 * (size_t)n_bands), &t.bands)) return 1;
-    t.loaded = true;
-    cur = t;
-    return 0;
-}
-
-int ev_stoi(ev_handle* h, const float* d_x, const float* d_y, const int32_t* d_len, int B, int L, double silence_ratio, double clip,
-            uint8_t* d_keep, double* d_tob, double* d_seg, double* d_score, int32_t* d_counts, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    const StoiW& w = h->stoi;
-    if (!w.loaded) return fail(h, "ev_stoi: tables not loaded (ev_load_stoi)");
-    if (B < 1 || B > 65535) return fail(h, "ev_stoi: B=%d outside 1 <= B <= 65535", B);
-    if (L < 1) return fail(h, "ev_stoi: L=%d must be at least 1", L);
-    if (!d_x || !d_y) return fail(h, "ev_stoi: d_x and d_y must be non-null");
-    if (!(silence_ratio > 0.0 && silence_ratio < 1.0)) return fail(h, "ev_stoi: silence_ratio=%g outside 0 < silence_ratio < 1", silence_ratio);
-    if (!(clip > 1.0) || !std::isfinite(clip)) return fail(h, "ev_stoi: clip=%g must be finite and greater than 1", clip);
-    if (!d_score || !d_counts) return fail(h, "ev_stoi: d_score and d_counts must be non-null");
-    h->stream = (hipStream_t)stream;
-    const int NF = L > w.W ? (L - w.W + w.H - 1) / w.H : 0, NM = std::max(NF - 1, 0), NSEG = std::max(NM - w.N + 1, 0);
-    const size_t n_e = (size_t)B * NF, n_tob = d_tob ? 0 : (size_t)B * 2 * w.n_bands * NM, n_seg = d_seg ? 0 : (size_t)B * NSEG * 2;
-    if (scratch_acquire(h, h->stoi_ws, (n_e + n_tob + n_seg) * sizeof(double) + n_e * sizeof(int32_t))) return 1;
-    double* E = (double*)h->stoi_ws.p;
-    double* tob = d_tob ? d_tob : E + n_e;
-    double* seg = d_seg ? d_seg : E + n_e + n_tob;
-    int32_t* idx = (int32_t*)(E + n_e + n_tob + n_seg);
-    StoiTables t{w.win, w.tw, w.bands, w.W, w.H, w.nfft, w.n_bands, w.N, w.bin_lo, w.bin_hi};
-    if (NF > 0) {
-        StoiEnergyParams pe{d_x, d_len, E, t, L, NF};
-        launch<stoi_energy_kernel>(h->device, dim3((unsigned)((NF + 63) / 64), (unsigned)B), dim3(64), 0, h->stream, pe);
-    }
-    StoiSelectParams ps{E, d_len, idx, d_keep, d_counts, t, L, NF, silence_ratio};
-    launch<stoi_select_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, ps);
-    if (NM > 0) {
-        StoiBandParams pb{d_x, d_y, idx, d_counts, tob, t, L, NF, NM};
-        const size_t smem = ((size_t)2 * w.nfft + 2 * w.W + 2 * (w.bin_hi - w.bin_lo)) * sizeof(double);
-        launch<stoi_band_kernel>(h->device, dim3((unsigned)NM, (unsigned)B), dim3(256), smem, h->stream, pb);
-    }
-    if (NSEG > 0) {
-        StoiSegParams pg{tob, d_counts, seg, t, NM, NSEG, clip};
-        const size_t smem = ((size_t)2 * w.n_bands * (w.N | 1) + 64) * sizeof(double);
-        launch<stoi_segment_kernel>(h->device, dim3((unsigned)NSEG, (unsigned)B), dim3(64), smem, h->stream, pg);
-    }
-    StoiMeanParams pm{seg, d_counts, d_score, NSEG};
-    launch<stoi_mean_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pm);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
-// Multi-resolution STFT distance at one resolution (kernels, the definition and every order: ev_kernels.h).  Arena: B x NF x 4 doubles, only
-// without d_frame.
-int ev_load_stft_dist(ev_handle* h, const double* window, const double* twiddle, int W, int H, int nfft) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!window || !twiddle) return fail(h, "ev_load_stft_dist: window and twiddle must be non-null (HOST)");
-    if (nfft < 16 || nfft > 2048 || nfft % 2) return fail(h, "ev_load_stft_dist: nfft=%d must be even with 16 <= nfft <= 2048", nfft);
-    if ((nfft - W) % 2) return fail(h, "ev_load_stft_dist: nfft - W = %d must be even (the window is padded centrally)", nfft - W);
-    if (W < 4 || W > nfft || W % 4) return fail(h, "ev_load_stft_dist: W=%d must be a multiple of 4 with 4 <= W <= nfft = %d", W, nfft);
-    if (H < 1 || H > 512) return fail(h, "ev_load_stft_dist: H=%d outside 1 <= H <= 512", H);
-    for (int j = 0; j < W; ++j) if (!std::isfinite(window[j])) return fail(h, "ev_load_stft_dist: window[%d] is not finite", j);
-    for (int j = 0; j < 2 * nfft; ++j) if (!std::isfinite(twiddle[j])) return fail(h, "ev_load_stft_dist: twiddle[%d] is not finite", j);
-    StftDistW t;
-    t.W = W; t.H = H; t.nfft = nfft; t.NB = nfft / 2 + 1; t.skew = ((2 - H) % 4 + 4) % 4;
-    StftDistW& cur = h->stftd;
-    if (cur.loaded) {                       // replace: nothing in flight may still read the old basis
-        HIPCHK(h, hipDeviceSynchronize());
-        auto it = std::find(h->owned.begin(), h->owned.end(), (void*)cur.basis);
-        if (it != h->owned.end()) { h->owned.erase(it); hipFree(cur.basis); }
-        cur = StftDistW();
-    }
-    double* d_win = nullptr; double* d_tw = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d_win, (size_t)W * sizeof(double)));
-    if (hipMalloc((void**)&d_tw, (size_t)2 * nfft * sizeof(double)) != hipSuccess) { hipFree(d_win); return fail(h, "ev_load_stft_dist: hipMalloc of the twiddles failed"); }
-    const size_t n_basis = (size_t)W * t.NB;
-    hipError_t e = hipMalloc((void**)&t.basis, n_basis * sizeof(double2));
-    if (e == hipSuccess) e = hipMemcpy(d_win, window, (size_t)W * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_tw, twiddle, (size_t)2 * nfft * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        StftBasisParams pb{d_win, d_tw, t.basis, W, nfft, t.NB};
-        launch<stft_dist_basis_kernel>(h->device, dim3((unsigned)((n_basis + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pb);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    hipFree(d_win); hipFree(d_tw);
-    if (e != hipSuccess) { if (t.basis) hipFree(t.basis); return fail(h, "ev_load_stft_dist: building the basis failed: %s", hipGetErrorString(e)); }
-    h->owned.push_back(t.basis);
-    ++h->n_allocs;                          // (the basis is the handle's largest table: 33.6 MB at W = nfft = 2048)
-    t.loaded = true;
-    cur = t;
-    return 0;
-}
-
-int ev_stft_dist(ev_handle* h, const float* d_x, const float* d_y, const int32_t* d_len, int B, int L, double power_floor,
-                 double* d_frame, double* d_sums, int32_t* d_counts, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    const StftDistW& w = h->stftd;
-    if (!w.loaded) return fail(h, "ev_stft_dist: tables not loaded (ev_load_stft_dist)");
-    if (B < 1 || B > 65535) return fail(h, "ev_stft_dist: B=%d outside 1 <= B <= 65535", B);
-    if (L < 1) return fail(h, "ev_stft_dist: L=%d must be at least 1", L);
-    if (!d_x || !d_y) return fail(h, "ev_stft_dist: d_x and d_y must be non-null");
-    if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_stft_dist: power_floor=%g must be finite and greater than 0", power_floor);
-    if (!d_sums || !d_counts) return fail(h, "ev_stft_dist: d_sums and d_counts must be non-null");
-    h->stream = (hipStream_t)stream;
-    if (L / w.H > 0x7fffffef) return fail(h, "ev_stft_dist: L=%d at H=%d has more frames than an int32 tile index holds", L, w.H);
-    const int NF = L > w.nfft / 2 ? 1 + L / w.H : 0;
-    double* frame = d_frame;
-    if (!frame && NF > 0) {
-        if (scratch_acquire(h, h->stftd_ws, (size_t)B * NF * 4 * sizeof(double))) return 1;
-        frame = (double*)h->stftd_ws.p;
-    }
-    StftDistTables t{w.basis, w.W, w.H, w.nfft, w.NB, w.skew};
-    if (NF > 0) {
-        StftFramesParams pf{d_x, d_y, d_len, frame, t, L, NF, power_floor};
-        const int span = 15 * w.H + w.W;
-        const size_t smem = (size_t)2 * (span + w.skew * ((span - 1) / w.H)) * sizeof(float);
-        launch<stft_dist_frames_kernel>(h->device, dim3((unsigned)((NF + 15) / 16), (unsigned)B), dim3(256), smem, h->stream, pf);
-    }
-    StftRowsParams pr{frame, d_len, d_sums, d_counts, t, L, NF};
-    launch<stft_dist_rows_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pr);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
+// The analysis side's 14 entry points, from ev_load_resampler to ev_stft_dist, with the checks they share (its own namespace { } and
+// extern "C" { } nest in this block).  Here and not at the end of the file: the kernel templates are instantiated in the order the host code
+// names them, and this place keeps the code object's order that of the single file
+#include "ev_analysis.h"
 
 int ev_hifigan(ev_handle* h, const float* d_mel, int B, int T, float* d_wav, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     if (!h->voc.loaded) return fail(h, "vocoder weights not loaded");
     if (B <= 0 || T <= 0 || !d_mel || !d_wav) return fail(h, "bad arguments B=%d T=%d", B, T);
     h->stream = (hipStream_t)stream;
@@ -3567,8 +3069,7 @@ int ev_dbg_conv_bench(ev_handle* h, int Cin, int Cout, int K, int dil, int B, in
     const bool no_res = (dbg & 128) != 0;     // bit 128: no residual input
     const bool no_pro = (dbg & 512) != 0;     // bit 512: no prologue activation (the estimator's layers)
     dbg &= ~(64 | 32 | 128 | 512);
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = nullptr;
     std::vector<float> w((size_t)Cout * Cin * K), b(Cout);
     unsigned s = 12345u;
@@ -3635,8 +3136,7 @@ int ev_dbg_conv_bench(ev_handle* h, int Cin, int Cout, int K, int dil, int B, in
 // ---------------------------------------------------------------------------
 int ev_op_conv1d(ev_handle* h, const float* d_x, const float* w, const float* bias, int B, int Cin, int T, int Cout, int K,
                  int dilation, int transposed, int stride, int padding, float pre_lrelu_slope, float* d_y, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = (hipStream_t)stream;
     ConvLayer L;
     HostTensor wt, bt;
@@ -3705,8 +3205,7 @@ int ev_op_conv1d(ev_handle* h, const float* d_x, const float* w, const float* bi
 
 int ev_op_groupnorm_mish(ev_handle* h, const float* d_x, const float* d_gamma, const float* d_beta, const int32_t* d_lengths,
                          int B, int C, int T, int groups, float* d_y, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = (hipStream_t)stream;
     if (groups != 8 || C != 256) return fail(h, "groupnorm op: C=256, groups=8 only");
     Geom g{B * (T + 4), T + 4, 2, T};
@@ -3729,8 +3228,7 @@ int ev_op_groupnorm_mish(ev_handle* h, const float* d_x, const float* d_gamma, c
 int ev_op_groupnorm_mish2(ev_handle* h, const float* d_x, const float* d_gamma, const float* d_beta, const int32_t* d_lengths,
                           int B, int C, int T, int groups, int mode, const float* d_temb, int temb_stride, const float* d_R,
                           float* d_y, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = (hipStream_t)stream;
     if (groups != 8 || C != 256) return fail(h, "groupnorm op: C=256, groups=8 only");
     if (B <= 0 || T <= 0 || !d_x || !d_gamma || !d_beta || !d_lengths || !d_y || mode < 0 || mode > 2 ||
@@ -3766,8 +3264,7 @@ int ev_op_groupnorm_mish2(ev_handle* h, const float* d_x, const float* d_gamma, 
 int ev_op_conv_groupnorm(ev_handle* h, const float* d_x, const float* w, const float* bias, int Cin, int T, int K, const float* d_gamma,
                          const float* d_beta, const int32_t* d_lengths, int mode, const float* d_temb, const float* d_R, float* d_conv,
                          float* d_part, float* d_y, int* tiles_out, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = (hipStream_t)stream;
     constexpr int C = 256;
     if (Cin <= 0 || T <= 0 || K <= 0 || !(K & 1) || !d_x || !w || !d_gamma || !d_beta || !d_lengths || !d_conv || !d_part || !d_y || !tiles_out ||
@@ -3827,8 +3324,7 @@ int ev_op_split_pieces(ev_handle* h, const float* d_x, int n, float* d_pieces, v
 }
 
 int ev_op_layernorm(ev_handle* h, const float* d_x, const float* d_gamma, const float* d_beta, int rows, int C, float* d_y, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = (hipStream_t)stream;
     if (C != 256) return fail(h, "layernorm op: C=256 only");
     Geom g{rows, rows, 0, rows};
@@ -3839,8 +3335,7 @@ int ev_op_layernorm(ev_handle* h, const float* d_x, const float* d_gamma, const 
 int ev_op_ln_mlp(ev_handle* h, const float* d_x, const float* d_ln_g, const float* d_ln_b, const float* w1, const float* b1,
                  const float* d_alpha_exp, const float* d_beta_inv, const float* w2, const float* b2, const float* d_rowmask,
                  int rows, int M1, int mode, float* d_y, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = (hipStream_t)stream;
     if (rows <= 0 || (M1 % 128) || !d_x || !w1 || !d_y || (mode == 0 && (!w2 || !b2 || !b1 || !d_alpha_exp || !d_beta_inv))) return fail(h, "ev_op_ln_mlp: bad arguments");
     size_t owned0 = h->owned.size();
@@ -3870,8 +3365,7 @@ int ev_op_ln_mlp(ev_handle* h, const float* d_x, const float* d_ln_g, const floa
 // plan_est sizes EstBufs::ATTP, and launch_attn's own rule picks the build; ran (2 ints) = {0 one launch | 1 split-key, KS}.
 static int op_attention_impl(const char* who, ev_handle* h, const float* d_qkv, const int32_t* d_lengths, int B, int S, int P, int T, int heads,
                              int no_scratch, float* d_out, int* ran, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = (hipStream_t)stream;
     if (B <= 0 || T <= 0 || P < 0 || S < P + T || heads <= 0 || (long)B * S > 0x7fffffffL / (3 * heads * 64) || !d_qkv || !d_lengths || !d_out)
         return fail(h, "%s: bad arguments", who);
@@ -3913,8 +3407,7 @@ int ev_op_attention(ev_handle* h, const float* d_qkv, const int32_t* d_lengths, 
 // weight bound (qkv_pack_scales).  ran (3 ints) = {0 fp32 | 1 fp16 pipe, ntail, nq}.
 static int op_attn_out_impl(const char* who, ev_handle* h, const float* d_qkv, const int32_t* d_lengths, int B, int S, int P, int T, const float* w_out,
                             const float* b_out, float sq, float sk, float sv, float* d_hid, int* ran, void* stream) {
-    if (!h) return 1;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (enter(h)) return 1;
     h->stream = (hipStream_t)stream;
     const bool given = sq != 0.f || sk != 0.f || sv != 0.f;
     if (B <= 0 || T <= 0 || P < 0 || S < P + T || (long)B * S > 0x7fffffffL / 384 || !d_qkv || !d_lengths || !w_out || !b_out || !d_hid)

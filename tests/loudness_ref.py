@@ -22,7 +22,7 @@ import pitch_ref as P
 OFFSET = -0.691
 ABS_GATE = 10.0 ** ((-70.0 + 0.691) / 10.0)
 GARBAGE = 50.0                           # what lies behind a row's length: loud, so that reading it would show
-CHUNK = 1024                             # LOUD_CHUNK of ev_kernels.h: the edge cases sit around it
+CHUNK = 1024                             # LOUD_CHUNK of ev_analysis_kernels.h: the edge cases sit around it
 
 # the BS.1770-4 table: the two biquads at 48 kHz, in ev_loudness' layout
 TABLE_48K = np.array([1.53512485958697, -2.69169618940638, 1.19839281085285, -1.69065929318241, 0.73248077421585,

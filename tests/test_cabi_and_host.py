@@ -33,6 +33,16 @@ def test_header_symbols_exported():
     assert lib.ev_abi_version() == 4
 
 
+def test_build_staleness_check_covers_every_source():
+    """build_library rebuilds when a file of _lib.SOURCES is newer than the library: a file under csrc/ that is not listed would leave a
+    stale library in place after an edit."""
+    listed = {os.path.realpath(p) for p in _lib.SOURCES}
+    for name in sorted(os.listdir(_lib.CSRC)):
+        assert os.path.realpath(os.path.join(_lib.CSRC, name)) in listed, f"csrc/{name} is not in _lib.SOURCES"
+    assert os.path.realpath(os.path.join(REPO, "include", "emojivoice.h")) in listed
+    assert all(os.path.isfile(p) for p in _lib.SOURCES) and _lib.SOURCES[0].endswith("ev_engine.hip")
+
+
 def test_driver_build_hook_accepts_the_library():
     """__graft_entry__.build()'s post-compile check (ABI of the loaded library == the header's) — without the two-minute compile."""
     import __graft_entry__ as entry

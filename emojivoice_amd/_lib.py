@@ -38,6 +38,7 @@ EXPORTS = [
     "ev_op_attention2", "ev_op_attn_out2",
     "ev_load_stoi", "ev_stoi",
     "ev_load_stft_dist", "ev_stft_dist",
+    "ev_load_voice_quality", "ev_voice_quality",
 ]
 
 
@@ -163,6 +164,8 @@ def load_library() -> C.CDLL:
     lib.ev_stoi.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
     lib.ev_load_stft_dist.argtypes = [vp, vp, vp, i32, i32, i32]
     lib.ev_stft_dist.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
+    lib.ev_load_voice_quality.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, C.c_double]
+    lib.ev_voice_quality.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -521,6 +524,42 @@ class Engine:
         self._check(self.lib.ev_stft_dist(self.h, x.data_ptr(), y.data_ptr(), _ptr(ln), B, L, float(power_floor), _ptr(frame), sums.data_ptr(),
                                           counts.data_ptr(), _stream_ptr()), "ev_stft_dist")
         return frame, sums, counts
+
+    def load_voice_quality(self, window, twiddle, H: int, nfft: int, bands, slope_w, q_fit: int, q_min: int, q_max: int, fit_w, q_mean: float) -> None:
+        """One geometry of ``voice_quality`` (ev_load_voice_quality), the tables on the host: ``window`` (W,) float64, ``twiddle`` (nfft, 2)
+        float64 {cos, sin}(2 pi n / nfft), ``H`` the hop, ``bands`` (6, 2) int32 {first bin, end bin}, ``slope_w`` (2, nfft / 2 + 1) float64,
+        the quefrencies, ``fit_w`` (q_max - q_fit + 1,) float64 and ``q_mean`` (``audio.voice_quality_tables`` makes them).  The handle builds
+        the windowed DFT basis and the cepstral basis on the device."""
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float64).reshape(-1))
+        tw = np.ascontiguousarray(np.asarray(twiddle, dtype=np.float64).reshape(-1, 2))
+        bd = np.ascontiguousarray(np.asarray(bands, dtype=np.int32).reshape(-1))
+        sw = np.ascontiguousarray(np.asarray(slope_w, dtype=np.float64).reshape(-1))
+        fw = np.ascontiguousarray(np.asarray(fit_w, dtype=np.float64).reshape(-1))
+        NQ = int(q_max) - int(q_fit) + 1
+        if tw.shape[0] != int(nfft) or bd.size != 12 or sw.size != 2 * (int(nfft) // 2 + 1) or fw.size != NQ:
+            raise ValueError(f"load_voice_quality: {nfft} twiddles, 12 band edges, {2 * (int(nfft) // 2 + 1)} slope weights and {NQ} fit weights "
+                             f"expected, got {tw.shape[0]}, {bd.size}, {sw.size} and {fw.size}")
+        self._check(self.lib.ev_load_voice_quality(self.h, w.ctypes.data, tw.ctypes.data, int(w.shape[0]), int(H), int(nfft), bd.ctypes.data,
+                                                   sw.ctypes.data, int(q_fit), int(q_min), int(q_max), fw.ctypes.data, float(q_mean)),
+                    "ev_load_voice_quality")
+        self.voice_quality_geometry = (int(w.shape[0]), int(H), int(nfft), NQ)
+
+    def voice_quality(self, x, lengths, power_floor: float, want_cepstrum: bool = False):
+        """The voice-quality figures of every frame of every row of ``x`` (B, L) at the loaded geometry (ev_voice_quality, after
+        load_voice_quality): (frame (B, NF, 8) float64: per frame {cpp, alpha ratio, Hammarberg index, slope 0, slope 1, power, C[q*], the
+        baseline at q*}, peak (B, NF) int32: q*, cepstrum (B, NF, NQ) float64 or None) on the device, NF = ceil(L / H).  ``lengths`` (B,):
+        samples per row (None: L)."""
+        if not hasattr(self, "voice_quality_geometry"):
+            raise EvLibraryError("voice_quality: tables not loaded (load_voice_quality)")
+        x, B, L, ln = self._rows(x, lengths, "voice_quality")
+        _, H, _, NQ = self.voice_quality_geometry
+        NF = -(-L // H)
+        frame = torch.empty((B, NF, 8), dtype=torch.float64, device=x.device)
+        peak = torch.empty((B, NF), dtype=torch.int32, device=x.device)
+        cep = torch.empty((B, NF, NQ), dtype=torch.float64, device=x.device) if want_cepstrum else None
+        self._check(self.lib.ev_voice_quality(self.h, x.data_ptr(), _ptr(ln), B, L, float(power_floor), frame.data_ptr(), peak.data_ptr(), _ptr(cep),
+                                              _stream_ptr()), "ev_voice_quality")
+        return frame, peak, cep
 
     def pyin_observe(self, x, lengths, frame_length: int, hop_length: int, tau_min: int, tau_max: int, sr: float, fmin: float,
                      bins_per_octave: int, n_bins: int, w, boltzmann: float = 2.0, no_trough_prob: float = 0.01, out=None):

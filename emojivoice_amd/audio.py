@@ -47,6 +47,14 @@ And their spectral-magnitude distance (``ev_stft_dist``: the multi-resolution ST
 distance, a float64 DFT on the matrix cores):
 
     r = stft_distance(recording, synthesis)                   # {"mstft" (B,), "sc" (B,), "log_mag" (B,), "lsd_db" (B,), "per_resolution", "frames" (B, 3)}
+
+And voice quality, what separates a tense voice from a breathy or a flat one (``ev_voice_quality``: the spectral-balance descriptors of
+eGeMAPS, Eyben et al. 2016, and the cepstral peak prominence of Hillenbrand et al. 1994, per frame on ``pitch_yin``'s frames; the figures are
+comparable across this project's runs, not to the digit with Praat or VoiceSauce):
+
+    vq = voice_quality(y)                                     # {"cpp_db", "alpha_ratio_db", "hammarberg_db", "slope_0_500", "slope_500_1500", "power",
+                                                              #  "peak_quefrency", "cepstral_f0"}, each (B, F)
+    st = voice_quality_statistics(vq, pitch_yin(y)["voiced"]) # per row the means over the voiced, non-silent frames, their count and the sums
 """
 from __future__ import annotations
 
@@ -849,3 +857,103 @@ def stft_distance(reference, degraded, lengths=None, resolutions=MSTFT_RESOLUTIO
 
     return {"sc": mean([p["sc"] for p in per]), "log_mag": mean([p["log_mag"] for p in per]), "lsd_db": mean([p["lsd_db"] for p in per]),
             "mstft": mean([p["sc"] + p["log_mag"] for p in per]), "per_resolution": per, "frames": torch.stack(frames, dim=1)}
+
+
+VOICE_QUALITY_FIGURES = ("cpp_db", "alpha_ratio_db", "hammarberg_db", "slope_0_500", "slope_500_1500")
+VOICE_QUALITY_BANDS_HZ = ((50, 1000), (1000, 5000), (0, 2000), (2000, 5000), (0, 500), (500, 1500))   # alpha lo / hi, Hammarberg lo / hi, slopes
+
+
+def voice_quality_tables(sr: int, n_fft: int, fmin: float = 65.0, fmax: float = 600.0) -> Dict:
+    """The host tables of ``ev_load_voice_quality`` at rate ``sr``: {"bands" (6, 2) int32: the bins [ceil(lo n_fft / sr), ceil(hi n_fft / sr)) of
+    the alpha ratio's 50-1000 and 1000-5000 Hz, the Hammarberg index's 0-2000 and 2000-5000 Hz and the slopes' 0-500 and 500-1500 Hz;
+    "slope_w" (2, n_fft / 2 + 1) float64: the centred least-squares slope weights of the two slope bands over x = bin frequency in kHz, zeros
+    outside; "q_fit" = round(sr / 1000) (1 ms), "q_min" = ceil(sr / fmax), "q_max" = min(floor(sr / fmin), n_fft / 2): the quefrencies of the
+    baseline fit and of the peak search, in samples; "fit_w" (q_max - q_fit + 1,) float64: the centred slope weights over q_fit .. q_max;
+    "q_mean": their mean}."""
+    sr, n_fft = int(sr), int(n_fft)
+    if sr < 1 or n_fft < 16 or n_fft % 2:
+        raise ValueError(f"voice_quality_tables: sr={sr} must be positive and n_fft={n_fft} even and at least 16")
+    if not (0 < fmin <= fmax):
+        raise ValueError(f"voice_quality_tables: 0 < fmin <= fmax expected (got fmin={fmin} fmax={fmax})")
+    NB = n_fft // 2 + 1
+    bands = np.array([[-(-(lo * n_fft) // sr), -(-(hi * n_fft) // sr)] for lo, hi in VOICE_QUALITY_BANDS_HZ], dtype=np.int32)
+    if int(bands.max()) > NB or bool((bands[:, 1] <= bands[:, 0]).any()) or bool((bands[4:, 1] - bands[4:, 0] < 2).any()):
+        raise ValueError(f"voice_quality_tables: sr={sr} with n_fft={n_fft} leaves a band empty, a slope band under 2 bins or a band past the "
+                         f"Nyquist bin (bins {bands.tolist()} of {NB})")
+    slope_w = np.zeros((2, NB), dtype=np.float64)
+    for b in range(2):
+        lo, hi = int(bands[4 + b, 0]), int(bands[4 + b, 1])
+        x = np.arange(lo, hi, dtype=np.float64) * sr / n_fft / 1000.0
+        d = x - x.mean()
+        slope_w[b, lo:hi] = d / np.sum(d * d)
+    q_fit, q_min, q_max = int(round(sr / 1000.0)), int(math.ceil(sr / fmax)), min(int(math.floor(sr / fmin)), n_fft // 2)
+    if not (1 <= q_fit <= q_min <= q_max) or q_max - q_fit + 1 < 2:
+        raise ValueError(f"voice_quality_tables: sr={sr} n_fft={n_fft} fmin={fmin} fmax={fmax} give q_fit={q_fit} q_min={q_min} q_max={q_max}, "
+                         "outside 1 <= q_fit <= q_min <= q_max")
+    q = np.arange(q_fit, q_max + 1, dtype=np.float64)
+    d = q - q.mean()
+    return {"bands": bands, "slope_w": slope_w, "q_fit": q_fit, "q_min": q_min, "q_max": q_max, "fit_w": d / np.sum(d * d), "q_mean": float(q.mean())}
+
+
+def _voice_quality_engine(device: torch.device, sr: int, n_fft: int, hop: int, fmin: float, fmax: float) -> Engine:
+    def load(eng):
+        t = voice_quality_tables(sr, n_fft, fmin, fmax)
+        eng.load_voice_quality(stft_dist_window(n_fft), stoi_twiddle(n_fft), hop, n_fft, t["bands"], t["slope_w"], t["q_fit"], t["q_min"], t["q_max"],
+                               t["fit_w"], t["q_mean"])
+    return _cached_engine(device, ("voice_quality", int(sr), int(n_fft), int(hop), float(fmin), float(fmax)), load)
+
+
+@torch.inference_mode()
+def voice_quality(y, sr: int = 22050, fmin: float = 65.0, fmax: float = 600.0, frame_length: int = 1024, hop_length: int = 256, lengths=None,
+                  power_floor: float = 1e-7):
+    """Voice quality per frame on the device (``ev_voice_quality``; no torch fallback): from the float64 log-power spectrum of every frame
+    (periodic Hann window of ``frame_length`` = n_fft points, zeros outside the row, the power clamped at ``power_floor``) the alpha ratio
+    (1-5 kHz over 50-1000 Hz), the Hammarberg index (strongest bin of 0-2 kHz over that of 2-5 kHz), the least-squares spectral slopes of
+    0-500 Hz and 500-1500 Hz in dB per kHz (eGeMAPS; Eyben et al. 2016), and from its cepstrum the cepstral peak prominence (Hillenbrand et
+    al. 1994): the cepstral peak between sr / fmax and sr / fmin over the least-squares line through the cepstrum from 1 ms on, at the peak.
+    Frame f is ``pitch_yin``'s frame f at the same hop.  ``y`` 1-D, or (B, L) with ``lengths`` (B,) samples or None, on the GPU ->
+    {"cpp_db", "alpha_ratio_db", "hammarberg_db", "slope_0_500", "slope_500_1500", "power": (B, F) float64; "peak_quefrency" (B, F) int32:
+    q* in samples; "cepstral_f0" (B, F) float32: sr / q*}, F = ceil(L / hop_length); a 1-D input gives B = 1.  A silent frame (no bin above
+    the floor) and a frame past a row's ceil(len / hop_length) have zeros everywhere but a silent frame's power.  The cepstrum is the linear
+    real cepstrum of the dB spectrum: the figures are comparable across runs of this project (a recording against its synthesis, voice by
+    voice); Praat and Hillenbrand put the cepstral magnitude in dB as well and VoiceSauce analyses pitch-synchronous windows, so they are not
+    comparable to the digit with those tools."""
+    _trim_input(y, "voice_quality")
+    eng = _voice_quality_engine(y.device, sr, frame_length, hop_length, fmin, fmax)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    frame, peak, _ = eng.voice_quality(x, lengths if y.dim() == 2 else None, power_floor)
+    has = peak > 0
+    out = {k: frame[:, :, i] for i, k in enumerate(VOICE_QUALITY_FIGURES + ("power",))}
+    out["peak_quefrency"] = peak
+    out["cepstral_f0"] = torch.where(has, float(sr) / peak.clamp(min=1).to(torch.float64), torch.zeros_like(peak, dtype=torch.float64)).to(torch.float32)
+    return out
+
+
+@torch.inference_mode()
+def voice_quality_statistics(vq, voiced, lengths=None):
+    """Per utterance, from ``voice_quality`` and a voicing mask at the same hop (``pitch_yin`` / ``pitch_pyin``): {"cpp_db", "alpha_ratio_db",
+    "hammarberg_db", "slope_0_500", "slope_500_1500": (B,) float64, the mean over the frames that are voiced and not silent
+    (``peak_quefrency`` > 0), NaN where no frame qualifies; "frames" (B,) int64: how many did; "sums": the same five keys, (B,) float64 sums
+    over those frames, for pooling over utterances}, where ``vq`` lives (torch ops only).  Entries are (B, F) or 1-D; ``lengths`` (B,): the
+    FRAMES that belong to each row (None: F)."""
+    peak = torch.as_tensor(vq["peak_quefrency"])
+    voiced = torch.as_tensor(voiced, dtype=torch.bool, device=peak.device)
+    one = peak.dim() == 1
+    if one:
+        peak, voiced = peak.unsqueeze(0), voiced.unsqueeze(0)
+    B, F = peak.shape
+    if voiced.shape != peak.shape:
+        raise ValueError(f"voice_quality_statistics: the mask {tuple(voiced.shape)} does not match the figures {tuple(peak.shape)}")
+    n = torch.full((B,), F, dtype=torch.int64, device=peak.device) if lengths is None else torch.as_tensor(lengths).to(peak.device, torch.int64)
+    if n.numel() != B:
+        raise ValueError(f"voice_quality_statistics: {B} lengths expected, got {n.numel()}")
+    use = voiced & (peak > 0) & (torch.arange(F, device=peak.device)[None, :] < n[:, None])
+    count = use.sum(dim=1)
+    out = {"frames": count, "sums": {}}
+    for k in VOICE_QUALITY_FIGURES:
+        v = torch.as_tensor(vq[k], dtype=torch.float64).to(peak.device)
+        v = v.unsqueeze(0) if one else v
+        s = torch.where(use, v, torch.zeros_like(v)).sum(dim=1)
+        out["sums"][k] = s
+        out[k] = torch.where(count > 0, s / count.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
+    return out

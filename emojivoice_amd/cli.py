@@ -15,6 +15,8 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean                              # trimmed, levelled 22.05 kHz wavs + clean/filelist.txt + raw.txt.durations.json
     python -m emojivoice_amd.cli --prosody_report clean/filelist.txt                                    # clean/filelist.txt.prosody.json: f0 per file and per speaker
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt                                             # pairs.txt.eval.json: MCD, f0 RMSE, voicing error per 'recorded.wav|synthesised.wav[|spk]'
+    python -m emojivoice_amd.cli --voice_report clean/filelist.txt                                      # clean/filelist.txt.voice.json: CPP, alpha ratio, Hammarberg index, spectral slopes per file and per speaker
+    python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --voice_quality                             # ... and, per pair, the voice-quality figures of both sides and their differences
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
     python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000          # clean/filelist.txt.vocoder.json: STOI / ESTOI, mel L1 and loudness shift of copy synthesis
@@ -65,6 +67,8 @@ def write_wav_pcm16(path, wav: np.ndarray, sr: int = 22050):
 def validate_args(args):
     if getattr(args, "spectral_distance", False):
         assert getattr(args, "vocoder_report", None), "--spectral_distance is an option of --vocoder_report"
+    if getattr(args, "voice_quality", False):
+        assert getattr(args, "evaluate_pairs", None), "--voice_quality is an option of --evaluate_pairs"
     if args.sample_rate is not None:
         assert args.sample_rate > 0, "--sample_rate must be positive"
     if args.prepare_dataset:
@@ -76,7 +80,7 @@ def validate_args(args):
             sr = int(args.sample_rate or 22050)
             assert sr % 10 == 0 and sr >= 8000, "--target_lufs needs a --sample_rate that is a multiple of 10 and at least 8000"
         return args
-    if getattr(args, "prosody_report", None) or getattr(args, "evaluate_pairs", None) or getattr(args, "loudness_report", None):
+    if getattr(args, "prosody_report", None) or getattr(args, "evaluate_pairs", None) or getattr(args, "loudness_report", None) or getattr(args, "voice_report", None):
         assert args.batch_size > 0, "Batch size must be greater than 0"
         return args
     if getattr(args, "vocoder_report", None):
@@ -466,6 +470,62 @@ def prosody_report(args, device):
     return rep
 
 
+def voice_means(sums, frames):
+    """The five voice-quality figures as sums / frames (None for each without a frame): how a file's, a speaker's and the overall means are
+    formed from per-file sums over the voiced frames."""
+    return {k: (sums[k] / frames if frames else None) for k in sums}
+
+
+@torch.inference_mode()
+def voice_report(args, device):
+    """--voice_report FILELIST (the filelist format of --prosody_report): every file is loaded with audio.load_audio(path, 22050), measured by
+    audio.voice_quality on the frames of the pitch tracker (--pitch_method) and reduced by audio.voice_quality_statistics over the frames that are
+    voiced and not silent, --batch_size files at a time.  FILELIST.voice.json receives per file seconds, frames, voiced_frames and the means
+    of cpp_db, alpha_ratio_db, hammarberg_db, slope_0_500 and slope_500_1500 (null without such a frame); per speaker and overall the same
+    means POOLED over the voiced frames (the files' sums over the files' counts), with the file count.  The figures are comparable across
+    runs of this tool, not to the digit with Praat or VoiceSauce (audio.voice_quality says why)."""
+    from . import audio
+
+    files, pooled = [], {}
+    for chunk, batch, lens in filelist_batches(args.voice_report, args.batch_size, PROSODY_SR, device):
+        pitch = pitch_tracker(args)(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
+        vq = audio.voice_quality(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
+        n_frames = [-(-n // PROSODY_HOP) for n in lens]
+        st = audio.voice_quality_statistics(vq, pitch["voiced"], n_frames)
+        count = st["frames"].cpu()
+        sums = {k: v.cpu() for k, v in st["sums"].items()}
+        for r, (wav, spk, _) in enumerate(chunk):
+            spk = spk if spk is not None else "0"
+            own = {k: float(sums[k][r]) for k in audio.VOICE_QUALITY_FIGURES}
+            files.append({"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r], "voiced_frames": int(count[r]),
+                          **voice_means(own, int(count[r]))})
+            acc = pooled.setdefault(spk, {"files": 0, "voiced_frames": 0, "sums": {k: [] for k in audio.VOICE_QUALITY_FIGURES}})
+            acc["files"] += 1
+            acc["voiced_frames"] += int(count[r])
+            for k in own:
+                acc["sums"][k].append(own[k])
+
+    def pool(accs):
+        n = sum(a["voiced_frames"] for a in accs)
+        return {"files": sum(a["files"] for a in accs), "voiced_frames": n,
+                **voice_means({k: math.fsum(v for a in accs for v in a["sums"][k]) for k in audio.VOICE_QUALITY_FIGURES}, n)}
+
+    rep = {"sample_rate": PROSODY_SR, "hop_length": PROSODY_HOP, "files": files, "speakers": {k: pool([v]) for k, v in pooled.items()},
+           "overall": pool(list(pooled.values()))}
+    if pitch_method(args) != "yin":
+        rep["pitch_method"] = pitch_method(args)
+    out_path = f"{args.voice_report}.voice.json"
+    with open(out_path, "w") as f:
+        json.dump(rep, f, indent=1)
+    for k in sorted(rep["speakers"]):
+        v = rep["speakers"][k]
+        fig = "no voiced frame" if v["cpp_db"] is None else (f"CPP {v['cpp_db']:.2f} dB, alpha ratio {v['alpha_ratio_db']:.1f} dB, Hammarberg {v['hammarberg_db']:.1f} dB, "
+                                                            f"slopes {v['slope_0_500']:.1f} / {v['slope_500_1500']:.1f} dB/kHz")
+        print(f"[i] speaker {k}: {v['files']} files, {v['voiced_frames']} voiced frames, {fig}")
+    print(f"[+] Voice report saved: {Path(out_path).resolve()}")
+    return rep
+
+
 LOUDNESS_SR = 22050          # the analysis rate, as for the prosody report
 LOUDNESS_OUTLIER_LU = 3.0    # a file this far from its speaker's mean is listed
 
@@ -664,7 +724,10 @@ def evaluate_pairs(args, device):
     --batch_size pairs at a time (padded to the longest, each row with its lengths).  PAIRS.eval.json receives per pair mcd_db,
     f0_rmse_cents (null without a frame pair voiced on both sides), voicing_error, voiced_pairs, frames_recorded, frames_synthesised and
     path_steps; per speaker and overall their means, f0 pooled over the both-voiced frame pairs; and under "skipped" the pairs with a file
-    too short for a mel (or longer than 4096 frames).  Needs no checkpoint."""
+    too short for a mel (or longer than 4096 frames).  Needs no checkpoint.
+    --voice_quality adds per pair "voice": {"recorded", "synthesised", "delta"}: the means of audio.voice_quality's five figures over each
+    side's own voiced, non-silent frames and synthesised - recorded (null where a side has no such frame), and per speaker and overall
+    "voice": per figure the mean and the mean absolute value of the deltas.  It compares utterance-level means, so it needs no alignment."""
     from . import audio
 
     entries = parse_pairs(args.evaluate_pairs)
@@ -681,7 +744,12 @@ def evaluate_pairs(args, device):
         for r, w in enumerate(wavs):
             cep[r, :, : frames[r]] = audio.mel_cepstrum(audio.mel_spectrogram(w, *EVAL_MEL), 13)[0]   # per file: each signal's own reflect padding
             sig[r, : w.shape[1]] = w[0]
-        return cep, frames, pitch_tracker(args)(sig, sr, hop_length=hop, lengths=[w.shape[1] for w in wavs])
+        lens = [w.shape[1] for w in wavs]
+        pitch = pitch_tracker(args)(sig, sr, hop_length=hop, lengths=lens)
+        if getattr(args, "voice_quality", False):
+            st = audio.voice_quality_statistics(audio.voice_quality(sig, sr, hop_length=hop, lengths=lens), pitch["voiced"], frames)
+            pitch["voice"] = [{k: (None if math.isnan(float(st[k][r])) else float(st[k][r])) for k in audio.VOICE_QUALITY_FIGURES} for r in range(len(wavs))]
+        return cep, frames, pitch
 
     for b0 in range(0, len(entries), args.batch_size):
         chunk = []
@@ -706,11 +774,25 @@ def evaluate_pairs(args, device):
             records.append({"recorded": rec, "synthesised": syn, "speaker": spk, "mcd_db": float(mcd[r]), "f0_rmse_cents": f0["rmse_cents"][r],
                             "voicing_error": float(verr[r]), "voiced_pairs": int(nv[r]), "frames_recorded": fr_a[r], "frames_synthesised": fr_b[r],
                             "path_steps": int(steps[r])})
+            if "voice" in pitch_a:
+                va, vb = pitch_a["voice"][r], pitch_b["voice"][r]
+                records[-1]["voice"] = {"recorded": va, "synthesised": vb,
+                                        "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
+
+    def means(recs):
+        out = evaluation_means(recs)
+        if getattr(args, "voice_quality", False):
+            out["voice"] = {}
+            for k in audio.VOICE_QUALITY_FIGURES:
+                d = [r["voice"]["delta"][k] for r in recs if r["voice"]["delta"][k] is not None]
+                out["voice"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
+        return out
+
     by_spk = {}
     for r in records:
         by_spk.setdefault(r["speaker"], []).append(r)
-    rep = {"sample_rate": sr, "hop_length": hop, "n_coeffs": 13, "pairs": records, "speakers": {k: evaluation_means(v) for k, v in by_spk.items()},
-           "overall": evaluation_means(records) if records else None, "skipped": skipped}
+    rep = {"sample_rate": sr, "hop_length": hop, "n_coeffs": 13, "pairs": records, "speakers": {k: means(v) for k, v in by_spk.items()},
+           "overall": means(records) if records else None, "skipped": skipped}
     if pitch_method(args) != "yin":
         rep["pitch_method"] = pitch_method(args)
     out_path = f"{args.evaluate_pairs}.eval.json"
@@ -790,7 +872,16 @@ def cli(argv=None):
     p.add_argument("--spectral_distance", action="store_true", help="--vocoder_report: add the multi-resolution STFT distance (\"mstft\": spectral convergence "
                    "\"sc\" + log-magnitude L1 \"log_mag\" at 1024/120/600, 2048/240/1200 and 512/50/240) and the log-spectral distance \"lsd_db\" per file, "
                    "with mean and maximum per speaker and overall")
+    p.add_argument("--voice_report", type=str, default=None, help="voice-quality analysis instead of synthesis: a filelist 'path|spk|text' -> FILELIST.voice.json: "
+                   "cepstral peak prominence, alpha ratio, Hammarberg index and the spectral slopes 0-500 / 500-1500 Hz, averaged over the voiced frames "
+                   "(--pitch_method) per file, per speaker and overall (on the device, --batch_size files per batch; needs no checkpoint)")
+    p.add_argument("--voice_quality", action="store_true", help="--evaluate_pairs: add \"voice\" per pair (the five voice-quality means of the recording, of the "
+                   "synthesis and their differences) and per speaker and overall (mean and mean absolute difference)")
     args = validate_args(p.parse_args(argv))
+    if args.voice_report:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return voice_report(args, torch.device("cuda", 0))
     if args.vocoder_report:
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")

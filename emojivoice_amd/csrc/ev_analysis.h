@@ -1,5 +1,5 @@
 // Host entry points of the analysis side: resampling, dataset statistics, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness,
-// STOI / ESTOI and the STFT distance (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
+// STOI / ESTOI, the STFT distance and voice quality (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
 // after ev_handle, fail / HIPCHK / enter, dev_upload, drop_owned, scratch_acquire and launch<>.  None of these calls runs on the engine's conv
 // path; ev_load_mel_basis, ev_mel_spectrogram, ev_denoise and ev_stft_magnitude do, and stay in ev_engine.hip.
 #pragma once
@@ -483,6 +483,91 @@ int ev_stft_dist(ev_handle* h, const float* d_x, const float* d_y, const int32_t
     }
     StftRowsParams pr{frame, d_len, d_sums, d_counts, t, L, NF};
     launch<stft_dist_rows_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pr);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Voice quality: spectral balance and cepstral peak prominence per frame (kernels, the definition and every order: ev_analysis_kernels.h).  One
+// device block per load holds the four tables; a call needs no arena.
+int ev_load_voice_quality(ev_handle* h, const double* window, const double* twiddle, int W, int H, int nfft, const int32_t* bands,
+                          const double* slope_w, int q_fit, int q_min, int q_max, const double* fit_w, double q_mean) {
+    if (enter(h)) return 1;
+    if (!window || !twiddle || !bands || !slope_w || !fit_w)
+        return fail(h, "ev_load_voice_quality: window, twiddle, bands, slope_w and fit_w must be non-null (HOST)");
+    if (nfft < 16 || nfft > 1024 || nfft % 2) return fail(h, "ev_load_voice_quality: nfft=%d must be even with 16 <= nfft <= 1024", nfft);
+    if ((nfft - W) % 2) return fail(h, "ev_load_voice_quality: nfft - W = %d must be even (the window is padded centrally)", nfft - W);
+    if (W < 4 || W > nfft || W % 4) return fail(h, "ev_load_voice_quality: W=%d must be a multiple of 4 with 4 <= W <= nfft = %d", W, nfft);
+    if (H < 1 || H > 512) return fail(h, "ev_load_voice_quality: H=%d outside 1 <= H <= 512", H);
+    const int NB = nfft / 2 + 1;
+    for (int i = 0; i < 6; ++i) {
+        const int lo = bands[2 * i], hi = bands[2 * i + 1];
+        if (lo < 0 || hi > NB || lo >= hi) return fail(h, "ev_load_voice_quality: bands[%d] = [%d, %d) must be non-empty inside [0, %d]", i, lo, hi, NB);
+        if (i >= 4 && hi - lo < 2) return fail(h, "ev_load_voice_quality: bands[%d] = [%d, %d) must hold at least 2 bins (a slope)", i, lo, hi);
+    }
+    if (q_fit < 1 || q_fit > q_min || q_min > q_max || q_max > nfft / 2 || q_max - q_fit + 1 < 2)
+        return fail(h, "ev_load_voice_quality: q_fit=%d q_min=%d q_max=%d outside 1 <= q_fit <= q_min <= q_max <= nfft / 2 = %d with at least 2 quefrencies",
+                    q_fit, q_min, q_max, nfft / 2);
+    const int NQ = q_max - q_fit + 1;
+    if (check_finite(h, __func__, "window", window, W) || check_finite(h, __func__, "twiddle", twiddle, 2 * nfft)
+        || check_finite(h, __func__, "slope_w", slope_w, 2 * NB) || check_finite(h, __func__, "fit_w", fit_w, NQ)) return 1;
+    if (!std::isfinite(q_mean)) return fail(h, "ev_load_voice_quality: q_mean=%g is not finite", q_mean);
+    VoiceQW t;
+    t.W = W; t.H = H; t.nfft = nfft; t.NB = NB; t.NBp = (NB + 3) / 4 * 4; t.NQ = NQ; t.skew = ((2 - H) % 4 + 4) % 4;
+    t.S = NB + ((2 - NB) % 32 + 32) % 32;                               // the smallest S >= NB with S = 2 mod 32
+    t.q_fit = q_fit; t.q_min = q_min; t.q_max = q_max; t.q_mean = q_mean;
+    for (int i = 0; i < 12; ++i) t.band[i] = bands[i];
+    const int span = 15 * H + W;
+    t.lds = (size_t)16 * t.S * sizeof(double) + (size_t)(span + t.skew * ((span - 1) / H)) * sizeof(float);
+    if (t.lds > 160 * 1024) return fail(h, "ev_load_voice_quality: nfft=%d H=%d W=%d need %zu bytes of LDS, over 160 KiB", nfft, H, W, t.lds);
+    VoiceQW& cur = h->voiceq;
+    if (cur.loaded) { if (drop_owned(h, {cur.basis})) return 1; cur = VoiceQW(); }
+    double* d_win = nullptr; double* d_tw = nullptr; char* blk = nullptr;
+    HIPCHK(h, hipMalloc((void**)&d_win, (size_t)W * sizeof(double)));
+    if (hipMalloc((void**)&d_tw, (size_t)2 * nfft * sizeof(double)) != hipSuccess) { hipFree(d_win); return fail(h, "ev_load_voice_quality: hipMalloc of the twiddles failed"); }
+    const size_t n_basis = (size_t)W * NB, n_cep = (size_t)t.NBp * NQ;
+    hipError_t e = hipMalloc((void**)&blk, n_basis * sizeof(double2) + (n_cep + 2 * (size_t)NB + NQ) * sizeof(double));
+    if (e == hipSuccess) {
+        t.basis = (double2*)blk;
+        t.cep = (double*)(t.basis + n_basis); t.slope_w = t.cep + n_cep; t.fit_w = t.slope_w + 2 * (size_t)NB;
+        e = hipMemcpy(d_win, window, (size_t)W * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemcpy(d_tw, twiddle, (size_t)2 * nfft * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t.slope_w, slope_w, (size_t)2 * NB * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t.fit_w, fit_w, (size_t)NQ * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        StftBasisParams pb{d_win, d_tw, t.basis, W, nfft, NB};
+        launch<stft_dist_basis_kernel>(h->device, dim3((unsigned)((n_basis + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pb);
+        VoiceQCepParams pc{d_tw, t.cep, nfft, NB, t.NBp, NQ, q_fit};
+        launch<voiceq_cep_basis_kernel>(h->device, dim3((unsigned)((n_cep + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pc);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    hipFree(d_win); hipFree(d_tw);
+    if (e != hipSuccess) { if (blk) hipFree(blk); return fail(h, "ev_load_voice_quality: building the tables failed: %s", hipGetErrorString(e)); }
+    h->owned.push_back(blk);
+    ++h->n_allocs;                          // (one block: both bases, slope_w and fit_w; 9.7 MB at W = nfft = 1024 with 319 quefrencies)
+    t.loaded = true;
+    cur = t;
+    return 0;
+}
+
+int ev_voice_quality(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, double power_floor,
+                     double* d_frame, int32_t* d_peak, double* d_cepstrum, void* stream) {
+    if (enter(h)) return 1;
+    const VoiceQW& w = h->voiceq;
+    if (!w.loaded) return fail(h, "ev_voice_quality: tables not loaded (ev_load_voice_quality)");
+    if (check_batch(h, __func__, B)) return 1;
+    if (L < 1) return fail(h, "ev_voice_quality: L=%d must be at least 1", L);
+    if (!d_x) return fail(h, "ev_voice_quality: d_x must be non-null");
+    if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_voice_quality: power_floor=%g must be finite and greater than 0", power_floor);
+    if (!d_frame || !d_peak) return fail(h, "ev_voice_quality: d_frame and d_peak must be non-null");
+    if (L / w.H > 0x7fffffef) return fail(h, "ev_voice_quality: L=%d at H=%d has more frames than an int32 tile index holds", L, w.H);
+    h->stream = (hipStream_t)stream;
+    const int NF = frames_of(L, w.H);
+    VoiceQTables t{w.basis, w.cep, w.slope_w, w.fit_w, w.W, w.H, w.nfft, w.NB, w.NBp, w.NQ, w.skew, w.S, w.q_fit, w.q_min, w.q_max, {}, w.q_mean};
+    for (int i = 0; i < 12; ++i) t.band[i] = w.band[i];
+    VoiceQParams pv{d_x, d_len, d_frame, d_peak, d_cepstrum, t, L, NF, power_floor};
+    launch<voice_quality_kernel>(h->device, dim3((unsigned)((NF + 15) / 16), (unsigned)B), dim3(256), w.lds, h->stream, pv);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -1,5 +1,5 @@
-// Analysis kernels: dataset statistics, resampling, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness, STOI / ESTOI and the
-// STFT distance.  None of them shares code with the synthesis engine: ev_kernels.h includes this file at its end, after every helper the
+// Analysis kernels: dataset statistics, resampling, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness, STOI / ESTOI, the
+// STFT distance and voice quality.  None of them shares code with the synthesis engine: ev_kernels.h includes this file at its end, after every helper the
 // kernels below use (the f32x4 vector type and cfm_valid_len, nothing else).  Their host entry points are in ev_analysis.h.
 #pragma once
 
@@ -1529,4 +1529,268 @@ __global__ __launch_bounds__(256) void stft_dist_rows_kernel(const StftRowsParam
     __syncthreads();
     if (tid < 4) p.sums[4 * (size_t)b + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
     if (tid == 0) p.counts[b] = nf;
+}
+
+// ---------------------------------------------------------------------------
+// Voice quality (ev_voice_quality): the spectral-balance descriptors of eGeMAPS (alpha ratio, Hammarberg index, the spectral slopes of two bands;
+// Eyben et al. 2016) and the cepstral peak prominence (Hillenbrand et al. 1994) of every frame of a row, from ONE float64 log-power spectrum
+// and its linear real cepstrum.  All float64, contraction OFF (STOI_EXACT), no atomics.  Two GEMMs on v_mfma_f64_16x16x4_f64, chained
+// through LDS inside one launch:
+//   GEMM 1  frames x samples times ev_stft_dist's windowed basis {w[j] cos, w[j] sin}(2 pi (j + off) k / nfft) (stft_dist_basis_kernel builds it):
+//           raw = fma(sm, sm, re * re), p = max(raw, floor), Ldb = (10 / ln 10) log(p);
+//   GEMM 2  Ldb (16 frames x NBp bins, from LDS) times cep[k][q - q_fit] = g[k] cos_tab[(k q) mod nfft] / nfft (g = 1 at k = 0 and k = nfft / 2,
+//           else 2; rows NB <= k < NBp = the next multiple of 4 are zeros), which voiceq_cep_basis_kernel builds once per load: one rounding
+//           of the quotient per entry (g cos is exact), the phase index in exact integers.
+// Everything a row's outputs depend on hangs on the row's own samples below len.
+struct VoiceQTables {
+    const double2* basis; const double* cep; const double* slope_w; const double* fit_w;
+    int W, H, nfft, NB, NBp, NQ, skew, S, q_fit, q_min, q_max;
+    int band[12];                                                       // {first, end} of alpha lo, alpha hi, Hammarberg lo, Hammarberg hi, slope 0, slope 1
+    double q_mean;
+};
+constexpr double VOICEQ_DB = 4.342944819032518;                         // 10 / ln 10
+
+// (n, nf) of row b: a row with len < 1 or len > L is an empty row; nf = ceil(n / H), pitch_yin's frames
+__device__ __forceinline__ int voiceq_frames(const int32_t* len, int b, int L, int H, int* n_out) {
+    int n = len ? len[b] : L;
+    if (n < 1 || n > L) n = 0;
+    *n_out = n;
+    return (int)(((long long)n + H - 1) / H);
+}
+
+struct VoiceQCepParams { const double* tw; double* cep; int nfft, NB, NBp, NQ, q_fit; };
+
+__global__ __launch_bounds__(256) void voiceq_cep_basis_kernel(const VoiceQCepParams p) {
+    STOI_EXACT
+    const int i = blockIdx.x * 256 + threadIdx.x;                       // (NBp NQ <= 516 x 512)
+    if (i >= p.NBp * p.NQ) return;
+    const int k = i / p.NQ, q = p.q_fit + (i - k * p.NQ);
+    const int ph = (k * q) % p.nfft;                                    // (< 516 x 512: exact)
+    const double g = (k == 0 || k == p.nfft / 2) ? 1.0 : 2.0;
+    p.cep[i] = k < p.NB ? g * p.tw[2 * ph] / (double)p.nfft : 0.0;
+}
+
+// One workgroup of 4 waves per (row b, tile of 16 frames f0 .. f0 + 15).  Dynamic LDS: Ld, the tile's log-spectrum (16 frames x S doubles),
+// then the tile's raw span, samples f0 H + H / 2 - W / 2 + t for 0 <= t < 15 H + W, staged once as fp32 with ZEROS outside [0, len) (no
+// reflection) under the skew scheme of stft_dist_frames_kernel (sample t at word t + skew (t / H), skew = (2 - H) mod 4).
+// PHASE 1 is that kernel's loop for one signal: wave w owns the bin tiles w, w + 4, ...; per tile W / 4 steps of two MFMAs (cos, sin), the
+// basis of the next four steps requested before this round's products.  Accumulator register i of lane l is frame (l >> 4) + 4 i, bin
+// 16 tile + (l & 15).  Epilogue per (frame, bin): raw, p, Ldb as above; Ldb goes to Ld[frame S + bin]; per frame the lane accumulates over its
+// tiles in ascending order: the two alpha sums and the power (s = s + p), the two slope sums (s = fma(slope_w[b][k], Ldb, s) over every bin:
+// the weights outside a band are zeros), the two Hammarberg maxima, the count of bins with raw > floor.  The 16 bin lanes are then reduced by
+// one xor tree (offsets 8, 4, 2, 1) and the waves as ((w0 + w1) + w2) + w3.
+// PHASE 2, after one barrier: wave w owns the quefrency tiles w, w + 4, ... of 16 columns from q_fit; per tile NBp / 4 steps of one MFMA.  Lane
+// l of an A fragment reads Ld[(l & 15) S + k0 + (l >> 4)] with ds_read_b64 (k >= NB: the address is clamped to NB - 1, the basis row is zero);
+// the B fragment is cep[k0 + (l >> 4)][16 tile + (l & 15)] from global memory (L2-resident; the column clamped at NQ - 1, the term dropped).
+// BANKS: ds_read_b64 is banked over 64 dwords and served in two groups of 32 lanes; lane l of a group reads dwords 2 ((l & 15) S + k0 + q)
+// and the next one, q = l >> 4 in {0, 1} or {2, 3}.  With S = 2 mod 32, 2 r S = 4 r mod 64: the group's 32 lanes start at the dword banks
+// 4 r + 2 q + const, all 32 even residues mod 64, each read covering its even bank and the odd one after it: all 64 banks once, conflict-free.
+// S is the smallest such number >= NB (NB = 513: S = 514).  The epilogue's stores of Ldb (once per bin tile) are not conflict-free and need not be.
+// Epilogue per (frame, quefrency): sum C (s = s + C) and sum fit_w C (s = fma(fit_w, C, s)) over the lane's tiles in ascending order, the
+// maximum over q_min <= q <= q_max with its index (strictly greater replaces: the lowest q of a tie), optionally the store of C; the 16 lanes
+// by the xor tree (8, 4, 2, 1; of equal maxima the lower index), the waves as ((w0 + w1) + w2) + w3 and in the order w0 .. w3 for the maximum.
+// Thread f < 16 then forms the frame's eight figures: mean = sum C / NQ, base = mean + (sum fit_w C) (q* - q_mean), cpp = C[q*] - base,
+// alpha = (10 / ln 10) (log(hi) - log(lo)).  A SILENT frame (no bin with raw > floor) keeps its power; its other figures, d_peak and
+// cepstrum are zeros by definition.  Frames >= nf are zeros.
+struct VoiceQParams { const float* x; const int32_t* len; double* frame; int32_t* peak; double* cepstrum; VoiceQTables t; int L, NF; double floor; };
+
+__global__ __launch_bounds__(256) void voice_quality_kernel(const VoiceQParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double voiceq_smem[];
+    __shared__ double red[4][16][7];
+    __shared__ int red_live[4][16];
+    __shared__ double red2[4][16][3];
+    __shared__ int red2_i[4][16];
+    const int b = blockIdx.y, f0 = blockIdx.x * 16, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int W = p.t.W, H = p.t.H, NB = p.t.NB, NQ = p.t.NQ, skew = p.t.skew, S = p.t.S;
+    int n;
+    const int nf = voiceq_frames(p.len, b, p.L, H, &n);
+    double* out = p.frame + ((size_t)b * p.NF + f0) * 8;
+    int32_t* pk = p.peak + (size_t)b * p.NF + f0;
+    double* cp = p.cepstrum ? p.cepstrum + ((size_t)b * p.NF + f0) * NQ : nullptr;
+    const int nfr = p.NF - f0 < 16 ? p.NF - f0 : 16;                    // the tile's frames inside the outputs (>= 1)
+    if (f0 >= nf) {                                                     // (uniform) zeros past the row's own frames
+        if (tid < 8 * nfr) out[tid] = 0.0;
+        if (tid < nfr) pk[tid] = 0;
+        if (cp) for (int i = tid; i < nfr * NQ; i += 256) cp[i] = 0.0;
+        return;
+    }
+    double* Ld = voiceq_smem;                                           // (16, S)
+    float* sx = (float*)(Ld + 16 * S);
+    const int span = 15 * H + W;
+    {
+        const float* xr = p.x + (size_t)b * p.L;
+        const long long i0 = (long long)f0 * H + H / 2 - W / 2;
+        for (int t = tid; t < span; t += 256) {
+            const long long i = i0 + t;
+            sx[t + skew * (t / H)] = i >= 0 && i < n ? xr[i] : 0.f;
+        }
+    }
+    __syncthreads();
+    const int r = lane & 15, q = lane >> 4;
+    {
+        const int rbase = r * (H + skew);                               // word of sample r H + j: r (H + skew) + j + skew (j / H)
+        const int ntile = (NB + 15) >> 4;
+        const int step_mod = 4 % H, step_pad = skew * (4 / H), nsteps = W >> 2;
+        const double ninf = -__builtin_huge_val();
+        double al[4] = {0.0, 0.0, 0.0, 0.0}, ah[4] = {0.0, 0.0, 0.0, 0.0}, s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
+        double pw[4] = {0.0, 0.0, 0.0, 0.0}, hl[4] = {ninf, ninf, ninf, ninf}, hh[4] = {ninf, ninf, ninf, ninf};
+        int live[4] = {0, 0, 0, 0};
+        for (int bt = wv; bt < ntile; bt += 4) {
+            const int col = bt * 16 + r, colc = col < NB ? col : NB - 1;
+            const double2* bp = p.t.basis + (size_t)q * NB + colc;
+            const double w0 = p.t.slope_w[colc], w1 = p.t.slope_w[NB + colc];
+            stftd_acc xc = {0.0, 0.0, 0.0, 0.0}, xs = xc;
+            int j = q, jm = q % H, pad = skew * (q / H);
+            double2 cur[4], nxt[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cur[u] = bp[(size_t)(u < nsteps ? u : nsteps - 1) * 4 * NB];
+            for (int t0 = 0; t0 < nsteps; t0 += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) nxt[u] = bp[(size_t)(t0 + 4 + u < nsteps ? t0 + 4 + u : nsteps - 1) * 4 * NB];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (t0 + u < nsteps) {                              // (uniform)
+                        const double ax = (double)sx[rbase + j + pad];
+                        xc = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].x, xc, 0, 0, 0);
+                        xs = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].y, xs, 0, 0, 0);
+                        j += 4; jm += step_mod; pad += step_pad;        // (j + 4) / H = j / H + 4 / H + (j % H + 4 % H >= H)
+                        if (jm >= H) { jm -= H; pad += skew; }
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+            }
+            if (col < NB) {
+                const bool in_al = col >= p.t.band[0] && col < p.t.band[1], in_ah = col >= p.t.band[2] && col < p.t.band[3];
+                const bool in_hl = col >= p.t.band[4] && col < p.t.band[5], in_hh = col >= p.t.band[6] && col < p.t.band[7];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double raw = fma(xs[i], xs[i], xc[i] * xc[i]);
+                    const double pp = fmax(raw, p.floor);
+                    const double ld = VOICEQ_DB * log(pp);
+                    Ld[(q + 4 * i) * S + col] = ld;
+                    if (in_al) al[i] = al[i] + pp;
+                    if (in_ah) ah[i] = ah[i] + pp;
+                    if (in_hl) hl[i] = fmax(hl[i], ld);
+                    if (in_hh) hh[i] = fmax(hh[i], ld);
+                    s0[i] = fma(w0, ld, s0[i]);
+                    s1[i] = fma(w1, ld, s1[i]);
+                    pw[i] = pw[i] + pp;
+                    live[i] += raw > p.floor ? 1 : 0;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) {
+                al[i] = al[i] + __shfl_xor(al[i], o, 64); ah[i] = ah[i] + __shfl_xor(ah[i], o, 64);
+                s0[i] = s0[i] + __shfl_xor(s0[i], o, 64); s1[i] = s1[i] + __shfl_xor(s1[i], o, 64);
+                pw[i] = pw[i] + __shfl_xor(pw[i], o, 64);
+                hl[i] = fmax(hl[i], __shfl_xor(hl[i], o, 64)); hh[i] = fmax(hh[i], __shfl_xor(hh[i], o, 64));
+                live[i] += __shfl_xor(live[i], o, 64);
+            }
+            if (r == 0) {
+                double* d = red[wv][q + 4 * i];
+                d[0] = al[i]; d[1] = ah[i]; d[2] = hl[i]; d[3] = hh[i]; d[4] = s0[i]; d[5] = s1[i]; d[6] = pw[i];
+                red_live[wv][q + 4 * i] = live[i];
+            }
+        }
+    }
+    __syncthreads();                                                    // Ld and the band terms are complete
+    {
+        const int nqt = (NQ + 15) >> 4, nsteps = p.t.NBp >> 2;
+        const double ninf = -__builtin_huge_val();
+        bool keep[4];                                                   // the frame is one of the row's and is not silent
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int fr = q + 4 * i;
+            keep[i] = f0 + fr < nf && red_live[0][fr] + red_live[1][fr] + red_live[2][fr] + red_live[3][fr] > 0;
+        }
+        double sc[4] = {0.0, 0.0, 0.0, 0.0}, sf[4] = {0.0, 0.0, 0.0, 0.0}, bv[4] = {ninf, ninf, ninf, ninf};
+        int bi[4] = {0, 0, 0, 0};
+        const double* La = Ld + r * S;
+        for (int qt = wv; qt < nqt; qt += 4) {
+            const int col = qt * 16 + r;
+            const double* bp = p.t.cep + (size_t)q * NQ + (col < NQ ? col : NQ - 1);
+            stftd_acc c = {0.0, 0.0, 0.0, 0.0};
+            double cur[4], nxt[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cur[u] = bp[(size_t)(u < nsteps ? u : nsteps - 1) * 4 * NQ];
+            for (int t0 = 0; t0 < nsteps; t0 += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) nxt[u] = bp[(size_t)(t0 + 4 + u < nsteps ? t0 + 4 + u : nsteps - 1) * 4 * NQ];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (t0 + u < nsteps) {                              // (uniform)
+                        const int k = 4 * (t0 + u) + q;
+                        c = __builtin_amdgcn_mfma_f64_16x16x4f64(La[k < NB ? k : NB - 1], cur[u], c, 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+            }
+            if (col < NQ) {
+                const double fw = p.t.fit_w[col];
+                const bool srch = p.t.q_fit + col >= p.t.q_min;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    sc[i] = sc[i] + c[i];
+                    sf[i] = fma(fw, c[i], sf[i]);
+                    if (srch && c[i] > bv[i]) { bv[i] = c[i]; bi[i] = col; }
+                    if (cp && q + 4 * i < nfr) cp[(size_t)(q + 4 * i) * NQ + col] = keep[i] ? c[i] : 0.0;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) {
+                sc[i] = sc[i] + __shfl_xor(sc[i], o, 64); sf[i] = sf[i] + __shfl_xor(sf[i], o, 64);
+                const double ov = __shfl_xor(bv[i], o, 64);
+                const int oi = __shfl_xor(bi[i], o, 64);
+                if (ov > bv[i] || (ov == bv[i] && oi < bi[i])) { bv[i] = ov; bi[i] = oi; }
+            }
+            if (r == 0) {
+                double* d = red2[wv][q + 4 * i];
+                d[0] = sc[i]; d[1] = sf[i]; d[2] = bv[i];
+                red2_i[wv][q + 4 * i] = bi[i];
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < nfr) {
+        const int fr = tid;
+        double cpp = 0.0, alpha = 0.0, ham = 0.0, sl0 = 0.0, sl1 = 0.0, power = 0.0, cq = 0.0, base = 0.0;
+        int qs = 0;
+        if (f0 + fr < nf) {
+            power = ((red[0][fr][6] + red[1][fr][6]) + red[2][fr][6]) + red[3][fr][6];
+            if (red_live[0][fr] + red_live[1][fr] + red_live[2][fr] + red_live[3][fr] > 0) {
+                const double lo = ((red[0][fr][0] + red[1][fr][0]) + red[2][fr][0]) + red[3][fr][0];
+                const double hi = ((red[0][fr][1] + red[1][fr][1]) + red[2][fr][1]) + red[3][fr][1];
+                alpha = VOICEQ_DB * (log(hi) - log(lo));
+                ham = fmax(fmax(red[0][fr][2], red[1][fr][2]), fmax(red[2][fr][2], red[3][fr][2]))
+                    - fmax(fmax(red[0][fr][3], red[1][fr][3]), fmax(red[2][fr][3], red[3][fr][3]));
+                sl0 = ((red[0][fr][4] + red[1][fr][4]) + red[2][fr][4]) + red[3][fr][4];
+                sl1 = ((red[0][fr][5] + red[1][fr][5]) + red[2][fr][5]) + red[3][fr][5];
+                const double sumc = ((red2[0][fr][0] + red2[1][fr][0]) + red2[2][fr][0]) + red2[3][fr][0];
+                const double sumf = ((red2[0][fr][1] + red2[1][fr][1]) + red2[2][fr][1]) + red2[3][fr][1];
+                cq = red2[0][fr][2];
+                int bi = red2_i[0][fr];
+#pragma unroll
+                for (int w = 1; w < 4; ++w) {
+                    const double v = red2[w][fr][2];
+                    const int vi = red2_i[w][fr];
+                    if (v > cq || (v == cq && vi < bi)) { cq = v; bi = vi; }
+                }
+                qs = p.t.q_fit + bi;
+                base = sumc / (double)NQ + sumf * ((double)qs - p.t.q_mean);
+                cpp = cq - base;
+            }
+        }
+        double* o = out + 8 * fr;
+        o[0] = cpp; o[1] = alpha; o[2] = ham; o[3] = sl0; o[4] = sl1; o[5] = power; o[6] = cq; o[7] = base;
+        pk[fr] = qs;
+    }
 }

@@ -126,6 +126,12 @@ struct ResamplerW { bool loaded = false; int up = 0, down = 0, n_taps = 0, W = 0
 struct StoiW { bool loaded = false; int W = 0, H = 0, nfft = 0, n_bands = 0, N = 0, bin_lo = 0, bin_hi = 0; double* win = nullptr; double* tw = nullptr; int32_t* bands = nullptr; };
 // Basis of ev_stft_dist: (W, NB) pairs {w[j] cos, w[j] sin}(2 pi (j + off) k / nfft), float64 on the device; skew: the LDS pad per hop (ev_kernels.h)
 struct StftDistW { bool loaded = false; int W = 0, H = 0, nfft = 0, NB = 0, skew = 0; double2* basis = nullptr; };
+// Tables of ev_voice_quality, one device block: ev_stft_dist's basis (W, NB), the cepstral basis (NBp, NQ) g[k] cos(2 pi k q / nfft) / nfft, slope_w
+// (2, NB) and fit_w (NQ); S: the row stride of the log-spectrum in LDS, lds: the launch's dynamic LDS in bytes (ev_analysis_kernels.h)
+struct VoiceQW {
+    bool loaded = false; int W = 0, H = 0, nfft = 0, NB = 0, NBp = 0, NQ = 0, skew = 0, S = 0, q_fit = 0, q_min = 0, q_max = 0; int band[12] = {0};
+    double q_mean = 0.0; size_t lds = 0; double2* basis = nullptr; double* cep = nullptr; double* slope_w = nullptr; double* fit_w = nullptr;
+};
 
 }  // namespace
 
@@ -142,6 +148,7 @@ struct ev_handle {
     ResamplerW rs;
     StoiW stoi;
     StftDistW stftd;
+    VoiceQW voiceq;
     // small per-stage scratch arenas (denoiser, text encoder): grown on demand, ordered against their last user's stream
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
     Scratch dn_ws, enc_ws, mas_ws;   // (mas_ws: the alignment search's frame -> token index and, for large Tx * Ty, its decision bits)
@@ -2759,7 +2766,7 @@ int ev_mel_spectrogram(ev_handle* h, const float* d_audio, int B, int L, float o
     return run_mel(h, d_audio, B, L, out_scale, out_shift, d_mel);
 }
 
-// The analysis side's 14 entry points, from ev_load_resampler to ev_stft_dist, with the checks they share (its own namespace { } and
+// The analysis side's 16 entry points, from ev_load_resampler to ev_voice_quality, with the checks they share (its own namespace { } and
 // extern "C" { } nest in this block).  Here and not at the end of the file: the kernel templates are instantiated in the order the host code
 // names them, and this place keeps the code object's order that of the single file
 #include "ev_analysis.h"

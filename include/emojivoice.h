@@ -41,6 +41,8 @@
  *   ev_stoi            <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_load_stft_dist  <- no counterpart; Yamamoto et al. 2020 (multi-resolution STFT loss) is the model
  *   ev_stft_dist       <- no counterpart; Yamamoto et al. 2020 (multi-resolution STFT loss) is the model
+ *   ev_load_voice_quality <- no counterpart; Eyben et al. 2016 (eGeMAPS) and Hillenbrand et al. 1994 (CPP) are the model
+ *   ev_voice_quality   <- no counterpart; Eyben et al. 2016 (eGeMAPS) and Hillenbrand et al. 1994 (CPP) are the model
  *   ev_pyin_observe    <- no counterpart; librosa.pyin is the model
  *   ev_pyin_decode     <- no counterpart; librosa.pyin is the model
  *
@@ -80,7 +82,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -607,6 +609,63 @@ int ev_load_stft_dist(ev_handle *h, const double *window /* HOST (W) */, const d
 int ev_stft_dist(ev_handle *h, const float *d_x /* (B, L) reference */, const float *d_y /* (B, L) processed */, const int32_t *d_len /* (B) or NULL */,
                  int B, int L, double power_floor /* 1e-7 */,
                  double *d_frame /* (B, NF, 4) or NULL */, double *d_sums /* (B, 4) */, int32_t *d_counts /* (B) */, void *stream);
+
+/* Voice quality per frame on the device: the spectral-balance descriptors of the eGeMAPS set (alpha ratio, Hammarberg index, the spectral slopes
+ * of two bands; Eyben et al., IEEE Trans. Affective Computing 2016) and the cepstral peak prominence (CPP; Hillenbrand, Cleveland and Erickson,
+ * JSHR 1994), all from one float64 log-power spectrum of the frame and its cepstrum.  ev_load_voice_quality stores one geometry;
+ * ev_voice_quality measures.  Everything is float64 (the fp32 samples are widened), the kernels are compiled with floating-point contraction off;
+ * no atomics; ev_set_arithmetic does not reach it.
+ * COMPARABILITY: the cepstrum here is the linear real cepstrum of the dB spectrum.  Hillenbrand's and Praat's CPP put the cepstral magnitude
+ *   itself in dB as well, and VoiceSauce analyses pitch-synchronous windows: these figures are comparable across runs of THIS library (recorded
+ *   against synthesised, per voice), not to the digit with those tools.
+ * ev_load_voice_quality: HOST tables.  window (W) doubles w; twiddle (nfft, 2) doubles {cos, sin}(2 pi n / nfft) (ev_load_stft_dist's); H the
+ *   hop; bands (6, 2) int32 {first bin, end bin (exclusive)} of: alpha low, alpha high, Hammarberg low, Hammarberg high, slope 0, slope 1;
+ *   slope_w (2, NB) and fit_w (NQ) doubles, q_mean (below); quefrencies q_fit, q_min, q_max in samples.  NB = nfft / 2 + 1, off = (nfft - W) / 2,
+ *   NQ = q_max - q_fit + 1.  Limits, each violation failing with a message that names it: nfft even with 16 <= nfft <= 1024; W a multiple of 4
+ *   with 4 <= W <= nfft; nfft - W even; 1 <= H <= 512; every band non-empty inside [0, NB], both slope bands of at least 2 bins;
+ *   1 <= q_fit <= q_min <= q_max <= nfft / 2 with NQ >= 2; finite, non-NULL tables, q_mean finite; at most 160 KiB of LDS per workgroup (cannot
+ *   be exceeded inside the other limits).  The handle builds on the device, each entry rounded once and every phase index in exact integers,
+ *   ev_stft_dist's basis c[j][k], s[j][k] = w[j] {cos_tab, sin_tab}[((j + off) k) mod nfft] and the cepstral basis
+ *     cep[k][q] = g[k] cos_tab[(k q) mod nfft] / nfft,  g = 1 for k = 0 and k = nfft / 2, else 2,  0 <= k < NB,  q_fit <= q <= q_max.
+ *   All tables live in one device block that counts once in ev_alloc_count.  Loading again replaces the tables; it waits for the device
+ *   first.  ev_voice_quality without loaded tables fails with a message.
+ *   The host tables are least-squares lines in their centred form: fit_w[i] = (q_i - q_mean) / sum (q - q_mean)^2 over q_fit .. q_max with q_mean
+ *   their mean; slope_w[b][k] = (x_k - xbar) / sum (x - xbar)^2 over band b with x_k = k sr / nfft / 1000 (dB per kHz), 0 outside the band.
+ * Sizes: NF = ceil(L / H); a row of len samples has nf = ceil(len / H) frames, ev_pitch_yin's.  d_len == NULL: every row is L long.
+ * Definition, per row:
+ *   framing   frame f reads s_j = x[f H + H / 2 - W / 2 + j] for 0 <= j < W, ZERO where the index is outside [0, len): no reflection (the one
+ *             staging difference from ev_stft_dist).  At an equal hop the frames line up with ev_pitch_yin's and the mel's
+ *   spectrum  re_k = sum_j s_j c[j][k], sm_k = sum_j s_j s[j][k] for 0 <= k < NB; raw_k = fma(sm_k, sm_k, re_k * re_k);
+ *             p_k = max(raw_k, power_floor); Ldb_k = (10 / ln 10) log(p_k), the device library's float64 natural logarithm
+ *   cepstrum  C_q = sum_k Ldb_k cep[k][q] for q_fit <= q <= q_max
+ *   peak      q* = argmax C_q over q_min <= q <= q_max, the lowest q of a tie
+ *   baseline  base = (sum_q C_q) / NQ + (sum_q fit_w[q - q_fit] C_q) (q* - q_mean): the least-squares line through C over q_fit .. q_max, at q*
+ *   d_frame   (B, NF, 8): {cpp = C[q*] - base,
+ *                          alpha = (10 / ln 10) (log sum_{alpha high} p - log sum_{alpha low} p),
+ *                          hammarberg = max_{Hammarberg low} Ldb - max_{Hammarberg high} Ldb,
+ *                          slope0 = sum_k slope_w[0][k] Ldb_k, slope1 = sum_k slope_w[1][k] Ldb_k (over all NB bins),
+ *                          power = sum_k p_k, C[q*], base}
+ *   d_peak    (B, NF) int32: q*
+ *   d_cepstrum (B, NF, NQ) or NULL: C_q
+ *   A SILENT frame, one without a bin of raw_k > power_floor, keeps its power; its other seven entries, its d_peak and its cepstrum are
+ *   zeros by definition (with every bin clamped C is summation noise and its argmax arbitrary).  Frames at or past nf are zeros.
+ * Orders (fixed; the sums over j and over k of the two matrix products run on v_mfma_f64_16x16x4_f64 in steps of four from 0, the order
+ *   inside the instruction is the hardware's): sums over the bins k = 16 (w + 4 i) + c, and over the quefrencies q = q_fit + 16 (w + 4 i) + c,
+ *   are added per (w, c) in ascending i (weighted terms as fma(weight, value, sum)), then over c by an xor tree (offsets 8, 4, 2, 1), then
+ *   over w as ((w0 + w1) + w2) + w3; maxima are exact in any order.
+ * A row with len < 1 or len > L is no error and no out-of-bounds access: all its outputs are zeros.  Nothing at or behind len is read, and
+ * nothing depends on the batch or on L: a row alone, inside a batch, or as the d_len prefix of a longer padded row with anything behind it,
+ * a second call, and a call with d_cepstrum NULL give the same bits in every output.
+ * Limits of ev_voice_quality, each violation failing with a message that names it and writing nothing: 1 <= B <= 65535; L >= 1 (and L / H below
+ * 2^31 - 16); power_floor > 0 and finite; d_x, d_frame and d_peak non-NULL.
+ * Kernel (one launch on `stream`; no host wait, no copy, no arena: a call never allocates): one workgroup of four waves per (row, 16 frames);
+ *   the tile's span of 15 H + W samples staged once in LDS, the first matrix product, the log-spectrum of the 16 frames kept in LDS (16 rows of
+ *   S doubles, S = 2 mod 32), the second matrix product against the cepstral basis, the reductions.  The call is capturable. */
+int ev_load_voice_quality(ev_handle *h, const double *window /* HOST (W) */, const double *twiddle /* HOST (nfft, 2): cos, sin of 2 pi n / nfft */,
+                          int W, int H, int nfft, const int32_t *bands /* HOST (6, 2) */, const double *slope_w /* HOST (2, NB) */,
+                          int q_fit, int q_min, int q_max, const double *fit_w /* HOST (NQ) */, double q_mean);
+int ev_voice_quality(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L, double power_floor /* 1e-7 */,
+                     double *d_frame /* (B, NF, 8) */, int32_t *d_peak /* (B, NF) */, double *d_cepstrum /* (B, NF, NQ) or NULL */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

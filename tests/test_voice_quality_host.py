@@ -1,0 +1,271 @@
+"""CPU-side checks of the voice-quality path: the numpy restatement (tests/voice_quality_ref.py) against independent routes (an inverse real
+FFT of the even-extended dB spectrum, ``np.fft.rfft`` of the padded frame, ``np.polyfit``), known signals, ``audio.voice_quality_tables`` and
+``audio.voice_quality_statistics``, the conditions on the inputs of the device tests, the mutants the device tests must tell apart, the
+silent-frame rule, and the C ABI's declaration and export.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import voice_quality_ref as R
+from emojivoice_amd import _lib, audio
+
+try:
+    from scipy.fft import irfft
+except ImportError:                                  # (numpy's is the same pocketfft routine)
+    from numpy.fft import irfft
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIG = R.GEOMETRIES[3]
+_ROWS = {}
+
+
+def rows(g):
+    """(x, lens, float64 results, longdouble results) of rows_for(g): computed once, never modified."""
+    if g not in _ROWS:
+        x, lens = R.rows_for(g)
+        r = (x, lens, R.batch(x, lens, g), R.batch(x, lens, g, dtype=np.longdouble))
+        for part in (r[2], r[3]):
+            for v in part:
+                v.setflags(write=False)
+        _ROWS[g] = r
+    return _ROWS[g]
+
+
+# ---- the restatement against independent routes ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("g", R.GEOMETRIES, ids=R.IDS)
+def test_restatement_against_fft_and_polyfit(g):
+    x, lens = rows(g)[:2]
+    n = lens[0]
+    sig = x[0, :n].astype(np.float64)
+    raw = R.spectrum(sig, g)
+    nf, NB, off = R.frames(n, g.H), g.nfft // 2 + 1, (g.nfft - g.W) // 2
+    assert raw.shape == (nf, NB)
+    fm = R.frame_matrix(sig, g)
+    padded = np.zeros((nf, g.nfft))
+    padded[:, off:off + g.W] = fm * R.hann(g.W)
+    want = np.abs(np.fft.rfft(padded, axis=1)) ** 2
+    e_spec = float(np.max(np.abs(raw - want) / want.max(axis=1, keepdims=True)))
+    fr, pk, C, _ = R.row(sig, g, guard=False)
+    L = (10.0 / np.log(10.0)) * np.log(np.maximum(raw, R.POWER_FLOOR))
+    ceps = irfft(L, n=g.nfft, axis=1)[:, g.q_fit:g.q_max + 1]          # the real cepstrum of the even-extended dB spectrum
+    e_cep = float(np.max(np.abs(C - ceps)))
+    q = np.arange(g.q_fit, g.q_max + 1, dtype=np.float64)
+    e_fit = e_slope = 0.0
+    for f in range(0, nf, 7):
+        a, b = np.polyfit(q, C[f], 1)
+        e_fit = max(e_fit, abs(fr[f, 7] - (a * pk[f] + b)))
+        for s in range(2):
+            lo, hi = g.bands[4 + s]
+            xk = np.arange(lo, hi) * g.sr / g.nfft / 1000.0
+            e_slope = max(e_slope, abs(fr[f, 3 + s] - np.polyfit(xk, L[f, lo:hi], 1)[0]) / max(abs(fr[f, 3 + s]), 1.0))
+    print(f"\nvoice quality restatement {g[:6]}: spectrum against rfft {e_spec:.3e} of the frame's largest, cepstrum against irfft {e_cep:.3e}, "
+          f"baseline against polyfit {e_fit:.3e}, slopes against polyfit {e_slope:.3e}")
+    assert e_spec <= 1e-12 and e_cep <= 1e-10 and e_fit <= 1e-9 and e_slope <= 1e-9
+
+
+# ---- known signals ----------------------------------------------------------------------------------------------------------------------------
+def test_a_harmonic_tone_peaks_at_its_period_and_stands_above_noise():
+    n = 8192
+    tone = R.harmonic_tone(n)                                              # 147 Hz: the period is 22050 / 147 = 150 samples exactly
+    noise = R.white_noise(n, float(np.sqrt(np.mean(tone.astype(np.float64) ** 2))))
+    ft, pt, _, _ = R.row(tone, BIG)
+    fn, _, _, _ = R.row(noise, BIG)
+    whole = slice(2, R.frames(n, BIG.H) - 2)                               # frames that lie inside the row
+    print(f"\nvoice quality: CPP of a 29-harmonic 147 Hz tone {ft[whole, 0].mean():.3f}, of white noise at the same level {fn[whole, 0].mean():.3f}")
+    assert (pt[whole] == 150).all()
+    assert ft[whole, 0].min() > 3.0 * fn[whole, 0].mean()
+
+
+def test_a_low_pass_lowers_the_alpha_ratio_and_both_slopes():
+    n = 8192
+    x = R.white_noise(n, 0.05, seed=3).astype(np.float64)
+    y = np.zeros(n)
+    a = 0.9
+    for i in range(n):
+        y[i] = (1 - a) * x[i] + a * (y[i - 1] if i else 0.0)
+    whole = slice(2, R.frames(n, BIG.H) - 2)
+    fx, fy = R.row(x, BIG)[0][whole], R.row(y, BIG)[0][whole]
+    for i in (1, 3, 4):
+        assert fy[:, i].mean() < fx[:, i].mean() - 1.0, R.FIGURES[i]
+
+
+# ---- tables ---------------------------------------------------------------------------------------------------------------------------------------
+def test_voice_quality_tables():
+    t = audio.voice_quality_tables(22050, 1024, 65.0, 600.0)
+    assert t["bands"].dtype == np.int32 and t["bands"].tolist() == [[3, 47], [47, 233], [0, 93], [93, 233], [0, 24], [24, 70]]
+    assert tuple(map(tuple, t["bands"].tolist())) == R.band_edges(22050, 1024) == BIG.bands
+    assert (t["q_fit"], t["q_min"], t["q_max"]) == (22, 37, 339)
+    assert audio.voice_quality_tables(22050, 512)["q_max"] == 256
+    fw, qm = R.fit_weights(22, 339)
+    assert np.array_equal(t["fit_w"], fw) and t["q_mean"] == qm == 180.5
+    assert np.array_equal(t["slope_w"], R.slope_weights(BIG.bands, 1024, 22050))
+    assert abs(t["fit_w"].sum()) < 1e-15 and abs(t["slope_w"].sum(axis=1)).max() < 1e-12
+    q = np.arange(22, 340, dtype=np.float64)
+    assert abs(t["fit_w"] @ (3.0 * q - 7.0) - 3.0) < 1e-12, "the weights return the slope of a line"
+    for bad in (dict(sr=0, n_fft=1024), dict(sr=22050, n_fft=1023), dict(sr=22050, n_fft=8), dict(sr=8000, n_fft=1024),
+                dict(sr=22050, n_fft=64), dict(sr=22050, n_fft=1024, fmin=0.0), dict(sr=22050, n_fft=1024, fmin=700.0, fmax=600.0),
+                dict(sr=22050, n_fft=1024, fmax=2000.0)):
+        with pytest.raises(ValueError, match="voice_quality_tables"):
+            audio.voice_quality_tables(**bad)
+
+
+def test_voice_quality_statistics_against_numpy():
+    g = np.random.default_rng(5)
+    B, F = 3, 40
+    vq = {k: torch.from_numpy(g.standard_normal((B, F))) for k in audio.VOICE_QUALITY_FIGURES}
+    peak = g.integers(36, 340, (B, F)).astype(np.int32)
+    peak[:, ::5] = 0                                                       # silent frames
+    vq["peak_quefrency"] = torch.from_numpy(peak)
+    voiced = g.random((B, F)) < 0.6
+    voiced[2] = False                                                      # a row without a voiced frame
+    lens = [40, 25, 40]
+    st = audio.voice_quality_statistics(vq, torch.from_numpy(voiced), lengths=lens)
+    use = voiced & (peak > 0) & (np.arange(F)[None, :] < np.array(lens)[:, None])
+    assert st["frames"].tolist() == use.sum(axis=1).tolist() and st["frames"][2] == 0 and st["frames"].dtype == torch.int64
+    for k in audio.VOICE_QUALITY_FIGURES:
+        v = vq[k].numpy()
+        assert st[k].dtype == torch.float64 and torch.isnan(st[k][2]) and float(st["sums"][k][2]) == 0.0
+        for b in range(2):
+            assert abs(float(st[k][b]) - v[b][use[b]].mean()) < 1e-13 and abs(float(st["sums"][k][b]) - v[b][use[b]].sum()) < 1e-13
+    one = audio.voice_quality_statistics({k: v[0] for k, v in vq.items()}, torch.from_numpy(voiced[0]))
+    assert one["frames"].tolist() == [int((voiced[0] & (peak[0] > 0)).sum())]
+    with pytest.raises(ValueError, match="voice_quality_statistics"):
+        audio.voice_quality_statistics(vq, torch.from_numpy(voiced[:, :5]))
+    with pytest.raises(ValueError, match="voice_quality_statistics"):
+        audio.voice_quality_statistics(vq, torch.from_numpy(voiced), lengths=[1, 2])
+
+
+# ---- the conditions on the inputs of the device tests -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("g", R.GEOMETRIES, ids=R.IDS)
+def test_device_cases_hold_the_input_conditions(g):
+    """For the rows the device tests run: float64 and longdouble restatements within 1e-11 max(|ref|, 1) on every entry and equal on every
+    q*; every non-silent frame's peak margin at least 1e-6; the frame counts 15, 0, 1 modulo 16.  So the device comparison leaves out no
+    frame."""
+    x, lens, (fr, pk, cp, mg), (frl, pkl, cpl, _) = rows(g)
+    assert [R.frames(n, g.H) % 16 for n in lens] == [15, 0, 1] and min(lens) >= 2500
+    NB, NQ = g.nfft // 2 + 1, g.q_max - g.q_fit + 1
+    assert NB % 4 == 1 and NB % 16 == 1 and NQ % 16 != 0, "a K tail of 1 in the second product, a one-column bin tail in the first"
+    per = [R.err(fr[..., i], frl[..., i]) for i in range(8)]
+    e_c = R.err(cp, cpl)
+    print(f"\nvoice quality {g[:6]} lens {lens}: float64 against longdouble per figure {[f'{e:.1e}' for e in per]} cepstrum {e_c:.1e} "
+          f"(gate {R.INPUT_TOL:g}); smallest peak margin {mg.min():.3e} (gate {R.MIN_PEAK_MARGIN:g}); silent frames {int((mg == np.inf).sum())}")
+    assert max(per) <= R.INPUT_TOL and e_c <= R.INPUT_TOL
+    assert np.array_equal(pk, pkl)
+    assert mg.min() >= R.MIN_PEAK_MARGIN
+
+
+def test_geometry_table():
+    assert [(g.nfft // 2 + 1, g.q_max - g.q_fit + 1) for g in R.GEOMETRIES] == [(33, 29), (33, 31), (257, 229), (513, 319)]
+    assert R.GEOMETRIES[2].bands == R.band_edges(22050, 512) and tuple(map(tuple, audio.voice_quality_tables(22050, 512)["bands"].tolist())) == R.GEOMETRIES[2].bands
+    for H in (10, 64, 128, 256):
+        assert [R.frames(n, H) % 16 for n in R.ragged_lens(H)] == [15, 0, 1]
+
+
+# ---- the mutants ------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mutant", R.MUTANTS)
+def test_every_mutant_shows_on_a_small_geometry(mutant):
+    moved = []
+    for g in R.GEOMETRIES[:2]:
+        x, lens, (fr, pk, _, _), _ = rows(g)
+        fm, pm, _, _ = R.batch(x, lens, g, mutant=mutant)
+        moved.append((float(np.abs(fm[..., 0] - fr[..., 0]).max()), int((pm != pk).sum())))
+    print(f"\nvoice quality mutant {mutant}: (largest move of cpp_db, frames whose q* moves) on the two 64-point geometries {moved}")
+    assert any(d > 1e-6 or k > 0 for d, k in moved)
+
+
+def test_peak_over_fit_does_not_show_at_1024():
+    x, lens, (fr, pk, _, _), _ = rows(BIG)
+    fm, pm, _, _ = R.batch(x, lens, BIG, mutant="peak_over_fit")
+    assert np.array_equal(pm, pk) and np.array_equal(fm, fr), "why the small geometries carry this mutant"
+
+
+# ---- silent frames ------------------------------------------------------------------------------------------------------------------------------------
+def test_the_silent_frame_rule_and_what_it_exists_for():
+    g = R.GEOMETRIES[0]
+    x = R.speech_like(600, seed=9, fs=R.FS)
+    x[200:400] = 0.0                                                       # digital silence in the middle
+    fr, pk, C, mg = R.row(x, g)
+    silent = ~(R.spectrum(x, g) > R.POWER_FLOOR).any(axis=1)
+    assert silent.sum() >= 10 and not silent[:15].any()
+    assert not fr[silent][:, [0, 1, 2, 3, 4, 6, 7]].any() and not pk[silent].any() and not C[silent].any() and (mg[silent] == np.inf).all()
+    NB = g.nfft // 2 + 1
+    assert np.array_equal(fr[silent, 5], np.full(int(silent.sum()), NB * R.POWER_FLOOR)), "the power is as computed: NB clamped bins"
+    fu, pu, Cu, _ = R.row(x, g, guard=False)
+    _, pl, _, _ = R.row(x, g, dtype=np.longdouble, guard=False)
+    noise = float(np.abs(Cu[silent]).max())
+    print(f"\nvoice quality: unguarded cepstrum of an all-clamped frame at most {noise:.3e}; float64 argmax {sorted(set(pu[silent].tolist()))}, "
+          f"longdouble argmax {sorted(set(pl[silent].tolist()))}")
+    assert 0.0 < noise < 1e-12, "summation noise, not a cepstrum"
+    assert (pu[silent] >= g.q_min).all(), "the unguarded argmax is some quefrency of the search range: arbitrary"
+
+
+# ---- the C ABI ----------------------------------------------------------------------------------------------------------------------------------------
+def test_header_declares_and_library_exports_ev_voice_quality():
+    with open(os.path.join(REPO, "include", "emojivoice.h")) as f:
+        header = f.read()
+    for name in ("ev_load_voice_quality", "ev_voice_quality"):
+        assert re.search(rf"\bint {name}\(ev_handle \*h,", header) and name in _lib.EXPORTS
+    assert "#define EV_ABI_VERSION 4" in header
+    for word in ("Hillenbrand", "Praat", "VoiceSauce", "to the digit"):
+        assert word in header and word in audio.voice_quality.__doc__
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build_library()
+    lib = _lib.load_library()
+    assert hasattr(lib, "ev_load_voice_quality") and hasattr(lib, "ev_voice_quality") and lib.ev_abi_version() == 4
+
+
+# ---- the CLI, with the device calls stubbed by the restatement --------------------------------------------------------------------------------------
+def test_voice_report_json_shape_and_validate_args(tmp_path, monkeypatch):
+    import argparse
+    import json
+
+    import pitch_ref as P
+    from emojivoice_amd import cli
+
+    wavs = {"a.wav": R.speech_like(6000, seed=20, fs=R.FS), "b.wav": R.speech_like(5000, seed=21, fs=R.FS), "c.wav": np.zeros(3000, np.float32)}
+    for name in wavs:
+        (tmp_path / name).write_bytes(b"")                                 # (the stubs below never open them)
+    flist = tmp_path / "filelist.txt"
+    flist.write_text(f"{tmp_path / 'a.wav'}|7|first\nb.wav|7|second\nc.wav|12|silent take\n", encoding="utf-8")
+    t = audio.voice_quality_tables(22050, 1024)
+    g = R.Geometry(1024, 256, 1024, t["q_fit"], t["q_min"], t["q_max"], BIG.bands, 22050)
+
+    def fake_yin(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, threshold=0.1, lengths=None):
+        r = P.pitch_yin(y.numpy(), lengths, frame_length, hop_length, 36, 340, threshold)
+        return {"f0": torch.from_numpy(P.f0_from_period(r["period"], sr)).float(), "voiced": torch.from_numpy(r["lag"] > 0)}
+
+    def fake_vq(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, lengths=None, power_floor=1e-7):
+        fr, pk, _, _ = R.batch(y.numpy(), lengths, g, floor=power_floor)
+        out = {k: torch.from_numpy(fr[..., i].copy()) for i, k in enumerate(audio.VOICE_QUALITY_FIGURES + ("power",))}
+        out["peak_quefrency"] = torch.from_numpy(pk)
+        return out
+
+    monkeypatch.setattr(audio, "load_audio", lambda path, sr=22050, device="cuda": torch.from_numpy(wavs[os.path.basename(str(path))]).unsqueeze(0))
+    monkeypatch.setattr(audio, "pitch_yin", fake_yin)
+    monkeypatch.setattr(audio, "voice_quality", fake_vq)
+    args = cli.validate_args(argparse.Namespace(voice_report=str(flist), batch_size=2, sample_rate=None, prepare_dataset=None))
+    rep = cli.voice_report(args, "cpu")
+    with open(f"{flist}.voice.json") as f:
+        saved = json.load(f)
+    figs = set(audio.VOICE_QUALITY_FIGURES)
+    assert saved == json.loads(json.dumps(rep)) and set(saved) == {"sample_rate", "hop_length", "files", "speakers", "overall"}
+    assert [set(f_) for f_ in saved["files"]] == [{"path", "speaker", "seconds", "frames", "voiced_frames"} | figs] * 3
+    a, b, c = saved["files"]
+    assert (a["frames"], b["frames"], c["frames"]) == (24, 20, 12) and a["voiced_frames"] > 3 and b["voiced_frames"] > 3 and a["seconds"] == 6000 / 22050
+    assert c["voiced_frames"] == 0 and all(c[k] is None for k in figs), "a silent take: NaN is written as null"
+    fr, pk, _, _ = R.row(wavs["a.wav"], g)
+    use = (P.pitch_yin(wavs["a.wav"][None], [6000], 1024, 256, 36, 340, 0.1)["lag"][0] > 0) & (pk > 0)
+    assert a["voiced_frames"] == int(use.sum())
+    for i, k in enumerate(audio.VOICE_QUALITY_FIGURES):
+        assert abs(a[k] - fr[use, i].mean()) < 1e-12
+        pooled = (a[k] * a["voiced_frames"] + b[k] * b["voiced_frames"]) / (a["voiced_frames"] + b["voiced_frames"])
+        assert abs(saved["speakers"]["7"][k] - pooled) < 1e-12 and saved["overall"][k] == saved["speakers"]["7"][k] and saved["speakers"]["12"][k] is None
+    assert saved["speakers"]["7"]["files"] == 2 and saved["overall"]["files"] == 3
+    with pytest.raises(AssertionError, match="--voice_quality"):
+        cli.validate_args(argparse.Namespace(voice_quality=True, evaluate_pairs=None, sample_rate=None, prepare_dataset=None))
+    with pytest.raises(AssertionError, match="Batch size"):
+        cli.validate_args(argparse.Namespace(voice_report=str(flist), batch_size=0, sample_rate=None, prepare_dataset=None))

@@ -27,6 +27,39 @@ int check_finite(ev_handle* h, const char* who, const char* name, const double* 
 }
 // ceil(L / H): the frames of a row of L samples at hop H
 int frames_of(int L, int H) { return (int)(((long long)L + H - 1) / H); }
+// the geometry of a windowed DFT as a GEMM (the float64 DFT GEMM kernels of ev_analysis_kernels.h)
+int check_dft_geometry(ev_handle* h, const char* who, int W, int H, int nfft, int nfft_max) {
+    if (nfft < 16 || nfft > nfft_max || nfft % 2) return fail(h, "%s: nfft=%d must be even with 16 <= nfft <= %d", who, nfft, nfft_max);
+    if ((nfft - W) % 2) return fail(h, "%s: nfft - W = %d must be even (the window is padded centrally)", who, nfft - W);
+    if (W < 4 || W > nfft || W % 4) return fail(h, "%s: W=%d must be a multiple of 4 with 4 <= W <= nfft = %d", who, W, nfft);
+    if (H < 1 || H > 512) return fail(h, "%s: H=%d outside 1 <= H <= 512", who, H);
+    return 0;
+}
+
+// The tables of a load that open with the windowed DFT basis: window and twiddles go to the device as temporaries, one block of `bytes` is allocated
+// behind them, stft_dist_basis_kernel builds the (W, nfft / 2 + 1) basis at the head of the block, extra(block, d_tw) makes the caller's further copies
+// and launches, and after ONE synchronisation the temporaries are freed.  Returns 0 with *blk the caller's to own; else the message is set (`what`:
+// "basis" or "tables") and nothing is left allocated.  (extern "C++": ev_engine.hip includes this file inside extern "C", where no template may stand.)
+extern "C++" template <typename Extra>
+int build_dft_basis(ev_handle* h, const char* who, const char* what, const double* window, const double* twiddle, int W, int nfft, size_t bytes, char** blk, Extra extra) {
+    const int NB = nfft / 2 + 1;
+    double* d_win = nullptr; double* d_tw = nullptr;
+    HIPCHK(h, hipMalloc((void**)&d_win, (size_t)W * sizeof(double)));
+    if (hipMalloc((void**)&d_tw, (size_t)2 * nfft * sizeof(double)) != hipSuccess) { hipFree(d_win); return fail(h, "%s: hipMalloc of the twiddles failed", who); }
+    hipError_t e = hipMalloc((void**)blk, bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_win, window, (size_t)W * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_tw, twiddle, (size_t)2 * nfft * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        StftBasisParams pb{d_win, d_tw, (double2*)*blk, W, nfft, NB};
+        launch<stft_dist_basis_kernel>(h->device, dim3((unsigned)(((size_t)W * NB + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pb);
+        e = extra(*blk, d_tw);
+        if (e == hipSuccess) e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    hipFree(d_win); hipFree(d_tw);
+    if (e != hipSuccess) { if (*blk) hipFree(*blk); return fail(h, "%s: building the %s failed: %s", who, what, hipGetErrorString(e)); }
+    return 0;
+}
 
 }  // namespace
 
@@ -425,34 +458,20 @@ int ev_stoi(ev_handle* h, const float* d_x, const float* d_y, const int32_t* d_l
 int ev_load_stft_dist(ev_handle* h, const double* window, const double* twiddle, int W, int H, int nfft) {
     if (enter(h)) return 1;
     if (!window || !twiddle) return fail(h, "ev_load_stft_dist: window and twiddle must be non-null (HOST)");
-    if (nfft < 16 || nfft > 2048 || nfft % 2) return fail(h, "ev_load_stft_dist: nfft=%d must be even with 16 <= nfft <= 2048", nfft);
-    if ((nfft - W) % 2) return fail(h, "ev_load_stft_dist: nfft - W = %d must be even (the window is padded centrally)", nfft - W);
-    if (W < 4 || W > nfft || W % 4) return fail(h, "ev_load_stft_dist: W=%d must be a multiple of 4 with 4 <= W <= nfft = %d", W, nfft);
-    if (H < 1 || H > 512) return fail(h, "ev_load_stft_dist: H=%d outside 1 <= H <= 512", H);
+    if (check_dft_geometry(h, __func__, W, H, nfft, 2048)) return 1;
     if (check_finite(h, __func__, "window", window, W) || check_finite(h, __func__, "twiddle", twiddle, 2 * nfft)) return 1;
-    StftDistW t;
-    t.W = W; t.H = H; t.nfft = nfft; t.NB = nfft / 2 + 1; t.skew = ((2 - H) % 4 + 4) % 4;
+    StftDistW w;
+    w.t.W = W; w.t.H = H; w.t.nfft = nfft; w.t.NB = nfft / 2 + 1; w.t.skew = dft_skew(H);
     StftDistW& cur = h->stftd;
-    if (cur.loaded) { if (drop_owned(h, {cur.basis})) return 1; cur = StftDistW(); }
-    double* d_win = nullptr; double* d_tw = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d_win, (size_t)W * sizeof(double)));
-    if (hipMalloc((void**)&d_tw, (size_t)2 * nfft * sizeof(double)) != hipSuccess) { hipFree(d_win); return fail(h, "ev_load_stft_dist: hipMalloc of the twiddles failed"); }
-    const size_t n_basis = (size_t)W * t.NB;
-    hipError_t e = hipMalloc((void**)&t.basis, n_basis * sizeof(double2));
-    if (e == hipSuccess) e = hipMemcpy(d_win, window, (size_t)W * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_tw, twiddle, (size_t)2 * nfft * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        StftBasisParams pb{d_win, d_tw, t.basis, W, nfft, t.NB};
-        launch<stft_dist_basis_kernel>(h->device, dim3((unsigned)((n_basis + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pb);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    hipFree(d_win); hipFree(d_tw);
-    if (e != hipSuccess) { if (t.basis) hipFree(t.basis); return fail(h, "ev_load_stft_dist: building the basis failed: %s", hipGetErrorString(e)); }
-    h->owned.push_back(t.basis);
+    if (cur.loaded) { if (drop_owned(h, {(void*)cur.t.basis})) return 1; cur = StftDistW(); }
+    char* blk = nullptr;
+    auto none = [](char*, const double*) { return hipSuccess; };
+    if (build_dft_basis(h, __func__, "basis", window, twiddle, W, nfft, (size_t)W * w.t.NB * sizeof(double2), &blk, none)) return 1;
+    w.t.basis = (const double2*)blk;
+    h->owned.push_back(blk);
     ++h->n_allocs;                          // (the basis is the handle's largest table: 33.6 MB at W = nfft = 2048)
-    t.loaded = true;
-    cur = t;
+    w.loaded = true;
+    cur = w;
     return 0;
 }
 
@@ -467,18 +486,17 @@ int ev_stft_dist(ev_handle* h, const float* d_x, const float* d_y, const int32_t
     if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_stft_dist: power_floor=%g must be finite and greater than 0", power_floor);
     if (!d_sums || !d_counts) return fail(h, "ev_stft_dist: d_sums and d_counts must be non-null");
     h->stream = (hipStream_t)stream;
-    if (L / w.H > 0x7fffffef) return fail(h, "ev_stft_dist: L=%d at H=%d has more frames than an int32 tile index holds", L, w.H);
-    const int NF = L > w.nfft / 2 ? 1 + L / w.H : 0;
+    const StftDistTables& t = w.t;
+    if (L / t.H > 0x7fffffef) return fail(h, "ev_stft_dist: L=%d at H=%d has more frames than an int32 tile index holds", L, t.H);
+    const int NF = L > t.nfft / 2 ? 1 + L / t.H : 0;
     double* frame = d_frame;
     if (!frame && NF > 0) {
         if (scratch_acquire(h, h->stftd_ws, (size_t)B * NF * 4 * sizeof(double))) return 1;
         frame = (double*)h->stftd_ws.p;
     }
-    StftDistTables t{w.basis, w.W, w.H, w.nfft, w.NB, w.skew};
     if (NF > 0) {
         StftFramesParams pf{d_x, d_y, d_len, frame, t, L, NF, power_floor};
-        const int span = 15 * w.H + w.W;
-        const size_t smem = (size_t)2 * (span + w.skew * ((span - 1) / w.H)) * sizeof(float);
+        const size_t smem = (size_t)2 * dft_span_words(15 * t.H + t.W, t.H, t.skew) * sizeof(float);
         launch<stft_dist_frames_kernel>(h->device, dim3((unsigned)((NF + 15) / 16), (unsigned)B), dim3(256), smem, h->stream, pf);
     }
     StftRowsParams pr{frame, d_len, d_sums, d_counts, t, L, NF};
@@ -494,10 +512,7 @@ int ev_load_voice_quality(ev_handle* h, const double* window, const double* twid
     if (enter(h)) return 1;
     if (!window || !twiddle || !bands || !slope_w || !fit_w)
         return fail(h, "ev_load_voice_quality: window, twiddle, bands, slope_w and fit_w must be non-null (HOST)");
-    if (nfft < 16 || nfft > 1024 || nfft % 2) return fail(h, "ev_load_voice_quality: nfft=%d must be even with 16 <= nfft <= 1024", nfft);
-    if ((nfft - W) % 2) return fail(h, "ev_load_voice_quality: nfft - W = %d must be even (the window is padded centrally)", nfft - W);
-    if (W < 4 || W > nfft || W % 4) return fail(h, "ev_load_voice_quality: W=%d must be a multiple of 4 with 4 <= W <= nfft = %d", W, nfft);
-    if (H < 1 || H > 512) return fail(h, "ev_load_voice_quality: H=%d outside 1 <= H <= 512", H);
+    if (check_dft_geometry(h, __func__, W, H, nfft, 1024)) return 1;
     const int NB = nfft / 2 + 1;
     for (int i = 0; i < 6; ++i) {
         const int lo = bands[2 * i], hi = bands[2 * i + 1];
@@ -511,43 +526,34 @@ int ev_load_voice_quality(ev_handle* h, const double* window, const double* twid
     if (check_finite(h, __func__, "window", window, W) || check_finite(h, __func__, "twiddle", twiddle, 2 * nfft)
         || check_finite(h, __func__, "slope_w", slope_w, 2 * NB) || check_finite(h, __func__, "fit_w", fit_w, NQ)) return 1;
     if (!std::isfinite(q_mean)) return fail(h, "ev_load_voice_quality: q_mean=%g is not finite", q_mean);
-    VoiceQW t;
-    t.W = W; t.H = H; t.nfft = nfft; t.NB = NB; t.NBp = (NB + 3) / 4 * 4; t.NQ = NQ; t.skew = ((2 - H) % 4 + 4) % 4;
+    VoiceQW w;
+    VoiceQTables& t = w.t;
+    t.W = W; t.H = H; t.nfft = nfft; t.NB = NB; t.NBp = (NB + 3) / 4 * 4; t.NQ = NQ; t.skew = dft_skew(H);
     t.S = NB + ((2 - NB) % 32 + 32) % 32;                               // the smallest S >= NB with S = 2 mod 32
     t.q_fit = q_fit; t.q_min = q_min; t.q_max = q_max; t.q_mean = q_mean;
     for (int i = 0; i < 12; ++i) t.band[i] = bands[i];
-    const int span = 15 * H + W;
-    t.lds = (size_t)16 * t.S * sizeof(double) + (size_t)(span + t.skew * ((span - 1) / H)) * sizeof(float);
-    if (t.lds > 160 * 1024) return fail(h, "ev_load_voice_quality: nfft=%d H=%d W=%d need %zu bytes of LDS, over 160 KiB", nfft, H, W, t.lds);
+    w.lds = (size_t)16 * t.S * sizeof(double) + (size_t)dft_span_words(15 * H + W, H, t.skew) * sizeof(float);
+    if (w.lds > 160 * 1024) return fail(h, "ev_load_voice_quality: nfft=%d H=%d W=%d need %zu bytes of LDS, over 160 KiB", nfft, H, W, w.lds);
     VoiceQW& cur = h->voiceq;
-    if (cur.loaded) { if (drop_owned(h, {cur.basis})) return 1; cur = VoiceQW(); }
-    double* d_win = nullptr; double* d_tw = nullptr; char* blk = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d_win, (size_t)W * sizeof(double)));
-    if (hipMalloc((void**)&d_tw, (size_t)2 * nfft * sizeof(double)) != hipSuccess) { hipFree(d_win); return fail(h, "ev_load_voice_quality: hipMalloc of the twiddles failed"); }
+    if (cur.loaded) { if (drop_owned(h, {(void*)cur.t.basis})) return 1; cur = VoiceQW(); }
     const size_t n_basis = (size_t)W * NB, n_cep = (size_t)t.NBp * NQ;
-    hipError_t e = hipMalloc((void**)&blk, n_basis * sizeof(double2) + (n_cep + 2 * (size_t)NB + NQ) * sizeof(double));
-    if (e == hipSuccess) {
-        t.basis = (double2*)blk;
-        t.cep = (double*)(t.basis + n_basis); t.slope_w = t.cep + n_cep; t.fit_w = t.slope_w + 2 * (size_t)NB;
-        e = hipMemcpy(d_win, window, (size_t)W * sizeof(double), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemcpy(d_tw, twiddle, (size_t)2 * nfft * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t.slope_w, slope_w, (size_t)2 * NB * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t.fit_w, fit_w, (size_t)NQ * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        StftBasisParams pb{d_win, d_tw, t.basis, W, nfft, NB};
-        launch<stft_dist_basis_kernel>(h->device, dim3((unsigned)((n_basis + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pb);
-        VoiceQCepParams pc{d_tw, t.cep, nfft, NB, t.NBp, NQ, q_fit};
-        launch<voiceq_cep_basis_kernel>(h->device, dim3((unsigned)((n_cep + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pc);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    hipFree(d_win); hipFree(d_tw);
-    if (e != hipSuccess) { if (blk) hipFree(blk); return fail(h, "ev_load_voice_quality: building the tables failed: %s", hipGetErrorString(e)); }
+    char* blk = nullptr;
+    const size_t o_cep = 2 * n_basis, o_sw = o_cep + n_cep, o_fw = o_sw + 2 * (size_t)NB;   // in doubles from the block's start, behind the basis
+    auto rest = [&](char* b, const double* d_tw) {
+        double* d = (double*)b;
+        hipError_t e = hipMemcpy(d + o_sw, slope_w, (size_t)2 * NB * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d + o_fw, fit_w, (size_t)NQ * sizeof(double), hipMemcpyHostToDevice);
+        VoiceQCepParams pc{d_tw, d + o_cep, nfft, NB, t.NBp, NQ, q_fit};
+        if (e == hipSuccess) launch<voiceq_cep_basis_kernel>(h->device, dim3((unsigned)((n_cep + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pc);
+        return e;
+    };
+    if (build_dft_basis(h, __func__, "tables", window, twiddle, W, nfft, (o_fw + NQ) * sizeof(double), &blk, rest)) return 1;
+    const double* d = (const double*)blk;
+    t.basis = (const double2*)blk; t.cep = d + o_cep; t.slope_w = d + o_sw; t.fit_w = d + o_fw;
     h->owned.push_back(blk);
     ++h->n_allocs;                          // (one block: both bases, slope_w and fit_w; 9.7 MB at W = nfft = 1024 with 319 quefrencies)
-    t.loaded = true;
-    cur = t;
+    w.loaded = true;
+    cur = w;
     return 0;
 }
 
@@ -561,12 +567,10 @@ int ev_voice_quality(ev_handle* h, const float* d_x, const int32_t* d_len, int B
     if (!d_x) return fail(h, "ev_voice_quality: d_x must be non-null");
     if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_voice_quality: power_floor=%g must be finite and greater than 0", power_floor);
     if (!d_frame || !d_peak) return fail(h, "ev_voice_quality: d_frame and d_peak must be non-null");
-    if (L / w.H > 0x7fffffef) return fail(h, "ev_voice_quality: L=%d at H=%d has more frames than an int32 tile index holds", L, w.H);
+    if (L / w.t.H > 0x7fffffef) return fail(h, "ev_voice_quality: L=%d at H=%d has more frames than an int32 tile index holds", L, w.t.H);
     h->stream = (hipStream_t)stream;
-    const int NF = frames_of(L, w.H);
-    VoiceQTables t{w.basis, w.cep, w.slope_w, w.fit_w, w.W, w.H, w.nfft, w.NB, w.NBp, w.NQ, w.skew, w.S, w.q_fit, w.q_min, w.q_max, {}, w.q_mean};
-    for (int i = 0; i < 12; ++i) t.band[i] = w.band[i];
-    VoiceQParams pv{d_x, d_len, d_frame, d_peak, d_cepstrum, t, L, NF, power_floor};
+    const int NF = frames_of(L, w.t.H);
+    VoiceQParams pv{d_x, d_len, d_frame, d_peak, d_cepstrum, w.t, L, NF, power_floor};
     launch<voice_quality_kernel>(h->device, dim3((unsigned)((NF + 15) / 16), (unsigned)B), dim3(256), w.lds, h->stream, pv);
     HIPCHK(h, hipGetLastError());
     return 0;

@@ -1391,21 +1391,42 @@ __global__ __launch_bounds__(256) void stft_dist_basis_kernel(const StftBasisPar
     p.basis[i] = make_double2(w * p.tw[2 * ph], w * p.tw[2 * ph + 1]);
 }
 
+// ---------------------------------------------------------------------------
+// The float64 DFT GEMM of stft_dist_frames_kernel and voice_quality_kernel: what both share.  A workgroup of 4 waves owns a tile of 16
+// frames; wave w owns the column tiles (bins, or quefrencies) w, w + 4, ... of 16 columns; per column tile the K dimension runs in steps of
+// one v_mfma_f64_16x16x4_f64 per (signal, plane).  Lane l of an A fragment holds row (frame) l & 15 at k0 + (l >> 4), lane l of a B fragment
+// row k0 + (l >> 4) of the basis at column l & 15 (read from global memory: L2-resident), and register i of lane l of an accumulator is frame
+// (l >> 4) + 4 i, column l & 15.
+// SKEW.  A tile's raw span of 15 H + W samples is staged once into LDS as fp32 and an A fragment reads t = (l & 15) H + k0 + (l >> 4), widened
+// on the way out: with ds_read_b32 banked over 32 words and served in two groups of 32 lanes, a frame stride H = 0 mod 4 (240: 16 banks) lands
+// the 16 frames of a group on few banks.  So sample t lives at word t + skew * (t / H) with skew = (2 - H) mod 4, and the frame stride
+// H + skew is 2 mod 4: 2 r (odd) mod 32 is 16 distinct even banks for r = 0 .. 15, and the two k of a lane group fill the odd ones —
+// conflict-free (except where k0 + (l >> 4) crosses a multiple of H inside a group).  At most 3 (16 + W / H) pad words per signal.
+__host__ __device__ __forceinline__ int dft_skew(int H) { return ((2 - H) % 4 + 4) % 4; }
+__host__ __device__ __forceinline__ int dft_span_words(int span, int H, int skew) { return span + skew * ((span - 1) / H); }   // (the last word + 1)
+__device__ __forceinline__ int dft_word(int t, int H, int skew) { return t + skew * (t / H); }
+
+// The word of sample r H + j of frame r, r (H + skew) + j + skew (j / H), for j = q, q + 4, ... without a division per step:
+// (j + 4) / H = j / H + 4 / H + (j % H + 4 % H >= H); step_pad is non-zero for H < 4 only.
+struct DftSkewWalk {
+    int H, skew, step_mod, step_pad, rbase, j, jm, pad;
+    __device__ __forceinline__ DftSkewWalk(int r, int h, int k) : H(h), skew(k), step_mod(4 % h), step_pad(k * (4 / h)), rbase(r * (h + k)), j(0), jm(0), pad(0) {}
+    __device__ __forceinline__ void start(int q) { j = q; jm = q % H; pad = skew * (q / H); }
+    __device__ __forceinline__ int word() const { return rbase + j + pad; }
+    __device__ __forceinline__ void step() { j += 4; jm += step_mod; pad += step_pad; if (jm >= H) { jm -= H; pad += skew; } }
+};
+
+// The hand-over of per-frame sums: over the 16 column lanes of a frame by one xor tree (offsets 8, 4, 2, 1; in each kernel, its sums side by
+// side), then, from the waves' partials in LDS (red[wave][frame][term]), over the waves as ((w0 + w1) + w2) + w3.
+template <int C>
+__device__ __forceinline__ double dft_waves_sum(const double (&red)[4][16][C], int fr, int c) { STOI_EXACT return ((red[0][fr][c] + red[1][fr][c]) + red[2][fr][c]) + red[3][fr][c]; }
+
 // One workgroup per (row b, tile of 16 frames f0 .. f0 + 15).  The tile's raw span, samples f0 H - W / 2 + t for 0 <= t < 15 H + W of both
-// signals, is staged once into LDS as fp32 with the reflection applied (refl(i) = -i below 0, 2 (len - 1) - i from len on; what a frame
-// >= nf would read outside the row is staged as 0 and that frame is masked).  Lane l of an A fragment reads t = (l & 15) H + k0 + (l >> 4):
-// with ds_read_b32 banked over 32 words and served in two groups of 32 lanes, a frame stride H = 0 mod 4 (240: 16 banks) lands the 16
-// frames of a group on few banks.  SKEW: sample t lives at word t + skew * (t / H) with skew = (2 - H) mod 4, so the frame stride H + skew
-// is 2 mod 4: 2 r (odd) mod 32 is 16 distinct even banks for r = 0 .. 15, and the two k of a lane group fill the odd ones — conflict-free
-// (except where k0 + (l >> 4) crosses a multiple of H inside a group).  At most 3 (16 + W / H) pad words per signal: 78 160 bytes for
-// both signals at H = 511, W = 2048, the largest footprint.
-// Wave w owns the bin tiles w, w + 4, ...; per bin tile W / 4 steps of four MFMAs (x c, x s, y c, y s): the A fragment of each signal
-// (frame l & 15, sample k0 + (l >> 4), widened on the way out of LDS) serves both planes, the B fragment (basis row k0 + (l >> 4), bin
-// l & 15, read from global memory: L2-resident) serves both signals.  Accumulators in the f64 layout: register i of lane l is frame
-// (l >> 4) + 4 i, bin l & 15.  Epilogue per (frame, bin): p = max(fma(sm, sm, re * re), floor), m = sqrt(p), l = log(p) for both signals; the
-// four terms are accumulated per frame over the wave's bin tiles in ascending order (squares as fma(d, d, sum)), reduced over the 16 bin
-// lanes by one xor tree (offsets 8, 4, 2, 1) and over the waves as ((w0 + w1) + w2) + w3.  Bins >= NB (the address is clamped, the term
-// dropped) and frames >= nf (zeros) are masked.
+// signals, is staged with the reflection applied (what a frame >= nf would read outside the row is staged as 0 and that frame is masked):
+// 78 160 bytes for both signals at H = 511, W = 2048, the largest footprint.  Per bin tile W / 4 steps of four MFMAs (x c, x s, y c, y s):
+// the A fragment of each signal serves both planes, the B fragment both signals.  Epilogue per (frame, bin): p = max(fma(sm, sm, re * re),
+// floor), m = sqrt(p), l = log(p) for both signals; the four terms are accumulated per frame over the wave's bin tiles in ascending order
+// (squares as fma(d, d, sum)) and handed over.  Bins >= NB (the address is clamped, the term dropped) and frames >= nf (zeros) are masked.
 struct StftFramesParams { const float* x; const float* y; const int32_t* len; double* frame; StftDistTables t; int L, NF; double floor; };
 
 __global__ __launch_bounds__(256) void stft_dist_frames_kernel(const StftFramesParams p) {
@@ -1423,7 +1444,7 @@ __global__ __launch_bounds__(256) void stft_dist_frames_kernel(const StftFramesP
     }
     const int span = 15 * H + W;
     float* sx = stftd_smem;
-    float* sy = sx + span + skew * ((span - 1) / H);                    // (the last word of x is (span - 1) + skew ((span - 1) / H))
+    float* sy = sx + dft_span_words(span, H, skew);
     {
         const float* xr = p.x + (size_t)b * p.L;
         const float* yr = p.y + (size_t)b * p.L;
@@ -1433,22 +1454,21 @@ __global__ __launch_bounds__(256) void stft_dist_frames_kernel(const StftFramesP
             if (i < 0) i = -i;
             else if (i >= n) i = 2LL * (n - 1) - i;
             const bool ok = i >= 0 && i < n;                            // (always, for a frame < nf)
-            const int a = t + skew * (t / H);
+            const int a = dft_word(t, H, skew);
             sx[a] = ok ? xr[i] : 0.f;
             sy[a] = ok ? yr[i] : 0.f;
         }
     }
     __syncthreads();
     const int r = lane & 15, q = lane >> 4;
-    const int rbase = r * (H + skew);                                   // word of sample r H + j: r (H + skew) + j + skew (j / H)
-    const int ntile = (NB + 15) >> 4;
-    const int step_mod = 4 % H, step_pad = skew * (4 / H), nsteps = W >> 2;
+    const int ntile = (NB + 15) >> 4, nsteps = W >> 2;
+    DftSkewWalk walk(r, H, skew);
     double t0[4] = {0.0, 0.0, 0.0, 0.0}, t1[4] = {0.0, 0.0, 0.0, 0.0}, t2[4] = {0.0, 0.0, 0.0, 0.0}, t3[4] = {0.0, 0.0, 0.0, 0.0};
     for (int bt = wv; bt < ntile; bt += 4) {
         const int col = bt * 16 + r;
         const double2* bp = p.t.basis + (size_t)q * NB + (col < NB ? col : NB - 1);
         stftd_acc xc = {0.0, 0.0, 0.0, 0.0}, xs = xc, yc = xc, ys = xc;
-        int j = q, jm = q % H, pad = skew * (q / H);
+        walk.start(q);
         // four steps per round; the basis of the NEXT round is requested before this round's products (the index clamped at the last
         // step: a repeated load, never one past the basis), so its L2 latency hides behind sixteen matrix instructions
         double2 cur[4], nxt[4];
@@ -1460,14 +1480,13 @@ __global__ __launch_bounds__(256) void stft_dist_frames_kernel(const StftFramesP
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (s0 + u < nsteps) {                                  // (uniform)
-                    const int a = rbase + j + pad;
+                    const int a = walk.word();
                     const double ax = (double)sx[a], ay = (double)sy[a];
                     xc = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].x, xc, 0, 0, 0);
                     xs = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].y, xs, 0, 0, 0);
                     yc = __builtin_amdgcn_mfma_f64_16x16x4f64(ay, cur[u].x, yc, 0, 0, 0);
                     ys = __builtin_amdgcn_mfma_f64_16x16x4f64(ay, cur[u].y, ys, 0, 0, 0);
-                    j += 4; jm += step_mod; pad += step_pad;            // (j + 4) / H = j / H + 4 / H + (j % H + 4 % H >= H)
-                    if (jm >= H) { jm -= H; pad += skew; }
+                    walk.step();
                 }
             }
 #pragma unroll
@@ -1498,7 +1517,7 @@ __global__ __launch_bounds__(256) void stft_dist_frames_kernel(const StftFramesP
     __syncthreads();
     if (tid < 64) {
         const int fr = tid >> 2, c = tid & 3;
-        const double v = ((red[0][fr][c] + red[1][fr][c]) + red[2][fr][c]) + red[3][fr][c];
+        const double v = dft_waves_sum(red, fr, c);
         if (f0 + fr < p.NF) out[tid] = f0 + fr < nf ? v : 0.0;
     }
 }
@@ -1570,25 +1589,23 @@ __global__ __launch_bounds__(256) void voiceq_cep_basis_kernel(const VoiceQCepPa
     p.cep[i] = k < p.NB ? g * p.tw[2 * ph] / (double)p.nfft : 0.0;
 }
 
-// One workgroup of 4 waves per (row b, tile of 16 frames f0 .. f0 + 15).  Dynamic LDS: Ld, the tile's log-spectrum (16 frames x S doubles),
-// then the tile's raw span, samples f0 H + H / 2 - W / 2 + t for 0 <= t < 15 H + W, staged once as fp32 with ZEROS outside [0, len) (no
-// reflection) under the skew scheme of stft_dist_frames_kernel (sample t at word t + skew (t / H), skew = (2 - H) mod 4).
-// PHASE 1 is that kernel's loop for one signal: wave w owns the bin tiles w, w + 4, ...; per tile W / 4 steps of two MFMAs (cos, sin), the
-// basis of the next four steps requested before this round's products.  Accumulator register i of lane l is frame (l >> 4) + 4 i, bin
-// 16 tile + (l & 15).  Epilogue per (frame, bin): raw, p, Ldb as above; Ldb goes to Ld[frame S + bin]; per frame the lane accumulates over its
-// tiles in ascending order: the two alpha sums and the power (s = s + p), the two slope sums (s = fma(slope_w[b][k], Ldb, s) over every bin:
-// the weights outside a band are zeros), the two Hammarberg maxima, the count of bins with raw > floor.  The 16 bin lanes are then reduced by
-// one xor tree (offsets 8, 4, 2, 1) and the waves as ((w0 + w1) + w2) + w3.
+// One workgroup of 4 waves per (row b, tile of 16 frames f0 .. f0 + 15), on the shared pieces above.  Dynamic LDS: Ld, the tile's log-spectrum
+// (16 frames x S doubles), then the tile's raw span, samples f0 H + H / 2 - W / 2 + t for 0 <= t < 15 H + W, staged under the skew with ZEROS
+// outside [0, len) (no reflection).
+// PHASE 1 is stft_dist_frames_kernel's loop for one signal: per bin tile W / 4 steps of two MFMAs (cos, sin).  Epilogue per (frame, bin): raw,
+// p, Ldb as above; Ldb goes to Ld[frame S + bin]; per frame the lane accumulates over its tiles in ascending order: the two alpha sums and the
+// power (s = s + p), the two slope sums (s = fma(slope_w[b][k], Ldb, s) over every bin: the weights outside a band are zeros), the two
+// Hammarberg maxima, the count of bins with raw > floor; then the hand-over (the maxima by fmax through the same tree and over the waves).
 // PHASE 2, after one barrier: wave w owns the quefrency tiles w, w + 4, ... of 16 columns from q_fit; per tile NBp / 4 steps of one MFMA.  Lane
 // l of an A fragment reads Ld[(l & 15) S + k0 + (l >> 4)] with ds_read_b64 (k >= NB: the address is clamped to NB - 1, the basis row is zero);
-// the B fragment is cep[k0 + (l >> 4)][16 tile + (l & 15)] from global memory (L2-resident; the column clamped at NQ - 1, the term dropped).
+// the B fragment is cep[k0 + (l >> 4)][16 tile + (l & 15)] (the column clamped at NQ - 1, the term dropped).
 // BANKS: ds_read_b64 is banked over 64 dwords and served in two groups of 32 lanes; lane l of a group reads dwords 2 ((l & 15) S + k0 + q)
 // and the next one, q = l >> 4 in {0, 1} or {2, 3}.  With S = 2 mod 32, 2 r S = 4 r mod 64: the group's 32 lanes start at the dword banks
 // 4 r + 2 q + const, all 32 even residues mod 64, each read covering its even bank and the odd one after it: all 64 banks once, conflict-free.
 // S is the smallest such number >= NB (NB = 513: S = 514).  The epilogue's stores of Ldb (once per bin tile) are not conflict-free and need not be.
 // Epilogue per (frame, quefrency): sum C (s = s + C) and sum fit_w C (s = fma(fit_w, C, s)) over the lane's tiles in ascending order, the
-// maximum over q_min <= q <= q_max with its index (strictly greater replaces: the lowest q of a tie), optionally the store of C; the 16 lanes
-// by the xor tree (8, 4, 2, 1; of equal maxima the lower index), the waves as ((w0 + w1) + w2) + w3 and in the order w0 .. w3 for the maximum.
+// maximum over q_min <= q <= q_max with its index (strictly greater replaces: the lowest q of a tie), optionally the store of C; the sums are
+// handed over, the maximum through the same tree (of equal maxima the lower index) and over the waves in the order w0 .. w3.
 // Thread f < 16 then forms the frame's eight figures: mean = sum C / NQ, base = mean + (sum fit_w C) (q* - q_mean), cpp = C[q*] - base,
 // alpha = (10 / ln 10) (log(hi) - log(lo)).  A SILENT frame (no bin with raw > floor) keeps its power; its other figures, d_peak and
 // cepstrum are zeros by definition.  Frames >= nf are zeros.
@@ -1623,15 +1640,14 @@ __global__ __launch_bounds__(256) void voice_quality_kernel(const VoiceQParams p
         const long long i0 = (long long)f0 * H + H / 2 - W / 2;
         for (int t = tid; t < span; t += 256) {
             const long long i = i0 + t;
-            sx[t + skew * (t / H)] = i >= 0 && i < n ? xr[i] : 0.f;
+            sx[dft_word(t, H, skew)] = i >= 0 && i < n ? xr[i] : 0.f;
         }
     }
     __syncthreads();
     const int r = lane & 15, q = lane >> 4;
     {
-        const int rbase = r * (H + skew);                               // word of sample r H + j: r (H + skew) + j + skew (j / H)
-        const int ntile = (NB + 15) >> 4;
-        const int step_mod = 4 % H, step_pad = skew * (4 / H), nsteps = W >> 2;
+        const int ntile = (NB + 15) >> 4, nsteps = W >> 2;
+        DftSkewWalk walk(r, H, skew);
         const double ninf = -__builtin_huge_val();
         double al[4] = {0.0, 0.0, 0.0, 0.0}, ah[4] = {0.0, 0.0, 0.0, 0.0}, s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
         double pw[4] = {0.0, 0.0, 0.0, 0.0}, hl[4] = {ninf, ninf, ninf, ninf}, hh[4] = {ninf, ninf, ninf, ninf};
@@ -1641,7 +1657,7 @@ __global__ __launch_bounds__(256) void voice_quality_kernel(const VoiceQParams p
             const double2* bp = p.t.basis + (size_t)q * NB + colc;
             const double w0 = p.t.slope_w[colc], w1 = p.t.slope_w[NB + colc];
             stftd_acc xc = {0.0, 0.0, 0.0, 0.0}, xs = xc;
-            int j = q, jm = q % H, pad = skew * (q / H);
+            walk.start(q);
             double2 cur[4], nxt[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) cur[u] = bp[(size_t)(u < nsteps ? u : nsteps - 1) * 4 * NB];
@@ -1651,11 +1667,10 @@ __global__ __launch_bounds__(256) void voice_quality_kernel(const VoiceQParams p
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (t0 + u < nsteps) {                              // (uniform)
-                        const double ax = (double)sx[rbase + j + pad];
+                        const double ax = (double)sx[walk.word()];
                         xc = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].x, xc, 0, 0, 0);
                         xs = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].y, xs, 0, 0, 0);
-                        j += 4; jm += step_mod; pad += step_pad;        // (j + 4) / H = j / H + 4 / H + (j % H + 4 % H >= H)
-                        if (jm >= H) { jm -= H; pad += skew; }
+                        walk.step();
                     }
                 }
 #pragma unroll
@@ -1765,17 +1780,17 @@ __global__ __launch_bounds__(256) void voice_quality_kernel(const VoiceQParams p
         double cpp = 0.0, alpha = 0.0, ham = 0.0, sl0 = 0.0, sl1 = 0.0, power = 0.0, cq = 0.0, base = 0.0;
         int qs = 0;
         if (f0 + fr < nf) {
-            power = ((red[0][fr][6] + red[1][fr][6]) + red[2][fr][6]) + red[3][fr][6];
+            power = dft_waves_sum(red, fr, 6);
             if (red_live[0][fr] + red_live[1][fr] + red_live[2][fr] + red_live[3][fr] > 0) {
-                const double lo = ((red[0][fr][0] + red[1][fr][0]) + red[2][fr][0]) + red[3][fr][0];
-                const double hi = ((red[0][fr][1] + red[1][fr][1]) + red[2][fr][1]) + red[3][fr][1];
+                const double lo = dft_waves_sum(red, fr, 0);
+                const double hi = dft_waves_sum(red, fr, 1);
                 alpha = VOICEQ_DB * (log(hi) - log(lo));
                 ham = fmax(fmax(red[0][fr][2], red[1][fr][2]), fmax(red[2][fr][2], red[3][fr][2]))
                     - fmax(fmax(red[0][fr][3], red[1][fr][3]), fmax(red[2][fr][3], red[3][fr][3]));
-                sl0 = ((red[0][fr][4] + red[1][fr][4]) + red[2][fr][4]) + red[3][fr][4];
-                sl1 = ((red[0][fr][5] + red[1][fr][5]) + red[2][fr][5]) + red[3][fr][5];
-                const double sumc = ((red2[0][fr][0] + red2[1][fr][0]) + red2[2][fr][0]) + red2[3][fr][0];
-                const double sumf = ((red2[0][fr][1] + red2[1][fr][1]) + red2[2][fr][1]) + red2[3][fr][1];
+                sl0 = dft_waves_sum(red, fr, 4);
+                sl1 = dft_waves_sum(red, fr, 5);
+                const double sumc = dft_waves_sum(red2, fr, 0);
+                const double sumf = dft_waves_sum(red2, fr, 1);
                 cq = red2[0][fr][2];
                 int bi = red2_i[0][fr];
 #pragma unroll

@@ -124,14 +124,11 @@ struct MelBasisW { bool loaded = false; int n_mels = 0, nb = 0; int* span = null
 struct ResamplerW { bool loaded = false; int up = 0, down = 0, n_taps = 0, W = 0, Wp = 0, tab_floats = 0; float* table = nullptr; };
 // Tables of ev_stoi: the analysis window (W), the twiddles (nfft, 2) and the bands (n_bands, 2), float64 / int32 on the device
 struct StoiW { bool loaded = false; int W = 0, H = 0, nfft = 0, n_bands = 0, N = 0, bin_lo = 0, bin_hi = 0; double* win = nullptr; double* tw = nullptr; int32_t* bands = nullptr; };
-// Basis of ev_stft_dist: (W, NB) pairs {w[j] cos, w[j] sin}(2 pi (j + off) k / nfft), float64 on the device; skew: the LDS pad per hop (ev_kernels.h)
-struct StftDistW { bool loaded = false; int W = 0, H = 0, nfft = 0, NB = 0, skew = 0; double2* basis = nullptr; };
+// Basis of ev_stft_dist: (W, NB) pairs {w[j] cos, w[j] sin}(2 pi (j + off) k / nfft), float64 on the device, as the kernels take it (ev_analysis_kernels.h)
+struct StftDistW { bool loaded = false; StftDistTables t{}; };
 // Tables of ev_voice_quality, one device block: ev_stft_dist's basis (W, NB), the cepstral basis (NBp, NQ) g[k] cos(2 pi k q / nfft) / nfft, slope_w
 // (2, NB) and fit_w (NQ); S: the row stride of the log-spectrum in LDS, lds: the launch's dynamic LDS in bytes (ev_analysis_kernels.h)
-struct VoiceQW {
-    bool loaded = false; int W = 0, H = 0, nfft = 0, NB = 0, NBp = 0, NQ = 0, skew = 0, S = 0, q_fit = 0, q_min = 0, q_max = 0; int band[12] = {0};
-    double q_mean = 0.0; size_t lds = 0; double2* basis = nullptr; double* cep = nullptr; double* slope_w = nullptr; double* fit_w = nullptr;
-};
+struct VoiceQW { bool loaded = false; size_t lds = 0; VoiceQTables t{}; };
 
 }  // namespace
 

@@ -20,6 +20,8 @@ POWER_FLOOR = 1e-7
 FS = 22050
 SNR_DB = 20.0
 GEOMETRIES = ((64, 10, 24), (512, 50, 240), (1024, 120, 600), (2048, 240, 1200))      # (nfft, H, W)
+# hops under 4 (the skew walk pads inside a step), a skew of 3 at a hop that is not 2 mod 4, W / 4 = 2 and 1 (the first round's clamp)
+EDGE_GEOMETRIES = ((16, 1, 8), (16, 3, 4))
 RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))                   # audio.MSTFT_RESOLUTIONS: (n_fft, hop, win)
 
 

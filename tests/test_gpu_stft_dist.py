@@ -142,6 +142,12 @@ def test_geometry_against_the_restatement(engines, geom):
     print(f"STFT distance {geom}: sc {np.round(sc, 5).tolist()} log_mag {np.round(lm, 5).tolist()} lsd_db {np.round(lsd, 4).tolist()}")
 
 
+@pytest.mark.parametrize("geom", R.EDGE_GEOMETRIES, ids=[f"{g[0]}-{g[1]}-{g[2]}" for g in R.EDGE_GEOMETRIES])
+def test_edge_geometry_against_the_restatement(engines, geom):
+    """The same check where the skew walk and the K loop take their rare paths: H < 4, a skew of 3, W / 4 = 2 and 1 (under one round of four steps)."""
+    test_geometry_against_the_restatement(engines, geom)
+
+
 # ---- 2. identical signals ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("geom", (SMALL, R.GEOMETRIES[2]), ids=(IDS[0], IDS[2]))
 def test_identical_signals_give_exact_zeros(engines, geom):

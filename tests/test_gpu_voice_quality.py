@@ -152,6 +152,13 @@ def test_geometry_against_the_restatement(engines, g):
     print(f"voice quality {g[:6]}: mean cpp / alpha / hammarberg / slope0 / slope1 over the non-silent frames of each row {means}")
 
 
+@pytest.mark.parametrize("g", R.EDGE_GEOMETRIES, ids=[f"{g.nfft}-{g.H}-{g.W}" for g in R.EDGE_GEOMETRIES])
+def test_edge_geometry_against_the_restatement(engines, g):
+    """The same check where the skew walk and the K loops take their rare paths: H < 4, a skew of 3, W / 4 = 3 and W / 4 = 4 (one whole round), one bin tile (waves
+    1-3 hand over their identities), three phase-2 steps, half a quefrency tile."""
+    test_geometry_against_the_restatement(engines, g)
+
+
 # ---- 2. invariance ----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("g", (SMALL, BIG), ids=(R.IDS[0], R.IDS[3]))
 def test_row_alone_in_a_batch_as_a_prefix_and_without_cepstrum_give_the_same_bits(engines, g):

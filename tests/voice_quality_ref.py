@@ -52,6 +52,10 @@ GEOMETRIES = (
     Geometry(1024, 256, 1024, 22, 36, 340, band_edges(FS, 1024), FS),
 )
 IDS = [f"{g.nfft}-{g.H}-{g.W}" for g in GEOMETRIES]
+# a hop under 4 (the skew walk pads inside a step), a skew of 3 at a hop that is not 2 mod 4, W / 4 = 3 (the first round's clamp) and W / 4 = 4 (one whole round);
+# NB = 9: one bin tile (waves 1-3 hand over their identities), NBp = 12: three phase-2 steps, NQ = 8: half a quefrency tile
+EDGE_BANDS = ((1, 3), (3, 7), (0, 4), (4, 9), (0, 3), (3, 6))
+EDGE_GEOMETRIES = (Geometry(16, 3, 12, 1, 2, 8, EDGE_BANDS, 2000), Geometry(16, 7, 16, 1, 2, 8, EDGE_BANDS, 2000))
 MUTANTS = ("ends2", "fit_from_qmin", "peak_over_fit", "natural_log", "reflect")
 
 

@@ -39,6 +39,7 @@ EXPORTS = [
     "ev_load_stoi", "ev_stoi",
     "ev_load_stft_dist", "ev_stft_dist",
     "ev_load_voice_quality", "ev_voice_quality",
+    "ev_load_formants", "ev_formants",
 ]
 
 
@@ -166,6 +167,8 @@ def load_library() -> C.CDLL:
     lib.ev_stft_dist.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_load_voice_quality.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, C.c_double]
     lib.ev_voice_quality.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
+    lib.ev_load_formants.argtypes = [vp, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, i32]
+    lib.ev_formants.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -560,6 +563,32 @@ class Engine:
         self._check(self.lib.ev_voice_quality(self.h, x.data_ptr(), _ptr(ln), B, L, float(power_floor), frame.data_ptr(), peak.data_ptr(), _ptr(cep),
                                               _stream_ptr()), "ev_voice_quality")
         return frame, peak, cep
+
+    def load_formants(self, window, H: int, order: int, pre_emphasis: float, sr: float, f_lo: float, n_formants: int) -> None:
+        """One geometry of ``formants`` (ev_load_formants): ``window`` (W,) float64 on the host (``audio.formant_window``), ``H`` the hop, the
+        order of the linear prediction, the pre-emphasis coefficient, the rate ``sr`` of the rows in Hz, the band edge ``f_lo`` in Hz (roots at
+        or below f_lo and at or above sr / 2 - f_lo are no formants) and the number of formants kept per frame."""
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float64).reshape(-1))
+        self._check(self.lib.ev_load_formants(self.h, w.ctypes.data, int(w.shape[0]), int(H), int(order), float(pre_emphasis), float(sr), float(f_lo),
+                                              int(n_formants)), "ev_load_formants")
+        self.formants_geometry = (int(w.shape[0]), int(H), int(order), int(n_formants))
+
+    def formants(self, x, lengths, power_floor: float, want_lpc: bool = True):
+        """The formants of every frame of every row of ``x`` (B, L) at the loaded geometry (ev_formants, after load_formants): (lpc (B, NF,
+        order + 2) float64 or None: per frame a_1 .. a_p, the gain and E0; formant (B, NF, n_formants, 2) float64: frequency and bandwidth in
+        Hz, lowest frequency first, zeros past count; count (B, NF) int32: the formants found, -1 where the root finder did not converge) on
+        the device, NF = ceil(L / H).  ``lengths`` (B,): samples per row (None: L)."""
+        if not hasattr(self, "formants_geometry"):
+            raise EvLibraryError("formants: tables not loaded (load_formants)")
+        x, B, L, ln = self._rows(x, lengths, "formants")
+        _, H, order, nform = self.formants_geometry
+        NF = -(-L // H)
+        lpc = torch.empty((B, NF, order + 2), dtype=torch.float64, device=x.device) if want_lpc else None
+        formant = torch.empty((B, NF, nform, 2), dtype=torch.float64, device=x.device)
+        count = torch.empty((B, NF), dtype=torch.int32, device=x.device)
+        self._check(self.lib.ev_formants(self.h, x.data_ptr(), _ptr(ln), B, L, float(power_floor), _ptr(lpc), formant.data_ptr(), count.data_ptr(),
+                                         _stream_ptr()), "ev_formants")
+        return lpc, formant, count
 
     def pyin_observe(self, x, lengths, frame_length: int, hop_length: int, tau_min: int, tau_max: int, sr: float, fmin: float,
                      bins_per_octave: int, n_bins: int, w, boltzmann: float = 2.0, no_trough_prob: float = 0.01, out=None):

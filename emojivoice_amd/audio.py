@@ -957,3 +957,103 @@ def voice_quality_statistics(vq, voiced, lengths=None):
         out["sums"][k] = s
         out[k] = torch.where(count > 0, s / count.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
     return out
+
+
+FORMANT_POWER_FLOOR = 1e-10                        # frames whose windowed, pre-emphasised energy is at or under it are silent: no formants
+
+
+def formant_window(W: int) -> np.ndarray:
+    """Praat's Gaussian analysis window over ``W`` points, float64: (exp(-48 ((j + 0.5) / W - 0.5)^2) - e^-12) / (1 - e^-12)."""
+    j = np.arange(int(W), dtype=np.float64)
+    e = np.exp(-12.0)
+    return (np.exp(-48.0 * ((j + 0.5) / int(W) - 0.5) ** 2) - e) / (1.0 - e)
+
+
+def formant_geometry(sr: int = 22050, max_formant: float = 5500.0, order: Optional[int] = None, frame_length: int = 1024, hop_length: int = 256) -> Dict:
+    """What ``formants`` analyses at: {"d": the integer decimation max(1, floor(sr / (2 max_formant))), "sr": the rate sr / d, "W" =
+    frame_length / d, "H" = hop_length / d, "pre" = exp(-2 pi 50 d / sr) (pre-emphasis from 50 Hz), "order" (2 + round(sr / d / 1000) when
+    None)}.  ``frame_length`` and ``hop_length`` must be multiples of d (ValueError): then ceil(ceil(L / d) / H) = ceil(L / hop_length) and the
+    frames line up one to one with ``pitch_yin``'s and ``voice_quality``'s at the same hop."""
+    if not (sr > 0 and max_formant > 0):
+        raise ValueError(f"formants: sr={sr} and max_formant={max_formant} must be positive")
+    d = max(1, int(math.floor(sr / (2.0 * max_formant))))
+    if int(frame_length) % d or int(hop_length) % d or int(hop_length) < d:
+        raise ValueError(f"formants: frame_length={frame_length} and hop_length={hop_length} must be multiples of the decimation {d} "
+                         f"(sr={sr}, max_formant={max_formant})")
+    rate = float(sr) / d
+    return {"d": d, "sr": rate, "W": int(frame_length) // d, "H": int(hop_length) // d, "pre": math.exp(-2.0 * math.pi * 50.0 * d / float(sr)),
+            "order": 2 + int(round(rate / 1000.0)) if order is None else int(order)}
+
+
+def _formant_engine(device: torch.device, rate: float, W: int, H: int, order: int, n_formants: int, f_lo: float, pre: float) -> Engine:
+    return _cached_engine(device, ("formants", float(rate), int(W), int(H), int(order), int(n_formants), float(f_lo)),
+                          lambda eng: eng.load_formants(formant_window(W), H, order, pre, rate, f_lo, n_formants))
+
+
+@torch.inference_mode()
+def formants(y, sr: int = 22050, max_formant: float = 5500.0, n_formants: int = 4, order: Optional[int] = None, frame_length: int = 1024,
+             hop_length: int = 256, f_lo: float = 50.0, lengths=None, power_floor: float = FORMANT_POWER_FLOOR):
+    """Formants per frame on the device (``ev_formants``; no torch fallback), the way Praat's Burg analysis finds them: the rows are decimated
+    by the integer d = max(1, floor(sr / (2 max_formant))) through ``resample`` (22050 -> 11025 Hz for 5500 Hz), every frame is pre-emphasised
+    from 50 Hz, weighted by ``formant_window`` (frame_length / d points), predicted linearly by Burg's lattice at ``order`` (2 + round(sr / d /
+    1000) when None: 13 at 11025 Hz), and the roots of the prediction polynomial inside f_lo < f < sr / (2 d) - f_lo are the candidates; the
+    ``n_formants`` of lowest frequency are kept, in ascending order.  Frame f is ``pitch_yin``'s and ``voice_quality``'s frame f at the same
+    hop.  No tracking across frames.  ``y`` 1-D, or (B, L) with ``lengths`` (B,) samples or None, on the GPU -> {"frequency", "bandwidth"
+    (B, F, n_formants) float64 Hz, zeros past "count"; "count" (B, F) int32: the formants found (0 on a silent frame and past a row's frames,
+    -1 where the root finder did not converge); "gain" (B, F) float64: the prediction error power per sample; "lpc" (B, F, order) float64:
+    a_1 .. a_p}, F = ceil(L / hop_length); a 1-D input gives B = 1."""
+    _trim_input(y, "formants")
+    g = formant_geometry(sr, max_formant, order, frame_length, hop_length)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    ln = lengths if y.dim() == 2 else None
+    d = g["d"]
+    if d > 1:
+        x = resample(x.float(), d, 1, ln)
+        if ln is not None:
+            ln = -(-torch.as_tensor(ln).to(torch.int64) // d)
+    eng = _formant_engine(y.device, g["sr"], g["W"], g["H"], g["order"], n_formants, f_lo, g["pre"])
+    lpc, fm, count = eng.formants(x, ln, power_floor)
+    p = g["order"]
+    return {"frequency": fm[..., 0], "bandwidth": fm[..., 1], "count": count, "gain": lpc[..., p], "lpc": lpc[..., :p]}
+
+
+@torch.inference_mode()
+def formant_statistics(fm, voiced, lengths=None, max_bandwidth: float = 700.0):
+    """Per utterance, from ``formants`` and a voicing mask at the same hop (``pitch_yin`` / ``pitch_pyin``): {"f1_hz", "f2_hz", "f3_hz",
+    "b1_hz", "b2_hz", "b3_hz": (B,) float64, the means of F_i and of its bandwidth over the frames that are voiced, lie inside ``lengths`` and
+    have count >= 3, leaving out for that i the frames whose F_i has a bandwidth over ``max_bandwidth``; NaN where no frame qualifies; "frames"
+    (B,) int64: the voiced frames with count >= 3; "unconverged_frames" (B,) int64: the frames inside ``lengths`` with count -1; "used" (B, 3)
+    int64: the frames behind each i's means; "sums": the six keys, (B,) float64 sums over those frames, for pooling over utterances}, where
+    ``fm`` lives (torch ops only).  Entries are (B, F, n) / (B, F) or one row without the leading axis; ``lengths`` (B,): the FRAMES that
+    belong to each row (None: F)."""
+    count = torch.as_tensor(fm["count"])
+    voiced = torch.as_tensor(voiced, dtype=torch.bool, device=count.device)
+    freq = torch.as_tensor(fm["frequency"], dtype=torch.float64).to(count.device)
+    band = torch.as_tensor(fm["bandwidth"], dtype=torch.float64).to(count.device)
+    if count.dim() == 1:
+        count, voiced, freq, band = count.unsqueeze(0), voiced.unsqueeze(0), freq.unsqueeze(0), band.unsqueeze(0)
+    B, F = count.shape
+    if voiced.shape != count.shape:
+        raise ValueError(f"formant_statistics: the mask {tuple(voiced.shape)} does not match the figures {tuple(count.shape)}")
+    if freq.shape[:2] != count.shape or freq.shape != band.shape or freq.shape[2] < 3:
+        raise ValueError(f"formant_statistics: frequency and bandwidth must be ({B}, {F}, n >= 3), got {tuple(freq.shape)} and {tuple(band.shape)}")
+    n = torch.full((B,), F, dtype=torch.int64, device=count.device) if lengths is None else torch.as_tensor(lengths).to(count.device, torch.int64)
+    if n.numel() != B:
+        raise ValueError(f"formant_statistics: {B} lengths expected, got {n.numel()}")
+    inside = torch.arange(F, device=count.device)[None, :] < n[:, None]
+    use = voiced & inside & (count >= 3)
+    out = {"frames": use.sum(dim=1), "unconverged_frames": (inside & (count < 0)).sum(dim=1), "sums": {}}
+    used = []
+    for i in range(3):
+        ok = use & (band[:, :, i] <= float(max_bandwidth))
+        k = ok.sum(dim=1)
+        used.append(k)
+        for name, v in ((f"f{i + 1}_hz", freq[:, :, i]), (f"b{i + 1}_hz", band[:, :, i])):
+            s = torch.where(ok, v, torch.zeros_like(v)).sum(dim=1)
+            out["sums"][name] = s
+            out[name] = torch.where(k > 0, s / k.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
+    out["used"] = torch.stack(used, dim=1)
+    return out
+
+
+FORMANT_FIGURES = ("f1_hz", "f2_hz", "f3_hz", "b1_hz", "b2_hz", "b3_hz")

@@ -16,6 +16,8 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --prosody_report clean/filelist.txt                                    # clean/filelist.txt.prosody.json: f0 per file and per speaker
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt                                             # pairs.txt.eval.json: MCD, f0 RMSE, voicing error per 'recorded.wav|synthesised.wav[|spk]'
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt                                      # clean/filelist.txt.voice.json: CPP, alpha ratio, Hammarberg index, spectral slopes per file and per speaker
+    python -m emojivoice_amd.cli --voice_report clean/filelist.txt --formants                           # ... and F1-F3 with their bandwidths (Burg's linear prediction at 11025 Hz), per file and per speaker
+    python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --formants                                  # ... and, per pair, the mean F1-F3 / B1-B3 of both sides and their differences
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --voice_quality                             # ... and, per pair, the voice-quality figures of both sides and their differences
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
@@ -69,6 +71,8 @@ def validate_args(args):
         assert getattr(args, "vocoder_report", None), "--spectral_distance is an option of --vocoder_report"
     if getattr(args, "voice_quality", False):
         assert getattr(args, "evaluate_pairs", None), "--voice_quality is an option of --evaluate_pairs"
+    if getattr(args, "formants", False):
+        assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--formants is an option of --voice_report and of --evaluate_pairs"
     if args.sample_rate is not None:
         assert args.sample_rate > 0, "--sample_rate must be positive"
     if args.prepare_dataset:
@@ -476,6 +480,30 @@ def voice_means(sums, frames):
     return {k: (sums[k] / frames if frames else None) for k in sums}
 
 
+def formant_rows(st):
+    """audio.formant_statistics' result as one host record per row: {"frames", "unconverged", "used": [3 ints], "sums": {figure: float}}."""
+    from . import audio
+
+    frames, unconv, used = st["frames"].cpu(), st["unconverged_frames"].cpu(), st["used"].cpu()
+    sums = {k: st["sums"][k].cpu() for k in audio.FORMANT_FIGURES}
+    return [{"frames": int(frames[r]), "unconverged": int(unconv[r]), "used": [int(v) for v in used[r]], "sums": {k: float(sums[k][r]) for k in sums}}
+            for r in range(frames.shape[0])]
+
+
+def formant_means(rows):
+    """The --formants figures of some rows of formant_rows together: every mean pooled over the frames behind it (the rows' sums over the rows'
+    counts; None without a frame), the frame counts summed."""
+    from . import audio
+
+    out = {}
+    for k in audio.FORMANT_FIGURES:
+        n = sum(r["used"][int(k[1]) - 1] for r in rows)
+        out[k] = math.fsum(r["sums"][k] for r in rows) / n if n else None
+    out["formant_frames"] = sum(r["frames"] for r in rows)
+    out["unconverged_frames"] = sum(r["unconverged"] for r in rows)
+    return out
+
+
 @torch.inference_mode()
 def voice_report(args, device):
     """--voice_report FILELIST (the filelist format of --prosody_report): every file is loaded with audio.load_audio(path, 22050), measured by
@@ -483,9 +511,13 @@ def voice_report(args, device):
     voiced and not silent, --batch_size files at a time.  FILELIST.voice.json receives per file seconds, frames, voiced_frames and the means
     of cpp_db, alpha_ratio_db, hammarberg_db, slope_0_500 and slope_500_1500 (null without such a frame); per speaker and overall the same
     means POOLED over the voiced frames (the files' sums over the files' counts), with the file count.  The figures are comparable across
-    runs of this tool, not to the digit with Praat or VoiceSauce (audio.voice_quality says why)."""
+    runs of this tool, not to the digit with Praat or VoiceSauce (audio.voice_quality says why).
+    --formants adds per file f1_hz .. f3_hz and b1_hz .. b3_hz (audio.formants reduced by audio.formant_statistics over the voiced frames with
+    at least three formants; null without such a frame), formant_frames (those frames) and unconverged_frames; per speaker and overall the
+    means pooled over the frames behind each figure, and both counts summed."""
     from . import audio
 
+    want_formants = getattr(args, "formants", False)
     files, pooled = [], {}
     for chunk, batch, lens in filelist_batches(args.voice_report, args.batch_size, PROSODY_SR, device):
         pitch = pitch_tracker(args)(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
@@ -499,16 +531,22 @@ def voice_report(args, device):
             own = {k: float(sums[k][r]) for k in audio.VOICE_QUALITY_FIGURES}
             files.append({"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r], "voiced_frames": int(count[r]),
                           **voice_means(own, int(count[r]))})
-            acc = pooled.setdefault(spk, {"files": 0, "voiced_frames": 0, "sums": {k: [] for k in audio.VOICE_QUALITY_FIGURES}})
+            acc = pooled.setdefault(spk, {"files": 0, "voiced_frames": 0, "sums": {k: [] for k in audio.VOICE_QUALITY_FIGURES}, "formants": []})
             acc["files"] += 1
             acc["voiced_frames"] += int(count[r])
             for k in own:
                 acc["sums"][k].append(own[k])
+        if want_formants:
+            fs = formant_rows(audio.formant_statistics(audio.formants(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens), pitch["voiced"], n_frames))
+            for r, (_, spk, _) in enumerate(chunk):
+                files[len(files) - len(chunk) + r].update(formant_means([fs[r]]))
+                pooled[spk if spk is not None else "0"]["formants"].append(fs[r])
 
     def pool(accs):
         n = sum(a["voiced_frames"] for a in accs)
         return {"files": sum(a["files"] for a in accs), "voiced_frames": n,
-                **voice_means({k: math.fsum(v for a in accs for v in a["sums"][k]) for k in audio.VOICE_QUALITY_FIGURES}, n)}
+                **voice_means({k: math.fsum(v for a in accs for v in a["sums"][k]) for k in audio.VOICE_QUALITY_FIGURES}, n),
+                **(formant_means([f for a in accs for f in a["formants"]]) if want_formants else {})}
 
     rep = {"sample_rate": PROSODY_SR, "hop_length": PROSODY_HOP, "files": files, "speakers": {k: pool([v]) for k, v in pooled.items()},
            "overall": pool(list(pooled.values()))}
@@ -727,7 +765,9 @@ def evaluate_pairs(args, device):
     too short for a mel (or longer than 4096 frames).  Needs no checkpoint.
     --voice_quality adds per pair "voice": {"recorded", "synthesised", "delta"}: the means of audio.voice_quality's five figures over each
     side's own voiced, non-silent frames and synthesised - recorded (null where a side has no such frame), and per speaker and overall
-    "voice": per figure the mean and the mean absolute value of the deltas.  It compares utterance-level means, so it needs no alignment."""
+    "voice": per figure the mean and the mean absolute value of the deltas.  It compares utterance-level means, so it needs no alignment.
+    --formants adds "formants" in the same form: the means of F1-F3 and B1-B3 (audio.formants, audio.formant_statistics) of each side, their
+    differences, and per speaker and overall the mean and mean absolute difference: a vowel-quality shift, where "voice" shows a tilt shift."""
     from . import audio
 
     entries = parse_pairs(args.evaluate_pairs)
@@ -749,6 +789,10 @@ def evaluate_pairs(args, device):
         if getattr(args, "voice_quality", False):
             st = audio.voice_quality_statistics(audio.voice_quality(sig, sr, hop_length=hop, lengths=lens), pitch["voiced"], frames)
             pitch["voice"] = [{k: (None if math.isnan(float(st[k][r])) else float(st[k][r])) for k in audio.VOICE_QUALITY_FIGURES} for r in range(len(wavs))]
+        if getattr(args, "formants", False):
+            fm = audio.formants(sig, sr, hop_length=hop, lengths=[min(n, sig.shape[1]) for n in lens])
+            pitch["formants"] = [{k: v for k, v in formant_means([row]).items() if k in audio.FORMANT_FIGURES}
+                                 for row in formant_rows(audio.formant_statistics(fm, pitch["voiced"], frames))]
         return cep, frames, pitch
 
     for b0 in range(0, len(entries), args.batch_size):
@@ -778,6 +822,10 @@ def evaluate_pairs(args, device):
                 va, vb = pitch_a["voice"][r], pitch_b["voice"][r]
                 records[-1]["voice"] = {"recorded": va, "synthesised": vb,
                                         "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
+            if "formants" in pitch_a:
+                va, vb = pitch_a["formants"][r], pitch_b["formants"][r]
+                records[-1]["formants"] = {"recorded": va, "synthesised": vb,
+                                           "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
 
     def means(recs):
         out = evaluation_means(recs)
@@ -786,6 +834,11 @@ def evaluate_pairs(args, device):
             for k in audio.VOICE_QUALITY_FIGURES:
                 d = [r["voice"]["delta"][k] for r in recs if r["voice"]["delta"][k] is not None]
                 out["voice"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
+        if getattr(args, "formants", False):
+            out["formants"] = {}
+            for k in audio.FORMANT_FIGURES:
+                d = [r["formants"]["delta"][k] for r in recs if r["formants"]["delta"][k] is not None]
+                out["formants"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
         return out
 
     by_spk = {}
@@ -877,6 +930,9 @@ def cli(argv=None):
                    "(--pitch_method) per file, per speaker and overall (on the device, --batch_size files per batch; needs no checkpoint)")
     p.add_argument("--voice_quality", action="store_true", help="--evaluate_pairs: add \"voice\" per pair (the five voice-quality means of the recording, of the "
                    "synthesis and their differences) and per speaker and overall (mean and mean absolute difference)")
+    p.add_argument("--formants", action="store_true", help="--voice_report: add the mean F1-F3 and their bandwidths B1-B3 in Hz over the voiced frames "
+                   "(Burg's linear prediction at 11025 Hz, Praat's settings; no tracking across frames) per file, per speaker and overall; "
+                   "--evaluate_pairs: add \"formants\" per pair (both sides and their differences) and per speaker and overall")
     args = validate_args(p.parse_args(argv))
     if args.voice_report:
         if not torch.cuda.is_available():

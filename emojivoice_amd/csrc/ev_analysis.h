@@ -1,5 +1,5 @@
 // Host entry points of the analysis side: resampling, dataset statistics, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness,
-// STOI / ESTOI, the STFT distance and voice quality (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
+// STOI / ESTOI, the STFT distance, voice quality and formants (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
 // after ev_handle, fail / HIPCHK / enter, dev_upload, drop_owned, scratch_acquire and launch<>.  None of these calls runs on the engine's conv
 // path; ev_load_mel_basis, ev_mel_spectrogram, ev_denoise and ev_stft_magnitude do, and stay in ev_engine.hip.
 #pragma once
@@ -572,6 +572,72 @@ int ev_voice_quality(ev_handle* h, const float* d_x, const int32_t* d_len, int B
     const int NF = frames_of(L, w.t.H);
     VoiceQParams pv{d_x, d_len, d_frame, d_peak, d_cepstrum, w.t, L, NF, power_floor};
     launch<voice_quality_kernel>(h->device, dim3((unsigned)((NF + 15) / 16), (unsigned)B), dim3(256), w.lds, h->stream, pv);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Formants: Burg's linear prediction, the roots of the prediction polynomial and the formants per frame (formants_kernel, ev_analysis_kernels.h; the
+// definition: include/emojivoice.h).  A load owns one device block, the window; the starting points of the root finder travel in the kernel's
+// arguments; a call needs no arena.
+int ev_load_formants(ev_handle* h, const double* window, int W, int H, int order, double pre_emphasis, double sr, double f_lo, int n_formants) {
+    if (enter(h)) return 1;
+    if (!window) return fail(h, "ev_load_formants: window must be non-null (HOST, W doubles)");
+    if (order < 2 || order > 32) return fail(h, "ev_load_formants: order=%d outside 2 <= order <= 32", order);
+    if (W < 8 || W > 1024 || W <= 2 * order) return fail(h, "ev_load_formants: W=%d outside 8 <= W <= 1024 with W > 2 order = %d", W, 2 * order);
+    if (H < 1 || H > 512) return fail(h, "ev_load_formants: H=%d outside 1 <= H <= 512", H);
+    if (n_formants < 1 || n_formants > 16) return fail(h, "ev_load_formants: n_formants=%d outside 1 <= n_formants <= 16", n_formants);
+    if (!(pre_emphasis >= 0.0 && pre_emphasis < 1.0)) return fail(h, "ev_load_formants: pre_emphasis=%g outside 0 <= pre_emphasis < 1", pre_emphasis);
+    if (!(sr > 0.0) || !std::isfinite(sr)) return fail(h, "ev_load_formants: sr=%g must be positive and finite", sr);
+    if (!(f_lo > 0.0 && f_lo < sr / 4.0)) return fail(h, "ev_load_formants: f_lo=%g outside 0 < f_lo < sr / 4 = %g", f_lo, sr / 4.0);
+    if (check_finite(h, __func__, "window", window, W)) return 1;
+    FormantW w;
+    w.W = W; w.H = H; w.order = order; w.nform = n_formants; w.pre = pre_emphasis; w.sr = sr; w.f_lo = f_lo;
+    w.R = 1;
+    while (64 * w.R < W) w.R *= 2;                                      // 1, 2, 4, 8 or 16 samples per lane
+    for (int i = 0; i < order; ++i) {
+        const double ang = 2.0 * M_PI * (double)i / (double)order + 0.4;
+        w.z0[2 * i] = 0.9 * std::cos(ang); w.z0[2 * i + 1] = 0.9 * std::sin(ang);
+    }
+    void* blk = nullptr;                                                // the new block first: a failed load leaves the tables in use as they are
+    if (hipMalloc(&blk, (size_t)W * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(h, "ev_load_formants: hipMalloc of the window failed"); }
+    if (hipMemcpy(blk, window, (size_t)W * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError(); hipFree(blk);
+        return fail(h, "ev_load_formants: the copy of the window failed");
+    }
+    FormantW& cur = h->fmt;
+    if (cur.loaded) { if (drop_owned(h, {(void*)cur.win})) { hipFree(blk); return 1; } cur = FormantW(); }
+    w.win = (double*)blk;
+    h->owned.push_back(blk);
+    ++h->n_allocs;
+    w.loaded = true;
+    cur = w;
+    return 0;
+}
+
+int ev_formants(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, double power_floor, double* d_lpc, double* d_formant,
+                int32_t* d_count, void* stream) {
+    if (enter(h)) return 1;
+    const FormantW& w = h->fmt;
+    if (!w.loaded) return fail(h, "ev_formants: tables not loaded (ev_load_formants)");
+    if (check_batch(h, __func__, B)) return 1;
+    if (L < 1) return fail(h, "ev_formants: L=%d must be at least 1", L);
+    if (!d_x) return fail(h, "ev_formants: d_x must be non-null");
+    if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_formants: power_floor=%g must be finite and greater than 0", power_floor);
+    if (!d_formant || !d_count) return fail(h, "ev_formants: d_formant and d_count must be non-null");
+    h->stream = (hipStream_t)stream;
+    FormantParams p{};
+    p.x = d_x; p.len = d_len; p.win = w.win; p.lpc = d_lpc; p.formant = d_formant; p.count = d_count;
+    p.L = L; p.NF = frames_of(L, w.H); p.W = w.W; p.H = w.H; p.order = w.order; p.nform = w.nform;
+    p.pre = w.pre; p.floor = power_floor; p.f_scale = w.sr / (2.0 * M_PI); p.bw_scale = w.sr / M_PI; p.f_lo = w.f_lo; p.f_hi = w.sr / 2.0 - w.f_lo;
+    for (int i = 0; i < 64; ++i) p.z0[i] = w.z0[i];
+    const dim3 grid((unsigned)((p.NF - 1) / 4 + 1), (unsigned)B), block(256);
+    switch (w.R) {
+        case 1: launch<formants_kernel<1>>(h->device, grid, block, 0, h->stream, p); break;
+        case 2: launch<formants_kernel<2>>(h->device, grid, block, 0, h->stream, p); break;
+        case 4: launch<formants_kernel<4>>(h->device, grid, block, 0, h->stream, p); break;
+        case 8: launch<formants_kernel<8>>(h->device, grid, block, 0, h->stream, p); break;
+        default: launch<formants_kernel<16>>(h->device, grid, block, 0, h->stream, p); break;
+    }
     HIPCHK(h, hipGetLastError());
     return 0;
 }

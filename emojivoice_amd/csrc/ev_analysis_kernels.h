@@ -1809,3 +1809,176 @@ __global__ __launch_bounds__(256) void voice_quality_kernel(const VoiceQParams p
         pk[fr] = qs;
     }
 }
+
+// ---------------------------------------------------------------------------
+// Formants (ev_formants): per frame the linear prediction of the pre-emphasised, windowed samples by Burg's lattice, the roots of the prediction
+// polynomial by the Aberth-Ehrlich iteration (all at once), and the formants as the roots of the upper half plane inside the band, lowest first
+// (the definition: include/emojivoice.h).  All float64, contraction OFF (STOI_EXACT), no atomics, no scratch, no LDS, no barrier: ONE WAVE PER
+// FRAME, four frames to a workgroup of 256 threads, and everything a frame needs lives in its wave's registers.
+//   samples   lane l holds y[n], n = l R + r for 0 <= r < R, R = the power of two >= ceil(W / 64) (<= 16), read straight from the row (ZEROS outside
+//             [0, len), no reflection); n >= W holds 0 and never takes part.  W < 64: lanes >= ceil(W / R) hold nothing.
+//   Burg      f[R], b[R] in registers; b[n - 1] of a lane's first sample is lane l - 1's last (one __shfl_up).  num and den: the lane adds its
+//             terms in ascending r (terms outside m <= n < W are +0.0), then an xor tree over the 64 lanes (offsets 32 .. 1): every lane ends with
+//             the same bits.  E0 the same way.  Lane i holds a[i]; step m reads a[m - i] by one shuffle.
+//   roots     lane i < p owns z_i (starting points: the host's table in the arguments).  a_1 .. a_p and the other lanes' roots come by wave
+//             broadcasts (__shfl from a uniform lane) in ascending index; P and P' by one complex Horner pass; complex products and quotients
+//             by the textbook formulas ((a c + b d, b c - a d) / (c^2 + d^2) for the quotient).  max |w| is an fmax xor tree.
+//   formants  rank counting: a candidate's slot is the number of candidates below it (of equal f the lower lane first); lane s < n_formants
+//             collects the candidate of rank s and stores slot s, zeros where there is none.
+// Orders are fixed and depend on the frame's own samples and the loaded geometry only.
+struct FormantParams {
+    const float* x; const int32_t* len; const double* win; double* lpc; double* formant; int32_t* count;
+    int L, NF, W, H, order, nform;
+    double pre, floor, f_scale, bw_scale, f_lo, f_hi;                   // f_scale = sr / (2 pi), bw_scale = sr / pi, f_hi = sr / 2 - f_lo
+    double z0[64];                                                      // {re, im} of the starting points 0.9 exp(i (2 pi i / p + 0.4))
+};
+constexpr double FORMANT_STOP = 9.313225746154785e-10;                  // 2^-30
+constexpr int FORMANT_MAX_ITERS = 64;
+
+__device__ __forceinline__ double formant_wave_sum(double v) {
+    STOI_EXACT
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void formants_kernel(const FormantParams p) {
+    STOI_EXACT
+    const int b = blockIdx.y, lane = threadIdx.x & 63, fr = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (fr >= p.NF) return;                                             // (wave-uniform; the kernel has no barrier)
+    const int W = p.W, P = p.order, NFM = p.nform;
+    int n;
+    const int nf = voiceq_frames(p.len, b, p.L, p.H, &n);
+    const size_t fi = (size_t)b * p.NF + fr;
+    double* o_lpc = p.lpc ? p.lpc + fi * (P + 2) : nullptr;
+    double* o_fm = p.formant + fi * NFM * 2;
+    if (fr >= nf) {                                                     // zeros past the row's own frames (and in a row without frames)
+        if (o_lpc && lane < P + 2) o_lpc[lane] = 0.0;
+        if (lane < 2 * NFM) o_fm[lane] = 0.0;
+        if (lane == 0) p.count[fi] = 0;
+        return;
+    }
+    // ---- the windowed, pre-emphasised samples and E0
+    double f[R], bk[R];
+    double e0 = 0.0;
+    {
+        const float* xr = p.x + (size_t)b * p.L;
+        const long long i0 = (long long)fr * p.H + p.H / 2 - W / 2 + (long long)lane * R;
+        long long i = i0 - 1;
+        double prev = i >= 0 && i < n ? (double)xr[i] : 0.0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            i = i0 + r;
+            const int j = lane * R + r;
+            const double s = i >= 0 && i < n ? (double)xr[i] : 0.0;
+            const double y = j < W ? p.win[j] * (s - p.pre * prev) : 0.0;
+            prev = s;
+            f[r] = y; bk[r] = y;
+            e0 = e0 + y * y;
+        }
+        e0 = formant_wave_sum(e0);
+    }
+    if (!(e0 > p.floor)) {                                              // SILENT (uniform): zeros
+        if (o_lpc && lane < P + 2) o_lpc[lane] = 0.0;
+        if (lane < 2 * NFM) o_fm[lane] = 0.0;
+        if (lane == 0) p.count[fi] = 0;
+        return;
+    }
+    // ---- Burg's lattice
+    double a = lane == 0 ? 1.0 : 0.0;                                   // lane i: a[i]
+    double gain = e0 / (double)W;
+    for (int m = 1; m <= P; ++m) {
+        const double up = __shfl_up(bk[R - 1], 1, 64);
+        double bp[R];
+        double num = 0.0, den = 0.0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int j = lane * R + r;
+            const bool on = j >= m && j < W;
+            bp[r] = r == 0 ? up : bk[r - 1];
+            num = num + (on ? f[r] * bp[r] : 0.0);
+            den = den + (on ? f[r] * f[r] + bp[r] * bp[r] : 0.0);
+        }
+        num = -2.0 * formant_wave_sum(num);
+        den = formant_wave_sum(den);
+        const double k = den > 0.0 ? num / den : 0.0;
+#pragma unroll
+        for (int r = R - 1; r >= 0; --r) {
+            const int j = lane * R + r;
+            if (j >= m && j < W) {
+                const double fo = f[r];
+                f[r] = fo + k * bp[r];
+                bk[r] = bp[r] + k * fo;
+            }
+        }
+        const int src = m - lane;
+        const double am = __shfl(a, src >= 0 ? src : 0, 64);
+        if (lane >= 1 && lane <= m) a = a + k * am;
+        gain = gain * (1.0 - k * k);
+    }
+    if (o_lpc) {
+        if (lane >= 1 && lane <= P) o_lpc[lane - 1] = a;
+        if (lane == 0) { o_lpc[P] = gain; o_lpc[P + 1] = e0; }
+    }
+    // ---- the roots: Aberth-Ehrlich, lane i < P owns z_i
+    const bool own = lane < P;
+    double zr = p.z0[2 * (own ? lane : 0)], zi = p.z0[2 * (own ? lane : 0) + 1];
+    int left = -1;
+    bool conv = false;
+    for (int it = 0; it < FORMANT_MAX_ITERS; ++it) {
+        double pr = 1.0, pi = 0.0, dr = 0.0, di = 0.0;                  // P(z), P'(z) by Horner
+        for (int i = 1; i <= P; ++i) {
+            const double ai = __shfl(a, i, 64);
+            const double ndr = (dr * zr - di * zi) + pr, ndi = (dr * zi + di * zr) + pi;
+            const double npr = (pr * zr - pi * zi) + ai, npi = pr * zi + pi * zr;
+            dr = ndr; di = ndi; pr = npr; pi = npi;
+        }
+        const double dd = dr * dr + di * di;
+        const double rr = (pr * dr + pi * di) / dd, ri = (pi * dr - pr * di) / dd;   // r = P / P'
+        double sr = 0.0, si = 0.0;                                      // s = sum_{j != i} 1 / (z_i - z_j)
+        for (int j = 0; j < P; ++j) {
+            const double qr = zr - __shfl(zr, j, 64), qi = zi - __shfl(zi, j, 64);
+            if (j != lane) {
+                const double q2 = qr * qr + qi * qi;
+                sr = sr + qr / q2;
+                si = si - qi / q2;
+            }
+        }
+        const double tr = 1.0 - (rr * sr - ri * si), ti = -(rr * si + ri * sr);      // 1 - r s
+        const double t2 = tr * tr + ti * ti;
+        const double wr = (rr * tr + ri * ti) / t2, wi = (ri * tr - rr * ti) / t2;   // w = r / (1 - r s)
+        zr = zr - wr; zi = zi - wi;
+        double mx = own ? sqrt(wr * wr + wi * wi) : 0.0;
+        const bool bad = own && !(isfinite(zr) && isfinite(zi));
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+        if (__any(bad)) break;                                          // (uniform) UNCONVERGED
+        if (left < 0) { if (mx <= FORMANT_STOP) left = 2; }
+        else if (--left == 0) { conv = true; break; }
+    }
+    if (!conv) {                                                        // UNCONVERGED: the coefficients stay, the formants are zeros
+        if (lane < 2 * NFM) o_fm[lane] = 0.0;
+        if (lane == 0) p.count[fi] = -1;
+        return;
+    }
+    // ---- candidates, ranks, slots
+    const double fq = own ? atan2(zi, zr) * p.f_scale : 0.0;
+    const double bw = own ? -log(sqrt(zr * zr + zi * zi)) * p.bw_scale : 0.0;
+    const bool cand = own && zi > 0.0 && fq > p.f_lo && fq < p.f_hi;
+    int rank = 0, total = 0;
+    for (int j = 0; j < P; ++j) {
+        const double fj = __shfl(fq, j, 64);
+        const int cj = __shfl((int)cand, j, 64);
+        total += cj;
+        if (cj && (fj < fq || (fj == fq && j < lane))) ++rank;
+    }
+    double of = 0.0, ob = 0.0;
+    for (int j = 0; j < P; ++j) {
+        const double fj = __shfl(fq, j, 64), bj = __shfl(bw, j, 64);
+        const int cj = __shfl((int)cand, j, 64), rj = __shfl(rank, j, 64);
+        if (cj && rj == lane) { of = fj; ob = bj; }
+    }
+    if (lane < NFM) { o_fm[2 * lane] = of; o_fm[2 * lane + 1] = ob; }
+    if (lane == 0) p.count[fi] = total < NFM ? total : NFM;
+}

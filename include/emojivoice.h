@@ -43,6 +43,8 @@
  *   ev_stft_dist       <- no counterpart; Yamamoto et al. 2020 (multi-resolution STFT loss) is the model
  *   ev_load_voice_quality <- no counterpart; Eyben et al. 2016 (eGeMAPS) and Hillenbrand et al. 1994 (CPP) are the model
  *   ev_voice_quality   <- no counterpart; Eyben et al. 2016 (eGeMAPS) and Hillenbrand et al. 1994 (CPP) are the model
+ *   ev_load_formants   <- no counterpart; Burg 1975 (maximum-entropy linear prediction), Aberth 1973 / Ehrlich 1967 and Praat's formant analysis are the model
+ *   ev_formants        <- no counterpart; Burg 1975 (maximum-entropy linear prediction), Aberth 1973 / Ehrlich 1967 and Praat's formant analysis are the model
  *   ev_pyin_observe    <- no counterpart; librosa.pyin is the model
  *   ev_pyin_decode     <- no counterpart; librosa.pyin is the model
  *
@@ -82,7 +84,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -666,6 +668,57 @@ int ev_load_voice_quality(ev_handle *h, const double *window /* HOST (W) */, con
                           int q_fit, int q_min, int q_max, const double *fit_w /* HOST (NQ) */, double q_mean);
 int ev_voice_quality(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L, double power_floor /* 1e-7 */,
                      double *d_frame /* (B, NF, 8) */, int32_t *d_peak /* (B, NF) */, double *d_cepstrum /* (B, NF, NQ) or NULL */, void *stream);
+
+/* Formants per frame on the device: the vocal-tract resonances F1 .. Fn with their bandwidths (the other half of the eGeMAPS minimal set; Eyben et
+ * al. 2016), from the linear prediction of every frame by Burg's lattice and the roots of its prediction polynomial, found all at once by the
+ * Aberth-Ehrlich iteration.  ev_load_formants stores one geometry; ev_formants measures.  Everything is float64 (the fp32 samples are widened), the
+ * kernel is compiled with floating-point contraction off; no atomics, no scratch; ev_set_arithmetic does not reach it.  The signal is expected at
+ * twice the highest formant looked for (audio.formants decimates to 11025 Hz for 5500 Hz, as Praat resamples); the window is the caller's (Praat's
+ * Gaussian window in audio.formant_window).  No tracking across frames: every frame stands alone.
+ * Sizes: NF = ceil(L / H); a row of len samples has nf = ceil(len / H) frames, ev_pitch_yin's and ev_voice_quality's.  d_len == NULL: every row is L long.
+ * Definition, per row and frame f, p = order:
+ *   frames(n)  = ceil(n / H)                                   (pitch_yin's and voice_quality's grid)
+ *   s_f[j]     = x[f H + H/2 - W/2 + j],  j = -1 .. W-1,  ZERO outside [0, len)      (no reflection)
+ *   y[j]       = w[j] (s_f[j] - pre * s_f[j-1]),  j = 0 .. W-1                        (float64 from the fp32 samples)
+ *   E0         = sum y[j]^2 ;  a frame with E0 <= power_floor is SILENT: all its outputs are zeros, count 0
+ *   Burg, order p:  f_0 = b_0 = y;  for m = 1 .. p over n = m .. W-1:
+ *       num = -2 sum f_{m-1}[n] b_{m-1}[n-1],  den = sum (f_{m-1}[n]^2 + b_{m-1}[n-1]^2),  k_m = den > 0 ? num / den : 0
+ *       a_m[i] = a_{m-1}[i] + k_m a_{m-1}[m-i] (i = 1 .. m, a[0] = 1, a_{m-1}[m] = 0)
+ *       f_m[n] = f_{m-1}[n] + k_m b_{m-1}[n-1],  b_m[n] = b_{m-1}[n-1] + k_m f_{m-1}[n]
+ *       gain   = (E0 / W) prod (1 - k_m^2)
+ *   roots of P(z) = z^p + a_1 z^(p-1) + ... + a_p by Aberth-Ehrlich, all p at once:
+ *       z_i = 0.9 exp(i (2 pi i / p + 0.4));  per iteration r_i = P(z_i) / P'(z_i) (Horner), s_i = sum_{j != i} 1 / (z_i - z_j),
+ *       w_i = r_i / (1 - r_i s_i),  z_i -= w_i;  once max_i |w_i| <= 2^-30 exactly two more iterations run and the iteration stops;
+ *       more than 64 iterations in all, or any non-finite value: the frame is UNCONVERGED: count -1, formant entries zeros (a_i and gain stay)
+ *   candidates: roots with Im z > 0 and f_lo < f < sr/2 - f_lo,  f = atan2(Im z, Re z) sr / (2 pi),  bw = -ln|z| sr / pi
+ *   formants   = the n_formants candidates of lowest f, ascending;  count = how many there are (0 .. n_formants);  the rest zeros
+ *   Real roots, with or without rounding noise in Im, land at f = 0 or f = sr / 2 (to rounding); the band rule removes them, which is why f_lo > 0.
+ *   d_lpc     (B, NF, p + 2) or NULL: a_1 .. a_p, gain, E0
+ *   d_formant (B, NF, n_formants, 2): {f, bw} in Hz
+ *   d_count   (B, NF) int32
+ *   Frames at or past nf are zeros.
+ * Orders (fixed; they depend on the frame's own samples and the loaded geometry only): with R the power of two >= ceil(W / 64), the sums over n are
+ *   added per c = floor(n / R) in ascending n, then over c by an xor tree over 64 terms (offsets 32, 16, 8, 4, 2, 1; absent terms are +0.0); Horner's
+ *   recurrences and the sum over j run in ascending index; complex products and quotients by the textbook formulas (the quotient a / b as
+ *   a conj(b) / |b|^2), |w| and |z| as sqrt(re^2 + im^2); sr / (2 pi) and sr / pi are formed once on the host; atan2, log and sqrt are the device
+ *   library's float64 ones; the starting points are formed on the host (std::cos, std::sin).
+ * A row with len < 1 or len > L is no error and no out-of-bounds access: all its outputs are zeros.  Nothing at or behind len is read, and nothing
+ * depends on the batch or on L: a row alone, inside a batch, or as the d_len prefix of a longer padded row with anything behind it, a second call,
+ * and a call with d_lpc NULL give the same bits in every output.
+ * Limits of ev_load_formants (HOST window of W doubles), each violation failing with a message that names it: 2 <= order <= 32; 8 <= W <= 1024 and
+ *   W > 2 order; 1 <= H <= 512; 1 <= n_formants <= 16; 0 <= pre_emphasis < 1; sr > 0 and finite; 0 < f_lo < sr / 4; the window finite and non-NULL.
+ *   The load owns one device block, the window, which counts once in ev_alloc_count.  Loading again drops the old block (it waits for the device
+ *   first); a failed load leaves the previous tables in use and the count unchanged.  ev_formants without loaded tables fails with a message.
+ * Limits of ev_formants, each violation failing with a message that names it and writing nothing: 1 <= B <= 65535; L >= 1; power_floor > 0 and
+ *   finite; d_x, d_formant and d_count non-NULL.
+ * Kernel (one launch on `stream`; no host wait, no copy, no arena: a call never allocates): one wavefront per frame, four frames to a workgroup;
+ *   lane l holds the samples l R .. l R + R - 1 of both lattice signals in registers, lane i the coefficient a_i and then the root z_i; no LDS and
+ *   no barrier.  The call is capturable. */
+int ev_load_formants(ev_handle *h, const double *window /* HOST (W) */, int W, int H, int order, double pre_emphasis,
+                     double sr, double f_lo, int n_formants);
+int ev_formants(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L, double power_floor,
+                double *d_lpc /* (B, NF, order + 2): a_1 .. a_p, gain, E0; or NULL */,
+                double *d_formant /* (B, NF, n_formants, 2): Hz, bandwidth Hz */, int32_t *d_count /* (B, NF) */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

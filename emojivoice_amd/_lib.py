@@ -40,6 +40,7 @@ EXPORTS = [
     "ev_load_stft_dist", "ev_stft_dist",
     "ev_load_voice_quality", "ev_voice_quality",
     "ev_load_formants", "ev_formants",
+    "ev_perturbation",
 ]
 
 
@@ -169,6 +170,7 @@ def load_library() -> C.CDLL:
     lib.ev_voice_quality.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_load_formants.argtypes = [vp, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, i32]
     lib.ev_formants.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
+    lib.ev_perturbation.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -589,6 +591,26 @@ class Engine:
         self._check(self.lib.ev_formants(self.h, x.data_ptr(), _ptr(ln), B, L, float(power_floor), _ptr(lpc), formant.data_ptr(), count.data_ptr(),
                                          _stream_ptr()), "ev_formants")
         return lpc, formant, count
+
+    def perturbation(self, x, lengths, lag, hop_length: int, n_cycles: int, corr_length: int, period_factor: float = 1.3,
+                     amplitude_factor: float = 1.6, power_floor: float = 1e-10, want_marks: bool = True):
+        """Jitter, shimmer and the harmonic strength of every frame of every row of ``x`` (B, L) at the lags ``lag`` (B, F) int32 that
+        ``pitch_yin`` wrote (ev_perturbation; no load step): (frame (B, F, 8) float64: local jitter, absolute jitter in samples, local shimmer,
+        shimmer in dB, the harmonic strength r, the mean period, the mean amplitude, RAP; count (B, F, 4) int32: the periods, the counted period
+        pairs, the counted amplitude pairs, the counted triples; marks (B, F, 2 n_cycles + 1) int32 or None: the pitch marks, -1 where there is
+        none) on the device, F = ceil(L / hop_length).  ``lengths`` (B,): samples per row (None: L)."""
+        x, B, L, ln = self._rows(x, lengths, "perturbation")
+        F = -(-L // int(hop_length))
+        if lag.dtype != torch.int32 or tuple(lag.shape) != (B, F) or lag.device != x.device:
+            raise EvLibraryError(f"perturbation: lag must be int32 ({B}, {F}) on {x.device}, got {lag.dtype} {tuple(lag.shape)} on {lag.device}")
+        lag = lag.contiguous()
+        frame = torch.empty((B, F, 8), dtype=torch.float64, device=x.device)
+        count = torch.empty((B, F, 4), dtype=torch.int32, device=x.device)
+        marks = torch.empty((B, F, 2 * int(n_cycles) + 1), dtype=torch.int32, device=x.device) if want_marks and 1 <= int(n_cycles) <= 16 else None
+        self._check(self.lib.ev_perturbation(self.h, x.data_ptr(), _ptr(ln), B, L, int(hop_length), lag.data_ptr(), int(n_cycles), int(corr_length),
+                                             float(period_factor), float(amplitude_factor), float(power_floor), frame.data_ptr(), count.data_ptr(),
+                                             _ptr(marks), _stream_ptr()), "ev_perturbation")
+        return frame, count, marks
 
     def pyin_observe(self, x, lengths, frame_length: int, hop_length: int, tau_min: int, tau_max: int, sr: float, fmin: float,
                      bins_per_octave: int, n_bins: int, w, boltzmann: float = 2.0, no_trough_prob: float = 0.01, out=None):

@@ -1057,3 +1057,74 @@ def formant_statistics(fm, voiced, lengths=None, max_bandwidth: float = 700.0):
 
 
 FORMANT_FIGURES = ("f1_hz", "f2_hz", "f3_hz", "b1_hz", "b2_hz", "b3_hz")
+
+
+PERTURBATION_POWER_FLOOR = 1e-10                   # a correlation whose energies' product is at or under its square gives r = 0
+PERTURBATION_FIGURES = ("jitter_pct", "rap_pct", "shimmer_pct", "shimmer_db", "hnr_db")
+_PERTURBATION_FRAME = ("jitter", "jitter_abs", "shimmer", "shimmer_db", "r", "period", "amplitude", "rap")
+
+
+@torch.inference_mode()
+def perturbation(y, sr: int = 22050, fmin: float = 65.0, fmax: float = 600.0, frame_length: int = 1024, hop_length: int = 256, lengths=None,
+                 lag=None, n_cycles: int = 3, period_factor: float = 1.3, amplitude_factor: float = 1.6,
+                 power_floor: float = PERTURBATION_POWER_FLOOR):
+    """Jitter, shimmer and the harmonic strength per frame on the device (``ev_perturbation``; no torch fallback; Praat's voice report is the
+    model): around the centre of every voiced frame up to ``n_cycles`` pitch marks on each side are picked as waveform peaks one YIN lag apart
+    (within an eighth of it) and refined by a parabola; the periods between them and their amplitudes give the cycle-to-cycle figures, the
+    normalised cross-correlation over ``frame_length`` samples at the lag gives r.  ``lag`` (B, F) int32: the lags of ``Engine.pitch_yin`` at the
+    same hop; None runs YIN on the device (fmin, fmax, frame_length).  ``y`` 1-D, or (B, L) with ``lengths`` (B,) samples or None, on the GPU ->
+    {"jitter" (local, a ratio), "jitter_abs" (samples), "shimmer" (local, a ratio), "shimmer_db", "r", "period" (the mean, samples), "amplitude"
+    (the mean), "rap": (B, F) float64, zeros on unvoiced frames; "count" (B, F, 4) int32: the periods, the counted period pairs, amplitude pairs
+    and triples; "marks" (B, F, 2 n_cycles + 1) int32, -1 where there is none; "lag" (B, F) int32}, F = ceil(L / hop_length)."""
+    _trim_input(y, "perturbation")
+    eng = _trim_engine(y.device)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    ln = lengths if y.dim() == 2 else None
+    if lag is None:
+        tau_min, tau_max = pitch_lag_range(sr, fmin, fmax)
+        lag, _, _ = eng.pitch_yin(x, ln, frame_length, hop_length, tau_min, tau_max, want_period=False, want_cmnd=False)
+    frame, count, marks = eng.perturbation(x, ln, lag, hop_length, n_cycles, frame_length, period_factor, amplitude_factor, power_floor)
+    out = {k: frame[..., i] for i, k in enumerate(_PERTURBATION_FRAME)}
+    out.update(count=count, marks=marks, lag=lag)
+    return out
+
+
+def hnr_db(r):
+    """The harmonics-to-noise ratio in dB of a harmonic strength r (the normalised cross-correlation at the period): 10 log10(r / (1 - r)), r
+    clipped to [1e-6, 1 - 1e-9] (-60 .. 90 dB).  Torch ops only."""
+    r = torch.as_tensor(r, dtype=torch.float64).clamp(1e-6, 1.0 - 1e-9)
+    return 10.0 * torch.log10(r / (1.0 - r))
+
+
+@torch.inference_mode()
+def perturbation_statistics(pt, voiced, lengths=None):
+    """Per utterance, from ``perturbation`` and a voicing mask at the same hop: {"jitter_pct", "rap_pct", "shimmer_pct", "shimmer_db", "hnr_db":
+    (B,) float64, the means of 100 jitter, 100 rap, 100 shimmer, shimmer_db and ``hnr_db``(r) over the frames that are voiced, lie inside
+    ``lengths`` and have at least one counted pair of the figure's kind (period pairs, triples, amplitude pairs; for hnr_db every such voiced
+    frame); NaN where no frame qualifies; "frames" (B,) int64: the voiced frames inside; "used": {figure: (B,) int64, the frames behind its
+    mean}; "sums": {figure: (B,) float64 sums over those frames, for pooling over utterances}}, where ``pt`` lives (torch ops only).  Entries
+    are (B, F) / (B, F, 4) or one row without the leading axis; ``lengths`` (B,): the FRAMES that belong to each row (None: F)."""
+    count = torch.as_tensor(pt["count"])
+    voiced = torch.as_tensor(voiced, dtype=torch.bool, device=count.device)
+    vals = {k: torch.as_tensor(pt[k], dtype=torch.float64).to(count.device) for k in ("jitter", "rap", "shimmer", "shimmer_db", "r")}
+    if count.dim() == 2:
+        count, voiced = count.unsqueeze(0), voiced.unsqueeze(0)
+        vals = {k: v.unsqueeze(0) for k, v in vals.items()}
+    B, F = count.shape[:2]
+    if count.dim() != 3 or count.shape[2] != 4 or voiced.shape != (B, F) or any(v.shape != (B, F) for v in vals.values()):
+        raise ValueError(f"perturbation_statistics: count (B, F, 4), the mask and the figures (B, F) expected, got {tuple(count.shape)}, "
+                         f"{tuple(voiced.shape)} and {[tuple(v.shape) for v in vals.values()]}")
+    n = torch.full((B,), F, dtype=torch.int64, device=count.device) if lengths is None else torch.as_tensor(lengths).to(count.device, torch.int64)
+    if n.numel() != B:
+        raise ValueError(f"perturbation_statistics: {B} lengths expected, got {n.numel()}")
+    use = voiced & (torch.arange(F, device=count.device)[None, :] < n[:, None])
+    out = {"frames": use.sum(dim=1), "used": {}, "sums": {}}
+    for name, v, ok in (("jitter_pct", 100.0 * vals["jitter"], count[..., 1] > 0), ("rap_pct", 100.0 * vals["rap"], count[..., 3] > 0),
+                        ("shimmer_pct", 100.0 * vals["shimmer"], count[..., 2] > 0), ("shimmer_db", vals["shimmer_db"], count[..., 2] > 0),
+                        ("hnr_db", hnr_db(vals["r"]), torch.ones_like(use))):
+        ok = use & ok
+        k = ok.sum(dim=1)
+        s = torch.where(ok, v, torch.zeros_like(v)).sum(dim=1)
+        out["used"][name], out["sums"][name] = k, s
+        out[name] = torch.where(k > 0, s / k.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
+    return out

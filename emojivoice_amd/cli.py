@@ -18,6 +18,8 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt                                      # clean/filelist.txt.voice.json: CPP, alpha ratio, Hammarberg index, spectral slopes per file and per speaker
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt --formants                           # ... and F1-F3 with their bandwidths (Burg's linear prediction at 11025 Hz), per file and per speaker
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --formants                                  # ... and, per pair, the mean F1-F3 / B1-B3 of both sides and their differences
+    python -m emojivoice_amd.cli --voice_report clean/filelist.txt --perturbation                       # ... and jitter, RAP, shimmer and HNR over the voiced frames, per file and per speaker
+    python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --perturbation                              # ... and, per pair, jitter, RAP, shimmer and HNR of both sides and their differences
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --voice_quality                             # ... and, per pair, the voice-quality figures of both sides and their differences
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
@@ -73,6 +75,8 @@ def validate_args(args):
         assert getattr(args, "evaluate_pairs", None), "--voice_quality is an option of --evaluate_pairs"
     if getattr(args, "formants", False):
         assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--formants is an option of --voice_report and of --evaluate_pairs"
+    if getattr(args, "perturbation", False):
+        assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--perturbation is an option of --voice_report and of --evaluate_pairs"
     if args.sample_rate is not None:
         assert args.sample_rate > 0, "--sample_rate must be positive"
     if args.prepare_dataset:
@@ -504,6 +508,38 @@ def formant_means(rows):
     return out
 
 
+def perturbation_rows(st):
+    """audio.perturbation_statistics' result as one host record per row: {"frames", "used": {figure: int}, "sums": {figure: float}}."""
+    from . import audio
+
+    frames = st["frames"].cpu()
+    used = {k: st["used"][k].cpu() for k in audio.PERTURBATION_FIGURES}
+    sums = {k: st["sums"][k].cpu() for k in audio.PERTURBATION_FIGURES}
+    return [{"frames": int(frames[r]), "used": {k: int(used[k][r]) for k in used}, "sums": {k: float(sums[k][r]) for k in sums}}
+            for r in range(frames.shape[0])]
+
+
+def perturbation_means(rows):
+    """The --perturbation figures of some rows of perturbation_rows together: every mean pooled over the frames behind it (the rows' sums over
+    the rows' counts; None without a frame), and perturbation_frames: the voiced frames summed."""
+    from . import audio
+
+    out = {}
+    for k in audio.PERTURBATION_FIGURES:
+        n = sum(r["used"][k] for r in rows)
+        out[k] = math.fsum(r["sums"][k] for r in rows) / n if n else None
+    out["perturbation_frames"] = sum(r["frames"] for r in rows)
+    return out
+
+
+def perturbation_of(batch, sr, hop, lens, voiced, n_frames):
+    """perturbation_rows of a batch: audio.perturbation at YIN's own lags, reduced over the frames that the pitch tracker AND YIN call voiced."""
+    from . import audio
+
+    pt = audio.perturbation(batch, sr, hop_length=hop, lengths=lens)
+    return perturbation_rows(audio.perturbation_statistics(pt, voiced & (pt["lag"] > 0), n_frames))
+
+
 @torch.inference_mode()
 def voice_report(args, device):
     """--voice_report FILELIST (the filelist format of --prosody_report): every file is loaded with audio.load_audio(path, 22050), measured by
@@ -514,10 +550,14 @@ def voice_report(args, device):
     runs of this tool, not to the digit with Praat or VoiceSauce (audio.voice_quality says why).
     --formants adds per file f1_hz .. f3_hz and b1_hz .. b3_hz (audio.formants reduced by audio.formant_statistics over the voiced frames with
     at least three formants; null without such a frame), formant_frames (those frames) and unconverged_frames; per speaker and overall the
-    means pooled over the frames behind each figure, and both counts summed."""
+    means pooled over the frames behind each figure, and both counts summed.
+    --perturbation adds per file jitter_pct, rap_pct, shimmer_pct, shimmer_db and hnr_db (audio.perturbation reduced by
+    audio.perturbation_statistics over the voiced frames; null without a frame that has a counted pair) and perturbation_frames (the voiced
+    frames); per speaker and overall the means pooled over the frames behind each figure, and the count summed."""
     from . import audio
 
     want_formants = getattr(args, "formants", False)
+    want_pert = getattr(args, "perturbation", False)
     files, pooled = [], {}
     for chunk, batch, lens in filelist_batches(args.voice_report, args.batch_size, PROSODY_SR, device):
         pitch = pitch_tracker(args)(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
@@ -531,7 +571,8 @@ def voice_report(args, device):
             own = {k: float(sums[k][r]) for k in audio.VOICE_QUALITY_FIGURES}
             files.append({"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r], "voiced_frames": int(count[r]),
                           **voice_means(own, int(count[r]))})
-            acc = pooled.setdefault(spk, {"files": 0, "voiced_frames": 0, "sums": {k: [] for k in audio.VOICE_QUALITY_FIGURES}, "formants": []})
+            acc = pooled.setdefault(spk, {"files": 0, "voiced_frames": 0, "sums": {k: [] for k in audio.VOICE_QUALITY_FIGURES}, "formants": [],
+                                          "perturbation": []})
             acc["files"] += 1
             acc["voiced_frames"] += int(count[r])
             for k in own:
@@ -541,12 +582,18 @@ def voice_report(args, device):
             for r, (_, spk, _) in enumerate(chunk):
                 files[len(files) - len(chunk) + r].update(formant_means([fs[r]]))
                 pooled[spk if spk is not None else "0"]["formants"].append(fs[r])
+        if want_pert:
+            ps = perturbation_of(batch, PROSODY_SR, PROSODY_HOP, lens, pitch["voiced"], n_frames)
+            for r, (_, spk, _) in enumerate(chunk):
+                files[len(files) - len(chunk) + r].update(perturbation_means([ps[r]]))
+                pooled[spk if spk is not None else "0"]["perturbation"].append(ps[r])
 
     def pool(accs):
         n = sum(a["voiced_frames"] for a in accs)
         return {"files": sum(a["files"] for a in accs), "voiced_frames": n,
                 **voice_means({k: math.fsum(v for a in accs for v in a["sums"][k]) for k in audio.VOICE_QUALITY_FIGURES}, n),
-                **(formant_means([f for a in accs for f in a["formants"]]) if want_formants else {})}
+                **(formant_means([f for a in accs for f in a["formants"]]) if want_formants else {}),
+                **(perturbation_means([f for a in accs for f in a["perturbation"]]) if want_pert else {})}
 
     rep = {"sample_rate": PROSODY_SR, "hop_length": PROSODY_HOP, "files": files, "speakers": {k: pool([v]) for k, v in pooled.items()},
            "overall": pool(list(pooled.values()))}
@@ -767,7 +814,9 @@ def evaluate_pairs(args, device):
     side's own voiced, non-silent frames and synthesised - recorded (null where a side has no such frame), and per speaker and overall
     "voice": per figure the mean and the mean absolute value of the deltas.  It compares utterance-level means, so it needs no alignment.
     --formants adds "formants" in the same form: the means of F1-F3 and B1-B3 (audio.formants, audio.formant_statistics) of each side, their
-    differences, and per speaker and overall the mean and mean absolute difference: a vowel-quality shift, where "voice" shows a tilt shift."""
+    differences, and per speaker and overall the mean and mean absolute difference: a vowel-quality shift, where "voice" shows a tilt shift.
+    --perturbation adds "perturbation" in the same form: jitter_pct, rap_pct, shimmer_pct, shimmer_db and hnr_db (audio.perturbation,
+    audio.perturbation_statistics) of each side and their differences: wobbling periods or a buzzy waveform where pitch and spectrum agree."""
     from . import audio
 
     entries = parse_pairs(args.evaluate_pairs)
@@ -793,6 +842,9 @@ def evaluate_pairs(args, device):
             fm = audio.formants(sig, sr, hop_length=hop, lengths=[min(n, sig.shape[1]) for n in lens])
             pitch["formants"] = [{k: v for k, v in formant_means([row]).items() if k in audio.FORMANT_FIGURES}
                                  for row in formant_rows(audio.formant_statistics(fm, pitch["voiced"], frames))]
+        if getattr(args, "perturbation", False):
+            rows = perturbation_of(sig, sr, hop, [min(n, sig.shape[1]) for n in lens], pitch["voiced"], frames)
+            pitch["perturbation"] = [{k: v for k, v in perturbation_means([row]).items() if k in audio.PERTURBATION_FIGURES} for row in rows]
         return cep, frames, pitch
 
     for b0 in range(0, len(entries), args.batch_size):
@@ -826,6 +878,10 @@ def evaluate_pairs(args, device):
                 va, vb = pitch_a["formants"][r], pitch_b["formants"][r]
                 records[-1]["formants"] = {"recorded": va, "synthesised": vb,
                                            "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
+            if "perturbation" in pitch_a:
+                va, vb = pitch_a["perturbation"][r], pitch_b["perturbation"][r]
+                records[-1]["perturbation"] = {"recorded": va, "synthesised": vb,
+                                               "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
 
     def means(recs):
         out = evaluation_means(recs)
@@ -839,6 +895,11 @@ def evaluate_pairs(args, device):
             for k in audio.FORMANT_FIGURES:
                 d = [r["formants"]["delta"][k] for r in recs if r["formants"]["delta"][k] is not None]
                 out["formants"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
+        if getattr(args, "perturbation", False):
+            out["perturbation"] = {}
+            for k in audio.PERTURBATION_FIGURES:
+                d = [r["perturbation"]["delta"][k] for r in recs if r["perturbation"]["delta"][k] is not None]
+                out["perturbation"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
         return out
 
     by_spk = {}
@@ -933,6 +994,10 @@ def cli(argv=None):
     p.add_argument("--formants", action="store_true", help="--voice_report: add the mean F1-F3 and their bandwidths B1-B3 in Hz over the voiced frames "
                    "(Burg's linear prediction at 11025 Hz, Praat's settings; no tracking across frames) per file, per speaker and overall; "
                    "--evaluate_pairs: add \"formants\" per pair (both sides and their differences) and per speaker and overall")
+    p.add_argument("--perturbation", action="store_true", help="--voice_report: add the mean local jitter, RAP and local shimmer in percent, shimmer in dB "
+                   "and the harmonics-to-noise ratio in dB over the voiced frames (pitch marks by peak picking at YIN's lag, three cycles each side) "
+                   "per file, per speaker and overall; --evaluate_pairs: add \"perturbation\" per pair (both sides and their differences) and per "
+                   "speaker and overall")
     args = validate_args(p.parse_args(argv))
     if args.voice_report:
         if not torch.cuda.is_available():

@@ -642,4 +642,33 @@ int ev_formants(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int
     return 0;
 }
 
+// Perturbation: jitter, shimmer, RAP and the harmonic strength per frame at the lags ev_pitch_yin wrote (perturbation_kernel, ev_analysis_kernels.h;
+// the definition: include/emojivoice.h).  No load step, no tables, no arena: one launch whose arguments carry everything.
+int ev_perturbation(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, int hop_length, const int32_t* d_lag, int n_cycles,
+                    int corr_length, double period_factor, double amplitude_factor, double power_floor, double* d_frame, int32_t* d_count,
+                    int32_t* d_marks, void* stream) {
+    if (enter(h)) return 1;
+    if (check_batch(h, __func__, B)) return 1;
+    if (L < 1) return fail(h, "ev_perturbation: L=%d must be at least 1", L);
+    if (hop_length < 1 || hop_length > 4096) return fail(h, "ev_perturbation: hop_length=%d outside 1 <= hop_length <= 4096", hop_length);
+    if (n_cycles < 1 || n_cycles > 16) return fail(h, "ev_perturbation: n_cycles=%d outside 1 <= n_cycles <= 16", n_cycles);
+    if (corr_length < 8 || corr_length > 4096) return fail(h, "ev_perturbation: corr_length=%d outside 8 <= corr_length <= 4096", corr_length);
+    if (!(period_factor > 1.0) || !std::isfinite(period_factor))
+        return fail(h, "ev_perturbation: period_factor=%g must be finite and greater than 1", period_factor);
+    if (!(amplitude_factor > 1.0) || !std::isfinite(amplitude_factor))
+        return fail(h, "ev_perturbation: amplitude_factor=%g must be finite and greater than 1", amplitude_factor);
+    if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_perturbation: power_floor=%g must be finite and greater than 0", power_floor);
+    if (!d_x) return fail(h, "ev_perturbation: d_x must be non-null");
+    if (!d_lag) return fail(h, "ev_perturbation: d_lag must be non-null");
+    if (!d_frame || !d_count) return fail(h, "ev_perturbation: d_frame and d_count must be non-null");
+    h->stream = (hipStream_t)stream;
+    PerturbParams p{};
+    p.x = d_x; p.len = d_len; p.lag = d_lag; p.frame = d_frame; p.count = d_count; p.marks = d_marks;
+    p.L = L; p.NF = frames_of(L, hop_length); p.H = hop_length; p.nc = n_cycles; p.W = corr_length;
+    p.pf = period_factor; p.af = amplitude_factor; p.floor2 = power_floor * power_floor;
+    launch<perturbation_kernel>(h->device, dim3((unsigned)((p.NF - 1) / 4 + 1), (unsigned)B), dim3(256), 0, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 }  // extern "C"

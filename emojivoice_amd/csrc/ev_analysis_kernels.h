@@ -1982,3 +1982,174 @@ __global__ __launch_bounds__(256) void formants_kernel(const FormantParams p) {
     if (lane < NFM) { o_fm[2 * lane] = of; o_fm[2 * lane + 1] = ob; }
     if (lane == 0) p.count[fi] = total < NFM ? total : NFM;
 }
+
+// ---------------------------------------------------------------------------
+// Perturbation (ev_perturbation): per frame the pitch marks around the frame's centre by peak picking at the frame's YIN lag, jitter, shimmer and RAP
+// from the refined marks, and the harmonic strength as the normalised cross-correlation at that lag (the definition: include/emojivoice.h).  All
+// float64 on widened fp32 samples, contraction OFF (STOI_EXACT), no atomics, no scratch, no LDS, no barrier: ONE WAVE PER FRAME, four frames to a
+// workgroup of 256 threads; samples are read straight from the row.
+//   search    lane l looks at the range's elements l, l + 64, ... in ascending order and keeps its first maximum; a 6-step xor reduction on (value,
+//             offset) prefers the higher value, then the lower offset: every lane ends with the range's lowest-index maximum.  The forward and the
+//             backward chain advance in the same loop, one search each per step.
+//   marks     lane s holds the mark of slot s = n_cycles + k, its refined time and amplitude; periods, pairs and triples come by one shuffle from
+//             the neighbours; every sum is one chain over the slots in ascending order by wave broadcasts (absent and uncounted terms are +0.0,
+//             which changes no bit of a sum of non-negative terms).
+//   r         lane l adds the terms j = l, l + 64, ... < W of E0 and of C and E1 at the three lags in ascending j, one fma per term (the products
+//             of widened fp32 samples are exact), then an xor tree over the 64 lanes (offsets 32 .. 1).
+// Orders are fixed and depend on the frame's own samples and the arguments only.
+struct PerturbParams {
+    const float* x; const int32_t* len; const int32_t* lag; double* frame; int32_t* count; int32_t* marks;
+    int L, NF, H, nc, W;
+    double pf, af, floor2;                                              // floor2 = power_floor^2
+};
+
+__device__ __forceinline__ float perturb_sample(const float* xr, int n, long long i) { return i >= 0 && i < n ? xr[i] : 0.0f; }
+
+// the lowest index of the maximum of x over [a, a + cnt), cnt >= 1; +0 outside [0, n)
+__device__ __forceinline__ long long perturb_argmax(const float* xr, int n, long long a, int cnt, int lane) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int o = lane; o < cnt; o += 64) {
+        const float v = perturb_sample(xr, n, a + o);
+        if (v > bv) { bv = v; bi = o; }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const float ov = __shfl_xor(bv, s, 64);
+        const int oi = __shfl_xor(bi, s, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    return a + bi;
+}
+
+__device__ __forceinline__ bool perturb_accepted(const float* xr, int n, long long m) {
+    const float v = perturb_sample(xr, n, m);
+    return v > 0.0f && v > perturb_sample(xr, n, m - 1) && v >= perturb_sample(xr, n, m + 1);
+}
+
+// the vertex of the parabola through (-1, a), (0, b), (1, c): its offset into *shift, its value returned
+__device__ __forceinline__ double perturb_vertex(double a, double b, double c, double* shift) {
+    STOI_EXACT
+    const double den = (a - 2.0 * b) + c;
+    double s = 0.0;
+    if (den < 0.0) {
+        s = 0.5 * (a - c) / den;
+        if (!(fabs(s) <= 1.0)) s = 0.0;
+    }
+    *shift = s;
+    return b - 0.25 * (a - c) * s;
+}
+
+__global__ __launch_bounds__(256) void perturbation_kernel(const PerturbParams p) {
+    STOI_EXACT
+    const int b = blockIdx.y, lane = threadIdx.x & 63, fr = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (fr >= p.NF) return;                                             // (wave-uniform; the kernel has no barrier)
+    int n;
+    const int nf = voiceq_frames(p.len, b, p.L, p.H, &n);
+    const size_t fi = (size_t)b * p.NF + fr;
+    const int nc = p.nc, NM = 2 * nc + 1;
+    double* o_fr = p.frame + fi * 8;
+    int32_t* o_ct = p.count + fi * 4;
+    int32_t* o_mk = p.marks ? p.marks + fi * NM : nullptr;
+    const int tau0 = fr < nf ? p.lag[fi] : 0;
+    if (tau0 < 16 || tau0 > 2048) {                                     // UNVOICED, or past the row's own frames (uniform)
+        if (lane < 8) o_fr[lane] = 0.0;
+        if (lane < 4) o_ct[lane] = 0;
+        if (o_mk && lane < NM) o_mk[lane] = -1;
+        return;
+    }
+    const float* xr = p.x + (size_t)b * p.L;
+    const long long c = (long long)fr * p.H + p.H / 2;
+    // ---- the marks: lane s keeps the mark of slot s
+    int mine = -1;
+    {
+        const int q = tau0 / 8, lo = tau0 - q, hi = tau0 + q;
+        const long long m0 = perturb_argmax(xr, n, c - tau0 / 2, tau0, lane);
+        if (perturb_accepted(xr, n, m0)) {
+            if (lane == nc) mine = (int)m0;
+            long long mf = m0, mb = m0;
+            bool fa = true, ba = true;
+            for (int k = 1; k <= nc && (fa || ba); ++k) {
+                if (fa) {
+                    mf = perturb_argmax(xr, n, mf + lo, 2 * q + 1, lane);
+                    fa = perturb_accepted(xr, n, mf);
+                    if (fa && lane == nc + k) mine = (int)mf;
+                }
+                if (ba) {
+                    mb = perturb_argmax(xr, n, mb - hi, 2 * q + 1, lane);
+                    ba = perturb_accepted(xr, n, mb);
+                    if (ba && lane == nc - k) mine = (int)mb;
+                }
+            }
+        }
+    }
+    // ---- refined times and amplitudes, periods, pairs and triples
+    const bool has = mine >= 0;
+    double t = 0.0, A = 0.0;
+    if (has) {
+        double shift;
+        A = perturb_vertex((double)perturb_sample(xr, n, (long long)mine - 1), (double)xr[mine], (double)perturb_sample(xr, n, (long long)mine + 1), &shift);
+        t = (double)mine + shift;
+    }
+    // (every shuffle is executed by the whole wave: none sits behind a lane's own condition)
+    const int has_n = __shfl_down((int)has, 1, 64);
+    const bool hasT = has && has_n && lane < 63;                        // slots s and s + 1 both hold a mark: period s
+    const double An = __shfl_down(A, 1, 64), tn = __shfl_down(t, 1, 64);
+    const double T = hasT ? tn - t : 0.0;
+    const double Tn = __shfl_down(T, 1, 64), Tp = __shfl_up(T, 1, 64);
+    const int hasT_n = __shfl_down((int)hasT, 1, 64);
+    const bool pp = hasT && hasT_n && fmax(T, Tn) <= p.pf * fmin(T, Tn);
+    const bool ap = hasT && fmax(A, An) <= p.af * fmin(A, An);
+    const int pp_p = __shfl_up((int)pp, 1, 64);
+    const bool tr = pp && pp_p && lane > 0;                             // the triple centred on period s
+    const double dT = pp ? fabs(T - Tn) : 0.0;
+    const double dA = ap ? fabs(A - An) : 0.0;
+    double dB = 0.0;
+    if (ap) dB = fabs(20.0 * log10(An / A));
+    const double dR = tr ? fabs(T - ((Tp + T) + Tn) / 3.0) : 0.0;
+    const int N = __popcll(__ballot(has)), nT = __popcll(__ballot(hasT)), npp = __popcll(__ballot(pp)), nap = __popcll(__ballot(ap)),
+              ntr = __popcll(__ballot(tr));
+    double sT = 0.0, sA = 0.0, sdT = 0.0, sdA = 0.0, sdB = 0.0, sdR = 0.0;
+    for (int s = 0; s < NM; ++s) {
+        sT = sT + __shfl(T, s, 64);
+        sA = sA + __shfl(A, s, 64);
+        sdT = sdT + __shfl(dT, s, 64);
+        sdA = sdA + __shfl(dA, s, 64);
+        sdB = sdB + __shfl(dB, s, 64);
+        sdR = sdR + __shfl(dR, s, 64);
+    }
+    const double Tmean = nT ? sT / (double)nT : 0.0, Amean = N ? sA / (double)N : 0.0;
+    const double jit_abs = npp ? sdT / (double)npp : 0.0;
+    const double jit = npp ? jit_abs / Tmean : 0.0;
+    const double shim = nap ? sdA / (double)nap / Amean : 0.0;
+    const double shim_db = nap ? sdB / (double)nap : 0.0;
+    const double rap = ntr ? sdR / (double)ntr / Tmean : 0.0;
+    // ---- the harmonic strength
+    double hr;
+    {
+        const int W = p.W;
+        const long long s0 = c - (W + tau0) / 2;
+        double e0 = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0, e10 = 0.0, e11 = 0.0, e12 = 0.0;
+        for (int j = lane; j < W; j += 64) {
+            const long long i = s0 + j;
+            const double u = (double)perturb_sample(xr, n, i);
+            const double v0 = (double)perturb_sample(xr, n, i + tau0 - 1), v1 = (double)perturb_sample(xr, n, i + tau0),
+                         v2 = (double)perturb_sample(xr, n, i + tau0 + 1);
+            e0 = fma(u, u, e0);
+            c0 = fma(u, v0, c0); c1 = fma(u, v1, c1); c2 = fma(u, v2, c2);
+            e10 = fma(v0, v0, e10); e11 = fma(v1, v1, e11); e12 = fma(v2, v2, e12);
+        }
+        e0 = formant_wave_sum(e0);
+        c0 = formant_wave_sum(c0); c1 = formant_wave_sum(c1); c2 = formant_wave_sum(c2);
+        e10 = formant_wave_sum(e10); e11 = formant_wave_sum(e11); e12 = formant_wave_sum(e12);
+        const double p0 = e0 * e10, p1 = e0 * e11, p2 = e0 * e12;
+        const double r0 = p0 > p.floor2 ? c0 / sqrt(p0) : 0.0, r1 = p1 > p.floor2 ? c1 / sqrt(p1) : 0.0, r2 = p2 > p.floor2 ? c2 / sqrt(p2) : 0.0;
+        double shift;
+        hr = perturb_vertex(r0, r1, r2, &shift);
+    }
+    if (lane == 0) {
+        o_fr[0] = jit; o_fr[1] = jit_abs; o_fr[2] = shim; o_fr[3] = shim_db; o_fr[4] = hr; o_fr[5] = Tmean; o_fr[6] = Amean; o_fr[7] = rap;
+        o_ct[0] = nT; o_ct[1] = npp; o_ct[2] = nap; o_ct[3] = ntr;
+    }
+    if (o_mk && lane < NM) o_mk[lane] = mine;
+}

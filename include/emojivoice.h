@@ -45,6 +45,7 @@
  *   ev_voice_quality   <- no counterpart; Eyben et al. 2016 (eGeMAPS) and Hillenbrand et al. 1994 (CPP) are the model
  *   ev_load_formants   <- no counterpart; Burg 1975 (maximum-entropy linear prediction), Aberth 1973 / Ehrlich 1967 and Praat's formant analysis are the model
  *   ev_formants        <- no counterpart; Burg 1975 (maximum-entropy linear prediction), Aberth 1973 / Ehrlich 1967 and Praat's formant analysis are the model
+ *   ev_perturbation    <- no counterpart; Praat's voice report (jitter local / absolute / RAP, shimmer local / dB, cc harmonicity; Boersma 1993) is the model
  *   ev_pyin_observe    <- no counterpart; librosa.pyin is the model
  *   ev_pyin_decode     <- no counterpart; librosa.pyin is the model
  *
@@ -84,7 +85,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -719,6 +720,53 @@ int ev_load_formants(ev_handle *h, const double *window /* HOST (W) */, int W, i
 int ev_formants(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L, double power_floor,
                 double *d_lpc /* (B, NF, order + 2): a_1 .. a_p, gain, E0; or NULL */,
                 double *d_formant /* (B, NF, n_formants, 2): Hz, bandwidth Hz */, int32_t *d_count /* (B, NF) */, void *stream);
+
+/* Jitter, shimmer and the harmonics-to-noise ratio per frame on the device: how regular the voice is from one glottal cycle to the next (the
+ * remaining time-domain members of eGeMAPS; Eyben et al. 2016), on ev_pitch_yin's frame grid and at the lag it wrote.  Everything is float64 on the
+ * widened fp32 samples, the kernel is compiled with floating-point contraction off; no atomics, no scratch; ev_set_arithmetic does not reach it.
+ * H is the hop.  There are F = ceil(L / H) frames per row; a row of len samples has ceil(len / H) of its own.  The centre of frame f is
+ * c = f H + H / 2, ev_pitch_yin's.  Samples outside [0, len) enter as +0.  d_len == NULL: every row is L long.
+ * tau0 = d_lag[b, f] (B, F), the integer lag ev_pitch_yin wrote, read on the device.  A frame with tau0 < 16 or tau0 > 2048 is UNVOICED (0 is the
+ * usual case): zeros in d_frame and d_count, -1 in every mark.
+ * Marks, by peak picking on the raw fp32 samples; every decision is exact, ties go to the lowest index:
+ *   q = tau0 / 8, lo = tau0 - q, hi = tau0 + q                       (integer divisions)
+ *   the anchor m_0 = argmax x[n] over s <= n < s + tau0, s = c - tau0 / 2
+ *   forward m_{k+1} = argmax over [m_k + lo, m_k + hi];  backward m_{k-1} = argmax over [m_k - hi, m_k - lo];  k runs to n_cycles on each side
+ *   a mark is accepted when x[m] > 0, x[m] > x[m - 1] and x[m] >= x[m + 1]; the first mark that is not accepted ends its direction; an anchor that
+ *   is not accepted leaves the frame with no marks.
+ *   (The window is +-1/8 of the period and not wider: with +-1/4 a secondary resonance peak 17 % away was picked on synthetic pulses at 120 Hz.)
+ * Refinement, float64 in this order:  a, b, c = x[m - 1], x[m], x[m + 1];  den = (a - 2 b) + c;  shift = 0.5 (a - c) / den when den < 0 and
+ *   |shift| <= 1, else 0;  t = m + shift;  A = b - 0.25 (a - c) shift.
+ * Periods T_i = t_{i+1} - t_i over consecutive marks, amplitudes A_i over the marks.  A period pair (T_i, T_{i+1}) counts when
+ *   max <= period_factor min, an amplitude pair (A_i, A_{i+1}) when max <= amplitude_factor min, a triple when both of its period pairs count.
+ *   Every sum is a single chain in ascending i.
+ * d_frame[b, f, 0..7] float64:  0 local jitter mean|T_i - T_{i+1}| / Tmean;  1 absolute jitter mean|T_i - T_{i+1}| in samples;  2 local shimmer
+ *   mean|A_i - A_{i+1}| / Amean;  3 shimmer in dB mean|20 log10(A_{i+1} / A_i)|;  4 the harmonic strength r;  5 Tmean over all periods;  6 Amean
+ *   over all marks;  7 RAP mean|T_i - (T_{i-1} + T_i + T_{i+1}) / 3| / Tmean over the counted triples.  The means of 0 .. 3 run over the counted
+ *   pairs; a mean over no terms is 0.
+ * d_count[b, f, 0..3] int32: the periods, the counted period pairs, the counted amplitude pairs, the counted triples.
+ * d_marks[b, f, n_cycles + k] int32 (B, F, 2 n_cycles + 1), may be NULL: m_k, or -1 where there is no mark.
+ * Harmonic strength: the normalised cross-correlation (Praat's "cc" harmonicity; it needs no window correction).  W = corr_length,
+ *   s = c - (W + tau0) / 2, the base is x[s + j], j < W.  For tau in {tau0 - 1, tau0, tau0 + 1}:  C = sum x[s + j] x[s + j + tau],
+ *   E1 = sum x[s + j + tau]^2,  E0 = sum x[s + j]^2,  r(tau) = C / sqrt(E0 E1) when E0 E1 > power_floor^2, else 0.  With a, b, c = r(tau0 - 1),
+ *   r(tau0), r(tau0 + 1) the output is b - 0.25 (a - c) shift under the shift rule above.  HNR in dB is 10 log10(r / (1 - r)).
+ *   Order of the sums: float64, every product of widened fp32 samples (exact), one fma per term; term j belongs to lane j mod 64, a lane adds its
+ *   terms in ascending j, then an xor tree over the 64 lanes (offsets 32, 16, 8, 4, 2, 1; absent terms are +0.0).  power_floor^2 is formed once on
+ *   the host; sqrt and log10 are the device library's float64 ones.
+ * Frames at or past a row's ceil(len / H) are zeros with -1 in the marks; so is every frame of a row with len < 1 or len > L, which is no error and
+ * no out-of-bounds access.  Nothing at or behind len is read, and every order depends on the frame's samples and the arguments only: a row alone,
+ * inside a batch, as the d_len prefix of a longer padded row, a call with d_marks NULL, a second call and a call under every ev_set_arithmetic
+ * setting give the same bits.
+ * Limits, each violation failing with a message that names it and writing nothing: 1 <= B <= 65535; L >= 1; 1 <= hop_length <= 4096;
+ *   1 <= n_cycles <= 16; 8 <= corr_length <= 4096; period_factor and amplitude_factor finite and greater than 1; power_floor finite and greater
+ *   than 0; d_x, d_lag, d_frame and d_count non-NULL.
+ * Kernel (one launch on `stream`; no load step, no host wait, no copy, no arena: ev_alloc_count never moves): one wavefront per frame, four frames to
+ *   a workgroup; a search is a lane-strided read of its range and a 6-step reduction on (value, index); the forward and the backward chain advance
+ *   in one loop; no LDS and no barrier.  The call is capturable. */
+int ev_perturbation(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L, int hop_length,
+                    const int32_t *d_lag /* (B, F) */, int n_cycles, int corr_length, double period_factor /* 1.3 */,
+                    double amplitude_factor /* 1.6 */, double power_floor, double *d_frame /* (B, F, 8) */, int32_t *d_count /* (B, F, 4) */,
+                    int32_t *d_marks /* (B, F, 2 n_cycles + 1) or NULL */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

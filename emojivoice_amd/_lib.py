@@ -41,6 +41,7 @@ EXPORTS = [
     "ev_load_voice_quality", "ev_voice_quality",
     "ev_load_formants", "ev_formants",
     "ev_perturbation",
+    "ev_load_harmonics", "ev_harmonics",
 ]
 
 
@@ -171,6 +172,8 @@ def load_library() -> C.CDLL:
     lib.ev_load_formants.argtypes = [vp, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, i32]
     lib.ev_formants.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_perturbation.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
+    lib.ev_load_harmonics.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, i32, C.c_double, C.c_double, C.c_double]
+    lib.ev_harmonics.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -611,6 +614,53 @@ class Engine:
                                              float(period_factor), float(amplitude_factor), float(power_floor), frame.data_ptr(), count.data_ptr(),
                                              _ptr(marks), _stream_ptr()), "ev_perturbation")
         return frame, count, marks
+
+    def load_harmonics(self, window, twiddle, H: int, nfft: int, sr: float, n_harm: int, search: float = 0.25, min_spacing: float = 4.0,
+                       a3_range: float = 0.1) -> None:
+        """One geometry of ``harmonics`` (ev_load_harmonics), the tables on the host: ``window`` (W,) float64, ``twiddle`` (nfft, 2) float64
+        {cos, sin}(2 pi n / nfft); ``H`` the hop, ``sr`` the rate of the rows in Hz, ``n_harm`` the harmonics kept per frame, ``search`` the half
+        width of a harmonic's search range as a fraction of the spacing, ``min_spacing`` the least harmonic spacing in bins that is resolved,
+        ``a3_range`` the half width of A3's range as a fraction of F3.  The handle builds the windowed DFT basis on the device."""
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float64).reshape(-1))
+        tw = np.ascontiguousarray(np.asarray(twiddle, dtype=np.float64).reshape(-1, 2))
+        if tw.shape[0] != int(nfft):
+            raise ValueError(f"load_harmonics: {nfft} twiddles expected, got {tw.shape[0]}")
+        self._check(self.lib.ev_load_harmonics(self.h, w.ctypes.data, tw.ctypes.data, int(w.shape[0]), int(H), int(nfft), float(sr), int(n_harm),
+                                               float(search), float(min_spacing), float(a3_range)), "ev_load_harmonics")
+        self.harmonics_geometry = (int(w.shape[0]), int(H), int(nfft), int(n_harm))
+
+    def harmonics(self, x, lengths, period, formant=None, fcount=None, power_floor: float = 1e-7, want_harm: bool = True):
+        """The harmonic differences of every frame of every row of ``x`` (B, L) at the loaded geometry (ev_harmonics, after load_harmonics), at
+        the periods ``period`` (B, NF) float32 that ``pitch_yin`` wrote (0: unvoiced) and, when given, the formants ``formant`` (B, NF,
+        n_formants, 2) float64 and ``fcount`` (B, NF) int32 that ``formants`` wrote: (frame (B, NF, 8) float64: per frame {H1-H2, H1-A3, the
+        level of the harmonic at F1, F2, F3 over H1, H1 in dB, H1 in Hz, the harmonic spacing in bins}; count (B, NF, 2) int32: the harmonics
+        measured and the flags; harm (B, NF, n_harm, 2) float64 or None: {Hz, dB} of every harmonic) on the device, NF = ceil(L / H).
+        ``lengths`` (B,): samples per row (None: L)."""
+        if not hasattr(self, "harmonics_geometry"):
+            raise EvLibraryError("harmonics: tables not loaded (load_harmonics)")
+        x, B, L, ln = self._rows(x, lengths, "harmonics")
+        _, H, _, n_harm = self.harmonics_geometry
+        NF = -(-L // H)
+        if period.dtype != torch.float32 or tuple(period.shape) != (B, NF) or period.device != x.device:
+            raise EvLibraryError(f"harmonics: period must be float32 ({B}, {NF}) on {x.device}, got {period.dtype} {tuple(period.shape)} on {period.device}")
+        period = period.contiguous()
+        if (formant is None) != (fcount is None):
+            raise EvLibraryError("harmonics: formant and fcount must both be given or both be None")
+        nform = 0
+        if formant is not None:
+            if (formant.dtype != torch.float64 or formant.dim() != 4 or tuple(formant.shape[:2]) != (B, NF) or formant.shape[3] != 2
+                    or formant.device != x.device):
+                raise EvLibraryError(f"harmonics: formant must be float64 ({B}, {NF}, n_formants, 2) on {x.device}, got {formant.dtype} "
+                                     f"{tuple(formant.shape)} on {formant.device}")
+            if fcount.dtype != torch.int32 or tuple(fcount.shape) != (B, NF) or fcount.device != x.device:
+                raise EvLibraryError(f"harmonics: fcount must be int32 ({B}, {NF}) on {x.device}, got {fcount.dtype} {tuple(fcount.shape)} on {fcount.device}")
+            formant, fcount, nform = formant.contiguous(), fcount.contiguous(), int(formant.shape[2])
+        frame = torch.empty((B, NF, 8), dtype=torch.float64, device=x.device)
+        count = torch.empty((B, NF, 2), dtype=torch.int32, device=x.device)
+        harm = torch.empty((B, NF, n_harm, 2), dtype=torch.float64, device=x.device) if want_harm else None
+        self._check(self.lib.ev_harmonics(self.h, x.data_ptr(), _ptr(ln), B, L, period.data_ptr(), _ptr(formant), _ptr(fcount), nform,
+                                          float(power_floor), frame.data_ptr(), count.data_ptr(), _ptr(harm), _stream_ptr()), "ev_harmonics")
+        return frame, count, harm
 
     def pyin_observe(self, x, lengths, frame_length: int, hop_length: int, tau_min: int, tau_max: int, sr: float, fmin: float,
                      bins_per_octave: int, n_bins: int, w, boltzmann: float = 2.0, no_trough_prob: float = 0.01, out=None):

@@ -1128,3 +1128,105 @@ def perturbation_statistics(pt, voiced, lengths=None):
         out["used"][name], out["sums"][name] = k, s
         out[name] = torch.where(k > 0, s / k.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
     return out
+
+
+HARMONIC_POWER_FLOOR = 1e-7                        # the clamp of |X|^2 before the logarithm, ``voice_quality``'s
+HARMONIC_FIGURES = ("h1_h2_db", "h1_a3_db", "f1_rel_db", "f2_rel_db", "f3_rel_db")
+_HARMONIC_FRAME = HARMONIC_FIGURES + ("h1_db", "h1_hz", "spacing_bins")
+_HARMONIC_FLAG = {"h1_h2_db": 1, "f1_rel_db": 2, "f2_rel_db": 4, "f3_rel_db": 8, "h1_a3_db": 16}
+_HARMONIC_FORMANT = {"f1_rel_db": 0, "f2_rel_db": 1, "f3_rel_db": 2, "h1_a3_db": 2}       # the formant whose bandwidth a figure hangs on
+
+
+def harmonic_arguments(n_harm: int = 48, search: float = 0.25, min_spacing: float = 4.0, a3_range: float = 0.1) -> None:
+    """ValueError unless the comb's parameters are ones ``ev_load_harmonics`` takes: 1 <= n_harm <= 64, 0 < search <= 0.5, min_spacing finite
+    and at least 2, 0 <= a3_range <= 0.5."""
+    if not 1 <= int(n_harm) <= 64:
+        raise ValueError(f"harmonics: n_harm={n_harm} outside 1 <= n_harm <= 64")
+    if not 0.0 < float(search) <= 0.5:
+        raise ValueError(f"harmonics: search={search} outside 0 < search <= 0.5")
+    if not (float(min_spacing) >= 2.0 and math.isfinite(float(min_spacing))):
+        raise ValueError(f"harmonics: min_spacing={min_spacing} must be finite and at least 2")
+    if not 0.0 <= float(a3_range) <= 0.5:
+        raise ValueError(f"harmonics: a3_range={a3_range} outside 0 <= a3_range <= 0.5")
+
+
+_formants = formants                               # (``harmonics`` has an argument of that name)
+
+
+def _harmonics_engine(device: torch.device, sr, n_fft: int, hop: int, n_harm: int, search: float, min_spacing: float, a3_range: float) -> Engine:
+    return _cached_engine(device, ("harmonics", float(sr), int(n_fft), int(hop), int(n_harm), float(search), float(min_spacing), float(a3_range)),
+                          lambda eng: eng.load_harmonics(stft_dist_window(n_fft), stoi_twiddle(n_fft), hop, n_fft, sr, n_harm, search, min_spacing,
+                                                         a3_range))
+
+
+@torch.inference_mode()
+def harmonics(y, sr: int = 22050, fmin: float = 65.0, fmax: float = 600.0, frame_length: int = 1024, hop_length: int = 256, lengths=None,
+              period=None, formants=None, n_harm: int = 48, search: float = 0.25, min_spacing: float = 4.0, a3_range: float = 0.1,
+              power_floor: float = HARMONIC_POWER_FLOOR):
+    """Harmonic differences per frame on the device (``ev_harmonics``; no torch fallback; Hanson 1997 and eGeMAPS, Eyben et al. 2016, are the
+    model): in the float64 log-power spectrum of every voiced frame (``voice_quality``'s: periodic Hann window of ``frame_length`` = n_fft
+    points, zeros outside the row) the harmonics of the frame's YIN period are found as the peaks within ``search`` of the spacing around
+    h nfft / period, refined by a parabola, and give H1-H2, H1-A3 (A3: the strongest harmonic within ``a3_range`` of F3) and the level of the
+    harmonic nearest F1, F2, F3 over H1.  A frame whose harmonics are closer than ``min_spacing`` bins is unresolved and gives zeros.
+    ``period`` (B, F) float32: the periods of ``Engine.pitch_yin`` at the same hop; None runs YIN on the device (fmin, fmax, frame_length).
+    ``formants``: the dict of ``formants`` at the same hop; None runs it; False leaves the formant terms out.  ``y`` 1-D, or (B, L) with
+    ``lengths`` (B,) samples or None, on the GPU -> {"h1_h2_db", "h1_a3_db", "f1_rel_db", "f2_rel_db", "f3_rel_db", "h1_db", "h1_hz",
+    "spacing_bins": (B, F) float64; "n_harmonics" (B, F) int32; "flags" (B, F) int32: bit 0 h1_h2_db, bits 1-3 fi_rel_db, bit 4 h1_a3_db is
+    valid (an entry that is not valid is 0); "harmonic_hz", "harmonic_db" (B, F, n_harm) float64, zeros past n_harmonics}, F = ceil(L /
+    hop_length); a 1-D input gives B = 1.  The levels are not corrected for the formants' gain (no H1*-H2*)."""
+    _trim_input(y, "harmonics")
+    harmonic_arguments(n_harm, search, min_spacing, a3_range)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    ln = lengths if y.dim() == 2 else None
+    if period is None:
+        tau_min, tau_max = pitch_lag_range(sr, fmin, fmax)
+        _, period, _ = _trim_engine(y.device).pitch_yin(x, ln, frame_length, hop_length, tau_min, tau_max, want_lag=False, want_cmnd=False)
+    fm = fc = None
+    if formants is None:
+        formants = _formants(x, sr, frame_length=frame_length, hop_length=hop_length, lengths=ln)
+    if formants is not False:
+        fm = torch.stack((formants["frequency"], formants["bandwidth"]), dim=-1).contiguous()
+        fc = formants["count"]
+    eng = _harmonics_engine(y.device, sr, frame_length, hop_length, n_harm, search, min_spacing, a3_range)
+    frame, count, harm = eng.harmonics(x, ln, period, fm, fc, power_floor)
+    out = {k: frame[..., i] for i, k in enumerate(_HARMONIC_FRAME)}
+    out.update(n_harmonics=count[..., 0], flags=count[..., 1], harmonic_hz=harm[..., 0], harmonic_db=harm[..., 1])
+    return out
+
+
+@torch.inference_mode()
+def harmonic_statistics(hm, voiced, lengths=None, fm=None, max_bandwidth: float = 700.0):
+    """Per utterance, from ``harmonics`` and a voicing mask at the same hop: {"h1_h2_db", "h1_a3_db", "f1_rel_db", "f2_rel_db", "f3_rel_db":
+    (B,) float64, the mean of each figure over the frames that are voiced, lie inside ``lengths`` and carry the figure's flag; with ``fm``
+    (the dict of ``formants`` at the same hop) fi_rel_db also needs F_i's bandwidth, and h1_a3_db F_3's, at or under ``max_bandwidth``; NaN
+    where no frame qualifies; "frames" (B,) int64: the voiced frames inside; "used": {figure: (B,) int64, the frames behind its mean}; "sums":
+    {figure: (B,) float64 sums over those frames, for pooling over utterances}}, where ``hm`` lives (torch ops only).  Entries are (B, F) or
+    one row without the leading axis; ``lengths`` (B,): the FRAMES that belong to each row (None: F)."""
+    flags = torch.as_tensor(hm["flags"])
+    voiced = torch.as_tensor(voiced, dtype=torch.bool, device=flags.device)
+    vals = {k: torch.as_tensor(hm[k], dtype=torch.float64).to(flags.device) for k in HARMONIC_FIGURES}
+    band = None if fm is None else torch.as_tensor(fm["bandwidth"], dtype=torch.float64).to(flags.device)
+    if flags.dim() == 1:
+        flags, voiced = flags.unsqueeze(0), voiced.unsqueeze(0)
+        vals = {k: v.unsqueeze(0) for k, v in vals.items()}
+        band = None if band is None else band.unsqueeze(0)
+    B, F = flags.shape[:2]
+    if flags.dim() != 2 or voiced.shape != (B, F) or any(v.shape != (B, F) for v in vals.values()):
+        raise ValueError(f"harmonic_statistics: flags, the mask and the figures (B, F) expected, got {tuple(flags.shape)}, {tuple(voiced.shape)} "
+                         f"and {[tuple(v.shape) for v in vals.values()]}")
+    if band is not None and (band.dim() != 3 or tuple(band.shape[:2]) != (B, F) or band.shape[2] < 3):
+        raise ValueError(f"harmonic_statistics: the bandwidths must be ({B}, {F}, n >= 3), got {tuple(band.shape)}")
+    n = torch.full((B,), F, dtype=torch.int64, device=flags.device) if lengths is None else torch.as_tensor(lengths).to(flags.device, torch.int64)
+    if n.numel() != B:
+        raise ValueError(f"harmonic_statistics: {B} lengths expected, got {n.numel()}")
+    use = voiced & (torch.arange(F, device=flags.device)[None, :] < n[:, None])
+    out = {"frames": use.sum(dim=1), "used": {}, "sums": {}}
+    for name in HARMONIC_FIGURES:
+        ok = use & ((flags & _HARMONIC_FLAG[name]) != 0)
+        if band is not None and name in _HARMONIC_FORMANT:
+            ok = ok & (band[:, :, _HARMONIC_FORMANT[name]] <= float(max_bandwidth))
+        k = ok.sum(dim=1)
+        s = torch.where(ok, vals[name], torch.zeros_like(vals[name])).sum(dim=1)
+        out["used"][name], out["sums"][name] = k, s
+        out[name] = torch.where(k > 0, s / k.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
+    return out

@@ -20,6 +20,8 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --formants                                  # ... and, per pair, the mean F1-F3 / B1-B3 of both sides and their differences
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt --perturbation                       # ... and jitter, RAP, shimmer and HNR over the voiced frames, per file and per speaker
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --perturbation                              # ... and, per pair, jitter, RAP, shimmer and HNR of both sides and their differences
+    python -m emojivoice_amd.cli --voice_report clean/filelist.txt --harmonics                          # ... and H1-H2, H1-A3 and the harmonic levels at F1-F3 over H1, per file and per speaker
+    python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --harmonics                                 # ... and, per pair, the harmonic differences of both sides and their differences
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --voice_quality                             # ... and, per pair, the voice-quality figures of both sides and their differences
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
@@ -77,6 +79,8 @@ def validate_args(args):
         assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--formants is an option of --voice_report and of --evaluate_pairs"
     if getattr(args, "perturbation", False):
         assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--perturbation is an option of --voice_report and of --evaluate_pairs"
+    if getattr(args, "harmonics", False):
+        assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--harmonics is an option of --voice_report and of --evaluate_pairs"
     if args.sample_rate is not None:
         assert args.sample_rate > 0, "--sample_rate must be positive"
     if args.prepare_dataset:
@@ -540,6 +544,41 @@ def perturbation_of(batch, sr, hop, lens, voiced, n_frames):
     return perturbation_rows(audio.perturbation_statistics(pt, voiced & (pt["lag"] > 0), n_frames))
 
 
+def harmonic_rows(st):
+    """audio.harmonic_statistics' result as one host record per row: {"frames", "used": {figure: int}, "sums": {figure: float}}."""
+    from . import audio
+
+    frames = st["frames"].cpu()
+    used = {k: st["used"][k].cpu() for k in audio.HARMONIC_FIGURES}
+    sums = {k: st["sums"][k].cpu() for k in audio.HARMONIC_FIGURES}
+    return [{"frames": int(frames[r]), "used": {k: int(used[k][r]) for k in used}, "sums": {k: float(sums[k][r]) for k in sums}}
+            for r in range(frames.shape[0])]
+
+
+def harmonic_means(rows):
+    """The --harmonics figures of some rows of harmonic_rows together: every mean pooled over the frames behind it (the rows' sums over the
+    rows' counts; None without a frame), and harmonic_frames: the voiced frames summed."""
+    from . import audio
+
+    out = {}
+    for k in audio.HARMONIC_FIGURES:
+        n = sum(r["used"][k] for r in rows)
+        out[k] = math.fsum(r["sums"][k] for r in rows) / n if n else None
+    out["harmonic_frames"] = sum(r["frames"] for r in rows)
+    return out
+
+
+def harmonics_of(batch, sr, hop, lens, voiced, n_frames, fm=None):
+    """harmonic_rows of a batch: audio.harmonics at YIN's own periods and the formants ``fm`` (None: audio.formants is run), reduced over the
+    frames that the pitch tracker calls voiced and whose figures YIN's period and the formants' bandwidths admit."""
+    from . import audio
+
+    if fm is None:
+        fm = audio.formants(batch, sr, hop_length=hop, lengths=lens)
+    hm = audio.harmonics(batch, sr, hop_length=hop, lengths=lens, formants=fm)
+    return harmonic_rows(audio.harmonic_statistics(hm, voiced, n_frames, fm=fm))
+
+
 @torch.inference_mode()
 def voice_report(args, device):
     """--voice_report FILELIST (the filelist format of --prosody_report): every file is loaded with audio.load_audio(path, 22050), measured by
@@ -553,11 +592,16 @@ def voice_report(args, device):
     means pooled over the frames behind each figure, and both counts summed.
     --perturbation adds per file jitter_pct, rap_pct, shimmer_pct, shimmer_db and hnr_db (audio.perturbation reduced by
     audio.perturbation_statistics over the voiced frames; null without a frame that has a counted pair) and perturbation_frames (the voiced
-    frames); per speaker and overall the means pooled over the frames behind each figure, and the count summed."""
+    frames); per speaker and overall the means pooled over the frames behind each figure, and the count summed.
+    --harmonics adds per file h1_h2_db, h1_a3_db, f1_rel_db, f2_rel_db and f3_rel_db (audio.harmonics reduced by audio.harmonic_statistics over
+    the voiced frames that carry each figure, at formants of at most 700 Hz bandwidth; null without such a frame) and harmonic_frames (the
+    voiced frames); per speaker and overall the means pooled over the frames behind each figure, and the count summed.  With --formants the
+    formants are analysed once for both."""
     from . import audio
 
     want_formants = getattr(args, "formants", False)
     want_pert = getattr(args, "perturbation", False)
+    want_harm = getattr(args, "harmonics", False)
     files, pooled = [], {}
     for chunk, batch, lens in filelist_batches(args.voice_report, args.batch_size, PROSODY_SR, device):
         pitch = pitch_tracker(args)(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
@@ -572,13 +616,14 @@ def voice_report(args, device):
             files.append({"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r], "voiced_frames": int(count[r]),
                           **voice_means(own, int(count[r]))})
             acc = pooled.setdefault(spk, {"files": 0, "voiced_frames": 0, "sums": {k: [] for k in audio.VOICE_QUALITY_FIGURES}, "formants": [],
-                                          "perturbation": []})
+                                          "perturbation": [], "harmonics": []})
             acc["files"] += 1
             acc["voiced_frames"] += int(count[r])
             for k in own:
                 acc["sums"][k].append(own[k])
+        fm = audio.formants(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens) if want_formants else None
         if want_formants:
-            fs = formant_rows(audio.formant_statistics(audio.formants(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens), pitch["voiced"], n_frames))
+            fs = formant_rows(audio.formant_statistics(fm, pitch["voiced"], n_frames))
             for r, (_, spk, _) in enumerate(chunk):
                 files[len(files) - len(chunk) + r].update(formant_means([fs[r]]))
                 pooled[spk if spk is not None else "0"]["formants"].append(fs[r])
@@ -587,13 +632,19 @@ def voice_report(args, device):
             for r, (_, spk, _) in enumerate(chunk):
                 files[len(files) - len(chunk) + r].update(perturbation_means([ps[r]]))
                 pooled[spk if spk is not None else "0"]["perturbation"].append(ps[r])
+        if want_harm:
+            hs = harmonics_of(batch, PROSODY_SR, PROSODY_HOP, lens, pitch["voiced"], n_frames, fm)
+            for r, (_, spk, _) in enumerate(chunk):
+                files[len(files) - len(chunk) + r].update(harmonic_means([hs[r]]))
+                pooled[spk if spk is not None else "0"]["harmonics"].append(hs[r])
 
     def pool(accs):
         n = sum(a["voiced_frames"] for a in accs)
         return {"files": sum(a["files"] for a in accs), "voiced_frames": n,
                 **voice_means({k: math.fsum(v for a in accs for v in a["sums"][k]) for k in audio.VOICE_QUALITY_FIGURES}, n),
                 **(formant_means([f for a in accs for f in a["formants"]]) if want_formants else {}),
-                **(perturbation_means([f for a in accs for f in a["perturbation"]]) if want_pert else {})}
+                **(perturbation_means([f for a in accs for f in a["perturbation"]]) if want_pert else {}),
+                **(harmonic_means([f for a in accs for f in a["harmonics"]]) if want_harm else {})}
 
     rep = {"sample_rate": PROSODY_SR, "hop_length": PROSODY_HOP, "files": files, "speakers": {k: pool([v]) for k, v in pooled.items()},
            "overall": pool(list(pooled.values()))}
@@ -816,7 +867,9 @@ def evaluate_pairs(args, device):
     --formants adds "formants" in the same form: the means of F1-F3 and B1-B3 (audio.formants, audio.formant_statistics) of each side, their
     differences, and per speaker and overall the mean and mean absolute difference: a vowel-quality shift, where "voice" shows a tilt shift.
     --perturbation adds "perturbation" in the same form: jitter_pct, rap_pct, shimmer_pct, shimmer_db and hnr_db (audio.perturbation,
-    audio.perturbation_statistics) of each side and their differences: wobbling periods or a buzzy waveform where pitch and spectrum agree."""
+    audio.perturbation_statistics) of each side and their differences: wobbling periods or a buzzy waveform where pitch and spectrum agree.
+    --harmonics adds "harmonics" in the same form: h1_h2_db, h1_a3_db, f1_rel_db, f2_rel_db and f3_rel_db (audio.harmonics,
+    audio.harmonic_statistics) of each side and their differences: a breathier or a more pressed source where the vowel is the same."""
     from . import audio
 
     entries = parse_pairs(args.evaluate_pairs)
@@ -838,6 +891,7 @@ def evaluate_pairs(args, device):
         if getattr(args, "voice_quality", False):
             st = audio.voice_quality_statistics(audio.voice_quality(sig, sr, hop_length=hop, lengths=lens), pitch["voiced"], frames)
             pitch["voice"] = [{k: (None if math.isnan(float(st[k][r])) else float(st[k][r])) for k in audio.VOICE_QUALITY_FIGURES} for r in range(len(wavs))]
+        fm = None
         if getattr(args, "formants", False):
             fm = audio.formants(sig, sr, hop_length=hop, lengths=[min(n, sig.shape[1]) for n in lens])
             pitch["formants"] = [{k: v for k, v in formant_means([row]).items() if k in audio.FORMANT_FIGURES}
@@ -845,6 +899,9 @@ def evaluate_pairs(args, device):
         if getattr(args, "perturbation", False):
             rows = perturbation_of(sig, sr, hop, [min(n, sig.shape[1]) for n in lens], pitch["voiced"], frames)
             pitch["perturbation"] = [{k: v for k, v in perturbation_means([row]).items() if k in audio.PERTURBATION_FIGURES} for row in rows]
+        if getattr(args, "harmonics", False):
+            rows = harmonics_of(sig, sr, hop, [min(n, sig.shape[1]) for n in lens], pitch["voiced"], frames, fm)
+            pitch["harmonics"] = [{k: v for k, v in harmonic_means([row]).items() if k in audio.HARMONIC_FIGURES} for row in rows]
         return cep, frames, pitch
 
     for b0 in range(0, len(entries), args.batch_size):
@@ -882,6 +939,10 @@ def evaluate_pairs(args, device):
                 va, vb = pitch_a["perturbation"][r], pitch_b["perturbation"][r]
                 records[-1]["perturbation"] = {"recorded": va, "synthesised": vb,
                                                "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
+            if "harmonics" in pitch_a:
+                va, vb = pitch_a["harmonics"][r], pitch_b["harmonics"][r]
+                records[-1]["harmonics"] = {"recorded": va, "synthesised": vb,
+                                            "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
 
     def means(recs):
         out = evaluation_means(recs)
@@ -900,6 +961,11 @@ def evaluate_pairs(args, device):
             for k in audio.PERTURBATION_FIGURES:
                 d = [r["perturbation"]["delta"][k] for r in recs if r["perturbation"]["delta"][k] is not None]
                 out["perturbation"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
+        if getattr(args, "harmonics", False):
+            out["harmonics"] = {}
+            for k in audio.HARMONIC_FIGURES:
+                d = [r["harmonics"]["delta"][k] for r in recs if r["harmonics"]["delta"][k] is not None]
+                out["harmonics"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
         return out
 
     by_spk = {}
@@ -998,6 +1064,10 @@ def cli(argv=None):
                    "and the harmonics-to-noise ratio in dB over the voiced frames (pitch marks by peak picking at YIN's lag, three cycles each side) "
                    "per file, per speaker and overall; --evaluate_pairs: add \"perturbation\" per pair (both sides and their differences) and per "
                    "speaker and overall")
+    p.add_argument("--harmonics", action="store_true", help="--voice_report: add the mean H1-H2, H1-A3 and the level of the harmonic at F1, F2 and F3 "
+                   "over H1 in dB over the voiced frames (the harmonics of YIN's period in the log spectrum, at the formants of --formants) per "
+                   "file, per speaker and overall; --evaluate_pairs: add \"harmonics\" per pair (both sides and their differences) and per speaker "
+                   "and overall")
     args = validate_args(p.parse_args(argv))
     if args.voice_report:
         if not torch.cuda.is_available():

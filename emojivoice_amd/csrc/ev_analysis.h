@@ -1,5 +1,5 @@
 // Host entry points of the analysis side: resampling, dataset statistics, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness,
-// STOI / ESTOI, the STFT distance, voice quality and formants (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
+// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation and harmonic differences (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
 // after ev_handle, fail / HIPCHK / enter, dev_upload, drop_owned, scratch_acquire and launch<>.  None of these calls runs on the engine's conv
 // path; ev_load_mel_basis, ev_mel_spectrogram, ev_denoise and ev_stft_magnitude do, and stay in ev_engine.hip.
 #pragma once
@@ -667,6 +667,65 @@ int ev_perturbation(ev_handle* h, const float* d_x, const int32_t* d_len, int B,
     p.L = L; p.NF = frames_of(L, hop_length); p.H = hop_length; p.nc = n_cycles; p.W = corr_length;
     p.pf = period_factor; p.af = amplitude_factor; p.floor2 = power_floor * power_floor;
     launch<perturbation_kernel>(h->device, dim3((unsigned)((p.NF - 1) / 4 + 1), (unsigned)B), dim3(256), 0, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Harmonic differences: H1-H2, H1-A3 and the harmonic levels at F1, F2, F3 over H1 per frame, at the periods ev_pitch_yin wrote and the formants
+// ev_formants wrote (harmonics_kernel, ev_analysis_kernels.h; the definition: include/emojivoice.h).  One device block per load holds the basis; a
+// call needs no arena.
+int ev_load_harmonics(ev_handle* h, const double* window, const double* twiddle, int W, int H, int nfft, double sr, int n_harm, double search,
+                      double min_spacing, double a3_range) {
+    if (enter(h)) return 1;
+    if (!window || !twiddle) return fail(h, "ev_load_harmonics: window and twiddle must be non-null (HOST)");
+    if (check_dft_geometry(h, __func__, W, H, nfft, 2048)) return 1;
+    if (!(sr > 0.0) || !std::isfinite(sr)) return fail(h, "ev_load_harmonics: sr=%g must be positive and finite", sr);
+    if (n_harm < 1 || n_harm > 64) return fail(h, "ev_load_harmonics: n_harm=%d outside 1 <= n_harm <= 64", n_harm);
+    if (!(search > 0.0 && search <= 0.5)) return fail(h, "ev_load_harmonics: search=%g outside 0 < search <= 0.5", search);
+    if (!(min_spacing >= 2.0) || !std::isfinite(min_spacing)) return fail(h, "ev_load_harmonics: min_spacing=%g must be finite and at least 2", min_spacing);
+    if (!(a3_range >= 0.0 && a3_range <= 0.5)) return fail(h, "ev_load_harmonics: a3_range=%g outside 0 <= a3_range <= 0.5", a3_range);
+    if (check_finite(h, __func__, "window", window, W) || check_finite(h, __func__, "twiddle", twiddle, 2 * nfft)) return 1;
+    HarmW w;
+    HarmTables& t = w.t;
+    t.W = W; t.H = H; t.nfft = nfft; t.NB = nfft / 2 + 1; t.skew = dft_skew(H); t.n_harm = n_harm;
+    t.S = t.NB + ((2 - t.NB) % 32 + 32) % 32;                           // the smallest S >= NB with S = 2 mod 32
+    t.bin_hz = sr / (double)nfft; t.sr = sr; t.search = search; t.min_spacing = min_spacing; t.a3_range = a3_range;
+    // the log-spectrum, the harmonics, the four waves' live counts (64 words), the skewed span
+    w.lds = (size_t)16 * t.S * sizeof(double) + (size_t)16 * n_harm * 2 * sizeof(double) + 64 * sizeof(int32_t)
+          + (size_t)dft_span_words(15 * H + W, H, t.skew) * sizeof(float);
+    if (w.lds > 160 * 1024)
+        return fail(h, "ev_load_harmonics: nfft=%d H=%d W=%d n_harm=%d need %zu bytes of LDS, over 160 KiB", nfft, H, W, n_harm, w.lds);
+    char* blk = nullptr;                                                // the new block first: a failed load leaves the tables in use as they are
+    auto none = [](char*, const double*) { return hipSuccess; };
+    if (build_dft_basis(h, __func__, "basis", window, twiddle, W, nfft, (size_t)W * t.NB * sizeof(double2), &blk, none)) return 1;
+    HarmW& cur = h->harm;
+    if (cur.loaded) { if (drop_owned(h, {(void*)cur.t.basis})) { hipFree(blk); return 1; } cur = HarmW(); }
+    t.basis = (const double2*)blk;
+    h->owned.push_back(blk);
+    ++h->n_allocs;                          // (one block: the basis, 8.4 MB at W = nfft = 1024)
+    w.loaded = true;
+    cur = w;
+    return 0;
+}
+
+int ev_harmonics(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, const float* d_period, const double* d_formant,
+                 const int32_t* d_fcount, int n_formants, double power_floor, double* d_frame, int32_t* d_count, double* d_harm, void* stream) {
+    if (enter(h)) return 1;
+    const HarmW& w = h->harm;
+    if (!w.loaded) return fail(h, "ev_harmonics: tables not loaded (ev_load_harmonics)");
+    if (check_batch(h, __func__, B)) return 1;
+    if (L < 1) return fail(h, "ev_harmonics: L=%d must be at least 1", L);
+    if (L / w.t.H > 0x7fffffef) return fail(h, "ev_harmonics: L=%d at H=%d has more frames than an int32 tile index holds", L, w.t.H);
+    if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_harmonics: power_floor=%g must be finite and greater than 0", power_floor);
+    if (!d_x) return fail(h, "ev_harmonics: d_x must be non-null");
+    if (!d_period) return fail(h, "ev_harmonics: d_period must be non-null");
+    if (!d_frame || !d_count) return fail(h, "ev_harmonics: d_frame and d_count must be non-null");
+    if ((d_formant == nullptr) != (d_fcount == nullptr)) return fail(h, "ev_harmonics: d_formant and d_fcount must both be given or both be null");
+    if (d_formant && (n_formants < 1 || n_formants > 16)) return fail(h, "ev_harmonics: n_formants=%d outside 1 <= n_formants <= 16", n_formants);
+    h->stream = (hipStream_t)stream;
+    const int NF = frames_of(L, w.t.H);
+    HarmParams ph{d_x, d_len, d_period, d_formant, d_fcount, d_frame, d_count, d_harm, w.t, L, NF, d_formant ? n_formants : 0, power_floor};
+    launch<harmonics_kernel>(h->device, dim3((unsigned)((NF + 15) / 16), (unsigned)B), dim3(256), w.lds, h->stream, ph);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -2153,3 +2153,206 @@ __global__ __launch_bounds__(256) void perturbation_kernel(const PerturbParams p
     }
     if (o_mk && lane < NM) o_mk[lane] = mine;
 }
+
+// ---------------------------------------------------------------------------
+// Harmonic differences (ev_harmonics): per frame the levels of the harmonics of the frame's YIN period in ONE float64 log-power spectrum, and from
+// them H1-H2, H1-A3 and the level of the harmonic nearest F1, F2, F3 over H1 (eGeMAPS; Hanson 1997; the definition: include/emojivoice.h).  All
+// float64, contraction OFF (STOI_EXACT), no atomics, no scratch.  One workgroup of 4 waves per (row b, tile of 16 frames f0 .. f0 + 15), on the shared
+// pieces of the float64 DFT GEMM above.  Dynamic LDS: Ld, the tile's log-spectrum (16 frames x S doubles, S = 2 mod 32 as in voice_quality_kernel);
+// Ht, the tile's harmonics (16 frames x n_harm x {f_h, A_h}); the live-bin counts (4 waves x 16 frames); then the tile's raw span, samples
+// f0 H + H / 2 - W / 2 + t for 0 <= t < 15 H + W, staged under the skew with ZEROS outside [0, len) (no reflection).
+// PHASE 1 is voice_quality_kernel's first loop: per bin tile W / 4 steps of two MFMAs (cos, sin), the basis of the next four steps requested ahead.
+// Epilogue per (frame, bin): raw = fma(sm, sm, re re), p = max(raw, floor), Ldb = (10 / ln 10) log(p) to Ld[frame S + bin]; the bins with raw > floor
+// are counted per frame (integers: over the 16 column lanes by an xor tree, over the waves in phase 2).
+// PHASE 2, after one barrier: thread t serves frame t >> 4, and lane j = t & 15 of that frame the harmonics j + 1, j + 17, ...: the range lo .. hi of
+// harmonic h is scanned in ascending k (strictly greater replaces: the lowest k of a tie), the vertex formed and {f_h, A_h} stored to Ht; harmonics
+// that are not measured, and every harmonic of an unvoiced, silent or unresolved frame, are stored as zeros.  A search is one lane's own loop: no
+// cross-lane step, so every order depends on the frame alone.  lo >= 1 and hi <= NB - 2 hold by the limits (v >= min_spacing >= 2, search <= 0.5), so
+// k* - 1 and k* + 1 are bins of the frame; lo is clamped at 1 all the same.
+// BANKS of the scan: the 16 lanes of a frame read different bins of one row, the four frames of a wave rows S apart; the scans are short (2 r + 1
+// bins, r = max(1, search v)) and not conflict-free, which phase 1 (W / 4 x 2 MFMAs per bin tile) hides.
+// PHASE 3, after a second barrier: thread f < 16 forms the frame's eight figures and the flags (the A3 maximum: one ascending loop over at most
+// n_harm terms); all threads copy Ht to d_harm.  Frames >= nf are zeros.
+struct HarmTables { const double2* basis; int W, H, nfft, NB, skew, S, n_harm; double bin_hz, sr, search, min_spacing, a3_range; };
+struct HarmParams {
+    const float* x; const int32_t* len; const float* period; const double* formant; const int32_t* fcount; double* frame; int32_t* count; double* harm;
+    HarmTables t; int L, NF, nform; double floor;
+};
+
+// harmonic h of spacing v is measured: floor(h v + r) <= NB - 2 (compared in float64: h v has no bound)
+__device__ __forceinline__ bool harm_measured(int h, double v, double r, int NB, double* c_out) {
+    STOI_EXACT
+    const double c = (double)h * v;
+    *c_out = c;
+    return floor(c + r) <= (double)(NB - 2);
+}
+
+// the class of frame f of the tile: true when it is voiced (T > 0), not silent and resolved; v is 0 for an unvoiced or silent frame
+__device__ __forceinline__ bool harm_class(const HarmParams& p, const int* live_w, int b, int f0, int f, int nf, double* T_out, double* v_out, double* r_out) {
+    STOI_EXACT
+    double T = 0.0, v = 0.0, r = 0.0;
+    bool comb = false;
+    if (f0 + f < nf) {
+        T = (double)p.period[(size_t)b * p.NF + f0 + f];
+        if (T > 0.0 && live_w[f] + live_w[16 + f] + live_w[32 + f] + live_w[48 + f] > 0) {
+            v = (double)p.t.nfft / T;
+            comb = !(v < p.t.min_spacing);
+            r = fmax(1.0, p.t.search * v);
+        }
+    }
+    *T_out = T; *v_out = v; *r_out = r;
+    return comb;
+}
+
+__global__ __launch_bounds__(256) void harmonics_kernel(const HarmParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double harm_smem[];
+    const int b = blockIdx.y, f0 = blockIdx.x * 16, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int W = p.t.W, H = p.t.H, NB = p.t.NB, skew = p.t.skew, S = p.t.S, NH = p.t.n_harm;
+    int n;
+    const int nf = voiceq_frames(p.len, b, p.L, H, &n);
+    double* out = p.frame + ((size_t)b * p.NF + f0) * 8;
+    int32_t* oc = p.count + ((size_t)b * p.NF + f0) * 2;
+    double* oh = p.harm ? p.harm + ((size_t)b * p.NF + f0) * NH * 2 : nullptr;
+    const int nfr = p.NF - f0 < 16 ? p.NF - f0 : 16;                    // the tile's frames inside the outputs (>= 1)
+    if (f0 >= nf) {                                                     // (uniform) zeros past the row's own frames
+        if (tid < 8 * nfr) out[tid] = 0.0;
+        if (tid < 2 * nfr) oc[tid] = 0;
+        if (oh) for (int i = tid; i < nfr * NH * 2; i += 256) oh[i] = 0.0;
+        return;
+    }
+    double* Ld = harm_smem;                                             // (16, S)
+    double* Ht = Ld + 16 * S;                                           // (16, n_harm, 2)
+    int* live_w = (int*)(Ht + 16 * NH * 2);                             // (4, 16)
+    float* sx = (float*)(live_w + 64);
+    const int span = 15 * H + W;
+    {
+        const float* xr = p.x + (size_t)b * p.L;
+        const long long i0 = (long long)f0 * H + H / 2 - W / 2;
+        for (int t = tid; t < span; t += 256) {
+            const long long i = i0 + t;
+            sx[dft_word(t, H, skew)] = i >= 0 && i < n ? xr[i] : 0.f;
+        }
+    }
+    __syncthreads();
+    {
+        const int r = lane & 15, q = lane >> 4;
+        const int ntile = (NB + 15) >> 4, nsteps = W >> 2;
+        DftSkewWalk walk(r, H, skew);
+        int live[4] = {0, 0, 0, 0};
+        for (int bt = wv; bt < ntile; bt += 4) {
+            const int col = bt * 16 + r, colc = col < NB ? col : NB - 1;
+            const double2* bp = p.t.basis + (size_t)q * NB + colc;
+            stftd_acc xc = {0.0, 0.0, 0.0, 0.0}, xs = xc;
+            walk.start(q);
+            double2 cur[4], nxt[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cur[u] = bp[(size_t)(u < nsteps ? u : nsteps - 1) * 4 * NB];
+            for (int t0 = 0; t0 < nsteps; t0 += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) nxt[u] = bp[(size_t)(t0 + 4 + u < nsteps ? t0 + 4 + u : nsteps - 1) * 4 * NB];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (t0 + u < nsteps) {                              // (uniform)
+                        const double ax = (double)sx[walk.word()];
+                        xc = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].x, xc, 0, 0, 0);
+                        xs = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].y, xs, 0, 0, 0);
+                        walk.step();
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+            }
+            if (col < NB) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double raw = fma(xs[i], xs[i], xc[i] * xc[i]);
+                    Ld[(q + 4 * i) * S + col] = VOICEQ_DB * log(fmax(raw, p.floor));
+                    live[i] += raw > p.floor ? 1 : 0;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) live[i] += __shfl_xor(live[i], o, 64);
+            if (r == 0) live_w[wv * 16 + q + 4 * i] = live[i];
+        }
+    }
+    __syncthreads();                                                    // Ld and the live counts are complete
+    const int fr = tid >> 4, j = tid & 15;
+    {
+        double T, v, rr;
+        const bool comb = harm_class(p, live_w, b, f0, fr, nf, &T, &v, &rr);
+        const double* Lf = Ld + fr * S;
+        double* Hf = Ht + fr * NH * 2;
+        for (int h = j + 1; h <= NH; h += 16) {
+            double fh = 0.0, Ah = 0.0, c;
+            if (comb && harm_measured(h, v, rr, NB, &c)) {
+                int lo = (int)ceil(c - rr);
+                const int hi = (int)floor(c + rr);                      // (<= NB - 2)
+                if (lo < 1) lo = 1;                                     // (never, by the limits)
+                int ks = lo;
+                double best = Lf[lo];
+                for (int k = lo + 1; k <= hi; ++k) {
+                    const double l = Lf[k];
+                    if (l > best) { best = l; ks = k; }
+                }
+                double shift;
+                Ah = perturb_vertex(Lf[ks - 1], best, Lf[ks + 1], &shift);
+                fh = ((double)ks + shift) * p.t.bin_hz;
+            }
+            Hf[2 * (h - 1)] = fh; Hf[2 * (h - 1) + 1] = Ah;
+        }
+    }
+    __syncthreads();                                                    // Ht is complete
+    if (oh) for (int i = tid; i < nfr * NH * 2; i += 256) oh[i] = Ht[i];
+    if (tid < nfr) {
+        const int f = tid;
+        double T, vv, r2;
+        const bool cmb = harm_class(p, live_w, b, f0, f, nf, &T, &vv, &r2);
+        double o[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, vv};
+        int nh = 0, flags = 0;
+        if (cmb) {
+            const double* Hf = Ht + f * NH * 2;
+            double c;
+            while (nh < NH && harm_measured(nh + 1, vv, r2, NB, &c)) ++nh;
+            if (nh >= 1) { o[5] = Hf[1]; o[6] = Hf[0]; }
+            if (nh >= 2) { o[0] = Hf[1] - Hf[3]; flags |= 1; }
+            if (p.formant && nh >= 1) {
+                const double u = p.t.sr / T;
+                const size_t bf = (size_t)b * p.NF + f0 + f;
+                const int fc = p.fcount[bf];
+                const double* Fp = p.formant + bf * p.nform * 2;
+                const int ni = p.nform < 3 ? p.nform : 3;
+#pragma unroll
+                for (int i = 1; i <= 3; ++i) {
+                    if (i > ni || i > fc) continue;
+                    const double F = Fp[2 * (i - 1)];
+                    if (!(F > 0.0)) continue;
+                    const double g = F / u;
+                    const double hd = floor(g + 0.5);
+                    if (hd >= 1.0 && hd <= (double)nh) {
+                        o[1 + i] = Hf[2 * ((int)hd - 1) + 1] - Hf[1];
+                        flags |= 1 << i;
+                    }
+                    if (i == 3) {
+                        const double w = fmax(0.5, p.t.a3_range * g);
+                        const double lod = fmax(1.0, ceil(g - w)), hid = fmin((double)nh, floor(g + w));
+                        if (lod <= hid) {                               // (1 <= lod <= hid <= nh <= 64)
+                            const int l3 = (int)lod, h3 = (int)hid;
+                            double a3 = Hf[2 * (l3 - 1) + 1];
+                            for (int h = l3 + 1; h <= h3; ++h) { const double a = Hf[2 * (h - 1) + 1]; if (a > a3) a3 = a; }
+                            o[1] = Hf[1] - a3;
+                            flags |= 16;
+                        }
+                    }
+                }
+            }
+        }
+        double* of = out + 8 * f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) of[i] = o[i];
+        oc[2 * f] = nh; oc[2 * f + 1] = flags;
+    }
+}

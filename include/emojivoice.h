@@ -46,6 +46,8 @@
  *   ev_load_formants   <- no counterpart; Burg 1975 (maximum-entropy linear prediction), Aberth 1973 / Ehrlich 1967 and Praat's formant analysis are the model
  *   ev_formants        <- no counterpart; Burg 1975 (maximum-entropy linear prediction), Aberth 1973 / Ehrlich 1967 and Praat's formant analysis are the model
  *   ev_perturbation    <- no counterpart; Praat's voice report (jitter local / absolute / RAP, shimmer local / dB, cc harmonicity; Boersma 1993) is the model
+ *   ev_load_harmonics  <- no counterpart; Eyben et al. 2016 and Hanson 1997 are the model
+ *   ev_harmonics       <- no counterpart; Eyben et al. 2016 and Hanson 1997 are the model
  *   ev_pyin_observe    <- no counterpart; librosa.pyin is the model
  *   ev_pyin_decode     <- no counterpart; librosa.pyin is the model
  *
@@ -85,7 +87,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -767,6 +769,59 @@ int ev_perturbation(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *
                     const int32_t *d_lag /* (B, F) */, int n_cycles, int corr_length, double period_factor /* 1.3 */,
                     double amplitude_factor /* 1.6 */, double power_floor, double *d_frame /* (B, F, 8) */, int32_t *d_count /* (B, F, 4) */,
                     int32_t *d_marks /* (B, F, 2 n_cycles + 1) or NULL */, void *stream);
+
+/* Harmonic differences per frame on the device: H1-H2 (the first harmonic over the second: the correlate of open quotient, a breathy against a
+ * pressed voice; Hanson 1997), H1-A3 (the first harmonic over the strongest harmonic in the third formant's range: the source's spectral tilt) and
+ * the level of the harmonic at F1, F2 and F3 over H1 (eGeMAPS's formant relative energy; Eyben et al. 2016), on ev_pitch_yin's frame grid, at the
+ * period it wrote and the formants ev_formants wrote.  ev_load_harmonics stores one geometry; ev_harmonics measures.  Everything is float64 (the
+ * fp32 samples are widened), the kernel is compiled with floating-point contraction off; no atomics, no scratch; ev_set_arithmetic does not reach it.
+ * Sizes: NB = nfft / 2 + 1; NF = ceil(L / H); a row of len samples has nf = ceil(len / H) frames.  d_len == NULL: every row is L long.
+ * Framing and spectrum are ev_voice_quality's: s_j = x[f H + H / 2 - W / 2 + j], zero outside [0, len), no reflection; ev_stft_dist's windowed
+ *   basis on v_mfma_f64_16x16x4_f64;  raw_k = fma(sm, sm, re re),  p_k = max(raw_k, power_floor),  Ldb_k = (10 / ln 10) log(p_k).
+ * Frame classes, in this order.  T = (double)d_period[b, f].  UNVOICED: T is not > 0.  SILENT: no bin has raw_k > power_floor.  UNRESOLVED:
+ *   v = (double)nfft / T < min_spacing (under a Hann window harmonics closer than 4 bins merge).  All three give zeros in d_frame and d_harm and a
+ *   count of 0, except that entry 7 (v) is kept for UNRESOLVED.
+ * Comb.  For h = 1, 2, ...:  c = (double)h v;  r = fmax(1.0, search v);  lo = (int)ceil(c - r), hi = (int)floor(c + r).  Harmonic h is measured
+ *   while hi <= NB - 2 and h <= n_harm; n_h is the number measured.  lo >= 1 follows from min_spacing >= 2 and search <= 0.5.
+ * Peak of one harmonic.  k* = argmax Ldb_k over lo .. hi, the lowest k of a tie;  a, b, c' = Ldb[k* - 1], Ldb[k*], Ldb[k* + 1];
+ *   den = (a - 2 b) + c';  shift = 0.5 (a - c') / den when den < 0 and |shift| <= 1, else 0 (ev_perturbation's vertex rule);
+ *   A_h = b - 0.25 (a - c') shift in dB;  f_h = (k* + shift) (sr / nfft), the quotient sr / nfft formed once on the host.
+ * Formant terms, only with d_formant and d_fcount.  u = sr / T.  For i = 1 .. min(3, n_formants): F_i = d_formant[b, f, i - 1, 0] is valid when
+ *   i <= d_fcount[b, f] and F_i > 0;  g = F_i / u,  h_i = (int)floor(g + 0.5), valid when 1 <= h_i <= n_h;  rel_i = A_{h_i} - A_1.
+ * A3.  g = F_3 / u;  w = fmax(0.5, a3_range g);  the range is max(1, ceil(g - w)) .. min(n_h, floor(g + w));  A3 is the maximum of A_h over it
+ *   (one ascending loop, the lowest h of a tie), valid when F_3 is valid and the range is not empty.
+ * d_frame[b, f, 0..7] float64:  0 H1-H2 = A_1 - A_2;  1 H1-A3 = A_1 - A3;  2, 3, 4 rel_1, rel_2, rel_3;  5 A_1;  6 f_1;  7 v.  An entry whose
+ *   ingredients are not valid is 0.
+ * d_count[b, f, 0..1] int32: n_h and the flags: bit 0 n_h >= 2; bits 1-3 rel_i valid; bit 4 A3 valid.
+ * d_harm[b, f, h - 1, 0..1] float64 (B, NF, n_harm, 2), may be NULL: {f_h, A_h} for h <= n_h, zeros behind.
+ * Frames at or past a row's ceil(len / H) are zeros; so is every frame of a row with len < 1 or len > L, which is no error and no out-of-bounds
+ * access.  Nothing at or behind len is read (of d_x, d_period, d_formant and d_fcount alike), and nothing depends on the batch or on L: a row alone,
+ * inside a batch, as the d_len prefix of a longer padded row, a call with d_harm NULL, a second call, a call under every ev_set_arithmetic setting
+ * and a replay from a captured graph give the same bits; a call with d_formant NULL gives the same entries 0, 5, 6, 7 and bit 0, and zeros in the
+ * formant entries and flags.
+ * Orders: the DFT sums are ev_stft_dist's (one chain of W / 4 matrix steps per bin); a search is one ascending scan by one lane; log is the device
+ *   library's float64 one.
+ * Loading (ev_load_harmonics: host tables, one device block with the basis, counted once in ev_alloc_count; loading again replaces the block after
+ *   waiting for the device; a failed load leaves the previous tables in use and the count unchanged).  ev_harmonics without loaded tables fails with
+ *   a message.  Limits of a load, each violation failing with a message that names it: nfft even, 16 <= nfft <= 2048; W a multiple of 4,
+ *   4 <= W <= nfft, nfft - W even; 1 <= H <= 512; sr positive and finite; 1 <= n_harm <= 64; 0 < search <= 0.5; min_spacing finite and at least 2;
+ *   0 <= a3_range <= 0.5; finite, non-NULL tables; at most 160 KiB of LDS per workgroup: 16 S doubles of log-spectrum (S the smallest number >= NB
+ *   with S = 2 mod 32), the skewed span of 15 H + W floats (at most 3 (16 + W / H) pad words), 16 n_harm 2 doubles of harmonics and 64 words of
+ *   counts.  nfft = 2048 with H = 256 fits up to n_harm = 34; nfft = 2048 with H = 512 does not.
+ * Limits of ev_harmonics, each violation failing with a message that names it and writing nothing: 1 <= B <= 65535; L >= 1 (and L / H below
+ *   2^31 - 16); power_floor finite and greater than 0; d_x, d_period, d_frame and d_count non-NULL; d_formant and d_fcount both NULL or both
+ *   non-NULL, with 1 <= n_formants <= 16 when given.
+ * Kernel (harmonics_kernel: one launch on `stream`, no host wait, no copy, no arena: ev_alloc_count never moves): one workgroup of four waves per
+ *   (row, 16 frames); phase 1 is ev_voice_quality's first matrix product into a log-spectrum in LDS; phase 2, after one barrier, gives each frame 16
+ *   lanes, lane j searching harmonics j + 1, j + 17, ...; phase 3, after a second barrier, forms the figures with one thread per frame.  The call is
+ *   capturable. */
+int ev_load_harmonics(ev_handle *h, const double *window /* HOST (W) */, const double *twiddle /* HOST (nfft, 2) */, int W, int H, int nfft,
+                      double sr, int n_harm, double search /* 0.25 */, double min_spacing /* 4.0 */, double a3_range /* 0.1 */);
+int ev_harmonics(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L,
+                 const float *d_period /* (B, NF): ev_pitch_yin's d_period, 0 = unvoiced */,
+                 const double *d_formant /* (B, NF, n_formants, 2) or NULL */, const int32_t *d_fcount /* (B, NF) or NULL */, int n_formants,
+                 double power_floor, double *d_frame /* (B, NF, 8) */, int32_t *d_count /* (B, NF, 2) */,
+                 double *d_harm /* (B, NF, n_harm, 2) or NULL */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

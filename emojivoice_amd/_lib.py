@@ -42,6 +42,7 @@ EXPORTS = [
     "ev_load_formants", "ev_formants",
     "ev_perturbation",
     "ev_load_harmonics", "ev_harmonics",
+    "ev_functionals",
 ]
 
 
@@ -174,6 +175,7 @@ def load_library() -> C.CDLL:
     lib.ev_perturbation.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     lib.ev_load_harmonics.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, i32, C.c_double, C.c_double, C.c_double]
     lib.ev_harmonics.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, C.c_double, vp, vp, vp, vp]
+    lib.ev_functionals.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -661,6 +663,33 @@ class Engine:
         self._check(self.lib.ev_harmonics(self.h, x.data_ptr(), _ptr(ln), B, L, period.data_ptr(), _ptr(formant), _ptr(fcount), nform,
                                           float(power_floor), frame.data_ptr(), count.data_ptr(), _ptr(harm), _stream_ptr()), "ev_harmonics")
         return frame, count, harm
+
+    def functionals(self, v, mask=None, lengths=None, q=(0.2, 0.5, 0.8)):
+        """The functionals of every contour of ``v`` (B, K, F) float64 on the device (ev_functionals; no load step): (stat (B, K, 12 + NQ)
+        float64: mean, sd, min, max, the mean and sd of the rising and of the falling slopes per frame, the mean and sd length of the runs of
+        valid frames and of the gaps, then the percentile at every ``q``; count (B, K, 8) int32: the valid frames, the dropped (non-finite)
+        ones, the rising parts, the falling parts, the peaks, the runs, the gaps, the adjacent pairs) on the device.  ``mask`` (B, K, F) uint8 or
+        bool beside v, or None: the frames that count; ``lengths`` (B,): frames per row (None: F); ``q``: up to 16 numbers in [0, 1], read on
+        the host during the call.  A statistic over no terms is 0."""
+        if v.dtype != torch.float64 or v.dim() != 3:
+            raise EvLibraryError(f"functionals: v must be float64 (B, K, F), got {v.dtype} {tuple(v.shape)}")
+        v = v.contiguous()
+        B, K, F = v.shape
+        if mask is not None:
+            if tuple(mask.shape) != (B, K, F) or mask.device != v.device or mask.dtype not in (torch.uint8, torch.bool):
+                raise EvLibraryError(f"functionals: mask must be uint8 or bool ({B}, {K}, {F}) on {v.device}, got {mask.dtype} {tuple(mask.shape)} "
+                                     f"on {mask.device}")
+            mask = mask.contiguous()
+        ln = None if lengths is None else torch.as_tensor(lengths).to(v.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"functionals: {B} lengths expected, got {ln.numel()}")
+        qa = np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(-1))
+        NQ = int(qa.shape[0])
+        stat = torch.empty((B, K, 12 + max(min(NQ, 16), 0)), dtype=torch.float64, device=v.device)
+        count = torch.empty((B, K, 8), dtype=torch.int32, device=v.device)
+        self._check(self.lib.ev_functionals(self.h, v.data_ptr(), _ptr(mask), _ptr(ln), B, K, F, qa.ctypes.data if NQ else None, NQ,
+                                            stat.data_ptr(), count.data_ptr(), _stream_ptr()), "ev_functionals")
+        return stat, count
 
     def pyin_observe(self, x, lengths, frame_length: int, hop_length: int, tau_min: int, tau_max: int, sr: float, fmin: float,
                      bins_per_octave: int, n_bins: int, w, boltzmann: float = 2.0, no_trough_prob: float = 0.01, out=None):

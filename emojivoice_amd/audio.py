@@ -929,6 +929,34 @@ def voice_quality(y, sr: int = 22050, fmin: float = 65.0, fmax: float = 600.0, f
     return out
 
 
+# The frames behind each figure of the ``*_statistics`` functions, shared with ``voice_functionals``: ``use`` is voiced and inside the row's length.
+def _voice_quality_mask(peak, use):
+    return use & (peak > 0)
+
+
+def _formant_masks(count, band, use, max_bandwidth: float):
+    """(the voiced frames with at least three formants, per i = 0 .. 2 those of them whose F_i is at most ``max_bandwidth`` wide)."""
+    use = use & (count >= 3)
+    return use, [use & (band[:, :, i] <= float(max_bandwidth)) for i in range(3)]
+
+
+def _perturbation_masks(count, use):
+    """figure -> the frames with a counted pair of the figure's kind (period pairs, triples, amplitude pairs; hnr_db: every frame of ``use``)."""
+    return {"jitter_pct": use & (count[..., 1] > 0), "rap_pct": use & (count[..., 3] > 0), "shimmer_pct": use & (count[..., 2] > 0),
+            "shimmer_db": use & (count[..., 2] > 0), "hnr_db": use & torch.ones_like(use)}
+
+
+def _harmonic_masks(flags, band, use, max_bandwidth: float):
+    """figure -> the frames that carry the figure's flag and, with ``band`` (B, F, n >= 3), whose formant is at most ``max_bandwidth`` wide."""
+    out = {}
+    for name in HARMONIC_FIGURES:
+        ok = use & ((flags & _HARMONIC_FLAG[name]) != 0)
+        if band is not None and name in _HARMONIC_FORMANT:
+            ok = ok & (band[:, :, _HARMONIC_FORMANT[name]] <= float(max_bandwidth))
+        out[name] = ok
+    return out
+
+
 @torch.inference_mode()
 def voice_quality_statistics(vq, voiced, lengths=None):
     """Per utterance, from ``voice_quality`` and a voicing mask at the same hop (``pitch_yin`` / ``pitch_pyin``): {"cpp_db", "alpha_ratio_db",
@@ -947,7 +975,7 @@ def voice_quality_statistics(vq, voiced, lengths=None):
     n = torch.full((B,), F, dtype=torch.int64, device=peak.device) if lengths is None else torch.as_tensor(lengths).to(peak.device, torch.int64)
     if n.numel() != B:
         raise ValueError(f"voice_quality_statistics: {B} lengths expected, got {n.numel()}")
-    use = voiced & (peak > 0) & (torch.arange(F, device=peak.device)[None, :] < n[:, None])
+    use = _voice_quality_mask(peak, voiced & (torch.arange(F, device=peak.device)[None, :] < n[:, None]))
     count = use.sum(dim=1)
     out = {"frames": count, "sums": {}}
     for k in VOICE_QUALITY_FIGURES:
@@ -1041,11 +1069,11 @@ def formant_statistics(fm, voiced, lengths=None, max_bandwidth: float = 700.0):
     if n.numel() != B:
         raise ValueError(f"formant_statistics: {B} lengths expected, got {n.numel()}")
     inside = torch.arange(F, device=count.device)[None, :] < n[:, None]
-    use = voiced & inside & (count >= 3)
+    use, oks = _formant_masks(count, band, voiced & inside, max_bandwidth)
     out = {"frames": use.sum(dim=1), "unconverged_frames": (inside & (count < 0)).sum(dim=1), "sums": {}}
     used = []
     for i in range(3):
-        ok = use & (band[:, :, i] <= float(max_bandwidth))
+        ok = oks[i]
         k = ok.sum(dim=1)
         used.append(k)
         for name, v in ((f"f{i + 1}_hz", freq[:, :, i]), (f"b{i + 1}_hz", band[:, :, i])):
@@ -1096,6 +1124,12 @@ def hnr_db(r):
     return 10.0 * torch.log10(r / (1.0 - r))
 
 
+def _perturbation_values(vals):
+    """figure -> its per-frame values in the report's units, from ``perturbation``'s jitter, rap, shimmer, shimmer_db and r."""
+    return {"jitter_pct": 100.0 * vals["jitter"], "rap_pct": 100.0 * vals["rap"], "shimmer_pct": 100.0 * vals["shimmer"], "shimmer_db": vals["shimmer_db"],
+            "hnr_db": hnr_db(vals["r"])}
+
+
 @torch.inference_mode()
 def perturbation_statistics(pt, voiced, lengths=None):
     """Per utterance, from ``perturbation`` and a voicing mask at the same hop: {"jitter_pct", "rap_pct", "shimmer_pct", "shimmer_db", "hnr_db":
@@ -1119,10 +1153,9 @@ def perturbation_statistics(pt, voiced, lengths=None):
         raise ValueError(f"perturbation_statistics: {B} lengths expected, got {n.numel()}")
     use = voiced & (torch.arange(F, device=count.device)[None, :] < n[:, None])
     out = {"frames": use.sum(dim=1), "used": {}, "sums": {}}
-    for name, v, ok in (("jitter_pct", 100.0 * vals["jitter"], count[..., 1] > 0), ("rap_pct", 100.0 * vals["rap"], count[..., 3] > 0),
-                        ("shimmer_pct", 100.0 * vals["shimmer"], count[..., 2] > 0), ("shimmer_db", vals["shimmer_db"], count[..., 2] > 0),
-                        ("hnr_db", hnr_db(vals["r"]), torch.ones_like(use))):
-        ok = use & ok
+    oks = _perturbation_masks(count, use)
+    for name, v in _perturbation_values(vals).items():
+        ok = oks[name]
         k = ok.sum(dim=1)
         s = torch.where(ok, v, torch.zeros_like(v)).sum(dim=1)
         out["used"][name], out["sums"][name] = k, s
@@ -1221,12 +1254,169 @@ def harmonic_statistics(hm, voiced, lengths=None, fm=None, max_bandwidth: float 
         raise ValueError(f"harmonic_statistics: {B} lengths expected, got {n.numel()}")
     use = voiced & (torch.arange(F, device=flags.device)[None, :] < n[:, None])
     out = {"frames": use.sum(dim=1), "used": {}, "sums": {}}
+    oks = _harmonic_masks(flags, band, use, max_bandwidth)
     for name in HARMONIC_FIGURES:
-        ok = use & ((flags & _HARMONIC_FLAG[name]) != 0)
-        if band is not None and name in _HARMONIC_FORMANT:
-            ok = ok & (band[:, :, _HARMONIC_FORMANT[name]] <= float(max_bandwidth))
+        ok = oks[name]
         k = ok.sum(dim=1)
         s = torch.where(ok, vals[name], torch.zeros_like(vals[name])).sum(dim=1)
         out["used"][name], out["sums"][name] = k, s
         out[name] = torch.where(k > 0, s / k.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
+    return out
+
+
+FUNCTIONAL_STATISTICS = ("mean", "sd", "min", "max", "rise_mean", "rise_sd", "fall_mean", "fall_sd", "run_mean", "run_sd", "gap_mean", "gap_sd")
+FUNCTIONAL_COUNTS = ("valid", "dropped", "rising_parts", "falling_parts", "peaks", "runs", "gaps", "adjacent_pairs")
+_FUNCTIONAL_BEHIND = {"mean": 0, "sd": 0, "min": 0, "max": 0, "rise_mean": 2, "rise_sd": 2, "fall_mean": 3, "fall_sd": 3, "run_mean": 5, "run_sd": 5,
+                      "gap_mean": 6, "gap_sd": 6}              # the count behind each statistic: 0 of it makes the statistic NaN
+FUNCTIONAL_MAX_FRAMES = 4096                                   # ``ev_functionals``' (and ``ev_dtw``'s) frame limit: 47 s at hop 256 and 22.05 kHz
+SEMITONE_REFERENCE_HZ = 27.5                                   # eGeMAPS's semitone scale starts at 27.5 Hz
+
+
+def functional_arguments(values, mask=None, lengths=None, percentiles=(0.2, 0.5, 0.8)):
+    """ValueError unless ``functionals`` takes the arguments (everything that needs no device): ``values`` a floating tensor of 1 to 3
+    dimensions with 1 <= F <= 4096 frames, ``mask`` broadcastable to it, one length per row, at most 16 ``percentiles``, each finite and in
+    [0, 1].  Returns (B, K, F) and the percentiles as a float64 array."""
+    if not torch.is_tensor(values) or not values.is_floating_point() or values.dim() not in (1, 2, 3):
+        raise ValueError("functionals: values must be a floating tensor (B, K, F), (B, F) or 1-D")
+    F = int(values.shape[-1])
+    B = int(values.shape[0]) if values.dim() > 1 else 1
+    K = int(values.shape[1]) if values.dim() == 3 else 1
+    if not 1 <= F <= FUNCTIONAL_MAX_FRAMES:
+        raise ValueError(f"functionals: F={F} outside 1 <= F <= {FUNCTIONAL_MAX_FRAMES}")
+    if B < 1 or K < 1:
+        raise ValueError(f"functionals: values {tuple(values.shape)} has no contour")
+    q = np.asarray(percentiles, dtype=np.float64).reshape(-1)
+    if q.shape[0] > 16:
+        raise ValueError(f"functionals: {q.shape[0]} percentiles given, at most 16 are taken")
+    if not bool(np.all(np.isfinite(q) & (q >= 0.0) & (q <= 1.0))):
+        raise ValueError(f"functionals: percentiles {[float(v) for v in q]} must be finite and lie in [0, 1] (fractions, not per cent)")
+    if mask is not None:
+        try:
+            torch.broadcast_shapes(tuple(torch.as_tensor(mask).shape), tuple(values.shape))
+        except RuntimeError:
+            raise ValueError(f"functionals: the mask {tuple(torch.as_tensor(mask).shape)} does not broadcast to the values {tuple(values.shape)}") from None
+        if torch.as_tensor(mask).dim() > values.dim():
+            raise ValueError(f"functionals: the mask {tuple(torch.as_tensor(mask).shape)} has more dimensions than the values {tuple(values.shape)}")
+    if lengths is not None and torch.as_tensor(lengths).numel() != B:
+        raise ValueError(f"functionals: {B} lengths expected, got {torch.as_tensor(lengths).numel()}")
+    return (B, K, F), q
+
+
+@torch.inference_mode()
+def functionals(values, mask=None, lengths=None, percentiles=(0.2, 0.5, 0.8)):
+    """The eGeMAPS functionals (Eyben et al. 2016) of every contour on the device (``ev_functionals``: one launch per call, a workgroup per
+    contour; no torch fallback).  ``values`` (B, K, F), (B, F) (K = 1) or 1-D (B = K = 1), any float dtype, on the GPU; ``mask`` broadcastable
+    to ``values`` (non-zero: the frame counts) or None; ``lengths`` (B,): the FRAMES of each row (None: F); ``percentiles``: up to 16 fractions
+    in [0, 1].  A frame is valid inside its row's length, under a non-zero mask and with a finite value.  -> a dict of (B, K) tensors:
+    "mean", "sd" (population), "min", "max"; "rise_mean", "rise_sd", "fall_mean", "fall_sd": the slopes per FRAME of the maximal strictly rising
+    / falling stretches of adjacent valid frames; "run_mean", "run_sd", "gap_mean", "gap_sd": the lengths in frames of the stretches of valid
+    frames and of the gaps between them (leading and trailing gaps included), float64, NaN where the count behind a statistic is 0;
+    "percentiles" (B, K, NQ) (numpy's linear interpolation) and "range", the last percentile minus the first (NaN without a valid frame or
+    without percentiles); "valid", "dropped" (non-finite values under the mask), "rising_parts", "falling_parts", "peaks" (u_i > u_{i-1} and
+    u_i >= u_{i+1} among adjacent frames), "runs", "gaps", "adjacent_pairs": int32."""
+    (B, K, F), q = functional_arguments(values, mask, lengths, percentiles)
+    if not values.is_cuda:
+        raise EvLibraryError("functionals runs on a ROCm GPU only (no CPU fallback): move values to the GPU")
+    v = values.reshape(B, K, F).to(torch.float64)
+    m = None
+    if mask is not None:
+        m = torch.as_tensor(mask, device=values.device)
+        m = (m != 0).expand(values.shape).reshape(B, K, F).to(torch.uint8).contiguous()
+    stat, count = _trim_engine(values.device).functionals(v, m, lengths, q)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=v.device)
+    out = {k: torch.where(count[..., _FUNCTIONAL_BEHIND[k]] > 0, stat[..., i], nan) for i, k in enumerate(FUNCTIONAL_STATISTICS)}
+    has = count[..., 0] > 0
+    out["percentiles"] = torch.where(has[..., None], stat[..., 12:], nan)
+    out["range"] = out["percentiles"][..., -1] - out["percentiles"][..., 0] if q.shape[0] else nan.expand(B, K).clone()
+    out.update({k: count[..., i] for i, k in enumerate(FUNCTIONAL_COUNTS)})
+    return out
+
+
+def _inside(n_frames, B: int, F: int, device, who: str):
+    """(B, F) bool: frame f lies inside row b's ``n_frames`` (None: every frame), and the lengths as int64 (B,)."""
+    n = torch.full((B,), F, dtype=torch.int64, device=device) if n_frames is None else torch.as_tensor(n_frames).to(device, torch.int64)
+    if n.numel() != B:
+        raise ValueError(f"{who}: {B} lengths expected, got {n.numel()}")
+    return torch.arange(F, device=device)[None, :] < n[:, None], n
+
+
+@torch.inference_mode()
+def voice_functionals(pitch, vq, n_frames=None, fm=None, pt=None, hm=None, sr: int = 22050, hop_length: int = 256, percentiles=(0.2, 0.5, 0.8),
+                      max_bandwidth: float = 700.0, harmonic_fm=None):
+    """The functionals of every contour the voice report has, in ONE ``functionals`` call per batch: ``pitch`` (the dict of ``pitch_yin`` /
+    ``pitch_pyin``), ``vq`` (of ``voice_quality``) and, when given, ``fm`` (``formants``), ``pt`` (``perturbation``) and ``hm`` (``harmonics``),
+    all (B, F) at the same hop on the GPU; ``n_frames`` (B,): the frames of each row (None: F).  The contours and their masks, each the mask
+    of the matching ``*_statistics`` function (so a contour's "mean" is that function's mean):
+      "f0_semitones"              12 log2(f0 / 27.5), eGeMAPS's scale, over the voiced frames (``prosody_statistics``' mask)
+      VOICE_QUALITY_FIGURES       voiced and not silent (``voice_quality_statistics``)
+      FORMANT_FIGURES             voiced, at least three formants, F_i's bandwidth at most ``max_bandwidth`` (``formant_statistics``)
+      PERTURBATION_FIGURES        voiced with YIN's lag > 0 and a counted pair of the figure's kind (``perturbation_statistics`` as --perturbation
+                                  calls it), in its units: per cent, dB, ``hnr_db``(r)
+      HARMONIC_FIGURES            voiced and carrying the figure's flag, and under the bandwidth rule of ``harmonic_statistics`` at the formants
+                                  ``harmonic_fm`` (None: ``fm``; neither: no bandwidth rule)
+    -> {contour: {statistic: (B,)}} with the keys of ``functionals`` and, beside them, "peaks_per_s" (peaks over the row's seconds) and the
+    four slope statistics in units per SECOND (scaled by sr / hop_length); "segments": {"voiced_per_s", "voiced_mean_s", "voiced_sd_s",
+    "unvoiced_mean_s", "unvoiced_sd_s"} from the runs and the gaps of the voicing contour; "contours": the names in stacking order."""
+    f0 = torch.as_tensor(pitch["f0"])
+    if f0.dim() == 1:
+        raise ValueError("voice_functionals: (B, F) contours expected (add the batch axis to a single row)")
+    B, F = f0.shape
+    dev = f0.device
+    inside, n = _inside(n_frames, B, F, dev, "voice_functionals")
+    voiced = torch.as_tensor(pitch["voiced"], dtype=torch.bool, device=dev)
+    use = voiced & inside
+    names, vals, masks = [], [], []
+
+    def add(name, v, m):
+        names.append(name)
+        vals.append(torch.as_tensor(v).to(dev, torch.float64))
+        masks.append(m)
+
+    add("f0_semitones", 12.0 * torch.log2(torch.where(use, f0.to(torch.float64), torch.full((), SEMITONE_REFERENCE_HZ, dtype=torch.float64, device=dev))
+                                          / SEMITONE_REFERENCE_HZ), use)
+    vuse = _voice_quality_mask(torch.as_tensor(vq["peak_quefrency"]).to(dev), use)
+    for k in VOICE_QUALITY_FIGURES:
+        add(k, vq[k], vuse)
+    band = None
+    if fm is not None:
+        count = torch.as_tensor(fm["count"]).to(dev)
+        freq = torch.as_tensor(fm["frequency"], dtype=torch.float64).to(dev)
+        band = torch.as_tensor(fm["bandwidth"], dtype=torch.float64).to(dev)
+        _, oks = _formant_masks(count, band, use, max_bandwidth)
+        for i in range(3):
+            add(f"f{i + 1}_hz", freq[:, :, i], oks[i])
+        for i in range(3):
+            add(f"b{i + 1}_hz", band[:, :, i], oks[i])
+    if pt is not None:
+        pc = torch.as_tensor(pt["count"]).to(dev)
+        puse = use & (torch.as_tensor(pt["lag"]).to(dev) > 0)
+        oks = _perturbation_masks(pc, puse)
+        frame = {k: torch.as_tensor(pt[k], dtype=torch.float64).to(dev) for k in ("jitter", "rap", "shimmer", "shimmer_db", "r")}
+        for name, v in _perturbation_values(frame).items():
+            add(name, v, oks[name])
+    if hm is not None:
+        flags = torch.as_tensor(hm["flags"]).to(dev)
+        if harmonic_fm is not None:
+            band = torch.as_tensor(harmonic_fm["bandwidth"], dtype=torch.float64).to(dev)
+        oks = _harmonic_masks(flags, band, use, max_bandwidth)
+        for name in HARMONIC_FIGURES:
+            add(name, hm[name], oks[name])
+    names.append("voicing")                                  # the runs and gaps of the voicing itself: the temporal group
+    vals.append(torch.zeros((B, F), dtype=torch.float64, device=dev))
+    masks.append(use)
+    fn = functionals(torch.stack(vals, dim=1), torch.stack(masks, dim=1), n, percentiles)
+    rate = float(sr) / float(hop_length)
+    seconds = n.to(torch.float64) / rate
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    out = {"contours": tuple(names[:-1])}
+    for j, name in enumerate(names[:-1]):
+        o = {k: v[:, j] for k, v in fn.items()}
+        for k in ("rise_mean", "rise_sd", "fall_mean", "fall_sd"):
+            o[k] = o[k] * rate
+        o["peaks_per_s"] = torch.where(seconds > 0, o["peaks"].to(torch.float64) / seconds.clamp(min=1e-300), nan)
+        out[name] = o
+    j = len(names) - 1
+    out["segments"] = {"voiced_per_s": torch.where(seconds > 0, fn["runs"][:, j].to(torch.float64) / seconds.clamp(min=1e-300), nan),
+                       "voiced_mean_s": fn["run_mean"][:, j] / rate, "voiced_sd_s": fn["run_sd"][:, j] / rate,
+                       "unvoiced_mean_s": fn["gap_mean"][:, j] / rate, "unvoiced_sd_s": fn["gap_sd"][:, j] / rate}
     return out

@@ -21,6 +21,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt --perturbation                       # ... and jitter, RAP, shimmer and HNR over the voiced frames, per file and per speaker
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --perturbation                              # ... and, per pair, jitter, RAP, shimmer and HNR of both sides and their differences
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt --harmonics                          # ... and H1-H2, H1-A3 and the harmonic levels at F1-F3 over H1, per file and per speaker
+    python -m emojivoice_amd.cli --voice_report clean/filelist.txt --functionals                        # ... and per contour mean, sd, percentiles, slopes and peak rate, and the voiced / unvoiced segment lengths (the eGeMAPS functionals)
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --harmonics                                 # ... and, per pair, the harmonic differences of both sides and their differences
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --voice_quality                             # ... and, per pair, the voice-quality figures of both sides and their differences
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
@@ -81,6 +82,8 @@ def validate_args(args):
         assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--perturbation is an option of --voice_report and of --evaluate_pairs"
     if getattr(args, "harmonics", False):
         assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--harmonics is an option of --voice_report and of --evaluate_pairs"
+    if getattr(args, "functionals", False):
+        assert getattr(args, "voice_report", None), "--functionals is an option of --voice_report"
     if args.sample_rate is not None:
         assert args.sample_rate > 0, "--sample_rate must be positive"
     if args.prepare_dataset:
@@ -579,6 +582,40 @@ def harmonics_of(batch, sr, hop, lens, voiced, n_frames, fm=None):
     return harmonic_rows(audio.harmonic_statistics(hm, voiced, n_frames, fm=fm))
 
 
+FUNCTIONAL_REPORT_KEYS = ("mean", "sd", "p20", "p50", "p80", "range", "rise_mean", "rise_sd", "fall_mean", "fall_sd", "peaks_per_s")
+SEGMENT_REPORT_KEYS = ("voiced_per_s", "voiced_mean_s", "voiced_sd_s", "unvoiced_mean_s", "unvoiced_sd_s")
+
+
+def functional_rows(vf):
+    """audio.voice_functionals' result (at the percentiles 0.2, 0.5, 0.8) as one host record per row: {"functionals": {contour: {key: float or
+    None}}, "segments": {key: float or None}}, the keys of FUNCTIONAL_REPORT_KEYS and SEGMENT_REPORT_KEYS; None where there is no value (NaN).
+    Everything crosses to the host in one copy."""
+    names = list(vf["contours"])
+
+    def fields(o):
+        pct = o["percentiles"]
+        return [o["mean"], o["sd"], pct[:, 0], pct[:, 1], pct[:, 2], o["range"], o["rise_mean"], o["rise_sd"], o["fall_mean"], o["fall_sd"], o["peaks_per_s"]]
+
+    table = torch.stack([torch.stack(fields(vf[c])) for c in names]).cpu()                      # (contours, keys, rows)
+    seg = torch.stack([vf["segments"][k] for k in SEGMENT_REPORT_KEYS]).cpu()                    # (keys, rows)
+    val = lambda x: None if math.isnan(float(x)) else float(x)
+    return [{"functionals": {c: {k: val(table[i, j, r]) for j, k in enumerate(FUNCTIONAL_REPORT_KEYS)} for i, c in enumerate(names)},
+             "segments": {k: val(seg[j, r]) for j, k in enumerate(SEGMENT_REPORT_KEYS)}} for r in range(seg.shape[1])]
+
+
+def functional_means(rows):
+    """The --functionals block of some rows of functional_rows together: for every value {"mean": the PLAIN mean over the files that have one
+    (None without one), "files": how many those were}.  Percentiles do not pool from sums and an eGeMAPS vector describes one utterance, so a
+    speaker's figure is the mean of the utterances' figures, not a figure of the pooled frames."""
+    def mean(vals):
+        vals = [v for v in vals if v is not None]
+        return {"mean": math.fsum(vals) / len(vals) if vals else None, "files": len(vals)}
+
+    contours = list(rows[0]["functionals"]) if rows else []
+    return {"functionals": {c: {k: mean([r["functionals"][c][k] for r in rows]) for k in FUNCTIONAL_REPORT_KEYS} for c in contours},
+            "segments": {k: mean([r["segments"][k] for r in rows]) for k in SEGMENT_REPORT_KEYS}}
+
+
 @torch.inference_mode()
 def voice_report(args, device):
     """--voice_report FILELIST (the filelist format of --prosody_report): every file is loaded with audio.load_audio(path, 22050), measured by
@@ -596,9 +633,16 @@ def voice_report(args, device):
     --harmonics adds per file h1_h2_db, h1_a3_db, f1_rel_db, f2_rel_db and f3_rel_db (audio.harmonics reduced by audio.harmonic_statistics over
     the voiced frames that carry each figure, at formants of at most 700 Hz bandwidth; null without such a frame) and harmonic_frames (the
     voiced frames); per speaker and overall the means pooled over the frames behind each figure, and the count summed.  With --formants the
-    formants are analysed once for both."""
+    formants are analysed once for both.
+    --functionals adds per file "functionals": {contour: {mean, sd, p20, p50, p80, range, rise_mean, rise_sd, fall_mean, fall_sd, peaks_per_s}}
+    for f0_semitones (12 log2(f0 / 27.5)), the five voice-quality figures and the figures of the other flags given, each over the frames its mean
+    above runs over (audio.voice_functionals: one device call per batch; slopes in units per second; null where there is no value), and
+    "segments": voiced segments per second and the mean and sd length in seconds of the voiced and of the unvoiced segments.  Per speaker and
+    overall every value becomes {"mean", "files"}: the PLAIN mean over the files that have the value and how many those were; percentiles do
+    not pool from sums, and an eGeMAPS vector (Eyben et al. 2016) describes one utterance, so nothing here is pooled over frames."""
     from . import audio
 
+    want_func = getattr(args, "functionals", False)
     want_formants = getattr(args, "formants", False)
     want_pert = getattr(args, "perturbation", False)
     want_harm = getattr(args, "harmonics", False)
@@ -616,7 +660,7 @@ def voice_report(args, device):
             files.append({"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r], "voiced_frames": int(count[r]),
                           **voice_means(own, int(count[r]))})
             acc = pooled.setdefault(spk, {"files": 0, "voiced_frames": 0, "sums": {k: [] for k in audio.VOICE_QUALITY_FIGURES}, "formants": [],
-                                          "perturbation": [], "harmonics": []})
+                                          "perturbation": [], "harmonics": [], "functionals": []})
             acc["files"] += 1
             acc["voiced_frames"] += int(count[r])
             for k in own:
@@ -627,16 +671,25 @@ def voice_report(args, device):
             for r, (_, spk, _) in enumerate(chunk):
                 files[len(files) - len(chunk) + r].update(formant_means([fs[r]]))
                 pooled[spk if spk is not None else "0"]["formants"].append(fs[r])
-        if want_pert:
-            ps = perturbation_of(batch, PROSODY_SR, PROSODY_HOP, lens, pitch["voiced"], n_frames)
+        pt = hm = hfm = None
+        if want_pert:                                # (perturbation_of, keeping the contours for --functionals)
+            pt = audio.perturbation(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
+            ps = perturbation_rows(audio.perturbation_statistics(pt, pitch["voiced"] & (pt["lag"] > 0), n_frames))
             for r, (_, spk, _) in enumerate(chunk):
                 files[len(files) - len(chunk) + r].update(perturbation_means([ps[r]]))
                 pooled[spk if spk is not None else "0"]["perturbation"].append(ps[r])
-        if want_harm:
-            hs = harmonics_of(batch, PROSODY_SR, PROSODY_HOP, lens, pitch["voiced"], n_frames, fm)
+        if want_harm:                                # (harmonics_of, keeping the contours for --functionals)
+            hfm = fm if fm is not None else audio.formants(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
+            hm = audio.harmonics(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens, formants=hfm)
+            hs = harmonic_rows(audio.harmonic_statistics(hm, pitch["voiced"], n_frames, fm=hfm))
             for r, (_, spk, _) in enumerate(chunk):
                 files[len(files) - len(chunk) + r].update(harmonic_means([hs[r]]))
                 pooled[spk if spk is not None else "0"]["harmonics"].append(hs[r])
+        if want_func:
+            fr = functional_rows(audio.voice_functionals(pitch, vq, n_frames, fm=fm, pt=pt, hm=hm, sr=PROSODY_SR, hop_length=PROSODY_HOP, harmonic_fm=hfm))
+            for r, (_, spk, _) in enumerate(chunk):
+                files[len(files) - len(chunk) + r].update(fr[r])
+                pooled[spk if spk is not None else "0"]["functionals"].append(fr[r])
 
     def pool(accs):
         n = sum(a["voiced_frames"] for a in accs)
@@ -644,7 +697,8 @@ def voice_report(args, device):
                 **voice_means({k: math.fsum(v for a in accs for v in a["sums"][k]) for k in audio.VOICE_QUALITY_FIGURES}, n),
                 **(formant_means([f for a in accs for f in a["formants"]]) if want_formants else {}),
                 **(perturbation_means([f for a in accs for f in a["perturbation"]]) if want_pert else {}),
-                **(harmonic_means([f for a in accs for f in a["harmonics"]]) if want_harm else {})}
+                **(harmonic_means([f for a in accs for f in a["harmonics"]]) if want_harm else {}),
+                **(functional_means([f for a in accs for f in a["functionals"]]) if want_func else {})}
 
     rep = {"sample_rate": PROSODY_SR, "hop_length": PROSODY_HOP, "files": files, "speakers": {k: pool([v]) for k, v in pooled.items()},
            "overall": pool(list(pooled.values()))}
@@ -1064,6 +1118,11 @@ def cli(argv=None):
                    "and the harmonics-to-noise ratio in dB over the voiced frames (pitch marks by peak picking at YIN's lag, three cycles each side) "
                    "per file, per speaker and overall; --evaluate_pairs: add \"perturbation\" per pair (both sides and their differences) and per "
                    "speaker and overall")
+    p.add_argument("--functionals", action="store_true", help="--voice_report: add \"functionals\" per file: mean, sd, the 20th / 50th / 80th percentile and "
+                   "their range, mean and sd of the rising and of the falling slopes per second and the peaks per second of every contour the report "
+                   "measures (f0 in semitones from 27.5 Hz, the voice-quality figures, and those of --formants / --perturbation / --harmonics), and "
+                   "\"segments\": rate and lengths of the voiced and unvoiced segments (the eGeMAPS functionals, one device call per batch); per "
+                   "speaker and overall the plain mean of each value over the files that have one")
     p.add_argument("--harmonics", action="store_true", help="--voice_report: add the mean H1-H2, H1-A3 and the level of the harmonic at F1, F2 and F3 "
                    "over H1 in dB over the voiced frames (the harmonics of YIN's period in the log spectrum, at the formants of --formants) per "
                    "file, per speaker and overall; --evaluate_pairs: add \"harmonics\" per pair (both sides and their differences) and per speaker "

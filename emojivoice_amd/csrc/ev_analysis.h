@@ -1,5 +1,5 @@
 // Host entry points of the analysis side: resampling, dataset statistics, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness,
-// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation and harmonic differences (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
+// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences and contour functionals (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
 // after ev_handle, fail / HIPCHK / enter, dev_upload, drop_owned, scratch_acquire and launch<>.  None of these calls runs on the engine's conv
 // path; ev_load_mel_basis, ev_mel_spectrogram, ev_denoise and ev_stft_magnitude do, and stay in ev_engine.hip.
 #pragma once
@@ -726,6 +726,34 @@ int ev_harmonics(ev_handle* h, const float* d_x, const int32_t* d_len, int B, in
     const int NF = frames_of(L, w.t.H);
     HarmParams ph{d_x, d_len, d_period, d_formant, d_fcount, d_frame, d_count, d_harm, w.t, L, NF, d_formant ? n_formants : 0, power_floor};
     launch<harmonics_kernel>(h->device, dim3((unsigned)((NF + 15) / 16), (unsigned)B), dim3(256), w.lds, h->stream, ph);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Contour functionals: moments, order statistics, slopes of the rising and falling parts, peaks, runs and gaps of every contour of a batch
+// (functionals_kernel, ev_analysis_kernels.h; the definition: include/emojivoice.h).  No load step, no tables, no arena: one launch, a workgroup
+// per contour, whose arguments carry everything (the percentiles' q travel by value).
+int ev_functionals(ev_handle* h, const double* d_v, const uint8_t* d_mask, const int32_t* d_len, int B, int K, int F, const double* q, int NQ,
+                   double* d_stat, int32_t* d_count, void* stream) {
+    if (enter(h)) return 1;
+    if (check_batch(h, __func__, B)) return 1;
+    if (K < 1 || K > 65535) return fail(h, "ev_functionals: K=%d outside 1 <= K <= 65535", K);
+    if (F < 1 || F > 4096) return fail(h, "ev_functionals: F=%d outside 1 <= F <= 4096", F);
+    if (NQ < 0 || NQ > 16) return fail(h, "ev_functionals: NQ=%d outside 0 <= NQ <= 16", NQ);
+    if (NQ > 0 && !q) return fail(h, "ev_functionals: q must be non-null (HOST) when NQ > 0");
+    if (check_finite(h, __func__, "q", q, NQ)) return 1;
+    for (int r = 0; r < NQ; ++r) if (!(q[r] >= 0.0 && q[r] <= 1.0)) return fail(h, "ev_functionals: q[%d]=%g outside 0 <= q <= 1", r, q[r]);
+    if (!d_v) return fail(h, "ev_functionals: d_v must be non-null");
+    if (!d_stat) return fail(h, "ev_functionals: d_stat must be non-null");
+    if (!d_count) return fail(h, "ev_functionals: d_count must be non-null");
+    h->stream = (hipStream_t)stream;
+    FuncParams p{};
+    p.v = d_v; p.mask = d_mask; p.len = d_len; p.stat = d_stat; p.count = d_count;
+    p.K = K; p.F = F; p.NQ = NQ; p.P = 256;
+    while (p.P < F) p.P <<= 1;
+    for (int r = 0; r < NQ; ++r) p.q[r] = q[r];
+    // 64 doubles and 64 words of hand-over, then u (8 B) and g, st (2 B each) per frame: 48.5 KiB at F = 4096
+    launch<functionals_kernel>(h->device, dim3((unsigned)K, (unsigned)B), dim3(256), 512 + (size_t)12 * p.P, h->stream, p);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

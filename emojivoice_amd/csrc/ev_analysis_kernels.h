@@ -2356,3 +2356,205 @@ __global__ __launch_bounds__(256) void harmonics_kernel(const HarmParams p) {
         oc[2 * f] = nh; oc[2 * f + 1] = flags;
     }
 }
+
+// ---------------------------------------------------------------------------
+// Contour functionals (ev_functionals): per contour (b, k) of F frames the eGeMAPS functionals: moments, order statistics, the slopes of the rising
+// and of the falling parts, peaks, and the lengths of the runs of valid frames and of the gaps between them (the definition: include/emojivoice.h).
+// All float64, contraction OFF (STOI_EXACT), no atomics, no scratch.  ONE WORKGROUP of 256 threads PER CONTOUR, everything in dynamic LDS: 64 doubles
+// and 64 words of hand-over, then u (P doubles), g and st (P uint16 each), P = F rounded up to a power of two and at least 256: 512 + 12 P bytes,
+// 48.5 KiB at F = 4096.  Element i of the compacted contour belongs to thread i mod 256 in every phase, which is the slot rule of the sums.
+//   PHASE 1  tiles of 256 frames in ascending order, one coalesced read each: the validity flag, a ballot per wave, the four waves' counts through
+//            LDS (two alternating sets: one barrier per tile) and the running total give each valid frame its place in u / g.
+//   PHASE 2  tiles of 256 elements of u: the classes of the pairs i - 1, i, i + 1 from the neighbours, then two inclusive max-scans of "a run starts
+//            here" / "a part starts here" markers (6 shuffle steps, the waves' last values through LDS, a running carry): they carry the start of
+//            the run / part to every element, so a part may cross every wave and tile.  The thread of a part's LAST pair forms its slope and keeps
+//            the start in st[i] (0xffff elsewhere); the thread of a run's last element squares its length; gaps come from g's differences.
+//   PHASE 3  the sums: slot accumulators in registers (ascending i), an xor tree per wave, the four waves added in ascending order by every thread;
+//            then the second pass (squared deviations from the means; the slopes are formed again from st, by the same operations).
+//   PHASE 4  u[k ..] = +inf up to the next power of two and a bitonic network in place, one barrier per stage.
+//   PHASE 5  thread r forms percentile r; thread 0 writes the rest.
+struct FuncParams {
+    const double* v; const uint8_t* mask; const int32_t* len; double* stat; int32_t* count;
+    int K, F, NQ, P;                                                    // P: F rounded up to a power of two, at least 256
+    double q[16];
+};
+
+__device__ __forceinline__ int func_wave_isum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ int func_class(double a, double b) { return (b > a) - (b < a); }     // of the adjacent pair (a, b)
+
+__global__ __launch_bounds__(256) void functionals_kernel(const FuncParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double func_smem[];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, b = blockIdx.y;
+    const int F = p.F, NQ = p.NQ, NS = 12 + NQ;
+    double* rd = func_smem;                                             // [2][4][3]: the waves' sums of pass 1 and of pass 2
+    int* ri = (int*)(func_smem + 32);                                   // [4][9]: the waves' counts
+    int* wc = ri + 36;                                                  // [2][4]: phase 1, the waves' valid frames of a tile
+    int* wm = ri + 44;                                                  // [2][4][2]: phase 2, the waves' last scan values of a tile
+    double* u = func_smem + 64;
+    unsigned short* g = (unsigned short*)(u + p.P);
+    unsigned short* st = g + p.P;
+    const size_t row = (size_t)b * p.K + blockIdx.x;
+    double* o_st = p.stat + row * NS;
+    int32_t* o_ct = p.count + row * 8;
+    const int n = p.len ? p.len[b] : F;
+    if (n < 0 || n > F) {                                               // a bad row is a row of zeros (uniform; before any barrier)
+        if (t < NS) o_st[t] = 0.0;
+        if (t < 8) o_ct[t] = 0;
+        return;
+    }
+    // ---- phase 1: validity and ordered compaction
+    const double* vr = p.v + row * F;
+    const uint8_t* mk = p.mask ? p.mask + row * F : nullptr;
+    int k = 0, dropped = 0;
+    for (int f0 = 0; f0 < n; f0 += 256) {
+        const int f = f0 + t;
+        const bool on = f < n && (!mk || mk[f] != 0);
+        const double x = on ? vr[f] : 0.0;
+        const bool valid = on && fabs(x) <= 1.7976931348623157e308;     // finite (NaN compares false)
+        dropped += on && !valid;
+        const unsigned long long bal = __ballot(valid);
+        const int slot = (f0 >> 8 & 1) * 4;
+        if (lane == 0) wc[slot + w] = __popcll(bal);
+        __syncthreads();
+        const int c0 = wc[slot], c1 = wc[slot + 1], c2 = wc[slot + 2], c3 = wc[slot + 3];
+        if (valid) {
+            const int at = k + (w > 0 ? c0 : 0) + (w > 1 ? c1 : 0) + (w > 2 ? c2 : 0) + __popcll(bal & ((1ull << lane) - 1ull));
+            u[at] = x; g[at] = (unsigned short)f;
+        }
+        k += c0 + c1 + c2 + c3;
+    }
+    __syncthreads();
+    // ---- phases 2 and 3, first pass
+    double su = 0.0, sr = 0.0, sf = 0.0;
+    int nrise = 0, nfall = 0, npeak = 0, nruns = 0, ngaps = 0, nadj = 0, s2r = 0, s2g = 0;
+    int car_r = -1, car_p = -1;
+    for (int i0 = 0; i0 < k; i0 += 256) {
+        const int i = i0 + t;
+        const bool in = i < k;
+        double ui = 0.0, un = 0.0, up = 0.0;
+        int gi = 0, gn = 0, cP = 0, cI = 0, cN = 0;
+        bool adjP = false, adjN = false;
+        if (in) {
+            ui = u[i]; gi = g[i];
+            if (i > 0) { up = u[i - 1]; adjP = (int)g[i - 1] + 1 == gi; }
+            if (i + 1 < k) { un = u[i + 1]; gn = g[i + 1]; adjN = gn == gi + 1; }
+            if (adjP) cP = func_class(up, ui);
+            if (adjN) cI = func_class(ui, un);
+            if (i + 2 < k && (int)g[i + 2] == gn + 1) cN = func_class(un, u[i + 2]);
+        }
+        int mr = in && !adjP ? i : -1;                                  // a run starts at i
+        int mp = in && cI != 0 && cP != cI ? i : -1;                    // a part starts with pair i
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {                              // (every shuffle is executed by the whole wave)
+            const int a = __shfl_up(mr, o, 64), c = __shfl_up(mp, o, 64);
+            if (lane >= o) { mr = max(mr, a); mp = max(mp, c); }
+        }
+        const int slot = (i0 >> 8 & 1) * 8;
+        if (lane == 63) { wm[slot + 2 * w] = mr; wm[slot + 2 * w + 1] = mp; }
+        __syncthreads();
+        mr = max(mr, car_r); mp = max(mp, car_p);
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            const int a = wm[slot + 2 * x], c = wm[slot + 2 * x + 1];
+            if (x < w) { mr = max(mr, a); mp = max(mp, c); }
+            car_r = max(car_r, a); car_p = max(car_p, c);
+        }
+        if (in) {
+            su = su + ui;
+            nadj += adjN;
+            npeak += adjP && adjN && ui > up && ui >= un;
+            if (!adjN) { const int l = i - mr + 1; ++nruns; s2r += l * l; }
+            if (i == 0 && gi > 0) { ++ngaps; s2g += gi * gi; }
+            const int d = i + 1 < k ? gn - gi - 1 : n - 1 - gi;         // the gap behind i, the trailing one behind the last
+            if (d > 0) { ++ngaps; s2g += d * d; }
+            int code = 0xffff;
+            if (cI != 0 && cN != cI) {                                  // pair i is the last of its part, which began with pair mp
+                code = mp;
+                const double s = (un - u[mp]) / (double)(i + 1 - mp);
+                if (cI > 0) { sr = sr + s; ++nrise; } else { sf = sf + s; ++nfall; }
+            }
+            st[i] = (unsigned short)code;                               // (read back by this thread only)
+        }
+    }
+    su = formant_wave_sum(su); sr = formant_wave_sum(sr); sf = formant_wave_sum(sf);
+    dropped = func_wave_isum(dropped); nrise = func_wave_isum(nrise); nfall = func_wave_isum(nfall); npeak = func_wave_isum(npeak);
+    nruns = func_wave_isum(nruns); ngaps = func_wave_isum(ngaps); nadj = func_wave_isum(nadj); s2r = func_wave_isum(s2r); s2g = func_wave_isum(s2g);
+    if (lane == 0) {
+        rd[3 * w] = su; rd[3 * w + 1] = sr; rd[3 * w + 2] = sf;
+        int* r = ri + 9 * w;
+        r[0] = dropped; r[1] = nrise; r[2] = nfall; r[3] = npeak; r[4] = nruns; r[5] = ngaps; r[6] = nadj; r[7] = s2r; r[8] = s2g;
+    }
+    __syncthreads();
+    su = ((rd[0] + rd[3]) + rd[6]) + rd[9]; sr = ((rd[1] + rd[4]) + rd[7]) + rd[10]; sf = ((rd[2] + rd[5]) + rd[8]) + rd[11];
+    dropped = ri[0] + ri[9] + ri[18] + ri[27]; nrise = ri[1] + ri[10] + ri[19] + ri[28]; nfall = ri[2] + ri[11] + ri[20] + ri[29];
+    npeak = ri[3] + ri[12] + ri[21] + ri[30]; nruns = ri[4] + ri[13] + ri[22] + ri[31]; ngaps = ri[5] + ri[14] + ri[23] + ri[32];
+    nadj = ri[6] + ri[15] + ri[24] + ri[33]; s2r = ri[7] + ri[16] + ri[25] + ri[34]; s2g = ri[8] + ri[17] + ri[26] + ri[35];
+    const double mean = k ? su / (double)k : 0.0, rmean = nrise ? sr / (double)nrise : 0.0, fmean = nfall ? sf / (double)nfall : 0.0;
+    // ---- second pass: squared deviations
+    double q2 = 0.0, r2 = 0.0, f2 = 0.0;
+    for (int i = t; i < k; i += 256) {
+        const double d = u[i] - mean;
+        q2 = q2 + d * d;
+        const int a = st[i];
+        if (a != 0xffff) {
+            const double ue = u[i + 1], ua = u[a];
+            const double s = (ue - ua) / (double)(i + 1 - a);
+            if (ue > ua) { const double e = s - rmean; r2 = r2 + e * e; }
+            else { const double e = s - fmean; f2 = f2 + e * e; }
+        }
+    }
+    q2 = formant_wave_sum(q2); r2 = formant_wave_sum(r2); f2 = formant_wave_sum(f2);
+    if (lane == 0) { rd[12 + 3 * w] = q2; rd[13 + 3 * w] = r2; rd[14 + 3 * w] = f2; }
+    __syncthreads();                                                    // (also: every read of u in compacted order lies before it)
+    q2 = ((rd[12] + rd[15]) + rd[18]) + rd[21]; r2 = ((rd[13] + rd[16]) + rd[19]) + rd[22]; f2 = ((rd[14] + rd[17]) + rd[20]) + rd[23];
+    // ---- phase 4: the bitonic network over PS >= max(k, 2) elements, ascending by <
+    int PS = 2;
+    while (PS < k) PS <<= 1;
+    for (int i = k + t; i < PS; i += 256) u[i] = INFINITY;
+    __syncthreads();
+    for (int size = 2; size <= PS; size <<= 1) {
+        for (int j = size >> 1; j > 0; j >>= 1) {
+            for (int pi = t; pi < PS >> 1; pi += 256) {
+                const int lo = (pi & ~(j - 1)) << 1 | (pi & (j - 1)), hi = lo | j;
+                const double a = u[lo], c = u[hi];
+                if ((lo & size) == 0 ? c < a : a < c) { u[lo] = c; u[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    // ---- phase 5
+    if (k > 0 && t < NQ) {
+        double qq = 0.0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) if (t == r) qq = p.q[r];            // (static indices: the arguments stay in scalar registers)
+        const double pp = qq * (double)(k - 1);
+        const double jf = floor(pp);
+        const int j = (int)jf, j1 = min(j + 1, k - 1);
+        const double tt = pp - jf, sj = u[j];
+        o_st[12 + t] = sj + tt * (u[j1] - sj);
+    }
+    if (k == 0 && t < NQ) o_st[12 + t] = 0.0;
+    if (t == 0) {
+        if (k == 0 && n > 0) { ngaps = 1; s2g = n * n; }
+        const long long nr = nruns, ng = ngaps, s1r = k, s1g = n - k;
+        o_st[0] = mean;
+        o_st[1] = k ? sqrt(q2 / (double)k) : 0.0;
+        o_st[2] = k ? u[0] : 0.0;
+        o_st[3] = k ? u[k - 1] : 0.0;
+        o_st[4] = rmean;
+        o_st[5] = nrise ? sqrt(r2 / (double)nrise) : 0.0;
+        o_st[6] = fmean;
+        o_st[7] = nfall ? sqrt(f2 / (double)nfall) : 0.0;
+        o_st[8] = nr ? (double)s1r / (double)nr : 0.0;
+        o_st[9] = nr ? sqrt((double)(nr * s2r - s1r * s1r)) / (double)nr : 0.0;
+        o_st[10] = ng ? (double)s1g / (double)ng : 0.0;
+        o_st[11] = ng ? sqrt((double)(ng * s2g - s1g * s1g)) / (double)ng : 0.0;
+        o_ct[0] = k; o_ct[1] = dropped; o_ct[2] = nrise; o_ct[3] = nfall; o_ct[4] = npeak; o_ct[5] = nruns; o_ct[6] = ngaps; o_ct[7] = nadj;
+    }
+}

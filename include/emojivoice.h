@@ -48,6 +48,7 @@
  *   ev_perturbation    <- no counterpart; Praat's voice report (jitter local / absolute / RAP, shimmer local / dB, cc harmonicity; Boersma 1993) is the model
  *   ev_load_harmonics  <- no counterpart; Eyben et al. 2016 and Hanson 1997 are the model
  *   ev_harmonics       <- no counterpart; Eyben et al. 2016 and Hanson 1997 are the model
+ *   ev_functionals     <- no counterpart; the functionals of Eyben et al. 2016 (eGeMAPS) as openSMILE computes them are the model
  *   ev_pyin_observe    <- no counterpart; librosa.pyin is the model
  *   ev_pyin_decode     <- no counterpart; librosa.pyin is the model
  *
@@ -87,7 +88,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -822,6 +823,50 @@ int ev_harmonics(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_l
                  const double *d_formant /* (B, NF, n_formants, 2) or NULL */, const int32_t *d_fcount /* (B, NF) or NULL */, int n_formants,
                  double power_floor, double *d_frame /* (B, NF, 8) */, int32_t *d_count /* (B, NF, 2) */,
                  double *d_harm /* (B, NF, n_harm, 2) or NULL */, void *stream);
+
+/* Contour functionals on the device: what turns the per-frame contours above (pitch, voice quality, formants, perturbation, harmonic differences)
+ * into a description of an utterance (the eGeMAPS functionals; Eyben et al. 2016): moments, percentiles, the slopes of the rising and of the
+ * falling parts, the peaks, and the lengths of the stretches of valid frames and of the gaps between them.  K contours of F frames per row, every
+ * contour on its own.  Everything is float64, the kernel is compiled with floating-point contraction off; no atomics, no scratch;
+ * ev_set_arithmetic does not reach it.
+ * Valid frames: n = d_len[b], or F when d_len is NULL.  A row with n < 0 or n > F is zeros in both outputs, which is no error and no out-of-bounds
+ *   access; nothing at or behind n is read.  Frame f of contour (b, k) is VALID when f < n, d_mask[b, k, f] != 0 (d_mask NULL: every byte is 1) and
+ *   d_v[b, k, f] is finite; a frame inside n with a non-zero mask byte and a non-finite value is DROPPED: counted, and invalid for everything else.
+ *   The valid values in ascending frame order are u_0 .. u_{k-1}, at the frames g_0 < .. < g_{k-1}.  Pair i (u_i, u_{i+1}) is ADJACENT when
+ *   g_{i+1} = g_i + 1.
+ * Moments: mean = sum u / k;  sd = sqrt(sum (u - mean)^2 / k) (population, two passes).
+ * Order statistics: s is u sorted ascending by < on the values (equal values are interchangeable; -0 equals +0).  min = s_0, max = s_{k-1}; for
+ *   each q_r:  p = q_r (double)(k - 1) (one rounded product),  j = floor(p),  t = p - j,  the result is s_j + t (s_{min(j+1, k-1)} - s_j): numpy's
+ *   linear interpolation up to rounding.
+ * Parts: the class of pair i is +1 when it is adjacent and u_{i+1} > u_i, -1 when adjacent and u_{i+1} < u_i, else 0 (a gap or an equal pair ends
+ *   a part).  A rising part is a maximal run of consecutive pairs of class +1, from index a to index e of u; its slope is
+ *   (u_e - u_a) / (double)(e - a) per frame; falling parts likewise, with negative slopes.  rise_mean, rise_sd, fall_mean, fall_sd: the mean and the
+ *   population sd of the slopes over the parts, two passes.
+ * Peaks: index i is a peak when both of its pairs are adjacent, u_i > u_{i-1} and u_i >= u_{i+1} (ev_perturbation's local-peak rule).
+ * Runs and gaps: inside [0, n) a RUN is a maximal stretch of valid frames, a GAP a maximal stretch of frames that are not valid, the leading and
+ *   the trailing one included.  With N stretches of lengths l:  S1 = sum l, S2 = sum l^2 (integers);  mean = (double)S1 / (double)N;
+ *   sd = sqrt((double)(N S2 - S1 S1)) / (double)N, in 64-bit integer arithmetic before the one conversion.
+ * d_stat[b, k, .] float64: 0 mean, 1 sd, 2 min, 3 max, 4 rise_mean, 5 rise_sd, 6 fall_mean, 7 fall_sd, 8 run_mean, 9 run_sd, 10 gap_mean,
+ *   11 gap_sd, 12 + r the percentile at q_r.  d_count[b, k, .] int32: 0 k, 1 dropped frames, 2 rising parts, 3 falling parts, 4 peaks, 5 runs,
+ *   6 gaps, 7 adjacent pairs.  A statistic over no terms is 0.
+ * Order of the float64 sums, one rule for every sum over an index i (sum u and sum (u - mean)^2 over the values; the slope sums over the PAIRS,
+ *   where a part's slope, or its squared deviation, sits at the index of the part's last pair and +0.0 elsewhere): term i belongs to slot i mod 256;
+ *   a slot starts at +0.0 and adds its terms in ascending i; the 256 slots are reduced by an xor tree (offsets 32, 16, 8, 4, 2, 1) inside each group
+ *   of 64; the four group sums are added in ascending order, ((g0 + g1) + g2) + g3.  Products are rounded before they are added.  The order depends
+ *   on k and the values only, never on B, K, F or the place in the grid: a contour alone, inside a batch, at another k, as the d_len prefix of a
+ *   longer F, in a second call, under every ev_set_arithmetic setting and from a captured graph gives the same bits.
+ * Limits, each violation failing with a message that names it and writing nothing: 1 <= B <= 65535; 1 <= K <= 65535; 1 <= F <= 4096 (ev_dtw's
+ *   frame limit); 0 <= NQ <= 16; every q_r finite with 0 <= q_r <= 1 (checked on the host); q non-NULL when NQ > 0; d_v, d_stat and d_count
+ *   non-NULL.
+ * Kernel (functionals_kernel: one launch on `stream`; no load step, no host wait, no copy, no arena: ev_alloc_count never moves): one workgroup of
+ *   four waves per contour, everything in LDS: u (8 bytes per frame), g and the parts' start indices (2 bytes each) at F rounded up to a power of
+ *   two and at least 256, and 512 bytes of hand-over: 48.5 KiB at F = 4096.  One coalesced pass compacts the valid frames by ballots and a running
+ *   prefix; two max-scans carry the start of every run and of every part to its end; the sums; a bitonic network sorts u in place behind +inf
+ *   padding; thread r forms percentile r.  The call is capturable. */
+int ev_functionals(ev_handle *h, const double *d_v /* (B, K, F) */, const uint8_t *d_mask /* (B, K, F) or NULL */,
+                   const int32_t *d_len /* (B) frames, or NULL */, int B, int K, int F,
+                   const double *q /* HOST (NQ), may be NULL when NQ == 0 */, int NQ,
+                   double *d_stat /* (B, K, 12 + NQ) */, int32_t *d_count /* (B, K, 8) */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

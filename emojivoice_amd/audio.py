@@ -929,31 +929,87 @@ def voice_quality(y, sr: int = 22050, fmin: float = 65.0, fmax: float = 600.0, f
     return out
 
 
-# The frames behind each figure of the ``*_statistics`` functions, shared with ``voice_functionals``: ``use`` is voiced and inside the row's length.
-def _voice_quality_mask(peak, use):
-    return use & (peak > 0)
+# The four figure families of the voice report (voice quality, formants, perturbation, harmonics), each described once and shared by its
+# ``*_statistics`` function and ``voice_functionals``: ``_coerced`` brings what a family reads of its analysis function's dict to one device,
+# ``_inside`` gives the rows their batch axis and their lengths, a ``_*_contours`` function turns the tensors and the base mask ``use`` (voiced
+# and inside the row) into (the family's frames mask, {figure: (values (B, F) float64, the frames behind the figure (B, F) bool)}) in the order
+# of the family's ``*_FIGURES``, and ``_reduce`` sums every contour under its mask.
+def _coerced(d, lead: str, f64=(), dev=None, voiced=None):
+    """{``lead``: d[lead] as it is, every key of ``f64`` as float64, "voiced": ``voiced`` as bool when given}, where d[lead] lives (``dev``:
+    there instead).  The first entry leads: its first two axes are (B, F)."""
+    first = torch.as_tensor(d[lead])
+    dev = first.device if dev is None else dev
+    t = {lead: first.to(dev), **{k: torch.as_tensor(d[k], dtype=torch.float64).to(dev) for k in f64}}
+    if voiced is not None:
+        t["voiced"] = torch.as_tensor(voiced, dtype=torch.bool, device=dev)
+    return t
 
 
-def _formant_masks(count, band, use, max_bandwidth: float):
-    """(the voiced frames with at least three formants, per i = 0 .. 2 those of them whose F_i is at most ``max_bandwidth`` wide)."""
-    use = use & (count >= 3)
-    return use, [use & (band[:, :, i] <= float(max_bandwidth)) for i in range(3)]
+def _inside(t, n_frames, who: str, one: bool = False, shapes=None):
+    """The rows of ``t`` ({name: tensor or None}, the first entry leading): a single row (``one``) gains the batch axis in every entry,
+    ``shapes(t, B, F)`` says what is wrong with the shapes (None: nothing) -> (t, (B, F) bool: frame f lies inside row b's ``n_frames`` (None:
+    every frame), the lengths as int64 (B,))."""
+    if one:
+        t = {k: None if v is None else v.unsqueeze(0) for k, v in t.items()}
+    lead = next(iter(t.values()))
+    B, F = lead.shape[:2]
+    wrong = shapes(t, B, F) if shapes is not None else None
+    if wrong:
+        raise ValueError(f"{who}: {wrong}")
+    n = torch.full((B,), F, dtype=torch.int64, device=lead.device) if n_frames is None else torch.as_tensor(n_frames).to(lead.device, torch.int64)
+    if n.numel() != B:
+        raise ValueError(f"{who}: {B} lengths expected, got {n.numel()}")
+    return t, torch.arange(F, device=lead.device)[None, :] < n[:, None], n
 
 
-def _perturbation_masks(count, use):
-    """figure -> the frames with a counted pair of the figure's kind (period pairs, triples, amplitude pairs; hnr_db: every frame of ``use``)."""
-    return {"jitter_pct": use & (count[..., 1] > 0), "rap_pct": use & (count[..., 3] > 0), "shimmer_pct": use & (count[..., 2] > 0),
-            "shimmer_db": use & (count[..., 2] > 0), "hnr_db": use & torch.ones_like(use)}
+def _voice_quality_contours(t, use):
+    """The voiced frames that are not silent, behind every figure."""
+    use = use & (t["peak_quefrency"] > 0)
+    return use, {k: (t[k], use) for k in VOICE_QUALITY_FIGURES}
 
 
-def _harmonic_masks(flags, band, use, max_bandwidth: float):
-    """figure -> the frames that carry the figure's flag and, with ``band`` (B, F, n >= 3), whose formant is at most ``max_bandwidth`` wide."""
+def _formant_contours(t, use, max_bandwidth: float):
+    """The voiced frames with at least three formants; behind F_i and its bandwidth those of them whose F_i is at most ``max_bandwidth`` wide."""
+    use = use & (t["count"] >= 3)
+    oks = [use & (t["bandwidth"][:, :, i] <= float(max_bandwidth)) for i in range(3)]
+    return use, {f"{q}{i + 1}_hz": (t[key][:, :, i], oks[i]) for q, key in (("f", "frequency"), ("b", "bandwidth")) for i in range(3)}
+
+
+_PERTURBATION_READ = ("jitter", "rap", "shimmer", "shimmer_db", "r")       # what the report's figures are made of
+
+
+def _perturbation_contours(t, use):
+    """``use`` itself; behind a figure (in the report's units: per cent, dB, ``hnr_db``(r)) the frames with a counted pair of its kind (period
+    pairs, triples, amplitude pairs; hnr_db: every frame of ``use``)."""
+    pairs, amps, triples = use & (t["count"][..., 1] > 0), use & (t["count"][..., 2] > 0), use & (t["count"][..., 3] > 0)
+    return use, {"jitter_pct": (100.0 * t["jitter"], pairs), "rap_pct": (100.0 * t["rap"], triples), "shimmer_pct": (100.0 * t["shimmer"], amps),
+                 "shimmer_db": (t["shimmer_db"], amps), "hnr_db": (hnr_db(t["r"]), use)}
+
+
+def _harmonic_contours(t, use, band, max_bandwidth: float):
+    """``use`` itself; behind a figure the frames that carry its flag and, with ``band`` (B, F, n >= 3), whose formant is at most
+    ``max_bandwidth`` wide."""
     out = {}
     for name in HARMONIC_FIGURES:
-        ok = use & ((flags & _HARMONIC_FLAG[name]) != 0)
+        ok = use & ((t["flags"] & _HARMONIC_FLAG[name]) != 0)
         if band is not None and name in _HARMONIC_FORMANT:
             ok = ok & (band[:, :, _HARMONIC_FORMANT[name]] <= float(max_bandwidth))
-        out[name] = ok
+        out[name] = (t[name], ok)
+    return use, out
+
+
+def _reduce(frames, contours):
+    """{"frames" (B,) int64: the frames of the mask ``frames``; "used", "sums", "means": {figure: (B,)}: the frames behind each contour, its sum
+    over them and sum / frames, NaN without a frame}.  Contours that share a mask share its count."""
+    counts = {id(frames): frames.sum(dim=1)}
+    out = {"frames": counts[id(frames)], "used": {}, "sums": {}, "means": {}}
+    for name, (v, ok) in contours.items():
+        if id(ok) not in counts:
+            counts[id(ok)] = ok.sum(dim=1)
+        k = counts[id(ok)]
+        s = torch.where(ok, v, torch.zeros_like(v)).sum(dim=1)
+        out["used"][name], out["sums"][name] = k, s
+        out["means"][name] = torch.where(k > 0, s / k.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
     return out
 
 
@@ -964,27 +1020,15 @@ def voice_quality_statistics(vq, voiced, lengths=None):
     (``peak_quefrency`` > 0), NaN where no frame qualifies; "frames" (B,) int64: how many did; "sums": the same five keys, (B,) float64 sums
     over those frames, for pooling over utterances}, where ``vq`` lives (torch ops only).  Entries are (B, F) or 1-D; ``lengths`` (B,): the
     FRAMES that belong to each row (None: F)."""
-    peak = torch.as_tensor(vq["peak_quefrency"])
-    voiced = torch.as_tensor(voiced, dtype=torch.bool, device=peak.device)
-    one = peak.dim() == 1
-    if one:
-        peak, voiced = peak.unsqueeze(0), voiced.unsqueeze(0)
-    B, F = peak.shape
-    if voiced.shape != peak.shape:
-        raise ValueError(f"voice_quality_statistics: the mask {tuple(voiced.shape)} does not match the figures {tuple(peak.shape)}")
-    n = torch.full((B,), F, dtype=torch.int64, device=peak.device) if lengths is None else torch.as_tensor(lengths).to(peak.device, torch.int64)
-    if n.numel() != B:
-        raise ValueError(f"voice_quality_statistics: {B} lengths expected, got {n.numel()}")
-    use = _voice_quality_mask(peak, voiced & (torch.arange(F, device=peak.device)[None, :] < n[:, None]))
-    count = use.sum(dim=1)
-    out = {"frames": count, "sums": {}}
-    for k in VOICE_QUALITY_FIGURES:
-        v = torch.as_tensor(vq[k], dtype=torch.float64).to(peak.device)
-        v = v.unsqueeze(0) if one else v
-        s = torch.where(use, v, torch.zeros_like(v)).sum(dim=1)
-        out["sums"][k] = s
-        out[k] = torch.where(count > 0, s / count.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
-    return out
+    t = _coerced(vq, "peak_quefrency", VOICE_QUALITY_FIGURES, voiced=voiced)
+
+    def shapes(t, B, F):
+        if t["voiced"].shape != t["peak_quefrency"].shape:
+            return f"the mask {tuple(t['voiced'].shape)} does not match the figures {tuple(t['peak_quefrency'].shape)}"
+
+    t, inside, _ = _inside(t, lengths, "voice_quality_statistics", t["peak_quefrency"].dim() == 1, shapes)
+    r = _reduce(*_voice_quality_contours(t, t["voiced"] & inside))
+    return {"frames": r["frames"], "sums": r["sums"], **r["means"]}
 
 
 FORMANT_POWER_FLOOR = 1e-10                        # frames whose windowed, pre-emphasised energy is at or under it are silent: no formants
@@ -1054,33 +1098,21 @@ def formant_statistics(fm, voiced, lengths=None, max_bandwidth: float = 700.0):
     int64: the frames behind each i's means; "sums": the six keys, (B,) float64 sums over those frames, for pooling over utterances}, where
     ``fm`` lives (torch ops only).  Entries are (B, F, n) / (B, F) or one row without the leading axis; ``lengths`` (B,): the FRAMES that
     belong to each row (None: F)."""
-    count = torch.as_tensor(fm["count"])
-    voiced = torch.as_tensor(voiced, dtype=torch.bool, device=count.device)
-    freq = torch.as_tensor(fm["frequency"], dtype=torch.float64).to(count.device)
-    band = torch.as_tensor(fm["bandwidth"], dtype=torch.float64).to(count.device)
-    if count.dim() == 1:
-        count, voiced, freq, band = count.unsqueeze(0), voiced.unsqueeze(0), freq.unsqueeze(0), band.unsqueeze(0)
-    B, F = count.shape
-    if voiced.shape != count.shape:
-        raise ValueError(f"formant_statistics: the mask {tuple(voiced.shape)} does not match the figures {tuple(count.shape)}")
-    if freq.shape[:2] != count.shape or freq.shape != band.shape or freq.shape[2] < 3:
-        raise ValueError(f"formant_statistics: frequency and bandwidth must be ({B}, {F}, n >= 3), got {tuple(freq.shape)} and {tuple(band.shape)}")
-    n = torch.full((B,), F, dtype=torch.int64, device=count.device) if lengths is None else torch.as_tensor(lengths).to(count.device, torch.int64)
-    if n.numel() != B:
-        raise ValueError(f"formant_statistics: {B} lengths expected, got {n.numel()}")
-    inside = torch.arange(F, device=count.device)[None, :] < n[:, None]
-    use, oks = _formant_masks(count, band, voiced & inside, max_bandwidth)
-    out = {"frames": use.sum(dim=1), "unconverged_frames": (inside & (count < 0)).sum(dim=1), "sums": {}}
-    used = []
-    for i in range(3):
-        ok = oks[i]
-        k = ok.sum(dim=1)
-        used.append(k)
-        for name, v in ((f"f{i + 1}_hz", freq[:, :, i]), (f"b{i + 1}_hz", band[:, :, i])):
-            s = torch.where(ok, v, torch.zeros_like(v)).sum(dim=1)
-            out["sums"][name] = s
-            out[name] = torch.where(k > 0, s / k.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
-    out["used"] = torch.stack(used, dim=1)
+    t = _coerced(fm, "count", ("frequency", "bandwidth"), voiced=voiced)
+
+    def shapes(t, B, F):
+        count, freq, band = t["count"], t["frequency"], t["bandwidth"]
+        if t["voiced"].shape != count.shape:
+            return f"the mask {tuple(t['voiced'].shape)} does not match the figures {tuple(count.shape)}"
+        if freq.shape[:2] != count.shape or freq.shape != band.shape or freq.shape[2] < 3:
+            return f"frequency and bandwidth must be ({B}, {F}, n >= 3), got {tuple(freq.shape)} and {tuple(band.shape)}"
+
+    t, inside, _ = _inside(t, lengths, "formant_statistics", t["count"].dim() == 1, shapes)
+    r = _reduce(*_formant_contours(t, t["voiced"] & inside, max_bandwidth))
+    out = {"frames": r["frames"], "unconverged_frames": (inside & (t["count"] < 0)).sum(dim=1), "sums": {}}
+    for name in (f"{q}{i + 1}_hz" for i in range(3) for q in "fb"):
+        out["sums"][name], out[name] = r["sums"][name], r["means"][name]
+    out["used"] = torch.stack([r["used"][f"f{i + 1}_hz"] for i in range(3)], dim=1)
     return out
 
 
@@ -1124,12 +1156,6 @@ def hnr_db(r):
     return 10.0 * torch.log10(r / (1.0 - r))
 
 
-def _perturbation_values(vals):
-    """figure -> its per-frame values in the report's units, from ``perturbation``'s jitter, rap, shimmer, shimmer_db and r."""
-    return {"jitter_pct": 100.0 * vals["jitter"], "rap_pct": 100.0 * vals["rap"], "shimmer_pct": 100.0 * vals["shimmer"], "shimmer_db": vals["shimmer_db"],
-            "hnr_db": hnr_db(vals["r"])}
-
-
 @torch.inference_mode()
 def perturbation_statistics(pt, voiced, lengths=None):
     """Per utterance, from ``perturbation`` and a voicing mask at the same hop: {"jitter_pct", "rap_pct", "shimmer_pct", "shimmer_db", "hnr_db":
@@ -1138,29 +1164,17 @@ def perturbation_statistics(pt, voiced, lengths=None):
     frame); NaN where no frame qualifies; "frames" (B,) int64: the voiced frames inside; "used": {figure: (B,) int64, the frames behind its
     mean}; "sums": {figure: (B,) float64 sums over those frames, for pooling over utterances}}, where ``pt`` lives (torch ops only).  Entries
     are (B, F) / (B, F, 4) or one row without the leading axis; ``lengths`` (B,): the FRAMES that belong to each row (None: F)."""
-    count = torch.as_tensor(pt["count"])
-    voiced = torch.as_tensor(voiced, dtype=torch.bool, device=count.device)
-    vals = {k: torch.as_tensor(pt[k], dtype=torch.float64).to(count.device) for k in ("jitter", "rap", "shimmer", "shimmer_db", "r")}
-    if count.dim() == 2:
-        count, voiced = count.unsqueeze(0), voiced.unsqueeze(0)
-        vals = {k: v.unsqueeze(0) for k, v in vals.items()}
-    B, F = count.shape[:2]
-    if count.dim() != 3 or count.shape[2] != 4 or voiced.shape != (B, F) or any(v.shape != (B, F) for v in vals.values()):
-        raise ValueError(f"perturbation_statistics: count (B, F, 4), the mask and the figures (B, F) expected, got {tuple(count.shape)}, "
-                         f"{tuple(voiced.shape)} and {[tuple(v.shape) for v in vals.values()]}")
-    n = torch.full((B,), F, dtype=torch.int64, device=count.device) if lengths is None else torch.as_tensor(lengths).to(count.device, torch.int64)
-    if n.numel() != B:
-        raise ValueError(f"perturbation_statistics: {B} lengths expected, got {n.numel()}")
-    use = voiced & (torch.arange(F, device=count.device)[None, :] < n[:, None])
-    out = {"frames": use.sum(dim=1), "used": {}, "sums": {}}
-    oks = _perturbation_masks(count, use)
-    for name, v in _perturbation_values(vals).items():
-        ok = oks[name]
-        k = ok.sum(dim=1)
-        s = torch.where(ok, v, torch.zeros_like(v)).sum(dim=1)
-        out["used"][name], out["sums"][name] = k, s
-        out[name] = torch.where(k > 0, s / k.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
-    return out
+    t = _coerced(pt, "count", _PERTURBATION_READ, voiced=voiced)
+
+    def shapes(t, B, F):
+        vals = [t[k] for k in _PERTURBATION_READ]
+        if t["count"].dim() != 3 or t["count"].shape[2] != 4 or t["voiced"].shape != (B, F) or any(v.shape != (B, F) for v in vals):
+            return (f"count (B, F, 4), the mask and the figures (B, F) expected, got {tuple(t['count'].shape)}, {tuple(t['voiced'].shape)} "
+                    f"and {[tuple(v.shape) for v in vals]}")
+
+    t, inside, _ = _inside(t, lengths, "perturbation_statistics", t["count"].dim() == 2, shapes)
+    r = _reduce(*_perturbation_contours(t, t["voiced"] & inside))
+    return {"frames": r["frames"], "used": r["used"], "sums": r["sums"], **r["means"]}
 
 
 HARMONIC_POWER_FLOOR = 1e-7                        # the clamp of |X|^2 before the logarithm, ``voice_quality``'s
@@ -1235,33 +1249,20 @@ def harmonic_statistics(hm, voiced, lengths=None, fm=None, max_bandwidth: float 
     where no frame qualifies; "frames" (B,) int64: the voiced frames inside; "used": {figure: (B,) int64, the frames behind its mean}; "sums":
     {figure: (B,) float64 sums over those frames, for pooling over utterances}}, where ``hm`` lives (torch ops only).  Entries are (B, F) or
     one row without the leading axis; ``lengths`` (B,): the FRAMES that belong to each row (None: F)."""
-    flags = torch.as_tensor(hm["flags"])
-    voiced = torch.as_tensor(voiced, dtype=torch.bool, device=flags.device)
-    vals = {k: torch.as_tensor(hm[k], dtype=torch.float64).to(flags.device) for k in HARMONIC_FIGURES}
-    band = None if fm is None else torch.as_tensor(fm["bandwidth"], dtype=torch.float64).to(flags.device)
-    if flags.dim() == 1:
-        flags, voiced = flags.unsqueeze(0), voiced.unsqueeze(0)
-        vals = {k: v.unsqueeze(0) for k, v in vals.items()}
-        band = None if band is None else band.unsqueeze(0)
-    B, F = flags.shape[:2]
-    if flags.dim() != 2 or voiced.shape != (B, F) or any(v.shape != (B, F) for v in vals.values()):
-        raise ValueError(f"harmonic_statistics: flags, the mask and the figures (B, F) expected, got {tuple(flags.shape)}, {tuple(voiced.shape)} "
-                         f"and {[tuple(v.shape) for v in vals.values()]}")
-    if band is not None and (band.dim() != 3 or tuple(band.shape[:2]) != (B, F) or band.shape[2] < 3):
-        raise ValueError(f"harmonic_statistics: the bandwidths must be ({B}, {F}, n >= 3), got {tuple(band.shape)}")
-    n = torch.full((B,), F, dtype=torch.int64, device=flags.device) if lengths is None else torch.as_tensor(lengths).to(flags.device, torch.int64)
-    if n.numel() != B:
-        raise ValueError(f"harmonic_statistics: {B} lengths expected, got {n.numel()}")
-    use = voiced & (torch.arange(F, device=flags.device)[None, :] < n[:, None])
-    out = {"frames": use.sum(dim=1), "used": {}, "sums": {}}
-    oks = _harmonic_masks(flags, band, use, max_bandwidth)
-    for name in HARMONIC_FIGURES:
-        ok = oks[name]
-        k = ok.sum(dim=1)
-        s = torch.where(ok, vals[name], torch.zeros_like(vals[name])).sum(dim=1)
-        out["used"][name], out["sums"][name] = k, s
-        out[name] = torch.where(k > 0, s / k.clamp(min=1).to(torch.float64), torch.full_like(s, float("nan")))
-    return out
+    t = _coerced(hm, "flags", HARMONIC_FIGURES, voiced=voiced)
+    t["band"] = None if fm is None else torch.as_tensor(fm["bandwidth"], dtype=torch.float64).to(t["flags"].device)
+
+    def shapes(t, B, F):
+        vals, band = [t[k] for k in HARMONIC_FIGURES], t["band"]
+        if t["flags"].dim() != 2 or t["voiced"].shape != (B, F) or any(v.shape != (B, F) for v in vals):
+            return (f"flags, the mask and the figures (B, F) expected, got {tuple(t['flags'].shape)}, {tuple(t['voiced'].shape)} "
+                    f"and {[tuple(v.shape) for v in vals]}")
+        if band is not None and (band.dim() != 3 or tuple(band.shape[:2]) != (B, F) or band.shape[2] < 3):
+            return f"the bandwidths must be ({B}, {F}, n >= 3), got {tuple(band.shape)}"
+
+    t, inside, _ = _inside(t, lengths, "harmonic_statistics", t["flags"].dim() == 1, shapes)
+    r = _reduce(*_harmonic_contours(t, t["voiced"] & inside, t["band"], max_bandwidth))
+    return {"frames": r["frames"], "used": r["used"], "sums": r["sums"], **r["means"]}
 
 
 FUNCTIONAL_STATISTICS = ("mean", "sd", "min", "max", "rise_mean", "rise_sd", "fall_mean", "fall_sd", "run_mean", "run_sd", "gap_mean", "gap_sd")
@@ -1332,14 +1333,6 @@ def functionals(values, mask=None, lengths=None, percentiles=(0.2, 0.5, 0.8)):
     return out
 
 
-def _inside(n_frames, B: int, F: int, device, who: str):
-    """(B, F) bool: frame f lies inside row b's ``n_frames`` (None: every frame), and the lengths as int64 (B,)."""
-    n = torch.full((B,), F, dtype=torch.int64, device=device) if n_frames is None else torch.as_tensor(n_frames).to(device, torch.int64)
-    if n.numel() != B:
-        raise ValueError(f"{who}: {B} lengths expected, got {n.numel()}")
-    return torch.arange(F, device=device)[None, :] < n[:, None], n
-
-
 @torch.inference_mode()
 def voice_functionals(pitch, vq, n_frames=None, fm=None, pt=None, hm=None, sr: int = 22050, hop_length: int = 256, percentiles=(0.2, 0.5, 0.8),
                       max_bandwidth: float = 700.0, harmonic_fm=None):
@@ -1362,48 +1355,25 @@ def voice_functionals(pitch, vq, n_frames=None, fm=None, pt=None, hm=None, sr: i
         raise ValueError("voice_functionals: (B, F) contours expected (add the batch axis to a single row)")
     B, F = f0.shape
     dev = f0.device
-    inside, n = _inside(n_frames, B, F, dev, "voice_functionals")
-    voiced = torch.as_tensor(pitch["voiced"], dtype=torch.bool, device=dev)
-    use = voiced & inside
-    names, vals, masks = [], [], []
-
-    def add(name, v, m):
-        names.append(name)
-        vals.append(torch.as_tensor(v).to(dev, torch.float64))
-        masks.append(m)
-
-    add("f0_semitones", 12.0 * torch.log2(torch.where(use, f0.to(torch.float64), torch.full((), SEMITONE_REFERENCE_HZ, dtype=torch.float64, device=dev))
-                                          / SEMITONE_REFERENCE_HZ), use)
-    vuse = _voice_quality_mask(torch.as_tensor(vq["peak_quefrency"]).to(dev), use)
-    for k in VOICE_QUALITY_FIGURES:
-        add(k, vq[k], vuse)
+    t, inside, n = _inside({"f0": f0, "voiced": torch.as_tensor(pitch["voiced"], dtype=torch.bool, device=dev)}, n_frames, "voice_functionals")
+    use = t["voiced"] & inside
+    contours = {"f0_semitones": (12.0 * torch.log2(torch.where(use, f0.to(torch.float64), torch.full((), SEMITONE_REFERENCE_HZ, dtype=torch.float64, device=dev))
+                                                   / SEMITONE_REFERENCE_HZ), use)}
+    contours.update(_voice_quality_contours(_coerced(vq, "peak_quefrency", VOICE_QUALITY_FIGURES, dev), use)[1])
     band = None
     if fm is not None:
-        count = torch.as_tensor(fm["count"]).to(dev)
-        freq = torch.as_tensor(fm["frequency"], dtype=torch.float64).to(dev)
-        band = torch.as_tensor(fm["bandwidth"], dtype=torch.float64).to(dev)
-        _, oks = _formant_masks(count, band, use, max_bandwidth)
-        for i in range(3):
-            add(f"f{i + 1}_hz", freq[:, :, i], oks[i])
-        for i in range(3):
-            add(f"b{i + 1}_hz", band[:, :, i], oks[i])
+        tf = _coerced(fm, "count", ("frequency", "bandwidth"), dev)
+        band = tf["bandwidth"]
+        contours.update(_formant_contours(tf, use, max_bandwidth)[1])
     if pt is not None:
-        pc = torch.as_tensor(pt["count"]).to(dev)
-        puse = use & (torch.as_tensor(pt["lag"]).to(dev) > 0)
-        oks = _perturbation_masks(pc, puse)
-        frame = {k: torch.as_tensor(pt[k], dtype=torch.float64).to(dev) for k in ("jitter", "rap", "shimmer", "shimmer_db", "r")}
-        for name, v in _perturbation_values(frame).items():
-            add(name, v, oks[name])
+        contours.update(_perturbation_contours(_coerced(pt, "count", _PERTURBATION_READ, dev), use & (torch.as_tensor(pt["lag"]).to(dev) > 0))[1])
     if hm is not None:
-        flags = torch.as_tensor(hm["flags"]).to(dev)
         if harmonic_fm is not None:
             band = torch.as_tensor(harmonic_fm["bandwidth"], dtype=torch.float64).to(dev)
-        oks = _harmonic_masks(flags, band, use, max_bandwidth)
-        for name in HARMONIC_FIGURES:
-            add(name, hm[name], oks[name])
-    names.append("voicing")                                  # the runs and gaps of the voicing itself: the temporal group
-    vals.append(torch.zeros((B, F), dtype=torch.float64, device=dev))
-    masks.append(use)
+        contours.update(_harmonic_contours(_coerced(hm, "flags", HARMONIC_FIGURES, dev), use, band, max_bandwidth)[1])
+    names = list(contours) + ["voicing"]                     # the runs and gaps of the voicing itself: the temporal group
+    vals = [v for v, _ in contours.values()] + [torch.zeros((B, F), dtype=torch.float64, device=dev)]
+    masks = [m for _, m in contours.values()] + [use]
     fn = functionals(torch.stack(vals, dim=1), torch.stack(masks, dim=1), n, percentiles)
     rate = float(sr) / float(hop_length)
     seconds = n.to(torch.float64) / rate

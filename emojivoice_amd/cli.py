@@ -35,6 +35,7 @@ record_audio.py:31): they are resampled to the analysis rate on the device (emoj
 from __future__ import annotations
 
 import argparse
+import collections
 import datetime as dt
 import json
 import math
@@ -74,14 +75,10 @@ def write_wav_pcm16(path, wav: np.ndarray, sr: int = 22050):
 def validate_args(args):
     if getattr(args, "spectral_distance", False):
         assert getattr(args, "vocoder_report", None), "--spectral_distance is an option of --vocoder_report"
-    if getattr(args, "voice_quality", False):
-        assert getattr(args, "evaluate_pairs", None), "--voice_quality is an option of --evaluate_pairs"
-    if getattr(args, "formants", False):
-        assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--formants is an option of --voice_report and of --evaluate_pairs"
-    if getattr(args, "perturbation", False):
-        assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--perturbation is an option of --voice_report and of --evaluate_pairs"
-    if getattr(args, "harmonics", False):
-        assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), "--harmonics is an option of --voice_report and of --evaluate_pairs"
+    for family in report_families():
+        if getattr(args, family.pairs_flag, False):
+            homes = (["voice_report"] if family.report_flag else []) + ["evaluate_pairs"]
+            assert any(getattr(args, h, None) for h in homes), f"--{family.pairs_flag} is an option of " + " and of ".join("--" + h for h in homes)
     if getattr(args, "functionals", False):
         assert getattr(args, "voice_report", None), "--functionals is an option of --voice_report"
     if args.sample_rate is not None:
@@ -485,101 +482,72 @@ def prosody_report(args, device):
     return rep
 
 
-def voice_means(sums, frames):
-    """The five voice-quality figures as sums / frames (None for each without a frame): how a file's, a speaker's and the overall means are
-    formed from per-file sums over the voiced frames."""
-    return {k: (sums[k] / frames if frames else None) for k in sums}
+Family = collections.namedtuple("Family", "report_flag pairs_flag block figures frames_key counts used measure")
 
 
-def formant_rows(st):
-    """audio.formant_statistics' result as one host record per row: {"frames", "unconverged", "used": [3 ints], "sums": {figure: float}}."""
+def report_families():
+    """The figure families of --voice_report and --evaluate_pairs, in the order of the reports.  Per family: ``report_flag`` and ``pairs_flag``,
+    the args attributes that switch it on in the two reports (None: always on); ``block``, its name in the evaluation report; ``figures``,
+    its tuple in audio; ``frames_key``, the report's key of its frame count; ``counts``, further keys of its statistics that the report sums;
+    ``used(st)`` -> {figure: (B,) the frames behind its mean}; ``measure(batch, sr, hop, lens, voiced, n_frames, got)`` -> its
+    audio.*_statistics of the batch, after leaving its per-frame dict under got[block] for the families behind it and for --functionals."""
     from . import audio
 
-    frames, unconv, used = st["frames"].cpu(), st["unconverged_frames"].cpu(), st["used"].cpu()
-    sums = {k: st["sums"][k].cpu() for k in audio.FORMANT_FIGURES}
-    return [{"frames": int(frames[r]), "unconverged": int(unconv[r]), "used": [int(v) for v in used[r]], "sums": {k: float(sums[k][r]) for k in sums}}
-            for r in range(frames.shape[0])]
+    def voice(batch, sr, hop, lens, voiced, n_frames, got):
+        got["voice"] = audio.voice_quality(batch, sr, hop_length=hop, lengths=lens)
+        return audio.voice_quality_statistics(got["voice"], voiced, n_frames)
+
+    def formants(batch, sr, hop, lens, voiced, n_frames, got):
+        got["formants"] = audio.formants(batch, sr, hop_length=hop, lengths=lens)
+        return audio.formant_statistics(got["formants"], voiced, n_frames)
+
+    def perturbation(batch, sr, hop, lens, voiced, n_frames, got):
+        """audio.perturbation at YIN's own lags, reduced over the frames that the pitch tracker AND YIN call voiced."""
+        pt = got["perturbation"] = audio.perturbation(batch, sr, hop_length=hop, lengths=lens)
+        return audio.perturbation_statistics(pt, voiced & (pt["lag"] > 0), n_frames)
+
+    def harmonics(batch, sr, hop, lens, voiced, n_frames, got):
+        """audio.harmonics at YIN's own periods and the formants of --formants (without it audio.formants is run here), reduced over the frames
+        that the pitch tracker calls voiced and whose figures YIN's period and the formants' bandwidths admit."""
+        fm = got["harmonic_fm"] = got["formants"] if "formants" in got else audio.formants(batch, sr, hop_length=hop, lengths=lens)
+        got["harmonics"] = audio.harmonics(batch, sr, hop_length=hop, lengths=lens, formants=fm)
+        return audio.harmonic_statistics(got["harmonics"], voiced, n_frames, fm=fm)
+
+    per_figure = lambda st: st["used"]
+    return (Family(None, "voice_quality", "voice", audio.VOICE_QUALITY_FIGURES, "voiced_frames", (), lambda st: {k: st["frames"] for k in st["sums"]}, voice),
+            Family("formants", "formants", "formants", audio.FORMANT_FIGURES, "formant_frames", ("unconverged_frames",),
+                   lambda st: {k: st["used"][:, int(k[1]) - 1] for k in st["sums"]}, formants),          # f_i and b_i share used[:, i]
+            Family("perturbation", "perturbation", "perturbation", audio.PERTURBATION_FIGURES, "perturbation_frames", (), per_figure, perturbation),
+            Family("harmonics", "harmonics", "harmonics", audio.HARMONIC_FIGURES, "harmonic_frames", (), per_figure, harmonics))
 
 
-def formant_means(rows):
-    """The --formants figures of some rows of formant_rows together: every mean pooled over the frames behind it (the rows' sums over the rows'
-    counts; None without a frame), the frame counts summed."""
-    from . import audio
+def enabled_families(args, flag: str):
+    """The families of report_families() that ``args`` switches on; ``flag``: "report_flag" (--voice_report) or "pairs_flag" (--evaluate_pairs)."""
+    return [f for f in report_families() if getattr(f, flag) is None or getattr(args, getattr(f, flag), False)]
 
+
+def family_rows(st, family):
+    """A family's audio.*_statistics result as one host record per row: {"frames": int, every key of family.counts: int, "used": {figure: int},
+    "sums": {figure: float}}.  The counts cross to the host in one copy and the sums in another."""
+    used = family.used(st)
+    ints = torch.stack([st["frames"]] + [st[k] for k in family.counts] + [used[k] for k in family.figures]).cpu()
+    sums = torch.stack([st["sums"][k] for k in family.figures]).cpu()
+    nc = 1 + len(family.counts)
+    return [{"frames": int(ints[0, r]), **{k: int(ints[1 + j, r]) for j, k in enumerate(family.counts)},
+             "used": {k: int(ints[nc + j, r]) for j, k in enumerate(family.figures)}, "sums": {k: float(sums[j, r]) for j, k in enumerate(family.figures)}}
+            for r in range(ints.shape[1])]
+
+
+def family_means(rows, family):
+    """A family's figures of some rows of family_rows together, as a file's, a speaker's and the overall record hold them: every mean pooled
+    over the frames behind it (the rows' sums over the rows' counts; None without a frame), then the frame count and family.counts summed."""
     out = {}
-    for k in audio.FORMANT_FIGURES:
-        n = sum(r["used"][int(k[1]) - 1] for r in rows)
-        out[k] = math.fsum(r["sums"][k] for r in rows) / n if n else None
-    out["formant_frames"] = sum(r["frames"] for r in rows)
-    out["unconverged_frames"] = sum(r["unconverged"] for r in rows)
-    return out
-
-
-def perturbation_rows(st):
-    """audio.perturbation_statistics' result as one host record per row: {"frames", "used": {figure: int}, "sums": {figure: float}}."""
-    from . import audio
-
-    frames = st["frames"].cpu()
-    used = {k: st["used"][k].cpu() for k in audio.PERTURBATION_FIGURES}
-    sums = {k: st["sums"][k].cpu() for k in audio.PERTURBATION_FIGURES}
-    return [{"frames": int(frames[r]), "used": {k: int(used[k][r]) for k in used}, "sums": {k: float(sums[k][r]) for k in sums}}
-            for r in range(frames.shape[0])]
-
-
-def perturbation_means(rows):
-    """The --perturbation figures of some rows of perturbation_rows together: every mean pooled over the frames behind it (the rows' sums over
-    the rows' counts; None without a frame), and perturbation_frames: the voiced frames summed."""
-    from . import audio
-
-    out = {}
-    for k in audio.PERTURBATION_FIGURES:
+    for k in family.figures:
         n = sum(r["used"][k] for r in rows)
         out[k] = math.fsum(r["sums"][k] for r in rows) / n if n else None
-    out["perturbation_frames"] = sum(r["frames"] for r in rows)
+    for key, field in ((family.frames_key, "frames"),) + tuple((k, k) for k in family.counts):
+        out[key] = sum(r[field] for r in rows)
     return out
-
-
-def perturbation_of(batch, sr, hop, lens, voiced, n_frames):
-    """perturbation_rows of a batch: audio.perturbation at YIN's own lags, reduced over the frames that the pitch tracker AND YIN call voiced."""
-    from . import audio
-
-    pt = audio.perturbation(batch, sr, hop_length=hop, lengths=lens)
-    return perturbation_rows(audio.perturbation_statistics(pt, voiced & (pt["lag"] > 0), n_frames))
-
-
-def harmonic_rows(st):
-    """audio.harmonic_statistics' result as one host record per row: {"frames", "used": {figure: int}, "sums": {figure: float}}."""
-    from . import audio
-
-    frames = st["frames"].cpu()
-    used = {k: st["used"][k].cpu() for k in audio.HARMONIC_FIGURES}
-    sums = {k: st["sums"][k].cpu() for k in audio.HARMONIC_FIGURES}
-    return [{"frames": int(frames[r]), "used": {k: int(used[k][r]) for k in used}, "sums": {k: float(sums[k][r]) for k in sums}}
-            for r in range(frames.shape[0])]
-
-
-def harmonic_means(rows):
-    """The --harmonics figures of some rows of harmonic_rows together: every mean pooled over the frames behind it (the rows' sums over the
-    rows' counts; None without a frame), and harmonic_frames: the voiced frames summed."""
-    from . import audio
-
-    out = {}
-    for k in audio.HARMONIC_FIGURES:
-        n = sum(r["used"][k] for r in rows)
-        out[k] = math.fsum(r["sums"][k] for r in rows) / n if n else None
-    out["harmonic_frames"] = sum(r["frames"] for r in rows)
-    return out
-
-
-def harmonics_of(batch, sr, hop, lens, voiced, n_frames, fm=None):
-    """harmonic_rows of a batch: audio.harmonics at YIN's own periods and the formants ``fm`` (None: audio.formants is run), reduced over the
-    frames that the pitch tracker calls voiced and whose figures YIN's period and the formants' bandwidths admit."""
-    from . import audio
-
-    if fm is None:
-        fm = audio.formants(batch, sr, hop_length=hop, lengths=lens)
-    hm = audio.harmonics(batch, sr, hop_length=hop, lengths=lens, formants=fm)
-    return harmonic_rows(audio.harmonic_statistics(hm, voiced, n_frames, fm=fm))
 
 
 FUNCTIONAL_REPORT_KEYS = ("mean", "sd", "p20", "p50", "p80", "range", "rise_mean", "rise_sd", "fall_mean", "fall_sd", "peaks_per_s")
@@ -643,62 +611,38 @@ def voice_report(args, device):
     from . import audio
 
     want_func = getattr(args, "functionals", False)
-    want_formants = getattr(args, "formants", False)
-    want_pert = getattr(args, "perturbation", False)
-    want_harm = getattr(args, "harmonics", False)
+    families = enabled_families(args, "report_flag")
     files, pooled = [], {}
     for chunk, batch, lens in filelist_batches(args.voice_report, args.batch_size, PROSODY_SR, device):
         pitch = pitch_tracker(args)(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
-        vq = audio.voice_quality(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
         n_frames = [-(-n // PROSODY_HOP) for n in lens]
-        st = audio.voice_quality_statistics(vq, pitch["voiced"], n_frames)
-        count = st["frames"].cpu()
-        sums = {k: v.cpu() for k, v in st["sums"].items()}
+        got = {}                                     # block -> the per-frame dict of its analysis: every one runs once per batch
+        rows = {f.block: family_rows(f.measure(batch, PROSODY_SR, PROSODY_HOP, lens, pitch["voiced"], n_frames, got), f) for f in families}
+        if want_func:
+            rows["functionals"] = functional_rows(audio.voice_functionals(pitch, got["voice"], n_frames, fm=got.get("formants"), pt=got.get("perturbation"),
+                                                                          hm=got.get("harmonics"), sr=PROSODY_SR, hop_length=PROSODY_HOP,
+                                                                          harmonic_fm=got.get("harmonic_fm")))
         for r, (wav, spk, _) in enumerate(chunk):
             spk = spk if spk is not None else "0"
-            own = {k: float(sums[k][r]) for k in audio.VOICE_QUALITY_FIGURES}
-            files.append({"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r], "voiced_frames": int(count[r]),
-                          **voice_means(own, int(count[r]))})
-            acc = pooled.setdefault(spk, {"files": 0, "voiced_frames": 0, "sums": {k: [] for k in audio.VOICE_QUALITY_FIGURES}, "formants": [],
-                                          "perturbation": [], "harmonics": [], "functionals": []})
+            rec = {"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r],
+                   "voiced_frames": None}            # (filled by the first family: the key keeps this place, ahead of the figures)
+            for f in families:
+                rec.update(family_means([rows[f.block][r]], f))
+            if want_func:
+                rec.update(rows["functionals"][r])
+            files.append(rec)
+            acc = pooled.setdefault(spk, {"files": 0, **{k: [] for k in rows}})
             acc["files"] += 1
-            acc["voiced_frames"] += int(count[r])
-            for k in own:
-                acc["sums"][k].append(own[k])
-        fm = audio.formants(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens) if want_formants else None
-        if want_formants:
-            fs = formant_rows(audio.formant_statistics(fm, pitch["voiced"], n_frames))
-            for r, (_, spk, _) in enumerate(chunk):
-                files[len(files) - len(chunk) + r].update(formant_means([fs[r]]))
-                pooled[spk if spk is not None else "0"]["formants"].append(fs[r])
-        pt = hm = hfm = None
-        if want_pert:                                # (perturbation_of, keeping the contours for --functionals)
-            pt = audio.perturbation(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
-            ps = perturbation_rows(audio.perturbation_statistics(pt, pitch["voiced"] & (pt["lag"] > 0), n_frames))
-            for r, (_, spk, _) in enumerate(chunk):
-                files[len(files) - len(chunk) + r].update(perturbation_means([ps[r]]))
-                pooled[spk if spk is not None else "0"]["perturbation"].append(ps[r])
-        if want_harm:                                # (harmonics_of, keeping the contours for --functionals)
-            hfm = fm if fm is not None else audio.formants(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
-            hm = audio.harmonics(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens, formants=hfm)
-            hs = harmonic_rows(audio.harmonic_statistics(hm, pitch["voiced"], n_frames, fm=hfm))
-            for r, (_, spk, _) in enumerate(chunk):
-                files[len(files) - len(chunk) + r].update(harmonic_means([hs[r]]))
-                pooled[spk if spk is not None else "0"]["harmonics"].append(hs[r])
-        if want_func:
-            fr = functional_rows(audio.voice_functionals(pitch, vq, n_frames, fm=fm, pt=pt, hm=hm, sr=PROSODY_SR, hop_length=PROSODY_HOP, harmonic_fm=hfm))
-            for r, (_, spk, _) in enumerate(chunk):
-                files[len(files) - len(chunk) + r].update(fr[r])
-                pooled[spk if spk is not None else "0"]["functionals"].append(fr[r])
+            for k in rows:
+                acc[k].append(rows[k][r])
 
     def pool(accs):
-        n = sum(a["voiced_frames"] for a in accs)
-        return {"files": sum(a["files"] for a in accs), "voiced_frames": n,
-                **voice_means({k: math.fsum(v for a in accs for v in a["sums"][k]) for k in audio.VOICE_QUALITY_FIGURES}, n),
-                **(formant_means([f for a in accs for f in a["formants"]]) if want_formants else {}),
-                **(perturbation_means([f for a in accs for f in a["perturbation"]]) if want_pert else {}),
-                **(harmonic_means([f for a in accs for f in a["harmonics"]]) if want_harm else {}),
-                **(functional_means([f for a in accs for f in a["functionals"]]) if want_func else {})}
+        out = {"files": sum(a["files"] for a in accs), "voiced_frames": None}
+        for f in families:
+            out.update(family_means([row for a in accs for row in a[f.block]], f))
+        if want_func:
+            out.update(functional_means([row for a in accs for row in a["functionals"]]))
+        return out
 
     rep = {"sample_rate": PROSODY_SR, "hop_length": PROSODY_HOP, "files": files, "speakers": {k: pool([v]) for k, v in pooled.items()},
            "overall": pool(list(pooled.values()))}
@@ -931,6 +875,7 @@ def evaluate_pairs(args, device):
         sys.exit(f"[-] {args.evaluate_pairs}: no pairs listed")
     sr, hop = EVAL_MEL[2], EVAL_MEL[3]
     records, skipped = [], []
+    families = enabled_families(args, "pairs_flag")
 
     def side(wavs):
         """mel cepstra (B, 13, T) padded with zeros, frames per row, and the pitch of every row"""
@@ -942,20 +887,10 @@ def evaluate_pairs(args, device):
             sig[r, : w.shape[1]] = w[0]
         lens = [w.shape[1] for w in wavs]
         pitch = pitch_tracker(args)(sig, sr, hop_length=hop, lengths=lens)
-        if getattr(args, "voice_quality", False):
-            st = audio.voice_quality_statistics(audio.voice_quality(sig, sr, hop_length=hop, lengths=lens), pitch["voiced"], frames)
-            pitch["voice"] = [{k: (None if math.isnan(float(st[k][r])) else float(st[k][r])) for k in audio.VOICE_QUALITY_FIGURES} for r in range(len(wavs))]
-        fm = None
-        if getattr(args, "formants", False):
-            fm = audio.formants(sig, sr, hop_length=hop, lengths=[min(n, sig.shape[1]) for n in lens])
-            pitch["formants"] = [{k: v for k, v in formant_means([row]).items() if k in audio.FORMANT_FIGURES}
-                                 for row in formant_rows(audio.formant_statistics(fm, pitch["voiced"], frames))]
-        if getattr(args, "perturbation", False):
-            rows = perturbation_of(sig, sr, hop, [min(n, sig.shape[1]) for n in lens], pitch["voiced"], frames)
-            pitch["perturbation"] = [{k: v for k, v in perturbation_means([row]).items() if k in audio.PERTURBATION_FIGURES} for row in rows]
-        if getattr(args, "harmonics", False):
-            rows = harmonics_of(sig, sr, hop, [min(n, sig.shape[1]) for n in lens], pitch["voiced"], frames, fm)
-            pitch["harmonics"] = [{k: v for k, v in harmonic_means([row]).items() if k in audio.HARMONIC_FIGURES} for row in rows]
+        clipped, got = [min(n, sig.shape[1]) for n in lens], {}
+        for f in families:
+            st = f.measure(sig, sr, hop, lens if f.block == "voice" else clipped, pitch["voiced"], frames, got)
+            pitch[f.block] = [{k: v for k, v in family_means([row], f).items() if k in f.figures} for row in family_rows(st, f)]
         return cep, frames, pitch
 
     for b0 in range(0, len(entries), args.batch_size):
@@ -981,45 +916,18 @@ def evaluate_pairs(args, device):
             records.append({"recorded": rec, "synthesised": syn, "speaker": spk, "mcd_db": float(mcd[r]), "f0_rmse_cents": f0["rmse_cents"][r],
                             "voicing_error": float(verr[r]), "voiced_pairs": int(nv[r]), "frames_recorded": fr_a[r], "frames_synthesised": fr_b[r],
                             "path_steps": int(steps[r])})
-            if "voice" in pitch_a:
-                va, vb = pitch_a["voice"][r], pitch_b["voice"][r]
-                records[-1]["voice"] = {"recorded": va, "synthesised": vb,
+            for f in families:
+                va, vb = pitch_a[f.block][r], pitch_b[f.block][r]
+                records[-1][f.block] = {"recorded": va, "synthesised": vb,
                                         "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
-            if "formants" in pitch_a:
-                va, vb = pitch_a["formants"][r], pitch_b["formants"][r]
-                records[-1]["formants"] = {"recorded": va, "synthesised": vb,
-                                           "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
-            if "perturbation" in pitch_a:
-                va, vb = pitch_a["perturbation"][r], pitch_b["perturbation"][r]
-                records[-1]["perturbation"] = {"recorded": va, "synthesised": vb,
-                                               "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
-            if "harmonics" in pitch_a:
-                va, vb = pitch_a["harmonics"][r], pitch_b["harmonics"][r]
-                records[-1]["harmonics"] = {"recorded": va, "synthesised": vb,
-                                            "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
 
     def means(recs):
         out = evaluation_means(recs)
-        if getattr(args, "voice_quality", False):
-            out["voice"] = {}
-            for k in audio.VOICE_QUALITY_FIGURES:
-                d = [r["voice"]["delta"][k] for r in recs if r["voice"]["delta"][k] is not None]
-                out["voice"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
-        if getattr(args, "formants", False):
-            out["formants"] = {}
-            for k in audio.FORMANT_FIGURES:
-                d = [r["formants"]["delta"][k] for r in recs if r["formants"]["delta"][k] is not None]
-                out["formants"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
-        if getattr(args, "perturbation", False):
-            out["perturbation"] = {}
-            for k in audio.PERTURBATION_FIGURES:
-                d = [r["perturbation"]["delta"][k] for r in recs if r["perturbation"]["delta"][k] is not None]
-                out["perturbation"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
-        if getattr(args, "harmonics", False):
-            out["harmonics"] = {}
-            for k in audio.HARMONIC_FIGURES:
-                d = [r["harmonics"]["delta"][k] for r in recs if r["harmonics"]["delta"][k] is not None]
-                out["harmonics"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
+        for f in families:
+            out[f.block] = {}
+            for k in f.figures:
+                d = [r[f.block]["delta"][k] for r in recs if r[f.block]["delta"][k] is not None]
+                out[f.block][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
         return out
 
     by_spk = {}

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import formants_ref as R
+import voice_stubs
 from emojivoice_amd import _lib, audio
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -226,37 +227,6 @@ def test_header_declares_and_library_exports_ev_formants():
 
 
 # ---- the CLI, with the device calls stubbed by the restatement --------------------------------------------------------------------------------------
-def _stubs(monkeypatch, wavs):
-    import pitch_ref as P
-    import voice_quality_ref as V
-
-    t = audio.voice_quality_tables(22050, 1024)
-    gv = V.Geometry(1024, 256, 1024, t["q_fit"], t["q_min"], t["q_max"], V.GEOMETRIES[3].bands, 22050)
-    gf = R.geometry(11025.0, 512, 128, 13)
-
-    def fake_yin(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, threshold=0.1, lengths=None):
-        r = P.pitch_yin(y.numpy(), lengths, frame_length, hop_length, 36, 340, threshold)
-        return {"f0": torch.from_numpy(P.f0_from_period(r["period"], sr)).float(), "voiced": torch.from_numpy(r["lag"] > 0)}
-
-    def fake_vq(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, lengths=None, power_floor=1e-7):
-        fr, pk, _, _ = V.batch(y.numpy(), lengths, gv, floor=power_floor)
-        out = {k: torch.from_numpy(fr[..., i].copy()) for i, k in enumerate(audio.VOICE_QUALITY_FIGURES + ("power",))}
-        out["peak_quefrency"] = torch.from_numpy(pk)
-        return out
-
-    def fake_formants(y, sr=22050, max_formant=5500.0, n_formants=4, order=None, frame_length=1024, hop_length=256, f_lo=50.0, lengths=None):
-        x = y.numpy()[:, ::2]                                              # (a plain decimation stands in for the device's resampler)
-        lpc, fm, ct, _, _ = R.batch(x, None if lengths is None else [-(-n // 2) for n in lengths], gf)
-        return {"frequency": torch.from_numpy(fm[..., 0].copy()), "bandwidth": torch.from_numpy(fm[..., 1].copy()), "count": torch.from_numpy(ct),
-                "gain": torch.from_numpy(lpc[..., 13].copy())}
-
-    monkeypatch.setattr(audio, "load_audio", lambda path, sr=22050, device="cuda": torch.from_numpy(wavs[os.path.basename(str(path))]).unsqueeze(0))
-    monkeypatch.setattr(audio, "pitch_yin", fake_yin)
-    monkeypatch.setattr(audio, "voice_quality", fake_vq)
-    monkeypatch.setattr(audio, "formants", fake_formants)
-    return fake_yin, fake_formants
-
-
 def test_voice_report_formants_json_shape_and_validate_args(tmp_path, monkeypatch):
     import argparse
     import json
@@ -264,11 +234,8 @@ def test_voice_report_formants_json_shape_and_validate_args(tmp_path, monkeypatc
     from emojivoice_amd import cli
 
     wavs = {"a.wav": R.speech_like(6000, seed=20, fs=22050), "b.wav": R.speech_like(5000, seed=21, fs=22050), "c.wav": np.zeros(3000, np.float32)}
-    for name in wavs:
-        (tmp_path / name).write_bytes(b"")                                 # (the stubs never open them)
-    flist = tmp_path / "filelist.txt"
-    flist.write_text(f"{tmp_path / 'a.wav'}|7|first\nb.wav|7|second\nc.wav|12|silent take\n", encoding="utf-8")
-    fake_yin, fake_formants = _stubs(monkeypatch, wavs)
+    flist = voice_stubs.filelist(tmp_path, wavs)
+    fake_yin, fake_formants = voice_stubs.base(monkeypatch, wavs), voice_stubs.formants(monkeypatch)
     ns = lambda **kw: argparse.Namespace(voice_report=str(flist), batch_size=2, sample_rate=None, prepare_dataset=None, **kw)
     plain = cli.voice_report(cli.validate_args(ns()), "cpu")
     rep = cli.voice_report(cli.validate_args(ns(formants=True)), "cpu")

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import functionals_ref as R
+import voice_stubs
 from emojivoice_amd import _lib, audio
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -190,18 +191,7 @@ def test_functional_arguments():
 
 
 # ---- the layers above, with the device calls stubbed by the restatements ----------------------------------------------------------------------------------
-def ref_functionals(values, mask=None, lengths=None, percentiles=(0.2, 0.5, 0.8)):
-    """audio.functionals on the host, from the restatement: the same dict, the same dtypes."""
-    (B, K, F), q = audio.functional_arguments(values, mask, lengths, percentiles)
-    m = None if mask is None else (torch.as_tensor(mask) != 0).expand(values.shape).reshape(B, K, F).numpy()
-    r = R.batch(values.reshape(B, K, F).double().numpy(), m, None if lengths is None else [int(n) for n in torch.as_tensor(lengths)], tuple(q))
-    stat, count = torch.from_numpy(r["stat"]), torch.from_numpy(r["count"])
-    nan = torch.tensor(float("nan"), dtype=torch.float64)
-    out = {k: torch.where(count[..., audio._FUNCTIONAL_BEHIND[k]] > 0, stat[..., i], nan) for i, k in enumerate(audio.FUNCTIONAL_STATISTICS)}
-    out["percentiles"] = torch.where(count[..., :1] > 0, stat[..., 12:], nan)
-    out["range"] = out["percentiles"][..., -1] - out["percentiles"][..., 0]
-    out.update({k: count[..., i] for i, k in enumerate(audio.FUNCTIONAL_COUNTS)})
-    return out
+ref_functionals = voice_stubs.ref_functionals
 
 
 def test_voice_functionals_masks_are_those_of_the_statistics_functions(monkeypatch):
@@ -255,40 +245,15 @@ def test_voice_functionals_masks_are_those_of_the_statistics_functions(monkeypat
     assert few["contours"] == ("f0_semitones",) + audio.VOICE_QUALITY_FIGURES and torch.equal(few["cpp_db"]["sd"][:2], vf["cpp_db"]["sd"][:2])
 
 
-def _stubs(monkeypatch, wavs):
-    import pitch_ref
-    import voice_quality_ref as V
-
-    t = audio.voice_quality_tables(22050, 1024)
-    gv = V.Geometry(1024, 256, 1024, t["q_fit"], t["q_min"], t["q_max"], V.GEOMETRIES[3].bands, 22050)
-
-    def fake_yin(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, threshold=0.1, lengths=None):
-        r = pitch_ref.pitch_yin(y.numpy(), lengths, frame_length, hop_length, 36, 340, threshold)
-        return {"f0": torch.from_numpy(pitch_ref.f0_from_period(r["period"], sr)).float(), "voiced": torch.from_numpy(r["lag"] > 0)}
-
-    def fake_vq(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, lengths=None, power_floor=1e-7):
-        fr, pk, _, _ = V.batch(y.numpy(), lengths, gv, floor=power_floor)
-        out = {k: torch.from_numpy(fr[..., i].copy()) for i, k in enumerate(audio.VOICE_QUALITY_FIGURES + ("power",))}
-        out["peak_quefrency"] = torch.from_numpy(pk)
-        return out
-
-    monkeypatch.setattr(audio, "load_audio", lambda path, sr=22050, device="cuda": torch.from_numpy(wavs[os.path.basename(str(path))]).unsqueeze(0))
-    monkeypatch.setattr(audio, "pitch_yin", fake_yin)
-    monkeypatch.setattr(audio, "voice_quality", fake_vq)
-    monkeypatch.setattr(audio, "functionals", ref_functionals)
-
-
 def test_voice_report_functionals_json_shape_and_validate_args(tmp_path, monkeypatch):
     import perturbation_ref as P
     from emojivoice_amd import cli
 
     wavs = {"a.wav": P.perturbed_pulses(6000, 120.0, 0.01, 0.05, seed=20), "b.wav": P.perturbed_pulses(5000, 150.0, 0.005, 0.1, seed=21),
             "c.wav": np.zeros(3000, np.float32)}
-    for name in wavs:
-        (tmp_path / name).write_bytes(b"")                                 # (the stubs never open them)
-    flist = tmp_path / "filelist.txt"
-    flist.write_text(f"{tmp_path / 'a.wav'}|7|first\nb.wav|7|second\nc.wav|12|silent take\n", encoding="utf-8")
-    _stubs(monkeypatch, wavs)
+    flist = voice_stubs.filelist(tmp_path, wavs)
+    voice_stubs.base(monkeypatch, wavs)
+    monkeypatch.setattr(audio, "functionals", ref_functionals)
     ns = lambda **kw: argparse.Namespace(voice_report=str(flist), batch_size=2, sample_rate=None, prepare_dataset=None, **kw)
     plain = cli.voice_report(cli.validate_args(ns()), "cpu")
     rep = cli.voice_report(cli.validate_args(ns(functionals=True)), "cpu")
@@ -330,3 +295,48 @@ def test_voice_report_functionals_json_shape_and_validate_args(tmp_path, monkeyp
     with pytest.raises(AssertionError, match="--functionals"):
         cli.validate_args(argparse.Namespace(functionals=True, evaluate_pairs=None, voice_report=None, sample_rate=None, prepare_dataset=None))
     cli.validate_args(ns(functionals=True, formants=True, perturbation=True, harmonics=True, pitch_method="pyin"))
+
+
+def test_voice_report_with_every_flag_is_the_single_flag_reports_side_by_side(tmp_path, monkeypatch):
+    """Every file's, every speaker's and the overall record of a run with all flags is, key for key and in key order, the plain record followed by
+    the blocks of --formants, --perturbation, --harmonics and --functionals as each single-flag run writes them (the functionals block gains contours
+    with each flag: there the single-flag run's contours are compared), and audio.formants runs once per batch."""
+    import perturbation_ref as P
+    from emojivoice_amd import cli
+
+    wavs = {"a.wav": P.perturbed_pulses(6000, 120.0, 0.01, 0.05, seed=20), "b.wav": P.perturbed_pulses(5000, 150.0, 0.005, 0.1, seed=21),
+            "c.wav": np.zeros(3000, np.float32)}
+    flist = voice_stubs.filelist(tmp_path, wavs)
+    voice_stubs.base(monkeypatch, wavs)
+    _, calls = voice_stubs.flat_formants(monkeypatch)
+    voice_stubs.perturbation(monkeypatch)
+    voice_stubs.harmonics(monkeypatch)
+    monkeypatch.setattr(audio, "functionals", ref_functionals)
+    run = lambda **kw: cli.voice_report(cli.validate_args(argparse.Namespace(voice_report=str(flist), batch_size=2, sample_rate=None, prepare_dataset=None, **kw)), "cpu")
+    records = lambda rep: rep["files"] + list(rep["speakers"].values()) + [rep["overall"]]
+    flags = ("formants", "perturbation", "harmonics", "functionals")
+    plain = run()
+    single = {flag: run(**{flag: True}) for flag in flags}
+    before = calls["formants"]
+    every = run(**{flag: True for flag in flags})
+    assert calls["formants"] - before == 2, "two batches: the formants are analysed once per batch for --formants, --harmonics and --functionals"
+    with open(f"{flist}.voice.json") as f:
+        assert json.load(f) == json.loads(json.dumps(every))
+    assert list(every) == list(plain) and list(every["speakers"]) == list(plain["speakers"]) == ["7", "12"] and len(records(every)) == 6
+    contours = ("f0_semitones",) + audio.VOICE_QUALITY_FIGURES + audio.FORMANT_FIGURES + audio.PERTURBATION_FIGURES + audio.HARMONIC_FIGURES
+    for i, (got, base) in enumerate(zip(records(every), records(plain))):
+        want = dict(base)
+        for flag in flags:
+            one = records(single[flag])[i]
+            assert list(one)[:len(base)] == list(base) and all(one[k] == base[k] for k in base), "a single flag appends its block to the plain record"
+            assert len(one) > len(base) and not (set(one) - set(base)) & set(want), "no two flags write the same key"
+            want.update({k: v for k, v in one.items() if k not in base})
+        assert list(got) == list(want), i
+        assert all(got[k] == want[k] for k in want if k != "functionals"), i
+        assert tuple(got["functionals"]) == contours and list(want["functionals"]) == list(contours[:6])
+        assert {c: got["functionals"][c] for c in want["functionals"]} == want["functionals"], i
+        assert all(tuple(v) == cli.FUNCTIONAL_REPORT_KEYS for v in got["functionals"].values())
+    for flag, own in zip(flags[:3], (audio.FORMANT_FIGURES, audio.PERTURBATION_FIGURES, audio.HARMONIC_FIGURES)):    # the contours a flag brings
+        both = run(**{flag: True, "functionals": True})
+        for got, part in zip(records(every), records(both)):
+            assert tuple(part["functionals"]) == contours[:6] + own and all(got["functionals"][c] == part["functionals"][c] for c in own), flag

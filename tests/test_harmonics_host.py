@@ -19,7 +19,7 @@ import pytest
 import torch
 
 import harmonics_ref as R
-import pitch_ref
+import voice_stubs
 from emojivoice_amd import _lib, audio
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -212,15 +212,42 @@ def test_cli_helpers_on_hand_made_rows():
     figs = audio.HARMONIC_FIGURES
     st = {"frames": torch.tensor([5, 0]), "used": {k: torch.tensor([i + 1, 0]) for i, k in enumerate(figs)},
           "sums": {k: torch.tensor([2.0 * (i + 1), 0.0], dtype=torch.float64) for i, k in enumerate(figs)}}
-    rows = cli.harmonic_rows(st)
+    family = {f.block: f for f in cli.report_families()}["harmonics"]
+    assert family.figures == figs and family.frames_key == "harmonic_frames" and family.counts == ()
+    rows = cli.family_rows(st, family)
     assert rows == [{"frames": 5, "used": {k: i + 1 for i, k in enumerate(figs)}, "sums": {k: 2.0 * (i + 1) for i, k in enumerate(figs)}},
                     {"frames": 0, "used": {k: 0 for k in figs}, "sums": {k: 0.0 for k in figs}}]
-    assert cli.harmonic_means(rows[:1]) == {**{k: 2.0 for k in figs}, "harmonic_frames": 5}
-    assert cli.harmonic_means(rows[1:]) == {**{k: None for k in figs}, "harmonic_frames": 0}
+    assert cli.family_means(rows[:1], family) == {**{k: 2.0 for k in figs}, "harmonic_frames": 5}
+    assert cli.family_means(rows[1:], family) == {**{k: None for k in figs}, "harmonic_frames": 0}
     other = {"frames": 3, "used": {k: 1 for k in figs}, "sums": {k: -4.0 for k in figs}}
-    m = cli.harmonic_means([rows[0], other, rows[1]])
+    m = cli.family_means([rows[0], other, rows[1]], family)
     assert m["harmonic_frames"] == 8 and all(abs(m[k] - (2.0 * (i + 1) - 4.0) / (i + 2)) < 1e-12 for i, k in enumerate(figs))
-    assert cli.harmonic_means([]) == {**{k: None for k in figs}, "harmonic_frames": 0}
+    assert cli.family_means([], family) == {**{k: None for k in figs}, "harmonic_frames": 0}
+
+
+def test_cli_helpers_on_hand_made_formant_rows():
+    """The same hand-made case for the formants family: unconverged_frames is summed, and f_i and b_i share used[:, i]."""
+    from emojivoice_amd import cli
+
+    figs = audio.FORMANT_FIGURES
+    family = {f.block: f for f in cli.report_families()}["formants"]
+    assert family.figures == figs and family.frames_key == "formant_frames" and family.counts == ("unconverged_frames",)
+    st = {"frames": torch.tensor([5, 0]), "unconverged_frames": torch.tensor([2, 1]), "used": torch.tensor([[1, 2, 4], [0, 0, 0]]),
+          "sums": {k: torch.tensor([3.0 * (i + 1), 0.0], dtype=torch.float64) for i, k in enumerate(figs)}}
+    used = {k: (1, 2, 4)[int(k[1]) - 1] for k in figs}
+    rows = cli.family_rows(st, family)
+    assert rows == [{"frames": 5, "unconverged_frames": 2, "used": used, "sums": {k: 3.0 * (i + 1) for i, k in enumerate(figs)}},
+                    {"frames": 0, "unconverged_frames": 1, "used": {k: 0 for k in figs}, "sums": {k: 0.0 for k in figs}}]
+    assert used["f2_hz"] == used["b2_hz"] == 2 and used["f3_hz"] == used["b3_hz"] == 4
+    one = cli.family_means(rows[:1], family)
+    assert one == {**{k: 3.0 * (i + 1) / used[k] for i, k in enumerate(figs)}, "formant_frames": 5, "unconverged_frames": 2}
+    assert list(one) == list(figs) + ["formant_frames", "unconverged_frames"], "the order of the report's keys"
+    assert cli.family_means(rows[1:], family) == {**{k: None for k in figs}, "formant_frames": 0, "unconverged_frames": 1}
+    other = {"frames": 3, "unconverged_frames": 4, "used": {k: 1 for k in figs}, "sums": {k: -4.0 for k in figs}}
+    m = cli.family_means([rows[0], other, rows[1]], family)
+    assert m["formant_frames"] == 8 and m["unconverged_frames"] == 7
+    assert all(abs(m[k] - (3.0 * (i + 1) - 4.0) / (used[k] + 1)) < 1e-12 for i, k in enumerate(figs))
+    assert cli.family_means([], family) == {**{k: None for k in figs}, "formant_frames": 0, "unconverged_frames": 0}
 
 
 # ---- the C ABI -----------------------------------------------------------------------------------------------------------------------------------------
@@ -257,52 +284,9 @@ HARM_KEYS = set(audio.HARMONIC_FIGURES) | {"harmonic_frames"}
 
 
 def _stubs(monkeypatch, wavs):
-    import voice_quality_ref as V
-
-    t = audio.voice_quality_tables(22050, 1024)
-    gv = V.Geometry(1024, 256, 1024, t["q_fit"], t["q_min"], t["q_max"], V.GEOMETRIES[3].bands, 22050)
-    calls = {"formants": 0}
-
-    def yin(y, lengths, hop_length, frame_length=1024):
-        return pitch_ref.pitch_yin(y.numpy(), lengths, frame_length, hop_length, 36, 340, 0.1)
-
-    def fake_yin(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, threshold=0.1, lengths=None):
-        r = yin(y, lengths, hop_length, frame_length)
-        return {"f0": torch.from_numpy(pitch_ref.f0_from_period(r["period"], sr)).float(), "voiced": torch.from_numpy(r["lag"] > 0)}
-
-    def fake_vq(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, lengths=None, power_floor=1e-7):
-        fr, pk, _, _ = V.batch(y.numpy(), lengths, gv, floor=power_floor)
-        out = {k: torch.from_numpy(fr[..., i].copy()) for i, k in enumerate(audio.VOICE_QUALITY_FIGURES + ("power",))}
-        out["peak_quefrency"] = torch.from_numpy(pk)
-        return out
-
-    def fake_formants(y, sr=22050, max_formant=5500.0, n_formants=4, order=None, frame_length=1024, hop_length=256, f_lo=50.0, lengths=None,
-                      power_floor=1e-10):
-        calls["formants"] += 1
-        B, F = y.shape[0], R.frames(y.shape[1], hop_length)
-        freq = torch.tensor([520.0, 1480.0, 2530.0, 3600.0], dtype=torch.float64).expand(B, F, 4).clone()
-        band = torch.full((B, F, 4), 120.0, dtype=torch.float64)
-        band[:, ::5, 1] = 900.0                                           # F2 too wide on every fifth frame
-        return {"frequency": freq, "bandwidth": band, "count": torch.full((B, F), 4, dtype=torch.int32)}
-
-    def fake_harmonics(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, lengths=None, period=None, formants=None, n_harm=48,
-                       search=0.25, min_spacing=4.0, a3_range=0.1, power_floor=1e-7):
-        assert formants is not None and formants is not False, "the CLI hands the formants over"
-        x = y.numpy()
-        g = R.Geometry(frame_length, hop_length, frame_length, sr, n_harm, search, min_spacing, a3_range)
-        fm = np.stack([formants["frequency"].numpy(), formants["bandwidth"].numpy()], axis=-1)
-        r = R.batch(x, lengths, yin(y, lengths, hop_length, frame_length)["period"], g, fm, formants["count"].numpy(), floor=power_floor)
-        out = {k: torch.from_numpy(r["frame"][..., i].copy()) for i, k in enumerate(audio._HARMONIC_FRAME)}
-        out.update(n_harmonics=torch.from_numpy(r["count"][..., 0].copy()), flags=torch.from_numpy(r["count"][..., 1].copy()),
-                   harmonic_hz=torch.from_numpy(r["harm"][..., 0].copy()), harmonic_db=torch.from_numpy(r["harm"][..., 1].copy()))
-        return out
-
-    monkeypatch.setattr(audio, "load_audio", lambda path, sr=22050, device="cuda": torch.from_numpy(wavs[os.path.basename(str(path))]).unsqueeze(0))
-    monkeypatch.setattr(audio, "pitch_yin", fake_yin)
-    monkeypatch.setattr(audio, "voice_quality", fake_vq)
-    monkeypatch.setattr(audio, "formants", fake_formants)
-    monkeypatch.setattr(audio, "harmonics", fake_harmonics)
-    return fake_yin, fake_formants, fake_harmonics, calls
+    fake_yin = voice_stubs.base(monkeypatch, wavs)
+    fake_formants, calls = voice_stubs.flat_formants(monkeypatch)
+    return fake_yin, fake_formants, voice_stubs.harmonics(monkeypatch), calls
 
 
 def _wavs():
@@ -313,10 +297,7 @@ def test_voice_report_harmonics_json_shape_and_validate_args(tmp_path, monkeypat
     from emojivoice_amd import cli
 
     wavs = _wavs()
-    for name in wavs:
-        (tmp_path / name).write_bytes(b"")                                 # (the stubs never open them)
-    flist = tmp_path / "filelist.txt"
-    flist.write_text(f"{tmp_path / 'a.wav'}|7|first\nb.wav|7|second\nc.wav|12|silent take\n", encoding="utf-8")
+    flist = voice_stubs.filelist(tmp_path, wavs)
     fake_yin, fake_fm, fake_hm, calls = _stubs(monkeypatch, wavs)
     ns = lambda **kw: argparse.Namespace(voice_report=str(flist), batch_size=2, sample_rate=None, prepare_dataset=None, **kw)
     plain = cli.voice_report(cli.validate_args(ns()), "cpu")

@@ -21,6 +21,7 @@ import torch
 import perturbation_ref as R
 import pitch_ref
 import stoi_ref
+import voice_stubs
 from emojivoice_amd import _lib, audio
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -188,38 +189,6 @@ def test_header_declares_and_library_exports_ev_perturbation():
 
 
 # ---- the CLI, with the device calls stubbed by the restatements ------------------------------------------------------------------------------------------
-def _stubs(monkeypatch, wavs):
-    import voice_quality_ref as V
-
-    t = audio.voice_quality_tables(22050, 1024)
-    gv = V.Geometry(1024, 256, 1024, t["q_fit"], t["q_min"], t["q_max"], V.GEOMETRIES[3].bands, 22050)
-
-    def fake_yin(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, threshold=0.1, lengths=None):
-        r = pitch_ref.pitch_yin(y.numpy(), lengths, frame_length, hop_length, 36, 340, threshold)
-        return {"f0": torch.from_numpy(pitch_ref.f0_from_period(r["period"], sr)).float(), "voiced": torch.from_numpy(r["lag"] > 0)}
-
-    def fake_vq(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, lengths=None, power_floor=1e-7):
-        fr, pk, _, _ = V.batch(y.numpy(), lengths, gv, floor=power_floor)
-        out = {k: torch.from_numpy(fr[..., i].copy()) for i, k in enumerate(audio.VOICE_QUALITY_FIGURES + ("power",))}
-        out["peak_quefrency"] = torch.from_numpy(pk)
-        return out
-
-    def fake_perturbation(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, lengths=None, lag=None, n_cycles=3,
-                          period_factor=1.3, amplitude_factor=1.6, power_floor=1e-10):
-        x = y.numpy()
-        lag = pitch_ref.pitch_yin(x, lengths, frame_length, hop_length, 36, 340, 0.1)["lag"]
-        r = R.batch(x, lengths, lag, R.geo(hop_length, frame_length, n_cycles, period_factor, amplitude_factor, power_floor))
-        out = {k: torch.from_numpy(r["frame"][..., i].copy()) for i, k in enumerate(audio._PERTURBATION_FRAME)}
-        out.update(count=torch.from_numpy(r["count"]), marks=torch.from_numpy(r["marks"]), lag=torch.from_numpy(lag))
-        return out
-
-    monkeypatch.setattr(audio, "load_audio", lambda path, sr=22050, device="cuda": torch.from_numpy(wavs[os.path.basename(str(path))]).unsqueeze(0))
-    monkeypatch.setattr(audio, "pitch_yin", fake_yin)
-    monkeypatch.setattr(audio, "voice_quality", fake_vq)
-    monkeypatch.setattr(audio, "perturbation", fake_perturbation)
-    return fake_yin, fake_perturbation
-
-
 def test_voice_report_perturbation_json_shape_and_validate_args(tmp_path, monkeypatch):
     import argparse
     import json
@@ -228,11 +197,8 @@ def test_voice_report_perturbation_json_shape_and_validate_args(tmp_path, monkey
 
     wavs = {"a.wav": R.perturbed_pulses(6000, 120.0, 0.01, 0.05, seed=20), "b.wav": R.perturbed_pulses(5000, 150.0, 0.005, 0.1, seed=21),
             "c.wav": np.zeros(3000, np.float32)}
-    for name in wavs:
-        (tmp_path / name).write_bytes(b"")                                 # (the stubs never open them)
-    flist = tmp_path / "filelist.txt"
-    flist.write_text(f"{tmp_path / 'a.wav'}|7|first\nb.wav|7|second\nc.wav|12|silent take\n", encoding="utf-8")
-    fake_yin, fake_pt = _stubs(monkeypatch, wavs)
+    flist = voice_stubs.filelist(tmp_path, wavs)
+    fake_yin, fake_pt = voice_stubs.base(monkeypatch, wavs), voice_stubs.perturbation(monkeypatch)
     ns = lambda **kw: argparse.Namespace(voice_report=str(flist), batch_size=2, sample_rate=None, prepare_dataset=None, **kw)
     plain = cli.voice_report(cli.validate_args(ns()), "cpu")
     rep = cli.voice_report(cli.validate_args(ns(perturbation=True)), "cpu")

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import voice_quality_ref as R
+import voice_stubs
 from emojivoice_amd import _lib, audio
 
 try:
@@ -227,26 +228,10 @@ def test_voice_report_json_shape_and_validate_args(tmp_path, monkeypatch):
     from emojivoice_amd import cli
 
     wavs = {"a.wav": R.speech_like(6000, seed=20, fs=R.FS), "b.wav": R.speech_like(5000, seed=21, fs=R.FS), "c.wav": np.zeros(3000, np.float32)}
-    for name in wavs:
-        (tmp_path / name).write_bytes(b"")                                 # (the stubs below never open them)
-    flist = tmp_path / "filelist.txt"
-    flist.write_text(f"{tmp_path / 'a.wav'}|7|first\nb.wav|7|second\nc.wav|12|silent take\n", encoding="utf-8")
+    flist = voice_stubs.filelist(tmp_path, wavs)
     t = audio.voice_quality_tables(22050, 1024)
-    g = R.Geometry(1024, 256, 1024, t["q_fit"], t["q_min"], t["q_max"], BIG.bands, 22050)
-
-    def fake_yin(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, threshold=0.1, lengths=None):
-        r = P.pitch_yin(y.numpy(), lengths, frame_length, hop_length, 36, 340, threshold)
-        return {"f0": torch.from_numpy(P.f0_from_period(r["period"], sr)).float(), "voiced": torch.from_numpy(r["lag"] > 0)}
-
-    def fake_vq(y, sr=22050, fmin=65.0, fmax=600.0, frame_length=1024, hop_length=256, lengths=None, power_floor=1e-7):
-        fr, pk, _, _ = R.batch(y.numpy(), lengths, g, floor=power_floor)
-        out = {k: torch.from_numpy(fr[..., i].copy()) for i, k in enumerate(audio.VOICE_QUALITY_FIGURES + ("power",))}
-        out["peak_quefrency"] = torch.from_numpy(pk)
-        return out
-
-    monkeypatch.setattr(audio, "load_audio", lambda path, sr=22050, device="cuda": torch.from_numpy(wavs[os.path.basename(str(path))]).unsqueeze(0))
-    monkeypatch.setattr(audio, "pitch_yin", fake_yin)
-    monkeypatch.setattr(audio, "voice_quality", fake_vq)
+    g = R.Geometry(1024, 256, 1024, t["q_fit"], t["q_min"], t["q_max"], BIG.bands, 22050)       # (the geometry voice_stubs.base analyses at)
+    voice_stubs.base(monkeypatch, wavs)
     args = cli.validate_args(argparse.Namespace(voice_report=str(flist), batch_size=2, sample_rate=None, prepare_dataset=None))
     rep = cli.voice_report(args, "cpu")
     with open(f"{flist}.voice.json") as f:

@@ -43,6 +43,7 @@ EXPORTS = [
     "ev_perturbation",
     "ev_load_harmonics", "ev_harmonics",
     "ev_functionals",
+    "ev_load_auditory", "ev_auditory",
 ]
 
 
@@ -176,6 +177,8 @@ def load_library() -> C.CDLL:
     lib.ev_load_harmonics.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, i32, C.c_double, C.c_double, C.c_double]
     lib.ev_harmonics.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_functionals.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]
+    lib.ev_load_auditory.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, C.c_double]
+    lib.ev_auditory.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -663,6 +666,44 @@ class Engine:
         self._check(self.lib.ev_harmonics(self.h, x.data_ptr(), _ptr(ln), B, L, period.data_ptr(), _ptr(formant), _ptr(fcount), nform,
                                           float(power_floor), frame.data_ptr(), count.data_ptr(), _ptr(harm), _stream_ptr()), "ev_harmonics")
         return frame, count, harm
+
+    def load_auditory(self, window, twiddle, H: int, nfft: int, mel_w, eq, dct, k_lo: int, k_hi: int, compress: float) -> None:
+        """One geometry of ``auditory`` (ev_load_auditory), the tables on the host (``audio.auditory_tables`` makes them): ``window`` (W,)
+        float64, ``twiddle`` (nfft, 2) float64 {cos, sin}(2 pi n / nfft), ``H`` the hop, ``mel_w`` (nfft / 2 + 1, n_mel) float64 (no entry
+        negative), ``eq`` (n_mel,) float64 (every entry positive), ``dct`` (n_mel, n_ceps) float64 (it carries the lifter), the bins
+        [k_lo, k_hi) of the spectral flux and the exponent ``compress`` of the loudness.  The handle builds the windowed DFT basis on the
+        device."""
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float64).reshape(-1))
+        tw = np.ascontiguousarray(np.asarray(twiddle, dtype=np.float64).reshape(-1, 2))
+        mw = np.ascontiguousarray(np.asarray(mel_w, dtype=np.float64))
+        e = np.ascontiguousarray(np.asarray(eq, dtype=np.float64).reshape(-1))
+        d = np.ascontiguousarray(np.asarray(dct, dtype=np.float64))
+        NB = int(nfft) // 2 + 1
+        if tw.shape[0] != int(nfft) or mw.ndim != 2 or mw.shape[0] != NB or d.ndim != 2 or e.size != mw.shape[1] or d.shape[0] != mw.shape[1]:
+            raise ValueError(f"load_auditory: {nfft} twiddles, mel_w ({NB}, n_mel), eq (n_mel,) and dct (n_mel, n_ceps) expected, got "
+                             f"{tw.shape[0]}, {tuple(mw.shape)}, {tuple(e.shape)} and {tuple(d.shape)}")
+        self._check(self.lib.ev_load_auditory(self.h, w.ctypes.data, tw.ctypes.data, int(w.shape[0]), int(H), int(nfft), mw.ctypes.data,
+                                              int(mw.shape[1]), e.ctypes.data, d.ctypes.data, int(d.shape[1]), int(k_lo), int(k_hi),
+                                              float(compress)), "ev_load_auditory")
+        self.auditory_geometry = (int(w.shape[0]), int(H), int(nfft), int(mw.shape[1]), int(d.shape[1]))
+
+    def auditory(self, x, lengths, power_floor: float, want_bands: bool = False):
+        """The auditory descriptors of every frame of every row of ``x`` (B, L) at the loaded geometry (ev_auditory, after load_auditory): a
+        dict of device tensors {"frame" (B, NF, 4) float64: per frame {loudness, spectral flux, power, log(max(power, floor))}; "mfcc" (B, NF,
+        n_ceps) float64; "flags" (B, NF) int32: 1 the frame is live, 2 it has a predecessor; "bands" (B, NF, n_mel) float64 or None: the mel
+        band energies}, NF = ceil(L / H).  ``lengths`` (B,): samples per row (None: L)."""
+        if not hasattr(self, "auditory_geometry"):
+            raise EvLibraryError("auditory: tables not loaded (load_auditory)")
+        x, B, L, ln = self._rows(x, lengths, "auditory")
+        _, H, _, n_mel, n_ceps = self.auditory_geometry
+        NF = -(-L // H)
+        frame = torch.empty((B, NF, 4), dtype=torch.float64, device=x.device)
+        mfcc = torch.empty((B, NF, n_ceps), dtype=torch.float64, device=x.device)
+        flags = torch.empty((B, NF), dtype=torch.int32, device=x.device)
+        bands = torch.empty((B, NF, n_mel), dtype=torch.float64, device=x.device) if want_bands else None
+        self._check(self.lib.ev_auditory(self.h, x.data_ptr(), _ptr(ln), B, L, float(power_floor), frame.data_ptr(), mfcc.data_ptr(),
+                                         flags.data_ptr(), _ptr(bands), _stream_ptr()), "ev_auditory")
+        return {"frame": frame, "mfcc": mfcc, "flags": flags, "bands": bands}
 
     def functionals(self, v, mask=None, lengths=None, q=(0.2, 0.5, 0.8)):
         """The functionals of every contour of ``v`` (B, K, F) float64 on the device (ev_functionals; no load step): (stat (B, K, 12 + NQ)

@@ -929,10 +929,10 @@ def voice_quality(y, sr: int = 22050, fmin: float = 65.0, fmax: float = 600.0, f
     return out
 
 
-# The four figure families of the voice report (voice quality, formants, perturbation, harmonics), each described once and shared by its
+# The five figure families of the voice report (voice quality, formants, perturbation, harmonics, auditory), each described once and shared by its
 # ``*_statistics`` function and ``voice_functionals``: ``_coerced`` brings what a family reads of its analysis function's dict to one device,
 # ``_inside`` gives the rows their batch axis and their lengths, a ``_*_contours`` function turns the tensors and the base mask ``use`` (voiced
-# and inside the row) into (the family's frames mask, {figure: (values (B, F) float64, the frames behind the figure (B, F) bool)}) in the order
+# and inside the row; for the auditory family, which is not a matter of the voiced frames alone, inside the row) into (the family's frames mask, {figure: (values (B, F) float64, the frames behind the figure (B, F) bool)}) in the order
 # of the family's ``*_FIGURES``, and ``_reduce`` sums every contour under its mask.
 def _coerced(d, lead: str, f64=(), dev=None, voiced=None):
     """{``lead``: d[lead] as it is, every key of ``f64`` as float64, "voiced": ``voiced`` as bool when given}, where d[lead] lives (``dev``:
@@ -1265,6 +1265,154 @@ def harmonic_statistics(hm, voiced, lengths=None, fm=None, max_bandwidth: float 
     return {"frames": r["frames"], "used": r["used"], "sums": r["sums"], **r["means"]}
 
 
+AUDITORY_POWER_FLOOR = 1e-7                        # the clamp of the band energies before the logarithm and the power law, ``voice_quality``'s
+AUDITORY_COMPRESS = 0.33                           # the exponent of the loudness: the cube-root law of Hermansky 1990 as openSMILE's cPlp rounds it
+_AUDITORY_CONTOURS = ("loudness", "spectral_flux", "spectral_flux_voiced", "spectral_flux_unvoiced", "mfcc_1", "mfcc_2", "mfcc_3", "mfcc_4",
+                      "mfcc_1_voiced", "mfcc_2_voiced", "mfcc_3_voiced", "mfcc_4_voiced")
+AUDITORY_FIGURES = _AUDITORY_CONTOURS + ("equivalent_level_db",)
+_AUDITORY_FRAME = ("loudness", "spectral_flux", "power", "log_energy")
+
+
+def htk_mel(f):
+    """The HTK mel scale, 2595 log10(1 + f / 700)."""
+    return 2595.0 * np.log10(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+
+
+def htk_mel_to_hz(m):
+    return 700.0 * (10.0 ** (np.asarray(m, dtype=np.float64) / 2595.0) - 1.0)
+
+
+def equal_loudness(f):
+    """The equal-loudness weight of Hermansky 1990 (eq. 4) at ``f`` Hz: ((w^2 + 56.8e6) w^4) / ((w^2 + 6.3e6)^2 (w^2 + 0.38e9)), w = 2 pi f."""
+    w2 = (2.0 * np.pi * np.asarray(f, dtype=np.float64)) ** 2
+    return (w2 + 56.8e6) * w2 * w2 / ((w2 + 6.3e6) ** 2 * (w2 + 0.38e9))
+
+
+def auditory_tables(sr: int, n_fft: int, n_mels: int = 26, fmin: float = 20.0, fmax: float = 8000.0, n_ceps: int = 4, lifter: float = 22.0,
+                    flux_band=(0.0, None)) -> Dict:
+    """The host tables of ``ev_load_auditory`` at rate ``sr``, float64 numpy: {"mel_w" (n_fft / 2 + 1, n_mels): triangular filters on the POWER
+    spectrum whose corners are n_mels + 2 points equally spaced on the HTK mel scale from ``fmin`` to ``fmax``, linear in mel between them (HTK's
+    and openSMILE's cMelspec: adjacent triangles sum to 1 between the first and the last centre); "centres_hz" (n_mels,); "eq" (n_mels,): the
+    equal-loudness weights of Hermansky 1990 at the centres; "dct" (n_mels, n_ceps): the DCT-II columns i = 1 .. n_ceps, sqrt(2 / n_mels)
+    cos(pi i (m + 1 / 2) / n_mels), times the HTK lifter 1 + lifter / 2 sin(pi i / lifter) (``lifter`` 0: none) - column 0, the level, is left
+    out: a gain moves nothing else; "k_lo", "k_hi": the bins [ceil(lo n_fft / sr), ceil(hi n_fft / sr)) of the spectral flux, ``flux_band`` =
+    (lo, hi) in Hz (hi None: up to and including the Nyquist bin); "compress": 0.33}.  ValueError on arguments ``ev_load_auditory`` would refuse,
+    on a band without a bin and on a flux range without one: everything is checked here, without a device."""
+    sr, n_fft, n_mels, n_ceps = int(sr), int(n_fft), int(n_mels), int(n_ceps)
+    if sr < 1 or n_fft < 16 or n_fft > 1024 or n_fft % 2:
+        raise ValueError(f"auditory_tables: sr={sr} must be positive and n_fft={n_fft} even with 16 <= n_fft <= 1024")
+    if not 1 <= n_mels <= 64:
+        raise ValueError(f"auditory_tables: n_mels={n_mels} outside 1 <= n_mels <= 64")
+    if not 1 <= n_ceps <= min(16, max(n_mels - 1, 1)):
+        raise ValueError(f"auditory_tables: n_ceps={n_ceps} outside 1 <= n_ceps <= min(16, n_mels - 1) = {min(16, max(n_mels - 1, 1))}")
+    if not (math.isfinite(fmin) and math.isfinite(fmax) and 0.0 <= fmin < fmax <= sr / 2.0):
+        raise ValueError(f"auditory_tables: 0 <= fmin < fmax <= sr / 2 expected (got fmin={fmin} fmax={fmax} sr={sr})")
+    if not (math.isfinite(lifter) and (lifter == 0.0 or lifter >= 1.0)):
+        raise ValueError(f"auditory_tables: lifter={lifter} must be 0 (none) or at least 1")
+    NB = n_fft // 2 + 1
+    lo, hi = flux_band
+    if not (math.isfinite(lo) and lo >= 0.0 and (hi is None or (math.isfinite(hi) and hi > lo))):
+        raise ValueError(f"auditory_tables: flux_band={flux_band} must be (lo, hi) in Hz with 0 <= lo < hi, or hi None")
+    k_lo = int(math.ceil(lo * n_fft / sr))
+    k_hi = NB if hi is None else min(NB, int(math.ceil(hi * n_fft / sr)))
+    if not 0 <= k_lo < k_hi:
+        raise ValueError(f"auditory_tables: flux_band={flux_band} holds no bin at sr={sr}, n_fft={n_fft} (bins [{k_lo}, {k_hi}))")
+    corners = np.linspace(float(htk_mel(fmin)), float(htk_mel(fmax)), n_mels + 2)
+    mel_k = htk_mel(np.arange(NB, dtype=np.float64) * sr / n_fft)[:, None]
+    left, centre, right = corners[None, :-2], corners[None, 1:-1], corners[None, 2:]
+    mel_w = np.maximum(0.0, np.minimum((mel_k - left) / (centre - left), (right - mel_k) / (right - centre)))
+    empty = np.flatnonzero(~(mel_w > 0.0).any(axis=0))
+    if empty.size:
+        raise ValueError(f"auditory_tables: band {int(empty[0])} of {n_mels} from {fmin} to {fmax} Hz holds no bin at sr={sr}, n_fft={n_fft}: "
+                         "fewer bands, a higher fmin or a longer n_fft")
+    centres = htk_mel_to_hz(corners[1:-1])
+    i = np.arange(1, n_ceps + 1, dtype=np.float64)[None, :]
+    dct = math.sqrt(2.0 / n_mels) * np.cos(np.pi * i * (np.arange(n_mels, dtype=np.float64)[:, None] + 0.5) / n_mels)
+    if lifter:
+        dct = dct * (1.0 + 0.5 * lifter * np.sin(np.pi * i / lifter))
+    return {"mel_w": np.ascontiguousarray(mel_w), "centres_hz": centres, "eq": equal_loudness(centres), "dct": np.ascontiguousarray(dct),
+            "k_lo": k_lo, "k_hi": k_hi, "compress": AUDITORY_COMPRESS}
+
+
+def _auditory_engine(device: torch.device, sr: int, n_fft: int, hop: int, n_mels: int, fmin: float, fmax: float, n_ceps: int, lifter: float,
+                     flux_band) -> Engine:
+    def load(eng):
+        t = auditory_tables(sr, n_fft, n_mels, fmin, fmax, n_ceps, lifter, flux_band)
+        eng.load_auditory(stft_dist_window(n_fft), stoi_twiddle(n_fft), hop, n_fft, t["mel_w"], t["eq"], t["dct"], t["k_lo"], t["k_hi"], t["compress"])
+    band = (float(flux_band[0]), None if flux_band[1] is None else float(flux_band[1]))
+    return _cached_engine(device, ("auditory", int(sr), int(n_fft), int(hop), int(n_mels), float(fmin), float(fmax), int(n_ceps), float(lifter), band), load)
+
+
+@torch.inference_mode()
+def auditory(y, sr: int = 22050, frame_length: int = 1024, hop_length: int = 256, lengths=None, n_mels: int = 26, fmin: float = 20.0,
+             fmax: float = 8000.0, n_ceps: int = 4, lifter: float = 22.0, flux_band=(0.0, None), power_floor: float = AUDITORY_POWER_FLOOR):
+    """Timbre and dynamics per frame on the device (``ev_auditory``; no torch fallback; eGeMAPS, Eyben et al. 2016, is the model): from the float64
+    power spectrum of every frame (``voice_quality``'s: periodic Hann window of ``frame_length`` = n_fft points, zeros outside the row) the
+    energies of ``n_mels`` HTK mel bands between ``fmin`` and ``fmax`` (clamped at ``power_floor``), and from them the loudness (the sum over the
+    bands of (equal-loudness weight x energy)^0.33), the cepstral coefficients 1 .. ``n_ceps`` (DCT-II of the log energies, HTK lifter
+    ``lifter``), and beside them the spectral flux (the rms difference of the magnitude spectrum to the frame before, over the bins of
+    ``flux_band`` Hz), the power and its logarithm (``auditory_tables`` has the details).  Frame f is ``pitch_yin``'s frame f at the same hop.
+    ``y`` 1-D, or (B, L) with ``lengths`` (B,) samples or None, on the GPU -> {"loudness", "spectral_flux", "power", "log_energy": (B, F)
+    float64; "mfcc" (B, F, n_ceps) float64; "live" (B, F) bool: some bin lies above the floor; "has_previous" (B, F) bool: the frame has a
+    predecessor in its row (every frame of a row but the first: the first frame's flux is 0 by definition)}, F = ceil(L / hop_length); a 1-D input
+    gives B = 1.  A silent frame keeps its power and its flux and has zeros elsewhere; a frame past a row's ceil(len / hop_length) has zeros and
+    False everywhere.  The figures are comparable across runs of this project, not to the digit with openSMILE's, which frames differently (25 ms
+    Hamming windows for MFCC) and scales its own way."""
+    _trim_input(y, "auditory")
+    eng = _auditory_engine(y.device, sr, frame_length, hop_length, n_mels, fmin, fmax, n_ceps, lifter, flux_band)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    r = eng.auditory(x, lengths if y.dim() == 2 else None, power_floor)
+    out = {k: r["frame"][:, :, i] for i, k in enumerate(_AUDITORY_FRAME)}
+    out.update(mfcc=r["mfcc"], live=(r["flags"] & 1) != 0, has_previous=(r["flags"] & 2) != 0)
+    return out
+
+
+def _auditory_contours(t, use):
+    """``use`` here is the frames inside the row (timbre and dynamics are not figures of the voiced frames alone) and t["voiced"] the voicing.
+    The frames mask: the live frames inside; behind the loudness and the MFCC those, behind the flux the frames with a predecessor, behind a
+    ``_voiced`` / ``_unvoiced`` figure the voiced / unvoiced ones of them."""
+    if t["mfcc"].shape[-1] < 4:
+        raise ValueError(f"auditory contours need the cepstral coefficients 1 .. 4, got {t['mfcc'].shape[-1]}")
+    live, moved = use & t["live"], use & t["has_previous"]
+    live_v, moved_v, moved_u = live & t["voiced"], moved & t["voiced"], moved & ~t["voiced"]
+    out = {"loudness": (t["loudness"], live), "spectral_flux": (t["spectral_flux"], moved), "spectral_flux_voiced": (t["spectral_flux"], moved_v),
+           "spectral_flux_unvoiced": (t["spectral_flux"], moved_u)}
+    out.update({f"mfcc_{i + 1}": (t["mfcc"][:, :, i], live) for i in range(4)})
+    out.update({f"mfcc_{i + 1}_voiced": (t["mfcc"][:, :, i], live_v) for i in range(4)})
+    return live, out
+
+
+def _auditory_coerced(au, voiced, dev=None):
+    t = _coerced(au, "live", ("loudness", "spectral_flux", "power", "mfcc"), dev, voiced)
+    t["live"], t["has_previous"] = t["live"].to(torch.bool), torch.as_tensor(au["has_previous"]).to(t["live"].device, torch.bool)
+    return t
+
+
+@torch.inference_mode()
+def auditory_statistics(au, voiced, lengths=None):
+    """Per utterance, from ``auditory`` and a voicing mask at the same hop: {"loudness", "mfcc_1" .. "mfcc_4": (B,) float64, the mean over the live
+    frames inside ``lengths``; "spectral_flux": over the frames inside that have a predecessor; "spectral_flux_voiced", "spectral_flux_unvoiced",
+    "mfcc_1_voiced" .. "mfcc_4_voiced": over the voiced / unvoiced ones of those; "equivalent_level_db": 10 log10 of the mean power over every
+    frame inside (a level comparable across runs, not dB SPL); NaN where no frame qualifies (-inf for an all-zero row); "frames" (B,) int64: the
+    live frames inside; "used": {figure: (B,) int64, the frames behind its mean}; "sums": {figure: (B,) float64 sums over those frames, for pooling
+    over utterances - under "equivalent_level_db" the sum of the POWER, which is what pools}}, where ``au`` lives (torch ops only).  Entries are (B,
+    F) (mfcc (B, F, n_ceps >= 4)) or one row without the leading axis; ``lengths`` (B,): the FRAMES that belong to each row (None: F)."""
+    t = _auditory_coerced(au, voiced)
+
+    def shapes(t, B, F):
+        flat = [t[k] for k in ("has_previous", "voiced", "loudness", "spectral_flux", "power")]
+        if t["live"].dim() != 2 or any(v.shape != (B, F) for v in flat) or t["mfcc"].dim() != 3 or tuple(t["mfcc"].shape[:2]) != (B, F):
+            return (f"live, has_previous, the mask and the figures (B, F) and mfcc (B, F, n_ceps) expected, got {tuple(t['live'].shape)}, "
+                    f"{[tuple(v.shape) for v in flat]} and {tuple(t['mfcc'].shape)}")
+
+    t, inside, _ = _inside(t, lengths, "auditory_statistics", t["live"].dim() == 1, shapes)
+    frames, contours = _auditory_contours(t, inside)
+    contours["equivalent_level_db"] = (t["power"], inside)
+    r = _reduce(frames, contours)
+    r["means"]["equivalent_level_db"] = 10.0 * torch.log10(r["means"]["equivalent_level_db"])
+    return {"frames": r["frames"], "used": r["used"], "sums": r["sums"], **r["means"]}
+
+
 FUNCTIONAL_STATISTICS = ("mean", "sd", "min", "max", "rise_mean", "rise_sd", "fall_mean", "fall_sd", "run_mean", "run_sd", "gap_mean", "gap_sd")
 FUNCTIONAL_COUNTS = ("valid", "dropped", "rising_parts", "falling_parts", "peaks", "runs", "gaps", "adjacent_pairs")
 _FUNCTIONAL_BEHIND = {"mean": 0, "sd": 0, "min": 0, "max": 0, "rise_mean": 2, "rise_sd": 2, "fall_mean": 3, "fall_sd": 3, "run_mean": 5, "run_sd": 5,
@@ -1335,10 +1483,10 @@ def functionals(values, mask=None, lengths=None, percentiles=(0.2, 0.5, 0.8)):
 
 @torch.inference_mode()
 def voice_functionals(pitch, vq, n_frames=None, fm=None, pt=None, hm=None, sr: int = 22050, hop_length: int = 256, percentiles=(0.2, 0.5, 0.8),
-                      max_bandwidth: float = 700.0, harmonic_fm=None):
+                      max_bandwidth: float = 700.0, harmonic_fm=None, au=None):
     """The functionals of every contour the voice report has, in ONE ``functionals`` call per batch: ``pitch`` (the dict of ``pitch_yin`` /
-    ``pitch_pyin``), ``vq`` (of ``voice_quality``) and, when given, ``fm`` (``formants``), ``pt`` (``perturbation``) and ``hm`` (``harmonics``),
-    all (B, F) at the same hop on the GPU; ``n_frames`` (B,): the frames of each row (None: F).  The contours and their masks, each the mask
+    ``pitch_pyin``), ``vq`` (of ``voice_quality``) and, when given, ``fm`` (``formants``), ``pt`` (``perturbation``), ``hm`` (``harmonics``) and
+    ``au`` (``auditory``), all (B, F) at the same hop on the GPU; ``n_frames`` (B,): the frames of each row (None: F).  The contours and their masks, each the mask
     of the matching ``*_statistics`` function (so a contour's "mean" is that function's mean):
       "f0_semitones"              12 log2(f0 / 27.5), eGeMAPS's scale, over the voiced frames (``prosody_statistics``' mask)
       VOICE_QUALITY_FIGURES       voiced and not silent (``voice_quality_statistics``)
@@ -1347,6 +1495,9 @@ def voice_functionals(pitch, vq, n_frames=None, fm=None, pt=None, hm=None, sr: i
                                   calls it), in its units: per cent, dB, ``hnr_db``(r)
       HARMONIC_FIGURES            voiced and carrying the figure's flag, and under the bandwidth rule of ``harmonic_statistics`` at the formants
                                   ``harmonic_fm`` (None: ``fm``; neither: no bandwidth rule)
+      the auditory contours       AUDITORY_FIGURES without the level: loudness and MFCC 1-4 over the live frames inside the row, the flux over the
+                                  frames with a predecessor, the ``_voiced`` / ``_unvoiced`` ones under the voicing (``auditory_statistics``);
+                                  "peaks_per_s" of "loudness" is eGeMAPS's loudness peaks per second
     -> {contour: {statistic: (B,)}} with the keys of ``functionals`` and, beside them, "peaks_per_s" (peaks over the row's seconds) and the
     four slope statistics in units per SECOND (scaled by sr / hop_length); "segments": {"voiced_per_s", "voiced_mean_s", "voiced_sd_s",
     "unvoiced_mean_s", "unvoiced_sd_s"} from the runs and the gaps of the voicing contour; "contours": the names in stacking order."""
@@ -1371,6 +1522,8 @@ def voice_functionals(pitch, vq, n_frames=None, fm=None, pt=None, hm=None, sr: i
         if harmonic_fm is not None:
             band = torch.as_tensor(harmonic_fm["bandwidth"], dtype=torch.float64).to(dev)
         contours.update(_harmonic_contours(_coerced(hm, "flags", HARMONIC_FIGURES, dev), use, band, max_bandwidth)[1])
+    if au is not None:
+        contours.update(_auditory_contours(_auditory_coerced(au, t["voiced"], dev), inside)[1])
     names = list(contours) + ["voicing"]                     # the runs and gaps of the voicing itself: the temporal group
     vals = [v for v, _ in contours.values()] + [torch.zeros((B, F), dtype=torch.float64, device=dev)]
     masks = [m for _, m in contours.values()] + [use]

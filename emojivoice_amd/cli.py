@@ -23,6 +23,8 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt --harmonics                          # ... and H1-H2, H1-A3 and the harmonic levels at F1-F3 over H1, per file and per speaker
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt --functionals                        # ... and per contour mean, sd, percentiles, slopes and peak rate, and the voiced / unvoiced segment lengths (the eGeMAPS functionals)
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --harmonics                                 # ... and, per pair, the harmonic differences of both sides and their differences
+    python -m emojivoice_amd.cli --voice_report clean/filelist.txt --auditory --functionals             # ... and loudness, spectral flux, MFCC 1-4 and the equivalent level, per file and per speaker, with their functionals (loudness peaks per second among them)
+    python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --auditory                                  # ... and, per pair, loudness, spectral flux, MFCC 1-4 and the level of both sides and their differences
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --voice_quality                             # ... and, per pair, the voice-quality figures of both sides and their differences
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
@@ -482,7 +484,7 @@ def prosody_report(args, device):
     return rep
 
 
-Family = collections.namedtuple("Family", "report_flag pairs_flag block figures frames_key counts used measure")
+Family = collections.namedtuple("Family", "report_flag pairs_flag block figures frames_key counts used measure finish", defaults=(None,))
 
 
 def report_families():
@@ -490,7 +492,8 @@ def report_families():
     the args attributes that switch it on in the two reports (None: always on); ``block``, its name in the evaluation report; ``figures``,
     its tuple in audio; ``frames_key``, the report's key of its frame count; ``counts``, further keys of its statistics that the report sums;
     ``used(st)`` -> {figure: (B,) the frames behind its mean}; ``measure(batch, sr, hop, lens, voiced, n_frames, got)`` -> its
-    audio.*_statistics of the batch, after leaving its per-frame dict under got[block] for the families behind it and for --functionals."""
+    audio.*_statistics of the batch, after leaving its per-frame dict under got[block] for the families behind it and for --functionals;
+    ``finish(means)`` (None: nothing) turns pooled means that are not yet the report's figures into them, in place."""
     from . import audio
 
     def voice(batch, sr, hop, lens, voiced, n_frames, got):
@@ -513,12 +516,24 @@ def report_families():
         got["harmonics"] = audio.harmonics(batch, sr, hop_length=hop, lengths=lens, formants=fm)
         return audio.harmonic_statistics(got["harmonics"], voiced, n_frames, fm=fm)
 
+    def auditory(batch, sr, hop, lens, voiced, n_frames, got):
+        """audio.auditory over every frame of the row: loudness and MFCC over the live frames, the flux over the frames with a predecessor, the
+        _voiced / _unvoiced figures under the pitch tracker's voicing."""
+        got["auditory"] = audio.auditory(batch, sr, hop_length=hop, lengths=lens)
+        return audio.auditory_statistics(got["auditory"], voiced, n_frames)
+
+    def level_db(means):
+        """equivalent_level_db pools as a mean POWER (audio.auditory_statistics' sums hold the power): the level is taken last."""
+        p = means["equivalent_level_db"]
+        means["equivalent_level_db"] = 10.0 * math.log10(p) if p is not None and p > 0.0 else None
+
     per_figure = lambda st: st["used"]
     return (Family(None, "voice_quality", "voice", audio.VOICE_QUALITY_FIGURES, "voiced_frames", (), lambda st: {k: st["frames"] for k in st["sums"]}, voice),
             Family("formants", "formants", "formants", audio.FORMANT_FIGURES, "formant_frames", ("unconverged_frames",),
                    lambda st: {k: st["used"][:, int(k[1]) - 1] for k in st["sums"]}, formants),          # f_i and b_i share used[:, i]
             Family("perturbation", "perturbation", "perturbation", audio.PERTURBATION_FIGURES, "perturbation_frames", (), per_figure, perturbation),
-            Family("harmonics", "harmonics", "harmonics", audio.HARMONIC_FIGURES, "harmonic_frames", (), per_figure, harmonics))
+            Family("harmonics", "harmonics", "harmonics", audio.HARMONIC_FIGURES, "harmonic_frames", (), per_figure, harmonics),
+            Family("auditory", "auditory", "auditory", audio.AUDITORY_FIGURES, "auditory_frames", (), per_figure, auditory, level_db))
 
 
 def enabled_families(args, flag: str):
@@ -545,6 +560,8 @@ def family_means(rows, family):
     for k in family.figures:
         n = sum(r["used"][k] for r in rows)
         out[k] = math.fsum(r["sums"][k] for r in rows) / n if n else None
+    if family.finish is not None:
+        family.finish(out)
     for key, field in ((family.frames_key, "frames"),) + tuple((k, k) for k in family.counts):
         out[key] = sum(r[field] for r in rows)
     return out
@@ -602,6 +619,10 @@ def voice_report(args, device):
     the voiced frames that carry each figure, at formants of at most 700 Hz bandwidth; null without such a frame) and harmonic_frames (the
     voiced frames); per speaker and overall the means pooled over the frames behind each figure, and the count summed.  With --formants the
     formants are analysed once for both.
+    --auditory adds per file loudness and mfcc_1 .. mfcc_4 (audio.auditory reduced by audio.auditory_statistics over the frames that are not silent),
+    spectral_flux (over the frames with a predecessor), spectral_flux_voiced, spectral_flux_unvoiced and mfcc_1_voiced .. mfcc_4_voiced (under the
+    pitch tracker's voicing), equivalent_level_db (10 log10 of the mean power over every frame) and auditory_frames (the frames that are not silent);
+    per speaker and overall the means pooled over the frames behind each figure (the level from the pooled power), and the count summed.
     --functionals adds per file "functionals": {contour: {mean, sd, p20, p50, p80, range, rise_mean, rise_sd, fall_mean, fall_sd, peaks_per_s}}
     for f0_semitones (12 log2(f0 / 27.5)), the five voice-quality figures and the figures of the other flags given, each over the frames its mean
     above runs over (audio.voice_functionals: one device call per batch; slopes in units per second; null where there is no value), and
@@ -621,7 +642,7 @@ def voice_report(args, device):
         if want_func:
             rows["functionals"] = functional_rows(audio.voice_functionals(pitch, got["voice"], n_frames, fm=got.get("formants"), pt=got.get("perturbation"),
                                                                           hm=got.get("harmonics"), sr=PROSODY_SR, hop_length=PROSODY_HOP,
-                                                                          harmonic_fm=got.get("harmonic_fm")))
+                                                                          harmonic_fm=got.get("harmonic_fm"), au=got.get("auditory")))
         for r, (wav, spk, _) in enumerate(chunk):
             spk = spk if spk is not None else "0"
             rec = {"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r],
@@ -867,7 +888,9 @@ def evaluate_pairs(args, device):
     --perturbation adds "perturbation" in the same form: jitter_pct, rap_pct, shimmer_pct, shimmer_db and hnr_db (audio.perturbation,
     audio.perturbation_statistics) of each side and their differences: wobbling periods or a buzzy waveform where pitch and spectrum agree.
     --harmonics adds "harmonics" in the same form: h1_h2_db, h1_a3_db, f1_rel_db, f2_rel_db and f3_rel_db (audio.harmonics,
-    audio.harmonic_statistics) of each side and their differences: a breathier or a more pressed source where the vowel is the same."""
+    audio.harmonic_statistics) of each side and their differences: a breathier or a more pressed source where the vowel is the same.
+    --auditory adds "auditory" in the same form: loudness, the spectral flux, MFCC 1-4, their voiced / unvoiced variants and equivalent_level_db
+    (audio.auditory, audio.auditory_statistics) of each side and their differences: a duller, flatter or quieter rendering of the same sentence."""
     from . import audio
 
     entries = parse_pairs(args.evaluate_pairs)
@@ -1035,6 +1058,12 @@ def cli(argv=None):
                    "over H1 in dB over the voiced frames (the harmonics of YIN's period in the log spectrum, at the formants of --formants) per "
                    "file, per speaker and overall; --evaluate_pairs: add \"harmonics\" per pair (both sides and their differences) and per speaker "
                    "and overall")
+    p.add_argument("--auditory", action="store_true", help="--voice_report: add the mean loudness (mel bands under an equal-loudness weighting, "
+                   "compressed by a 0.33 power law) and MFCC 1-4 over the frames that are not silent, the mean spectral flux over the frames with a "
+                   "predecessor, the flux and the MFCC over the voiced (the flux also over the unvoiced) frames and the equivalent level in dB, with "
+                   "auditory_frames, per file, per speaker and overall; with --functionals the functionals of these contours (the peaks per second of "
+                   "\"loudness\" is the eGeMAPS loudness peak rate); --evaluate_pairs: add \"auditory\" per pair (both sides and their differences) "
+                   "and per speaker and overall")
     args = validate_args(p.parse_args(argv))
     if args.voice_report:
         if not torch.cuda.is_available():

@@ -1,5 +1,5 @@
 // Host entry points of the analysis side: resampling, dataset statistics, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness,
-// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences and contour functionals (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
+// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals and auditory descriptors (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
 // after ev_handle, fail / HIPCHK / enter, dev_upload, drop_owned, scratch_acquire and launch<>.  None of these calls runs on the engine's conv
 // path; ev_load_mel_basis, ev_mel_spectrogram, ev_denoise and ev_stft_magnitude do, and stay in ev_engine.hip.
 #pragma once
@@ -726,6 +726,77 @@ int ev_harmonics(ev_handle* h, const float* d_x, const int32_t* d_len, int B, in
     const int NF = frames_of(L, w.t.H);
     HarmParams ph{d_x, d_len, d_period, d_formant, d_fcount, d_frame, d_count, d_harm, w.t, L, NF, d_formant ? n_formants : 0, power_floor};
     launch<harmonics_kernel>(h->device, dim3((unsigned)((NF + 15) / 16), (unsigned)B), dim3(256), w.lds, h->stream, ph);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Auditory descriptors: loudness of an auditory spectrum, spectral flux, power and MFCC per frame (auditory_kernel, ev_analysis_kernels.h; the
+// definition: include/emojivoice.h).  One device block per load holds the basis, the mel table padded with zeros to (NBp, NMp), eq and dct; a call
+// needs no arena.
+int ev_load_auditory(ev_handle* h, const double* window, const double* twiddle, int W, int H, int nfft, const double* mel_w, int n_mel,
+                     const double* eq, const double* dct, int n_ceps, int k_lo, int k_hi, double compress) {
+    if (enter(h)) return 1;
+    if (!window || !twiddle || !mel_w || !eq || !dct)
+        return fail(h, "ev_load_auditory: window, twiddle, mel_w, eq and dct must be non-null (HOST)");
+    if (check_dft_geometry(h, __func__, W, H, nfft, 1024)) return 1;
+    const int NB = nfft / 2 + 1;
+    if (n_mel < 1 || n_mel > 64) return fail(h, "ev_load_auditory: n_mel=%d outside 1 <= n_mel <= 64", n_mel);
+    if (n_ceps < 1 || n_ceps > 16) return fail(h, "ev_load_auditory: n_ceps=%d outside 1 <= n_ceps <= 16", n_ceps);
+    if (k_lo < 0 || k_lo >= k_hi || k_hi > NB) return fail(h, "ev_load_auditory: k_lo=%d k_hi=%d outside 0 <= k_lo < k_hi <= %d", k_lo, k_hi, NB);
+    if (!(compress > 0.0 && compress <= 1.0)) return fail(h, "ev_load_auditory: compress=%g outside 0 < compress <= 1", compress);
+    if (check_finite(h, __func__, "window", window, W) || check_finite(h, __func__, "twiddle", twiddle, 2 * nfft)
+        || check_finite(h, __func__, "mel_w", mel_w, NB * n_mel) || check_finite(h, __func__, "eq", eq, n_mel)
+        || check_finite(h, __func__, "dct", dct, n_mel * n_ceps)) return 1;
+    for (int j = 0; j < NB * n_mel; ++j) if (mel_w[j] < 0.0) return fail(h, "ev_load_auditory: mel_w[%d] = %g must not be negative", j, mel_w[j]);
+    for (int j = 0; j < n_mel; ++j) if (!(eq[j] > 0.0)) return fail(h, "ev_load_auditory: eq[%d] = %g must be greater than 0", j, eq[j]);
+    AudW w;
+    AudTables& t = w.t;
+    t.W = W; t.H = H; t.nfft = nfft; t.NB = NB; t.NBp = (NB + 3) / 4 * 4; t.skew = dft_skew(H);
+    t.S = NB + ((2 - NB) % 32 + 32) % 32;                               // the smallest S >= NB with S = 2 mod 32
+    t.n_mel = n_mel; t.NMp = (n_mel + 15) / 16 * 16; t.LS = t.NMp + 1; t.n_ceps = n_ceps; t.k_lo = k_lo; t.k_hi = k_hi; t.compress = compress;
+    // the power spectrum, log(Ef) and pow(eq Ef, compress), the skewed span
+    w.lds = (size_t)16 * t.S * sizeof(double) + (size_t)32 * t.LS * sizeof(double) + (size_t)dft_span_words(15 * H + W, H, t.skew) * sizeof(float);
+    if (w.lds > 160 * 1024)
+        return fail(h, "ev_load_auditory: nfft=%d H=%d W=%d n_mel=%d need %zu bytes of LDS, over 160 KiB", nfft, H, W, n_mel, w.lds);
+    const size_t n_basis = (size_t)W * NB, n_melp = (size_t)t.NBp * t.NMp;
+    const size_t o_mel = 2 * n_basis, o_eq = o_mel + n_melp, o_dct = o_eq + (size_t)n_mel;   // in doubles from the block's start, behind the basis
+    std::vector<double> melp(n_melp, 0.0);
+    for (int k = 0; k < NB; ++k) for (int m = 0; m < n_mel; ++m) melp[(size_t)k * t.NMp + m] = mel_w[(size_t)k * n_mel + m];
+    char* blk = nullptr;                                                // the new block first: a failed load leaves the tables in use as they are
+    auto rest = [&](char* b, const double*) {
+        double* d = (double*)b;
+        hipError_t e = hipMemcpy(d + o_mel, melp.data(), n_melp * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d + o_eq, eq, (size_t)n_mel * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d + o_dct, dct, (size_t)n_mel * n_ceps * sizeof(double), hipMemcpyHostToDevice);
+        return e;
+    };
+    if (build_dft_basis(h, __func__, "tables", window, twiddle, W, nfft, (o_dct + (size_t)n_mel * n_ceps) * sizeof(double), &blk, rest)) return 1;
+    AudW& cur = h->aud;
+    if (cur.loaded) { if (drop_owned(h, {(void*)cur.t.basis})) { hipFree(blk); return 1; } cur = AudW(); }
+    const double* d = (const double*)blk;
+    t.basis = (const double2*)blk; t.mel = d + o_mel; t.eq = d + o_eq; t.dct = d + o_dct;
+    h->owned.push_back(blk);
+    ++h->n_allocs;                          // (one block: the basis, mel, eq and dct; 8.5 MB at W = nfft = 1024 with 26 bands)
+    w.loaded = true;
+    cur = w;
+    return 0;
+}
+
+int ev_auditory(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, double power_floor, double* d_frame, double* d_mfcc,
+                int32_t* d_flags, double* d_bands, void* stream) {
+    if (enter(h)) return 1;
+    const AudW& w = h->aud;
+    if (!w.loaded) return fail(h, "ev_auditory: tables not loaded (ev_load_auditory)");
+    if (check_batch(h, __func__, B)) return 1;
+    if (L < 1) return fail(h, "ev_auditory: L=%d must be at least 1", L);
+    if (!d_x) return fail(h, "ev_auditory: d_x must be non-null");
+    if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_auditory: power_floor=%g must be finite and greater than 0", power_floor);
+    if (!d_frame || !d_mfcc || !d_flags) return fail(h, "ev_auditory: d_frame, d_mfcc and d_flags must be non-null");
+    if (L / w.t.H > 0x7fffffef) return fail(h, "ev_auditory: L=%d at H=%d has more frames than an int32 tile index holds", L, w.t.H);
+    h->stream = (hipStream_t)stream;
+    const int NF = frames_of(L, w.t.H);
+    AudParams pa{d_x, d_len, d_frame, d_mfcc, d_flags, d_bands, w.t, L, NF, power_floor};
+    launch<auditory_kernel>(h->device, dim3((unsigned)((NF + 14) / 15), (unsigned)B), dim3(256), w.lds, h->stream, pa);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

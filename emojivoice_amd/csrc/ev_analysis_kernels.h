@@ -2558,3 +2558,208 @@ __global__ __launch_bounds__(256) void functionals_kernel(const FuncParams p) {
         o_ct[0] = k; o_ct[1] = dropped; o_ct[2] = nrise; o_ct[3] = nfall; o_ct[4] = npeak; o_ct[5] = nruns; o_ct[6] = ngaps; o_ct[7] = nadj;
     }
 }
+
+// ---------------------------------------------------------------------------
+// Auditory descriptors (ev_auditory): per frame the loudness of an auditory spectrum, the spectral flux against the frame before, the power and
+// the first cepstral coefficients over mel bands (MFCC), from ONE float64 power spectrum (the definition: include/emojivoice.h; Eyben et al. 2016).
+// All float64, contraction OFF (STOI_EXACT), no atomics.  Two GEMMs on v_mfma_f64_16x16x4_f64, chained through LDS inside one launch, on the shared
+// pieces of the float64 DFT GEMM above; the device sees only tables (mel: (NBp, NMp) zero-padded, NMp = 16 ceil(n_mel / 16); eq (n_mel); dct
+// (n_mel, n_ceps)).
+// One workgroup of 4 waves per (row b, tile).  The flux of frame f needs the spectrum of frame f - 1, so the 16 matrix rows of a tile are the
+// frames f0 - 1 .. f0 + 14 and tiles advance by 15 frames, f0 = 15 blockIdx.x: row 0 is carried for the flux of row 1 only and nothing of it is
+// written (1 / 15 more matrix work; no second launch, no arena, no dependence between workgroups).  Dynamic LDS: P, the tile's power spectrum (16
+// rows x S doubles, S = 2 mod 32 as in voice_quality_kernel); Lg and Lc (16 rows x LS doubles each, LS = NMp + 1): log(Ef) and pow(eq Ef, compress);
+// then the tile's raw span, samples (f0 - 1) H + H / 2 - W / 2 + t for 0 <= t < 15 H + W, staged under the skew with ZEROS outside [0, len).
+// 1024 / 256 / 1024 with 26 bands: 65 792 + 2 x 4 224 + 19 600 = 93 840 bytes, and 896 static: 92.5 KiB, one workgroup per CU.
+// PHASE 1 is voice_quality_kernel's first loop.  Epilogue per (row, bin): raw = fma(sm, sm, re * re) goes to P[row S + bin]; per row the lane
+// accumulates over its bin tiles in ascending order the power (s = s + raw) and the count of bins with raw > floor; then the hand-over (xor tree 8, 4,
+// 2, 1 over the 16 column lanes, the waves as ((w0 + w1) + w2) + w3).
+// PHASE 2, after one barrier: wave w < NMp / 16 owns the band tile w: NBp / 4 steps of one MFMA, lane l of an A fragment reads P[(l & 15) S + k0 +
+// (l >> 4)] with ds_read_b64 (k >= NB: the address clamped to NB - 1, the table row zero), the B fragment is mel[k0 + (l >> 4)][16 w + (l & 15)] from
+// L2, the next four steps requested ahead: E[m] is the sum over k ascending in steps of 4.  Its epilogue is PHASE 3: Ef = max(E, floor), Lg = log(Ef),
+// Lc = pow(eq[m] Ef, compress), and the store of E to d_bands.
+// FLUX, by every wave in the same phase: the 16 lanes j of lane group g = tid >> 4 serve row (g >> 1) + 8 (g & 1) >= 1 over the bins k = j mod 16 of
+// [k_lo, k_hi) ascending, d = sqrt(P[row][k]) - sqrt(P[row - 1][k]), s = fma(d, d, s); xor tree 8, 4, 2, 1; flux = sqrt(s / (k_hi - k_lo)).
+// PHASE 4, after one barrier: thread (row g, i) forms mfcc[i] = fma(Lg[m], dct[m][i], s) over ascending m; thread (row g, 15) adds the loudness s = s +
+// Lc[m] over ascending m and writes the frame's four figures and its flags.  Every order depends on the geometry and the frame only.
+// BANKS (from the LDS table of the micro-architecture guide; no counter was read).  Phase 2's ds_read_b64 is voice_quality_kernel's: conflict-free
+// at S = 2 mod 32.  Flux: ds_read_b64 is served in groups of 32 lanes and banked over 64 dwords; a group holds the rows r and r + 8, each 16
+// consecutive doubles (32 dwords), and 8 S doubles = 32 mod 64 dwords: all 64 banks once, conflict-free (that is what the row order of g is for).
+// Phase 3's ds_write_b64 is served 16 contiguous lanes at a time, here 16 consecutive doubles of one row: conflict-free.  Phase 4's reads are two
+// broadcast addresses per group, LS doubles = 2 NMp + 2 dwords apart: distinct banks.  Phase 1's stores of raw are voice_quality_kernel's stores of
+// Ldb: not conflict-free (rows q and q + 4 i at 4 mod 32 dwords), once per bin tile.
+// A SILENT frame (no bin with raw > floor) keeps its power and its flux; loudness, log-energy, d_mfcc and d_bands are zeros and the live bit is 0.
+// Frames >= nf are zeros.
+struct AudTables {
+    const double2* basis; const double* mel; const double* eq; const double* dct;
+    int W, H, nfft, NB, NBp, skew, S, n_mel, NMp, LS, n_ceps, k_lo, k_hi;
+    double compress;
+};
+struct AudParams { const float* x; const int32_t* len; double* frame; double* mfcc; int32_t* flags; double* bands; AudTables t; int L, NF; double floor; };
+
+__global__ __launch_bounds__(256) void auditory_kernel(const AudParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double aud_smem[];
+    __shared__ double red[4][16][1];
+    __shared__ int red_live[4][16];
+    __shared__ double flux_s[16];
+    const int b = blockIdx.y, f0 = blockIdx.x * 15, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int W = p.t.W, H = p.t.H, NB = p.t.NB, skew = p.t.skew, S = p.t.S, NM = p.t.n_mel, NMp = p.t.NMp, LS = p.t.LS, NC = p.t.n_ceps;
+    int n;
+    const int nf = voiceq_frames(p.len, b, p.L, H, &n);
+    const size_t o0 = (size_t)b * p.NF + f0;
+    double* out = p.frame + o0 * 4;
+    double* mf = p.mfcc + o0 * NC;
+    int32_t* fl = p.flags + o0;
+    double* bd = p.bands ? p.bands + o0 * NM : nullptr;
+    const int nfr = p.NF - f0 < 15 ? p.NF - f0 : 15;                    // the tile's frames inside the outputs (>= 1)
+    if (f0 >= nf) {                                                     // (uniform) zeros past the row's own frames
+        if (tid < 4 * nfr) out[tid] = 0.0;
+        if (tid < nfr) fl[tid] = 0;
+        if (tid < nfr * NC) mf[tid] = 0.0;
+        if (bd) for (int i = tid; i < nfr * NM; i += 256) bd[i] = 0.0;
+        return;
+    }
+    double* P = aud_smem;                                               // (16, S)
+    double* Lg = P + 16 * S;                                            // (16, LS)
+    double* Lc = Lg + 16 * LS;                                          // (16, LS)
+    float* sx = (float*)(Lc + 16 * LS);
+    const int span = 15 * H + W;
+    {
+        const float* xr = p.x + (size_t)b * p.L;
+        const long long i0 = ((long long)f0 - 1) * H + H / 2 - W / 2;
+        for (int t = tid; t < span; t += 256) {
+            const long long i = i0 + t;
+            sx[dft_word(t, H, skew)] = i >= 0 && i < n ? xr[i] : 0.f;
+        }
+    }
+    __syncthreads();
+    const int r = lane & 15, q = lane >> 4;
+    {
+        const int ntile = (NB + 15) >> 4, nsteps = W >> 2;
+        DftSkewWalk walk(r, H, skew);
+        double pw[4] = {0.0, 0.0, 0.0, 0.0};
+        int live[4] = {0, 0, 0, 0};
+        for (int bt = wv; bt < ntile; bt += 4) {
+            const int col = bt * 16 + r;
+            const double2* bp = p.t.basis + (size_t)q * NB + (col < NB ? col : NB - 1);
+            stftd_acc xc = {0.0, 0.0, 0.0, 0.0}, xs = xc;
+            walk.start(q);
+            double2 cur[4], nxt[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cur[u] = bp[(size_t)(u < nsteps ? u : nsteps - 1) * 4 * NB];
+            for (int t0 = 0; t0 < nsteps; t0 += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) nxt[u] = bp[(size_t)(t0 + 4 + u < nsteps ? t0 + 4 + u : nsteps - 1) * 4 * NB];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (t0 + u < nsteps) {                              // (uniform)
+                        const double ax = (double)sx[walk.word()];
+                        xc = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].x, xc, 0, 0, 0);
+                        xs = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].y, xs, 0, 0, 0);
+                        walk.step();
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+            }
+            if (col < NB) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double raw = fma(xs[i], xs[i], xc[i] * xc[i]);
+                    P[(q + 4 * i) * S + col] = raw;
+                    pw[i] = pw[i] + raw;
+                    live[i] += raw > p.floor ? 1 : 0;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) {
+                pw[i] = pw[i] + __shfl_xor(pw[i], o, 64);
+                live[i] += __shfl_xor(live[i], o, 64);
+            }
+            if (r == 0) { red[wv][q + 4 * i][0] = pw[i]; red_live[wv][q + 4 * i] = live[i]; }
+        }
+    }
+    __syncthreads();                                                    // P, the powers and the live counts are complete
+    if (wv < (NMp >> 4)) {                                              // (uniform per wave) E = P x mel, then phase 3
+        const int nsteps = p.t.NBp >> 2;
+        const int col = wv * 16 + r;                                    // (< NMp)
+        const double* bp = p.t.mel + (size_t)q * NMp + col;
+        const double* Pa = P + r * S;
+        stftd_acc c = {0.0, 0.0, 0.0, 0.0};
+        double cur[4], nxt[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) cur[u] = bp[(size_t)(u < nsteps ? u : nsteps - 1) * 4 * NMp];
+        for (int t0 = 0; t0 < nsteps; t0 += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) nxt[u] = bp[(size_t)(t0 + 4 + u < nsteps ? t0 + 4 + u : nsteps - 1) * 4 * NMp];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (t0 + u < nsteps) {                                  // (uniform)
+                    const int k = 4 * (t0 + u) + q;
+                    c = __builtin_amdgcn_mfma_f64_16x16x4f64(Pa[k < NB ? k : NB - 1], cur[u], c, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+        }
+        if (col < NM) {
+            const double eqv = p.t.eq[col];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int row = q + 4 * i;
+                const double ef = fmax(c[i], p.floor);
+                Lg[row * LS + col] = log(ef);
+                Lc[row * LS + col] = pow(eqv * ef, p.t.compress);
+                if (bd && row >= 1 && row <= nfr) {
+                    const bool keep = f0 - 1 + row < nf && red_live[0][row] + red_live[1][row] + red_live[2][row] + red_live[3][row] > 0;
+                    bd[(size_t)(row - 1) * NM + col] = keep ? c[i] : 0.0;
+                }
+            }
+        }
+    }
+    {                                                                   // flux of row `row` against row - 1
+        const int g = tid >> 4, j = tid & 15;
+        const int row = (g >> 1) | ((g & 1) << 3);
+        double s = 0.0;
+        if (row >= 1) {
+            const double* pa = P + row * S;
+            const double* pb = pa - S;
+            for (int k = p.t.k_lo + ((j - p.t.k_lo) & 15); k < p.t.k_hi; k += 16) {
+                const double d = sqrt(pa[k]) - sqrt(pb[k]);
+                s = fma(d, d, s);
+            }
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
+        if (j == 0) flux_s[row] = sqrt(s / (double)(p.t.k_hi - p.t.k_lo));
+    }
+    __syncthreads();                                                    // Lg, Lc and the fluxes are complete
+    {
+        const int row = tid >> 4, i = tid & 15;
+        if (row >= 1 && row <= nfr) {
+            const int f = f0 - 1 + row;
+            const bool in = f < nf;
+            const bool alive = in && red_live[0][row] + red_live[1][row] + red_live[2][row] + red_live[3][row] > 0;
+            if (i < NC) {
+                double s = 0.0;
+                if (alive) for (int m = 0; m < NM; ++m) s = fma(Lg[row * LS + m], p.t.dct[m * NC + i], s);
+                mf[(size_t)(row - 1) * NC + i] = s;
+            }
+            if (i == 15) {
+                double loud = 0.0, power = 0.0, le = 0.0;
+                if (in) power = dft_waves_sum(red, row, 0);
+                if (alive) {
+                    for (int m = 0; m < NM; ++m) loud = loud + Lc[row * LS + m];
+                    le = log(fmax(power, p.floor));
+                }
+                double* o = out + 4 * (row - 1);
+                o[0] = loud; o[1] = in && f >= 1 ? flux_s[row] : 0.0; o[2] = power; o[3] = le;
+                fl[row - 1] = in ? (alive ? 1 : 0) | (f >= 1 ? 2 : 0) : 0;
+            }
+        }
+    }
+}

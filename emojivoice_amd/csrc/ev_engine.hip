@@ -131,6 +131,9 @@ struct StftDistW { bool loaded = false; StftDistTables t{}; };
 struct VoiceQW { bool loaded = false; size_t lds = 0; VoiceQTables t{}; };
 // Tables of ev_harmonics, one device block: ev_stft_dist's basis (W, NB); the comb's parameters travel in t; lds: the launch's dynamic LDS in bytes
 struct HarmW { bool loaded = false; size_t lds = 0; HarmTables t{}; };
+// Tables of ev_auditory, one device block: ev_stft_dist's basis (W, NB), the mel table padded with zeros to (NBp, NMp), eq (n_mel) and dct (n_mel,
+// n_ceps); lds: the launch's dynamic LDS in bytes (ev_analysis_kernels.h)
+struct AudW { bool loaded = false; size_t lds = 0; AudTables t{}; };
 // Geometry of ev_formants: the analysis window (W) float64 on the device, one block; the rest travels in the kernel's arguments (z0: the root
 // finder's starting points {re, im}, R: samples per lane of formants_kernel)
 struct FormantW { bool loaded = false; double* win = nullptr; int W = 0, H = 0, order = 0, nform = 0, R = 0; double pre = 0, sr = 0, f_lo = 0; double z0[64] = {0}; };
@@ -153,6 +156,7 @@ struct ev_handle {
     VoiceQW voiceq;
     FormantW fmt;
     HarmW harm;
+    AudW aud;
     // small per-stage scratch arenas (denoiser, text encoder): grown on demand, ordered against their last user's stream
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
     Scratch dn_ws, enc_ws, mas_ws;   // (mas_ws: the alignment search's frame -> token index and, for large Tx * Ty, its decision bits)

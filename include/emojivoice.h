@@ -49,6 +49,8 @@
  *   ev_load_harmonics  <- no counterpart; Eyben et al. 2016 and Hanson 1997 are the model
  *   ev_harmonics       <- no counterpart; Eyben et al. 2016 and Hanson 1997 are the model
  *   ev_functionals     <- no counterpart; the functionals of Eyben et al. 2016 (eGeMAPS) as openSMILE computes them are the model
+ *   ev_load_auditory   <- no counterpart; Eyben et al. 2016 (eGeMAPS) as openSMILE's cMelspec / cMfcc / cPlp / cSpectral compute them are the model
+ *   ev_auditory        <- no counterpart; Eyben et al. 2016 (eGeMAPS) as openSMILE's cMelspec / cMfcc / cPlp / cSpectral compute them are the model
  *   ev_pyin_observe    <- no counterpart; librosa.pyin is the model
  *   ev_pyin_decode     <- no counterpart; librosa.pyin is the model
  *
@@ -88,7 +90,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -867,6 +869,60 @@ int ev_functionals(ev_handle *h, const double *d_v /* (B, K, F) */, const uint8_
                    const int32_t *d_len /* (B) frames, or NULL */, int B, int K, int F,
                    const double *q /* HOST (NQ), may be NULL when NQ == 0 */, int NQ,
                    double *d_stat /* (B, K, 12 + NQ) */, int32_t *d_count /* (B, K, 8) */, void *stream);
+
+/* Auditory descriptors per frame on the device: the descriptors of timbre and dynamics that eGeMAPS (Eyben et al. 2016) adds to pitch, balance,
+ * formants and perturbation: the LOUDNESS of an auditory spectrum (mel bands under an equal-loudness weighting, compressed by a power law), the
+ * SPECTRAL FLUX (how fast the magnitude spectrum moves from one frame to the next) and the first MEL-FREQUENCY CEPSTRAL COEFFICIENTS, with the frame's
+ * power and log-energy, on ev_pitch_yin's frame grid.  ev_load_auditory stores one geometry and its tables; ev_auditory measures.  Everything is
+ * float64 (the fp32 samples are widened), the kernel is compiled with floating-point contraction off; no atomics, no scratch; ev_set_arithmetic does
+ * not reach it.  The device sees only tables: which mel scale, which equal-loudness curve, which cepstral coefficients and which lifter is the host
+ * layer's choice (audio.auditory_tables: HTK mel triangles, Hermansky 1990, DCT-II columns 1 .. n_ceps with the HTK lifter, compress 0.33).
+ * Units: the figures are comparable across this project's runs and NOT to the digit with openSMILE's, which frames differently (25 ms Hamming
+ * windows for its MFCC), and scales the spectrum and the loudness its own way.
+ * Sizes: NB = nfft / 2 + 1; NF = ceil(L / H); a row of len samples has nf = ceil(len / H) frames (ev_pitch_yin's and ev_voice_quality's frames).
+ * d_len == NULL: every row is L long.
+ *   s_f[j]    = x[f H + H / 2 - W / 2 + j], ZERO outside [0, len)          (no reflection)
+ *   re, sm    = s_f @ {c, s}                                               (ev_stft_dist's windowed basis, on v_mfma_f64_16x16x4_f64)
+ *   raw[k]    = fma(sm, sm, re re),  0 <= k < NB
+ *   power     = sum_k raw[k]
+ *   E[m]      = sum_k raw[k] mel_w[k][m],  0 <= m < n_mel                  (mel_w: dense (NB, n_mel) host doubles, finite and >= 0)
+ *   Ef[m]     = max(E[m], power_floor)
+ *   loudness  = sum_m pow(eq[m] Ef[m], compress)                           (eq: n_mel host doubles, finite and > 0;  0 < compress <= 1)
+ *   mfcc[i]   = sum_m log(Ef[m]) dct[m][i],  0 <= i < n_ceps               (dct: (n_mel, n_ceps) host doubles, finite; it carries the lifter)
+ *   flux_f    = sqrt( sum_{k_lo <= k < k_hi} (sqrt(raw_f[k]) - sqrt(raw_{f-1}[k]))^2 / (k_hi - k_lo) )   for 1 <= f < nf
+ *   flux_0    = 0 by definition: frame -1 is not a frame of the row, although its window reaches into the row when W > H
+ *   live_f    = some raw_f[k] > power_floor
+ * d_frame[b, f, 0..3] float64: {loudness, flux, power, log(max(power, power_floor))};  d_mfcc[b, f, i] float64 (B, NF, n_ceps);
+ * d_flags[b, f] int32: bit 0 live, bit 1 f >= 1 (the frame has a predecessor);  d_bands[b, f, m] float64 (B, NF, n_mel), may be NULL: E[m], unfloored.
+ * A SILENT frame (not live) keeps its power and its flux (an offset into silence is a flux event); its loudness, log-energy, d_mfcc and d_bands are
+ * zeros and its live bit is 0.  Frames at or past a row's ceil(len / H) are zeros in every output, flags included; so is every frame of a row with
+ * len < 1 or len > L, which is no error and no out-of-bounds access.  Nothing at or behind len is read, and nothing depends on the batch or on L: a
+ * row alone, inside a batch, as the d_len prefix of a longer padded row, a call with d_bands NULL, a second call, a call under every
+ * ev_set_arithmetic setting and a replay from a captured graph give the same bits.
+ * Orders: the DFT sums are ev_stft_dist's (one chain of W / 4 matrix steps per bin); power: per lane over its bin tiles ascending, an xor tree (8, 4,
+ *   2, 1) over the 16 column lanes, the four waves as ((w0 + w1) + w2) + w3; E[m]: one chain of ceil(NB / 4) matrix steps over ascending k; the flux:
+ *   lane j of 16 adds the bins k = j mod 16 of [k_lo, k_hi) ascending as fma(d, d, s), then the xor tree; mfcc[i] one chain of fma over ascending m; the
+ *   loudness one chain of additions over ascending m.  log, pow and sqrt are the device library's float64 ones.
+ * Loading (ev_load_auditory: host tables, one device block with the basis, mel_w padded with zeros to (4 ceil(NB / 4), 16 ceil(n_mel / 16)), eq and
+ *   dct, counted once in ev_alloc_count; loading again replaces the block after waiting for the device; a failed load leaves the previous tables in
+ *   use and the count unchanged).  ev_auditory without loaded tables fails with a message.  Limits of a load, each violation failing with a message
+ *   that names it: nfft even, 16 <= nfft <= 1024; W a multiple of 4, 4 <= W <= nfft, nfft - W even; 1 <= H <= 512; 1 <= n_mel <= 64; 1 <= n_ceps <=
+ *   16; 0 <= k_lo < k_hi <= NB; 0 < compress <= 1; finite, non-NULL tables, no negative entry in mel_w, every entry of eq greater than 0; at most 160
+ *   KiB of LDS per workgroup: 16 S doubles of power spectrum (S the smallest number >= NB with S = 2 mod 32), 32 (16 ceil(n_mel / 16) + 1) doubles of
+ *   band terms and the skewed span of 15 H + W floats (at most 3 (16 + W / H) pad words): 93 840 bytes at 1024 / 256 / 1024 with 26 bands.
+ * Limits of ev_auditory, each violation failing with a message that names it and writing nothing: 1 <= B <= 65535; L >= 1 (and L / H below
+ *   2^31 - 16); power_floor finite and greater than 0; d_x, d_frame, d_mfcc and d_flags non-NULL.
+ * Kernel (auditory_kernel: one launch on `stream`, no host wait, no copy, no arena: ev_alloc_count never moves): one workgroup of four waves per
+ *   (row, 15 frames): the 16 matrix rows of a tile are the 15 frames and the one before them, carried for the first flux only, so no spectrum crosses
+ *   a workgroup; phase 1 is ev_voice_quality's first matrix product into a power spectrum in LDS; phase 2, after one barrier, the product with mel_w
+ *   on the matrix cores (one band tile per wave) and the flux (16 lanes per frame); phase 3 the band terms; phase 4, after a second barrier, the
+ *   cepstral coefficients (a thread per (frame, i)) and the frame's figures.  The call is capturable. */
+int ev_load_auditory(ev_handle *h, const double *window /* HOST (W) */, const double *twiddle /* HOST (nfft, 2) */, int W, int H, int nfft,
+                     const double *mel_w /* HOST (NB, n_mel) */, int n_mel, const double *eq /* HOST (n_mel) */,
+                     const double *dct /* HOST (n_mel, n_ceps) */, int n_ceps, int k_lo, int k_hi, double compress /* 0.33 */);
+int ev_auditory(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L, double power_floor,
+                double *d_frame /* (B, NF, 4) */, double *d_mfcc /* (B, NF, n_ceps) */, int32_t *d_flags /* (B, NF) */,
+                double *d_bands /* (B, NF, n_mel) or NULL */, void *stream);
 
 /* Timing hooks for bench.py: HIP-event time (ms) of the dominant kernel family
  * (implicit-GEMM convs, fused pairs, fused LayerNorm + MLP, fused attention) accumulated over the calls since the last reset,

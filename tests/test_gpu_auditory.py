@@ -13,7 +13,7 @@ comparison (``check``):
   * exact zeros where the definition says zeros.
 Observed on the MI355X: d_mfcc 6.2e-14 (64 bands at 64 / 10 / 24), d_frame 2.3e-15 (the power at 1024 / 256 / 1024) and d_bands 4.1e-15 at worst over
 all cases, every flag equal.  Every case prints its worst figures, DESIGN section 3.24 records them; the gate stays at 1e-9.  Every raw call writes into buffers with sentinel
-margins; 50.0 sits behind every row's length.
+margins (tests/analysis_gpu.py); 50.0 sits behind every row's length.
 """
 import json
 
@@ -21,14 +21,14 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import auditory_ref as R
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-M = 64                                   # sentinel margin, elements
 SMALL = R.GEOMETRIES[0]                  # 64 / 10 / 24: NB = 33, 6 bands, 4 cepstra
 BIG = R.GEOMETRIES[3]
 NAMES = ("frame", "mfcc", "flags", "bands")
@@ -37,13 +37,7 @@ _REF = {}
 
 def ref_of(key, x, lens, g, t):
     """The restatements' results (float64, longdouble), computed once per case and never modified."""
-    if key not in _REF:
-        r = (R.batch(x, lens, g, t), R.batch(x, lens, g, t, dtype=np.longdouble))
-        for part in r:
-            for v in part.values():
-                v.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
+    return A.frozen(_REF, key, lambda: (R.batch(x, lens, g, t), R.batch(x, lens, g, t, dtype=np.longdouble)))
 
 
 def load(eng, g, t=None, null=(), **kw):
@@ -60,11 +54,6 @@ def load(eng, g, t=None, null=(), **kw):
                                     a["k_lo"], a["k_hi"], float(a["compress"]))
 
 
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
-
-
 def raw(eng, g, x, lens, floor=R.POWER_FLOOR, B=None, L=None, null=()):
     """ev_auditory into guarded buffers: (rc, {"frame" (B, NF, 4), "mfcc" (B, NF, n_ceps), "flags" (B, NF), "bands" (B, NF, n_mel)}) on the host; an
     output named in ``null`` is passed as NULL and comes back None.  ``B`` / ``L`` override the shape passed to the library."""
@@ -73,23 +62,11 @@ def raw(eng, g, x, lens, floor=R.POWER_FLOOR, B=None, L=None, null=()):
     B, L = Bx if B is None else B, Lx if L is None else L
     NF = R.frames(Lx, g.H)
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
-    shapes = ((Bx, NF, 4), (Bx, NF, g.n_ceps), (Bx, NF), (Bx, NF, g.n_mel))
-    fills = ((torch.float64, 777.0), (torch.float64, 777.0), (torch.int32, -777), (torch.float64, 777.0))
-    bufs = [guarded(int(np.prod(s)), dt, f) for s, (dt, f) in zip(shapes, fills)]
-    ptr = lambda i: None if NAMES[i] in null else bufs[i][1].data_ptr()
+    out = A.Guarded({"frame": ((Bx, NF, 4), torch.float64), "mfcc": ((Bx, NF, g.n_ceps), torch.float64), "flags": ((Bx, NF), torch.int32),
+                     "bands": ((Bx, NF, g.n_mel), torch.float64)}, null)
     rc = eng.lib.ev_auditory(eng.h, None if "x" in null else x.data_ptr(), None if d_len is None else d_len.data_ptr(), B, L, float(floor),
-                             ptr(0), ptr(1), ptr(2), ptr(3), _stream_ptr())
-    torch.cuda.synchronize()
-    out = {}
-    for i, ((whole, view), shape) in enumerate(zip(bufs, shapes)):
-        fill, n = whole[0].item(), int(np.prod(shape))
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), f"sentinel margin of d_{NAMES[i]}"
-        if rc != 0 or NAMES[i] in null:
-            assert bool((view == fill).all()), f"d_{NAMES[i]} was not asked for (or the call failed) and was written"
-            out[NAMES[i]] = None
-        else:
-            out[NAMES[i]] = view.reshape(shape).cpu().numpy().copy()
-    return rc, out
+                             out.ptr("frame"), out.ptr("mfcc"), out.ptr("flags"), out.ptr("bands"), _stream_ptr())
+    return rc, out.collect(rc)
 
 
 def check(dev, ref, what):
@@ -115,22 +92,12 @@ def check(dev, ref, what):
 
 
 def engine_with(g, t=None):
-    e = Engine(0)                                                        # no weights loaded
-    assert load(e, g, t) == 0, e.lib.ev_last_error(e.h).decode()
-    return e
+    return A.engine_with(load, g, t)
 
 
 @pytest.fixture(scope="module")
 def engines():
-    made = {}
-
-    def get(g):
-        if g not in made:
-            made[g] = engine_with(g)
-        return made[g]
-    yield get
-    for e in made.values():
-        e.close()
+    yield from A.engines_on_demand(engine_with)
 
 
 @pytest.fixture(scope="module")
@@ -140,7 +107,7 @@ def small(engines):
 
 def run(eng, g, x, lens, key, what, t=None, **kw):
     rc, dev = raw(eng, g, x, lens, **kw)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     ref = ref_of(key, x, lens, g, R.tables(g) if t is None else t)
     check(dev, ref, what)
     return dev, ref
@@ -208,7 +175,7 @@ def test_row_alone_in_a_batch_as_a_prefix_and_without_bands_give_the_same_bits(e
     n = lens[0]
     c = x[0, :n].copy()
     rc, alone = raw(eng, g, c[None], None)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     rc, again = raw(eng, g, c[None], None)
     assert rc == 0 and all(np.array_equal(alone[k], again[k]) for k in NAMES), "two calls"
     rc, nb = raw(eng, g, c[None], None, null=("bands",))
@@ -324,7 +291,7 @@ BAD_CALL = [
 def test_each_limit_of_ev_auditory_fails_with_a_message_naming_it(small, word, kw):
     z = np.zeros((2, 256), np.float32)
     rc, _ = raw(small, SMALL, z, None, **kw)                             # (a failed call writes nothing: raw checks that)
-    msg = small.lib.ev_last_error(small.h).decode()
+    msg = err_of(small)
     assert rc != 0 and "ev_auditory" in msg and word in msg, msg
 
 
@@ -333,7 +300,7 @@ def test_more_frames_than_a_tile_index_holds_fails(small):
     e = engine_with(SMALL._replace(H=1, W=24))
     try:
         rc, _ = raw(e, SMALL._replace(H=1), z, None, L=0x7ffffff0)
-        msg = e.lib.ev_last_error(e.h).decode()
+        msg = err_of(e)
         assert rc != 0 and "ev_auditory" in msg and "L=" in msg and "int32" in msg, msg
     finally:
         e.close()
@@ -370,7 +337,7 @@ def test_each_limit_of_ev_load_auditory_fails_with_a_message_naming_it(small, wo
         kw.update(mel_w=np.ones((33, nm)), eq=np.ones(nm), dct=np.ones((nm, nc)))
     n0 = small.alloc_count()
     rc = load(small, SMALL, null=null, **kw)
-    msg = small.lib.ev_last_error(small.h).decode()
+    msg = err_of(small)
     assert rc != 0 and "ev_load_auditory" in msg and word in msg, msg
     assert small.alloc_count() == n0
     x, lens = R.rows_for(SMALL)                                           # the tables loaded before are still the ones in use
@@ -390,9 +357,9 @@ def test_the_largest_geometry_the_limits_admit_fits_the_lds_budget():
         need = 16 * 514 * 8 + 32 * 65 * 8 + (15 * 512 + 1024 + 2 * ((15 * 512 + 1023) // 512)) * 4
         assert need == 117376 and need <= 160 * 1024
         n0 = e.alloc_count()
-        assert load(e, g, t) == 0 and e.alloc_count() == n0 + 1, e.lib.ev_last_error(e.h).decode()
+        assert load(e, g, t) == 0 and e.alloc_count() == n0 + 1, err_of(e)
         rc, dev = raw(e, g, np.full((1, 2000), 0.25, np.float32), None)
-        assert rc == 0 and (dev["flags"][0] & 1).all() and (dev["frame"][0, :, 0] > 0).all(), e.lib.ev_last_error(e.h).decode()
+        assert rc == 0 and (dev["flags"][0] & 1).all() and (dev["frame"][0, :, 0] > 0).all(), err_of(e)
     finally:
         e.close()
 
@@ -402,14 +369,14 @@ def test_a_call_before_a_load_fails_loading_again_replaces_the_tables_and_calls_
     try:
         z = np.zeros((1, 256), np.float32)
         rc, _ = raw(e, SMALL, z, None)
-        assert rc != 0 and "ev_load_auditory" in e.lib.ev_last_error(e.h).decode()
+        assert rc != 0 and "ev_load_auditory" in err_of(e)
         n0 = e.alloc_count()
-        assert load(e, R.GEOMETRIES[2]) == 0, e.lib.ev_last_error(e.h).decode()
+        assert load(e, R.GEOMETRIES[2]) == 0, err_of(e)
         assert e.alloc_count() == n0 + 1, "the tables are one device block that counts in ev_alloc_count"
         assert load(e, SMALL) == 0 and e.alloc_count() == n0 + 2
         x, lens = R.rows_for(SMALL)
         rc, dev = raw(e, SMALL, x, lens)
-        assert rc == 0, e.lib.ev_last_error(e.h).decode()
+        assert rc == 0, err_of(e)
         check(dev, ref_of(("rows", SMALL), x, lens, SMALL, R.tables(SMALL)), "after loading twice")
         n1 = e.alloc_count()
         assert n1 == n0 + 2, "a call allocates nothing"

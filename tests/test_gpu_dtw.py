@@ -7,7 +7,7 @@ channel where numpy multiplies and adds, so the cost of a K-cell path may differ
   * Euclidean inputs: the restatement's path margin (dtw_ref: the least gap between the best and the second-best predecessor along the
     path, over the cost) is asserted >= 1e-9 first, four orders above that rounding; then steps and path are EQUAL and
     |cost - ref| <= 1e-9 ref.
-Every raw call writes into buffers with sentinel margins.  Inputs carry loud garbage behind each row's lengths.
+Every raw call writes into buffers with sentinel margins (tests/analysis_gpu.py).  Inputs carry loud garbage behind each row's lengths.
 
 Times: not gated here (tools/dtw_bench.py).
 """
@@ -19,32 +19,22 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import dtw_ref as R
 import pitch_ref as P
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, EvLibraryError, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 GARBAGE = R.GARBAGE
-M = 64                                   # sentinel margin, elements
 _REF = {}
 
 
 def ref_of(key, x, y, xl, yl, metric):
     """The restatement's result, computed once per case and never modified."""
-    if key not in _REF:
-        r = R.dtw(x, y, xl, yl, metric)
-        for v in r.values():
-            v.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
-
-
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
+    return A.frozen(_REF, key, lambda: R.dtw(x, y, xl, yl, metric))
 
 
 def raw(eng, x, y, xl=None, yl=None, metric=0, want_path=True):
@@ -56,17 +46,10 @@ def raw(eng, x, y, xl=None, yl=None, metric=0, want_path=True):
     NP = Tx + Ty - 1
     d_xl = None if xl is None else torch.tensor(xl, dtype=torch.int32, device=DEV)
     d_yl = None if yl is None else torch.tensor(yl, dtype=torch.int32, device=DEV)
-    bufs = [guarded(B, torch.float64, 777.0), guarded(B, torch.int32, -777), guarded(B * NP * 2, torch.int32, -777)]
+    out = A.Guarded({"cost": ((B,), torch.float64), "steps": ((B,), torch.int32), "path": ((B, NP, 2), torch.int32)}, () if want_path else ("path",))
     rc = eng.lib.ev_dtw(eng.h, x.data_ptr(), y.data_ptr(), None if d_xl is None else d_xl.data_ptr(), None if d_yl is None else d_yl.data_ptr(),
-                        B, C, Tx, Ty, metric, bufs[0][1].data_ptr(), bufs[1][1].data_ptr(), bufs[2][1].data_ptr() if want_path else None, _stream_ptr())
-    torch.cuda.synchronize()
-    for (whole, view), n in zip(bufs, (B, B, B * NP * 2)):
-        fill = whole[0].item()
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), "sentinel margin of ev_dtw"
-    if not want_path:
-        assert bool((bufs[2][1] == -777).all()), "a path that was not asked for was written"
-    return (rc, bufs[0][1].cpu().numpy().copy(), bufs[1][1].cpu().numpy().copy(),
-            bufs[2][1].reshape(B, NP, 2).cpu().numpy().copy() if want_path else None)
+                        B, C, Tx, Ty, metric, out.ptr("cost"), out.ptr("steps"), out.ptr("path"), _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 def check_equal(dev, ref, what):
@@ -89,9 +72,7 @@ def check_close(dev, ref, what):
 
 @pytest.fixture(scope="module")
 def eng():
-    e = Engine(0)                                                        # no weights loaded
-    yield e
-    e.close()
+    yield from A.one_engine()
 
 
 # ---- 1. exact, with ties -----------------------------------------------------------------------------------------------------------------
@@ -100,7 +81,7 @@ def test_integer_features_are_exact_ties_included(eng, C, Tx, Ty):
     x, y, xl, yl = R.exact_batch(C, Tx, Ty)
     ref = ref_of(("exact", C, Tx, Ty), x, y, xl, yl, 1)
     rc, *dev = raw(eng, x, y, xl, yl, 1)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check_equal(dev, ref, f"exact C{C} {Tx}x{Ty}")
 
 
@@ -111,7 +92,7 @@ def test_euclidean_parity_with_the_restatement(eng, C, Tx, Ty):
     ref = ref_of(("euclid", C, Tx, Ty), x, y, xl, yl, 0)
     assert np.all(ref["margin"] >= 1e-9), "the reference's path margin is under 1e-9 (change the seed)"
     rc, *dev = raw(eng, x, y, xl, yl, 0)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check_close(dev, ref, f"euclid C{C} {Tx}x{Ty}")
     for b in range(len(xl)):
         K = dev[1][b]
@@ -130,7 +111,7 @@ def test_a_warp_is_recovered_exactly(eng, metric):
         want.append(np.stack([idx, np.arange(ty)], axis=1))
     x, y, xl, yl = R.pad_batch(rows)
     rc, cost, steps, path = raw(eng, x, y, xl, yl, metric)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     for b, w in enumerate(want):
         assert cost[b] == 0.0 and steps[b] == yl[b]
         assert np.array_equal(path[b, : yl[b]], w) and np.all(path[b, yl[b]:] == -1)
@@ -142,7 +123,7 @@ def test_edges(eng, Tx, Ty):
     x, y, xl, yl = R.edge_batch(Tx, Ty)
     ref = ref_of(("edge", Tx, Ty), x, y, xl, yl, 0)
     rc, *dev = raw(eng, x, y, xl, yl, 0)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check_close(dev, ref, f"edge {Tx}x{Ty}")
 
 
@@ -151,7 +132,7 @@ def test_the_limit_4096_by_4096(eng):
     ref = ref_of("limit", x, y, None, None, R.LIMIT_METRIC)
     assert ref["margin"][0] >= 1e-9, "the reference's path margin is under 1e-9 (change the seed)"
     rc, *dev = raw(eng, x, y, None, None, R.LIMIT_METRIC)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check_close(dev, ref, "limit 4096x4096")
 
 
@@ -235,7 +216,7 @@ def test_null_outputs_fail_with_a_message(eng):
     steps = torch.zeros(1, dtype=torch.int32, device=DEV)
     for c, s, word in ((None, steps.data_ptr(), "d_cost"), (cost.data_ptr(), None, "d_steps")):
         rc = eng.lib.ev_dtw(eng.h, x.data_ptr(), x.data_ptr(), None, None, 1, 2, 4, 4, 0, c, s, None, _stream_ptr())
-        assert rc != 0 and word in eng.lib.ev_last_error(eng.h).decode()
+        assert rc != 0 and word in err_of(eng)
 
 
 # ---- 8. NULL path ------------------------------------------------------------------------------------------------------------------------

@@ -11,7 +11,7 @@ by float64 rounding.  The rule of every comparison (``check``):
   * every entry of d_lpc and d_formant within 1e-9 max(|ref|, 1): the project's float64 margin (tests/test_gpu_voice_quality.py).
 Observed on the MI355X: d_lpc 2.1e-14, frequency 3.1e-14 and bandwidth 4.4e-14 at worst over all cases, every count equal, at most 15 iterations.
 Every case prints its worst figure, DESIGN section 3.20 records them; the gate stays at 1e-9.  Every raw call writes into buffers with sentinel
-margins; 50.0 sits behind every row's length.
+margins (tests/analysis_gpu.py); 50.0 sits behind every row's length.
 """
 import json
 
@@ -19,14 +19,14 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import formants_ref as R
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-M = 64                                   # sentinel margin, elements
 SMALL = R.GEOMETRIES[0]
 BIG = R.GEOMETRIES[3]
 _REF = {}
@@ -35,12 +35,7 @@ _REF = {}
 def ref_of(key, x, lens, g):
     """The restatements' results (float64: lpc, formant, count, iters, margin; longdouble: the same five), computed once per case and never
     modified."""
-    if key not in _REF:
-        r = R.batch(x, lens, g) + R.batch(x, lens, g, dtype=np.longdouble)
-        for v in r:
-            v.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
+    return A.frozen(_REF, key, lambda: R.batch(x, lens, g) + R.batch(x, lens, g, dtype=np.longdouble))
 
 
 def load(eng, g, null=False, window=None, **kw):
@@ -52,11 +47,6 @@ def load(eng, g, null=False, window=None, **kw):
                                     a["nform"])
 
 
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
-
-
 def raw(eng, g, x, lens, floor=R.POWER_FLOOR, B=None, L=None, null=()):
     """ev_formants into guarded buffers: (rc, lpc (B, NF, p + 2), formant (B, NF, nform, 2), count (B, NF)) on the host; an output named in
     ``null`` is passed as NULL and comes back None.  ``B`` / ``L`` override the shape passed to the library."""
@@ -65,24 +55,11 @@ def raw(eng, g, x, lens, floor=R.POWER_FLOOR, B=None, L=None, null=()):
     B, L = Bx if B is None else B, Lx if L is None else L
     NF = R.frames(Lx, g.H)
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
-    names = ("lpc", "formant", "count")
-    shapes = ((Bx, NF, g.order + 2), (Bx, NF, g.nform, 2), (Bx, NF))
-    fills = ((torch.float64, 777.0), (torch.float64, 777.0), (torch.int32, -777))
-    bufs = [guarded(int(np.prod(s)), dt, f) for s, (dt, f) in zip(shapes, fills)]
-    ptr = lambda i: None if names[i] in null else bufs[i][1].data_ptr()
+    out = A.Guarded({"lpc": ((Bx, NF, g.order + 2), torch.float64), "formant": ((Bx, NF, g.nform, 2), torch.float64), "count": ((Bx, NF), torch.int32)},
+                    null)
     rc = eng.lib.ev_formants(eng.h, None if "x" in null else x.data_ptr(), None if d_len is None else d_len.data_ptr(), B, L, float(floor),
-                             ptr(0), ptr(1), ptr(2), _stream_ptr())
-    torch.cuda.synchronize()
-    out = []
-    for i, ((whole, view), shape) in enumerate(zip(bufs, shapes)):
-        fill, n = whole[0].item(), int(np.prod(shape))
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), f"sentinel margin of d_{names[i]}"
-        if rc != 0 or names[i] in null:
-            assert bool((view == fill).all()), f"d_{names[i]} was not asked for (or the call failed) and was written"
-            out.append(None)
-        else:
-            out.append(view.reshape(shape).cpu().numpy().copy())
-    return (rc, *out)
+                             out.ptr("lpc"), out.ptr("formant"), out.ptr("count"), _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 def check(dev, ref, what):
@@ -107,22 +84,12 @@ def check(dev, ref, what):
 
 
 def engine_with(g):
-    e = Engine(0)                                                        # no weights loaded
-    assert load(e, g) == 0, e.lib.ev_last_error(e.h).decode()
-    return e
+    return A.engine_with(load, g)
 
 
 @pytest.fixture(scope="module")
 def engines():
-    made = {}
-
-    def get(g):
-        if g not in made:
-            made[g] = engine_with(g)
-        return made[g]
-    yield get
-    for e in made.values():
-        e.close()
+    yield from A.engines_on_demand(engine_with)
 
 
 @pytest.fixture(scope="module")
@@ -141,7 +108,7 @@ def test_geometry_against_the_restatement(engines, g):
     assert [n % 4 for n in nfs] == [3, 0, 1] and max(lens) <= 8000
     eng = engines(g)
     rc, *dev = raw(eng, g, x, lens)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref, f"{g[:4]} lens {lens}")
     for b in range(3):
         assert not dev[0][b, nfs[b]:].any() and not dev[1][b, nfs[b]:].any() and not dev[2][b, nfs[b]:].any(), "zeros past the row's own frames"
@@ -161,7 +128,7 @@ def test_row_alone_in_a_batch_as_a_prefix_and_without_lpc_give_the_same_bits(eng
     n = lens[0]
     c = x[0, :n].copy()
     rc, *alone = raw(eng, g, c[None], None)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     rc, *again = raw(eng, g, c[None], None)
     assert rc == 0 and all(np.array_equal(a, b) for a, b in zip(alone, again)), "two calls"
     rc, none, f2, c2 = raw(eng, g, c[None], None, null=("lpc",))
@@ -198,7 +165,7 @@ def test_silent_frames_and_bad_rows(small):
     x = np.concatenate([x, np.zeros((1, L), np.float32), hole[None], x[:1], x[:1], x[:1]])
     lens = lens + [2000, lens[0], 0, -3, L + 1]
     rc, lpc, fm, ct = raw(small, g, x, lens)
-    assert rc == 0, small.lib.ev_last_error(small.h).decode()
+    assert rc == 0, err_of(small)
     ref = ref_of("degenerate", x, lens, g)
     check((lpc, fm, ct), ref, "a zero row, a row with a silent middle and bad rows beside good ones")
     assert not lpc[3].any() and not fm[3].any() and not ct[3].any(), "a zero row: every frame is silent"
@@ -218,13 +185,13 @@ def test_a_row_of_one_sample_has_one_frame(small):
     quiet[0, 0] = 1e-6
     for xs, ls in ((quiet, [1, lens[1]]), (quiet[:1, :1], None)):
         rc, lpc, fm, ct = raw(small, g, xs, ls)
-        assert rc == 0, small.lib.ev_last_error(small.h).decode()
+        assert rc == 0, err_of(small)
         assert not ct[0].any() and not fm[0].any() and not lpc[0].any(), "under the floor: a silent frame"
         assert np.isfinite(lpc).all() and np.isfinite(fm).all()
     assert ct.shape == (1, 1)
     for i, (xs, ls) in enumerate(((x[:2], [1, lens[1]]), (x[:2, :1], None), (np.full((1, 1), 0.5, np.float32), None))):
         rc, lpc, fm, ct = raw(small, g, xs, ls)
-        assert rc == 0, small.lib.ev_last_error(small.h).decode()
+        assert rc == 0, err_of(small)
         check((lpc, fm, ct), ref_of(("one sample", i), xs, ls, g), f"a row of one sample, case {i}")
         assert not ct[0, 1:].any() and not fm[0, 1:].any() and not lpc[0, 1:].any()
         print(f"formants, a row of one sample: count {ct[0, 0]}, E0 {lpc[0, 0, -1]:.3e}, formants {fm[0, 0].ravel().round(2).tolist()}")
@@ -251,7 +218,7 @@ def test_zeros_outside_the_row_at_both_ends(engines, g):
     x, _, lens = R.padded([(s, s) for s in sig])
     ref = ref_of(("edge", g), x, lens, g)
     rc, *dev = raw(eng, g, x, lens)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref, f"edges {g[:4]} lens {lens}")
     for b, n in enumerate(lens):
         nf = R.frames(n, g.H)
@@ -274,7 +241,7 @@ BAD_CALL = [
 def test_each_limit_of_ev_formants_fails_with_a_message_naming_it(small, word, kw):
     z = np.zeros((2, 256), np.float32)
     rc, *_ = raw(small, SMALL, z, None, **kw)                             # (a failed call writes nothing: raw checks that)
-    msg = small.lib.ev_last_error(small.h).decode()
+    msg = err_of(small)
     assert rc != 0 and "ev_formants" in msg and word in msg, msg
 
 
@@ -299,7 +266,7 @@ BAD_LOAD = [
 def test_each_limit_of_ev_load_formants_fails_with_a_message_naming_it(small, word, kw):
     n0 = small.alloc_count()
     rc = load(small, SMALL, **kw)
-    msg = small.lib.ev_last_error(small.h).decode()
+    msg = err_of(small)
     assert rc != 0 and "ev_load_formants" in msg and word in msg, msg
     assert small.alloc_count() == n0
     x, lens = R.rows_for(SMALL)                                           # the tables loaded before are still the ones in use
@@ -314,14 +281,14 @@ def test_a_call_before_a_load_fails_loading_again_replaces_the_tables_and_calls_
     try:
         z = np.zeros((1, 256), np.float32)
         rc, *_ = raw(e, SMALL, z, None)
-        assert rc != 0 and "ev_load_formants" in e.lib.ev_last_error(e.h).decode()
+        assert rc != 0 and "ev_load_formants" in err_of(e)
         n0 = e.alloc_count()
-        assert load(e, R.GEOMETRIES[2]) == 0, e.lib.ev_last_error(e.h).decode()
+        assert load(e, R.GEOMETRIES[2]) == 0, err_of(e)
         assert e.alloc_count() == n0 + 1, "the window is one device block that counts in ev_alloc_count"
         assert load(e, SMALL) == 0 and e.alloc_count() == n0 + 2
         x, lens = R.rows_for(SMALL)
         rc, *dev = raw(e, SMALL, x, lens)
-        assert rc == 0, e.lib.ev_last_error(e.h).decode()
+        assert rc == 0, err_of(e)
         check(dev, ref_of(("rows", SMALL), x, lens, SMALL), "after loading twice")
         n1 = e.alloc_count()
         assert n1 == n0 + 2, "a call allocates nothing"

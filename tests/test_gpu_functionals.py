@@ -11,7 +11,7 @@ Observed on the MI355X: every entry of d_stat and d_count EQUAL to the float64 r
 (the restatement adds in the device's order; the square root is the only library function); float64 against longdouble 5.1e-14 at worst (the
 4096-frame ramp); voice_functionals' 63 means within 2.6e-16 relative of the *_statistics functions (gate 1e-12) and its f0_semitones percentiles
 within 6.4e-6 semitones of prosody_statistics (gate 1e-4).  Every case prints its worst figure; DESIGN section 3.23 records them.  Every raw call
-writes into buffers with 64-element sentinel margins; NaN under a mask of ones lies behind every row's length, so a read behind it would show as a
+writes into buffers with 64-element sentinel margins (tests/analysis_gpu.py); NaN under a mask of ones lies behind every row's length, so a read behind it would show as a
 dropped frame.
 """
 import json
@@ -20,15 +20,15 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import functionals_ref as R
 import perturbation_ref as P
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-M = 64                                   # sentinel margin, elements
 _REF, _CASES = {}, {}
 
 
@@ -40,18 +40,7 @@ def case(name):
 
 def ref_of(key, v, mask, lens, q):
     """The restatements' results (float64, longdouble), computed once per case and never modified."""
-    if key not in _REF:
-        r = (R.batch(v, mask, lens, q), R.batch(v, mask, lens, q, dtype=np.longdouble))
-        for d in r:
-            for a in d.values():
-                a.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
-
-
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
+    return A.frozen(_REF, key, lambda: (R.batch(v, mask, lens, q), R.batch(v, mask, lens, q, dtype=np.longdouble)))
 
 
 def raw(eng, v, mask, lens, q, null=(), **kw):
@@ -63,23 +52,11 @@ def raw(eng, v, mask, lens, q, null=(), **kw):
     NQx = len(qa)
     d_mask = None if mask is None else torch.as_tensor(np.asarray(mask, dtype=np.uint8)).to(DEV).contiguous()
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
-    names, shapes = ("stat", "count"), ((Bx, Kx, 12 + NQx), (Bx, Kx, 8))
-    bufs = [guarded(int(np.prod(s)), dt, f) for s, (dt, f) in zip(shapes, ((torch.float64, 777.0), (torch.int32, -777)))]
-    ptr = lambda i: None if names[i] in null else bufs[i][1].data_ptr()
+    out = A.Guarded({"stat": ((Bx, Kx, 12 + NQx), torch.float64), "count": ((Bx, Kx, 8), torch.int32)}, null)
     rc = eng.lib.ev_functionals(eng.h, None if "v" in null else v.data_ptr(), None if d_mask is None else d_mask.data_ptr(),
                                 None if d_len is None else d_len.data_ptr(), kw.get("B", Bx), kw.get("K", Kx), kw.get("F", Fx),
-                                None if "q" in null or not NQx else qa.ctypes.data, kw.get("NQ", NQx), ptr(0), ptr(1), _stream_ptr())
-    torch.cuda.synchronize()
-    out = []
-    for i, ((whole, view), shape) in enumerate(zip(bufs, shapes)):
-        fill, n = whole[0].item(), int(np.prod(shape))
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), f"sentinel margin of d_{names[i]}"
-        if rc != 0:
-            assert bool((view == fill).all()), f"the call failed and d_{names[i]} was written"
-            out.append(None)
-        else:
-            out.append(view.reshape(shape).cpu().numpy().copy())
-    return (rc, *out)
+                                None if "q" in null or not NQx else qa.ctypes.data, kw.get("NQ", NQx), out.ptr("stat"), out.ptr("count"), _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 def check(dev, ref, what):
@@ -108,15 +85,13 @@ def check(dev, ref, what):
 
 @pytest.fixture(scope="module")
 def eng():
-    e = Engine(0)                                                        # no weights loaded
-    yield e
-    e.close()
+    yield from A.one_engine()
 
 
 def run_case(eng, name):
     v, mask, lens, q = case(name)
     rc, *dev = raw(eng, v, mask, lens, q)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     ref = ref_of(name, v, mask, lens, q)
     check(dev, ref, f"{name} {v.shape} lens {lens} NQ {len(q)}")
     return v, mask, lens, q, dev, ref
@@ -191,7 +166,7 @@ def test_alone_in_a_batch_at_another_k_as_a_prefix_twice_and_under_every_arithme
     q = R.Q3
     n0 = eng.alloc_count()
     rc, *alone = raw(eng, c[None, None], cm[None, None], None, q)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(alone, ref_of("identity", c[None, None], cm[None, None], None, q), "the identity contour alone")
     assert alone[1][0, 0, 2] > 3 and alone[1][0, 0, 6] > 3
     rc, *again = raw(eng, c[None, None], cm[None, None], None, q)
@@ -267,7 +242,7 @@ def test_each_limit_fails_with_a_message_naming_it_and_writes_nothing(eng, word,
     q = kw.pop("q", R.Q3)
     z = np.zeros((2, 2, 16))
     rc, *_ = raw(eng, z, None, None, q, **kw)                            # (a failed call writes nothing: raw checks that)
-    msg = eng.lib.ev_last_error(eng.h).decode()
+    msg = err_of(eng)
     assert rc != 0 and "ev_functionals" in msg and word in msg, msg
 
 

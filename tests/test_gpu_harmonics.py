@@ -9,7 +9,7 @@ over d_period and d_formant of their own, so only the spectrum differs between d
   * d_count EQUAL and every k* equal (rint(f_h nfft / sr - the restatement's shift) against the restatement's k*);
   * every entry of d_frame and d_harm within 1e-9 max(|ref|, 1), the project's float64 margin, and exactly zero where the restatement is.
 Every case prints its worst figures and its smallest margins; DESIGN section 3.22 records them.  Every raw call writes into buffers with 64-element
-sentinel margins; 50.0 lies behind every row's length, and a period behind a row's frames.
+sentinel margins (tests/analysis_gpu.py); 50.0 lies behind every row's length, and a period behind a row's frames.
 """
 import json
 
@@ -17,38 +17,26 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import harmonics_ref as R
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-M = 64                                   # sentinel margin, elements
 _CASES, _REF, _LOADED = {}, {}, {}
-NAMES = ("frame", "count", "harm")
 
 
 def case(g):
     """(x, lens, period, formant, fcount) of a geometry, made once and never modified."""
-    if g not in _CASES:
-        c = R.case(g)
-        for v in c:
-            if isinstance(v, np.ndarray):
-                v.setflags(write=False)
-        _CASES[g] = c
-    return _CASES[g]
+    return A.frozen(_CASES, g, lambda: R.case(g))
 
 
 def ref_of(g):
     """(float64 result, the conditions' report) of a geometry's case, computed once and never modified."""
-    if g not in _REF:
-        x, lens, period, formant, fcount = case(g)
-        r64, rep = R.conditions(x, lens, period, g, formant, fcount)
-        for v in r64.values():
-            v.setflags(write=False)
-        _REF[g] = (r64, rep)
-    return _REF[g]
+    x, lens, period, formant, fcount = case(g)
+    return A.frozen(_REF, g, lambda: R.conditions(x, lens, period, g, formant, fcount))
 
 
 def load(eng, g, **kw):
@@ -69,11 +57,6 @@ def load(eng, g, **kw):
     return rc
 
 
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
-
-
 def raw(eng, g, x, lens, period, formant=None, fcount=None, B=None, L=None, null=(), nform=None, floor=R.POWER_FLOOR):
     """ev_harmonics into guarded buffers: (rc, frame (B, NF, 8), count (B, NF, 2), harm (B, NF, n_harm, 2)) on the host; an argument named in
     ``null`` is passed as NULL (an output then comes back None).  ``B`` / ``L`` / ``nform`` override what is passed to the library."""
@@ -86,24 +69,11 @@ def raw(eng, g, x, lens, period, formant=None, fcount=None, B=None, L=None, null
     d_fm = None if formant is None else torch.tensor(np.array(formant, dtype=np.float64)).to(DEV)
     d_fc = None if fcount is None else torch.tensor(np.array(fcount, dtype=np.int32)).to(DEV)
     nform = (0 if formant is None else int(np.asarray(formant).shape[2])) if nform is None else nform
-    shapes = ((Bx, NF, 8), (Bx, NF, 2), (Bx, NF, g.n_harm, 2))
-    fills = ((torch.float64, 777.0), (torch.int32, -777), (torch.float64, 777.0))
-    bufs = [guarded(int(np.prod(s)), dt, f) for s, (dt, f) in zip(shapes, fills)]
-    ptr = lambda i: None if NAMES[i] in null else bufs[i][1].data_ptr()
+    out = A.Guarded({"frame": ((Bx, NF, 8), torch.float64), "count": ((Bx, NF, 2), torch.int32), "harm": ((Bx, NF, g.n_harm, 2), torch.float64)}, null)
     opt = lambda name, t: None if t is None or name in null else t.data_ptr()
     rc = eng.lib.ev_harmonics(eng.h, opt("x", x), opt("len", d_len), B, L, opt("period", d_per), opt("formant", d_fm), opt("fcount", d_fc), nform,
-                              float(floor), ptr(0), ptr(1), ptr(2), _stream_ptr())
-    torch.cuda.synchronize()
-    out = []
-    for i, ((whole, view), shape) in enumerate(zip(bufs, shapes)):
-        fill, n = whole[0].item(), int(np.prod(shape))
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), f"sentinel margin of d_{NAMES[i]}"
-        if rc != 0 or NAMES[i] in null:
-            assert bool((view == fill).all()), f"d_{NAMES[i]} was not asked for (or the call failed) and was written"
-            out.append(None)
-        else:
-            out.append(view.reshape(shape).cpu().numpy().copy())
-    return (rc, *out)
+                              float(floor), out.ptr("frame"), out.ptr("count"), out.ptr("harm"), _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 def check(dev, r64, rep, g, what):
@@ -129,13 +99,7 @@ def check(dev, r64, rep, g, what):
 
 @pytest.fixture(scope="module")
 def eng():
-    e = Engine(0)                                                        # no weights loaded
-    yield e
-    e.close()
-
-
-def err_of(eng):
-    return eng.lib.ev_last_error(eng.h).decode()
+    yield from A.one_engine()
 
 
 # ---- 1. against the restatement ----------------------------------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@ comparison (``check``):
     its own row maximum.  1e-9 is four orders above the reordering error and corresponds to 4e-9 dB;
   * each case first asserts that the restatement's gate margin is at least 1e-3 dB; then d_counts must be EQUAL;
   * d_block must be BIT-EQUAL to the header's formula applied on the host to the device's own d_sub.
-Every raw call writes into buffers with sentinel margins.  Inputs carry loud garbage (50.0) behind each row's length.
+Every raw call writes into buffers with sentinel margins (tests/analysis_gpu.py).  Inputs carry loud garbage (50.0) behind each row's length.
 
 Observed on the MI355X (printed by every case; the gate stays at 1e-9): the worst relative error of any case is 8.6e-12 (d_sub of the
 gating row at S = 64, on a sub-block 7e-9 of the row's maximum, where the loud segment's decaying tail is measured against near-silence);
@@ -23,14 +23,14 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import loudness_ref as R
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
-from emojivoice_amd._lib import Engine, _stream_ptr
+from emojivoice_amd._lib import _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-M = 64                                   # sentinel margin, elements
 TOL = 1e-9
 K22 = audio.k_weighting(22050)
 _REF = {}
@@ -38,17 +38,7 @@ _REF = {}
 
 def ref_of(key, x, lens, S, coef=K22):
     """The restatement's result, computed once per case and never modified."""
-    if key not in _REF:
-        r = R.loudness(x, lens, S, coef)
-        for v in r.values():
-            v.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
-
-
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
+    return A.frozen(_REF, key, lambda: R.loudness(x, lens, S, coef))
 
 
 def raw(eng, x, lens, S, coef=K22, abs_gate=R.ABS_GATE, want=(True, True), B=None, L=None, null=()):
@@ -60,25 +50,13 @@ def raw(eng, x, lens, S, coef=K22, abs_gate=R.ABS_GATE, want=(True, True), B=Non
     NS = Lx // S if S > 0 else 0
     NB = max(NS - 3, 0)
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
-    bufs = [guarded(n, dt, fill) for n, dt, fill in ((Bx * NS, torch.float64, 777.0), (Bx * NB, torch.float64, 777.0), (Bx * 2, torch.float64, 777.0),
-                                                    (Bx * 3, torch.int32, -777))]
+    out = A.Guarded({"sub": ((Bx, NS), torch.float64), "block": ((Bx, NB), torch.float64), "gated": ((Bx, 2), torch.float64),
+                     "counts": ((Bx, 3), torch.int32)}, tuple(null) + tuple(k for k, w in zip(("sub", "block"), want) if not w))
     coef = None if coef is None else np.ascontiguousarray(coef, dtype=np.float64)
-    ptr = lambda i, name: None if name in null or (i < 2 and not want[i]) else bufs[i][1].data_ptr()
     rc = eng.lib.ev_loudness(eng.h, None if "x" in null else x.data_ptr(), None if d_len is None else d_len.data_ptr(), B, L, S,
-                             None if coef is None else coef.ctypes.data, float(abs_gate), ptr(0, "sub"), ptr(1, "block"), ptr(2, "gated"), ptr(3, "counts"),
-                             _stream_ptr())
-    torch.cuda.synchronize()
-    out = []
-    for i, ((whole, view), shape) in enumerate(zip(bufs, ((Bx, NS), (Bx, NB), (Bx, 2), (Bx, 3)))):
-        fill = whole[0].item()
-        n = shape[0] * shape[1]
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), "sentinel margin of ev_loudness"
-        if rc != 0 or (i < 2 and not want[i]):
-            assert bool((view == fill).all()), "an output that was not asked for (or of a failed call) was written"
-            out.append(None)
-        else:
-            out.append(view.reshape(shape).cpu().numpy().copy())
-    return (rc, *out)
+                             None if coef is None else coef.ctypes.data, float(abs_gate), out.ptr("sub"), out.ptr("block"), out.ptr("gated"),
+                             out.ptr("counts"), _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 def rel_err(dev, ref):
@@ -109,9 +87,7 @@ def check(dev, ref, S, what):
 
 @pytest.fixture(scope="module")
 def eng():
-    e = Engine(0)                                                        # no weights loaded
-    yield e
-    e.close()
+    yield from A.one_engine()
 
 
 # ---- 1. gating ---------------------------------------------------------------------------------------------------------------------------
@@ -122,7 +98,7 @@ def test_gating(eng, S):
     ref = ref_of(("gating", S), x, lens, S)
     assert tuple(ref["counts"][0]) == R.GATING_COUNTS[S] and abs(ref["integrated"][0] - R.GATING_LUFS[S]) <= 0.01
     rc, *dev = raw(eng, x, lens, S)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref, S, f"gating S{S} len {len(row)}")
     assert not dev[0][0, len(row) // S:].any() and not dev[1][0, ref["counts"][0, 0]:].any(), "zeros past the row's own sub-blocks and blocks"
 
@@ -133,7 +109,7 @@ def test_edges_in_one_ragged_batch(eng):
     ref = ref_of("edges", x, lens, R.EDGE_S)
     assert ref["counts"][:, 0].tolist() == [0, 1, 1, 1, 0, 12, 13, 13, 30, 0, 0]
     rc, *dev = raw(eng, x, lens, R.EDGE_S)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref, R.EDGE_S, f"edges S64 lens {lens}")
     for b in (9, 10):
         assert not dev[0][b].any() and not dev[1][b].any() and not dev[2][b].any() and not dev[3][b].any(), "len > L and len = 0 are rows of zeros"
@@ -147,7 +123,7 @@ def test_row_alone_in_a_batch_and_as_a_prefix_give_the_same_bits(eng):
     row = R.gating_row(S)                                                # 4028 samples: four chunks of the device's filter
     n, ns = len(row), len(row) // S
     rc, *alone = raw(eng, row[None], None, S)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     rc, *again = raw(eng, row[None], None, S)
     assert rc == 0 and all(np.array_equal(a, b) for a, b in zip(alone, again)), "two calls"
     g = np.random.default_rng(3)
@@ -177,7 +153,7 @@ def test_row_alone_in_a_batch_and_as_a_prefix_give_the_same_bits(eng):
 # ---- 4. silence --------------------------------------------------------------------------------------------------------------------------
 def test_silence(eng):
     rc, sub, block, gated, counts = raw(eng, np.zeros((1, 8 * 64), np.float32), None, 64)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     assert counts.tolist() == [[5, 0, 0]] and gated.tolist() == [[0.0, 0.0]]
     assert sub.shape == (1, 8) and block.shape == (1, 5) and not sub.any() and not block.any()
     out = audio.loudness(torch.zeros(2, 22050, device=DEV), lengths=[22050, 500])
@@ -226,7 +202,7 @@ def test_each_limit_fails_with_a_message_naming_it(eng, word, kw):
     kw = dict(kw)
     S = kw.pop("S", 64)
     rc, *_ = raw(eng, np.zeros((2, 1024), np.float32), None, S, **kw)   # (a failed call writes nothing: raw checks that)
-    msg = eng.lib.ev_last_error(eng.h).decode()
+    msg = err_of(eng)
     assert rc != 0 and "ev_loudness" in msg and word in msg, msg
 
 

@@ -9,7 +9,7 @@ every comparison (``check``):
   * d_marks and d_count EQUAL;
   * every entry of d_frame within 1e-9 max(|ref|, 1): the project's float64 margin.
 Observed on the MI355X: every mark and count equal, d_frame 3.3e-16 at worst over all cases (the restatement adds in the device's order, so what
-remains is the device library's log10 in the shimmer in dB).  Every case prints its worst figure; DESIGN section 3.21 records them.  Every raw call writes into buffers with 64-element sentinel margins; 50.0 lies
+remains is the device library's log10 in the shimmer in dB).  Every case prints its worst figure; DESIGN section 3.21 records them.  Every raw call writes into buffers with 64-element sentinel margins (tests/analysis_gpu.py); 50.0 lies
 behind every row's length.
 """
 import json
@@ -18,15 +18,15 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import perturbation_ref as R
 import pitch_ref
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-M = 64                                   # sentinel margin, elements
 _REF, _CASES = {}, {}
 
 
@@ -38,19 +38,7 @@ def case(name):
 
 def ref_of(key, x, lens, lag, g):
     """The restatements' results (float64, longdouble), computed once per case and never modified."""
-    if key not in _REF:
-        r = (R.batch(x, lens, lag, g), R.batch(x, lens, lag, g, dtype=np.longdouble))
-        for d in r:
-            for v in d.values():
-                if isinstance(v, np.ndarray):
-                    v.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
-
-
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
+    return A.frozen(_REF, key, lambda: (R.batch(x, lens, lag, g), R.batch(x, lens, lag, g, dtype=np.longdouble)))
 
 
 def raw(eng, g, x, lens, lag, B=None, L=None, null=(), **kw):
@@ -65,25 +53,11 @@ def raw(eng, g, x, lens, lag, B=None, L=None, null=(), **kw):
     F = R.frames(Lx, g.H)
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
     d_lag = torch.as_tensor(np.asarray(lag, dtype=np.int32).reshape(Bx, F)).to(DEV).contiguous()
-    names = ("frame", "count", "marks")
-    shapes = ((Bx, F, 8), (Bx, F, 4), (Bx, F, 2 * g.nc + 1))
-    fills = ((torch.float64, 777.0), (torch.int32, -777), (torch.int32, -777))
-    bufs = [guarded(int(np.prod(s)), dt, f) for s, (dt, f) in zip(shapes, fills)]
-    ptr = lambda i: None if names[i] in null else bufs[i][1].data_ptr()
+    out = A.Guarded({"frame": ((Bx, F, 8), torch.float64), "count": ((Bx, F, 4), torch.int32), "marks": ((Bx, F, 2 * g.nc + 1), torch.int32)}, null)
     rc = eng.lib.ev_perturbation(eng.h, None if "x" in null else x.data_ptr(), None if d_len is None else d_len.data_ptr(), B, L, a["H"],
                                  None if "lag" in null else d_lag.data_ptr(), a["nc"], a["W"], float(a["pf"]), float(a["af"]), float(a["floor"]),
-                                 ptr(0), ptr(1), ptr(2), _stream_ptr())
-    torch.cuda.synchronize()
-    out = []
-    for i, ((whole, view), shape) in enumerate(zip(bufs, shapes)):
-        fill, n = whole[0].item(), int(np.prod(shape))
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), f"sentinel margin of d_{names[i]}"
-        if rc != 0 or names[i] in null:
-            assert bool((view == fill).all()), f"d_{names[i]} was not asked for (or the call failed) and was written"
-            out.append(None)
-        else:
-            out.append(view.reshape(shape).cpu().numpy().copy())
-    return (rc, *out)
+                                 out.ptr("frame"), out.ptr("count"), out.ptr("marks"), _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 NAMES = ("jitter", "jitter_abs", "shimmer", "shimmer_db", "r", "Tmean", "Amean", "rap")
@@ -110,15 +84,13 @@ def check(dev, ref, what):
 
 @pytest.fixture(scope="module")
 def eng():
-    e = Engine(0)                                                        # no weights loaded
-    yield e
-    e.close()
+    yield from A.one_engine()
 
 
 def run_case(eng, name):
     x, lens, lag, g = case(name)
     rc, *dev = raw(eng, g, x, lens, lag)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     ref = ref_of(name, x, lens, lag, g)
     check(dev, ref, f"{name} {tuple(g)[:3]} lens {lens}")
     return x, lens, lag, g, dev, ref
@@ -165,7 +137,7 @@ def test_a_row_of_one_sample_alone(eng):
     x = np.full((1, 1), 0.5, np.float32)
     lag = np.full((1, 1), 40, np.int32)
     rc, *dev = raw(eng, g, x, None, lag)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref_of("one", x, None, lag, g), "a (1, 1) row")
     assert dev[1].shape == (1, 1, 4) and not dev[1].any() and (dev[2] == -1).all()
 
@@ -198,7 +170,7 @@ def test_row_alone_in_a_batch_as_a_prefix_without_marks_twice_and_under_every_ar
     c = x[0, :n].copy()
     n0 = eng.alloc_count()
     rc, *alone = raw(eng, g, c[None], None, lag[:1, :nf])
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     rc, *again = raw(eng, g, c[None], None, lag[:1, :nf])
     assert rc == 0 and all(np.array_equal(a, b) for a, b in zip(alone, again)), "two calls"
     rc, f2, c2, none = raw(eng, g, c[None], None, lag[:1, :nf], null=("marks",))
@@ -277,7 +249,7 @@ def test_each_limit_fails_with_a_message_naming_it_and_writes_nothing(eng, word,
     g = R.geo()
     z = np.zeros((2, 256), np.float32)
     rc, *_ = raw(eng, g, z, None, np.full((2, 4), 40, np.int32), **kw)    # (a failed call writes nothing: raw checks that)
-    msg = eng.lib.ev_last_error(eng.h).decode()
+    msg = err_of(eng)
     assert rc != 0 and "ev_perturbation" in msg and word in msg, msg
 
 

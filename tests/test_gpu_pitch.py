@@ -8,7 +8,7 @@ few 2^-53 relative and d' likewise.  The rule of every comparison (``check``):
     tests/test_pitch_host.py asserts on the CPU that the parity rows leave out none;
   * |period - ref| <= 1e-5 ref on the voiced frames: the output is ONE float32 rounding (2^-24 = 6e-8 relative) of a float64 value;
   * d_cmnd within 1e-5 relative, by the same argument.
-Every raw call writes into buffers with sentinel margins.  Inputs carry loud garbage behind each row's d_len samples.
+Every raw call writes into buffers with sentinel margins (tests/analysis_gpu.py).  Inputs carry loud garbage behind each row's d_len samples.
 
 Times: not gated here (tools/pitch_bench.py).
 """
@@ -16,32 +16,22 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import pitch_ref as P
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, EvLibraryError, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 GARBAGE = P.GARBAGE
-M = 64                                   # sentinel margin, elements
 STD = P.STD
 _REF = {}
 
 
 def ref_of(key, x, lens, **kw):
     """The restatement's result, computed once per case and never modified."""
-    if key not in _REF:
-        r = P.pitch_yin(x, lens, **kw)
-        for v in r.values():
-            v.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
-
-
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
+    return A.frozen(_REF, key, lambda: P.pitch_yin(x, lens, **kw))
 
 
 def raw(eng, x, lens, frame_length=1024, hop_length=256, tau_min=36, tau_max=340, threshold=0.1, want=(True, True, True)):
@@ -50,21 +40,11 @@ def raw(eng, x, lens, frame_length=1024, hop_length=256, tau_min=36, tau_max=340
     B, L = x.shape
     F = -(-L // hop_length)
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
-    bufs = [guarded(B * F, dt, fill) for dt, fill in ((torch.int32, -777), (torch.float32, 777.0), (torch.float32, 777.0))]
-    ptrs = [bufs[i][1].data_ptr() if want[i] else None for i in range(3)]
+    out = A.Guarded({"lag": ((B, F), torch.int32), "period": ((B, F), torch.float32), "cmnd": ((B, F), torch.float32)},
+                    tuple(k for k, w in zip(("lag", "period", "cmnd"), want) if not w))
     rc = eng.lib.ev_pitch_yin(eng.h, x.data_ptr(), None if d_len is None else d_len.data_ptr(), B, L, frame_length, hop_length, tau_min, tau_max,
-                              threshold, ptrs[0], ptrs[1], ptrs[2], _stream_ptr())
-    torch.cuda.synchronize()
-    out = []
-    for i, (whole, view) in enumerate(bufs):
-        fill = whole[0].item()
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + B * F:] == fill).all()), "sentinel margin of ev_pitch_yin"
-        if want[i]:
-            out.append(view.reshape(B, F).cpu().numpy().copy())
-        else:
-            assert bool((view == fill).all()), "an output that was not asked for was written"
-            out.append(None)
-    return (rc, *out)
+                              threshold, out.ptr("lag"), out.ptr("period"), out.ptr("cmnd"), _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 def check(dev, ref, what, may_leave_out=None):
@@ -92,9 +72,7 @@ def check(dev, ref, what, may_leave_out=None):
 
 @pytest.fixture(scope="module")
 def eng():
-    e = Engine(0)                                                        # no weights loaded
-    yield e
-    e.close()
+    yield from A.one_engine()
 
 
 # ---- 1. parity ---------------------------------------------------------------------------------------------------------------------------
@@ -104,7 +82,7 @@ def test_parity_with_the_restatement(eng):
     assert int((ref["margin"] < 1e-9).sum()) == 0, "the parity rows must leave out no frame (change the seed)"
     assert (ref["lag"][0] > 0).sum() >= 26 and (ref["lag"][1] > 0).sum() >= 26 and (ref["lag"][2] > 0).sum() >= 4 and not ref["lag"][3].any()
     rc, *dev = raw(eng, x, lens, **STD)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref, "parity B4 L8192")
     assert np.all(dev[2][3] == 1.0), "a silent frame has d' = 1 at every lag"
     assert np.all(dev[0][2, 20:] == 0) and np.all(dev[2][2, 20:] == 0.0), "frames past ceil(5001 / 256) = 20"
@@ -120,7 +98,7 @@ def test_other_geometries(eng, W, H, t0, t1, L, f0):
     kw = dict(frame_length=W, hop_length=H, tau_min=t0, tau_max=t1, threshold=0.1)
     ref = ref_of(("geo", W, H, t0, t1), x, None, **kw)
     rc, *dev = raw(eng, x, None, **kw)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref, f"W{W} H{H} tau {t0}..{t1} L{L}")
     if t0 == t1 == 100:
         assert (ref["lag"][0] == 100).all()
@@ -210,7 +188,7 @@ def test_any_output_may_be_null(eng):
     assert rc == 0
     for want in [(True, False, False), (False, True, False), (False, False, True), (True, True, False), (True, False, True), (False, True, True)]:
         rc, *got = raw(eng, x, lens, want=want, **STD)
-        assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+        assert rc == 0, err_of(eng)
         for w, g, f in zip(want, got, full):
             assert (g is None) if not w else np.array_equal(g, f), f"outputs {want}"
 

@@ -15,7 +15,7 @@ to the reference's on every frame, a differing frame being tolerated only where 
 most 1 % of the frames.  The bin of an unvoiced frame is compared through the score only: unvoiced emissions are equal over the bins by
 construction, so where an unvoiced stretch sits is decided by roundings of the host tables alone.
 
-Every raw call writes into buffers with sentinel margins; inputs carry loud garbage behind each row's d_len samples.
+Every raw call writes into buffers with sentinel margins (tests/analysis_gpu.py); inputs carry loud garbage behind each row's d_len samples.
 Times: not gated here (tools/pyin_bench.py).
 """
 import math
@@ -24,44 +24,27 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import pitch_ref as P
 import pyin_ref as Y
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, EvLibraryError, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 GARBAGE = P.GARBAGE
-M = 64                                   # sentinel margin, elements
 _REF = {}
 
 
 def cached(key, make):
     """A reference result, computed once and never modified."""
-    if key not in _REF:
-        r = make()
-        flat = list(r.values()) if isinstance(r, dict) else [v for item in r for v in (item if isinstance(item, tuple) else (item,))]
-        for v in flat:
-            if isinstance(v, np.ndarray):
-                v.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
+    return A.frozen(_REF, key, make)
 
 
 def observed(name):
     x, lens, kw = {"std": Y.std_case, "small": Y.small_case}[name]()
     return x, lens, kw, cached(("observe", name), lambda: Y.observe(x, lens, **kw))
-
-
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
-
-
-def intact(whole, n, what):
-    fill = whole[0].item()
-    assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), f"sentinel margin of {what}"
 
 
 def raw_observe(eng, x, lens, frame_length, hop_length, tau_min, tau_max, sr, fmin, bins_per_octave, n_bins, w, boltzmann, no_trough_prob):
@@ -71,14 +54,11 @@ def raw_observe(eng, x, lens, frame_length, hop_length, tau_min, tau_max, sr, fm
     F = -(-L // hop_length)
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
     w = np.ascontiguousarray(w, dtype=np.float64)
-    (ow, ov), (pw, pvv) = guarded(B * F * n_bins, torch.float64, 777.0), guarded(B * F, torch.float64, 777.0)
+    out = A.Guarded({"obs": ((B, F, n_bins), torch.float64), "pv": ((B, F), torch.float64)})
     rc = eng.lib.ev_pyin_observe(eng.h, x.data_ptr(), None if d_len is None else d_len.data_ptr(), B, L, frame_length, hop_length, tau_min, tau_max,
                                  float(sr), float(fmin), bins_per_octave, n_bins, w.ctypes.data, w.size, boltzmann, no_trough_prob,
-                                 ov.data_ptr(), pvv.data_ptr(), _stream_ptr())
-    torch.cuda.synchronize()
-    intact(ow, B * F * n_bins, "d_obs")
-    intact(pw, B * F, "d_pv")
-    return rc, ov.reshape(B, F, n_bins).cpu().numpy().copy(), pvv.reshape(B, F).cpu().numpy().copy()
+                                 out.ptr("obs"), out.ptr("pv"), _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 def raw_decode(eng, obs, pv, lens, L, hop_length, tables):
@@ -88,23 +68,18 @@ def raw_decode(eng, obs, pv, lens, L, hop_length, tables):
     B, F, nb = obs_d.shape
     assert F == -(-L // hop_length)
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
-    (bw, bv), (sw, sview), (lw, lv) = guarded(B * F * 2 * nb, torch.uint8, 201), guarded(B * F, torch.int32, -777), guarded(B, torch.float64, 777.0)
+    out = A.Guarded({"back": ((B, F, 2 * nb), torch.uint8), "state": ((B, F), torch.int32), "loglik": ((B,), torch.float64)}, fills={"back": 201})
     lt, lz = np.ascontiguousarray(tables["log_tri"]), np.ascontiguousarray(tables["log_Z"])
     rc = eng.lib.ev_pyin_decode(eng.h, obs_d.data_ptr(), pv_d.data_ptr(), None if d_len is None else d_len.data_ptr(), B, L, hop_length, nb,
-                                tables["R"], lt.ctypes.data, lz.ctypes.data, tables["log_stay"], tables["log_switch"], bv.data_ptr(),
-                                sview.data_ptr(), lv.data_ptr(), _stream_ptr())
-    torch.cuda.synchronize()
-    intact(bw, B * F * 2 * nb, "d_back")
-    intact(sw, B * F, "d_state")
-    intact(lw, B, "d_loglik")
-    return rc, sview.reshape(B, F).cpu().numpy().copy(), lv.cpu().numpy().copy()
+                                tables["R"], lt.ctypes.data, lz.ctypes.data, tables["log_stay"], tables["log_switch"], out.ptr("back"),
+                                out.ptr("state"), out.ptr("loglik"), _stream_ptr())
+    got = out.collect(rc)
+    return rc, got["state"], got["loglik"]
 
 
 @pytest.fixture(scope="module")
 def eng():
-    e = Engine(0)                                                        # no weights loaded
-    yield e
-    e.close()
+    yield from A.one_engine()
 
 
 # ---- 1. the observation against the restatement -----------------------------------------------------------------------------------------------
@@ -112,7 +87,7 @@ def eng():
 def test_observe_parity_with_the_restatement(eng, name):
     x, lens, kw, ref = observed(name)
     rc, obs, pv = raw_observe(eng, x, lens, **kw)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     keep = ~ref["fragile"]
     e_o = float(np.max(np.abs(obs - ref["obs"])[keep])) if keep.any() else 0.0
     e_p = float(np.max(np.abs(pv - ref["pv"])[keep])) if keep.any() else 0.0
@@ -156,7 +131,7 @@ def test_decode_parity_with_the_restatement(eng, name):
     nfs = [-(-n // H) for n in lens]
     ref = cached(("decode-ref", name), lambda: [Y.viterbi_fast(obs[b, :nf], pv[b, :nf], tables) for b, nf in enumerate(nfs)])
     rc, state, loglik = raw_decode(eng, obs, pv, lens, L, H, tables)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     differing = total = 0
     for b, nf in enumerate(nfs):
         want, best = ref[b]
@@ -307,17 +282,17 @@ def test_null_outputs_fail(eng):
     for obs_p, pv_p in ((None, out.data_ptr()), (out.data_ptr(), None)):
         rc = eng.lib.ev_pyin_observe(eng.h, x.data_ptr(), None, 1, 2048, 1024, 256, 36, 340, 22050.0, 65.0, 120, 385, w.ctypes.data, 100, 2.0, 0.01,
                                      obs_p, pv_p, _stream_ptr())
-        assert rc != 0 and "output" in eng.lib.ev_last_error(eng.h).decode()
+        assert rc != 0 and "output" in err_of(eng)
     t = Y.transition_tables(385, 25)
     back = torch.zeros(8 * 770, dtype=torch.uint8, device=DEV)
     st = torch.zeros(8, dtype=torch.int32, device=DEV)
     for st_p, ll_p in ((None, out.data_ptr()), (st.data_ptr(), None)):
         rc = eng.lib.ev_pyin_decode(eng.h, out.data_ptr(), out.data_ptr(), None, 1, 2048, 256, 385, 25, t["log_tri"].ctypes.data, t["log_Z"].ctypes.data,
                                     t["log_stay"], t["log_switch"], back.data_ptr(), st_p, ll_p, _stream_ptr())
-        assert rc != 0 and "output" in eng.lib.ev_last_error(eng.h).decode()
+        assert rc != 0 and "output" in err_of(eng)
     rc = eng.lib.ev_pyin_decode(eng.h, out.data_ptr(), out.data_ptr(), None, 1, 2048, 256, 385, 25, t["log_tri"].ctypes.data, t["log_Z"].ctypes.data,
                                 t["log_stay"], t["log_switch"], None, st.data_ptr(), out.data_ptr(), _stream_ptr())
-    assert rc != 0 and "d_back" in eng.lib.ev_last_error(eng.h).decode()
+    assert rc != 0 and "d_back" in err_of(eng)
     torch.cuda.synchronize()
 
 

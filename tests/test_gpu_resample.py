@@ -37,13 +37,14 @@ import pytest
 import torch
 from scipy import signal as sps
 
+import analysis_gpu as A
 import mel_ref as R
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, EvLibraryError, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 TILE = 1024
 F32_MAX, F32_RMS = 1.92e-6, 1.40e-7              # scipy's float32 run: worst case over CASES (module docstring)
 GATE_MAX, GATE_RMS = 3 * F32_MAX, 3 * F32_RMS
@@ -89,17 +90,8 @@ def engine_with(taps, up, down):
 
 @pytest.fixture(scope="module")
 def engines():
-    cache = {}
-
-    def get(up, down, zeros=10, beta=5.0):
-        key = (up, down, zeros, beta)
-        if key not in cache:
-            cache[key] = engine_with(audio.resample_filter(up, down, zeros, beta), up, down)
-        return cache[key]
-
-    yield get
-    for e in cache.values():
-        e.close()
+    for get in A.engines_on_demand(lambda key: engine_with(audio.resample_filter(*key), key[0], key[1])):
+        yield lambda up, down, zeros=10, beta=5.0: get((up, down, zeros, beta))
 
 
 def test_the_cases_cover_the_tile_boundary_and_the_31_bit_limit():
@@ -202,8 +194,8 @@ def test_bad_and_empty_rows_sentinels_and_allocations():
         assert torch.equal(y[r:r + 1], eng.resample(x[r:r + 1].contiguous())), "the neighbours of a bad row are unchanged"
     k = l_out(5, up, down)
     assert torch.equal(y[3, :k], eng.resample(x[3:4, :5].contiguous())[0]) and not y[3, k:].any()
-    assert call(Lo + 1) != 0 and "L_out" in eng.lib.ev_last_error(eng.h).decode()
-    assert call(Lo - 1) != 0 and "L_out" in eng.lib.ev_last_error(eng.h).decode()
+    assert call(Lo + 1) != 0 and "L_out" in err_of(eng)
+    assert call(Lo - 1) != 0 and "L_out" in err_of(eng)
     eng.close()
 
 

@@ -12,7 +12,7 @@ rounding.  The rule of every comparison (``check``):
 1e-9 is the project's float64 margin (tests/test_gpu_stoi.py, tests/test_gpu_loudness.py): four orders above float64 order effects.
 Observed on the MI355X: d_frame 9.2e-15 and d_sums 5.0e-16 at worst over all cases.  Every case prints its worst figure, DESIGN section 3.18
 records them; the gate stays at 1e-9.  Every raw call writes into buffers with
-sentinel margins; 50.0 / -50.0 sit behind every row's length in the two signals.
+sentinel margins (tests/analysis_gpu.py); 50.0 / -50.0 sit behind every row's length in the two signals.
 """
 import json
 
@@ -20,14 +20,14 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import stft_dist_ref as R
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-M = 64                                   # sentinel margin, elements
 SMALL = R.GEOMETRIES[0]                  # (64, 10, 24): NB = 33, a one-column bin tail
 _REF = {}
 IDS = [f"{g[0]}-{g[1]}-{g[2]}" for g in R.GEOMETRIES]
@@ -35,12 +35,7 @@ IDS = [f"{g[0]}-{g[1]}-{g[2]}" for g in R.GEOMETRIES]
 
 def ref_of(key, x, y, lens, geom):
     """The restatements' results (float64, longdouble), computed once per case and never modified."""
-    if key not in _REF:
-        r = R.batch(x, y, lens, geom) + R.batch(x, y, lens, geom, dtype=np.longdouble)[:2]
-        for v in r:
-            v.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
+    return A.frozen(_REF, key, lambda: R.batch(x, y, lens, geom) + R.batch(x, y, lens, geom, dtype=np.longdouble)[:2])
 
 
 def load(eng, geom, null=(), **kw):
@@ -53,11 +48,6 @@ def load(eng, geom, null=(), **kw):
     return eng.lib.ev_load_stft_dist(eng.h, p(w, "window"), p(tw, "twiddle"), a["W"], a["H"], a["nfft"])
 
 
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
-
-
 def raw(eng, geom, x, y, lens, floor=R.POWER_FLOOR, B=None, L=None, null=()):
     """ev_stft_dist into guarded buffers: (rc, frame (B, NF, 4), sums (B, 4), counts (B,)) on the host; an output named in ``null`` is passed
     as NULL and comes back None.  ``B`` / ``L`` override the shape passed to the library."""
@@ -67,24 +57,10 @@ def raw(eng, geom, x, y, lens, floor=R.POWER_FLOOR, B=None, L=None, null=()):
     B, L = Bx if B is None else B, Lx if L is None else L
     NF = R.frames(Lx, geom[0], geom[1])
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
-    names = ("frame", "sums", "counts")
-    shapes = ((Bx, NF, 4), (Bx, 4), (Bx,))
-    fills = ((torch.float64, 777.0), (torch.float64, 777.0), (torch.int32, -777))
-    bufs = [guarded(int(np.prod(s)), dt, f) for s, (dt, f) in zip(shapes, fills)]
-    ptr = lambda i: None if names[i] in null else bufs[i][1].data_ptr()
+    out = A.Guarded({"frame": ((Bx, NF, 4), torch.float64), "sums": ((Bx, 4), torch.float64), "counts": ((Bx,), torch.int32)}, null)
     rc = eng.lib.ev_stft_dist(eng.h, None if "x" in null else x.data_ptr(), None if "y" in null else y.data_ptr(), None if d_len is None else d_len.data_ptr(),
-                              B, L, float(floor), ptr(0), ptr(1), ptr(2), _stream_ptr())
-    torch.cuda.synchronize()
-    out = []
-    for i, ((whole, view), shape) in enumerate(zip(bufs, shapes)):
-        fill, n = whole[0].item(), int(np.prod(shape))
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), f"sentinel margin of d_{names[i]}"
-        if rc != 0 or names[i] in null:
-            assert bool((view == fill).all()), f"d_{names[i]} was not asked for (or the call failed) and was written"
-            out.append(None)
-        else:
-            out.append(view.reshape(shape).cpu().numpy().copy())
-    return (rc, *out)
+                              B, L, float(floor), out.ptr("frame"), out.ptr("sums"), out.ptr("counts"), _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 def check(dev, ref, what):
@@ -103,22 +79,12 @@ def check(dev, ref, what):
 
 
 def engine_with(geom):
-    e = Engine(0)                                                        # no weights loaded
-    assert load(e, geom) == 0, e.lib.ev_last_error(e.h).decode()
-    return e
+    return A.engine_with(load, geom)
 
 
 @pytest.fixture(scope="module")
 def engines():
-    made = {}
-
-    def get(geom):
-        if geom not in made:
-            made[geom] = engine_with(geom)
-        return made[geom]
-    yield get
-    for e in made.values():
-        e.close()
+    yield from A.engines_on_demand(engine_with)
 
 
 @pytest.fixture(scope="module")
@@ -134,7 +100,7 @@ def test_geometry_against_the_restatement(engines, geom):
     assert [c % 16 for c in ref[2].tolist()] == [15, 0, 1]
     eng = engines(geom)
     rc, *dev = raw(eng, geom, x, y, lens)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref, f"{geom} lens {lens}")
     for b in range(3):
         assert not dev[0][b, dev[2][b]:].any(), "zeros past the row's own frames"
@@ -154,7 +120,7 @@ def test_identical_signals_give_exact_zeros(engines, geom):
     x, _, lens = R.rows_for(geom)
     eng = engines(geom)
     rc, frame, sums, counts = raw(eng, geom, x, x, lens)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     assert not frame[:, :, 0].any() and not frame[:, :, 2].any() and not frame[:, :, 3].any(), "y = x: both signals take the same path, bit for bit"
     assert not sums[:, 0].any() and not sums[:, 2].any() and not sums[:, 3].any()
     assert (sums[:, 1] > 0).all() and counts.tolist() == [R.frames(n, geom[0], geom[1]) for n in lens]
@@ -170,7 +136,7 @@ def test_row_alone_in_a_batch_and_as_a_prefix_give_the_same_bits(engines, geom):
     n = lens[0]
     c, d = x[0, :n].copy(), y[0, :n].copy()
     rc, *alone = raw(eng, geom, c[None], d[None], None)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     rc, *again = raw(eng, geom, c[None], d[None], None)
     assert rc == 0 and all(np.array_equal(a, b) for a, b in zip(alone, again)), "two calls"
     xb, yb, lb = R.padded([(x[2, :lens[2]], y[2, :lens[2]]), (c, d), (x[1, :lens[1]], y[1, :lens[1]])])
@@ -209,7 +175,7 @@ def test_reflection_at_both_ends(engines, geom):
     x, y, lens = R.padded(rows)
     ref = ref_of(("edge", geom), x, y, lens, geom)
     rc, *dev = raw(eng, geom, x, y, lens)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref, f"reflection {geom} lens {lens}")
     for b, n in enumerate(lens):
         nf = dev[2][b]
@@ -230,7 +196,7 @@ def test_bad_rows_are_zeros_and_a_call_without_frames_succeeds(small):
     y = np.concatenate([y, y[:1], y[:1], y[:1], y[:1]])
     lens = lens + [0, -3, L + 1, geom[0] // 2]
     rc, frame, sums, counts = raw(small, geom, x, y, lens)
-    assert rc == 0, small.lib.ev_last_error(small.h).decode()
+    assert rc == 0, err_of(small)
     assert counts[3:].tolist() == [0, 0, 0, 0], "len 0, len < 0, len > L, len = nfft / 2: empty rows"
     assert not frame[3:].any() and not sums[3:].any()
     check((frame, sums, counts), ref_of("bad", x, y, lens, geom), "bad rows beside good ones")
@@ -239,7 +205,7 @@ def test_bad_rows_are_zeros_and_a_call_without_frames_succeeds(small):
     check((frame, sums, counts), ref_of("shortest", x[:, :geom[0] // 2 + 1], y[:, :geom[0] // 2 + 1], None, geom), "the shortest rows with frames")
     z = np.zeros((2, geom[0] // 2), np.float32)
     rc, frame, sums, counts = raw(small, geom, z, z, None)               # L <= nfft / 2: NF = 0
-    assert rc == 0, small.lib.ev_last_error(small.h).decode()
+    assert rc == 0, err_of(small)
     assert frame.shape == (2, 0, 4) and not sums.any() and counts.tolist() == [0, 0]
 
 
@@ -250,7 +216,7 @@ def test_without_d_frame_the_sums_are_the_same_bits_and_a_second_call_allocates_
     try:
         x, y, lens = R.rows_for(geom)
         rc, frame, sums, counts = raw(eng, geom, x, y, lens)
-        assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+        assert rc == 0, err_of(eng)
         n0 = eng.alloc_count()
         rc, none, sums2, counts2 = raw(eng, geom, x, y, lens, null=("frame",))
         torch.cuda.synchronize()
@@ -278,7 +244,7 @@ BAD_CALL = [
 def test_each_limit_of_ev_stft_dist_fails_with_a_message_naming_it(small, word, kw):
     z = np.zeros((2, 256), np.float32)
     rc, *_ = raw(small, SMALL, z, z, None, **kw)                          # (a failed call writes nothing: raw checks that)
-    msg = small.lib.ev_last_error(small.h).decode()
+    msg = err_of(small)
     assert rc != 0 and "ev_stft_dist" in msg and word in msg, msg
 
 
@@ -298,7 +264,7 @@ def test_each_limit_of_ev_load_stft_dist_fails_with_a_message_naming_it(small, w
     kw = dict(kw)
     null = kw.pop("null", ())
     rc = load(small, SMALL, null=null, **kw)
-    msg = small.lib.ev_last_error(small.h).decode()
+    msg = err_of(small)
     assert rc != 0 and "ev_load_stft_dist" in msg and word in msg, msg
     x, y, lens = R.rows_for(SMALL)                                        # the basis loaded before is still the one in use
     ref = ref_of(("rows", SMALL), x, y, lens, SMALL)
@@ -311,11 +277,11 @@ def test_ev_stft_dist_before_a_load_fails_and_loading_again_replaces_the_basis()
     try:
         z = np.zeros((1, 256), np.float32)
         rc, *_ = raw(e, SMALL, z, z, None)
-        assert rc != 0 and "ev_load_stft_dist" in e.lib.ev_last_error(e.h).decode()
-        assert load(e, R.GEOMETRIES[1]) == 0 and load(e, SMALL) == 0, e.lib.ev_last_error(e.h).decode()
+        assert rc != 0 and "ev_load_stft_dist" in err_of(e)
+        assert load(e, R.GEOMETRIES[1]) == 0 and load(e, SMALL) == 0, err_of(e)
         x, y, lens = R.rows_for(SMALL)
         rc, *dev = raw(e, SMALL, x, y, lens)
-        assert rc == 0, e.lib.ev_last_error(e.h).decode()
+        assert rc == 0, err_of(e)
         check(dev, ref_of(("rows", SMALL), x, y, lens, SMALL), "after loading twice")
     finally:
         e.close()

@@ -10,7 +10,7 @@ one fixed order of its own (include/emojivoice.h), so it differs from the restat
   * d_seg and d_score within 1e-9 absolute.
 A direct DFT as 256-term fma chains and an FFT differ by float64 rounding, some 1e-13 of a band's value; 1e-9 is four orders above
 that, the margin tests/test_gpu_loudness.py takes for the same reason.  Observed on the MI355X (every case prints its worst figures, DESIGN
-section 3.17 records them; the gate stays at 1e-9): d_tob 6.1e-14 (standard geometry), d_seg 1.7e-14, d_score 1.4e-15.  Every raw call writes into buffers with sentinel margins; 50.0 / -50.0 sit behind every row's length in the two signals.
+section 3.17 records them; the gate stays at 1e-9): d_tob 6.1e-14 (standard geometry), d_seg 1.7e-14, d_score 1.4e-15.  Every raw call writes into buffers with sentinel margins (tests/analysis_gpu.py); 50.0 / -50.0 sit behind every row's length in the two signals.
 """
 import json
 
@@ -18,25 +18,20 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import stoi_ref as R
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-M = 64                                   # sentinel margin, elements
 _REF = {}
 
 
 def ref_of(key, x, y, lens, g):
     """The restatement's result, computed once per case and never modified."""
-    if key not in _REF:
-        r = R.stoi(x, y, lens, g)
-        for v in r.values():
-            v.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
+    return A.frozen(_REF, key, lambda: R.stoi(x, y, lens, g))
 
 
 def load(eng, g, null=(), **kw):
@@ -49,11 +44,6 @@ def load(eng, g, null=(), **kw):
     return eng.lib.ev_load_stoi(eng.h, p(w, "window"), p(tw, "twiddle"), p(bd, "bands"), a["W"], a["H"], a["nfft"], a["n_bands"], a["N"])
 
 
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
-
-
 def raw(eng, g, x, y, lens, ratio=R.SILENCE_RATIO, clip=R.CLIP, B=None, L=None, null=()):
     """ev_stoi into guarded buffers: (rc, keep (B, NF), tob (B, 2, n_bands, NM), seg (B, NSEG, 2), score (B, 2), counts (B, 3)) on the host;
     an output named in ``null`` is passed as NULL and comes back None.  ``B`` / ``L`` override the shape passed to the library."""
@@ -64,24 +54,12 @@ def raw(eng, g, x, y, lens, ratio=R.SILENCE_RATIO, clip=R.CLIP, B=None, L=None, 
     NF, NM, NSEG = g.sizes(Lx)
     nb = len(g.bands)
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
-    names = ("keep", "tob", "seg", "score", "counts")
-    shapes = ((Bx, NF), (Bx, 2, nb, NM), (Bx, NSEG, 2), (Bx, 2), (Bx, 3))
-    fills = ((torch.uint8, 77), (torch.float64, 777.0), (torch.float64, 777.0), (torch.float64, 777.0), (torch.int32, -777))
-    bufs = [guarded(int(np.prod(s)), dt, f) for s, (dt, f) in zip(shapes, fills)]
-    ptr = lambda i: None if names[i] in null else bufs[i][1].data_ptr()
+    out = A.Guarded({"keep": ((Bx, NF), torch.uint8), "tob": ((Bx, 2, nb, NM), torch.float64), "seg": ((Bx, NSEG, 2), torch.float64),
+                     "score": ((Bx, 2), torch.float64), "counts": ((Bx, 3), torch.int32)}, null)
     rc = eng.lib.ev_stoi(eng.h, None if "x" in null else x.data_ptr(), None if "y" in null else y.data_ptr(), None if d_len is None else d_len.data_ptr(),
-                         B, L, float(ratio), float(clip), ptr(0), ptr(1), ptr(2), ptr(3), ptr(4), _stream_ptr())
-    torch.cuda.synchronize()
-    out = []
-    for i, ((whole, view), shape) in enumerate(zip(bufs, shapes)):
-        fill, n = whole[0].item(), int(np.prod(shape))
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), f"sentinel margin of d_{names[i]}"
-        if rc != 0 or names[i] in null:
-            assert bool((view == fill).all()), f"d_{names[i]} was not asked for (or the call failed) and was written"
-            out.append(None)
-        else:
-            out.append(view.reshape(shape).cpu().numpy().copy())
-    return (rc, *out)
+                         B, L, float(ratio), float(clip), out.ptr("keep"), out.ptr("tob"), out.ptr("seg"), out.ptr("score"), out.ptr("counts"),
+                         _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 def tob_err(dev, ref):
@@ -119,23 +97,17 @@ def check(dev, ref, what):
 
 
 def engine_with(g):
-    e = Engine(0)                                                        # no weights loaded
-    assert load(e, g) == 0, e.lib.ev_last_error(e.h).decode()
-    return e
+    return A.engine_with(load, g)
 
 
 @pytest.fixture(scope="module")
 def std():
-    e = engine_with(R.STANDARD)
-    yield e
-    e.close()
+    yield from A.one_engine(load, R.STANDARD)
 
 
 @pytest.fixture(scope="module")
 def small():
-    e = engine_with(R.SMALL)
-    yield e
-    e.close()
+    yield from A.one_engine(load, R.SMALL)
 
 
 # ---- 1. the standard geometry -------------------------------------------------------------------------------------------------------------
@@ -144,7 +116,7 @@ def test_standard_geometry_three_snrs(std):
     ref = ref_of("standard", x, y, lens, R.STANDARD)
     assert ref["counts"][:, 0].tolist() == [155, 103, 69] and (ref["counts"][:, 2] > 0).all()
     rc, *dev = raw(std, R.STANDARD, x, y, lens)
-    assert rc == 0, std.lib.ev_last_error(std.h).decode()
+    assert rc == 0, err_of(std)
     check(dev, ref, f"standard 256/128/512 lens {lens} SNR {R.SNRS_DB}")
     for b in range(3):
         nf, nk, nseg = dev[4][b]
@@ -157,7 +129,7 @@ def test_small_geometry_edges_in_one_ragged_batch(small):
     ref = ref_of("small", x, y, lens, R.SMALL)
     assert ref["counts"].tolist() == R.SMALL_COUNTS
     rc, *dev = raw(small, R.SMALL, x, y, lens)
-    assert rc == 0, small.lib.ev_last_error(small.h).decode()
+    assert rc == 0, err_of(small)
     check(dev, ref, f"small 64/32/128 lens {lens}")
     score = dev[3]
     assert not score[1:6].any() and not score[8].any(), "no segment: score 0"
@@ -176,7 +148,7 @@ def test_scan_shapes(small, shape):
     assert {"first_dropped": not k[0] and k[1:].all(), "last_dropped": not k[-1] and k[0], "run_over_64": 64 < run <= 256, "run_over_256": run > 256,
             "all_kept": k.all()}[shape], f"{shape}: the mask (longest dropped run {run}) is not the shape the case is about"
     rc, *dev = raw(small, R.SMALL, x, y, lens)
-    assert rc == 0, small.lib.ev_last_error(small.h).decode()
+    assert rc == 0, err_of(small)
     check(dev, ref, f"scan {shape} (longest dropped run {run})")
 
 
@@ -187,7 +159,7 @@ def test_row_alone_in_a_batch_and_as_a_prefix_give_the_same_bits(small):
     d = R.processed(c, 5.0, seed=0)
     n = len(c)
     rc, *alone = raw(small, g, c[None], d[None], None)
-    assert rc == 0, small.lib.ev_last_error(small.h).decode()
+    assert rc == 0, err_of(small)
     rc, *again = raw(small, g, c[None], d[None], None)
     assert rc == 0 and all(np.array_equal(a, b) for a, b in zip(alone, again)), "two calls"
     o1, o2 = R.dense_row(90, seed=5), R.dense_row(17, seed=6)
@@ -221,7 +193,7 @@ def test_row_alone_in_a_batch_and_as_a_prefix_give_the_same_bits(small):
 def test_identical_signals_score_one(std, small):
     x, _, lens = R.standard_rows()
     rc, _, _, seg, score, counts = raw(std, R.STANDARD, x, x, lens)
-    assert rc == 0, std.lib.ev_last_error(std.h).decode()
+    assert rc == 0, err_of(std)
     print(f"\nSTOI identical signals, standard geometry: 1 - score {(1.0 - score).tolist()}  counts {counts.tolist()}")
     assert (counts[:, 2] > 0).all() and (score[:, 0] >= 1.0 - 1e-12).all() and (score[:, 1] >= 1.0 - 1e-12).all()
     c = R.small_clean(3000)
@@ -238,7 +210,7 @@ def test_bad_rows_are_zeros_and_optional_outputs_may_be_null(small):
     y = np.stack([d, d, d, d, d])
     lens = [0, -4, 3001, 3000, 3000]
     rc, keep, tob, seg, score, counts = raw(small, g, x, y, lens)
-    assert rc == 0, small.lib.ev_last_error(small.h).decode()
+    assert rc == 0, err_of(small)
     assert counts[:3].tolist() == [[0, 0, 0]] * 3 and counts[3].tolist() == [92, 0, 0], "len < 1, len > L: empty rows; all-zero clean row: no frame kept"
     for b in range(4):
         assert not keep[b].any() and not tob[b].any() and not seg[b].any() and not score[b].any(), f"row {b} must be zeros"
@@ -247,7 +219,7 @@ def test_bad_rows_are_zeros_and_optional_outputs_may_be_null(small):
     n0 = small.alloc_count()
     for null in (("keep",), ("tob",), ("seg",), ("keep", "tob", "seg")):
         rc, *got = raw(small, g, x, y, lens, null=null)
-        assert rc == 0, small.lib.ev_last_error(small.h).decode()
+        assert rc == 0, err_of(small)
         assert np.array_equal(got[3], score) and np.array_equal(got[4], counts), f"without {null}"
         if "seg" not in null:
             assert np.array_equal(got[2], seg)
@@ -270,7 +242,7 @@ BAD_STOI = [
 def test_each_limit_of_ev_stoi_fails_with_a_message_naming_it(small, word, kw):
     z = np.zeros((2, 1024), np.float32)
     rc, *_ = raw(small, R.SMALL, z, z, None, **kw)                       # (a failed call writes nothing: raw checks that)
-    msg = small.lib.ev_last_error(small.h).decode()
+    msg = err_of(small)
     assert rc != 0 and "ev_stoi" in msg and word in msg, msg
 
 
@@ -296,7 +268,7 @@ def test_each_limit_of_ev_load_stoi_fails_with_a_message_naming_it(small, word, 
     if kw.get("n_bands") == 33:
         kw["bands"] = [[2, 4]] * 33
     rc = load(small, R.SMALL, **kw)
-    msg = small.lib.ev_last_error(small.h).decode()
+    msg = err_of(small)
     assert rc != 0 and "ev_load_stoi" in msg and word in msg, msg
     c = R.small_clean(1500, seed=1)                                      # the tables loaded before are still the ones in use
     ref = ref_of("after-bad-load", c[None], R.processed(c, 5.0)[None], None, R.SMALL)
@@ -309,12 +281,12 @@ def test_ev_stoi_before_ev_load_stoi_fails_and_loading_again_replaces_the_tables
     try:
         z = np.zeros((1, 1024), np.float32)
         rc, *_ = raw(e, R.SMALL, z, z, None)
-        assert rc != 0 and "ev_load_stoi" in e.lib.ev_last_error(e.h).decode()
-        assert load(e, R.STANDARD) == 0 and load(e, R.SMALL) == 0, e.lib.ev_last_error(e.h).decode()
+        assert rc != 0 and "ev_load_stoi" in err_of(e)
+        assert load(e, R.STANDARD) == 0 and load(e, R.SMALL) == 0, err_of(e)
         c = R.small_clean(1500, seed=1)
         d = R.processed(c, 5.0)
         rc, *dev = raw(e, R.SMALL, c[None], d[None], None)
-        assert rc == 0, e.lib.ev_last_error(e.h).decode()
+        assert rc == 0, err_of(e)
         check(dev, ref_of("after-bad-load", c[None], d[None], None, R.SMALL), "after loading twice")
     finally:
         e.close()

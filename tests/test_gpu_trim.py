@@ -12,7 +12,7 @@ paths run.  Two mutants of the EXPECTATION (the uncentred frame [f H, f H + F); 
 device on at least one of these cases.
 
 The peak is compared bit for bit with ``x.abs().max()``, the output of ev_trim_apply bit for bit with ``x[start:end] * (target / peak)``
-computed by torch in fp32 (one division, one multiply per sample).  Every raw call writes into buffers with sentinel margins.
+computed by torch in fp32 (one division, one multiply per sample).  Every raw call writes into buffers with sentinel margins (tests/analysis_gpu.py).
 
 Times: not gated here (tools/trim_bench.py).  This module has not run on an MI355X yet: the margins and the restatement's bounds above are
 CPU figures (tests/test_trim_host.py asserts them without a GPU); the TRIM lines of a -s run carry the device's.
@@ -24,18 +24,18 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import trim_ref as T
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, EvLibraryError, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 LENGTHS = [1, 63, 1023, 1024, 1025, 5000, 5120, 3 * 2048 + 511]
 CONFIGS = [(2048, 512), (1024, 256), (512, 512)]
 L_PAD = max(LENGTHS) + 4                 # 6659: odd, so the rows of a batch start at every alignment
 GARBAGE = 50.0                           # what lies behind a row's d_len samples: loud, so that reading it would show
-M = 64                                   # sentinel margin, elements
 _ROWS, _REF = {}, {}
 
 
@@ -62,47 +62,33 @@ def padded_batch(lengths=LENGTHS, L=L_PAD):
     return x.to(DEV)
 
 
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
-
-
-def intact(buf, n, fill):
-    return bool((buf[:M] == fill).all()) and bool((buf[M + n:] == fill).all())
+def on_device(out):
+    """The collected host copies back on the device, where the tests compare them with torch (None stays None)."""
+    return tuple(None if a is None else torch.from_numpy(a).to(DEV) for a in out.values())
 
 
 def raw_bounds(eng, x, lens, F=2048, H=512, top_db=60.0, want_peak=True):
     """ev_trim_bounds into guarded buffers: (rc, bounds (B, 2) int32, peak (B,) or None)."""
     B, L = x.shape
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
-    bb, bounds = guarded(2 * B, torch.int32, -777)
-    pb, peak = guarded(B, torch.float32, 777.0)
-    rc = eng.lib.ev_trim_bounds(eng.h, x.data_ptr(), None if d_len is None else d_len.data_ptr(), B, L, F, H, top_db, bounds.data_ptr(),
-                                peak.data_ptr() if want_peak else None, _stream_ptr())
-    torch.cuda.synchronize()
-    assert intact(bb, 2 * B, -777) and intact(pb, B, 777.0), "sentinel margin of ev_trim_bounds"
-    if not want_peak:
-        assert bool((peak == 777.0).all())
-    return rc, bounds.reshape(B, 2).clone(), (peak.clone() if want_peak else None)
+    out = A.Guarded({"bounds": ((B, 2), torch.int32), "peak": ((B,), torch.float32)}, () if want_peak else ("peak",))
+    rc = eng.lib.ev_trim_bounds(eng.h, x.data_ptr(), None if d_len is None else d_len.data_ptr(), B, L, F, H, top_db, out.ptr("bounds"),
+                                out.ptr("peak"), _stream_ptr())
+    return (rc, *on_device(out.collect(rc)))
 
 
 def raw_apply(eng, x, bounds, peak, target, L_out):
     """ev_trim_apply into guarded buffers: (rc, y (B, L_out), out_len (B,))."""
     B, L = x.shape
-    yb, y = guarded(B * L_out, torch.float32, 777.0)
-    nb, n = guarded(B, torch.int32, -777)
-    rc = eng.lib.ev_trim_apply(eng.h, x.data_ptr(), bounds.data_ptr(), None if peak is None else peak.data_ptr(), target, B, L, y.data_ptr(), L_out,
-                               n.data_ptr(), _stream_ptr())
-    torch.cuda.synchronize()
-    assert intact(yb, B * L_out, 777.0) and intact(nb, B, -777), "sentinel margin of ev_trim_apply"
-    return rc, y.reshape(B, L_out).clone(), n.clone()
+    out = A.Guarded({"y": ((B, L_out), torch.float32), "out_len": ((B,), torch.int32)})
+    rc = eng.lib.ev_trim_apply(eng.h, x.data_ptr(), bounds.data_ptr(), None if peak is None else peak.data_ptr(), target, B, L, out.ptr("y"), L_out,
+                               out.ptr("out_len"), _stream_ptr())
+    return (rc, *on_device(out.collect(rc)))
 
 
 @pytest.fixture(scope="module")
 def eng():
-    e = Engine(0)
-    yield e
-    e.close()
+    yield from A.one_engine()
 
 
 @pytest.mark.parametrize("F,H", CONFIGS, ids=[f"F{F}-H{H}" for F, H in CONFIGS])
@@ -110,7 +96,7 @@ def test_bounds_and_peak_equal_the_restatement_exactly(eng, F, H):
     want = [list(ref_bounds(n, F, H)) for n in LENGTHS]
     x = padded_batch()
     rc, bounds, peak = raw_bounds(eng, x, LENGTHS, F, H)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     print(f"\nTRIM F{F} H{H}: device {bounds.tolist()}  restatement {want}")
     assert bounds.tolist() == want
     for b, n in enumerate(LENGTHS):
@@ -166,7 +152,7 @@ def test_apply_is_the_torch_product_bit_for_bit(eng, L_out):
     assert rc == 0
     gain = (torch.tensor(0.95, dtype=torch.float32) / peak.cpu()).to(DEV)    # one fp32 division per row, IEEE (on the host)
     rc, y, out_len = raw_apply(eng, x, bounds, peak, 0.95, L_out)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     rc, c, c_len = raw_apply(eng, x, bounds, peak, 0.0, L_out)           # target <= 0: a copy
     rc2, c2, _ = raw_apply(eng, x, bounds, None, 0.95, L_out)            # no peak: a copy as well
     assert rc == 0 and rc2 == 0 and torch.equal(c, c2) and torch.equal(c_len, out_len)

@@ -12,7 +12,7 @@ of every comparison (``check``):
     tests/test_gpu_loudness.py, tests/test_gpu_stft_dist.py), four orders above float64 order effects.
 Observed on the MI355X: d_frame 5.1e-13 (slope_0_500 at 1024 / 256 / 1024) and d_cepstrum 8.8e-14 at worst over all cases, every q* equal.
 Every case prints its worst figure, DESIGN section 3.19 records them; the gate stays at 1e-9.  Every raw call writes into buffers with sentinel
-margins; 50.0 sits behind every row's length.
+margins (tests/analysis_gpu.py); 50.0 sits behind every row's length.
 """
 import json
 
@@ -20,14 +20,14 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_gpu as A
 import voice_quality_ref as R
+from analysis_gpu import DEV, err_of
 from emojivoice_amd import audio
 from emojivoice_amd._lib import Engine, _stream_ptr
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-M = 64                                   # sentinel margin, elements
 SMALL = R.GEOMETRIES[0]                  # 64 / 10 / 24: NB = 33, NQ = 29
 BIG = R.GEOMETRIES[3]
 _REF = {}
@@ -36,12 +36,7 @@ _REF = {}
 def ref_of(key, x, lens, g):
     """The restatements' results (float64: frame, peak, cepstrum, margin; longdouble: frame, peak, cepstrum), computed once per case and never
     modified."""
-    if key not in _REF:
-        r = R.batch(x, lens, g) + R.batch(x, lens, g, dtype=np.longdouble)[:3]
-        for v in r:
-            v.setflags(write=False)
-        _REF[key] = r
-    return _REF[key]
+    return A.frozen(_REF, key, lambda: R.batch(x, lens, g) + R.batch(x, lens, g, dtype=np.longdouble)[:3])
 
 
 def load(eng, g, null=(), **kw):
@@ -58,11 +53,6 @@ def load(eng, g, null=(), **kw):
                                          a["q_max"], p("fit_w"), float(a["q_mean"]))
 
 
-def guarded(n, dtype, fill):
-    buf = torch.full((n + 2 * M,), fill, dtype=dtype, device=DEV)
-    return buf, buf[M: M + n]
-
-
 def raw(eng, g, x, lens, floor=R.POWER_FLOOR, B=None, L=None, null=()):
     """ev_voice_quality into guarded buffers: (rc, frame (B, NF, 8), peak (B, NF), cepstrum (B, NF, NQ)) on the host; an output named in
     ``null`` is passed as NULL and comes back None.  ``B`` / ``L`` override the shape passed to the library."""
@@ -71,24 +61,10 @@ def raw(eng, g, x, lens, floor=R.POWER_FLOOR, B=None, L=None, null=()):
     B, L = Bx if B is None else B, Lx if L is None else L
     NF, NQ = R.frames(Lx, g.H), g.q_max - g.q_fit + 1
     d_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
-    names = ("frame", "peak", "cepstrum")
-    shapes = ((Bx, NF, 8), (Bx, NF), (Bx, NF, NQ))
-    fills = ((torch.float64, 777.0), (torch.int32, -777), (torch.float64, 777.0))
-    bufs = [guarded(int(np.prod(s)), dt, f) for s, (dt, f) in zip(shapes, fills)]
-    ptr = lambda i: None if names[i] in null else bufs[i][1].data_ptr()
+    out = A.Guarded({"frame": ((Bx, NF, 8), torch.float64), "peak": ((Bx, NF), torch.int32), "cepstrum": ((Bx, NF, NQ), torch.float64)}, null)
     rc = eng.lib.ev_voice_quality(eng.h, None if "x" in null else x.data_ptr(), None if d_len is None else d_len.data_ptr(), B, L, float(floor),
-                                  ptr(0), ptr(1), ptr(2), _stream_ptr())
-    torch.cuda.synchronize()
-    out = []
-    for i, ((whole, view), shape) in enumerate(zip(bufs, shapes)):
-        fill, n = whole[0].item(), int(np.prod(shape))
-        assert bool((whole[:M] == fill).all()) and bool((whole[M + n:] == fill).all()), f"sentinel margin of d_{names[i]}"
-        if rc != 0 or names[i] in null:
-            assert bool((view == fill).all()), f"d_{names[i]} was not asked for (or the call failed) and was written"
-            out.append(None)
-        else:
-            out.append(view.reshape(shape).cpu().numpy().copy())
-    return (rc, *out)
+                                  out.ptr("frame"), out.ptr("peak"), out.ptr("cepstrum"), _stream_ptr())
+    return (rc, *out.collect(rc).values())
 
 
 def check(dev, ref, what):
@@ -111,22 +87,12 @@ def check(dev, ref, what):
 
 
 def engine_with(g):
-    e = Engine(0)                                                        # no weights loaded
-    assert load(e, g) == 0, e.lib.ev_last_error(e.h).decode()
-    return e
+    return A.engine_with(load, g)
 
 
 @pytest.fixture(scope="module")
 def engines():
-    made = {}
-
-    def get(g):
-        if g not in made:
-            made[g] = engine_with(g)
-        return made[g]
-    yield get
-    for e in made.values():
-        e.close()
+    yield from A.engines_on_demand(engine_with)
 
 
 @pytest.fixture(scope="module")
@@ -143,7 +109,7 @@ def test_geometry_against_the_restatement(engines, g):
     assert [n % 16 for n in nfs] == [15, 0, 1]
     eng = engines(g)
     rc, *dev = raw(eng, g, x, lens)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref, f"{g[:6]} lens {lens}")
     for b in range(3):
         assert not dev[0][b, nfs[b]:].any() and not dev[1][b, nfs[b]:].any() and not dev[2][b, nfs[b]:].any(), "zeros past the row's own frames"
@@ -167,7 +133,7 @@ def test_row_alone_in_a_batch_as_a_prefix_and_without_cepstrum_give_the_same_bit
     n = lens[0]
     c = x[0, :n].copy()
     rc, *alone = raw(eng, g, c[None], None)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     rc, *again = raw(eng, g, c[None], None)
     assert rc == 0 and all(np.array_equal(a, b) for a, b in zip(alone, again)), "two calls"
     rc, f2, p2, none = raw(eng, g, c[None], None, null=("cepstrum",))
@@ -205,7 +171,7 @@ def test_silent_frames_and_bad_rows(small):
     x = np.concatenate([x, np.zeros((1, L), np.float32), hole[None], x[:1], x[:1], x[:1]])
     lens = lens + [2000, lens[0], 0, -3, L + 1]
     rc, frame, peak, cep = raw(small, g, x, lens)
-    assert rc == 0, small.lib.ev_last_error(small.h).decode()
+    assert rc == 0, err_of(small)
     ref = ref_of("degenerate", x, lens, g)
     check((frame, peak, cep), ref, "a zero row, a row with a silent middle and bad rows beside good ones")
     nfz = R.frames(2000, g.H)
@@ -224,7 +190,7 @@ def test_a_row_of_one_sample_has_one_frame(small):
     x, lens = R.rows_for(g)
     for xs, ls in ((x[:2], [1, lens[1]]), (x[:2, :1], None)):            # a row of 1 sample beside a good row; L = 1: NF = 1
         rc, frame, peak, cep = raw(small, g, xs, ls)
-        assert rc == 0, small.lib.ev_last_error(small.h).decode()
+        assert rc == 0, err_of(small)
         want = R.batch(xs, ls, g)[0]
         assert g.q_min <= peak[0, 0] <= g.q_max and not peak[0, 1:].any() and not frame[0, 1:].any() and not cep[0, 1:].any()
         assert R.err(frame[0, 0, 1:6], want[0, 0, 1:6]) <= R.TOL and frame[0, 0, 5] > (g.nfft // 2 + 1) * R.POWER_FLOOR
@@ -242,7 +208,7 @@ def test_zeros_outside_the_row_at_both_ends(engines, g):
     x, _, lens = R.padded([(s, s) for s in sig])
     ref = ref_of(("edge", g), x, lens, g)
     rc, *dev = raw(eng, g, x, lens)
-    assert rc == 0, eng.lib.ev_last_error(eng.h).decode()
+    assert rc == 0, err_of(eng)
     check(dev, ref, f"edges {g[:6]} lens {lens}")
     for b, n in enumerate(lens):
         nf = R.frames(n, g.H)
@@ -265,7 +231,7 @@ BAD_CALL = [
 def test_each_limit_of_ev_voice_quality_fails_with_a_message_naming_it(small, word, kw):
     z = np.zeros((2, 256), np.float32)
     rc, *_ = raw(small, SMALL, z, None, **kw)                             # (a failed call writes nothing: raw checks that)
-    msg = small.lib.ev_last_error(small.h).decode()
+    msg = err_of(small)
     assert rc != 0 and "ev_voice_quality" in msg and word in msg, msg
 
 
@@ -300,7 +266,7 @@ def test_each_limit_of_ev_load_voice_quality_fails_with_a_message_naming_it(smal
         kw["fit_w"] = np.zeros(max(kw.get("q_max", SMALL.q_max) - kw["q_fit"] + 1, 1))
     n0 = small.alloc_count()
     rc = load(small, SMALL, null=null, **kw)
-    msg = small.lib.ev_last_error(small.h).decode()
+    msg = err_of(small)
     assert rc != 0 and "ev_load_voice_quality" in msg and word in msg, msg
     assert small.alloc_count() == n0
     x, lens = R.rows_for(SMALL)                                           # the tables loaded before are still the ones in use
@@ -315,14 +281,14 @@ def test_a_call_before_a_load_fails_loading_again_replaces_the_tables_and_calls_
     try:
         z = np.zeros((1, 256), np.float32)
         rc, *_ = raw(e, SMALL, z, None)
-        assert rc != 0 and "ev_load_voice_quality" in e.lib.ev_last_error(e.h).decode()
+        assert rc != 0 and "ev_load_voice_quality" in err_of(e)
         n0 = e.alloc_count()
-        assert load(e, R.GEOMETRIES[2]) == 0, e.lib.ev_last_error(e.h).decode()
+        assert load(e, R.GEOMETRIES[2]) == 0, err_of(e)
         assert e.alloc_count() == n0 + 1, "the tables are one device block that counts in ev_alloc_count"
         assert load(e, SMALL) == 0 and e.alloc_count() == n0 + 2
         x, lens = R.rows_for(SMALL)
         rc, *dev = raw(e, SMALL, x, lens)
-        assert rc == 0, e.lib.ev_last_error(e.h).decode()
+        assert rc == 0, err_of(e)
         check(dev, ref_of(("rows", SMALL), x, lens, SMALL), "after loading twice")
         n1 = e.alloc_count()
         assert n1 == n0 + 2, "a call allocates nothing"

@@ -13,9 +13,7 @@ so what the machine does meanwhile lands on all of them alike; per variant the m
 and the spread (max - min) / median.  No time is a gate and no counter is read.  The rows are harmonic tones of 100 .. 250 Hz on a noise floor.
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -27,36 +25,13 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 
 import auditory_ref as R  # noqa: E402
 import harmonics_ref as HR  # noqa: E402
+from bench_timing import rounds_of, stats, write_json  # noqa: E402
 from emojivoice_amd import audio  # noqa: E402
 from emojivoice_amd._lib import Engine, _stream_ptr  # noqa: E402
 
 SR, SECONDS = 22050, 6
 NFFT, HOP, WIN, NMEL, NCEPS, NHARM = 1024, 256, 1024, 26, 4, 48
 FLOOR = 1e-7
-
-
-def rounds_of(variants, rounds, inner, warmup=3):
-    """{name: per-call ms of every round}: every variant warmed up, then ``rounds`` rounds in which the variants take turns."""
-    for fn in variants.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(inner):
-                fn()
-            b.record()
-            b.synchronize()
-            ms[k].append(a.elapsed_time(b) / inner)
-    return ms
-
-
-def stats(v, inner):
-    med = statistics.median(v)
-    return {"median_ms": med, "min_ms": min(v), "max_ms": max(v), "spread": (max(v) - min(v)) / med, "rounds": len(v), "calls_per_round": inner}
 
 
 def torch_restatement(x, c, s, mel, eq, dct, compress, NF):
@@ -154,11 +129,7 @@ def main():
         del x, dst
     for e in (au, hm, vq):
         e.close()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    write_json(args.out, res)
 
 
 if __name__ == "__main__":

@@ -12,11 +12,9 @@ event times.  No ratio is promised; none of the figures is a gate.
 Measured: not measured (no GPU run of this tool has been recorded yet).
 """
 import argparse
-import json
+import functools
 import os
-import statistics
 import sys
-import time
 
 import torch
 
@@ -24,31 +22,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
+import bench_timing  # noqa: E402
 import mas_ref as R  # noqa: E402
 from emojivoice_amd.matcha_tts import synthetic  # noqa: E402
 
 SHAPES = [(16, 120, 516), (64, 120, 516)]
-
-
-def timed(fn, calls, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    torch.cuda.synchronize()                     # cross-check: host clock around `calls` back-to-back calls that end in a synchronise
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    host = (time.perf_counter() - t0) * 1e3 / calls
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls, "host_clock_back_to_back_ms": host}
+timed = functools.partial(bench_timing.timed, warmup=3, host_clock=True)
 
 
 def main():
@@ -76,11 +55,7 @@ def main():
         print(f"(B, Tx, Ty) = {(B, Tx, Ty)}: (a) batched {a['median_ms']:.2f} ms  (b) row by row {b['median_ms']:.2f} ms  [min {a['min_ms']:.2f} / {b['min_ms']:.2f}]"
               f"  (host clock, back to back: {a['host_clock_back_to_back_ms']:.2f} / {b['host_clock_back_to_back_ms']:.2f} ms)\n"
               f"    losses differ by a relative {rel[0]:.1e} / {rel[1]:.1e} / {rel[2]:.1e} (dur / prior / diff); same alignment: {torch.equal(ra[3], rb[3])}")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

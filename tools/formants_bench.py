@@ -13,7 +13,7 @@ root finder `order` Horner steps and `order` complex reciprocals per root.  "rou
 30 p^2 per iteration at an assumed 12 iterations (the restatement's mean is recorded beside it); no figure is a gate.
 """
 import argparse
-import json
+import functools
 import os
 import statistics
 import sys
@@ -26,6 +26,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
+import bench_timing  # noqa: E402
 import formants_ref as R  # noqa: E402
 from emojivoice_amd import audio  # noqa: E402
 from emojivoice_amd._lib import Engine, _stream_ptr  # noqa: E402
@@ -34,21 +35,7 @@ SR, SECONDS, CPU_THREADS = 11025, 6, 16
 W, H, ORDER, NFORM, F_LO = 512, 128, 13, 4, 50.0
 VQ_NFFT = 1024
 FLOOR = audio.FORMANT_POWER_FLOOR
-
-
-def timed(fn, calls, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls}
+timed = functools.partial(bench_timing.timed, warmup=3, host_clock=False)
 
 
 def main():
@@ -116,11 +103,7 @@ def main():
         del x, dst
     fe.close()
     vq.close()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

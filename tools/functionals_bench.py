@@ -15,7 +15,7 @@ Nothing here is a gate: the figures are what was seen.  Every shape is also comp
 (tests/functionals_ref.py): counts equal, worst error.
 """
 import argparse
-import json
+import functools
 import os
 import statistics
 import sys
@@ -28,6 +28,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
+import bench_timing  # noqa: E402
 import functionals_ref as R  # noqa: E402
 from emojivoice_amd import audio  # noqa: E402
 from emojivoice_amd._lib import Engine, _stream_ptr  # noqa: E402
@@ -49,19 +50,7 @@ def wall(fn, calls, warmup=3):
     return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls}
 
 
-def events(fn, calls, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls}
+events = functools.partial(bench_timing.timed, warmup=3, host_clock=False)
 
 
 def _masked_mean_sd(x, m):
@@ -177,11 +166,7 @@ def main():
               + (f"  against the restatement: counts equal {shape['counts_equal_to_the_restatement']}, "
                  f"{shape['worst_error_against_the_restatement']:.2e}" if B * K <= 20 else ""))
     eng.close()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

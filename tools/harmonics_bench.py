@@ -15,9 +15,7 @@ and the spread (max - min) / median.  No time is a gate.  The rows are harmonic 
 noise floor, at their true periods, so the combs are as long as a voice's.
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 import time
 
@@ -29,36 +27,13 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
 import harmonics_ref as R  # noqa: E402
+from bench_timing import rounds_of, stats, write_json  # noqa: E402
 from emojivoice_amd import audio  # noqa: E402
 from emojivoice_amd._lib import Engine, _stream_ptr  # noqa: E402
 
 SR, SECONDS, CPU_THREADS = 22050, 6, 16
 NFFT, HOP, WIN, NHARM = 1024, 256, 1024, 48
 FLOOR = 1e-7
-
-
-def rounds_of(variants, rounds, inner, warmup=3):
-    """{name: per-call ms of every round}: every variant warmed up, then ``rounds`` rounds in which the variants take turns."""
-    for fn in variants.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(inner):
-                fn()
-            b.record()
-            b.synchronize()
-            ms[k].append(a.elapsed_time(b) / inner)
-    return ms
-
-
-def stats(v, inner):
-    med = statistics.median(v)
-    return {"median_ms": med, "min_ms": min(v), "max_ms": max(v), "spread": (max(v) - min(v)) / med, "rounds": len(v), "calls_per_round": inner}
 
 
 def main():
@@ -146,11 +121,7 @@ def main():
         del x, y, dst
     for e in (hm, vq, sd):
         e.close()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    write_json(args.out, res)
 
 
 if __name__ == "__main__":

@@ -12,11 +12,9 @@ holds 100 x the samples of one row of 6 s, and a kernel that walked a row as one
 The input is Gaussian noise at -20 dBFS (the cost does not depend on the data).  None of the figures is a gate.
 """
 import argparse
-import json
+import functools
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -24,31 +22,12 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
+import bench_timing  # noqa: E402
 from emojivoice_amd import audio  # noqa: E402
 from emojivoice_amd._lib import Engine, _stream_ptr  # noqa: E402
 
 SR, S, CHUNK = 22050, 2205, 1024
-
-
-def timed(fn, calls, warmup=5):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    torch.cuda.synchronize()                     # cross-check: host clock around `calls` back-to-back calls that end in a synchronise
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    host = (time.perf_counter() - t0) * 1e3 / calls
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls, "host_clock_back_to_back_ms": host}
+timed = functools.partial(bench_timing.timed, warmup=5, host_clock=True)
 
 
 def main():
@@ -93,11 +72,7 @@ def main():
     res["one_row_600s_over_one_row_6s"] = t600 / t6
     print(f"1 x 600 s takes {t600 / t6:.1f} x the time of 1 x 6 s for 100 x the samples (a row walked as one chain would take 100 x)")
     eng.close()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

@@ -11,11 +11,9 @@ the fused route avoids are printed: the fp32 score matrix written and read again
 round trip of that matrix and of the int32 path the reference makes.  None of the figures is a gate.
 """
 import argparse
-import json
+import functools
 import os
-import statistics
 import sys
-import time
 
 import torch
 
@@ -23,31 +21,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
+import bench_timing  # noqa: E402
 import mas_ref as R  # noqa: E402
 from emojivoice_amd._lib import Engine  # noqa: E402
 
 SHAPES = [(64, 120, 516), (64, 300, 1032), (1, 200, 860)]
-
-
-def timed(fn, calls, warmup=5):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    torch.cuda.synchronize()                     # cross-check: host clock around `calls` back-to-back calls that end in a synchronise
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    host = (time.perf_counter() - t0) * 1e3 / calls
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls, "host_clock_back_to_back_ms": host}
+timed = functools.partial(bench_timing.timed, warmup=5, host_clock=True)
 
 
 def main():
@@ -73,11 +52,7 @@ def main():
               f"  [min {a['min_ms']:.3f} / {b['min_ms']:.3f} / {c['min_ms']:.3f}]  same result: {same}\n"
               f"    the fused route avoids {2 * matrix / 1e6:.1f} MB of device traffic (scores written and read again); the reference moves "
               f"{2 * matrix / 1e6:.1f} MB over the host link (scores down, int32 path up) and searches one row after another on one core")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

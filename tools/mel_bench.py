@@ -7,40 +7,20 @@ ev_stft_magnitude is the nearest equivalent that existed before the analysis pat
 Shapes: B = 64 and B = 1 at 132 096 samples (516 frames, the bench utterance).  None of the figures is a gate.
 """
 import argparse
-import json
+import functools
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
+import bench_timing  # noqa: E402
 from emojivoice_amd._lib import Engine  # noqa: E402
 from emojivoice_amd.audio import mel_filterbank  # noqa: E402
 
-
-def timed(fn, calls, warmup=5):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    torch.cuda.synchronize()                     # cross-check: host clock around `calls` back-to-back calls that end in a synchronise
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    host = (time.perf_counter() - t0) * 1e3 / calls
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls, "host_clock_back_to_back_ms": host}
+timed = functools.partial(bench_timing.timed, warmup=5, host_clock=True)
 
 
 def main():
@@ -62,11 +42,7 @@ def main():
                                   "mel_frames_per_s": B * (L // 256) / (mel["median_ms"] * 1e-3)}
         print(f"B={B}: ev_mel_spectrogram {mel['median_ms']:.3f} ms  ev_stft_magnitude {stft['median_ms']:.3f} ms  ratio {mel['median_ms'] / stft['median_ms']:.2f}"
               f"  (host clock, back to back: {mel['host_clock_back_to_back_ms']:.3f} / {stft['host_clock_back_to_back_ms']:.3f} ms)")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

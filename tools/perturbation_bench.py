@@ -12,9 +12,8 @@ strided read and a 6-step reduction that the next search depends on, then 7 sums
 are what was seen.  The B = 1 row is also compared with the numpy restatement (tests/perturbation_ref.py): marks and counts equal, worst error.
 """
 import argparse
-import json
+import functools
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -24,6 +23,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
+import bench_timing  # noqa: E402
 import perturbation_ref as R  # noqa: E402
 import stoi_ref  # noqa: E402
 from emojivoice_amd import audio  # noqa: E402
@@ -34,21 +34,7 @@ W, H, NC, PF, AF = 1024, 256, 3, 1.3, 1.6
 TAU_MIN, TAU_MAX = 36, 340
 FM_ORDER = 13
 FLOOR = audio.PERTURBATION_POWER_FLOOR
-
-
-def timed(fn, calls, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls}
+timed = functools.partial(bench_timing.timed, warmup=3, host_clock=False)
 
 
 def main():
@@ -111,11 +97,7 @@ def main():
         del x, dst
     eng.close()
     fe.close()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

@@ -11,42 +11,21 @@ and one conversion), so the figure that matters is the fma rate printed beside i
 frames are voiced and the decision takes its usual path (the cost does not depend on the data otherwise).  None of the figures is a gate.
 """
 import argparse
-import json
+import functools
 import math
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
+import bench_timing  # noqa: E402
 from emojivoice_amd._lib import Engine, _stream_ptr  # noqa: E402
 
 W, H, TAU_MIN, TAU_MAX, THRESHOLD = 1024, 256, 36, 340, 0.1
-
-
-def timed(fn, calls, warmup=5):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    torch.cuda.synchronize()                     # cross-check: host clock around `calls` back-to-back calls that end in a synchronise
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    host = (time.perf_counter() - t0) * 1e3 / calls
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls, "host_clock_back_to_back_ms": host}
+timed = functools.partial(bench_timing.timed, warmup=5, host_clock=True)
 
 
 def main():
@@ -90,11 +69,7 @@ def main():
               f"({fmas / (tp['median_ms'] * 1e-3) / 1e12:.2f} T float64 fma/s; {B * F} frames, {voiced} voiced; "
               f"host clock, back to back: {tp['host_clock_back_to_back_ms']:.4f} / {cp['host_clock_back_to_back_ms']:.4f} ms)")
     eng.close()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

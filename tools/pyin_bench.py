@@ -11,10 +11,9 @@ F dependent byte loads of one lane: it is latency-bound and does not shrink with
 torch allocations and the conversion of the states into Hz.  None of the figures is a gate.
 """
 import argparse
-import json
+import functools
 import math
 import os
-import statistics
 import sys
 
 import torch
@@ -22,25 +21,12 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
+import bench_timing  # noqa: E402
 from emojivoice_amd import audio  # noqa: E402
 from emojivoice_amd._lib import Engine  # noqa: E402
 
 SR, W, H, FMIN, FMAX = 22050, 1024, 256, 65.0, 600.0
-
-
-def timed(fn, calls, warmup=5):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls}
+timed = functools.partial(bench_timing.timed, warmup=5, host_clock=False)
 
 
 def main():
@@ -88,11 +74,7 @@ def main():
               f"decode {t_dec['median_ms']:.4f} ms ({t_dec['median_ms'] / yin:.2f} x)  audio.pitch_pyin {t_all['median_ms']:.4f} ms "
               f"({t_all['median_ms'] / yin:.2f} x)  ({B * F} frames, {voiced} voiced)")
     eng.close()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

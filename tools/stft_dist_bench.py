@@ -13,7 +13,7 @@ measured here, so no share of peak is stated and no figure is a gate.  The scrip
 CPU's (float64 order effects) and, for B = 1, what one row costs: 35 to 166 workgroups do not fill the chip.
 """
 import argparse
-import json
+import functools
 import math
 import os
 import statistics
@@ -25,31 +25,12 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
+import bench_timing  # noqa: E402
 from emojivoice_amd import audio  # noqa: E402
 from emojivoice_amd._lib import Engine, _stream_ptr  # noqa: E402
 
 SR, SECONDS, CPU_THREADS = 22050, 6, 16
-
-
-def timed(fn, calls, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    torch.cuda.synchronize()                     # cross-check: host clock around `calls` back-to-back calls that end in a synchronise
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    host = (time.perf_counter() - t0) * 1e3 / calls
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls, "host_clock_back_to_back_ms": host}
+timed = functools.partial(bench_timing.timed, warmup=3, host_clock=True)
 
 
 def cpu_metric(x, y, nfft, hop, win):
@@ -130,11 +111,7 @@ def main():
         del x, y
     for e in engines.values():
         e.close()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ achieved rate counts those USEFUL fmas (2 flops each) over the whole call's even
 cores and none has been measured here, so no share of peak is stated and no figure is a gate.
 """
 import argparse
-import json
+import functools
 import os
 import statistics
 import sys
@@ -26,6 +26,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
+import bench_timing  # noqa: E402
 import voice_quality_ref as R  # noqa: E402
 from emojivoice_amd import audio  # noqa: E402
 from emojivoice_amd._lib import Engine, _stream_ptr  # noqa: E402
@@ -33,21 +34,7 @@ from emojivoice_amd._lib import Engine, _stream_ptr  # noqa: E402
 SR, SECONDS, CPU_THREADS = 22050, 6, 16
 NFFT, HOP, WIN = 1024, 256, 1024
 FLOOR = 1e-7
-
-
-def timed(fn, calls, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": calls}
+timed = functools.partial(bench_timing.timed, warmup=3, host_clock=False)
 
 
 def main():
@@ -115,11 +102,7 @@ def main():
         del x, y, dst
     vq.close()
     sd.close()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(f"wrote {args.out}")
+    bench_timing.write_json(args.out, res)
 
 
 if __name__ == "__main__":

@@ -7,6 +7,7 @@ HIP library is missing or no GPU is visible.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 from typing import Dict, Optional
@@ -39,7 +40,7 @@ EXPORTS = [
     "ev_load_stoi", "ev_stoi",
     "ev_load_stft_dist", "ev_stft_dist",
     "ev_load_voice_quality", "ev_voice_quality",
-    "ev_load_formants", "ev_formants",
+    "ev_load_formants", "ev_formants", "ev_formant_track",
     "ev_perturbation",
     "ev_load_harmonics", "ev_harmonics",
     "ev_functionals",
@@ -173,6 +174,7 @@ def load_library() -> C.CDLL:
     lib.ev_voice_quality.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_load_formants.argtypes = [vp, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, i32]
     lib.ev_formants.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
+    lib.ev_formant_track.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp]
     lib.ev_perturbation.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     lib.ev_load_harmonics.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, i32, C.c_double, C.c_double, C.c_double]
     lib.ev_harmonics.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, C.c_double, vp, vp, vp, vp]
@@ -599,6 +601,37 @@ class Engine:
         self._check(self.lib.ev_formants(self.h, x.data_ptr(), _ptr(ln), B, L, float(power_floor), _ptr(lpc), formant.data_ptr(), count.data_ptr(),
                                          _stream_ptr()), "ev_formants")
         return lpc, formant, count
+
+    def formant_track(self, formant, count, n_tracks: int, reference, cost_f: float = 1.0, cost_b: float = 1.0, cost_j: float = 1.0,
+                      want_cost: bool = True, back=None):
+        """Tracks through the candidates ``formants`` wrote (ev_formant_track; no load step): ``formant`` (B, NF, n_cand, 2) float64 and ``count``
+        (B, NF) int32 on the GPU, ``reference`` the ``n_tracks`` reference frequencies in Hz on the host: (track (B, NF, n_tracks, 2) float64: the
+        chosen candidates, zeros on gaps; sel (B, NF) int32: the state, -1 on gaps; cost (B, NF) float64 or None: each segment's optimum at its
+        last frame) on the device.  ``back``: (B, NF, S) int16 scratch (16-bit words) to use instead of a new tensor, S = C(n_cand, n_tracks)."""
+        if formant.dtype != torch.float64 or formant.dim() != 4 or formant.shape[3] != 2 or count.dtype != torch.int32 or tuple(count.shape) != tuple(formant.shape[:2]):
+            raise ValueError(f"formant_track: float64 formant (B, NF, n_cand, 2) and int32 count (B, NF) expected, got {formant.dtype} "
+                             f"{tuple(formant.shape)} and {count.dtype} {tuple(count.shape)}")
+        if not formant.is_cuda or count.device != formant.device:
+            raise EvLibraryError("no CPU fallback: formant_track needs its inputs on one GPU")
+        formant, count = formant.contiguous(), count.contiguous()
+        B, NF, nc, _ = formant.shape
+        nt = int(n_tracks)
+        ref = np.ascontiguousarray(np.asarray(reference, dtype=np.float64).reshape(-1))
+        if ref.size != nt:
+            raise ValueError(f"formant_track: reference must hold n_tracks = {nt} values, got {ref.size}")
+        S = math.comb(nc, nt) if 1 <= nt <= nc else 1
+        if S <= 1024:                                                    # (over it the library fails with its message; nothing is allocated for it)
+            if back is None:
+                back = torch.empty((B, NF, S), dtype=torch.int16, device=formant.device)
+            elif back.dtype != torch.int16 or back.numel() < B * NF * S or not back.is_contiguous():
+                raise ValueError(f"formant_track: back must be contiguous int16 with at least {B * NF * S} elements")
+        track = torch.empty((B, NF, max(nt, 0), 2), dtype=torch.float64, device=formant.device)
+        sel = torch.empty((B, NF), dtype=torch.int32, device=formant.device)
+        cost = torch.empty((B, NF), dtype=torch.float64, device=formant.device) if want_cost else None
+        self._check(self.lib.ev_formant_track(self.h, formant.data_ptr(), count.data_ptr(), B, NF, nc, nt, ref.ctypes.data, float(cost_f), float(cost_b),
+                                              float(cost_j), _ptr(back), track.data_ptr(), sel.data_ptr(), _ptr(cost), _stream_ptr()),
+                    "ev_formant_track")
+        return track, sel, cost
 
     def perturbation(self, x, lengths, lag, hop_length: int, n_cycles: int, corr_length: int, period_factor: float = 1.3,
                      amplitude_factor: float = 1.6, power_floor: float = 1e-10, want_marks: bool = True):

@@ -58,6 +58,7 @@ comparable across this project's runs, not to the digit with Praat or VoiceSauce
 """
 from __future__ import annotations
 
+import itertools
 import math
 import wave
 from typing import Callable, Dict, Iterable, Optional, Tuple
@@ -1117,6 +1118,82 @@ def formant_statistics(fm, voiced, lengths=None, max_bandwidth: float = 700.0):
 
 
 FORMANT_FIGURES = ("f1_hz", "f2_hz", "f3_hz", "b1_hz", "b2_hz", "b3_hz")
+
+FORMANT_TRACK_REFERENCE = (550.0, 1650.0, 2750.0)  # Hz: the resonances of a neutral vocal tract of 17.5 cm, Praat's defaults for F1 .. F3
+FORMANT_TRACK_MAX_STATES = 1024                    # ``ev_formant_track``'s limit on S = C(n_cand, n_tracks)
+
+
+def formant_track_arguments(fm, n_tracks: int = 3, reference=FORMANT_TRACK_REFERENCE, frequency_cost: float = 1.0, bandwidth_cost: float = 1.0,
+                            transition_cost: float = 1.0) -> Dict:
+    """``formant_tracks``' checks, on the host and before any device is touched (ValueError): ``fm`` holds "frequency" and "bandwidth" (B, F,
+    n_cand) or one row (F, n_cand) and "count" (B, F) or (F,) with F >= 1 and 1 <= n_cand <= 16; 1 <= n_tracks <= n_cand; ``reference`` holds
+    n_tracks finite frequencies greater than 0; the three costs are finite and at least 0; S = C(n_cand, n_tracks) <= 1024 -> {"one": a single
+    row, "n_cand", "n_tracks", "S", "reference": (n_tracks,) float64}."""
+    who = "formant_tracks"
+    if not isinstance(fm, dict) or any(k not in fm for k in ("frequency", "bandwidth", "count")):
+        raise ValueError(f"{who}: fm must be the dict of formants (frequency, bandwidth, count)")
+    freq, band, count = (torch.as_tensor(fm[k]) for k in ("frequency", "bandwidth", "count"))
+    if freq.dim() not in (2, 3) or freq.shape != band.shape or tuple(count.shape) != tuple(freq.shape[:-1]):
+        raise ValueError(f"{who}: frequency and bandwidth must be (B, F, n_cand) or (F, n_cand) and count (B, F) or (F,), got {tuple(freq.shape)}, "
+                         f"{tuple(band.shape)} and {tuple(count.shape)}")
+    F, nc = int(freq.shape[-2]), int(freq.shape[-1])
+    if F < 1:
+        raise ValueError(f"{who}: no frames")
+    if not 1 <= nc <= 16:
+        raise ValueError(f"{who}: n_cand={nc} outside 1 <= n_cand <= 16")
+    if isinstance(n_tracks, bool) or int(n_tracks) != n_tracks or not 1 <= int(n_tracks) <= nc:
+        raise ValueError(f"{who}: n_tracks={n_tracks} outside 1 <= n_tracks <= n_cand = {nc}")
+    nt = int(n_tracks)
+    ref = np.asarray(reference, dtype=np.float64).reshape(-1)
+    if ref.size != nt:
+        raise ValueError(f"{who}: reference must hold n_tracks = {nt} frequencies, got {ref.size}")
+    if not (np.isfinite(ref) & (ref > 0)).all():
+        raise ValueError(f"{who}: reference={ref.tolist()} must be finite and greater than 0")
+    for name, v in (("frequency_cost", frequency_cost), ("bandwidth_cost", bandwidth_cost), ("transition_cost", transition_cost)):
+        if not (math.isfinite(float(v)) and float(v) >= 0.0):
+            raise ValueError(f"{who}: {name}={v} must be finite and at least 0")
+    S = math.comb(nc, nt)
+    if S > FORMANT_TRACK_MAX_STATES:
+        raise ValueError(f"{who}: S={S} states = C(n_cand={nc}, n_tracks={nt}) over the limit S <= {FORMANT_TRACK_MAX_STATES}")
+    return {"one": freq.dim() == 2, "n_cand": nc, "n_tracks": nt, "S": S, "reference": ref}
+
+
+def formant_track_states(n_cand: int, n_tracks: int) -> np.ndarray:
+    """(S, n_tracks) int64: the states of ``ev_formant_track`` in their numbering, the strictly increasing index tuples over 0 .. n_cand - 1 in
+    lexicographic order."""
+    return np.array(list(itertools.combinations(range(int(n_cand)), int(n_tracks))), dtype=np.int64).reshape(-1, int(n_tracks))
+
+
+@torch.inference_mode()
+def formant_tracks(fm, n_tracks: int = 3, reference=FORMANT_TRACK_REFERENCE, frequency_cost: float = 1.0, bandwidth_cost: float = 1.0,
+                   transition_cost: float = 1.0):
+    """Formant tracks through the candidates of ``formants`` on the device (``ev_formant_track``; no torch fallback; Praat's Formant: Track is
+    the model): per row a Viterbi pass over the ways of mapping ``n_tracks`` tracks, which do not cross, onto each frame's candidates.  A
+    mapping costs, per track k, frequency_cost |f - reference[k]| / 1000 + bandwidth_cost bw / f in its frame and transition_cost |log2 f -
+    log2 f'| against the frame before.  A frame with fewer than ``n_tracks`` candidates (silent, unconverged, past the row) is a gap; the runs
+    of frames between gaps are segments, each decoded on its own.  Ask ``formants`` for more candidates than tracks (n_formants=5 for three
+    tracks), so that a spurious candidate can be left out.  ``fm``: the dict of ``formants``, on the GPU -> {"frequency", "bandwidth" (B, F,
+    n_tracks) float64: the chosen candidates, zeros on gaps; "count" (B, F) int32: n_tracks on tracked frames, 0 on gaps, -1 where the input
+    was -1; "selection" (B, F, n_tracks) int64: the chosen candidates' indices, -1 on gaps; "cost" (B, F) float64: each segment's optimum at
+    its last frame, 0 elsewhere; "segments" (B,) int64}: the same contract as ``formants``', so the result goes wherever its dict goes
+    (``formant_statistics``, ``harmonics``, ``harmonic_statistics``, ``voice_functionals``).  A single row (F, n_cand) gives B = 1."""
+    a = formant_track_arguments(fm, n_tracks, reference, frequency_cost, bandwidth_cost, transition_cost)
+    freq, band, count = (torch.as_tensor(fm[k]) for k in ("frequency", "bandwidth", "count"))
+    if not (freq.is_cuda and band.device == freq.device and count.device == freq.device):
+        raise EvLibraryError("formant_tracks runs on a ROCm GPU only (no CPU fallback): its input is the dict formants returned")
+    if a["one"]:
+        freq, band, count = freq.unsqueeze(0), band.unsqueeze(0), count.unsqueeze(0)
+    cand = torch.stack((freq.to(torch.float64), band.to(torch.float64)), dim=-1).contiguous()
+    count = count.to(torch.int32).contiguous()
+    eng = _cached_engine(freq.device, ("formant_track",))
+    track, sel, cost = eng.formant_track(cand, count, a["n_tracks"], a["reference"], frequency_cost, bandwidth_cost, transition_cost)
+    tracked = sel >= 0
+    table = torch.from_numpy(formant_track_states(a["n_cand"], a["n_tracks"])).to(freq.device)
+    selection = torch.where(tracked[..., None], table[sel.clamp(min=0).to(torch.int64)], torch.full_like(table[:1], -1))
+    after = torch.cat((tracked[:, 1:], torch.zeros_like(tracked[:, :1])), dim=1)
+    out_count = torch.where(tracked, torch.full_like(count, a["n_tracks"]), torch.where(count < 0, torch.full_like(count, -1), torch.zeros_like(count)))
+    return {"frequency": track[..., 0], "bandwidth": track[..., 1], "count": out_count, "selection": selection, "cost": cost,
+            "segments": (tracked & ~after).sum(dim=1)}
 
 
 PERTURBATION_POWER_FLOOR = 1e-10                   # a correlation whose energies' product is at or under its square gives r = 0

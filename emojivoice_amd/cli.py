@@ -17,6 +17,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt                                             # pairs.txt.eval.json: MCD, f0 RMSE, voicing error per 'recorded.wav|synthesised.wav[|spk]'
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt                                      # clean/filelist.txt.voice.json: CPP, alpha ratio, Hammarberg index, spectral slopes per file and per speaker
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt --formants                           # ... and F1-F3 with their bandwidths (Burg's linear prediction at 11025 Hz), per file and per speaker
+    python -m emojivoice_amd.cli --voice_report clean/filelist.txt --formants --track_formants          # ... with F1-F3 tracked across frames through five candidates per frame (a Viterbi pass per file) instead of the three lowest
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --formants                                  # ... and, per pair, the mean F1-F3 / B1-B3 of both sides and their differences
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt --perturbation                       # ... and jitter, RAP, shimmer and HNR over the voiced frames, per file and per speaker
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --perturbation                              # ... and, per pair, jitter, RAP, shimmer and HNR of both sides and their differences
@@ -83,6 +84,9 @@ def validate_args(args):
             assert any(getattr(args, h, None) for h in homes), f"--{family.pairs_flag} is an option of " + " and of ".join("--" + h for h in homes)
     if getattr(args, "functionals", False):
         assert getattr(args, "voice_report", None), "--functionals is an option of --voice_report"
+    if getattr(args, "track_formants", False):
+        assert (getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None)) and (getattr(args, "formants", False) or getattr(args, "harmonics", False)), \
+            "--track_formants is an option of --formants and of --harmonics under --voice_report and --evaluate_pairs"
     if args.sample_rate is not None:
         assert args.sample_rate > 0, "--sample_rate must be positive"
     if args.prepare_dataset:
@@ -487,8 +491,21 @@ def prosody_report(args, device):
 Family = collections.namedtuple("Family", "report_flag pairs_flag block figures frames_key counts used measure finish", defaults=(None,))
 
 
-def report_families():
-    """The figure families of --voice_report and --evaluate_pairs, in the order of the reports.  Per family: ``report_flag`` and ``pairs_flag``,
+TRACK_CANDIDATES, TRACK_FORMANTS = 5, 3             # --track_formants: candidates per frame from audio.formants, tracks through them
+
+
+def formant_tracking_parameters():
+    """The top-level "formant_tracking" object of a report made with --track_formants: what audio.formant_tracks ran with."""
+    from . import audio
+
+    return {"candidates": TRACK_CANDIDATES, "tracks": TRACK_FORMANTS, "reference_hz": list(audio.FORMANT_TRACK_REFERENCE), "frequency_cost": 1.0,
+            "bandwidth_cost": 1.0, "transition_cost": 1.0}
+
+
+def report_families(track: bool = False):
+    """The figure families of --voice_report and --evaluate_pairs, in the order of the reports.  ``track`` (--track_formants): the formants that
+    the formants and the harmonics family read are audio.formant_tracks' (TRACK_CANDIDATES candidates per frame tracked to TRACK_FORMANTS), and the
+    formants family also counts tracked_frames and track_segments.  Per family: ``report_flag`` and ``pairs_flag``,
     the args attributes that switch it on in the two reports (None: always on); ``block``, its name in the evaluation report; ``figures``,
     its tuple in audio; ``frames_key``, the report's key of its frame count; ``counts``, further keys of its statistics that the report sums;
     ``used(st)`` -> {figure: (B,) the frames behind its mean}; ``measure(batch, sr, hop, lens, voiced, n_frames, got)`` -> its
@@ -500,9 +517,17 @@ def report_families():
         got["voice"] = audio.voice_quality(batch, sr, hop_length=hop, lengths=lens)
         return audio.voice_quality_statistics(got["voice"], voiced, n_frames)
 
+    def analysed_formants(batch, sr, hop, lens):
+        if not track:
+            return audio.formants(batch, sr, hop_length=hop, lengths=lens)
+        return audio.formant_tracks(audio.formants(batch, sr, hop_length=hop, lengths=lens, n_formants=TRACK_CANDIDATES), n_tracks=TRACK_FORMANTS)
+
     def formants(batch, sr, hop, lens, voiced, n_frames, got):
-        got["formants"] = audio.formants(batch, sr, hop_length=hop, lengths=lens)
-        return audio.formant_statistics(got["formants"], voiced, n_frames)
+        fm = got["formants"] = analysed_formants(batch, sr, hop, lens)
+        st = audio.formant_statistics(fm, voiced, n_frames)
+        if track:
+            st.update(tracked_frames=(fm["count"] > 0).sum(dim=1), track_segments=fm["segments"])
+        return st
 
     def perturbation(batch, sr, hop, lens, voiced, n_frames, got):
         """audio.perturbation at YIN's own lags, reduced over the frames that the pitch tracker AND YIN call voiced."""
@@ -512,7 +537,7 @@ def report_families():
     def harmonics(batch, sr, hop, lens, voiced, n_frames, got):
         """audio.harmonics at YIN's own periods and the formants of --formants (without it audio.formants is run here), reduced over the frames
         that the pitch tracker calls voiced and whose figures YIN's period and the formants' bandwidths admit."""
-        fm = got["harmonic_fm"] = got["formants"] if "formants" in got else audio.formants(batch, sr, hop_length=hop, lengths=lens)
+        fm = got["harmonic_fm"] = got["formants"] if "formants" in got else analysed_formants(batch, sr, hop, lens)
         got["harmonics"] = audio.harmonics(batch, sr, hop_length=hop, lengths=lens, formants=fm)
         return audio.harmonic_statistics(got["harmonics"], voiced, n_frames, fm=fm)
 
@@ -529,7 +554,8 @@ def report_families():
 
     per_figure = lambda st: st["used"]
     return (Family(None, "voice_quality", "voice", audio.VOICE_QUALITY_FIGURES, "voiced_frames", (), lambda st: {k: st["frames"] for k in st["sums"]}, voice),
-            Family("formants", "formants", "formants", audio.FORMANT_FIGURES, "formant_frames", ("unconverged_frames",),
+            Family("formants", "formants", "formants", audio.FORMANT_FIGURES, "formant_frames",
+                   ("unconverged_frames",) + (("tracked_frames", "track_segments") if track else ()),
                    lambda st: {k: st["used"][:, int(k[1]) - 1] for k in st["sums"]}, formants),          # f_i and b_i share used[:, i]
             Family("perturbation", "perturbation", "perturbation", audio.PERTURBATION_FIGURES, "perturbation_frames", (), per_figure, perturbation),
             Family("harmonics", "harmonics", "harmonics", audio.HARMONIC_FIGURES, "harmonic_frames", (), per_figure, harmonics),
@@ -538,7 +564,7 @@ def report_families():
 
 def enabled_families(args, flag: str):
     """The families of report_families() that ``args`` switches on; ``flag``: "report_flag" (--voice_report) or "pairs_flag" (--evaluate_pairs)."""
-    return [f for f in report_families() if getattr(f, flag) is None or getattr(args, getattr(f, flag), False)]
+    return [f for f in report_families(getattr(args, "track_formants", False)) if getattr(f, flag) is None or getattr(args, getattr(f, flag), False)]
 
 
 def family_rows(st, family):
@@ -612,6 +638,11 @@ def voice_report(args, device):
     --formants adds per file f1_hz .. f3_hz and b1_hz .. b3_hz (audio.formants reduced by audio.formant_statistics over the voiced frames with
     at least three formants; null without such a frame), formant_frames (those frames) and unconverged_frames; per speaker and overall the
     means pooled over the frames behind each figure, and both counts summed.
+    --track_formants (with --formants or --harmonics) analyses five candidates per frame and tracks F1-F3 through them (audio.formant_tracks: a
+    Viterbi pass per row, Praat's Formant: Track), so that a spurious low candidate no longer shifts every formant by one slot; the tracked dict
+    stands wherever the formants are passed on (the formant figures, the harmonics' formant input, --functionals).  The formants family gains
+    tracked_frames and track_segments per file, summed per speaker and overall, and the report a top-level "formant_tracking" object with the
+    parameters.
     --perturbation adds per file jitter_pct, rap_pct, shimmer_pct, shimmer_db and hnr_db (audio.perturbation reduced by
     audio.perturbation_statistics over the voiced frames; null without a frame that has a counted pair) and perturbation_frames (the voiced
     frames); per speaker and overall the means pooled over the frames behind each figure, and the count summed.
@@ -669,6 +700,8 @@ def voice_report(args, device):
            "overall": pool(list(pooled.values()))}
     if pitch_method(args) != "yin":
         rep["pitch_method"] = pitch_method(args)
+    if getattr(args, "track_formants", False):
+        rep["formant_tracking"] = formant_tracking_parameters()
     out_path = f"{args.voice_report}.voice.json"
     with open(out_path, "w") as f:
         json.dump(rep, f, indent=1)
@@ -890,7 +923,9 @@ def evaluate_pairs(args, device):
     --harmonics adds "harmonics" in the same form: h1_h2_db, h1_a3_db, f1_rel_db, f2_rel_db and f3_rel_db (audio.harmonics,
     audio.harmonic_statistics) of each side and their differences: a breathier or a more pressed source where the vowel is the same.
     --auditory adds "auditory" in the same form: loudness, the spectral flux, MFCC 1-4, their voiced / unvoiced variants and equivalent_level_db
-    (audio.auditory, audio.auditory_statistics) of each side and their differences: a duller, flatter or quieter rendering of the same sentence."""
+    (audio.auditory, audio.auditory_statistics) of each side and their differences: a duller, flatter or quieter rendering of the same sentence.
+    --track_formants (with --formants or --harmonics): the formants of both are audio.formant_tracks' (five candidates per frame tracked to F1-F3);
+    the report gains a top-level "formant_tracking" object with the parameters and keeps every other key."""
     from . import audio
 
     entries = parse_pairs(args.evaluate_pairs)
@@ -960,6 +995,8 @@ def evaluate_pairs(args, device):
            "overall": means(records) if records else None, "skipped": skipped}
     if pitch_method(args) != "yin":
         rep["pitch_method"] = pitch_method(args)
+    if getattr(args, "track_formants", False):
+        rep["formant_tracking"] = formant_tracking_parameters()
     out_path = f"{args.evaluate_pairs}.eval.json"
     with open(out_path, "w") as f:
         json.dump(rep, f, indent=1)
@@ -1049,6 +1086,9 @@ def cli(argv=None):
                    "and the harmonics-to-noise ratio in dB over the voiced frames (pitch marks by peak picking at YIN's lag, three cycles each side) "
                    "per file, per speaker and overall; --evaluate_pairs: add \"perturbation\" per pair (both sides and their differences) and per "
                    "speaker and overall")
+    p.add_argument("--track_formants", action="store_true", help="with --formants or --harmonics under --voice_report or --evaluate_pairs: analyse five "
+                   "candidates per frame and track F1-F3 through them on the device (a Viterbi pass per file, Praat's Formant: Track) instead of taking "
+                   "the three lowest; adds tracked_frames and track_segments to the formants' keys and \"formant_tracking\" (the parameters) to the report")
     p.add_argument("--functionals", action="store_true", help="--voice_report: add \"functionals\" per file: mean, sd, the 20th / 50th / 80th percentile and "
                    "their range, mean and sd of the rising and of the falling slopes per second and the peaks per second of every contour the report "
                    "measures (f0 in semitones from 27.5 Hz, the voice-quality figures, and those of --formants / --perturbation / --harmonics), and "

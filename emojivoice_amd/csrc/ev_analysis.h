@@ -1,5 +1,5 @@
 // Host entry points of the analysis side: resampling, dataset statistics, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness,
-// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals and auditory descriptors (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
+// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals, auditory descriptors and formant tracks (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
 // after ev_handle, fail / HIPCHK / enter, dev_upload, drop_owned, scratch_acquire and launch<>.  None of these calls runs on the engine's conv
 // path; ev_load_mel_basis, ev_mel_spectrogram, ev_denoise and ev_stft_magnitude do, and stay in ev_engine.hip.
 #pragma once
@@ -825,6 +825,44 @@ int ev_functionals(ev_handle* h, const double* d_v, const uint8_t* d_mask, const
     for (int r = 0; r < NQ; ++r) p.q[r] = q[r];
     // 64 doubles and 64 words of hand-over, then u (8 B) and g, st (2 B each) per frame: 48.5 KiB at F = 4096
     launch<functionals_kernel>(h->device, dim3((unsigned)K, (unsigned)B), dim3(256), 512 + (size_t)12 * p.P, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Formant tracking: a Viterbi pass over the candidates ev_formants wrote, one workgroup per row (formant_track_kernel, ev_analysis_kernels.h; the
+// definition: include/emojivoice.h).  No load step, no tables, no arena: one launch whose arguments carry the reference frequencies and the three
+// costs.  LDS in doubles: delta 2 S, the states' tuples S, two table buffers of 16 x 17 + 256 each, the ring of four staged frames 4 x 48, ref 16;
+// then four words of m: 10 368 bytes at S = 10, 34 704 at S = 1024.
+int ev_formant_track(ev_handle* h, const double* d_formant, const int32_t* d_count, int B, int NF, int n_cand, int n_tracks, const double* ref,
+                     double cost_f, double cost_b, double cost_j, uint16_t* d_back, double* d_track, int32_t* d_sel, double* d_cost, void* stream) {
+    if (enter(h)) return 1;
+    if (check_batch(h, __func__, B)) return 1;
+    if (NF < 1) return fail(h, "ev_formant_track: NF=%d must be at least 1", NF);
+    if (n_cand < 1 || n_cand > 16) return fail(h, "ev_formant_track: n_cand=%d outside 1 <= n_cand <= 16", n_cand);
+    if (n_tracks < 1 || n_tracks > n_cand) return fail(h, "ev_formant_track: n_tracks=%d outside 1 <= n_tracks <= n_cand = %d", n_tracks, n_cand);
+    long long S = 1;
+    for (int i = 1; i <= n_tracks; ++i) S = S * (n_cand - n_tracks + i) / i;                 // C(n_cand, n_tracks), exact at every step
+    if (S > 1024) return fail(h, "ev_formant_track: S=%lld states = C(n_cand=%d, n_tracks=%d) over the limit S <= 1024", S, n_cand, n_tracks);
+    if (!ref) return fail(h, "ev_formant_track: ref (HOST, n_tracks doubles) must be non-null");
+    for (int k = 0; k < n_tracks; ++k)
+        if (!(ref[k] > 0.0) || !std::isfinite(ref[k])) return fail(h, "ev_formant_track: ref[%d]=%g must be finite and greater than 0", k, ref[k]);
+    if (!(cost_f >= 0.0) || !std::isfinite(cost_f)) return fail(h, "ev_formant_track: cost_f=%g must be finite and at least 0", cost_f);
+    if (!(cost_b >= 0.0) || !std::isfinite(cost_b)) return fail(h, "ev_formant_track: cost_b=%g must be finite and at least 0", cost_b);
+    if (!(cost_j >= 0.0) || !std::isfinite(cost_j)) return fail(h, "ev_formant_track: cost_j=%g must be finite and at least 0", cost_j);
+    if (!d_formant || !d_count) return fail(h, "ev_formant_track: d_formant and d_count must be non-null");
+    if (!d_back) return fail(h, "ev_formant_track: d_back must be non-null (B x NF x S uint16 of the caller's)");
+    if (!d_track || !d_sel) return fail(h, "ev_formant_track: d_track and d_sel must be non-null");
+    h->stream = (hipStream_t)stream;
+    FormantTrackParams p{};
+    p.formant = d_formant; p.count = d_count; p.back = d_back; p.track = d_track; p.sel = d_sel; p.cost = d_cost;
+    p.NF = NF; p.nc = n_cand; p.nt = n_tracks; p.S = (int)S;
+    p.G = 1;
+    while (p.S * p.G * 2 <= 64) p.G *= 2;                                                    // lanes per target state: S G <= 64 (S = 10: 4)
+    p.cf = cost_f; p.cb = cost_b; p.cj = cost_j;
+    for (int k = 0; k < n_tracks; ++k) p.ref[k] = ref[k];
+    const int NT = std::min(1024, round_up(p.S, 64));
+    const size_t smem = (3 * (size_t)p.S + 2 * FTRACK_TABLE + 4 * 48 + 16) * sizeof(double) + 4 * sizeof(int);
+    launch<formant_track_kernel>(h->device, dim3(B), dim3(NT), smem, h->stream, p);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -2763,3 +2763,208 @@ __global__ __launch_bounds__(256) void auditory_kernel(const AudParams p) {
         }
     }
 }
+
+// ---------------------------------------------------------------------------
+// Formant tracking (ev_formant_track): a Viterbi pass over the ways of mapping n_tracks tracks onto the candidates ev_formants wrote for a frame
+// (the definition: include/emojivoice.h; Praat's Formant: Track is the model).  All float64, contraction OFF (STOI_EXACT), no atomics, no scratch.
+// One workgroup per row, sequential over the frames like pyin_decode_kernel.  The S = C(n_cand, n_tracks) states are the strictly increasing index
+// tuples in lexicographic order; a thread unranks its tuple once by the combinatorial number system into 16 nibbles of one 64-bit word (tup[s] in
+// LDS for the predecessors, its own in a register), so no table is loaded and no array is indexed at run time.
+//   lanes     S <= 32: one wave, G = the power of two with S G <= 64 lanes per target state (S = 10: 4); else one thread per target, G = 1, and
+//             round_up(S, 64) threads.  Lane sub of a target scans the predecessors sub, sub + G, ... in ascending order, a later one replacing an
+//             earlier one only when STRICTLY smaller; the G partial minima meet in an xor tree on (value, lowest index).  Min-with-lowest-index is
+//             associative and commutative, so the split changes no bit.
+//   per frame three pieces run, each for its own frame, and ONE barrier closes them:
+//     A  delta_t from delta_{t-1} (LDS, double-buffered: t reads (t - 1) & 1 and writes t & 1), the tables of frame t and the back-pointer to d_back;
+//     B  the tables of frame t + 1 into the other table buffer: Lt[k][c] = (cost_f |f - ref_k|) / 1000 + (cost_b bw) / f and, inside a segment,
+//        D[c][c'] = cost_j |lg_t[c] - lg_{t+1}[c']|, so local is n_tracks lookups added in ascending k and trans another n_tracks: the same terms in
+//        the same order as the direct formulas, and no log2, abs or division in the S^2 loop;
+//     C  wave 0 stages frame t + 2 into a ring of four: {f, bw, log2 f} of its candidates and m (-1: a GAP; the finite / positive test is one ballot),
+//        from registers whose loads were asked for a frame earlier.
+//   Gaps, segment starts and segment ends are read from the ring's m and are uniform over the workgroup: nothing diverges around the barrier.
+//   A state that is not valid in its frame holds +inf; D is 0 wherever a candidate at or past m is involved, so inf + D stays inf and never wins
+//   (the state (0, 1, ..) is valid in every trackable frame: a valid target always has a finite minimum).
+//   Behind the barrier of a segment's last frame wave 0 finds the lowest state of least delta (lane-strided read, xor tree) and lane 0 walks
+//   d_back to the segment's first frame, writing d_sel and d_cost; the other waves go on and meet it at the next barrier.  After the last frame
+//   the workgroup gathers d_track from d_sel in parallel.
+// BANKS (from the LDS table of the kernel guide; no counter was read): ds_read_b64 is served 32 lanes at a time over 64 dword banks.  With G = 1
+// the 64 lanes of a wave scan the same predecessor: tup[s] and delta[s] are broadcasts, and D[c_s(k)][c'(k)] is ONE row, at most 16 consecutive
+// doubles: conflict-free.  With G > 1 a group's lanes read up to G rows; rows are 17 doubles apart (34 dwords), so rows r and r + 1 .. r + 15 start
+// on different banks and two lanes meet on a bank only by chance of their columns (S <= 32: at most 3 x n_tracks such reads per frame).
+struct FormantTrackParams {
+    const double* formant; const int32_t* count; unsigned short* back; double* track; int32_t* sel; double* cost;
+    int NF, nc, nt, S, G;
+    double cf, cb, cj;
+    double ref[16];
+};
+constexpr int FTRACK_DROW = 17;                                         // doubles per row of D
+constexpr int FTRACK_TABLE = 16 * FTRACK_DROW + 256;                    // D, then Lt[k][16]
+
+__device__ __forceinline__ int ftrack_binom(int n, int k) {             // C(n, k), exact (n <= 16)
+    if (k < 0 || k > n) return 0;
+    int r = 1;
+    for (int i = 1; i <= k; ++i) r = r * (n - k + i) / i;
+    return r;
+}
+
+__global__ __launch_bounds__(1024) void formant_track_kernel(const FormantTrackParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double ftrack_lds[];
+    const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;
+    const int NF = p.NF, nc = p.nc, nt = p.nt, S = p.S, G = p.G;
+    const double inf = 1.0 / 0.0;
+    double* dl = ftrack_lds;                                            // [2][S]
+    unsigned long long* tup = (unsigned long long*)(dl + 2 * (size_t)S);   // [S]
+    double* tb = (double*)(tup + S);                                    // [2][FTRACK_TABLE]
+    double* ring = tb + 2 * FTRACK_TABLE;                               // [4][48]: f, bw, log2 f
+    double* rf = ring + 4 * 48;                                         // [16]
+    int* mm = (int*)(rf + 16);                                          // [4]
+    const double* fmr = p.formant + (size_t)b * NF * nc * 2;
+    const int32_t* ctr = p.count + (size_t)b * NF;
+    unsigned short* back = p.back + (size_t)b * NF * S;
+    double* trk = p.track + (size_t)b * NF * nt * 2;
+    int32_t* sel = p.sel + (size_t)b * NF;
+    double* cst = p.cost ? p.cost + (size_t)b * NF : nullptr;
+
+    // C: frame w into ring slot w & 3 (wave 0 only; lanes >= n_cand hold no candidate).  fetch(w) asks for the frame's count and for every lane's
+    // candidate, inside the count or not (the entry exists: lane < n_cand), into registers and waits for nothing; stage(w) uses them one frame
+    // later, so the two loads, which do not depend on each other, travel under a whole frame's work instead of stalling it.
+    int pc = 0;
+    double pf = 0.0, pb = 0.0;
+    auto fetch = [&](int w) {
+        pc = ctr[w];
+        if (lane < nc) { pf = fmr[((size_t)w * nc + lane) * 2]; pb = fmr[((size_t)w * nc + lane) * 2 + 1]; }
+    };
+    auto stage = [&](int w) {
+        const int m = min(pc, nc);
+        const bool mine = lane < m;                                     // (m <= n_cand <= 16)
+        const double f = mine ? pf : 0.0, bw = mine ? pb : 0.0;
+        const bool bad = mine && !(f > 0.0 && f < inf && fabs(bw) < inf);
+        const bool gap = m < nt || __ballot(bad) != 0ull;
+        if (lane < 16) {
+            double* r = ring + (w & 3) * 48;
+            r[lane] = f; r[16 + lane] = bw; r[32 + lane] = mine && !bad ? log2(f) : 0.0;
+        }
+        if (lane == 0) mm[w & 3] = gap ? -1 : m;
+    };
+    // B: the tables of frame u (trackable, m = mu) into buffer u & 1; D only where frame u - 1 is trackable too (mp >= 0)
+    auto tables = [&](int u, int mu, int mp) {
+        double* T = tb + (u & 1) * FTRACK_TABLE;
+        const double* r = ring + (u & 3) * 48;
+        const double* rp = ring + ((u - 1) & 3) * 48;
+        for (int i = tid; i < nt * nc; i += NT) {
+            const int k = i / nc, c = i - k * nc;
+            double v = 0.0;
+            if (c < mu) { const double f = r[c]; v = (p.cf * fabs(f - rf[k])) / 1000.0 + (p.cb * r[16 + c]) / f; }
+            T[16 * FTRACK_DROW + k * 16 + c] = v;
+        }
+        if (mp >= 0)
+            for (int i = tid; i < nc * nc; i += NT) {
+                const int c = i / nc, c2 = i - c * nc;
+                T[c * FTRACK_DROW + c2] = (c < mp && c2 < mu) ? p.cj * fabs(rp[32 + c] - r[32 + c2]) : 0.0;
+            }
+    };
+
+    if (tid < 16) rf[tid] = tid < nt ? p.ref[tid] : 0.0;
+    if (tid < S) {                                                      // the tuple of state tid: lexicographic unranking
+        unsigned long long t = 0ull;
+        int r = tid, x = 0;
+        for (int i = 0; i < nt; ++i) {
+            for (;; ++x) {
+                const int below = ftrack_binom(nc - x - 1, nt - i - 1);
+                if (r < below) break;
+                r -= below;
+            }
+            t |= (unsigned long long)x << (4 * i);
+            ++x;
+        }
+        tup[tid] = t;
+    }
+    if (tid < 64) {
+        fetch(0); stage(0);
+        if (NF > 1) { fetch(1); stage(1); }
+        if (NF > 2) fetch(2);
+    }
+    __syncthreads();
+    const int sp = min(tid / G, S - 1), sub = tid & (G - 1);
+    const bool owner = tid / G < S && sub == 0;
+    const unsigned long long mine = tup[sp];
+    const int top = (int)((mine >> (4 * (nt - 1))) & 15);               // the state is valid in a frame iff top < m
+    {
+        const int m0 = mm[0];
+        if (m0 >= 0) tables(0, m0, -1);
+    }
+    __syncthreads();
+
+    int seg0 = 0;                                                       // the first frame of the segment frame t lies in
+    for (int t = 0; t < NF; ++t) {
+        const int m = mm[t & 3], mp = t > 0 ? mm[(t - 1) & 3] : -1, mn = t + 1 < NF ? mm[(t + 1) & 3] : -1;
+        if (m >= 0) {
+            const double* T = tb + (t & 1) * FTRACK_TABLE;
+            const double* Lt = T + 16 * FTRACK_DROW;
+            double local = Lt[(int)(mine & 15)];
+            for (int k = 1; k < nt; ++k) local = local + Lt[k * 16 + (int)((mine >> (4 * k)) & 15)];
+            double d;
+            if (mp < 0) { seg0 = t; d = local; }
+            else {
+                const double* prev = dl + (size_t)((t - 1) & 1) * S;
+                double best = inf;
+                int arg = 0x7fffffff;
+                for (int s = sub; s < S; s += G) {
+                    const unsigned long long ts = tup[s];
+                    double tr = T[(int)(ts & 15) * FTRACK_DROW + (int)(mine & 15)];
+                    for (int k = 1; k < nt; ++k)
+                        tr = tr + T[(int)((ts >> (4 * k)) & 15) * FTRACK_DROW + (int)((mine >> (4 * k)) & 15)];
+                    const double v = prev[s] + tr;
+                    if (v < best) { best = v; arg = s; }
+                }
+                for (int o = G >> 1; o > 0; o >>= 1) {                  // (G is uniform: every lane of the wave takes part)
+                    const double ov = __shfl_xor(best, o, 64);
+                    const int os = __shfl_xor(arg, o, 64);
+                    if (ov < best || (ov == best && os < arg)) { best = ov; arg = os; }
+                }
+                d = best + local;
+                if (owner) back[(size_t)t * S + sp] = (unsigned short)(top < m && arg < S ? arg : 0);
+            }
+            if (owner) dl[(size_t)(t & 1) * S + sp] = top < m ? d : inf;
+        } else {                                                        // a GAP: zeros and -1
+            if (tid == 0) { sel[t] = -1; if (cst) cst[t] = 0.0; }
+        }
+        if (mn >= 0) tables(t + 1, mn, m);
+        if (tid < 64 && t + 2 < NF) {
+            stage(t + 2);
+            if (t + 3 < NF) fetch(t + 3);
+        }
+        __syncthreads();
+        if (m >= 0 && mn < 0 && tid < 64) {                             // the segment seg0 .. t is complete: its end state and its path
+            const double* cur = dl + (size_t)(t & 1) * S;
+            double bv = inf;
+            int bs = 0x7fffffff;
+            for (int s = lane; s < S; s += 64) { const double v = cur[s]; if (v < bv) { bv = v; bs = s; } }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ov = __shfl_xor(bv, o, 64);
+                const int os = __shfl_xor(bs, o, 64);
+                if (ov < bv || (ov == bv && os < bs)) { bv = ov; bs = os; }
+            }
+            if (tid == 0) {
+                int s = min(bs, S - 1);
+                for (int q = t; q >= seg0; --q) {
+                    sel[q] = s;
+                    if (cst) cst[q] = q == t ? bv : 0.0;
+                    if (q > seg0) s = min((int)back[(size_t)q * S + s], S - 1);   // (the clamp keeps a damaged word inside the states)
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < NF * nt; i += NT) {                           // d_track: a copy of the chosen candidates, zeros on gaps
+        const int t = i / nt, k = i - t * nt, s = sel[t];
+        double f = 0.0, bw = 0.0;
+        if (s >= 0) {
+            const int c = (int)((tup[min(s, S - 1)] >> (4 * k)) & 15);
+            f = fmr[((size_t)t * nc + c) * 2]; bw = fmr[((size_t)t * nc + c) * 2 + 1];
+        }
+        trk[(size_t)i * 2] = f; trk[(size_t)i * 2 + 1] = bw;
+    }
+}

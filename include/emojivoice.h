@@ -45,6 +45,7 @@
  *   ev_voice_quality   <- no counterpart; Eyben et al. 2016 (eGeMAPS) and Hillenbrand et al. 1994 (CPP) are the model
  *   ev_load_formants   <- no counterpart; Burg 1975 (maximum-entropy linear prediction), Aberth 1973 / Ehrlich 1967 and Praat's formant analysis are the model
  *   ev_formants        <- no counterpart; Burg 1975 (maximum-entropy linear prediction), Aberth 1973 / Ehrlich 1967 and Praat's formant analysis are the model
+ *   ev_formant_track   <- no counterpart; Praat's Formant: Track is the model
  *   ev_perturbation    <- no counterpart; Praat's voice report (jitter local / absolute / RAP, shimmer local / dB, cc harmonicity; Boersma 1993) is the model
  *   ev_load_harmonics  <- no counterpart; Eyben et al. 2016 and Hanson 1997 are the model
  *   ev_harmonics       <- no counterpart; Eyben et al. 2016 and Hanson 1997 are the model
@@ -90,7 +91,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -725,6 +726,47 @@ int ev_load_formants(ev_handle *h, const double *window /* HOST (W) */, int W, i
 int ev_formants(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L, double power_floor,
                 double *d_lpc /* (B, NF, order + 2): a_1 .. a_p, gain, E0; or NULL */,
                 double *d_formant /* (B, NF, n_formants, 2): Hz, bandwidth Hz */, int32_t *d_count /* (B, NF) */, void *stream);
+
+/* Formant tracks through the candidates ev_formants wrote: which candidate of a frame is F1, which F2, which F3.  ev_formants keeps the candidates
+ * of lowest frequency, so one spurious low root (a nasal pole, a split F1, a root just inside f_lo) moves every formant up by one slot for that
+ * frame.  This is Praat's tracker (Formant: Track; Formant_tracker: a Viterbi pass over the ways of mapping tracks onto a frame's candidates),
+ * restated so that every order is fixed.  Everything is float64, the kernel is compiled with floating-point contraction off; no atomics, no
+ * scratch; ev_set_arithmetic does not reach it.
+ * Inputs are ev_formants' outputs, unchanged: d_formant (B, NF, n_cand, 2) {f, bw} in Hz and d_count (B, NF) int32.  There is no audio and no
+ *   d_len: frames past a row's end already have count 0 and are therefore gaps.
+ * Parameters: 1 <= n_cand <= 16;  1 <= n_tracks <= n_cand;  HOST ref[n_tracks] in Hz, finite and > 0;  cost_f, cost_b, cost_j finite and >= 0;
+ *   S = C(n_cand, n_tracks) <= 1024.
+ * States: the S strictly increasing index tuples c(0) < .. < c(n_tracks - 1) over 0 .. n_cand - 1, numbered in lexicographic order.  Formants do
+ *   not cross, so track k takes the k-th chosen candidate.
+ * Trackable frames: with m = min(count, n_cand), a frame is trackable iff m >= n_tracks and its first m candidates have finite f > 0 and finite bw.
+ *   Every other frame is a GAP: silent frames, unconverged frames (count -1), frames with too few candidates, frames past the row.  A state is
+ *   valid in a frame iff c(n_tracks - 1) < m; a state that is not valid costs +inf.
+ * Segments: a maximal run of trackable frames.  Every segment is decoded on its own and nothing crosses a gap.  (Praat refuses frames with too
+ *   few candidates; here such a frame ends a segment.)
+ * Costs, float64, sums in ascending track k starting from the first term:
+ *   local(t, s)      = sum_k ( (cost_f |f - ref[k]|) / 1000 + (cost_b bw) / f ),  f, bw of candidate c_s(k) in frame t
+ *   trans(t, s -> s') = sum_k cost_j |lg_{t-1}[c_s(k)] - lg_t[c_s'(k)]|,  lg = log2(f) from the device library
+ *   delta_t0(s)      = local(t0, s) at a segment's first frame t0
+ *   delta_t(s')      = min_s (delta_{t-1}(s) + trans(t, s -> s')) + local(t, s');  of equal minima the lowest s wins
+ *   At the segment's last frame the lowest s of least delta ends the path, and the back-pointers give the rest.
+ *   Min-with-lowest-index is associative and commutative: how the predecessor scan is split over lanes cannot change a bit.
+ * Outputs:
+ *   d_track (B, NF, n_tracks, 2): {f, bw} of the chosen candidates, copies of the input entries; zeros on gaps
+ *   d_sel   (B, NF) int32: the state number, -1 on gaps
+ *   d_cost  (B, NF) float64 or NULL: the segment's optimum at the segment's LAST frame, 0 elsewhere
+ *   d_back  (B, NF, S) uint16: the caller's work buffer, as ev_pyin_decode's d_back is; what it holds after the call is not defined
+ * Nothing depends on the batch or on NF: a row alone, inside a batch, with extra gap frames behind it (a larger NF), a second call, a call with
+ *   d_cost NULL and a replay from a captured graph give the same bits.
+ * Limits, each violation failing with a message that names it and writing nothing: 1 <= B <= 65535; NF >= 1; the parameters above (the message for
+ *   S names S); ref, d_formant, d_count, d_back, d_track and d_sel non-NULL.
+ * Kernel (one launch on `stream`; no load step, no host wait, no copy, no arena: ev_alloc_count never moves): one workgroup per row, sequential
+ *   over the frames with one barrier each; a thread per target state, its tuple unranked once by the combinatorial number system (for S <= 32 the
+ *   predecessor scan of a target is spread over 64 / S lanes, a power of two, and reduced on (value, lowest index)); delta double-buffered in
+ *   LDS; ref and the costs travel in the kernel's arguments; lane 0 walks d_back per segment.  The call is capturable. */
+int ev_formant_track(ev_handle *h, const double *d_formant /* (B, NF, n_cand, 2) */, const int32_t *d_count /* (B, NF) */, int B, int NF,
+                     int n_cand, int n_tracks, const double *ref /* HOST (n_tracks) Hz */, double cost_f, double cost_b, double cost_j,
+                     uint16_t *d_back /* (B, NF, S) work */, double *d_track /* (B, NF, n_tracks, 2) */, int32_t *d_sel /* (B, NF) */,
+                     double *d_cost /* (B, NF) or NULL */, void *stream);
 
 /* Jitter, shimmer and the harmonics-to-noise ratio per frame on the device: how regular the voice is from one glottal cycle to the next (the
  * remaining time-domain members of eGeMAPS; Eyben et al. 2016), on ev_pitch_yin's frame grid and at the lag it wrote.  Everything is float64 on the

@@ -43,7 +43,7 @@ EXPORTS = [
     "ev_load_formants", "ev_formants", "ev_formant_track",
     "ev_perturbation",
     "ev_load_harmonics", "ev_harmonics",
-    "ev_functionals",
+    "ev_functionals", "ev_modulation",
     "ev_load_auditory", "ev_auditory",
 ]
 
@@ -179,6 +179,7 @@ def load_library() -> C.CDLL:
     lib.ev_load_harmonics.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, i32, C.c_double, C.c_double, C.c_double]
     lib.ev_harmonics.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_functionals.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]
+    lib.ev_modulation.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_double, C.c_double, i32, i32, C.c_double, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.ev_load_auditory.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, C.c_double]
     lib.ev_auditory.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
@@ -764,6 +765,38 @@ class Engine:
         self._check(self.lib.ev_functionals(self.h, v.data_ptr(), _ptr(mask), _ptr(ln), B, K, F, qa.ctypes.data if NQ else None, NQ,
                                             stat.data_ptr(), count.data_ptr(), _stream_ptr()), "ev_functionals")
         return stat, count
+
+    def modulation(self, v, mask, lengths, nu0: float, dnu: float, NM: int, min_run: int, min_cycles: float = 2.0, bands=()):
+        """The modulation spectrum of every contour of ``v`` (B, K, F) float64 on the device (ev_modulation; no load step): (spec (B, K, NM)
+        float64: the power at nu0 + j dnu cycles per frame, pooled over the runs of at least ``min_run`` valid frames that hold at least
+        ``min_cycles`` cycles of it; weight (B, K, NM) int32: the frames behind each; peak (B, K, NBAND, 4) float64: per band the interpolated
+        frequency in cycles per frame, the amplitude, the band's mean power and the peak's power over it, zeros without a peak; stat (B, K, 2):
+        the variance the lines leave, the mean slope per frame; count (B, K, 4 + NBAND) int32: the valid frames, the dropped (non-finite) ones,
+        the analysed runs, the analysed frames, then per band the peak's grid index or -1) on the device.  ``mask`` and ``lengths`` as for
+        ``functionals``; ``bands``: up to four (j_lo, j_hi) index pairs, read on the host."""
+        if v.dim() != 3 or v.dtype != torch.float64:
+            raise EvLibraryError(f"modulation: v must be float64 (B, K, F), got {v.dtype} {tuple(v.shape)}")
+        v = v.contiguous()
+        B, K, F = v.shape
+        if mask is not None:
+            if tuple(mask.shape) != (B, K, F) or mask.device != v.device or mask.dtype not in (torch.uint8, torch.bool):
+                raise EvLibraryError(f"modulation: mask must be uint8 or bool ({B}, {K}, {F}) on {v.device}, got {mask.dtype} {tuple(mask.shape)} "
+                                     f"on {mask.device}")
+            mask = mask.contiguous()
+        ln = None if lengths is None else torch.as_tensor(lengths).to(v.device, torch.int32).contiguous()
+        if ln is not None and ln.numel() != B:
+            raise ValueError(f"modulation: {B} lengths expected, got {ln.numel()}")
+        ba = np.ascontiguousarray(np.asarray(bands, dtype=np.int32).reshape(-1, 2))
+        NB, NMo = int(ba.shape[0]), max(min(int(NM), 128), 1)
+        spec = torch.empty((B, K, NMo), dtype=torch.float64, device=v.device)
+        weight = torch.empty((B, K, NMo), dtype=torch.int32, device=v.device)
+        peak = torch.empty((B, K, max(min(NB, 4), 0), 4), dtype=torch.float64, device=v.device)
+        stat = torch.empty((B, K, 2), dtype=torch.float64, device=v.device)
+        count = torch.empty((B, K, 4 + max(min(NB, 4), 0)), dtype=torch.int32, device=v.device)
+        self._check(self.lib.ev_modulation(self.h, v.data_ptr(), _ptr(mask), _ptr(ln), B, K, F, float(nu0), float(dnu), int(NM), int(min_run),
+                                           float(min_cycles), ba.ctypes.data if NB else None, NB, spec.data_ptr(), weight.data_ptr(),
+                                           peak.data_ptr() if NB else None, stat.data_ptr(), count.data_ptr(), _stream_ptr()), "ev_modulation")
+        return spec, weight, peak, stat, count
 
     def pyin_observe(self, x, lengths, frame_length: int, hop_length: int, tau_min: int, tau_max: int, sr: float, fmin: float,
                      bins_per_octave: int, n_bins: int, w, boltzmann: float = 2.0, no_trough_prob: float = 0.01, out=None):

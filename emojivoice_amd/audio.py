@@ -1620,3 +1620,197 @@ def voice_functionals(pitch, vq, n_frames=None, fm=None, pt=None, hm=None, sr: i
                        "voiced_mean_s": fn["run_mean"][:, j] / rate, "voiced_sd_s": fn["run_sd"][:, j] / rate,
                        "unvoiced_mean_s": fn["gap_mean"][:, j] / rate, "unvoiced_sd_s": fn["gap_sd"][:, j] / rate}
     return out
+
+
+MODULATION_MAX_FREQUENCIES = 128                               # ``ev_modulation``'s grid limit
+MODULATION_MIN_RUN_S = 0.2                                     # runs of valid frames shorter than this are not analysed (17 frames at hop 256)
+MODULATION_MIN_CYCLES = 2.0                                    # a run speaks for a frequency when it holds at least two cycles of it
+MODULATION_TREMOR_HZ = (4.0, 12.0)                             # tremor and vibrato of f0 and of loudness
+MODULATION_RHYTHM_HZ = (2.0, 8.0)                              # the syllable rate of the loudness contour
+MODULATION_COUNTS = ("valid", "dropped", "runs", "frames")
+
+
+def _modulation_grid(frame_rate: float, fmin_hz: float, fmax_hz: float, step_hz: float) -> Tuple[float, float, int]:
+    vals = (frame_rate, fmin_hz, fmax_hz, step_hz)
+    if not all(math.isfinite(float(v)) and float(v) > 0.0 for v in vals) or fmax_hz < fmin_hz:
+        raise ValueError(f"modulation: frame_rate={frame_rate}, fmin_hz={fmin_hz}, fmax_hz={fmax_hz}, step_hz={step_hz} must be finite and greater "
+                         "than 0 with fmin_hz <= fmax_hz")
+    NM = int(math.floor((float(fmax_hz) - float(fmin_hz)) / float(step_hz) + 1e-9)) + 1
+    if NM > MODULATION_MAX_FREQUENCIES:
+        raise ValueError(f"modulation: {fmin_hz} .. {fmax_hz} Hz in steps of {step_hz} Hz are {NM} frequencies, at most {MODULATION_MAX_FREQUENCIES} "
+                         "are taken")
+    nu0, dnu = float(fmin_hz) / float(frame_rate), float(step_hz) / float(frame_rate)
+    if nu0 + (NM - 1) * dnu > 0.5:
+        raise ValueError(f"modulation: the grid ends at {fmin_hz + (NM - 1) * step_hz} Hz, over half the frame rate of {frame_rate} Hz")
+    return nu0, dnu, NM
+
+
+def modulation_grid(sr, hop_length, fmin_hz: float = 1.0, fmax_hz: float = 16.0, step_hz: float = 0.125) -> Tuple[float, float, int]:
+    """(nu0, dnu, NM) of ``ev_modulation`` for contours at ``sr`` / ``hop_length`` frames per second: the frequencies fmin_hz + j step_hz up
+    to fmax_hz, in cycles per frame.  ValueError for more than 128 of them or for a grid over half the frame rate.  At 0.125 Hz a sinusoid
+    between two grid points loses under 1 % of its extent to the parabola through the log powers; at 0.25 Hz and 6 s it loses 18 %."""
+    if not (float(sr) > 0 and float(hop_length) > 0):
+        raise ValueError(f"modulation_grid: sr={sr} and hop_length={hop_length} must be greater than 0")
+    return _modulation_grid(float(sr) / float(hop_length), fmin_hz, fmax_hz, step_hz)
+
+
+def modulation_bands(bands_hz, fmin_hz: float, step_hz: float, NM: int):
+    """The index ranges [j_lo, j_hi) of the grid points inside each closed band (lo_hz, hi_hz); ValueError for more than four bands or for a
+    band without a grid point."""
+    bands = [tuple(float(x) for x in b) for b in bands_hz]
+    if len(bands) > 4:
+        raise ValueError(f"modulation: {len(bands)} bands given, at most 4 are taken")
+    out = []
+    for lo, hi in bands:
+        j_lo = max(int(math.ceil((lo - fmin_hz) / step_hz - 1e-9)), 0)
+        j_hi = min(int(math.floor((hi - fmin_hz) / step_hz + 1e-9)) + 1, NM)
+        if not (math.isfinite(lo) and math.isfinite(hi)) or j_lo >= j_hi:
+            raise ValueError(f"modulation: the band {lo} .. {hi} Hz holds no frequency of the grid")
+        out.append((j_lo, j_hi))
+    return out
+
+
+def modulation_arguments(values, mask=None, lengths=None, frame_rate: float = 22050.0 / 256.0, bands_hz=(), fmin_hz: float = 1.0,
+                         fmax_hz: float = 16.0, step_hz: float = 0.125, min_run: Optional[int] = None, min_cycles: float = MODULATION_MIN_CYCLES):
+    """ValueError unless ``modulation`` takes the arguments (everything that needs no device): ``functionals``' rules for ``values``, ``mask``
+    and ``lengths``, a grid ``modulation_grid`` accepts, at most four bands that each hold a grid point, 3 <= min_run <= F (None: the frames
+    of MODULATION_MIN_RUN_S, inside those bounds), min_cycles finite and at least 0.  Returns ((B, K, F), (nu0, dnu, NM), the bands as index
+    pairs, min_run)."""
+    try:
+        shape, _ = functional_arguments(values, mask, lengths, ())
+    except ValueError as e:
+        raise ValueError(str(e).replace("functionals:", "modulation:")) from None
+    grid = _modulation_grid(frame_rate, fmin_hz, fmax_hz, step_hz)
+    bands = modulation_bands(bands_hz, float(fmin_hz), float(step_hz), grid[2])
+    F = shape[2]
+    if F < 3:
+        raise ValueError(f"modulation: F={F} frames, at least 3 are needed")
+    if min_run is None:
+        min_run = min(max(int(math.ceil(MODULATION_MIN_RUN_S * float(frame_rate))), 3), F)
+    if not 3 <= int(min_run) <= F:
+        raise ValueError(f"modulation: min_run={min_run} outside 3 <= min_run <= F = {F}")
+    if not (math.isfinite(float(min_cycles)) and float(min_cycles) >= 0.0):
+        raise ValueError(f"modulation: min_cycles={min_cycles} must be finite and at least 0")
+    return shape, grid, bands, int(min_run)
+
+
+@torch.inference_mode()
+def modulation(values, mask=None, lengths=None, frame_rate: float = 22050.0 / 256.0, bands_hz=(), fmin_hz: float = 1.0, fmax_hz: float = 16.0,
+               step_hz: float = 0.125, min_run: Optional[int] = None, min_cycles: float = MODULATION_MIN_CYCLES):
+    """The modulation spectrum of every contour on the device (``ev_modulation``: one launch per call, a workgroup per contour; no torch
+    fallback): how strongly the contour oscillates at each of the frequencies fmin_hz + j step_hz, and the strongest local peak of up to four
+    bands.  ``values``, ``mask`` and ``lengths`` follow ``functionals``' rules; ``frame_rate``: frames per second.  Every run of at least
+    ``min_run`` valid frames is detrended by its own line, Hann-windowed and analysed on its own: nothing crosses a gap.  A run counts at a
+    frequency when it holds ``min_cycles`` cycles of it; runs pool by their lengths.  -> {"frequencies_hz" (NM,) float64; "spectrum" (B, K,
+    NM) float64: half the squared amplitude of the oscillation at each frequency, in the contour's units squared, 0 where no run counts;
+    "weight" (B, K, NM) int32: the frames behind each; per band (B, K, NBAND): "rate_hz", the interpolated frequency of the peak, "extent",
+    its amplitude in the contour's units, "prominence_db", 10 log10 of its power over the band's mean, "band_mean", NaN where the band has
+    no local peak, and "peak_index" int32, -1 there; "residual_variance" and "slope" (per second) (B, K): what the lines leave and their
+    length-weighted mean, NaN without an analysed run; "valid", "dropped", "runs", "frames" (B, K) int32: the valid frames, the non-finite
+    ones under the mask, the analysed runs and their frames}."""
+    (B, K, F), (nu0, dnu, NM), bands, min_run = modulation_arguments(values, mask, lengths, frame_rate, bands_hz, fmin_hz, fmax_hz, step_hz, min_run,
+                                                                     min_cycles)
+    if not values.is_cuda:
+        raise EvLibraryError("modulation runs on a ROCm GPU only (no CPU fallback): move values to the GPU")
+    v = values.reshape(B, K, F).to(torch.float64)
+    m = None
+    if mask is not None:
+        m = torch.as_tensor(mask, device=values.device)
+        m = (m != 0).expand(values.shape).reshape(B, K, F).to(torch.uint8).contiguous()
+    spec, weight, peak, stat, count = _trim_engine(values.device).modulation(v, m, lengths, nu0, dnu, NM, min_run, float(min_cycles), bands)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=v.device)
+    idx = count[..., 4:]
+    has = idx >= 0
+    ran = count[..., 2] > 0
+    out = {"frequencies_hz": torch.from_numpy(float(fmin_hz) + np.arange(NM, dtype=np.float64) * float(step_hz)).to(v.device),
+           "spectrum": spec, "weight": weight,
+           "rate_hz": torch.where(has, peak[..., 0] * float(frame_rate), nan), "extent": torch.where(has, peak[..., 1], nan),
+           "band_mean": torch.where(has, peak[..., 2], nan),
+           "prominence_db": torch.where(has, 10.0 * torch.log10(torch.where(has, peak[..., 3], torch.ones_like(peak[..., 3]))), nan),
+           "peak_index": idx, "residual_variance": torch.where(ran, stat[..., 0], nan),
+           "slope": torch.where(ran, stat[..., 1] * float(frame_rate), nan)}
+    out.update({k: count[..., i] for i, k in enumerate(MODULATION_COUNTS)})
+    return out
+
+
+VOICE_MODULATION_FIGURES = ("tremor_rate_hz", "tremor_extent_st", "tremor_prominence_db", "f0_residual_sd_st", "loudness_tremor_rate_hz",
+                            "loudness_tremor_depth", "rhythm_rate_hz", "rhythm_depth", "rhythm_prominence_db")
+
+
+@torch.inference_mode()
+def voice_modulation(pitch, au, n_frames=None, sr: int = 22050, hop_length: int = 256, min_run: Optional[int] = None,
+                     min_cycles: float = MODULATION_MIN_CYCLES, fmin_hz: float = 1.0, fmax_hz: float = 16.0, step_hz: float = 0.125):
+    """Tremor and rhythm of a voice in ONE ``modulation`` call over two contours: ``pitch`` (the dict of ``pitch_yin`` / ``pitch_pyin``) and
+    ``au`` (of ``auditory``), (B, F) at the same hop on the GPU; ``n_frames`` (B,): the frames of each row (None: F).
+      "f0_semitones"   12 log2(f0 / 27.5) under the voicing (``voice_functionals``' contour): the tremor band is 4-12 Hz, the extent in semitones
+      "loudness"       over the live frames inside the row: the rhythm band is 2-8 Hz; a depth is the amplitude over the mean loudness
+    -> {figure: (B,) float64 for the VOICE_MODULATION_FIGURES, NaN where the band has no peak (or no run was analysed); "f0_semitones" and
+    "loudness": the two contours' rows of ``modulation``'s result; "frequencies_hz"}."""
+    f0 = torch.as_tensor(pitch["f0"])
+    if f0.dim() == 1:
+        raise ValueError("voice_modulation: (B, F) contours expected (add the batch axis to a single row)")
+    B, F = f0.shape
+    dev = f0.device
+    t, inside, n = _inside({"f0": f0, "voiced": torch.as_tensor(pitch["voiced"], dtype=torch.bool, device=dev)}, n_frames, "voice_modulation")
+    use = t["voiced"] & inside
+    st = 12.0 * torch.log2(torch.where(use, f0.to(torch.float64), torch.full((), SEMITONE_REFERENCE_HZ, dtype=torch.float64, device=dev))
+                           / SEMITONE_REFERENCE_HZ)
+    ta = _auditory_coerced(au, t["voiced"], dev)
+    if tuple(ta["loudness"].shape) != (B, F):
+        raise ValueError(f"voice_modulation: the loudness {tuple(ta['loudness'].shape)} and the pitch {(B, F)} are not at the same frames")
+    live = inside & ta["live"]
+    md = modulation(torch.stack([st, ta["loudness"]], dim=1), torch.stack([use, live], dim=1), n, float(sr) / float(hop_length),
+                    (MODULATION_TREMOR_HZ, MODULATION_RHYTHM_HZ), fmin_hz, fmax_hz, step_hz, min_run, min_cycles)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    cnt = live.sum(dim=1)
+    mean_l = torch.where(cnt > 0, (ta["loudness"] * live).sum(dim=1) / cnt.clamp(min=1), nan)
+    mean_l = torch.where(mean_l > 0, mean_l, nan)
+    out = {"tremor_rate_hz": md["rate_hz"][:, 0, 0], "tremor_extent_st": md["extent"][:, 0, 0], "tremor_prominence_db": md["prominence_db"][:, 0, 0],
+           "f0_residual_sd_st": torch.sqrt(md["residual_variance"][:, 0]),
+           "loudness_tremor_rate_hz": md["rate_hz"][:, 1, 0], "loudness_tremor_depth": md["extent"][:, 1, 0] / mean_l,
+           "rhythm_rate_hz": md["rate_hz"][:, 1, 1], "rhythm_depth": md["extent"][:, 1, 1] / mean_l, "rhythm_prominence_db": md["prominence_db"][:, 1, 1]}
+    for j, name in enumerate(("f0_semitones", "loudness")):
+        out[name] = {k: v[:, j] for k, v in md.items() if k != "frequencies_hz"}
+    out["frequencies_hz"] = md["frequencies_hz"]
+    return out
+
+
+MS_DISTANCE_GRID_HZ = (1.0, 32.0, 0.25)                        # fmin, fmax, step of ``modulation_spectrum_distance``: 125 frequencies
+
+
+@torch.inference_mode()
+def cepstral_modulation_distance(cep_a, cep_b, len_a=None, len_b=None, sr: int = 22050, hop_length: int = 256, min_run: Optional[int] = None,
+                                 min_cycles: float = MODULATION_MIN_CYCLES):
+    """``modulation_spectrum_distance`` of two stacks of trajectories (B, K, Ta) and (B, K, Tb) that are already cepstra (or any K contours per
+    row): two ``modulation`` calls and the comparison in dB."""
+    if cep_a.dim() != 3 or cep_b.dim() != 3 or cep_a.shape[:2] != cep_b.shape[:2]:
+        raise ValueError(f"modulation_spectrum_distance: two stacks (B, K, T) of one batch expected, got {tuple(cep_a.shape)} and {tuple(cep_b.shape)}")
+    fmin, fmax, step = MS_DISTANCE_GRID_HZ
+    rate = float(sr) / float(hop_length)
+    sp = []
+    for cep, ln in ((cep_a, len_a), (cep_b, len_b)):
+        md = modulation(cep, None, ln, rate, (), fmin, fmax, step, min_run, min_cycles)
+        sp.append((md["spectrum"], md["weight"]))
+    (pa, wa), (pb, wb) = sp
+    both = (wa > 0) & (wb > 0) & (pa > 0) & (pb > 0)
+    one = torch.ones_like(pa)
+    d = torch.where(both, 10.0 * torch.log10(torch.where(both, pb, one)) - 10.0 * torch.log10(torch.where(both, pa, one)), torch.zeros_like(pa))
+    pairs = both.sum(dim=(1, 2))
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=pa.device)
+    cnt = pairs.clamp(min=1).to(torch.float64)
+    return {"ms_distortion_db": torch.where(pairs > 0, torch.sqrt((d * d).sum(dim=(1, 2)) / cnt), nan),
+            "ms_shift_db": torch.where(pairs > 0, d.sum(dim=(1, 2)) / cnt, nan), "pairs": pairs}
+
+
+@torch.inference_mode()
+def modulation_spectrum_distance(mel_a, mel_b, len_a=None, len_b=None, n_coeffs: int = 13, sr: int = 22050, hop_length: int = 256,
+                                 min_run: Optional[int] = None, min_cycles: float = MODULATION_MIN_CYCLES):
+    """How much trajectory detail the second of two log-mels (B, n_mels, Ta) and (B, n_mels, Tb) lacks (Takamichi et al. 2016): the modulation
+    spectra of ``mel_cepstrum``'s coefficients 1 .. ``n_coeffs`` over 1-32 Hz at 0.25 Hz, compared in dB.  The spectrum lives on a fixed grid
+    and does not move with a shift in time, so the two need no alignment and may differ in length (recorded against synthesised).
+    ``len_a`` / ``len_b`` (B,): frames per row (None: all).  -> {"ms_distortion_db" (B,) float64: the rms over (coefficient, frequency resolved
+    on both sides, with a power above 0) of 10 log10 Pm_b - 10 log10 Pm_a; "ms_shift_db": their signed mean, negative when the second input is
+    the smoother; "pairs" (B,) int64: the terms behind them; both figures NaN where no frequency is resolved on both sides}."""
+    if mel_a.dim() != 3 or mel_b.dim() != 3 or mel_a.shape[:2] != mel_b.shape[:2]:
+        raise ValueError(f"modulation_spectrum_distance: two log-mels (B, n_mels, T) of one batch expected, got {tuple(mel_a.shape)} and {tuple(mel_b.shape)}")
+    return cepstral_modulation_distance(mel_cepstrum(mel_a, n_coeffs), mel_cepstrum(mel_b, n_coeffs), len_a, len_b, sr, hop_length, min_run, min_cycles)

@@ -25,6 +25,8 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt --functionals                        # ... and per contour mean, sd, percentiles, slopes and peak rate, and the voiced / unvoiced segment lengths (the eGeMAPS functionals)
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --harmonics                                 # ... and, per pair, the harmonic differences of both sides and their differences
     python -m emojivoice_amd.cli --voice_report clean/filelist.txt --auditory --functionals             # ... and loudness, spectral flux, MFCC 1-4 and the equivalent level, per file and per speaker, with their functionals (loudness peaks per second among them)
+    python -m emojivoice_amd.cli --voice_report clean/filelist.txt --modulation                         # ... and rate, extent and prominence of the tremor / vibrato of f0 and of the loudness and of the syllable rhythm, from the modulation spectra of the two contours
+    python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --modulation                                # ... the same of both sides with their differences, and the modulation-spectrum distance of the mel-cepstral trajectories (over-smoothing)
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --auditory                                  # ... and, per pair, loudness, spectral flux, MFCC 1-4 and the level of both sides and their differences
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --voice_quality                             # ... and, per pair, the voice-quality figures of both sides and their differences
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
@@ -84,6 +86,9 @@ def validate_args(args):
             assert any(getattr(args, h, None) for h in homes), f"--{family.pairs_flag} is an option of " + " and of ".join("--" + h for h in homes)
     if getattr(args, "functionals", False):
         assert getattr(args, "voice_report", None), "--functionals is an option of --voice_report"
+    if getattr(args, "modulation", False):
+        assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), \
+            "--modulation is an option of --voice_report and of --evaluate_pairs"
     if getattr(args, "track_formants", False):
         assert (getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None)) and (getattr(args, "formants", False) or getattr(args, "harmonics", False)), \
             "--track_formants is an option of --formants and of --harmonics under --voice_report and --evaluate_pairs"
@@ -627,6 +632,33 @@ def functional_means(rows):
             "segments": {k: mean([r["segments"][k] for r in rows]) for k in SEGMENT_REPORT_KEYS}}
 
 
+def modulation_rows(vm):
+    """audio.voice_modulation's figures as one host record per row: {"modulation": {figure: float or None}}, the keys of
+    audio.VOICE_MODULATION_FIGURES; None where there is no value (NaN).  Everything crosses to the host in one copy."""
+    from . import audio
+
+    table = torch.stack([vm[k] for k in audio.VOICE_MODULATION_FIGURES]).cpu()                   # (figures, rows)
+    val = lambda x: None if math.isnan(float(x)) else float(x)
+    return [{"modulation": {k: val(table[j, r]) for j, k in enumerate(audio.VOICE_MODULATION_FIGURES)}} for r in range(table.shape[1])]
+
+
+def modulation_means(rows):
+    """The --modulation block of some rows of modulation_rows together: per figure {"mean": the PLAIN mean over the files that have one (None
+    without one), "files": how many those were}, as --functionals does it: a rate and an extent describe one utterance."""
+    def mean(vals):
+        vals = [v for v in vals if v is not None]
+        return {"mean": math.fsum(vals) / len(vals) if vals else None, "files": len(vals)}
+
+    figures = list(rows[0]["modulation"]) if rows else []
+    return {"modulation": {k: mean([r["modulation"][k] for r in rows]) for k in figures}}
+
+
+def voice_modulation_of(audio, pitch, got, sig, sr, hop, lens, n_frames):
+    """audio.voice_modulation of a batch, on the auditory frames of --auditory where that ran (``got``), else on its own."""
+    au = got["auditory"] if "auditory" in got else audio.auditory(sig, sr, hop_length=hop, lengths=lens)
+    return modulation_rows(audio.voice_modulation(pitch, au, n_frames, sr=sr, hop_length=hop))
+
+
 @torch.inference_mode()
 def voice_report(args, device):
     """--voice_report FILELIST (the filelist format of --prosody_report): every file is loaded with audio.load_audio(path, 22050), measured by
@@ -659,10 +691,17 @@ def voice_report(args, device):
     above runs over (audio.voice_functionals: one device call per batch; slopes in units per second; null where there is no value), and
     "segments": voiced segments per second and the mean and sd length in seconds of the voiced and of the unvoiced segments.  Per speaker and
     overall every value becomes {"mean", "files"}: the PLAIN mean over the files that have the value and how many those were; percentiles do
-    not pool from sums, and an eGeMAPS vector (Eyben et al. 2016) describes one utterance, so nothing here is pooled over frames."""
+    not pool from sums, and an eGeMAPS vector (Eyben et al. 2016) describes one utterance, so nothing here is pooled over frames.
+    --modulation adds per file "modulation": the rate in Hz, the extent in semitones and the prominence in dB of the strongest 4-12 Hz
+    oscillation of f0 over the voiced runs (tremor, vibrato), the sd of what the runs' lines leave, the same band of the loudness, and the
+    rate, depth (relative to the mean loudness) and prominence of its strongest 2-8 Hz oscillation (the syllable rhythm)
+    (audio.voice_modulation: one device call per batch; null where no run is long enough or the band has no peak).  Per speaker and overall
+    every figure becomes {"mean", "files"} like the functionals: the figures are per utterance, not per frame, so they do not go through the
+    figure families."""
     from . import audio
 
     want_func = getattr(args, "functionals", False)
+    want_mod = getattr(args, "modulation", False)
     families = enabled_families(args, "report_flag")
     files, pooled = [], {}
     for chunk, batch, lens in filelist_batches(args.voice_report, args.batch_size, PROSODY_SR, device):
@@ -674,6 +713,8 @@ def voice_report(args, device):
             rows["functionals"] = functional_rows(audio.voice_functionals(pitch, got["voice"], n_frames, fm=got.get("formants"), pt=got.get("perturbation"),
                                                                           hm=got.get("harmonics"), sr=PROSODY_SR, hop_length=PROSODY_HOP,
                                                                           harmonic_fm=got.get("harmonic_fm"), au=got.get("auditory")))
+        if want_mod:
+            rows["modulation"] = voice_modulation_of(audio, pitch, got, batch, PROSODY_SR, PROSODY_HOP, lens, n_frames)
         for r, (wav, spk, _) in enumerate(chunk):
             spk = spk if spk is not None else "0"
             rec = {"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r],
@@ -682,6 +723,8 @@ def voice_report(args, device):
                 rec.update(family_means([rows[f.block][r]], f))
             if want_func:
                 rec.update(rows["functionals"][r])
+            if want_mod:
+                rec.update(rows["modulation"][r])
             files.append(rec)
             acc = pooled.setdefault(spk, {"files": 0, **{k: [] for k in rows}})
             acc["files"] += 1
@@ -694,6 +737,8 @@ def voice_report(args, device):
             out.update(family_means([row for a in accs for row in a[f.block]], f))
         if want_func:
             out.update(functional_means([row for a in accs for row in a["functionals"]]))
+        if want_mod:
+            out.update(modulation_means([row for a in accs for row in a["modulation"]]))
         return out
 
     rep = {"sample_rate": PROSODY_SR, "hop_length": PROSODY_HOP, "files": files, "speakers": {k: pool([v]) for k, v in pooled.items()},
@@ -925,8 +970,15 @@ def evaluate_pairs(args, device):
     --auditory adds "auditory" in the same form: loudness, the spectral flux, MFCC 1-4, their voiced / unvoiced variants and equivalent_level_db
     (audio.auditory, audio.auditory_statistics) of each side and their differences: a duller, flatter or quieter rendering of the same sentence.
     --track_formants (with --formants or --harmonics): the formants of both are audio.formant_tracks' (five candidates per frame tracked to F1-F3);
-    the report gains a top-level "formant_tracking" object with the parameters and keeps every other key."""
+    the report gains a top-level "formant_tracking" object with the parameters and keeps every other key.
+    --modulation adds per pair "modulation": {"recorded", "synthesised", "delta"} over audio.voice_modulation's figures of each side (tremor
+    and rhythm: rates, extents, prominences) and "ms_distortion_db" / "ms_shift_db", the distance between the modulation spectra of the two
+    sides' mel-cepstral trajectories (audio.cepstral_modulation_distance: no alignment; a negative shift says the synthesised side moves
+    less, i.e. is over-smoothed); per speaker and overall the mean and mean absolute difference per figure and the plain means of the two
+    distances over the pairs that have them."""
     from . import audio
+
+    want_mod = getattr(args, "modulation", False)
 
     entries = parse_pairs(args.evaluate_pairs)
     if not entries:
@@ -949,6 +1001,8 @@ def evaluate_pairs(args, device):
         for f in families:
             st = f.measure(sig, sr, hop, lens if f.block == "voice" else clipped, pitch["voiced"], frames, got)
             pitch[f.block] = [{k: v for k, v in family_means([row], f).items() if k in f.figures} for row in family_rows(st, f)]
+        if want_mod:
+            pitch["modulation"] = [row["modulation"] for row in voice_modulation_of(audio, pitch, got, sig, sr, hop, clipped, frames)]
         return cep, frames, pitch
 
     for b0 in range(0, len(entries), args.batch_size):
@@ -970,6 +1024,9 @@ def evaluate_pairs(args, device):
         mcd = audio.mcd_from_cost(al["cost"], al["steps"]).cpu()
         f0 = audio.f0_errors(pitch_a["f0"], pitch_a["voiced"], pitch_b["f0"], pitch_b["voiced"], al["path"], al["steps"])
         steps, verr, nv = al["steps"].cpu(), f0["voicing_error"].cpu(), f0["voiced_pairs"].cpu()
+        if want_mod:
+            msd = audio.cepstral_modulation_distance(cep_a, cep_b, fr_a, fr_b, sr, hop)
+            msd = torch.stack([msd["ms_distortion_db"], msd["ms_shift_db"]]).cpu()
         for r, (rec, syn, spk, _, _) in enumerate(chunk):
             records.append({"recorded": rec, "synthesised": syn, "speaker": spk, "mcd_db": float(mcd[r]), "f0_rmse_cents": f0["rmse_cents"][r],
                             "voicing_error": float(verr[r]), "voiced_pairs": int(nv[r]), "frames_recorded": fr_a[r], "frames_synthesised": fr_b[r],
@@ -978,6 +1035,12 @@ def evaluate_pairs(args, device):
                 va, vb = pitch_a[f.block][r], pitch_b[f.block][r]
                 records[-1][f.block] = {"recorded": va, "synthesised": vb,
                                         "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va}}
+            if want_mod:
+                va, vb = pitch_a["modulation"][r], pitch_b["modulation"][r]
+                val = lambda x: None if math.isnan(float(x)) else float(x)
+                records[-1]["modulation"] = {"recorded": va, "synthesised": vb,
+                                             "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va},
+                                             "ms_distortion_db": val(msd[0, r]), "ms_shift_db": val(msd[1, r])}
 
     def means(recs):
         out = evaluation_means(recs)
@@ -986,6 +1049,15 @@ def evaluate_pairs(args, device):
             for k in f.figures:
                 d = [r[f.block]["delta"][k] for r in recs if r[f.block]["delta"][k] is not None]
                 out[f.block][k] = {"mean_delta": math.fsum(d) / len(d) if d else None, "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
+        if want_mod:
+            out["modulation"] = {}
+            for k in audio.VOICE_MODULATION_FIGURES:
+                d = [r["modulation"]["delta"][k] for r in recs if r["modulation"]["delta"][k] is not None]
+                out["modulation"][k] = {"mean_delta": math.fsum(d) / len(d) if d else None,
+                                        "mean_abs_delta": math.fsum(abs(v) for v in d) / len(d) if d else None}
+            for k in ("ms_distortion_db", "ms_shift_db"):
+                d = [r["modulation"][k] for r in recs if r["modulation"][k] is not None]
+                out["modulation"][k] = {"mean": math.fsum(d) / len(d) if d else None, "pairs": len(d)}
         return out
 
     by_spk = {}
@@ -1089,6 +1161,12 @@ def cli(argv=None):
     p.add_argument("--track_formants", action="store_true", help="with --formants or --harmonics under --voice_report or --evaluate_pairs: analyse five "
                    "candidates per frame and track F1-F3 through them on the device (a Viterbi pass per file, Praat's Formant: Track) instead of taking "
                    "the three lowest; adds tracked_frames and track_segments to the formants' keys and \"formant_tracking\" (the parameters) to the report")
+    p.add_argument("--modulation", action="store_true", help="--voice_report: add \"modulation\" per file: rate (Hz), extent (semitones) and prominence "
+                   "(dB) of the strongest 4-12 Hz oscillation of f0 (tremor, vibrato) and of the loudness, and rate, depth and prominence of the "
+                   "loudness contour's strongest 2-8 Hz oscillation (the syllable rhythm), from the modulation spectra of the two contours (one device "
+                   "call per batch); per speaker and overall the mean over the files that have each figure.  --evaluate_pairs: the same figures of "
+                   "both sides with their differences, and ms_distortion_db / ms_shift_db, the distance between the modulation spectra of the two "
+                   "sides' mel-cepstral trajectories (negative shift: the synthesised side is over-smoothed)")
     p.add_argument("--functionals", action="store_true", help="--voice_report: add \"functionals\" per file: mean, sd, the 20th / 50th / 80th percentile and "
                    "their range, mean and sd of the rising and of the falling slopes per second and the peaks per second of every contour the report "
                    "measures (f0 in semitones from 27.5 Hz, the voice-quality figures, and those of --formants / --perturbation / --harmonics), and "

@@ -867,4 +867,46 @@ int ev_formant_track(ev_handle* h, const double* d_formant, const int32_t* d_cou
     return 0;
 }
 
+// Modulation spectra of contours: per contour the pooled power on a grid of modulation frequencies and the peak of up to four bands
+// (modulation_kernel, ev_analysis_kernels.h; the definition: include/emojivoice.h).  No load step, no tables, no arena: one launch, a workgroup
+// per contour, whose arguments carry the grid and the bands.
+int ev_modulation(ev_handle* h, const double* d_v, const uint8_t* d_mask, const int32_t* d_len, int B, int K, int F, double nu0, double dnu, int NM,
+                  int min_run, double min_cycles, const int32_t* band, int NBAND, double* d_spec, int32_t* d_weight, double* d_peak, double* d_stat,
+                  int32_t* d_count, void* stream) {
+    if (enter(h)) return 1;
+    if (check_batch(h, __func__, B)) return 1;
+    if (K < 1 || K > 65535) return fail(h, "ev_modulation: K=%d outside 1 <= K <= 65535", K);
+    if (F < 1 || F > 4096) return fail(h, "ev_modulation: F=%d outside 1 <= F <= 4096", F);
+    if (NM < 1 || NM > 128) return fail(h, "ev_modulation: NM=%d outside 1 <= NM <= 128", NM);
+    if (!std::isfinite(nu0) || !(nu0 > 0.0)) return fail(h, "ev_modulation: nu0=%g must be finite and greater than 0", nu0);
+    if (!std::isfinite(dnu) || !(dnu > 0.0)) return fail(h, "ev_modulation: dnu=%g must be finite and greater than 0", dnu);
+    if (!(nu0 + (double)(NM - 1) * dnu <= 0.5))
+        return fail(h, "ev_modulation: the grid ends at nu0 + (NM - 1) dnu = %g cycles per frame, over the limit 0.5", nu0 + (double)(NM - 1) * dnu);
+    if (min_run < 3 || min_run > F) return fail(h, "ev_modulation: min_run=%d outside 3 <= min_run <= F = %d", min_run, F);
+    if (!std::isfinite(min_cycles) || !(min_cycles >= 0.0)) return fail(h, "ev_modulation: min_cycles=%g must be finite and at least 0", min_cycles);
+    if (NBAND < 0 || NBAND > 4) return fail(h, "ev_modulation: NBAND=%d outside 0 <= NBAND <= 4", NBAND);
+    if (NBAND > 0 && !band) return fail(h, "ev_modulation: band must be non-null (HOST) when NBAND > 0");
+    for (int i = 0; i < NBAND; ++i)
+        if (band[2 * i] < 0 || band[2 * i] >= band[2 * i + 1] || band[2 * i + 1] > NM)
+            return fail(h, "ev_modulation: band[%d] = [%d, %d) outside 0 <= j_lo < j_hi <= NM = %d", i, band[2 * i], band[2 * i + 1], NM);
+    if (!d_v) return fail(h, "ev_modulation: d_v must be non-null");
+    if (!d_spec) return fail(h, "ev_modulation: d_spec must be non-null");
+    if (!d_weight) return fail(h, "ev_modulation: d_weight must be non-null");
+    if (NBAND > 0 && !d_peak) return fail(h, "ev_modulation: d_peak must be non-null when NBAND > 0");
+    if (!d_stat) return fail(h, "ev_modulation: d_stat must be non-null");
+    if (!d_count) return fail(h, "ev_modulation: d_count must be non-null");
+    h->stream = (hipStream_t)stream;
+    ModParams p{};
+    p.v = d_v; p.mask = d_mask; p.len = d_len; p.spec = d_spec; p.weight = d_weight; p.peak = NBAND ? d_peak : nullptr; p.stat = d_stat; p.count = d_count;
+    p.K = K; p.F = F; p.NM = NM; p.NBAND = NBAND; p.min_run = min_run;
+    p.MR = std::max(2, round_up((F + 1) / 4, 2));                                    // the most runs of >= 3 frames, each a frame apart, that F frames hold
+    p.nu0 = nu0; p.dnu = dnu; p.min_cycles = min_cycles;
+    for (int i = 0; i < 2 * NBAND; ++i) p.band[i] = band[i];
+    // wr (8 B a frame), the runs' window sums and packed bounds (12 B a run), the pooled spectrum and weights (128 x 12 B), 24 words: 45.6 KiB at 4096
+    const size_t smem = ((size_t)F + (F & 1) + p.MR + 128) * sizeof(double) + ((size_t)p.MR + 128 + 24) * sizeof(int);
+    launch<modulation_kernel>(h->device, dim3((unsigned)K, (unsigned)B), dim3(256), smem, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 }  // extern "C"

@@ -2560,6 +2560,223 @@ __global__ __launch_bounds__(256) void functionals_kernel(const FuncParams p) {
 }
 
 // ---------------------------------------------------------------------------
+// Modulation spectra of contours (ev_modulation): per contour (b, k) of F frames the power of its oscillations on a grid of NM modulation
+// frequencies, pooled over the runs of valid frames that are long enough, and the strongest local peak of up to four bands (the definition:
+// include/emojivoice.h).  All float64, contraction OFF (STOI_EXACT), no atomics, no scratch.  ONE WORKGROUP of 256 threads PER CONTOUR,
+// everything in dynamic LDS: wr (F doubles: the value, NaN where the frame is not valid, then w_t r_t in place), sw (MR doubles, a run's window
+// sum), the pooled spectrum (128 doubles), the runs as start | length << 16 (MR words), the pooled weights (128 words) and 24 words of hand-over,
+// MR = (F + 1) / 4 rounded up to even being the most runs of at least 3 frames that F frames hold: 45.6 KiB at F = 4096.
+//   PHASE A  (1) one coalesced read: wr[f] = the value or NaN, the counts of valid and dropped frames.  (2) tiles of 256 frames: functionals_kernel's
+//            inclusive max-scan of "a run starts here" carries the start to the run's last frame, whose thread knows the length; the runs of at
+//            least min_run frames are appended to the table in ascending order through a ballot per wave and the waves' counts.  (3) WAVE 0 alone
+//            takes the runs in ascending order, frame t of a run in lane t mod 64: the mean and the slope, then r_t, the window, wr = w_t r_t in
+//            place and the sums of w and of r^2 (an xor tree each); it also pools the two statistics.  Phase B dwarfs this: three waves idle here.
+//   PHASE B  thread (j, c) = (unit >> 2, unit & 3) of 4 NM units, 256 a pass: over the runs in ascending order the chain c of xr and xi (frames
+//            t = c mod 4 ascending, a rounded product and a rounded sum each), the four chains of a j joined through shuffles inside their
+//            quad of lanes, P, and the pooled sum.  A wave reads FOUR addresses of wr per step (16 j x 4 chains: four adjacent doubles, distinct
+//            banks, each a broadcast to 16 lanes), so LDS traffic is one ds_read_b64 per two library calls; the float64 cospi / sinpi bound the
+//            kernel.
+//   PHASE C  wave x < NBAND takes band x: lane l scans j = j_lo + l, + 64 for candidates, a wave-wide (power, lowest j) maximum, lane 0 adds the
+//            band's mean in ascending j and forms the parabola.  Thread 0 writes the statistics and the counts.
+struct ModParams {
+    const double* v; const uint8_t* mask; const int32_t* len; double* spec; int32_t* weight; double* peak; double* stat; int32_t* count;
+    int K, F, NM, NBAND, min_run, MR;
+    double nu0, dnu, min_cycles;
+    int band[8];
+};
+
+__device__ __forceinline__ bool mod_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }     // (NaN compares false)
+
+__global__ __launch_bounds__(256) void modulation_kernel(const ModParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double mod_smem[];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, b = blockIdx.y;
+    const int F = p.F, NM = p.NM, NB = p.NBAND;
+    double* wr = mod_smem;                                              // [F + (F & 1)]
+    double* rsw = wr + F + (F & 1);                                     // [MR]
+    double* sp = rsw + p.MR;                                            // [128]
+    int* rs = (int*)(sp + 128);                                         // [MR]
+    int* wg = rs + p.MR;                                                // [128]
+    int* wm = wg + 128;                                                 // [2][4]: the waves' last scan values of a tile
+    int* wc = wm + 8;                                                   // [2][4]: the waves' analysed runs of a tile
+    int* tot = wc + 8;                                                  // [4][2]: the waves' valid and dropped frames
+    const size_t row = (size_t)b * p.K + blockIdx.x;
+    double* o_sp = p.spec + row * NM;
+    int32_t* o_wg = p.weight + row * NM;
+    double* o_pk = p.peak ? p.peak + row * NB * 4 : nullptr;
+    double* o_st = p.stat + row * 2;
+    int32_t* o_ct = p.count + row * (4 + NB);
+    const int n = p.len ? p.len[b] : F;
+    if (n < 0 || n > F) {                                               // a bad row is a row of zeros (uniform; before any barrier)
+        if (t < NM) { o_sp[t] = 0.0; o_wg[t] = 0; }
+        if (t < 4 * NB) o_pk[t] = 0.0;
+        if (t < 2) o_st[t] = 0.0;
+        if (t < 4 + NB) o_ct[t] = 0;
+        return;
+    }
+    // ---- phase A1: validity
+    const double* vr = p.v + row * F;
+    const uint8_t* mk = p.mask ? p.mask + row * F : nullptr;
+    int nvalid = 0, dropped = 0;
+    for (int f = t; f < n; f += 256) {
+        const bool on = !mk || mk[f] != 0;
+        const double x = on ? vr[f] : 0.0;
+        const bool valid = on && mod_finite(x);
+        nvalid += valid; dropped += on && !valid;
+        wr[f] = valid ? x : __builtin_nan("");
+    }
+    nvalid = func_wave_isum(nvalid); dropped = func_wave_isum(dropped);
+    if (lane == 0) { tot[2 * w] = nvalid; tot[2 * w + 1] = dropped; }
+    __syncthreads();
+    // ---- phase A2: the runs of at least min_run frames, in ascending order
+    int nruns = 0, car = -1;
+    for (int f0 = 0; f0 < n; f0 += 256) {
+        const int f = f0 + t;
+        const bool vi = f < n && mod_finite(wr[f]);
+        const bool vp = vi && f > 0 && mod_finite(wr[f - 1]), vn = vi && f + 1 < n && mod_finite(wr[f + 1]);
+        int mr = vi && !vp ? f : -1;                                    // a run starts at f
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {                              // (every shuffle is executed by the whole wave)
+            const int a = __shfl_up(mr, o, 64);
+            if (lane >= o) mr = max(mr, a);
+        }
+        const int slot = (f0 >> 8 & 1) * 4;
+        if (lane == 63) wm[slot + w] = mr;
+        __syncthreads();
+        mr = max(mr, car);
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            const int a = wm[slot + x];
+            if (x < w) mr = max(mr, a);
+            car = max(car, a);
+        }
+        const int l = vi && !vn ? f - mr + 1 : 0;                       // the thread of a run's last frame (mr >= 0 there) knows its length
+        const bool an = l >= p.min_run;
+        const unsigned long long bal = __ballot(an);
+        if (lane == 0) wc[slot + w] = __popcll(bal);
+        __syncthreads();
+        const int c0 = wc[slot], c1 = wc[slot + 1], c2 = wc[slot + 2], c3 = wc[slot + 3];
+        if (an) {                                                       // (at < MR: runs of >= 3 frames are at least one frame apart)
+            const int at = nruns + (w > 0 ? c0 : 0) + (w > 1 ? c1 : 0) + (w > 2 ? c2 : 0) + __popcll(bal & ((1ull << lane) - 1ull));
+            rs[at] = mr | l << 16;
+        }
+        nruns += c0 + c1 + c2 + c3;
+    }
+    __syncthreads();
+    // ---- phase A3: wave 0 detrends and windows every analysed run in place
+    double q_sum = 0.0, lb_sum = 0.0;
+    int aframes = 0;
+    if (w == 0) {
+        for (int r = 0; r < nruns; ++r) {
+            const int e = rs[r], s = e & 0xffff, l = e >> 16;
+            const double hl = (double)(l - 1) / 2.0, dl = (double)l;
+            double su = 0.0, sc = 0.0;
+            for (int i = lane; i < l; i += 64) {
+                const double u = wr[s + i], tc = (double)i - hl;
+                su = su + u;
+                sc = sc + tc * u;
+            }
+            su = formant_wave_sum(su); sc = formant_wave_sum(sc);
+            const long long li = l;
+            const double m = su / dl, bb = sc / ((double)(li * (li * li - 1)) / 12.0);
+            double sw = 0.0, s2 = 0.0;
+            for (int i = lane; i < l; i += 64) {
+                const double tc = (double)i - hl;
+                const double rr = (wr[s + i] - m) - bb * tc;
+                const double ww = 0.5 - 0.5 * cospi((double)(2 * i + 1) / dl);
+                sw = sw + ww;
+                s2 = s2 + rr * rr;
+                wr[s + i] = ww * rr;
+            }
+            sw = formant_wave_sum(sw); s2 = formant_wave_sum(s2);
+            if (lane == 0) rsw[r] = sw;
+            q_sum = q_sum + s2;
+            lb_sum = lb_sum + dl * bb;
+            aframes += l;
+        }
+    }
+    __syncthreads();
+    // ---- phase B: the spectra of the runs and their pooling
+    for (int u0 = 0; u0 < 4 * NM; u0 += 256) {                          // (uniform)
+        const int j = (u0 + t) >> 2, c = t & 3;
+        const bool act = j < NM;
+        const double nu = p.nu0 + (double)j * p.dnu;
+        double acc = 0.0;
+        int W = 0;
+        for (int r = 0; r < nruns; ++r) {
+            const int e = rs[r], s = e & 0xffff, l = e >> 16;
+            const bool res = act && nu * (double)l >= p.min_cycles;
+            double ar = 0.0, ai = 0.0;
+            if (res) {
+                for (int i = c; i < l; i += 4) {
+                    const double x = wr[s + i], ph = nu * (double)i;
+                    ar = ar + x * cospi(2.0 * ph);
+                    ai = ai + x * sinpi(2.0 * ph);
+                }
+            }
+            const int q0 = lane & ~3;                                   // (every shuffle is executed by the whole wave)
+            const double xr = ((__shfl(ar, q0, 64) + __shfl(ar, q0 + 1, 64)) + __shfl(ar, q0 + 2, 64)) + __shfl(ar, q0 + 3, 64);
+            const double xi = ((__shfl(ai, q0, 64) + __shfl(ai, q0 + 1, 64)) + __shfl(ai, q0 + 2, 64)) + __shfl(ai, q0 + 3, 64);
+            if (res) {
+                const double sw = rsw[r];
+                const double P = 2.0 * (xr * xr + xi * xi) / (sw * sw);
+                acc = acc + (double)l * P;
+                W += l;
+            }
+        }
+        if (act && c == 0) {
+            const double Pm = W ? acc / (double)W : 0.0;
+            sp[j] = Pm; wg[j] = W;
+            o_sp[j] = Pm; o_wg[j] = W;
+        }
+    }
+    __syncthreads();
+    // ---- phase C: the peak of every band
+    if (w < NB) {
+        int jlo = 0, jhi = 0;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) if (w == x) { jlo = p.band[2 * x]; jhi = p.band[2 * x + 1]; }     // (static indices: scalar registers)
+        double bp = 0.0;
+        int bj = -1;
+        for (int j = jlo + lane; j < jhi; j += 64) {
+            if (j >= 1 && j <= NM - 2) {
+                const double Pa = sp[j - 1], Pc = sp[j], Pe = sp[j + 1];
+                const bool cand = wg[j - 1] > 0 && wg[j] > 0 && wg[j + 1] > 0 && Pa > 0.0 && Pe > 0.0 && Pc > Pa && Pc >= Pe;
+                if (cand && Pc > bp) { bp = Pc; bj = j; }               // (ascending j: the lowest of equal powers stays)
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double op = __shfl_xor(bp, o, 64);
+            const int oj = __shfl_xor(bj, o, 64);
+            if (oj >= 0 && (bj < 0 || op > bp || (op == bp && oj < bj))) { bp = op; bj = oj; }
+        }
+        if (lane == 0) {
+            double pk[4] = {0.0, 0.0, 0.0, 0.0};
+            if (bj >= 0) {
+                double bs = 0.0;
+                int bn = 0;
+                for (int j = jlo; j < jhi; ++j) if (wg[j] > 0) { bs = bs + sp[j]; ++bn; }
+                const double bm = bs / (double)bn;                      // (bn >= 1: the peak itself)
+                const double a = log(sp[bj - 1]), cc = log(sp[bj]), e = log(sp[bj + 1]);
+                const double den = (a - 2.0 * cc) + e;
+                const double off = den < 0.0 ? 0.5 * (a - e) / den : 0.0;
+                const double pw = exp(cc - 0.25 * (a - e) * off);
+                pk[0] = p.nu0 + ((double)bj + off) * p.dnu; pk[1] = sqrt(2.0 * pw); pk[2] = bm; pk[3] = pw / bm;
+            }
+            double* o = o_pk + 4 * w;
+            o[0] = pk[0]; o[1] = pk[1]; o[2] = pk[2]; o[3] = pk[3];
+            o_ct[4 + w] = bj;
+        }
+    }
+    if (t == 0) {
+        o_st[0] = aframes ? q_sum / (double)aframes : 0.0;
+        o_st[1] = aframes ? lb_sum / (double)aframes : 0.0;
+        o_ct[0] = tot[0] + tot[2] + tot[4] + tot[6]; o_ct[1] = tot[1] + tot[3] + tot[5] + tot[7]; o_ct[2] = nruns; o_ct[3] = aframes;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Auditory descriptors (ev_auditory): per frame the loudness of an auditory spectrum, the spectral flux against the frame before, the power and
 // the first cepstral coefficients over mel bands (MFCC), from ONE float64 power spectrum (the definition: include/emojivoice.h; Eyben et al. 2016).
 // All float64, contraction OFF (STOI_EXACT), no atomics.  Two GEMMs on v_mfma_f64_16x16x4_f64, chained through LDS inside one launch, on the shared

@@ -50,6 +50,7 @@
  *   ev_load_harmonics  <- no counterpart; Eyben et al. 2016 and Hanson 1997 are the model
  *   ev_harmonics       <- no counterpart; Eyben et al. 2016 and Hanson 1997 are the model
  *   ev_functionals     <- no counterpart; the functionals of Eyben et al. 2016 (eGeMAPS) as openSMILE computes them are the model
+ *   ev_modulation      <- no counterpart; the modulation spectrum (Takamichi et al. 2016 for cepstral trajectories) is the model
  *   ev_load_auditory   <- no counterpart; Eyben et al. 2016 (eGeMAPS) as openSMILE's cMelspec / cMfcc / cPlp / cSpectral compute them are the model
  *   ev_auditory        <- no counterpart; Eyben et al. 2016 (eGeMAPS) as openSMILE's cMelspec / cMfcc / cPlp / cSpectral compute them are the model
  *   ev_pyin_observe    <- no counterpart; librosa.pyin is the model
@@ -91,7 +92,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -911,6 +912,58 @@ int ev_functionals(ev_handle *h, const double *d_v /* (B, K, F) */, const uint8_
                    const int32_t *d_len /* (B) frames, or NULL */, int B, int K, int F,
                    const double *q /* HOST (NQ), may be NULL when NQ == 0 */, int NQ,
                    double *d_stat /* (B, K, 12 + NQ) */, int32_t *d_count /* (B, K, 8) */, void *stream);
+
+/* Modulation spectra of contours on the device: how a contour OSCILLATES in time, which the functionals above do not say.  Tremor and vibrato are a
+ * 4-12 Hz oscillation of f0 and of loudness; the loudness contour's modulation spectrum peaks at the syllable rate; the modulation spectrum of the
+ * mel-cepstral trajectories is the measure of a synthesiser that flattens fast spectral movement (Takamichi et al. 2016).  All three are one
+ * computation on ev_functionals' interface: K contours of F frames per row under masks, every contour on its own.  On a fixed frequency grid the
+ * spectrum does not move with a shift in time and is comparable between rows of different length, so it needs no sample alignment.  Everything is
+ * float64, the kernel is compiled with floating-point contraction off; no atomics, no scratch; ev_set_arithmetic does not reach it.
+ * Valid frames, dropped frames, runs: ev_functionals' rules.  n = d_len[b], or F when d_len is NULL.  A row with n < 0 or n > F is zeros in EVERY
+ *   output (the peak indices of d_count included), which is no error and no out-of-bounds access; nothing at or behind n is read.  Frame f of
+ *   contour (b, k) is VALID when f < n, d_mask[b, k, f] != 0 (d_mask NULL: every byte is 1) and d_v[b, k, f] is finite; a frame inside n with a
+ *   non-zero mask byte and a non-finite value is DROPPED: counted, and invalid for everything else.  A RUN is a maximal stretch of valid frames
+ *   inside [0, n); a run of length l >= min_run is ANALYSED.  Nothing crosses a gap and nothing is interpolated: a figure over a gap would be invented.
+ * Grid: nu_j = nu0 + (double)j * dnu cycles per frame, 0 <= j < NM (one rounded product, one rounded sum).
+ * One analysed run u_0 .. u_{l-1}, t run-local:  tc = (double)t - (double)(l - 1) / 2 (exact);  m = sum u / l;
+ *   b = sum(tc u) / ((double)(l (l l - 1)) / 12.0), the least-squares line (the product of integers is exact in 64 bits before the one conversion);
+ *   r_t = (u_t - m) - b tc;  w_t = 0.5 - 0.5 cospi((double)(2 t + 1) / (double)l), a symmetric Hann window that is never zero inside the run;
+ *   sw = sum w_t;  ph = nu_j * (double)t (one rounded product);  xr_j = sum w_t r_t cospi(2 ph),  xi_j = sum w_t r_t sinpi(2 ph);
+ *   P_j = 2 (xr^2 + xi^2) / (sw sw): half the squared amplitude of a sinusoid at nu_j, in the contour's units squared.
+ *   (run, j) is RESOLVED when nu_j * (double)l >= min_cycles (one IEEE product).
+ * Pooling over the analysed runs in ascending order:  W_j = sum l over the runs that resolve j (an integer);  Pm_j = (sum (double)l * P_j) /
+ *   (double)W_j, 0 when W_j = 0.  d_spec = Pm, d_weight = W.  d_stat[0] = (sum over the runs of sum_t r_t^2) / (frames analysed): the variance of
+ *   what the lines leave;  d_stat[1] = (sum (double)l * b) / (frames analysed): the length-weighted mean slope per frame.  Both are 0 without an
+ *   analysed run.
+ * Peak per band [j_lo, j_hi): the candidates are the j of the band with 1 <= j <= NM - 2, W_{j-1}, W_j, W_{j+1} > 0, Pm_{j-1}, Pm_{j+1} > 0,
+ *   Pm_j > Pm_{j-1} and Pm_j >= Pm_{j+1} (ev_perturbation's local-peak rule; the neighbours may lie outside the band).  The peak is the candidate
+ *   with the largest Pm_j, the lowest j among equals.  With a, c, e = log Pm_{j-1}, log Pm_j, log Pm_{j+1}:  den = (a - 2 c) + e;
+ *   off = den < 0 ? (0.5 (a - e)) / den : 0;  pw = exp(c - (0.25 (a - e)) off), the peak power.
+ *   d_peak[b, k, band, .] = { nu0 + ((double)j + off) dnu,  sqrt(2 pw): the amplitude,  the mean of Pm over the band's j with W_j > 0 (added in
+ *   ascending j),  pw / that mean }.  Without a candidate the four are zeros and the band's entry of d_count is -1; otherwise that entry is j.
+ * d_count[b, k, .] int32: 0 valid frames, 1 dropped frames, 2 analysed runs, 3 analysed frames, 4 + band the peak index.
+ * Order of the float64 sums.  Per run (sum u, sum tc u, sum w, sum r^2): term t belongs to slot t mod 64; a slot starts at +0.0 and adds its terms
+ *   in ascending t; the 64 slots are reduced by an xor tree (offsets 32, 16, 8, 4, 2, 1).  xr and xi: four chains c = t mod 4, each from +0.0 in
+ *   ascending t, a term being the rounded product (w_t r_t) cospi(2 ph) added by a rounded sum (no fused multiply-add anywhere, so that a
+ *   restatement without one adds the same numbers); joined as ((s0 + s1) + s2) + s3.  The sums over the runs (Pm's numerator, both statistics)
+ *   start at +0.0 and add the runs in ascending order.  Products are rounded before they are added.  Every order is a function of the contour, the
+ *   grid and min_run alone, never of B, K, F or the place in the grid: a contour alone, inside a batch, at another k, as the d_len prefix of a
+ *   longer F, in a second call, under every ev_set_arithmetic setting and from a captured graph gives the same bits.
+ * Limits, each violation failing with a message that names it and writing nothing: 1 <= B <= 65535; 1 <= K <= 65535; 1 <= F <= 4096; 1 <= NM <=
+ *   128; nu0 and dnu finite and greater than 0; nu0 + (NM - 1) dnu <= 0.5; 3 <= min_run <= F; min_cycles finite and at least 0; 0 <= NBAND <= 4
+ *   with 0 <= j_lo < j_hi <= NM for every band; band non-NULL and d_peak non-NULL when NBAND > 0; d_v, d_spec, d_weight, d_stat and d_count
+ *   non-NULL.
+ * Kernel (modulation_kernel: one launch on `stream`; no load step, no host wait, no copy, no arena: ev_alloc_count never moves): one workgroup of
+ *   four waves per contour, everything in LDS: w_t r_t (8 bytes per frame), the table of the analysed runs (12 bytes each, at most (F + 1) / 4 of
+ *   them) and the pooled spectrum: 45.6 KiB at F = 4096.  Phase A finds the runs with ev_functionals' max-scan, detrends and windows them in
+ *   place; phase B gives every (j, chain) a thread, which reads w_t r_t as an LDS broadcast and calls the device library's float64 cospi and sinpi
+ *   (they bound the kernel); phase C pools, picks the peaks (log, exp, sqrt: the device library's) and writes.  The call is capturable. */
+int ev_modulation(ev_handle *h, const double *d_v /* (B, K, F) */, const uint8_t *d_mask /* (B, K, F) or NULL */,
+                  const int32_t *d_len /* (B) frames, or NULL */, int B, int K, int F,
+                  double nu0, double dnu, int NM, int min_run, double min_cycles,
+                  const int32_t *band /* HOST (NBAND, 2): j_lo, j_hi; may be NULL when NBAND == 0 */, int NBAND,
+                  double *d_spec /* (B, K, NM) */, int32_t *d_weight /* (B, K, NM) */, double *d_peak /* (B, K, NBAND, 4) or NULL when NBAND == 0 */,
+                  double *d_stat /* (B, K, 2) */, int32_t *d_count /* (B, K, 4 + NBAND) */, void *stream);
 
 /* Auditory descriptors per frame on the device: the descriptors of timbre and dynamics that eGeMAPS (Eyben et al. 2016) adds to pitch, balance,
  * formants and perturbation: the LOUDNESS of an auditory spectrum (mel bands under an equal-loudness weighting, compressed by a power law), the

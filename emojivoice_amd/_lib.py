@@ -45,6 +45,7 @@ EXPORTS = [
     "ev_load_harmonics", "ev_harmonics",
     "ev_functionals", "ev_modulation",
     "ev_load_auditory", "ev_auditory",
+    "ev_load_srmr", "ev_srmr",
 ]
 
 
@@ -182,6 +183,8 @@ def load_library() -> C.CDLL:
     lib.ev_modulation.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_double, C.c_double, i32, i32, C.c_double, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.ev_load_auditory.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, C.c_double]
     lib.ev_auditory.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp, vp]
+    lib.ev_load_srmr.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32]
+    lib.ev_srmr.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -474,6 +477,34 @@ class Engine:
         self._check(self.lib.ev_loudness(self.h, x.data_ptr(), _ptr(ln), B, L, S, coef.ctypes.data, float(abs_gate), _ptr(sub), _ptr(block),
                                          gated.data_ptr(), counts.data_ptr(), _stream_ptr()), "ev_loudness")
         return sub, block, gated, counts
+
+    def load_srmr(self, chan, mod, window, erb, cutoff, hop: int) -> None:
+        """The tables of ``srmr`` (ev_load_srmr), all float64 on the host: ``chan`` (N, 3) {Re a, Im a, gain}, ``mod`` (K, 5) {b0, b1, b2, a1,
+        a2}, ``window`` (4 hop,), ``erb`` (N,), ``cutoff`` (K,): what ``audio.srmr_tables`` designs."""
+        f = lambda v, *shape: np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(*shape))
+        ch, md, w, eb, ct = f(chan, -1, 3), f(mod, -1, 5), f(window, -1), f(erb, -1), f(cutoff, -1)
+        N, K, H = int(ch.shape[0]), int(md.shape[0]), int(hop)
+        if w.shape[0] != 4 * H or eb.shape[0] != N or ct.shape[0] != K:
+            raise ValueError(f"load_srmr: window ({4 * H},), erb ({N},) and cutoff ({K},) expected, got {w.shape}, {eb.shape} and {ct.shape}")
+        self._check(self.lib.ev_load_srmr(self.h, ch.ctypes.data, md.ctypes.data, w.ctypes.data, eb.ctypes.data, ct.ctypes.data, N, K, H), "ev_load_srmr")
+        self.srmr_geometry = (N, K, H)
+
+    def srmr(self, x, lengths, want_frame: bool = False):
+        """SRMR of every row of ``x`` (B, L) at the tables' rate (ev_srmr, after load_srmr): (frame (B, NF, N, K) float64 or None, mean (B, N, K)
+        float64, srmr (B, 2) float64 {ratio (0 without a frame or a denominator), bw}, counts (B, 3) int32 {frames, j90, K*}) on the device.
+        ``lengths`` (B,): samples per row (None: L)."""
+        if not hasattr(self, "srmr_geometry"):
+            raise EvLibraryError("srmr: tables not loaded (load_srmr)")
+        x, B, L, ln = self._rows(x, lengths, "srmr")
+        N, K, H = self.srmr_geometry
+        NF = (L - 4 * H) // H + 1 if L >= 4 * H else 0
+        frame = torch.empty((B, NF, N, K), dtype=torch.float64, device=x.device) if want_frame else None
+        mean = torch.empty((B, N, K), dtype=torch.float64, device=x.device)
+        out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+        counts = torch.empty((B, 3), dtype=torch.int32, device=x.device)
+        self._check(self.lib.ev_srmr(self.h, x.data_ptr(), _ptr(ln), B, L, _ptr(frame), mean.data_ptr(), out.data_ptr(), counts.data_ptr(),
+                                     _stream_ptr()), "ev_srmr")
+        return frame, mean, out, counts
 
     def load_stoi(self, window, twiddle, bands, hop: int, n_fft: int, seg_frames: int) -> None:
         """The tables of ``stoi`` (ev_load_stoi), all on the host: ``window`` (W,) float64 with W = 2 hop, ``twiddle`` (n_fft, 2) float64

@@ -801,6 +801,101 @@ def stoi(reference, degraded, sr: int = 22050, lengths=None, rows: Optional[Call
     return {"stoi": torch.where(scored, score[:, 0], nan), "estoi": torch.where(scored, score[:, 1], nan), "segments": seg, "counts": counts, "keep": keep}
 
 
+# ---- reverberation: the speech-to-reverberation modulation energy ratio (Falk, Zheng, Chan 2010) ----------------------------------------------------
+SRMR_SR = 16000                                    # the rate the measure's tables are designed for
+SRMR_EAR_Q, SRMR_MIN_BW = 9.26449, 24.7            # Glasberg and Moore's ERB scale
+SRMR_GAMMATONE_ORDER = 4
+
+
+def srmr_tables(sr: int = SRMR_SR, n_channels: int = 23, low_freq: float = 125.0, n_bands: int = 8, mod_lo: float = 4.0, mod_hi: float = 128.0,
+                q: float = 2.0, frame_ms: float = 256, hop_ms: float = 64) -> Dict:
+    """The tables ``ev_load_srmr`` takes, all float64, for rows at ``sr``:
+      * "centres" (N,): ERB-spaced centre frequencies (Glasberg and Moore, EarQ = 9.26449, minBW = 24.7; Slaney's spacing) ascending from
+        ``low_freq`` to below sr / 2; "erb" (N,) = centre / EarQ + minBW;
+      * "chan" (N, 3) {Re a, Im a, gain}: Hohmann's (2002) complex pole a = lambda exp(2 pi i centre / sr), lambda = exp(-2 pi (erb / a_4) / sr),
+        a_4 = pi 6! / (2^6 (3!)^2) the order-4 gammatone's bandwidth factor; gain = 2 (1 - |a|)^4;
+      * "mod_centres" (K,): log-spaced from ``mod_lo`` to ``mod_hi``; "mod" (K, 5) {b0, b1, b2, a1, a2}: the second-order band pass with
+        W0 = tan(pi f / sr), B0 = W0 / q: b = (B0, 0, -B0) / a0, a = (1 + B0 + W0^2, 2 W0^2 - 2, 1 - B0 + W0^2) / a0; "cutoff" (K,) =
+        f - B0 sr / (2 pi), the lower band edges;
+      * "window" (W,): the symmetric Hamming window of W = sr frame_ms / 1000 samples; "hop" H = sr hop_ms / 1000.
+    The device wants W = 4 H and H a multiple of 64 between 64 and 1024, 1 <= N <= 32 and 1 <= K <= 8."""
+    sr, N, K = int(sr), int(n_channels), int(n_bands)
+    H, W = sr * hop_ms / 1000.0, sr * frame_ms / 1000.0
+    if H != int(H) or W != int(W) or int(W) != 4 * int(H) or int(H) % 64 or not 64 <= int(H) <= 1024:
+        raise ValueError(f"srmr_tables: hop {H:g} and frame {W:g} samples: the frame must be 4 hops and the hop a multiple of 64 with 64 <= hop <= 1024")
+    if not 1 <= N <= 32 or not 1 <= K <= 8:
+        raise ValueError(f"srmr_tables: n_channels={N} outside 1 .. 32 or n_bands={K} outside 1 .. 8")
+    if not 0 < low_freq < sr / 2.0 or not 0 < mod_lo <= mod_hi < sr / 2.0 or not q > 0:
+        raise ValueError(f"srmr_tables: 0 < low_freq < sr / 2, 0 < mod_lo <= mod_hi < sr / 2 and q > 0 expected (got {low_freq}, {mod_lo}, {mod_hi}, {q})")
+    H, W = int(H), int(W)
+    c = SRMR_EAR_Q * SRMR_MIN_BW
+    i = np.arange(1, N + 1, dtype=np.float64)
+    centres = (-c + np.exp(i * (np.log(low_freq + c) - np.log(sr / 2.0 + c)) / N) * (sr / 2.0 + c))[::-1].copy()
+    erb = centres / SRMR_EAR_Q + SRMR_MIN_BW
+    g = SRMR_GAMMATONE_ORDER
+    a_g = math.pi * math.factorial(2 * g - 2) * 2.0 ** -(2 * g - 2) / math.factorial(g - 1) ** 2
+    lam = np.exp(-2.0 * np.pi * (erb / a_g) / sr)
+    beta = 2.0 * np.pi * centres / sr
+    chan = np.stack([lam * np.cos(beta), lam * np.sin(beta), 2.0 * (1.0 - lam) ** 4], axis=1)
+    mod_centres = mod_lo * (mod_hi / mod_lo) ** (np.arange(K, dtype=np.float64) / max(K - 1, 1))
+    W0 = np.tan(np.pi * mod_centres / sr)
+    B0 = W0 / q
+    a0 = 1.0 + B0 + W0 ** 2
+    mod = np.stack([B0 / a0, np.zeros(K), -B0 / a0, (2.0 * W0 ** 2 - 2.0) / a0, (1.0 - B0 + W0 ** 2) / a0], axis=1)
+    cutoff = mod_centres - B0 * sr / (2.0 * np.pi)
+    return {"sr": sr, "hop": H, "centres": centres, "erb": erb, "chan": np.ascontiguousarray(chan), "mod_centres": mod_centres,
+            "mod": np.ascontiguousarray(mod), "cutoff": cutoff, "window": np.hamming(W).astype(np.float64)}
+
+
+def _srmr_engine(device: torch.device) -> Engine:
+    def load(eng):
+        t = srmr_tables()
+        eng.load_srmr(t["chan"], t["mod"], t["window"], t["erb"], t["cutoff"], t["hop"])
+    return _cached_engine(device, ("srmr",), load)
+
+
+def _device_srmr_rows(x, lengths, want_frame):
+    return _srmr_engine(x.device).srmr(x, lengths, want_frame)
+
+
+@torch.inference_mode()
+def srmr(y, sr: int = 22050, lengths=None, rows: Optional[Callable] = None, energies: bool = False):
+    """The speech-to-reverberation modulation energy ratio of ``y`` (1-D or (B, L) at ``sr`` on the GPU), on the device (``ev_srmr``; no torch
+    fallback): NON-INTRUSIVE, no clean reference.  The rows go to 16 kHz through ``resample`` unless ``sr`` is 16000; then 23 gammatone channels
+    from 125 Hz, their envelopes, 8 modulation bands from 4 to 128 Hz, 256 ms Hamming frames every 64 ms (``srmr_tables``).  A dry voice reads
+    high, a reverberant one low.  The envelope comes from a complex gammatone (Hohmann 2002), a stated difference from SRMRpy: figures compare
+    across this project's runs, not with other tools.  -> {"srmr" (B,) float64: NaN for a row without a frame (under 256 ms) or without energy
+    in the high bands; "bw" (B,) float64: the bandwidth of the channel that closes 90 % of the energy; "k_star" (B,) int32: the bands counted;
+    "frames" (B,) int32; "mean" (B, N, K) float64: the mean energy per (channel, band); with ``energies`` "energies" (B, NF, N, K) float64};
+    a 1-D input gives B = 1.  ``rows``: the per-batch measurement, (x, lengths, want_frame) at 16 kHz -> (frame or None, mean, (B, 2) {ratio,
+    bw}, counts (B, 3) {frames, j90, K*}) — the device call unless given."""
+    if int(sr) != sr or int(sr) < 1:
+        raise ValueError(f"srmr: sr must be a positive integer (got {sr})")
+    if not torch.is_tensor(y) or y.dim() not in (1, 2) or y.shape[-1] < 1:
+        raise ValueError("srmr: y must be a non-empty tensor, 1-D or (B, L)")
+    if rows is None and not y.is_cuda:
+        raise EvLibraryError("srmr runs on a ROCm GPU only (no CPU fallback): move y to the GPU")
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    ln = None
+    if lengths is not None and y.dim() == 2:
+        ln = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
+        if ln.numel() != x.shape[0]:
+            raise ValueError(f"srmr: {x.shape[0]} lengths expected, got {ln.numel()}")
+    if int(sr) != SRMR_SR:
+        up, down = resample_ratio(int(sr), SRMR_SR)
+        x = resample(x, int(sr), SRMR_SR, lengths=ln)
+        if ln is not None:
+            ln = torch.where((ln >= 1) & (ln <= y.shape[-1]), -(-ln * up // down), torch.zeros_like(ln))
+    frame, mean, out, counts = (rows or _device_srmr_rows)(x, ln, bool(energies))
+    out, counts = torch.as_tensor(out, dtype=torch.float64), torch.as_tensor(counts)
+    scored = ((counts[:, 0] > 0).to(out.device)) & (out[:, 0] > 0)
+    res = {"srmr": torch.where(scored, out[:, 0], torch.full_like(out[:, 0], float("nan"))), "bw": out[:, 1], "k_star": counts[:, 2],
+           "frames": counts[:, 0], "mean": mean}
+    if energies:
+        res["energies"] = frame
+    return res
+
+
 # ---- spectral-magnitude distance: multi-resolution STFT (Yamamoto, Song, Kim 2020) and log-spectral distance ---------------------------------------
 MSTFT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))   # (n_fft, hop, win): the published defaults
 MSTFT_POWER_FLOOR = 1e-7                                                    # the clamp of |X|^2 before the root and the logarithm

@@ -30,6 +30,8 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --auditory                                  # ... and, per pair, loudness, spectral flux, MFCC 1-4 and the level of both sides and their differences
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --voice_quality                             # ... and, per pair, the voice-quality figures of both sides and their differences
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
+    python -m emojivoice_amd.cli --reverb_report clean/filelist.txt                                     # clean/filelist.txt.srmr.json: SRMR (reverberation, no clean reference needed) per file and per speaker
+    python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --srmr                                      # ... and, per pair, the SRMR of both sides and their difference
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
     python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000          # clean/filelist.txt.vocoder.json: STOI / ESTOI, mel L1 and loudness shift of copy synthesis
     python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000 --spectral_distance   # + multi-resolution STFT distance and log-spectral distance
@@ -103,7 +105,8 @@ def validate_args(args):
             sr = int(args.sample_rate or 22050)
             assert sr % 10 == 0 and sr >= 8000, "--target_lufs needs a --sample_rate that is a multiple of 10 and at least 8000"
         return args
-    if getattr(args, "prosody_report", None) or getattr(args, "evaluate_pairs", None) or getattr(args, "loudness_report", None) or getattr(args, "voice_report", None):
+    if (getattr(args, "prosody_report", None) or getattr(args, "evaluate_pairs", None) or getattr(args, "loudness_report", None) or getattr(args, "voice_report", None)
+            or getattr(args, "reverb_report", None)):
         assert args.batch_size > 0, "Batch size must be greater than 0"
         return args
     if getattr(args, "vocoder_report", None):
@@ -813,6 +816,49 @@ def loudness_report(args, device):
     return rep
 
 
+REVERB_SR = 22050            # the rate the files are loaded at, as for the other reports; audio.srmr takes them to 16 kHz
+
+
+def reverb_summary(values):
+    """{"measured", "mean", "std", "min"} of SRMR values (the files that have one), as ``loudness_summary`` forms them; the minimum is the most
+    reverberant file.  None for every statistic when there is none."""
+    return {k: v for k, v in loudness_summary(values).items() if k != "max"}
+
+
+def srmr_value(v):
+    return None if math.isnan(float(v)) else float(v)
+
+
+@torch.inference_mode()
+def reverb_report(args, device):
+    """--reverb_report FILELIST: the filelist format of --loudness_report.  Every file is loaded with audio.load_audio(path, 22050) and measured by
+    audio.srmr (the speech-to-reverberation modulation energy ratio on the device; no clean reference needed), --batch_size files at a time
+    (padded to the longest, each row with its own length).  FILELIST.srmr.json receives per file "srmr" (null for a file under 256 ms or without
+    energy in the high modulation bands; a dry voice reads high, a reverberant one low), "frames", "k_star" (the modulation bands counted) and
+    "seconds"; per speaker and overall the file count and measured / mean / std / min of the SRMR over the files that have one."""
+    from . import audio
+
+    files = []
+    for chunk, batch, lens in filelist_batches(args.reverb_report, args.batch_size, REVERB_SR, device):
+        out = audio.srmr(batch, REVERB_SR, lengths=lens, rows=getattr(args, "srmr_rows", None))
+        ratio, frames, ks = out["srmr"].cpu(), out["frames"].cpu(), out["k_star"].cpu()
+        for r, (wav, spk, _) in enumerate(chunk):
+            files.append({"path": wav, "speaker": spk if spk is not None else "0", "seconds": lens[r] / float(REVERB_SR), "srmr": srmr_value(ratio[r]),
+                          "frames": int(frames[r]), "k_star": int(ks[r])})
+    pool = lambda mine: {"files": len(mine), **reverb_summary([f["srmr"] for f in mine if f["srmr"] is not None])}
+    speakers = {spk: pool([f for f in files if f["speaker"] == spk]) for spk in dict.fromkeys(f["speaker"] for f in files)}
+    rep = {"sample_rate": REVERB_SR, "srmr_sample_rate": audio.SRMR_SR, "files": files, "speakers": speakers, "overall": pool(files)}
+    out_path = f"{args.reverb_report}.srmr.json"
+    with open(out_path, "w") as f:
+        json.dump(rep, f, indent=1)
+    for k in sorted(speakers):
+        v = speakers[k]
+        fig = "no file long enough to measure" if v["mean"] is None else f"SRMR {v['mean']:.2f} mean, std {v['std']:.2f}, {v['min']:.2f} min"
+        print(f"[i] speaker {k}: {v['files']} files, {fig}")
+    print(f"[+] Reverberation report saved: {Path(out_path).resolve()}")
+    return rep
+
+
 VOCODER_REPORT_KEYS = ("stoi", "estoi", "mel_l1", "lufs_shift")
 
 
@@ -975,10 +1021,13 @@ def evaluate_pairs(args, device):
     and rhythm: rates, extents, prominences) and "ms_distortion_db" / "ms_shift_db", the distance between the modulation spectra of the two
     sides' mel-cepstral trajectories (audio.cepstral_modulation_distance: no alignment; a negative shift says the synthesised side moves
     less, i.e. is over-smoothed); per speaker and overall the mean and mean absolute difference per figure and the plain means of the two
-    distances over the pairs that have them."""
+    distances over the pairs that have them.
+    --srmr adds per pair "srmr": {"recorded", "synthesised", "delta"}, audio.srmr of each side (non-intrusive: it needs no alignment; null for
+    a side without a figure) and synthesised - recorded; per speaker and overall "srmr": the means of the three over the pairs that have them."""
     from . import audio
 
     want_mod = getattr(args, "modulation", False)
+    want_srmr = getattr(args, "srmr", False)
 
     entries = parse_pairs(args.evaluate_pairs)
     if not entries:
@@ -1003,6 +1052,8 @@ def evaluate_pairs(args, device):
             pitch[f.block] = [{k: v for k, v in family_means([row], f).items() if k in f.figures} for row in family_rows(st, f)]
         if want_mod:
             pitch["modulation"] = [row["modulation"] for row in voice_modulation_of(audio, pitch, got, sig, sr, hop, clipped, frames)]
+        if want_srmr:
+            pitch["srmr"] = [srmr_value(v) for v in audio.srmr(sig, sr, lengths=clipped, rows=getattr(args, "srmr_rows", None))["srmr"].cpu()]
         return cep, frames, pitch
 
     for b0 in range(0, len(entries), args.batch_size):
@@ -1041,6 +1092,9 @@ def evaluate_pairs(args, device):
                 records[-1]["modulation"] = {"recorded": va, "synthesised": vb,
                                              "delta": {k: (None if va[k] is None or vb[k] is None else vb[k] - va[k]) for k in va},
                                              "ms_distortion_db": val(msd[0, r]), "ms_shift_db": val(msd[1, r])}
+            if want_srmr:
+                va, vb = pitch_a["srmr"][r], pitch_b["srmr"][r]
+                records[-1]["srmr"] = {"recorded": va, "synthesised": vb, "delta": None if va is None or vb is None else vb - va}
 
     def means(recs):
         out = evaluation_means(recs)
@@ -1058,6 +1112,11 @@ def evaluate_pairs(args, device):
             for k in ("ms_distortion_db", "ms_shift_db"):
                 d = [r["modulation"][k] for r in recs if r["modulation"][k] is not None]
                 out["modulation"][k] = {"mean": math.fsum(d) / len(d) if d else None, "pairs": len(d)}
+        if want_srmr:
+            out["srmr"] = {}
+            for k in ("recorded", "synthesised", "delta"):
+                d = [r["srmr"][k] for r in recs if r["srmr"][k] is not None]
+                out["srmr"][k] = math.fsum(d) / len(d) if d else None
         return out
 
     by_spk = {}
@@ -1138,6 +1197,12 @@ def cli(argv=None):
     p.add_argument("--loudness_report", type=str, default=None, help="loudness analysis instead of synthesis: a filelist 'path|spk|text' -> FILELIST.loudness.json: "
                    "ITU-R BS.1770-4 integrated LUFS, loudest 400 ms block, peak in dBFS and seconds per file; mean / std / min / max per speaker and the files "
                    "more than 3 LU from their speaker's mean (on the device, --batch_size files per batch; needs no checkpoint)")
+    p.add_argument("--reverb_report", type=str, default=None, help="reverberation analysis instead of synthesis: a filelist 'path|spk|text' -> FILELIST.srmr.json: "
+                   "the speech-to-reverberation modulation energy ratio (SRMR, non-intrusive; a dry voice reads high, a reverberant room low), frames, "
+                   "modulation bands counted and seconds per file; mean / std / min per speaker and overall (on the device, --batch_size files per "
+                   "batch; needs no checkpoint)")
+    p.add_argument("--srmr", action="store_true", help="--evaluate_pairs: add \"srmr\" per pair (the SRMR of the recording, of the synthesis and their "
+                   "difference; no alignment needed) and the means per speaker and overall")
     p.add_argument("--target_lufs", type=float, default=None, help="--prepare_dataset: level every recording to this integrated loudness (BS.1770, e.g. -23) "
                    "instead of to --peak; the gain is capped where the peak would pass --peak, and the gain and the cap go into FILELIST.durations.json")
     p.add_argument("--vocoder_report", type=str, default=None, help="vocoder evaluation instead of synthesis: a filelist 'path|spk|text' -> FILELIST.vocoder.json: "
@@ -1191,6 +1256,10 @@ def cli(argv=None):
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
         return vocoder_report(args, torch.device("cuda", 0))
+    if args.reverb_report:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return reverb_report(args, torch.device("cuda", 0))
     if args.loudness_report:
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")

@@ -1,5 +1,5 @@
 // Host entry points of the analysis side: resampling, dataset statistics, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness,
-// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals, auditory descriptors and formant tracks (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
+// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals, auditory descriptors, formant tracks and SRMR (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
 // after ev_handle, fail / HIPCHK / enter, dev_upload, drop_owned, scratch_acquire and launch<>.  None of these calls runs on the engine's conv
 // path; ev_load_mel_basis, ev_mel_spectrogram, ev_denoise and ev_stft_magnitude do, and stay in ev_engine.hip.
 #pragma once
@@ -377,6 +377,113 @@ int ev_loudness(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int
     pg.sub = sub; pg.len = d_len; pg.block = d_block; pg.gated = d_gated; pg.counts = d_counts;
     pg.L = L; pg.S = S; pg.NS = NS; pg.NB = NB; pg.abs_gate = abs_gate;
     launch<loud_gate_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pg);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// SRMR (kernels and the scheme: ev_analysis_kernels.h; the definition: include/emojivoice.h).  The load computes both zero-input transitions
+// over H samples by running the kernels' own recurrences on unit states, and puts everything into ONE device block.  Arena of a call, in doubles:
+// [channel states B x NC x 8 N][band states B x NC x 2 N K][window-quarter sums B x NC x 4 N K], NC = NF + 3 chunks.
+int ev_load_srmr(ev_handle* h, const double* chan, const double* mod, const double* window, const double* erb, const double* cutoff, int N, int K, int H) {
+    STOI_EXACT
+    if (enter(h)) return 1;
+    if (!chan || !mod || !window || !erb || !cutoff) return fail(h, "ev_load_srmr: chan, mod, window, erb and cutoff must be non-null (HOST)");
+    if (N < 1 || N > SRMR_MAXN) return fail(h, "ev_load_srmr: N=%d outside 1 <= N <= %d", N, SRMR_MAXN);
+    if (K < 1 || K > SRMR_MAXK) return fail(h, "ev_load_srmr: K=%d outside 1 <= K <= %d", K, SRMR_MAXK);
+    if (H < 64 || H > 1024 || H % 64) return fail(h, "ev_load_srmr: H=%d must be a multiple of 64 with 64 <= H <= 1024", H);
+    const int W = 4 * H;
+    if (check_finite(h, __func__, "chan", chan, 3 * N) || check_finite(h, __func__, "window", window, W) || check_finite(h, __func__, "erb", erb, N) ||
+        check_finite(h, __func__, "cutoff", cutoff, K)) return 1;
+    for (int j = 0; j < N; ++j) {
+        const double r = std::hypot(chan[3 * j], chan[3 * j + 1]);
+        if (!(r < 1.0)) return fail(h, "ev_load_srmr: chan[%d] has |a| = %g; |a| < 1 expected", j, r);
+    }
+    for (int k = 0; k < K; ++k) {
+        const double a1 = mod[5 * k + 3], a2 = mod[5 * k + 4];
+        bool finite = true;
+        for (int i = 0; i < 5; ++i) finite = finite && std::isfinite(mod[5 * k + i]);
+        if (!(finite && std::fabs(a2) < 1.0 && std::fabs(a1) < 1.0 + a2))
+            return fail(h, "ev_load_srmr: mod band %d is unstable or not finite (a1=%g a2=%g; |a2| < 1 and |a1| < 1 + a2 expected)", k, a1, a2);
+    }
+    const size_t o_chan = 0, o_Mc = o_chan + 3 * (size_t)N, o_mod = o_Mc + 20 * (size_t)N, o_Mb = o_mod + 5 * (size_t)K, o_win = o_Mb + 4 * (size_t)K,
+                 o_erb = o_win + W, o_cut = o_erb + N, total = o_cut + K;
+    std::vector<double> blk(total);
+    std::copy(chan, chan + 3 * N, blk.begin() + o_chan);
+    std::copy(mod, mod + 5 * K, blk.begin() + o_mod);
+    std::copy(window, window + W, blk.begin() + o_win);
+    std::copy(erb, erb + N, blk.begin() + o_erb);
+    std::copy(cutoff, cutoff + K, blk.begin() + o_cut);
+    for (int j = 0; j < N; ++j) {                                        // column c of a channel's M: the cascade H zero samples after unit state c
+        const double ar = chan[3 * j], ai = chan[3 * j + 1];
+        for (int c = 0; c < 4; ++c) {
+            double r[4] = {0.0, 0.0, 0.0, 0.0}, i[4] = {0.0, 0.0, 0.0, 0.0};
+            r[c] = 1.0;
+            for (int n = 0; n < H; ++n) {
+                const double xv = 0.0;
+                double nr = xv + (ar * r[0] - ai * i[0]), ni = ar * i[0] + ai * r[0];
+                r[0] = nr; i[0] = ni;
+                for (int s = 1; s < 4; ++s) {
+                    nr = r[s - 1] + (ar * r[s] - ai * i[s]); ni = i[s - 1] + (ar * i[s] + ai * r[s]);
+                    r[s] = nr; i[s] = ni;
+                }
+            }
+            for (int s = c; s < 4; ++s) {
+                blk[o_Mc + 20 * (size_t)j + 2 * (s * (s + 1) / 2 + c)] = r[s];
+                blk[o_Mc + 20 * (size_t)j + 2 * (s * (s + 1) / 2 + c) + 1] = i[s];
+            }
+        }
+    }
+    for (int k = 0; k < K; ++k) {                                        // column c of a band's M
+        const double* m = mod + 5 * k;
+        for (int c = 0; c < 2; ++c) {
+            double s1 = c == 0 ? 1.0 : 0.0, s2 = c == 1 ? 1.0 : 0.0;
+            for (int n = 0; n < H; ++n) {
+                const double e = 0.0;
+                const double y = std::fma(m[0], e, s1);
+                s1 = std::fma(-m[3], y, std::fma(m[1], e, s2));
+                s2 = std::fma(-m[4], y, m[2] * e);
+            }
+            blk[o_Mb + 4 * (size_t)k + c] = s1; blk[o_Mb + 4 * (size_t)k + 2 + c] = s2;
+        }
+    }
+    SrmrW& cur = h->srmr;
+    if (cur.loaded) { if (drop_owned(h, {(void*)cur.blk})) return 1; cur = SrmrW(); }
+    SrmrW t;
+    if (dev_upload(h, blk, &t.blk)) return 1;
+    t.t = SrmrTables{t.blk + o_chan, t.blk + o_Mc, t.blk + o_mod, t.blk + o_Mb, t.blk + o_win, t.blk + o_erb, t.blk + o_cut, N, K, H};
+    t.loaded = true;
+    cur = t;
+    return 0;
+}
+
+int ev_srmr(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, double* d_frame, double* d_mean, double* d_srmr, int32_t* d_counts,
+            void* stream) {
+    if (enter(h)) return 1;
+    const SrmrW& w = h->srmr;
+    if (!w.loaded) return fail(h, "ev_srmr: tables not loaded (ev_load_srmr)");
+    if (check_batch(h, __func__, B)) return 1;
+    if (L < 1) return fail(h, "ev_srmr: L=%d must be at least 1", L);
+    if (!d_x) return fail(h, "ev_srmr: d_x must be non-null");
+    if (!d_mean || !d_srmr || !d_counts) return fail(h, "ev_srmr: d_mean, d_srmr and d_counts must be non-null");
+    h->stream = (hipStream_t)stream;
+    const int N = w.t.N, K = w.t.K, H = w.t.H, NK = N * K;
+    const int NF = L >= 4 * H ? (L - 4 * H) / H + 1 : 0, NC = NF > 0 ? NF + 3 : 0;
+    double* cst = nullptr; double* bst = nullptr; double* part = nullptr;
+    if (NF > 0) {
+        const size_t n_c = (size_t)B * NC * 8 * N, n_b = (size_t)B * NC * 2 * NK, n_p = (size_t)B * NC * 4 * NK;
+        if (scratch_acquire(h, h->srmr_ws, (n_c + n_b + n_p) * sizeof(double))) return 1;
+        cst = (double*)h->srmr_ws.p; bst = cst + n_c; part = bst + n_b;
+        SrmrChunkParams pc{d_x, d_len, cst, bst, part, w.t, L, NC};
+        SrmrCarryParams kc{cst, d_len, w.t, L, NC}, kb{bst, d_len, w.t, L, NC};
+        const dim3 grid((unsigned)NC, (unsigned)B);
+        launch<srmr_chunk_kernel<0>>(h->device, grid, dim3(64), 0, h->stream, pc);
+        launch<srmr_carry_chan_kernel>(h->device, dim3((unsigned)B), dim3(64), 0, h->stream, kc);
+        launch<srmr_chunk_kernel<1>>(h->device, grid, dim3(64), 0, h->stream, pc);
+        launch<srmr_carry_band_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, kb);
+        launch<srmr_chunk_kernel<2>>(h->device, grid, dim3(64), 0, h->stream, pc);
+    }
+    SrmrRowsParams pr{part, d_len, d_frame, d_mean, d_srmr, d_counts, w.t, L, NC, NF};
+    launch<srmr_rows_kernel>(h->device, dim3((unsigned)B), dim3(256), 0, h->stream, pr);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -3185,3 +3185,245 @@ __global__ __launch_bounds__(1024) void formant_track_kernel(const FormantTrackP
         trk[(size_t)i * 2] = f; trk[(size_t)i * 2 + 1] = bw;
     }
 }
+
+// ---------------------------------------------------------------------------
+// SRMR (ev_srmr): the speech-to-reverberation modulation energy ratio of a row (Falk, Zheng and Chan 2010), the definition and every order:
+// include/emojivoice.h.  All float64, contraction OFF (STOI_EXACT): an fma is an fma only where fma() is written.  No atomics.
+// A row is cut into chunks of H samples from its first sample; a row of nf frames has nc = nf + 3 chunks, all of them whole and inside len.  Both
+// recurrences are linear in (state, input) (the cascade over the complex numbers, a band's biquad over the reals), the envelope between them is not,
+// so the true states come in two rounds.  Six launches:
+//   1. srmr_chunk_kernel<0>:   a wave per (row, chunk), lane = channel: the cascade from zero state; keeps the 4 complex states it reaches;
+//   2. srmr_carry_chan_kernel: a wave per row, lane = channel: s[c + 1] = M s[c] + z[c] in ascending c, in place: slot c then holds the state at the
+//                              START of chunk c;
+//   3. srmr_chunk_kernel<1>:   lane = (channel, half of the bands): the cascade from its true state, the envelope, the lane's up to four bands from
+//                              zero state; keeps the two doubles per band they reach;
+//   4. srmr_carry_band_kernel: a workgroup per row, thread = (channel, band): the 2 x 2 carry, in place;
+//   5. srmr_chunk_kernel<2>:   everything from its true state; per band the four window-quarter sums of the chunk (one fma per sample, ascending);
+//   6. srmr_rows_kernel:       a workgroup per row, thread = (channel, band): E[f] from the pieces of four chunks, the ascending mean; then thread 0
+//                              takes the shares, j90, K* and the ratio in the header's order.
+// MAPPING.  The channels of one (row, chunk) read the SAME samples and the same window values, so they lie along the lanes of one wave and those
+// reads are wave-uniform (scalar loads).  A lane with all eight bands would hold 16 band states, 32 piece sums, 40 coefficients and the cascade:
+// well over a hundred doubles.  Two lanes per channel (bands 0..3 and 4..7) hold 55 each and both run the cascade: it is a third of a lane's work.
+// Lanes past N, and bands past K, run on zero coefficients and store nothing.
+constexpr int SRMR_MAXN = 32, SRMR_MAXK = 8, SRMR_KB = 4;               // channels, bands, bands per lane
+
+struct SrmrTables {
+    const double* chan; const double* Mc;                              // (N, 3) {Re a, Im a, gain}; (N, 10, 2) the lower triangle of M by rows {re, im}
+    const double* mod; const double* Mb;                               // (K, 5) {b0, b1, b2, a1, a2}; (K, 4) {M00, M01, M10, M11}
+    const double* win; const double* erb; const double* cut;           // (4 H); (N); (K)
+    int N, K, H;
+};
+
+__device__ __forceinline__ int srmr_frames(const int32_t* len, int b, int L, int H) {
+    int n = len ? len[b] : L;
+    if (n < 1 || n > L) n = 0;                                          // a bad row is an empty row (the ev_mas_align convention)
+    return n >= 4 * H ? (n - 4 * H) / H + 1 : 0;
+}
+
+// Arena: cst (B, NC, 8, N) {re1, im1 .. re4, im4}; bst (B, NC, 2, N K); part (B, NC, 4, N K)
+struct SrmrChunkParams { const float* x; const int32_t* len; double* cst; double* bst; double* part; SrmrTables t; int L, NC; };
+
+template <int PASS>
+__global__ __launch_bounds__(64) void srmr_chunk_kernel(const SrmrChunkParams p) {
+    STOI_EXACT
+    const int b = blockIdx.y, c = blockIdx.x, lane = threadIdx.x;
+    const int N = p.t.N, K = p.t.K, H = p.t.H, NK = N * K;
+    const int nf = srmr_frames(p.len, b, p.L, H);
+    if (nf == 0 || c >= nf + 3) return;                                 // (uniform) chunk c is no chunk of this row
+    const int j = PASS == 0 ? lane : lane >> 1, k0 = PASS == 0 ? 0 : (lane & 1) * SRMR_KB;
+    const bool live = j < N;
+    const int jj = live ? j : 0;
+    const double ar = live ? p.t.chan[3 * jj] : 0.0, ai = live ? p.t.chan[3 * jj + 1] : 0.0, g = live ? p.t.chan[3 * jj + 2] : 0.0;
+    double* cs = p.cst + ((size_t)b * p.NC + c) * 8 * N + jj;
+    double r1 = 0.0, i1 = 0.0, r2 = 0.0, i2 = 0.0, r3 = 0.0, i3 = 0.0, r4 = 0.0, i4 = 0.0;
+    if (PASS > 0 && live) {
+        r1 = cs[0]; i1 = cs[N]; r2 = cs[2 * N]; i2 = cs[3 * N]; r3 = cs[4 * N]; i3 = cs[5 * N]; r4 = cs[6 * N]; i4 = cs[7 * N];
+    }
+    double b0[SRMR_KB], b1[SRMR_KB], b2[SRMR_KB], a1[SRMR_KB], a2[SRMR_KB], s1[SRMR_KB], s2[SRMR_KB], acc[SRMR_KB][4];
+    double* bs = p.bst + ((size_t)b * p.NC + c) * 2 * NK + (size_t)jj * K;
+    if (PASS > 0) {
+#pragma unroll
+        for (int i = 0; i < SRMR_KB; ++i) {
+            const bool on = live && k0 + i < K;
+            const double* m = p.t.mod + 5 * (on ? k0 + i : 0);
+            b0[i] = on ? m[0] : 0.0; b1[i] = on ? m[1] : 0.0; b2[i] = on ? m[2] : 0.0; a1[i] = on ? m[3] : 0.0; a2[i] = on ? m[4] : 0.0;
+            s1[i] = PASS == 2 && on ? bs[k0 + i] : 0.0;
+            s2[i] = PASS == 2 && on ? bs[NK + k0 + i] : 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[i][q] = 0.0;
+        }
+    }
+    const float* x = p.x + (size_t)b * p.L + (size_t)c * H;             // ((c + 1) H <= (nf + 3) H <= len: the chunk lies inside the row)
+    const double* w = p.t.win;
+#pragma unroll 4
+    for (int t = 0; t < H; ++t) {
+        const double xv = (double)x[t];                                 // (wave-uniform, as the window values below)
+        double nr, ni;                                                  // stage k: s = v + a s, v the stage before's NEW value (stage 1: the sample)
+        nr = xv + (ar * r1 - ai * i1); ni = ar * i1 + ai * r1;        r1 = nr; i1 = ni;
+        nr = r1 + (ar * r2 - ai * i2); ni = i1 + (ar * i2 + ai * r2); r2 = nr; i2 = ni;
+        nr = r2 + (ar * r3 - ai * i3); ni = i2 + (ar * i3 + ai * r3); r3 = nr; i3 = ni;
+        nr = r3 + (ar * r4 - ai * i4); ni = i3 + (ar * i4 + ai * r4); r4 = nr; i4 = ni;
+        if (PASS > 0) {
+            const double e = g * sqrt(r4 * r4 + i4 * i4);
+            double wq[4];
+            if (PASS == 2) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) wq[q] = w[q * H + t];
+            }
+#pragma unroll
+            for (int i = 0; i < SRMR_KB; ++i) {
+                const double y = fma(b0[i], e, s1[i]);                  // transposed direct form II, ev_loudness's fmas
+                s1[i] = fma(-a1[i], y, fma(b1[i], e, s2[i]));
+                s2[i] = fma(-a2[i], y, b2[i] * e);
+                if (PASS == 2) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { const double v = wq[q] * y; acc[i][q] = fma(v, v, acc[i][q]); }
+                }
+            }
+        }
+    }
+    if (!live) return;
+    if (PASS == 0) {
+        cs[0] = r1; cs[N] = i1; cs[2 * N] = r2; cs[3 * N] = i2; cs[4 * N] = r3; cs[5 * N] = i3; cs[6 * N] = r4; cs[7 * N] = i4;
+    } else if (PASS == 1) {
+#pragma unroll
+        for (int i = 0; i < SRMR_KB; ++i) if (k0 + i < K) { bs[k0 + i] = s1[i]; bs[NK + k0 + i] = s2[i]; }
+    } else {
+        double* pt = p.part + ((size_t)b * p.NC + c) * 4 * NK + (size_t)j * K;
+#pragma unroll
+        for (int i = 0; i < SRMR_KB; ++i)
+            if (k0 + i < K) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pt[(size_t)q * NK + k0 + i] = acc[i][q];
+            }
+    }
+}
+
+// The carries.  Slot c of a row's states goes from "what chunk c reaches from zero" to "the state at the start of chunk c", in ascending c.  Four
+// chunks' results are loaded before the chain takes them (the loads do not wait for the chain).
+// Channel: s'[r] = z[r] + sum over k <= r of M[r][k] s[k] as complex numbers, k ascending from z[r]: re = re + (Mre sre - Mim sim),
+// im = im + (Mre sim + Mim sre).
+struct SrmrCarryParams { double* st; const int32_t* len; SrmrTables t; int L, NC; };
+
+__global__ __launch_bounds__(64) void srmr_carry_chan_kernel(const SrmrCarryParams p) {
+    STOI_EXACT
+    const int b = blockIdx.x, j = threadIdx.x, N = p.t.N;
+    const int nf = srmr_frames(p.len, b, p.L, p.t.H);
+    if (nf == 0 || j >= N) return;
+    const int nc = nf + 3;
+    double M[20];
+#pragma unroll
+    for (int i = 0; i < 20; ++i) M[i] = p.t.Mc[20 * j + i];
+    double* st = p.st + (size_t)b * p.NC * 8 * N + j;
+    double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int c0 = 0; c0 < nc; c0 += 4) {
+        double z[4][8];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int r = 0; r < 8; ++r) z[u][r] = c0 + u < nc ? st[((size_t)(c0 + u) * 8 + r) * N] : 0.0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (c0 + u >= nc) break;
+            double n[8];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                double re = z[u][2 * r], im = z[u][2 * r + 1];
+#pragma unroll
+                for (int k = 0; k <= r; ++k) {
+                    const double mr = M[2 * (r * (r + 1) / 2 + k)], mi = M[2 * (r * (r + 1) / 2 + k) + 1];
+                    re = re + (mr * s[2 * k] - mi * s[2 * k + 1]);
+                    im = im + (mr * s[2 * k + 1] + mi * s[2 * k]);
+                }
+                n[2 * r] = re; n[2 * r + 1] = im;
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) { st[((size_t)(c0 + u) * 8 + r) * N] = s[r]; s[r] = n[r]; }
+        }
+    }
+}
+
+// Band: s1' = (z1 + M00 s1) + M01 s2; s2' = (z2 + M10 s1) + M11 s2.
+__global__ __launch_bounds__(256) void srmr_carry_band_kernel(const SrmrCarryParams p) {
+    STOI_EXACT
+    const int b = blockIdx.x, jk = threadIdx.x, NK = p.t.N * p.t.K;
+    const int nf = srmr_frames(p.len, b, p.L, p.t.H);
+    if (nf == 0 || jk >= NK) return;
+    const int nc = nf + 3;
+    const double* m = p.t.Mb + 4 * (jk % p.t.K);
+    const double m00 = m[0], m01 = m[1], m10 = m[2], m11 = m[3];
+    double* st = p.st + (size_t)b * p.NC * 2 * NK + jk;
+    double s1 = 0.0, s2 = 0.0;
+    for (int c0 = 0; c0 < nc; c0 += 4) {
+        double z[4][2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            z[u][0] = c0 + u < nc ? st[(size_t)(c0 + u) * 2 * NK] : 0.0;
+            z[u][1] = c0 + u < nc ? st[(size_t)(c0 + u) * 2 * NK + NK] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (c0 + u >= nc) break;
+            const double n1 = (z[u][0] + m00 * s1) + m01 * s2, n2 = (z[u][1] + m10 * s1) + m11 * s2;
+            st[(size_t)(c0 + u) * 2 * NK] = s1; st[(size_t)(c0 + u) * 2 * NK + NK] = s2;
+            s1 = n1; s2 = n2;
+        }
+    }
+}
+
+// One workgroup per row; thread (j, k) walks the frames in ascending f, then thread 0 closes the row in the header's order.
+struct SrmrRowsParams { const double* part; const int32_t* len; double* frame; double* mean; double* srmr; int32_t* counts; SrmrTables t; int L, NC, NF; };
+
+__global__ __launch_bounds__(256) void srmr_rows_kernel(const SrmrRowsParams p) {
+    STOI_EXACT
+    __shared__ double mean[SRMR_MAXN * SRMR_MAXK];
+    __shared__ double chan[SRMR_MAXN];
+    const int b = blockIdx.x, jk = threadIdx.x, N = p.t.N, K = p.t.K, NK = N * K;
+    const int nf = srmr_frames(p.len, b, p.L, p.t.H);
+    if (jk < NK) {
+        const double* pt = p.part + (size_t)b * p.NC * 4 * NK + jk;     // (not read where nf == 0: there may be no arena)
+        double* fr = p.frame ? p.frame + (size_t)b * p.NF * NK + jk : nullptr;
+        double sum = 0.0;
+#pragma unroll 4
+        for (int f = 0; f < nf; ++f) {
+            const double E = (pt[((size_t)f * 4) * NK] + pt[((size_t)(f + 1) * 4 + 1) * NK]) + (pt[((size_t)(f + 2) * 4 + 2) * NK] + pt[((size_t)(f + 3) * 4 + 3) * NK]);
+            if (fr) fr[(size_t)f * NK] = E;
+            sum = sum + E;
+        }
+        if (fr) for (int f = nf; f < p.NF; ++f) fr[(size_t)f * NK] = 0.0;
+        const double m = nf > 0 ? sum / (double)nf : 0.0;
+        mean[jk] = m;
+        p.mean[(size_t)b * NK + jk] = m;
+    }
+    __syncthreads();
+    if (jk != 0) return;
+    double ratio = 0.0, bw = 0.0;
+    int j90 = 0, ks = 0;
+    if (nf > 0) {
+        double total = 0.0;
+        for (int j = 0; j < N; ++j) {
+            double ch = 0.0;
+            for (int k = 0; k < K; ++k) ch = ch + mean[j * K + k];
+            chan[j] = ch;
+            total = total + ch;
+        }
+        double cum = 0.0;
+        j90 = N - 1;                                                    // (silence: no share exceeds anything)
+        for (int j = 0; j < N; ++j) {
+            cum = cum + chan[j] / total;
+            if (cum > 0.9) { j90 = j; break; }
+        }
+        bw = p.t.erb[j90];
+        int below = 0;
+        for (int k = 0; k < K; ++k) below += p.t.cut[k] < bw ? 1 : 0;
+        ks = min(K, max(min(5, K), below));
+        double num = 0.0, den = 0.0;
+        for (int j = 0; j < N; ++j)
+            for (int k = 0; k < min(4, K); ++k) num = num + mean[j * K + k];
+        for (int j = 0; j < N; ++j)
+            for (int k = 4; k < ks; ++k) den = den + mean[j * K + k];
+        ratio = K > 4 && den > 0.0 ? num / den : 0.0;
+    }
+    p.srmr[2 * b] = ratio; p.srmr[2 * b + 1] = bw;
+    p.counts[3 * b] = nf; p.counts[3 * b + 1] = j90; p.counts[3 * b + 2] = ks;
+}

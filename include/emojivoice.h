@@ -37,6 +37,8 @@
  *   ev_pitch_yin       <- no counterpart: the reference never measures pitch; librosa.yin is the model
  *   ev_dtw             <- no counterpart: the reference never compares what it says with what was recorded; MCD-DTW evaluation is the model
  *   ev_loudness        <- no counterpart; ITU-R BS.1770-4 is the model
+ *   ev_load_srmr       <- no counterpart; Falk, Zheng and Chan 2010 (SRMR) and Hohmann 2002 (complex gammatone) are the model
+ *   ev_srmr            <- no counterpart; Falk, Zheng and Chan 2010 (SRMR) and Hohmann 2002 (complex gammatone) are the model
  *   ev_load_stoi       <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_stoi            <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_load_stft_dist  <- no counterpart; Yamamoto et al. 2020 (multi-resolution STFT loss) is the model
@@ -92,7 +94,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation, ev_load_srmr, ev_srmr (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -512,6 +514,67 @@ int ev_loudness(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_le
                 int sub_len /* S: samples per 100 ms */, const double *coef /* HOST (10) */, double abs_gate /* mean square */,
                 double *d_sub /* (B, NS) or NULL */, double *d_block /* (B, NB) or NULL */,
                 double *d_gated /* (B, 2) */, int32_t *d_counts /* (B, 3) */, void *stream);
+
+/* SRMR on the device: the speech-to-reverberation modulation energy ratio of mono rows (Falk, Zheng and Chan, IEEE TASLP 18(7), 2010), a
+ * NON-INTRUSIVE measure: no clean reference.  A cochlear filterbank, the temporal envelope of every channel, a modulation filterbank over each
+ * envelope, and the energy in the low modulation bands over the energy in the high ones.  ev_load_srmr stores the tables; ev_srmr measures rows that
+ * are ALREADY at the rate the tables were designed for (emojivoice_amd.audio.srmr_tables designs them, audio.srmr resamples).  Everything is
+ * float64, samples are widened, floating-point contraction is off (an fma only where one is written below); ev_set_arithmetic does not reach it.
+ *
+ * ev_load_srmr: HOST tables, copied to the device; N channels, K modulation bands, hop H, frame W = 4 H.  A second load replaces the first.
+ *   chan    (N, 3)  {Re a, Im a, gain} per channel, |a| < 1
+ *   mod     (K, 5)  {b0, b1, b2, a1, a2} per band, a0 = 1; stable iff |a2| < 1 and |a1| < 1 + a2 (ev_loudness's rule and message)
+ *   window  (W)     the frame window
+ *   erb     (N)     the bandwidth of every channel, channels ascending in frequency
+ *   cutoff  (K)     the lower edge of every band
+ * Limits, each violation failing with a message that names it: 1 <= N <= 32; 1 <= K <= 8; H a multiple of 64 with 64 <= H <= 1024; every table
+ * finite and non-NULL.
+ *
+ * DEFINITION.  x[n] is a row's sample n as a double.
+ *   channel   a fourth-order complex gammatone (Hohmann, Acta Acustica 88, 2002): four cascaded one-pole stages s_k[n] = v_{k-1}[n] + a s_k[n-1],
+ *             v_0 = x, v_k = s_k (the value of THIS sample), every row from zero state.  Written out in reals, s = (r, i), a = (ar, ai):
+ *                 r' = v_r + (ar r - ai i);   i' = v_i + (ar i + ai r)        (stage 1, whose input is real: i' = ar i + ai r)
+ *             with every product rounded, then the inner sum or difference, then the outer sum.
+ *   envelope  e[n] = gain * sqrt(r4 r4 + i4 i4).  The analytic filter yields the envelope with no Hilbert transform over the whole row: a stated
+ *             deviation from SRMRpy's real ERB filterbank and FFT Hilbert transform.  Absolute values are this definition's own.
+ *   bands     per band the biquad in transposed direct form II on e, from zero state, with ev_loudness's fmas:
+ *                 m = fma(b0, e, s1);   s1 = fma(-a1, m, fma(b1, e, s2));   s2 = fma(-a2, m, b2 e)
+ *   frames    frame f covers samples [f H, f H + W); nf = (len - W) / H + 1 for len >= W, else 0; NF is the same of L.  Nothing at or behind
+ *             (nf + 3) H <= len is read.  E[f, j, k] = sum over t of (window[t] m_k[f H + t])^2.
+ * PARALLEL IN TIME (the bits depend on it).  A row is cut into chunks of H samples from its first sample; the nf + 3 chunks of a row are all
+ *   whole.  The state at a chunk's start is carried in ascending chunk order as s[c + 1] = M s[c] + z[c]: z[c] the state chunk c reaches from zero,
+ *   M the zero-input transition over H samples, computed by ev_load_srmr on the host in double by running the recurrences above on unit states
+ *   (4 x 4 complex lower triangular per channel, 2 x 2 per band).  Channel row r: from z[r], for k = 0 .. r: re = re + (Mre sre - Mim sim),
+ *   im = im + (Mre sim + Mim sre).  Band: s1' = (z1 + M00 s1) + M01 s2, s2' = (z2 + M10 s1) + M11 s2.  Inside a chunk the recurrences run
+ *   sequentially from the carried state.  The envelope is not linear in the channel state, so there are three passes over the samples with a carry
+ *   between each pair: channels from zero; channels true and bands from zero; everything true.  In the last pass chunk c leaves per (channel,
+ *   band) four sums p[c, q] = sum over its samples t of (window[q H + t] m)^2, q = 0 .. 3, each from 0 by acc = fma(v, v, acc), v the rounded
+ *   product, in ascending t.  E[f] = ((p[f, 0] + p[f + 1, 1]) + (p[f + 2, 2] + p[f + 3, 3])).
+ * PER ROW, sequentially, no atomics:
+ *   Em[j, k]  the sum of E[f, j, k] over ascending f from 0, divided by nf
+ *   shares    ch[j] = sum of Em[j, k] over ascending k; total = sum of ch[j] over ascending j; cum = cum + ch[j] / total over ascending j
+ *   j90       the first channel at which cum > 0.9 (N - 1 when none does: silence);  bw = erb[j90]
+ *   K*        min(K, max(min(5, K), #{k : cutoff[k] < bw}))
+ *   ratio     (sum over ascending j, then ascending k < min(4, K), of Em) / (the same over 4 <= k < K*), one accumulator each; 0 where the
+ *             denominator is 0 or K <= 4 (the caller makes NaN of it)
+ * Outputs of ev_srmr:
+ *   d_frame   (B, NF, N, K) float64 or NULL: E[f, j, k]; 0 for f >= nf
+ *   d_mean    (B, N, K) float64: Em
+ *   d_srmr    (B, 2) float64: {ratio, bw}
+ *   d_counts  (B, 3) int32: {nf, j90, K*}
+ * A row with len < W or len > L is no error and no out-of-bounds access: all its outputs are zeros.  d_len == NULL: every row is L long.
+ * Limits of ev_srmr, each violation failing with a message that names it: tables loaded; 1 <= B <= 65535; L >= 1; d_x, d_mean, d_srmr and d_counts
+ * non-NULL.  A failed call writes nothing and leaves ev_alloc_count unmoved.
+ * Scratch: per (row, chunk) 8 N + 6 N K doubles in an arena of the handle that grows on demand and counts in ev_alloc_count: a second call at the
+ *   same shape allocates nothing; ev_reserve does not cover it.  Six kernel launches on `stream` (one when L < W), no host wait, no copy: the call
+ *   is capturable once the arena has its size.
+ * The same inputs give the same bits in every output: a row alone, inside a batch, as the d_len prefix of a longer row with anything (NaN
+ *   included) behind it, in a second call, under every ev_set_arithmetic setting, and from a captured graph. */
+int ev_load_srmr(ev_handle *h, const double *chan /* HOST (N, 3) */, const double *mod /* HOST (K, 5) */, const double *window /* HOST (4 H) */,
+                 const double *erb /* HOST (N) */, const double *cutoff /* HOST (K) */, int N, int K, int H);
+int ev_srmr(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L,
+            double *d_frame /* (B, NF, N, K) or NULL */, double *d_mean /* (B, N, K) */, double *d_srmr /* (B, 2) */,
+            int32_t *d_counts /* (B, 3) */, void *stream);
 
 /* STOI and ESTOI on the device: short-time objective intelligibility of a processed row y against the clean, sample-aligned row x (Taal,
  * Hendriks, Heusdens and Jensen, IEEE TASL 19(7), 2011) and its extended form (Jensen and Taal, IEEE/ACM TASLP 24(11), 2016), for rows already

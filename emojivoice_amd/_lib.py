@@ -46,6 +46,7 @@ EXPORTS = [
     "ev_functionals", "ev_modulation",
     "ev_load_auditory", "ev_auditory",
     "ev_load_srmr", "ev_srmr",
+    "ev_load_speech_rate", "ev_speech_rate",
 ]
 
 
@@ -185,6 +186,8 @@ def load_library() -> C.CDLL:
     lib.ev_auditory.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp, vp]
     lib.ev_load_srmr.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32]
     lib.ev_srmr.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.ev_load_speech_rate.argtypes = [vp, vp, i32, i32]
+    lib.ev_speech_rate.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -505,6 +508,38 @@ class Engine:
         self._check(self.lib.ev_srmr(self.h, x.data_ptr(), _ptr(ln), B, L, _ptr(frame), mean.data_ptr(), out.data_ptr(), counts.data_ptr(),
                                      _stream_ptr()), "ev_srmr")
         return frame, mean, out, counts
+
+    def load_speech_rate(self, window, hop: int) -> None:
+        """The geometry of ``speech_rate`` (ev_load_speech_rate): ``window`` (W,) float64 on the host (``audio.intensity_window``), W even with
+        8 <= W <= 4096; ``hop`` a multiple of 64 with 64 <= hop <= 1024."""
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float64).reshape(-1))
+        self._check(self.lib.ev_load_speech_rate(self.h, w.ctypes.data, int(w.shape[0]), int(hop)), "ev_load_speech_rate")
+        self.speech_rate_geometry = (int(w.shape[0]), int(hop))
+
+    def speech_rate(self, x, lengths, voiced, power_floor: float, rank_fraction: float, silence_ratio: float, dip_ratio: float, min_pause: int,
+                    min_sound: int, want_power: bool = True, want_mark: bool = True):
+        """Power contour, sounding / silent segmentation and syllable nuclei of every row of ``x`` (B, L) (ev_speech_rate, after
+        load_speech_rate): (power (B, NF) float64 or None, mark (B, NF) uint8 {1 sounding, 2 raw, 4 candidate, 8 nucleus} or None, stat (B, 4)
+        float64 {ref, thr, mean, sd of the pause lengths in frames}, count (B, 8) int32 {frames, sounding, pauses, pause frames, candidates,
+        nuclei, leading, trailing silent frames}) on the device.  ``lengths`` (B,): samples per row (None: L); ``voiced`` (B, NF) uint8 / bool or
+        None: the frames a nucleus may lie on."""
+        if not hasattr(self, "speech_rate_geometry"):
+            raise EvLibraryError("speech_rate: tables not loaded (load_speech_rate)")
+        x, B, L, ln = self._rows(x, lengths, "speech_rate")
+        NF = -(-L // self.speech_rate_geometry[1])
+        vc = None
+        if voiced is not None:
+            vc = torch.as_tensor(voiced).to(x.device).ne(0).to(torch.uint8).contiguous()
+            if tuple(vc.shape) != (B, NF):
+                raise ValueError(f"speech_rate: voiced must be ({B}, {NF}), got {tuple(vc.shape)}")
+        power = torch.empty((B, NF), dtype=torch.float64, device=x.device) if want_power else None
+        mark = torch.empty((B, NF), dtype=torch.uint8, device=x.device) if want_mark else None
+        stat = torch.empty((B, 4), dtype=torch.float64, device=x.device)
+        count = torch.empty((B, 8), dtype=torch.int32, device=x.device)
+        self._check(self.lib.ev_speech_rate(self.h, x.data_ptr(), _ptr(ln), _ptr(vc), B, L, float(power_floor), float(rank_fraction),
+                                            float(silence_ratio), float(dip_ratio), int(min_pause), int(min_sound), _ptr(power), _ptr(mark),
+                                            stat.data_ptr(), count.data_ptr(), _stream_ptr()), "ev_speech_rate")
+        return power, mark, stat, count
 
     def load_stoi(self, window, twiddle, bands, hop: int, n_fft: int, seg_frames: int) -> None:
         """The tables of ``stoi`` (ev_load_stoi), all on the host: ``window`` (W,) float64 with W = 2 hop, ``twiddle`` (n_fft, 2) float64

@@ -896,6 +896,101 @@ def srmr(y, sr: int = 22050, lengths=None, rows: Optional[Callable] = None, ener
     return res
 
 
+# ---- speech rate and pauses: syllable nuclei (De Jong and Wempe 2009) --------------------------------------------------------------------------------
+SPEECH_RATE_POWER_FLOOR = 1e-12                    # a frame at or under this power is silent whatever the row's level (digital silence)
+SPEECH_RATE_MAX_FRAMES = 16384                     # ``ev_speech_rate``'s frame limit: 190 s at hop 256 and 22.05 kHz
+
+
+def intensity_window(W: int) -> np.ndarray:
+    """Praat's intensity window, ``np.kaiser(W, 20.24)`` in float64."""
+    return np.kaiser(int(W), 20.24).astype(np.float64)
+
+
+def speech_rate_geometry(sr, hop_length: int = 256, min_pitch: float = 50.0) -> Tuple[int, int]:
+    """(W, H) of ``speech_rate``: the window of 3.2 / min_pitch seconds (Praat's intensity analysis) rounded to the nearest even number of
+    samples, and the hop.  The device wants 8 <= W <= 4096 and H a multiple of 64 with 64 <= H <= 1024."""
+    if not sr > 0 or not min_pitch > 0:
+        raise ValueError(f"speech_rate_geometry: sr and min_pitch must be positive (got {sr}, {min_pitch})")
+    W, H = 2 * int(round(3.2 / float(min_pitch) * float(sr) / 2.0)), int(hop_length)
+    if not 8 <= W <= 4096:
+        raise ValueError(f"speech_rate_geometry: the window of 3.2 / {min_pitch:g} s at {sr} Hz is {W} samples, outside 8 .. 4096")
+    if H != hop_length or H % 64 or not 64 <= H <= 1024:
+        raise ValueError(f"speech_rate_geometry: hop_length={hop_length} must be a multiple of 64 with 64 <= hop_length <= 1024")
+    return W, H
+
+
+def _speech_rate_engine(device: torch.device, W: int, H: int) -> Engine:
+    return _cached_engine(device, ("speech_rate", W, H), lambda eng: eng.load_speech_rate(intensity_window(W), H))
+
+
+def _device_speech_rate_rows(x, lengths, voiced, W, H, power_floor, rank_fraction, silence_ratio, dip_ratio, min_pause, min_sound):
+    return _speech_rate_engine(x.device, W, H).speech_rate(x, lengths, voiced, power_floor, rank_fraction, silence_ratio, dip_ratio, min_pause,
+                                                           min_sound)
+
+
+@torch.inference_mode()
+def speech_rate(y, sr: int = 22050, voiced=None, lengths=None, hop_length: int = 256, silence_db: float = 25.0, dip_db: float = 2.0,
+                min_pause_s: float = 0.3, min_sound_s: float = 0.1, rank_fraction: float = 0.01, rows: Optional[Callable] = None):
+    """How fast ``y`` (1-D or (B, L) at ``sr`` on the GPU) speaks and where it pauses, by De Jong and Wempe's (2009) syllable nuclei on the device
+    (``ev_speech_rate``; no torch fallback), on ``pitch_yin``'s frames: the power under Praat's intensity window, frames more than ``silence_db``
+    under the 99 % quantile (``rank_fraction``) silent, silences under ``min_pause_s`` filled and sounds under ``min_sound_s`` dropped, and as
+    nuclei the local peaks of the power that are followed by a dip of ``dip_db`` and lie on a frame of ``voiced`` ((B, F) as ``pitch_yin``
+    returns it; None: every frame).  The last peak counts, which the published script never does.  -> {"nuclei", "pauses", "frames" (B,) int32;
+    "speech_rate" (nuclei per second of the row), "articulation_rate" (nuclei per sounding second), "phonation_ratio" (sounding over all
+    frames), "pause_mean_s", "pause_sd_s" (B,) float64, a rate over zero seconds NaN; "intensity_db" (B, F) float64, 10 log10 of the power
+    (-inf where it is 0); "mark" (B, F) uint8: 1 sounding, 2 raw, 4 candidate, 8 nucleus; "sounding", "leading", "trailing" (B,) int32 frames};
+    a 1-D input gives B = 1.  ``rows``: the per-batch measurement, (x, lengths, voiced, W, H, power_floor, rank_fraction, silence_ratio,
+    dip_ratio, min_pause, min_sound) -> (power (B, F), mark (B, F), stat (B, 4), count (B, 8)) — the device call unless given."""
+    if not torch.is_tensor(y) or y.dim() not in (1, 2) or y.shape[-1] < 1:
+        raise ValueError("speech_rate: y must be a non-empty tensor, 1-D or (B, L)")
+    if rows is None and not y.is_cuda:
+        raise EvLibraryError("speech_rate runs on a ROCm GPU only (no CPU fallback): move y to the GPU")
+    if not silence_db > 0 or not dip_db >= 0 or not min_pause_s > 0 or not min_sound_s > 0 or not 0 <= rank_fraction < 1:
+        raise ValueError(f"speech_rate: silence_db > 0, dip_db >= 0, min_pause_s > 0, min_sound_s > 0 and 0 <= rank_fraction < 1 expected (got "
+                         f"{silence_db}, {dip_db}, {min_pause_s}, {min_sound_s}, {rank_fraction})")
+    W, H = speech_rate_geometry(sr, hop_length)
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    F = -(-x.shape[1] // H)
+    if F > SPEECH_RATE_MAX_FRAMES:
+        raise ValueError(f"speech_rate: {F} frames over the limit of {SPEECH_RATE_MAX_FRAMES} ({SPEECH_RATE_MAX_FRAMES * H / float(sr):.0f} s)")
+    ln = None
+    if lengths is not None and y.dim() == 2:
+        ln = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
+        if ln.numel() != x.shape[0]:
+            raise ValueError(f"speech_rate: {x.shape[0]} lengths expected, got {ln.numel()}")
+    if voiced is not None:
+        voiced = torch.as_tensor(voiced)
+        voiced = voiced.unsqueeze(0) if voiced.dim() == 1 else voiced
+        if tuple(voiced.shape) != (x.shape[0], F):
+            raise ValueError(f"speech_rate: voiced must be ({x.shape[0]}, {F}), got {tuple(voiced.shape)}")
+    frame_s = H / float(sr)
+    clamp = lambda s: min(max(int(round(s / frame_s)), 1), 4096)
+    power, mark, stat, count = (rows or _device_speech_rate_rows)(x, ln, voiced, W, H, SPEECH_RATE_POWER_FLOOR, float(rank_fraction),
+                                                                 10.0 ** (-float(silence_db) / 10.0), 10.0 ** (float(dip_db) / 10.0),
+                                                                 clamp(min_pause_s), clamp(min_sound_s))
+    power, stat, count = torch.as_tensor(power, dtype=torch.float64), torch.as_tensor(stat, dtype=torch.float64), torch.as_tensor(count)
+    c = count.to(torch.float64).to(stat.device)
+    nan = torch.full_like(c[:, 0], float("nan"))
+    over = lambda a, b: torch.where(b > 0, a / torch.where(b > 0, b, torch.ones_like(b)), nan)
+    return {"nuclei": count[:, 5], "pauses": count[:, 2], "frames": count[:, 0], "sounding": count[:, 1], "leading": count[:, 6],
+            "trailing": count[:, 7], "speech_rate": over(c[:, 5], c[:, 0] * frame_s), "articulation_rate": over(c[:, 5], c[:, 1] * frame_s),
+            "phonation_ratio": over(c[:, 1], c[:, 0]), "pause_mean_s": stat[:, 2] * frame_s, "pause_sd_s": stat[:, 3] * frame_s,
+            "pause_s": c[:, 3] * frame_s, "intensity_db": 10.0 * torch.log10(power), "mark": torch.as_tensor(mark)}
+
+
+def speech_rate_difference(a, b):
+    """What ``speech_rate`` says of two renderings of the same text, row by row (b against a): {"rate_ratio": speech rate of b over a, minus 1
+    (0.15: b is 15 % faster), "articulation_ratio": the same of the articulation rates, "pauses_delta": pauses of b minus a, "pause_s_delta":
+    the time spent in pauses, b minus a, in seconds}; NaN where a rate of a is 0 or NaN."""
+    ra, rb = torch.as_tensor(a["speech_rate"]), torch.as_tensor(b["speech_rate"]).to(torch.as_tensor(a["speech_rate"]).device)
+    aa, ab = torch.as_tensor(a["articulation_rate"]), torch.as_tensor(b["articulation_rate"]).to(ra.device)
+    nan = torch.full_like(ra, float("nan"))
+    ratio = lambda p, q: torch.where(p > 0, q / torch.where(p > 0, p, torch.ones_like(p)) - 1.0, nan)
+    return {"rate_ratio": ratio(ra, rb), "articulation_ratio": ratio(aa, ab),
+            "pauses_delta": torch.as_tensor(b["pauses"]).cpu().to(torch.int64) - torch.as_tensor(a["pauses"]).cpu().to(torch.int64),
+            "pause_s_delta": torch.as_tensor(b["pause_s"]).to(ra.device) - torch.as_tensor(a["pause_s"])}
+
+
 # ---- spectral-magnitude distance: multi-resolution STFT (Yamamoto, Song, Kim 2020) and log-spectral distance ---------------------------------------
 MSTFT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))   # (n_fft, hop, win): the published defaults
 MSTFT_POWER_FLOOR = 1e-7                                                    # the clamp of |X|^2 before the root and the logarithm

@@ -32,6 +32,8 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --loudness_report clean/filelist.txt                                   # clean/filelist.txt.loudness.json: BS.1770 LUFS per file and per speaker
     python -m emojivoice_amd.cli --reverb_report clean/filelist.txt                                     # clean/filelist.txt.srmr.json: SRMR (reverberation, no clean reference needed) per file and per speaker
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --srmr                                      # ... and, per pair, the SRMR of both sides and their difference
+    python -m emojivoice_amd.cli --prosody_report clean/filelist.txt --rhythm                           # ... and, per file and per speaker, speech rate, articulation rate, pauses and phonation ratio (syllable nuclei)
+    python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --rhythm                                    # ... and, per pair, rate and pauses of both sides and their differences
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
     python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000          # clean/filelist.txt.vocoder.json: STOI / ESTOI, mel L1 and loudness shift of copy synthesis
     python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000 --spectral_distance   # + multi-resolution STFT distance and log-spectral distance
@@ -91,6 +93,9 @@ def validate_args(args):
     if getattr(args, "modulation", False):
         assert getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None), \
             "--modulation is an option of --voice_report and of --evaluate_pairs"
+    if getattr(args, "rhythm", False):
+        assert getattr(args, "prosody_report", None) or getattr(args, "evaluate_pairs", None), \
+            "--rhythm is an option of --prosody_report and of --evaluate_pairs"
     if getattr(args, "track_formants", False):
         assert (getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None)) and (getattr(args, "formants", False) or getattr(args, "harmonics", False)), \
             "--track_formants is an option of --formants and of --harmonics under --voice_report and --evaluate_pairs"
@@ -461,19 +466,26 @@ def prosody_report(args, device):
     gains "pitch_method": "pyin"), --batch_size files at a time (padded to the longest,
     each row with its own length).  FILELIST.prosody.json receives, per file, the numbers of audio.prosody_statistics (voiced fraction,
     f0 median / 5th / 95th percentile in Hz, the 5-to-95 range in semitones; null where a file has no voiced frame) and, per speaker,
-    the same over that speaker's POOLED voiced frames, with the file count."""
+    the same over that speaker's POOLED voiced frames, with the file count.
+    --rhythm adds per file "rhythm": RHYTHM_REPORT_KEYS of audio.speech_rate (syllable nuclei on the same frames, voiced by the tracker this
+    report ran; null for a rate over zero seconds) with "nuclei", and per speaker "rhythm": their plain means over the files that have them
+    and "pooled_speech_rate", the speaker's nuclei over the speaker's seconds."""
     from . import audio
 
+    want_rhythm = getattr(args, "rhythm", False)
     files, pooled, frames_of = [], {}, {}
     for chunk, batch, lens in filelist_batches(args.prosody_report, args.batch_size, PROSODY_SR, device):
         out = pitch_tracker(args)(batch, PROSODY_SR, hop_length=PROSODY_HOP, lengths=lens)
         n_frames = [-(-n // PROSODY_HOP) for n in lens]
         st = {k: v.cpu() for k, v in audio.prosody_statistics(out["f0"], out["voiced"], n_frames).items()}
+        rhythm = rhythm_rows(audio, args, batch, PROSODY_SR, PROSODY_HOP, lens, out["voiced"]) if want_rhythm else None
         for r, (wav, spk, _) in enumerate(chunk):
             spk = spk if spk is not None else "0"
             rec = {"path": wav, "speaker": spk, "seconds": lens[r] / float(PROSODY_SR), "frames": n_frames[r]}
             for k, v in st.items():
                 rec[k] = None if math.isnan(float(v[r])) else float(v[r])
+            if want_rhythm:
+                rec["rhythm"] = rhythm[r]
             files.append(rec)
             pooled.setdefault(spk, []).append(out["f0"][r, : n_frames[r]][out["voiced"][r, : n_frames[r]]])
             frames_of[spk] = frames_of.get(spk, 0) + n_frames[r]
@@ -481,6 +493,11 @@ def prosody_report(args, device):
     for spk, parts in pooled.items():
         v = torch.cat(parts)
         speakers[spk] = {"files": len(parts), "voiced_fraction": v.numel() / max(frames_of[spk], 1), **pitch_summary(v)}
+        if want_rhythm:
+            mine = [f for f in files if f["speaker"] == spk]
+            secs = math.fsum(f["frames"] * PROSODY_HOP / float(PROSODY_SR) for f in mine)
+            speakers[spk]["rhythm"] = {**rhythm_means([f["rhythm"] for f in mine]),
+                                       "pooled_speech_rate": sum(f["rhythm"]["nuclei"] for f in mine) / secs if secs > 0 else None}
     rep = {"sample_rate": PROSODY_SR, "hop_length": PROSODY_HOP, "files": files, "speakers": speakers}
     if pitch_method(args) != "yin":
         rep["pitch_method"] = pitch_method(args)
@@ -494,6 +511,33 @@ def prosody_report(args, device):
         print(f"[i] speaker {k}: {v['files']} files, voiced {100 * v['voiced_fraction']:.0f} %, {pitch}")
     print(f"[+] Prosody report saved: {Path(out_path).resolve()}")
     return rep
+
+
+RHYTHM_REPORT_KEYS = ("speech_rate", "articulation_rate", "pauses", "pause_mean_s", "phonation_ratio")
+
+
+def rhythm_rows(audio, args, sig, sr, hop, lens, voiced):
+    """Per row of ``sig`` {RHYTHM_REPORT_KEYS ..., "nuclei", "pause_s"} of audio.speech_rate under the tracker's voicing (None for NaN)."""
+    out = audio.speech_rate(sig, sr, voiced=voiced, lengths=lens, hop_length=hop, rows=getattr(args, "speech_rate_rows", None))
+    cols = {k: torch.as_tensor(out[k]).cpu() for k in RHYTHM_REPORT_KEYS + ("nuclei", "pause_s")}
+    val = lambda k, v: int(v) if k in ("pauses", "nuclei") else (None if math.isnan(float(v)) else float(v))
+    return [{k: val(k, v[r]) for k, v in cols.items()} for r in range(sig.shape[0])]
+
+
+def rhythm_means(rows, keys=RHYTHM_REPORT_KEYS):
+    """{key: the plain mean over the rows that have it, or None}"""
+    out = {}
+    for k in keys:
+        d = [row[k] for row in rows if row[k] is not None]
+        out[k] = math.fsum(d) / len(d) if d else None
+    return out
+
+
+def rhythm_difference(a, b):
+    """audio.speech_rate_difference on two report rows: {"rate_ratio" (0.15: the synthesis is 15 % faster), "pauses_delta", "pause_s_delta"}."""
+    ok = a["speech_rate"] is not None and a["speech_rate"] > 0 and b["speech_rate"] is not None
+    return {"rate_ratio": b["speech_rate"] / a["speech_rate"] - 1.0 if ok else None, "pauses_delta": b["pauses"] - a["pauses"],
+            "pause_s_delta": b["pause_s"] - a["pause_s"]}
 
 
 Family = collections.namedtuple("Family", "report_flag pairs_flag block figures frames_key counts used measure finish", defaults=(None,))
@@ -1023,11 +1067,15 @@ def evaluate_pairs(args, device):
     less, i.e. is over-smoothed); per speaker and overall the mean and mean absolute difference per figure and the plain means of the two
     distances over the pairs that have them.
     --srmr adds per pair "srmr": {"recorded", "synthesised", "delta"}, audio.srmr of each side (non-intrusive: it needs no alignment; null for
-    a side without a figure) and synthesised - recorded; per speaker and overall "srmr": the means of the three over the pairs that have them."""
+    a side without a figure) and synthesised - recorded; per speaker and overall "srmr": the means of the three over the pairs that have them.
+    --rhythm adds per pair "rhythm": {"recorded", "synthesised"} (RHYTHM_REPORT_KEYS of audio.speech_rate with "nuclei" and "pause_s", voiced by
+    the tracker of this report) and "delta": {"rate_ratio" (0.15: the synthesis speaks 15 % faster), "pauses_delta", "pause_s_delta"}; per
+    speaker and overall "rhythm": the means of the three differences over the pairs that have them."""
     from . import audio
 
     want_mod = getattr(args, "modulation", False)
     want_srmr = getattr(args, "srmr", False)
+    want_rhythm = getattr(args, "rhythm", False)
 
     entries = parse_pairs(args.evaluate_pairs)
     if not entries:
@@ -1054,6 +1102,8 @@ def evaluate_pairs(args, device):
             pitch["modulation"] = [row["modulation"] for row in voice_modulation_of(audio, pitch, got, sig, sr, hop, clipped, frames)]
         if want_srmr:
             pitch["srmr"] = [srmr_value(v) for v in audio.srmr(sig, sr, lengths=clipped, rows=getattr(args, "srmr_rows", None))["srmr"].cpu()]
+        if want_rhythm:
+            pitch["rhythm"] = rhythm_rows(audio, args, sig, sr, hop, clipped, pitch["voiced"])
         return cep, frames, pitch
 
     for b0 in range(0, len(entries), args.batch_size):
@@ -1095,6 +1145,9 @@ def evaluate_pairs(args, device):
             if want_srmr:
                 va, vb = pitch_a["srmr"][r], pitch_b["srmr"][r]
                 records[-1]["srmr"] = {"recorded": va, "synthesised": vb, "delta": None if va is None or vb is None else vb - va}
+            if want_rhythm:
+                va, vb = pitch_a["rhythm"][r], pitch_b["rhythm"][r]
+                records[-1]["rhythm"] = {"recorded": va, "synthesised": vb, "delta": rhythm_difference(va, vb)}
 
     def means(recs):
         out = evaluation_means(recs)
@@ -1117,6 +1170,8 @@ def evaluate_pairs(args, device):
             for k in ("recorded", "synthesised", "delta"):
                 d = [r["srmr"][k] for r in recs if r["srmr"][k] is not None]
                 out["srmr"][k] = math.fsum(d) / len(d) if d else None
+        if want_rhythm:
+            out["rhythm"] = rhythm_means([r["rhythm"]["delta"] for r in recs], ("rate_ratio", "pauses_delta", "pause_s_delta"))
         return out
 
     by_spk = {}
@@ -1203,6 +1258,9 @@ def cli(argv=None):
                    "batch; needs no checkpoint)")
     p.add_argument("--srmr", action="store_true", help="--evaluate_pairs: add \"srmr\" per pair (the SRMR of the recording, of the synthesis and their "
                    "difference; no alignment needed) and the means per speaker and overall")
+    p.add_argument("--rhythm", action="store_true", help="--prosody_report and --evaluate_pairs: add \"rhythm\" (speech rate and articulation rate in "
+                   "syllable nuclei per second, pauses, mean pause and phonation ratio by De Jong and Wempe's method on the device, voiced by the "
+                   "report's pitch tracker); per pair both sides and the relative rate difference, the pause-count and the pause-time difference")
     p.add_argument("--target_lufs", type=float, default=None, help="--prepare_dataset: level every recording to this integrated loudness (BS.1770, e.g. -23) "
                    "instead of to --peak; the gain is capped where the peak would pass --peak, and the gain and the cap go into FILELIST.durations.json")
     p.add_argument("--vocoder_report", type=str, default=None, help="vocoder evaluation instead of synthesis: a filelist 'path|spk|text' -> FILELIST.vocoder.json: "

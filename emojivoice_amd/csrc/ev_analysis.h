@@ -1,5 +1,5 @@
 // Host entry points of the analysis side: resampling, dataset statistics, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness,
-// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals, auditory descriptors, formant tracks and SRMR (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
+// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals, auditory descriptors, formant tracks, SRMR and speech rate (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
 // after ev_handle, fail / HIPCHK / enter, dev_upload, drop_owned, scratch_acquire and launch<>.  None of these calls runs on the engine's conv
 // path; ev_load_mel_basis, ev_mel_spectrogram, ev_denoise and ev_stft_magnitude do, and stay in ev_engine.hip.
 #pragma once
@@ -1012,6 +1012,65 @@ int ev_modulation(ev_handle* h, const double* d_v, const uint8_t* d_mask, const 
     // wr (8 B a frame), the runs' window sums and packed bounds (12 B a run), the pooled spectrum and weights (128 x 12 B), 24 words: 45.6 KiB at 4096
     const size_t smem = ((size_t)F + (F & 1) + p.MR + 128) * sizeof(double) + ((size_t)p.MR + 128 + 24) * sizeof(int);
     launch<modulation_kernel>(h->device, dim3((unsigned)K, (unsigned)B), dim3(256), smem, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Speech rate and pauses: the power contour, the sounding / silent segmentation and the syllable nuclei of every row (speech_power_kernel and
+// speech_rate_rows_kernel, ev_analysis_kernels.h; the definition: include/emojivoice.h).  A load owns one device block, the window; its sum is
+// formed here, once, in ascending order.  Arena of a call without d_power: the power contour, B x NF doubles.
+int ev_load_speech_rate(ev_handle* h, const double* window, int W, int H) {
+    STOI_EXACT
+    if (enter(h)) return 1;
+    if (!window) return fail(h, "ev_load_speech_rate: window must be non-null (HOST, W doubles)");
+    if (W < 8 || W > 4096 || W % 2) return fail(h, "ev_load_speech_rate: W=%d must be even with 8 <= W <= 4096", W);
+    if (H < 64 || H > 1024 || H % 64) return fail(h, "ev_load_speech_rate: H=%d must be a multiple of 64 with 64 <= H <= 1024", H);
+    if (check_finite(h, __func__, "window", window, W)) return 1;
+    double sw = 0.0;
+    for (int j = 0; j < W; ++j) sw = sw + window[j];
+    if (!(sw > 0.0) || !std::isfinite(sw)) return fail(h, "ev_load_speech_rate: the window's sum sw=%g must be finite and greater than 0", sw);
+    RateW t;                                                            // the new block first: a failed load leaves the tables in use as they are
+    if (dev_upload(h, std::vector<double>(window, window + W), &t.win)) return 1;
+    ++h->n_allocs;
+    t.W = W; t.H = H; t.sw = sw; t.loaded = true;
+    RateW& cur = h->rate;
+    if (cur.loaded && drop_owned(h, {(void*)cur.win})) return 1;
+    cur = t;
+    return 0;
+}
+
+int ev_speech_rate(ev_handle* h, const float* d_x, const int32_t* d_len, const uint8_t* d_voiced, int B, int L, double power_floor,
+                   double rank_fraction, double silence_ratio, double dip_ratio, int min_pause, int min_sound, double* d_power, uint8_t* d_mark,
+                   double* d_stat, int32_t* d_count, void* stream) {
+    if (enter(h)) return 1;
+    const RateW& w = h->rate;
+    if (!w.loaded) return fail(h, "ev_speech_rate: tables not loaded (ev_load_speech_rate)");
+    if (check_batch(h, __func__, B)) return 1;
+    if (L < 1) return fail(h, "ev_speech_rate: L=%d must be at least 1", L);
+    const int NF = frames_of(L, w.H);
+    if (NF > RATE_MAXF) return fail(h, "ev_speech_rate: NF=%d frames (L=%d at H=%d) over the limit NF <= %d", NF, L, w.H, RATE_MAXF);
+    if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_speech_rate: power_floor=%g must be finite and greater than 0", power_floor);
+    if (!(rank_fraction >= 0.0 && rank_fraction < 1.0)) return fail(h, "ev_speech_rate: rank_fraction=%g outside 0 <= rank_fraction < 1", rank_fraction);
+    if (!(silence_ratio > 0.0 && silence_ratio < 1.0)) return fail(h, "ev_speech_rate: silence_ratio=%g outside 0 < silence_ratio < 1", silence_ratio);
+    if (!(dip_ratio >= 1.0) || !std::isfinite(dip_ratio)) return fail(h, "ev_speech_rate: dip_ratio=%g must be finite and at least 1", dip_ratio);
+    if (min_pause < 1 || min_pause > 4096) return fail(h, "ev_speech_rate: min_pause=%d outside 1 <= min_pause <= 4096", min_pause);
+    if (min_sound < 1 || min_sound > 4096) return fail(h, "ev_speech_rate: min_sound=%d outside 1 <= min_sound <= 4096", min_sound);
+    if (!d_x) return fail(h, "ev_speech_rate: d_x must be non-null");
+    if (!d_stat) return fail(h, "ev_speech_rate: d_stat must be non-null");
+    if (!d_count) return fail(h, "ev_speech_rate: d_count must be non-null");
+    h->stream = (hipStream_t)stream;
+    double* power = d_power;
+    if (!power) {
+        if (scratch_acquire(h, h->rate_ws, (size_t)B * NF * sizeof(double))) return 1;
+        power = (double*)h->rate_ws.p;
+    }
+    RatePowerParams pp{d_x, d_len, w.win, power, L, NF, w.W, w.H, w.sw};
+    // the tile's span of samples as float: 7.4 KiB at H = 64, W = 1024; 76 KiB at H = 1024, W = 4096
+    launch<speech_power_kernel>(h->device, dim3((unsigned)((NF - 1) / RATE_T + 1), (unsigned)B), dim3(256),
+                                ((size_t)(RATE_T - 1) * w.H + w.W) * sizeof(float), h->stream, pp);
+    RateRowsParams pr{power, d_len, d_voiced, d_mark, d_stat, d_count, L, NF, w.H, min_pause, min_sound, power_floor, rank_fraction, silence_ratio, dip_ratio};
+    // the row's power (8 B a frame) and flags (1 B), 32 doubles and 224 words of hand-over: 145.1 KiB at NF = 16384
+    launch<speech_rate_rows_kernel>(h->device, dim3((unsigned)B), dim3(1024), (size_t)9 * NF + 1152, h->stream, pr);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -3427,3 +3427,299 @@ __global__ __launch_bounds__(256) void srmr_rows_kernel(const SrmrRowsParams p) 
     p.srmr[2 * b] = ratio; p.srmr[2 * b + 1] = bw;
     p.counts[3 * b] = nf; p.counts[3 * b + 1] = j90; p.counts[3 * b + 2] = ks;
 }
+
+// ---------------------------------------------------------------------------
+// Speech rate and pauses (ev_speech_rate): De Jong and Wempe's syllable nuclei on ev_pitch_yin's frame grid: a power contour, a sounding / silent
+// segmentation with minimum durations, and the local peaks of the power that are followed by a dip and are voiced (the definition:
+// include/emojivoice.h).  All float64, contraction OFF (STOI_EXACT), no atomics.  Two launches.
+//   speech_power_kernel      grid (tiles of RATE_T frames, B), 256 threads.  The tile's span of (T - 1) H + W samples is staged ONCE in LDS as
+//            float (zero outside [0, len): nothing at or behind len is read), so a sample leaves global memory once per tile and not W / H
+//            times.  A wave per frame, lane = slot: term j belongs to lane j mod 64, which adds its terms in ascending j, then
+//            formant_wave_sum's xor tree (32, 16, 8, 4, 2, 1), which leaves the same bits in every lane.  A wave takes its four frames TOGETHER:
+//            four independent chains per lane that share every load of the window, which is read from global memory (W doubles, coalesced,
+//            resident in L2 for the whole grid).  Frames in [nf, NF) are written as zeros.
+//   speech_rate_rows_kernel  grid B, 1024 threads, the row's power in dynamic LDS (8 B a frame) beside one byte of flags per frame and 1152 bytes
+//            of hand-over: 9 NF + 1152 bytes, 145.1 KiB at NF = 16384.  Frame f belongs to thread f mod 1024 of tile f / 1024 in every phase.
+//            (1) the (k + 1)-th largest power by 64 passes over the bit patterns (held in registers, 16 a thread), most significant bit first: a
+//            ballot per wave and tile counts the frames
+//            that agree with the prefix found so far and carry the bit, the 16 waves' counts go through LDS (two alternating sets: one barrier
+//            a pass).  (2) every decision on runs is a FORWARD pass and a BACKWARD pass over the tiles: forward, functionals_kernel's inclusive
+//            max-scan of "a run starts here" brings the start to the run's last frame, whose thread knows the length and leaves the decision in
+//            bit 7 of its flag byte; backward, the same scan on mirrored indices brings every frame the last frame of its run, where it reads the
+//            decision.  Step (a) reads bit 1 (raw) and writes bit 2, step (b) reads bit 2 and writes bit 0 (snd), so no pass reads a bit that it
+//            writes.  (3) a forward pass over the runs of snd counts the pauses and marks the candidates (bit 2); (4) a backward SEGMENTED
+//            min-scan, whose segments end in front of every candidate, brings candidate c the minimum over (c, e).  (5) integer reductions.
+constexpr int RATE_T = 16;                                              // frames per tile of speech_power_kernel
+constexpr int RATE_MAXF = 16384;                                        // frames per row: the row's power stays in LDS
+
+__device__ __forceinline__ int rate_frames(const int32_t* len, int b, int L, int H, int* n_out) {
+    const int n = len ? len[b] : L;
+    *n_out = n;
+    return n < 1 || n > L ? 0 : (n + H - 1) / H;                        // (n <= L <= RATE_MAXF * 1024)
+}
+
+struct RatePowerParams { const float* x; const int32_t* len; const double* win; double* power; int L, NF, W, H; double sw; };
+
+__global__ __launch_bounds__(256) void speech_power_kernel(const RatePowerParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) float rate_xs[];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, b = blockIdx.y, f0 = blockIdx.x * RATE_T;
+    const int W = p.W, H = p.H;
+    int n;
+    const int nf = rate_frames(p.len, b, p.L, H, &n);
+    const int nt = min(RATE_T, nf - f0);                                // the tile's live frames (none where <= 0)
+    double* out = p.power + (size_t)b * p.NF;
+    if (nt <= 0) {                                                      // (uniform; before any barrier)
+        if (t < RATE_T && f0 + t < p.NF) out[f0 + t] = 0.0;
+        return;
+    }
+    const float* xr = p.x + (size_t)b * p.L;
+    const int base = f0 * H + H / 2 - W / 2, span = (RATE_T - 1) * H + W;
+    for (int i = t; i < span; i += 256) {                               // (the whole span, so that every frame of the tile reads defined values)
+        const int g = base + i;
+        rate_xs[i] = g >= 0 && g < n ? xr[g] : 0.0f;
+    }
+    __syncthreads();
+    // wave w takes frames w, w + 4, w + 8 and w + 12 of the tile TOGETHER: four independent chains per lane share every load of the window
+    const float* s = rate_xs + w * H;
+    double a[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0}, m[4];
+    for (int j = lane; j < W; j += 64) {
+        const double wj = p.win[j];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) a[r] = a[r] + wj * (double)s[4 * r * H + j];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) m[r] = formant_wave_sum(a[r]) / p.sw;
+    for (int j = lane; j < W; j += 64) {
+        const double wj = p.win[j];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double d = (double)s[4 * r * H + j] - m[r];
+            q[r] = q[r] + wj * (d * d);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const double P = formant_wave_sum(q[r]) / p.sw;
+        const int fi = w + 4 * r;
+        if (lane == 0 && f0 + fi < p.NF) out[f0 + fi] = fi < nt ? P : 0.0;
+    }
+}
+
+struct RateRowsParams {
+    const double* power; const int32_t* len; const uint8_t* voiced; uint8_t* mark; double* stat; int32_t* count;
+    int L, NF, H, min_pause, min_sound;
+    double floor, rank, silence, dip;
+};
+
+// One tile of an inclusive max-scan over the workgroup's 1024 threads in ascending (FWD) or descending thread order, `car` the running maximum of
+// the tiles before; wm: 16 words, another set than the tile before used (one barrier per tile).  Every thread of the workgroup calls it.
+template <bool FWD>
+__device__ __forceinline__ int rate_scan_max(int v, int& car, int* wm, int lane, int w) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int a = FWD ? __shfl_up(v, o, 64) : __shfl_down(v, o, 64);
+        if (FWD ? lane >= o : lane + o < 64) v = max(v, a);
+    }
+    if (lane == (FWD ? 63 : 0)) wm[w] = v;
+    __syncthreads();
+    v = max(v, car);
+#pragma unroll
+    for (int x = 0; x < 16; ++x) {
+        const int a = wm[x];
+        if (FWD ? x < w : x > w) v = max(v, a);
+        car = max(car, a);
+    }
+    return v;
+}
+
+__device__ __forceinline__ int rate_bit(const uint8_t* mk, int f, int bit) { return mk[f] >> bit & 1; }
+
+// Forward: whether frame f is the last of its run of equal `bit`; *start: the run's first frame (valid there)
+__device__ __forceinline__ bool rate_run_fwd(const uint8_t* mk, int f, int nf, int bit, int& car, int* wm, int lane, int w, int* fl, int* start) {
+    const bool in = f < nf;
+    *fl = in ? rate_bit(mk, f, bit) : 0;
+    const bool first = in && (f == 0 || rate_bit(mk, f - 1, bit) != *fl), last = in && (f + 1 == nf || rate_bit(mk, f + 1, bit) != *fl);
+    *start = rate_scan_max<true>(first ? f : -1, car, wm, lane, w);
+    return last;
+}
+
+// Backward: the last frame of the run of equal `bit` that holds frame f (for f < nf)
+__device__ __forceinline__ int rate_run_bwd(const uint8_t* mk, int f, int nf, int bit, int& car, int* wm, int lane, int w) {
+    const bool last = f < nf && (f + 1 == nf || rate_bit(mk, f + 1, bit) != rate_bit(mk, f, bit));
+    return nf - 1 - rate_scan_max<false>(last ? nf - 1 - f : -1, car, wm, lane, w);
+}
+
+// The bit pattern of the (k + 1)-th largest of Pl[0 .. nf), nf <= 1024 NT: 64 passes, most significant bit first, over the thread's NT frames held
+// in registers (0 past nf: it never carries a bit); per pass a ballot per wave and tile counts the frames that agree with the prefix found so far
+// and carry the bit, and the 16 waves' counts go through wc (two alternating sets of 16 words: one barrier a pass).  Every thread calls it.
+template <int NT>
+__device__ __forceinline__ unsigned long long rate_select(const double* Pl, int nf, int k, int* wc, int t) {
+    const int lane = t & 63, w = t >> 6;
+    unsigned long long pv[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        const int f = (i << 10) + t;
+        pv[i] = f < nf ? (unsigned long long)__double_as_longlong(Pl[f]) : 0ull;
+    }
+    unsigned long long pre = 0ull;
+    for (int bit = 63; bit >= 0; --bit) {
+        const unsigned long long want = pre >> bit | 1ull;
+        int c = 0;
+#pragma unroll
+        for (int i = 0; i < NT; ++i) c += __popcll(__ballot(pv[i] >> bit == want));
+        int* set = wc + (bit & 1) * 16;
+        if (lane == 0) set[w] = c;
+        __syncthreads();
+        int tot = 0;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) tot += set[x];
+        if (tot > k) pre |= 1ull << bit; else k -= tot;
+    }
+    return pre;
+}
+
+__global__ __launch_bounds__(1024) void speech_rate_rows_kernel(const RateRowsParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double rate_smem[];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, b = blockIdx.x, NF = p.NF;
+    double* Pl = rate_smem;                                             // [NF]
+    double* wv = Pl + NF;                                               // [2][16]: the waves' minima of a tile (segmented scan)
+    int* wm = (int*)(wv + 32);                                          // [2][16]: the waves' last scan values of a tile
+    int* wh = wm + 32;                                                  // [2][16]: the waves' segment flags of a tile
+    int* wc = wh + 32;                                                  // [2][16]: the waves' counts of a selection pass
+    int* red = wc + 32;                                                 // [16][8]
+    uint8_t* mk = (uint8_t*)(red + 128);                                // [NF]
+    uint8_t* o_mk = p.mark ? p.mark + (size_t)b * NF : nullptr;
+    double* o_st = p.stat + (size_t)b * 4;
+    int32_t* o_ct = p.count + (size_t)b * 8;
+    int n;
+    const int nf = rate_frames(p.len, b, p.L, p.H, &n);
+    if (nf == 0) {                                                      // a bad row is a row of zeros (uniform; before any barrier)
+        if (o_mk) for (int f = t; f < NF; f += 1024) o_mk[f] = 0;
+        if (t < 4) o_st[t] = 0.0;
+        if (t < 8) o_ct[t] = 0;
+        return;
+    }
+    const double* pw = p.power + (size_t)b * NF;
+    for (int f = t; f < nf; f += 1024) Pl[f] = pw[f];
+    __syncthreads();
+    const int ntile = (nf + 1023) >> 10;
+    // ---- (1) the (k + 1)-th largest of the bit patterns
+    const int k = (int)floor(p.rank * (double)(nf - 1));
+    const unsigned long long pre = ntile <= 1 ? rate_select<1>(Pl, nf, k, wc, t) : ntile <= 4 ? rate_select<4>(Pl, nf, k, wc, t) : rate_select<RATE_MAXF / 1024>(Pl, nf, k, wc, t);
+    const double ref = __longlong_as_double((long long)pre), thr = ref * p.silence;
+    for (int f = t; f < nf; f += 1024) { const double v = Pl[f]; mk[f] = v > thr && v > p.floor ? 2 : 0; }
+    __syncthreads();
+    int it = 0, car;
+    // ---- (2a) silent runs under min_pause between raw frames become sounding: bit 1 -> bit 2
+    car = -1;
+    for (int i = 0; i < ntile; ++i, ++it) {
+        const int f = (i << 10) + t;
+        int fl, s;
+        if (rate_run_fwd(mk, f, nf, 1, car, wm + (it & 1) * 16, lane, w, &fl, &s))
+            mk[f] = (uint8_t)(fl << 1 | (!fl && s > 0 && f + 1 < nf && f - s + 1 < p.min_pause ? 0x80 : 0));
+    }
+    __syncthreads();
+    car = -1;
+    for (int i = ntile - 1; i >= 0; --i, ++it) {
+        const int f = (i << 10) + t;
+        const int e = rate_run_bwd(mk, f, nf, 1, car, wm + (it & 1) * 16, lane, w);
+        if (f < nf) { const int m = mk[f]; mk[f] = (uint8_t)(m | ((m & 2) || (mk[e] & 0x80) ? 4 : 0)); }
+    }
+    __syncthreads();
+    // ---- (2b) sounding runs under min_sound become silent: bit 2 -> bit 0
+    car = -1;
+    for (int i = 0; i < ntile; ++i, ++it) {
+        const int f = (i << 10) + t;
+        int fl, s;
+        if (rate_run_fwd(mk, f, nf, 2, car, wm + (it & 1) * 16, lane, w, &fl, &s))
+            mk[f] = (uint8_t)((mk[f] & 0x7f) | (fl && f - s + 1 < p.min_sound ? 0x80 : 0));
+    }
+    __syncthreads();
+    car = -1;
+    for (int i = ntile - 1; i >= 0; --i, ++it) {
+        const int f = (i << 10) + t;
+        const int e = rate_run_bwd(mk, f, nf, 2, car, wm + (it & 1) * 16, lane, w);
+        if (f < nf) { const int m = mk[f]; mk[f] = (uint8_t)(m | ((m & 4) && !(mk[e] & 0x80) ? 1 : 0)); }
+    }
+    __syncthreads();
+    // ---- (3) the runs of snd: pauses, the leading and the trailing silence; the candidates (bit 2 from here on)
+    int nsnd = 0, npause = 0, s1 = 0, s2 = 0, ncand = 0, nnuc = 0, lead = 0, trail = 0;
+    car = -1;
+    for (int i = 0; i < ntile; ++i, ++it) {
+        const int f = (i << 10) + t;
+        int fl, s;
+        const bool last = rate_run_fwd(mk, f, nf, 0, car, wm + (it & 1) * 16, lane, w, &fl, &s);
+        if (f < nf) {
+            nsnd += fl;
+            if (last && !fl) {
+                const int l = f - s + 1;
+                if (s == 0) lead = l;                                   // (a row without a sounding frame is all leading silence)
+                else if (f + 1 == nf) trail = l;
+                else { ++npause; s1 += l; s2 += l * l; }
+            }
+            bool cand = false;
+            if (fl && f >= 1 && f + 2 <= nf) { const double v = Pl[f]; cand = v > Pl[f - 1] && v >= Pl[f + 1] && v > thr; }
+            ncand += cand;
+            mk[f] = (uint8_t)((mk[f] & 3) | (cand ? 4 : 0));
+        }
+    }
+    __syncthreads();
+    // ---- (4) element f stands for frame f + 1; a segment ends (h) at the row's last frame and in front of a candidate
+    double carv = INFINITY;
+    for (int i = ntile - 1; i >= 0; --i, ++it) {
+        const int f = (i << 10) + t, g = f + 1;
+        double v = g < nf ? Pl[g] : INFINITY;
+        int h = g + 1 >= nf || (mk[g + 1] & 4) ? 1 : 0;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const double a = __shfl_down(v, o, 64);
+            const int c = __shfl_down(h, o, 64);
+            if (lane + o < 64) { if (!h && a < v) v = a; h |= c; }
+        }
+        double* sv = wv + (it & 1) * 16;
+        int* sh = wh + (it & 1) * 16;
+        if (lane == 0) { sv[w] = v; sh[w] = h; }
+        __syncthreads();
+        double av = carv, rv = v;
+#pragma unroll
+        for (int x = 15; x >= 0; --x) {                                 // the tiles behind, then the waves behind, nearest last
+            if (x == w && !h && av < v) rv = av;
+            const double xv = sv[x];
+            const int xh = sh[x];
+            if (xh) av = xv; else if (xv < av) av = xv;
+        }
+        carv = av;
+        if (f < nf) {
+            int m = mk[f];
+            if (m & 4) {
+                const bool dip = rv * p.dip <= Pl[f];
+                if (dip && (!p.voiced || p.voiced[(size_t)b * NF + f] != 0)) { m |= 8; ++nnuc; }
+            }
+            if (o_mk) o_mk[f] = (uint8_t)(m & 15);
+        }
+    }
+    if (o_mk) for (int f = nf + t; f < NF; f += 1024) o_mk[f] = 0;
+    // ---- (5)
+    nsnd = func_wave_isum(nsnd); npause = func_wave_isum(npause); s1 = func_wave_isum(s1); s2 = func_wave_isum(s2);
+    ncand = func_wave_isum(ncand); nnuc = func_wave_isum(nnuc); lead = func_wave_isum(lead); trail = func_wave_isum(trail);
+    if (lane == 0) {
+        int* r = red + 8 * w;
+        r[0] = nsnd; r[1] = npause; r[2] = s1; r[3] = s2; r[4] = ncand; r[5] = nnuc; r[6] = lead; r[7] = trail;
+    }
+    __syncthreads();
+    if (t < 8) {
+        int v = 0;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) v += red[8 * x + t];
+        if (t != 3) o_ct[t == 0 ? 1 : t < 3 ? t + 1 : t] = v;          // {sounding, pauses, pause frames, -, candidates, nuclei, leading, trailing}
+        const long long np = __shfl(v, 1, 64), S1 = __shfl(v, 2, 64), S2 = __shfl(v, 3, 64);
+        if (t == 0) {
+            o_ct[0] = nf;
+            o_st[0] = ref; o_st[1] = thr;
+            o_st[2] = np ? (double)S1 / (double)np : 0.0;
+            o_st[3] = np ? sqrt((double)(np * S2 - S1 * S1)) / (double)np : 0.0;
+        }
+    }
+}

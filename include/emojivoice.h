@@ -39,6 +39,8 @@
  *   ev_loudness        <- no counterpart; ITU-R BS.1770-4 is the model
  *   ev_load_srmr       <- no counterpart; Falk, Zheng and Chan 2010 (SRMR) and Hohmann 2002 (complex gammatone) are the model
  *   ev_srmr            <- no counterpart; Falk, Zheng and Chan 2010 (SRMR) and Hohmann 2002 (complex gammatone) are the model
+ *   ev_load_speech_rate <- no counterpart; De Jong and Wempe 2009 (syllable nuclei) is the model
+ *   ev_speech_rate     <- no counterpart; De Jong and Wempe 2009 (syllable nuclei) is the model
  *   ev_load_stoi       <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_stoi            <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_load_stft_dist  <- no counterpart; Yamamoto et al. 2020 (multi-resolution STFT loss) is the model
@@ -94,7 +96,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation, ev_load_srmr, ev_srmr (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation, ev_load_srmr, ev_srmr, ev_load_speech_rate, ev_speech_rate (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -575,6 +577,62 @@ int ev_load_srmr(ev_handle *h, const double *chan /* HOST (N, 3) */, const doubl
 int ev_srmr(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L,
             double *d_frame /* (B, NF, N, K) or NULL */, double *d_mean /* (B, N, K) */, double *d_srmr /* (B, 2) */,
             int32_t *d_counts /* (B, 3) */, void *stream);
+
+/* Speech rate and pauses on the device: the syllable nuclei of mono rows after De Jong and Wempe (Behavior Research Methods 41, 2009): a power
+ * contour, a sounding / silent segmentation with minimum durations, and the local peaks of the power that are followed by a dip and are voiced.
+ * No transcript and no alignment.  ev_load_speech_rate stores the window; ev_speech_rate measures on the grid of ev_pitch_yin and ev_formants, so
+ * frame f of every contour is the same frame.  Everything is float64, the fp32 samples are widened, floating-point contraction is off;
+ * ev_set_arithmetic does not reach it.
+ *
+ * ev_load_speech_rate: HOST window of W doubles, copied to the device; hop H.  Limits, each violation failing with a message that names it: window
+ * non-NULL and finite with sw > 0; 8 <= W <= 4096, W even; H a multiple of 64 with 64 <= H <= 1024 (W need not be a multiple of H).  The load owns
+ * one device block and counts once in ev_alloc_count; loading again waits for the device and drops the old block; a failed load leaves the previous
+ * tables in use.
+ *
+ * DEFINITION.  NF = ceil(L / H); a row of len samples has nf = ceil(len / H) frames.  d_len == NULL: every row is L long.
+ *   power     s_f[j] = x[f H + H/2 - W/2 + j] for j = 0 .. W-1, zero outside [0, len).  sw = sum of w[j], formed once on the host in ascending j.
+ *             m = (sum w[j] s_f[j]) / sw (Praat's "subtract mean");  P[f] = (sum w[j] (s_f[j] - m)^2) / sw.  The terms are the rounded products
+ *             w[j] s and w[j] ((s - m)(s - m)).  Both sums use the 64-slot rule of ev_modulation: term j belongs to slot j mod 64, a slot starts at
+ *             +0.0 and adds its terms in ascending j, and the 64 slots are reduced by the xor tree with offsets 32, 16, 8, 4, 2, 1.  The order
+ *             depends on the frame's own samples and the loaded window only.
+ *   decisions are made on P, in the power domain: the thresholds arrive as ratios (the host forms silence_ratio = 10^(-silence_db / 10) and
+ *             dip_ratio = 10^(dip_db / 10)) and no decision passes through a logarithm, so a restatement that adds in the same order takes the
+ *             same decisions.
+ *   level     k = floor(rank_fraction * (double)(nf - 1)), one rounded product; ref is the (k + 1)-th largest of P[0 .. nf): rank_fraction = 0 is
+ *             the maximum, 0.01 the script's 99 % quantile without interpolation.  P >= 0 (for a window without negative entries), so its bit
+ *             pattern orders as an unsigned 64-bit integer, and the selection counts bits: no float arithmetic.  thr = ref * silence_ratio.
+ *   sounding  raw[f] = P[f] > thr and P[f] > power_floor.  (a) every maximal run of non-raw frames of length < min_pause becomes sounding, if raw
+ *             frames lie on both of its sides; (b) then every maximal sounding run of length < min_sound becomes silent: snd[f].  A PAUSE is a
+ *             maximal silent run with sounding frames on both sides; the leading and the trailing silent run are counted on their own, and a row
+ *             without a sounding frame is all leading silence, so sounding + pause + leading + trailing frames = nf.
+ *   candidate 1 <= f <= nf - 2, P[f] > P[f-1] and P[f] >= P[f+1] (ev_perturbation's local-peak rule), P[f] > thr, snd[f]:  c_0 < c_1 < ...
+ *   nucleus   for candidate c_i let e = c_{i+1}, and e = nf for the last one (the published script never counts its last peak: a stated
+ *             difference).  d = min P over (c_i, e); the candidate has its DIP when d * dip_ratio <= P[c_i], one product.  An empty interval has
+ *             no dip (under the peak rule frame c_i + 1 is never a candidate, so the interval holds at least that frame).  A candidate with its
+ *             dip is a NUCLEUS when d_voiced is NULL or d_voiced[b, c_i] != 0.
+ * Outputs:
+ *   d_power   (B, NF) float64 or NULL: P, zeros at and past nf
+ *   d_mark    (B, NF) uint8 or NULL: bit 0 snd, bit 1 raw, bit 2 candidate, bit 3 nucleus; zeros past nf
+ *   d_count   (B, 8) int32: {nf, sounding frames, pauses, pause frames, candidates, nuclei, leading silent frames, trailing silent frames}
+ *   d_stat    (B, 4) float64: {ref, thr, mean, sd of the pause lengths in frames}; mean and sd by ev_functionals' integer formula (S1, S2 in
+ *             64-bit integers, then one conversion: S1 / n, sqrt(n S2 - S1 S1) / n); both 0 without a pause
+ * A row with len < 1 or len > L is no error and no out-of-bounds access: zeros in every output.  Nothing at or behind len is read; d_voiced is
+ * read only at candidates with their dip, inside nf.  Nothing depends on B, L, NF or the place in the grid: the same inputs give the same bits in
+ * every output for a row alone, inside a batch, as the d_len prefix of a longer row with anything (NaN included) behind it, in a second call,
+ * under every ev_set_arithmetic setting, and from a captured graph.
+ * Limits of ev_speech_rate, each violation failing with a message that names it, the call writing nothing: tables loaded; 1 <= B <= 65535; L >= 1
+ * and NF <= 16384 (the row's power stays in LDS); power_floor finite and > 0; 0 <= rank_fraction < 1; 0 < silence_ratio < 1; dip_ratio finite and
+ * >= 1; 1 <= min_pause, min_sound <= 4096; d_x, d_stat and d_count non-NULL.
+ * Scratch: without d_power the power contour (B x NF doubles) lives in an arena of the handle that grows on demand and counts in ev_alloc_count: a
+ *   second call at the same shape allocates nothing; ev_reserve does not cover it.  Two kernel launches on `stream`, no atomics, no host wait, no
+ *   copy: the call is capturable once the arena has its size. */
+int ev_load_speech_rate(ev_handle *h, const double *window /* HOST (W) */, int W, int H);
+int ev_speech_rate(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */,
+                   const uint8_t *d_voiced /* (B, NF) or NULL */, int B, int L,
+                   double power_floor, double rank_fraction, double silence_ratio, double dip_ratio,
+                   int min_pause, int min_sound,
+                   double *d_power /* (B, NF) or NULL */, uint8_t *d_mark /* (B, NF) or NULL */,
+                   double *d_stat /* (B, 4) */, int32_t *d_count /* (B, 8) */, void *stream);
 
 /* STOI and ESTOI on the device: short-time objective intelligibility of a processed row y against the clean, sample-aligned row x (Taal,
  * Hendriks, Heusdens and Jensen, IEEE TASL 19(7), 2011) and its extended form (Jensen and Taal, IEEE/ACM TASLP 24(11), 2016), for rows already

@@ -47,6 +47,7 @@ EXPORTS = [
     "ev_load_auditory", "ev_auditory",
     "ev_load_srmr", "ev_srmr",
     "ev_load_speech_rate", "ev_speech_rate",
+    "ev_load_envelope", "ev_envelope",
 ]
 
 
@@ -188,6 +189,8 @@ def load_library() -> C.CDLL:
     lib.ev_srmr.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.ev_load_speech_rate.argtypes = [vp, vp, i32, i32]
     lib.ev_speech_rate.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp, vp, vp]
+    lib.ev_load_envelope.argtypes = [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, i32]
+    lib.ev_envelope.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -540,6 +543,39 @@ class Engine:
                                             float(silence_ratio), float(dip_ratio), int(min_pause), int(min_sound), _ptr(power), _ptr(mark),
                                             stat.data_ptr(), count.data_ptr(), _stream_ptr()), "ev_speech_rate")
         return power, mark, stat, count
+
+    def load_envelope(self, twiddle, H: int, nfft: int, sr: float, warp, default_period: float = 0.0, q1: float = -0.15) -> None:
+        """One geometry of ``envelope`` (ev_load_envelope), the tables on the host: ``twiddle`` (nfft, 2) float64 {cos, sin}(2 pi n / nfft),
+        ``H`` the hop, the rate ``sr`` in Hz, ``warp`` (n_mcep, nfft / 2 + 1) float64 (``audio.freq_warp_matrix``), ``default_period`` in samples
+        for the frames without a usable period (0: sr / 500) and the lifter's ``q1``."""
+        tw = np.ascontiguousarray(np.asarray(twiddle, dtype=np.float64).reshape(-1, 2))
+        wp = np.ascontiguousarray(np.asarray(warp, dtype=np.float64))
+        NB = int(nfft) // 2 + 1
+        if tw.shape[0] != int(nfft) or wp.ndim != 2 or wp.shape[1] != NB:
+            raise ValueError(f"load_envelope: {nfft} twiddles and warp (n_mcep, {NB}) expected, got {tw.shape[0]} and {tuple(wp.shape)}")
+        self._check(self.lib.ev_load_envelope(self.h, tw.ctypes.data, int(H), int(nfft), float(sr), float(default_period), float(q1), wp.ctypes.data,
+                                              int(wp.shape[0])), "ev_load_envelope")
+        self.envelope_geometry = (int(H), int(nfft), int(wp.shape[0]))
+
+    def envelope(self, x, lengths, period, power_floor: float, want_envelope: bool = False):
+        """CheapTrick's envelope and its mel-cepstrum for every frame of every row of ``x`` (B, L) (ev_envelope, after load_envelope):
+        (env (B, NF, NB) float64: the log power envelope in nepers, or None; mcep (B, NF, n_mcep) float64; cls (B, NF, 3) int32: {class, half,
+        kd}) on the device, NF = ceil(L / H).  ``period`` (B, NF) float32: ev_pitch_yin's periods in samples, 0 where unvoiced; ``lengths``
+        (B,): samples per row (None: L)."""
+        if not hasattr(self, "envelope_geometry"):
+            raise EvLibraryError("envelope: tables not loaded (load_envelope)")
+        x, B, L, ln = self._rows(x, lengths, "envelope")
+        H, nfft, NM = self.envelope_geometry
+        NF = -(-L // H)
+        pd = torch.as_tensor(period, device=x.device).to(torch.float32).contiguous()
+        if tuple(pd.shape) != (B, NF):
+            raise ValueError(f"envelope: period must be ({B}, {NF}), got {tuple(pd.shape)}")
+        env = torch.empty((B, NF, nfft // 2 + 1), dtype=torch.float64, device=x.device) if want_envelope else None
+        mcep = torch.empty((B, NF, NM), dtype=torch.float64, device=x.device)
+        cls = torch.empty((B, NF, 3), dtype=torch.int32, device=x.device)
+        self._check(self.lib.ev_envelope(self.h, x.data_ptr(), _ptr(ln), pd.data_ptr(), B, L, float(power_floor), _ptr(env), mcep.data_ptr(),
+                                         cls.data_ptr(), _stream_ptr()), "ev_envelope")
+        return env, mcep, cls
 
     def load_stoi(self, window, twiddle, bands, hop: int, n_fft: int, seg_frames: int) -> None:
         """The tables of ``stoi`` (ev_load_stoi), all on the host: ``window`` (W,) float64 with W = 2 hop, ``twiddle`` (n_fft, 2) float64

@@ -591,6 +591,128 @@ def mel_cepstral_distortion(mel_a, mel_b, len_a=None, len_b=None, n_coeffs: int 
     return mcd_from_cost(out["cost"], out["steps"])
 
 
+ENVELOPE_POWER_FLOOR = 1e-7                        # a frame with no bin of |X|^2 above it is silent; the clamp before the logarithm, ``voice_quality``'s
+ENVELOPE_Q1 = -0.15                                # CheapTrick's compensation coefficient
+ENVELOPE_CLASSES = ("voiced", "default_period", "silent", "beyond")
+
+
+def freq_warp_matrix(n_in: int, order: int, alpha: float) -> np.ndarray:
+    """The frequency warping of a one-sided cepstrum as a matrix, float64 (order + 1, n_in): column n is what SPTK's ``freqt`` recursion makes
+    of the unit vector e_n (for i = n_in - 1 down to 0, with d the g of the previous pass: g[0] = c[i] + alpha d[0]; g[1] = (1 - alpha^2) d[0]
+    + alpha d[1]; g[m] = d[m-1] + alpha (d[m] - g[m-1])), so A @ c is freqt of c at ``alpha`` (0.455 suits 22.05 kHz; 0 is the identity)."""
+    n_in, order, alpha = int(n_in), int(order), float(alpha)
+    if n_in < 1 or order < 0 or not abs(alpha) < 1.0:
+        raise ValueError(f"freq_warp_matrix: n_in >= 1, order >= 0 and |alpha| < 1 expected (got n_in={n_in} order={order} alpha={alpha})")
+    g = np.zeros((order + 1, n_in), dtype=np.float64)
+    for i in range(n_in - 1, -1, -1):
+        d = g.copy()
+        g[0] = alpha * d[0]
+        g[0, i] += 1.0                                                   # (c[i] of the unit vector e_n is 1 at n = i)
+        if order >= 1:
+            g[1] = (1.0 - alpha * alpha) * d[0] + alpha * d[1]
+        for m in range(2, order + 1):
+            g[m] = d[m - 1] + alpha * (d[m] - g[m - 1])
+    return g
+
+
+def _envelope_engine(device: torch.device, sr, n_fft: int, hop: int, order: int, alpha: float) -> Engine:
+    return _cached_engine(device, ("envelope", float(sr), int(n_fft), int(hop), int(order), float(alpha)),
+                          lambda eng: eng.load_envelope(stoi_twiddle(n_fft), hop, n_fft, float(sr),
+                                                        freq_warp_matrix(n_fft // 2 + 1, order, alpha), 0.0, ENVELOPE_Q1))
+
+
+def _device_envelope_rows(x, lengths, period, sr, n_fft, hop, order, alpha, want_envelope):
+    return _envelope_engine(x.device, sr, n_fft, hop, order, alpha).envelope(x, lengths, period, ENVELOPE_POWER_FLOOR, want_envelope)
+
+
+@torch.inference_mode()
+def spectral_envelope(y, period, sr: int = 22050, n_fft: int = 1024, hop_length: int = 256, order: int = 24, alpha: float = 0.455, lengths=None,
+                      envelope: bool = False, rows: Optional[Callable] = None):
+    """The f0-adaptive spectral envelope and its mel-cepstrum per frame on the device (``ev_envelope``; no torch fallback): CheapTrick (Morise
+    2015: a pitch-synchronous window of three periods, the DC correction, the smoothing over 2 f0 / 3 and the cepstral lifter that removes the
+    harmonic structure) and SPTK's ``freqt`` at ``alpha``, both as defined in DESIGN section 3.29 and include/emojivoice.h (zero padding at the
+    edges, no safeguard noise: deterministic; held to a numpy restatement, not to pyworld).  ``y`` 1-D, or (B, L) with ``lengths`` (B,) samples
+    or None, on the GPU; ``period`` (F,) or (B, F): the period of every frame in samples, 0 where unvoiced (``sr / f0`` of ``pitch_yin`` at the
+    same hop: frame f is its frame f); a frame without a period inside [2, (n_fft - 3) / 3] is analysed at sr / 500.  -> {"mcep" (B, F, order +
+    1) float64: the mel-cepstrum of the log amplitude, coefficient 0 the level; "class" (B, F) int32: an index into ENVELOPE_CLASSES;
+    "log_envelope" (B, F, n_fft / 2 + 1) float64 with ``envelope``: the log power envelope in nepers, else None}, F = ceil(L / hop_length).
+    Silent frames and frames past a row are zeros."""
+    if not torch.is_tensor(y) or y.dim() not in (1, 2) or y.numel() == 0:
+        raise ValueError("spectral_envelope: y must be a non-empty tensor, 1-D or (B, L)")
+    if not 0 <= int(order) <= 63 or not abs(float(alpha)) < 1.0 or int(order) > int(n_fft) // 2:
+        raise ValueError(f"spectral_envelope: 0 <= order <= min(63, n_fft / 2) and |alpha| < 1 expected (got order={order} alpha={alpha})")
+    if int(n_fft) % 2 or not 16 <= int(n_fft) <= 1024 or not 1 <= int(hop_length) <= 512:
+        raise ValueError(f"spectral_envelope: n_fft even with 16 <= n_fft <= 1024 and 1 <= hop_length <= 512 expected (got {n_fft}, {hop_length})")
+    if not 2.0 <= float(sr) / 500.0 <= (int(n_fft) - 3) / 3.0:
+        raise ValueError(f"spectral_envelope: the default period sr / 500 = {float(sr) / 500.0:g} lies outside [2, (n_fft - 3) / 3] at sr={sr} n_fft={n_fft}")
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    F = -(-x.shape[1] // int(hop_length))
+    pd = torch.as_tensor(period)
+    pd = pd.unsqueeze(0) if pd.dim() == 1 else pd
+    if tuple(pd.shape) != (x.shape[0], F):
+        raise ValueError(f"spectral_envelope: period must be ({x.shape[0]}, {F}), got {tuple(pd.shape)}")
+    if rows is None and not y.is_cuda:
+        raise EvLibraryError("spectral_envelope runs on a ROCm GPU only (no CPU fallback): move y to the GPU")
+    env, mcep, cls = (rows or _device_envelope_rows)(x, lengths if y.dim() == 2 else None, pd, sr, int(n_fft), int(hop_length), int(order),
+                                                     float(alpha), bool(envelope))
+    return {"mcep": mcep, "class": cls[:, :, 0], "log_envelope": env}
+
+
+def period_from_pitch(pitch, sr) -> torch.Tensor:
+    """(B, F) float32 periods in samples from a pitch tracker's dict ({"f0", "voiced"}): sr / f0 where voiced, else 0."""
+    f0 = torch.as_tensor(pitch["f0"], dtype=torch.float32)
+    v = torch.as_tensor(pitch["voiced"]).to(f0.device, torch.bool) & (f0 > 0)
+    return torch.where(v, float(sr) / torch.where(v, f0, torch.ones_like(f0)), torch.zeros_like(f0))
+
+
+@torch.inference_mode()
+def envelope_cepstra(y, period, sr: int = 22050, n_fft: int = 1024, hop_length: int = 256, order: int = 24, alpha: float = 0.455, lengths=None,
+                     rows: Optional[Callable] = None):
+    """What ``envelope_mcd`` aligns, of one side: (coefficients 1 .. ``order`` of ``spectral_envelope``'s mel-cepstrum as (B, order, F) float32
+    with the frames that are neither silent nor past the row moved to the front in their order, their count per row (B,) int32)."""
+    if order < 1:
+        raise ValueError(f"envelope_cepstra: order={order} must be at least 1 (coefficient 0, the level, is left out)")
+    if not torch.is_tensor(y) or y.dim() != 2:
+        raise ValueError("envelope_cepstra: y must be a (B, L) tensor")
+    out = spectral_envelope(y, period, sr, n_fft, hop_length, order, alpha, lengths, rows=rows)
+    keep = out["class"] < 2                                              # voiced or default period
+    first = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)   # the kept frames first, in their order
+    mc = torch.gather(out["mcep"], 1, first[:, :, None].expand(-1, -1, out["mcep"].shape[2]))[:, :, 1:]
+    return mc.transpose(1, 2).to(torch.float32).contiguous(), keep.sum(dim=1).to(torch.int32)
+
+
+@torch.inference_mode()
+def cepstra_mcd(cep_a, n_a, cep_b, n_b):
+    """MCD in dB, (B,) float64, between two sides of ``envelope_cepstra``: ``dtw`` over the Euclidean distance of the first n_a / n_b frames and
+    ``mcd_from_cost``; NaN for a pair with no frame on a side."""
+    if cep_a.shape[0] != cep_b.shape[0]:
+        raise ValueError(f"cepstra_mcd: {cep_a.shape[0]} rows against {cep_b.shape[0]}")
+    got = dtw(cep_a, cep_b, n_a.clamp_min(1), n_b.clamp_min(1), "euclidean")
+    mcd = mcd_from_cost(got["cost"], got["steps"])
+    both = ((n_a > 0) & (n_b > 0)).to(mcd.device)
+    return torch.where(both, mcd, torch.full_like(mcd, float("nan")))
+
+
+@torch.inference_mode()
+def envelope_mcd(y_a, y_b, sr: int = 22050, len_a=None, len_b=None, pitch: Optional[Callable] = None, n_fft: int = 1024, hop_length: int = 256,
+                 order: int = 24, alpha: float = 0.455, rows: Optional[Callable] = None):
+    """Mel-cepstral distortion in dB between two batches of recordings (B, La) and (B, Lb) the way the TTS literature takes it, (B,) float64:
+    ``pitch`` (a tracker such as ``pitch_yin`` or ``pitch_pyin``: ``pitch(y, sr, hop_length=..., lengths=...)`` -> {"f0", "voiced"}; None:
+    ``pitch_yin``) gives the periods, ``spectral_envelope`` the mel-cepstra of CheapTrick's envelope, ``dtw`` aligns coefficients 1 .. ``order``
+    (the level, coefficient 0, is left out) by their Euclidean distance and ``mcd_from_cost`` scales the mean over the path.  Silent frames
+    and frames past a row are left out on both sides before the alignment: the frames kept move to the front and their count is the row's
+    length, the way ``mel_cepstral_distortion`` takes ``len_a`` / ``len_b``.  NaN for a pair with no frame kept on a side.  The envelope is
+    CheapTrick as DESIGN section 3.29 defines it (no pyworld): of the kind of the WORLD-based figures, not equal to them to the digit."""
+    track = pitch_yin if pitch is None else pitch
+    sides = []
+    for y, ln in ((y_a, len_a), (y_b, len_b)):
+        if not torch.is_tensor(y) or y.dim() != 2:
+            raise ValueError("envelope_mcd: y_a and y_b must be (B, L) tensors")
+        pd = period_from_pitch(track(y, sr, hop_length=hop_length, lengths=ln), sr)
+        sides.append(envelope_cepstra(y, pd, sr, n_fft, hop_length, order, alpha, ln, rows))
+    return cepstra_mcd(*sides[0], *sides[1])
+
+
 @torch.inference_mode()
 def f0_errors(f0_a, voiced_a, f0_b, voiced_b, path, steps):
     """Pitch agreement over a DTW path, per utterance: ``f0_a`` / ``voiced_a`` (B, Fa), ``f0_b`` / ``voiced_b`` (B, Fb), ``path``

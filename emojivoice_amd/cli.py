@@ -34,6 +34,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --srmr                                      # ... and, per pair, the SRMR of both sides and their difference
     python -m emojivoice_amd.cli --prosody_report clean/filelist.txt --rhythm                           # ... and, per file and per speaker, speech rate, articulation rate, pauses and phonation ratio (syllable nuclei)
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --rhythm                                    # ... and, per pair, rate and pauses of both sides and their differences
+    python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --envelope_mcd                              # ... and, per pair, the MCD of the mel-cepstra of CheapTrick's spectral envelope (the literature's kind of MCD)
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
     python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000          # clean/filelist.txt.vocoder.json: STOI / ESTOI, mel L1 and loudness shift of copy synthesis
     python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000 --spectral_distance   # + multi-resolution STFT distance and log-spectral distance
@@ -96,6 +97,8 @@ def validate_args(args):
     if getattr(args, "rhythm", False):
         assert getattr(args, "prosody_report", None) or getattr(args, "evaluate_pairs", None), \
             "--rhythm is an option of --prosody_report and of --evaluate_pairs"
+    if getattr(args, "envelope_mcd", False):
+        assert getattr(args, "evaluate_pairs", None), "--envelope_mcd is an option of --evaluate_pairs"
     if getattr(args, "track_formants", False):
         assert (getattr(args, "voice_report", None) or getattr(args, "evaluate_pairs", None)) and (getattr(args, "formants", False) or getattr(args, "harmonics", False)), \
             "--track_formants is an option of --formants and of --harmonics under --voice_report and --evaluate_pairs"
@@ -1070,9 +1073,13 @@ def evaluate_pairs(args, device):
     a side without a figure) and synthesised - recorded; per speaker and overall "srmr": the means of the three over the pairs that have them.
     --rhythm adds per pair "rhythm": {"recorded", "synthesised"} (RHYTHM_REPORT_KEYS of audio.speech_rate with "nuclei" and "pause_s", voiced by
     the tracker of this report) and "delta": {"rate_ratio" (0.15: the synthesis speaks 15 % faster), "pauses_delta", "pause_s_delta"}; per
-    speaker and overall "rhythm": the means of the three differences over the pairs that have them."""
+    speaker and overall "rhythm": the means of the three differences over the pairs that have them.
+    --envelope_mcd adds per pair "mcd_env_db": the mel-cepstral distortion of the mel-cepstra (order 24, alpha 0.455, coefficient 0 left out) of
+    CheapTrick's spectral envelope on the tracker's periods (audio.envelope_cepstra, audio.cepstra_mcd: silent frames left out, an alignment of
+    its own), null for a pair with a side without a frame; per speaker and overall "mcd_env_db": the mean over the pairs that have it."""
     from . import audio
 
+    want_env = getattr(args, "envelope_mcd", False)
     want_mod = getattr(args, "modulation", False)
     want_srmr = getattr(args, "srmr", False)
     want_rhythm = getattr(args, "rhythm", False)
@@ -1104,6 +1111,9 @@ def evaluate_pairs(args, device):
             pitch["srmr"] = [srmr_value(v) for v in audio.srmr(sig, sr, lengths=clipped, rows=getattr(args, "srmr_rows", None))["srmr"].cpu()]
         if want_rhythm:
             pitch["rhythm"] = rhythm_rows(audio, args, sig, sr, hop, clipped, pitch["voiced"])
+        if want_env:
+            pitch["envelope"] = audio.envelope_cepstra(sig, audio.period_from_pitch(pitch, sr), sr, hop_length=hop, lengths=clipped,
+                                                       rows=getattr(args, "envelope_rows", None))
         return cep, frames, pitch
 
     for b0 in range(0, len(entries), args.batch_size):
@@ -1128,6 +1138,8 @@ def evaluate_pairs(args, device):
         if want_mod:
             msd = audio.cepstral_modulation_distance(cep_a, cep_b, fr_a, fr_b, sr, hop)
             msd = torch.stack([msd["ms_distortion_db"], msd["ms_shift_db"]]).cpu()
+        if want_env:
+            mcd_env = audio.cepstra_mcd(*pitch_a["envelope"], *pitch_b["envelope"]).cpu()
         for r, (rec, syn, spk, _, _) in enumerate(chunk):
             records.append({"recorded": rec, "synthesised": syn, "speaker": spk, "mcd_db": float(mcd[r]), "f0_rmse_cents": f0["rmse_cents"][r],
                             "voicing_error": float(verr[r]), "voiced_pairs": int(nv[r]), "frames_recorded": fr_a[r], "frames_synthesised": fr_b[r],
@@ -1148,6 +1160,8 @@ def evaluate_pairs(args, device):
             if want_rhythm:
                 va, vb = pitch_a["rhythm"][r], pitch_b["rhythm"][r]
                 records[-1]["rhythm"] = {"recorded": va, "synthesised": vb, "delta": rhythm_difference(va, vb)}
+            if want_env:
+                records[-1]["mcd_env_db"] = None if math.isnan(float(mcd_env[r])) else float(mcd_env[r])
 
     def means(recs):
         out = evaluation_means(recs)
@@ -1172,6 +1186,9 @@ def evaluate_pairs(args, device):
                 out["srmr"][k] = math.fsum(d) / len(d) if d else None
         if want_rhythm:
             out["rhythm"] = rhythm_means([r["rhythm"]["delta"] for r in recs], ("rate_ratio", "pauses_delta", "pause_s_delta"))
+        if want_env:
+            d = [r["mcd_env_db"] for r in recs if r["mcd_env_db"] is not None]
+            out["mcd_env_db"] = math.fsum(d) / len(d) if d else None
         return out
 
     by_spk = {}
@@ -1261,6 +1278,9 @@ def cli(argv=None):
     p.add_argument("--rhythm", action="store_true", help="--prosody_report and --evaluate_pairs: add \"rhythm\" (speech rate and articulation rate in "
                    "syllable nuclei per second, pauses, mean pause and phonation ratio by De Jong and Wempe's method on the device, voiced by the "
                    "report's pitch tracker); per pair both sides and the relative rate difference, the pause-count and the pause-time difference")
+    p.add_argument("--envelope_mcd", action="store_true", help="--evaluate_pairs: add \"mcd_env_db\" per pair, per speaker and overall: the mel-cepstral "
+                   "distortion of the mel-cepstra (order 24, alpha 0.455) of CheapTrick's f0-adaptive spectral envelope on the report's pitch tracker, "
+                   "aligned by DTW on the device: the literature's kind of MCD beside the log-mel one")
     p.add_argument("--target_lufs", type=float, default=None, help="--prepare_dataset: level every recording to this integrated loudness (BS.1770, e.g. -23) "
                    "instead of to --peak; the gain is capped where the peak would pass --peak, and the gain and the cap go into FILELIST.durations.json")
     p.add_argument("--vocoder_report", type=str, default=None, help="vocoder evaluation instead of synthesis: a filelist 'path|spk|text' -> FILELIST.vocoder.json: "

@@ -1,5 +1,5 @@
 // Host entry points of the analysis side: resampling, dataset statistics, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness,
-// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals, auditory descriptors, formant tracks, SRMR and speech rate (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
+// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals, auditory descriptors, formant tracks, SRMR, speech rate and the spectral envelope (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
 // after ev_handle, fail / HIPCHK / enter, dev_upload, drop_owned, scratch_acquire and launch<>.  None of these calls runs on the engine's conv
 // path; ev_load_mel_basis, ev_mel_spectrogram, ev_denoise and ev_stft_magnitude do, and stay in ev_engine.hip.
 #pragma once
@@ -1071,6 +1071,86 @@ int ev_speech_rate(ev_handle* h, const float* d_x, const int32_t* d_len, const u
     RateRowsParams pr{power, d_len, d_voiced, d_mark, d_stat, d_count, L, NF, w.H, min_pause, min_sound, power_floor, rank_fraction, silence_ratio, dip_ratio};
     // the row's power (8 B a frame) and flags (1 B), 32 doubles and 224 words of hand-over: 145.1 KiB at NF = 16384
     launch<speech_rate_rows_kernel>(h->device, dim3((unsigned)B), dim3(1024), (size_t)9 * NF + 1152, h->stream, pr);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Spectral envelope and mel-cepstrum: CheapTrick on ev_pitch_yin's periods and freqt (envelope_power_kernel and envelope_cepstrum_kernel,
+// ev_analysis_kernels.h; the definition: include/emojivoice.h).  H follows the DFT families' rule, 1 <= H <= 512.  A load owns one device block: the
+// plain DFT basis (stft_dist_basis_kernel under a window of ones, W = nfft), the cepstral basis (voiceq_cep_basis_kernel at q_fit = 0, NQ = NB) and
+// the warp table, transposed to (NBp, n_mcep) with zero rows from NB on and row 0 halved (c[0] = c'[0] / 2).  Arena of a call: the power spectra,
+// B x NF x NB doubles.
+int ev_load_envelope(ev_handle* h, const double* twiddle, int H, int nfft, double sr, double default_period, double q1, const double* warp, int n_mcep) {
+    if (enter(h)) return 1;
+    if (!twiddle || !warp) return fail(h, "ev_load_envelope: twiddle and warp must be non-null (HOST)");
+    if (nfft < 16 || nfft > 1024 || nfft % 2) return fail(h, "ev_load_envelope: nfft=%d must be even with 16 <= nfft <= 1024", nfft);
+    if (H < 1 || H > 512) return fail(h, "ev_load_envelope: H=%d outside 1 <= H <= 512", H);
+    if (n_mcep < 1 || n_mcep > 64) return fail(h, "ev_load_envelope: n_mcep=%d outside 1 <= n_mcep <= 64", n_mcep);
+    if (!(sr > 0.0) || !std::isfinite(sr)) return fail(h, "ev_load_envelope: sr=%g must be finite and greater than 0", sr);
+    if (!std::isfinite(q1)) return fail(h, "ev_load_envelope: q1=%g is not finite", q1);
+    const int NB = nfft / 2 + 1, NBp = (NB + 3) / 4 * 4;
+    const double T_max = (double)(nfft - 3) / 3.0;
+    if (!std::isfinite(default_period)) return fail(h, "ev_load_envelope: default_period=%g is not finite", default_period);
+    const double T_def = default_period == 0.0 ? sr / 500.0 : default_period;
+    if (!(T_def >= 2.0 && T_def <= T_max))
+        return fail(h, "ev_load_envelope: default_period=%g (0: sr / 500) outside 2 <= default_period <= (nfft - 3) / 3 = %g", T_def, T_max);
+    if (check_finite(h, __func__, "twiddle", twiddle, 2 * nfft) || check_finite(h, __func__, "warp", warp, n_mcep * NB)) return 1;
+    EnvW w;
+    EnvTables& t = w.t;
+    t.H = H; t.nfft = nfft; t.NB = NB; t.NBp = NBp; t.n_mcep = n_mcep; t.T_max = T_max; t.T_def = T_def; t.q1 = q1;
+    const int rows = (nfft + 3) / 4 * 4;
+    t.S1 = rows + ((2 - rows) % 32 + 32) % 32;                          // the smallest numbers >= the rows of a frame / of a plane that are 2 mod 32
+    t.S = NBp + ((2 - NBp) % 32 + 32) % 32;
+    w.lds1 = (size_t)16 * t.S1 * sizeof(double);
+    w.lds2 = (size_t)2 * 16 * t.S * sizeof(double);
+    if (w.lds1 > 160 * 1024 || w.lds2 > 160 * 1024)
+        return fail(h, "ev_load_envelope: nfft=%d needs %zu and %zu bytes of LDS, over 160 KiB", nfft, w.lds1, w.lds2);
+    std::vector<double> ones((size_t)nfft, 1.0), wt((size_t)NBp * n_mcep, 0.0);
+    for (int m = 0; m < n_mcep; ++m)
+        for (int q = 0; q < NB; ++q) wt[(size_t)q * n_mcep + m] = (q == 0 ? 0.5 : 1.0) * warp[(size_t)m * NB + q];
+    const size_t n_basis = (size_t)nfft * NB, n_cep = (size_t)NBp * NB;
+    const size_t o_cep = 2 * n_basis, o_warp = o_cep + n_cep;          // in doubles from the block's start, behind the basis
+    char* blk = nullptr;                                                // the new block first: a failed load leaves the tables in use as they are
+    auto rest = [&](char* b, const double* d_tw) {
+        double* d = (double*)b;
+        hipError_t e = hipMemcpy(d + o_warp, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice);
+        VoiceQCepParams pc{d_tw, d + o_cep, nfft, NB, NBp, NB, 0};
+        if (e == hipSuccess) launch<voiceq_cep_basis_kernel>(h->device, dim3((unsigned)((n_cep + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pc);
+        return e;
+    };
+    if (build_dft_basis(h, __func__, "tables", ones.data(), twiddle, nfft, nfft, (o_warp + wt.size()) * sizeof(double), &blk, rest)) return 1;
+    const double* d = (const double*)blk;
+    t.basis = (const double2*)blk; t.cep = d + o_cep; t.warp = d + o_warp;
+    EnvW& cur = h->env;
+    if (cur.loaded && drop_owned(h, {(void*)cur.t.basis})) { hipFree(blk); return 1; }
+    h->owned.push_back(blk);
+    ++h->n_allocs;                          // (one block: 8.4 MB of basis, 2.1 MB of cepstral basis and the warp table at nfft = 1024)
+    w.loaded = true;
+    cur = w;
+    return 0;
+}
+
+int ev_envelope(ev_handle* h, const float* d_x, const int32_t* d_len, const float* d_period, int B, int L, double power_floor,
+                double* d_env, double* d_mcep, int32_t* d_class, void* stream) {
+    if (enter(h)) return 1;
+    const EnvW& w = h->env;
+    if (!w.loaded) return fail(h, "ev_envelope: tables not loaded (ev_load_envelope)");
+    if (check_batch(h, __func__, B)) return 1;
+    if (L < 1) return fail(h, "ev_envelope: L=%d must be at least 1", L);
+    if (!d_x) return fail(h, "ev_envelope: d_x must be non-null");
+    if (!d_period) return fail(h, "ev_envelope: d_period must be non-null (ev_pitch_yin's periods; 0 where unvoiced)");
+    if (!(power_floor > 0.0) || !std::isfinite(power_floor)) return fail(h, "ev_envelope: power_floor=%g must be finite and greater than 0", power_floor);
+    if (!d_mcep || !d_class) return fail(h, "ev_envelope: d_mcep and d_class must be non-null");
+    if (L / w.t.H > 0x7fffffef) return fail(h, "ev_envelope: L=%d at H=%d has more frames than an int32 tile index holds", L, w.t.H);
+    h->stream = (hipStream_t)stream;
+    const int NF = frames_of(L, w.t.H);
+    if (scratch_acquire(h, h->env_ws, (size_t)B * NF * w.t.NB * sizeof(double))) return 1;
+    double* P = (double*)h->env_ws.p;
+    const dim3 grid((unsigned)((NF + 15) / 16), (unsigned)B);
+    EnvPowerParams pp{d_x, d_len, d_period, P, w.t, L, NF};
+    launch<envelope_power_kernel>(h->device, grid, dim3(256), w.lds1, h->stream, pp);
+    EnvCepParams pc{d_len, d_period, P, d_env, d_mcep, d_class, w.t, L, NF, power_floor};
+    launch<envelope_cepstrum_kernel>(h->device, grid, dim3(256), w.lds2, h->stream, pc);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

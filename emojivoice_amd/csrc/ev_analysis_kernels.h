@@ -3723,3 +3723,316 @@ __global__ __launch_bounds__(1024) void speech_rate_rows_kernel(const RateRowsPa
         }
     }
 }
+
+// ---------------------------------------------------------------------------
+// Spectral envelope and mel-cepstrum (ev_envelope): CheapTrick's f0-adaptive envelope (Morise 2015) and its frequency-warped cepstrum (SPTK's
+// freqt) on ev_voice_quality's frames, the period of every frame from ev_pitch_yin (the definition, steps 1 to 7: include/emojivoice.h).  All
+// float64, contraction OFF (STOI_EXACT), no atomics, no scratch.  Two launches on the grid (ceil(NF / 16), B), a workgroup of 4 waves per tile of 16
+// frames, four GEMMs on v_mfma_f64_16x16x4_f64 with the fragment layout of the float64 DFT GEMM above:
+//   envelope_power_kernel     GEMM 1  the windowed, mean-removed frames (16 x K, float64 in LDS) times the PLAIN DFT basis {cos, sin}(2 pi m k / nfft)
+//                                     (stft_dist_basis_kernel with a window of ones and W = nfft): sample j of a frame stands at row m = j + nfft / 2
+//                                     (the shift is a sign per bin: |X|^2 does not see it).  The window differs per frame, so it is applied to the
+//                                     A operand, not baked into the basis, and K runs over the tile's LONGEST window only: rows m_lo <= m < m_hi,
+//                                     m_lo = (nfft / 2 - hmax) rounded down and m_hi = nfft / 2 + hmax + 1 rounded up to a multiple of 4, shorter
+//                                     windows padded with zeros.  P = fma(sm, sm, re re) goes to the handle's arena (B, NF, NB).
+//   envelope_cepstrum_kernel  steps 3 and 4 per frame in LDS; GEMM 2: Lg (16 x NBp) times voiceq_cep_basis_kernel's table at q_fit = 0, NQ = NB,
+//                                     the lifter in its epilogue; GEMM 3a: the liftered cepstrum times the SAME table (g[q] cos(2 pi q k / nfft) is
+//                                     nfft cep[q][k]), skipped without d_env; GEMM 3b: the liftered cepstrum times the warp table (NBp, n_mcep).
+// A tile holds frames of ONE row and everything in it hangs on that row's samples below len and its own periods: a row's outputs do not depend on
+// the batch or on L (m_lo and m_hi follow the row's own periods; a product with a padding zero adds +0).
+// ORDERS.  Window sums (sum w^2, sum w, sum x w): wave v owns the frames 4 v .. 4 v + 3; lane l adds its samples i = l, l + 64, ... (i = j + half)
+// in ascending order, then one xor tree over the 64 lanes (offsets 32 .. 1).  live (the count of P[k] > floor): the same, over bins.  The
+// smoothing sum: one lane per (frame, bin), ascending cells.  GEMMs: K ascending in steps of 4 inside the matrix instruction.
+struct EnvTables {
+    const double2* basis; const double* cep; const double* warp;       // (nfft, NB) pairs, (NBp, NB), (NBp, n_mcep) with zero rows from NB on
+    int H, nfft, NB, NBp, S1, S, n_mcep;                                // S1, S: the LDS row strides of the frames and of the planes, both 2 mod 32
+    double T_max, T_def, q1;
+};
+
+// the period of frame idx of the row and its class (0: ev_pitch_yin's, 1: the default period)
+__device__ __forceinline__ double env_period(const float* pr, size_t idx, const EnvTables& t, int* cls) {
+    const double T = (double)pr[idx];
+    const bool ok = T > 0.0 && T >= 2.0 && T <= t.T_max;                // (a NaN is not > 0)
+    *cls = ok ? 0 : 1;
+    return ok ? T : t.T_def;
+}
+__device__ __forceinline__ int env_half(double T) { STOI_EXACT return (int)floor(1.5 * T + 0.5); }
+__device__ __forceinline__ double env_wave_sum(double v) {
+    STOI_EXACT
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Dynamic LDS: the tile's frames, 16 x S1 doubles (S1 the smallest number >= nfft rounded up to 4 that is 2 mod 32: 131 328 bytes at nfft = 1024).
+// The samples come straight from the row (each is read by about (2 half + 1) / H frames: cache hits), zeros outside [0, len).
+// BANKS.  The window passes write and read ws[m] with m consecutive over the 64 lanes (ds_write_b64 / ds_read_b64: consecutive doubles,
+// conflict-free).  The A fragment of GEMM 1 reads frames[(l & 15) S1 + m_lo + 4 s + (l >> 4)] with ds_read_b64: voice_quality_kernel's phase 2
+// pattern with the same stride class (S1 = 2 mod 32, m_lo a constant offset): all 64 banks once per group of 32 lanes, conflict-free.
+struct EnvPowerParams { const float* x; const int32_t* len; const float* period; double* P; EnvTables t; int L, NF; };
+
+__global__ __launch_bounds__(256) void envelope_power_kernel(const EnvPowerParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double env_smem[];
+    const int b = blockIdx.y, f0 = blockIdx.x * 16, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int H = p.t.H, nfft = p.t.nfft, NB = p.t.NB, S1 = p.t.S1, hn = nfft >> 1;
+    int n;
+    const int nf = voiceq_frames(p.len, b, p.L, H, &n);
+    if (f0 >= nf) return;                                               // (uniform) envelope_cepstrum_kernel writes this tile's zeros and reads no P
+    const float* xr = p.x + (size_t)b * p.L;
+    const float* pr = p.period + (size_t)b * p.NF;
+    int hmax = 0;                                                       // the tile's longest window (uniform: every thread walks the 16 periods)
+    for (int fr = 0; fr < 16 && f0 + fr < nf; ++fr) {
+        int c;
+        const int hf = env_half(env_period(pr, (size_t)(f0 + fr), p.t, &c));
+        hmax = hf > hmax ? hf : hmax;
+    }
+    const int m_lo = (hn - hmax) & ~3, m_hi = (hn + hmax + 4) & ~3;     // (hmax <= nfft / 2 - 1: 0 <= m_lo, m_hi <= nfft rounded up to 4 <= S1)
+#pragma unroll 1
+    for (int i = 0; i < 4; ++i) {
+        const int fr = 4 * wv + i;
+        double* ws = env_smem + (size_t)fr * S1;
+        int half = -1;                                                  // (a frame past the row: zeros throughout)
+        if (f0 + fr < nf) {
+            int c;
+            const double T = env_period(pr, (size_t)(f0 + fr), p.t, &c);
+            const double a = 1.5 * T;
+            half = env_half(T);
+            const long long ctr = (long long)(f0 + fr) * H + H / 2;
+            double sw2 = 0.0, sw = 0.0, sxw = 0.0;
+            for (int ii = lane; ii <= 2 * half; ii += 64) {
+                const int j = ii - half;
+                const double w = 0.5 * cospi((double)j / a) + 0.5;
+                const long long s = ctr + j;
+                const double xv = s >= 0 && s < n ? (double)xr[s] : 0.0;
+                const double xw = xv * w;
+                ws[hn + j] = xw;
+                sw2 = sw2 + w * w; sw = sw + w; sxw = sxw + xw;
+            }
+            sw2 = env_wave_sum(sw2); sw = env_wave_sum(sw); sxw = env_wave_sum(sxw);
+            const double nrm = sqrt(sw2), ratio = sxw / sw;             // s[j] = (x w - w (sum x w) / (sum w)) / sqrt(sum w^2)
+            for (int ii = lane; ii <= 2 * half; ii += 64) {             // (each lane returns to the entries it wrote itself)
+                const int j = ii - half;
+                const double w = 0.5 * cospi((double)j / a) + 0.5;
+                ws[hn + j] = (ws[hn + j] - w * ratio) / nrm;
+            }
+        }
+        for (int m = m_lo + lane; m < m_hi; m += 64)
+            if (m < hn - half || m > hn + half) ws[m] = 0.0;
+    }
+    __syncthreads();
+    const int r = lane & 15, q = lane >> 4;
+    const int ntile = (NB + 15) >> 4, nsteps = (m_hi - m_lo) >> 2;      // (nsteps >= 1)
+    const double* La = env_smem + (size_t)r * S1 + m_lo + q;
+    double* Pt = p.P + ((size_t)b * p.NF + f0) * NB;
+    for (int bt = wv; bt < ntile; bt += 4) {
+        const int col = bt * 16 + r;
+        const double2* bp = p.t.basis + (col < NB ? col : NB - 1);
+        stftd_acc xc = {0.0, 0.0, 0.0, 0.0}, xs = xc;
+        // the basis row of step s is m_lo + 4 s + q, clamped to nfft - 1 (nfft no multiple of 4: the frames hold zeros there); the rows of the NEXT
+        // four steps are requested before this round's products, the step clamped at the last one, as in the kernels above
+        double2 cur[4], nxt[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int m = m_lo + 4 * (u < nsteps ? u : nsteps - 1) + q;
+            cur[u] = bp[(size_t)(m < nfft ? m : nfft - 1) * NB];
+        }
+        for (int s0 = 0; s0 < nsteps; s0 += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int m = m_lo + 4 * (s0 + 4 + u < nsteps ? s0 + 4 + u : nsteps - 1) + q;
+                nxt[u] = bp[(size_t)(m < nfft ? m : nfft - 1) * NB];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (s0 + u < nsteps) {                                  // (uniform)
+                    const double ax = La[4 * (s0 + u)];
+                    xc = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].x, xc, 0, 0, 0);
+                    xs = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].y, xs, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+        }
+        if (col < NB) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (f0 + q + 4 * i < nf) Pt[(size_t)(q + 4 * i) * NB + col] = fma(xs[i], xs[i], xc[i] * xc[i]);
+        }
+    }
+}
+
+// One GEMM of envelope_cepstrum_kernel: C (16 frames x ncol) = plane (16 x NBp, LDS, row stride S) times tab (NBp x ncol, row-major, its rows from
+// NB on zeros), wave w owning the column tiles w, w + 4, ...; voice_quality_kernel's phase 2 loop.  La is the plane at the lane's row, (l & 15) S;
+// k >= NB reads the address NB - 1 (the table's row is zero).  epi(col, c) takes the finished tile: register i of c is frame (l >> 4) + 4 i.
+template <typename Epi>
+__device__ __forceinline__ void env_gemm(const double* La, const double* tab, int ncol, int NB, int NBp, int wv, int r, int q, Epi epi) {
+    STOI_EXACT
+    const int nt = (ncol + 15) >> 4, nsteps = NBp >> 2;
+    for (int ct = wv; ct < nt; ct += 4) {
+        const int col = ct * 16 + r;
+        const double* bp = tab + (size_t)q * ncol + (col < ncol ? col : ncol - 1);
+        stftd_acc c = {0.0, 0.0, 0.0, 0.0};
+        double cur[4], nxt[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) cur[u] = bp[(size_t)(u < nsteps ? u : nsteps - 1) * 4 * ncol];
+        for (int t0 = 0; t0 < nsteps; t0 += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) nxt[u] = bp[(size_t)(t0 + 4 + u < nsteps ? t0 + 4 + u : nsteps - 1) * 4 * ncol];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (t0 + u < nsteps) {                                  // (uniform)
+                    const int k = 4 * (t0 + u) + q;
+                    c = __builtin_amdgcn_mfma_f64_16x16x4f64(La[k < NB ? k : NB - 1], cur[u], c, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+        }
+        if (col < ncol) epi(col, c);
+    }
+}
+
+// Dynamic LDS: two planes X and Y of 16 x S doubles (S the smallest number >= NBp that is 2 mod 32: 131 584 bytes at nfft = 1024).  Wave v owns
+// the frames 4 v .. 4 v + 3 in the passes per frame, lane l the bins l, l + 64, ...; a barrier stands between any two passes.
+//   pass 1  X[k] = P[k] from the arena; live = the count of P[k] > floor; the frame's T, class, half and kd; d_class
+//   pass 2  Y[k] = P'[k]: for k <= kd, u = nfft / T - k, i = floor(u), P[k] + (P[i] (1 - (u - i)) + P[min(i + 1, NB - 1)] (u - i)), read from X
+//   pass 3  X[k] = log(max(S[k], floor)), S[k] = (sum over the cells of [k - wd / 2, k + wd / 2) of Y) / wd, wd = (2 nfft) / (3 T): with lo and hi
+//           the ends, ilo = floor(lo + 0.5), ihi = floor(hi + 0.5): ilo == ihi: Y[ilo] (hi - lo); else Y[ilo] ((ilo + 0.5) - lo), then Y[i] for
+//           ilo < i < ihi ascending, then Y[ihi] (hi - (ihi - 0.5)); an index i < 0 reads -i, one > nfft / 2 reads nfft - i (wd <= nfft / 3: once)
+//   GEMM 2  Y[q] = (c sinc) comp, c = (X times cep)[q], sinc = sinpi(q / T) / (pi (q / T)) (1 at q = 0), comp = (1 - 2 q1) + (2 q1) cospi(2 (q / T))
+//   GEMM 3a d_env[k] = nfft (Y times cep)[k];  GEMM 3b d_mcep[m] = (Y times warp)[m].  Zeros for a silent frame (live = 0) and past the row.
+// BANKS.  Passes 1 to 3 touch a plane at consecutive doubles over the 64 lanes, pass 2's interpolation at consecutive doubles descending and pass 3's
+// cells at a common offset from consecutive bins (mirrored: descending): conflict-free but where a mirror folds a group onto itself (2-way, at the
+// two ends of the spectrum only).  The A fragments of the three GEMMs are voice_quality_kernel's phase 2 reads (S = 2 mod 32): conflict-free.
+// GEMM 2's epilogue stores Y[(q + 4 i) S + col] once per quefrency tile: 16 consecutive doubles per frame, the two frames of a group of 32 lanes
+// 2 S = 4 mod 64 dwords apart, so their spans overlap on 28 banks: 2-way, as voice_quality_kernel's stores of Ldb, and as rare.
+struct EnvCepParams { const int32_t* len; const float* period; const double* P; double* env; double* mcep; int32_t* cls; EnvTables t; int L, NF; double floor; };
+
+__global__ __launch_bounds__(256) void envelope_cepstrum_kernel(const EnvCepParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) double env_smem[];
+    __shared__ double Ts[16];
+    __shared__ int keep_s[16];
+    const int b = blockIdx.y, f0 = blockIdx.x * 16, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int H = p.t.H, nfft = p.t.nfft, NB = p.t.NB, NBp = p.t.NBp, S = p.t.S, NM = p.t.n_mcep, hn = nfft >> 1;
+    int n;
+    const int nf = voiceq_frames(p.len, b, p.L, H, &n);
+    const int nfr = p.NF - f0 < 16 ? p.NF - f0 : 16;                    // the tile's frames inside the outputs (>= 1)
+    int32_t* ck = p.cls + ((size_t)b * p.NF + f0) * 3;
+    double* ev = p.env ? p.env + ((size_t)b * p.NF + f0) * NB : nullptr;
+    double* mc = p.mcep + ((size_t)b * p.NF + f0) * NM;
+    if (f0 >= nf) {                                                     // (uniform) zeros past the row's own frames, class 3
+        if (tid < 3 * nfr) ck[tid] = tid % 3 == 0 ? 3 : 0;
+        for (int i = tid; i < nfr * NM; i += 256) mc[i] = 0.0;
+        if (ev) for (int i = tid; i < nfr * NB; i += 256) ev[i] = 0.0;
+        return;
+    }
+    double* X = env_smem;
+    double* Y = env_smem + (size_t)16 * S;
+    const float* pr = p.period + (size_t)b * p.NF;
+    double T[4], rn[4];                                                 // of the wave's own frames: the period and nfft / T
+    int kd[4];
+    // ---- pass 1
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int fr = 4 * wv + i;
+        const bool in = f0 + fr < nf;
+        double* xa = X + (size_t)fr * S;
+        int cls = 3, live = 0, half = 0;
+        T[i] = p.t.T_def;
+        if (in) {
+            T[i] = env_period(pr, (size_t)(f0 + fr), p.t, &cls);
+            half = env_half(T[i]);
+            const double* Pg = p.P + ((size_t)b * p.NF + f0 + fr) * NB;
+            for (int k = lane; k < NB; k += 64) { const double v = Pg[k]; xa[k] = v; live += v > p.floor ? 1 : 0; }
+        } else {
+            for (int k = lane; k < NB; k += 64) xa[k] = 0.0;
+        }
+        rn[i] = (double)nfft / T[i];
+        kd[i] = in ? (int)floor(rn[i]) : -1;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) live += __shfl_xor(live, o, 64);
+        if (lane == 0) {
+            Ts[fr] = T[i];
+            keep_s[fr] = in && live > 0 ? 1 : 0;
+            if (fr < nfr) { ck[3 * fr] = in ? (live > 0 ? cls : 2) : 3; ck[3 * fr + 1] = half; ck[3 * fr + 2] = in ? kd[i] : 0; }
+        }
+    }
+    __syncthreads();
+    // ---- pass 2
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int fr = 4 * wv + i;
+        const double* xa = X + (size_t)fr * S;
+        double* ya = Y + (size_t)fr * S;
+        for (int k = lane; k < NB; k += 64) {
+            double v = xa[k];
+            if (k <= kd[i]) {
+                const double u = rn[i] - (double)k;
+                const int i0 = (int)floor(u);
+                const double fu = u - (double)i0;
+                const int i1 = i0 + 1 < NB - 1 ? i0 + 1 : NB - 1;
+                v = v + (xa[i0] * (1.0 - fu) + xa[i1] * fu);
+            }
+            ya[k] = v;
+        }
+    }
+    __syncthreads();
+    // ---- pass 3
+#pragma unroll 1
+    for (int i = 0; i < 4; ++i) {
+        const int fr = 4 * wv + i;
+        double* xa = X + (size_t)fr * S;
+        const double* ya = Y + (size_t)fr * S;
+        const double wd = (2.0 * (double)nfft) / (3.0 * Ts[fr]), hw = 0.5 * wd;
+        for (int k = lane; k < NB; k += 64) {
+            const double lo = (double)k - hw, hi = (double)k + hw;
+            const int ilo = (int)floor(lo + 0.5), ihi = (int)floor(hi + 0.5);
+            const int alo = ilo < 0 ? -ilo : ilo > hn ? nfft - ilo : ilo;
+            double acc;
+            if (ilo == ihi) acc = ya[alo] * (hi - lo);
+            else {
+                acc = ya[alo] * (((double)ilo + 0.5) - lo);
+                for (int c = ilo + 1; c < ihi; ++c) acc = acc + ya[c < 0 ? -c : c > hn ? nfft - c : c];
+                acc = acc + ya[ihi < 0 ? -ihi : ihi > hn ? nfft - ihi : ihi] * (hi - ((double)ihi - 0.5));
+            }
+            xa[k] = log(fmax(acc / wd, p.floor));
+        }
+    }
+    __syncthreads();
+    const int r = lane & 15, q = lane >> 4;
+    // ---- GEMM 2 and the lifter
+    {
+        const double q1 = p.t.q1, c0 = 1.0 - 2.0 * q1, c1 = 2.0 * q1;
+        env_gemm(X + (size_t)r * S, p.t.cep, NB, NB, NBp, wv, r, q, [&](int col, const stftd_acc& c) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int fr = q + 4 * i;
+                const double x = (double)col / Ts[fr];
+                const double sinc = col == 0 ? 1.0 : sinpi(x) / (3.141592653589793 * x);
+                const double comp = c0 + c1 * cospi(2.0 * x);
+                Y[(size_t)fr * S + col] = (c[i] * sinc) * comp;
+            }
+        });
+    }
+    __syncthreads();
+    // ---- GEMM 3a and 3b
+    if (ev) {
+        const double dn = (double)nfft;
+        env_gemm(Y + (size_t)r * S, p.t.cep, NB, NB, NBp, wv, r, q, [&](int col, const stftd_acc& c) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int fr = q + 4 * i;
+                if (fr < nfr) ev[(size_t)fr * NB + col] = keep_s[fr] ? dn * c[i] : 0.0;
+            }
+        });
+    }
+    env_gemm(Y + (size_t)r * S, p.t.warp, NM, NB, NBp, wv, r, q, [&](int col, const stftd_acc& c) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int fr = q + 4 * i;
+            if (fr < nfr) mc[(size_t)fr * NM + col] = keep_s[fr] ? c[i] : 0.0;
+        }
+    });
+}

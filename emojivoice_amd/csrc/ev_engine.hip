@@ -138,6 +138,9 @@ struct AudW { bool loaded = false; size_t lds = 0; AudTables t{}; };
 struct SrmrW { bool loaded = false; double* blk = nullptr; SrmrTables t{}; };
 // Geometry of ev_speech_rate: the intensity window (W) float64 on the device, one block, and its sum in ascending order
 struct RateW { bool loaded = false; double* win = nullptr; int W = 0, H = 0; double sw = 0; };
+// Tables of ev_envelope, one device block: the plain DFT basis (nfft, NB), the cepstral basis (NBp, NB) and the warp table (NBp, n_mcep); lds1, lds2:
+// the dynamic LDS of the two launches in bytes (ev_analysis_kernels.h)
+struct EnvW { bool loaded = false; size_t lds1 = 0, lds2 = 0; EnvTables t{}; };
 // Geometry of ev_formants: the analysis window (W) float64 on the device, one block; the rest travels in the kernel's arguments (z0: the root
 // finder's starting points {re, im}, R: samples per lane of formants_kernel)
 struct FormantW { bool loaded = false; double* win = nullptr; int W = 0, H = 0, order = 0, nform = 0, R = 0; double pre = 0, sr = 0, f_lo = 0; double z0[64] = {0}; };
@@ -163,6 +166,7 @@ struct ev_handle {
     AudW aud;
     SrmrW srmr;
     RateW rate;
+    EnvW env;
     // small per-stage scratch arenas (denoiser, text encoder): grown on demand, ordered against their last user's stream
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
     Scratch dn_ws, enc_ws, mas_ws;   // (mas_ws: the alignment search's frame -> token index and, for large Tx * Ty, its decision bits)
@@ -174,6 +178,7 @@ struct ev_handle {
     Scratch stftd_ws;                // ev_stft_dist: the per-frame sums (B x NF x 4 doubles) without d_frame
     Scratch srmr_ws;                 // ev_srmr: per (row, chunk) the channel states, the band states and the window-quarter sums
     Scratch rate_ws;                 // ev_speech_rate: the power contour (B x NF doubles) without d_power
+    Scratch env_ws;                  // ev_envelope: the power spectra between its two launches (B x NF x NB doubles)
     float* zeros = nullptr;     // 4096 zero floats (stand-in bias for the fused kernels' unconditional loads)
     int max_steps = 64;         // Euler steps the time-grid buffers of the workspace are planned for (grows on demand)
     int* bad_ids_host = nullptr; int* bad_ids_dev = nullptr;   // mapped host word: count of out-of-range token ids seen by ev_text_encoder
@@ -2048,6 +2053,7 @@ void ev_destroy(ev_handle* h) {
     if (h->stftd_ws.p) hipFree(h->stftd_ws.p);
     if (h->srmr_ws.p) hipFree(h->srmr_ws.p);
     if (h->rate_ws.p) hipFree(h->rate_ws.p);
+    if (h->env_ws.p) hipFree(h->env_ws.p);
     if (h->dn_ws.p) hipFree(h->dn_ws.p);
     if (h->bad_ids_host) hipHostFree(h->bad_ids_host);
     for (int i = 0; i < 2; ++i) { if (h->temb_ev[i]) hipEventDestroy(h->temb_ev[i]); if (h->temb_host[i]) hipHostFree(h->temb_host[i]); }

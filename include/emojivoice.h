@@ -41,6 +41,8 @@
  *   ev_srmr            <- no counterpart; Falk, Zheng and Chan 2010 (SRMR) and Hohmann 2002 (complex gammatone) are the model
  *   ev_load_speech_rate <- no counterpart; De Jong and Wempe 2009 (syllable nuclei) is the model
  *   ev_speech_rate     <- no counterpart; De Jong and Wempe 2009 (syllable nuclei) is the model
+ *   ev_load_envelope   <- no counterpart; Morise 2015 (CheapTrick) and SPTK's freqt are the model
+ *   ev_envelope        <- no counterpart; Morise 2015 (CheapTrick) and SPTK's freqt are the model
  *   ev_load_stoi       <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_stoi            <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_load_stft_dist  <- no counterpart; Yamamoto et al. 2020 (multi-resolution STFT loss) is the model
@@ -96,7 +98,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation, ev_load_srmr, ev_srmr, ev_load_speech_rate, ev_speech_rate (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation, ev_load_srmr, ev_srmr, ev_load_speech_rate, ev_speech_rate, ev_load_envelope, ev_envelope (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -633,6 +635,66 @@ int ev_speech_rate(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d
                    int min_pause, int min_sound,
                    double *d_power /* (B, NF) or NULL */, uint8_t *d_mark /* (B, NF) or NULL */,
                    double *d_stat /* (B, 4) */, int32_t *d_count /* (B, 8) */, void *stream);
+
+/* Spectral envelope and mel-cepstrum on the device: the f0-adaptive envelope of CheapTrick (Morise, Speech Communication 67, 2015), the envelope
+ * WORLD uses, and its frequency-warped cepstrum by the recursion of SPTK's freqt, per frame of ev_voice_quality's grid, the period of every frame
+ * coming from ev_pitch_yin's d_period.  pyworld and pysptk are NOT the yardstick: the published algorithms are the model and the definition below
+ * is what the device is held to (tests/envelope_ref.py restates it in numpy float64).  Everything is float64, the fp32 samples and periods are
+ * widened, floating-point contraction is off; ev_set_arithmetic does not reach it.
+ *
+ * ev_load_envelope: HOST twiddle (nfft, 2) {cos, sin}(2 pi n / nfft); hop H; the rate sr in Hz; default_period in samples (0: sr / 500, WORLD's
+ * default f0); the lifter's q1 (CheapTrick: -0.15); HOST warp (n_mcep, NB), the matrix A of step 7 (NB = nfft / 2 + 1).  Limits, each violation
+ * failing with a message that names it: twiddle and warp non-NULL and finite; nfft even with 16 <= nfft <= 1024; 1 <= H <= 512 (the DFT families'
+ * rule); 1 <= n_mcep <= 64; sr finite and > 0; q1 and default_period finite; 2 <= default_period <= T_max; the two launches' LDS (16 S1 and 32 S
+ * doubles, S1 and S the row strides: 131 328 and 131 584 bytes at nfft = 1024) at most 160 KiB.  The load owns one device block (the plain DFT
+ * basis, the cepstral basis, the warp table) and counts once in ev_alloc_count; loading again waits for the device and drops the old block; a
+ * failed load leaves the previous tables in use.
+ *
+ * DEFINITION.  NF = ceil(L / H); a row of len samples has nf = ceil(len / H) frames; a row with len < 1 or len > L is empty.  d_len == NULL: every
+ * row is L long.  Frame f is centred at sample c = f H + H / 2.  T = (double)d_period[b, f]; if T is not > 0 (unvoiced, NaN), T < T_min = 2 or
+ * T > T_max = (nfft - 3) / 3 (CheapTrick's f0 floor 3 sr / (nfft - 3)), then T = default_period and the frame's class is 1.  Every integer below is
+ * formed from T by exactly the stated float64 expression.
+ *   1 window    half = floor(1.5 T + 0.5); w[j] = 0.5 cospi(j / (1.5 T)) + 0.5 for -half <= j <= half.  x[c + j] is 0 outside [0, len) (WORLD
+ *               repeats the edge sample; this project pads with zeros, as its other frame families do).  With the three sums sum w w, sum w and
+ *               sum x w, each over the 64-slot rule (term i = j + half belongs to slot i mod 64, ascending in a slot, then the xor tree with offsets
+ *               32 .. 1): s[j] = (x w - w ((sum x w) / (sum w))) / sqrt(sum w w): the window has unit energy and the weighted mean is removed.
+ *               WORLD's random safeguard noise is left out: the output is deterministic.
+ *   2 power     P[k] = |DFT_nfft(s)|^2 = fma(im, im, re re), k = 0 .. NB - 1.  A frame with no P[k] > power_floor is SILENT (class 2): its d_env
+ *               and d_mcep are zeros.
+ *   3 DC        rn = nfft / T, kd = floor(rn).  For 0 <= k <= kd: u = rn - k, i = floor(u), P'[k] = P[k] + (P[i] (1 - (u - i)) + P[min(i + 1,
+ *               NB - 1)] (u - i)), the interpolation reading the uncorrected P.  P'[k] = P[k] for every other k.
+ *   4 smoothing wd = (2 nfft) / (3 T) bins (2 f0 / 3).  S[k] = (1 / wd) times the integral over [lo, hi) = [k - wd / 2, k + wd / 2) of the
+ *               piecewise-constant P', cell i covering [i - 1/2, i + 1/2), an index i < 0 reading -i and i > nfft / 2 reading nfft - i.  With
+ *               ilo = floor(lo + 0.5) and ihi = floor(hi + 0.5): P'[ilo] (hi - lo) if ilo == ihi, else P'[ilo] ((ilo + 0.5) - lo), plus P'[i] for
+ *               ilo < i < ihi in ascending order, plus P'[ihi] (hi - (ihi - 0.5)); then one division by wd.  WORLD takes the same integral as a
+ *               difference of cumulative sums; the direct sum adds positive terms only, so no weak bin is lost to cancellation.
+ *   5 lifter    Lg[k] = log(max(S[k], power_floor));  c^[q] = sum_k Lg[k] (g[k] cos(2 pi k q / nfft) / nfft), q = 0 .. nfft / 2, g = 1 at k = 0 and
+ *               k = nfft / 2, else 2 (ev_voice_quality's cepstral table at q_fit = 0);  c'[q] = (c^[q] sinc) comp with x = q / T,
+ *               sinc = sinpi(x) / (pi x) (1 at q = 0) and comp = (1 - 2 q1) + (2 q1) cospi(2 x).
+ *   6 envelope  Le[k] = nfft sum_q c'[q] (g[q] cos(2 pi q k / nfft) / nfft): the log POWER envelope in nepers (d_env; 10 / ln 10 times it is dB).
+ *   7 mcep      c[0] = c'[0] / 2, c[m] = c'[m]: SPTK's one-sided cepstrum of the log AMPLITUDE.  mc = A c, A (n_mcep, NB) the matrix of freqt at
+ *               alpha: column n is the result of the recursion on the unit vector e_n: for i = N down to 0, with d = g saved from the previous
+ *               pass: g[0] = c[i] + alpha d[0]; g[1] = (1 - alpha^2) d[0] + alpha d[1]; g[m] = d[m-1] + alpha (d[m] - g[m-1]) for m >= 2.
+ *               (alpha = 0.455 suits 22.05 kHz.)  The host builds A in float64; the load folds the halving of c[0] into its copy.
+ * The sums over k and q are matrix products on v_mfma_f64_16x16x4_f64, K ascending in steps of 4.
+ * Outputs:
+ *   d_env     (B, NF, NB) float64 or NULL: Le
+ *   d_mcep    (B, NF, n_mcep) float64: mc
+ *   d_class   (B, NF, 3) int32: {class, half, kd}; class 0 voiced (T from d_period), 1 default period, 2 silent (half and kd as computed),
+ *             3 beyond the row ({3, 0, 0})
+ * Frames at and past nf are zeros in d_env and d_mcep.  Nothing at or behind len is read, of d_x or of d_period's frames past nf.  Nothing depends
+ * on B, L or the place in the grid: the same inputs give the same bits for a row alone, inside a batch, at a larger L, in a second call, under
+ * every ev_set_arithmetic setting and from a captured graph.
+ * Limits of ev_envelope, each violation failing with a message that names it, the call writing nothing: tables loaded; 1 <= B <= 65535; L >= 1;
+ * d_x, d_period, d_mcep and d_class non-NULL; power_floor finite and > 0.
+ * Scratch: the power spectra (B x NF x NB doubles: 135 MB at 64 rows of 6 s) live in an arena of the handle that grows on demand and counts in
+ *   ev_alloc_count: a second call at the same shape allocates nothing; ev_reserve does not cover it.  Two kernel launches on `stream`, no atomics,
+ *   no host wait, no copy: the call is capturable once the arena has its size. */
+int ev_load_envelope(ev_handle *h, const double *twiddle /* HOST (nfft, 2) */, int H, int nfft, double sr, double default_period, double q1,
+                     const double *warp /* HOST (n_mcep, nfft / 2 + 1) */, int n_mcep);
+int ev_envelope(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, const float *d_period /* (B, NF) */,
+                int B, int L, double power_floor, double *d_env /* (B, NF, NB) or NULL */, double *d_mcep /* (B, NF, n_mcep) */,
+                int32_t *d_class /* (B, NF, 3) */, void *stream);
 
 /* STOI and ESTOI on the device: short-time objective intelligibility of a processed row y against the clean, sample-aligned row x (Taal,
  * Hendriks, Heusdens and Jensen, IEEE TASL 19(7), 2011) and its extended form (Jensen and Taal, IEEE/ACM TASLP 24(11), 2016), for rows already

@@ -48,6 +48,7 @@ EXPORTS = [
     "ev_load_srmr", "ev_srmr",
     "ev_load_speech_rate", "ev_speech_rate",
     "ev_load_envelope", "ev_envelope",
+    "ev_op_conv1d_epi",
 ]
 
 
@@ -67,6 +68,16 @@ class ev_model_dims(C.Structure):
 class ev_vocoder_config(C.Structure):
     _fields_ = [("resblock", C.c_int32), ("num_levels", C.c_int32), ("upsample_rates", C.c_int32 * 4), ("upsample_kernel_sizes", C.c_int32 * 4),
                 ("resblock_kernel_sizes", C.c_int32 * 3), ("resblock_dilations", (C.c_int32 * 3) * 3)]
+
+
+class ev_conv_epi(C.Structure):
+    _fields_ = [("act", C.c_int32), ("act_slope", C.c_float), ("d_alpha_exp", C.c_void_p), ("d_beta_inv", C.c_void_p), ("d_lengths", C.c_void_p),
+                ("mask1", C.c_int32), ("mask2", C.c_int32), ("scale", C.c_float), ("d_R", C.c_void_p), ("accum", C.c_int32), ("d_yold", C.c_void_p),
+                ("div3", C.c_int32), ("act2_slope", C.c_float), ("pre_lrelu_slope", C.c_float)]
+
+
+CONV_EPI_SENTINEL = 1234.5                         # EV_CONV_EPI_SENTINEL: what ev_op_conv1d_epi leaves in Y's pad rows before the launch
+CONV_ACTS = {"none": 0, "lrelu": 1, "tanh": 2, "silu": 3, "mish": 4, "snake": 5}
 
 
 def vocoder_config(h) -> ev_vocoder_config:
@@ -206,6 +217,7 @@ def load_library() -> C.CDLL:
     lib.ev_dbg_sk_taken.argtypes = [vp]
     lib.ev_dbg_sk_taken.restype = C.c_int64
     lib.ev_op_conv1d.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]
+    lib.ev_op_conv1d_epi.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(ev_conv_epi), vp, vp, vp, vp]
     lib.ev_op_groupnorm_mish.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     lib.ev_op_groupnorm_mish2.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]
     lib.ev_op_conv_groupnorm.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, C.POINTER(C.c_int), vp]
@@ -1223,6 +1235,42 @@ class Engine:
                                           int(transposed), stride, padding, float(pre_lrelu_slope), y.data_ptr(), _stream_ptr()),
                     "ev_op_conv1d")
         return y
+
+    def op_conv1d_epi(self, x, w, bias, dilation=1, transposed=False, stride=1, padding=0, P=32, pre_lrelu_slope=-1.0, act="none",
+                      act_slope=0.0, alpha_exp=None, beta_inv=None, lengths=None, mask1=False, mask2=False, scale=1.0, R=None, yold=None,
+                      accum=False, div3=False, act2_slope=-1.0, want_y2=False, want_padded=False):
+        """One conv launch with the whole fused epilogue (ev_op_conv1d_epi; +bias, act, *mask1, *scale, +R, +Yold, /3, lrelu2, *mask2).
+        x (B, Cin, T); R, yold (B, Cout, Tout); lengths (B,) in output frames; P pad rows a side.  Returns (y, y2 or None, padded Y or None):
+        the padded Y is frame-major (B * (Tout + 2 Pout), Cout), its pad rows CONV_EPI_SENTINEL unless the launch stored there."""
+        x = self._f32(x)
+        B, Cin, T = x.shape
+        w = np.ascontiguousarray(w.detach().cpu().float().numpy())
+        if transposed:
+            Cout, K, Tout, Pout = w.shape[1], w.shape[2], T * stride, P * stride
+        else:
+            Cout, K, Tout, Pout = w.shape[0], w.shape[2], T // stride, P // stride
+        bp = None
+        if bias is not None:
+            bnp = np.ascontiguousarray(bias.detach().cpu().float().numpy())
+            bp = bnp.ctypes.data_as(C.c_void_p)
+        keep = [None if t is None else self._f32(t) for t in (alpha_exp, beta_inv, R, yold)]
+        if lengths is not None:
+            lengths = lengths.to(x.device, torch.int32).contiguous()
+        for t in keep[2:]:
+            if t is not None and tuple(t.shape) != (B, Cout, Tout):
+                raise ValueError(f"R / yold must be {(B, Cout, Tout)}, got {tuple(t.shape)}")
+        for t in keep[:2]:
+            if t is not None and t.numel() != Cout:
+                raise ValueError("alpha_exp / beta_inv must hold Cout values")
+        ep = ev_conv_epi(CONV_ACTS[act], float(act_slope), _ptr(keep[0]), _ptr(keep[1]), _ptr(lengths), int(mask1), int(mask2), float(scale),
+                         _ptr(keep[2]), int(accum), _ptr(keep[3]), int(div3), float(act2_slope), float(pre_lrelu_slope))
+        y = torch.empty((B, Cout, Tout), dtype=torch.float32, device=x.device)
+        y2 = torch.empty_like(y) if want_y2 else None
+        ypad = torch.empty((B * (Tout + 2 * Pout), Cout), dtype=torch.float32, device=x.device) if want_padded else None
+        self._check(self.lib.ev_op_conv1d_epi(self.h, x.data_ptr(), w.ctypes.data_as(C.c_void_p), bp, B, Cin, T, Cout, K, dilation, int(transposed),
+                                              stride, padding, int(P), C.byref(ep), y.data_ptr(), _ptr(y2), _ptr(ypad), _stream_ptr()),
+                    "ev_op_conv1d_epi")
+        return y, y2, ypad
 
     def op_groupnorm_mish(self, x, gamma, beta, lengths, groups=8):
         x, gamma, beta = self._f32(x), self._f32(gamma), self._f32(beta)

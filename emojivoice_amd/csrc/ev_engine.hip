@@ -3234,6 +3234,131 @@ int ev_op_conv1d(ev_handle* h, const float* d_x, const float* w, const float* bi
     return rc;
 }
 
+// ev_op_conv1d with the whole epilogue of launch_conv (tests/test_gpu_conv.py): the layer packed and the input staged as above, ONE launch_conv
+// with an Epi filled from `ep`, the caller's pad rows P a side.  Y starts as EV_CONV_EPI_SENTINEL in every pad row and in every valid frame
+// that d_yold does not fill, so d_ypad shows any store outside the valid frames.  Bad arguments fail the call before anything is launched.
+int ev_op_conv1d_epi(ev_handle* h, const float* d_x, const float* w, const float* bias, int B, int Cin, int T, int Cout, int K,
+                     int dilation, int transposed, int stride, int padding, int P, const ev_conv_epi* ep, float* d_y, float* d_y2,
+                     float* d_ypad, void* stream) {
+    if (enter(h)) return 1;
+    h->stream = (hipStream_t)stream;
+    if (!d_x || !w || !ep || !d_y || B <= 0 || Cin <= 0 || T <= 0 || Cout <= 0 || K <= 0 || dilation <= 0 || stride <= 0 || P < 0 || (Cin & 3))
+        return fail(h, "ev_op_conv1d_epi: bad arguments (null pointer, non-positive size or Cin %% 4 != 0)");
+    if (ep->act < ACT_NONE || ep->act > ACT_SNAKE) return fail(h, "ev_op_conv1d_epi: act %d is not one of 0 .. 5", ep->act);
+    if (ep->act == ACT_LRELU && !(ep->act_slope >= 0.f && ep->act_slope <= 1.f)) return fail(h, "ev_op_conv1d_epi: act_slope must lie in [0, 1]");
+    if (ep->act == ACT_SNAKE && (!ep->d_alpha_exp || !ep->d_beta_inv || (((size_t)ep->d_alpha_exp | (size_t)ep->d_beta_inv) & 15)))
+        return fail(h, "ev_op_conv1d_epi: SnakeBeta needs d_alpha_exp and d_beta_inv, 16-byte aligned");
+    if ((ep->mask1 || ep->mask2) && !ep->d_lengths) return fail(h, "ev_op_conv1d_epi: mask1 / mask2 need d_lengths");
+    if (d_y2 && !ep->d_lengths) return fail(h, "ev_op_conv1d_epi: d_y2 (= v * rowmask) needs d_lengths");
+    if (ep->d_lengths && transposed) return fail(h, "ev_op_conv1d_epi: no row mask on a transposed conv (column-split views are out of scope)");
+    if (ep->accum && !ep->d_yold) return fail(h, "ev_op_conv1d_epi: accum needs d_yold");
+    if (!std::isfinite(ep->scale)) return fail(h, "ev_op_conv1d_epi: scale must be finite");
+    if (ep->act2_slope > 1.f || ep->pre_lrelu_slope > 1.f) return fail(h, "ev_op_conv1d_epi: leaky-relu slopes must not exceed 1");
+    const bool s2 = !transposed && stride == 2;
+    if (!transposed && stride != 1 && stride != 2) return fail(h, "ev_op_conv1d_epi: conv stride 1 or 2");
+    if (s2 && (P & 1)) return fail(h, "ev_op_conv1d_epi: the pair view of a stride-2 conv needs an even P");
+    ConvLayer L;
+    HostTensor wt, bt;
+    wt.p = w; wt.ndim = 3;
+    bt.p = bias; bt.ndim = 1;
+    int Tout = T;
+    size_t owned0 = h->owned.size();
+    auto drop_layer = [&]() { while (h->owned.size() > owned0) { hipFree(h->owned.back()); h->owned.pop_back(); } };
+    int prc = 0;
+    if (!transposed && stride == 1) {
+        wt.shape[0] = Cout; wt.shape[1] = Cin; wt.shape[2] = K; bt.shape[0] = Cout;
+        if (padding != (K * dilation - dilation) / 2) return fail(h, "only 'same' padding is supported");
+        prc = pack_conv(h, L, wt, bias ? &bt : nullptr, dilation);
+    } else if (s2) {
+        wt.shape[0] = Cout; wt.shape[1] = Cin; wt.shape[2] = K; bt.shape[0] = Cout;
+        if (K != 3 || padding != 1 || (T & 1)) return fail(h, "stride-2 conv: k=3, p=1, even T");
+        prc = pack_conv_stride2(h, L, wt, bias ? &bt : nullptr);
+        Tout = T / 2;
+    } else {
+        wt.shape[0] = Cin; wt.shape[1] = Cout; wt.shape[2] = K; bt.shape[0] = Cout;
+        if ((K - 2 * padding) != stride || padding < 0) return fail(h, "transposed conv must satisfy K - 2p == stride");
+        prc = pack_convT(h, L, wt, bias ? &bt : nullptr, stride, padding);
+        Tout = T * stride;
+    }
+    if (prc) { drop_layer(); return 1; }
+    const int Pv = s2 ? P / 2 : P;      // pad rows of the view launch_conv walks
+    if (Pv < std::max(L.halo_lo, L.halo_hi)) {
+        drop_layer();
+        return fail(h, "ev_op_conv1d_epi: P = %d pad rows are fewer than the layer's halo (%d view rows)", P, std::max(L.halo_lo, L.halo_hi));
+    }
+    int rc = 0;
+    float *X = nullptr, *Y = nullptr, *R = nullptr, *Y2 = nullptr, *rm = nullptr, *SA = nullptr, *SB = nullptr;
+    unsigned* XM = nullptr;
+    do {
+        const float *act_a = ep->d_alpha_exp, *act_b = ep->d_beta_inv;
+        if (ep->act == ACT_SNAKE && transposed) {   // the packed layer has stride x Cout channels: SnakeBeta's vectors once per phase, as pack_convT lays the bias
+            if (hipMalloc((void**)&SA, (size_t)stride * Cout * 4) != hipSuccess || hipMalloc((void**)&SB, (size_t)stride * Cout * 4) != hipSuccess) { rc = fail(h, "hipMalloc failed"); break; }
+            for (int r = 0; r < stride; ++r) {
+                hipMemcpyAsync(SA + (size_t)r * Cout, ep->d_alpha_exp, (size_t)Cout * 4, hipMemcpyDeviceToDevice, h->stream);
+                hipMemcpyAsync(SB + (size_t)r * Cout, ep->d_beta_inv, (size_t)Cout * 4, hipMemcpyDeviceToDevice, h->stream);
+            }
+            act_a = SA; act_b = SB;
+        }
+        const Geom gin{B * (T + 2 * P), T + 2 * P, P, T};
+        const int Pout = transposed ? P * stride : Pv;
+        const Geom gout{B * (Tout + 2 * Pout), Tout + 2 * Pout, Pout, Tout};
+        const size_t nx = (size_t)gin.nrows * Cin, ny = (size_t)gout.nrows * Cout;
+        if (hipMalloc((void**)&X, nx * 4) != hipSuccess || hipMalloc((void**)&Y, ny * 4) != hipSuccess ||
+            (ep->d_R && hipMalloc((void**)&R, ny * 4) != hipSuccess) || (d_y2 && hipMalloc((void**)&Y2, ny * 4) != hipSuccess) ||
+            (ep->d_lengths && hipMalloc((void**)&rm, (size_t)gout.nrows * 4) != hipSuccess)) { rc = fail(h, "hipMalloc failed"); break; }
+        hipMemsetAsync(X, 0, nx * 4, h->stream);
+        {   // the sentinel everywhere, then Yold over the valid frames
+            std::vector<float> fill(ny, EV_CONV_EPI_SENTINEL);
+            if (hipMemcpyAsync(Y, fill.data(), ny * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+                (Y2 && hipMemcpyAsync(Y2, fill.data(), ny * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
+                hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(h, "sentinel fill failed"); break; }
+        }
+        if (R) hipMemsetAsync(R, 0, ny * 4, h->stream);
+        const dim3 g1((T + 31) / 32, (Cin + 31) / 32, B), g2((Tout + 31) / 32, (Cout + 31) / 32, B);
+        hipLaunchKernelGGL(cm_to_fm_kernel, g1, dim3(256), 0, h->stream, d_x, X, Cin, 0, Cin, T, gin.S, gin.P, (const float*)nullptr, 1.0f);
+        if (ep->d_yold) hipLaunchKernelGGL(cm_to_fm_kernel, g2, dim3(256), 0, h->stream, ep->d_yold, Y, Cout, 0, Cout, Tout, gout.S, gout.P, (const float*)nullptr, 1.0f);
+        if (R) hipLaunchKernelGGL(cm_to_fm_kernel, g2, dim3(256), 0, h->stream, ep->d_R, R, Cout, 0, Cout, Tout, gout.S, gout.P, (const float*)nullptr, 1.0f);
+        if (rm) hipLaunchKernelGGL(rowmask_kernel, dim3((gout.nrows + 255) / 256), dim3(256), 0, h->stream, rm, ep->d_lengths, gout.nrows, gout.S, gout.P, gout.T, 1);
+        Epi e;
+        e.pro_slope = ep->pre_lrelu_slope;
+        e.act = ep->act; e.act_slope = ep->act_slope; e.act_a = act_a; e.act_b = act_b;
+        e.mask1 = ep->mask1 != 0; e.mask2 = ep->mask2 != 0; e.rowmask = rm; e.scale = ep->scale;
+        e.accum = ep->accum != 0; e.div3 = ep->div3 != 0;
+        e.act2_lrelu = ep->act2_slope >= 0.f; e.act2_slope = ep->act2_slope >= 0.f ? ep->act2_slope : 0.f;
+        const int ldy = transposed ? stride * Cout : Cout;      // (a transposed conv writes the view whose row holds `stride` output frames)
+        e.R = R; e.ldr = R ? ldy : 0; e.Y2 = Y2; e.ldy2 = Y2 ? ldy : 0;
+        if (h->use_amax && !s2) {   // the input's amax slots, exact, as ev_op_conv1d leaves them
+            const int ns = (gin.nrows >> 7) + 2;
+            if (hipMalloc((void**)&XM, (size_t)ns * 4) != hipSuccess) { rc = fail(h, "hipMalloc failed"); break; }
+            hipMemsetAsync(XM, 0, (size_t)ns * 4, h->stream);
+            hipLaunchKernelGGL(amax_rows_kernel, dim3((gin.nrows + 127) / 128), dim3(256), 0, h->stream, (const float*)X, Cin, Cin, gin.nrows, XM);
+            e.xmax = XM; e.xmax_n = ns;
+        }
+        if (s2) {
+            const Geom gv{gin.nrows / 2, gin.S / 2, gin.P / 2, T / 2};
+            rc = launch_conv(h, L, X, 2 * Cin, Y, Cout, gv, e);
+        } else {
+            rc = launch_conv(h, L, X, Cin, Y, ldy, gin, e);
+        }
+        if (rc) break;
+        hipLaunchKernelGGL(fm_to_cm_kernel, g2, dim3(256), 0, h->stream, (const float*)Y, Cout, 0, d_y, Cout, Tout, gout.S, gout.P, 1.0f, 0.0f);
+        if (Y2) hipLaunchKernelGGL(fm_to_cm_kernel, g2, dim3(256), 0, h->stream, (const float*)Y2, Cout, 0, d_y2, Cout, Tout, gout.S, gout.P, 1.0f, 0.0f);
+        if (d_ypad) hipMemcpyAsync(d_ypad, Y, ny * 4, hipMemcpyDeviceToDevice, h->stream);
+        if (hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, "sync failed: %s", hipGetErrorString(hipGetLastError()));
+    } while (0);
+    if (rc) hipStreamSynchronize(h->stream);
+    if (X) hipFree(X);
+    if (Y) hipFree(Y);
+    if (R) hipFree(R);
+    if (Y2) hipFree(Y2);
+    if (rm) hipFree(rm);
+    if (XM) hipFree(XM);
+    if (SA) hipFree(SA);
+    if (SB) hipFree(SB);
+    drop_layer();
+    return rc;
+}
+
 int ev_op_groupnorm_mish(ev_handle* h, const float* d_x, const float* d_gamma, const float* d_beta, const int32_t* d_lengths,
                          int B, int C, int T, int groups, float* d_y, void* stream) {
     if (enter(h)) return 1;

@@ -98,7 +98,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation, ev_load_srmr, ev_srmr, ev_load_speech_rate, ev_speech_rate, ev_load_envelope, ev_envelope (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation, ev_load_srmr, ev_srmr, ev_load_speech_rate, ev_speech_rate, ev_load_envelope, ev_envelope, ev_op_conv1d_epi (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -1269,6 +1269,33 @@ int64_t ev_dbg_sk_taken(ev_handle *h);
 int ev_op_conv1d(ev_handle *h, const float *d_x /*(B,Cin,T)*/, const float *w /*HOST (Cout,Cin,K)*/,
                  const float *bias /*HOST (Cout) or NULL*/, int B, int Cin, int T, int Cout, int K, int dilation,
                  int transposed, int stride, int padding, float pre_lrelu_slope /*<0: none*/, float *d_y, void *stream);
+/* ev_op_conv1d with the whole fused epilogue of a conv launch (tests/test_gpu_conv.py).  The layer is packed and the input staged exactly as
+ * ev_op_conv1d does ('same' conv; stride-2 k3 over the pair view, even T and P; polyphase transposed conv), then ONE launch runs with this
+ * epilogue, in the order  +bias, act, *mask1, *scale, +R, +Yold, /3, lrelu(act2_slope), *mask2,  and Y2 = v * rowmask beside it.
+ * Sizes and lengths are in OUTPUT frames Tout (T; T / 2; T * stride). */
+typedef struct ev_conv_epi {
+  int32_t act;                /* 0 none, 1 leaky-relu(act_slope in [0, 1]), 2 tanh, 3 SiLU, 4 Mish, 5 SnakeBeta */
+  float act_slope;
+  const float *d_alpha_exp;   /* SnakeBeta: exp(alpha) and 1 / (exp(beta) + 1e-9), device (Cout), 16-byte aligned */
+  const float *d_beta_inv;
+  const int32_t *d_lengths;   /* device (B) valid output frames per utterance, or NULL (no row mask; mask1 / mask2 / d_y2 need it; not with transposed) */
+  int32_t mask1, mask2;
+  float scale;
+  const float *d_R;           /* device (B, Cout, Tout) or NULL */
+  int32_t accum;              /* add what Y held before the launch: d_yold */
+  const float *d_yold;        /* device (B, Cout, Tout) or NULL: the valid frames of Y before the launch (NULL: EV_CONV_EPI_SENTINEL) */
+  int32_t div3;
+  float act2_slope;           /* < 0: none */
+  float pre_lrelu_slope;      /* < 0: none */
+} ev_conv_epi;
+#define EV_CONV_EPI_SENTINEL 1234.5f
+/* P: pad rows a side of every utterance (input frames); fewer than the layer's halo is refused.  Y's pad rows hold EV_CONV_EPI_SENTINEL before
+ * the launch.  d_y (B, Cout, Tout): the valid frames; d_y2 (B, Cout, Tout) or NULL: the second output; d_ypad or NULL: the whole padded
+ * frame-major Y, (B * (Tout + 2 * Pout), Cout) with Pout = P (stride 1), P / 2 (stride 2), P * stride (transposed).  Bad arguments fail the
+ * call with a message and launch nothing.  bias NULL is allowed.  Column-split views, GroupNorm statistics and amax emission are not reachable. */
+int ev_op_conv1d_epi(ev_handle *h, const float *d_x /*(B,Cin,T)*/, const float *w /*HOST, as ev_op_conv1d*/, const float *bias /*HOST or NULL*/,
+                     int B, int Cin, int T, int Cout, int K, int dilation, int transposed, int stride, int padding, int P,
+                     const ev_conv_epi *ep, float *d_y, float *d_y2, float *d_ypad, void *stream);
 int ev_op_groupnorm_mish(ev_handle *h, const float *d_x /*(B,C,T)*/, const float *d_gamma, const float *d_beta,
                          const int32_t *d_lengths, int B, int C, int T, int groups, float *d_y, void *stream);
 /* ev_op_groupnorm_mish with the three epilogues of the U-Net's ResnetBlock1D (GNParams in ev_kernels.h): mode 0: mish(gn(x)) * m; mode 1:

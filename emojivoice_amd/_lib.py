@@ -48,6 +48,7 @@ EXPORTS = [
     "ev_load_srmr", "ev_srmr",
     "ev_load_speech_rate", "ev_speech_rate",
     "ev_load_envelope", "ev_envelope",
+    "ev_load_phase_vocoder", "ev_phase_vocoder",
     "ev_op_conv1d_epi",
 ]
 
@@ -202,6 +203,8 @@ def load_library() -> C.CDLL:
     lib.ev_speech_rate.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp, vp, vp]
     lib.ev_load_envelope.argtypes = [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, i32]
     lib.ev_envelope.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
+    lib.ev_load_phase_vocoder.argtypes = [vp, vp, vp, i32]
+    lib.ev_phase_vocoder.argtypes = [vp, vp, vp, i32, i32, C.c_double, vp, i32, vp, vp, vp, vp]
     lib.ev_maximum_path.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ev_log_prior.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ev_mas_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -588,6 +591,36 @@ class Engine:
         self._check(self.lib.ev_envelope(self.h, x.data_ptr(), _ptr(ln), pd.data_ptr(), B, L, float(power_floor), _ptr(env), mcep.data_ptr(),
                                          cls.data_ptr(), _stream_ptr()), "ev_envelope")
         return env, mcep, cls
+
+    def load_phase_vocoder(self, window, twiddle, nfft: int) -> None:
+        """One nfft of ``phase_vocoder`` (ev_load_phase_vocoder), the tables on the host: ``window`` (nfft,) float64 (the periodic Hann window for
+        librosa's defaults), ``twiddle`` (nfft, 2) float64 {cos, sin}(2 pi n / nfft).  The hop is nfft / 4."""
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float64).reshape(-1))
+        tw = np.ascontiguousarray(np.asarray(twiddle, dtype=np.float64).reshape(-1, 2))
+        if w.shape[0] != int(nfft) or tw.shape[0] != int(nfft):
+            raise ValueError(f"load_phase_vocoder: a window and twiddles of {nfft} entries expected, got {w.shape[0]} and {tw.shape[0]}")
+        self._check(self.lib.ev_load_phase_vocoder(self.h, w.ctypes.data, tw.ctypes.data, int(nfft)), "ev_load_phase_vocoder")
+        self.phase_vocoder_nfft = int(nfft)
+
+    def phase_vocoder(self, x, lengths, rate: float, want_counts: bool = False, want_stretch: bool = False):
+        """Every row of ``x`` (B, L) rendered ``rate`` times faster at its own pitch (ev_phase_vocoder, after load_phase_vocoder): (y (B, L_out)
+        float32 with L_out = rint(L / rate), out_len (B,) int32, counts (B, 2) int32 {frames in, frames out} or None, stretch (B, NO, NB, 2)
+        float64 — the stretched spectra {re, im} — or None) on the device.  ``lengths`` (B,): samples per row (None: L)."""
+        if not hasattr(self, "phase_vocoder_nfft"):
+            raise EvLibraryError("phase_vocoder: tables not loaded (load_phase_vocoder)")
+        x, B, L, ln = self._rows(x, lengths, "phase_vocoder")
+        nfft, rate = self.phase_vocoder_nfft, float(rate)
+        if not (math.isfinite(rate) and 0.125 <= rate <= 8.0):
+            raise ValueError(f"phase_vocoder: rate must be finite with 0.125 <= rate <= 8 (got {rate})")
+        L_out = int(np.rint(np.float64(L) / np.float64(rate)))
+        NO = int(np.ceil(np.float64(1 + L // (nfft // 4)) / np.float64(rate)))
+        y = torch.empty((B, L_out), dtype=torch.float32, device=x.device)
+        out_len = torch.empty((B,), dtype=torch.int32, device=x.device)
+        counts = torch.empty((B, 2), dtype=torch.int32, device=x.device) if want_counts else None
+        st = torch.empty((B, NO, nfft // 2 + 1, 2), dtype=torch.float64, device=x.device) if want_stretch else None
+        self._check(self.lib.ev_phase_vocoder(self.h, x.data_ptr(), _ptr(ln), B, L, rate, y.data_ptr(), L_out, out_len.data_ptr(), _ptr(counts),
+                                              _ptr(st), _stream_ptr()), "ev_phase_vocoder")
+        return y, out_len, counts, st
 
     def load_stoi(self, window, twiddle, bands, hop: int, n_fft: int, seg_frames: int) -> None:
         """The tables of ``stoi`` (ev_load_stoi), all on the host: ``window`` (W,) float64 with W = 2 hop, ``twiddle`` (n_fft, 2) float64

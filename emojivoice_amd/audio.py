@@ -2126,3 +2126,127 @@ def modulation_spectrum_distance(mel_a, mel_b, len_a=None, len_b=None, n_coeffs:
     if mel_a.dim() != 3 or mel_b.dim() != 3 or mel_a.shape[:2] != mel_b.shape[:2]:
         raise ValueError(f"modulation_spectrum_distance: two log-mels (B, n_mels, T) of one batch expected, got {tuple(mel_a.shape)} and {tuple(mel_b.shape)}")
     return cepstral_modulation_distance(mel_cepstrum(mel_a, n_coeffs), mel_cepstrum(mel_b, n_coeffs), len_a, len_b, sr, hop_length, min_run, min_cycles)
+
+
+# ---- time stretching and pitch shifting: the phase vocoder (librosa.effects.time_stretch / pitch_shift are the model) ---------------------------
+PHASE_VOCODER_SCRATCH_BYTES = 4 << 30              # ``ev_phase_vocoder``'s limit on the scratch of one call: ``time_stretch`` splits the batch below it
+PITCH_RATIO_MAX_DENOMINATOR = 320                  # p / q ~ 2^(n_steps / 12) with q <= 320 and |n_steps| <= 12: p, q <= 640, ``ev_load_resampler``'s limit
+
+
+def phase_vocoder_window(n_fft: int) -> np.ndarray:
+    """The periodic Hann window of librosa.stft's default (scipy's get_window("hann", n_fft, fftbins=True)), float64."""
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(int(n_fft), dtype=np.float64) / int(n_fft))
+
+
+def phase_vocoder_arguments(rate, n_fft) -> Tuple[float, int]:
+    """The checks of ``time_stretch``: rate finite with 0.125 <= rate <= 8, n_fft a multiple of 16 with 16 <= n_fft <= 2048 -> (rate, n_fft)."""
+    if isinstance(rate, bool) or not isinstance(rate, (int, float, np.floating, np.integer)) or not math.isfinite(float(rate)) \
+            or not 0.125 <= float(rate) <= 8.0:
+        raise ValueError(f"time_stretch: rate must be a finite number with 0.125 <= rate <= 8 (got {rate!r})")
+    if int(n_fft) != n_fft or int(n_fft) < 16 or int(n_fft) > 2048 or int(n_fft) % 16:
+        raise ValueError(f"time_stretch: n_fft must be a multiple of 16 with 16 <= n_fft <= 2048 (got {n_fft!r})")
+    return float(rate), int(n_fft)
+
+
+def phase_vocoder_scratch_bytes(B: int, L: int, rate: float, n_fft: int) -> int:
+    """What ``ev_phase_vocoder`` needs for B rows of L samples without d_stretch: magnitudes, angles and the stretched spectra, float64."""
+    NF, NB = 1 + int(L) // (int(n_fft) // 4), int(n_fft) // 2 + 1
+    NO = int(np.ceil(np.float64(NF) / np.float64(rate)))
+    return 8 * int(B) * NB * (2 * NF + 2 * NO)
+
+
+def _phase_vocoder_engine(device: torch.device, n_fft: int) -> Engine:
+    return _cached_engine(device, ("phase_vocoder", int(n_fft)), lambda eng: eng.load_phase_vocoder(phase_vocoder_window(n_fft), stoi_twiddle(n_fft), n_fft))
+
+
+def _device_time_stretch_rows(x, lengths, rate, n_fft):
+    y, out_len, _, _ = _phase_vocoder_engine(x.device, n_fft).phase_vocoder(x, lengths, rate)
+    return y, out_len
+
+
+@torch.inference_mode()
+def time_stretch(y, rate: float, lengths=None, n_fft: int = 1024, rows: Optional[Callable] = None):
+    """``y`` 1-D or (B, L) on the GPU rendered ``rate`` times faster (``rate`` > 1) or slower (< 1) at its own pitch, by the phase vocoder on the
+    device (``ev_phase_vocoder``; no torch fallback): what ``librosa.effects.time_stretch(y, rate=rate, n_fft=n_fft)`` computes with librosa
+    0.10's defaults (hop n_fft / 4, periodic Hann, centred frames over zero padding), as include/emojivoice.h defines it, in float64, rounded
+    once to float32.  ``lengths`` (B,): samples per row of a padded batch or None.  -> (y_out (B, rint(L / rate)) float32, zeros from a row's own
+    end on; out_lengths (B,) int64 on the host: rint(len / rate), 0 for a row with len < 1 or len > L).  A 1-D input gives B = 1.  The tables and
+    the native handle are cached per (device, n_fft); a batch whose scratch would pass 4 GiB is processed in row groups below it.
+    ``rows``: the per-batch call, (x, lengths, rate, n_fft) -> (y, out_len) — the device call unless given."""
+    rate, n_fft = phase_vocoder_arguments(rate, n_fft)
+    if not torch.is_tensor(y) or y.dim() not in (1, 2):
+        raise ValueError("time_stretch: y must be a tensor, 1-D or (B, L)")
+    if y.shape[-1] < 1:
+        raise ValueError("time_stretch: the signal is empty")
+    if rows is None and not y.is_cuda:
+        raise EvLibraryError("time_stretch runs on a ROCm GPU only (no CPU fallback): move y to the GPU")
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    B, L = x.shape
+    ln = None
+    if lengths is not None:
+        ln = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
+        if ln.numel() != B:
+            raise ValueError(f"time_stretch: {B} lengths expected, got {ln.numel()}")
+    L_out = int(np.rint(np.float64(L) / np.float64(rate)))
+    if L_out < 1:                                                        # (a row of under five samples at rate 8)
+        return torch.zeros((B, 0), dtype=torch.float32, device=x.device), torch.zeros(B, dtype=torch.int64)
+    per_row = phase_vocoder_scratch_bytes(1, L, rate, n_fft)
+    if per_row > PHASE_VOCODER_SCRATCH_BYTES:
+        raise ValueError(f"time_stretch: one row of {L} samples needs {per_row} bytes of scratch, over 4 GiB: cut the recording")
+    group = max(1, min(B, 65535, PHASE_VOCODER_SCRATCH_BYTES // per_row))
+    call = rows or _device_time_stretch_rows
+    ys, ns = [], []
+    for b0 in range(0, B, group):
+        yo, no = call(x[b0:b0 + group], None if ln is None else ln[b0:b0 + group], rate, n_fft)
+        ys.append(yo)
+        ns.append(torch.as_tensor(no).to(torch.int64).cpu())
+    return (ys[0] if len(ys) == 1 else torch.cat(ys, dim=0)), torch.cat(ns)
+
+
+def pitch_ratio(n_steps: float):
+    """The frequency ratio of a shift by ``n_steps`` semitones as a fraction p / q ~ 2^(n_steps / 12) with q <= 320
+    (``Fraction.limit_denominator``), for |n_steps| <= 12: both terms are at most 640, the resampler's limit.  +1: 196 / 185 (0.006 cents off)."""
+    from fractions import Fraction
+
+    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, float, np.floating, np.integer)) or not math.isfinite(float(n_steps)) \
+            or abs(float(n_steps)) > 12:
+        raise ValueError(f"pitch_shift: n_steps must be a finite number with |n_steps| <= 12 (got {n_steps!r})")
+    return Fraction(2.0 ** (float(n_steps) / 12.0)).limit_denominator(PITCH_RATIO_MAX_DENOMINATOR)
+
+
+def pitch_cents(ratio) -> float:
+    """1200 log2(p / q): the shift a ratio realises, in cents."""
+    return 1200.0 * math.log2(ratio.numerator / ratio.denominator)
+
+
+@torch.inference_mode()
+def pitch_shift(y, n_steps: float, sr: int = 22050, lengths=None, n_fft: int = 1024, rows: Optional[Callable] = None,
+                resampler: Optional[Callable] = None):
+    """``y`` 1-D or (B, L) on the GPU, ``n_steps`` semitones higher (> 0) or lower at its own duration, as librosa.effects.pitch_shift does it:
+    ``time_stretch`` at rate q / p, then ``resample`` with up = q, down = p, p / q = ``pitch_ratio(n_steps)``; every row is then cut or
+    zero-padded to its input length (samples from ``lengths[b]`` on are zeros).  ``sr`` does not enter the arithmetic (the ratio is all the
+    resampler needs); it is kept for the model's signature.  -> (y_out (B, L) float32, cents: the shift realised, 1200 log2(p / q)).
+    ``n_steps == 0`` returns a copy.  ``rows``: ``time_stretch``'s hook; ``resampler``: (y, q, p, lengths) -> y at q / p times the rate — the
+    device resampler unless given."""
+    ratio = pitch_ratio(n_steps)
+    phase_vocoder_arguments(1.0, n_fft)
+    if not torch.is_tensor(y) or y.dim() not in (1, 2):
+        raise ValueError("pitch_shift: y must be a tensor, 1-D or (B, L)")
+    if int(sr) != sr or int(sr) < 1:
+        raise ValueError(f"pitch_shift: sr must be a positive integer (got {sr})")
+    x = y.unsqueeze(0) if y.dim() == 1 else y
+    B, L = x.shape
+    ln = torch.full((B,), L, dtype=torch.int64) if lengths is None else torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
+    if ln.numel() != B:
+        raise ValueError(f"pitch_shift: {B} lengths expected, got {ln.numel()}")
+    p, q = ratio.numerator, ratio.denominator
+    if p == q:
+        return x.to(torch.float32).clone(), 0.0
+    st, st_len = time_stretch(x, q / p, ln, n_fft, rows)
+    rs = resampler(st, q, p, st_len) if resampler is not None else resample(st, p, q, lengths=st_len)
+    out = torch.zeros((B, L), dtype=torch.float32, device=rs.device)
+    keep = min(L, rs.shape[-1])
+    out[:, :keep] = rs[:, :keep]
+    valid = torch.where((ln >= 1) & (ln <= L), ln, torch.zeros_like(ln)).to(out.device)
+    out = out * (torch.arange(L, device=out.device)[None, :] < valid[:, None])
+    return out, pitch_cents(ratio)

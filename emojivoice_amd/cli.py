@@ -36,6 +36,7 @@ emojivoice_amd/text.py); everything after that point mirrors the reference: vali
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --rhythm                                    # ... and, per pair, rate and pauses of both sides and their differences
     python -m emojivoice_amd.cli --evaluate_pairs pairs.txt --envelope_mcd                              # ... and, per pair, the MCD of the mel-cepstra of CheapTrick's spectral envelope (the literature's kind of MCD)
     python -m emojivoice_amd.cli --prepare_dataset raw.txt --out_dir clean --target_lufs -23            # levelled by loudness instead of by peak
+    python -m emojivoice_amd.cli --augment_dataset clean/filelist.txt --out_dir aug --rates 0.9,1.1 --semitones -1,1   # slower / faster / lower / higher copies + aug/filelist.txt + FILELIST.augment.json
     python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000          # clean/filelist.txt.vocoder.json: STOI / ESTOI, mel L1 and loudness shift of copy synthesis
     python -m emojivoice_amd.cli --vocoder_report clean/filelist.txt --vocoder_path g_02500000 --spectral_distance   # + multi-resolution STFT distance and log-spectral distance
 
@@ -104,6 +105,14 @@ def validate_args(args):
             "--track_formants is an option of --formants and of --harmonics under --voice_report and --evaluate_pairs"
     if args.sample_rate is not None:
         assert args.sample_rate > 0, "--sample_rate must be positive"
+    if getattr(args, "augment_dataset", None):
+        assert args.out_dir, "--augment_dataset needs --out_dir"
+        assert args.batch_size > 0, "Batch size must be greater than 0"
+        args.rates, args.semitones = augment_values(args.rates, "--rates"), augment_values(args.semitones, "--semitones")
+        assert args.rates or args.semitones, "--augment_dataset needs at least one of --rates and --semitones"
+        assert all(0.125 <= r <= 8.0 and r != 1.0 for r in args.rates), "--rates must lie in [0.125, 8] and differ from 1"
+        assert all(abs(v) <= 12 and v != 0 for v in args.semitones), "--semitones must lie in [-12, 12] and differ from 0"
+        return args
     if args.prepare_dataset:
         assert args.out_dir, "--prepare_dataset needs --out_dir"
         assert 0 <= args.peak <= 1, "--peak must lie in [0, 1] (0: no levelling)"
@@ -418,6 +427,87 @@ def prepare_dataset(args, device):
         v = rep["speakers"][k]
         print(f"[i] speaker {k}: {v['files']} files, {v['minutes']:.2f} min" + ("  (below two minutes)" if v["below_two_minutes"] else ""))
     print(f"[+] File list saved: {(out_dir / 'filelist.txt').resolve()}\n[+] Durations saved: {Path(out).resolve()}")
+    return rep
+
+
+def augment_values(text, flag: str):
+    """The finite numbers of a comma-separated option (a list passes through; None or "": none)."""
+    if text is None or isinstance(text, (list, tuple)):
+        return [float(v) for v in (text or [])]
+    try:
+        vals = [float(v) for v in str(text).split(",") if v.strip()]
+    except ValueError:
+        raise AssertionError(f"{flag} takes comma-separated numbers (got {text!r})") from None
+    assert all(math.isfinite(v) for v in vals), f"{flag} takes finite numbers (got {text!r})"
+    return vals
+
+
+def augment_report(files, sr: int, rates, semitones, cents):
+    """The content of FILELIST.augment.json: per speaker the seconds before (the listed files) and after (with every variant), whether the speaker
+    is still below two minutes, and per shift the cents realised.  ``files``: dicts with path, speaker, seconds and variants [{out, kind, value,
+    seconds}]."""
+    speakers = {}
+    for f in files:
+        s = speakers.setdefault(f["speaker"], {"files": 0, "variants": 0, "before": [], "after": []})
+        s["files"] += 1
+        s["variants"] += len(f["variants"])
+        s["before"].append(f["seconds"])
+        s["after"].extend([f["seconds"]] + [v["seconds"] for v in f["variants"]])
+    per_spk = {}
+    for k, v in speakers.items():
+        before, after = math.fsum(v["before"]), math.fsum(v["after"])
+        per_spk[k] = {"files": v["files"], "variants": v["variants"], "seconds_before": before, "seconds_after": after,
+                      "below_two_minutes_before": before / 60.0 < TWO_MINUTES, "below_two_minutes": after / 60.0 < TWO_MINUTES}
+    return {"sample_rate": sr, "rates": list(rates), "semitones": list(semitones), "realised_cents": {f"{v:+.2f}": c for v, c in zip(semitones, cents)},
+            "files": files, "speakers": per_spk, "below_two_minutes": sorted(k for k, v in per_spk.items() if v["below_two_minutes"])}
+
+
+def augment_dataset(args, device, rows=None, resampler=None):
+    """--augment_dataset FILELIST --out_dir DIR [--rates 0.9,1.1] [--semitones -1,1]: every recording of the filelist --prepare_dataset writes,
+    rendered once per rate (audio.time_stretch: slower below 1, faster above) and once per shift (audio.pitch_shift) — no cross product —
+    --batch_size files at a time on the device (padded to the longest, each row with its own length).  DIR/<base>_r0.90.wav and
+    DIR/<base>_p+1.00.wav are 16-bit mono wavs; DIR/filelist.txt holds the original lines followed by the variants with the same speaker and
+    text; FILELIST.augment.json holds ``augment_report``.  ``rows`` / ``resampler``: the hooks of audio.time_stretch and audio.pitch_shift."""
+    from . import audio
+
+    sr = int(args.sample_rate or PROSODY_SR)
+    entries = parse_filelist(args.augment_dataset)
+    if not entries:
+        sys.exit(f"[-] {args.augment_dataset}: no files listed")
+    stems = [Path(wav).stem for wav, _, _ in entries]
+    if len(set(stems)) != len(stems):
+        sys.exit(f"[-] {args.augment_dataset}: two recordings share a base name; their variants would overwrite each other under {args.out_dir}")
+    out_dir = Path(args.out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    cents = [audio.pitch_cents(audio.pitch_ratio(v)) for v in args.semitones]
+    originals = ["|".join([wav] + rest) for wav, _, rest in entries]
+    files, lines, at = [], [], 0
+    for chunk, batch, lens in filelist_batches(args.augment_dataset, args.batch_size, sr, device):
+        recs = [{"path": wav, "speaker": spk if spk is not None else "0", "seconds": n / sr, "variants": []} for (wav, spk, _), n in zip(chunk, lens)]
+        renders = [("rate", r, f"_r{r:.2f}") + audio.time_stretch(batch, r, lens, rows=rows) for r in args.rates]
+        for v in args.semitones:
+            shifted, _ = audio.pitch_shift(batch, v, sr, lens, rows=rows, resampler=resampler)
+            renders.append(("semitones", v, f"_p{v:+.2f}", shifted, lens))
+        for kind, value, tag, y, out_lens in renders:
+            y = y.cpu().numpy()
+            for r, ((wav, _, rest), rec) in enumerate(zip(chunk, recs)):
+                n = int(out_lens[r])
+                dst = (out_dir / (stems[at + r] + tag + ".wav")).resolve()
+                write_wav_pcm16(dst, y[r, :n], sr)
+                rec["variants"].append({"out": str(dst), "kind": kind, "value": value, "seconds": n / sr})
+                lines.append("|".join([str(dst)] + rest))
+        files.extend(recs)
+        at += len(chunk)
+    (out_dir / "filelist.txt").write_text("\n".join(originals + lines) + "\n", encoding="utf-8")
+    rep = augment_report(files, sr, args.rates, args.semitones, cents)
+    out = f"{args.augment_dataset}.augment.json"
+    with open(out, "w") as f:
+        json.dump(rep, f, indent=1)
+    for k in sorted(rep["speakers"]):
+        v = rep["speakers"][k]
+        print(f"[i] speaker {k}: {v['files']} files + {v['variants']} variants, {v['seconds_before'] / 60.0:.2f} -> {v['seconds_after'] / 60.0:.2f} min"
+              + ("  (still below two minutes)" if v["below_two_minutes"] else ""))
+    print(f"[+] File list saved: {(out_dir / 'filelist.txt').resolve()}\n[+] Report saved: {Path(out).resolve()}")
     return rep
 
 
@@ -1254,7 +1344,12 @@ def cli(argv=None):
                    "omitted: 22050 Hz, untouched.  With --prepare_dataset: the rate of the prepared recordings (default 22050)")
     p.add_argument("--prepare_dataset", type=str, default=None, help="dataset preparation instead of synthesis: a filelist 'path|spk|text' or 'path|text' of raw "
                    "recordings -> trimmed, levelled 16-bit mono wavs under --out_dir, DIR/filelist.txt and FILELIST.durations.json")
-    p.add_argument("--out_dir", type=str, default=None, help="folder of --prepare_dataset's wavs and filelist.txt")
+    p.add_argument("--out_dir", type=str, default=None, help="folder of --prepare_dataset's / --augment_dataset's wavs and filelist.txt")
+    p.add_argument("--augment_dataset", type=str, default=None, help="dataset augmentation instead of synthesis: the filelist 'path|spk|text' --prepare_dataset "
+                   "writes -> every file once per --rates value (time-stretched) and once per --semitones value (pitch-shifted) under --out_dir, "
+                   "--out_dir/filelist.txt (originals, then variants) and FILELIST.augment.json (phase vocoder on the device, --batch_size files per batch)")
+    p.add_argument("--rates", type=str, default=None, help="--augment_dataset: comma-separated speed factors, e.g. 0.9,1.1 (each in [0.125, 8], not 1)")
+    p.add_argument("--semitones", type=str, default=None, help="--augment_dataset: comma-separated pitch shifts in semitones, e.g. -1,1 (each in [-12, 12], not 0)")
     p.add_argument("--top_db", type=float, default=60.0, help="--prepare_dataset: frames this many dB below the loudest one are silence (librosa.effects.trim)")
     p.add_argument("--peak", type=float, default=0.95, help="--prepare_dataset: peak level of the prepared recordings (hifigan/meldataset.py:152); 0: level untouched")
     p.add_argument("--prosody_report", type=str, default=None, help="pitch analysis instead of synthesis: a filelist 'path|spk|text' (the one --prepare_dataset "
@@ -1350,6 +1445,10 @@ def cli(argv=None):
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
         return prosody_report(args, torch.device("cuda", 0))
+    if args.augment_dataset:
+        if not torch.cuda.is_available():
+            sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")
+        return augment_dataset(args, torch.device("cuda", 0))
     if args.prepare_dataset:
         if not torch.cuda.is_available():
             sys.exit("[-] No ROCm GPU visible: this CLI drives the MI355X path only (no CPU fallback)")

@@ -1,5 +1,5 @@
 // Host entry points of the analysis side: resampling, dataset statistics, silence trimming, YIN / pYIN pitch tracking, DTW, BS.1770 loudness,
-// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals, auditory descriptors, formant tracks, SRMR, speech rate and the spectral envelope (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
+// STOI / ESTOI, the STFT distance, voice quality, formants, perturbation, harmonic differences, contour functionals, auditory descriptors, formant tracks, SRMR, speech rate, the spectral envelope and the phase vocoder (kernels: ev_analysis_kernels.h).  Part of ev_engine.hip's translation unit: that file includes this one
 // after ev_handle, fail / HIPCHK / enter, dev_upload, drop_owned, scratch_acquire and launch<>.  None of these calls runs on the engine's conv
 // path; ev_load_mel_basis, ev_mel_spectrogram, ev_denoise and ev_stft_magnitude do, and stay in ev_engine.hip.
 #pragma once
@@ -1151,6 +1151,76 @@ int ev_envelope(ev_handle* h, const float* d_x, const int32_t* d_len, const floa
     launch<envelope_power_kernel>(h->device, grid, dim3(256), w.lds1, h->stream, pp);
     EnvCepParams pc{d_len, d_period, P, d_env, d_mcep, d_class, w.t, L, NF, power_floor};
     launch<envelope_cepstrum_kernel>(h->device, grid, dim3(256), w.lds2, h->stream, pc);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// Phase vocoder: time stretching by stft -> phase propagation -> istft (pv_analysis_kernel, pv_propagate_kernel and pv_synthesis_kernel,
+// ev_analysis_kernels.h; the definition: include/emojivoice.h).  W = nfft, H = nfft / 4.  A load owns one device block: the windowed DFT basis
+// (stft_dist_basis_kernel), the inverse basis (pv_inv_basis_kernel), w / nfft and w^2 (formed here, one rounding each).  Arena of a call: mag and
+// ang, 2 x B x NF x NB doubles, and without d_stretch Y, B x NO x NB pairs.
+int ev_load_phase_vocoder(ev_handle* h, const double* window, const double* twiddle, int nfft) {
+    if (enter(h)) return 1;
+    if (!window || !twiddle) return fail(h, "ev_load_phase_vocoder: window and twiddle must be non-null (HOST)");
+    if (nfft < 16 || nfft > 2048 || nfft % 16) return fail(h, "ev_load_phase_vocoder: nfft=%d must be a multiple of 16 with 16 <= nfft <= 2048", nfft);
+    if (check_finite(h, __func__, "window", window, nfft) || check_finite(h, __func__, "twiddle", twiddle, 2 * nfft)) return 1;
+    PvW w;
+    PvTables& t = w.t;
+    t.nfft = nfft; t.H = nfft / 4; t.NB = nfft / 2 + 1; t.NBp = (t.NB + 3) / 4 * 4; t.skew = dft_skew(t.H);
+    w.lds = (size_t)dft_span_words(15 * t.H + nfft, t.H, t.skew) * sizeof(float);
+    std::vector<double> tab((size_t)2 * nfft);
+    for (int j = 0; j < nfft; ++j) { tab[j] = window[j] / (double)nfft; tab[(size_t)nfft + j] = window[j] * window[j]; }
+    const size_t n_basis = (size_t)nfft * t.NB, n_inv = (size_t)t.NBp * nfft;
+    const size_t o_inv = 2 * n_basis, o_wn = o_inv + 2 * n_inv;       // in doubles from the block's start
+    char* blk = nullptr;                                                // the new block first: a failed load leaves the tables in use as they are
+    auto rest = [&](char* b, const double* d_tw) {
+        double* d = (double*)b;
+        hipError_t e = hipMemcpy(d + o_wn, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
+        PvInvParams pi{d_tw, (double2*)(d + o_inv), nfft, t.H, t.NB, t.NBp};
+        if (e == hipSuccess) launch<pv_inv_basis_kernel>(h->device, dim3((unsigned)((n_inv + 255) / 256)), dim3(256), 0, (hipStream_t)nullptr, pi);
+        return e;
+    };
+    if (build_dft_basis(h, __func__, "tables", window, twiddle, nfft, nfft, (o_wn + tab.size()) * sizeof(double), &blk, rest)) return 1;
+    const double* d = (const double*)blk;
+    t.basis = (const double2*)blk; t.inv = (const double2*)(d + o_inv); t.wn = d + o_wn; t.wsq = d + o_wn + nfft;
+    PvW& cur = h->pv;
+    if (cur.loaded && drop_owned(h, {(void*)cur.t.basis})) { hipFree(blk); return 1; }
+    h->owned.push_back(blk);
+    ++h->n_allocs;                          // (one block: 8.4 MB of basis and 8.5 MB of inverse basis at nfft = 1024)
+    w.loaded = true;
+    cur = w;
+    return 0;
+}
+
+int ev_phase_vocoder(ev_handle* h, const float* d_x, const int32_t* d_len, int B, int L, double rate, float* d_y, int L_out, int32_t* d_out_len,
+                     int32_t* d_counts, double* d_stretch, void* stream) {
+    if (enter(h)) return 1;
+    const PvW& w = h->pv;
+    if (!w.loaded) return fail(h, "ev_phase_vocoder: tables not loaded (ev_load_phase_vocoder)");
+    if (check_batch(h, __func__, B)) return 1;
+    if (L < 1) return fail(h, "ev_phase_vocoder: L=%d must be at least 1", L);
+    if (!std::isfinite(rate) || rate < 0.125 || rate > 8.0) return fail(h, "ev_phase_vocoder: rate=%g must be finite with 0.125 <= rate <= 8", rate);
+    const long long want = (long long)std::rint((double)L / rate);
+    if (L_out != want) return fail(h, "ev_phase_vocoder: L_out=%d must be rint(L / rate) = %lld", L_out, want);
+    if (!d_x) return fail(h, "ev_phase_vocoder: d_x must be non-null");
+    if (!d_y || !d_out_len) return fail(h, "ev_phase_vocoder: d_y and d_out_len must be non-null");
+    const PvTables& t = w.t;
+    const int NF = 1 + L / t.H, NO = pv_steps(NF, rate);
+    const size_t n_ma = (size_t)B * NF * t.NB, n_y = d_stretch ? 0 : (size_t)B * NO * t.NB * 2;
+    const size_t bytes = (2 * n_ma + n_y) * sizeof(double);
+    if (bytes > ((size_t)4 << 30))
+        return fail(h, "ev_phase_vocoder: B=%d rows of L=%d at rate=%g need %zu bytes of scratch, over 4 GiB: split the batch", B, L, rate, bytes);
+    h->stream = (hipStream_t)stream;
+    if (scratch_acquire(h, h->pv_ws, bytes)) return 1;
+    double* mag = (double*)h->pv_ws.p;
+    double* ang = mag + n_ma;
+    double2* Y = d_stretch ? (double2*)d_stretch : (double2*)(ang + n_ma);
+    PvAnalysisParams pa{d_x, d_len, mag, ang, t, L, NF};
+    launch<pv_analysis_kernel>(h->device, dim3((unsigned)((NF + 15) / 16), (unsigned)B), dim3(256), w.lds, h->stream, pa);
+    PvPropParams pp{mag, ang, d_len, Y, d_out_len, d_counts, t, L, NF, NO, rate};
+    launch<pv_propagate_kernel>(h->device, dim3((unsigned)((t.NB + 63) / 64), (unsigned)B), dim3(64), 0, h->stream, pp);
+    PvSynthParams ps{Y, d_len, d_y, t, L, NO, L_out, rate};
+    launch<pv_synthesis_kernel>(h->device, dim3((unsigned)((NO + 3 + 12) / 13), (unsigned)B), dim3(256), 0, h->stream, ps);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -4036,3 +4036,257 @@ __global__ __launch_bounds__(256) void envelope_cepstrum_kernel(const EnvCepPara
         }
     });
 }
+
+// ---------------------------------------------------------------------------
+// Phase vocoder (ev_phase_vocoder): time stretching of every row by librosa's stft -> phase_vocoder -> istft chain (the definition, with every
+// order: include/emojivoice.h; tests/phase_vocoder_ref.py restates it).  W = nfft, H = nfft / 4, NB = nfft / 2 + 1.  All float64, contraction OFF
+// (STOI_EXACT), no atomics.  Launches of a call:
+//   1. pv_analysis_kernel:  one workgroup of 4 waves per (row, 16 frames from the row's frame 0): the DFT GEMM of stft_dist_frames_kernel for one
+//      signal on the windowed basis (stft_dist_basis_kernel builds it) -> mag, ang (B, NF, NB), bins fast.  Frames at and behind nf are not
+//      stored: the definition's two zero frames behind nf - 1 are what pv_propagate_kernel takes for every frame >= nf.
+//   2. pv_propagate_kernel: one thread per (row, bin) walks t = 0 .. n_out - 1 -> Y (B, NO, NB) pairs {re, im}, zeros from n_out on.
+//   3. pv_synthesis_kernel: the inverse DFT as a GEMM, frames x bins times inv[k][.] = {c_k cos, -c_k sin}(2 pi j k / nfft) (pv_inv_basis_kernel
+//      builds it: exact multiples of the twiddles, zero rows from NB on, zero sine entries at DC and Nyquist), the window, the overlap-add in
+//      ascending frame order and the division by the window's sum of squares formed in the same order -> d_y.
+// Everything a row's outputs depend on hangs on the row's own samples below len.
+struct PvTables { const double2* basis; const double2* inv; const double* wn; const double* wsq; int nfft, H, NB, NBp, skew; };
+#define PV_TWO_PI 6.283185307179586
+
+// (n, nf) of row b: a row with len < 1 or len > L is an empty row
+__device__ __forceinline__ int pv_frames(const int32_t* len, int b, int L, int H, int* n_out) {
+    int n = len ? len[b] : L;
+    if (n < 1 || n > L) n = 0;
+    *n_out = n;
+    return n > 0 ? 1 + n / H : 0;
+}
+// ceil(nf / rate): the output frames of nf input frames (host: NO from NF by the same expression, so n_out <= NO)
+__host__ __device__ __forceinline__ int pv_steps(int nf, double rate) { return nf > 0 ? (int)ceil((double)nf / rate) : 0; }
+__device__ __forceinline__ int pv_out_len(int n, double rate) { return n > 0 ? (int)rint((double)n / rate) : 0; }
+
+// inv (NBp, nfft) in the column order of pv_synthesis_kernel: column 16 tile + c holds sample j = (c >> 2) H + 4 tile + (c & 3)
+struct PvInvParams { const double* tw; double2* inv; int nfft, H, NB, NBp; };
+
+__global__ __launch_bounds__(256) void pv_inv_basis_kernel(const PvInvParams p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;                       // (NBp nfft <= 1028 x 2048)
+    if (i >= p.NBp * p.nfft) return;
+    const int k = i / p.nfft, col = i - k * p.nfft, c = col & 15;
+    const int j = (c >> 2) * p.H + 4 * (col >> 4) + (c & 3);
+    double2 v = make_double2(0.0, 0.0);
+    if (k < p.NB) {
+        const int ph = (j * k) % p.nfft;                                // (< 2048 x 1024: exact)
+        const bool edge = k == 0 || k == p.NB - 1;                      // irfft: the imaginary parts of DC and Nyquist are ignored
+        v = edge ? make_double2(p.tw[2 * ph], 0.0) : make_double2(2.0 * p.tw[2 * ph], -2.0 * p.tw[2 * ph + 1]);
+    }
+    p.inv[i] = v;
+}
+
+// The K loop of one bin tile for ONE signal: stft_dist_frames_kernel's loop (four steps a round, the basis of the next round requested before
+// this round's products) with the cos and sin planes of a single staged signal.
+__device__ __forceinline__ void dft_tile_planes(const float* sx, DftSkewWalk& walk, const double2* bp, int NB, int nsteps, int q, stftd_acc& xc, stftd_acc& xs) {
+    walk.start(q);
+    double2 cur[4], nxt[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) cur[u] = bp[(size_t)(u < nsteps ? u : nsteps - 1) * 4 * NB];
+    for (int s0 = 0; s0 < nsteps; s0 += 4) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) nxt[u] = bp[(size_t)(s0 + 4 + u < nsteps ? s0 + 4 + u : nsteps - 1) * 4 * NB];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (s0 + u < nsteps) {                                      // (uniform)
+                const double ax = (double)sx[walk.word()];
+                xc = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].x, xc, 0, 0, 0);
+                xs = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, cur[u].y, xs, 0, 0, 0);
+                walk.step();
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+    }
+}
+
+// One workgroup per (row b, tile of 16 frames f0 .. f0 + 15).  The tile's raw span, samples f0 H - nfft / 2 + t for 0 <= t < 15 H + nfft, is staged
+// once as fp32 with the skew, zeros outside [0, n): 39 KB at nfft = 2048.  Epilogue per (frame < nf, bin < NB): re = sum cos, im = -sum sin,
+// mag = sqrt(fma(im, im, re re)), ang = atan2(im, re).
+struct PvAnalysisParams { const float* x; const int32_t* len; double* mag; double* ang; PvTables t; int L, NF; };
+
+__global__ __launch_bounds__(256) void pv_analysis_kernel(const PvAnalysisParams p) {
+    STOI_EXACT
+    extern __shared__ __attribute__((aligned(16))) float pv_smem[];
+    const int b = blockIdx.y, f0 = blockIdx.x * 16, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int W = p.t.nfft, H = p.t.H, NB = p.t.NB, skew = p.t.skew;
+    int n;
+    const int nf = pv_frames(p.len, b, p.L, H, &n);
+    if (f0 >= nf) return;                                               // (uniform)
+    const int span = 15 * H + W;
+    {
+        const float* xr = p.x + (size_t)b * p.L;
+        const long long i0 = (long long)f0 * H - W / 2;
+        for (int t = tid; t < span; t += 256) {
+            const long long i = i0 + t;
+            pv_smem[dft_word(t, H, skew)] = i >= 0 && i < n ? xr[i] : 0.f;
+        }
+    }
+    __syncthreads();
+    const int r = lane & 15, q = lane >> 4;
+    const int ntile = (NB + 15) >> 4, nsteps = W >> 2;
+    DftSkewWalk walk(r, H, skew);
+    for (int bt = wv; bt < ntile; bt += 4) {
+        const int col = bt * 16 + r;
+        const double2* bp = p.t.basis + (size_t)q * NB + (col < NB ? col : NB - 1);
+        stftd_acc xc = {0.0, 0.0, 0.0, 0.0}, xs = xc;
+        dft_tile_planes(pv_smem, walk, bp, NB, nsteps, q, xc, xs);
+        if (col < NB) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int fr = f0 + q + 4 * i;
+                if (fr < nf) {
+                    const double re = xc[i], im = -xs[i];
+                    const size_t o = ((size_t)b * p.NF + fr) * NB + col;
+                    p.mag[o] = sqrt(fma(im, im, re * re));
+                    p.ang[o] = atan2(im, re);
+                }
+            }
+        }
+    }
+}
+
+// One thread per (row b, bin k), 64 bins a workgroup: the loads of a step do not depend on the phase, so those of step t + 1 are issued before
+// step t's sine and cosine; the loads and the stores are coalesced over the bins.  Thread k = 0 also writes the row's out_len and counts.
+struct PvPropParams { const double* mag; const double* ang; const int32_t* len; double2* Y; int32_t* out_len; int32_t* counts; PvTables t; int L, NF, NO; double rate; };
+
+__global__ __launch_bounds__(64) void pv_propagate_kernel(const PvPropParams p) {
+    STOI_EXACT
+    const int b = blockIdx.y, k = blockIdx.x * 64 + threadIdx.x;
+    const int NB = p.t.NB;
+    int n;
+    const int nf = pv_frames(p.len, b, p.L, p.t.H, &n);
+    const int n_out = pv_steps(nf, p.rate);
+    if (k == 0) {
+        p.out_len[b] = pv_out_len(n, p.rate);
+        if (p.counts) { p.counts[2 * b] = nf; p.counts[2 * b + 1] = n_out; }
+    }
+    if (k >= NB) return;
+    const double* mg = p.mag + (size_t)b * p.NF * NB + k;
+    const double* ag = p.ang + (size_t)b * p.NF * NB + k;
+    double2* y = p.Y + (size_t)b * p.NO * NB + k;
+    const double omega = (PV_TWO_PI * (double)(p.t.H * k)) / (double)p.t.nfft;
+    // frames >= nf are the definition's zero frames (nothing is stored for them)
+    int i = 0;
+    double al = 0.0;
+    double m0 = 0.0, m1 = 0.0, a0 = 0.0, a1 = 0.0;
+    if (n_out > 0) {
+        m0 = mg[0]; a0 = ag[0];
+        if (1 < nf) { m1 = mg[(size_t)NB]; a1 = ag[(size_t)NB]; }
+    }
+    double phi = a0;
+    for (int t = 0; t < n_out; ++t) {
+        int in = i; double aln = 0.0, n0 = 0.0, n1 = 0.0, b0 = 0.0, b1 = 0.0;
+        if (t + 1 < n_out) {
+            const double s = (double)(t + 1) * p.rate;
+            const double fl = floor(s);
+            in = (int)fl; aln = s - fl;
+            if (in < nf) { n0 = mg[(size_t)in * NB]; b0 = ag[(size_t)in * NB]; }
+            if (in + 1 < nf) { n1 = mg[(size_t)(in + 1) * NB]; b1 = ag[(size_t)(in + 1) * NB]; }
+        }
+        const double m = (1.0 - al) * m0 + al * m1;
+        y[(size_t)t * NB] = make_double2(m * cos(phi), m * sin(phi));
+        double d = a1 - a0 - omega;
+        d = d - PV_TWO_PI * rint(d / PV_TWO_PI);
+        phi = phi + (omega + d);
+        i = in; al = aln; m0 = n0; m1 = n1; a0 = b0; a1 = b1;
+    }
+    for (int t = n_out; t < p.NO; ++t) y[(size_t)t * NB] = make_double2(0.0, 0.0);
+}
+
+// One workgroup of 4 waves per (row b, group g): the 16 output frames t0 .. t0 + 15 with t0 = 13 g - 3, and the 13 hop segments s = 13 g ..
+// 13 g + 12 (padded samples s H .. s H + H - 1) that these frames cover completely: segment s takes frame s - q at its quarter q = 3, 2, 1, 0,
+// i.e. in ascending frame order.  Wave w owns the column tiles w, w + 4, ... of nfft / 16; tile c holds, for the four offsets m = 4 c .. 4 c + 3
+// inside a hop, the four quarters j = q H + m, so every term of 13 x 4 output samples lies in the wave's own accumulators.  They cross through a
+// 16 x 16 exchange in LDS (8.5 KB for the four waves, whatever nfft is), after the window: ex[frame][column] = wn[j] (acc_cos + acc_sin).  Lane
+// (sl, mm) < 52 then adds the frames that exist (0 <= t < n_out) and the squares of the window in the same order, divides where the sum of
+// squares is above FLT_MIN, rounds once to fp32 and stores; outside [0, min(out_len, H (n_out - 1) + nfft / 2)) it stores zeros, so that every
+// sample of d_y's row is written exactly once per call.  A lane of an A fragment reads Y[t0 + (l & 15)][k0 + (l >> 4)] from global memory (frames
+// outside [0, n_out) and bins >= NB: the address clamped, the value zero), a B fragment inv[k0 + (l >> 4)][16 tile + (l & 15)].
+struct PvSynthParams { const double2* Y; const int32_t* len; float* y; PvTables t; int L, NO, L_out; double rate; };
+
+__global__ __launch_bounds__(256) void pv_synthesis_kernel(const PvSynthParams p) {
+    STOI_EXACT
+    __shared__ double ex[4][16][17];
+    const int b = blockIdx.y, g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nfft = p.t.nfft, H = p.t.H, NB = p.t.NB;
+    int n;
+    const int nf = pv_frames(p.len, b, p.L, H, &n);
+    const int n_out = pv_steps(nf, p.rate);
+    long long lim = 0;
+    if (n_out > 0) {
+        lim = (long long)H * (n_out - 1) + nfft / 2;
+        const long long ol = pv_out_len(n, p.rate);
+        if (ol < lim) lim = ol;
+    }
+    if (lim > p.L_out) lim = p.L_out;
+    float* yr = p.y + (size_t)b * p.L_out;
+    const long long i_first = (long long)13 * g * H - nfft / 2;         // the block's samples: i_first <= i < i_first + 13 H
+    if (i_first >= lim) {                                               // (uniform) zeros behind the row's own output
+        for (int u = tid; u < 13 * H; u += 256) {
+            const long long i = i_first + u;
+            if (i >= 0 && i < p.L_out) yr[i] = 0.f;
+        }
+        return;
+    }
+    const int r = lane & 15, q = lane >> 4;
+    const int t0 = 13 * g - 3, ta = t0 + r;
+    const bool live = ta >= 0 && ta < n_out;
+    const double2* arow = p.Y + ((size_t)b * p.NO + (live ? ta : 0)) * NB;
+    const int ntile = nfft >> 4, nsteps = p.t.NBp >> 2;
+    const int sl = lane >> 2, mm = lane & 3;
+    for (int c0 = 0; c0 < ntile; c0 += 4) {                             // (uniform: every wave meets both barriers)
+        const int ct = c0 + wv;
+        if (ct < ntile) {
+            const double2* bp = p.t.inv + (size_t)q * nfft + ct * 16 + r;
+            stftd_acc ac = {0.0, 0.0, 0.0, 0.0}, as = ac;
+            double2 ca[4], cb[4], na[4], nb[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int s = u < nsteps ? u : nsteps - 1, k = 4 * s + q;
+                ca[u] = arow[k < NB ? k : NB - 1];
+                cb[u] = bp[(size_t)s * 4 * nfft];
+            }
+            for (int s0 = 0; s0 < nsteps; s0 += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int s = s0 + 4 + u < nsteps ? s0 + 4 + u : nsteps - 1, k = 4 * s + q;
+                    na[u] = arow[k < NB ? k : NB - 1];
+                    nb[u] = bp[(size_t)s * 4 * nfft];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (s0 + u < nsteps) {                              // (uniform)
+                        const bool ok = live && 4 * (s0 + u) + q < NB;
+                        const double are = ok ? ca[u].x : 0.0, aim = ok ? ca[u].y : 0.0;
+                        ac = __builtin_amdgcn_mfma_f64_16x16x4f64(are, cb[u].x, ac, 0, 0, 0);
+                        as = __builtin_amdgcn_mfma_f64_16x16x4f64(aim, cb[u].y, as, 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { ca[u] = na[u]; cb[u] = nb[u]; }
+            }
+            const double wj = p.t.wn[(r >> 2) * H + 4 * ct + (r & 3)];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ex[wv][q + 4 * i][r] = wj * (ac[i] + as[i]);
+        }
+        __syncthreads();
+        if (ct < ntile && lane < 52) {
+            const int m = 4 * ct + mm, s = 13 * g + sl;
+            double num = 0.0, wss = 0.0;
+#pragma unroll
+            for (int qt = 3; qt >= 0; --qt) {
+                const int t = s - qt;
+                if (t >= 0 && t < n_out) { num = num + ex[wv][sl + 3 - qt][4 * qt + mm]; wss = wss + p.t.wsq[qt * H + m]; }
+            }
+            const double v = wss > 1.1754943508222875e-38 ? num / wss : num;
+            const long long i = (long long)s * H + m - nfft / 2;
+            if (i >= 0 && i < p.L_out) yr[i] = i < lim ? (float)v : 0.f;
+        }
+        __syncthreads();
+    }
+}

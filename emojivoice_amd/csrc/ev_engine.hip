@@ -141,6 +141,9 @@ struct RateW { bool loaded = false; double* win = nullptr; int W = 0, H = 0; dou
 // Tables of ev_envelope, one device block: the plain DFT basis (nfft, NB), the cepstral basis (NBp, NB) and the warp table (NBp, n_mcep); lds1, lds2:
 // the dynamic LDS of the two launches in bytes (ev_analysis_kernels.h)
 struct EnvW { bool loaded = false; size_t lds1 = 0, lds2 = 0; EnvTables t{}; };
+// Tables of ev_phase_vocoder, one device block: the windowed DFT basis (nfft, NB), the inverse basis (NBp, nfft), w / nfft and w^2 (nfft each); lds:
+// the dynamic LDS of the analysis launch in bytes (ev_analysis_kernels.h)
+struct PvW { bool loaded = false; size_t lds = 0; PvTables t{}; };
 // Geometry of ev_formants: the analysis window (W) float64 on the device, one block; the rest travels in the kernel's arguments (z0: the root
 // finder's starting points {re, im}, R: samples per lane of formants_kernel)
 struct FormantW { bool loaded = false; double* win = nullptr; int W = 0, H = 0, order = 0, nform = 0, R = 0; double pre = 0, sr = 0, f_lo = 0; double z0[64] = {0}; };
@@ -167,6 +170,7 @@ struct ev_handle {
     SrmrW srmr;
     RateW rate;
     EnvW env;
+    PvW pv;
     // small per-stage scratch arenas (denoiser, text encoder): grown on demand, ordered against their last user's stream
     struct Scratch { char* p = nullptr; size_t bytes = 0; hipStream_t last = nullptr; bool last_valid = false; };
     Scratch dn_ws, enc_ws, mas_ws;   // (mas_ws: the alignment search's frame -> token index and, for large Tx * Ty, its decision bits)
@@ -179,6 +183,7 @@ struct ev_handle {
     Scratch srmr_ws;                 // ev_srmr: per (row, chunk) the channel states, the band states and the window-quarter sums
     Scratch rate_ws;                 // ev_speech_rate: the power contour (B x NF doubles) without d_power
     Scratch env_ws;                  // ev_envelope: the power spectra between its two launches (B x NF x NB doubles)
+    Scratch pv_ws;                   // ev_phase_vocoder: magnitudes and angles (2 x B x NF x NB doubles) and, without d_stretch, Y (B x NO x NB pairs)
     float* zeros = nullptr;     // 4096 zero floats (stand-in bias for the fused kernels' unconditional loads)
     int max_steps = 64;         // Euler steps the time-grid buffers of the workspace are planned for (grows on demand)
     int* bad_ids_host = nullptr; int* bad_ids_dev = nullptr;   // mapped host word: count of out-of-range token ids seen by ev_text_encoder
@@ -2054,6 +2059,7 @@ void ev_destroy(ev_handle* h) {
     if (h->srmr_ws.p) hipFree(h->srmr_ws.p);
     if (h->rate_ws.p) hipFree(h->rate_ws.p);
     if (h->env_ws.p) hipFree(h->env_ws.p);
+    if (h->pv_ws.p) hipFree(h->pv_ws.p);
     if (h->dn_ws.p) hipFree(h->dn_ws.p);
     if (h->bad_ids_host) hipHostFree(h->bad_ids_host);
     for (int i = 0; i < 2; ++i) { if (h->temb_ev[i]) hipEventDestroy(h->temb_ev[i]); if (h->temb_host[i]) hipHostFree(h->temb_host[i]); }

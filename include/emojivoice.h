@@ -43,6 +43,8 @@
  *   ev_speech_rate     <- no counterpart; De Jong and Wempe 2009 (syllable nuclei) is the model
  *   ev_load_envelope   <- no counterpart; Morise 2015 (CheapTrick) and SPTK's freqt are the model
  *   ev_envelope        <- no counterpart; Morise 2015 (CheapTrick) and SPTK's freqt are the model
+ *   ev_load_phase_vocoder <- no counterpart; librosa.effects.time_stretch (stft -> phase_vocoder -> istft) is the model
+ *   ev_phase_vocoder   <- no counterpart; librosa.effects.time_stretch (stft -> phase_vocoder -> istft) is the model
  *   ev_load_stoi       <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_stoi            <- no counterpart; Taal et al. 2011 / Jensen and Taal 2016 are the model
  *   ev_load_stft_dist  <- no counterpart; Yamamoto et al. 2020 (multi-resolution STFT loss) is the model
@@ -98,7 +100,7 @@
 extern "C" {
 #endif
 
-#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation, ev_load_srmr, ev_srmr, ev_load_speech_rate, ev_speech_rate, ev_load_envelope, ev_envelope, ev_op_conv1d_epi (look the symbol up to detect them);
+#define EV_ABI_VERSION 4   /* 4 + additions that change nothing of 4: ev_vocoder_config, ev_load_vocoder_cfg, ev_load_mel_basis, ev_mel_spectrogram, ev_maximum_path, ev_log_prior, ev_mas_align, ev_estimator_rows, ev_cfm_loss, ev_load_resampler, ev_resample, ev_mel_stats, ev_trim_bounds, ev_trim_apply, ev_pitch_yin, ev_dtw, ev_loudness, ev_pyin_observe, ev_pyin_decode, ev_op_groupnorm_mish2, ev_op_conv_groupnorm, ev_op_attention2, ev_op_attn_out2, ev_load_stoi, ev_stoi, ev_load_stft_dist, ev_stft_dist, ev_load_voice_quality, ev_voice_quality, ev_load_formants, ev_formants, ev_perturbation, ev_load_harmonics, ev_harmonics, ev_functionals, ev_load_auditory, ev_auditory, ev_formant_track, ev_modulation, ev_load_srmr, ev_srmr, ev_load_speech_rate, ev_speech_rate, ev_load_envelope, ev_envelope, ev_load_phase_vocoder, ev_phase_vocoder, ev_op_conv1d_epi (look the symbol up to detect them);
                               4: ev_dbg_set_amax, ev_dbg_set_attn_h16, ev_dbg_set_chain, ev_dbg_sk_taken, captured decodes of many shapes; 3: ev_set_arithmetic / ev_get_arithmetic, ev_profile_read_split, test hooks; everything of earlier versions unchanged */
 
 typedef struct ev_handle ev_handle;
@@ -695,6 +697,59 @@ int ev_load_envelope(ev_handle *h, const double *twiddle /* HOST (nfft, 2) */, i
 int ev_envelope(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, const float *d_period /* (B, NF) */,
                 int B, int L, double power_floor, double *d_env /* (B, NF, NB) or NULL */, double *d_mcep /* (B, NF, n_mcep) */,
                 int32_t *d_class /* (B, NF, 3) */, void *stream);
+
+/* Time stretching on the device: the phase vocoder.  ev_load_phase_vocoder stores the tables of one nfft; ev_phase_vocoder renders every row of a
+ * batch `rate` times faster (rate > 1) or slower (rate < 1) at its own pitch.  The model is librosa.stft -> librosa.phase_vocoder -> librosa.istft
+ * (librosa 0.10 defaults: center=True with zero padding, periodic Hann, hop nfft / 4); librosa is NOT the yardstick: the definition below is what
+ * the device is held to, and tests/phase_vocoder_ref.py restates it in numpy (float64 and longdouble).  Everything is float64, the fp32 samples
+ * are widened, floating-point contraction is off; ev_set_arithmetic does not reach it.  A pitch shift is a stretch followed by ev_resample.
+ *
+ * ev_load_phase_vocoder: HOST window (nfft) float64 (the periodic Hann window for the model), HOST twiddle (nfft, 2) {cos, sin}(2 pi n / nfft).
+ * Limits, each violation failing with a message that names it: window and twiddle non-NULL and finite; nfft a multiple of 16 with
+ * 16 <= nfft <= 2048.  The load owns one device block (the windowed DFT basis (nfft, NB), the inverse basis (NBp, nfft), w / nfft and w^2; NBp the
+ * next multiple of 4 from NB: 67 MB at nfft = 2048, 17 MB at 1024) and counts once in ev_alloc_count; loading again waits for the device and
+ * drops the old block; a failed load leaves the previous tables in use.
+ *
+ * DEFINITION.  W = nfft, H = nfft / 4, NB = nfft / 2 + 1.  A row of n = len samples has nf = 1 + n / H frames (integer division); NF = 1 + L / H.
+ * d_len == NULL: every row is L long.  A row with len < 1 or len > L is empty: its outputs are zeros, its out_len and counts 0.
+ *   analysis    frame f reads t_j = x[f H - nfft / 2 + j], 0 <= j < nfft, zeros outside [0, n).  re_k = sum_j t_j w_j cos(2 pi j k / nfft),
+ *               im_k = -sum_j t_j w_j sin(2 pi j k / nfft) (matrix products on v_mfma_f64_16x16x4_f64, j ascending in steps of 4, the phase index
+ *               (j k) mod nfft in exact integers, w_j cos and w_j sin rounded once); mag = sqrt(fma(im, im, re re)), ang = atan2(im, re) with the
+ *               device library's float64 functions (atan2(0, 0) = 0).  Every frame >= nf is all zeros (two of them are read at most).
+ *   time steps  n_out = ceil((double)nf / rate); s_t = (double)t rate (ONE float64 product), i_t = floor(s_t), a_t = s_t - i_t.  The steps are part
+ *               of the definition and they are float64: a restatement in higher precision takes s_t as given (t 1.7 floors differently in long
+ *               double and then selects another frame).
+ *   propagation per bin k, in ascending t, sequentially, with omega_k = (2 pi (H k)) / nfft and 2 pi = 6.283185307179586:  phi_0 = ang[0][k];
+ *               Y_t[k] = ((1 - a_t) mag[i_t][k] + a_t mag[i_t + 1][k]) (cos phi_t, sin phi_t) — the phasor is formed before the phase moves on;
+ *               d = ang[i_t + 1][k] - ang[i_t][k] - omega_k;  d = d - 2 pi rint(d / 2 pi);  phi_{t+1} = phi_t + (omega_k + d).
+ *   synthesis   g_t[j] = (w_j / nfft) sum_k c_k (Re Y_t[k] cos(2 pi j k / nfft) - Im Y_t[k] sin(2 pi j k / nfft)), c_0 = c_{NB-1} = 1, c_k = 2
+ *               otherwise, the imaginary parts of DC and Nyquist ignored (irfft); two matrix products, k ascending in steps of 4 (the cosine
+ *               terms, the sine terms), added once.  In padded coordinates p = i + nfft / 2: num[p] = sum_t g_t[p - t H] and wss[p] = sum_t
+ *               w[p - t H]^2 over the frames 0 <= t < n_out that cover p, in ascending t.  y[i] = num / wss where wss > FLT_MIN, else num.
+ *               out_len = (int)rint((double)n / rate); y[i] = 0 for i >= min(out_len, H (n_out - 1) + nfft / 2).  Rounded once to float32.
+ * L_out must be rint(L / rate); NO = ceil(NF / rate).
+ * Outputs:
+ *   d_y        (B, L_out) float32: the stretched rows, zeros from the row's own end on
+ *   d_out_len  (B) int32: out_len
+ *   d_counts   (B, 2) int32 or NULL: {nf, n_out}
+ *   d_stretch  (B, NO, NB, 2) float64 or NULL: Y as {re, im}, zeros at t >= n_out
+ * Nothing at or behind len is read.  Nothing depends on B, L or the place in the grid: the same samples give the same bits for a row alone, inside
+ * a batch, as the d_len prefix of a longer row with anything behind it, and in a second call.  A row of one sample is a valid row.
+ * Limits of ev_phase_vocoder, each violation failing with a message that names it, the call writing nothing: tables loaded; 1 <= B <= 65535;
+ * L >= 1; rate finite with 0.125 <= rate <= 8; L_out == rint(L / rate); d_x, d_y and d_out_len non-NULL; the scratch of the call at most 4 GiB
+ * (the message names the figure; the caller splits the batch).
+ * Kernels: pv_analysis_kernel, one workgroup per (row, 16 frames): the span staged once in LDS as fp32, the DFT GEMM of ev_stft_dist for one
+ *   signal; pv_propagate_kernel, one thread per (row, bin), the loads of step t + 1 issued ahead of step t's sine and cosine; pv_synthesis_kernel,
+ *   one workgroup per (row, 16 output frames): it owns the 13 hop segments those frames cover completely, the column tiles ordered (j mod H,
+ *   quarter) so that the four terms of a sample meet inside one wave's accumulators, crossing through 8.5 KB of LDS; edge tiles add the frames that
+ *   exist.  One fixed order, no atomics.
+ * Scratch: mag and ang (2 x B x NF x NB doubles) and, without d_stretch, Y (B x NO x NB pairs: 0.7 GB together at 64 rows of 6 s, rate 0.8) live
+ *   in an arena of the handle that grows on demand and counts in ev_alloc_count: a second call at the same shape allocates nothing; ev_reserve
+ *   does not cover it.  Three kernel launches on `stream`, no host wait, no copy: the call is capturable once the arena has its size. */
+int ev_load_phase_vocoder(ev_handle *h, const double *window /* HOST (nfft) */, const double *twiddle /* HOST (nfft, 2) */, int nfft);
+int ev_phase_vocoder(ev_handle *h, const float *d_x /* (B, L) */, const int32_t *d_len /* (B) or NULL */, int B, int L, double rate,
+                     float *d_y /* (B, L_out) */, int L_out, int32_t *d_out_len /* (B) */, int32_t *d_counts /* (B, 2): nf, n_out; or NULL */,
+                     double *d_stretch /* (B, NO, NB, 2): Y, zeros at t >= n_out; or NULL */, void *stream);
 
 /* STOI and ESTOI on the device: short-time objective intelligibility of a processed row y against the clean, sample-aligned row x (Taal,
  * Hendriks, Heusdens and Jensen, IEEE TASL 19(7), 2011) and its extended form (Jensen and Taal, IEEE/ACM TASLP 24(11), 2016), for rows already
